@@ -13,7 +13,9 @@ largest), reference launch-file parameters.  Input images are resident in HBM be
 region.  N GPUs = N independent stereo streams, one rank per GPU (weak scaling); the only
 collective is the all-gather of the 7-double poses over RCCL (batches of 64 frames, off the critical path).
 
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times exactly --steps steps in one block and prints the line
+(--dump-outputs DIR: and writes what the last timed step computed); --full adds the repeated blocks, the per-kernel and roofline
+figures, the informational legs and the CPU baseline.
 """
 import argparse
 import json
@@ -252,6 +254,25 @@ def gpu_sequence(host, models_dir, prefix, seq, P_l, P_r):
     return np.array(rows, np.float64)
 
 
+def dump_outputs(directory, fe, host, pose):
+    """--dump-outputs: what the last timed step handed to its caller -- its pose and the solver's outcome -- and what the front end holds for
+    that frame: the keypoints of both images, the stereo and the temporal matches (query, train, distance) and the PnP inliers, as
+    float32 / float64 .npy files.  The inputs are seeded, so two builds can be compared file by file.  (The descriptors of the device path
+    stay in the context's slots: the host deque holds n x 0 headers.)"""
+    os.makedirs(directory, exist_ok=True)
+    q, t = pose if pose is not None else ((0, 0, 0, 1), (0, 0, 0))
+    flags = fe.last_solve()
+    arrays = {"pose": np.concatenate([np.asarray(q, np.float64), np.asarray(t, np.float64)]),   # q (x, y, z, w), t of cam0_curr_T_cam0_prev
+              "solver_outcome": np.array([pose is not None, flags["pnp_ok"], flags["accepted"], flags["refined"], flags["lm_iterations"]], np.float64),
+              "keypoints_left": fe.keypoints(host.CURR_LEFT), "keypoints_right": fe.keypoints(host.CURR_RIGHT),
+              "pnp_inliers": fe.inliers("pnp").astype(np.float64)}
+    for name, kind in (("stereo_matches", host.CURR_LEFT_CURR_RIGHT), ("temporal_matches", host.CURR_LEFT_PREV_LEFT)):
+        qi, ti, d = fe.matches(kind)
+        arrays[name] = np.stack([qi.astype(np.float64), ti.astype(np.float64), d.astype(np.float64)], axis=1)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def outcome_stats(a):
     return {"pnp_ok_rate": round(float(a[:, 0].mean()), 3), "accepted_rate": round(float(a[:, 1].mean()), 3), "refined_rate": round(float(a[:, 2].mean()), 3),
             "mean_lm_iterations": round(float(a[:, 3].mean()), 2), "mean_pnp_inliers": round(float(a[:, 4].mean()), 1),
@@ -392,11 +413,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=0, help="timed blocks of --steps steps (default 0: as many as make about one second, 5..200); the line reports the median block")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the informational second measurement (FP32 engine in split mode)")
-    ap.add_argument("--legs", default="split,host,trained,classic,configs", help="informational legs to run after the headline (comma list of split, host, trained, classic, configs)")
-    ap.add_argument("--no-profile", action="store_true", help="do not record per-kernel HIP events in the timed region")
+    ap.add_argument("--repeats", type=int, default=0, help="timed blocks of --steps steps (default 0: one block; with --full as many as make about one second, 5..200); "
+                                                            "the line reports the median block")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: repeated timed blocks, per-kernel events in the timed region, the "
+                                                         "stage / roofline pass, the informational legs and the CPU baseline with the trajectory check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed (pose, solver outcome, "
+                                                                         "keypoints, matches, PnP inliers) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baseline and the trajectory check")
+    ap.add_argument("--no-extras", action="store_true", help="(with --full) skip the informational legs (split mode, host images, trained graph, classic front end, other configs)")
+    ap.add_argument("--legs", default="split,host,trained,classic,configs", help="(with --full) informational legs to run after the headline (comma list of split, host, trained, classic, configs)")
+    ap.add_argument("--no-profile", action="store_true", help="(with --full) do not record per-kernel HIP events in the timed region")
     ap.add_argument("--no-pipeline", action="store_true", help="do not hand the next stereo pairs over early")
     ap.add_argument("--sync-solve", action="store_true", help="solve inside the step (solveStereoOdometry in one piece) instead of handing every frame's solve over and "
                                                               "collecting its pose during the next step (solveStereoOdometrySubmit / Collect: the default whenever pairs are handed over "
@@ -414,7 +440,7 @@ def main():
                          "spvo_set_fp32_split) -- opt-in, not the headline")
     ap.add_argument("--config", type=int, default=0, choices=[0, 2, 3, 5],
                     help="BASELINE.json config shortcut: 2 = default; 3 = FP16 192x640; 5 = sp_mbv1 INT8, 2048 keypoints, fp8 shortlist")
-    ap.add_argument("--dump-ops", action="store_true", help="add per-layer network times to the JSON line")
+    ap.add_argument("--dump-ops", action="store_true", help="(with --full) add per-layer network times to the JSON line")
     ap.add_argument("--py-loop", action="store_true", help="drive the timed steps from Python, one front-end call at a time, instead of handing blocks of stereoCallbacks to the host "
                                                              "library's C loop (spvo_host_run_device_block): what the interpreter costs per step, for A/B")
     ap.add_argument("--cpus", type=int, default=0, help="restrict this process to that many CPUs (os.sched_setaffinity, BEFORE anything touches the GPU): what one rank of an "
@@ -426,6 +452,8 @@ def main():
     elif args.config == 5:
         args.precision, args.graph, args.max_keypoints, args.match_fp8 = "INT8", "sp_mbv1", 2048, True
     headline = args.precision == "FP32" and args.graph == "vgg" and args.max_keypoints == 1000 and not args.match_fp8 and not args.fp32_split
+    profile = args.full and not args.no_profile     # per-kernel events in the timed region + the stage pass behind it
+    extras = args.full and headline and not args.no_extras
     global NET_H, NET_W
     NET_H, NET_W = (int(v) for v in args.net_size.lower().split("x"))
 
@@ -551,12 +579,15 @@ def main():
     def run_frames(first, n, order=order, depth=None, records=None):
         """n stereoCallbacks starting at frame index `first`: through the host library's C loop in sub-blocks of at most 64 frames (the
         poses of a sub-block go to the pose gather as they did per step), or -- with --py-loop -- one Python call per front-end call.
-        Appends the frames' records (pose, first-call -> pose latency, solver outcome) to `records` when given."""
+        Appends the frames' records (pose, first-call -> pose latency, solver outcome) to `records` when given.  Returns the last pose
+        the caller received, (q, t), or None."""
         depth = (0 if args.no_pipeline else args.depth) if depth is None else depth
+        got = None
         if args.py_loop:
             for i in range(first, first + n):
-                step(i, order)
-            return
+                res = step(i, order)
+                got = res if res is not None else got
+            return got
         key = tuple(order)
         if key not in ptr_cache:
             cyc = cycle_buffers(order)
@@ -571,7 +602,9 @@ def main():
                     pg.gather_async(*((r["q"], r["t"]) if r["has_pose"] else (None, None)))
             if records is not None:
                 records.append(rec)
+            got = (rec["q"][-1], rec["t"][-1]) if rec["has_pose"][-1] else got
             done += m
+        return got
 
     def barrier():
         if dist_on:
@@ -593,14 +626,15 @@ def main():
     # Inside the timed region only the dominant kernel (conv1b = stage "conv:1") is bracketed by HIP events on the
     # context's stream: two event records per step.  Timing every stage costs 2 records per kernel and 7 % of the
     # throughput, so the stage breakdown comes from a separate, untimed pass below.
-    if not args.no_profile:
+    if profile:
         ctx.profile_only("conv:1" if args.graph == "vgg" else "detect")
         ctx.profile_enable(True)
         ctx.profile_reset()
-    # A timed block = EXACTLY args.steps steps between two barriers (+ device synchronisation).  The block is repeated -- a block
-    # of the driver's 20 steps lasts 18 ms, one such sample is thin -- and `value` is the MEDIAN block (max over ranks per block);
-    # the number of repeats follows from the first block's duration and is the same on every rank.
+    # A timed block = EXACTLY args.steps steps between two barriers (+ device synchronisation).  A plain run times one block (or
+    # --repeats); with --full the block is repeated -- a block of 20 steps lasts 18 ms, one such sample is thin -- and `value` is the
+    # MEDIAN block (max over ranks per block); the number of repeats follows from the first block's duration and is the same on every rank.
     cursor = [args.warmup]
+    last_pose = [None]      # the pose the last timed step handed to its caller (--dump-outputs)
     timed_records = []
     local_times = []        # THIS rank's block times (the line's `value` uses the max over ranks per block; `per_rank_fps` shows the ranks apart)
     pg.reset_timing()
@@ -608,8 +642,9 @@ def main():
     def timed_block():
         barrier()
         t0 = time.perf_counter()
-        run_frames(cursor[0], args.steps, records=timed_records)
+        got = run_frames(cursor[0], args.steps, records=timed_records)
         last = fe.finish_solve()                                            # the last step's pose (deferred solve): inside the timed region (the C loop collects it itself)
+        last_pose[0] = last if last is not None else got
         if dist_on and last is not None:
             pg.gather_async(*last)
         if dist_on:
@@ -629,8 +664,10 @@ def main():
         return [float(v) for v in t.tolist()]
 
     block_times = over_ranks([timed_block()])
-    n_rep = args.repeats if args.repeats > 0 else repeats_for(block_times[0])
+    n_rep = args.repeats if args.repeats > 0 else (repeats_for(block_times[0]) if args.full else 1)
     block_times += over_ranks([timed_block() for _ in range(n_rep - 1)])
+    if args.dump_outputs and rank == 0:   # before anything else runs on this front end
+        dump_outputs(args.dump_outputs, fe, host, last_pose[0])
     elapsed, headline_spread = spread(block_times, args.steps)
     gather_timing = pg.timing()
     rank_fps = [args.steps / float(np.median(local_times))]
@@ -642,7 +679,7 @@ def main():
         dist.all_gather(allr, t)
         rank_fps, rank_gather_ms, rank_init_ms = ([float(a[i]) for a in allr] for i in range(3))
     prof, prof_all = {}, {}
-    if not args.no_profile:
+    if profile:
         prof = ctx.profile()
         ctx.profile_only(None)
         ctx.profile_reset()
@@ -805,7 +842,8 @@ def main():
         # NMS: round launches are enqueued with the submission; a heat map whose decisions are still open after them is continued by
         # the HOST (spvo_detect_wait), synchronously behind everything queued on the tail stream -- in the pipelined loop that is a
         # stall of more than a trunk.  Counted over the timed blocks: 0 is what the default of four launches is chosen for.
-        out["nms_host_continuations"] = {"timed_region": int(prof.get("nms_redo", {}).get("calls", 0)), "timed_steps": args.steps * len(block_times)}
+        if profile:
+            out["nms_host_continuations"] = {"timed_region": int(prof.get("nms_redo", {}).get("calls", 0)), "timed_steps": args.steps * len(block_times)}
         any_stage = next((v for k, v in prof_all.items() if k.startswith("conv:") and v["calls"]), None)
         if any_stage:   # stage breakdown: the separate pass with every stage timed (it runs ~7 % slower than the timed region)
             calls = any_stage["calls"]
@@ -847,7 +885,7 @@ def main():
                     out["roofline"]["conv_stack_hbm_gbps"] = round(cs["traffic_MB"] * 1e6 * pairs_per_launch / (conv_ms * 1e-3) / 1e9, 1)
                     out["roofline"]["conv_stack_frac_of_hbm_peak"] = round(cs["traffic_MB"] * 1e6 * pairs_per_launch / (conv_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
                     out["roofline"]["conv_stack_traffic_source"] = "profiles/r06_pmc_layers.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE over a forward-only loop, per layer; counters include Infinity-Cache hits; same csrc_sha16) / conv_stack_sum of this run"
-        if world == 1 and headline and not args.no_extras and "split" in legs:
+        if world == 1 and extras and "split" in legs:
             try:
                 # Informational, never `value`: the same workload with the FP32 engine in its opt-in split mode (every fp32 operand as
                 # three bf16 pieces, six partial products on the bf16 matrix pipe, fp32 accumulation: results agree with the
@@ -869,7 +907,7 @@ def main():
                                                       "6 partial products per product, fp32 accumulate; fp32-equivalent results"}
             except Exception as exc:   # the headline line must survive a failure of this informational part
                 out["fp32_split_mode"] = {"error": repr(exc)}
-        if world == 1 and headline and not args.no_extras and "host" in legs:
+        if world == 1 and extras and "host" in legs:
             try:
                 # The reference's own entry point, addStereoImagePair(cv::Mat&, ...) (node.cpp:175): images in HOST memory (as
                 # cv_bridge hands them over), resized images and descriptors copied back into images_dq / descriptors_dq -- PCIe
@@ -958,7 +996,7 @@ def main():
                                                  "images_dq / descriptors_dq inside addStereoImagePair as the reference does (synchronous_default_copies)"}
             except Exception as exc:   # the headline line must survive a failure of this informational part
                 out["host_interface"] = {"error": repr(exc)}
-        if world == 1 and headline and not args.no_extras and "trained" in legs:
+        if world == 1 and extras and "trained" in legs:
             try:
                 # Second workload, never `value`: the reference's TRAINED sp_squeeze graph (tests/golden/sp_squeeze.spvw = its ONNX file
                 # re-packed), FP32, same stream and size.  With trained weights the geometry is real: the gate accepts, the LM refinement
@@ -984,7 +1022,7 @@ def main():
                                                "value": round(args.steps / e4, 2), "unit": "stereo frames/s", "ms_per_step": round(1e3 * e4 / args.steps, 4), **sp4, **fs4}
             except Exception as exc:   # the headline line must survive a failure of this informational part
                 out["trained_workload"] = {"error": repr(exc)}
-        if world == 1 and headline and not args.no_extras and "classic" in legs:
+        if world == 1 and extras and "classic" in legs:
             try:
                 # BASELINE config 1's front end on the GPU, never `value`: ClassicFeatureFrontEnd(ORB, ORB, BF, KNN) as node.cpp:353-360
                 # constructs it -- ORB (spvo_orb_detect) and Hamming matching (spvo_match_hamming) as HIP kernels, the same solver --
@@ -1001,7 +1039,7 @@ def main():
                                                         "seeded test pairs and fixed rounding choices, so descriptors are not comparable with OpenCV's cv::ORB"}
             except Exception as exc:   # the headline line must survive a failure of this informational part
                 out["classic_front_end_gpu"] = {"error": repr(exc)}
-        if world == 1 and headline and not args.no_extras and "configs" in legs:
+        if world == 1 and extras and "configs" in legs:
             # The other GPU configurations of BASELINE.json and the second network size of SURVEY.md section 8d, never `value`: each is
             # the SAME loop (two pairs handed over ahead, deferred solve) on an engine of its own, timed like the other legs (blocks of
             # >= 100 steps, the median block), followed by a short pass with every stage bracketed by events that names the dominant
@@ -1112,7 +1150,7 @@ def main():
                 finally:
                     if "SPVO_TUNE_SOLVE_KEEP" not in os.environ:
                         capi.set_tuning("solve_keep", 2 if keep2_main else 1)   # (the leg's setting does not outlive it)
-        if not args.no_cpu_baseline and world == 1 and headline:
+        if args.full and not args.no_cpu_baseline and world == 1 and headline:
             try:
                 # BASELINE.json's metric is "stereo frames/sec ...; ATE vs ref": the trajectory half, from an UNTIMED pass.  ATE_FRAMES synthetic frames
                 # with exact ground truth through the reference's TRAINED sp_squeeze graph (the seeded VGG weights of the headline track nothing), FP32,

@@ -55,9 +55,38 @@ def test_headline_workload_needs_no_host_driven_nms_continuation():
     finishing kernel).  A continuation by the host (spvo_detect_wait -> nms_settle) waits behind everything queued on the tail
     stream; with three round launches alone it ran on 7 % of the frames and cost the headline 6 %."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "60", "--warmup", "10", "--repeats", "2", "--no-cpu-baseline", "--no-extras"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "60", "--warmup", "10", "--repeats", "2", "--full", "--no-cpu-baseline", "--no-extras"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["nms_host_continuations"] == {"timed_region": 0, "timed_steps": 120}
     assert out["roofline"]["frac"] > 0.3 and out["value"] > 0
+
+
+def test_plain_run_times_the_steps_once_and_dumps_the_same_outputs_every_time(tmp_path):
+    """A plain `bench.py --steps N --warmup W` times exactly N steps in one block, leaves out what only --full measures, and with
+    --dump-outputs writes what the last timed step computed as float .npy files: identical from run to run (seeded inputs)."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"out{run}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "5", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 30 and out["repeats"] == 1 and out["value"] > 0 and out["dtype"] == "f32" and out["higher_is_better"] is True
+        assert abs(out["value"] - 1e3 / out["ms_per_step"]) < 0.01 * out["value"]
+        for moved in ("roofline", "stages_ms", "nms_host_continuations", "cpu_baseline", "host_interface", "other_configs", "ate"):
+            assert moved not in out, moved
+        files = sorted(p.name for p in d.iterdir())
+        assert files == sorted(f"{n}.npy" for n in ("pose", "solver_outcome", "keypoints_left", "keypoints_right", "pnp_inliers", "stereo_matches", "temporal_matches"))
+        arrays = {f: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["solver_outcome.npy"][0] == 1 and arrays["keypoints_left.npy"].shape[1] == 2 and len(arrays["stereo_matches.npy"]) > 0
+        dumps.append(arrays)
+    for f, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][f]), f

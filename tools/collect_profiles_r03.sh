@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/prof_r03
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $ROOT/bench.py --steps 20 --warmup 5 > $OUT/bench.log 2> $OUT/bench.err
+python3 $ROOT/bench.py --full --steps 20 --warmup 5 > $OUT/bench.log 2> $OUT/bench.err
 python3 $ROOT/tools/layer_roofline_json.py $OUT/layer_roofline.json > /dev/null 2> $OUT/layer_roofline.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o st -- python3 $ROOT/bench.py --no-cpu-baseline --no-extras > $OUT/bench_under_rocprof.log 2>&1
 export WINO_DYNAMIC=1   # tools/wino_bench4: tiles through the XCD-banded counters, as the library launches the layer

@@ -7,8 +7,8 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/prof_r05
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.log 2> $OUT/bench.err      # the driver's command
-python3 $ROOT/bench.py --steps 200 --warmup 20 --no-cpu-baseline > $OUT/bench_200step.log 2> $OUT/bench_200step.err
+python3 $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.log 2> $OUT/bench.err      # the whole record: headline, legs, CPU baseline
+python3 $ROOT/bench.py --full --steps 200 --warmup 20 --no-cpu-baseline > $OUT/bench_200step.log 2> $OUT/bench_200step.err
 python3 $ROOT/bench.py --no-cpu-baseline --no-extras --cpus 2 > $OUT/bench_2cpu.log 2> $OUT/bench_2cpu.err   # one rank's share of an 8-rank node's CPUs
 # per-layer timing (HIP events, nothing else on the chip)
 python3 $ROOT/tools/layer_roofline_json.py $OUT/layer_roofline.json 360x1176 FP32 > /dev/null 2> $OUT/lr.err

@@ -4,7 +4,7 @@ O=gpurun_out/r5j; mkdir -p $O
 python -m pytest tests/test_gpu_host.py tests/test_gpu_pipeline.py tests/test_gpu_post.py -x -q -m gpu > $O/pytest.log 2>&1; tail -3 $O/pytest.log
 for rep in 1 2 3; do
   for v in 1 0; do
-    SPVO_TUNE_PREPROCESS_FUSED=$v python bench.py --no-cpu-baseline --legs host > $O/head_pre${v}_$rep.json 2> $O/head_pre${v}_$rep.err
+    SPVO_TUNE_PREPROCESS_FUSED=$v python bench.py --full --no-cpu-baseline --legs host > $O/head_pre${v}_$rep.json 2> $O/head_pre${v}_$rep.err
   done
 done
 python - <<'PY'

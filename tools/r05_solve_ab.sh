@@ -9,9 +9,9 @@ V=$PWD/superpoint-stereo-visual-odometry_amd/variants/base
 for rep in 1 2; do
   for lib in new old; do
     if [ $lib = old ]; then export SPVO_LIB_DIR=$V; else unset SPVO_LIB_DIR; fi
-    python bench.py --config 3 --no-cpu-baseline --no-extras > $O/cfg3_${lib}_$rep.json 2> /dev/null
-    python bench.py --config 5 --no-cpu-baseline --no-extras > $O/cfg5_${lib}_$rep.json 2> /dev/null
-    python bench.py --no-cpu-baseline --legs host > $O/head_${lib}_$rep.json 2> /dev/null
+    python bench.py --full --config 3 --no-cpu-baseline --no-extras > $O/cfg3_${lib}_$rep.json 2> /dev/null
+    python bench.py --full --config 5 --no-cpu-baseline --no-extras > $O/cfg5_${lib}_$rep.json 2> /dev/null
+    python bench.py --full --no-cpu-baseline --legs host > $O/head_${lib}_$rep.json 2> /dev/null
   done
 done
 unset SPVO_LIB_DIR
