@@ -41,18 +41,22 @@ struct DwPwArgs8 {
   const float *w0 = nullptr, *b0 = nullptr;       // [9], [1]
   const float *w1 = nullptr, *b1 = nullptr, *bn1_scale = nullptr, *bn1_shift = nullptr;   // [64] each
   float inv_s_stem = 0.f;
+  int pad0 = 0;                      // (pad0 .. pad3: no implicit padding, launch segments compare argument bytes (launch_segments.hip.h))
   // depthwise layer
   const int *dw_wsel = nullptr;      // [G][9][16]: quantised weight of (channel, tap) shifted into byte (channel & 3): the dot4 operand
   const float *dw_qm = nullptr, *dw_bias = nullptr;   // [C]
   float inv_s_dw = 0.f;
+  int pad1 = 0;
   // pointwise layer
   const int8_t *pw_w = nullptr;      // [co_tiles][G][co 64][16]  (pack_conv_weights_i8 with ks = 1, ckg = G)
   const float *pw_qm = nullptr, *pw_bias = nullptr, *bn_scale = nullptr, *bn_shift = nullptr;   // [co_tiles * 64]
   float inv_s_out = 0.f;
+  int pad2 = 0;
   int8_t *out = nullptr;             // C16 output (pooled: level + 1), image 0
   size_t out_per_image = 0;          // bytes
   int out_hp = 0, out_wp = 0, cout = 0, co_tiles = 0;
   int tiles_x = 0, tiles_y = 0, batch = 0;
+  int pad3 = 0;
   // tensors a fused block skips, stored only when a pointer is given (synchronous entry points)
   float *dbg_stem_plane = nullptr;   // STEM: output of op 0 (fp32 padded plane), image 0
   size_t dbg_stem_plane_per_image = 0;
@@ -60,6 +64,7 @@ struct DwPwArgs8 {
   int8_t *dbg_dw_out = nullptr;      // output of the depthwise layer (C16), image 0
   size_t dbg_c16_per_image = 0;      // bytes per image of those two
 };
+static_assert(sizeof(DwPwArgs8) == 264, "DwPwArgs8: padding");
 
 template <int G, bool STEM>
 struct DwPwTile {

@@ -59,7 +59,9 @@ struct HeadsArgs {
   size_t raw_per_image;
   float *desc;                          // [img][H][W][256] normalised, dense
   int H, W, batch;
+  int pad = 0;                          // no implicit padding: launch segments compare argument bytes (launch_segments.hip.h)
 };
+static_assert(sizeof(HeadsArgs) == 104, "HeadsArgs: padding");
 
 constexpr int HEADS_CIN = 256;
 constexpr int HEADS_DET_UNITS = 5, HEADS_UNITS = 21;   // units of 16 output channels: detector 0..4 (65 of 80 used), descriptor 5..20

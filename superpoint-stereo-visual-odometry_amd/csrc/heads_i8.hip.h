@@ -35,7 +35,9 @@ struct HeadsArgs8 {
   size_t raw_per_image;
   float *desc;                              // [img][H][W][256] normalised, dense
   int H, W, batch;
+  int pad = 0;                              // no implicit padding: launch segments compare argument bytes (launch_segments.hip.h)
 };
+static_assert(sizeof(HeadsArgs8) == 120, "HeadsArgs8: padding");
 
 constexpr int HEADS8_CIN = 256, HEADS8_DET_UNITS = 5, HEADS8_UNITS = 21, HEADS8_THREADS = 256;
 

@@ -9,51 +9,68 @@
 // 2.6-4 us each against ~0.1 ms of network (NOTES.md round 6; tools/graph_bench.hip: ONE hipGraphLaunch costs the host 4.7 us whatever the
 // number of kernel nodes).  So a run of kernel launches on one stream between two event operations -- a SEGMENT: a group's trunk, its heads,
 // a pair's heat map + NMS + sampling, its two matches -- is recorded instead of launched (the launch macro below lands here), and when the
-// segment closes it is either replayed from the HIP graph built the last time the same segment (same key: buffer set, slots, batch, plan
-// and tuning generation ...) came by, or launched kernel by kernel and turned into a graph for the next time.  The enqueueing code is
-// unchanged: every hipLaunchKernelGGL of the library goes through launch_kernel(), which launches at once unless a segment is open on
-// that stream.  Anything that is not a kernel launch (event record / wait, copies, memsets -- also the profiler's events) inside an
-// open segment flushes it and falls back to plain launches for the rest of that segment (rec_poison), so ordering is never at risk.
-#include <initializer_list>
+// segment closes it is either replayed from the HIP graph its entry holds -- when the recorded launches are identical to the ones that graph
+// was built from: kernels, launch dimensions, LDS sizes and argument bytes -- or launched kernel by kernel and, when it recorded the same
+// launches as the last time, turned into a graph for the next time.  The enqueueing code is unchanged: every hipLaunchKernelGGL of the
+// library goes through launch_kernel(), which launches at once unless a segment is open on that stream.  Anything that is not a kernel
+// launch (event record / wait, copies, memsets -- also the profiler's events) inside an open segment flushes it and falls back to plain
+// launches for the rest of that segment (rec_poison), so ordering is never at risk.
 #include <tuple>
 #include <utility>
 namespace spvo_int {
 struct LaunchNode { const void *func; dim3 grid, block; unsigned lds; int n_args; unsigned arg_off[32]; };
+// a segment's launches as recorded: the nodes and the argument copies they point into (arg_off).  Every byte of `args` is written -- the
+// gaps in front of the 16-byte aligned arguments are zero, and the argument structs have no implicit padding -- so two recordings of the
+// same launches are equal byte for byte.
+struct Recording {
+  std::vector<LaunchNode> nodes;
+  std::vector<char> args;
+  void clear() { nodes.clear(); args.clear(); }
+  void params(const LaunchNode &n, void **p) const {
+    for (int i = 0; i < n.n_args; ++i) p[i] = const_cast<char *>(args.data()) + n.arg_off[i];
+  }
+  hipError_t launch(const LaunchNode &n, hipStream_t stream) const {
+    void *p[32];
+    params(n, p);
+    return hipLaunchKernel(n.func, n.grid, n.block, p, n.lds, stream);
+  }
+};
+inline bool operator==(const LaunchNode &a, const LaunchNode &b) {
+  auto same = [](dim3 x, dim3 y) { return x.x == y.x && x.y == y.y && x.z == y.z; };
+  return a.func == b.func && same(a.grid, b.grid) && same(a.block, b.block) && a.lds == b.lds && a.n_args == b.n_args &&
+         std::memcmp(a.arg_off, b.arg_off, a.n_args * sizeof(unsigned)) == 0;
+}
+inline bool operator==(const Recording &a, const Recording &b) { return a.nodes == b.nodes && a.args == b.args; }
 struct GraphEntry {
-  bool valid = false, never = false;
-  unsigned long long key = 0, seen_key = 0;
+  bool never = false;          // instantiation failed once: this segment stays plain launches
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
-  std::vector<const void *> funcs;           // the replayed segment must be the same kernels with the same launch dimensions
-  std::vector<unsigned long long> dims;
+  Recording rec;               // the launches `exec` was built from; without one, the launches that went out plainly the last time
 };
 struct LaunchRecorder {
   bool active = false, poisoned = false;
   hipStream_t stream = nullptr;
   GraphEntry *entry = nullptr;
-  unsigned long long key = 0;
-  std::vector<LaunchNode> nodes;
-  std::vector<char> arena;                   // argument copies of the open segment
-  size_t used = 0;
-  long graph_launches = 0, direct_segments = 0, poisoned_segments = 0;
+  Recording rec;               // the open segment
 };
 extern __thread LaunchRecorder *t_rec;   // (__thread, not thread_local: no dynamic-initialisation wrapper between the translation units of the library)
-void rec_flush_direct(LaunchRecorder *r);    // launches the recorded nodes one by one, in order, and forgets them
+// the open segment's recorded launches go out one by one, in order, and what comes behind them as plain launches (not held against the
+// entry: the profiler's events come and go)
 inline void rec_poison() {
   LaunchRecorder *r = t_rec;
   if (!r || !r->active) return;
-  rec_flush_direct(r);
+  for (const LaunchNode &n : r->rec.nodes) (void)r->rec.launch(n, r->stream);
+  r->rec.clear();
   r->poisoned = true;
   r->active = false;
-  ++r->poisoned_segments;   // (not held against the entry: the profiler's events come and go)
 }
-template <typename T> inline void rec_put_arg(LaunchRecorder *r, LaunchNode &n, const T &v, bool &ok) {
+template <typename T> inline void rec_put_arg(Recording &r, LaunchNode &n, const T &v, bool &ok) {
   static_assert(std::is_trivially_copyable<T>::value, "kernel arguments are plain data");
-  const size_t at = (r->used + 15) & ~(size_t)15;
-  if (n.n_args >= 32 || at + sizeof(T) > r->arena.size()) { ok = false; return; }
-  std::memcpy(r->arena.data() + at, &v, sizeof(T));
+  if (n.n_args >= 32) { ok = false; return; }
+  const size_t at = (r.args.size() + 15) & ~(size_t)15;
+  r.args.resize(at + sizeof(T));   // (zero-fills the gap in front of the argument)
+  std::memcpy(r.args.data() + at, &v, sizeof(T));
   n.arg_off[n.n_args++] = (unsigned)at;
-  r->used = at + sizeof(T);
 }
 template <typename... KArgs, typename... Args>
 inline void launch_kernel(void (*k)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args &&...a) {
@@ -64,10 +81,10 @@ inline void launch_kernel(void (*k)(KArgs...), dim3 grid, dim3 block, size_t lds
     if (stream == r->stream) {
       LaunchNode n{(const void *)k, grid, block, (unsigned)lds, 0, {}};
       bool ok = true;
-      std::apply([&](const auto &...v) { (rec_put_arg(r, n, v, ok), ...); }, vals);
-      if (ok) { r->nodes.push_back(n); return; }
+      std::apply([&](const auto &...v) { (rec_put_arg(r->rec, n, v, ok), ...); }, vals);
+      if (ok) { r->rec.nodes.push_back(n); return; }
     }
-    rec_poison();   // another stream inside the segment, or the arena is full: plain launches from here on
+    rec_poison();   // another stream inside the segment, or more than 32 arguments: plain launches from here on
   }
   void *params[sizeof...(KArgs) + 1];
   int i = 0;

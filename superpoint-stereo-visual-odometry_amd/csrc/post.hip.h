@@ -568,6 +568,7 @@ struct SampleJob {
   const int *xy;            // keypoints [n][2] int
   const int *n_ptr;         // device count (or NULL -> n_fixed)
   int n_fixed;
+  int pad;                  // 0: no implicit padding, launch segments compare argument bytes (launch_segments.hip.h)
   float *out;               // [n][256]
   float *out_sqn;           // [n] squared norm of the stored descriptor (for K12a) or NULL
   float *out_xy_f32;        // [n][2] or NULL
@@ -575,6 +576,7 @@ struct SampleJob {
   int *out_n;               // device copy of n or NULL
   float *out_host;          // [n][256] second copy of the descriptors, written straight into pinned HOST memory, or NULL
 };
+static_assert(sizeof(SampleJob) == 80, "SampleJob: padding");
 struct SampleJobs { SampleJob j[2]; };   // blockIdx.y selects the image
 
 __global__ __launch_bounds__(256) void sample_desc_kernel(SampleJobs jobs, int H, int W, int Hc, int Wc) {

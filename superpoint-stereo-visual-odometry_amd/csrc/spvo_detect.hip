@@ -336,7 +336,7 @@ int spvo_sample_descriptors(spvo_ctx *c, const float *desc_nhwc, const int32_t *
   HIP_TRY(c, hipMemcpyAsync(ts.d, desc_nhwc, ts.per_image * sizeof(float), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipMemcpyAsync(c->d_xy_tmp, xy, (size_t)n * 2 * sizeof(int), hipMemcpyHostToDevice, c->stream));
   SampleJobs sj;
-  sj.j[0] = SampleJob{ts.d, c->d_xy_tmp, nullptr, n, c->d_desc_tmp, nullptr, nullptr, nullptr, nullptr, nullptr};
+  sj.j[0] = SampleJob{ts.d, c->d_xy_tmp, nullptr, n, 0, c->d_desc_tmp, nullptr, nullptr, nullptr, nullptr, nullptr};
   sj.j[1] = sj.j[0];
   hipLaunchKernelGGL(sample_desc_kernel, dim3((n + 3) / 4, 1), dim3(256), 0, c->stream, sj, c->H, c->W, c->Hc, c->Wc);
   HIP_TRY(c, hipGetLastError());
@@ -357,7 +357,7 @@ static int enqueue_sample(spvo_ctx *c, const int slots[2], const NmsPair &np, in
   for (int i = 0; i < 2; ++i) {
     FeatureSlot &s = c->slots[slots[i]];
     // the keypoint count is read from the NMS counters on the device: no host round trip
-    sj.j[i] = SampleJob{desc + (size_t)i * ts.per_image, np.b[i].out_xy, (const int *)(np.b[i].counters + 2), 0, s.d_desc, s.d_sqn,
+    sj.j[i] = SampleJob{desc + (size_t)i * ts.per_image, np.b[i].out_xy, (const int *)(np.b[i].counters + 2), 0, 0, s.d_desc, s.d_sqn,
                         stage + (size_t)i * cap * 2, s.d_xy, s.d_n, nullptr};
   }
   hipLaunchKernelGGL(sample_desc_kernel, dim3((cap + 3) / 4, 2), dim3(256), 0, c->post, sj, c->H, c->W, c->Hc, c->Wc);
@@ -637,14 +637,11 @@ static int launch_group_body(spvo_ctx *c) {
   const bool heads_on_net = hon < 0 ? c->heads_on_net : hon != 0;
   bool any_res0 = false;
   for (int m = 0; m < n; ++m) any_res0 = any_res0 || mem[m]->early_res;
-  const long long gen = ((long long)c->plan_gen << 40) ^ ((long long)c->alloc_gen << 20) ^ (long long)tuning_generation();   // engine, buffers, switches
   {
     ScopedStage net(c, stage_id(c, "net"));
     // launch segment T: the group's trunk (and its heads where they stay on the network stream) -- not for a group whose first layer also
     // preprocesses (its arguments are the caller's image pointers) or whose resized images leave through the tail stream in between
-    const bool seg_t = !mem[0]->pre_pending && !any_res0 &&
-                       seg_begin(c, &c->seg_T[tring][n - 1], seg_key({1, tring, batch, gen, heads_on_net ? 1 : 0, (long long)c->head_start}), c->stream);
-    (void)seg_t;
+    if (!mem[0]->pre_pending && !any_res0) seg_begin(c, &c->seg_T[tring][n - 1], c->stream);
     rc = mem[0]->pre_pending ? launch_first_pre(c, mem, n, c->stream) : run_ops(c, batch, 0, std::min<size_t>(1, c->head_start), c->stream);
     for (int m = 0; m < n; ++m) mem[m]->pre_pending = false;
     // The resized images leave for their sets' pinned mirrors UNDER the network: a copy kernel (16 bytes per lane, no SDMA engine involved)
@@ -697,7 +694,7 @@ static int launch_group_body(spvo_ctx *c) {
   if (trunk_timing) (void)hipEventRecord(tt_tb[tt_n % TT], ts0);
   c->post = ts0;
   if (!heads_on_net) {
-    seg_begin(c, &c->seg_H[tring][n - 1], seg_key({2, tring, batch, gen, (long long)c->head_start}), ts0);   // launch segment H: the heads
+    seg_begin(c, &c->seg_H[tring][n - 1], ts0);   // launch segment H: the heads
     rc = run_ops(c, batch, c->head_start, c->ops.size(), ts0);   // heads: on the (first pair's) tail stream, reading this group's ring buffers
     { const int rce = seg_end(c); if (!rc) rc = rce; }
     if (!rc && n == 2 && mem[1]->ts != mem[0]->ts) {
@@ -717,7 +714,7 @@ static int launch_group_body(spvo_ctx *c) {
     c->post = tsm;
     c->ms_set = pd.ts;
     // launch segment A: heat map, NMS rounds + finish, rank, write, sampling -- eight dependent kernels up to ev_feat
-    seg_begin(c, &c->seg_A[ring], seg_key({3, ring, tring, pd.img0, pd.slot_l, pd.slot_r, gen, c->tail_streams, c->nms_first, c->cfg.max_keypoints}), tsm);
+    seg_begin(c, &c->seg_A[ring], tsm);
     {
       // heat map + threshold + candidate list in one kernel; the counter block of this set was
       // zeroed by the previous submission's last NMS kernel (or at allocation)
@@ -739,9 +736,7 @@ static int launch_group_body(spvo_ctx *c) {
       // (two tail streams: the temporal partner's features come from the submission before, on the other stream)
       if (c->tail_streams == 2 && pd.prev_l >= 0) HIP_TRY(c, hipStreamWaitEvent(tsm, c->ev_feat[(ring + RING - 1) % RING], 0));
       // launch segment B: the pair's two matches (distance GEMM + merge; the fp8 shortlist's conversions and re-rank)
-      unsigned ratio_bits;
-      std::memcpy(&ratio_bits, &c->pm_ratio, 4);
-      seg_begin(c, &c->seg_B[ring], seg_key({4, ring, pd.slot_l, pd.slot_r, pd.prev_l, gen, c->pm_selector, c->pm_cross, (long long)ratio_bits, c->match_fp8 ? 1 : 0, pd.ts}), tsm);
+      seg_begin(c, &c->seg_B[ring], tsm);
       rc = enqueue_prematch(c, pd.slot_l, pd.slot_r, pd.prev_l, ring);
       { const int rce = seg_end(c); if (!rc) rc = rce; }
     }
@@ -879,7 +874,6 @@ static int detect_wait(spvo_ctx *c, double P_l[12], double P_r[12], spvo_feature
 static int ensure_host_sets(spvo_ctx *c, size_t image_bytes) {
   const size_t hw2 = (size_t)2 * c->H * c->W, desc = (size_t)2 * c->cfg.max_keypoints * 256;
   if (!c->host_sets_ready) {   // (a flag of its own: a failure half-way must not look like "allocated" to the next call)
-    ++c->alloc_gen;   // (pinned buffers recorded launch segments may point to: a new generation of segment keys)
     for (int r = 0; r < RING; ++r) {
       if (!c->d_resized_r[r]) { int rc = dev_alloc(c, &c->d_resized_r[r], hw2, false); if (rc) return rc; }
       if (!c->h_resized_r[r]) HIP_TRY(c, hipHostMalloc((void **)&c->h_resized_r[r], hw2));
@@ -888,7 +882,6 @@ static int ensure_host_sets(spvo_ctx *c, size_t image_bytes) {
     c->host_sets_ready = true;
   }
   if (image_bytes > c->img_cap_r) {
-    ++c->alloc_gen;
     if (!c->pendq.empty()) return fail(c, SPVO_ERR_STATE, "the image size grew while submissions are in flight");
     HIP_TRY(c, hipDeviceSynchronize());
     for (int r = 0; r < RING; ++r) {

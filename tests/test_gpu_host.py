@@ -510,14 +510,9 @@ def test_a_node_like_caller_linked_against_the_host_library_runs(tmp_path, squee
     assert np.array_equal(got_c[1:], ref_c[1:]) and (stats[1:, 3] > 300).all()
 
 
-@pytest.mark.parametrize("precision", ["FP16", "INT8"])
-def test_launch_segments_replayed_from_graphs_do_not_change_results(tmp_path, squeeze_weights_path, sequence, precision, tuning):
-    """Round 6: for FP16 / INT8 engines the runs of kernel launches between two event operations of a submission -- a group's trunk, its heads,
-    a pair's heat map + NMS + sampling, its two matches -- are recorded and, from the third time the same run (same buffer set, slots, batch,
-    engine and tuning generation) comes by, replayed from a captured HIP graph: one hipGraphLaunch instead of up to eleven launches
-    (csrc/launch_segments.hip.h; tuning "graphs" = 0 keeps plain launches).  Over 48 frames of the block loop with four pairs announced
-    ahead and trunk pairing: every pose, every solver outcome and the keypoint / match counts of every frame are identical bit for bit with
-    and without, and most segments do go out as replays."""
+def _segment_engine(tmp_path, squeeze_weights_path, sequence, precision):
+    """The small engine of a launch-segment test on disk (sp_squeeze FP16, or sp_mbv1 INT8 calibrated on the first pair) and the
+    sequence's device-resident pairs in the order 0 1 2 3 4 3 2 1: (models dir, prefix, block-loop arguments)."""
     import torch
     from spvo import quant
     from oracle import frontend as ofe
@@ -534,12 +529,24 @@ def test_launch_segments_replayed_from_graphs_do_not_change_results(tmp_path, sq
     dev = [(torch.from_numpy(frames[f][0]).cuda().clone(), torch.from_numpy(frames[f][1]).cuda().clone()) for f in order]
     dl, dr = [a.data_ptr() for a, _ in dev], [b.data_ptr() for _, b in dev]
     rows, cols, stride = frames[0][0].shape[0], frames[0][0].shape[1], dev[0][0].stride(0)
+    return str(d), prefix, (dl, dr, rows, cols, stride, P_l, P_r), dev
+
+
+@pytest.mark.parametrize("precision", ["FP16", "INT8"])
+def test_launch_segments_replayed_from_graphs_do_not_change_results(tmp_path, squeeze_weights_path, sequence, precision, tuning):
+    """Round 6: for FP16 / INT8 engines the runs of kernel launches between two event operations of a submission -- a group's trunk, its heads,
+    a pair's heat map + NMS + sampling, its two matches -- are recorded and replayed from a captured HIP graph when the recorded launches are
+    identical to the ones the graph was built from (kernels, launch dimensions, LDS sizes, argument bytes; the graph is built the second time
+    the same launches come by): one hipGraphLaunch instead of up to eleven launches (csrc/launch_segments.hip.h; tuning "graphs" = 0 keeps
+    plain launches).  Over 48 frames of the block loop with four pairs announced ahead and trunk pairing: every pose, every solver outcome
+    and the keypoint / match counts of every frame are identical bit for bit with and without, and most segments do go out as replays."""
+    models, prefix, args, dev = _segment_engine(tmp_path, squeeze_weights_path, sequence, precision)
     out = {}
     for graphs in (0, 1):
         tuning(graphs=graphs)
-        fe = host.FrontEnd(str(d), prefix=prefix, precision=precision)
+        fe = host.FrontEnd(models, prefix=prefix, precision=precision)
         assert fe.engine_loaded, fe.last_error
-        recs = [fe.run_device_block(dl, dr, rows, cols, stride, P_l, P_r, first, 16, depth=4, deferred=True) for first in (0, 16, 32)]
+        recs = [fe.run_device_block(*args, first, 16, depth=4, deferred=True) for first in (0, 16, 32)]
         prof = fe.context().profile()
         out[graphs] = (np.concatenate(recs), prof.get("segment_graph_launch", {}).get("calls", 0), prof.get("segment_plain_launch", {}).get("calls", 0))
         fe.close()
@@ -547,5 +554,37 @@ def test_launch_segments_replayed_from_graphs_do_not_change_results(tmp_path, sq
     for field in ("q", "t", "has_pose", "pnp_ok", "accepted", "refined", "lm_iterations", "pnp_inliers", "stereo_matches", "keypoints_left"):
         assert np.array_equal(a[field], b[field]), field
     assert out[0][1] == 0 and out[0][2] == 0                       # tuning "graphs" = 0: no segment is ever opened
-    assert out[1][2] > 0 and out[1][1] >= 0.4 * (out[1][1] + out[1][2]), out[1][1:]   # 48 frames = six rounds of the eight buffer sets: the first two of every key go out as plain launches (and
-    #                                                                                       the first frames' allocations start new key generations), the rest as replays (a long loop: 82 %)
+    assert out[1][2] > 0 and out[1][1] >= 0.4 * (out[1][1] + out[1][2]), out[1][1:]   # 48 frames = six rounds of the eight buffer sets: the first two visits of
+    #                                                                                       every segment go out as plain launches, the rest as replays (a long loop: 82 %)
+
+
+@pytest.mark.parametrize("precision", ["FP16", "INT8"])
+def test_launch_segments_follow_setters_between_blocks(tmp_path, squeeze_weights_path, sequence, precision, tuning):
+    """A replay is decided from the recorded launches themselves, so a setter that changes them needs no part in it: between the three
+    blocks of one run the pre-computed matches change their ratio (0.8 -> 0.7: other kernel arguments; the front end's own matches then
+    miss the cache and are computed on demand) and then go back to the front end's settings with the fp8 shortlist on (other kernels, the
+    matcher's fp8 buffers allocated half-way through the run).  Every pose, solver outcome and count is identical bit for bit with graphs
+    on and off, and segments are still replayed."""
+    models, prefix, args, dev = _segment_engine(tmp_path, squeeze_weights_path, sequence, precision)
+    out = {}
+    for graphs in (0, 1):
+        tuning(graphs=graphs)
+        fe = host.FrontEnd(models, prefix=prefix, precision=precision)
+        assert fe.engine_loaded, fe.last_error
+        ctx = fe.context()
+        assert not ctx.match_fp8()
+        recs = [fe.run_device_block(*args, 0, 16, depth=4, deferred=True)]
+        ctx.set_prematch(True, "KNN", True, 0.7)
+        recs.append(fe.run_device_block(*args, 16, 16, depth=4, deferred=True))
+        ctx.set_prematch(True, "KNN", True, 0.8)                   # (the front end's own: KNN, cross-checked, ratio 0.8)
+        ctx.set_match_fp8(True)
+        recs.append(fe.run_device_block(*args, 32, 16, depth=4, deferred=True))
+        prof = ctx.profile()
+        out[graphs] = (np.concatenate(recs), prof.get("segment_graph_launch", {}).get("calls", 0), prof.get("segment_plain_launch", {}).get("calls", 0))
+        fe.close()
+    a, b = out[0][0], out[1][0]
+    for field in a.dtype.names:
+        if field != "latency_ms":                                  # (a time)
+            assert np.array_equal(a[field], b[field]), field
+    assert out[0][1] == 0 and out[0][2] == 0
+    assert out[1][1] > 0 and out[1][2] > 0, out[1][1:]

@@ -1,21 +1,11 @@
-// Stand-alone check of csrc/launch_segments.hip.h: plain launches through launch_kernel(), a recorded segment flushed directly, and a graph replay.
+// Stand-alone check of csrc/launch_segments.hip.h: plain launches through launch_kernel(), and a recorded segment flushed as plain launches.
 // hipcc --offload-arch=gfx950 -O3 -std=c++17 -I superpoint-stereo-visual-odometry_amd/csrc tools/launch_wrap_test.hip -o tools/launch_wrap_test
 #include "launch_segments.hip.h"
 #include <cstdio>
 struct Args { const float *in; float *out; int n; float k; };
 template <int ADD> __global__ __launch_bounds__(256) void k_struct(const Args a) { const int i = blockIdx.x * 256 + threadIdx.x; if (i < a.n) a.out[i] = a.in[i] * a.k + ADD; }
 __global__ void k_plain(const float *__restrict__ in, float *__restrict__ out, int n, float k, const int *opt) { const int i = blockIdx.x * 256 + threadIdx.x; if (i < n) out[i] = in[i] + k + (opt ? 1 : 0); }
-namespace spvo_int {
-__thread LaunchRecorder *t_rec = nullptr;
-void rec_flush_direct(LaunchRecorder *r) {
-  for (const LaunchNode &n : r->nodes) {
-    void *params[33];
-    for (int i = 0; i < n.n_args; ++i) params[i] = r->arena.data() + n.arg_off[i];
-    (void)::hipLaunchKernel(n.func, n.grid, n.block, params, n.lds, r->stream);
-  }
-  r->nodes.clear(); r->used = 0;
-}
-}
+namespace spvo_int { __thread LaunchRecorder *t_rec = nullptr; }
 int main() {
   const int n = 1000;
   float *a, *b, *c2;
@@ -29,11 +19,11 @@ int main() {
   hipStreamSynchronize(s);
   hipMemcpy(h.data(), c2, n * 4, hipMemcpyDeviceToHost);
   std::printf("plain: %g (expect 9) err %s\n", h[5], hipGetErrorString(hipGetLastError()));
-  spvo_int::LaunchRecorder r; r.arena.resize(1 << 16); r.active = true; r.stream = s; spvo_int::t_rec = &r;
+  spvo_int::LaunchRecorder r; r.active = true; r.stream = s; spvo_int::t_rec = &r;
   hipLaunchKernelGGL(k_plain, dim3(4), dim3(256), 0, s, a, b, n, 5.f, (const int *)nullptr);
   hipLaunchKernelGGL((k_struct<1>), dim3(4), dim3(256), 0, s, Args{b, c2, n, 3.f});
-  std::printf("recorded %zu nodes\n", r.nodes.size());
-  spvo_int::rec_flush_direct(&r); r.active = false; spvo_int::t_rec = nullptr;
+  std::printf("recorded %zu nodes\n", r.rec.nodes.size());
+  spvo_int::rec_poison(); spvo_int::t_rec = nullptr;
   hipStreamSynchronize(s);
   hipMemcpy(h.data(), c2, n * 4, hipMemcpyDeviceToHost);
   std::printf("segment flushed: %g (expect 19) err %s\n", h[5], hipGetErrorString(hipGetLastError()));
