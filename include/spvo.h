@@ -87,7 +87,10 @@ int spvo_set_fp32_split(spvo_ctx *ctx, int enable);
 /* preprocessImageImpl (base.cpp:68-121) + preprocessImage (nn.cpp:139-161):
  * centre-crop to the network aspect ratio, cv::resize(INTER_LINEAR) 8-bit
  * fixed-point semantics, scale P rows 0-1.  `P` (3x4 row-major, f64) is
- * updated in place.  `resized_u8` (net_height*net_width) may be NULL. */
+ * updated in place.  `resized_u8` (net_height*net_width) may be NULL.
+ * Before spvo_load_weights (a context without an engine: the classic front
+ * end at a fixed input size, classic.cpp:96-100) only the crop, the resize
+ * and P are done -- the same image, no network input plane is written. */
 int spvo_preprocess(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, size_t stride,
                     double P[12], uint8_t *resized_u8);
 
@@ -233,6 +236,42 @@ int spvo_orb_detect(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, size_
                     spvo_orb_keypoint *keypoints, uint8_t *descriptors /* [cap][32] */, int cap, int *n);
 /* the tables the descriptor uses: 256 x (x1, y1, x2, y2) test pairs and the 7 smoothing taps (either may be NULL) */
 int spvo_orb_tables(float *pattern /* [1024] */, float *taps /* [7] */);
+
+/* detectKeypoints of ClassicFeatureFrontEnd for DetectorType::ShiTomasi (cv::GFTTDetector::create(1000, 0.03, 7.5, 5, false, 0.04),
+ * feature_detection_classic.cpp:37-47) on one 8-bit image in host memory: 3x3 Sobel, 5x5 box sums of the gradient products (exact
+ * integers), minimum eigenvalue, candidates above quality_level x the image's maximum that are 3x3 local maxima, then greedily, best
+ * response first (of equals the later raster position first), every candidate that keeps min_distance from all kept ones, until
+ * max_corners are kept (<= 0: no limit).  OpenCV is not available to this build: the algorithm is the published one with OpenCV's
+ * tie and border rules as far as they are known, as restated by tests/classic_ref.py (its header lists the choices), and the kernels
+ * reproduce that restatement bit for bit.  Only block_size = 5 and min_distance <= 15 are built, images of at least 8 x 8:
+ * SPVO_ERR_INVALID otherwise.  Keypoints come in the order they were kept, integer coordinates as float; response = the minimum
+ * eigenvalue in OpenCV's scale.  `n` receives their number, of which min(n, cap) are written.  The image stays on the device for
+ * a spvo_orb_describe that follows. */
+int spvo_gftt_detect(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, size_t stride, int max_corners, double quality_level,
+                     double min_distance, int block_size, float *xy /* [cap][2] */, float *response /* [cap], may be NULL */, int cap,
+                     int *n);
+/* how the minimum-distance iteration of this context's last spvo_gftt_detect went: candidates still undecided after each of its
+ * three grid-wide round launches, and the rounds the one-workgroup finish then took (0: it had nothing to do) */
+int spvo_gftt_last_rounds(spvo_ctx *ctx, int *undecided_after_launch /* [3], may be NULL */, int *finish_rounds /* may be NULL */);
+
+/* detectKeypoints for DetectorType::FAST (cv::FastFeatureDetector::create(10, true), feature_detection_classic.cpp:32-36): FAST-9/16
+ * at `threshold` on the image itself (3-pixel border), response = the largest threshold at which the pixel is still a corner;
+ * with nonmax_suppression a corner stays iff its response is strictly greater than all eight neighbours' (two equal neighbours
+ * both go).  Raster order (row, then column), no cap: `n` receives the number found, of which min(n, cap) are written -- at most
+ * (rows / 2 + 1) (cols / 2 + 1) with suppression, rows x cols without.  Status and conventions as spvo_gftt_detect. */
+int spvo_fast_detect(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, size_t stride, int threshold, int nonmax_suppression,
+                     float *xy /* [cap][2] */, float *response /* [cap], may be NULL */, int cap, int *n);
+
+/* describeKeypoints for DescriptorType::ORB on keypoints the extractor did not detect itself (cv::ORB::create()->compute,
+ * feature_detection_classic.cpp:66-68, 110-111), octave 0: keypoints closer than 31 pixels to a border are dropped, order-preserving
+ * (`kept` receives the indices into xy that survived, ascending; `n_kept` their number); the others get spvo_orb_detect's direction
+ * and 256-bit steered BRIEF on the 7x7-smoothed image -- the same kernels, so a keypoint that spvo_orb_detect reports on level 0
+ * gets the same 32 bytes here.  Row i of `desc` / `angle` belongs to keypoint kept[i].  Coordinates must be integers (what both
+ * detectors above return): SPVO_ERR_INVALID otherwise.  img = NULL: the image of this context's last spvo_gftt_detect /
+ * spvo_fast_detect / spvo_orb_describe, still on the device (no second upload in the detect-then-describe sequence);
+ * SPVO_ERR_STATE if none is resident or its shape is not rows x cols. */
+int spvo_orb_describe(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, size_t stride, const float *xy /* [n][2] */, int n,
+                      int32_t *kept /* [n] */, float *angle /* [n] rad, may be NULL */, uint8_t *desc /* [n][32] */, int *n_kept);
 
 /* The same for BINARY descriptors: cv::BFMatcher(NORM_HAMMING), what initMatcher (base.cpp:17-21) builds for the ORB / BRISK /
  * AKAZE descriptors of ClassicFeatureFrontEnd (classic.cpp:66-79) and matchDescriptors (base.cpp:434-500) runs on them.

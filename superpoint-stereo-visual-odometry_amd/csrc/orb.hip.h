@@ -48,14 +48,14 @@ struct OrbLevel {
 struct OrbLevels { OrbLevel l[ORB_LEVELS]; };
 
 // FAST-9 corner score on the Bresenham circle of radius 3: the largest threshold at which the pixel is still a corner, 0 if it is not
-// one at threshold t (or lies in the border)
-__global__ __launch_bounds__(256) void orb_fast_kernel(const OrbLevels lv, int t) {
+// one at threshold t (or lies in the border of `edge` pixels, >= 3: ORB_EDGE for ORB, 3 for the plain FAST detector of classic_detect.hip.h)
+__global__ __launch_bounds__(256) void orb_fast_kernel(const OrbLevels lv, int t, int edge) {
   const OrbLevel L = lv.l[blockIdx.z];
   const int h = L.h, w = L.w;
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (L.want <= 0 || x >= w || y >= h) return;
   int best = 0;
-  if (x >= ORB_EDGE && x < w - ORB_EDGE && y >= ORB_EDGE && y < h - ORB_EDGE) {
+  if (x >= edge && x < w - edge && y >= edge && y < h - edge) {
     const uint8_t *p = L.im + (size_t)y * w + x;
     const int c = *p;
     const int off[16] = {-3 * w, -3 * w + 1, -2 * w + 2, -w + 3, 3, w + 3, 2 * w + 2, 3 * w + 1, 3 * w, 3 * w - 1, 2 * w - 2, w - 3, -3, -w - 3, -2 * w - 2, -3 * w - 1};

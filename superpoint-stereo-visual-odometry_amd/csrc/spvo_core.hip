@@ -442,6 +442,9 @@ void spvo_destroy(spvo_ctx *c) {
   for (void *dp : {(void *)c->orb.im, (void *)c->orb.score, (void *)c->orb.blur, (void *)c->orb.src, (void *)c->orb.tmp, (void *)c->orb.pattern, (void *)c->orb.taps, (void *)c->orb.keys,
                    (void *)c->orb.rank, (void *)c->orb.out_xy, (void *)c->orb.counters, (void *)c->orb.tab, (void *)c->orb.disc, (void *)c->orb.kps, (void *)c->orb.desc})
     if (dp) (void)hipFree(dp);
+  for (void *dp : {(void *)c->cls.im, (void *)c->cls.score, (void *)c->cls.blur, (void *)c->cls.src, (void *)c->cls.state, (void *)c->cls.desc, (void *)c->cls.tmp, (void *)c->cls.lam,
+                   (void *)c->cls.xy, (void *)c->cls.resp, (void *)c->cls.keys, (void *)c->cls.rank, (void *)c->cls.cand, (void *)c->cls.counters, (void *)c->cls.kp_xy, (void *)c->cls.kps, (void *)c->cls.pre_out, (void *)c->cls.pre_tab})
+    if (dp) (void)hipFree(dp);
   for (auto hp : c->h_match_out) if (hp) (void)hipHostFree(hp);
   if (c->h_match_tmp) (void)hipHostFree(c->h_match_tmp);
   if (c->stream_t) (void)hipStreamDestroy(c->stream_t);

@@ -284,6 +284,23 @@ struct spvo_ctx {
     size_t src_cap = 0;
     int tab_rows = 0, tab_cols = 0;   // image size the resize tables in `tab` belong to
   } orb;
+  // Shi-Tomasi / FAST detectors and the ORB extractor for given keypoints (classic_detect.hip.h): one image resident at a time,
+  // buffers grow with the image (per-pixel ones with rows x cols, the state map with its padded shape) and the keypoint list
+  struct ClassicBufs {
+    size_t px_cap = 0, state_cap = 0, src_cap = 0;
+    int kp_cap = 0;
+    int rows = 0, cols = 0;               // shape of the image in `im` (0: none resident)
+    int state_rows = 0, state_cols = 0;   // shape the state map's padding was cleared for
+    uint8_t *im = nullptr, *score = nullptr, *blur = nullptr, *src = nullptr, *state = nullptr, *desc = nullptr;
+    float *tmp = nullptr, *lam = nullptr, *xy = nullptr, *resp = nullptr;
+    unsigned long long *keys = nullptr;
+    int *rank = nullptr, *cand = nullptr, *counters = nullptr, *kp_xy = nullptr;
+    OrbKeypoint *kps = nullptr;
+    uint8_t *pre_out = nullptr;           // spvo_preprocess of a context without an engine (the classic front end at a fixed input size): resized image,
+    int *pre_tab = nullptr;               // resize tables of the crop pre_crop_rows x pre_crop_cols
+    int pre_crop_rows = 0, pre_crop_cols = 0;
+    int last_counters[16] = {0};          // the counter block of the last spvo_gftt_detect (rounds, undecided after each launch)
+  } cls;
   // Hamming matcher (classic front end's binary descriptors): rows padded to 16 words
   int ham_cap = 0;
   uint32_t *d_ham_a = nullptr, *d_ham_b = nullptr;

@@ -485,13 +485,16 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
   }
 }
 #else
-// Without OpenCV: ORB + ORB (the reference's baseline configuration, launch/visual_odometry_classic.launch) runs on the GPU
-// through spvo_orb_detect -- detection and description are one pass there, so detectKeypoints keeps the descriptors for the
-// describeKeypoints call that follows on the same image; the other detector / descriptor types are OpenCV features2d calls and
-// stay unavailable.
+// Without OpenCV: the detectors that need only a binary descriptor run on the GPU.  ORB + ORB (the reference's baseline
+// configuration, launch/visual_odometry_classic.launch) goes through spvo_orb_detect -- detection and description are one pass
+// there, so detectKeypoints keeps the descriptors for the describeKeypoints call that follows on the same image.  ShiTomasi + ORB
+// (the default constructor) and FAST + ORB go through spvo_gftt_detect / spvo_fast_detect and spvo_orb_describe (classic.cpp:32-47,
+// 66-68, 110-111); the image stays on the device between the two.  BRISK, AKAZE, SIFT are OpenCV features2d calls and stay unavailable.
 bool ClassicFeatureFrontEnd::available() { return true; }
+static bool classic_detector_runs(DetectorType d) { return d == DetectorType::ORB || d == DetectorType::ShiTomasi || d == DetectorType::FAST; }
 void ClassicFeatureFrontEnd::initDetector() {
-  if (detector_type_ != DetectorType::ORB) logError("[initDetector] only ORB runs without OpenCV (build with SPVO_USE_OPENCV for the other detectors of classic.cpp:7-56)");
+  if (!classic_detector_runs(detector_type_))
+    logError("[initDetector] only ORB, ShiTomasi and FAST run without OpenCV (build with SPVO_USE_OPENCV for the other detectors of classic.cpp:7-56)");
 }
 void ClassicFeatureFrontEnd::initDescriptor() {
   if (descriptor_type_ != DescriptorType::ORB) logError("[initDescriptor] only ORB runs without OpenCV (build with SPVO_USE_OPENCV for the other descriptors of classic.cpp:58-79)");
@@ -500,13 +503,38 @@ void ClassicFeatureFrontEnd::initDescriptor() {
 std::vector<cv::KeyPoint> ClassicFeatureFrontEnd::detectKeypoints(const cv::Mat &img) {
   std::vector<cv::KeyPoint> keypoints;
   orb_desc_ = cv::Mat();
-  if (detector_type_ != DetectorType::ORB || descriptor_type_ != DescriptorType::ORB) {
-    logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB + ORB runs");
+  detected_data_ = nullptr;
+  if (!classic_detector_runs(detector_type_) || descriptor_type_ != DescriptorType::ORB) {
+    logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB, ShiTomasi and FAST with ORB descriptors run");
     return keypoints;
   }
   if (!ensureContext()) return keypoints;
   if (img.depth() != CV_8U || img.rows <= 0) {
     logError("detectKeypoints: 8-bit single-channel image expected");
+    return keypoints;
+  }
+  if (detector_type_ != DetectorType::ORB) {
+    // cv::GFTTDetector::create(1000, 0.03, 7.5, 5, false, 0.04) / cv::FastFeatureDetector::create(10, true), classic.cpp:32-47
+    const bool gftt = detector_type_ == DetectorType::ShiTomasi;
+    const int cap = gftt ? 1000 : (img.rows / 2 + 1) * (img.cols / 2 + 1);
+    std::vector<float> xy((size_t)cap * 2), resp((size_t)cap);
+    int n = 0;
+    const int rc = gftt ? spvo_gftt_detect(ctx_, img.ptr<uint8_t>(0), img.rows, img.cols, (size_t)img.step, 1000, 0.03, 7.5, 5, xy.data(), resp.data(), cap, &n)
+                        : spvo_fast_detect(ctx_, img.ptr<uint8_t>(0), img.rows, img.cols, (size_t)img.step, 10, 1, xy.data(), resp.data(), cap, &n);
+    if (rc != SPVO_OK) {
+      logError(std::string(gftt ? "spvo_gftt_detect: " : "spvo_fast_detect: ") + spvo_last_error(ctx_));
+      return keypoints;
+    }
+    n = std::min(n, cap);
+    keypoints.reserve(n);
+    for (int i = 0; i < n; ++i) {
+      cv::KeyPoint k(cv::Point2f(xy[2 * i], xy[2 * i + 1]), gftt ? 5.f : 7.f);   // KeyPoint::convert(corners, keypoints, blockSize) / KeyPoint(x, y, 7.f, -1, score)
+      k.angle = -1.f;
+      k.response = resp[i];
+      k.octave = 0;
+      keypoints.push_back(k);
+    }
+    detected_data_ = img.data; detected_rows_ = img.rows; detected_cols_ = img.cols;
     return keypoints;
   }
   constexpr int NFEATURES = 2000;   // classic.cpp:13
@@ -534,7 +562,41 @@ std::vector<cv::KeyPoint> ClassicFeatureFrontEnd::detectKeypoints(const cv::Mat 
   return keypoints;
 }
 
-cv::Mat ClassicFeatureFrontEnd::describeKeypoints(std::vector<cv::KeyPoint> &keypoints, const cv::Mat &) {
+cv::Mat ClassicFeatureFrontEnd::describeKeypoints(std::vector<cv::KeyPoint> &keypoints, const cv::Mat &img) {
+  if (detector_type_ != DetectorType::ORB && classic_detector_runs(detector_type_) && descriptor_type_ == DescriptorType::ORB) {
+    // cv::ORB::create()->compute(img, keypoints, descriptors), classic.cpp:66-68: keypoints too close to a border are ERASED from the
+    // caller's vector (it is passed by non-const reference, classic.cpp:110-111), so keypoints_dq and descriptors_dq stay aligned
+    if (!ensureContext()) return cv::Mat();
+    if (img.depth() != CV_8U || img.rows <= 0) {
+      logError("describeKeypoints: 8-bit single-channel image expected");
+      return cv::Mat();
+    }
+    const int n = (int)keypoints.size();
+    std::vector<float> xy((size_t)n * 2), angle((size_t)n);
+    std::vector<int32_t> kept((size_t)n);
+    for (int i = 0; i < n; ++i) { xy[2 * i] = keypoints[i].pt.x; xy[2 * i + 1] = keypoints[i].pt.y; }
+    cv::Mat desc(n, 32, CV_8UC1);
+    const bool resident = detected_data_ && detected_data_ == img.data && detected_rows_ == img.rows && detected_cols_ == img.cols;
+    int m = 0;
+    if (spvo_orb_describe(ctx_, resident ? nullptr : img.ptr<uint8_t>(0), img.rows, img.cols, (size_t)img.step, xy.data(), n, kept.data(), angle.data(),
+                          n ? desc.ptr<uint8_t>(0) : nullptr, &m) != SPVO_OK) {
+      logError(std::string("spvo_orb_describe: ") + spvo_last_error(ctx_));
+      keypoints.clear();
+      return cv::Mat();
+    }
+    std::vector<cv::KeyPoint> out;
+    out.reserve(m);
+    for (int i = 0; i < m; ++i) {
+      cv::KeyPoint k = keypoints[kept[i]];
+      k.angle = angle[i] * 57.29577951308232f;   // cv::KeyPoint::angle is in degrees
+      if (k.angle < 0) k.angle += 360.f;
+      out.push_back(k);
+    }
+    keypoints.swap(out);
+    cv::Mat d(m, 32, CV_8UC1);
+    if (m) std::memcpy(d.ptr<uint8_t>(0), desc.ptr<uint8_t>(0), (size_t)m * 32);
+    return d;
+  }
   if (orb_desc_.rows != (int)keypoints.size()) {
     logError("describeKeypoints: call detectKeypoints on the same image first (ORB detects and describes in one pass here)");
     return cv::Mat();
@@ -547,8 +609,8 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
     logError("input images shape doesn't match!");
     return;
   }
-  if (detector_type_ != DetectorType::ORB || descriptor_type_ != DescriptorType::ORB) {
-    logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB + ORB runs");
+  if (!classic_detector_runs(detector_type_) || descriptor_type_ != DescriptorType::ORB) {
+    logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB, ShiTomasi and FAST with ORB descriptors run");
     return;
   }
   if (!ensureContext()) return;   // no device: logged, nothing pushed (nn.cpp:53-55 convention)

@@ -243,14 +243,40 @@ int spvo_host_classic_match(int knn, int cross_check, int match_type, const uint
   return (int)m.size();
 }
 
-// stereoCallback (node.cpp:150-262) replayed on a ClassicFeatureFrontEnd(ORB, ORB, BF, selector, cross_check, stereo_threshold, ..)
-// exactly as node.cpp:353-360 constructs it, over n stereo pairs in host memory (native resolution, launch/visual_odometry_classic.launch).
+// the default-constructed classic front end (hpp: ShiTomasi + ORB, BF, NN, cross-check, 120 x 392) offered one stereo pair of
+// rows x cols: returns the number of deque entries it produced (negative: the deques are not aligned), the keypoint / descriptor
+// row counts of the pair in counts[4] (keypoints L, descriptors L, keypoints R, descriptors R) and the error it logged
+int spvo_host_classic_default_probe(const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, const double *P_l, const double *P_r, int *counts, char *err, int cap) {
+  ClassicFeatureFrontEnd fe;
+  cv::Mat l(rows, cols, CV_8UC1), r(rows, cols, CV_8UC1), pl(3, 4, CV_64FC1), pr(3, 4, CV_64FC1);
+  std::memcpy(l.data, img_l, (size_t)rows * cols);
+  std::memcpy(r.data, img_r, (size_t)rows * cols);
+  std::memcpy(pl.data, P_l, 12 * sizeof(double));
+  std::memcpy(pr.data, P_r, 12 * sizeof(double));
+  fe.addStereoImagePair(l, r, pl, pr);
+  std::strncpy(err, fe.lastError().c_str(), cap - 1);
+  err[cap - 1] = 0;
+  for (int i = 0; i < 4; ++i) counts[i] = 0;
+  if (fe.keypoints_dq.size() != fe.descriptors_dq.size()) return -1;
+  if (fe.keypoints_dq.size() >= 2) {
+    counts[0] = (int)fe.keypoints_dq.end()[-2].size(); counts[1] = fe.descriptors_dq.end()[-2].rows;
+    counts[2] = (int)fe.keypoints_dq.end()[-1].size(); counts[3] = fe.descriptors_dq.end()[-1].rows;
+  }
+  return (int)fe.keypoints_dq.size();
+}
+
+// stereoCallback (node.cpp:150-262) replayed on a ClassicFeatureFrontEnd(detector, ORB, BF, selector, cross_check, stereo_threshold, ..)
+// exactly as node.cpp:353-360 constructs it, over n stereo pairs in host memory.  input_height / input_width 0 / 0: native resolution
+// (launch/visual_odometry_classic.launch); otherwise preprocessImageImpl runs first (classic.cpp:96-100).
 // poses: n x 7 (q xyzw, t of cam0_curr_T_cam0_prev; identity for frame 0); stats: n x 4 (keypoints left, right, stereo matches,
 // PnP inliers); seconds: wall time of frames warm .. n-1.  Returns the number of frames processed, negative on failure.
-int spvo_host_classic_sequence(int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l, const double *P_r, int knn,
-                               int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats, double *seconds) {
-  ClassicFeatureFrontEnd fe(detector_name_to_type.at("ORB"), descriptor_name_to_type.at("ORB"), matcher_name_to_type.at("BF"),
-                            selector_name_to_type.at(knn ? "KNN" : "NN"), cross_check != 0, stereo_threshold, stereo_threshold, refinement_degree, false, 0, 0);
+int spvo_host_classic_sequence_ex(const char *detector_name, int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l,
+                                  const double *P_r, int knn, int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats,
+                                  double *seconds, int input_height, int input_width) {
+  if (!detector_name || !detector_name_to_type.count(detector_name)) return -1000000;
+  ClassicFeatureFrontEnd fe(detector_name_to_type.at(detector_name), descriptor_name_to_type.at("ORB"), matcher_name_to_type.at("BF"),
+                            selector_name_to_type.at(knn ? "KNN" : "NN"), cross_check != 0, stereo_threshold, stereo_threshold, refinement_degree, false, input_height,
+                            input_width);
   timespec t0{}, t1{};
   for (int k = 0; k < n; ++k) {
     if (k == warm) clock_gettime(CLOCK_MONOTONIC, &t0);
@@ -282,6 +308,12 @@ int spvo_host_classic_sequence(int n, const uint8_t *const *imgs_l, const uint8_
   clock_gettime(CLOCK_MONOTONIC, &t1);
   if (seconds) *seconds = n > warm ? (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec) : 0.0;
   return n;
+}
+
+// the ORB + ORB front end at the native resolution (the export's first form)
+int spvo_host_classic_sequence(int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l, const double *P_r, int knn,
+                               int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats, double *seconds) {
+  return spvo_host_classic_sequence_ex("ORB", n, imgs_l, imgs_r, rows, cols, P_l, P_r, knn, cross_check, stereo_threshold, refinement_degree, warm, poses, stats, seconds, 0, 0);
 }
 
 // bit 0 pnp ok, bit 1 accepted by the gate, bit 2 refinement kept; LM iterations in bits 8..

@@ -63,7 +63,7 @@ SYMBOLS = [
     "spvo_default_config", "spvo_create", "spvo_destroy", "spvo_last_error", "spvo_load_weights", "spvo_engine_precision", "spvo_set_fp32_split",
     "spvo_preprocess", "spvo_forward", "spvo_debug_tensor", "spvo_heatmap", "spvo_nms",
     "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8",
-    "spvo_match_hamming", "spvo_orb_detect", "spvo_orb_tables", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
+    "spvo_match_hamming", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
     "spvo_profile_enable", "spvo_profile_reset", "spvo_profile_only", "spvo_profile_count", "spvo_profile_get", "spvo_profile_stage_kernel",
     "spvo_set_tuning", "spvo_get_tuning", "spvo_clear_tuning",
     "spvo_comm_unique_id", "spvo_comm_available", "spvo_comm_create", "spvo_comm_create_host", "spvo_comm_rank", "spvo_comm_world", "spvo_comm_destroy",
@@ -116,6 +116,10 @@ def load() -> C.CDLL:
     lib.spvo_match_hamming.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]
     lib.spvo_orb_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, vp, vp, C.c_int, ip]
     lib.spvo_orb_tables.argtypes = [vp, vp]
+    lib.spvo_gftt_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_double, C.c_double, C.c_int, vp, vp, C.c_int, ip]
+    lib.spvo_gftt_last_rounds.argtypes = [vp, vp, ip]
+    lib.spvo_fast_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, vp, vp, C.c_int, ip]
+    lib.spvo_orb_describe.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, vp, vp, vp, ip]
     lib.spvo_set_prematch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float]
     lib.spvo_triangulate.argtypes = [vp, dp, dp, vp, vp, C.c_int, vp]
     lib.spvo_pnp_ransac.argtypes = [vp, dp, vp, vp, C.c_int, C.POINTER(RansacOpts), dp, dp, vp, ip, ip]
@@ -156,6 +160,14 @@ class SpvoError(RuntimeError):
 
 def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _u8_rows(img) -> np.ndarray:
+    """a 2-D u8 image whose rows are contiguous; a strided view (rows of a larger image) is passed as it is, with its row stride"""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim != 2 or img.strides[1] != 1 or img.strides[0] < img.shape[1]:
+        img = np.ascontiguousarray(img, np.uint8)
+    return img
 
 
 def _dptr(a: np.ndarray):
@@ -365,6 +377,62 @@ class Context:
         taps = np.zeros(7, np.float32)
         self._check(self.lib.spvo_orb_tables(_ptr(pat), _ptr(taps)))
         return pat, taps
+
+    def gftt(self, img: np.ndarray, max_corners=1000, quality=0.03, min_distance=7.5, block_size=5):
+        """Shi-Tomasi corners of one u8 image (spvo_gftt_detect): dict of xy [n,2] in the order they were kept, response [n]."""
+        img = _u8_rows(img)
+        cap = max_corners if max_corners > 0 else img.shape[0] * img.shape[1]
+        xy = np.zeros((cap, 2), np.float32)
+        resp = np.zeros(cap, np.float32)
+        n = C.c_int(0)
+        self._check(self.lib.spvo_gftt_detect(self.h, _ptr(img), img.shape[0], img.shape[1], img.strides[0], max_corners, quality, min_distance, block_size,
+                                              _ptr(xy), _ptr(resp), cap, C.byref(n)))
+        self._resident_shape = img.shape
+        k = min(n.value, cap)
+        return dict(xy=xy[:k].copy(), response=resp[:k].copy())
+
+    def gftt_rounds(self):
+        """(undecided candidates after each round launch, rounds of the finish kernel) of the last gftt() call"""
+        rem = np.zeros(3, np.int32)
+        fin = C.c_int(0)
+        self._check(self.lib.spvo_gftt_last_rounds(self.h, _ptr(rem), C.byref(fin)))
+        return rem, fin.value
+
+    def fast(self, img: np.ndarray, threshold=10, nonmax_suppression=True):
+        """FAST-9/16 corners of one u8 image in raster order (spvo_fast_detect): dict of xy [n,2], response [n]; all of them (no cap)."""
+        img = _u8_rows(img)
+        cap = (img.shape[0] // 2 + 1) * (img.shape[1] // 2 + 1) if nonmax_suppression else img.shape[0] * img.shape[1]
+        xy = np.zeros((cap, 2), np.float32)
+        resp = np.zeros(cap, np.float32)
+        n = C.c_int(0)
+        self._check(self.lib.spvo_fast_detect(self.h, _ptr(img), img.shape[0], img.shape[1], img.strides[0], threshold, int(bool(nonmax_suppression)), _ptr(xy), _ptr(resp),
+                                              cap, C.byref(n)))
+        assert n.value <= cap
+        self._resident_shape = img.shape
+        return dict(xy=xy[:n.value].copy(), response=resp[:n.value].copy())
+
+    def orb_describe(self, img, xy: np.ndarray, shape=None):
+        """ORB descriptors of given level-0 keypoints (spvo_orb_describe).  img = None: the image of the last gftt() / fast() /
+        orb_describe() of this context, still on the device (shape: its (rows, cols), by default the one this object remembers).
+        -> dict of kept [m] (indices into xy that survived the 31-pixel border rule), angle [m] rad, desc [m,32]."""
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        n = len(xy)
+        kept = np.zeros(max(n, 1), np.int32)
+        angle = np.zeros(max(n, 1), np.float32)
+        desc = np.zeros((max(n, 1), 32), np.uint8)
+        m = C.c_int(0)
+        if img is None:
+            rows, cols = shape if shape is not None else getattr(self, "_resident_shape", (0, 0))
+            ptr, stride = None, 0
+            if rows <= 0 or cols <= 0:
+                rows = cols = 1            # nothing remembered: let the library answer (SPVO_ERR_STATE)
+        else:
+            img = _u8_rows(img)
+            (rows, cols), ptr, stride = img.shape, _ptr(img), img.strides[0]
+        self._check(self.lib.spvo_orb_describe(self.h, ptr, rows, cols, stride, _ptr(xy), n, _ptr(kept), _ptr(angle), _ptr(desc), C.byref(m)))
+        if img is not None:
+            self._resident_shape = img.shape
+        return dict(kept=kept[:m.value].copy(), angle=angle[:m.value].copy(), desc=desc[:m.value].copy())
 
     def match_hamming(self, a: np.ndarray, b: np.ndarray, selector="KNN", cross_check=False, ratio=0.8):
         """cv::BFMatcher(NORM_HAMMING) on u8 descriptor rows (spvo_match_hamming)."""

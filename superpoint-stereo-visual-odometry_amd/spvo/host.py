@@ -341,14 +341,15 @@ class FrontEnd:
         return self.solve_stereo_odometry()                      # node.cpp:218
 
 
-def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_threshold=2.0, refinement_degree=4, warm=0):
-    """stereoCallback replayed on ClassicFeatureFrontEnd(ORB, ORB, BF, ...) (node.cpp:353-360) over host image pairs at their native
-    resolution: returns (poses [n, 7] = q xyzw + t of cam0_curr_T_cam0_prev, stats [n, 4] = keypoints L, R, stereo matches, PnP
-    inliers, seconds spent on frames warm .. n-1)."""
+def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_threshold=2.0, refinement_degree=4, warm=0, detector="ORB", input_size=None):
+    """stereoCallback replayed on ClassicFeatureFrontEnd(detector, ORB, BF, ...) (node.cpp:353-360) over host image pairs -- detector
+    "ORB", "ShiTomasi" or "FAST"; input_size None: at their native resolution, (height, width): through preprocessImageImpl first
+    (classic.cpp:96-100).  Returns (poses [n, 7] = q xyzw + t of cam0_curr_T_cam0_prev, stats [n, 4] = keypoints L, R, stereo
+    matches, PnP inliers, seconds spent on frames warm .. n-1)."""
     lib = load()
-    lib.spvo_host_classic_sequence.restype = C.c_int
-    lib.spvo_host_classic_sequence.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                               C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+    lib.spvo_host_classic_sequence_ex.restype = C.c_int
+    lib.spvo_host_classic_sequence_ex.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                  C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int]
     n = len(frames)
     ls = [np.ascontiguousarray(f[0], np.uint8) for f in frames]
     rs = [np.ascontiguousarray(f[1], np.uint8) for f in frames]
@@ -360,8 +361,27 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     poses = np.zeros((n, 7), np.float64)
     stats = np.zeros((n, 4), np.int32)
     sec = C.c_double(0)
-    rc = lib.spvo_host_classic_sequence(n, pl, pr, rows, cols, Pl.ctypes.data, Pr.ctypes.data, 1 if selector == "KNN" else 0, int(cross_check), stereo_threshold,
-                                        refinement_degree, warm, poses.ctypes.data, stats.ctypes.data, C.byref(sec))
+    ih, iw = (0, 0) if input_size is None else (int(input_size[0]), int(input_size[1]))
+    rc = lib.spvo_host_classic_sequence_ex(detector.encode(), n, pl, pr, rows, cols, Pl.ctypes.data, Pr.ctypes.data, 1 if selector == "KNN" else 0, int(cross_check),
+                                           stereo_threshold, refinement_degree, warm, poses.ctypes.data, stats.ctypes.data, C.byref(sec), ih, iw)
+    if rc == -1000000:
+        raise ValueError("unknown detector %r" % (detector,))
     if rc != n:
         raise RuntimeError("classic front end failed at frame %d" % (-rc - 1))
     return poses, stats, sec.value
+
+
+def classic_default_probe(img_l, img_r, P_l, P_r):
+    """ClassicFeatureFrontEnd() -- the default constructor: ShiTomasi + ORB at 120 x 392 -- offered one stereo pair.
+    -> (deque entries, [keypoints L, descriptor rows L, keypoints R, descriptor rows R], the error it logged)"""
+    lib = load()
+    lib.spvo_host_classic_default_probe.restype = C.c_int
+    lib.spvo_host_classic_default_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
+    l = np.ascontiguousarray(img_l, np.uint8)
+    r = np.ascontiguousarray(img_r, np.uint8)
+    Pl = np.ascontiguousarray(P_l, np.float64).reshape(12)
+    Pr = np.ascontiguousarray(P_r, np.float64).reshape(12)
+    counts = np.zeros(4, np.int32)
+    buf = C.create_string_buffer(512)
+    rc = lib.spvo_host_classic_default_probe(l.ctypes.data, r.ctypes.data, l.shape[0], l.shape[1], Pl.ctypes.data, Pr.ctypes.data, counts.ctypes.data, buf, 512)
+    return rc, counts, buf.value.decode()

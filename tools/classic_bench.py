@@ -1,12 +1,69 @@
-"""ClassicFeatureFrontEnd(ORB, ORB, BF, KNN) on the GPU over the synthetic stream: frames/s of the synchronous stereoCallback
-(python tools/classic_bench.py [frames]); run under rocprofv3 --kernel-trace --stats for the per-kernel split."""
-import os, sys
+"""The classic front end on the GPU.
+
+python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST]
+    ClassicFeatureFrontEnd(detector, ORB, BF, KNN) over the synthetic stream: frames/s of the synchronous stereoCallback.
+python tools/classic_bench.py --detectors [--calls 200] [--warmup 20]
+    per image at 1241 x 376: spvo_orb_detect (the yardstick, same run) beside spvo_gftt_detect + spvo_orb_describe and
+    spvo_fast_detect + spvo_orb_describe -- median, 10th / 90th percentile of the synchronous calls, keypoints, and how the
+    minimum-distance iteration went (undecided candidates after each round launch, rounds of the finish kernel).
+python tools/classic_bench.py --leg gftt|fast|orb [--calls 50]
+    one leg alone, for rocprofv3 --kernel-trace --stats -- python tools/classic_bench.py --leg gftt
+"""
+import argparse
+import os
+import sys
+import time
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "superpoint-stereo-visual-odometry_amd"))
 import numpy as np
-from spvo import host, synth
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 60
+from spvo import capi, host, synth
+
+ap = argparse.ArgumentParser()
+ap.add_argument("frames", nargs="?", type=int, default=60)
+ap.add_argument("--detector", default="ORB")
+ap.add_argument("--detectors", action="store_true")
+ap.add_argument("--leg", choices=["gftt", "fast", "orb"])
+ap.add_argument("--calls", type=int, default=200)
+ap.add_argument("--warmup", type=int, default=20)
+args = ap.parse_args()
 frames, poses, P_l, P_r = synth.stereo_sequence(8, os.path.join(ROOT, "tests", "golden", "images", "0000000000.png"), seed=0)
-seq = [frames[i % 8] for i in range(n)]
-p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5)
-print("classic front end on the GPU: %.1f stereo frames/s (%.3f ms per pair), keypoints %d, stereo matches %d, inliers %d" % ((n - 5) / sec, 1e3 * sec / (n - 5), np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3])))
+
+if args.detectors or args.leg:
+    img = np.ascontiguousarray(frames[0][0][:376, :1241])
+    ctx = capi.Context(net_height=64, net_width=96)
+
+    def leg_orb():
+        return len(ctx.orb(img)["xy"])
+
+    def leg_gftt():
+        g = ctx.gftt(img)
+        return len(ctx.orb_describe(None, g["xy"])["kept"])
+
+    def leg_fast():
+        g = ctx.fast(img)
+        return len(ctx.orb_describe(None, g["xy"])["kept"])
+
+    legs = dict(orb=("spvo_orb_detect", leg_orb), gftt=("spvo_gftt_detect + spvo_orb_describe", leg_gftt), fast=("spvo_fast_detect + spvo_orb_describe", leg_fast))
+    for key in ([args.leg] if args.leg else ["orb", "gftt", "fast"]):
+        name, fn = legs[key]
+        for _ in range(args.warmup):
+            n = fn()
+        ts = []
+        for _ in range(args.calls):
+            t0 = time.perf_counter()
+            n = fn()
+            ts.append(1e3 * (time.perf_counter() - t0))
+        ts = np.array(ts)
+        extra = ""
+        if key == "gftt":
+            rem, fin = ctx.gftt_rounds()
+            extra = ", undecided after the round launches %s, finish rounds %d" % (rem.tolist(), fin)
+        print("%-40s %d x %d: median %.3f ms (p10 %.3f, p90 %.3f) over %d calls, %d described keypoints%s" % (name, img.shape[1], img.shape[0], np.median(ts), np.percentile(ts, 10),
+                                                                                                      np.percentile(ts, 90), args.calls, n, extra))
+    ctx.close()
+else:
+    n = args.frames
+    seq = [frames[i % 8] for i in range(n)]
+    p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5, detector=args.detector)
+    print("classic front end (%s) on the GPU: %.1f stereo frames/s (%.3f ms per pair), keypoints %d, stereo matches %d, inliers %d" % (args.detector, (n - 5) / sec, 1e3 * sec / (n - 5), np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3])))
