@@ -13,7 +13,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "post.hip.h"
+#include "conv_mfma.hip.h"    // mul_rn, add_rn
+#include "spvo_types.hip.h"   // rank_key, RANK_TILE, ST_*, OrbKeypoint
 
 namespace spvo {
 

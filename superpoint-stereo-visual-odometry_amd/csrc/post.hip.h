@@ -163,13 +163,7 @@ __global__ __launch_bounds__(256) void heatmap_kernel(const float *__restrict__ 
 // Border candidates suppress but are not emitted (nn.cpp:239-244); the cap keeps
 // the first `max_kp` emitted in rank order (nn.cpp:256-257).
 // ---------------------------------------------------------------------------
-enum : uint8_t { ST_NONE = 0, ST_UNDECIDED = 1, ST_KEPT = 2, ST_SUPPRESSED = 4 };   // one bit each: word-wide tests
-
-// (NMS_PAD, NMS_COUNTER_INTS, nms_state_pitch, NmsBuffers, NmsPair: spvo_types.hip.h)
-
-__device__ __forceinline__ unsigned long long rank_key(float conf, int x, int y, int H) {
-  return ((unsigned long long)(0xFFFFFFFFu - __float_as_uint(conf)) << 32) | (unsigned)(x * H + y);
-}
+// (ST_*, NMS_PAD, NMS_COUNTER_INTS, nms_state_pitch, NmsBuffers, NmsPair, rank_key, RANK_TILE: spvo_types.hip.h)
 
 // K8: threshold + stream compaction.  One atomic per workgroup (wave ballots + LDS prefix), so
 // the candidate list comes out grouped by 64x4-pixel tiles: neighbours in the image are
@@ -506,8 +500,7 @@ __global__ __launch_bounds__(256) void nms_collect_kernel(const float *__restric
 }
 
 // K9: rank by counting -- the output position of a survivor is the number of survivors with a
-// smaller key.  2-D decomposition: block (bi, bj) counts 256 keys against a 1024-key LDS tile.
-constexpr int RANK_TILE = 1024;
+// smaller key.  2-D decomposition: block (bi, bj) counts 256 keys against a 1024-key LDS tile (RANK_TILE).
 // The grid does not depend on the buffer's capacity (one survivor per 5x5 cell at most: 17 k; a few thousand in practice): a fixed
 // number of workgroups per image walks the blocks the survivor count on the device calls for -- a capacity-sized grid is 2278
 // workgroups per launch, most of which only start and exit, next to convolutions whose workgroups need whole CUs.

@@ -236,26 +236,73 @@ void free_plan(spvo_ctx *c) {
     if (t.d) (void)hipFree(t.d);
     for (int r = 1; r < RING; ++r) if (t.dr[r]) (void)hipFree(t.dr[r]);
   }
-  for (auto &o : c->ops)
-  {
-    for (float *p : {o.d_w, o.d_b, o.d_bn_scale, o.d_bn_shift}) if (p) (void)hipFree(p);
-    if (o.d_w16) (void)hipFree(o.d_w16);
-    if (o.d_w8) (void)hipFree(o.d_w8);
-    if (o.d_ws3) (void)hipFree(o.d_ws3);
-    if (o.d_wq32) (void)hipFree(o.d_wq32);
-    if (o.d_wsel) (void)hipFree(o.d_wsel);
-    if (o.d_qm) (void)hipFree(o.d_qm);
-    if (o.d_sched) (void)hipFree(o.d_sched);
-  }
-  if (c->d_heads_w) (void)hipFree(c->d_heads_w);
-  if (c->d_heads_w8) (void)hipFree(c->d_heads_w8);
-  if (c->d_heads_qm) (void)hipFree(c->d_heads_qm);
-  if (c->d_heads_b) (void)hipFree(c->d_heads_b);
-  c->d_heads_w = nullptr; c->d_heads_w8 = nullptr; c->d_heads_qm = c->d_heads_b = nullptr; c->heads_fused = false;
+  for (auto &o : c->ops) dev_free(o.d_w, o.d_b, o.d_bn_scale, o.d_bn_shift, o.d_w16, o.d_w8, o.d_ws3, o.d_wq32, o.d_wsel, o.d_qm, o.d_sched);
+  dev_free(c->d_heads_w, c->d_heads_w8, c->d_heads_qm, c->d_heads_b);
+  c->heads_fused = false;
   c->tensors.clear(); c->ops.clear(); c->weights = false; c->fp16 = false; c->int8 = false; c->s3 = false;
 }
 
 }  // namespace spvo_int
+
+// tuning "trunk_timing" = 1 (diagnostic): how long the network stream works per trunk launch and how long it stands idle between two,
+// from timing events at both ends of the trunk (printed every 200 launches); > 1: one line per launch from that launch on (80 of
+// them), with the host clock.  The switch is read when the context is created (spvo_create), the timing events and sums belong to the context.
+void TrunkDiag::launch_begin(spvo_ctx *c, int npairs) {
+  const int trace_lo = c->trunk_timing;
+  const double tnow = diag_now_us();
+  const bool found_idle = c->last_launch_ring >= 0 && hipEventQuery(c->ev_net[c->last_launch_ring]) == hipSuccess;
+  if (found_idle) ++g_diag.late;   // the trunk before this one is done already: the stream is idle
+  if (trace_lo > 1 && g_diag.launches + 1 >= trace_lo && g_diag.launches + 1 < trace_lo + 80)
+    std::fprintf(stderr, "T %.0f launch %ld: %d pairs, stream %s, submissions so far %u, in flight %zu\n", tnow, g_diag.launches + 1, npairs, found_idle ? "IDLE" : "busy", c->submit_count, c->pendq.size());
+  if (++g_diag.launches > 100 && g_diag.iv_printed < 16 && (found_idle || g_diag.iv_printed % 4 != 0)) {   // an idle launch and the three behind it
+    std::fprintf(stderr, "[spvo]   launch %ld (%d pairs, stream %s): %.0f us since the previous launch, of which the host waited %.0f us for features, %.0f us for matches, %.0f us for the solver; %zu submissions in flight\n",
+                 g_diag.launches, npairs, found_idle ? "IDLE" : "busy", tnow - g_diag.t_last_submit, g_diag.iv_tail, g_diag.iv_match, g_diag.iv_solve, c->pendq.size());
+    ++g_diag.iv_printed;
+  }
+  g_diag.iv_tail = g_diag.iv_match = g_diag.iv_solve = 0;
+  g_diag.depth_sum += (int)c->pendq.size();
+  if (g_diag.t_last_submit > 0) g_diag.max_interval = std::max(g_diag.max_interval, tnow - g_diag.t_last_submit);
+  g_diag.t_last_submit = tnow;
+  if (n == 0)
+    for (int r = 0; r < TT; ++r) { (void)hipEventCreate(&b[r]); (void)hipEventCreate(&e[r]); (void)hipEventCreate(&tb[r]); (void)hipEventCreate(&te[r]); }
+  if (n >= TT) {   // the launches before those that may be in flight are complete: ring slots (n-8) and (n-9)
+    const int r2 = (int)((n - 8) % TT), r3 = (int)((n - 9) % TT);
+    float busy_ms = 0, idle_ms = 0;
+    if (hipEventElapsedTime(&busy_ms, b[r2], e[r2]) == hipSuccess && hipEventElapsedTime(&idle_ms, e[r3], b[r2]) == hipSuccess) {
+      busy += busy_ms; idle += idle_ms;
+      late += idle_ms > 0.05f ? 1 : 0;
+      max_idle = std::max(max_idle, idle_ms);
+    }
+    pat += (char)('0' + np[r2]);
+    if (idle_ms > 0.05f) pat += idle_ms > 0.3f ? 'I' : 'i';
+    if (n % 200 == 0) { std::fprintf(stderr, "[spvo]   pairs per launch (i / I: the stream stood idle > 50 / > 300 us in front of it): %s\n", pat.c_str()); pat.clear(); }
+    if (trace_lo > 1) {   // device-side times of launch (n - 8), relative to the first trace line's moment
+      if (!base && g_diag.launches >= trace_lo - 8) { (void)hipEventCreate(&base); (void)hipEventRecord(base, c->stream_t); (void)hipEventSynchronize(base); base_host = diag_now_us(); }
+      float b0 = 0, e0 = 0, tb0 = 0, te0 = 0;
+      if (base && g_diag.launches - 8 >= trace_lo && g_diag.launches - 8 < trace_lo + 80 && hipEventElapsedTime(&b0, base, b[r2]) == hipSuccess &&
+          hipEventElapsedTime(&e0, base, e[r2]) == hipSuccess && hipEventElapsedTime(&tb0, base, tb[r2]) == hipSuccess && hipEventElapsedTime(&te0, base, te[r2]) == hipSuccess)
+        std::fprintf(stderr, "G launch %ld (%d pairs): trunk %.0f .. %.0f, tail %.0f .. %.0f (host clock)\n", g_diag.launches - 8, np[r2], base_host + b0 * 1e3, base_host + e0 * 1e3,
+                     base_host + tb0 * 1e3, base_host + te0 * 1e3);
+    }
+    float tail_ms = 0, lag_ms = 0;
+    if (hipEventElapsedTime(&tail_ms, tb[r2], te[r2]) == hipSuccess && hipEventElapsedTime(&lag_ms, e[r2], te[r2]) == hipSuccess) { tail += tail_ms; lag += lag_ms; }
+    if (n % 200 == 0) {
+      std::fprintf(stderr, "[spvo] trunk timing over 200 launches (%.0f pairs): network stream busy %.1f us, idle %.1f us per launch (%d gaps above 50 us, longest %.0f us)\n",
+                   pairs, busy * 1e3 / 200, idle * 1e3 / 200, late, max_idle * 1e3);
+      std::fprintf(stderr, "[spvo]   NMS continuations driven by the host so far: %lld\n", c->stages[stage_id(c, "nms_redo")].calls);
+      std::fprintf(stderr, "[spvo]   tail stream: %.1f us per launch from its first kernel to its last, which ends %.1f us behind the trunk\n", tail * 1e3 / 200, lag * 1e3 / 200);
+      tail = lag = 0;
+      std::fprintf(stderr, "[spvo]   host: longest interval between launches %.0f us, longest wait for a tail %.0f us, for a solve %.0f us, matches not served from the cache %d; "
+                           "launches that found the network stream idle %d, mean submissions in flight at launch %.2f\n",
+                   g_diag.max_interval, g_diag.max_tail_wait, g_diag.max_solve_wait, g_diag.match_miss, g_diag.late, g_diag.depth_sum / 200.0);
+      g_diag.max_interval = g_diag.max_tail_wait = g_diag.max_solve_wait = 0; g_diag.match_miss = 0; g_diag.late = 0; g_diag.depth_sum = 0;
+      busy = idle = pairs = 0; late = 0; max_idle = 0;
+    }
+  }
+  pairs += npairs;
+  np[n % TT] = npairs;
+  (void)hipEventRecord(b[n % TT], c->stream);
+}
 
 // ===========================================================================
 extern "C" {
@@ -409,14 +456,11 @@ void spvo_destroy(spvo_ctx *c) {
   for (void *p : ptrs) if (p) (void)hipFree(p);
   for (auto &set : c->ms)
     for (auto &m : set)
-      for (void *p : {(void *)m.d_na, (void *)m.d_nb, (void *)m.d_best_d2, (void *)m.d_dt, (void *)m.d_cand, (void *)m.d_meta, (void *)m.d_best_idx, (void *)m.d_train_best,
-                      (void *)m.d_a8, (void *)m.d_b8, (void *)m.d_qa8, (void *)m.d_qb8})
-        if (p) (void)hipFree(p);
+      dev_free(m.d_na, m.d_nb, m.d_best_d2, m.d_dt, m.d_cand, m.d_meta, m.d_best_idx, m.d_train_best, m.d_a8, m.d_b8, m.d_qa8, m.d_qb8);
   for (int r = 0; r < RING; ++r) {
     for (int i = 0; i < 2; ++i) {
       NmsBuffers &b = c->nms_r[r][i].b;
-      void *q[] = {b.state, b.cand, b.surv_key, b.rank, b.out_xy};
-      for (void *p : q) if (p) (void)hipFree(p);
+      dev_free(b.state, b.cand, b.surv_key, b.rank, b.out_xy);
     }
     if (c->d_heat_base_r[r]) (void)hipFree(c->d_heat_base_r[r]);
     if (c->h_counters_r[r]) (void)hipHostFree(c->h_counters_r[r]);
@@ -428,23 +472,18 @@ void spvo_destroy(spvo_ctx *c) {
     if (c->h_desc_r[r]) (void)hipHostFree(c->h_desc_r[r]);
     for (hipEvent_t e : {c->ev_net[r], c->ev_tail[r], c->ev_feat[r], c->ev_copy[r], c->ev_pre[r], c->ev_res[r], c->ev_up[r]}) if (e) (void)hipEventDestroy(e);
   }
-  for (int i = 0; i < N_SLOTS; ++i) {
-    void *q[] = {c->slots[i].d_xy, c->slots[i].d_xyf, c->slots[i].d_desc, c->slots[i].d_n, c->slots[i].d_sqn};
-    for (void *p : q) if (p) (void)hipFree(p);
-  }
+  for (auto &sl : c->slots) dev_free(sl.d_xy, sl.d_xyf, sl.d_desc, sl.d_n, sl.d_sqn);
   for (int sl = 0; sl < spvo_ctx::SOLVE_BUFS; ++sl) {
     for (void *dp : {(void *)c->x_counts[sl], (void *)c->x_poses[sl], (void *)c->x_obs[sl]}) if (dp) (void)hipFree(dp);
     for (void *hp : {(void *)c->h_solve_in[sl], (void *)c->h_solve_res[sl], (void *)c->h_solve_o[sl]}) if (hp) (void)hipHostFree(hp);
     for (void *dp : {(void *)c->d_solve_in[sl], (void *)c->d_solve_res[sl], (void *)c->d_solve_o[sl]}) if (dp) (void)hipFree(dp);
   }
   if (c->d_ctl) (void)hipFree(c->d_ctl);
-  for (void *dp : {(void *)c->d_ham_a, (void *)c->d_ham_b, (void *)c->d_ham_idx, (void *)c->d_ham_dist, (void *)c->d_ham_vote}) if (dp) (void)hipFree(dp);
-  for (void *dp : {(void *)c->orb.im, (void *)c->orb.score, (void *)c->orb.blur, (void *)c->orb.src, (void *)c->orb.tmp, (void *)c->orb.pattern, (void *)c->orb.taps, (void *)c->orb.keys,
-                   (void *)c->orb.rank, (void *)c->orb.out_xy, (void *)c->orb.counters, (void *)c->orb.tab, (void *)c->orb.disc, (void *)c->orb.kps, (void *)c->orb.desc})
-    if (dp) (void)hipFree(dp);
-  for (void *dp : {(void *)c->cls.im, (void *)c->cls.score, (void *)c->cls.blur, (void *)c->cls.src, (void *)c->cls.state, (void *)c->cls.desc, (void *)c->cls.tmp, (void *)c->cls.lam,
-                   (void *)c->cls.xy, (void *)c->cls.resp, (void *)c->cls.keys, (void *)c->cls.rank, (void *)c->cls.cand, (void *)c->cls.counters, (void *)c->cls.kp_xy, (void *)c->cls.kps, (void *)c->cls.pre_out, (void *)c->cls.pre_tab})
-    if (dp) (void)hipFree(dp);
+  dev_free(c->d_ham_a, c->d_ham_b, c->d_ham_idx, c->d_ham_dist, c->d_ham_vote);
+  auto &o = c->orb;
+  dev_free(o.im, o.score, o.blur, o.src, o.tmp, o.pattern, o.taps, o.keys, o.rank, o.out_xy, o.counters, o.tab, o.disc, o.kps, o.desc);
+  auto &b = c->cls;
+  dev_free(b.im, b.score, b.blur, b.src, b.state, b.desc, b.tmp, b.lam, b.xy, b.resp, b.keys, b.rank, b.cand, b.counters, b.kp_xy, b.kps, b.pre_out, b.pre_tab);
   for (auto hp : c->h_match_out) if (hp) (void)hipHostFree(hp);
   if (c->h_match_tmp) (void)hipHostFree(c->h_match_tmp);
   if (c->stream_t) (void)hipStreamDestroy(c->stream_t);

@@ -1,16 +1,14 @@
 // spvo_detect.hip -- preprocess (K0), heat map / NMS / descriptor sampling (K7-K11), the detector submissions (addStereoImagePair,
-// feature_detection_neural_network.cpp:449-498), spvo_forward / spvo_debug_tensor, and the ORB detector of the classic front end.
+// feature_detection_neural_network.cpp:449-498), spvo_forward / spvo_debug_tensor.
 #include "spvo_internal.hip.h"
 #include "conv_mfma.hip.h"
 #include "post.hip.h"
 #include "conv_first_pre.hip.h"
-#include "orb.hip.h"
-#include "classic_detect.hip.h"
 
 namespace spvo_int {
 
 // ---------------------------------------------------------------- resize tables
-void linear_coeffs(int dst, int src, std::vector<int> &idx, std::vector<int> &a0, std::vector<int> &a1) {
+static void linear_coeffs(int dst, int src, std::vector<int> &idx, std::vector<int> &a0, std::vector<int> &a1) {
   // OpenCV resize.cpp, INTER_LINEAR, 8-bit: float32 fractional part, 11-bit coefficients
   const double scale = (double)src / (double)dst;
   idx.resize(dst); a0.resize(dst); a1.resize(dst);
@@ -26,7 +24,12 @@ void linear_coeffs(int dst, int src, std::vector<int> &idx, std::vector<int> &a0
   }
 }
 
-struct CropGeom { int row_off, col_off, crop_rows, crop_cols; float scale; };
+void resize_tables(int dst_w, int src_w, int dst_h, int src_h, std::vector<int> &out) {
+  std::vector<int> xi, xa0, xa1, yi, yb0, yb1;
+  linear_coeffs(dst_w, src_w, xi, xa0, xa1);
+  linear_coeffs(dst_h, src_h, yi, yb0, yb1);
+  for (auto *v : {&xi, &xa0, &xa1, &yi, &yb0, &yb1}) out.insert(out.end(), v->begin(), v->end());
+}
 
 CropGeom crop_geometry(int rows, int cols, int net_h, int net_w) {
   // base.cpp:75-119, float32 arithmetic and int truncation as written there
@@ -66,20 +69,29 @@ void fix_projection(double P[12], const CropGeom &g, int rows, int cols, int bug
 
 int ensure_tables(spvo_ctx *c, const CropGeom &g) {
   if (c->tab_rows == g.crop_rows && c->tab_cols == g.crop_cols) return SPVO_OK;
-  std::vector<int> xi, xa0, xa1, yi, yb0, yb1;
-  linear_coeffs(c->W, g.crop_cols, xi, xa0, xa1);
-  linear_coeffs(c->H, g.crop_rows, yi, yb0, yb1);
   std::vector<int> all;
-  all.insert(all.end(), xi.begin(), xi.end());
-  all.insert(all.end(), xa0.begin(), xa0.end());
-  all.insert(all.end(), xa1.begin(), xa1.end());
-  all.insert(all.end(), yi.begin(), yi.end());
-  all.insert(all.end(), yb0.begin(), yb0.end());
-  all.insert(all.end(), yb1.begin(), yb1.end());
+  resize_tables(c->W, g.crop_cols, c->H, g.crop_rows, all);
   HIP_TRY(c, hipMemcpyAsync(c->d_tab, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // `all` is a stack-lifetime buffer
   c->tab_rows = g.crop_rows;
   c->tab_cols = g.crop_cols;
+  return SPVO_OK;
+}
+
+static ResizeTab resize_tab(const spvo_ctx *c) {
+  ResizeTab t;   // xi, xa0, xa1 [W]; yi, yb0, yb1 [H]
+  t.xi = c->d_tab; t.xa0 = c->d_tab + c->W; t.xa1 = c->d_tab + 2 * c->W;
+  t.yi = c->d_tab + 3 * c->W; t.yb0 = t.yi + c->H; t.yb1 = t.yi + 2 * c->H;
+  return t;
+}
+
+// the stand-alone entry points' staging for two input images of `bytes` each (a failed allocation leaves the capacity at 0)
+static int ensure_img_staging(spvo_ctx *c, size_t bytes) {
+  if (bytes <= c->img_cap) return SPVO_OK;
+  dev_free(c->d_img[0], c->d_img[1]);
+  c->img_cap = 0;
+  for (int i = 0; i < 2; ++i) { int rc = dev_alloc(c, &c->d_img[i], bytes, false); if (rc) return rc; }
+  c->img_cap = bytes;
   return SPVO_OK;
 }
 
@@ -90,9 +102,7 @@ int launch_preprocess(spvo_ctx *c, const uint8_t *d_src0, const uint8_t *d_src1,
                       uint8_t *resized_dst = nullptr) {
   int rc = ensure_tables(c, g);
   if (rc) return rc;
-  ResizeTab tab;
-  tab.xi = c->d_tab; tab.xa0 = c->d_tab + c->W; tab.xa1 = c->d_tab + 2 * c->W;
-  tab.yi = c->d_tab + 3 * c->W; tab.yb0 = tab.yi + c->H; tab.yb1 = tab.yi + 2 * c->H;
+  ResizeTab tab = resize_tab(c);
   const Tensor &tin = c->tensors[c->t_input];
   const int identity = (g.crop_rows == c->H && g.crop_cols == c->W) ? 1 : 0;
   dim3 grid((c->W + 63) / 64, (c->H + 3) / 4, count);
@@ -107,7 +117,7 @@ int launch_preprocess(spvo_ctx *c, const uint8_t *d_src0, const uint8_t *d_src1,
 int launch_first_pre(spvo_ctx *c, PendingDetect *const *mem, int n, hipStream_t stream) {
   const Op &op = c->ops[0];
   const Tensor &ti = c->tensors[op.in], &to = c->tensors[op.out];
-  const CropGeomS &g = mem[0]->g;
+  const CropGeom &g = mem[0]->g;
   FirstPreArgs a;
   for (int k = 0; k < 4; ++k) { a.src[k] = nullptr; a.out_u8[k] = nullptr; }
   const size_t hw = (size_t)c->H * c->W;
@@ -120,8 +130,7 @@ int launch_first_pre(spvo_ctx *c, PendingDetect *const *mem, int n, hipStream_t 
   a.stride = mem[0]->stride;
   a.row_off = g.row_off; a.col_off = g.col_off; a.crop_rows = g.crop_rows; a.crop_cols = g.crop_cols;
   a.identity = (g.crop_rows == c->H && g.crop_cols == c->W) ? 1 : 0;
-  a.tab.xi = c->d_tab; a.tab.xa0 = c->d_tab + c->W; a.tab.xa1 = c->d_tab + 2 * c->W;
-  a.tab.yi = c->d_tab + 3 * c->W; a.tab.yb0 = a.tab.yi + c->H; a.tab.yb1 = a.tab.yi + 2 * c->H;
+  a.tab = resize_tab(c);
   a.in_plane = ti.d; a.in_per_image = ti.per_image;
   a.out = to.dr[c->cur_ring] ? to.dr[c->cur_ring] : to.d;
   a.w = op.d_w; a.bias = op.d_b;
@@ -231,59 +240,24 @@ extern "C" {
 
 int spvo_preprocess(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride, double P[12], uint8_t *resized_u8) {
   if (!c || !img || !P || rows <= 0 || cols <= 0 || stride < (size_t)cols) return fail(c, SPVO_ERR_INVALID, "bad argument");
-  if (!c->pendq.empty()) return fail(c, SPVO_ERR_STATE, "detector submissions are in flight: complete them with spvo_detect_wait first");
+  if (int rc = require_idle(c)) return rc;
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   const size_t bytes = (size_t)(rows - 1) * stride + cols;   // what is the caller's of a strided view: not the last row's padding
-  if (bytes > c->img_cap) {
-    for (int i = 0; i < 2; ++i) { if (c->d_img[i]) (void)hipFree(c->d_img[i]); c->d_img[i] = nullptr; }
-    c->img_cap = 0;
-    for (int i = 0; i < 2; ++i) { int rc = dev_alloc(c, &c->d_img[i], bytes, false); if (rc) return rc; }
-    c->img_cap = bytes;
-  }
+  if (int rc = ensure_img_staging(c, bytes)) return rc;
   const CropGeom g = crop_geometry(rows, cols, c->H, c->W);
   HIP_TRY(c, hipMemcpyAsync(c->d_img[0], img, bytes, hipMemcpyHostToDevice, c->stream));
-  if (!c->weights) {
-    // A context without an engine (the classic front end with a fixed input size, classic.cpp:96-100): there is no network input
-    // plane to fill, only the crop + cv::resize(INTER_LINEAR) of the u8 image -- orb_resize_kernel is preprocess_kernel's arithmetic.
-    auto &b = c->cls;
-    const int H = c->H, W = c->W;
-    if (!b.pre_out) {
-      int rc;
-      if ((rc = dev_alloc(c, &b.pre_out, (size_t)H * W)) || (rc = dev_alloc(c, &b.pre_tab, (size_t)3 * (H + W)))) return rc;
-      b.pre_crop_rows = b.pre_crop_cols = 0;
-    }
-    const uint8_t *src = c->d_img[0] + (size_t)g.row_off * stride + g.col_off;
-    if (g.crop_rows == H && g.crop_cols == W) {   // cv::resize copies when the sizes already match
-      HIP_TRY(c, hipMemcpy2DAsync(b.pre_out, W, src, stride, W, H, hipMemcpyDeviceToDevice, c->stream));
-    } else {
-      if (b.pre_crop_rows != g.crop_rows || b.pre_crop_cols != g.crop_cols) {
-        std::vector<int> all, xi, xa0, xa1, yi, yb0, yb1;
-        linear_coeffs(W, g.crop_cols, xi, xa0, xa1);
-        linear_coeffs(H, g.crop_rows, yi, yb0, yb1);
-        for (auto *v : {&xi, &xa0, &xa1, &yi, &yb0, &yb1}) all.insert(all.end(), v->begin(), v->end());
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        HIP_TRY(c, hipMemcpy(b.pre_tab, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice));
-        b.pre_crop_rows = g.crop_rows; b.pre_crop_cols = g.crop_cols;
-      }
-      hipLaunchKernelGGL(orb_resize_kernel, dim3((W + 63) / 64, (H + 3) / 4), dim3(256), 0, c->stream, src, g.crop_rows, g.crop_cols, (int)stride, b.pre_out, H, W, b.pre_tab);
-      HIP_TRY(c, hipGetLastError());
-    }
-    fix_projection(P, g, rows, cols, c->cfg.bug_compat_p);
-    if (resized_u8) HIP_TRY(c, hipMemcpyAsync(resized_u8, b.pre_out, (size_t)H * W, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return SPVO_OK;
-  }
-  int rc = launch_preprocess(c, c->d_img[0], c->d_img[0], 1, rows, cols, stride, g, 0);
+  // (a context without an engine -- the classic front end at a fixed input size -- resizes the u8 image only: spvo_classic.hip)
+  int rc = c->weights ? launch_preprocess(c, c->d_img[0], c->d_img[0], 1, rows, cols, stride, g, 0) : classic_preprocess(c, g, stride);
   if (rc) return rc;
   fix_projection(P, g, rows, cols, c->cfg.bug_compat_p);
-  if (resized_u8) HIP_TRY(c, hipMemcpyAsync(resized_u8, c->d_resized, (size_t)c->H * c->W, hipMemcpyDeviceToHost, c->stream));
+  if (resized_u8) HIP_TRY(c, hipMemcpyAsync(resized_u8, c->weights ? c->d_resized : c->cls.pre_out, (size_t)c->H * c->W, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return SPVO_OK;
 }
 
 int spvo_forward(spvo_ctx *c, const float *input, int batch, float *det, float *desc_nhwc) {
   if (!c || !input) return fail(c, SPVO_ERR_INVALID, "null argument");
-  if (!c->pendq.empty()) return fail(c, SPVO_ERR_STATE, "detector submissions are in flight: complete them with spvo_detect_wait first");
+  if (int rc = require_idle(c)) return rc;
   if (!c->weights) return fail(c, SPVO_ERR_STATE, "no weights loaded");
   if (batch < 1 || batch > c->B) return fail(c, SPVO_ERR_INVALID, "batch %d out of range", batch);
   HIP_TRY(c, hipSetDevice(c->cfg.device));
@@ -309,7 +283,7 @@ int spvo_forward(spvo_ctx *c, const float *input, int batch, float *det, float *
 
 int spvo_debug_tensor(spvo_ctx *c, int tensor_id, int batch, float *out, size_t out_floats) {
   if (!c || !out) return fail(c, SPVO_ERR_INVALID, "null argument");
-  if (!c->pendq.empty()) return fail(c, SPVO_ERR_STATE, "detector submissions are in flight: complete them with spvo_detect_wait first");
+  if (int rc = require_idle(c)) return rc;
   if (!c->weights) return fail(c, SPVO_ERR_STATE, "no weights loaded");
   if (tensor_id < 0 || tensor_id >= (int)c->tensors.size() || batch < 1 || batch > c->B) return fail(c, SPVO_ERR_INVALID, "bad tensor id / batch");
   const Tensor &t = c->tensors[tensor_id];
@@ -335,7 +309,7 @@ int spvo_debug_tensor(spvo_ctx *c, int tensor_id, int batch, float *out, size_t 
 
 int spvo_heatmap(spvo_ctx *c, const float *det, float *heat) {
   if (!c || !det || !heat) return fail(c, SPVO_ERR_INVALID, "null argument");
-  if (!c->pendq.empty()) return fail(c, SPVO_ERR_STATE, "detector submissions are in flight: complete them with spvo_detect_wait first");
+  if (int rc = require_idle(c)) return rc;
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   HIP_TRY(c, hipMemcpyAsync(c->d_det_dense, det, (size_t)65 * c->Hc * c->Wc * sizeof(float), hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(heatmap_kernel<false>, dim3((c->Wc + 63) / 64, (c->Hc + 3) / 4, 1), dim3(256), 0, c->stream, c->d_det_dense, c->d_heat, c->Hc, c->Wc, 0, 0);
@@ -347,7 +321,7 @@ int spvo_heatmap(spvo_ctx *c, const float *det, float *heat) {
 
 int spvo_nms(spvo_ctx *c, const float *heat, int32_t *xy, int *n) {
   if (!c || !heat || !xy || !n) return fail(c, SPVO_ERR_INVALID, "null argument");
-  if (!c->pendq.empty()) return fail(c, SPVO_ERR_STATE, "detector submissions are in flight: complete them with spvo_detect_wait first");
+  if (int rc = require_idle(c)) return rc;
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   HIP_TRY(c, hipMemcpyAsync(c->d_heat, heat, (size_t)c->H * c->W * sizeof(float), hipMemcpyHostToDevice, c->stream));
   int rc = run_nms(c, 1);
@@ -359,7 +333,7 @@ int spvo_nms(spvo_ctx *c, const float *heat, int32_t *xy, int *n) {
 
 int spvo_sample_descriptors(spvo_ctx *c, const float *desc_nhwc, const int32_t *xy, int n, float *out) {
   if (!c || !desc_nhwc || (n > 0 && (!xy || !out))) return fail(c, SPVO_ERR_INVALID, "null argument");
-  if (!c->pendq.empty()) return fail(c, SPVO_ERR_STATE, "detector submissions are in flight: complete them with spvo_detect_wait first");
+  if (int rc = require_idle(c)) return rc;
   if (!c->weights) return fail(c, SPVO_ERR_STATE, "no weights loaded");
   if (n < 0 || n > c->cfg.max_keypoints) return fail(c, SPVO_ERR_CAPACITY, "n = %d exceeds max_keypoints", n);
   if (n == 0) return SPVO_OK;
@@ -520,7 +494,7 @@ static int detect_submit(spvo_ctx *c, const uint8_t *d_l, const uint8_t *d_r, in
   for (int i = 0; i < 2; ++i) c->slots[slots[i]].filled = true;
   c->last_slot_l = slot_l;
   PendingDetect pd;
-  pd.g = CropGeomS{g.row_off, g.col_off, g.crop_rows, g.crop_cols, g.scale};
+  pd.g = g;
   pd.rows = rows; pd.cols = cols;
   pd.slot_l = slot_l; pd.slot_r = slot_r; pd.prev_l = prev_l; pd.ring = ring; pd.extras = extras; pd.early_res = (extras & 1) != 0;
   pd.launched = false; pd.img0 = 2 * pos; pd.tring = ring;
@@ -562,6 +536,7 @@ static int launch_group(spvo_ctx *c, bool from_submit) {
   c->held = 0;
   c->post = c->stream;
   c->cur_ring = 0;
+  c->ms_set = 0;
   for (int m = 0; m < n && m < (int)c->pendq.size(); ++m) {
     PendingDetect &pd = c->pendq[c->pendq.size() - 1 - m];
     pd.failed = true;
@@ -574,113 +549,22 @@ static int launch_group(spvo_ctx *c, bool from_submit) {
   return rc;
 }
 
-// phases B (the trunk of the held pairs: one or two, 2 or 4 images per launch) and C (each pair's tail)
-static int launch_group_body(spvo_ctx *c) {
-  const int n = c->held;
-  if (n <= 0) return SPVO_OK;
-  if (n > 2 || (int)c->pendq.size() < n) return fail(c, SPVO_ERR_STATE, "internal: %d held submissions, %zu in flight", n, c->pendq.size());
-  c->held = 0;
-  PendingDetect *mem[2] = {&c->pendq[c->pendq.size() - n], n == 2 ? &c->pendq[c->pendq.size() - 1] : nullptr};
-  const int tring = mem[0]->ring;      // the set whose network outputs (det, desc, head inputs) hold all images of the group
-  const int batch = 2 * n;
-  const Tensor &td = c->tensors[c->t_det];
-  // ---- everything below is enqueued without a host round trip
-  c->cur_ring = tring;
-  c->post = c->stream;
-  // tuning "trunk_timing" = 1 (diagnostic): how long the network stream works per trunk launch and how long it stands idle between two,
-  // from timing events at both ends of the trunk (printed every 200 launches)
-  // -- the switch is read when the context is created (spvo_create), its timing events and sums belong to the context
-  TrunkDiag &td_ = c->tdiag;
-  const bool trunk_timing = c->trunk_timing != 0;
-  constexpr int TT = TrunkDiag::TT;   // ring of timing events: deeper than the launches that can be in flight
-  hipEvent_t *tt_b = td_.b, *tt_e = td_.e, *tt_tb = td_.tb, *tt_te = td_.te;   // trunk begin / end (network stream), tail begin / end (tail stream)
-  double &tt_tail = td_.tail, &tt_lag = td_.lag;
-  int *tt_np = td_.np;
-  long &tt_n = td_.n;
-  double &tt_busy = td_.busy, &tt_idle = td_.idle, &tt_pairs = td_.pairs;
-  const int trace_lo = c->trunk_timing;   // > 1: one line per launch from that launch on (80 of them), with the host clock
-  if (c->inject_launch_failure > 0 && ++c->launch_count == c->inject_launch_failure)   // tests of the error path (tuning "inject_launch_failure")
-    return fail(c, SPVO_ERR_DEVICE, "injected launch failure (diagnostic switch)");
-  if (trunk_timing) {
-    const double tnow = diag_now_us();
-    const bool found_idle = c->last_launch_ring >= 0 && hipEventQuery(c->ev_net[c->last_launch_ring]) == hipSuccess;
-    if (found_idle) ++g_diag.late;   // the trunk before this one is done already: the stream is idle
-    if (trace_lo > 1 && g_diag.launches + 1 >= trace_lo && g_diag.launches + 1 < trace_lo + 80)
-      std::fprintf(stderr, "T %.0f launch %ld: %d pairs, stream %s, submissions so far %u, in flight %zu\n", tnow, g_diag.launches + 1, n, found_idle ? "IDLE" : "busy", c->submit_count, c->pendq.size());
-    if (++g_diag.launches > 100 && g_diag.iv_printed < 16 && (found_idle || g_diag.iv_printed % 4 != 0)) {   // an idle launch and the three behind it
-      std::fprintf(stderr, "[spvo]   launch %ld (%d pairs, stream %s): %.0f us since the previous launch, of which the host waited %.0f us for features, %.0f us for matches, %.0f us for the solver; %zu submissions in flight\n",
-                   g_diag.launches, n, found_idle ? "IDLE" : "busy", tnow - g_diag.t_last_submit, g_diag.iv_tail, g_diag.iv_match, g_diag.iv_solve, c->pendq.size());
-      ++g_diag.iv_printed;
-    }
-    g_diag.iv_tail = g_diag.iv_match = g_diag.iv_solve = 0;
-    g_diag.depth_sum += (int)c->pendq.size();
-    if (g_diag.t_last_submit > 0) g_diag.max_interval = std::max(g_diag.max_interval, tnow - g_diag.t_last_submit);
-    g_diag.t_last_submit = tnow;
-    if (tt_n == 0)
-      for (int r = 0; r < TT; ++r) { (void)hipEventCreate(&tt_b[r]); (void)hipEventCreate(&tt_e[r]); (void)hipEventCreate(&tt_tb[r]); (void)hipEventCreate(&tt_te[r]); }
-    if (tt_n >= TT) {   // the launches before those that may be in flight are complete: ring slots (n-8) and (n-9)
-      const int r2 = (int)((tt_n - 8) % TT), r3 = (int)((tt_n - 9) % TT);
-      float busy = 0, idle = 0;
-      int &tt_late = td_.late;
-      float &tt_max = td_.max_idle;
-      if (hipEventElapsedTime(&busy, tt_b[r2], tt_e[r2]) == hipSuccess && hipEventElapsedTime(&idle, tt_e[r3], tt_b[r2]) == hipSuccess) {
-        tt_busy += busy; tt_idle += idle;
-        tt_late += idle > 0.05f ? 1 : 0;
-        tt_max = std::max(tt_max, idle);
-      }
-      std::string &tt_pat = td_.pat;
-      tt_pat += (char)('0' + tt_np[r2]);
-      if (idle > 0.05f) tt_pat += idle > 0.3f ? 'I' : 'i';
-      if (tt_n % 200 == 0) { std::fprintf(stderr, "[spvo]   pairs per launch (i / I: the stream stood idle > 50 / > 300 us in front of it): %s\n", tt_pat.c_str()); tt_pat.clear(); }
-      if (trace_lo > 1) {   // device-side times of launch (tt_n - 8), relative to the first trace line's moment
-        hipEvent_t &base = td_.base;
-        double &base_host = td_.base_host;
-        if (!base && g_diag.launches >= trace_lo - 8) { (void)hipEventCreate(&base); (void)hipEventRecord(base, c->stream_t); (void)hipEventSynchronize(base); base_host = diag_now_us(); }
-        float b0 = 0, e0 = 0, tb0 = 0, te0 = 0;
-        if (base && g_diag.launches - 8 >= trace_lo && g_diag.launches - 8 < trace_lo + 80 && hipEventElapsedTime(&b0, base, tt_b[r2]) == hipSuccess &&
-            hipEventElapsedTime(&e0, base, tt_e[r2]) == hipSuccess && hipEventElapsedTime(&tb0, base, tt_tb[r2]) == hipSuccess && hipEventElapsedTime(&te0, base, tt_te[r2]) == hipSuccess)
-          std::fprintf(stderr, "G launch %ld (%d pairs): trunk %.0f .. %.0f, tail %.0f .. %.0f (host clock)\n", g_diag.launches - 8, tt_np[r2], base_host + b0 * 1e3, base_host + e0 * 1e3,
-                       base_host + tb0 * 1e3, base_host + te0 * 1e3);
-      }
-      float tail = 0, lag = 0;
-      if (hipEventElapsedTime(&tail, tt_tb[r2], tt_te[r2]) == hipSuccess && hipEventElapsedTime(&lag, tt_e[r2], tt_te[r2]) == hipSuccess) { tt_tail += tail; tt_lag += lag; }
-      if (tt_n % 200 == 0) {
-        std::fprintf(stderr, "[spvo] trunk timing over 200 launches (%.0f pairs): network stream busy %.1f us, idle %.1f us per launch (%d gaps above 50 us, longest %.0f us)\n",
-                     tt_pairs, tt_busy * 1e3 / 200, tt_idle * 1e3 / 200, tt_late, tt_max * 1e3);
-        std::fprintf(stderr, "[spvo]   NMS continuations driven by the host so far: %lld\n", c->stages[stage_id(c, "nms_redo")].calls);
-        std::fprintf(stderr, "[spvo]   tail stream: %.1f us per launch from its first kernel to its last, which ends %.1f us behind the trunk\n", tt_tail * 1e3 / 200, tt_lag * 1e3 / 200);
-        tt_tail = tt_lag = 0;
-        std::fprintf(stderr, "[spvo]   host: longest interval between launches %.0f us, longest wait for a tail %.0f us, for a solve %.0f us, matches not served from the cache %d; "
-                             "launches that found the network stream idle %d, mean submissions in flight at launch %.2f\n",
-                     g_diag.max_interval, g_diag.max_tail_wait, g_diag.max_solve_wait, g_diag.match_miss, g_diag.late, g_diag.depth_sum / 200.0);
-        g_diag.max_interval = g_diag.max_tail_wait = g_diag.max_solve_wait = 0; g_diag.match_miss = 0; g_diag.late = 0; g_diag.depth_sum = 0;
-        tt_busy = tt_idle = tt_pairs = 0; tt_late = 0; tt_max = 0;
-      }
-    }
-    tt_pairs += n;
-    tt_np[tt_n % TT] = n;
-    (void)hipEventRecord(tt_b[tt_n % TT], c->stream);
-  }
-  hipEvent_t det_e0 = nullptr;
-  const bool prof_detect = c->prof && (c->prof_only < 0 || c->prof_only == stage_id(c, "detect"));
-  if (prof_detect) { det_e0 = get_event(c); (void)hipEventRecord(det_e0, c->stream); }
+// phase B: the trunk of the group's `n` pairs (2 or 4 images per launch) on the network stream, and its heads where they stay there
+static int launch_trunk(spvo_ctx *c, PendingDetect *const *mem, int n, bool heads_on_net) {
+  const int tring = mem[0]->ring, batch = 2 * n;
+  bool any_res = false;
+  for (int m = 0; m < n; ++m) any_res = any_res || mem[m]->early_res;
   int rc;
-  const int hon = tuning("heads_on_net", -1);
-  const bool heads_on_net = hon < 0 ? c->heads_on_net : hon != 0;
-  bool any_res0 = false;
-  for (int m = 0; m < n; ++m) any_res0 = any_res0 || mem[m]->early_res;
   {
     ScopedStage net(c, stage_id(c, "net"));
     // launch segment T: the group's trunk (and its heads where they stay on the network stream) -- not for a group whose first layer also
     // preprocesses (its arguments are the caller's image pointers) or whose resized images leave through the tail stream in between
-    if (!mem[0]->pre_pending && !any_res0) seg_begin(c, &c->seg_T[tring][n - 1], c->stream);
+    if (!mem[0]->pre_pending && !any_res) seg_begin(c, &c->seg_T[tring][n - 1], c->stream);
     rc = mem[0]->pre_pending ? launch_first_pre(c, mem, n, c->stream) : run_ops(c, batch, 0, std::min<size_t>(1, c->head_start), c->stream);
     for (int m = 0; m < n; ++m) mem[m]->pre_pending = false;
     // The resized images leave for their sets' pinned mirrors UNDER the network: a copy kernel (16 bytes per lane, no SDMA engine involved)
     // on the TAIL stream behind the FIRST layer -- beside it (conv1a is bound by its 217 MB of stores) the copy made that layer 54 us
     // instead of 37 -- i.e. beside conv1b, which leaves 12 CUs free and does not notice
-    bool any_res = false;
-    for (int m = 0; m < n; ++m) any_res = any_res || mem[m]->early_res;
     if (!rc && any_res) {
       HIP_TRY(c, hipEventRecord(c->ev_pre[tring], c->stream));
       HIP_TRY(c, hipStreamWaitEvent(c->stream_t, c->ev_pre[tring], 0));
@@ -695,21 +579,115 @@ static int launch_group_body(spvo_ctx *c) {
     }
     if (!rc) rc = run_ops(c, batch, std::min<size_t>(1, c->head_start), c->head_start, c->stream);
   }
-  if (rc) { (void)seg_end(c); c->cur_ring = 0; return rc; }
-  c->last_batch = batch;
+  if (!rc) c->last_batch = batch;
   // The heads (2.2 GFLOP: the one heavy piece behind the trunk): on the network stream, in front of the next pair's trunk, when the
   // trunk is made of persistent one-workgroup-per-CU launches (VGG fp32: beside the next pair's conv1b they would have 12 CUs, the
   // tail would finish late and the network stream idle 50-70 us per pair: 1257-1265 against 1308 frames/s); on the tail stream
   // otherwise, where the overlap pays (sp_squeeze fp32 1286 against 1248 frames/s, INT8 sp_mbv1 2360 against 2237).  The plan
   // loader decides (spvo_ctx::heads_on_net); tuning "heads_on_net" = 0 / 1 overrides (measurements).
-  if (heads_on_net) {
-    rc = run_ops(c, batch, c->head_start, c->ops.size(), c->stream);
-    if (rc) { (void)seg_end(c); c->cur_ring = 0; return rc; }
-  }
-  if ((rc = seg_end(c))) { c->cur_ring = 0; return rc; }   // segment T goes out here: one graph launch, or its kernels one by one
-  if (trunk_timing) (void)hipEventRecord(tt_e[tt_n % TT], c->stream);
+  if (!rc && heads_on_net) rc = run_ops(c, batch, c->head_start, c->ops.size(), c->stream);
+  { const int rce = seg_end(c); if (!rc) rc = rce; }   // segment T goes out here: one graph launch, or its kernels one by one
+  if (rc) return rc;
+  if (c->trunk_timing) c->tdiag.trunk_end(c->stream);
   for (int m = 0; m < n; ++m) HIP_TRY(c, hipEventRecord(c->ev_net[mem[m]->ring], c->stream));
   c->last_launch_ring = mem[n - 1]->ring;
+  return SPVO_OK;
+}
+
+// the heads on the (first pair's) tail stream, reading this group's ring buffers; a second pair on the other tail stream waits for them
+static int launch_heads_on_tail(spvo_ctx *c, PendingDetect *const *mem, int n, const hipStream_t tstreams[2]) {
+  const int tring = mem[0]->ring;
+  hipStream_t ts0 = tstreams[mem[0]->ts];
+  seg_begin(c, &c->seg_H[tring][n - 1], ts0);   // launch segment H: the heads
+  int rc = run_ops(c, 2 * n, c->head_start, c->ops.size(), ts0);
+  { const int rce = seg_end(c); if (!rc) rc = rce; }
+  if (!rc && n == 2 && mem[1]->ts != mem[0]->ts) {
+    HIP_TRY(c, hipEventRecord(c->ev_heads[tring], ts0));
+    HIP_TRY(c, hipStreamWaitEvent(tstreams[mem[1]->ts], c->ev_heads[tring], 0));
+  }
+  return rc;
+}
+
+// phase C for one pair, on its tail stream `tsm`: segment A up to ev_feat, segment B (the matches) up to ev_tail, the descriptor mirror.
+// det_e0 != NULL: the "detect" stage is timed from that event; `ts_next`: the tail stream of the group's next pair, or NULL
+static int launch_pair_tail(spvo_ctx *c, PendingDetect &pd, int tring, hipStream_t tsm, hipEvent_t &det_e0, hipStream_t ts_next) {
+  const Tensor &td = c->tensors[c->t_det];
+  const int ring = pd.ring, slots[2] = {pd.slot_l, pd.slot_r};
+  pd.tring = tring;
+  const NmsPair np = nms_pair(c, ring);
+  c->post = tsm;
+  c->ms_set = pd.ts;
+  // launch segment A: heat map, NMS rounds + finish, rank, write, sampling -- eight dependent kernels up to ev_feat
+  seg_begin(c, &c->seg_A[ring], tsm);
+  {
+    // heat map + threshold + candidate list in one kernel; the counter block of this set was
+    // zeroed by the previous submission's last NMS kernel (or at allocation)
+    ScopedStage sh(c, stage_id(c, "heatmap"));
+    hipLaunchKernelGGL(heatmap_nms_kernel, dim3((c->Wc + 63) / 64, (c->Hc + 3) / 4, 2), dim3(256), 0, c->post, td.dr[tring] + (size_t)pd.img0 * td.per_image, c->d_heat_r[ring],
+                       c->Hc, c->Wc, td.hp, td.wp, c->cfg.conf_thresh, np);
+    HIP_TRY(c, hipGetLastError());
+  }
+  int rc;
+  {
+    ScopedStage sn(c, stage_id(c, "nms"));
+    rc = launch_nms_rounds(c, 2, np, ring, c->nms_first, c->d_counters_all + (size_t)(((ring + c->tail_streams) % RING) * 2) * NMS_COUNTER_INTS);
+  }
+  if (!rc) rc = enqueue_sample(c, slots, np, ring, tring, pd.img0);
+  { const int rce = seg_end(c); if (!rc) rc = rce; }
+  // Keypoints, counts and descriptors are final here: spvo_detect_wait / _collect waits for THIS point (ev_feat); the matches enqueued
+  // behind it are waited for where they are asked for (spvo_match_slots, ev_tail).
+  if (!rc) rc = dev_check(c, hipEventRecord(c->ev_feat[ring], tsm), "hipEventRecord");
+  if (!rc && c->prematch) {
+    // (two tail streams: the temporal partner's features come from the submission before, on the other stream)
+    if (c->tail_streams == 2 && pd.prev_l >= 0) HIP_TRY(c, hipStreamWaitEvent(tsm, c->ev_feat[(ring + RING - 1) % RING], 0));
+    // launch segment B: the pair's two matches (distance GEMM + merge; the fp8 shortlist's conversions and re-rank)
+    seg_begin(c, &c->seg_B[ring], tsm);
+    rc = enqueue_prematch(c, pd.slot_l, pd.slot_r, pd.prev_l, ring);
+    { const int rce = seg_end(c); if (!rc) rc = rce; }
+  }
+  if (!rc && det_e0) {   // "detect" spans both streams: first kernel on `stream` .. last kernel on the tail stream
+    hipEvent_t e1 = get_event(c);
+    (void)hipEventRecord(e1, tsm);
+    c->pending.push_back({stage_id(c, "detect"), det_e0, e1});
+    det_e0 = nullptr;
+    if (ts_next) { det_e0 = get_event(c); (void)hipEventRecord(det_e0, ts_next); }   // (an event is timed once)
+  }
+  if (!rc) rc = dev_check(c, hipEventRecord(c->ev_tail[ring], tsm), "hipEventRecord");
+  // The descriptors a host-image submission takes back (extras bit 1: 2 x 1 MB) leave for the set's pinned mirror BEHIND the
+  // matches, on the tail stream (a stream of their own had them share a hardware queue with the network stream in processes that had
+  // created and destroyed contexts before -- the runtime deals streams onto four queues -- and bench.py's look-ahead leg fell from
+  // 1230 to 1070 frames/s while the same calls from tools/sync_leg.py ran at 1260): written by the sampling kernel itself they
+  // made it 40 us instead of 4 in front of ev_feat; beside the matches the copy kernel (44 us of PCIe writes) made the distance GEMM
+  // 55 us instead of 20.  ev_copy = they have arrived (spvo_detect_mirrors_wait; spvo_detect_collect waits for it itself).
+  if (!rc && (pd.extras & 2)) {
+    rc = enqueue_desc_mirror(c, slots, ring, tsm);
+    if (!rc) HIP_TRY(c, hipEventRecord(c->ev_copy[ring], tsm));
+  }
+  if (!rc) pd.launched = true;
+  return rc;
+}
+
+// Phases B (the trunk of the held pairs: one or two) and C (each pair's tail), enqueued without a host round trip: the trunk on the
+// network stream; the tail stream(s) behind ev_net; the heads there unless they went with the trunk; then pair by pair the tail.
+// A failure returns at once: launch_group puts the context's launch state (cur_ring, post, ms_set) and the queue right.
+static int launch_group_body(spvo_ctx *c) {
+  const int n = c->held;
+  if (n <= 0) return SPVO_OK;
+  if (n > 2 || (int)c->pendq.size() < n) return fail(c, SPVO_ERR_STATE, "internal: %d held submissions, %zu in flight", n, c->pendq.size());
+  c->held = 0;
+  PendingDetect *mem[2] = {&c->pendq[c->pendq.size() - n], n == 2 ? &c->pendq[c->pendq.size() - 1] : nullptr};
+  const int tring = mem[0]->ring;      // the set whose network outputs (det, desc, head inputs) hold all images of the group
+  c->cur_ring = tring;
+  c->post = c->stream;
+  if (c->inject_launch_failure > 0 && ++c->launch_count == c->inject_launch_failure)   // tests of the error path (tuning "inject_launch_failure")
+    return fail(c, SPVO_ERR_DEVICE, "injected launch failure (diagnostic switch)");
+  if (c->trunk_timing) c->tdiag.launch_begin(c, n);
+  hipEvent_t det_e0 = nullptr;
+  if (c->prof && (c->prof_only < 0 || c->prof_only == stage_id(c, "detect"))) { det_e0 = get_event(c); (void)hipEventRecord(det_e0, c->stream); }
+  const int hon = tuning("heads_on_net", -1);
+  const bool heads_on_net = hon < 0 ? c->heads_on_net : hon != 0;
+  int rc = launch_trunk(c, mem, n, heads_on_net);
+  if (rc) return rc;
   // Tail streams: one, or two that consecutive submissions alternate between by the parity of their set (tuning "tail_streams" = 2: for
   // engines whose network is shorter than a pair's chain of ~10 dependent tail kernels -- FP16 / INT8 -- that chain, one pair after the
   // other on one stream, is the frame loop's cycle time: config 3 5670 -> 6490 frames/s).  It pays only when the second stream gets a
@@ -718,83 +696,22 @@ static int launch_group_body(spvo_ctx *c) {
   // environment; FP32 engines lose with it (more small kernels beside the trunk's persistent launches).  What crosses
   // from one submission's tail to the next one's: the features the temporal match reads (ev_feat of the submission before) and the clean
   // NMS counter block, which a tail hands to the next submission ON ITS OWN STREAM (two sets ahead with two streams).
-  hipStream_t tstreams[2] = {c->stream_t, c->tail_streams == 2 ? c->stream_tb : c->stream_t};
+  const hipStream_t tstreams[2] = {c->stream_t, c->tail_streams == 2 ? c->stream_tb : c->stream_t};
   for (int m = 0; m < n; ++m) mem[m]->ts = c->tail_streams == 2 ? (mem[m]->ring & 1) : 0;
   hipStream_t ts0 = tstreams[mem[0]->ts];
   HIP_TRY(c, hipStreamWaitEvent(ts0, c->ev_net[tring], 0));
   if (n == 2 && mem[1]->ts != mem[0]->ts) HIP_TRY(c, hipStreamWaitEvent(tstreams[mem[1]->ts], c->ev_net[tring], 0));
-  if (trunk_timing) (void)hipEventRecord(tt_tb[tt_n % TT], ts0);
+  if (c->trunk_timing) c->tdiag.tail_begin(ts0);
   c->post = ts0;
-  if (!heads_on_net) {
-    seg_begin(c, &c->seg_H[tring][n - 1], ts0);   // launch segment H: the heads
-    rc = run_ops(c, batch, c->head_start, c->ops.size(), ts0);   // heads: on the (first pair's) tail stream, reading this group's ring buffers
-    { const int rce = seg_end(c); if (!rc) rc = rce; }
-    if (!rc && n == 2 && mem[1]->ts != mem[0]->ts) {
-      HIP_TRY(c, hipEventRecord(c->ev_heads[tring], ts0));
-      HIP_TRY(c, hipStreamWaitEvent(tstreams[mem[1]->ts], c->ev_heads[tring], 0));
-    }
-  }
+  if (!heads_on_net && (rc = launch_heads_on_tail(c, mem, n, tstreams))) return rc;
   c->cur_ring = 0;
-  if (rc) { c->post = c->stream; return rc; }
   // ---- phase C: each pair's tail, in submission order (the second pair's temporal match reads the first pair's features)
-  for (int m = 0; m < n && !rc; ++m) {
-    PendingDetect &pd = *mem[m];
-    const int ring = pd.ring, slots[2] = {pd.slot_l, pd.slot_r};
-    pd.tring = tring;
-    const NmsPair np = nms_pair(c, ring);
-    hipStream_t tsm = tstreams[pd.ts];
-    c->post = tsm;
-    c->ms_set = pd.ts;
-    // launch segment A: heat map, NMS rounds + finish, rank, write, sampling -- eight dependent kernels up to ev_feat
-    seg_begin(c, &c->seg_A[ring], tsm);
-    {
-      // heat map + threshold + candidate list in one kernel; the counter block of this set was
-      // zeroed by the previous submission's last NMS kernel (or at allocation)
-      ScopedStage sh(c, stage_id(c, "heatmap"));
-      hipLaunchKernelGGL(heatmap_nms_kernel, dim3((c->Wc + 63) / 64, (c->Hc + 3) / 4, 2), dim3(256), 0, c->post, td.dr[tring] + (size_t)pd.img0 * td.per_image, c->d_heat_r[ring],
-                         c->Hc, c->Wc, td.hp, td.wp, c->cfg.conf_thresh, np);
-      HIP_TRY(c, hipGetLastError());
-    }
-    {
-      ScopedStage sn(c, stage_id(c, "nms"));
-      rc = launch_nms_rounds(c, 2, np, ring, c->nms_first, c->d_counters_all + (size_t)(((ring + c->tail_streams) % RING) * 2) * NMS_COUNTER_INTS);
-    }
-    if (!rc) rc = enqueue_sample(c, slots, np, ring, tring, pd.img0);
-    { const int rce = seg_end(c); if (!rc) rc = rce; }
-    // Keypoints, counts and descriptors are final here: spvo_detect_wait / _collect waits for THIS point (ev_feat); the matches enqueued
-    // behind it are waited for where they are asked for (spvo_match_slots, ev_tail).
-    if (!rc) rc = hipEventRecord(c->ev_feat[ring], tsm) == hipSuccess ? SPVO_OK : fail(c, SPVO_ERR_DEVICE, "hipEventRecord failed");
-    if (!rc && c->prematch) {
-      // (two tail streams: the temporal partner's features come from the submission before, on the other stream)
-      if (c->tail_streams == 2 && pd.prev_l >= 0) HIP_TRY(c, hipStreamWaitEvent(tsm, c->ev_feat[(ring + RING - 1) % RING], 0));
-      // launch segment B: the pair's two matches (distance GEMM + merge; the fp8 shortlist's conversions and re-rank)
-      seg_begin(c, &c->seg_B[ring], tsm);
-      rc = enqueue_prematch(c, pd.slot_l, pd.slot_r, pd.prev_l, ring);
-      { const int rce = seg_end(c); if (!rc) rc = rce; }
-    }
-    if (!rc && prof_detect) {   // "detect" spans both streams: first kernel on `stream` .. last kernel on the tail stream
-      hipEvent_t e1 = get_event(c);
-      (void)hipEventRecord(e1, tsm);
-      c->pending.push_back({stage_id(c, "detect"), det_e0, e1});
-      if (m + 1 < n) { det_e0 = get_event(c); (void)hipEventRecord(det_e0, tstreams[mem[m + 1]->ts]); }   // (an event is timed once)
-    }
-    if (!rc) rc = (hipEventRecord(c->ev_tail[ring], tsm) == hipSuccess) ? SPVO_OK : fail(c, SPVO_ERR_DEVICE, "hipEventRecord failed");
-    // The descriptors a host-image submission takes back (extras bit 1: 2 x 1 MB) leave for the set's pinned mirror BEHIND the
-    // matches, on the tail stream (a stream of their own had them share a hardware queue with the network stream in processes that had
-    // created and destroyed contexts before -- the runtime deals streams onto four queues -- and bench.py's look-ahead leg fell from
-    // 1230 to 1070 frames/s while the same calls from tools/sync_leg.py ran at 1260): written by the sampling kernel itself they
-    // made it 40 us instead of 4 in front of ev_feat; beside the matches the copy kernel (44 us of PCIe writes) made the distance GEMM
-    // 55 us instead of 20.  ev_copy = they have arrived (spvo_detect_mirrors_wait; spvo_detect_collect waits for it itself).
-    if (!rc && (pd.extras & 2)) {
-      rc = enqueue_desc_mirror(c, slots, ring, tsm);
-      if (!rc) HIP_TRY(c, hipEventRecord(c->ev_copy[ring], tsm));
-    }
-    pd.launched = true;
-  }
-  if (trunk_timing) { (void)hipEventRecord(tt_te[tt_n % TT], tstreams[mem[n - 1]->ts]); ++tt_n; }
+  for (int m = 0; m < n; ++m)
+    if ((rc = launch_pair_tail(c, *mem[m], tring, tstreams[mem[m]->ts], det_e0, m + 1 < n ? tstreams[mem[m + 1]->ts] : nullptr))) return rc;
+  if (c->trunk_timing) c->tdiag.tail_end(tstreams[mem[n - 1]->ts]);
   c->post = c->stream;
   c->ms_set = 0;
-  return rc;
+  return SPVO_OK;
 }
 
 // completes the OLDEST submission
@@ -844,15 +761,15 @@ static int detect_wait(spvo_ctx *c, double P_l[12], double P_r[12], spvo_feature
   int rc = SPVO_OK;
   if (extras) {
     if ((rc = copy_extras())) { c->post = c->stream; c->ms_set = 0; return rc; }
-    rc = hipStreamSynchronize(tsw) == hipSuccess ? SPVO_OK : fail(c, SPVO_ERR_DEVICE, "stream synchronisation failed");
+    rc = dev_check(c, hipStreamSynchronize(tsw), "stream synchronisation");
   } else {
     // only this submission's tail: a younger one may be queued behind it on both streams
     const double tw0 = diag_now_us();
-    rc = wait_event(c->ev_feat[pd.ring]) == hipSuccess ? SPVO_OK : fail(c, SPVO_ERR_DEVICE, "event synchronisation failed");
+    rc = dev_check(c, wait_event(c->ev_feat[pd.ring]), "event synchronisation");
     g_diag.max_tail_wait = std::max(g_diag.max_tail_wait, diag_now_us() - tw0);
     g_diag.iv_tail += diag_now_us() - tw0;
   }
-  if (!rc && pd.early_res) rc = wait_event(c->ev_res[pd.ring]) == hipSuccess ? SPVO_OK : fail(c, SPVO_ERR_DEVICE, "event synchronisation failed");   // the resized images: they left under the network (copy kernel on the tail stream)
+  if (!rc && pd.early_res) rc = dev_check(c, wait_event(c->ev_res[pd.ring]), "event synchronisation");   // the resized images: they left under the network (copy kernel on the tail stream)
   bool redone = false;
   const NmsPair np = nms_pair(c, pd.ring);
   if (!rc) rc = nms_settle(c, 2, np, pd.ring, &redone);
@@ -863,7 +780,7 @@ static int detect_wait(spvo_ctx *c, double P_l[12], double P_r[12], spvo_feature
     if (!rc && redone && (pd.extras & 2)) rc = enqueue_desc_mirror(c, slots, pd.ring, c->post);
     if (!rc && c->prematch) rc = enqueue_prematch(c, pd.slot_l, pd.slot_r, pd.prev_l, pd.ring);
     if (!rc && extras) rc = copy_extras();
-    if (!rc) rc = hipStreamSynchronize(tsw) == hipSuccess ? SPVO_OK : fail(c, SPVO_ERR_DEVICE, "stream synchronisation failed");
+    if (!rc) rc = dev_check(c, hipStreamSynchronize(tsw), "stream synchronisation");
     if (redone)
       for (auto &q : c->pendq)
         if (q.prev_l == pd.slot_l) q.rematch = true;   // it matched against keypoints that have just been replaced
@@ -896,9 +813,8 @@ static int detect_wait(spvo_ctx *c, double P_l[12], double P_r[12], spvo_feature
       mirrors->resized[i] = (pd.extras & 1) ? c->h_resized_r[pd.ring] + (size_t)i * c->H * c->W : nullptr;
       mirrors->token = pd.ring;
     }
-  const CropGeom g{pd.g.row_off, pd.g.col_off, pd.g.crop_rows, pd.g.crop_cols, pd.g.scale};
-  if (P_l) fix_projection(P_l, g, pd.rows, pd.cols, c->cfg.bug_compat_p);
-  if (P_r) fix_projection(P_r, g, pd.rows, pd.cols, c->cfg.bug_compat_p);
+  if (P_l) fix_projection(P_l, pd.g, pd.rows, pd.cols, c->cfg.bug_compat_p);
+  if (P_r) fix_projection(P_r, pd.g, pd.rows, pd.cols, c->cfg.bug_compat_p);
   return SPVO_OK;
 }
 
@@ -942,15 +858,11 @@ static int detect_common(spvo_ctx *c, const uint8_t *d_l, const uint8_t *d_r, in
 int spvo_detect(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, double P_l[12], double P_r[12],
                 int slot_l, int slot_r, spvo_features *out_l, spvo_features *out_r, uint8_t *resized_l, uint8_t *resized_r) {
   if (!c || !img_l || !img_r || !P_l || !P_r || rows <= 0 || cols <= 0 || stride < (size_t)cols) return fail(c, SPVO_ERR_INVALID, "bad argument");
-  if (!c->pendq.empty()) return fail(c, SPVO_ERR_STATE, "detector submissions are in flight: complete them with spvo_detect_wait first");
+  if (int rc = require_idle(c)) return rc;
   if (!c->weights) return fail(c, SPVO_ERR_STATE, "no weights loaded");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   const size_t bytes = (size_t)(rows - 1) * stride + cols;   // what is the caller's of a strided view: not the last row's padding
-  if (bytes > c->img_cap) {
-    for (int i = 0; i < 2; ++i) { if (c->d_img[i]) (void)hipFree(c->d_img[i]); c->d_img[i] = nullptr; }
-    for (int i = 0; i < 2; ++i) { int rc = dev_alloc(c, &c->d_img[i], bytes, false); if (rc) return rc; }
-    c->img_cap = bytes;
-  }
+  if (int rc = ensure_img_staging(c, bytes)) return rc;
   HIP_TRY(c, hipMemcpyAsync(c->d_img[0], img_l, bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipMemcpyAsync(c->d_img[1], img_r, bytes, hipMemcpyHostToDevice, c->stream));
   return detect_common(c, c->d_img[0], c->d_img[1], rows, cols, stride, P_l, P_r, slot_l, slot_r, out_l, out_r, resized_l, resized_r);
@@ -959,7 +871,7 @@ int spvo_detect(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r, int row
 int spvo_detect_dev(spvo_ctx *c, const void *d_img_l, const void *d_img_r, int rows, int cols, size_t stride, double P_l[12], double P_r[12],
                     int slot_l, int slot_r, spvo_features *out_l, spvo_features *out_r) {
   if (!c || !d_img_l || !d_img_r || !P_l || !P_r || rows <= 0 || cols <= 0 || stride < (size_t)cols) return fail(c, SPVO_ERR_INVALID, "bad argument");
-  if (!c->pendq.empty()) return fail(c, SPVO_ERR_STATE, "detector submissions are in flight: complete them with spvo_detect_wait first");
+  if (int rc = require_idle(c)) return rc;
   if (!c->weights) return fail(c, SPVO_ERR_STATE, "no weights loaded");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   return detect_common(c, (const uint8_t *)d_img_l, (const uint8_t *)d_img_r, rows, cols, stride, P_l, P_r, slot_l, slot_r, out_l, out_r, nullptr, nullptr);
@@ -1002,7 +914,7 @@ int spvo_detect_mirrors_wait(spvo_ctx *c, const spvo_detect_mirrors *m) {
   if (!c || !m || m->token < 0 || m->token >= RING) return fail(c, SPVO_ERR_INVALID, "bad argument");
   if (!m->desc[0] && !m->desc[1]) return SPVO_OK;
   HIP_TRY(c, hipSetDevice(c->cfg.device));
-  return wait_event(c->ev_copy[m->token]) == hipSuccess ? SPVO_OK : fail(c, SPVO_ERR_DEVICE, "event synchronisation failed");
+  return dev_check(c, wait_event(c->ev_copy[m->token]), "event synchronisation");
 }
 
 int spvo_detect_collect_mirrors(spvo_ctx *c, double P_l[12], double P_r[12], spvo_detect_mirrors *out) {
@@ -1010,382 +922,6 @@ int spvo_detect_collect_mirrors(spvo_ctx *c, double P_l[12], double P_r[12], spv
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   std::memset(out, 0, sizeof *out);
   return detect_wait(c, P_l, P_r, nullptr, nullptr, nullptr, nullptr, out);
-}
-
-// ---------------------------------------------------------------- ORB (classic front end, orb.hip.h)
-namespace {
-uint32_t host_hash32(uint32_t x) { x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16; return x; }
-// the 256 test pairs: isotropic Gaussian of the original BRIEF (sigma = patch / 5), fixed seed, rounded, kept inside the patch
-// (the same construction as oracle/cpu/orb_cpu.inc; tests/test_gpu_orb.py compares the two tables)
-void orb_host_tables(std::vector<float> &pattern, float taps[7], std::vector<signed char> &disc) {
-  constexpr int PATCH = 31, HALF = ORB_HALF;
-  pattern.resize(1024);
-  uint32_t state = 0x9E3779B9u;
-  auto uni = [&]() { state = host_hash32(state + 0x6D2B79F5u); return ((state >> 8) + 0.5f) / 16777216.0f; };
-  auto gauss = [&]() { const float u1 = uni(), u2 = uni(); return std::sqrt(-2.0f * std::log(u1)) * std::cos(6.2831853f * u2); };
-  for (int i = 0; i < 1024; ++i) {
-    float v = gauss() * (PATCH / 5.0f);
-    v = std::min(std::max(v, -(float)(HALF - 2)), (float)(HALF - 2));
-    pattern[i] = std::round(v);
-  }
-  float sum = 0;
-  for (int i = 0; i < 7; ++i) { taps[i] = std::exp(-0.5f * (i - 3) * (i - 3) / 4.0f); sum += taps[i]; }
-  for (int i = 0; i < 7; ++i) taps[i] /= sum;
-  disc.clear();
-  for (int dy = -HALF; dy <= HALF; ++dy) {
-    const int lim = (int)std::floor(std::sqrt((double)HALF * HALF - dy * dy));
-    for (int dx = -lim; dx <= lim; ++dx) { disc.push_back((signed char)dx); disc.push_back((signed char)dy); }
-  }
-}
-// the descriptor's tables on the device (pattern, taps, disc), uploaded once per context
-int orb_ensure_tables(spvo_ctx *c) {
-  auto &o = c->orb;
-  if (o.pattern) return SPVO_OK;
-  std::vector<float> pat;
-  std::vector<signed char> disc;
-  float taps[7];
-  orb_host_tables(pat, taps, disc);
-  int rc;
-  if ((rc = dev_alloc(c, &o.pattern, 1024)) || (rc = dev_alloc(c, &o.taps, 8)) || (rc = dev_alloc(c, &o.disc, disc.size()))) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipMemcpy(o.pattern, pat.data(), 1024 * 4, hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(o.taps, taps, 7 * 4, hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(o.disc, disc.data(), disc.size(), hipMemcpyHostToDevice));
-  return SPVO_OK;
-}
-}  // namespace
-
-int spvo_orb_tables(float *pattern, float *taps) {
-  std::vector<float> p;
-  std::vector<signed char> d;
-  float t[7];
-  orb_host_tables(p, t, d);
-  if (pattern) std::memcpy(pattern, p.data(), 1024 * sizeof(float));
-  if (taps) std::memcpy(taps, t, sizeof t);
-  return SPVO_OK;
-}
-
-int spvo_orb_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride, int nfeatures, spvo_orb_keypoint *kps, uint8_t *desc, int cap, int *n_out) {
-  if (!c || !img || !n_out || rows <= 0 || cols <= 0 || stride < (size_t)cols || nfeatures <= 0 || cap < 0 || (cap > 0 && (!kps || !desc)))
-    return fail(c, SPVO_ERR_INVALID, "bad argument");
-  static_assert(sizeof(spvo_orb_keypoint) == sizeof(OrbKeypoint), "keypoint records differ");
-  HIP_TRY(c, hipSetDevice(c->cfg.device));
-  *n_out = 0;
-  hipStream_t st = c->stream2;
-  auto &o = c->orb;
-  // ---- level geometry and per-level quota (the reference's parameters: 8 levels, scale 1.2)
-  constexpr float SCALE = 1.2f;
-  int ph[ORB_LEVELS], pw[ORB_LEVELS], want[ORB_LEVELS];
-  float lscale[ORB_LEVELS];
-  size_t off[ORB_LEVELS + 1];
-  {
-    float scale = 1.f;
-    const float f = 1.0f / SCALE;
-    float n_level = nfeatures * (1 - f) / (1 - std::pow(f, (float)ORB_LEVELS));
-    int assigned = 0;
-    off[0] = 0;
-    for (int l = 0; l < ORB_LEVELS; ++l, scale *= SCALE) {
-      ph[l] = (int)std::lround(rows / scale); pw[l] = (int)std::lround(cols / scale);
-      lscale[l] = scale;
-      want[l] = l == ORB_LEVELS - 1 ? std::max(nfeatures - assigned, 0) : (int)std::lround(n_level);
-      assigned += want[l];
-      n_level *= f;
-      off[l + 1] = off[l] + (((size_t)ph[l] * pw[l] + 255) & ~(size_t)255);
-    }
-  }
-  const int surv_cap = (rows / 2 + 1) * (cols / 2 + 1);   // 3x3 suppression: at most one survivor per 2x2 block
-  const int kp_cap = nfeatures;
-  // what THIS image needs: the pyramid (all levels side by side), one key / rank entry per possible survivor of every level, the
-  // resize tables of levels 1..7.  All three depend on rows and cols separately (a 100 x 1500 image needs longer tables than a
-  // 400 x 400 one although it has fewer pixels), so each is compared with what is allocated.
-  size_t need_keys = 0, need_tab = 0;
-  for (int l = 0; l < ORB_LEVELS; ++l) {
-    need_keys += (size_t)std::min(surv_cap, (ph[l] / 2 + 1) * (pw[l] / 2 + 1));
-    if (l > 0) need_tab += (size_t)3 * (pw[l] + ph[l]);
-  }
-  const size_t need_pyr = off[ORB_LEVELS] + 256;
-  if (need_pyr > o.pyr_cap || need_keys > o.key_cap || need_tab > o.tab_cap || kp_cap > o.kp_cap) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    for (void *p : {(void *)o.im, (void *)o.score, (void *)o.blur, (void *)o.tmp, (void *)o.keys, (void *)o.rank, (void *)o.out_xy, (void *)o.counters, (void *)o.tab,
-                    (void *)o.kps, (void *)o.desc}) if (p) (void)hipFree(p);
-    o.im = o.score = o.blur = nullptr; o.tmp = nullptr; o.keys = nullptr; o.rank = o.out_xy = o.counters = o.tab = nullptr; o.kps = nullptr; o.desc = nullptr;
-    const size_t pyr = std::max(need_pyr, o.pyr_cap), kall = std::max(need_keys, o.key_cap), tabn = std::max(need_tab, o.tab_cap);
-    const int kpn = std::max(kp_cap, o.kp_cap);
-    o.pyr_cap = o.key_cap = o.tab_cap = 0; o.kp_cap = 0;   // a failed allocation below leaves a context that spvo_destroy and a later call can still handle
-    int rc;
-    if ((rc = dev_alloc(c, &o.im, pyr)) || (rc = dev_alloc(c, &o.score, pyr)) || (rc = dev_alloc(c, &o.blur, pyr)) || (rc = dev_alloc(c, &o.tmp, pyr)) ||
-        (rc = dev_alloc(c, &o.keys, kall)) || (rc = dev_alloc(c, &o.rank, kall)) || (rc = dev_alloc(c, &o.out_xy, 2 * kall)) ||
-        (rc = dev_alloc(c, &o.counters, (size_t)ORB_LEVELS * NMS_COUNTER_INTS)) || (rc = dev_alloc(c, &o.tab, tabn)) || (rc = dev_alloc(c, &o.kps, kpn)) ||
-        (rc = dev_alloc(c, &o.desc, (size_t)kpn * 32)))
-      return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
-    o.pyr_cap = pyr; o.key_cap = kall; o.tab_cap = tabn; o.kp_cap = kpn;
-    o.tab_rows = o.tab_cols = 0;
-  }
-  // resize tables of all levels, one upload per image size
-  size_t toff[ORB_LEVELS] = {0};
-  {
-    size_t t = 0;
-    for (int l = 1; l < ORB_LEVELS; ++l) { toff[l] = t; t += (size_t)3 * (pw[l] + ph[l]); }
-    if (o.tab_rows != rows || o.tab_cols != cols) {
-      std::vector<int> all, xi, xa0, xa1, yi, yb0, yb1;
-      for (int l = 1; l < ORB_LEVELS; ++l) {
-        linear_coeffs(pw[l], pw[l - 1], xi, xa0, xa1);
-        linear_coeffs(ph[l], ph[l - 1], yi, yb0, yb1);
-        for (auto *v : {&xi, &xa0, &xa1, &yi, &yb0, &yb1}) all.insert(all.end(), v->begin(), v->end());
-      }
-      HIP_TRY(c, hipStreamSynchronize(st));
-      HIP_TRY(c, hipMemcpy(o.tab, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice));
-      o.tab_rows = rows; o.tab_cols = cols;
-    }
-  }
-  if (int rc = orb_ensure_tables(c)) return rc;
-  // of a strided view (a cv::Mat ROI) only (rows - 1) * stride + cols bytes are the caller's: the last row's padding may lie
-  // beyond the end of the parent allocation
-  const size_t src_bytes = (size_t)(rows - 1) * stride + cols;
-  if (src_bytes > o.src_cap) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if (o.src) (void)hipFree(o.src);
-    o.src = nullptr; o.src_cap = 0;
-    int rc = dev_alloc(c, &o.src, src_bytes, false);
-    if (rc) return rc;
-    o.src_cap = src_bytes;
-  }
-  HIP_TRY(c, hipMemcpyAsync(o.src, img, src_bytes, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemcpy2DAsync(o.im, cols, o.src, stride, cols, rows, hipMemcpyDeviceToDevice, st));   // level 0: the image, rows packed
-  // the whole image is enqueued without a host round trip: the pyramid level by level, then every stage once for all levels;
-  // one counter block per level, a level's keypoints land behind those of the levels below (orb_describe_kernel sums their counts)
-  HIP_TRY(c, hipMemsetAsync(o.counters, 0, (size_t)ORB_LEVELS * NMS_COUNTER_INTS * sizeof(int), st));
-  OrbLevels lv;
-  size_t koff = 0;
-  int want_max = 0;
-  for (int l = 0; l < ORB_LEVELS; ++l) {
-    OrbLevel &L = lv.l[l];
-    const int lcap = std::min(surv_cap, (ph[l] / 2 + 1) * (pw[l] / 2 + 1));
-    L.im = o.im + off[l]; L.score = o.score + off[l]; L.blur = o.blur + off[l]; L.tmp = o.tmp + off[l];
-    L.keys = o.keys + koff; L.rank = o.rank + koff; L.out_xy = o.out_xy + 2 * koff; L.counters = o.counters + l * NMS_COUNTER_INTS;
-    L.h = ph[l]; L.w = pw[l]; L.cap = lcap; L.scale = lscale[l];
-    L.want = (ph[l] <= 2 * ORB_EDGE + 2 || pw[l] <= 2 * ORB_EDGE + 2) ? 0 : want[l];
-    want_max = std::max(want_max, L.want);
-    koff += lcap;
-    if (l > 0) hipLaunchKernelGGL(orb_resize_kernel, dim3((pw[l] + 63) / 64, (ph[l] + 3) / 4), dim3(256), 0, st, o.im + off[l - 1], ph[l - 1], pw[l - 1], pw[l - 1], L.im, ph[l], pw[l],
-                                  o.tab + toff[l]);
-  }
-  if (want_max > 0) {
-    const dim3 grid((cols + 63) / 64, (rows + 3) / 4, ORB_LEVELS);
-    hipLaunchKernelGGL(orb_fast_kernel, grid, dim3(256), 0, st, lv, ORB_FAST_T, ORB_EDGE);
-    hipLaunchKernelGGL(orb_collect_kernel, grid, dim3(256), 0, st, lv);
-    hipLaunchKernelGGL(orb_rank_kernel, dim3(128, ORB_LEVELS), dim3(256), 0, st, lv);
-    hipLaunchKernelGGL(orb_write_kernel, dim3(32, ORB_LEVELS), dim3(256), 0, st, lv);
-    hipLaunchKernelGGL(orb_blur_h_kernel, grid, dim3(256), 0, st, lv, o.taps);
-    hipLaunchKernelGGL(orb_blur_v_kernel, grid, dim3(256), 0, st, lv, o.taps);
-    hipLaunchKernelGGL(orb_describe_kernel, dim3((want_max + 3) / 4, ORB_LEVELS), dim3(256), 0, st, lv, o.disc, o.pattern, o.kps, o.desc, kp_cap);
-  }
-  HIP_TRY(c, hipGetLastError());
-  int cnt[ORB_LEVELS * NMS_COUNTER_INTS];
-  HIP_TRY(c, hipMemcpyAsync(cnt, o.counters, sizeof cnt, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipStreamSynchronize(st));
-  int base = 0;
-  for (int l = 0; l < ORB_LEVELS; ++l) {
-    if (cnt[l * NMS_COUNTER_INTS + 3]) return fail(c, SPVO_ERR_CAPACITY, "ORB: corner buffer overflow at level %d", l);
-    base += cnt[l * NMS_COUNTER_INTS + 2];
-  }
-  base = std::min(base, kp_cap);
-  *n_out = base;
-  const int ncopy = std::min(base, cap);
-  if (ncopy > 0) {
-    HIP_TRY(c, hipMemcpyAsync(kps, o.kps, (size_t)ncopy * sizeof(OrbKeypoint), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(desc, o.desc, (size_t)ncopy * 32, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-  }
-  return SPVO_OK;
-}
-
-// ---------------------------------------------------------------- Shi-Tomasi, FAST, ORB extractor (classic front end, classic_detect.hip.h)
-namespace {
-// the image into the context's level-0 buffer (rows packed), every buffer grown to what this image needs
-int cls_prepare(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride) {
-  auto &b = c->cls;
-  hipStream_t st = c->stream2;
-  const size_t px = (size_t)rows * cols, state_bytes = (size_t)(rows + 2 * CLS_PAD) * cls_state_pitch(cols);
-  b.rows = b.cols = 0;   // nothing resident until the upload below is enqueued
-  if (px > b.px_cap || state_bytes > b.state_cap) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    for (void *p : {(void *)b.im, (void *)b.score, (void *)b.blur, (void *)b.state, (void *)b.tmp, (void *)b.lam, (void *)b.xy, (void *)b.resp, (void *)b.keys, (void *)b.rank,
-                    (void *)b.cand}) if (p) (void)hipFree(p);
-    b.im = b.score = b.blur = b.state = nullptr; b.tmp = b.lam = b.xy = b.resp = nullptr; b.keys = nullptr; b.rank = b.cand = nullptr;
-    const size_t npx = std::max(px, b.px_cap), nst = std::max(state_bytes, b.state_cap);
-    b.px_cap = b.state_cap = 0;   // a failed allocation below leaves a context that spvo_destroy and a later call can still handle
-    b.state_rows = b.state_cols = 0;
-    int rc;
-    if ((rc = dev_alloc(c, &b.im, npx + 256)) || (rc = dev_alloc(c, &b.score, npx + 256)) || (rc = dev_alloc(c, &b.blur, npx + 256)) || (rc = dev_alloc(c, &b.state, nst)) ||
-        (rc = dev_alloc(c, &b.tmp, npx)) || (rc = dev_alloc(c, &b.lam, npx)) || (rc = dev_alloc(c, &b.xy, 2 * npx)) || (rc = dev_alloc(c, &b.resp, npx)) ||
-        (rc = dev_alloc(c, &b.keys, npx)) || (rc = dev_alloc(c, &b.rank, npx)) || (rc = dev_alloc(c, &b.cand, npx)))
-      return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
-    b.px_cap = npx; b.state_cap = nst;
-  }
-  if (!b.counters) {
-    int rc = dev_alloc(c, &b.counters, CLS_COUNTER_INTS);
-    if (rc) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  // of a strided view (a cv::Mat ROI) only (rows - 1) * stride + cols bytes are the caller's (spvo_orb_detect)
-  const size_t src_bytes = (size_t)(rows - 1) * stride + cols;
-  if (src_bytes > b.src_cap) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if (b.src) (void)hipFree(b.src);
-    b.src = nullptr; b.src_cap = 0;
-    int rc = dev_alloc(c, &b.src, src_bytes, false);
-    if (rc) return rc;
-    b.src_cap = src_bytes;
-  }
-  HIP_TRY(c, hipMemcpyAsync(b.src, img, src_bytes, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemcpy2DAsync(b.im, cols, b.src, stride, cols, rows, hipMemcpyDeviceToDevice, st));
-  b.rows = rows; b.cols = cols;
-  return SPVO_OK;
-}
-
-// counters -> host, then min(n, cap) keypoints
-int cls_read_out(spvo_ctx *c, float *xy, float *response, int cap, int *n_out, const char *what) {
-  auto &b = c->cls;
-  hipStream_t st = c->stream2;
-  HIP_TRY(c, hipGetLastError());
-  int cnt[CLS_COUNTER_INTS];
-  HIP_TRY(c, hipMemcpyAsync(cnt, b.counters, sizeof cnt, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipStreamSynchronize(st));
-  std::memcpy(b.last_counters, cnt, sizeof cnt);
-  if (cnt[3]) return fail(c, SPVO_ERR_CAPACITY, "%s: key buffer overflow", what);
-  *n_out = cnt[2];
-  const int ncopy = std::min(cnt[2], cap);
-  if (ncopy > 0) {
-    HIP_TRY(c, hipMemcpyAsync(xy, b.xy, (size_t)ncopy * 2 * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (response) HIP_TRY(c, hipMemcpyAsync(response, b.resp, (size_t)ncopy * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-  }
-  return SPVO_OK;
-}
-}  // namespace
-
-int spvo_gftt_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride, int max_corners, double quality_level, double min_distance, int block_size,
-                     float *xy, float *response, int cap, int *n_out) {
-  if (!c || !img || !n_out || rows < 8 || cols < 8 || stride < (size_t)cols || cap < 0 || (cap > 0 && !xy) || !(quality_level > 0))
-    return fail(c, SPVO_ERR_INVALID, "bad argument");
-  if (block_size != 5 || !(min_distance >= 0 && min_distance <= 15)) return fail(c, SPVO_ERR_INVALID, "spvo_gftt_detect: block_size 5 and min_distance <= 15 only");
-  HIP_TRY(c, hipSetDevice(c->cfg.device));
-  *n_out = 0;
-  if (int rc = cls_prepare(c, img, rows, cols, stride)) return rc;
-  auto &b = c->cls;
-  hipStream_t st = c->stream2;
-  // dx^2 + dy^2 < min_distance^2 on integer coordinates: <= lim (OpenCV compares in float: min_distance as float, squared in float)
-  const float mdf = (float)min_distance;
-  const int lim = (int)std::ceil((double)mdf * (double)mdf) - 1;
-  const int radius = lim > 0 ? (int)std::floor(std::sqrt((double)lim)) : 0;
-  const int want = max_corners > 0 ? max_corners : 0x7FFFFFFF;   // (cv::goodFeaturesToTrack: max_corners <= 0 is "no limit")
-  const int key_cap = (int)std::min<size_t>((size_t)rows * cols, 0x7FFFFFFF);
-  HIP_TRY(c, hipMemsetAsync(b.counters, 0, CLS_COUNTER_INTS * sizeof(int), st));
-  if (b.state_rows != rows || b.state_cols != cols) {   // the padding of the state map: cleared once per shape (the kernels write the image's own bytes only)
-    HIP_TRY(c, hipMemsetAsync(b.state, 0, (size_t)(rows + 2 * CLS_PAD) * cls_state_pitch(cols), st));
-    b.state_rows = rows; b.state_cols = cols;
-  }
-  const dim3 grid((cols + 63) / 64, (rows + 3) / 4);
-  hipLaunchKernelGGL(gftt_response_kernel, grid, dim3(256), 0, st, b.im, rows, cols, b.lam, b.counters);
-  hipLaunchKernelGGL(gftt_collect_kernel, grid, dim3(256), 0, st, b.lam, rows, cols, quality_level, b.state, b.cand, b.counters);
-  for (int l = 0; l < CLS_ROUND_LAUNCHES; ++l)
-    hipLaunchKernelGGL(gftt_round_kernel<4>, dim3(64), dim3(256), 0, st, b.lam, cols, radius, lim, b.state, b.cand, b.keys, key_cap, b.counters, l);
-  hipLaunchKernelGGL(gftt_finish_kernel, dim3(1), dim3(1024), 0, st, b.lam, cols, radius, lim, b.state, b.cand, b.keys, key_cap, b.counters, CLS_ROUND_LAUNCHES);
-  hipLaunchKernelGGL(cls_rank_kernel, dim3(128), dim3(256), 0, st, b.keys, b.rank, b.counters + 1, key_cap);
-  hipLaunchKernelGGL(gftt_write_kernel, dim3(32), dim3(256), 0, st, b.lam, cols, b.keys, b.rank, key_cap, want, (float)(0.5 / (5100.0 * 5100.0)), b.xy, b.resp, b.counters);
-  return cls_read_out(c, xy, response, cap, n_out, "spvo_gftt_detect");
-}
-
-int spvo_gftt_last_rounds(spvo_ctx *c, int *undecided_after_launch /* [3] */, int *finish_rounds) {
-  if (!c) return fail(c, SPVO_ERR_INVALID, "null context");
-  for (int l = 0; l < CLS_ROUND_LAUNCHES; ++l) if (undecided_after_launch) undecided_after_launch[l] = c->cls.last_counters[8 + l];
-  if (finish_rounds) *finish_rounds = c->cls.last_counters[5];
-  return SPVO_OK;
-}
-
-int spvo_fast_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride, int threshold, int nonmax_suppression, float *xy, float *response, int cap,
-                     int *n_out) {
-  if (!c || !img || !n_out || rows <= 0 || cols <= 0 || stride < (size_t)cols || cap < 0 || (cap > 0 && !xy) || threshold < 0 || threshold > 255)
-    return fail(c, SPVO_ERR_INVALID, "bad argument");
-  HIP_TRY(c, hipSetDevice(c->cfg.device));
-  *n_out = 0;
-  if (int rc = cls_prepare(c, img, rows, cols, stride)) return rc;
-  auto &b = c->cls;
-  hipStream_t st = c->stream2;
-  const int key_cap = (int)std::min<size_t>((size_t)rows * cols, 0x7FFFFFFF);   // no cap in the reference: with suppression off every pixel can be a corner
-  HIP_TRY(c, hipMemsetAsync(b.counters, 0, CLS_COUNTER_INTS * sizeof(int), st));
-  OrbLevels lv{};
-  lv.l[0].im = b.im; lv.l[0].score = b.score; lv.l[0].h = rows; lv.l[0].w = cols; lv.l[0].want = 1; lv.l[0].scale = 1.f;
-  const dim3 grid((cols + 63) / 64, (rows + 3) / 4, 1);
-  hipLaunchKernelGGL(orb_fast_kernel, grid, dim3(256), 0, st, lv, threshold, 3);
-  hipLaunchKernelGGL(fast_collect_kernel, grid, dim3(256), 0, st, b.score, rows, cols, nonmax_suppression ? 1 : 0, b.keys, key_cap, b.counters);
-  hipLaunchKernelGGL(cls_rank_kernel, dim3(128), dim3(256), 0, st, b.keys, b.rank, b.counters + 1, key_cap);
-  hipLaunchKernelGGL(fast_write_kernel, dim3(32), dim3(256), 0, st, cols, b.keys, b.rank, key_cap, b.xy, b.resp, b.counters);
-  return cls_read_out(c, xy, response, cap, n_out, "spvo_fast_detect");
-}
-
-int spvo_orb_describe(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride, const float *xy, int n, int32_t *kept, float *angle, uint8_t *desc, int *n_kept) {
-  if (!c || !n_kept || rows <= 0 || cols <= 0 || n < 0 || (n > 0 && (!xy || !kept || !desc)) || (img && stride < (size_t)cols)) return fail(c, SPVO_ERR_INVALID, "bad argument");
-  *n_kept = 0;
-  auto &b = c->cls;
-  if (!img && (b.rows != rows || b.cols != cols))
-    return fail(c, SPVO_ERR_STATE, "spvo_orb_describe: no image of %d x %d is resident (call spvo_gftt_detect / spvo_fast_detect first, or pass the image)", rows, cols);
-  // cv::ORB::compute drops, order-preserving, what is closer than 31 pixels to a border; coordinates must be integers (no rounding rule is invented)
-  std::vector<int> kxy;
-  kxy.reserve((size_t)n * 2);
-  int nk = 0;
-  for (int i = 0; i < n; ++i) {
-    const float x = xy[2 * i], y = xy[2 * i + 1];
-    if (!(x == std::floor(x)) || !(y == std::floor(y)) || std::fabs(x) > 1e9f || std::fabs(y) > 1e9f)
-      return fail(c, SPVO_ERR_INVALID, "spvo_orb_describe: keypoint %d (%g, %g) is not at integer coordinates", i, (double)x, (double)y);
-    const int xi = (int)x, yi = (int)y;
-    if (xi < ORB_EDGE || xi >= cols - ORB_EDGE || yi < ORB_EDGE || yi >= rows - ORB_EDGE) continue;
-    kept[nk++] = i;
-    kxy.push_back(xi); kxy.push_back(yi);
-  }
-  HIP_TRY(c, hipSetDevice(c->cfg.device));
-  hipStream_t st = c->stream2;
-  if (img) {
-    if (int rc = cls_prepare(c, img, rows, cols, stride)) return rc;
-  }
-  *n_kept = nk;
-  if (nk == 0) {
-    HIP_TRY(c, hipStreamSynchronize(st));   // (the caller's image may be in flight)
-    return SPVO_OK;
-  }
-  if (int rc = orb_ensure_tables(c)) return rc;
-  if (nk > b.kp_cap) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    for (void *p : {(void *)b.kp_xy, (void *)b.kps, (void *)b.desc}) if (p) (void)hipFree(p);
-    b.kp_xy = nullptr; b.kps = nullptr; b.desc = nullptr; b.kp_cap = 0;
-    int rc;
-    if ((rc = dev_alloc(c, &b.kp_xy, (size_t)2 * nk)) || (rc = dev_alloc(c, &b.kps, (size_t)nk)) || (rc = dev_alloc(c, &b.desc, (size_t)nk * 32))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    b.kp_cap = nk;
-  }
-  int cnt[CLS_COUNTER_INTS] = {0};
-  cnt[2] = nk;
-  HIP_TRY(c, hipMemcpyAsync(b.counters, cnt, sizeof cnt, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemcpyAsync(b.kp_xy, kxy.data(), (size_t)2 * nk * sizeof(int), hipMemcpyHostToDevice, st));
-  // orb.hip.h's extractor on a one-level OrbLevels whose keypoint list is the caller's: 7x7 blur of level 0, then direction + steered tests
-  OrbLevels lv{};
-  OrbLevel &L = lv.l[0];
-  L.im = b.im; L.score = b.score; L.blur = b.blur; L.tmp = b.tmp; L.out_xy = b.kp_xy; L.counters = b.counters;
-  L.h = rows; L.w = cols; L.want = nk; L.cap = nk; L.scale = 1.f;
-  const dim3 grid((cols + 63) / 64, (rows + 3) / 4, 1);
-  hipLaunchKernelGGL(orb_blur_h_kernel, grid, dim3(256), 0, st, lv, c->orb.taps);
-  hipLaunchKernelGGL(orb_blur_v_kernel, grid, dim3(256), 0, st, lv, c->orb.taps);
-  hipLaunchKernelGGL(orb_describe_kernel, dim3((nk + 3) / 4, 1), dim3(256), 0, st, lv, c->orb.disc, c->orb.pattern, b.kps, b.desc, nk);
-  HIP_TRY(c, hipGetLastError());
-  std::vector<OrbKeypoint> kp((size_t)nk);
-  HIP_TRY(c, hipMemcpyAsync(kp.data(), b.kps, (size_t)nk * sizeof(OrbKeypoint), hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipMemcpyAsync(desc, b.desc, (size_t)nk * 32, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipStreamSynchronize(st));
-  if (angle) for (int i = 0; i < nk; ++i) angle[i] = kp[i].angle;
-  return SPVO_OK;
 }
 
 }  // extern "C"

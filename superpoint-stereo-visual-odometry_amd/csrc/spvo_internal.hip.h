@@ -6,7 +6,8 @@
 //   spvo_net_f32.hip   FP32 engines: direct + Winograd convolution launchers, the layer executor (run_ops)
 //   spvo_net_f16.hip   FP16 engines                     spvo_net_s3.hip   FP32 engines in split (bf16x3) mode
 //   spvo_net_i8.hip    INT8 engines
-//   spvo_detect.hip    preprocess, heat map / NMS / sampling, the detector submissions, spvo_forward, ORB
+//   spvo_detect.hip    preprocess, heat map / NMS / sampling, the detector submissions, spvo_forward
+//   spvo_classic.hip   the classic front end: ORB, Shi-Tomasi, FAST, the ORB extractor, preprocess without an engine
 //   spvo_match.hip     descriptor matching (L2, Hamming)
 //   spvo_solve.hip     triangulation, PnP-RANSAC, gating, Levenberg-Marquardt, the fused solve
 #pragma once
@@ -45,7 +46,7 @@ struct Tensor {
   bool s3 = false;    // FP32 engines in split mode: C8x3 bf16 pieces [C/8][3][Hp][Wp][8] (conv_bf16x3.hip.h)
   float scale = 0.f;  // INT8 engines: real value = q * scale (calibrated)
   float *d = nullptr;
-  float *dr[RING] = {nullptr, nullptr, nullptr, nullptr};  // network outputs only: one buffer per submission set (d == dr[0])
+  float *dr[RING] = {};  // network outputs only: one buffer per submission set (d == dr[0])
   size_t per_image = 0;  // floats
 };
 
@@ -124,13 +125,14 @@ struct NmsImage {
   NmsBuffers b;
 };
 
+// what base.cpp:75-119 crops of an image before it resizes it to the network's size, and the resize's scale
+struct CropGeom { int row_off = 0, col_off = 0, crop_rows = 0, crop_cols = 0; float scale = 1.f; };
+
 }  // namespace spvo_int
 using namespace spvo_int;
 
-struct CropGeomS { int row_off = 0, col_off = 0, crop_rows = 0, crop_cols = 0; float scale = 1.f; };
-
 struct PendingDetect {           // one spvo_detect*_submit in flight
-  CropGeomS g;
+  CropGeom g;
   int rows = 0, cols = 0, slot_l = 0, slot_r = 0, prev_l = -1, ring = 0;
   bool rematch = false;          // the temporal partner's keypoints were redone after this submission matched against them
   int extras = 0;                // spvo_detect_submit: bit 0 resized images, bit 1 descriptors travel to the set's pinned mirrors
@@ -159,6 +161,11 @@ struct TrunkDiag {
   int late = 0;
   float max_idle = 0;
   std::string pat;
+  // the four points of a group launch where it records (spvo_core.hip); every caller tests spvo_ctx::trunk_timing first
+  void launch_begin(spvo_ctx *c, int npairs);   // the report lines, the sums from the events of the launch eight back, the trunk's begin event
+  void trunk_end(hipStream_t net) { (void)hipEventRecord(e[n % TT], net); }
+  void tail_begin(hipStream_t tail) { (void)hipEventRecord(tb[n % TT], tail); }
+  void tail_end(hipStream_t tail) { (void)hipEventRecord(te[n % TT], tail); ++n; }
 };
 
 struct spvo_ctx {
@@ -231,29 +238,29 @@ struct spvo_ctx {
   float *d_ma = nullptr, *d_mb = nullptr;
   MatchScratch ms[2][2];         // [tail stream][stereo, temporal]
   int2 *d_match_out = nullptr;   // [2][cap]: both jobs' results leave in one copy
-  int2 *h_match_out[RING] = {nullptr, nullptr, nullptr, nullptr};   // pinned [2][cap] per submission set
+  int2 *h_match_out[RING] = {};   // pinned [2][cap] per submission set
   int2 *h_match_tmp = nullptr;   // pinned [cap] for the synchronous entry points
   int *d_counters_all = nullptr; // [RING sets + 1 stand-alone set][2 images][NMS_COUNTER_INTS]
   float *d_xy_stage = nullptr;   // [RING][2][cap][2] keypoints of both images as floats: one copy per submission
   MatchCache mcache[RING][2];    // [submission set][stereo, temporal]
   // per submission set (index 0 doubles as the stand-alone entry points' set)
   NmsImage nms_r[RING][2];
-  float *d_heat_r[RING] = {nullptr, nullptr, nullptr, nullptr}, *d_heat_base_r[RING] = {nullptr, nullptr, nullptr, nullptr};
-  int *h_counters_r[RING] = {nullptr, nullptr, nullptr, nullptr};
-  float *h_xy_r[RING] = {nullptr, nullptr, nullptr, nullptr};
+  float *d_heat_r[RING] = {}, *d_heat_base_r[RING] = {};
+  int *h_counters_r[RING] = {};
+  float *h_xy_r[RING] = {};
   // host-image submissions (spvo_detect_submit): per set, pinned staging + device copies of the two input images, a resized-image
   // buffer of its own and pinned mirrors of the resized images and of the descriptors
-  uint8_t *h_img_r[RING] = {nullptr, nullptr, nullptr, nullptr}, *d_img_r[RING] = {nullptr, nullptr, nullptr, nullptr};
+  uint8_t *h_img_r[RING] = {}, *d_img_r[RING] = {};
   size_t img_cap_r = 0;          // bytes per image in those buffers
-  uint8_t *d_resized_r[RING] = {nullptr, nullptr, nullptr, nullptr}, *h_resized_r[RING] = {nullptr, nullptr, nullptr, nullptr};
-  float *h_desc_r[RING] = {nullptr, nullptr, nullptr, nullptr};   // [2][cap][256]
+  uint8_t *d_resized_r[RING] = {}, *h_resized_r[RING] = {};
+  float *h_desc_r[RING] = {};   // [2][cap][256]
   bool host_sets_ready = false;  // d_resized_r / h_resized_r / h_desc_r of EVERY set are allocated
-  hipEvent_t ev_net[RING] = {nullptr, nullptr, nullptr, nullptr}, ev_tail[RING] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t ev_net[RING] = {}, ev_tail[RING] = {};
   // a submission's tail in two parts: ev_feat = keypoints, counts and descriptors are final (what spvo_detect_wait needs), ev_tail = the
   // matches enqueued behind them have landed too (what spvo_match_slots needs); ev_copy = the descriptors of a host-image submission have reached their pinned mirror (copy kernel behind the matches)
-  hipEvent_t ev_feat[RING] = {nullptr, nullptr, nullptr, nullptr}, ev_copy[RING] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_pre[RING] = {nullptr, nullptr, nullptr, nullptr}, ev_res[RING] = {nullptr, nullptr, nullptr, nullptr};   // first layer done (network stream) / resized images on the host (tail stream)
-  hipEvent_t ev_up[RING] = {nullptr, nullptr, nullptr, nullptr};   // a queued host-image submission's upload, on the solver's stream, has landed (its preprocess kernel waits for it)
+  hipEvent_t ev_feat[RING] = {}, ev_copy[RING] = {};
+  hipEvent_t ev_pre[RING] = {}, ev_res[RING] = {};   // first layer done (network stream) / resized images on the host (tail stream)
+  hipEvent_t ev_up[RING] = {};   // a queued host-image submission's upload, on the solver's stream, has landed (its preprocess kernel waits for it)
   hipEvent_t ev_post = nullptr, ev_post_b = nullptr;    // PostScope: orders a synchronous entry point behind what is left on the tail stream(s)
   hipEvent_t ev_heads[RING] = {};  // the group's heads are done (tail_streams == 2, heads on the tail stream: the second pair's stream waits for it)
   bool match_fp8 = false;        // fp8 shortlist GEMM (approximate; spvo_set_match_fp8)
@@ -366,6 +373,19 @@ int dev_alloc(spvo_ctx *c, T **p, size_t count, bool zero = true) {
   return SPVO_OK;
 }
 
+// frees device buffers, where there is one, and forgets them
+template <typename T, typename... Rest>
+void dev_free(T *&p, Rest *&...rest) {
+  if (p) { (void)hipFree(p); p = nullptr; }
+  if constexpr (sizeof...(rest) > 0) dev_free(rest...);
+}
+
+// the synchronous entry points that work in the submissions' buffers refuse to run beside them; a failed wait / record: "`what` failed"
+inline int require_idle(spvo_ctx *c) {
+  return c->pendq.empty() ? SPVO_OK : fail(c, SPVO_ERR_STATE, "detector submissions are in flight: complete them with spvo_detect_wait first");
+}
+inline int dev_check(spvo_ctx *c, hipError_t e, const char *what) { return e == hipSuccess ? SPVO_OK : fail(c, SPVO_ERR_DEVICE, "%s failed", what); }
+
 int stage_id(spvo_ctx *c, const std::string &name);
 hipError_t wait_event(hipEvent_t ev);
 // a diagnostic switch (spvo_set_tuning, include/spvo.h): the value set for `name`, or `dflt`.  Never the environment.
@@ -438,7 +458,10 @@ void launch_unpad_c16(const Tensor &t, int batch, float *dst, hipStream_t stream
 int run_ops(spvo_ctx *c, int batch, size_t first, size_t last, hipStream_t stream);   // ops [first, last) on `stream`
 int run_network(spvo_ctx *c, int batch);
 // ---- spvo_detect.hip
-void linear_coeffs(int dst, int src, std::vector<int> &idx, std::vector<int> &a0, std::vector<int> &a1);
+// appends the six tables of a dst_w x dst_h <- src_w x src_h bilinear resize: xi, xa0, xa1 [dst_w]; yi, yb0, yb1 [dst_h]
+void resize_tables(int dst_w, int src_w, int dst_h, int src_h, std::vector<int> &out);
+// ---- spvo_classic.hip: spvo_preprocess of a context without an engine (d_img[0] -> cls.pre_out, enqueued on the network stream)
+int classic_preprocess(spvo_ctx *c, const CropGeom &g, size_t stride);
 // ---- spvo_match.hip
 int ensure_match(spvo_ctx *c, int na, int nb);
 struct MatchReq {

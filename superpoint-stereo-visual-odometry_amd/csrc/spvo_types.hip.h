@@ -25,6 +25,13 @@ struct NmsBuffers {   // per image
 };
 struct NmsPair { NmsBuffers b[2]; };   // blockIdx.y / blockIdx.z selects the image
 
+// the state map's values, K9's rank keys and LDS tile: the classic front end's kernels (orb.hip.h, classic_detect.hip.h) use them too
+enum : uint8_t { ST_NONE = 0, ST_UNDECIDED = 1, ST_KEPT = 2, ST_SUPPRESSED = 4 };   // one bit each: word-wide tests
+__device__ __forceinline__ unsigned long long rank_key(float conf, int x, int y, int H) {
+  return ((unsigned long long)(0xFFFFFFFFu - __float_as_uint(conf)) << 32) | (unsigned)(x * H + y);
+}
+constexpr int RANK_TILE = 1024;
+
 // ---- K15 (odometry.hip.h)
 struct RansacWork {      // device scratch
   int *counts;           // [iterations]  (-1 = invalid hypothesis)
