@@ -144,12 +144,11 @@ static void seg_drop(GraphEntry &e) {
   e = GraphEntry();
 }
 
+void set_release_segments(SubmitSet &s) {
+  for (GraphEntry *e : {&s.seg_T[0], &s.seg_T[1], &s.seg_H[0], &s.seg_H[1], &s.seg_A, &s.seg_B}) seg_drop(*e);
+}
 void seg_free_all(spvo_ctx *c) {
-  for (int r = 0; r < RING; ++r) {
-    for (int k = 0; k < 2; ++k) { seg_drop(c->seg_T[r][k]); seg_drop(c->seg_H[r][k]); }
-    seg_drop(c->seg_A[r]);
-    seg_drop(c->seg_B[r]);
-  }
+  for (SubmitSet &s : c->sets) set_release_segments(s);
 }
 
 void seg_abort(spvo_ctx *c) {
@@ -242,6 +241,48 @@ void free_plan(spvo_ctx *c) {
   c->tensors.clear(); c->ops.clear(); c->weights = false; c->fp16 = false; c->int8 = false; c->s3 = false;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- submission sets
+// (SubmitSet, spvo_internal.hip.h.)  What every set has from spvo_create on; the rest is allocated on first use (ensure_host_sets, ensure_match, seg_end)
+int set_alloc(spvo_ctx *c, int index) {
+  SubmitSet &s = c->sets[index];
+  const size_t hw = (size_t)c->H * c->W;
+  const int cap = c->cfg.max_keypoints;
+  for (hipEvent_t *e : {&s.ev_net, &s.ev_tail, &s.ev_feat, &s.ev_copy, &s.ev_pre, &s.ev_res, &s.ev_up, &s.ev_heads})
+    if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return fail(c, SPVO_ERR_DEVICE, "cannot create events on device %d", c->cfg.device);
+  s.d_counters = c->d_counters_all + (size_t)index * 2 * NMS_COUNTER_INTS;
+  int rc = dev_alloc(c, &s.d_heat_base, 2 * hw + 128);
+  if (rc) return rc;
+  s.d_heat = s.d_heat_base + 64;   // K10 reads aligned float4 rows that may start left of column 0
+  for (NmsBuffers &b : s.nms) {
+    if ((rc = dev_alloc(c, &b.state, (size_t)(c->H + 2 * NMS_PAD) * nms_state_pitch(c->W)))) return rc;
+    if ((rc = dev_alloc(c, &b.cand, hw))) return rc;
+    b.counters = nullptr;   // set per submission (nms_pair)
+    if ((rc = dev_alloc(c, &b.surv_key, c->surv_cap))) return rc;
+    if ((rc = dev_alloc(c, &b.rank, c->surv_cap))) return rc;
+    if ((rc = dev_alloc(c, &b.out_xy, (size_t)cap * 2))) return rc;
+  }
+  if (hipHostMalloc((void **)&s.h_counters, 2 * NMS_COUNTER_INTS * sizeof(int)) != hipSuccess ||
+      hipHostMalloc((void **)&s.h_xy, (size_t)2 * cap * 2 * sizeof(float)) != hipSuccess) return fail(c, SPVO_ERR_DEVICE, "hipHostMalloc failed");
+  return SPVO_OK;
+}
+
+void set_release_images(SubmitSet &s) {
+  dev_free(s.d_img);
+  if (s.h_img) { (void)hipHostFree(s.h_img); s.h_img = nullptr; }
+}
+void set_release_match(SubmitSet &s) {
+  if (s.h_match_out) { (void)hipHostFree(s.h_match_out); s.h_match_out = nullptr; }
+  for (MatchCache &mc : s.mcache) { mc.valid = false; mc.h_out = nullptr; }
+}
+void set_release(SubmitSet &s) {
+  set_release_images(s); set_release_match(s); set_release_segments(s);
+  for (NmsBuffers &b : s.nms) dev_free(b.state, b.cand, b.surv_key, b.rank, b.out_xy);
+  dev_free(s.d_heat_base, s.d_resized);   // (d_heat and d_counters point into other allocations)
+  for (void *hp : {(void *)s.h_counters, (void *)s.h_xy, (void *)s.h_resized, (void *)s.h_desc}) if (hp) (void)hipHostFree(hp);
+  for (hipEvent_t e : {s.ev_net, s.ev_tail, s.ev_feat, s.ev_copy, s.ev_pre, s.ev_res, s.ev_up, s.ev_heads}) if (e) (void)hipEventDestroy(e);
+  s = SubmitSet();
+}
+
 }  // namespace spvo_int
 
 // tuning "trunk_timing" = 1 (diagnostic): how long the network stream works per trunk launch and how long it stands idle between two,
@@ -250,7 +291,7 @@ void free_plan(spvo_ctx *c) {
 void TrunkDiag::launch_begin(spvo_ctx *c, int npairs) {
   const int trace_lo = c->trunk_timing;
   const double tnow = diag_now_us();
-  const bool found_idle = c->last_launch_ring >= 0 && hipEventQuery(c->ev_net[c->last_launch_ring]) == hipSuccess;
+  const bool found_idle = c->last_launch_ring >= 0 && hipEventQuery(c->sets[c->last_launch_ring].ev_net) == hipSuccess;
   if (found_idle) ++g_diag.late;   // the trunk before this one is done already: the stream is idle
   if (trace_lo > 1 && g_diag.launches + 1 >= trace_lo && g_diag.launches + 1 < trace_lo + 80)
     std::fprintf(stderr, "T %.0f launch %ld: %d pairs, stream %s, submissions so far %u, in flight %zu\n", tnow, g_diag.launches + 1, npairs, found_idle ? "IDLE" : "busy", c->submit_count, c->pendq.size());
@@ -361,18 +402,7 @@ int spvo_create(const spvo_config *cfg, spvo_ctx **out) {
     return fail(nullptr, SPVO_ERR_DEVICE, "cannot create a stream on device %d", cfg->device);
   }
   c->post = c->stream;
-  (void)hipEventCreateWithFlags(&c->ev_post, hipEventDisableTiming);
-  (void)hipEventCreateWithFlags(&c->ev_post_b, hipEventDisableTiming);
-  for (int r = 0; r < RING; ++r) (void)hipEventCreateWithFlags(&c->ev_heads[r], hipEventDisableTiming);
   c->split_req = tuning("fp32_split", 0) != 0;
-  for (int r = 0; r < RING; ++r)
-    if (hipEventCreateWithFlags(&c->ev_net[r], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_tail[r], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_feat[r], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_copy[r], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_pre[r], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_res[r], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_up[r], hipEventDisableTiming) != hipSuccess) {
-      spvo_destroy(c);
-      return fail(nullptr, SPVO_ERR_DEVICE, "cannot create events on device %d", cfg->device);
-    }
   int rc = SPVO_OK;
   const size_t hw = (size_t)c->H * c->W;
   const int cap = cfg->max_keypoints;
@@ -380,34 +410,17 @@ int spvo_create(const spvo_config *cfg, spvo_ctx **out) {
   const int cell = cfg->dist_thresh + 1;
   c->surv_cap = ((c->H + cell - 1) / cell) * ((c->W + cell - 1) / cell) + 64;
   do {
+    if ((rc = dev_check(c, hipEventCreateWithFlags(&c->ev_post, hipEventDisableTiming), "hipEventCreate")) || (rc = dev_check(c, hipEventCreateWithFlags(&c->ev_post_b, hipEventDisableTiming), "hipEventCreate"))) break;
     if ((rc = dev_alloc(c, &c->d_dense_in, c->B * hw))) break;
     if ((rc = dev_alloc(c, &c->d_det_dense, (size_t)c->B * 65 * c->Hc * c->Wc))) break;
     if ((rc = dev_alloc(c, &c->d_counters_all, (size_t)(RING + 1) * 2 * NMS_COUNTER_INTS))) break;   // RING submission sets, stand-alone
-    if ((rc = dev_alloc(c, &c->d_xy_stage, (size_t)RING * 2 * cfg->max_keypoints * 2))) break;
-    for (int r = 0; r < RING && !rc; ++r) {
-      if ((rc = dev_alloc(c, &c->d_heat_base_r[r], 2 * hw + 128))) break;
-      c->d_heat_r[r] = c->d_heat_base_r[r] + 64;   // K10 reads aligned float4 rows that may start left of column 0
-    }
+    c->d_counters_alone = c->d_counters_all + (size_t)RING * 2 * NMS_COUNTER_INTS;
+    for (int r = 0; r < RING && !rc; ++r) rc = set_alloc(c, r);
     if (rc) break;
-    c->d_heat_base = c->d_heat_base_r[0];
-    c->d_heat = c->d_heat_r[0];
     if ((rc = dev_alloc(c, &c->d_resized, 2 * hw))) break;
     if ((rc = dev_alloc(c, &c->d_tab, (size_t)3 * (c->H + c->W)))) break;
-    for (int r = 0; r < RING && !rc; ++r)
-      for (int i = 0; i < 2 && !rc; ++i) {
-        NmsBuffers &b = c->nms_r[r][i].b;
-        if ((rc = dev_alloc(c, &b.state, (size_t)(c->H + 2 * NMS_PAD) * nms_state_pitch(c->W)))) break;
-        if ((rc = dev_alloc(c, &b.cand, hw))) break;
-        b.counters = nullptr;   // set per submission (nms_pair)
-        if ((rc = dev_alloc(c, &b.surv_key, c->surv_cap))) break;
-        if ((rc = dev_alloc(c, &b.rank, c->surv_cap))) break;
-        if ((rc = dev_alloc(c, &b.out_xy, (size_t)cap * 2))) break;
-      }
-    if (rc) break;
-    for (int i = 0; i < 2; ++i) c->nms[i] = c->nms_r[0][i];   // the stand-alone entry points work in set 0
     for (int i = 0; i < N_SLOTS && !rc; ++i) {
       if ((rc = dev_alloc(c, &c->slots[i].d_xy, (size_t)cap * 2))) break;
-      if ((rc = dev_alloc(c, &c->slots[i].d_xyf, (size_t)cap * 2))) break;
       if ((rc = dev_alloc(c, &c->slots[i].d_desc, (size_t)cap * 256))) break;
       if ((rc = dev_alloc(c, &c->slots[i].d_n, 1))) break;
       if ((rc = dev_alloc(c, &c->slots[i].d_sqn, cap + 4))) break;   // K12b reads the norms four at a time
@@ -415,12 +428,6 @@ int spvo_create(const spvo_config *cfg, spvo_ctx **out) {
     if (rc) break;
     if ((rc = dev_alloc(c, &c->d_xy_tmp, (size_t)cap * 2))) break;
     if ((rc = dev_alloc(c, &c->d_desc_tmp, (size_t)cap * 256))) break;
-    for (int r = 0; r < RING && !rc; ++r)
-      if (hipHostMalloc((void **)&c->h_counters_r[r], 2 * NMS_COUNTER_INTS * sizeof(int)) != hipSuccess ||
-          hipHostMalloc((void **)&c->h_xy_r[r], (size_t)2 * cap * 2 * sizeof(float)) != hipSuccess) rc = fail(c, SPVO_ERR_DEVICE, "hipHostMalloc failed");
-    if (rc) break;
-    c->h_counters = c->h_counters_r[0];
-    c->h_xy = c->h_xy_r[0];
     if ((rc = ensure_match(c, cap, cap))) break;
   } while (0);
   if (rc) {
@@ -443,7 +450,6 @@ void spvo_destroy(spvo_ctx *c) {
   for (hipEvent_t e : c->ev_solve) if (e) (void)hipEventDestroy(e);
   if (c->ev_post) (void)hipEventDestroy(c->ev_post);
   if (c->ev_post_b) (void)hipEventDestroy(c->ev_post_b);
-  for (int r = 0; r < RING; ++r) if (c->ev_heads[r]) (void)hipEventDestroy(c->ev_heads[r]);
   resolve_pending(c);
   for (int r = 0; r < TrunkDiag::TT; ++r)
     for (hipEvent_t e : {c->tdiag.b[r], c->tdiag.e[r], c->tdiag.tb[r], c->tdiag.te[r]}) if (e) (void)hipEventDestroy(e);
@@ -451,28 +457,14 @@ void spvo_destroy(spvo_ctx *c) {
   for (auto e : c->free_events) (void)hipEventDestroy(e);
   free_plan(c);
   void *ptrs[] = {c->d_dense_in, c->d_det_dense, c->d_resized, c->d_tab, c->d_img[0], c->d_img[1], c->d_xy_tmp, c->d_desc_tmp,
-                  c->d_ma, c->d_mb, c->d_match_out, c->d_counters_all, c->d_xy_stage,
+                  c->d_ma, c->d_mb, c->d_match_out, c->d_counters_all,
                   c->d_P, c->d_pts_a, c->d_pts_b, c->d_xyz, c->rw.counts, c->rw.poses, c->rw.result, c->rw.inliers, c->d_obs, c->d_refine};
   for (void *p : ptrs) if (p) (void)hipFree(p);
   for (auto &set : c->ms)
     for (auto &m : set)
       dev_free(m.d_na, m.d_nb, m.d_best_d2, m.d_dt, m.d_cand, m.d_meta, m.d_best_idx, m.d_train_best, m.d_a8, m.d_b8, m.d_qa8, m.d_qb8);
-  for (int r = 0; r < RING; ++r) {
-    for (int i = 0; i < 2; ++i) {
-      NmsBuffers &b = c->nms_r[r][i].b;
-      dev_free(b.state, b.cand, b.surv_key, b.rank, b.out_xy);
-    }
-    if (c->d_heat_base_r[r]) (void)hipFree(c->d_heat_base_r[r]);
-    if (c->h_counters_r[r]) (void)hipHostFree(c->h_counters_r[r]);
-    if (c->h_xy_r[r]) (void)hipHostFree(c->h_xy_r[r]);
-    if (c->d_img_r[r]) (void)hipFree(c->d_img_r[r]);
-    if (c->h_img_r[r]) (void)hipHostFree(c->h_img_r[r]);
-    if (c->d_resized_r[r]) (void)hipFree(c->d_resized_r[r]);
-    if (c->h_resized_r[r]) (void)hipHostFree(c->h_resized_r[r]);
-    if (c->h_desc_r[r]) (void)hipHostFree(c->h_desc_r[r]);
-    for (hipEvent_t e : {c->ev_net[r], c->ev_tail[r], c->ev_feat[r], c->ev_copy[r], c->ev_pre[r], c->ev_res[r], c->ev_up[r]}) if (e) (void)hipEventDestroy(e);
-  }
-  for (auto &sl : c->slots) dev_free(sl.d_xy, sl.d_xyf, sl.d_desc, sl.d_n, sl.d_sqn);
+  for (SubmitSet &s : c->sets) set_release(s);
+  for (auto &sl : c->slots) dev_free(sl.d_xy, sl.d_desc, sl.d_n, sl.d_sqn);
   for (int sl = 0; sl < spvo_ctx::SOLVE_BUFS; ++sl) {
     for (void *dp : {(void *)c->x_counts[sl], (void *)c->x_poses[sl], (void *)c->x_obs[sl]}) if (dp) (void)hipFree(dp);
     for (void *hp : {(void *)c->h_solve_in[sl], (void *)c->h_solve_res[sl], (void *)c->h_solve_o[sl]}) if (hp) (void)hipHostFree(hp);
@@ -484,7 +476,6 @@ void spvo_destroy(spvo_ctx *c) {
   dev_free(o.im, o.score, o.blur, o.src, o.tmp, o.pattern, o.taps, o.keys, o.rank, o.out_xy, o.counters, o.tab, o.disc, o.kps, o.desc);
   auto &b = c->cls;
   dev_free(b.im, b.score, b.blur, b.src, b.state, b.desc, b.tmp, b.lam, b.xy, b.resp, b.keys, b.rank, b.cand, b.counters, b.kp_xy, b.kps, b.pre_out, b.pre_tab);
-  for (auto hp : c->h_match_out) if (hp) (void)hipHostFree(hp);
   if (c->h_match_tmp) (void)hipHostFree(c->h_match_tmp);
   if (c->stream_t) (void)hipStreamDestroy(c->stream_t);
   if (c->stream_tb) (void)hipStreamDestroy(c->stream_tb);

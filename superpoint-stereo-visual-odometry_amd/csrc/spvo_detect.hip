@@ -132,7 +132,7 @@ int launch_first_pre(spvo_ctx *c, PendingDetect *const *mem, int n, hipStream_t 
   a.identity = (g.crop_rows == c->H && g.crop_cols == c->W) ? 1 : 0;
   a.tab = resize_tab(c);
   a.in_plane = ti.d; a.in_per_image = ti.per_image;
-  a.out = to.dr[c->cur_ring] ? to.dr[c->cur_ring] : to.d;
+  a.out = ring_ptr(c, to);
   a.w = op.d_w; a.bias = op.d_b;
   a.H = ti.H; a.W = ti.W; a.hp = ti.hp; a.wp = ti.wp; a.out_ctot = to.ch; a.out_coff = op.out_c_off; a.cout = op.cout;
   const int batch = 2 * n;
@@ -150,22 +150,21 @@ constexpr int NMS_GRID = 128;
 
 // NMS counter blocks rotate through RING sets with the submissions: the last NMS kernel of one
 // submission zeroes the block of the next one, so the steady state needs no memset.
-// `set` < RING: a detector submission's buffers and counters; set == RING: the stand-alone entry
-// points (buffers of set 0, counters of their own so that the submissions' blocks stay zeroed).
-NmsPair nms_pair(spvo_ctx *c, int set) {
+// `counters`: the set's own (a detector submission), or the stand-alone entry points' (standalone()).
+NmsPair nms_pair(const SubmitSet &s, int *counters) {
   NmsPair p;
   for (int i = 0; i < 2; ++i) {
-    p.b[i] = c->nms_r[set % RING][i].b;
-    p.b[i].counters = c->d_counters_all + (size_t)(set * 2 + i) * NMS_COUNTER_INTS;
+    p.b[i] = s.nms[i];
+    p.b[i].counters = counters + (size_t)i * NMS_COUNTER_INTS;
   }
   return p;
 }
 
 // `n_launch` round launches + collect + rank + write for `nimg` images; the last kernel writes the counters
 // into the set's pinned mirror.  Launch 0 of a batch never exits early.
-int launch_nms_rounds(spvo_ctx *c, int nimg, const NmsPair &np, int set, int n_launch, int *zero_next, bool redo = false) {
+int launch_nms_rounds(spvo_ctx *c, int nimg, const NmsPair &np, const SubmitSet &s, int n_launch, int *zero_next, bool redo = false) {
   hipStream_t st = c->post;
-  const float *heat = c->d_heat_r[set % RING];
+  const float *heat = s.d_heat;
   const int collect = redo ? 0 : 1;   // first batch: survivors are listed as they are decided; continuation: the list was cleared, re-collect everything
   // a submission's first batch: n_launch - 1 round launches, then the one-workgroup-per-image kernel that finishes the stragglers
   // (nms_finish_kernel); the host's continuation (redo): round launches only
@@ -184,7 +183,7 @@ int launch_nms_rounds(spvo_ctx *c, int nimg, const NmsPair &np, int set, int n_l
   }
   if (redo) hipLaunchKernelGGL(nms_collect_kernel, dim3(NMS_GRID, nimg), dim3(256), 0, st, heat, c->H, c->W, c->cfg.border_remove, c->surv_cap, np);
   hipLaunchKernelGGL(nms_rank_kernel, dim3(128, nimg), dim3(256), 0, st, c->surv_cap, np);
-  hipLaunchKernelGGL(nms_write_kernel, dim3(32, nimg), dim3(256), 0, st, c->H, c->cfg.max_keypoints, c->surv_cap, np, zero_next, c->h_counters_r[set % RING]);
+  hipLaunchKernelGGL(nms_write_kernel, dim3(32, nimg), dim3(256), 0, st, c->H, c->cfg.max_keypoints, c->surv_cap, np, zero_next, s.h_counters);
   HIP_TRY(c, hipGetLastError());
   return SPVO_OK;
 }
@@ -198,10 +197,10 @@ int launch_nms_rounds(spvo_ctx *c, int nimg, const NmsPair &np, int set, int n_l
 // nms_settle runs after the caller's wait and reports whether it had to redo work (the caller then re-runs what depends on the keypoints).
 
 // more rounds for the (rare) submissions whose first batch left candidates undecided
-int nms_settle(spvo_ctx *c, int nimg, const NmsPair &np, int set, bool *redone) {
+int nms_settle(spvo_ctx *c, int nimg, const NmsPair &np, const SubmitSet &s, bool *redone) {
   int last = c->nms_first;
   *redone = false;
-  const int *hc = c->h_counters_r[set % RING];
+  const int *hc = s.h_counters;
   for (;;) {
     bool pending = false;
     for (int i = 0; i < nimg; ++i) pending |= hc[i * NMS_COUNTER_INTS + 8 + last - 1] != 0;
@@ -211,7 +210,7 @@ int nms_settle(spvo_ctx *c, int nimg, const NmsPair &np, int set, bool *redone) 
     last = NMS_MAX_LAUNCH;
     for (int i = 0; i < nimg; ++i)   // keep n_cand, clear the rest of the block
       HIP_TRY(c, hipMemsetAsync(np.b[i].counters + 1, 0, (NMS_COUNTER_INTS - 1) * sizeof(int), c->post));
-    int rc = launch_nms_rounds(c, nimg, np, set, last, nullptr, true);
+    int rc = launch_nms_rounds(c, nimg, np, s, last, nullptr, true);
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->post));
   }
@@ -220,17 +219,18 @@ int nms_settle(spvo_ctx *c, int nimg, const NmsPair &np, int set, bool *redone) 
   return SPVO_OK;
 }
 
-// stand-alone entry (heat map already in d_heat): threshold + rounds, synchronous
+// stand-alone entry (heat map already in the set's d_heat): threshold + rounds, synchronous
 int run_nms(spvo_ctx *c, int nimg) {
-  const NmsPair np = nms_pair(c, RING);   // its own counter set: the submissions' blocks stay clean
+  SubmitSet &s = standalone(c);
+  const NmsPair np = nms_pair(s, c->d_counters_alone);   // its own counter block: the submissions' blocks stay clean
   for (int i = 0; i < nimg; ++i) HIP_TRY(c, hipMemsetAsync(np.b[i].counters, 0, NMS_COUNTER_INTS * sizeof(int), c->stream));
   dim3 grid((c->W + 63) / 64, (c->H + 3) / 4, nimg);
-  hipLaunchKernelGGL(nms_threshold_kernel, grid, dim3(256), 0, c->stream, c->d_heat, c->H, c->W, c->cfg.conf_thresh, np);
-  int rc = launch_nms_rounds(c, nimg, np, RING, c->nms_first, nullptr);
+  hipLaunchKernelGGL(nms_threshold_kernel, grid, dim3(256), 0, c->stream, s.d_heat, c->H, c->W, c->cfg.conf_thresh, np);
+  int rc = launch_nms_rounds(c, nimg, np, s, c->nms_first, nullptr);
   if (rc) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   bool redone;
-  return nms_settle(c, nimg, np, RING, &redone);
+  return nms_settle(c, nimg, np, s, &redone);
 }
 
 }  // namespace spvo_int
@@ -312,9 +312,10 @@ int spvo_heatmap(spvo_ctx *c, const float *det, float *heat) {
   if (int rc = require_idle(c)) return rc;
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   HIP_TRY(c, hipMemcpyAsync(c->d_det_dense, det, (size_t)65 * c->Hc * c->Wc * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(heatmap_kernel<false>, dim3((c->Wc + 63) / 64, (c->Hc + 3) / 4, 1), dim3(256), 0, c->stream, c->d_det_dense, c->d_heat, c->Hc, c->Wc, 0, 0);
+  float *d_heat = standalone(c).d_heat;
+  hipLaunchKernelGGL(heatmap_kernel<false>, dim3((c->Wc + 63) / 64, (c->Hc + 3) / 4, 1), dim3(256), 0, c->stream, c->d_det_dense, d_heat, c->Hc, c->Wc, 0, 0);
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(heat, c->d_heat, (size_t)c->H * c->W * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(heat, d_heat, (size_t)c->H * c->W * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return SPVO_OK;
 }
@@ -323,11 +324,11 @@ int spvo_nms(spvo_ctx *c, const float *heat, int32_t *xy, int *n) {
   if (!c || !heat || !xy || !n) return fail(c, SPVO_ERR_INVALID, "null argument");
   if (int rc = require_idle(c)) return rc;
   HIP_TRY(c, hipSetDevice(c->cfg.device));
-  HIP_TRY(c, hipMemcpyAsync(c->d_heat, heat, (size_t)c->H * c->W * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(standalone(c).d_heat, heat, (size_t)c->H * c->W * sizeof(float), hipMemcpyHostToDevice, c->stream));
   int rc = run_nms(c, 1);
   if (rc) return rc;
-  *n = c->h_counters[2];
-  HIP_TRY(c, hipMemcpy(xy, c->nms[0].b.out_xy, (size_t)(*n) * 2 * sizeof(int), hipMemcpyDeviceToHost));
+  *n = standalone(c).h_counters[2];
+  HIP_TRY(c, hipMemcpy(xy, standalone(c).nms[0].out_xy, (size_t)(*n) * 2 * sizeof(int), hipMemcpyDeviceToHost));
   return SPVO_OK;
 }
 
@@ -351,14 +352,14 @@ int spvo_sample_descriptors(spvo_ctx *c, const float *desc_nhwc, const int32_t *
   return SPVO_OK;
 }
 
-// ring: the submission's own set (keypoint mirror); tring / img0: whose network outputs hold this pair's descriptor maps, and where
-static int enqueue_sample(spvo_ctx *c, const int slots[2], const NmsPair &np, int ring, int tring, int img0) {
+// set: the submission's own (keypoint mirror); tring / img0: whose network outputs hold this pair's descriptor maps, and where
+static int enqueue_sample(spvo_ctx *c, const int slots[2], const NmsPair &np, SubmitSet &set, int tring, int img0) {
   const Tensor &ts = c->tensors[c->t_desc];
-  const float *desc = (ts.dr[tring] ? ts.dr[tring] : ts.d) + (size_t)img0 * ts.per_image;
+  const float *desc = ring_ptr(ts, tring, img0);
   ScopedStage ss(c, stage_id(c, "sample"));
   const int cap = c->cfg.max_keypoints;
   // the keypoints as floats go straight into the set's pinned mirror (8 bytes per keypoint), not through a staging buffer and a copy
-  float *stage = c->h_xy_r[ring];
+  float *stage = set.h_xy;
   SampleJobs sj;
   for (int i = 0; i < 2; ++i) {
     FeatureSlot &s = c->slots[slots[i]];
@@ -372,37 +373,37 @@ static int enqueue_sample(spvo_ctx *c, const int slots[2], const NmsPair &np, in
 }
 
 // descriptors of a host-image submission -> the set's pinned mirror, on `st` (a copy kernel: posted PCIe writes, no SDMA engine)
-static int enqueue_desc_mirror(spvo_ctx *c, const int slots[2], int ring, hipStream_t st) {
+static int enqueue_desc_mirror(spvo_ctx *c, const int slots[2], SubmitSet &set, hipStream_t st) {
   const int cap = c->cfg.max_keypoints;
   MirrorDescJob mj;
   for (int i = 0; i < 2; ++i) {
     const FeatureSlot &s = c->slots[slots[i]];
-    mj.src[i] = s.d_desc; mj.n[i] = s.d_n; mj.dst[i] = c->h_desc_r[ring] + (size_t)i * cap * 256;
+    mj.src[i] = s.d_desc; mj.n[i] = s.d_n; mj.dst[i] = set.h_desc + (size_t)i * cap * 256;
   }
   hipLaunchKernelGGL(mirror_desc_kernel, dim3(32, 2), dim3(256), 0, st, mj);
   HIP_TRY(c, hipGetLastError());
   return SPVO_OK;
 }
 
-static int enqueue_prematch(spvo_ctx *c, int slot_l, int slot_r, int prev_l, int ring) {
+static int enqueue_prematch(spvo_ctx *c, int slot_l, int slot_r, int prev_l, SubmitSet &set) {
   const int cap = c->cfg.max_keypoints;
   const int partner[2] = {slot_r, prev_l};
   MatchReq req[2];
   int nj = 0;
   for (int k = 0; k < 2; ++k) {
-    MatchCache &mc = c->mcache[ring][k];
+    MatchCache &mc = set.mcache[k];
     mc.valid = false;
     if (partner[k] < 0) continue;
     FeatureSlot &a = c->slots[slot_l], &b = c->slots[partner[k]];
     req[nj] = MatchReq{a.d_desc, b.d_desc, cap, cap, a.d_n, b.d_n, a.d_sqn, b.d_sqn};
-    MatchCache &dst = c->mcache[ring][nj];   // job nj's result lands in cache entry nj
+    MatchCache &dst = set.mcache[nj];   // job nj's result lands in cache entry nj
     dst.slot_a = slot_l; dst.slot_b = partner[k];
     dst.selector = c->pm_selector; dst.cross = c->pm_cross; dst.ratio = c->pm_ratio;
     dst.valid = true;   // generations are stamped after the slots' counts are known
     ++nj;
   }
   if (nj == 0) return SPVO_OK;
-  return enqueue_matches(c, req, nj, c->pm_selector, c->pm_cross, c->pm_ratio, c->h_match_out[ring]);
+  return enqueue_matches(c, req, nj, c->pm_selector, c->pm_cross, c->pm_ratio, set.h_match_out);
 }
 
 // Submission = network on `stream`, then the tail (heat map + NMS, sampling, the two matches and
@@ -444,29 +445,30 @@ static int detect_submit(spvo_ctx *c, const uint8_t *d_l, const uint8_t *d_r, in
     if (rc0) return rc0;
   }
   const int ring = (int)(c->submit_count++ % RING);
-  for (auto &mc : c->mcache[ring]) mc.valid = false;
+  SubmitSet &set = c->sets[ring];
+  for (auto &mc : set.mcache) mc.valid = false;
   // The bulk results a host-image submission takes back (`extras`) are WRITTEN into the set's pinned mirrors by kernels (posted PCIe
   // writes), never copied behind events: a device-to-host copy waiting for its event occupies an SDMA queue, and the NEXT pair's image
   // upload queued on the same engine waits with it (round 3: bench.py's look-ahead leg 0.95 ms per frame, the same calls from
   // tools/sync_leg.py 0.81, depending on the process's copy history).
   if (host_l) {   // pageable -> pinned (host copy), pinned -> device (ONE DMA on the network stream): the caller's buffers are free on return
     const size_t bytes = (size_t)(rows - 1) * stride + cols;   // what is the caller's of a strided view: not the last row's padding
-    std::memcpy(c->h_img_r[ring], host_l, bytes);
-    std::memcpy(c->h_img_r[ring] + c->img_cap_r, host_r, bytes);
+    std::memcpy(set.h_img, host_l, bytes);
+    std::memcpy(set.h_img + c->img_cap_r, host_r, bytes);
     // both images in one copy (the staging buffers of a set are contiguous, left then right): two copies were 17 + 16 us with 9 us
     // between them on the synchronous path's critical path (profiles/r04_sync_timeline.log)
     // ... on the SOLVER's stream when the pair's trunk will only queue behind another one: the copy then runs at once, beside the
     // running trunk, instead of between two trunks on the network stream, which only waits for its event (look-ahead leg 1313 ->
     // 1332-1343 frames/s; no device-to-host copy shares that engine any more: the bulk results leave through copy kernels).
     // Tuning "upload_side" = 0: always on the network stream.
-    const bool up_side = tuning("upload_side", 1) != 0 && c->last_launch_ring >= 0 && hipEventQuery(c->ev_net[c->last_launch_ring]) == hipErrorNotReady;
-    HIP_TRY(c, hipMemcpyAsync(c->d_img_r[ring], c->h_img_r[ring], c->img_cap_r + bytes, hipMemcpyHostToDevice, up_side ? c->stream2 : c->stream));
+    const bool up_side = tuning("upload_side", 1) != 0 && c->last_launch_ring >= 0 && hipEventQuery(c->sets[c->last_launch_ring].ev_net) == hipErrorNotReady;
+    HIP_TRY(c, hipMemcpyAsync(set.d_img, set.h_img, c->img_cap_r + bytes, hipMemcpyHostToDevice, up_side ? c->stream2 : c->stream));
     if (up_side) {
-      HIP_TRY(c, hipEventRecord(c->ev_up[ring], c->stream2));
-      HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_up[ring], 0));
+      HIP_TRY(c, hipEventRecord(set.ev_up, c->stream2));
+      HIP_TRY(c, hipStreamWaitEvent(c->stream, set.ev_up, 0));
     }
-    srcs[0] = c->d_img_r[ring];
-    srcs[1] = c->d_img_r[ring] + c->img_cap_r;
+    srcs[0] = set.d_img;
+    srcs[1] = set.d_img + c->img_cap_r;
   }
   // ---- phase A, at once: the pair's images into the network's input planes (images 2 * position in the group, + 1).  Same stream as
   // the trunks: it runs behind the trunk that is using the input planes now.
@@ -488,7 +490,7 @@ static int detect_submit(spvo_ctx *c, const uint8_t *d_l, const uint8_t *d_r, in
     ScopedStage sp(c, stage_id(c, "preprocess"));
     // the resized u8 images (what nn.cpp:154 pushes to images_dq) stay in device memory here: one byte per thread into pinned host
     // memory made this kernel 31 us instead of 8, in front of the whole network
-    int rc = launch_preprocess(c, srcs[0], srcs[1], 2, rows, cols, stride, g, 2 * pos, (extras & 1) ? c->d_resized_r[ring] : nullptr);
+    int rc = launch_preprocess(c, srcs[0], srcs[1], 2, rows, cols, stride, g, 2 * pos, (extras & 1) ? set.d_resized : nullptr);
     if (rc) return rc;
   }
   for (int i = 0; i < 2; ++i) c->slots[slots[i]].filled = true;
@@ -498,12 +500,12 @@ static int detect_submit(spvo_ctx *c, const uint8_t *d_l, const uint8_t *d_r, in
   pd.rows = rows; pd.cols = cols;
   pd.slot_l = slot_l; pd.slot_r = slot_r; pd.prev_l = prev_l; pd.ring = ring; pd.extras = extras; pd.early_res = (extras & 1) != 0;
   pd.launched = false; pd.img0 = 2 * pos; pd.tring = ring;
-  if (c->pre_fused) { pd.pre_pending = true; pd.src[0] = srcs[0]; pd.src[1] = srcs[1]; pd.res_dst = (extras & 1) ? c->d_resized_r[ring] : nullptr; pd.stride = stride; }
+  if (c->pre_fused) { pd.pre_pending = true; pd.src[0] = srcs[0]; pd.src[1] = srcs[1]; pd.res_dst = (extras & 1) ? set.d_resized : nullptr; pd.stride = stride; }
   c->pendq.push_back(pd);
   c->held += 1;
   // ---- phases B and C now, unless the pair may wait for a partner: pairing is on, it is the first of its group, and an earlier
   // trunk is still queued or running (so nothing idles while it waits)
-  const bool earlier_trunk_pending = c->last_launch_ring >= 0 && hipEventQuery(c->ev_net[c->last_launch_ring]) == hipErrorNotReady;
+  const bool earlier_trunk_pending = c->last_launch_ring >= 0 && hipEventQuery(c->sets[c->last_launch_ring].ev_net) == hipErrorNotReady;
   // (tuning "pair_always" = 0: only while an earlier trunk is queued or running.  Holding the first pair of a group unconditionally costs
   // nothing where the GPU bounds the step -- the stream is never idle there -- and where the HOST does (FP16 / INT8 engines: ~35 launches of
   // ~4 us per pair against 0.1 ms of network) it halves the trunk's launches per pair: config 3 4050-4200 -> 4230-4520 frames/s, the
@@ -515,7 +517,7 @@ static int detect_submit(spvo_ctx *c, const uint8_t *d_l, const uint8_t *d_r, in
 extern "C++" {
 namespace spvo_int {
 int release_held_if_idle(spvo_ctx *c) {
-  if (c->held != 1 || c->pair_always || (c->last_launch_ring >= 0 && hipEventQuery(c->ev_net[c->last_launch_ring]) == hipErrorNotReady)) return SPVO_OK;
+  if (c->held != 1 || c->pair_always || (c->last_launch_ring >= 0 && hipEventQuery(c->sets[c->last_launch_ring].ev_net) == hipErrorNotReady)) return SPVO_OK;
   return launch_group(c);
 }
 }  // namespace spvo_int
@@ -559,22 +561,23 @@ static int launch_trunk(spvo_ctx *c, PendingDetect *const *mem, int n, bool head
     ScopedStage net(c, stage_id(c, "net"));
     // launch segment T: the group's trunk (and its heads where they stay on the network stream) -- not for a group whose first layer also
     // preprocesses (its arguments are the caller's image pointers) or whose resized images leave through the tail stream in between
-    if (!mem[0]->pre_pending && !any_res) seg_begin(c, &c->seg_T[tring][n - 1], c->stream);
+    if (!mem[0]->pre_pending && !any_res) seg_begin(c, &c->sets[tring].seg_T[n - 1], c->stream);
     rc = mem[0]->pre_pending ? launch_first_pre(c, mem, n, c->stream) : run_ops(c, batch, 0, std::min<size_t>(1, c->head_start), c->stream);
     for (int m = 0; m < n; ++m) mem[m]->pre_pending = false;
     // The resized images leave for their sets' pinned mirrors UNDER the network: a copy kernel (16 bytes per lane, no SDMA engine involved)
     // on the TAIL stream behind the FIRST layer -- beside it (conv1a is bound by its 217 MB of stores) the copy made that layer 54 us
     // instead of 37 -- i.e. beside conv1b, which leaves 12 CUs free and does not notice
     if (!rc && any_res) {
-      HIP_TRY(c, hipEventRecord(c->ev_pre[tring], c->stream));
-      HIP_TRY(c, hipStreamWaitEvent(c->stream_t, c->ev_pre[tring], 0));
+      HIP_TRY(c, hipEventRecord(c->sets[tring].ev_pre, c->stream));
+      HIP_TRY(c, hipStreamWaitEvent(c->stream_t, c->sets[tring].ev_pre, 0));
       const size_t n16 = ((size_t)2 * c->H * c->W + 15) / 16;   // (the buffers are allocated in multiples of 256 bytes)
       for (int m = 0; m < n; ++m) {
         if (!mem[m]->early_res) continue;
+        SubmitSet &set = c->sets[mem[m]->ring];
         hipLaunchKernelGGL(mirror_copy_kernel, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 64)), dim3(256), 0, c->stream_t,
-                           reinterpret_cast<const uint4 *>(c->d_resized_r[mem[m]->ring]), reinterpret_cast<uint4 *>(c->h_resized_r[mem[m]->ring]), n16);
+                           reinterpret_cast<const uint4 *>(set.d_resized), reinterpret_cast<uint4 *>(set.h_resized), n16);
         HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipEventRecord(c->ev_res[mem[m]->ring], c->stream_t));
+        HIP_TRY(c, hipEventRecord(set.ev_res, c->stream_t));
       }
     }
     if (!rc) rc = run_ops(c, batch, std::min<size_t>(1, c->head_start), c->head_start, c->stream);
@@ -589,21 +592,21 @@ static int launch_trunk(spvo_ctx *c, PendingDetect *const *mem, int n, bool head
   { const int rce = seg_end(c); if (!rc) rc = rce; }   // segment T goes out here: one graph launch, or its kernels one by one
   if (rc) return rc;
   if (c->trunk_timing) c->tdiag.trunk_end(c->stream);
-  for (int m = 0; m < n; ++m) HIP_TRY(c, hipEventRecord(c->ev_net[mem[m]->ring], c->stream));
+  for (int m = 0; m < n; ++m) HIP_TRY(c, hipEventRecord(c->sets[mem[m]->ring].ev_net, c->stream));
   c->last_launch_ring = mem[n - 1]->ring;
   return SPVO_OK;
 }
 
 // the heads on the (first pair's) tail stream, reading this group's ring buffers; a second pair on the other tail stream waits for them
 static int launch_heads_on_tail(spvo_ctx *c, PendingDetect *const *mem, int n, const hipStream_t tstreams[2]) {
-  const int tring = mem[0]->ring;
+  SubmitSet &tset = c->sets[mem[0]->ring];
   hipStream_t ts0 = tstreams[mem[0]->ts];
-  seg_begin(c, &c->seg_H[tring][n - 1], ts0);   // launch segment H: the heads
+  seg_begin(c, &tset.seg_H[n - 1], ts0);   // launch segment H: the heads
   int rc = run_ops(c, 2 * n, c->head_start, c->ops.size(), ts0);
   { const int rce = seg_end(c); if (!rc) rc = rce; }
   if (!rc && n == 2 && mem[1]->ts != mem[0]->ts) {
-    HIP_TRY(c, hipEventRecord(c->ev_heads[tring], ts0));
-    HIP_TRY(c, hipStreamWaitEvent(tstreams[mem[1]->ts], c->ev_heads[tring], 0));
+    HIP_TRY(c, hipEventRecord(tset.ev_heads, ts0));
+    HIP_TRY(c, hipStreamWaitEvent(tstreams[mem[1]->ts], tset.ev_heads, 0));
   }
   return rc;
 }
@@ -613,36 +616,37 @@ static int launch_heads_on_tail(spvo_ctx *c, PendingDetect *const *mem, int n, c
 static int launch_pair_tail(spvo_ctx *c, PendingDetect &pd, int tring, hipStream_t tsm, hipEvent_t &det_e0, hipStream_t ts_next) {
   const Tensor &td = c->tensors[c->t_det];
   const int ring = pd.ring, slots[2] = {pd.slot_l, pd.slot_r};
+  SubmitSet &set = c->sets[ring];
   pd.tring = tring;
-  const NmsPair np = nms_pair(c, ring);
+  const NmsPair np = nms_pair(set, set.d_counters);
   c->post = tsm;
   c->ms_set = pd.ts;
   // launch segment A: heat map, NMS rounds + finish, rank, write, sampling -- eight dependent kernels up to ev_feat
-  seg_begin(c, &c->seg_A[ring], tsm);
+  seg_begin(c, &set.seg_A, tsm);
   {
     // heat map + threshold + candidate list in one kernel; the counter block of this set was
     // zeroed by the previous submission's last NMS kernel (or at allocation)
     ScopedStage sh(c, stage_id(c, "heatmap"));
-    hipLaunchKernelGGL(heatmap_nms_kernel, dim3((c->Wc + 63) / 64, (c->Hc + 3) / 4, 2), dim3(256), 0, c->post, td.dr[tring] + (size_t)pd.img0 * td.per_image, c->d_heat_r[ring],
+    hipLaunchKernelGGL(heatmap_nms_kernel, dim3((c->Wc + 63) / 64, (c->Hc + 3) / 4, 2), dim3(256), 0, c->post, ring_ptr(td, tring, pd.img0), set.d_heat,
                        c->Hc, c->Wc, td.hp, td.wp, c->cfg.conf_thresh, np);
     HIP_TRY(c, hipGetLastError());
   }
   int rc;
   {
     ScopedStage sn(c, stage_id(c, "nms"));
-    rc = launch_nms_rounds(c, 2, np, ring, c->nms_first, c->d_counters_all + (size_t)(((ring + c->tail_streams) % RING) * 2) * NMS_COUNTER_INTS);
+    rc = launch_nms_rounds(c, 2, np, set, c->nms_first, c->sets[(ring + c->tail_streams) % RING].d_counters);   // (zeroes the block of the next set on this stream)
   }
-  if (!rc) rc = enqueue_sample(c, slots, np, ring, tring, pd.img0);
+  if (!rc) rc = enqueue_sample(c, slots, np, set, tring, pd.img0);
   { const int rce = seg_end(c); if (!rc) rc = rce; }
   // Keypoints, counts and descriptors are final here: spvo_detect_wait / _collect waits for THIS point (ev_feat); the matches enqueued
   // behind it are waited for where they are asked for (spvo_match_slots, ev_tail).
-  if (!rc) rc = dev_check(c, hipEventRecord(c->ev_feat[ring], tsm), "hipEventRecord");
+  if (!rc) rc = dev_check(c, hipEventRecord(set.ev_feat, tsm), "hipEventRecord");
   if (!rc && c->prematch) {
     // (two tail streams: the temporal partner's features come from the submission before, on the other stream)
-    if (c->tail_streams == 2 && pd.prev_l >= 0) HIP_TRY(c, hipStreamWaitEvent(tsm, c->ev_feat[(ring + RING - 1) % RING], 0));
+    if (c->tail_streams == 2 && pd.prev_l >= 0) HIP_TRY(c, hipStreamWaitEvent(tsm, c->sets[(ring + RING - 1) % RING].ev_feat, 0));
     // launch segment B: the pair's two matches (distance GEMM + merge; the fp8 shortlist's conversions and re-rank)
-    seg_begin(c, &c->seg_B[ring], tsm);
-    rc = enqueue_prematch(c, pd.slot_l, pd.slot_r, pd.prev_l, ring);
+    seg_begin(c, &set.seg_B, tsm);
+    rc = enqueue_prematch(c, pd.slot_l, pd.slot_r, pd.prev_l, set);
     { const int rce = seg_end(c); if (!rc) rc = rce; }
   }
   if (!rc && det_e0) {   // "detect" spans both streams: first kernel on `stream` .. last kernel on the tail stream
@@ -652,7 +656,7 @@ static int launch_pair_tail(spvo_ctx *c, PendingDetect &pd, int tring, hipStream
     det_e0 = nullptr;
     if (ts_next) { det_e0 = get_event(c); (void)hipEventRecord(det_e0, ts_next); }   // (an event is timed once)
   }
-  if (!rc) rc = dev_check(c, hipEventRecord(c->ev_tail[ring], tsm), "hipEventRecord");
+  if (!rc) rc = dev_check(c, hipEventRecord(set.ev_tail, tsm), "hipEventRecord");
   // The descriptors a host-image submission takes back (extras bit 1: 2 x 1 MB) leave for the set's pinned mirror BEHIND the
   // matches, on the tail stream (a stream of their own had them share a hardware queue with the network stream in processes that had
   // created and destroyed contexts before -- the runtime deals streams onto four queues -- and bench.py's look-ahead leg fell from
@@ -660,8 +664,8 @@ static int launch_pair_tail(spvo_ctx *c, PendingDetect &pd, int tring, hipStream
   // made it 40 us instead of 4 in front of ev_feat; beside the matches the copy kernel (44 us of PCIe writes) made the distance GEMM
   // 55 us instead of 20.  ev_copy = they have arrived (spvo_detect_mirrors_wait; spvo_detect_collect waits for it itself).
   if (!rc && (pd.extras & 2)) {
-    rc = enqueue_desc_mirror(c, slots, ring, tsm);
-    if (!rc) HIP_TRY(c, hipEventRecord(c->ev_copy[ring], tsm));
+    rc = enqueue_desc_mirror(c, slots, set, tsm);
+    if (!rc) HIP_TRY(c, hipEventRecord(set.ev_copy, tsm));
   }
   if (!rc) pd.launched = true;
   return rc;
@@ -699,8 +703,8 @@ static int launch_group_body(spvo_ctx *c) {
   const hipStream_t tstreams[2] = {c->stream_t, c->tail_streams == 2 ? c->stream_tb : c->stream_t};
   for (int m = 0; m < n; ++m) mem[m]->ts = c->tail_streams == 2 ? (mem[m]->ring & 1) : 0;
   hipStream_t ts0 = tstreams[mem[0]->ts];
-  HIP_TRY(c, hipStreamWaitEvent(ts0, c->ev_net[tring], 0));
-  if (n == 2 && mem[1]->ts != mem[0]->ts) HIP_TRY(c, hipStreamWaitEvent(tstreams[mem[1]->ts], c->ev_net[tring], 0));
+  HIP_TRY(c, hipStreamWaitEvent(ts0, c->sets[tring].ev_net, 0));
+  if (n == 2 && mem[1]->ts != mem[0]->ts) HIP_TRY(c, hipStreamWaitEvent(tstreams[mem[1]->ts], c->sets[tring].ev_net, 0));
   if (c->trunk_timing) c->tdiag.tail_begin(ts0);
   c->post = ts0;
   if (!heads_on_net && (rc = launch_heads_on_tail(c, mem, n, tstreams))) return rc;
@@ -735,6 +739,7 @@ static int detect_wait(spvo_ctx *c, double P_l[12], double P_r[12], spvo_feature
     }
   }
   const PendingDetect pd = c->pendq.front();
+  SubmitSet &set = c->sets[pd.ring];
   const int slots[2] = {pd.slot_l, pd.slot_r};
   const int cap = c->cfg.max_keypoints;
   uint8_t *res[2] = {resized_l, resized_r};
@@ -765,20 +770,20 @@ static int detect_wait(spvo_ctx *c, double P_l[12], double P_r[12], spvo_feature
   } else {
     // only this submission's tail: a younger one may be queued behind it on both streams
     const double tw0 = diag_now_us();
-    rc = dev_check(c, wait_event(c->ev_feat[pd.ring]), "event synchronisation");
+    rc = dev_check(c, wait_event(set.ev_feat), "event synchronisation");
     g_diag.max_tail_wait = std::max(g_diag.max_tail_wait, diag_now_us() - tw0);
     g_diag.iv_tail += diag_now_us() - tw0;
   }
-  if (!rc && pd.early_res) rc = dev_check(c, wait_event(c->ev_res[pd.ring]), "event synchronisation");   // the resized images: they left under the network (copy kernel on the tail stream)
+  if (!rc && pd.early_res) rc = dev_check(c, wait_event(set.ev_res), "event synchronisation");   // the resized images: they left under the network (copy kernel on the tail stream)
   bool redone = false;
-  const NmsPair np = nms_pair(c, pd.ring);
-  if (!rc) rc = nms_settle(c, 2, np, pd.ring, &redone);
+  const NmsPair np = nms_pair(set, set.d_counters);
+  if (!rc) rc = nms_settle(c, 2, np, set, &redone);
   if (!rc && (redone || pd.rematch)) {   // rare: keypoints changed after the first batch -> redo what depends on them
     if (pd.rematch) c->stages[stage_id(c, "rematch")].calls += 1;
-    if (redone && (pd.extras & 2)) (void)wait_event(c->ev_copy[pd.ring]);   // the mirror of the superseded descriptors has landed: the new one goes on top
-    if (redone) rc = enqueue_sample(c, slots, np, pd.ring, pd.tring, pd.img0);
-    if (!rc && redone && (pd.extras & 2)) rc = enqueue_desc_mirror(c, slots, pd.ring, c->post);
-    if (!rc && c->prematch) rc = enqueue_prematch(c, pd.slot_l, pd.slot_r, pd.prev_l, pd.ring);
+    if (redone && (pd.extras & 2)) (void)wait_event(set.ev_copy);   // the mirror of the superseded descriptors has landed: the new one goes on top
+    if (redone) rc = enqueue_sample(c, slots, np, set, pd.tring, pd.img0);
+    if (!rc && redone && (pd.extras & 2)) rc = enqueue_desc_mirror(c, slots, set, c->post);
+    if (!rc && c->prematch) rc = enqueue_prematch(c, pd.slot_l, pd.slot_r, pd.prev_l, set);
     if (!rc && extras) rc = copy_extras();
     if (!rc) rc = dev_check(c, hipStreamSynchronize(tsw), "stream synchronisation");
     if (redone)
@@ -788,30 +793,30 @@ static int detect_wait(spvo_ctx *c, double P_l[12], double P_r[12], spvo_feature
   c->post = c->stream;
   c->ms_set = 0;
   if (rc) return rc;
-  const int *hc = c->h_counters_r[pd.ring];
+  const int *hc = set.h_counters;
   for (int i = 0; i < 2; ++i) {
     FeatureSlot &s = c->slots[slots[i]];
     s.n = hc[i * NMS_COUNTER_INTS + 2];
     s.gen += 1;
     if (outs[i]) {
       outs[i]->n = s.n;
-      if (outs[i]->xy && s.n > 0) std::memcpy(outs[i]->xy, c->h_xy_r[pd.ring] + (size_t)i * cap * 2, (size_t)s.n * 2 * sizeof(float));
+      if (outs[i]->xy && s.n > 0) std::memcpy(outs[i]->xy, set.h_xy + (size_t)i * cap * 2, (size_t)s.n * 2 * sizeof(float));
       if (outs[i]->desc && (pd.extras & 2) && s.n > 0) {
-        (void)wait_event(c->ev_copy[pd.ring]);   // the descriptors' mirror (copy kernel behind the matches)
-        std::memcpy(outs[i]->desc, c->h_desc_r[pd.ring] + (size_t)i * cap * 256, (size_t)s.n * 256 * sizeof(float));
+        (void)wait_event(set.ev_copy);   // the descriptors' mirror (copy kernel behind the matches)
+        std::memcpy(outs[i]->desc, set.h_desc + (size_t)i * cap * 256, (size_t)s.n * 256 * sizeof(float));
       }
     }
-    if (res[i] && (pd.extras & 1)) std::memcpy(res[i], c->h_resized_r[pd.ring] + (size_t)i * c->H * c->W, (size_t)c->H * c->W);
+    if (res[i] && (pd.extras & 1)) std::memcpy(res[i], set.h_resized + (size_t)i * c->H * c->W, (size_t)c->H * c->W);
   }
-  for (auto &mc : c->mcache[pd.ring])
+  for (auto &mc : set.mcache)
     if (mc.valid) { mc.gen_a = c->slots[mc.slot_a].gen; mc.gen_b = c->slots[mc.slot_b].gen; }
   if (mirrors)
     for (int i = 0; i < 2; ++i) {
       mirrors->n[i] = c->slots[slots[i]].n;
-      mirrors->xy[i] = c->h_xy_r[pd.ring] + (size_t)i * cap * 2;
-      mirrors->desc[i] = (pd.extras & 2) ? c->h_desc_r[pd.ring] + (size_t)i * cap * 256 : nullptr;
-      mirrors->resized[i] = (pd.extras & 1) ? c->h_resized_r[pd.ring] + (size_t)i * c->H * c->W : nullptr;
-      mirrors->token = pd.ring;
+      mirrors->xy[i] = set.h_xy + (size_t)i * cap * 2;
+      mirrors->desc[i] = (pd.extras & 2) ? set.h_desc + (size_t)i * cap * 256 : nullptr;
+      mirrors->resized[i] = (pd.extras & 1) ? set.h_resized + (size_t)i * c->H * c->W : nullptr;
+      mirrors->token = pd.ring;   // (the set's index: part of the ABI)
     }
   if (P_l) fix_projection(P_l, pd.g, pd.rows, pd.cols, c->cfg.bug_compat_p);
   if (P_r) fix_projection(P_r, pd.g, pd.rows, pd.cols, c->cfg.bug_compat_p);
@@ -822,26 +827,22 @@ static int detect_wait(spvo_ctx *c, double P_l[12], double P_r[12], spvo_feature
 static int ensure_host_sets(spvo_ctx *c, size_t image_bytes) {
   const size_t hw2 = (size_t)2 * c->H * c->W, desc = (size_t)2 * c->cfg.max_keypoints * 256;
   if (!c->host_sets_ready) {   // (a flag of its own: a failure half-way must not look like "allocated" to the next call)
-    for (int r = 0; r < RING; ++r) {
-      if (!c->d_resized_r[r]) { int rc = dev_alloc(c, &c->d_resized_r[r], hw2, false); if (rc) return rc; }
-      if (!c->h_resized_r[r]) HIP_TRY(c, hipHostMalloc((void **)&c->h_resized_r[r], hw2));
-      if (!c->h_desc_r[r]) HIP_TRY(c, hipHostMalloc((void **)&c->h_desc_r[r], desc * sizeof(float)));
+    for (SubmitSet &s : c->sets) {
+      if (!s.d_resized) { int rc = dev_alloc(c, &s.d_resized, hw2, false); if (rc) return rc; }
+      if (!s.h_resized) HIP_TRY(c, hipHostMalloc((void **)&s.h_resized, hw2));
+      if (!s.h_desc) HIP_TRY(c, hipHostMalloc((void **)&s.h_desc, desc * sizeof(float)));
     }
     c->host_sets_ready = true;
   }
   if (image_bytes > c->img_cap_r) {
     if (!c->pendq.empty()) return fail(c, SPVO_ERR_STATE, "the image size grew while submissions are in flight");
     HIP_TRY(c, hipDeviceSynchronize());
-    for (int r = 0; r < RING; ++r) {
-      if (c->d_img_r[r]) (void)hipFree(c->d_img_r[r]);
-      if (c->h_img_r[r]) (void)hipHostFree(c->h_img_r[r]);
-      c->d_img_r[r] = c->h_img_r[r] = nullptr;
-    }
+    for (SubmitSet &s : c->sets) set_release_images(s);
     c->img_cap_r = 0;
-    for (int r = 0; r < RING; ++r) {
-      int rc = dev_alloc(c, &c->d_img_r[r], 2 * image_bytes, false);
+    for (SubmitSet &s : c->sets) {
+      int rc = dev_alloc(c, &s.d_img, 2 * image_bytes, false);
       if (rc) return rc;
-      HIP_TRY(c, hipHostMalloc((void **)&c->h_img_r[r], 2 * image_bytes));
+      HIP_TRY(c, hipHostMalloc((void **)&s.h_img, 2 * image_bytes));
     }
     c->img_cap_r = image_bytes;
   }
@@ -914,7 +915,7 @@ int spvo_detect_mirrors_wait(spvo_ctx *c, const spvo_detect_mirrors *m) {
   if (!c || !m || m->token < 0 || m->token >= RING) return fail(c, SPVO_ERR_INVALID, "bad argument");
   if (!m->desc[0] && !m->desc[1]) return SPVO_OK;
   HIP_TRY(c, hipSetDevice(c->cfg.device));
-  return dev_check(c, wait_event(c->ev_copy[m->token]), "event synchronisation");
+  return dev_check(c, wait_event(c->sets[m->token].ev_copy), "event synchronisation");
 }
 
 int spvo_detect_collect_mirrors(spvo_ctx *c, double P_l[12], double P_r[12], spvo_detect_mirrors *out) {

@@ -2,7 +2,7 @@
 // records, error / profiling helpers and the functions one unit offers the others.  Not installed, not part of the C ABI
 // (include/spvo.h is); everything here has hidden visibility.
 //
-//   spvo_core.hip      context life cycle, engine files (plan loader, weight repacking), profiling entry points
+//   spvo_core.hip      context and submission-set (SubmitSet) life cycle, launch segments, engine files (plan loader, weight repacking), profiling entry points
 //   spvo_net_f32.hip   FP32 engines: direct + Winograd convolution launchers, the layer executor (run_ops)
 //   spvo_net_f16.hip   FP16 engines                     spvo_net_s3.hip   FP32 engines in split (bf16x3) mode
 //   spvo_net_i8.hip    INT8 engines
@@ -93,7 +93,6 @@ struct FeatureSlot {
   int n = 0;
   bool filled = false;      // a submission has written (or is writing) this slot
   int *d_xy = nullptr;      // [cap][2] int
-  float *d_xyf = nullptr;   // [cap][2] float
   float *d_desc = nullptr;  // [cap][256]
   int *d_n = nullptr;       // device copy of n (read by kernels enqueued before the host knows n)
   float *d_sqn = nullptr;   // [cap] squared norms of the descriptors (written by the sampler)
@@ -121,8 +120,33 @@ struct MatchScratch {         // one set per concurrently enqueued match
   int2 *d_out = nullptr;      // packed result, points into spvo_ctx::d_match_out
 };
 
-struct NmsImage {
-  NmsBuffers b;
+// One of the RING buffer sets a detector submission owns from spvo_detect*_submit until a later submission takes the set over: everything its
+// tail writes, the mirrors the host reads its results from, and the events that say when.  Who may touch what:
+//   the tail's kernels (behind ev_net)  nms, d_counters, d_heat, and through them h_counters, h_xy; the matches write h_match_out
+//   the host                            h_counters, h_xy after ev_feat; mcache[].h_out after ev_tail; h_desc after ev_copy; h_resized after ev_res
+//   the network stream                  d_img behind ev_up; d_resized (preprocess / first layer), read by the tail stream's copy behind ev_pre
+// (the network outputs a tail reads are the tensors' own: Tensor::dr[set])
+struct SubmitSet {
+  NmsBuffers nms[2];             // per image (`counters` is filled in per use: nms_pair)
+  int *d_counters = nullptr;     // [2 images][NMS_COUNTER_INTS], inside spvo_ctx::d_counters_all: zeroed by the last NMS kernel of the submission before
+  float *d_heat = nullptr, *d_heat_base = nullptr;   // [2][H][W], inside d_heat_base with a 64-float guard on both sides
+  int *h_counters = nullptr;     // pinned [2][NMS_COUNTER_INTS]
+  float *h_xy = nullptr;         // pinned [2][cap][2]
+  // host-image submissions (spvo_detect_submit): pinned staging + device copies of the two input images (ensure_host_sets: on first use, grown
+  // with the image), a resized-image buffer of its own and pinned mirrors of the resized images and of the descriptors
+  uint8_t *h_img = nullptr, *d_img = nullptr;   // [2][spvo_ctx::img_cap_r]
+  uint8_t *d_resized = nullptr, *h_resized = nullptr;   // [2][H][W]
+  float *h_desc = nullptr;       // pinned [2][cap][256]
+  hipEvent_t ev_net = nullptr;   // the trunk (and the heads that went with it) of the submission's group is done: its tail may start
+  // a submission's tail in two parts: ev_feat = keypoints, counts and descriptors are final (what spvo_detect_wait needs), ev_tail = the
+  // matches enqueued behind them have landed too (what spvo_match_slots needs); ev_copy = the descriptors of a host-image submission have reached their pinned mirror (copy kernel behind the matches)
+  hipEvent_t ev_feat = nullptr, ev_tail = nullptr, ev_copy = nullptr;
+  hipEvent_t ev_pre = nullptr, ev_res = nullptr;   // first layer done (network stream) / resized images on the host (tail stream)
+  hipEvent_t ev_up = nullptr;    // a queued host-image submission's upload, on the solver's stream, has landed (its preprocess kernel waits for it)
+  hipEvent_t ev_heads = nullptr; // the group's heads are done (tail_streams == 2, heads on the tail stream: the second pair's stream waits for it)
+  GraphEntry seg_T[2], seg_H[2], seg_A, seg_B;   // launch segments: trunk / heads per pairs in the group (the set is the group's network set); the two halves of the set's tail
+  MatchCache mcache[2];          // [stereo, temporal]
+  int2 *h_match_out = nullptr;   // pinned [2][cap] (ensure_match)
 };
 
 // what base.cpp:75-119 crops of an image before it resizes it to the network's size, and the resize's scale
@@ -186,7 +210,7 @@ struct spvo_ctx {
   int held = 0;                  // submissions at the back of pendq whose trunk has not been launched yet (0 .. 2: trunk pairing)
   bool pair_trunks = false;      // spvo_set_trunk_pairing
   bool pair_always = true;       // ... the first pair of a group waits for its partner also when the network stream is idle (tuning "pair_always", read at spvo_create)
-  int last_launch_ring = -1;     // ev_net[...] of the newest trunk launched
+  int last_launch_ring = -1;     // the set whose ev_net belongs to the newest trunk launched
   int cur_ring = 0;                // set whose network outputs the running forward pass writes
   unsigned submit_count = 0;
   std::string error;
@@ -195,10 +219,9 @@ struct spvo_ctx {
   bool split_req = false;          // spvo_set_fp32_split / SPVO_FP32_SPLIT: FP32 engines loaded from now on run on the bf16x3 kernels
   bool s3 = false;                 // the loaded FP32 engine runs in split mode
   size_t head_start = 0;           // ops [head_start, end) = the 1x1 heads + L2 norm: a submission runs them on the tail stream
-  // launch segments replayed from HIP graphs (top of this file): on for FP16 / INT8 engines (tuning "graphs": 0 off, 2 on for every engine)
+  // launch segments replayed from HIP graphs (launch_segments.hip.h; the entries are the sets': SubmitSet::seg_*): on for FP16 / INT8 engines (tuning "graphs": 0 off, 2 on for every engine)
   bool use_graphs = false;
   LaunchRecorder rec;
-  GraphEntry seg_T[RING][2], seg_H[RING][2], seg_A[RING], seg_B[RING];   // trunk / heads per (network set, pairs in the group); tail halves per submission set
   bool heads_fused = false;        // ... as ONE launch (heads.hip.h): FP32 engines whose tail is convPb (256 -> 65), convDb (256 -> 256), L2 norm
   bool heads_keep_raw = false;     // the fused launch also stores the un-normalised descriptor planes (spvo_forward / spvo_debug_tensor)
   float *d_heads_w = nullptr;      // pack_heads_weights()
@@ -216,12 +239,8 @@ struct spvo_ctx {
   // post-processing buffers
   float *d_dense_in = nullptr;   // [B][H][W] staging for spvo_forward
   float *d_det_dense = nullptr;  // [B][65][Hc][Wc]
-  float *d_heat = nullptr;       // [B][H][W], inside d_heat_base with a 64-float guard on both sides
-  float *d_heat_base = nullptr;
-  NmsImage nms[2];
   int surv_cap = 0;
   int nms_first = 4;             // NMS launches enqueued with a submission: nms_first - 1 round launches (4 in-kernel rounds each) + the finishing kernel; what that leaves undecided is continued by the host (nms_settle)
-  int *h_counters = nullptr;     // pinned [2][NMS_COUNTER_INTS]
   uint8_t *d_img[2] = {nullptr, nullptr};
   size_t img_cap = 0;
   uint8_t *d_resized = nullptr;  // [2][H][W]
@@ -230,7 +249,6 @@ struct spvo_ctx {
   FeatureSlot slots[N_SLOTS];
   int *d_xy_tmp = nullptr;       // [cap][2] for spvo_sample_descriptors
   float *d_desc_tmp = nullptr;   // [cap][256]
-  float *h_xy = nullptr;         // pinned [2][cap][2]
   int last_slot_l = -1;          // left slot of the previous submission (temporal partner)
 
   // matching scratch
@@ -238,31 +256,13 @@ struct spvo_ctx {
   float *d_ma = nullptr, *d_mb = nullptr;
   MatchScratch ms[2][2];         // [tail stream][stereo, temporal]
   int2 *d_match_out = nullptr;   // [2][cap]: both jobs' results leave in one copy
-  int2 *h_match_out[RING] = {};   // pinned [2][cap] per submission set
   int2 *h_match_tmp = nullptr;   // pinned [cap] for the synchronous entry points
-  int *d_counters_all = nullptr; // [RING sets + 1 stand-alone set][2 images][NMS_COUNTER_INTS]
-  float *d_xy_stage = nullptr;   // [RING][2][cap][2] keypoints of both images as floats: one copy per submission
-  MatchCache mcache[RING][2];    // [submission set][stereo, temporal]
-  // per submission set (index 0 doubles as the stand-alone entry points' set)
-  NmsImage nms_r[RING][2];
-  float *d_heat_r[RING] = {}, *d_heat_base_r[RING] = {};
-  int *h_counters_r[RING] = {};
-  float *h_xy_r[RING] = {};
-  // host-image submissions (spvo_detect_submit): per set, pinned staging + device copies of the two input images, a resized-image
-  // buffer of its own and pinned mirrors of the resized images and of the descriptors
-  uint8_t *h_img_r[RING] = {}, *d_img_r[RING] = {};
-  size_t img_cap_r = 0;          // bytes per image in those buffers
-  uint8_t *d_resized_r[RING] = {}, *h_resized_r[RING] = {};
-  float *h_desc_r[RING] = {};   // [2][cap][256]
-  bool host_sets_ready = false;  // d_resized_r / h_resized_r / h_desc_r of EVERY set are allocated
-  hipEvent_t ev_net[RING] = {}, ev_tail[RING] = {};
-  // a submission's tail in two parts: ev_feat = keypoints, counts and descriptors are final (what spvo_detect_wait needs), ev_tail = the
-  // matches enqueued behind them have landed too (what spvo_match_slots needs); ev_copy = the descriptors of a host-image submission have reached their pinned mirror (copy kernel behind the matches)
-  hipEvent_t ev_feat[RING] = {}, ev_copy[RING] = {};
-  hipEvent_t ev_pre[RING] = {}, ev_res[RING] = {};   // first layer done (network stream) / resized images on the host (tail stream)
-  hipEvent_t ev_up[RING] = {};   // a queued host-image submission's upload, on the solver's stream, has landed (its preprocess kernel waits for it)
+  int *d_counters_all = nullptr; // [RING sets + 1 stand-alone block][2 images][NMS_COUNTER_INTS]: ONE zeroed allocation (a tail zeroes the block of the set behind it)
+  int *d_counters_alone = nullptr;   // ... its last block: the stand-alone entry points' (standalone(), below)
+  SubmitSet sets[RING];          // submission n works in sets[n % RING]
+  size_t img_cap_r = 0;          // bytes per image in the sets' h_img / d_img
+  bool host_sets_ready = false;  // d_resized / h_resized / h_desc of EVERY set are allocated
   hipEvent_t ev_post = nullptr, ev_post_b = nullptr;    // PostScope: orders a synchronous entry point behind what is left on the tail stream(s)
-  hipEvent_t ev_heads[RING] = {};  // the group's heads are done (tail_streams == 2, heads on the tail stream: the second pair's stream waits for it)
   bool match_fp8 = false;        // fp8 shortlist GEMM (approximate; spvo_set_match_fp8)
   bool prematch = false;
   int pm_selector = SPVO_SELECT_KNN, pm_cross = 0;
@@ -426,8 +426,12 @@ struct ScopedStage {
   }
 };
 
-// a tensor's buffer for the submission being enqueued (tensors a tail reads have one per submission set)
-inline float *ring_ptr(spvo_ctx *c, const Tensor &t) { return t.dr[c->cur_ring] ? t.dr[c->cur_ring] : t.d; }
+// a tensor's buffer, from image `img0` on, for submission set `ring` (tensors a tail reads have one per set, the others one for all) / for the forward pass being enqueued
+inline float *ring_ptr(const Tensor &t, int ring, int img0 = 0) { return (t.dr[ring] ? t.dr[ring] : t.d) + (size_t)img0 * t.per_image; }
+inline float *ring_ptr(spvo_ctx *c, const Tensor &t, int img0 = 0) { return ring_ptr(t, c->cur_ring, img0); }
+// The stand-alone entry points (spvo_heatmap, spvo_nms) have no set of their own: index 0 doubles as theirs -- they refuse to run beside
+// submissions (require_idle) -- with the counter block spvo_ctx::d_counters_alone, so that the submissions' blocks stay zeroed.
+inline SubmitSet &standalone(spvo_ctx *c) { return c->sets[0]; }
 
 // post-processing issued by a synchronous entry point while submissions are queued goes behind them
 struct PostScope {
@@ -445,6 +449,13 @@ struct PostScope {
 
 // ---- spvo_core.hip
 void free_plan(spvo_ctx *c);
+// a submission set's life cycle: set_alloc creates what every set has from spvo_create on; set_release frees ALL a set holds and forgets it
+// (the one list of its members), through the three helpers for what is allocated lazily and re-allocated when it grows
+int set_alloc(spvo_ctx *c, int index);
+void set_release(SubmitSet &s);
+void set_release_images(SubmitSet &s);     // h_img, d_img (ensure_host_sets)
+void set_release_match(SubmitSet &s);      // h_match_out and the cache entries that point into it (ensure_match)
+void set_release_segments(SubmitSet &s);   // the graphs of its launch segments (seg_free_all)
 // ---- spvo_net_*.hip
 int launch_conv16(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t stream);
 int launch_conv_s3(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t stream);

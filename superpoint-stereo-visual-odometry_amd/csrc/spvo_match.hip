@@ -19,10 +19,9 @@ int ensure_match(spvo_ctx *c, int na, int nb) {
       drop(m.d_na); drop(m.d_nb); drop(m.d_best_d2); drop(m.d_dt); drop(m.d_cand); drop(m.d_meta); drop(m.d_best_idx); drop(m.d_train_best); drop(m.d_a8); drop(m.d_b8); drop(m.d_qa8); drop(m.d_qb8);
       m.d_out = nullptr;
     }
-  for (auto &p : c->h_match_out) { if (p) (void)hipHostFree(p); p = nullptr; }
+  for (SubmitSet &s : c->sets) set_release_match(s);
   if (c->h_match_tmp) (void)hipHostFree(c->h_match_tmp);
   c->h_match_tmp = nullptr;
-  for (auto &set : c->mcache) for (auto &mc : set) { mc.valid = false; mc.h_out = nullptr; }
   int rc;
   if ((rc = dev_alloc(c, &c->d_ma, (size_t)cap * MATCH_D))) return rc;
   if ((rc = dev_alloc(c, &c->d_mb, (size_t)cap * MATCH_D))) return rc;
@@ -45,13 +44,11 @@ int ensure_match(spvo_ctx *c, int na, int nb) {
     if ((rc = dev_alloc(c, &m.d_qb8, cap))) return rc;
     m.d_out = c->d_match_out + (size_t)k4 * cap;
   }
-  for (int r = 0; r < RING; ++r) HIP_TRY(c, hipHostMalloc((void **)&c->h_match_out[r], (size_t)2 * cap * sizeof(int2)));
+  for (SubmitSet &s : c->sets) {
+    HIP_TRY(c, hipHostMalloc((void **)&s.h_match_out, (size_t)2 * cap * sizeof(int2)));
+    for (int k = 0; k < 2; ++k) s.mcache[k].h_out = s.h_match_out + (size_t)k * cap;   // (not valid: set_release_match)
+  }
   HIP_TRY(c, hipHostMalloc((void **)&c->h_match_tmp, (size_t)cap * sizeof(int2)));
-  for (int par = 0; par < RING; ++par)
-    for (int k = 0; k < 2; ++k) {
-      c->mcache[par][k].h_out = c->h_match_out[par] + (size_t)k * cap;
-      c->mcache[par][k].valid = false;
-    }
   c->match_cap = cap;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return SPVO_OK;
@@ -240,12 +237,12 @@ int spvo_match_slots(spvo_ctx *c, int slot_a, int slot_b, int selector, int cros
     bool inflight = false;
     for (const auto &q : c->pendq) inflight |= q.ring == set;
     if (inflight) continue;   // that set belongs to a submission in flight
-    for (const auto &mc : c->mcache[set])
+    for (const auto &mc : c->sets[set].mcache)
       if (mc.valid && mc.slot_a == slot_a && mc.slot_b == slot_b && mc.gen_a == a.gen && mc.gen_b == b.gen && mc.selector == selector &&
           mc.cross == (cross_check ? 1 : 0) && mc.ratio == ratio) {
         // the matches were enqueued behind the submission's features; spvo_detect_wait returned when the features were final
         const double tw0 = diag_now_us();
-        HIP_TRY(c, wait_event(c->ev_tail[set]));
+        HIP_TRY(c, wait_event(c->sets[set].ev_tail));
         g_diag.iv_match += diag_now_us() - tw0;
         if (a.n > 0) unpack_match(mc.h_out, a.n, train_idx, distance);
         return SPVO_OK;
@@ -269,16 +266,16 @@ int spvo_set_prematch(spvo_ctx *c, int enable, int selector, int cross_check, fl
   c->pm_selector = selector;
   c->pm_cross = cross_check ? 1 : 0;
   c->pm_ratio = ratio;
-  for (auto &set : c->mcache)
-    for (auto &mc : set) mc.valid = false;
+  for (SubmitSet &s : c->sets)
+    for (auto &mc : s.mcache) mc.valid = false;
   return SPVO_OK;
 }
 
 int spvo_set_match_fp8(spvo_ctx *c, int enable) {
   if (!c) return fail(c, SPVO_ERR_INVALID, "null context");
   c->match_fp8 = enable != 0;
-  for (auto &set : c->mcache)
-    for (auto &mc : set) mc.valid = false;
+  for (SubmitSet &s : c->sets)
+    for (auto &mc : s.mcache) mc.valid = false;
   return SPVO_OK;
 }
 

@@ -43,8 +43,8 @@ int launch_conv16_epi(spvo_ctx *c, const ConvArgs16 &a, int epi, hipStream_t str
 int launch_conv16(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t stream) {
   const Tensor &ti = c->tensors[op.in];
   const Tensor &to = c->tensors[op.out];
-  const float *tin = (ti.dr[c->cur_ring] ? ti.dr[c->cur_ring] : ti.d) + (size_t)img0 * ti.per_image;
-  float *tout = (to.dr[c->cur_ring] ? to.dr[c->cur_ring] : to.d) + (size_t)img0 * to.per_image;
+  const float *tin = ring_ptr(c, ti, img0);
+  float *tout = ring_ptr(c, to, img0);
   const bool relu = op.flags & FLAG_RELU, pool = op.flags & FLAG_POOL;
   if (op.type == OP_DWCONV) {
     dim3 grid((ti.W + 63) / 64, (ti.H + 3) / 4, batch * (op.cout / 8));
@@ -84,7 +84,7 @@ int launch_conv16(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t st
   const int epi = (op.flags & FLAG_BN) ? 1 : (op.flags & FLAG_ADD) ? 2 : 0;
   if (epi) {
     a.bn_scale = op.d_bn_scale; a.bn_shift = op.d_bn_shift;
-    if (epi == 2) a.residual = (const _Float16 *)(ring_ptr(c, c->tensors[op.residual]) + (size_t)img0 * c->tensors[op.residual].per_image);
+    if (epi == 2) a.residual = (const _Float16 *)ring_ptr(c, c->tensors[op.residual], img0);
     switch (key) {
       case 14220: return launch_conv16_epi<4, 2, 2, false>(c, a, epi, stream);
       case 14120: return launch_conv16_epi<4, 1, 2, false>(c, a, epi, stream);

@@ -134,8 +134,8 @@ int launch_conv_wino(spvo_ctx *c, const ConvArgs &a, int batch, bool relu, bool 
 int launch_conv(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t stream) {
   const Tensor &ti = c->tensors[op.in];
   const Tensor &to = c->tensors[op.out];
-  const float *tin = (ti.dr[c->cur_ring] ? ti.dr[c->cur_ring] : ti.d) + (size_t)img0 * ti.per_image;
-  float *tout = (to.dr[c->cur_ring] ? to.dr[c->cur_ring] : to.d) + (size_t)img0 * to.per_image;
+  const float *tin = ring_ptr(c, ti, img0);
+  float *tout = ring_ptr(c, to, img0);
   const bool relu = op.flags & FLAG_RELU, pool = op.flags & FLAG_POOL;
   const int epi = (op.flags & FLAG_BN) ? 1 : (op.flags & FLAG_ADD) ? 2 : 0;
   if (op.type == OP_DWCONV) {
@@ -175,7 +175,7 @@ int launch_conv(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t stre
   const int key = op.ks * 10000 + op.ck * 100 + op.wr * 20 + op.wc * 2 + (pool ? 1 : 0);   // ks, ck, wr, wc, pool
   if (epi) {
     a.bn_scale = op.d_bn_scale; a.bn_shift = op.d_bn_shift;
-    if (epi == 2) a.residual = ring_ptr(c, c->tensors[op.residual]) + (size_t)img0 * c->tensors[op.residual].per_image;
+    if (epi == 2) a.residual = ring_ptr(c, c->tensors[op.residual], img0);
     switch (key) {
       case 11644: return launch_conv_epi<2, 2, false>(c, a, batch, epi, stream);
       case 11624: return launch_conv_epi<1, 2, false>(c, a, batch, epi, stream);
@@ -224,8 +224,8 @@ int launch_op(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t stream
     return c->int8 ? launch_conv8(c, op, img0, batch, stream) : c->fp16 ? launch_conv16(c, op, img0, batch, stream)
            : c->s3 ? launch_conv_s3(c, op, img0, batch, stream) : launch_conv(c, op, img0, batch, stream);
   }
-  const float *tin = (ti.dr[c->cur_ring] ? ti.dr[c->cur_ring] : ti.d) + (size_t)img0 * ti.per_image;
-  float *tout = (to.dr[c->cur_ring] ? to.dr[c->cur_ring] : to.d) + (size_t)img0 * to.per_image;
+  const float *tin = ring_ptr(c, ti, img0);
+  float *tout = ring_ptr(c, to, img0);
   // (max-pool / L2 normalisation: read one tensor, write one -- in the element sizes of the engine's tensors)
   auto tsz = [](const Tensor &t) { return t.i8 ? 1.0 : t.f16 ? 2.0 : t.s3 ? 6.0 : 4.0; };
   ScopedStage st(c, op.stage, 0, batch * ((double)ti.ch * ti.H * ti.W * tsz(ti) + (double)to.ch * to.H * to.W * tsz(to)), stream);

@@ -91,11 +91,11 @@ static int launch_dwpw8(spvo_ctx *c, const Op &pw, int img0, int batch, hipStrea
   const Tensor &ti = c->tensors[dw.in], &tm = c->tensors[dw.out], &to = c->tensors[pw.out];
   DwPwArgs8 a;
   a.hp = ti.hp; a.wp = ti.wp; a.H = ti.H; a.W = ti.W;
-  a.in = (const int8_t *)(ring_ptr(c, ti) + (size_t)img0 * ti.per_image);
+  a.in = (const int8_t *)ring_ptr(c, ti, img0);
   a.in_per_image = ti.per_image * 4;
   a.dw_wsel = dw.d_wsel; a.dw_qm = dw.d_qm; a.dw_bias = dw.d_b; a.inv_s_dw = dw.inv_s_out;
   a.pw_w = pw.d_w8; a.pw_qm = pw.d_qm; a.pw_bias = pw.d_b; a.bn_scale = pw.d_bn_scale; a.bn_shift = pw.d_bn_shift; a.inv_s_out = pw.inv_s_out;
-  a.out = (int8_t *)(ring_ptr(c, to) + (size_t)img0 * to.per_image);
+  a.out = (int8_t *)ring_ptr(c, to, img0);
   a.out_per_image = to.per_image * 4;
   a.out_hp = to.hp; a.out_wp = to.wp; a.cout = pw.cout; a.co_tiles = pw.cout / CO_TILE;
   a.tiles_x = (ti.W + 31) / 32; a.tiles_y = (ti.H + 7) / 8; a.batch = batch;
@@ -106,7 +106,7 @@ static int launch_dwpw8(spvo_ctx *c, const Op &pw, int img0, int batch, hipStrea
     const Op &s0 = c->ops[0], &s1 = c->ops[1];
     const Tensor &t0 = c->tensors[s0.in], &t1 = c->tensors[s0.out];
     a.in = nullptr;
-    a.in_f32 = ring_ptr(c, t0) + (size_t)img0 * t0.per_image;
+    a.in_f32 = ring_ptr(c, t0, img0);
     a.in_per_image = t0.per_image;
     a.w0 = s0.d_w; a.b0 = s0.d_b; a.w1 = s1.d_w; a.b1 = s1.d_b; a.bn1_scale = s1.d_bn_scale; a.bn1_shift = s1.d_bn_shift; a.inv_s_stem = s1.inv_s_out;
     if (keep) { a.dbg_stem_plane = t1.d + (size_t)img0 * t1.per_image; a.dbg_stem_plane_per_image = t1.per_image; a.dbg_stem_out = (int8_t *)(ti.d + (size_t)img0 * ti.per_image); }
@@ -125,8 +125,8 @@ int launch_conv8(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t str
   if (op.fused_dw >= 0) return launch_dwpw8(c, op, img0, batch, stream);
   const Tensor &ti = c->tensors[op.in];
   const Tensor &to = c->tensors[op.out];
-  const float *tin = (ti.dr[c->cur_ring] ? ti.dr[c->cur_ring] : ti.d) + (size_t)img0 * ti.per_image;
-  float *tout = (to.dr[c->cur_ring] ? to.dr[c->cur_ring] : to.d) + (size_t)img0 * to.per_image;
+  const float *tin = ring_ptr(c, ti, img0);
+  float *tout = ring_ptr(c, to, img0);
   const bool relu = op.flags & FLAG_RELU, pool = op.flags & FLAG_POOL;
   if (op.type == OP_DWCONV) {
     dim3 grid((ti.W + 63) / 64, (ti.H + 3) / 4, batch * (op.cout / 16));
@@ -161,7 +161,7 @@ int launch_conv8(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t str
   a.tiles_x = a.tiles_y = 0;
   a.batch = batch;
   const int epi = (op.flags & FLAG_BN) ? 1 : (op.flags & FLAG_ADD) ? 2 : 0;
-  if (epi == 2) a.residual = (const int8_t *)(ring_ptr(c, c->tensors[op.residual]) + (size_t)img0 * c->tensors[op.residual].per_image);
+  if (epi == 2) a.residual = (const int8_t *)ring_ptr(c, c->tensors[op.residual], img0);
   const bool out_f32 = !to.i8;
   const int key = op.ks * 10000 + (op.ck / 16) * 1000 + op.wr * 100 + op.wc * 10 + (pool ? 1 : 0);   // ks, groups per chunk, wr, wc, pool
   switch (key) {

@@ -36,8 +36,8 @@ int launch_conv_s3_variant(spvo_ctx *c, const ConvArgsS3 &a, bool relu, bool out
 int launch_conv_s3(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t stream) {
   const Tensor &ti = c->tensors[op.in];
   const Tensor &to = c->tensors[op.out];
-  const float *tin = (ti.dr[c->cur_ring] ? ti.dr[c->cur_ring] : ti.d) + (size_t)img0 * ti.per_image;
-  float *tout = (to.dr[c->cur_ring] ? to.dr[c->cur_ring] : to.d) + (size_t)img0 * to.per_image;
+  const float *tin = ring_ptr(c, ti, img0);
+  float *tout = ring_ptr(c, to, img0);
   const bool relu = op.flags & FLAG_RELU, pool = op.flags & FLAG_POOL;
   if (op.cin == 1) {
     dim3 grid((ti.W + 63) / 64, (ti.H + 3) / 4, batch);
