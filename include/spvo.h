@@ -273,6 +273,40 @@ int spvo_fast_detect(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, size
 int spvo_orb_describe(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, size_t stride, const float *xy /* [n][2] */, int n,
                       int32_t *kept /* [n] */, float *angle /* [n] rad, may be NULL */, uint8_t *desc /* [n][32] */, int *n_kept);
 
+/* ------------------------------------------------------- classic front end: one submission per stereo pair, features resident
+ * detectKeypoints + describeKeypoints of ClassicFeatureFrontEnd for BOTH images of a stereo pair in one call: ORB, or Shi-Tomasi /
+ * FAST followed by the ORB extractor (the three pairs the per-image entry points above cover).  Both images go up through pinned
+ * staging, the whole chain of both is enqueued without a host round trip -- for the two non-ORB kinds the keypoints go from the
+ * detector to the extractor on the device, the extractor's border rule being an order-preserving compaction there -- and the call
+ * waits once for the result, the features (before that, for whatever an earlier call left running on the solver's stream: its staging is reused).  They are left in two BINARY FEATURE SLOTS (0 .. 9; separate from the float slots of spvo_detect*,
+ * used as a ring of pairs like those): keypoint records, 32-byte descriptor rows and the row count stay on the device for
+ * spvo_match_hamming_slots.  What the host receives equals, byte for byte, what spvo_orb_detect -- or spvo_gftt_detect /
+ * spvo_fast_detect followed by spvo_orb_describe(img = NULL) -- returns for the same image and parameters; for the two non-ORB kinds a
+ * record carries the extractor's angle (radians), the DETECTOR's response and octave 0.
+ *   SPVO_ERR_CAPACITY  an image yields more rows than slot_capacity: out_*->n report the counts, both slots are left unfilled
+ *                      (nothing is truncated: a shortened FAST list would not be the reference's)
+ *   SPVO_ERR_STATE     a spvo_detect*_submit is in flight
+ * (all ten slots share one allocation size: a call with a larger slot_capacity than any before re-allocates and EMPTIES every slot)
+ *   SPVO_ERR_INVALID   bad or equal slots, slot_capacity outside 1 .. 2^22, sizes / parameters the per-image entry points refuse
+ * With spvo_set_prematch enabled the two standard matches (slot_l -> slot_r, slot_l -> the previous call's slot_l) are enqueued in the
+ * same submission behind the features; the call does not wait for them. */
+typedef enum { SPVO_CLASSIC_ORB = 0, SPVO_CLASSIC_GFTT_ORB = 1, SPVO_CLASSIC_FAST_ORB = 2 } spvo_classic_kind;
+typedef struct {
+  int kind;                               /* spvo_classic_kind */
+  int nfeatures;                          /* ORB [2000] */
+  int max_corners; double quality_level, min_distance; int block_size;   /* GFTT [1000, 0.03, 7.5, 5] */
+  int fast_threshold, fast_nonmax;        /* FAST [10, 1] */
+  int slot_capacity;                      /* rows a slot can hold [8192] */
+} spvo_classic_opts;
+/* the reference's parameters (feature_detection_classic.cpp:12-47) for `kind` */
+void spvo_default_classic_opts(spvo_classic_opts *o, int kind);
+typedef struct { int n; spvo_orb_keypoint *kp; uint8_t *desc; int cap; } spvo_classic_features;  /* n: out; min(n, cap) rows are written; desc, kp may be NULL */
+int spvo_classic_detect(spvo_ctx *ctx, const spvo_classic_opts *opts, const uint8_t *img_l, const uint8_t *img_r,
+                        int rows, int cols, size_t stride, int slot_l, int slot_r,
+                        spvo_classic_features *out_l, spvo_classic_features *out_r);
+/* rows a binary feature slot holds; SPVO_ERR_STATE for one that holds nothing (never filled, or left unfilled by SPVO_ERR_CAPACITY) */
+int spvo_classic_slot_rows(spvo_ctx *ctx, int slot, int *n);
+
 /* The same for BINARY descriptors: cv::BFMatcher(NORM_HAMMING), what initMatcher (base.cpp:17-21) builds for the ORB / BRISK /
  * AKAZE descriptors of ClassicFeatureFrontEnd (classic.cpp:66-79) and matchDescriptors (base.cpp:434-500) runs on them.
  * Rows of `desc_bytes` bytes (ORB 32, BRISK 64, AKAZE 61; at most 64), distance = number of differing bits (exact), reported
@@ -285,12 +319,21 @@ int spvo_match_hamming(spvo_ctx *ctx, const uint8_t *desc_a, int na, const uint8
 int spvo_match_slots(spvo_ctx *ctx, int slot_a, int slot_b, int selector, int cross_check,
                      float ratio, int32_t *train_idx, float *distance);
 
+/* spvo_match_hamming on the device-resident rows of two BINARY feature slots (spvo_classic_detect): nothing is packed or uploaded,
+ * the kernel reads both row counts on the device.  Results equal spvo_match_hamming on the host copies of the two slots, index for
+ * index and distance for distance.  Returns the result stored by spvo_classic_detect when spvo_set_prematch is on and this is exactly
+ * that match of exactly those slot contents.  SPVO_ERR_STATE for a slot that holds nothing; spvo_match_slots on a binary slot number
+ * means the FLOAT slot of that number, as before. */
+int spvo_match_hamming_slots(spvo_ctx *ctx, int slot_a, int slot_b, int selector, int cross_check, float ratio,
+                             int32_t *train_idx, float *distance);
+
 /* Optional latency hiding for the reference's fixed call order (node.cpp:175-198: detect, then
  * match CURR_LEFT->CURR_RIGHT, then CURR_LEFT->PREV_LEFT): when enabled, spvo_detect* enqueues
  * those two matches (slot_l -> slot_r, slot_l -> the previous call's slot_l) with these selector
  * parameters in the same GPU submission, and spvo_match_slots returns the stored result when it
  * is asked for exactly that match (same slots, same slot contents, same parameters).  Results
- * are identical with it on or off. */
+ * are identical with it on or off.  spvo_classic_detect / spvo_match_hamming_slots do the same on the
+ * binary slots. */
 int spvo_set_prematch(spvo_ctx *ctx, int enable, int selector, int cross_check, float ratio);
 
 /* Extension (BASELINE config 5): build the matcher's candidate shortlist with an fp8 (e4m3) distance GEMM instead of

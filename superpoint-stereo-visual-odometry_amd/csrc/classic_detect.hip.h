@@ -303,4 +303,72 @@ __global__ __launch_bounds__(256) void fast_write_kernel(int w, const unsigned l
   }
 }
 
+// ---- spvo_classic_detect: detector -> extractor -> feature slot without the host in between
+// cv::ORB::compute's border rule on the device (what spvo_orb_describe does on the host around its launch): of the n = counters[2] keypoints
+// in xy, those at least `edge` pixels from every border, ORDER-PRESERVING, as the extractor's integer list + the detector's responses.
+// ONE workgroup walks the list in chunks of 1024 with a running base: wave ballots + an LDS prefix over the 16 waves (gftt_collect_kernel's
+// compaction, made stable by the fixed chunk order).  out_cnt[0] = kept in all, out_cnt[2] = min(kept, cap) = what orb_describe_kernel describes.
+__global__ __launch_bounds__(1024) void cls_compact_kernel(const float *__restrict__ xy, const float *__restrict__ resp, const int *__restrict__ counters, int h, int w, int edge,
+                                                           int *__restrict__ kxy, float *__restrict__ kresp, int cap, int *__restrict__ out_cnt) {
+  __shared__ int s_wave[16];
+  const int n = counters[2];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int base = 0;
+  for (int i0 = 0; i0 < n; i0 += 1024) {
+    const int i = i0 + (int)threadIdx.x;
+    int x = 0, y = 0;
+    bool keep = false;
+    if (i < n) {
+      x = (int)xy[2 * i]; y = (int)xy[2 * i + 1];
+      keep = !(x < edge || x >= w - edge || y < edge || y >= h - edge);
+    }
+    const unsigned long long m = __ballot(keep);
+    __syncthreads();   // (the previous chunk's sums have been read)
+    if (lane == 0) s_wave[wave] = __popcll(m);
+    __syncthreads();
+    int off = base, tot = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const int v = s_wave[k];
+      off += k < wave ? v : 0;
+      tot += v;
+    }
+    off += __popcll(m & ((1ull << lane) - 1ull));
+    if (keep && off < cap) {
+      kxy[2 * off] = x; kxy[2 * off + 1] = y;
+      kresp[off] = resp[i];
+    }
+    base += tot;
+  }
+  if (threadIdx.x == 0) { out_cnt[0] = base; out_cnt[2] = min(base, cap); }
+}
+
+// The last launch of an image: the slot's count on the device, and the host's copy of the slot -- count, keypoint records and descriptors
+// go to pinned memory from here, n rows instead of a capacity-sized copy whose length the host cannot know yet.
+//   ORB (n_levels = 8):  n = min(sum of the levels' written counts, kp_cap) as spvo_orb_detect computes it; overflow = any level's flag
+//   extractor (n_levels = 0): n = ext_cnt[0] (all that passed the border rule); the record's response becomes the DETECTOR's (kresp)
+// h_n = {n, overflow}; the slot holds min(n, cap) rows (n > cap: the caller reports SPVO_ERR_CAPACITY and the slot stays unfilled).
+__global__ __launch_bounds__(256) void classic_finish_kernel(const int *__restrict__ orb_counters, int n_levels, int counter_stride, int kp_cap, const int *__restrict__ det_counters,
+                                                             const int *__restrict__ ext_cnt, const float *__restrict__ kresp, OrbKeypoint *__restrict__ kps,
+                                                             const uint4 *__restrict__ desc, int cap, int *__restrict__ d_n, int *__restrict__ h_n,
+                                                             OrbKeypoint *__restrict__ h_kp, uint4 *__restrict__ h_desc) {
+  int n_all = 0, overflow = 0;
+  if (n_levels > 0) {
+    for (int l = 0; l < n_levels; ++l) { n_all += orb_counters[l * counter_stride + 2]; overflow |= orb_counters[l * counter_stride + 3]; }
+    n_all = min(n_all, kp_cap);
+  } else {
+    n_all = ext_cnt[0];
+    overflow = det_counters[3];
+  }
+  const int n = min(n_all, cap);
+  if (blockIdx.x == 0 && threadIdx.x == 0) { *d_n = n; h_n[0] = n_all; h_n[1] = overflow; }
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    OrbKeypoint k = kps[i];
+    if (n_levels == 0) { k.response = kresp[i]; kps[i] = k; }
+    h_kp[i] = k;
+    h_desc[2 * i] = desc[2 * i];
+    h_desc[2 * i + 1] = desc[2 * i + 1];
+  }
+}
+
 }  // namespace spvo

@@ -785,4 +785,130 @@ __global__ __launch_bounds__(256) void match_hamming_cross_kernel(const unsigned
   out_dist[q] = hit ? (float)(unsigned)(key >> 32) : 0.f;
 }
 
+// ---------------------------------------------------------------------------
+// K12t: the Hamming matcher for DEVICE-RESIDENT rows of 8 words (the binary feature slots of spvo_classic_detect) -- modes, tie rules
+// and results of K12h (match_hamming_kernel stays for spvo_match_hamming), but built for rows that are already on the device:
+//   * both row counts are read from device memory, so the launch can be enqueued behind the detector before the host knows them; the
+//     grid comes from the slots' capacity and surplus workgroups exit at once.
+//   * register blocking: a wave keeps HAM_R = 8 query rows in registers (wave-uniform, 64 words: they live in scalar registers) and
+//     scores every train row it reads against all eight, so a train row costs one LDS read per 8 distances instead of one global
+//     read per distance.
+//   * LDS staging: the workgroup (4 waves, HAM_QB = 16 query rows: two groups of eight) walks the train set in tiles of HAM_T = 256
+//     rows.  A tile is loaded from global memory ONCE per workgroup with 16-byte loads (thread = row, coalesced) and stored word-major
+//     ([8][256] words, 8 KB), so that a wave reading 64 consecutive rows of one word hits 64 different banks -- row-major rows of 32
+//     bytes would put lanes l and l + 8 on the same banks.  The next tile's global loads are issued before the current tile is scored and
+//     land in the other of two buffers: one barrier per tile.  Each of the two waves of a query group scores half of the tile (lane =
+//     row), so a word of the tile is read twice per workgroup; the train set is read from L2 once per 16 query rows (2000 x 2000
+//     rows: 8 MB instead of the 128 MB of one wave per query).
+//   * 16 KB of LDS and well under 128 registers: eight workgroups fit a CU, and 2000 query rows are only 125 workgroups, so
+//     occupancy is bounded by the problem, not by resources -- which is why a workgroup does not take more query rows than 16.
+//   * (distance, row) is ONE unsigned key, distance << 22 | row: ham_less's order (lower distance, then lower row) is the key's,
+//     and a lane's running best two are min / max / min.  Rows beyond the count get the key ~0, which decodes to "none".
+// ---------------------------------------------------------------------------
+constexpr int HAM_R = 8, HAM_QB = 16, HAM_T = 256, HAM_SHIFT = 22;
+
+__device__ __forceinline__ void ham_top2(uint32_t &m0, uint32_t &m1, uint32_t k0, uint32_t k1) {   // merges the sorted pair (k0 <= k1) into (m0 <= m1)
+  const uint32_t hi = max(m0, k0);
+  m0 = min(m0, k0);
+  m1 = min(hi, min(m1, k1));
+}
+
+__global__ __launch_bounds__(256) void match_hamming_tiled_kernel(const uint32_t *__restrict__ A, const int *__restrict__ na_ptr, const uint32_t *__restrict__ B,
+                                                                  const int *__restrict__ nb_ptr, int cap, int mode, float ratio, int2 *__restrict__ out,
+                                                                  unsigned long long *__restrict__ vote) {
+  __shared__ uint32_t tile[2][8][HAM_T];
+  __shared__ uint32_t s_merge[2][HAM_R][2];
+  const int na = min(*na_ptr, cap), nb = min(*nb_ptr, cap);
+  const int q0 = blockIdx.x * HAM_QB;
+  if (q0 >= na) return;   // (the whole workgroup: no barrier is skipped by part of it)
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int group = wave >> 1, half = wave & 1;
+  const int qg = q0 + group * HAM_R;
+  uint32_t a[HAM_R][8], m0[HAM_R], m1[HAM_R];
+#pragma unroll
+  for (int r = 0; r < HAM_R; ++r) {
+    const uint32_t *row = A + (size_t)min(qg + r, na - 1) * 8;   // (rows past the end repeat the last one; they are not written)
+#pragma unroll
+    for (int w = 0; w < 8; ++w) a[r][w] = row[w];
+    m0[r] = m1[r] = ~0u;
+  }
+  const int ntiles = (nb + HAM_T - 1) / HAM_T;
+  uint4 v0 = make_uint4(0, 0, 0, 0), v1 = v0;
+  auto fetch = [&](int t) {
+    const int row = t * HAM_T + (int)threadIdx.x;
+    if (row < nb) {
+      const uint4 *p = reinterpret_cast<const uint4 *>(B + (size_t)row * 8);
+      v0 = p[0]; v1 = p[1];
+    }
+  };
+  auto stage = [&](int buf) {
+    uint32_t(*tb)[HAM_T] = tile[buf];
+    tb[0][threadIdx.x] = v0.x; tb[1][threadIdx.x] = v0.y; tb[2][threadIdx.x] = v0.z; tb[3][threadIdx.x] = v0.w;
+    tb[4][threadIdx.x] = v1.x; tb[5][threadIdx.x] = v1.y; tb[6][threadIdx.x] = v1.z; tb[7][threadIdx.x] = v1.w;
+  };
+  if (ntiles > 0) { fetch(0); stage(0); }
+  __syncthreads();
+  for (int t = 0; t < ntiles; ++t) {
+    if (t + 1 < ntiles) fetch(t + 1);
+    const uint32_t(*tb)[HAM_T] = tile[t & 1];
+#pragma unroll
+    for (int s = 0; s < HAM_T / 128; ++s) {
+      const int r_in = half * (HAM_T / 2) + s * 64 + lane, grow = t * HAM_T + r_in;
+      uint32_t b[8];
+#pragma unroll
+      for (int w = 0; w < 8; ++w) b[w] = tb[w][r_in];
+      const bool valid = grow < nb;
+#pragma unroll
+      for (int r = 0; r < HAM_R; ++r) {
+        uint32_t d = 0;
+#pragma unroll
+        for (int w = 0; w < 8; ++w) d += __popc(b[w] ^ a[r][w]);
+        const uint32_t key = valid ? ((d << HAM_SHIFT) | (uint32_t)grow) : ~0u;
+        ham_top2(m0[r], m1[r], key, ~0u);
+      }
+    }
+    if (t + 1 < ntiles) stage((t + 1) & 1);
+    __syncthreads();
+  }
+  // the wave's 64 pairs -> one, then the two halves of the tile through LDS
+#pragma unroll
+  for (int r = 0; r < HAM_R; ++r) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      const uint32_t k0 = (uint32_t)__shfl_xor((int)m0[r], o), k1 = (uint32_t)__shfl_xor((int)m1[r], o);
+      ham_top2(m0[r], m1[r], k0, k1);
+    }
+  }
+  if (half == 1 && lane == 0) {
+#pragma unroll
+    for (int r = 0; r < HAM_R; ++r) { s_merge[group][r][0] = m0[r]; s_merge[group][r][1] = m1[r]; }
+  }
+  __syncthreads();
+  if (half == 1 || lane != 0) return;
+#pragma unroll
+  for (int r = 0; r < HAM_R; ++r) {
+    const int q = qg + r;
+    if (q >= na) break;
+    ham_top2(m0[r], m1[r], s_merge[group][r][0], s_merge[group][r][1]);
+    const int i0 = m0[r] == ~0u ? -1 : (int)(m0[r] & ((1u << HAM_SHIFT) - 1)), d0 = (int)(m0[r] >> HAM_SHIFT);
+    const int i1 = m1[r] == ~0u ? -1 : (int)(m1[r] & ((1u << HAM_SHIFT) - 1)), d1 = (int)(m1[r] >> HAM_SHIFT);
+    if (mode == 2) {
+      if (i0 >= 0) atomicMin(&vote[i0], ((unsigned long long)(unsigned)d0 << 32) | (unsigned)q);
+      continue;
+    }
+    const float dist = i0 >= 0 ? (float)d0 : 0.f;
+    const int idx = mode == 0 ? i0 : ((i1 >= 0 && (float)d0 < ratio * (float)d1) ? i0 : -1);
+    out[q] = make_int2(idx, __float_as_int(dist));
+  }
+}
+
+// the cross-check's second half (match_hamming_cross_kernel) with the count on the device and the packed result format
+__global__ __launch_bounds__(256) void match_hamming_cross_slots_kernel(const unsigned long long *__restrict__ vote, const int *__restrict__ na_ptr, int cap, int2 *__restrict__ out) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= min(*na_ptr, cap)) return;
+  const unsigned long long key = vote[q];
+  const bool hit = key != ~0ull;
+  out[q] = make_int2(hit ? (int)(key & 0xFFFFFFFFull) : -1, hit ? __float_as_int((float)(unsigned)(key >> 32)) : 0);
+}
+
 }  // namespace spvo

@@ -105,19 +105,23 @@ int spvo_orb_tables(float *pattern, float *taps) {
   return SPVO_OK;
 }
 
-int spvo_orb_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride, int nfeatures, spvo_orb_keypoint *kps, uint8_t *desc, int cap, int *n_out) {
-  if (!c || !img || !n_out || rows <= 0 || cols <= 0 || stride < (size_t)cols || nfeatures <= 0 || cap < 0 || (cap > 0 && (!kps || !desc)))
-    return fail(c, SPVO_ERR_INVALID, "bad argument");
-  static_assert(sizeof(spvo_orb_keypoint) == sizeof(OrbKeypoint), "keypoint records differ");
-  HIP_TRY(c, hipSetDevice(c->cfg.device));
-  *n_out = 0;
-  hipStream_t st = c->stream2;
-  auto &o = c->orb;
-  // ---- level geometry and per-level quota (the reference's parameters: 8 levels, scale 1.2)
-  constexpr float SCALE = 1.2f;
+namespace {
+// level geometry and per-level quota of an image (the reference's parameters: 8 levels, scale 1.2), and where a level lies in the buffers
+struct OrbPlan {
   int ph[ORB_LEVELS], pw[ORB_LEVELS], want[ORB_LEVELS];
   float lscale[ORB_LEVELS];
-  size_t off[ORB_LEVELS + 1];
+  size_t off[ORB_LEVELS + 1], toff[ORB_LEVELS];
+  int surv_cap;
+};
+
+// the plan of a rows x cols image, every buffer grown to what it needs, the resize tables and the descriptor's tables on the device
+int orb_prepare(spvo_ctx *c, int rows, int cols, int nfeatures, OrbPlan &p) {
+  hipStream_t st = c->stream2;
+  auto &o = c->orb;
+  constexpr float SCALE = 1.2f;
+  int *ph = p.ph, *pw = p.pw, *want = p.want;
+  float *lscale = p.lscale;
+  size_t *off = p.off;
   {
     float scale = 1.f;
     const float f = 1.0f / SCALE;
@@ -133,7 +137,7 @@ int spvo_orb_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t 
       off[l + 1] = off[l] + (((size_t)ph[l] * pw[l] + 255) & ~(size_t)255);
     }
   }
-  const int surv_cap = (rows / 2 + 1) * (cols / 2 + 1);   // 3x3 suppression: at most one survivor per 2x2 block
+  const int surv_cap = p.surv_cap = (rows / 2 + 1) * (cols / 2 + 1);   // 3x3 suppression: at most one survivor per 2x2 block
   const int kp_cap = nfeatures;
   // what THIS image needs: the pyramid (all levels side by side), one key / rank entry per possible survivor of every level, the
   // resize tables of levels 1..7.  All three depend on rows and cols separately (a 100 x 1500 image needs longer tables than a
@@ -161,10 +165,10 @@ int spvo_orb_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t 
     o.tab_rows = o.tab_cols = 0;
   }
   // resize tables of all levels, one upload per image size
-  size_t toff[ORB_LEVELS] = {0};
   {
     size_t t = 0;
-    for (int l = 1; l < ORB_LEVELS; ++l) { toff[l] = t; t += (size_t)3 * (pw[l] + ph[l]); }
+    p.toff[0] = 0;
+    for (int l = 1; l < ORB_LEVELS; ++l) { p.toff[l] = t; t += (size_t)3 * (pw[l] + ph[l]); }
     if (o.tab_rows != rows || o.tab_cols != cols) {
       std::vector<int> all;
       for (int l = 1; l < ORB_LEVELS; ++l) resize_tables(pw[l], pw[l - 1], ph[l], ph[l - 1], all);
@@ -173,25 +177,31 @@ int spvo_orb_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t 
       o.tab_rows = rows; o.tab_cols = cols;
     }
   }
-  if (int rc = orb_ensure_tables(c)) return rc;
-  if (int rc = upload_strided(c, img, rows, cols, stride, o.src, o.src_cap, o.im, st)) return rc;   // level 0: the image, rows packed
-  // the whole image is enqueued without a host round trip: the pyramid level by level, then every stage once for all levels;
-  // one counter block per level, a level's keypoints land behind those of the levels below (orb_describe_kernel sums their counts)
+  return orb_ensure_tables(c);
+}
+
+// The image in level 0 (o.im) -> keypoint records and descriptors in `kps` / `desc` (kp_cap rows), enqueued without a host round trip:
+// the pyramid level by level, then every stage once for all levels; one counter block per level, a level's keypoints land behind
+// those of the levels below (orb_describe_kernel sums their counts)
+int orb_enqueue(spvo_ctx *c, const OrbPlan &p, int rows, int cols, OrbKeypoint *kps, uint8_t *desc, int kp_cap) {
+  hipStream_t st = c->stream2;
+  auto &o = c->orb;
+  const int *ph = p.ph, *pw = p.pw;
   HIP_TRY(c, hipMemsetAsync(o.counters, 0, (size_t)ORB_LEVELS * NMS_COUNTER_INTS * sizeof(int), st));
   OrbLevels lv;
   size_t koff = 0;
   int want_max = 0;
   for (int l = 0; l < ORB_LEVELS; ++l) {
     OrbLevel &L = lv.l[l];
-    const int lcap = std::min(surv_cap, (ph[l] / 2 + 1) * (pw[l] / 2 + 1));
-    L.im = o.im + off[l]; L.score = o.score + off[l]; L.blur = o.blur + off[l]; L.tmp = o.tmp + off[l];
+    const int lcap = std::min(p.surv_cap, (ph[l] / 2 + 1) * (pw[l] / 2 + 1));
+    L.im = o.im + p.off[l]; L.score = o.score + p.off[l]; L.blur = o.blur + p.off[l]; L.tmp = o.tmp + p.off[l];
     L.keys = o.keys + koff; L.rank = o.rank + koff; L.out_xy = o.out_xy + 2 * koff; L.counters = o.counters + l * NMS_COUNTER_INTS;
-    L.h = ph[l]; L.w = pw[l]; L.cap = lcap; L.scale = lscale[l];
-    L.want = (ph[l] <= 2 * ORB_EDGE + 2 || pw[l] <= 2 * ORB_EDGE + 2) ? 0 : want[l];
+    L.h = ph[l]; L.w = pw[l]; L.cap = lcap; L.scale = p.lscale[l];
+    L.want = (ph[l] <= 2 * ORB_EDGE + 2 || pw[l] <= 2 * ORB_EDGE + 2) ? 0 : p.want[l];
     want_max = std::max(want_max, L.want);
     koff += lcap;
-    if (l > 0) hipLaunchKernelGGL(orb_resize_kernel, dim3((pw[l] + 63) / 64, (ph[l] + 3) / 4), dim3(256), 0, st, o.im + off[l - 1], ph[l - 1], pw[l - 1], pw[l - 1], L.im, ph[l], pw[l],
-                                  o.tab + toff[l]);
+    if (l > 0) hipLaunchKernelGGL(orb_resize_kernel, dim3((pw[l] + 63) / 64, (ph[l] + 3) / 4), dim3(256), 0, st, o.im + p.off[l - 1], ph[l - 1], pw[l - 1], pw[l - 1], L.im, ph[l], pw[l],
+                                  o.tab + p.toff[l]);
   }
   if (want_max > 0) {
     const dim3 grid((cols + 63) / 64, (rows + 3) / 4, ORB_LEVELS);
@@ -201,9 +211,26 @@ int spvo_orb_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t 
     hipLaunchKernelGGL(orb_write_kernel, dim3(32, ORB_LEVELS), dim3(256), 0, st, lv);
     hipLaunchKernelGGL(orb_blur_h_kernel, grid, dim3(256), 0, st, lv, o.taps);
     hipLaunchKernelGGL(orb_blur_v_kernel, grid, dim3(256), 0, st, lv, o.taps);
-    hipLaunchKernelGGL(orb_describe_kernel, dim3((want_max + 3) / 4, ORB_LEVELS), dim3(256), 0, st, lv, o.disc, o.pattern, o.kps, o.desc, kp_cap);
+    hipLaunchKernelGGL(orb_describe_kernel, dim3((want_max + 3) / 4, ORB_LEVELS), dim3(256), 0, st, lv, o.disc, o.pattern, kps, desc, kp_cap);
   }
   HIP_TRY(c, hipGetLastError());
+  return SPVO_OK;
+}
+}  // namespace
+
+int spvo_orb_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride, int nfeatures, spvo_orb_keypoint *kps, uint8_t *desc, int cap, int *n_out) {
+  if (!c || !img || !n_out || rows <= 0 || cols <= 0 || stride < (size_t)cols || nfeatures <= 0 || cap < 0 || (cap > 0 && (!kps || !desc)))
+    return fail(c, SPVO_ERR_INVALID, "bad argument");
+  static_assert(sizeof(spvo_orb_keypoint) == sizeof(OrbKeypoint), "keypoint records differ");
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  *n_out = 0;
+  hipStream_t st = c->stream2;
+  auto &o = c->orb;
+  const int kp_cap = nfeatures;
+  OrbPlan plan;
+  if (int rc = orb_prepare(c, rows, cols, nfeatures, plan)) return rc;
+  if (int rc = upload_strided(c, img, rows, cols, stride, o.src, o.src_cap, o.im, st)) return rc;   // level 0: the image, rows packed
+  if (int rc = orb_enqueue(c, plan, rows, cols, o.kps, o.desc, kp_cap)) return rc;
   int cnt[ORB_LEVELS * NMS_COUNTER_INTS];
   HIP_TRY(c, hipMemcpyAsync(cnt, o.counters, sizeof cnt, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
@@ -225,8 +252,8 @@ int spvo_orb_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t 
 
 // ---------------------------------------------------------------- Shi-Tomasi, FAST, ORB extractor (classic_detect.hip.h)
 namespace {
-// the image into the context's level-0 buffer (rows packed), every buffer grown to what this image needs
-int cls_prepare(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride) {
+// every buffer of the Shi-Tomasi / FAST detectors grown to what a rows x cols image needs; no image is resident afterwards
+int cls_ensure(spvo_ctx *c, int rows, int cols) {
   auto &b = c->cls;
   hipStream_t st = c->stream2;
   const size_t px = (size_t)rows * cols, state_bytes = (size_t)(rows + 2 * CLS_PAD) * cls_state_pitch(cols);
@@ -250,8 +277,57 @@ int cls_prepare(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stri
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
-  if (int rc = upload_strided(c, img, rows, cols, stride, b.src, b.src_cap, b.im, st)) return rc;
+  return SPVO_OK;
+}
+
+// the image into the context's level-0 buffer (rows packed), every buffer grown to what this image needs
+int cls_prepare(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride) {
+  auto &b = c->cls;
+  if (int rc = cls_ensure(c, rows, cols)) return rc;
+  if (int rc = upload_strided(c, img, rows, cols, stride, b.src, b.src_cap, b.im, c->stream2)) return rc;
   b.rows = rows; b.cols = cols;
+  return SPVO_OK;
+}
+
+// the resident image -> Shi-Tomasi corners in b.xy / b.resp, their number in b.counters[2]
+int gftt_enqueue(spvo_ctx *c, int rows, int cols, int max_corners, double quality_level, double min_distance) {
+  auto &b = c->cls;
+  hipStream_t st = c->stream2;
+  // dx^2 + dy^2 < min_distance^2 on integer coordinates: <= lim (OpenCV compares in float: min_distance as float, squared in float)
+  const float mdf = (float)min_distance;
+  const int lim = (int)std::ceil((double)mdf * (double)mdf) - 1;
+  const int radius = lim > 0 ? (int)std::floor(std::sqrt((double)lim)) : 0;
+  const int want = max_corners > 0 ? max_corners : 0x7FFFFFFF;   // (cv::goodFeaturesToTrack: max_corners <= 0 is "no limit")
+  const int key_cap = (int)std::min<size_t>((size_t)rows * cols, 0x7FFFFFFF);
+  HIP_TRY(c, hipMemsetAsync(b.counters, 0, CLS_COUNTER_INTS * sizeof(int), st));
+  if (b.state_rows != rows || b.state_cols != cols) {   // the padding of the state map: cleared once per shape (the kernels write the image's own bytes only)
+    HIP_TRY(c, hipMemsetAsync(b.state, 0, (size_t)(rows + 2 * CLS_PAD) * cls_state_pitch(cols), st));
+    b.state_rows = rows; b.state_cols = cols;
+  }
+  const dim3 grid((cols + 63) / 64, (rows + 3) / 4);
+  hipLaunchKernelGGL(gftt_response_kernel, grid, dim3(256), 0, st, b.im, rows, cols, b.lam, b.counters);
+  hipLaunchKernelGGL(gftt_collect_kernel, grid, dim3(256), 0, st, b.lam, rows, cols, quality_level, b.state, b.cand, b.counters);
+  for (int l = 0; l < CLS_ROUND_LAUNCHES; ++l)
+    hipLaunchKernelGGL(gftt_round_kernel<4>, dim3(64), dim3(256), 0, st, b.lam, cols, radius, lim, b.state, b.cand, b.keys, key_cap, b.counters, l);
+  hipLaunchKernelGGL(gftt_finish_kernel, dim3(1), dim3(1024), 0, st, b.lam, cols, radius, lim, b.state, b.cand, b.keys, key_cap, b.counters, CLS_ROUND_LAUNCHES);
+  hipLaunchKernelGGL(cls_rank_kernel, dim3(128), dim3(256), 0, st, b.keys, b.rank, b.counters + 1, key_cap);
+  hipLaunchKernelGGL(gftt_write_kernel, dim3(32), dim3(256), 0, st, b.lam, cols, b.keys, b.rank, key_cap, want, (float)(0.5 / (5100.0 * 5100.0)), b.xy, b.resp, b.counters);
+  return SPVO_OK;
+}
+
+// the resident image -> FAST corners in b.xy / b.resp (raster order), their number in b.counters[2]
+int fast_enqueue(spvo_ctx *c, int rows, int cols, int threshold, int nonmax_suppression) {
+  auto &b = c->cls;
+  hipStream_t st = c->stream2;
+  const int key_cap = (int)std::min<size_t>((size_t)rows * cols, 0x7FFFFFFF);   // no cap in the reference: with suppression off every pixel can be a corner
+  HIP_TRY(c, hipMemsetAsync(b.counters, 0, CLS_COUNTER_INTS * sizeof(int), st));
+  OrbLevels lv{};
+  lv.l[0].im = b.im; lv.l[0].score = b.score; lv.l[0].h = rows; lv.l[0].w = cols; lv.l[0].want = 1; lv.l[0].scale = 1.f;
+  const dim3 grid((cols + 63) / 64, (rows + 3) / 4, 1);
+  hipLaunchKernelGGL(orb_fast_kernel, grid, dim3(256), 0, st, lv, threshold, 3);
+  hipLaunchKernelGGL(fast_collect_kernel, grid, dim3(256), 0, st, b.score, rows, cols, nonmax_suppression ? 1 : 0, b.keys, key_cap, b.counters);
+  hipLaunchKernelGGL(cls_rank_kernel, dim3(128), dim3(256), 0, st, b.keys, b.rank, b.counters + 1, key_cap);
+  hipLaunchKernelGGL(fast_write_kernel, dim3(32), dim3(256), 0, st, cols, b.keys, b.rank, key_cap, b.xy, b.resp, b.counters);
   return SPVO_OK;
 }
 
@@ -284,27 +360,7 @@ int spvo_gftt_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   *n_out = 0;
   if (int rc = cls_prepare(c, img, rows, cols, stride)) return rc;
-  auto &b = c->cls;
-  hipStream_t st = c->stream2;
-  // dx^2 + dy^2 < min_distance^2 on integer coordinates: <= lim (OpenCV compares in float: min_distance as float, squared in float)
-  const float mdf = (float)min_distance;
-  const int lim = (int)std::ceil((double)mdf * (double)mdf) - 1;
-  const int radius = lim > 0 ? (int)std::floor(std::sqrt((double)lim)) : 0;
-  const int want = max_corners > 0 ? max_corners : 0x7FFFFFFF;   // (cv::goodFeaturesToTrack: max_corners <= 0 is "no limit")
-  const int key_cap = (int)std::min<size_t>((size_t)rows * cols, 0x7FFFFFFF);
-  HIP_TRY(c, hipMemsetAsync(b.counters, 0, CLS_COUNTER_INTS * sizeof(int), st));
-  if (b.state_rows != rows || b.state_cols != cols) {   // the padding of the state map: cleared once per shape (the kernels write the image's own bytes only)
-    HIP_TRY(c, hipMemsetAsync(b.state, 0, (size_t)(rows + 2 * CLS_PAD) * cls_state_pitch(cols), st));
-    b.state_rows = rows; b.state_cols = cols;
-  }
-  const dim3 grid((cols + 63) / 64, (rows + 3) / 4);
-  hipLaunchKernelGGL(gftt_response_kernel, grid, dim3(256), 0, st, b.im, rows, cols, b.lam, b.counters);
-  hipLaunchKernelGGL(gftt_collect_kernel, grid, dim3(256), 0, st, b.lam, rows, cols, quality_level, b.state, b.cand, b.counters);
-  for (int l = 0; l < CLS_ROUND_LAUNCHES; ++l)
-    hipLaunchKernelGGL(gftt_round_kernel<4>, dim3(64), dim3(256), 0, st, b.lam, cols, radius, lim, b.state, b.cand, b.keys, key_cap, b.counters, l);
-  hipLaunchKernelGGL(gftt_finish_kernel, dim3(1), dim3(1024), 0, st, b.lam, cols, radius, lim, b.state, b.cand, b.keys, key_cap, b.counters, CLS_ROUND_LAUNCHES);
-  hipLaunchKernelGGL(cls_rank_kernel, dim3(128), dim3(256), 0, st, b.keys, b.rank, b.counters + 1, key_cap);
-  hipLaunchKernelGGL(gftt_write_kernel, dim3(32), dim3(256), 0, st, b.lam, cols, b.keys, b.rank, key_cap, want, (float)(0.5 / (5100.0 * 5100.0)), b.xy, b.resp, b.counters);
+  if (int rc = gftt_enqueue(c, rows, cols, max_corners, quality_level, min_distance)) return rc;
   return cls_read_out(c, xy, response, cap, n_out, "spvo_gftt_detect");
 }
 
@@ -322,17 +378,7 @@ int spvo_fast_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   *n_out = 0;
   if (int rc = cls_prepare(c, img, rows, cols, stride)) return rc;
-  auto &b = c->cls;
-  hipStream_t st = c->stream2;
-  const int key_cap = (int)std::min<size_t>((size_t)rows * cols, 0x7FFFFFFF);   // no cap in the reference: with suppression off every pixel can be a corner
-  HIP_TRY(c, hipMemsetAsync(b.counters, 0, CLS_COUNTER_INTS * sizeof(int), st));
-  OrbLevels lv{};
-  lv.l[0].im = b.im; lv.l[0].score = b.score; lv.l[0].h = rows; lv.l[0].w = cols; lv.l[0].want = 1; lv.l[0].scale = 1.f;
-  const dim3 grid((cols + 63) / 64, (rows + 3) / 4, 1);
-  hipLaunchKernelGGL(orb_fast_kernel, grid, dim3(256), 0, st, lv, threshold, 3);
-  hipLaunchKernelGGL(fast_collect_kernel, grid, dim3(256), 0, st, b.score, rows, cols, nonmax_suppression ? 1 : 0, b.keys, key_cap, b.counters);
-  hipLaunchKernelGGL(cls_rank_kernel, dim3(128), dim3(256), 0, st, b.keys, b.rank, b.counters + 1, key_cap);
-  hipLaunchKernelGGL(fast_write_kernel, dim3(32), dim3(256), 0, st, cols, b.keys, b.rank, key_cap, b.xy, b.resp, b.counters);
+  if (int rc = fast_enqueue(c, rows, cols, threshold, nonmax_suppression)) return rc;
   return cls_read_out(c, xy, response, cap, n_out, "spvo_fast_detect");
 }
 
@@ -394,6 +440,211 @@ int spvo_orb_describe(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_
   HIP_TRY(c, hipMemcpyAsync(desc, b.desc, (size_t)nk * 32, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
   if (angle) for (int i = 0; i < nk; ++i) angle[i] = kp[i].angle;
+  return SPVO_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- one submission per stereo pair, features stay on the device
+// everything bin_ensure sizes by the slot capacity; the slots are empty afterwards
+void spvo_int::classic_release_slots(spvo_ctx *c) {
+  auto &bb = c->bin;
+  for (BinarySlot &s : bb.slots) {
+    dev_free(s.d_kp, s.d_desc, s.d_n);
+    s.filled = false; s.n = 0; ++s.gen;
+  }
+  dev_free(bb.d_cnt, bb.d_kxy, bb.d_kresp, bb.d_vote);
+  for (void *p : {(void *)bb.h_kp, (void *)bb.h_desc, (void *)bb.h_n, (void *)bb.h_match}) if (p) (void)hipHostFree(p);
+  bb.h_kp = nullptr; bb.h_desc = nullptr; bb.h_n = nullptr; bb.h_match = nullptr;
+  for (auto &mc : bb.mcache) { mc.valid = false; mc.h_out = nullptr; }
+  bb.cap = 0; bb.last_slot_l = -1;
+}
+
+void spvo_int::classic_release(spvo_ctx *c) {
+  auto &bb = c->bin;
+  classic_release_slots(c);
+  if (bb.h_img) (void)hipHostFree(bb.h_img);
+  bb.h_img = nullptr; bb.img_cap = 0;
+  if (bb.ev_feat) (void)hipEventDestroy(bb.ev_feat);
+  if (bb.ev_match) (void)hipEventDestroy(bb.ev_match);
+  bb.ev_feat = bb.ev_match = nullptr;
+}
+
+extern "C" {
+
+namespace {
+// the binary slots and the call's own buffers for `cap` rows per slot and images of `px` bytes; growing un-fills every slot
+int bin_ensure(spvo_ctx *c, int cap, size_t px) {
+  auto &bb = c->bin;
+  if (!bb.ev_feat) {
+    HIP_TRY(c, hipEventCreateWithFlags(&bb.ev_feat, hipEventDisableTiming));
+    HIP_TRY(c, hipEventCreateWithFlags(&bb.ev_match, hipEventDisableTiming));
+  }
+  if (px > bb.img_cap) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream2));
+    if (bb.h_img) (void)hipHostFree(bb.h_img);
+    bb.h_img = nullptr; bb.img_cap = 0;
+    HIP_TRY(c, hipHostMalloc((void **)&bb.h_img, 2 * px));
+    bb.img_cap = px;
+  }
+  if (cap <= bb.cap) return SPVO_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream2));
+  classic_release_slots(c);
+  int rc;
+  for (BinarySlot &s : bb.slots)
+    if ((rc = dev_alloc(c, &s.d_kp, cap)) || (rc = dev_alloc(c, &s.d_desc, (size_t)cap * 8)) || (rc = dev_alloc(c, &s.d_n, 1))) return rc;
+  if ((rc = dev_alloc(c, &bb.d_cnt, 2 * CLS_COUNTER_INTS)) || (rc = dev_alloc(c, &bb.d_kxy, (size_t)2 * cap)) || (rc = dev_alloc(c, &bb.d_kresp, cap)) ||
+      (rc = dev_alloc(c, &bb.d_vote, cap)))
+    return rc;
+  HIP_TRY(c, hipHostMalloc((void **)&bb.h_kp, (size_t)2 * cap * sizeof(OrbKeypoint)));
+  HIP_TRY(c, hipHostMalloc((void **)&bb.h_desc, (size_t)2 * cap * 32));
+  HIP_TRY(c, hipHostMalloc((void **)&bb.h_n, 2 * 4 * sizeof(int)));
+  HIP_TRY(c, hipHostMalloc((void **)&bb.h_match, (size_t)3 * cap * sizeof(int2)));
+  for (int k = 0; k < 2; ++k) bb.mcache[k].h_out = bb.h_match + (size_t)k * cap;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
+  bb.cap = cap;
+  return SPVO_OK;
+}
+}  // namespace
+
+void spvo_default_classic_opts(spvo_classic_opts *o, int kind) {
+  if (!o) return;
+  o->kind = kind;
+  o->nfeatures = 2000;                                                                  // cv::ORB::create(2000, ...), classic.cpp:12-25
+  o->max_corners = 1000; o->quality_level = 0.03; o->min_distance = 7.5; o->block_size = 5;   // cv::GFTTDetector::create(1000, 0.03, 7.5, 5, ..), classic.cpp:37-47
+  o->fast_threshold = 10; o->fast_nonmax = 1;                                           // cv::FastFeatureDetector::create(10, true), classic.cpp:32-36
+  o->slot_capacity = 8192;
+}
+
+int spvo_classic_slot_rows(spvo_ctx *c, int slot, int *n) {
+  if (!c || !n || slot < 0 || slot >= N_BIN_SLOTS) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  const BinarySlot &s = c->bin.slots[slot];
+  if (!s.filled) return fail(c, SPVO_ERR_STATE, "binary slot %d holds no features (spvo_classic_detect fills it)", slot);
+  *n = s.n;
+  return SPVO_OK;
+}
+
+int spvo_classic_detect(spvo_ctx *c, const spvo_classic_opts *opts, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int slot_l, int slot_r,
+                        spvo_classic_features *out_l, spvo_classic_features *out_r) {
+  if (!c || !opts || !img_l || !img_r || !out_l || !out_r || rows <= 0 || cols <= 0 || stride < (size_t)cols) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  if (slot_l < 0 || slot_l >= N_BIN_SLOTS || slot_r < 0 || slot_r >= N_BIN_SLOTS || slot_l == slot_r) return fail(c, SPVO_ERR_INVALID, "bad slot");
+  spvo_classic_features *outs[2] = {out_l, out_r};
+  for (auto *o : outs)
+    if (o->cap < 0) return fail(c, SPVO_ERR_INVALID, "bad output buffer");
+  const int kind = opts->kind, cap = opts->slot_capacity;
+  if (cap <= 0 || cap > (1 << HAM_KEY_SHIFT)) return fail(c, SPVO_ERR_INVALID, "slot_capacity must be 1 .. %d", 1 << HAM_KEY_SHIFT);
+  // what the per-image entry points refuse
+  if (kind == SPVO_CLASSIC_ORB) {
+    if (opts->nfeatures <= 0) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  } else if (kind == SPVO_CLASSIC_GFTT_ORB) {
+    if (rows < 8 || cols < 8 || !(opts->quality_level > 0)) return fail(c, SPVO_ERR_INVALID, "bad argument");
+    if (opts->block_size != 5 || !(opts->min_distance >= 0 && opts->min_distance <= 15)) return fail(c, SPVO_ERR_INVALID, "spvo_classic_detect: block_size 5 and min_distance <= 15 only");
+  } else if (kind == SPVO_CLASSIC_FAST_ORB) {
+    if (opts->fast_threshold < 0 || opts->fast_threshold > 255) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  } else {
+    return fail(c, SPVO_ERR_INVALID, "unknown kind %d", kind);
+  }
+  if (!c->pendq.empty()) return fail(c, SPVO_ERR_STATE, "detector submissions are in flight: complete them with spvo_detect_wait first");
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  out_l->n = out_r->n = 0;
+  hipStream_t st = c->stream2;
+  auto &bb = c->bin;
+  auto &o = c->orb;
+  auto &b = c->cls;
+  const size_t px = (size_t)rows * cols;
+  if (int rc = bin_ensure(c, cap, px)) return rc;
+  OrbPlan plan;
+  if (kind == SPVO_CLASSIC_ORB) {
+    if (int rc = orb_prepare(c, rows, cols, opts->nfeatures, plan)) return rc;
+  } else {
+    if (int rc = cls_ensure(c, rows, cols)) return rc;
+    if (int rc = orb_ensure_tables(c)) return rc;
+  }
+  // both slots are being rewritten: whatever was matched against their old contents is stale
+  const int slots[2] = {slot_l, slot_r};
+  for (int sl : slots) { BinarySlot &s = bb.slots[sl]; s.filled = false; s.n = 0; ++s.gen; }
+  for (auto &mc : bb.mcache) mc.valid = false;
+  // pinned staging: both images with packed rows (of a strided view only the rows' own bytes are the caller's), one upload each
+  HIP_TRY(c, hipStreamSynchronize(st));   // (the staging buffer and the mirrors are the previous call's until its work is done)
+  const uint8_t *imgs[2] = {img_l, img_r};
+  for (int k = 0; k < 2; ++k)
+    for (int r = 0; r < rows; ++r) std::memcpy(bb.h_img + k * px + (size_t)r * cols, imgs[k] + (size_t)r * stride, cols);
+  for (int k = 0; k < 2; ++k) {
+    BinarySlot &s = bb.slots[slots[k]];
+    int *h_n = bb.h_n + 4 * k;
+    OrbKeypoint *h_kp = bb.h_kp + (size_t)k * cap;
+    uint4 *h_desc = reinterpret_cast<uint4 *>(bb.h_desc + (size_t)k * cap * 32);
+    if (kind == SPVO_CLASSIC_ORB) {
+      HIP_TRY(c, hipMemcpyAsync(o.im, bb.h_img + k * px, px, hipMemcpyHostToDevice, st));
+      const int kp_cap = std::min(opts->nfeatures, cap);   // (more than `cap` rows are an error below: the slot need not hold them)
+      if (int rc = orb_enqueue(c, plan, rows, cols, s.d_kp, reinterpret_cast<uint8_t *>(s.d_desc), kp_cap)) return rc;
+      hipLaunchKernelGGL(classic_finish_kernel, dim3(32), dim3(256), 0, st, o.counters, ORB_LEVELS, NMS_COUNTER_INTS, opts->nfeatures, nullptr, nullptr, nullptr, s.d_kp,
+                         reinterpret_cast<const uint4 *>(s.d_desc), cap, s.d_n, h_n, h_kp, h_desc);
+    } else {
+      b.rows = b.cols = 0;
+      HIP_TRY(c, hipMemcpyAsync(b.im, bb.h_img + k * px, px, hipMemcpyHostToDevice, st));
+      b.rows = rows; b.cols = cols;
+      if (int rc = kind == SPVO_CLASSIC_GFTT_ORB ? gftt_enqueue(c, rows, cols, opts->max_corners, opts->quality_level, opts->min_distance)
+                                                 : fast_enqueue(c, rows, cols, opts->fast_threshold, opts->fast_nonmax))
+        return rc;
+      // detector -> extractor on the device: the border rule as an order-preserving compaction, then orb.hip.h's extractor on a one-level
+      // OrbLevels whose keypoint list is the compacted one and whose count is the compaction's (spvo_orb_describe, without the host)
+      int *cnt = bb.d_cnt + k * CLS_COUNTER_INTS;
+      hipLaunchKernelGGL(cls_compact_kernel, dim3(1), dim3(1024), 0, st, b.xy, b.resp, b.counters, rows, cols, ORB_EDGE, bb.d_kxy, bb.d_kresp, cap, cnt);
+      const int most = kind == SPVO_CLASSIC_GFTT_ORB && opts->max_corners > 0 ? std::min(cap, opts->max_corners) : cap;   // rows the extractor's grid covers
+      OrbLevels lv{};
+      OrbLevel &L = lv.l[0];
+      L.im = b.im; L.score = b.score; L.blur = b.blur; L.tmp = b.tmp; L.out_xy = bb.d_kxy; L.counters = cnt;
+      L.h = rows; L.w = cols; L.want = most; L.cap = most; L.scale = 1.f;
+      const dim3 grid((cols + 63) / 64, (rows + 3) / 4, 1);
+      hipLaunchKernelGGL(orb_blur_h_kernel, grid, dim3(256), 0, st, lv, o.taps);
+      hipLaunchKernelGGL(orb_blur_v_kernel, grid, dim3(256), 0, st, lv, o.taps);
+      hipLaunchKernelGGL(orb_describe_kernel, dim3((most + 3) / 4, 1), dim3(256), 0, st, lv, o.disc, o.pattern, s.d_kp, reinterpret_cast<uint8_t *>(s.d_desc), cap);
+      hipLaunchKernelGGL(classic_finish_kernel, dim3(32), dim3(256), 0, st, nullptr, 0, 0, 0, b.counters, cnt, bb.d_kresp, s.d_kp, reinterpret_cast<const uint4 *>(s.d_desc), cap,
+                         s.d_n, h_n, h_kp, h_desc);
+    }
+    HIP_TRY(c, hipGetLastError());
+  }
+  HIP_TRY(c, hipEventRecord(bb.ev_feat, st));
+  // spvo_set_prematch: the two standard matches behind the features, counts read on the device (a pair that turns out not to fit its
+  // slots is matched on whatever rows the slots hold; that result is dropped below)
+  const int prev_l = bb.last_slot_l;
+  const bool temporal = prev_l >= 0 && prev_l != slot_l && prev_l != slot_r && bb.slots[prev_l].filled;
+  if (c->prematch) {
+    if (int rc = enqueue_hamming_slots(c, slot_l, slot_r, c->pm_selector, c->pm_cross, c->pm_ratio, bb.mcache[0].h_out)) return rc;
+    if (temporal)
+      if (int rc = enqueue_hamming_slots(c, slot_l, prev_l, c->pm_selector, c->pm_cross, c->pm_ratio, bb.mcache[1].h_out)) return rc;
+    HIP_TRY(c, hipEventRecord(bb.ev_match, st));
+  }
+  HIP_TRY(c, wait_event(bb.ev_feat));   // the one wait of the call: the matches go on behind it
+  bb.last_slot_l = -1;
+  int worst = SPVO_OK;
+  for (int k = 0; k < 2; ++k) {
+    const int *h_n = bb.h_n + 4 * k;
+    outs[k]->n = h_n[0];
+    if (h_n[1]) return fail(c, SPVO_ERR_CAPACITY, "spvo_classic_detect: corner buffer overflow in the %s image", k ? "right" : "left");
+    if (h_n[0] > cap) worst = SPVO_ERR_CAPACITY;
+  }
+  if (worst) return fail(c, worst, "spvo_classic_detect: %d / %d rows do not fit slots of %d (slot_capacity)", out_l->n, out_r->n, cap);
+  for (int k = 0; k < 2; ++k) {
+    BinarySlot &s = bb.slots[slots[k]];
+    s.n = outs[k]->n; s.filled = true;
+    const int ncopy = std::min(s.n, outs[k]->cap);
+    if (ncopy > 0 && outs[k]->kp) std::memcpy(outs[k]->kp, bb.h_kp + (size_t)k * cap, (size_t)ncopy * sizeof(OrbKeypoint));
+    if (ncopy > 0 && outs[k]->desc) std::memcpy(outs[k]->desc, bb.h_desc + (size_t)k * cap * 32, (size_t)ncopy * 32);
+  }
+  if (c->prematch) {
+    const BinarySlot &l = bb.slots[slot_l];
+    const int partner[2] = {slot_r, temporal ? prev_l : -1};
+    for (int k = 0; k < 2; ++k) {
+      MatchCache &mc = bb.mcache[k];
+      if (partner[k] < 0) continue;
+      mc.valid = true;
+      mc.slot_a = slot_l; mc.slot_b = partner[k]; mc.selector = c->pm_selector; mc.cross = c->pm_cross; mc.ratio = c->pm_ratio;
+      mc.gen_a = l.gen; mc.gen_b = bb.slots[partner[k]].gen;
+    }
+  }
+  bb.last_slot_l = slot_l;
   return SPVO_OK;
 }
 

@@ -472,6 +472,7 @@ void spvo_destroy(spvo_ctx *c) {
   }
   if (c->d_ctl) (void)hipFree(c->d_ctl);
   dev_free(c->d_ham_a, c->d_ham_b, c->d_ham_idx, c->d_ham_dist, c->d_ham_vote);
+  classic_release(c);
   auto &o = c->orb;
   dev_free(o.im, o.score, o.blur, o.src, o.tmp, o.pattern, o.taps, o.keys, o.rank, o.out_xy, o.counters, o.tab, o.disc, o.kps, o.desc);
   auto &b = c->cls;

@@ -37,6 +37,8 @@ namespace spvo_int {
 constexpr int RING = 8;          // buffer sets a detector submission owns (network outputs, heat map, NMS state, counters, host mirrors)
 constexpr int MAX_INFLIGHT = 6;  // detector submissions that may be queued at once (< RING - 1: the sets of the pairs just completed still serve their matches and mirrors)
 constexpr int N_SLOTS = 16;      // feature slots: 8 stereo pairs (previous, current and up to six in flight)
+constexpr int N_BIN_SLOTS = 10;  // binary feature slots of the classic front end (spvo_classic_detect): a ring of stereo pairs, numbered like the float slots
+constexpr int HAM_KEY_SHIFT = 22;   // the tiled Hamming matcher orders (distance, row) as ONE 32-bit key: distance << 22 | row, so a slot holds at most 2^22 rows
 
 struct Tensor {
   int ch = 0, level = 0, H = 0, W = 0, hp = 0, wp = 0;
@@ -97,6 +99,17 @@ struct FeatureSlot {
   int *d_n = nullptr;       // device copy of n (read by kernels enqueued before the host knows n)
   float *d_sqn = nullptr;   // [cap] squared norms of the descriptors (written by the sampler)
   unsigned long long gen = 0;  // bumped whenever the slot is rewritten
+};
+
+// a classic stereo image's features, resident on the device (spvo_classic_detect -> spvo_match_hamming_slots); the buffers of all
+// binary slots have ONE capacity (spvo_ctx::bin.cap)
+struct BinarySlot {
+  int n = 0;
+  bool filled = false;
+  OrbKeypoint *d_kp = nullptr;   // [cap] x, y, angle, response, octave
+  uint32_t *d_desc = nullptr;    // [cap][8] the matcher's row format: 32 bytes are 8 words, nothing to pad
+  int *d_n = nullptr;            // device copy of n (read by kernels enqueued before the host knows n)
+  unsigned long long gen = 0;    // bumped whenever the slot is rewritten
 };
 
 // matches enqueued together with the detector (spvo_set_prematch); results live in pinned memory
@@ -308,6 +321,25 @@ struct spvo_ctx {
     int pre_crop_rows = 0, pre_crop_cols = 0;
     int last_counters[16] = {0};          // the counter block of the last spvo_gftt_detect (rounds, undecided after each launch)
   } cls;
+  // spvo_classic_detect / spvo_match_hamming_slots: the binary slots, the call's pinned staging and mirrors, the matcher's vote scratch and
+  // the two matches enqueued with the detector (spvo_set_prematch).  Everything is sized by `cap` rows and lives on the solver's stream.
+  struct BinaryBufs {
+    int cap = 0;
+    BinarySlot slots[N_BIN_SLOTS];
+    uint8_t *h_img = nullptr;            // pinned [2][img_cap]: both images of a call, rows packed
+    size_t img_cap = 0;
+    OrbKeypoint *h_kp = nullptr;         // pinned [2][cap]      what the finishing kernel of an image writes for the host:
+    uint8_t *h_desc = nullptr;           // pinned [2][cap][32]  keypoint records, descriptors,
+    int *h_n = nullptr;                  // pinned [2][4]        {rows found, overflow flag of the detector}
+    int *d_cnt = nullptr;                // [2][CLS_COUNTER_INTS] the extractor's counter block per image (0: kept in all, 2: kept and described)
+    int *d_kxy = nullptr;                // [cap][2] the kept keypoints of a Shi-Tomasi / FAST image (cls_compact_kernel), ...
+    float *d_kresp = nullptr;            // [cap]    ... and the detector's responses of those
+    unsigned long long *d_vote = nullptr;   // [cap] cross-check votes
+    int2 *h_match = nullptr;             // pinned [3][cap]: the two prematches, the synchronous call
+    MatchCache mcache[2];                // [stereo, temporal]: slot numbers are BINARY slots
+    hipEvent_t ev_feat = nullptr, ev_match = nullptr;   // features of the last call final / its prematches landed
+    int last_slot_l = -1;                // left slot of the previous call (temporal partner)
+  } bin;
   // Hamming matcher (classic front end's binary descriptors): rows padded to 16 words
   int ham_cap = 0;
   uint32_t *d_ham_a = nullptr, *d_ham_b = nullptr;
@@ -473,6 +505,8 @@ int run_network(spvo_ctx *c, int batch);
 void resize_tables(int dst_w, int src_w, int dst_h, int src_h, std::vector<int> &out);
 // ---- spvo_classic.hip: spvo_preprocess of a context without an engine (d_img[0] -> cls.pre_out, enqueued on the network stream)
 int classic_preprocess(spvo_ctx *c, const CropGeom &g, size_t stride);
+void classic_release(spvo_ctx *c);   // frees spvo_ctx::bin (spvo_destroy)
+void classic_release_slots(spvo_ctx *c);   // ... the part of it that is sized by the slot capacity
 // ---- spvo_match.hip
 int ensure_match(spvo_ctx *c, int na, int nb);
 struct MatchReq {
@@ -482,6 +516,8 @@ struct MatchReq {
   const float *sqA, *sqB;         // squared norms if already known (feature slots), else NULL
 };
 int enqueue_matches(spvo_ctx *c, const MatchReq *req_in, int njobs, int selector, int cross_check, float ratio, int2 *host_out);
+// one Hamming match between two binary slots, enqueued on the solver's stream with the counts read on the device; packed result -> host_out (pinned)
+int enqueue_hamming_slots(spvo_ctx *c, int slot_a, int slot_b, int selector, int cross_check, float ratio, int2 *host_out);
 
 }  // namespace spvo_int
 #pragma GCC visibility pop

@@ -156,6 +156,27 @@ int run_match(spvo_ctx *c, const MatchReq &r, int selector, int cross_check, flo
   return SPVO_OK;
 }
 
+// One Hamming match between two binary slots on the solver's stream, counts read on the device (match.hip.h K12t): the packed result
+// {train_idx, distance bits} of every row of slot_a lands in `host_out` (pinned).  NN + cross-check is cv::batchDistance's crosscheck as in
+// spvo_match_hamming: the train rows vote for their nearest query row, then every query row reads its vote.
+int enqueue_hamming_slots(spvo_ctx *c, int slot_a, int slot_b, int selector, int cross_check, float ratio, int2 *host_out) {
+  static_assert(HAM_SHIFT == HAM_KEY_SHIFT, "the key layout of match.hip.h and the capacity limit of spvo_classic_detect differ");
+  auto &bb = c->bin;
+  const BinarySlot &a = bb.slots[slot_a], &b = bb.slots[slot_b];
+  hipStream_t st = c->stream2;
+  const int cap = bb.cap;
+  const dim3 grid((cap + HAM_QB - 1) / HAM_QB);
+  if (cross_check && selector == SPVO_SELECT_NN) {   // BFMatcher's crossCheck is off for knnMatch (base.cpp:27-28)
+    HIP_TRY(c, hipMemsetAsync(bb.d_vote, 0xFF, (size_t)cap * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(match_hamming_tiled_kernel, grid, dim3(256), 0, st, b.d_desc, b.d_n, a.d_desc, a.d_n, cap, 2, ratio, host_out, bb.d_vote);
+    hipLaunchKernelGGL(match_hamming_cross_slots_kernel, dim3((cap + 255) / 256), dim3(256), 0, st, bb.d_vote, a.d_n, cap, host_out);
+  } else {
+    hipLaunchKernelGGL(match_hamming_tiled_kernel, grid, dim3(256), 0, st, a.d_desc, a.d_n, b.d_desc, b.d_n, cap, selector == SPVO_SELECT_KNN ? 1 : 0, ratio, host_out, bb.d_vote);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return SPVO_OK;
+}
+
 }  // namespace spvo_int
 
 // ===========================================================================
@@ -259,6 +280,31 @@ int spvo_match_slots(spvo_ctx *c, int slot_a, int slot_b, int selector, int cros
   return run_match(c, MatchReq{a.d_desc, b.d_desc, a.n, b.n, nullptr, nullptr, a.d_sqn, b.d_sqn}, selector, cross_check ? 1 : 0, ratio, train_idx, distance);
 }
 
+// The Hamming match of two binary slots (spvo_classic_detect).  Served from the call's prematch when it is exactly that match of exactly
+// those slot contents (the generation check of spvo_match_slots), computed on the spot otherwise.
+int spvo_match_hamming_slots(spvo_ctx *c, int slot_a, int slot_b, int selector, int cross_check, float ratio, int32_t *train_idx, float *distance) {
+  if (!c || slot_a < 0 || slot_a >= N_BIN_SLOTS || slot_b < 0 || slot_b >= N_BIN_SLOTS) return fail(c, SPVO_ERR_INVALID, "bad slot");
+  if (selector != SPVO_SELECT_NN && selector != SPVO_SELECT_KNN) return fail(c, SPVO_ERR_INVALID, "bad selector");
+  auto &bb = c->bin;
+  const BinarySlot &a = bb.slots[slot_a], &b = bb.slots[slot_b];
+  if (!a.filled || !b.filled) return fail(c, SPVO_ERR_STATE, "binary slot %d holds no features (spvo_classic_detect fills it)", a.filled ? slot_b : slot_a);
+  if (a.n > 0 && (!train_idx || !distance)) return fail(c, SPVO_ERR_INVALID, "null output");
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  const int cross = cross_check ? 1 : 0;
+  for (const auto &mc : bb.mcache)
+    if (mc.valid && mc.slot_a == slot_a && mc.slot_b == slot_b && mc.gen_a == a.gen && mc.gen_b == b.gen && mc.selector == selector && mc.cross == cross && mc.ratio == ratio) {
+      HIP_TRY(c, wait_event(bb.ev_match));
+      unpack_match(mc.h_out, a.n, train_idx, distance);
+      return SPVO_OK;
+    }
+  if (a.n == 0) return SPVO_OK;
+  int2 *h = bb.h_match + (size_t)2 * bb.cap;
+  if (int rc = enqueue_hamming_slots(c, slot_a, slot_b, selector, cross, ratio, h)) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream2));
+  unpack_match(h, a.n, train_idx, distance);
+  return SPVO_OK;
+}
+
 int spvo_set_prematch(spvo_ctx *c, int enable, int selector, int cross_check, float ratio) {
   if (!c) return fail(c, SPVO_ERR_INVALID, "null context");
   if (selector != SPVO_SELECT_NN && selector != SPVO_SELECT_KNN) return fail(c, SPVO_ERR_INVALID, "bad selector");
@@ -268,6 +314,7 @@ int spvo_set_prematch(spvo_ctx *c, int enable, int selector, int cross_check, fl
   c->pm_ratio = ratio;
   for (SubmitSet &s : c->sets)
     for (auto &mc : s.mcache) mc.valid = false;
+  for (auto &mc : c->bin.mcache) mc.valid = false;
   return SPVO_OK;
 }
 

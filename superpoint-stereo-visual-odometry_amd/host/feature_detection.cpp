@@ -143,6 +143,7 @@ void FeatureFrontEnd::clearLagecyData() {
   keypoints_dq.clear();
   descriptors_dq.clear();
   slots_dq_.clear();
+  bin_slots_dq_.clear();
   for (auto &m : cv_DMatches_list) m.clear();
   projection_matrix_l_.release();
   projection_matrix_r_.release();
@@ -197,7 +198,11 @@ void FeatureFrontEnd::matchDescriptors(const MatchType match_type) {
       logError("matchDescriptors: binary descriptors expected (CV_8U, one row per keypoint, equal widths)");
       return;
     }
-    rc = spvo_match_hamming(ctx_, rows_of(d0, b0), d0.rows, rows_of(d1, b1), d1.rows, nbytes, sel, matcher_cross_check_ ? 1 : 0, knn_threshold_, train.data(), dist.data());
+    // both sides resident on the device (ClassicFeatureFrontEnd::setDeviceResident): no packing, no upload, and usually no launch either
+    // -- the two standard matches were enqueued with the detector
+    const bool resident = bin_slots_dq_.size() == keypoints_dq.size() && bin_slots_dq_.end()[p0] >= 0 && bin_slots_dq_.end()[p1] >= 0;
+    if (resident) rc = spvo_match_hamming_slots(ctx_, bin_slots_dq_.end()[p0], bin_slots_dq_.end()[p1], sel, matcher_cross_check_ ? 1 : 0, knn_threshold_, train.data(), dist.data());
+    else rc = spvo_match_hamming(ctx_, rows_of(d0, b0), d0.rows, rows_of(d1, b1), d1.rows, nbytes, sel, matcher_cross_check_ ? 1 : 0, knn_threshold_, train.data(), dist.data());
   } else {
     completeImageCopies();   // the GPU is still matching (spvo_match_slots waits for it): images_dq's share of the deferred copies fits here
     rc = spvo_match_slots(ctx_, slots_dq_.end()[p0], slots_dq_.end()[p1], sel, matcher_cross_check_ ? 1 : 0, knn_threshold_, train.data(), dist.data());
@@ -408,6 +413,11 @@ cv::Mat FeatureFrontEnd::visualizeInliers(const ImagePosition image_position) {
 // The reference's constructor hands `stereo_threshold` to the base class a second time in the place of `min_disparity`
 // (hpp:203-206), so the classic launch file's min_disparity is never used; kept, because the stereo gate of
 // solveStereoOdometry (base.cpp:169-172) then behaves as the reference's does.
+static bool g_classic_resident = false;
+static int g_classic_resident_capacity = 8192;
+void ClassicFeatureFrontEnd::setDeviceResident(bool on) { g_classic_resident = on; }
+void ClassicFeatureFrontEnd::setResidentCapacity(int rows) { g_classic_resident_capacity = rows; }
+
 ClassicFeatureFrontEnd::ClassicFeatureFrontEnd()
     : ClassicFeatureFrontEnd(DetectorType::ShiTomasi, DescriptorType::ORB, MatcherType::BF, SelectorType::NN, true, 2.0f, 1.0f, 4, true, 120, 392) {}
 
@@ -420,6 +430,8 @@ ClassicFeatureFrontEnd::ClassicFeatureFrontEnd(const DetectorType detector_type,
   initDetector();
   initDescriptor();
   initMatcher();
+  resident_ = g_classic_resident;
+  resident_capacity_ = g_classic_resident_capacity;
 }
 
 ClassicFeatureFrontEnd::~ClassicFeatureFrontEnd() {
@@ -429,6 +441,7 @@ ClassicFeatureFrontEnd::~ClassicFeatureFrontEnd() {
 
 #ifdef SPVO_USE_OPENCV
 bool ClassicFeatureFrontEnd::available() { return true; }
+bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &, cv::Mat &) { return false; }   // (the OpenCV detectors work on the host)
 
 void ClassicFeatureFrontEnd::initDetector() {   // parameters: classic.cpp:7-56
   if (detector_type_ == DetectorType::ORB) detector_ = cv::ORB::create(2000, 1.2f, 8, 31, 0, 2, cv::ORB::FAST_SCORE, 31, 20);
@@ -620,18 +633,73 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
     preprocessImageImpl(img_l, projection_matrix_l_);
     preprocessImageImpl(img_r, projection_matrix_r_);
   }
-  cv::Mat *imgs[2] = {&img_l, &img_r};
-  for (cv::Mat *im : imgs) {
-    images_dq.push_back(*im);
-    keypoints_dq.push_back(detectKeypoints(*im));
-    descriptors_dq.push_back(describeKeypoints(keypoints_dq.back(), *im));
+  if (!resident_ || !addStereoImagePairResident(img_l, img_r)) {
+    cv::Mat *imgs[2] = {&img_l, &img_r};
+    for (cv::Mat *im : imgs) {
+      images_dq.push_back(*im);
+      keypoints_dq.push_back(detectKeypoints(*im));
+      descriptors_dq.push_back(describeKeypoints(keypoints_dq.back(), *im));
+      if (resident_) bin_slots_dq_.push_back(-1);   // on the host only
+    }
   }
   if (verbose_) logInfo(std::to_string(keypoints_dq.end()[-2].size()) + ", " + std::to_string(keypoints_dq.end()[-1].size()) + " keypoints for img_l and img_r");
   while (images_dq.size() > NUM_IMAGE_POSITIONS) {
     images_dq.pop_front();
     keypoints_dq.pop_front();
     descriptors_dq.pop_front();
+    if (!bin_slots_dq_.empty()) bin_slots_dq_.pop_front();
   }
+}
+
+// setDeviceResident: the pair through ONE spvo_classic_detect call into the next slot pair of the ring; the deques are filled from what it
+// hands out, which is what detectKeypoints + describeKeypoints produce image by image.  false: nothing was pushed and the caller takes
+// the per-image path (the pair does not fit its slots, or the call failed and the per-image path reports why).
+bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &img_l, cv::Mat &img_r) {
+  if (img_l.depth() != CV_8U || img_l.rows <= 0 || img_r.depth() != CV_8U || (size_t)img_l.step != (size_t)img_r.step) return false;
+  spvo_classic_opts opts;
+  const bool orb = detector_type_ == DetectorType::ORB, gftt = detector_type_ == DetectorType::ShiTomasi;
+  spvo_default_classic_opts(&opts, orb ? SPVO_CLASSIC_ORB : gftt ? SPVO_CLASSIC_GFTT_ORB : SPVO_CLASSIC_FAST_ORB);
+  opts.slot_capacity = resident_capacity_;
+  if (resident_pairs_ == 0) spvo_set_prematch(ctx_, 1, selector_type_ == SelectorType::KNN ? SPVO_SELECT_KNN : SPVO_SELECT_NN, matcher_cross_check_ ? 1 : 0, knn_threshold_);
+  const int cap = std::max(resident_capacity_, 1);
+  spvo_classic_features f[2];
+  for (int k = 0; k < 2; ++k) {
+    if (resident_kp_[k].size() != (size_t)cap) { resident_kp_[k].resize((size_t)cap); resident_desc_[k].resize((size_t)cap * 32); }   // first pair only
+    f[k] = spvo_classic_features{0, resident_kp_[k].data(), resident_desc_[k].data(), cap};
+  }
+  const int slot_l = 2 * (int)(resident_pairs_ % 4), slot_r = slot_l + 1;
+  ++resident_pairs_;
+  const int rc = spvo_classic_detect(ctx_, &opts, img_l.ptr<uint8_t>(0), img_r.ptr<uint8_t>(0), img_l.rows, img_l.cols, (size_t)img_l.step, slot_l, slot_r, &f[0], &f[1]);
+  if (rc != SPVO_OK) {
+    if (rc != SPVO_ERR_CAPACITY) logError(std::string("spvo_classic_detect: ") + spvo_last_error(ctx_));
+    return false;
+  }
+  float level_scale[8];
+  level_scale[0] = 1.f;
+  for (int l = 1; l < 8; ++l) level_scale[l] = level_scale[l - 1] * 1.2f;
+  cv::Mat *imgs[2] = {&img_l, &img_r};
+  for (int k = 0; k < 2; ++k) {
+    const int n = f[k].n;
+    std::vector<cv::KeyPoint> keypoints;
+    keypoints.reserve(n);
+    for (int i = 0; i < n; ++i) {
+      const spvo_orb_keypoint &p = resident_kp_[k][i];
+      // size: 31 x the level's scale (ORB) / KeyPoint::convert(corners, keypoints, blockSize) / KeyPoint(x, y, 7.f, -1, score), as detectKeypoints
+      cv::KeyPoint q(cv::Point2f(p.x, p.y), orb ? 31.f * level_scale[p.octave & 7] : gftt ? 5.f : 7.f);
+      q.angle = p.angle * 57.29577951308232f;   // cv::KeyPoint::angle is in degrees
+      if (q.angle < 0) q.angle += 360.f;
+      q.response = p.response;
+      q.octave = p.octave;
+      keypoints.push_back(q);
+    }
+    cv::Mat d(n, 32, CV_8UC1);
+    if (n) std::memcpy(d.ptr<uint8_t>(0), resident_desc_[k].data(), (size_t)n * 32);
+    images_dq.push_back(*imgs[k]);
+    keypoints_dq.push_back(std::move(keypoints));
+    descriptors_dq.push_back(d);
+    bin_slots_dq_.push_back(k ? slot_r : slot_l);
+  }
+  return true;
 }
 #endif
 

@@ -303,6 +303,9 @@ protected:
   // C-ABI context and the device feature slot each deque entry lives in
   spvo_ctx *ctx_ = nullptr;
   std::deque<int> slots_dq_;
+  // the classic front end with setDeviceResident: the BINARY slot each deque entry lives in, -1 for one that exists on the host only
+  // (a pair that did not fit its slots); empty when the option is off
+  std::deque<int> bin_slots_dq_;
   std::string last_error_;
   bool last_pnp_ok_ = false, last_accepted_ = false, last_refined_ = false;
   int last_lm_iterations_ = 0;
@@ -336,8 +339,21 @@ public:
   std::vector<cv::KeyPoint> detectKeypoints(const cv::Mat &img);
   cv::Mat describeKeypoints(std::vector<cv::KeyPoint> &keypoints, const cv::Mat &img);
   static bool available();   // false in a build without OpenCV
+  // Extension, set like SuperPointFeatureFrontEnd::setMatchFp8: before construction, for the front ends constructed afterwards.  On: a stereo
+  // pair is ONE spvo_classic_detect call into a rolling ring of four binary slot pairs, its features stay on the device and matchDescriptors
+  // runs spvo_match_hamming_slots on them, the two standard matches enqueued with the detector (spvo_set_prematch).  keypoints_dq,
+  // descriptors_dq and every match are what they are with the option off (the default).  A pair with more rows than the slots hold
+  // (setResidentCapacity; SPVO_ERR_CAPACITY) goes through the per-image path and is matched from the host matrices.
+  static void setDeviceResident(bool on);
+  static void setResidentCapacity(int rows);   // rows per binary slot [8192]
 
 private:
+  bool resident_ = false;
+  int resident_capacity_ = 8192;
+  unsigned resident_pairs_ = 0;   // pairs handed to spvo_classic_detect: pair k lives in slots 2 (k % 4), 2 (k % 4) + 1
+  std::vector<spvo_orb_keypoint> resident_kp_[2];   // what spvo_classic_detect hands out, resident_capacity_ rows per image: allocated once
+  std::vector<uint8_t> resident_desc_[2];
+  bool addStereoImagePairResident(cv::Mat &img_l, cv::Mat &img_r);
 #ifdef SPVO_USE_OPENCV
   cv::Ptr<cv::FeatureDetector> detector_;
   cv::Ptr<cv::DescriptorExtractor> extractor_;

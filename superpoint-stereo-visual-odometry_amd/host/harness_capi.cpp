@@ -270,9 +270,45 @@ int spvo_host_classic_default_probe(const uint8_t *img_l, const uint8_t *img_r, 
 // (launch/visual_odometry_classic.launch); otherwise preprocessImageImpl runs first (classic.cpp:96-100).
 // poses: n x 7 (q xyzw, t of cam0_curr_T_cam0_prev; identity for frame 0); stats: n x 4 (keypoints left, right, stereo matches,
 // PnP inliers); seconds: wall time of frames warm .. n-1.  Returns the number of frames processed, negative on failure.
-int spvo_host_classic_sequence_ex(const char *detector_name, int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l,
-                                  const double *P_r, int knn, int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats,
-                                  double *seconds, int input_height, int input_width) {
+// digest (may be NULL): n x 8 FNV-1a sums of what a frame left in the front end -- keypoints left, descriptors left, keypoints right, descriptors
+// right, the stereo matches, the temporal matches, the previous frame's stereo matches (the third list) and the map derived from them, the two
+// inlier sets -- so that two runs can be compared for identity without shipping every deque entry.  Computed inside the timed loop: a run
+// with digests is not a frame-rate measurement.
+static void fnv(uint64_t &h, const void *p, size_t n) {
+  const unsigned char *b = static_cast<const unsigned char *>(p);
+  for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; }
+}
+static uint64_t digest_keypoints(const std::vector<cv::KeyPoint> &v) {
+  uint64_t h = 1469598103934665603ull;
+  for (const cv::KeyPoint &k : v) { fnv(h, &k.pt.x, 4); fnv(h, &k.pt.y, 4); fnv(h, &k.size, 4); fnv(h, &k.angle, 4); fnv(h, &k.response, 4); fnv(h, &k.octave, 4); }
+  const size_t n = v.size();
+  fnv(h, &n, sizeof n);
+  return h;
+}
+static uint64_t digest_rows(const cv::Mat &m) {
+  uint64_t h = 1469598103934665603ull;
+  for (int r = 0; r < m.rows; ++r) fnv(h, m.ptr<uint8_t>(r), (size_t)m.cols);
+  fnv(h, &m.rows, sizeof m.rows);
+  return h;
+}
+static uint64_t digest_matches(const std::vector<cv::DMatch> &v) {
+  uint64_t h = 1469598103934665603ull;
+  for (const cv::DMatch &m : v) { fnv(h, &m.queryIdx, 4); fnv(h, &m.trainIdx, 4); fnv(h, &m.distance, 4); }
+  const size_t n = v.size();
+  fnv(h, &n, sizeof n);
+  return h;
+}
+static uint64_t digest_ints(const std::vector<int> &a, const std::vector<int> &b) {
+  uint64_t h = 1469598103934665603ull;
+  const size_t na = a.size(), nb = b.size();
+  fnv(h, &na, sizeof na); if (na) fnv(h, a.data(), na * sizeof(int));
+  fnv(h, &nb, sizeof nb); if (nb) fnv(h, b.data(), nb * sizeof(int));
+  return h;
+}
+
+static int classic_sequence_run(const char *detector_name, int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l,
+                                const double *P_r, int knn, int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats,
+                                double *seconds, int input_height, int input_width, uint64_t *digest) {
   if (!detector_name || !detector_name_to_type.count(detector_name)) return -1000000;
   ClassicFeatureFrontEnd fe(detector_name_to_type.at(detector_name), descriptor_name_to_type.at("ORB"), matcher_name_to_type.at("BF"),
                             selector_name_to_type.at(knn ? "KNN" : "NN"), cross_check != 0, stereo_threshold, stereo_threshold, refinement_degree, false, input_height,
@@ -304,10 +340,39 @@ int spvo_host_classic_sequence_ex(const char *detector_name, int n, const uint8_
       stats[4 * k] = (int)fe.keypoints_dq.end()[-2].size(); stats[4 * k + 1] = (int)fe.keypoints_dq.end()[-1].size();
       stats[4 * k + 2] = (int)fe.cv_DMatches_list[CURR_LEFT_CURR_RIGHT].size(); stats[4 * k + 3] = inl;
     }
+    if (digest) {
+      uint64_t *d = digest + 8 * k;
+      d[0] = digest_keypoints(fe.keypoints_dq.end()[-2]); d[1] = digest_rows(fe.descriptors_dq.end()[-2]);
+      d[2] = digest_keypoints(fe.keypoints_dq.end()[-1]); d[3] = digest_rows(fe.descriptors_dq.end()[-1]);
+      d[4] = digest_matches(fe.cv_DMatches_list[CURR_LEFT_CURR_RIGHT]); d[5] = digest_matches(fe.cv_DMatches_list[CURR_LEFT_PREV_LEFT]);
+      d[6] = digest_matches(fe.cv_DMatches_list[PREV_LEFT_PREV_RIGHT]) ^ digest_ints(fe.mapsOfIndices()[PREV_LEFT_PREV_RIGHT], std::vector<int>());
+      d[7] = digest_ints(fe.inliersPnp(), fe.inliersPostmatching());
+    }
   }
   clock_gettime(CLOCK_MONOTONIC, &t1);
   if (seconds) *seconds = n > warm ? (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec) : 0.0;
   return n;
+}
+
+int spvo_host_classic_sequence_ex(const char *detector_name, int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l,
+                                  const double *P_r, int knn, int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats,
+                                  double *seconds, int input_height, int input_width) {
+  return classic_sequence_run(detector_name, n, imgs_l, imgs_r, rows, cols, P_l, P_r, knn, cross_check, stereo_threshold, refinement_degree, warm, poses, stats, seconds, input_height,
+                              input_width, nullptr);
+}
+
+// ... with the per-frame digests (n x 8 uint64, see above)
+int spvo_host_classic_sequence_trace(const char *detector_name, int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l,
+                                     const double *P_r, int knn, int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats,
+                                     double *seconds, int input_height, int input_width, uint64_t *digest) {
+  return classic_sequence_run(detector_name, n, imgs_l, imgs_r, rows, cols, P_l, P_r, knn, cross_check, stereo_threshold, refinement_degree, warm, poses, stats, seconds, input_height,
+                              input_width, digest);
+}
+
+// ClassicFeatureFrontEnd::setDeviceResident / setResidentCapacity for the front ends constructed afterwards (capacity <= 0: unchanged)
+void spvo_host_classic_set_resident(int on, int capacity) {
+  ClassicFeatureFrontEnd::setDeviceResident(on != 0);
+  if (capacity > 0) ClassicFeatureFrontEnd::setResidentCapacity(capacity);
 }
 
 // the ORB + ORB front end at the native resolution (the export's first form)

@@ -25,6 +25,18 @@ class Features(C.Structure):
     _fields_ = [("n", C.c_int), ("xy", C.POINTER(C.c_float)), ("desc", C.POINTER(C.c_float))]
 
 
+class ClassicOpts(C.Structure):
+    _fields_ = [("kind", C.c_int), ("nfeatures", C.c_int), ("max_corners", C.c_int), ("quality_level", C.c_double), ("min_distance", C.c_double), ("block_size", C.c_int),
+                ("fast_threshold", C.c_int), ("fast_nonmax", C.c_int), ("slot_capacity", C.c_int)]
+
+
+class ClassicFeatures(C.Structure):
+    _fields_ = [("n", C.c_int), ("kp", C.c_void_p), ("desc", C.c_void_p), ("cap", C.c_int)]
+
+
+CLASSIC_KINDS = {"ORB": 0, "ShiTomasi": 1, "GFTT": 1, "FAST": 2}
+
+
 class DetectMirrors(C.Structure):
     _fields_ = [("n", C.c_int * 2), ("xy", C.POINTER(C.c_float) * 2), ("desc", C.POINTER(C.c_float) * 2), ("resized", C.POINTER(C.c_uint8) * 2), ("token", C.c_int)]
 
@@ -63,7 +75,7 @@ SYMBOLS = [
     "spvo_default_config", "spvo_create", "spvo_destroy", "spvo_last_error", "spvo_load_weights", "spvo_engine_precision", "spvo_set_fp32_split",
     "spvo_preprocess", "spvo_forward", "spvo_debug_tensor", "spvo_heatmap", "spvo_nms",
     "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8",
-    "spvo_match_hamming", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
+    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
     "spvo_profile_enable", "spvo_profile_reset", "spvo_profile_only", "spvo_profile_count", "spvo_profile_get", "spvo_profile_stage_kernel",
     "spvo_set_tuning", "spvo_get_tuning", "spvo_clear_tuning",
     "spvo_comm_unique_id", "spvo_comm_available", "spvo_comm_create", "spvo_comm_create_host", "spvo_comm_rank", "spvo_comm_world", "spvo_comm_destroy",
@@ -121,6 +133,11 @@ def load() -> C.CDLL:
     lib.spvo_fast_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, vp, vp, C.c_int, ip]
     lib.spvo_orb_describe.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, vp, vp, vp, ip]
     lib.spvo_set_prematch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float]
+    lib.spvo_default_classic_opts.argtypes = [C.POINTER(ClassicOpts), C.c_int]
+    lib.spvo_default_classic_opts.restype = None
+    lib.spvo_classic_detect.argtypes = [vp, C.POINTER(ClassicOpts), vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.POINTER(ClassicFeatures), C.POINTER(ClassicFeatures)]
+    lib.spvo_classic_slot_rows.argtypes = [vp, C.c_int, ip]
+    lib.spvo_match_hamming_slots.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]
     lib.spvo_triangulate.argtypes = [vp, dp, dp, vp, vp, C.c_int, vp]
     lib.spvo_pnp_ransac.argtypes = [vp, dp, vp, vp, C.c_int, C.POINTER(RansacOpts), dp, dp, vp, ip, ip]
     lib.spvo_pnp_refine.argtypes = [vp, dp, dp, vp, C.c_int, C.POINTER(RefineOpts), dp, dp,
@@ -433,6 +450,54 @@ class Context:
         if img is not None:
             self._resident_shape = img.shape
         return dict(kept=kept[:m.value].copy(), angle=angle[:m.value].copy(), desc=desc[:m.value].copy())
+
+    def classic_detect(self, img_l, img_r, slot_l: int, slot_r: int, kind="ORB", **opts):
+        """One stereo pair through the classic front end's detector + ORB extractor into two binary feature slots (spvo_classic_detect).
+        kind "ORB", "ShiTomasi" or "FAST"; opts: fields of spvo_classic_opts that differ from the reference's parameters.
+        -> (left, right): dicts of xy [n,2], angle, response, octave, desc [n,32] -- the host's copy of what the slots hold.
+        On SPVO_ERR_CAPACITY the SpvoError carries the two counts as .counts."""
+        o = ClassicOpts()
+        self.lib.spvo_default_classic_opts(C.byref(o), CLASSIC_KINDS[kind] if isinstance(kind, str) else int(kind))
+        for k, v in opts.items():
+            if not hasattr(o, k):
+                raise TypeError(k)
+            setattr(o, k, v)
+        l, r = _u8_rows(img_l), _u8_rows(img_r)
+        if l.shape != r.shape or l.strides[0] != r.strides[0]:
+            l, r = np.ascontiguousarray(l), np.ascontiguousarray(r)
+            if l.shape != r.shape:
+                raise ValueError("the two images of a pair must have one shape")
+        cap = max(int(o.slot_capacity), 1)
+        bufs, feats = [], []
+        for _ in range(2):
+            kp = np.zeros((cap, 5), np.float32)          # x, y, angle, response, octave (int32 bits)
+            desc = np.zeros((cap, 32), np.uint8)
+            bufs.append((kp, desc))
+            feats.append(ClassicFeatures(0, kp.ctypes.data, desc.ctypes.data, cap))
+        rc = self.lib.spvo_classic_detect(self.h, C.byref(o), _ptr(l), _ptr(r), l.shape[0], l.shape[1], l.strides[0], slot_l, slot_r, C.byref(feats[0]), C.byref(feats[1]))
+        if rc:
+            e = SpvoError(rc, self.lib.spvo_last_error(self.h).decode())
+            e.counts = (feats[0].n, feats[1].n)
+            raise e
+        out = []
+        for (kp, desc), f in zip(bufs, feats):
+            k = f.n
+            out.append(dict(xy=kp[:k, :2].copy(), angle=kp[:k, 2].copy(), response=kp[:k, 3].copy(), octave=kp[:k, 4].copy().view(np.int32), desc=desc[:k].copy()))
+        return out[0], out[1]
+
+    def classic_slot_rows(self, slot: int) -> int:
+        n = C.c_int(0)
+        self._check(self.lib.spvo_classic_slot_rows(self.h, slot, C.byref(n)))
+        return n.value
+
+    def match_hamming_slots(self, slot_a: int, slot_b: int, selector="KNN", cross_check=False, ratio=0.8):
+        """cv::BFMatcher(NORM_HAMMING) between two binary feature slots, on the device (spvo_match_hamming_slots)."""
+        n = self.classic_slot_rows(slot_a)
+        self.classic_slot_rows(slot_b)
+        idx = np.full(max(n, 1), -1, np.int32)
+        dist = np.zeros(max(n, 1), np.float32)
+        self._check(self.lib.spvo_match_hamming_slots(self.h, slot_a, slot_b, 1 if selector == "KNN" else 0, int(cross_check), ratio, _ptr(idx), _ptr(dist)))
+        return idx[:n], dist[:n]
 
     def match_hamming(self, a: np.ndarray, b: np.ndarray, selector="KNN", cross_check=False, ratio=0.8):
         """cv::BFMatcher(NORM_HAMMING) on u8 descriptor rows (spvo_match_hamming)."""

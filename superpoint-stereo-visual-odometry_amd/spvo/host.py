@@ -341,15 +341,23 @@ class FrontEnd:
         return self.solve_stereo_odometry()                      # node.cpp:218
 
 
-def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_threshold=2.0, refinement_degree=4, warm=0, detector="ORB", input_size=None):
+def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_threshold=2.0, refinement_degree=4, warm=0, detector="ORB", input_size=None, resident=False,
+                     resident_capacity=0, trace=False):
     """stereoCallback replayed on ClassicFeatureFrontEnd(detector, ORB, BF, ...) (node.cpp:353-360) over host image pairs -- detector
     "ORB", "ShiTomasi" or "FAST"; input_size None: at their native resolution, (height, width): through preprocessImageImpl first
     (classic.cpp:96-100).  Returns (poses [n, 7] = q xyzw + t of cam0_curr_T_cam0_prev, stats [n, 4] = keypoints L, R, stereo
-    matches, PnP inliers, seconds spent on frames warm .. n-1)."""
+    matches, PnP inliers, seconds spent on frames warm .. n-1).
+    resident: ClassicFeatureFrontEnd::setDeviceResident for this run -- one spvo_classic_detect per pair, features and matching stay on the
+    device (resident_capacity > 0: rows per binary slot; a pair that does not fit falls back to the per-image path).
+    trace: a fourth value, digests [n, 8] uint64 of what every frame left in the front end (keypoints L, descriptors L, keypoints R,
+    descriptors R, stereo matches, temporal matches, the previous frame's stereo matches + map, the inlier sets): equal digests = identical
+    contents.  The digests are computed inside the timed loop, so `seconds` of a traced run is not a frame-rate figure."""
     lib = load()
-    lib.spvo_host_classic_sequence_ex.restype = C.c_int
-    lib.spvo_host_classic_sequence_ex.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                                  C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int]
+    lib.spvo_host_classic_sequence_trace.restype = C.c_int
+    lib.spvo_host_classic_sequence_trace.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                     C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_void_p]
+    lib.spvo_host_classic_set_resident.restype = None
+    lib.spvo_host_classic_set_resident.argtypes = [C.c_int, C.c_int]
     n = len(frames)
     ls = [np.ascontiguousarray(f[0], np.uint8) for f in frames]
     rs = [np.ascontiguousarray(f[1], np.uint8) for f in frames]
@@ -362,12 +370,19 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     stats = np.zeros((n, 4), np.int32)
     sec = C.c_double(0)
     ih, iw = (0, 0) if input_size is None else (int(input_size[0]), int(input_size[1]))
-    rc = lib.spvo_host_classic_sequence_ex(detector.encode(), n, pl, pr, rows, cols, Pl.ctypes.data, Pr.ctypes.data, 1 if selector == "KNN" else 0, int(cross_check),
-                                           stereo_threshold, refinement_degree, warm, poses.ctypes.data, stats.ctypes.data, C.byref(sec), ih, iw)
+    digest = np.zeros((n, 8), np.uint64) if trace else None     # NULL: nothing is digested (the digests are computed inside the timed loop)
+    lib.spvo_host_classic_set_resident(int(bool(resident)), int(resident_capacity) if resident_capacity > 0 else 8192)
+    try:
+        rc = lib.spvo_host_classic_sequence_trace(detector.encode(), n, pl, pr, rows, cols, Pl.ctypes.data, Pr.ctypes.data, 1 if selector == "KNN" else 0, int(cross_check),
+                                                  stereo_threshold, refinement_degree, warm, poses.ctypes.data, stats.ctypes.data, C.byref(sec), ih, iw, digest.ctypes.data if trace else None)
+    finally:
+        lib.spvo_host_classic_set_resident(0, 8192)
     if rc == -1000000:
         raise ValueError("unknown detector %r" % (detector,))
     if rc != n:
         raise RuntimeError("classic front end failed at frame %d" % (-rc - 1))
+    if trace:
+        return poses, stats, sec.value, digest
     return poses, stats, sec.value
 
 

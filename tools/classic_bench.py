@@ -1,13 +1,17 @@
 """The classic front end on the GPU.
 
-python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST]
-    ClassicFeatureFrontEnd(detector, ORB, BF, KNN) over the synthetic stream: frames/s of the synchronous stereoCallback.
+python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST] [--resident]
+    ClassicFeatureFrontEnd(detector, ORB, BF, KNN) over the synthetic stream: frames/s of the synchronous stereoCallback;
+    --resident: with ClassicFeatureFrontEnd::setDeviceResident (one spvo_classic_detect per pair, matching on the binary slots).
 python tools/classic_bench.py --detectors [--calls 200] [--warmup 20]
     per image at 1241 x 376: spvo_orb_detect (the yardstick, same run) beside spvo_gftt_detect + spvo_orb_describe and
     spvo_fast_detect + spvo_orb_describe -- median, 10th / 90th percentile of the synchronous calls, keypoints, and how the
     minimum-distance iteration went (undecided candidates after each round launch, rounds of the finish kernel).
 python tools/classic_bench.py --leg gftt|fast|orb [--calls 50]
     one leg alone, for rocprofv3 --kernel-trace --stats -- python tools/classic_bench.py --leg gftt
+python tools/classic_bench.py --leg match|match_slots [--selector NN|KNN] [--cross] [--calls 50]
+    one matcher alone on the two resident ORB sets of the 1241 x 376 sample pair: spvo_match_hamming on the host copies (match_hamming_kernel<8>)
+    or spvo_match_hamming_slots on the binary slots (match_hamming_tiled_kernel), for rocprofv3 --kernel-trace --stats as above.
 """
 import argparse
 import os
@@ -23,7 +27,10 @@ ap = argparse.ArgumentParser()
 ap.add_argument("frames", nargs="?", type=int, default=60)
 ap.add_argument("--detector", default="ORB")
 ap.add_argument("--detectors", action="store_true")
-ap.add_argument("--leg", choices=["gftt", "fast", "orb"])
+ap.add_argument("--resident", action="store_true")
+ap.add_argument("--leg", choices=["gftt", "fast", "orb", "match", "match_slots"])
+ap.add_argument("--selector", default="KNN", choices=["NN", "KNN"])
+ap.add_argument("--cross", action="store_true")
 ap.add_argument("--calls", type=int, default=200)
 ap.add_argument("--warmup", type=int, default=20)
 args = ap.parse_args()
@@ -44,7 +51,22 @@ if args.detectors or args.leg:
         g = ctx.fast(img)
         return len(ctx.orb_describe(None, g["xy"])["kept"])
 
-    legs = dict(orb=("spvo_orb_detect", leg_orb), gftt=("spvo_gftt_detect + spvo_orb_describe", leg_gftt), fast=("spvo_fast_detect + spvo_orb_describe", leg_fast))
+    if args.leg in ("match", "match_slots"):
+        img_r = np.ascontiguousarray(frames[0][1][:376, :1241])
+        fl, fr = ctx.classic_detect(img, img_r, 0, 1, "ORB")
+
+        def leg_match():
+            return int((ctx.match_hamming(fl["desc"], fr["desc"], args.selector, args.cross, 0.8)[0] >= 0).sum())
+
+        def leg_match_slots():
+            return int((ctx.match_hamming_slots(0, 1, args.selector, args.cross, 0.8)[0] >= 0).sum())
+
+    else:
+        leg_match = leg_match_slots = None
+
+    legs = dict(match=("spvo_match_hamming, %d x %d rows" % (len(fl["xy"]) if leg_match else 0, len(fr["xy"]) if leg_match else 0), leg_match),
+                match_slots=("spvo_match_hamming_slots, %d x %d rows" % (len(fl["xy"]) if leg_match else 0, len(fr["xy"]) if leg_match else 0), leg_match_slots),
+                orb=("spvo_orb_detect", leg_orb), gftt=("spvo_gftt_detect + spvo_orb_describe", leg_gftt), fast=("spvo_fast_detect + spvo_orb_describe", leg_fast))
     for key in ([args.leg] if args.leg else ["orb", "gftt", "fast"]):
         name, fn = legs[key]
         for _ in range(args.warmup):
@@ -59,11 +81,11 @@ if args.detectors or args.leg:
         if key == "gftt":
             rem, fin = ctx.gftt_rounds()
             extra = ", undecided after the round launches %s, finish rounds %d" % (rem.tolist(), fin)
-        print("%-40s %d x %d: median %.3f ms (p10 %.3f, p90 %.3f) over %d calls, %d described keypoints%s" % (name, img.shape[1], img.shape[0], np.median(ts), np.percentile(ts, 10),
+        print("%-40s %d x %d: median %.3f ms (p10 %.3f, p90 %.3f) over %d calls, %d described keypoints / matches%s" % (name, img.shape[1], img.shape[0], np.median(ts), np.percentile(ts, 10),
                                                                                                       np.percentile(ts, 90), args.calls, n, extra))
     ctx.close()
 else:
     n = args.frames
     seq = [frames[i % 8] for i in range(n)]
-    p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5, detector=args.detector)
-    print("classic front end (%s) on the GPU: %.1f stereo frames/s (%.3f ms per pair), keypoints %d, stereo matches %d, inliers %d" % (args.detector, (n - 5) / sec, 1e3 * sec / (n - 5), np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3])))
+    p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5, detector=args.detector, resident=args.resident)
+    print("classic front end (%s%s) on the GPU: %.1f stereo frames/s (%.3f ms per pair), keypoints %d, stereo matches %d, inliers %d" % (args.detector, ", device-resident" if args.resident else "", (n - 5) / sec, 1e3 * sec / (n - 5), np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3])))
