@@ -273,6 +273,31 @@ int spvo_fast_detect(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, size
 int spvo_orb_describe(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, size_t stride, const float *xy /* [n][2] */, int n,
                       int32_t *kept /* [n] */, float *angle /* [n] rad, may be NULL */, uint8_t *desc /* [n][32] */, int *n_kept);
 
+/* ------------------------------------------------------- classic front end: SIFT
+ * detectKeypoints + describeKeypoints of ClassicFeatureFrontEnd for DetectorType::SIFT / DescriptorType::SIFT (cv::SIFT::create():
+ * nfeatures 0, 3 layers per octave, contrast threshold 0.04, edge threshold 10, sigma 1.6) on one 8-bit image in host memory: 2x
+ * upsampled base image (first octave -1), Gaussian / difference-of-Gaussians pyramid, 26-neighbour extrema, up to five sub-pixel
+ * refinement steps, contrast and edge tests, one keypoint per peak of the 36-bin orientation histogram, 4 x 4 x 8 descriptor scaled
+ * by 512 and saturated to 0..255 -- 128 INTEGERS stored as float (the only classic descriptor matched with NORM_L2, base.cpp:18-20:
+ * spvo_match_l2).  OpenCV is not available to this build: the algorithm is Lowe 2004 with OpenCV 4.5.4's conventions as far as they
+ * are known, as restated by tests/sift_ref.py (its header lists every choice).  The pyramid, the extrema and the refinement reproduce
+ * that restatement bit for bit; orientation and descriptor use exp / atan2 and agree with it to rounding level.  Keypoints come in
+ * OpenCV's total order (x, y, size, angle, response, octave ascending), records equal in (x, y, size, angle) once (the ordering runs on
+ * the host, after one copy of the records).  `n` receives their number, of which min(n, cap) rows are written; strided input is accepted.
+ *   SPVO_ERR_INVALID   an image smaller than 6 x 6 (the first octave of the doubled image needs an interior inside its 5-pixel border)
+ *   SPVO_ERR_STATE     a spvo_detect*_submit is in flight */
+typedef struct {
+  float x, y, size;
+  float angle;       /* degrees, cv::KeyPoint convention                      */
+  float response;    /* |contrast| of the refined extremum                    */
+  int32_t octave;    /* OpenCV's packed (octave & 255) | layer << 8 | xi << 16 */
+} spvo_sift_keypoint;
+int spvo_sift_detect(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, size_t stride,
+                     spvo_sift_keypoint *kp, float *desc /* [cap][128] */, int cap, int *n);
+/* A level of the pyramid of this context's last spvo_sift_detect (test hook): Gaussian layer 0..5, or with `dog` difference layer 0..4,
+ * of octave 0.. (octave 0 is the doubled image).  `out` (rows x cols floats) may be NULL to ask for the shape only. */
+int spvo_sift_debug_level(spvo_ctx *ctx, int octave, int layer, int dog, float *out, int *rows, int *cols);
+
 /* ------------------------------------------------------- classic front end: one submission per stereo pair, features resident
  * detectKeypoints + describeKeypoints of ClassicFeatureFrontEnd for BOTH images of a stereo pair in one call: ORB, or Shi-Tomasi /
  * FAST followed by the ORB extractor (the three pairs the per-image entry points above cover).  Both images go up through pinned
@@ -306,6 +331,12 @@ int spvo_classic_detect(spvo_ctx *ctx, const spvo_classic_opts *opts, const uint
                         spvo_classic_features *out_l, spvo_classic_features *out_r);
 /* rows a binary feature slot holds; SPVO_ERR_STATE for one that holds nothing (never filled, or left unfilled by SPVO_ERR_CAPACITY) */
 int spvo_classic_slot_rows(spvo_ctx *ctx, int slot, int *n);
+
+/* spvo_match for rows of `dim` floats (1 .. 256; SIFT: 128): the rows are zero-padded to the 256 columns the matcher's kernels are
+ * built for while they are uploaded, which changes no distance.  dim = 256 returns exactly what spvo_match returns.  Rows of integers
+ * <= 255 (SIFT) have squared distances below 2^24: every distance is exact in float in any summation order, and so are the matches. */
+int spvo_match_l2(spvo_ctx *ctx, const float *desc_a, int na, const float *desc_b, int nb, int dim,
+                  int selector, int cross_check, float ratio, int32_t *train_idx, float *distance);
 
 /* The same for BINARY descriptors: cv::BFMatcher(NORM_HAMMING), what initMatcher (base.cpp:17-21) builds for the ORB / BRISK /
  * AKAZE descriptors of ClassicFeatureFrontEnd (classic.cpp:66-79) and matchDescriptors (base.cpp:434-500) runs on them.

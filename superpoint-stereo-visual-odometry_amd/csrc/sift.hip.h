@@ -1,0 +1,333 @@
+// sift.hip.h -- the classic front end's SIFT detector + descriptor on the GPU (ClassicFeatureFrontEnd with DetectorType::SIFT /
+// DescriptorType::SIFT, feature_detection_classic.cpp: cv::SIFT::create() = nfeatures 0, 3 layers per octave, contrast 0.04, edge 10,
+// sigma 1.6).  The reference obtains these from OpenCV; the algorithm built here is Lowe 2004 with OpenCV 4.5.4's conventions as far as
+// they are known, in exactly the form tests/sift_ref.py restates it (its header lists every choice).  Two halves:
+//   bit-exact   the Gaussian pyramid, the differences of Gaussians, the 26-neighbour extrema and the sub-pixel refinement are separately
+//               rounded IEEE float operations in the restatement's order (__fmul_rn / __fadd_rn / __fsub_rn / __fdiv_rn: never contracted)
+//   not exact   the orientation histogram and the 4x4x8 descriptor use expf / atan2f / sinf / cosf and sum in another order than the
+//               restatement; they are deterministic (no float atomics: a lane adds into its own LDS column, lanes that share a column
+//               take turns, columns are summed in a fixed order), so one image always gives the same bytes
+// Data flow per image, enqueued without a host round trip: sift_blur_kernel x (1 + 5 per octave) -> sift_extrema_kernel per octave
+// (candidates appended through one counter: their order depends on scheduling and nothing downstream depends on their order) ->
+// sift_refine_kernel (a thread per candidate, in place) -> sift_describe_kernel (a wave per candidate: orientation peaks, one output row
+// per peak through a second counter).  The host copies the records once, builds the keypoints, sorts them by OpenCV's total order and
+// drops duplicates (spvo_sift.hip): n is a few thousand.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "conv_mfma.hip.h"    // mul_rn, add_rn, sub_rn
+#include "spvo_types.hip.h"   // SiftPyr
+
+namespace spvo {
+
+constexpr int SIFT_LAYERS = 3, SIFT_GAUSS = SIFT_LAYERS + 3, SIFT_DOG = SIFT_LAYERS + 2, SIFT_BORDER = 5, SIFT_STEPS = 5;
+constexpr int SIFT_MAX_R = 13;        // the widest blur of the default parameters (layer 5: sigma 3.09, 27 taps)
+constexpr int SIFT_TW = 64, SIFT_TH = 32;   // output tile of the blur
+constexpr int SIFT_COLS = 16;         // LDS columns of a histogram bin (lanes l, l + 16, l + 32, l + 48 share one and take turns)
+
+struct SiftTaps { float t[SIFT_MAX_R + 1]; int r; };   // t[0] = centre
+
+// (SiftPyr, SIFT_MAX_OCT: spvo_types.hip.h)
+
+// reflect-101 as an index map that stays valid for any i (a level may be smaller than the blur radius)
+__device__ __forceinline__ int sift_reflect(int i, int n) {
+  if (n == 1) return 0;
+  const int p = 2 * n - 2;
+  int m = i % p;
+  if (m < 0) m += p;
+  return m >= n ? p - m : m;
+}
+
+// 2x bilinear upsampling of the u8 image at (y, x) of the doubled grid: weights 0.25 / 0.75, indices clamped; every sum is exact
+__device__ __forceinline__ float sift_upsample(const uint8_t *img, int sh, int sw, int y, int x) {
+  const int ky = y >> 1, kx = x >> 1;
+  const bool ey = !(y & 1), ex = !(x & 1);
+  const int ay = ey ? max(ky - 1, 0) : ky, by = ey ? ky : min(ky + 1, sh - 1);
+  const int ax = ex ? max(kx - 1, 0) : kx, bx = ex ? kx : min(kx + 1, sw - 1);
+  const float way = ey ? 0.25f : 0.75f, wax = ex ? 0.25f : 0.75f;
+  const uint8_t *ra = img + (size_t)ay * sw, *rb = img + (size_t)by * sw;
+  const float ta = add_rn(mul_rn(wax, (float)ra[ax]), mul_rn(1.f - wax, (float)ra[bx]));
+  const float tb = add_rn(mul_rn(wax, (float)rb[ax]), mul_rn(1.f - wax, (float)rb[bx]));
+  return add_rn(mul_rn(way, ta), mul_rn(1.f - way, tb));
+}
+
+// One separable blur, rows then columns, both from LDS.  MODE 0: src is a level of the same size.  MODE 1: src is layer 3 of the octave
+// below (sh x sw), read at every second pixel; the decimated image itself is stored as layer 0 (g0).  MODE 2: src is the u8 image
+// (sh x sw), upsampled 2x on the fly.  dog (may be NULL) receives dst - source: the difference of Gaussians this layer completes.
+template <int MODE>
+__global__ __launch_bounds__(256) void sift_blur_kernel(const void *__restrict__ src_, int sh, int sw, float *__restrict__ dst, float *__restrict__ dog,
+                                                        float *__restrict__ g0, int h, int w, SiftTaps tp) {
+  __shared__ float tile[SIFT_TH + 2 * SIFT_MAX_R][SIFT_TW + 2 * SIFT_MAX_R + 1];
+  __shared__ float rowf[SIFT_TH + 2 * SIFT_MAX_R][SIFT_TW + 1];
+  const int r = tp.r, tid = threadIdx.x;
+  const int x0 = blockIdx.x * SIFT_TW, y0 = blockIdx.y * SIFT_TH;
+  const int tw2 = SIFT_TW + 2 * r, th2 = SIFT_TH + 2 * r;
+  for (int idx = tid; idx < th2 * tw2; idx += 256) {
+    const int ty = idx / tw2, tx = idx - ty * tw2;
+    const int gy = sift_reflect(y0 + ty - r, h), gx = sift_reflect(x0 + tx - r, w);
+    float v;
+    if (MODE == 0) v = static_cast<const float *>(src_)[(size_t)gy * w + gx];
+    else if (MODE == 1) v = static_cast<const float *>(src_)[(size_t)(2 * gy) * sw + 2 * gx];
+    else v = sift_upsample(static_cast<const uint8_t *>(src_), sh, sw, gy, gx);
+    tile[ty][tx] = v;
+  }
+  __syncthreads();
+  for (int idx = tid; idx < th2 * SIFT_TW; idx += 256) {
+    const int ty = idx / SIFT_TW, tx = idx - ty * SIFT_TW;
+    const float *p = &tile[ty][tx + r];
+    float acc = mul_rn(tp.t[0], p[0]);
+    for (int j = 1; j <= r; ++j) acc = add_rn(acc, mul_rn(tp.t[j], add_rn(p[-j], p[j])));
+    rowf[ty][tx] = acc;
+  }
+  __syncthreads();
+  const int tx = tid & 63, gx = x0 + tx;
+  for (int ty = tid >> 6; ty < SIFT_TH; ty += 4) {
+    const int gy = y0 + ty;
+    if (gx >= w || gy >= h) continue;
+    float acc = mul_rn(tp.t[0], rowf[ty + r][tx]);
+    for (int j = 1; j <= r; ++j) acc = add_rn(acc, mul_rn(tp.t[j], add_rn(rowf[ty + r - j][tx], rowf[ty + r + j][tx])));
+    const size_t o = (size_t)gy * w + gx;
+    const float centre = tile[ty + r][tx + r];
+    dst[o] = acc;
+    if (dog) dog[o] = sub_rn(acc, centre);
+    if (MODE == 1) g0[o] = centre;
+  }
+}
+
+// 26-neighbour extrema of DoG layers 1..3 of one octave (blockIdx.z = layer - 1) inside the 5-pixel border; the three layers of a
+// 64 x 16 tile go through LDS.  Candidates {octave, layer, row, column} are appended through counter[0] (which keeps counting beyond cap).
+__global__ __launch_bounds__(256) void sift_extrema_kernel(const float *__restrict__ dog, int h, int w, int octave, int4 *__restrict__ cand, int cap,
+                                                           int *__restrict__ counter) {
+  constexpr int EW = 64, EH = 16;
+  __shared__ float t[3][EH + 2][EW + 2 + 1];
+  const int layer = blockIdx.z + 1, tid = threadIdx.x;
+  const int x0 = SIFT_BORDER + blockIdx.x * EW, y0 = SIFT_BORDER + blockIdx.y * EH;
+  const size_t lvl = (size_t)h * w;
+  for (int idx = tid; idx < 3 * (EH + 2) * (EW + 2); idx += 256) {
+    const int l = idx / ((EH + 2) * (EW + 2)), rem = idx - l * (EH + 2) * (EW + 2), ty = rem / (EW + 2), tx = rem - ty * (EW + 2);
+    const int gy = min(y0 + ty - 1, h - 1), gx = min(x0 + tx - 1, w - 1);   // (>= 4: never negative)
+    t[l][ty][tx] = dog[(size_t)(layer - 1 + l) * lvl + (size_t)gy * w + gx];
+  }
+  __syncthreads();
+  const int tx = tid & 63, gx = x0 + tx;
+  for (int ty = tid >> 6; ty < EH; ty += 4) {
+    const int gy = y0 + ty;
+    if (gx >= w - SIFT_BORDER || gy >= h - SIFT_BORDER) continue;
+    const float v = t[1][ty + 1][tx + 1];
+    if (!(fabsf(v) > 1.0f)) continue;   // floor(0.5 * 0.04 / 3 * 255)
+    bool ge = true, le = true;
+    for (int l = 0; l < 3; ++l)
+      for (int dy = 0; dy < 3; ++dy)
+        for (int dx = 0; dx < 3; ++dx) {
+          const float nb = t[l][ty + dy][tx + dx];
+          ge = ge && v >= nb;
+          le = le && v <= nb;
+        }
+    if ((v > 0 && ge) || (v < 0 && le)) {
+      const int pos = atomicAdd(counter, 1);
+      if (pos < cap) cand[pos] = make_int4(octave, layer, gy, gx);
+    }
+  }
+}
+
+// Sub-pixel refinement, contrast and edge tests of every candidate, a thread each, in place: pos becomes the position the iteration
+// ended at (layer 0: rejected), off = {xi, xr, xc, contrast}.  The arithmetic is tests/sift_ref.py's _derivs / _solve / _refine.
+__global__ __launch_bounds__(256) void sift_refine_kernel(SiftPyr P, int4 *__restrict__ pos, float4 *__restrict__ off, const int *__restrict__ counter, int cap) {
+  const int n = min(counter[0], cap);
+  const float img_scale = __fdiv_rn(1.f, 255.f), d1 = mul_rn(img_scale, 0.5f), d2 = img_scale, dc = mul_rn(img_scale, 0.25f);
+  const float lim = (float)(2147483647 / 3);
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    int4 p = pos[i];
+    const int o = p.x, h = P.h[o], w = P.w[o];
+    const size_t lvl = (size_t)h * w;
+    const float *D = P.pyr + P.d_off[o];
+    int layer = p.y, r = p.z, c = p.w;
+    bool keep = false;
+    float4 res = make_float4(0, 0, 0, 0);
+    for (int step = 0; step < SIFT_STEPS; ++step) {
+      const float *img = D + (size_t)layer * lvl + (size_t)r * w + c, *prv = img - lvl, *nxt = img + lvl;
+      const float v = img[0];
+      const float dx = mul_rn(sub_rn(img[1], img[-1]), d1), dy = mul_rn(sub_rn(img[w], img[-w]), d1), ds = mul_rn(sub_rn(nxt[0], prv[0]), d1);
+      const float v2 = mul_rn(v, 2.f);
+      const float dxx = mul_rn(sub_rn(add_rn(img[1], img[-1]), v2), d2);
+      const float dyy = mul_rn(sub_rn(add_rn(img[w], img[-w]), v2), d2);
+      const float dss = mul_rn(sub_rn(add_rn(nxt[0], prv[0]), v2), d2);
+      const float dxy = mul_rn(add_rn(sub_rn(sub_rn(img[w + 1], img[w - 1]), img[-w + 1]), img[-w - 1]), dc);
+      const float dxs = mul_rn(add_rn(sub_rn(sub_rn(nxt[1], nxt[-1]), prv[1]), prv[-1]), dc);
+      const float dys = mul_rn(add_rn(sub_rn(sub_rn(nxt[w], nxt[-w]), prv[w]), prv[-w]), dc);
+      const float c00 = sub_rn(mul_rn(dyy, dss), mul_rn(dys, dys));
+      const float c01 = sub_rn(mul_rn(dxy, dss), mul_rn(dys, dxs));
+      const float c02 = sub_rn(mul_rn(dxy, dys), mul_rn(dyy, dxs));
+      const float det = add_rn(sub_rn(mul_rn(dxx, c00), mul_rn(dxy, c01)), mul_rn(dxs, c02));
+      if (det == 0.f) break;
+      const float inv = __fdiv_rn(1.f, det);
+      const float m0 = sub_rn(mul_rn(dy, dss), mul_rn(dys, ds));
+      const float m1 = sub_rn(mul_rn(dy, dys), mul_rn(dyy, ds));
+      const float m2 = sub_rn(mul_rn(dxy, ds), mul_rn(dy, dxs));
+      const float X0 = mul_rn(inv, add_rn(sub_rn(mul_rn(dx, c00), mul_rn(dxy, m0)), mul_rn(dxs, m1)));
+      const float X1 = mul_rn(inv, add_rn(sub_rn(mul_rn(dxx, m0), mul_rn(dx, c01)), mul_rn(dxs, m2)));
+      const float X2 = mul_rn(inv, add_rn(sub_rn(mul_rn(dxx, sub_rn(mul_rn(dyy, ds), mul_rn(dy, dys))), mul_rn(dxy, m2)), mul_rn(dx, c02)));
+      const float xc = -X0, xr = -X1, xi = -X2;
+      if (fabsf(xi) < 0.5f && fabsf(xr) < 0.5f && fabsf(xc) < 0.5f) {
+        const float t = add_rn(add_rn(mul_rn(dx, xc), mul_rn(dy, xr)), mul_rn(ds, xi));
+        const float contr = add_rn(mul_rn(v, img_scale), mul_rn(t, 0.5f));
+        const float tr = add_rn(dxx, dyy), det2 = sub_rn(mul_rn(dxx, dyy), mul_rn(dxy, dxy));
+        keep = !(mul_rn(fabsf(contr), (float)SIFT_LAYERS) < 0.04f) && !(det2 <= 0.f || mul_rn(mul_rn(tr, tr), 10.f) >= mul_rn(121.f, det2));
+        res = make_float4(xi, xr, xc, contr);
+        break;
+      }
+      if (!(fabsf(xi) <= lim && fabsf(xr) <= lim && fabsf(xc) <= lim)) break;
+      c += __float2int_rn(xc); r += __float2int_rn(xr); layer += __float2int_rn(xi);
+      if (layer < 1 || layer > SIFT_LAYERS || c < SIFT_BORDER || c >= w - SIFT_BORDER || r < SIFT_BORDER || r >= h - SIFT_BORDER) break;
+    }
+    pos[i] = make_int4(o, keep ? layer : 0, r, c);
+    off[i] = res;
+  }
+}
+
+__device__ __forceinline__ float sift_wave_sum(float v) {   // every lane gets the same sum, in a fixed order
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+  return v;
+}
+
+// Orientation and descriptor of every surviving candidate: one wave (= one workgroup) per candidate, lanes over the patch.  A peak of the
+// smoothed 36-bin histogram is one keypoint: row `slot` (counter[1], which keeps counting beyond kp_cap) of kp = {candidate, angle bits}
+// and of desc (128 integers 0..255 as float).
+__global__ __launch_bounds__(64) void sift_describe_kernel(SiftPyr P, const int4 *__restrict__ pos, const float4 *__restrict__ off, int *__restrict__ counter, int cap,
+                                                           int2 *__restrict__ kp, float *__restrict__ desc, int kp_cap) {
+  __shared__ float hist[128 * SIFT_COLS];
+  __shared__ float sm_t[36], sm_h[36];
+  __shared__ int sm_base;
+  const int n = min(counter[0], cap), lane = threadIdx.x, col = lane & (SIFT_COLS - 1), turn = lane >> 4;
+  for (int i = blockIdx.x; i < n; i += gridDim.x) {
+    const int4 p = pos[i];
+    if (p.y == 0) continue;   // (the same in every lane)
+    const float4 f = off[i];
+    const int o = p.x, layer = p.y, r = p.z, c = p.w, h = P.h[o], w = P.w[o];
+    const float *G = P.pyr + P.g_off[o] + (size_t)layer * h * w;
+    const float scl = 1.6f * exp2f(((float)layer + f.x) / 3.f);
+    // ---- orientation histogram
+    {
+      const int radius = (int)rintf(4.5f * scl), side = 2 * radius + 1, total = side * side;
+      const float sigma = 1.5f * scl, escale = -1.f / (2.f * sigma * sigma);
+      for (int k = lane; k < 36 * SIFT_COLS; k += 64) hist[k] = 0.f;
+      __syncthreads();
+      for (int k0 = 0; k0 < total; k0 += 64) {
+        const int k = k0 + lane, di = k / side - radius, dj = k % side - radius, y = r + di, x = c + dj;
+        const bool ok = k < total && y > 0 && y < h - 1 && x > 0 && x < w - 1;
+        int bin = 0;
+        float val = 0.f;
+        if (ok) {
+          const float *q = G + (size_t)y * w + x;
+          const float dx = q[1] - q[-1], dy = q[-w] - q[w];
+          float ang = atan2f(dy, dx) * 57.29577951308232f;
+          if (ang < 0.f) ang += 360.f;
+          bin = (int)rintf(0.1f * ang);
+          if (bin >= 36) bin -= 36;
+          if (bin < 0) bin += 36;
+          val = expf((float)(di * di + dj * dj) * escale) * sqrtf(dx * dx + dy * dy);
+        }
+        for (int tn = 0; tn < 4; ++tn) {
+          if (ok && turn == tn) hist[bin * SIFT_COLS + col] += val;
+          __syncthreads();
+        }
+      }
+      if (lane < 36) {
+        float s = 0.f;
+        for (int k = 0; k < SIFT_COLS; ++k) s += hist[lane * SIFT_COLS + k];
+        sm_t[lane] = s;
+      }
+      __syncthreads();
+      if (lane < 36) {
+        const float a2 = sm_t[(lane + 34) % 36], a1 = sm_t[(lane + 35) % 36], b1 = sm_t[(lane + 1) % 36], b2 = sm_t[(lane + 2) % 36];
+        sm_h[lane] = (a2 + b2) * (1.f / 16.f) + (a1 + b1) * (4.f / 16.f) + sm_t[lane] * (6.f / 16.f);
+      }
+      __syncthreads();
+    }
+    float hmax = sm_h[0];
+    for (int k = 1; k < 36; ++k) hmax = fmaxf(hmax, sm_h[k]);
+    const float thr = hmax * 0.8f;
+    bool peak = false;
+    if (lane < 36) {
+      const float hl = sm_h[(lane + 35) % 36], hr = sm_h[(lane + 1) % 36], hj = sm_h[lane];
+      peak = hj > hl && hj > hr && hj >= thr;
+    }
+    unsigned long long mask = __ballot(peak);
+    const int n_peaks = __popcll(mask);
+    if (n_peaks == 0) continue;
+    if (lane == 0) sm_base = atomicAdd(counter + 1, n_peaks);
+    __syncthreads();
+    const int base = sm_base;
+    // ---- one descriptor per peak, ascending bin
+    for (int q = 0; q < n_peaks; ++q) {
+      const int j = __ffsll((long long)mask) - 1;
+      mask &= mask - 1;
+      const int slot = base + q;
+      if (slot >= kp_cap) break;
+      const float hl = sm_h[(j + 35) % 36], hr = sm_h[(j + 1) % 36], hj = sm_h[j];
+      float b = (float)j + 0.5f * (hl - hr) / (hl - 2.f * hj + hr);
+      b = b < 0.f ? 36.f + b : (b >= 36.f ? b - 36.f : b);
+      float angle = 360.f - 10.f * b;
+      if (fabsf(angle - 360.f) < 1.1920929e-7f) angle = 0.f;
+      float ori = 360.f - angle;
+      if (fabsf(ori - 360.f) < 1.1920929e-7f) ori = 0.f;
+      const int px = __float2int_rn(add_rn((float)c, f.z)), py = __float2int_rn(add_rn((float)r, f.y));
+      const float hist_width = 3.f * scl;
+      int radius = (int)rintf(hist_width * 1.4142135623730951f * 5.f * 0.5f);
+      radius = min(radius, (int)sqrt((double)w * w + (double)h * h));
+      const float cos_t = cosf(ori * 0.017453292519943295f) / hist_width, sin_t = sinf(ori * 0.017453292519943295f) / hist_width;
+      const int side = 2 * radius + 1, total = side * side;
+      for (int k = lane; k < 128 * SIFT_COLS; k += 64) hist[k] = 0.f;
+      __syncthreads();
+      for (int k0 = 0; k0 < total; k0 += 64) {
+        const int k = k0 + lane, di = k / side - radius, dj = k % side - radius, y = py + di, x = px + dj;
+        const float c_rot = dj * cos_t - di * sin_t, r_rot = dj * sin_t + di * cos_t;
+        float rbin = r_rot + 1.5f, cbin = c_rot + 1.5f;
+        const bool ok = k < total && rbin > -1.f && rbin < 4.f && cbin > -1.f && cbin < 4.f && y > 0 && y < h - 1 && x > 0 && x < w - 1;
+        int r0 = 0, c0 = 0, o0 = 0;
+        float v[8];
+        if (ok) {
+          const float *g = G + (size_t)y * w + x;
+          const float dx = g[1] - g[-1], dy = g[-w] - g[w];
+          float ang = atan2f(dy, dx) * 57.29577951308232f;
+          if (ang < 0.f) ang += 360.f;
+          const float mag = sqrtf(dx * dx + dy * dy) * expf((c_rot * c_rot + r_rot * r_rot) * -0.125f);
+          float obin = (ang - ori) * (8.f / 360.f);
+          const float fr = floorf(rbin), fc = floorf(cbin), fo = floorf(obin);
+          rbin -= fr; cbin -= fc; obin -= fo;
+          r0 = (int)fr; c0 = (int)fc; o0 = (int)fo;
+          if (o0 < 0) o0 += 8;
+          if (o0 >= 8) o0 -= 8;
+          const float v_r1 = mag * rbin, v_r0 = mag - v_r1;
+          const float v_rc11 = v_r1 * cbin, v_rc10 = v_r1 - v_rc11, v_rc01 = v_r0 * cbin, v_rc00 = v_r0 - v_rc01;
+          v[1] = v_rc00 * obin; v[0] = v_rc00 - v[1];
+          v[3] = v_rc01 * obin; v[2] = v_rc01 - v[3];
+          v[5] = v_rc10 * obin; v[4] = v_rc10 - v[5];
+          v[7] = v_rc11 * obin; v[6] = v_rc11 - v[7];
+        }
+        for (int tn = 0; tn < 4; ++tn) {
+          if (ok && turn == tn) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+              const int rr = r0 + (e >> 2), cc = c0 + ((e >> 1) & 1), oo = (o0 + (e & 1)) & 7;
+              if (rr >= 0 && rr < 4 && cc >= 0 && cc < 4) hist[((rr * 4 + cc) * 8 + oo) * SIFT_COLS + col] += v[e];
+            }
+          }
+          __syncthreads();
+        }
+      }
+      float d0 = 0.f, d1 = 0.f;
+      for (int k = 0; k < SIFT_COLS; ++k) { d0 += hist[lane * SIFT_COLS + k]; d1 += hist[(lane + 64) * SIFT_COLS + k]; }
+      const float thr2 = sqrtf(sift_wave_sum(d0 * d0 + d1 * d1)) * 0.2f;
+      d0 = fminf(d0, thr2); d1 = fminf(d1, thr2);
+      const float nrm = 512.f / fmaxf(sqrtf(sift_wave_sum(d0 * d0 + d1 * d1)), 1.1920929e-7f);
+      desc[(size_t)slot * 128 + lane] = fminf(fmaxf(rintf(d0 * nrm), 0.f), 255.f);
+      desc[(size_t)slot * 128 + 64 + lane] = fminf(fmaxf(rintf(d1 * nrm), 0.f), 255.f);
+      if (lane == 0) kp[slot] = make_int2(i, __float_as_int(angle));
+      __syncthreads();   // (hist is cleared for the next peak / candidate)
+    }
+    __syncthreads();   // (sm_base, sm_h are rewritten by the next candidate)
+  }
+}
+
+}  // namespace spvo

@@ -8,6 +8,7 @@
 //   spvo_net_i8.hip    INT8 engines
 //   spvo_detect.hip    preprocess, heat map / NMS / sampling, the detector submissions, spvo_forward
 //   spvo_classic.hip   the classic front end: ORB, Shi-Tomasi, FAST, the ORB extractor, preprocess without an engine
+//   spvo_sift.hip      the classic front end: SIFT detector + descriptor
 //   spvo_match.hip     descriptor matching (L2, Hamming)
 //   spvo_solve.hip     triangulation, PnP-RANSAC, gating, Levenberg-Marquardt, the fused solve
 #pragma once
@@ -340,6 +341,26 @@ struct spvo_ctx {
     hipEvent_t ev_feat = nullptr, ev_match = nullptr;   // features of the last call final / its prematches landed
     int last_slot_l = -1;                // left slot of the previous call (temporal partner)
   } bin;
+  // SIFT detector + descriptor of the classic front end (sift.hip.h): the image, its pyramid (all Gaussian and DoG levels: what
+  // spvo_sift_debug_level serves until the next call), the candidate and output lists; device buffers grow on demand, the host staging keeps its capacity
+  struct SiftBufs {
+    int rows = 0, cols = 0;               // shape of the image whose pyramid is resident (0: none)
+    SiftPyr plan{};
+    size_t img_cap = 0, pyr_cap = 0;      // bytes / floats
+    int cand_cap = 0;                     // candidates, and output rows, the lists hold
+    uint8_t *img = nullptr;
+    float *pyr = nullptr, *desc = nullptr;
+    int4 *cand_pos = nullptr;             // {octave, layer (0: rejected), row, column}
+    float4 *cand_off = nullptr;           // {xi, xr, xc, contrast}
+    int2 *kp = nullptr;                   // {candidate, angle bits}
+    int *counters = nullptr;              // [4]: candidates, output rows
+    std::vector<int4> h_pos;
+    std::vector<float4> h_off;
+    std::vector<int2> h_kp;
+    std::vector<float> h_desc;
+    std::vector<spvo_sift_keypoint> h_rec;
+    std::vector<int> h_order;
+  } sift;
   // Hamming matcher (classic front end's binary descriptors): rows padded to 16 words
   int ham_cap = 0;
   uint32_t *d_ham_a = nullptr, *d_ham_b = nullptr;

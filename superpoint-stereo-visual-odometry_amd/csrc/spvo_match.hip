@@ -194,6 +194,23 @@ int spvo_match(spvo_ctx *c, const float *desc_a, int na, const float *desc_b, in
   return run_match(c, MatchReq{c->d_ma, c->d_mb, na, nb, nullptr, nullptr, nullptr, nullptr}, selector, cross_check ? 1 : 0, ratio, train_idx, distance);
 }
 
+// spvo_match for rows of `dim` floats: zero-padded to MATCH_D columns on the way up (a 2-D copy into cleared buffers)
+int spvo_match_l2(spvo_ctx *c, const float *desc_a, int na, const float *desc_b, int nb, int dim, int selector, int cross_check, float ratio, int32_t *train_idx, float *distance) {
+  if (!c || na < 0 || nb < 0 || (na > 0 && (!desc_a || !train_idx || !distance)) || (nb > 0 && !desc_b)) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  if (dim < 1 || dim > MATCH_D) return fail(c, SPVO_ERR_INVALID, "spvo_match_l2: rows of 1 .. %d floats", MATCH_D);
+  if (selector != SPVO_SELECT_NN && selector != SPVO_SELECT_KNN) return fail(c, SPVO_ERR_INVALID, "bad selector");
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  int rc = ensure_match(c, na, nb);
+  if (rc) return rc;
+  PostScope ps(c);   // behind the queued tails: they share the matcher's scratch
+  const size_t row = (size_t)dim * sizeof(float), pitch = (size_t)MATCH_D * sizeof(float);
+  if (na && dim < MATCH_D) HIP_TRY(c, hipMemsetAsync(c->d_ma, 0, (size_t)na * pitch, c->post));
+  if (nb && dim < MATCH_D) HIP_TRY(c, hipMemsetAsync(c->d_mb, 0, (size_t)nb * pitch, c->post));
+  if (na) HIP_TRY(c, hipMemcpy2DAsync(c->d_ma, pitch, desc_a, row, row, na, hipMemcpyHostToDevice, c->post));
+  if (nb) HIP_TRY(c, hipMemcpy2DAsync(c->d_mb, pitch, desc_b, row, row, nb, hipMemcpyHostToDevice, c->post));
+  return run_match(c, MatchReq{c->d_ma, c->d_mb, na, nb, nullptr, nullptr, nullptr, nullptr}, selector, cross_check ? 1 : 0, ratio, train_idx, distance);
+}
+
 // cv::BFMatcher(NORM_HAMMING): binary descriptors of `desc_bytes` bytes per row (ORB 32, BRISK 64, AKAZE 61), see match.hip.h K12h
 int spvo_match_hamming(spvo_ctx *c, const uint8_t *desc_a, int na, const uint8_t *desc_b, int nb, int desc_bytes, int selector, int cross_check, float ratio,
                        int32_t *train_idx, float *distance) {

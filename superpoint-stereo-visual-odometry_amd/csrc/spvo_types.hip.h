@@ -55,4 +55,14 @@ struct RefineOut {   // device, doubles: q(4) t(3) iterations converged usable i
 // ---- ORB (orb.hip.h)
 struct OrbKeypoint { float x, y, angle, response; int32_t octave; };   // mirrors spvo_orb_keypoint (include/spvo.h)
 
+// ---- SIFT (sift.hip.h): where the levels of an image's pyramid lie -- Gaussian layer i of octave o at pyr + g_off[o] + i * h[o] * w[o],
+// difference-of-Gaussians layer i alike from d_off[o]
+constexpr int SIFT_MAX_OCT = 16;
+struct SiftPyr {
+  float *pyr;
+  long long g_off[SIFT_MAX_OCT], d_off[SIFT_MAX_OCT];
+  int h[SIFT_MAX_OCT], w[SIFT_MAX_OCT];
+  int n_oct;
+};
+
 }  // namespace spvo

@@ -71,7 +71,8 @@ void FeatureFrontEnd::initMatcher() {
     // cv::BFMatcher::create(norm_type, cross_check_ & (selector_type_ != KNN))   base.cpp:27-28
     matcher_cross_check_ = cross_check_ && (selector_type_ != SelectorType::KNN);
     // NORM_HAMMING for the binary descriptors of the classic front end (ORB / BRISK / AKAZE, base.cpp:17-21): spvo_match_hamming
-    // on the host matrices of descriptors_dq; NORM_L2 (SuperPoint / SIFT): spvo_match_slots on the device-resident feature slots
+    // on the host matrices of descriptors_dq; NORM_L2: spvo_match_slots on the device-resident feature slots (SuperPoint), spvo_match_l2 on
+    // the host matrices (SIFT: 128 floats per row, no float slot)
     matcher_hamming_ = descriptor_type_ != DescriptorType::SIFT && descriptor_type_ != DescriptorType::SuperPoint;
     matcher_ready_ = true;
   } else {
@@ -168,8 +169,9 @@ void FeatureFrontEnd::matchDescriptors(const MatchType match_type) {
     return;
   }
   const std::vector<cv::KeyPoint> &keypoints0 = keypoints_dq.end()[p0];
-  if (matcher_hamming_ && !ensureContext()) return;
-  if (!ctx_ || !matcher_ready_ || (!matcher_hamming_ && slots_dq_.size() != keypoints_dq.size())) {
+  const bool l2_host = !matcher_hamming_ && descriptor_type_ == DescriptorType::SIFT;   // a float descriptor that has no float slot
+  if ((matcher_hamming_ || l2_host) && !ensureContext()) return;
+  if (!ctx_ || !matcher_ready_ || (!matcher_hamming_ && !l2_host && slots_dq_.size() != keypoints_dq.size())) {
     logError("matchDescriptors: front end not initialised");
     return;
   }
@@ -203,6 +205,16 @@ void FeatureFrontEnd::matchDescriptors(const MatchType match_type) {
     const bool resident = bin_slots_dq_.size() == keypoints_dq.size() && bin_slots_dq_.end()[p0] >= 0 && bin_slots_dq_.end()[p1] >= 0;
     if (resident) rc = spvo_match_hamming_slots(ctx_, bin_slots_dq_.end()[p0], bin_slots_dq_.end()[p1], sel, matcher_cross_check_ ? 1 : 0, knn_threshold_, train.data(), dist.data());
     else rc = spvo_match_hamming(ctx_, rows_of(d0, b0), d0.rows, rows_of(d1, b1), d1.rows, nbytes, sel, matcher_cross_check_ ? 1 : 0, knn_threshold_, train.data(), dist.data());
+  } else if (l2_host) {   // float descriptors on the host: CV_32F matrices, one row per keypoint
+    const cv::Mat &d0 = descriptors_dq.end()[p0], &d1 = descriptors_dq.end()[p1];
+    const int dim = d0.rows ? d0.cols : d1.cols;
+    if ((d0.rows && d0.depth() != CV_32F) || (d1.rows && d1.depth() != CV_32F) || (d0.rows && d1.rows && d0.cols != d1.cols) || d0.rows != n0 ||
+        (d0.rows && (size_t)d0.step != (size_t)dim * sizeof(float)) || (d1.rows && (size_t)d1.step != (size_t)dim * sizeof(float))) {
+      logError("matchDescriptors: float descriptors expected (CV_32F, continuous, one row per keypoint, equal widths)");
+      return;
+    }
+    rc = spvo_match_l2(ctx_, d0.rows ? d0.ptr<float>(0) : nullptr, d0.rows, d1.rows ? d1.ptr<float>(0) : nullptr, d1.rows, std::max(dim, 1), sel, matcher_cross_check_ ? 1 : 0,
+                       knn_threshold_, train.data(), dist.data());
   } else {
     completeImageCopies();   // the GPU is still matching (spvo_match_slots waits for it): images_dq's share of the deferred copies fits here
     rc = spvo_match_slots(ctx_, slots_dq_.end()[p0], slots_dq_.end()[p1], sel, matcher_cross_check_ ? 1 : 0, knn_threshold_, train.data(), dist.data());
@@ -502,28 +514,60 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
 // configuration, launch/visual_odometry_classic.launch) goes through spvo_orb_detect -- detection and description are one pass
 // there, so detectKeypoints keeps the descriptors for the describeKeypoints call that follows on the same image.  ShiTomasi + ORB
 // (the default constructor) and FAST + ORB go through spvo_gftt_detect / spvo_fast_detect and spvo_orb_describe (classic.cpp:32-47,
-// 66-68, 110-111); the image stays on the device between the two.  BRISK, AKAZE, SIFT are OpenCV features2d calls and stay unavailable.
+// 66-68, 110-111); the image stays on the device between the two.  SIFT + SIFT goes through spvo_sift_detect, one pass like ORB: float
+// descriptors (n x 128 CV_32F), matched with NORM_L2 by spvo_match_l2.  BRISK and AKAZE are OpenCV features2d calls and stay unavailable,
+// and so does every other mix (SIFT keypoints with an ORB descriptor, ...).
 bool ClassicFeatureFrontEnd::available() { return true; }
 static bool classic_detector_runs(DetectorType d) { return d == DetectorType::ORB || d == DetectorType::ShiTomasi || d == DetectorType::FAST; }
+static bool classic_sift_pair(DetectorType d, DescriptorType e) { return d == DetectorType::SIFT && e == DescriptorType::SIFT; }
+static bool classic_pair_runs(DetectorType d, DescriptorType e) { return classic_sift_pair(d, e) || (classic_detector_runs(d) && e == DescriptorType::ORB); }
 void ClassicFeatureFrontEnd::initDetector() {
-  if (!classic_detector_runs(detector_type_))
-    logError("[initDetector] only ORB, ShiTomasi and FAST run without OpenCV (build with SPVO_USE_OPENCV for the other detectors of classic.cpp:7-56)");
+  if (!classic_detector_runs(detector_type_) && !classic_sift_pair(detector_type_, descriptor_type_))
+    logError("[initDetector] only ORB, ShiTomasi, FAST and SIFT (with SIFT descriptors) run without OpenCV (build with SPVO_USE_OPENCV for the other detectors of classic.cpp:7-56)");
 }
 void ClassicFeatureFrontEnd::initDescriptor() {
-  if (descriptor_type_ != DescriptorType::ORB) logError("[initDescriptor] only ORB runs without OpenCV (build with SPVO_USE_OPENCV for the other descriptors of classic.cpp:58-79)");
+  if (descriptor_type_ != DescriptorType::ORB && !classic_sift_pair(detector_type_, descriptor_type_))
+    logError("[initDescriptor] only ORB, and SIFT on SIFT keypoints, run without OpenCV (build with SPVO_USE_OPENCV for the other descriptors of classic.cpp:58-79)");
 }
 
 std::vector<cv::KeyPoint> ClassicFeatureFrontEnd::detectKeypoints(const cv::Mat &img) {
   std::vector<cv::KeyPoint> keypoints;
   orb_desc_ = cv::Mat();
   detected_data_ = nullptr;
-  if (!classic_detector_runs(detector_type_) || descriptor_type_ != DescriptorType::ORB) {
-    logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB, ShiTomasi and FAST with ORB descriptors run");
+  if (!classic_pair_runs(detector_type_, descriptor_type_)) {
+    logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB, ShiTomasi and FAST with ORB descriptors and SIFT with SIFT descriptors run");
     return keypoints;
   }
   if (!ensureContext()) return keypoints;
   if (img.depth() != CV_8U || img.rows <= 0) {
     logError("detectKeypoints: 8-bit single-channel image expected");
+    return keypoints;
+  }
+  if (detector_type_ == DetectorType::SIFT) {
+    // cv::SIFT::create(): detection and description are one pass (spvo_sift_detect), the descriptors wait for describeKeypoints
+    int cap = 4096, n = 0;
+    std::vector<spvo_sift_keypoint> kp;
+    cv::Mat desc;
+    for (;;) {
+      kp.resize((size_t)cap);
+      desc = cv::Mat(cap, 128, CV_32FC1);
+      if (spvo_sift_detect(ctx_, img.ptr<uint8_t>(0), img.rows, img.cols, (size_t)img.step, kp.data(), desc.ptr<float>(0), cap, &n) != SPVO_OK) {
+        logError(std::string("spvo_sift_detect: ") + spvo_last_error(ctx_));
+        return keypoints;
+      }
+      if (n <= cap) break;
+      cap = n;   // more than the buffers held: once more with room for all
+    }
+    keypoints.reserve(n);
+    for (int i = 0; i < n; ++i) {
+      cv::KeyPoint k(cv::Point2f(kp[i].x, kp[i].y), kp[i].size);
+      k.angle = kp[i].angle;
+      k.response = kp[i].response;
+      k.octave = kp[i].octave;
+      keypoints.push_back(k);
+    }
+    orb_desc_ = cv::Mat(n, 128, CV_32FC1);
+    if (n) std::memcpy(orb_desc_.ptr<float>(0), desc.ptr<float>(0), (size_t)n * 128 * sizeof(float));
     return keypoints;
   }
   if (detector_type_ != DetectorType::ORB) {
@@ -611,7 +655,7 @@ cv::Mat ClassicFeatureFrontEnd::describeKeypoints(std::vector<cv::KeyPoint> &key
     return d;
   }
   if (orb_desc_.rows != (int)keypoints.size()) {
-    logError("describeKeypoints: call detectKeypoints on the same image first (ORB detects and describes in one pass here)");
+    logError("describeKeypoints: call detectKeypoints on the same image first (ORB and SIFT detect and describe in one pass here)");
     return cv::Mat();
   }
   return orb_desc_;
@@ -622,8 +666,8 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
     logError("input images shape doesn't match!");
     return;
   }
-  if (!classic_detector_runs(detector_type_) || descriptor_type_ != DescriptorType::ORB) {
-    logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB, ShiTomasi and FAST with ORB descriptors run");
+  if (!classic_pair_runs(detector_type_, descriptor_type_)) {
+    logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB, ShiTomasi and FAST with ORB descriptors and SIFT with SIFT descriptors run");
     return;
   }
   if (!ensureContext()) return;   // no device: logged, nothing pushed (nn.cpp:53-55 convention)
@@ -633,7 +677,8 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
     preprocessImageImpl(img_l, projection_matrix_l_);
     preprocessImageImpl(img_r, projection_matrix_r_);
   }
-  if (!resident_ || !addStereoImagePairResident(img_l, img_r)) {
+  // (SIFT has no device-resident slot path yet: its pairs take the per-image path)
+  if (!resident_ || detector_type_ == DetectorType::SIFT || !addStereoImagePairResident(img_l, img_r)) {
     cv::Mat *imgs[2] = {&img_l, &img_r};
     for (cv::Mat *im : imgs) {
       images_dq.push_back(*im);

@@ -358,7 +358,7 @@ private:
   cv::Ptr<cv::FeatureDetector> detector_;
   cv::Ptr<cv::DescriptorExtractor> extractor_;
 #else
-  cv::Mat orb_desc_;   // descriptors of the image detectKeypoints saw last (spvo_orb_detect: one pass for both)
+  cv::Mat orb_desc_;   // descriptors of the image detectKeypoints saw last (spvo_orb_detect / spvo_sift_detect: one pass for both)
   // ShiTomasi / FAST: the image detectKeypoints saw last is still on the device; describeKeypoints on the same image does not upload it again
   const void *detected_data_ = nullptr;
   int detected_rows_ = 0, detected_cols_ = 0;

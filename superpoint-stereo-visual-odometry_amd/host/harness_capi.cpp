@@ -310,7 +310,9 @@ static int classic_sequence_run(const char *detector_name, int n, const uint8_t 
                                 const double *P_r, int knn, int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats,
                                 double *seconds, int input_height, int input_width, uint64_t *digest) {
   if (!detector_name || !detector_name_to_type.count(detector_name)) return -1000000;
-  ClassicFeatureFrontEnd fe(detector_name_to_type.at(detector_name), descriptor_name_to_type.at("ORB"), matcher_name_to_type.at("BF"),
+  // "SIFT" means SIFT keypoints with SIFT descriptors (NORM_L2); every other detector goes with the ORB extractor
+  const bool sift = detector_name_to_type.at(detector_name) == DetectorType::SIFT;
+  ClassicFeatureFrontEnd fe(detector_name_to_type.at(detector_name), descriptor_name_to_type.at(sift ? "SIFT" : "ORB"), matcher_name_to_type.at("BF"),
                             selector_name_to_type.at(knn ? "KNN" : "NN"), cross_check != 0, stereo_threshold, stereo_threshold, refinement_degree, false, input_height,
                             input_width);
   timespec t0{}, t1{};

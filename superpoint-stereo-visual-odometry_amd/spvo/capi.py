@@ -68,6 +68,7 @@ class SolveOutput(C.Structure):
                 ("summary", RefineSummary)]
 
 
+SIFT_KP_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("size", np.float32), ("angle", np.float32), ("response", np.float32), ("octave", np.int32)])   # spvo_sift_keypoint
 OBS_DTYPE = np.dtype([("X", np.float32, 3), ("uv", np.float32, 2), ("cam", np.int32), ("inverse", np.int32)])
 
 # every symbol include/spvo.h declares
@@ -75,7 +76,7 @@ SYMBOLS = [
     "spvo_default_config", "spvo_create", "spvo_destroy", "spvo_last_error", "spvo_load_weights", "spvo_engine_precision", "spvo_set_fp32_split",
     "spvo_preprocess", "spvo_forward", "spvo_debug_tensor", "spvo_heatmap", "spvo_nms",
     "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8",
-    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
+    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
     "spvo_profile_enable", "spvo_profile_reset", "spvo_profile_only", "spvo_profile_count", "spvo_profile_get", "spvo_profile_stage_kernel",
     "spvo_set_tuning", "spvo_get_tuning", "spvo_clear_tuning",
     "spvo_comm_unique_id", "spvo_comm_available", "spvo_comm_create", "spvo_comm_create_host", "spvo_comm_rank", "spvo_comm_world", "spvo_comm_destroy",
@@ -132,6 +133,9 @@ def load() -> C.CDLL:
     lib.spvo_gftt_last_rounds.argtypes = [vp, vp, ip]
     lib.spvo_fast_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, vp, vp, C.c_int, ip]
     lib.spvo_orb_describe.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, vp, vp, vp, ip]
+    lib.spvo_sift_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, C.c_int, ip]
+    lib.spvo_sift_debug_level.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, ip, ip]
+    lib.spvo_match_l2.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]
     lib.spvo_set_prematch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float]
     lib.spvo_default_classic_opts.argtypes = [C.POINTER(ClassicOpts), C.c_int]
     lib.spvo_default_classic_opts.restype = None
@@ -450,6 +454,42 @@ class Context:
         if img is not None:
             self._resident_shape = img.shape
         return dict(kept=kept[:m.value].copy(), angle=angle[:m.value].copy(), desc=desc[:m.value].copy())
+
+    def sift_detect(self, img: np.ndarray, cap: Optional[int] = None):
+        """SIFT keypoints + descriptors of one u8 image (spvo_sift_detect): dict of kp [m] (SIFT_KP_DTYPE records), desc [m, 128] float32 (integers
+        0..255) and n, the number found; m = min(n, cap).  cap = None: all of them (a second call when the first buffer was too small)."""
+        img = _u8_rows(img)
+        want = 4096 if cap is None else int(cap)
+        while True:
+            kp = np.zeros(max(want, 1), SIFT_KP_DTYPE)
+            desc = np.zeros((max(want, 1), 128), np.float32)
+            n = C.c_int(0)
+            self._check(self.lib.spvo_sift_detect(self.h, _ptr(img), img.shape[0], img.shape[1], img.strides[0], _ptr(kp), _ptr(desc), want, C.byref(n)))
+            if cap is not None or n.value <= want:
+                m = min(n.value, want)
+                return dict(kp=kp[:m].copy(), desc=desc[:m].copy(), n=n.value)
+            want = n.value
+
+    def sift_level(self, octave: int, layer: int, dog: bool = False) -> np.ndarray:
+        """A Gaussian (layer 0..5) or difference-of-Gaussians (dog: 0..4) level of the last sift_detect()'s pyramid (spvo_sift_debug_level)."""
+        rows, cols = C.c_int(0), C.c_int(0)
+        self._check(self.lib.spvo_sift_debug_level(self.h, octave, layer, int(bool(dog)), None, C.byref(rows), C.byref(cols)))
+        out = np.zeros((rows.value, cols.value), np.float32)
+        self._check(self.lib.spvo_sift_debug_level(self.h, octave, layer, int(bool(dog)), _ptr(out), C.byref(rows), C.byref(cols)))
+        return out
+
+    def match_l2(self, a: np.ndarray, b: np.ndarray, selector="KNN", cross_check=False, ratio=0.8, dim: Optional[int] = None):
+        """cv::BFMatcher(NORM_L2) on float rows of `dim` columns (spvo_match_l2); dim = None: the arrays' own width (128 when both are empty)."""
+        a = np.ascontiguousarray(a, np.float32)
+        b = np.ascontiguousarray(b, np.float32)
+        if dim is None:
+            dim = a.shape[1] if a.ndim == 2 and a.shape[1] else (b.shape[1] if b.ndim == 2 and b.shape[1] else 128)
+        if dim > 0:
+            a, b = a.reshape(-1, dim), b.reshape(-1, dim)
+        idx = np.full(len(a), -1, np.int32)
+        dist = np.zeros(len(a), np.float32)
+        self._check(self.lib.spvo_match_l2(self.h, _ptr(a), len(a), _ptr(b), len(b), dim, 1 if selector == "KNN" else 0, int(cross_check), ratio, _ptr(idx), _ptr(dist)))
+        return idx, dist
 
     def classic_detect(self, img_l, img_r, slot_l: int, slot_r: int, kind="ORB", **opts):
         """One stereo pair through the classic front end's detector + ORB extractor into two binary feature slots (spvo_classic_detect).

@@ -7,8 +7,10 @@ python tools/classic_bench.py --detectors [--calls 200] [--warmup 20]
     per image at 1241 x 376: spvo_orb_detect (the yardstick, same run) beside spvo_gftt_detect + spvo_orb_describe and
     spvo_fast_detect + spvo_orb_describe -- median, 10th / 90th percentile of the synchronous calls, keypoints, and how the
     minimum-distance iteration went (undecided candidates after each round launch, rounds of the finish kernel).
-python tools/classic_bench.py --leg gftt|fast|orb [--calls 50]
+python tools/classic_bench.py --leg gftt|fast|orb|sift [--calls 50]
     one leg alone, for rocprofv3 --kernel-trace --stats -- python tools/classic_bench.py --leg gftt
+    (sift: spvo_sift_detect per image at 1241 x 376; the per-kernel split -- sift_blur_kernel / sift_extrema_kernel / sift_refine_kernel /
+    sift_describe_kernel -- is the kernel trace's)
 python tools/classic_bench.py --leg match|match_slots [--selector NN|KNN] [--cross] [--calls 50]
     one matcher alone on the two resident ORB sets of the 1241 x 376 sample pair: spvo_match_hamming on the host copies (match_hamming_kernel<8>)
     or spvo_match_hamming_slots on the binary slots (match_hamming_tiled_kernel), for rocprofv3 --kernel-trace --stats as above.
@@ -28,7 +30,7 @@ ap.add_argument("frames", nargs="?", type=int, default=60)
 ap.add_argument("--detector", default="ORB")
 ap.add_argument("--detectors", action="store_true")
 ap.add_argument("--resident", action="store_true")
-ap.add_argument("--leg", choices=["gftt", "fast", "orb", "match", "match_slots"])
+ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "match", "match_slots"])
 ap.add_argument("--selector", default="KNN", choices=["NN", "KNN"])
 ap.add_argument("--cross", action="store_true")
 ap.add_argument("--calls", type=int, default=200)
@@ -51,6 +53,9 @@ if args.detectors or args.leg:
         g = ctx.fast(img)
         return len(ctx.orb_describe(None, g["xy"])["kept"])
 
+    def leg_sift():
+        return ctx.sift_detect(img)["n"]
+
     if args.leg in ("match", "match_slots"):
         img_r = np.ascontiguousarray(frames[0][1][:376, :1241])
         fl, fr = ctx.classic_detect(img, img_r, 0, 1, "ORB")
@@ -66,7 +71,7 @@ if args.detectors or args.leg:
 
     legs = dict(match=("spvo_match_hamming, %d x %d rows" % (len(fl["xy"]) if leg_match else 0, len(fr["xy"]) if leg_match else 0), leg_match),
                 match_slots=("spvo_match_hamming_slots, %d x %d rows" % (len(fl["xy"]) if leg_match else 0, len(fr["xy"]) if leg_match else 0), leg_match_slots),
-                orb=("spvo_orb_detect", leg_orb), gftt=("spvo_gftt_detect + spvo_orb_describe", leg_gftt), fast=("spvo_fast_detect + spvo_orb_describe", leg_fast))
+                orb=("spvo_orb_detect", leg_orb), sift=("spvo_sift_detect", leg_sift), gftt=("spvo_gftt_detect + spvo_orb_describe", leg_gftt), fast=("spvo_fast_detect + spvo_orb_describe", leg_fast))
     for key in ([args.leg] if args.leg else ["orb", "gftt", "fast"]):
         name, fn = legs[key]
         for _ in range(args.warmup):
