@@ -283,7 +283,7 @@ int spvo_orb_describe(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, siz
  * are known, as restated by tests/sift_ref.py (its header lists every choice).  The pyramid, the extrema and the refinement reproduce
  * that restatement bit for bit; orientation and descriptor use exp / atan2 and agree with it to rounding level.  Keypoints come in
  * OpenCV's total order (x, y, size, angle, response, octave ascending), records equal in (x, y, size, angle) once (the ordering runs on
- * the host, after one copy of the records).  `n` receives their number, of which min(n, cap) rows are written; strided input is accepted.
+ * the host, after one copy of the records; spvo_sift_detect_pair, below, orders on the device).  `n` receives their number, of which min(n, cap) rows are written; strided input is accepted.
  *   SPVO_ERR_INVALID   an image smaller than 6 x 6 (the first octave of the doubled image needs an interior inside its 5-pixel border)
  *   SPVO_ERR_STATE     a spvo_detect*_submit is in flight */
 typedef struct {
@@ -358,13 +358,44 @@ int spvo_match_slots(spvo_ctx *ctx, int slot_a, int slot_b, int selector, int cr
 int spvo_match_hamming_slots(spvo_ctx *ctx, int slot_a, int slot_b, int selector, int cross_check, float ratio,
                              int32_t *train_idx, float *distance);
 
+/* ------------------------------------------------------- SIFT: one submission per stereo pair, features resident
+ * spvo_sift_detect for BOTH images of a stereo pair in one call.  Both images go up through pinned staging; the chain -- the left image's
+ * pyramid, features and ORDERING, then the right image's, the one resident pyramid reused in stream order -- is enqueued on the solver's
+ * stream and the call waits once (before that, for whatever an earlier call left running there: its staging is reused).  The ordering
+ * and the duplicate removal run on the device (key, rank by counting, order-preserving compaction, gather), so the features stay in two
+ * SIFT FEATURE SLOTS (0 .. 9; a third ring, separate from the float and the binary slots): descriptor rows in the L2 matcher's format
+ * (256 floats, columns 128.. zero), their squared norms and the row count, for spvo_match_l2_slots.
+ *   Byte equality: what the host receives equals, byte for byte in every field and every descriptor, what spvo_sift_detect returns for
+ *   the same image.  The records are built on the host, by the function spvo_sift_detect uses, from the {candidate, offsets, angle} the
+ *   device hands over per final row.  The `size` the device computes (a double pow) is a sort key only; rows of one candidate get
+ *   identical keys on the device as on the host, so ties and duplicates are preserved.
+ * All slots are sized by the largest slot_capacity seen (1 .. 32768); growing it empties every slot.
+ *   SPVO_ERR_CAPACITY  an image yields more rows than slot_capacity: out_*->n report the counts, both slots are left unfilled, nothing
+ *                      is truncated.  (Candidate or raw-row lists that overflow are grown and the pair runs again: a second wait.)
+ *   SPVO_ERR_INVALID   bad or equal slots, sizes spvo_sift_detect refuses
+ *   SPVO_ERR_STATE     a spvo_detect*_submit is in flight */
+typedef struct { int n; spvo_sift_keypoint *kp; float *desc /* [cap][128] */; int cap; } spvo_sift_features;   /* n: out; min(n, cap) rows are written */
+int spvo_sift_detect_pair(spvo_ctx *ctx, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride,
+                          int slot_l, int slot_r, int slot_capacity, spvo_sift_features *out_l, spvo_sift_features *out_r);
+/* rows a SIFT slot holds; SPVO_ERR_STATE for one that holds nothing (never filled, or left unfilled by SPVO_ERR_CAPACITY) */
+int spvo_sift_slot_rows(spvo_ctx *ctx, int slot, int *n);
+/* spvo_match_l2(dim = 128) on the device-resident rows of two SIFT slots: nothing is uploaded, no norm is recomputed.  Results equal
+ * spvo_match_l2 on the host copies, index for index and distance for distance (distances are exact integers).  Returns the result stored
+ * by spvo_sift_detect_pair when spvo_set_prematch is on and this is exactly that match of exactly those slot contents.  Empty and
+ * unfilled slots as in spvo_match_hamming_slots. */
+int spvo_match_l2_slots(spvo_ctx *ctx, int slot_a, int slot_b, int selector, int cross_check, float ratio,
+                        int32_t *train_idx, float *distance);
+/* The ordering stage of spvo_sift_detect_pair alone, on caller-supplied records (test hook): `order` receives the indices of the records
+ * that stay, in output order -- OpenCV's total order, of records equal in (x, y, size, angle) the first -- and n_kept their number. */
+int spvo_sift_order_debug(spvo_ctx *ctx, const spvo_sift_keypoint *rec, int n, int32_t *order /* [n] */, int *n_kept);
+
 /* Optional latency hiding for the reference's fixed call order (node.cpp:175-198: detect, then
  * match CURR_LEFT->CURR_RIGHT, then CURR_LEFT->PREV_LEFT): when enabled, spvo_detect* enqueues
  * those two matches (slot_l -> slot_r, slot_l -> the previous call's slot_l) with these selector
  * parameters in the same GPU submission, and spvo_match_slots returns the stored result when it
  * is asked for exactly that match (same slots, same slot contents, same parameters).  Results
  * are identical with it on or off.  spvo_classic_detect / spvo_match_hamming_slots do the same on the
- * binary slots. */
+ * binary slots, spvo_sift_detect_pair / spvo_match_l2_slots on the SIFT slots. */
 int spvo_set_prematch(spvo_ctx *ctx, int enable, int selector, int cross_check, float ratio);
 
 /* Extension (BASELINE config 5): build the matcher's candidate shortlist with an fp8 (e4m3) distance GEMM instead of

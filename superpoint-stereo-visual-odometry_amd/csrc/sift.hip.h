@@ -11,7 +11,8 @@
 // (candidates appended through one counter: their order depends on scheduling and nothing downstream depends on their order) ->
 // sift_refine_kernel (a thread per candidate, in place) -> sift_describe_kernel (a wave per candidate: orientation peaks, one output row
 // per peak through a second counter).  The host copies the records once, builds the keypoints, sorts them by OpenCV's total order and
-// drops duplicates (spvo_sift.hip): n is a few thousand.
+// drops duplicates (spvo_sift.hip): n is a few thousand.  spvo_sift_detect_pair does that on the device instead (the ordering kernels at
+// the end of this file) and keeps the features in a slot.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -327,6 +328,143 @@ __global__ __launch_bounds__(64) void sift_describe_kernel(SiftPyr P, const int4
       __syncthreads();   // (hist is cleared for the next peak / candidate)
     }
     __syncthreads();   // (sm_base, sm_h are rewritten by the next candidate)
+  }
+}
+
+// ---------------------------------------------------------------- the final ordering on the device (spvo_sift_detect_pair)
+// sift_describe_kernel leaves raw rows {candidate, angle bits} + 128 floats in the order its waves happened to append them.  Four
+// launches turn them into OpenCV's output order without the host -- what spvo_sift_detect's std::sort + duplicate loop do:
+//   sift_key_kernel     a thread per raw row: its key (x, y, size, angle, response, octave) from the candidate, with the arithmetic of
+//                       spvo_sift.hip's sift_record (separately rounded float operations; `size` through a double pow -- a SORT KEY only:
+//                       rows of one candidate get one size, so ties and duplicates are those of the host's keys)
+//   sift_rank_kernel    rank by counting (cls_rank_kernel's idiom): a tile of keys in LDS, every row counts the rows in front of it under
+//                       the host comparator (float != and <, so -0 = 0); rows equal in all six fields go by raw index: a permutation
+//   sift_unique_kernel  cv::KeyPointsFilter::removeDuplicatedSorted: a sorted row whose (x, y, size, angle) equal its predecessor's is
+//                       dropped (equality is transitive and equal rows are adjacent: the predecessor stands for the last kept row);
+//                       order-preserving prefix by one workgroup in chunks of 1024 with a running base (cls_compact_kernel's)
+//   sift_gather_kernel  a wave per final row: descriptor (pitch 256, columns 128.. zero), squared norm (an exact integer < 2^24) and source
+//                       into the slot, the same to the host's pinned mirrors, the counts to both
+// Every length is read from device memory and clamped to the list's capacity (the counters keep counting beyond it).
+constexpr int SIFT_ORD_TILE = 1024;
+
+__global__ __launch_bounds__(256) void sift_key_kernel(const int4 *__restrict__ pos, const float4 *__restrict__ off, const int2 *__restrict__ kp, const int *__restrict__ counter,
+                                                       int kp_cap, SiftKey *__restrict__ keys) {
+  const int n = min(counter[1], kp_cap);
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const int2 row = kp[i];
+    const int4 p = pos[row.x];
+    const float4 f = off[row.x];
+    const int o = p.x, layer = p.y;
+    const float scale = __int_as_float((127 + o) << 23);   // 2^o
+    SiftKey k;
+    k.x = mul_rn(mul_rn(add_rn((float)p.w, f.z), scale), 0.5f);
+    k.y = mul_rn(mul_rn(add_rn((float)p.z, f.y), scale), 0.5f);
+    k.size = (float)(1.6 * pow(2.0, ((double)layer + (double)f.x) / 3.0) * (double)scale);
+    k.angle = __int_as_float(row.y);
+    k.response = fabsf(f.w);
+    const int packed = o + (layer << 8) + (__float2int_rn(mul_rn(add_rn(f.x, 0.5f), 255.f)) << 16);
+    k.octave = (packed & ~255) | ((packed - 1) & 255);
+    keys[i] = k;
+  }
+}
+
+// sorted[rank of raw row i] = i.  A workgroup takes 256 rows and walks all keys in LDS tiles; every lane reads the same tile entry (a broadcast)
+__global__ __launch_bounds__(256) void sift_rank_kernel(const SiftKey *__restrict__ keys, const int *__restrict__ n_ptr, int cap, int *__restrict__ sorted) {
+  __shared__ float tx[SIFT_ORD_TILE], ty[SIFT_ORD_TILE], ts[SIFT_ORD_TILE], ta[SIFT_ORD_TILE], tr[SIFT_ORD_TILE];
+  __shared__ int to[SIFT_ORD_TILE];
+  const int n = min(*n_ptr, cap);
+  const int nbi = (n + 255) / 256;
+  for (int bi = blockIdx.x; bi < nbi; bi += gridDim.x) {
+    const int i = bi * 256 + (int)threadIdx.x;
+    SiftKey k = {0.f, 0.f, 0.f, 0.f, 0.f, 0};
+    if (i < n) k = keys[i];
+    int cnt = 0;
+    for (int j0 = 0; j0 < n; j0 += SIFT_ORD_TILE) {
+      const int m = min(SIFT_ORD_TILE, n - j0);
+      __syncthreads();   // (the previous tile has been read)
+      for (int t = threadIdx.x; t < m; t += 256) {
+        const SiftKey q = keys[j0 + t];
+        tx[t] = q.x; ty[t] = q.y; ts[t] = q.size; ta[t] = q.angle; tr[t] = q.response; to[t] = q.octave;
+      }
+      __syncthreads();
+      for (int t = 0; t < m; ++t) {
+        const float qx = tx[t];
+        bool before;
+        if (qx != k.x) before = qx < k.x;
+        else if (ty[t] != k.y) before = ty[t] < k.y;
+        else if (ts[t] != k.size) before = ts[t] < k.size;
+        else if (ta[t] != k.angle) before = ta[t] < k.angle;
+        else if (tr[t] != k.response) before = tr[t] < k.response;
+        else if (to[t] != k.octave) before = to[t] < k.octave;
+        else before = j0 + t < i;
+        cnt += before ? 1 : 0;
+      }
+    }
+    if (i < n) sorted[cnt] = i;
+  }
+}
+
+// order[0 .. *n_out) = the raw rows that stay, in output order
+__global__ __launch_bounds__(1024) void sift_unique_kernel(const SiftKey *__restrict__ keys, const int *__restrict__ sorted, const int *__restrict__ n_ptr, int cap,
+                                                           int *__restrict__ order, int *__restrict__ n_out) {
+  __shared__ int s_wave[16];
+  const int n = min(*n_ptr, cap);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int base = 0;
+  for (int s0 = 0; s0 < n; s0 += 1024) {
+    const int s = s0 + (int)threadIdx.x;
+    int raw = 0;
+    bool keep = false;
+    if (s < n) {
+      raw = sorted[s];
+      keep = true;
+      if (s > 0) {
+        const SiftKey a = keys[sorted[s - 1]], b = keys[raw];
+        keep = !(a.x == b.x && a.y == b.y && a.size == b.size && a.angle == b.angle);
+      }
+    }
+    const unsigned long long m = __ballot(keep);
+    __syncthreads();   // (the previous chunk's sums have been read)
+    if (lane == 0) s_wave[wave] = __popcll(m);
+    __syncthreads();
+    int o = base, tot = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const int v = s_wave[k];
+      o += k < wave ? v : 0;
+      tot += v;
+    }
+    o += __popcll(m & ((1ull << lane) - 1ull));
+    if (keep) order[o] = raw;   // (o <= s < n)
+    base += tot;
+  }
+  if (threadIdx.x == 0) *n_out = base;
+}
+
+// h_n = {rows kept (may exceed slot_cap), candidates counted, raw rows counted}; the slot holds min(kept, slot_cap) rows
+__global__ __launch_bounds__(256) void sift_gather_kernel(const int *__restrict__ order, const int *__restrict__ n_kept, const int *__restrict__ counter, const int2 *__restrict__ kp,
+                                                          const int4 *__restrict__ pos, const float4 *__restrict__ off, const float *__restrict__ desc, int slot_cap,
+                                                          float *__restrict__ s_desc, float *__restrict__ s_sqn, SiftSrc *__restrict__ s_src, int *__restrict__ d_n,
+                                                          float *__restrict__ h_desc, SiftSrc *__restrict__ h_src, int *__restrict__ h_n) {
+  const int n_all = *n_kept, n = min(n_all, slot_cap);
+  if (blockIdx.x == 0 && threadIdx.x == 0) { *d_n = n; h_n[0] = n_all; h_n[1] = counter[0]; h_n[2] = counter[1]; }
+  const int lane = threadIdx.x & 63;
+  for (int r = blockIdx.x * 4 + (threadIdx.x >> 6); r < n; r += gridDim.x * 4) {
+    const int raw = order[r];
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (lane < 32) v = *reinterpret_cast<const float4 *>(desc + (size_t)raw * 128 + lane * 4);
+    *reinterpret_cast<float4 *>(s_desc + (size_t)r * 256 + lane * 4) = v;
+    if (lane < 32) *reinterpret_cast<float4 *>(h_desc + (size_t)r * 128 + lane * 4) = v;
+    const float sq = sift_wave_sum(v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w);   // integers: exact in any order
+    if (lane == 0) {
+      const int2 row = kp[raw];
+      SiftSrc src;
+      src.pos = pos[row.x]; src.off = off[row.x]; src.angle = __int_as_float(row.y);
+      src.pad[0] = src.pad[1] = src.pad[2] = 0;
+      s_sqn[r] = sq;
+      s_src[r] = src;
+      h_src[r] = src;
+    }
   }
 }
 

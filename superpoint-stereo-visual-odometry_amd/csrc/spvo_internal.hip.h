@@ -39,6 +39,8 @@ constexpr int RING = 8;          // buffer sets a detector submission owns (netw
 constexpr int MAX_INFLIGHT = 6;  // detector submissions that may be queued at once (< RING - 1: the sets of the pairs just completed still serve their matches and mirrors)
 constexpr int N_SLOTS = 16;      // feature slots: 8 stereo pairs (previous, current and up to six in flight)
 constexpr int N_BIN_SLOTS = 10;  // binary feature slots of the classic front end (spvo_classic_detect): a ring of stereo pairs, numbered like the float slots
+constexpr int N_SIFT_SLOTS = 10;   // SIFT feature slots (spvo_sift_detect_pair): a third ring of stereo pairs, numbered like the others
+constexpr int SIFT_SLOT_MAX = 32768;   // rows a SIFT slot may be asked to hold
 constexpr int HAM_KEY_SHIFT = 22;   // the tiled Hamming matcher orders (distance, row) as ONE 32-bit key: distance << 22 | row, so a slot holds at most 2^22 rows
 
 struct Tensor {
@@ -109,6 +111,18 @@ struct BinarySlot {
   bool filled = false;
   OrbKeypoint *d_kp = nullptr;   // [cap] x, y, angle, response, octave
   uint32_t *d_desc = nullptr;    // [cap][8] the matcher's row format: 32 bytes are 8 words, nothing to pad
+  int *d_n = nullptr;            // device copy of n (read by kernels enqueued before the host knows n)
+  unsigned long long gen = 0;    // bumped whenever the slot is rewritten
+};
+
+// a SIFT stereo image's features, resident on the device (spvo_sift_detect_pair -> spvo_match_l2_slots) in the L2 matcher's row format; the
+// buffers of all SIFT slots have ONE capacity (spvo_ctx::sift.slot_cap)
+struct SiftSlot {
+  int n = 0;
+  bool filled = false;
+  float *d_desc = nullptr;       // [cap][256] 128 integers as float, columns 128.. zero
+  float *d_sqn = nullptr;        // [cap] squared norms (exact integers)
+  SiftSrc *d_src = nullptr;      // [cap] candidate and angle every row came from
   int *d_n = nullptr;            // device copy of n (read by kernels enqueued before the host knows n)
   unsigned long long gen = 0;    // bumped whenever the slot is rewritten
 };
@@ -360,6 +374,26 @@ struct spvo_ctx {
     std::vector<float> h_desc;
     std::vector<spvo_sift_keypoint> h_rec;
     std::vector<int> h_order;
+    // the ordering stage on the device (sift.hip.h: spvo_sift_detect_pair, spvo_sift_order_debug), `ord_cap` raw rows
+    int ord_cap = 0;
+    SiftKey *keys = nullptr;
+    int *sorted = nullptr, *order = nullptr;   // raw row at every sorted position / at every final position
+    int *ord_n = nullptr;                      // [2]: final rows; spvo_sift_order_debug's n
+    // spvo_sift_detect_pair / spvo_match_l2_slots: the SIFT slots (`slot_cap` rows each), the call's pinned staging and mirrors and the two
+    // matches enqueued with the detector (spvo_set_prematch).  Features on the solver's stream, matches where the L2 matcher runs (PostScope).
+    int slot_cap = 0;
+    SiftSlot slots[N_SIFT_SLOTS];
+    uint8_t *h_img = nullptr;            // pinned [2][h_img_cap]: both images of a call, rows packed
+    size_t h_img_cap = 0;
+    SiftSrc *h_src = nullptr;            // pinned [2][slot_cap]      what sift_gather_kernel writes for the host: sources,
+    float *hm_desc = nullptr;            // pinned [2][slot_cap][128] descriptors,
+    int *h_n = nullptr;                  // pinned [2][4]             {final rows, candidates counted, raw rows counted}
+    int2 *h_match = nullptr;             // pinned [2][h_match_cap]: the two prematches (enqueue_matches spaces its jobs by spvo_ctx::match_cap)
+    int h_match_cap = 0;
+    MatchCache mcache[2];                // [stereo, temporal]: slot numbers are SIFT slots
+    hipEvent_t ev_feat = nullptr, ev_match = nullptr;   // features of the last call final / its prematches landed
+    bool match_pending = false;          // ev_match has been recorded: a later call's kernels wait for it before they rewrite a slot
+    int last_slot_l = -1;                // left slot of the previous call (temporal partner)
   } sift;
   // Hamming matcher (classic front end's binary descriptors): rows padded to 16 words
   int ham_cap = 0;
@@ -528,6 +562,9 @@ void resize_tables(int dst_w, int src_w, int dst_h, int src_h, std::vector<int> 
 int classic_preprocess(spvo_ctx *c, const CropGeom &g, size_t stride);
 void classic_release(spvo_ctx *c);   // frees spvo_ctx::bin (spvo_destroy)
 void classic_release_slots(spvo_ctx *c);   // ... the part of it that is sized by the slot capacity
+// ---- spvo_sift.hip
+void sift_release(spvo_ctx *c);      // frees spvo_ctx::sift (spvo_destroy)
+void sift_invalidate_matches(spvo_ctx *c);   // the stored prematches of the SIFT slots are stale (spvo_set_prematch, spvo_set_match_fp8)
 // ---- spvo_match.hip
 int ensure_match(spvo_ctx *c, int na, int nb);
 struct MatchReq {

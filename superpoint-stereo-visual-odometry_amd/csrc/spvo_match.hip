@@ -322,6 +322,34 @@ int spvo_match_hamming_slots(spvo_ctx *c, int slot_a, int slot_b, int selector, 
   return SPVO_OK;
 }
 
+// The L2 match of two SIFT slots (spvo_sift_detect_pair): the slots' rows, counts and squared norms go to the matcher as they lie on the
+// device.  Served from the call's prematch when it is exactly that match of exactly those slot contents, computed on the spot otherwise.
+int spvo_match_l2_slots(spvo_ctx *c, int slot_a, int slot_b, int selector, int cross_check, float ratio, int32_t *train_idx, float *distance) {
+  if (!c || slot_a < 0 || slot_a >= N_SIFT_SLOTS || slot_b < 0 || slot_b >= N_SIFT_SLOTS) return fail(c, SPVO_ERR_INVALID, "bad slot");
+  if (selector != SPVO_SELECT_NN && selector != SPVO_SELECT_KNN) return fail(c, SPVO_ERR_INVALID, "bad selector");
+  auto &sf = c->sift;
+  const SiftSlot &a = sf.slots[slot_a], &b = sf.slots[slot_b];
+  if (!a.filled || !b.filled) return fail(c, SPVO_ERR_STATE, "SIFT slot %d holds no features (spvo_sift_detect_pair fills it)", a.filled ? slot_b : slot_a);
+  if (a.n > 0 && (!train_idx || !distance)) return fail(c, SPVO_ERR_INVALID, "null output");
+  if (a.n == 0) return SPVO_OK;
+  if (b.n == 0) {
+    for (int i = 0; i < a.n; ++i) { train_idx[i] = -1; distance[i] = 0.f; }
+    return SPVO_OK;
+  }
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  const int cross = cross_check ? 1 : 0;
+  for (const auto &mc : sf.mcache)
+    if (mc.valid && mc.slot_a == slot_a && mc.slot_b == slot_b && mc.gen_a == a.gen && mc.gen_b == b.gen && mc.selector == selector && mc.cross == cross && mc.ratio == ratio) {
+      HIP_TRY(c, wait_event(sf.ev_match));
+      unpack_match(mc.h_out, a.n, train_idx, distance);
+      return SPVO_OK;
+    }
+  PostScope ps(c);   // behind the queued tails: they share the matcher's scratch
+  if (int rc = ensure_match(c, a.n, b.n)) return rc;
+  HIP_TRY(c, hipStreamWaitEvent(c->post, sf.ev_feat, 0));   // behind the feature chain (the solver's stream)
+  return run_match(c, MatchReq{a.d_desc, b.d_desc, a.n, b.n, a.d_n, b.d_n, a.d_sqn, b.d_sqn}, selector, cross, ratio, train_idx, distance);
+}
+
 int spvo_set_prematch(spvo_ctx *c, int enable, int selector, int cross_check, float ratio) {
   if (!c) return fail(c, SPVO_ERR_INVALID, "null context");
   if (selector != SPVO_SELECT_NN && selector != SPVO_SELECT_KNN) return fail(c, SPVO_ERR_INVALID, "bad selector");
@@ -332,6 +360,7 @@ int spvo_set_prematch(spvo_ctx *c, int enable, int selector, int cross_check, fl
   for (SubmitSet &s : c->sets)
     for (auto &mc : s.mcache) mc.valid = false;
   for (auto &mc : c->bin.mcache) mc.valid = false;
+  sift_invalidate_matches(c);
   return SPVO_OK;
 }
 
@@ -340,6 +369,7 @@ int spvo_set_match_fp8(spvo_ctx *c, int enable) {
   c->match_fp8 = enable != 0;
   for (SubmitSet &s : c->sets)
     for (auto &mc : s.mcache) mc.valid = false;
+  sift_invalidate_matches(c);
   return SPVO_OK;
 }
 

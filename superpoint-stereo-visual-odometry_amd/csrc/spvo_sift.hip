@@ -1,8 +1,11 @@
 // spvo_sift.hip -- the classic front end's SIFT detector + descriptor (sift.hip.h): plan of the pyramid, scratch in the context (grown on
-// shape change, nothing allocated per call in steady state), the launch chain, and the final ordering.  The final sort and the removal of
-// duplicates run on the HOST after one copy of the records (a few thousand rows): OpenCV's total order (x, y, size, angle, response,
-// octave) makes the output independent of the order in which the kernels appended candidates.  Runs on the solver's stream (stream2),
-// like the rest of the classic front end.
+// shape change, nothing allocated per call in steady state), the launch chain, and the final ordering.  OpenCV's total order (x, y, size,
+// angle, response, octave) makes the output independent of the order in which the kernels appended candidates.  spvo_sift_detect sorts
+// and removes duplicates on the HOST after one copy of the records (a few thousand rows); spvo_sift_detect_pair does both on the device
+// (sift.hip.h: key, rank, unique, gather) and leaves a stereo pair's features in two SIFT slots for spvo_match_l2_slots.  Byte equality
+// of the two: the host's records are built by ONE function (sift_record) from {candidate, offsets, angle bits}, which the device hands
+// over per final row; the device-computed size is a sort key only, and rows of one candidate get identical keys on the device as on the
+// host, so ties and duplicates are the same.  Runs on the solver's stream (stream2), like the rest of the classic front end.
 #include "spvo_internal.hip.h"
 #include "sift.hip.h"
 
@@ -117,7 +120,122 @@ int sift_enqueue_features(spvo_ctx *c, const SiftPyr &P) {
   HIP_TRY(c, hipGetLastError());
   return SPVO_OK;
 }
+
+// the keypoint record of a raw row (tests/sift_ref.py: candidate_record), the first octave being -1: coordinates and size are halved
+spvo_sift_keypoint sift_record(const int4 &p, const float4 &f, int angle_bits) {
+  const int o = p.x, layer = p.y;
+  const float scale = std::ldexp(1.f, o);
+  spvo_sift_keypoint k;
+  k.x = (((float)p.w + f.z) * scale) * 0.5f;
+  k.y = (((float)p.z + f.y) * scale) * 0.5f;
+  k.size = (float)(1.6 * std::pow(2.0, ((double)layer + (double)f.x) / 3.0) * std::ldexp(1.0, o));
+  std::memcpy(&k.angle, &angle_bits, sizeof(float));
+  k.response = std::fabs(f.w);
+  const int packed = o + (layer << 8) + ((int)std::nearbyint((f.x + 0.5f) * 255.f) << 16);
+  k.octave = (packed & ~255) | ((packed - 1) & 255);
+  return k;
+}
+
+// the ordering stage's scratch for `n` raw rows
+int sift_order_ensure(spvo_ctx *c, int n) {
+  auto &s = c->sift;
+  if (!s.ord_n) {
+    if (int rc = dev_alloc(c, &s.ord_n, 2, false)) return rc;
+  }
+  if (n <= s.ord_cap) return SPVO_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream2));
+  dev_free(s.keys, s.sorted, s.order);
+  s.ord_cap = 0;
+  int rc;
+  if ((rc = dev_alloc(c, &s.keys, n, false)) || (rc = dev_alloc(c, &s.sorted, n, false)) || (rc = dev_alloc(c, &s.order, n, false))) return rc;
+  s.ord_cap = n;
+  return SPVO_OK;
+}
+
+// keys[0 .. min(*n_ptr, cap)) -> order, ord_n[0]: rank, duplicate removal.  `sorted` is cleared first: keys that are no total order
+// (a NaN in a caller's records) may leave ranks unused, and every entry read must be a row
+int sift_enqueue_sort(spvo_ctx *c, const int *n_ptr, int cap) {
+  auto &s = c->sift;
+  hipStream_t st = c->stream2;
+  HIP_TRY(c, hipMemsetAsync(s.sorted, 0, (size_t)std::max(cap, 1) * sizeof(int), st));
+  hipLaunchKernelGGL(sift_rank_kernel, dim3(std::min(std::max((cap + 255) / 256, 1), 256)), dim3(256), 0, st, (const SiftKey *)s.keys, n_ptr, cap, s.sorted);
+  hipLaunchKernelGGL(sift_unique_kernel, dim3(1), dim3(1024), 0, st, (const SiftKey *)s.keys, (const int *)s.sorted, n_ptr, cap, s.order, s.ord_n);
+  HIP_TRY(c, hipGetLastError());
+  return SPVO_OK;
+}
+
+// the raw rows of the image just described -> `slot` and the host's mirrors of image k, behind sift_enqueue_features
+int sift_enqueue_order(spvo_ctx *c, SiftSlot &slot, int k) {
+  auto &s = c->sift;
+  hipStream_t st = c->stream2;
+  hipLaunchKernelGGL(sift_key_kernel, dim3(std::min((s.cand_cap + 255) / 256, 256)), dim3(256), 0, st, (const int4 *)s.cand_pos, (const float4 *)s.cand_off, (const int2 *)s.kp,
+                     (const int *)s.counters, s.cand_cap, s.keys);
+  if (int rc = sift_enqueue_sort(c, s.counters + 1, s.cand_cap)) return rc;
+  hipLaunchKernelGGL(sift_gather_kernel, dim3(64), dim3(256), 0, st, (const int *)s.order, (const int *)s.ord_n, (const int *)s.counters, (const int2 *)s.kp, (const int4 *)s.cand_pos,
+                     (const float4 *)s.cand_off, (const float *)s.desc, s.slot_cap, slot.d_desc, slot.d_sqn, slot.d_src, slot.d_n, s.hm_desc + (size_t)k * s.slot_cap * 128,
+                     s.h_src + (size_t)k * s.slot_cap, s.h_n + 4 * k);
+  HIP_TRY(c, hipGetLastError());
+  return SPVO_OK;
+}
+
+// everything sized by the slot capacity; the slots are empty afterwards
+void sift_release_slots(spvo_ctx *c) {
+  auto &s = c->sift;
+  for (SiftSlot &sl : s.slots) {
+    dev_free(sl.d_desc, sl.d_sqn, sl.d_src, sl.d_n);
+    sl.filled = false; sl.n = 0; ++sl.gen;
+  }
+  for (void *p : {(void *)s.h_src, (void *)s.hm_desc, (void *)s.h_n}) if (p) (void)hipHostFree(p);
+  s.h_src = nullptr; s.hm_desc = nullptr; s.h_n = nullptr;
+  for (auto &mc : s.mcache) mc.valid = false;
+  s.slot_cap = 0; s.last_slot_l = -1;
+}
+
+// the SIFT slots and the call's own buffers for `cap` rows per slot and images of `px` bytes; growing un-fills every slot
+int sift_slots_ensure(spvo_ctx *c, int cap, size_t px) {
+  auto &s = c->sift;
+  if (!s.ev_feat) {
+    HIP_TRY(c, hipEventCreateWithFlags(&s.ev_feat, hipEventDisableTiming));
+    HIP_TRY(c, hipEventCreateWithFlags(&s.ev_match, hipEventDisableTiming));
+  }
+  if (px > s.h_img_cap) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream2));
+    if (s.h_img) (void)hipHostFree(s.h_img);
+    s.h_img = nullptr; s.h_img_cap = 0;
+    HIP_TRY(c, hipHostMalloc((void **)&s.h_img, 2 * px));
+    s.h_img_cap = px;
+  }
+  if (cap <= s.slot_cap) return SPVO_OK;
+  HIP_TRY(c, hipDeviceSynchronize());   // (a match may still read the slots where the L2 matcher runs)
+  s.match_pending = false;
+  sift_release_slots(c);
+  int rc;
+  for (SiftSlot &sl : s.slots)
+    if ((rc = dev_alloc(c, &sl.d_desc, (size_t)cap * 256)) || (rc = dev_alloc(c, &sl.d_sqn, (size_t)cap + 4)) || (rc = dev_alloc(c, &sl.d_src, cap)) || (rc = dev_alloc(c, &sl.d_n, 1)))
+      return rc;
+  HIP_TRY(c, hipHostMalloc((void **)&s.h_src, (size_t)2 * cap * sizeof(SiftSrc)));
+  HIP_TRY(c, hipHostMalloc((void **)&s.hm_desc, (size_t)2 * cap * 128 * sizeof(float)));
+  HIP_TRY(c, hipHostMalloc((void **)&s.h_n, 2 * 4 * sizeof(int)));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
+  s.slot_cap = cap;
+  return SPVO_OK;
+}
 }  // namespace
+
+void spvo_int::sift_invalidate_matches(spvo_ctx *c) {
+  for (auto &mc : c->sift.mcache) mc.valid = false;
+}
+
+void spvo_int::sift_release(spvo_ctx *c) {
+  auto &s = c->sift;
+  sift_release_slots(c);
+  dev_free(s.img, s.pyr, s.desc, s.cand_pos, s.cand_off, s.kp, s.counters, s.keys, s.sorted, s.order, s.ord_n);
+  for (void *p : {(void *)s.h_img, (void *)s.h_match}) if (p) (void)hipHostFree(p);
+  s.h_img = nullptr; s.h_match = nullptr; s.h_img_cap = 0; s.h_match_cap = 0;
+  if (s.ev_feat) (void)hipEventDestroy(s.ev_feat);
+  if (s.ev_match) (void)hipEventDestroy(s.ev_match);
+  s.ev_feat = s.ev_match = nullptr;
+}
 
 extern "C" {
 
@@ -157,22 +275,10 @@ int spvo_sift_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t
   HIP_TRY(c, hipMemcpyAsync(s.h_kp.data(), s.kp, (size_t)n_kp * sizeof(int2), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipMemcpyAsync(s.h_desc.data(), s.desc, (size_t)n_kp * 128 * sizeof(float), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
-  // keypoint records (tests/sift_ref.py: candidate_record), the first octave being -1: coordinates and size are halved
   s.h_rec.resize(n_kp);
   s.h_order.resize(n_kp);
   for (int i = 0; i < n_kp; ++i) {
-    const int4 p = s.h_pos[s.h_kp[i].x];
-    const float4 f = s.h_off[s.h_kp[i].x];
-    const int o = p.x, layer = p.y;
-    const float scale = std::ldexp(1.f, o);
-    spvo_sift_keypoint &k = s.h_rec[i];
-    k.x = (((float)p.w + f.z) * scale) * 0.5f;
-    k.y = (((float)p.z + f.y) * scale) * 0.5f;
-    k.size = (float)(1.6 * std::pow(2.0, ((double)layer + (double)f.x) / 3.0) * std::ldexp(1.0, o));
-    std::memcpy(&k.angle, &s.h_kp[i].y, sizeof(float));
-    k.response = std::fabs(f.w);
-    const int packed = o + (layer << 8) + ((int)std::nearbyint((f.x + 0.5f) * 255.f) << 16);
-    k.octave = (packed & ~255) | ((packed - 1) & 255);
+    s.h_rec[i] = sift_record(s.h_pos[s.h_kp[i].x], s.h_off[s.h_kp[i].x], s.h_kp[i].y);
     s.h_order[i] = i;
   }
   const auto &rec = s.h_rec;
@@ -198,6 +304,151 @@ int spvo_sift_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t
     ++n;
   }
   *n_out = n;
+  return SPVO_OK;
+}
+
+int spvo_sift_slot_rows(spvo_ctx *c, int slot, int *n) {
+  if (!c || !n || slot < 0 || slot >= N_SIFT_SLOTS) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  const SiftSlot &s = c->sift.slots[slot];
+  if (!s.filled) return fail(c, SPVO_ERR_STATE, "SIFT slot %d holds no features (spvo_sift_detect_pair fills it)", slot);
+  *n = s.n;
+  return SPVO_OK;
+}
+
+int spvo_sift_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int slot_l, int slot_r, int slot_capacity,
+                          spvo_sift_features *out_l, spvo_sift_features *out_r) {
+  if (!c || !img_l || !img_r || !out_l || !out_r || rows <= 0 || cols <= 0 || stride < (size_t)cols) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  if (slot_l < 0 || slot_l >= N_SIFT_SLOTS || slot_r < 0 || slot_r >= N_SIFT_SLOTS || slot_l == slot_r) return fail(c, SPVO_ERR_INVALID, "bad slot");
+  spvo_sift_features *outs[2] = {out_l, out_r};
+  for (auto *o : outs)
+    if (o->cap < 0 || (o->cap > 0 && (!o->kp || !o->desc))) return fail(c, SPVO_ERR_INVALID, "bad output buffer");
+  if (slot_capacity <= 0 || slot_capacity > SIFT_SLOT_MAX) return fail(c, SPVO_ERR_INVALID, "slot_capacity must be 1 .. %d", SIFT_SLOT_MAX);
+  // what spvo_sift_detect refuses
+  if (rows < SIFT_MIN_SIDE || cols < SIFT_MIN_SIDE) return fail(c, SPVO_ERR_INVALID, "spvo_sift_detect_pair: images of at least %d x %d (the first octave needs an interior)", SIFT_MIN_SIDE, SIFT_MIN_SIDE);
+  if ((size_t)rows * cols > ((size_t)1 << 26)) return fail(c, SPVO_ERR_INVALID, "spvo_sift_detect_pair: image too large");
+  if (!c->pendq.empty()) return fail(c, SPVO_ERR_STATE, "detector submissions are in flight: complete them with spvo_detect_wait first");
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  out_l->n = out_r->n = 0;
+  auto &s = c->sift;
+  hipStream_t st = c->stream2;
+  SiftPyr P{};
+  const size_t pyr_floats = sift_plan(rows, cols, P), px = (size_t)rows * cols;
+  s.rows = s.cols = 0;   // nothing resident until a pyramid is enqueued
+  const int cand_cap = std::max(s.cand_cap, std::max(8192, (int)((size_t)4 * rows * cols / 16)));
+  if (int rc = sift_ensure(c, rows, cols, pyr_floats, cand_cap)) return rc;
+  if (int rc = sift_order_ensure(c, s.cand_cap)) return rc;
+  if (int rc = sift_slots_ensure(c, slot_capacity, px)) return rc;
+  const int cap = s.slot_cap;
+  if (c->prematch) {   // the matches are enqueued before the counts are known: scratch for full slots, results spaced by the matcher's capacity
+    if (int rc = ensure_match(c, cap, cap)) return rc;
+    if (s.h_match_cap != c->match_cap) {
+      HIP_TRY(c, hipDeviceSynchronize());
+      s.match_pending = false;
+      if (s.h_match) (void)hipHostFree(s.h_match);
+      s.h_match = nullptr; s.h_match_cap = 0;
+      for (auto &mc : s.mcache) mc.valid = false;
+      HIP_TRY(c, hipHostMalloc((void **)&s.h_match, (size_t)2 * c->match_cap * sizeof(int2)));
+      s.h_match_cap = c->match_cap;
+    }
+  }
+  P.pyr = s.pyr;
+  // both slots are being rewritten: whatever was matched against their old contents is stale
+  const int slots[2] = {slot_l, slot_r};
+  for (int sl : slots) { SiftSlot &t = s.slots[sl]; t.filled = false; t.n = 0; ++t.gen; }
+  for (auto &mc : s.mcache) mc.valid = false;
+  const int prev_l = s.last_slot_l;
+  s.last_slot_l = -1;
+  HIP_TRY(c, hipStreamSynchronize(st));   // (the staging buffer and the mirrors are the previous call's until its work is done)
+  const uint8_t *imgs[2] = {img_l, img_r};
+  for (int k = 0; k < 2; ++k)
+    for (int r = 0; r < rows; ++r) std::memcpy(s.h_img + k * px + (size_t)r * cols, imgs[k] + (size_t)r * stride, cols);
+  const bool temporal = prev_l >= 0 && prev_l != slot_l && prev_l != slot_r && s.slots[prev_l].filled;
+  int njobs = 0;
+  for (int attempt = 0;; ++attempt) {
+    // a match of an earlier call (or of the attempt before) may still read the slots where the L2 matcher runs
+    if (s.match_pending) HIP_TRY(c, hipStreamWaitEvent(st, s.ev_match, 0));
+    for (int k = 0; k < 2; ++k) {   // left chain, then the right one: the one resident pyramid is reused in stream order
+      s.rows = s.cols = 0;
+      HIP_TRY(c, hipMemcpyAsync(s.img, s.h_img + k * px, px, hipMemcpyHostToDevice, st));
+      if (int rc = sift_enqueue_pyramid(c, rows, cols, P)) return rc;
+      s.plan = P; s.rows = rows; s.cols = cols;
+      if (int rc = sift_enqueue_features(c, P)) return rc;
+      if (int rc = sift_enqueue_order(c, s.slots[slots[k]], k)) return rc;
+    }
+    HIP_TRY(c, hipEventRecord(s.ev_feat, st));
+    // spvo_set_prematch: the two standard matches as ONE set of launches behind the features, counts read on the device (a pair that turns
+    // out not to fit its slots is matched on whatever rows the slots hold; that result is dropped below)
+    njobs = 0;
+    if (c->prematch) {
+      PostScope ps(c);
+      const int partner[2] = {slot_r, temporal ? prev_l : -1};
+      MatchReq req[2];
+      const SiftSlot &a = s.slots[slot_l];
+      for (int k = 0; k < 2; ++k) {
+        if (partner[k] < 0) continue;
+        const SiftSlot &b = s.slots[partner[k]];
+        req[njobs++] = MatchReq{a.d_desc, b.d_desc, cap, cap, a.d_n, b.d_n, a.d_sqn, b.d_sqn};
+      }
+      HIP_TRY(c, hipStreamWaitEvent(c->post, s.ev_feat, 0));
+      if (int rc = enqueue_matches(c, req, njobs, c->pm_selector, c->pm_cross, c->pm_ratio, s.h_match)) return rc;
+      HIP_TRY(c, hipEventRecord(s.ev_match, c->post));
+      s.match_pending = true;
+    }
+    HIP_TRY(c, wait_event(s.ev_feat));   // the one wait of the call: the matches go on behind it
+    int most = 0;
+    for (int k = 0; k < 2; ++k) most = std::max(most, std::max(s.h_n[4 * k + 1], s.h_n[4 * k + 2]));
+    if (most <= s.cand_cap) break;
+    // more candidates (or raw rows) than the lists hold: grow them to what was counted and run the pair again (a second wait)
+    if (attempt >= 2) return fail(c, SPVO_ERR_CAPACITY, "spvo_sift_detect_pair: %d candidates / keypoints do not fit", most);
+    if (s.match_pending) HIP_TRY(c, wait_event(s.ev_match));
+    if (int rc = sift_ensure(c, rows, cols, pyr_floats, most + 1024)) return rc;
+    if (int rc = sift_order_ensure(c, s.cand_cap)) return rc;
+  }
+  for (int k = 0; k < 2; ++k) outs[k]->n = s.h_n[4 * k];
+  if (out_l->n > cap || out_r->n > cap) return fail(c, SPVO_ERR_CAPACITY, "spvo_sift_detect_pair: %d / %d rows do not fit slots of %d (slot_capacity)", out_l->n, out_r->n, cap);
+  for (int k = 0; k < 2; ++k) {
+    SiftSlot &t = s.slots[slots[k]];
+    t.n = outs[k]->n; t.filled = true;
+    const int ncopy = std::min(t.n, outs[k]->cap);
+    const SiftSrc *src = s.h_src + (size_t)k * cap;
+    for (int i = 0; i < ncopy; ++i) outs[k]->kp[i] = sift_record(src[i].pos, src[i].off, __builtin_bit_cast(int, src[i].angle));
+    if (ncopy > 0) std::memcpy(outs[k]->desc, s.hm_desc + (size_t)k * cap * 128, (size_t)ncopy * 128 * sizeof(float));
+  }
+  if (c->prematch) {
+    const SiftSlot &l = s.slots[slot_l];
+    const int partner[2] = {slot_r, temporal ? prev_l : -1};
+    int job = 0;
+    for (int k = 0; k < 2; ++k) {
+      if (partner[k] < 0) continue;
+      MatchCache &mc = s.mcache[job];   // job `job`'s result lands in cache entry `job`
+      mc.valid = true;
+      mc.h_out = s.h_match + (size_t)job * c->match_cap;
+      mc.slot_a = slot_l; mc.slot_b = partner[k]; mc.selector = c->pm_selector; mc.cross = c->pm_cross; mc.ratio = c->pm_ratio;
+      mc.gen_a = l.gen; mc.gen_b = s.slots[partner[k]].gen;
+      ++job;
+    }
+  }
+  s.last_slot_l = slot_l;
+  return SPVO_OK;
+}
+
+int spvo_sift_order_debug(spvo_ctx *c, const spvo_sift_keypoint *rec, int n, int32_t *order, int *n_kept) {
+  static_assert(sizeof(spvo_sift_keypoint) == sizeof(SiftKey), "keypoint records differ");
+  if (!c || !n_kept || n < 0 || n > (1 << 20) || (n > 0 && (!rec || !order))) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  *n_kept = 0;
+  auto &s = c->sift;
+  hipStream_t st = c->stream2;
+  if (int rc = sift_order_ensure(c, std::max(n, 1))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(st));
+  if (n) HIP_TRY(c, hipMemcpyAsync(s.keys, rec, (size_t)n * sizeof(SiftKey), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(s.ord_n + 1, &n, sizeof(int), hipMemcpyHostToDevice, st));
+  if (int rc = sift_enqueue_sort(c, s.ord_n + 1, n)) return rc;
+  int kept = 0;
+  HIP_TRY(c, hipMemcpyAsync(&kept, s.ord_n, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  if (kept > 0) HIP_TRY(c, hipMemcpy(order, s.order, (size_t)kept * sizeof(int), hipMemcpyDeviceToHost));
+  *n_kept = kept;
   return SPVO_OK;
 }
 

@@ -64,5 +64,8 @@ struct SiftPyr {
   int h[SIFT_MAX_OCT], w[SIFT_MAX_OCT];
   int n_oct;
 };
+// the ordering stage on the device (sift.hip.h): a raw row's sort key, and where a final row came from
+struct SiftKey { float x, y, size, angle, response; int32_t octave; };   // mirrors spvo_sift_keypoint (include/spvo.h)
+struct SiftSrc { int4 pos; float4 off; float angle; int pad[3]; };        // the candidate {octave, layer, row, column}, {xi, xr, xc, contrast}, the peak's angle
 
 }  // namespace spvo

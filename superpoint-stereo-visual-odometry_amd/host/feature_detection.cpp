@@ -72,7 +72,7 @@ void FeatureFrontEnd::initMatcher() {
     matcher_cross_check_ = cross_check_ && (selector_type_ != SelectorType::KNN);
     // NORM_HAMMING for the binary descriptors of the classic front end (ORB / BRISK / AKAZE, base.cpp:17-21): spvo_match_hamming
     // on the host matrices of descriptors_dq; NORM_L2: spvo_match_slots on the device-resident feature slots (SuperPoint), spvo_match_l2 on
-    // the host matrices (SIFT: 128 floats per row, no float slot)
+    // the host matrices (SIFT: 128 floats per row, no float slot), spvo_match_l2_slots on the SIFT slots of resident pairs
     matcher_hamming_ = descriptor_type_ != DescriptorType::SIFT && descriptor_type_ != DescriptorType::SuperPoint;
     matcher_ready_ = true;
   } else {
@@ -213,7 +213,10 @@ void FeatureFrontEnd::matchDescriptors(const MatchType match_type) {
       logError("matchDescriptors: float descriptors expected (CV_32F, continuous, one row per keypoint, equal widths)");
       return;
     }
-    rc = spvo_match_l2(ctx_, d0.rows ? d0.ptr<float>(0) : nullptr, d0.rows, d1.rows ? d1.ptr<float>(0) : nullptr, d1.rows, std::max(dim, 1), sel, matcher_cross_check_ ? 1 : 0,
+    // both sides resident in SIFT slots (ClassicFeatureFrontEnd::setDeviceResident): no upload, no norms, and usually no launch either
+    const bool resident = bin_slots_dq_.size() == keypoints_dq.size() && bin_slots_dq_.end()[p0] >= 0 && bin_slots_dq_.end()[p1] >= 0;
+    if (resident) rc = spvo_match_l2_slots(ctx_, bin_slots_dq_.end()[p0], bin_slots_dq_.end()[p1], sel, matcher_cross_check_ ? 1 : 0, knn_threshold_, train.data(), dist.data());
+    else rc = spvo_match_l2(ctx_, d0.rows ? d0.ptr<float>(0) : nullptr, d0.rows, d1.rows ? d1.ptr<float>(0) : nullptr, d1.rows, std::max(dim, 1), sel, matcher_cross_check_ ? 1 : 0,
                        knn_threshold_, train.data(), dist.data());
   } else {
     completeImageCopies();   // the GPU is still matching (spvo_match_slots waits for it): images_dq's share of the deferred copies fits here
@@ -677,8 +680,7 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
     preprocessImageImpl(img_l, projection_matrix_l_);
     preprocessImageImpl(img_r, projection_matrix_r_);
   }
-  // (SIFT has no device-resident slot path yet: its pairs take the per-image path)
-  if (!resident_ || detector_type_ == DetectorType::SIFT || !addStereoImagePairResident(img_l, img_r)) {
+  if (!resident_ || !addStereoImagePairResident(img_l, img_r)) {
     cv::Mat *imgs[2] = {&img_l, &img_r};
     for (cv::Mat *im : imgs) {
       images_dq.push_back(*im);
@@ -696,11 +698,48 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
   }
 }
 
-// setDeviceResident: the pair through ONE spvo_classic_detect call into the next slot pair of the ring; the deques are filled from what it
-// hands out, which is what detectKeypoints + describeKeypoints produce image by image.  false: nothing was pushed and the caller takes
-// the per-image path (the pair does not fit its slots, or the call failed and the per-image path reports why).
+// setDeviceResident: the pair through ONE spvo_classic_detect (SIFT: spvo_sift_detect_pair) call into the next slot pair of the ring; the
+// deques are filled from what it hands out, which is what detectKeypoints + describeKeypoints produce image by image.  false: nothing was
+// pushed and the caller takes the per-image path (the pair does not fit its slots, or the call failed and the per-image path reports why).
 bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &img_l, cv::Mat &img_r) {
   if (img_l.depth() != CV_8U || img_l.rows <= 0 || img_r.depth() != CV_8U || (size_t)img_l.step != (size_t)img_r.step) return false;
+  if (detector_type_ == DetectorType::SIFT) {
+    if (resident_pairs_ == 0) spvo_set_prematch(ctx_, 1, selector_type_ == SelectorType::KNN ? SPVO_SELECT_KNN : SPVO_SELECT_NN, matcher_cross_check_ ? 1 : 0, knn_threshold_);
+    const int cap = std::max(resident_capacity_, 1);
+    spvo_sift_features f[2];
+    for (int k = 0; k < 2; ++k) {
+      if (resident_sift_kp_[k].size() != (size_t)cap) { resident_sift_kp_[k].resize((size_t)cap); resident_sift_desc_[k].resize((size_t)cap * 128); }   // first pair only
+      f[k] = spvo_sift_features{0, resident_sift_kp_[k].data(), resident_sift_desc_[k].data(), cap};
+    }
+    const int slot_l = 2 * (int)(resident_pairs_ % 4), slot_r = slot_l + 1;
+    ++resident_pairs_;
+    const int rc = spvo_sift_detect_pair(ctx_, img_l.ptr<uint8_t>(0), img_r.ptr<uint8_t>(0), img_l.rows, img_l.cols, (size_t)img_l.step, slot_l, slot_r, resident_capacity_, &f[0], &f[1]);
+    if (rc != SPVO_OK) {
+      if (rc != SPVO_ERR_CAPACITY) logError(std::string("spvo_sift_detect_pair: ") + spvo_last_error(ctx_));
+      return false;
+    }
+    cv::Mat *imgs[2] = {&img_l, &img_r};
+    for (int k = 0; k < 2; ++k) {
+      const int n = f[k].n;
+      std::vector<cv::KeyPoint> keypoints;
+      keypoints.reserve(n);
+      for (int i = 0; i < n; ++i) {   // as detectKeypoints
+        const spvo_sift_keypoint &p = resident_sift_kp_[k][i];
+        cv::KeyPoint q(cv::Point2f(p.x, p.y), p.size);
+        q.angle = p.angle;
+        q.response = p.response;
+        q.octave = p.octave;
+        keypoints.push_back(q);
+      }
+      cv::Mat d(n, 128, CV_32FC1);
+      if (n) std::memcpy(d.ptr<float>(0), resident_sift_desc_[k].data(), (size_t)n * 128 * sizeof(float));
+      images_dq.push_back(*imgs[k]);
+      keypoints_dq.push_back(std::move(keypoints));
+      descriptors_dq.push_back(d);
+      bin_slots_dq_.push_back(k ? slot_r : slot_l);
+    }
+    return true;
+  }
   spvo_classic_opts opts;
   const bool orb = detector_type_ == DetectorType::ORB, gftt = detector_type_ == DetectorType::ShiTomasi;
   spvo_default_classic_opts(&opts, orb ? SPVO_CLASSIC_ORB : gftt ? SPVO_CLASSIC_GFTT_ORB : SPVO_CLASSIC_FAST_ORB);

@@ -303,7 +303,7 @@ protected:
   // C-ABI context and the device feature slot each deque entry lives in
   spvo_ctx *ctx_ = nullptr;
   std::deque<int> slots_dq_;
-  // the classic front end with setDeviceResident: the BINARY slot each deque entry lives in, -1 for one that exists on the host only
+  // the classic front end with setDeviceResident: the BINARY slot (SIFT: the SIFT slot) each deque entry lives in, -1 for one that exists on the host only
   // (a pair that did not fit its slots); empty when the option is off
   std::deque<int> bin_slots_dq_;
   std::string last_error_;
@@ -343,7 +343,8 @@ public:
   // pair is ONE spvo_classic_detect call into a rolling ring of four binary slot pairs, its features stay on the device and matchDescriptors
   // runs spvo_match_hamming_slots on them, the two standard matches enqueued with the detector (spvo_set_prematch).  keypoints_dq,
   // descriptors_dq and every match are what they are with the option off (the default).  A pair with more rows than the slots hold
-  // (setResidentCapacity; SPVO_ERR_CAPACITY) goes through the per-image path and is matched from the host matrices.
+  // (setResidentCapacity; SPVO_ERR_CAPACITY) goes through the per-image path and is matched from the host matrices.  SIFT + SIFT does
+  // the same through spvo_sift_detect_pair, the SIFT slots and spvo_match_l2_slots.
   static void setDeviceResident(bool on);
   static void setResidentCapacity(int rows);   // rows per binary slot [8192]
 
@@ -353,6 +354,8 @@ private:
   unsigned resident_pairs_ = 0;   // pairs handed to spvo_classic_detect: pair k lives in slots 2 (k % 4), 2 (k % 4) + 1
   std::vector<spvo_orb_keypoint> resident_kp_[2];   // what spvo_classic_detect hands out, resident_capacity_ rows per image: allocated once
   std::vector<uint8_t> resident_desc_[2];
+  std::vector<spvo_sift_keypoint> resident_sift_kp_[2];   // the same for spvo_sift_detect_pair
+  std::vector<float> resident_sift_desc_[2];
   bool addStereoImagePairResident(cv::Mat &img_l, cv::Mat &img_r);
 #ifdef SPVO_USE_OPENCV
   cv::Ptr<cv::FeatureDetector> detector_;

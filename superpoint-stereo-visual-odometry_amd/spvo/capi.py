@@ -37,6 +37,10 @@ class ClassicFeatures(C.Structure):
 CLASSIC_KINDS = {"ORB": 0, "ShiTomasi": 1, "GFTT": 1, "FAST": 2}
 
 
+class SiftFeatures(C.Structure):
+    _fields_ = [("n", C.c_int), ("kp", C.c_void_p), ("desc", C.c_void_p), ("cap", C.c_int)]
+
+
 class DetectMirrors(C.Structure):
     _fields_ = [("n", C.c_int * 2), ("xy", C.POINTER(C.c_float) * 2), ("desc", C.POINTER(C.c_float) * 2), ("resized", C.POINTER(C.c_uint8) * 2), ("token", C.c_int)]
 
@@ -76,7 +80,7 @@ SYMBOLS = [
     "spvo_default_config", "spvo_create", "spvo_destroy", "spvo_last_error", "spvo_load_weights", "spvo_engine_precision", "spvo_set_fp32_split",
     "spvo_preprocess", "spvo_forward", "spvo_debug_tensor", "spvo_heatmap", "spvo_nms",
     "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8",
-    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
+    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_detect_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
     "spvo_profile_enable", "spvo_profile_reset", "spvo_profile_only", "spvo_profile_count", "spvo_profile_get", "spvo_profile_stage_kernel",
     "spvo_set_tuning", "spvo_get_tuning", "spvo_clear_tuning",
     "spvo_comm_unique_id", "spvo_comm_available", "spvo_comm_create", "spvo_comm_create_host", "spvo_comm_rank", "spvo_comm_world", "spvo_comm_destroy",
@@ -135,6 +139,10 @@ def load() -> C.CDLL:
     lib.spvo_orb_describe.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, vp, vp, vp, ip]
     lib.spvo_sift_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, C.c_int, ip]
     lib.spvo_sift_debug_level.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, ip, ip]
+    lib.spvo_sift_detect_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(SiftFeatures), C.POINTER(SiftFeatures)]
+    lib.spvo_sift_slot_rows.argtypes = [vp, C.c_int, ip]
+    lib.spvo_match_l2_slots.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]
+    lib.spvo_sift_order_debug.argtypes = [vp, vp, C.c_int, vp, ip]
     lib.spvo_match_l2.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]
     lib.spvo_set_prematch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float]
     lib.spvo_default_classic_opts.argtypes = [C.POINTER(ClassicOpts), C.c_int]
@@ -477,6 +485,55 @@ class Context:
         out = np.zeros((rows.value, cols.value), np.float32)
         self._check(self.lib.spvo_sift_debug_level(self.h, octave, layer, int(bool(dog)), _ptr(out), C.byref(rows), C.byref(cols)))
         return out
+
+    def sift_detect_pair(self, img_l, img_r, slot_l: int, slot_r: int, slot_capacity: int = 8192, cap: Optional[int] = None):
+        """One stereo pair through the SIFT detector + descriptor into two SIFT slots (spvo_sift_detect_pair) -> (left, right): dicts like
+        sift_detect's -- the host's copy of what the slots hold; cap: rows the host buffers take (None: slot_capacity, i.e. all).
+        On SPVO_ERR_CAPACITY the SpvoError carries the two counts as .counts."""
+        l, r = _u8_rows(img_l), _u8_rows(img_r)
+        if l.shape != r.shape or l.strides[0] != r.strides[0]:
+            l, r = np.ascontiguousarray(l), np.ascontiguousarray(r)
+            if l.shape != r.shape:
+                raise ValueError("the two images of a pair must have one shape")
+        want = max(int(slot_capacity), 1) if cap is None else int(cap)
+        bufs, feats = [], []
+        for _ in range(2):
+            kp = np.zeros(max(want, 1), SIFT_KP_DTYPE)
+            desc = np.zeros((max(want, 1), 128), np.float32)
+            bufs.append((kp, desc))
+            feats.append(SiftFeatures(0, kp.ctypes.data, desc.ctypes.data, want))
+        rc = self.lib.spvo_sift_detect_pair(self.h, _ptr(l), _ptr(r), l.shape[0], l.shape[1], l.strides[0], slot_l, slot_r, int(slot_capacity), C.byref(feats[0]), C.byref(feats[1]))
+        if rc:
+            e = SpvoError(rc, self.lib.spvo_last_error(self.h).decode())
+            e.counts = (feats[0].n, feats[1].n)
+            raise e
+        out = []
+        for (kp, desc), f in zip(bufs, feats):
+            m = min(f.n, want)
+            out.append(dict(kp=kp[:m].copy(), desc=desc[:m].copy(), n=f.n))
+        return out[0], out[1]
+
+    def sift_slot_rows(self, slot: int) -> int:
+        n = C.c_int(0)
+        self._check(self.lib.spvo_sift_slot_rows(self.h, slot, C.byref(n)))
+        return n.value
+
+    def match_l2_slots(self, slot_a: int, slot_b: int, selector="KNN", cross_check=False, ratio=0.8):
+        """cv::BFMatcher(NORM_L2) between two SIFT slots, on the device (spvo_match_l2_slots)."""
+        n = self.sift_slot_rows(slot_a)
+        self.sift_slot_rows(slot_b)
+        idx = np.full(max(n, 1), -1, np.int32)
+        dist = np.zeros(max(n, 1), np.float32)
+        self._check(self.lib.spvo_match_l2_slots(self.h, slot_a, slot_b, 1 if selector == "KNN" else 0, int(cross_check), ratio, _ptr(idx), _ptr(dist)))
+        return idx[:n], dist[:n]
+
+    def sift_order(self, rec: np.ndarray) -> np.ndarray:
+        """The device ordering stage of sift_detect_pair alone on SIFT_KP_DTYPE records (spvo_sift_order_debug): the indices that stay, in output order."""
+        rec = np.ascontiguousarray(rec, SIFT_KP_DTYPE)
+        order = np.zeros(max(len(rec), 1), np.int32)
+        n = C.c_int(0)
+        self._check(self.lib.spvo_sift_order_debug(self.h, _ptr(rec), len(rec), _ptr(order), C.byref(n)))
+        return order[:n.value].copy()
 
     def match_l2(self, a: np.ndarray, b: np.ndarray, selector="KNN", cross_check=False, ratio=0.8, dim: Optional[int] = None):
         """cv::BFMatcher(NORM_L2) on float rows of `dim` columns (spvo_match_l2); dim = None: the arrays' own width (128 when both are empty)."""
