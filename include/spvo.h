@@ -273,6 +273,28 @@ int spvo_fast_detect(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, size
 int spvo_orb_describe(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, size_t stride, const float *xy /* [n][2] */, int n,
                       int32_t *kept /* [n] */, float *angle /* [n] rad, may be NULL */, uint8_t *desc /* [n][32] */, int *n_kept);
 
+/* describeKeypoints for DescriptorType::BRISK (cv::BRISK::create(30, 3, 1.0f)->compute, feature_detection_classic.cpp:56-65, 110-111) on
+ * keypoints at any position and size: per keypoint the scale index from `size`, the border rule of that scale (dropped keypoints leave
+ * the list, order-preserving: `kept` receives the surviving indices into xy, ascending, `n_kept` their number), the direction from
+ * the 870 long pairs of 60 box-smoothed samples (always recomputed), and the 512 short-pair bits at that rotation.  OpenCV is not
+ * available to this build: the algorithm is OpenCV's as far as it is known, as restated by tests/brisk_ref.py (its header lists every
+ * choice), and the kernels reproduce that restatement bit for bit on the same tables.  Row i of `angle` / `desc` / `values0` belongs to
+ * keypoint kept[i]; coordinates may be fractional; `values0` (test hook) receives the 60 intensities at rotation 0, which tells a wrong
+ * descriptor's sampling from its pairs.  img = NULL: the image of this context's last spvo_gftt_detect / spvo_fast_detect /
+ * spvo_orb_describe / spvo_brisk_describe, still on the device; SPVO_ERR_STATE if none is resident or its shape is not rows x cols.
+ *   SPVO_ERR_INVALID   a size that is not finite and positive, rows * cols * 255 >= 2^31 (the integral image is int32), n < 0
+ *   SPVO_ERR_STATE     a spvo_detect*_submit is in flight
+ * One-off cost: the point table (64 scales x 1024 rotations x 60 points x 3 floats = 47 MB) is built once per process on the host
+ * and uploaded to a context on its first BRISK call (NOTES.md, "BRISK descriptor extractor": 61 ms and 8 ms measured); the
+ * Shi-Tomasi / FAST keypoints of this front end (sizes 5 and 7) read only its 737 KB scale-0 slice. */
+int spvo_brisk_describe(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, size_t stride, const float *xy /* [n][2] */,
+                        const float *size /* [n] */, int n, int32_t *kept /* [n] */, float *angle /* [n] degrees, may be NULL */,
+                        uint8_t *desc /* [n][64] */, int32_t *values0 /* [n][60], may be NULL: test hook */, int *n_kept);
+/* the tables the extractor uses (no context needed; every pointer may be NULL): the points of one scale, the pairs in descriptor bit
+ * order, the 64 scales and their border sizes */
+int spvo_brisk_tables(int scale, float *points /* [1024][60][3] x, y, sigma; may be NULL */, int32_t *short_pairs /* [512][2] i, j */,
+                      int32_t *long_pairs /* [870][4] i, j, wdx, wdy */, float *scale_list /* [64] */, int32_t *size_list /* [64] */);
+
 /* ------------------------------------------------------- classic front end: SIFT
  * detectKeypoints + describeKeypoints of ClassicFeatureFrontEnd for DetectorType::SIFT / DescriptorType::SIFT (cv::SIFT::create():
  * nfeatures 0, 3 layers per octave, contrast threshold 0.04, edge threshold 10, sigma 1.6) on one 8-bit image in host memory: 2x

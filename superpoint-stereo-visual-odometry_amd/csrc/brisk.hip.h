@@ -1,0 +1,216 @@
+// brisk.hip.h -- the BRISK descriptor extractor of the classic front end on given keypoints (cv::BRISK::create(30, 3, 1.0f)->compute,
+// feature_detection_classic.cpp:56-65, 110-111) as tests/brisk_ref.py restates it; its header lists every choice, the kernels reproduce
+// it bit for bit on the same tables.  Everything numeric here is integer or a fixed sequence of single float operations (no contraction,
+// no atomics on floats, no order-dependent sums): two calls return identical bytes.
+//   brisk_integral_rows_kernel / _cols_kernel   the (rows + 1) x (cols + 1) int32 integral image: a wave-level scan along every row, then
+//                                               a running sum down every column (exact integers: any order gives the same image)
+//   brisk_compact_kernel                        the border rule as an order-preserving compaction (cls_compact_kernel's scheme): the kept
+//                                               indices and their scale index
+//   brisk_describe_kernel                       one wave64 per kept keypoint at a time, four per workgroup: 60 box means at rotation 0, direction
+//                                               from the 870 long pairs, 60 box means at rotation theta, 512 short-pair bits
+//   brisk_finish_kernel                         count and results to pinned host memory, n_kept rows instead of a capacity-sized copy
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace spvo {
+
+constexpr int BRISK_DESCRIBE_BLOCKS = 512;   // workgroups of brisk_describe_kernel at most (two per CU): beyond 2048 keypoints a wave takes several
+constexpr int BRISK_SCALES = 64, BRISK_ROT = 1024, BRISK_POINTS = 60, BRISK_SHORT = 512, BRISK_LONG = 870, BRISK_BYTES = 64;
+
+struct BriskLongPair { unsigned char i, j; short wdx, wdy; short pad; };   // 8 bytes
+struct BriskShortPair { unsigned char i, j; };
+
+// what the per-keypoint rules need besides the tables: size_list, and the two float constants of the scale index (brisk_ref.py choice 8)
+struct BriskParams {
+  int size_list[BRISK_SCALES];
+  float basic_size_06;     // 12 * 0.6f
+  float scales_over_lb;    // 64 / lb, lb = (float)log(30) / 0.693147180559945f
+};
+
+// I[r + 1][c + 1] of row r = the prefix sums of the row itself; row 0 and column 0 are zero.  One wave per row, four rows per workgroup.
+__global__ __launch_bounds__(256) void brisk_integral_rows_kernel(const uint8_t *__restrict__ im, int rows, int cols, int *__restrict__ integ) {
+  const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int pitch = cols + 1;
+  if (r == 0)
+    for (int c = lane; c < pitch; c += 64) integ[c] = 0;
+  if (r >= rows) return;
+  int *out = integ + (size_t)(r + 1) * pitch;
+  const uint8_t *src = im + (size_t)r * cols;
+  if (lane == 0) out[0] = 0;
+  int carry = 0;
+  for (int c0 = 0; c0 < cols; c0 += 64) {   // (wave-uniform trip count: the shuffles below are executed by all 64 lanes)
+    const int c = c0 + lane;
+    int v = c < cols ? (int)src[c] : 0;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int t = __shfl_up(v, d);
+      if (lane >= d) v += t;
+    }
+    if (c < cols) out[c + 1] = carry + v;
+    carry += __shfl(v, 63);
+  }
+}
+
+// a running sum down every column of rows 1 .. rows (one thread per column: neighbouring threads read and write neighbouring ints)
+__global__ __launch_bounds__(256) void brisk_integral_cols_kernel(int rows, int cols, int *__restrict__ integ) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  const int pitch = cols + 1;
+  if (c >= pitch) return;
+  int acc = 0;
+  for (int r = 1; r <= rows; ++r) {
+    acc += integ[(size_t)r * pitch + c];
+    integ[(size_t)r * pitch + c] = acc;
+  }
+}
+
+// brisk_ref.py choice 8
+__device__ inline int brisk_scale_index(float size, const BriskParams &P) {
+  const float q = __fdiv_rn(size, P.basic_size_06);
+  const float lq = (float)log((double)q);
+  const float w = __fmul_rn(P.scales_over_lb, __fdiv_rn(lq, 0.693147180559945f));
+  const double s = (double)w + 0.5;
+  if (!(s >= 1.0)) return 0;
+  return s >= (double)BRISK_SCALES ? BRISK_SCALES - 1 : (int)s;
+}
+
+// choice 9 as an order-preserving compaction: ONE workgroup walks the list in chunks of 1024 with a running base (wave ballots + an LDS
+// prefix over the 16 waves).  kept[k] = index into xy of the k-th survivor, kscale[k] its scale index; out_cnt[0] = their number.
+__global__ __launch_bounds__(1024) void brisk_compact_kernel(const float *__restrict__ xy, const float *__restrict__ size, int n, int h, int w, BriskParams P,
+                                                             int *__restrict__ kept, int *__restrict__ kscale, int *__restrict__ out_cnt) {
+  __shared__ int s_wave[16];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int base = 0;
+  for (int i0 = 0; i0 < n; i0 += 1024) {
+    const int i = i0 + (int)threadIdx.x;
+    int s = 0;
+    bool keep = false;
+    if (i < n) {
+      const float x = xy[2 * i], y = xy[2 * i + 1];
+      s = brisk_scale_index(size[i], P);
+      const float b = (float)P.size_list[s];
+      keep = x >= b && x < (float)w - b && y >= b && y < (float)h - b;   // (a NaN coordinate is dropped)
+    }
+    const unsigned long long m = __ballot(keep);
+    __syncthreads();   // (the previous chunk's sums have been read)
+    if (lane == 0) s_wave[wave] = __popcll(m);
+    __syncthreads();
+    int off = base, tot = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const int v = s_wave[k];
+      off += k < wave ? v : 0;
+      tot += v;
+    }
+    off += __popcll(m & ((1ull << lane) - 1ull));
+    if (keep) { kept[off] = i; kscale[off] = s; }   // (off < n: at most n survive)
+    base += tot;
+  }
+  if (threadIdx.x == 0) out_cnt[0] = base;
+}
+
+// choices 10 and 11: the box mean of half-width sigma around (xf, yf).  Every index is clamped into the image: for a keypoint that passed
+// the border rule no clamp binds (brisk_ref.py asserts it), and nothing else may read out of bounds.
+__device__ inline int brisk_smoothed(const uint8_t *__restrict__ im, const int *__restrict__ integ, int rows, int cols, float xf, float yf, float sigma) {
+#pragma clang fp contract(off)
+  const float area = 4.0f * sigma * sigma;
+  const int scaling = (int)(4194304.0 / (double)area);
+  const float scf = (float)scaling;
+  int scaling2 = (int)((double)(scf * area) / 1024.0);
+  scaling2 = scaling2 > 0 ? scaling2 : 1;
+  const float x_1 = xf - sigma, x1 = xf + sigma, y_1 = yf - sigma, y1 = yf + sigma;
+  const int xl = min(max((int)((double)x_1 + 0.5), 0), cols - 1), yt = min(max((int)((double)y_1 + 0.5), 0), rows - 1);
+  const int xr = min(max((int)((double)x1 + 0.5), xl), cols - 1), yb = min(max((int)((double)y1 + 0.5), yt), rows - 1);
+  const float r_x_1 = (float)xl - x_1 + 0.5f, r_y_1 = (float)yt - y_1 + 0.5f;
+  const float r_x1 = x1 - (float)xr + 0.5f, r_y1 = y1 - (float)yb + 0.5f;
+  const int A = (int)((r_x_1 * r_y_1) * scf), B = (int)((r_x1 * r_y_1) * scf), C = (int)((r_x1 * r_y1) * scf), D = (int)((r_x_1 * r_y1) * scf);
+  const int wl = (int)(r_x_1 * scf), wt = (int)(r_y_1 * scf), wr = (int)(r_x1 * scf), wb = (int)(r_y1 * scf);
+  const int pitch = cols + 1;
+  const int *r0 = integ + (size_t)yt * pitch, *r1 = r0 + pitch, *r2 = integ + (size_t)yb * pitch, *r3 = r2 + pitch;
+  // the integral image at the four rows yt, yt + 1, yb, yb + 1 and the four columns xl, xl + 1, xr, xr + 1
+  const int a0 = r0[xl + 1], a1 = r0[xr];
+  const int b0 = r1[xl], b1 = r1[xl + 1], b2 = r1[xr], b3 = r1[xr + 1];
+  const int c0 = r2[xl], c1 = r2[xl + 1], c2 = r2[xr], c3 = r2[xr + 1];
+  const int d0 = r3[xl + 1], d1 = r3[xr];
+  int total = A * (int)im[(size_t)yt * cols + xl] + B * (int)im[(size_t)yt * cols + xr] + C * (int)im[(size_t)yb * cols + xr] + D * (int)im[(size_t)yb * cols + xl];
+  total += (b2 - a1 - b1 + a0) * wt + (d1 - c2 - d0 + c1) * wb;     // the rows yt and yb between the corners
+  total += (c1 - b1 - c0 + b0) * wl + (c3 - b3 - c2 + b2) * wr;     // the columns xl and xr between the corners
+  total += (c2 - b2 - c1 + b1) * scaling;                           // the interior
+  return (total + scaling2 / 2) / scaling2;
+}
+
+__device__ inline int brisk_wave_sum(int v) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+  return v;
+}
+
+// One wave per kept keypoint at a time (a wave strides over the list when there are more keypoints than waves, so a workgroup loads the pair
+// tables once for all of its keypoints).  The 60 intensities stay in the registers of lanes 0 .. 59 and a pair reads its two through __shfl (every
+// shuffle is executed by all 64 lanes with an index below 60); the pair tables are in LDS, loaded once per workgroup.
+//   angle [n] degrees (0 .. 360), desc [n][64], values0 [n][60] (may be NULL): row k belongs to keypoint kept[k]
+__global__ __launch_bounds__(256) void brisk_describe_kernel(const uint8_t *__restrict__ im, const int *__restrict__ integ, int rows, int cols, const float *__restrict__ xy,
+                                                             const int *__restrict__ kept, const int *__restrict__ kscale, const int *__restrict__ cnt,
+                                                             const float *__restrict__ points, const BriskLongPair *__restrict__ long_pairs,
+                                                             const BriskShortPair *__restrict__ short_pairs, float *__restrict__ angle, uint8_t *__restrict__ desc,
+                                                             int *__restrict__ values0) {
+  __shared__ BriskLongPair s_long[BRISK_LONG];
+  __shared__ BriskShortPair s_short[BRISK_SHORT];
+  for (int p = threadIdx.x; p < BRISK_LONG; p += 256) s_long[p] = long_pairs[p];
+  for (int p = threadIdx.x; p < BRISK_SHORT; p += 256) s_short[p] = short_pairs[p];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, n_kept = cnt[0];
+  for (int k = blockIdx.x * 4 + (threadIdx.x >> 6); k < n_kept; k += gridDim.x * 4) {   // (wave-uniform; no barrier inside)
+    const int src = kept[k], s = kscale[k];
+    const float kx = xy[2 * src], ky = xy[2 * src + 1];
+    const int pt = lane < BRISK_POINTS ? lane : 0;
+    const float *p0 = points + ((size_t)s * BRISK_ROT * BRISK_POINTS + pt) * 3;
+    int v = brisk_smoothed(im, integ, rows, cols, p0[0] + kx, p0[1] + ky, p0[2]);
+    if (values0 && lane < BRISK_POINTS) values0[(size_t)k * BRISK_POINTS + lane] = v;
+    int dir0 = 0, dir1 = 0;
+#pragma unroll 2
+    for (int it = 0; it < (BRISK_LONG + 63) / 64; ++it) {
+      const int p = it * 64 + lane;
+      const BriskLongPair lp = s_long[p < BRISK_LONG ? p : 0];
+      const int delta = __shfl(v, (int)lp.i) - __shfl(v, (int)lp.j);
+      if (p < BRISK_LONG) {
+        dir0 += delta * lp.wdx / 1024;   // (C division: towards zero)
+        dir1 += delta * lp.wdy / 1024;
+      }
+    }
+    dir0 = brisk_wave_sum(dir0);
+    dir1 = brisk_wave_sum(dir1);
+    // choice 13 (every lane computes the same numbers)
+    float ang = (float)(atan2((double)dir1, (double)dir0) / 3.141592653589793 * 180.0);
+    int theta = (int)(1024.0 * ((double)ang / 360.0) + 0.5);
+    if (theta < 0) theta += BRISK_ROT;
+    if (theta >= BRISK_ROT) theta -= BRISK_ROT;
+    if (ang < 0) ang += 360.f;
+    if (lane == 0) angle[k] = ang;
+    const float *p1 = p0 + (size_t)theta * BRISK_POINTS * 3;
+    v = brisk_smoothed(im, integ, rows, cols, p1[0] + kx, p1[1] + ky, p1[2]);
+    unsigned byte = 0;
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+      const BriskShortPair sp = s_short[lane * 8 + b];
+      const int t1 = __shfl(v, (int)sp.i), t2 = __shfl(v, (int)sp.j);
+      byte |= (t1 > t2 ? 1u : 0u) << b;
+    }
+    desc[(size_t)k * BRISK_BYTES + lane] = (uint8_t)byte;
+  }
+}
+
+// The last launch of a call: count and the rows that exist go to pinned host memory.  h_n[0] = n_kept.
+__global__ __launch_bounds__(256) void brisk_finish_kernel(const int *__restrict__ cnt, const int *__restrict__ kept, const float *__restrict__ angle, const uint32_t *__restrict__ desc,
+                                                           const int *__restrict__ values0, int *__restrict__ h_n, int *__restrict__ h_kept, float *__restrict__ h_angle,
+                                                           uint32_t *__restrict__ h_desc, int *__restrict__ h_values0) {
+  const int n = cnt[0];
+  const int tid = blockIdx.x * 256 + threadIdx.x, nth = gridDim.x * 256;
+  if (tid == 0) h_n[0] = n;
+  for (int i = tid; i < n; i += nth) { h_kept[i] = kept[i]; h_angle[i] = angle[i]; }
+  for (int i = tid; i < n * (BRISK_BYTES / 4); i += nth) h_desc[i] = desc[i];
+  if (h_values0)
+    for (int i = tid; i < n * BRISK_POINTS; i += nth) h_values0[i] = values0[i];
+}
+
+}  // namespace spvo

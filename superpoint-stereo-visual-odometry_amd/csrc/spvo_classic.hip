@@ -445,6 +445,8 @@ int spvo_orb_describe(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_
 
 }  // extern "C"
 
+int spvo_int::classic_upload_image(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride) { return cls_prepare(c, img, rows, cols, stride); }
+
 // ---------------------------------------------------------------- one submission per stereo pair, features stay on the device
 // everything bin_ensure sizes by the slot capacity; the slots are empty afterwards
 void spvo_int::classic_release_slots(spvo_ctx *c) {

@@ -9,6 +9,7 @@
 //   spvo_detect.hip    preprocess, heat map / NMS / sampling, the detector submissions, spvo_forward
 //   spvo_classic.hip   the classic front end: ORB, Shi-Tomasi, FAST, the ORB extractor, preprocess without an engine
 //   spvo_sift.hip      the classic front end: SIFT detector + descriptor
+//   spvo_brisk.hip     the classic front end: BRISK descriptor extractor on given keypoints
 //   spvo_match.hip     descriptor matching (L2, Hamming)
 //   spvo_solve.hip     triangulation, PnP-RANSAC, gating, Levenberg-Marquardt, the fused solve
 #pragma once
@@ -29,6 +30,7 @@
 #include "spvo_types.hip.h"
 
 #pragma GCC visibility push(hidden)
+namespace spvo { struct BriskLongPair; struct BriskShortPair; }   // brisk.hip.h
 using namespace spvo;
 
 #include "launch_segments.hip.h"
@@ -355,6 +357,24 @@ struct spvo_ctx {
     hipEvent_t ev_feat = nullptr, ev_match = nullptr;   // features of the last call final / its prematches landed
     int last_slot_l = -1;                // left slot of the previous call (temporal partner)
   } bin;
+  // BRISK extractor for given keypoints (brisk.hip.h) on the image resident in `cls`: the pattern tables (uploaded on the first call), the
+  // integral image, the keypoint list with its results and their pinned mirrors; buffers grow on demand
+  struct BriskBufs {
+    float *points = nullptr;              // [64][1024][60][3] x, y, sigma
+    BriskLongPair *long_pairs = nullptr;
+    BriskShortPair *short_pairs = nullptr;
+    bool tables_ready = false;            // set last: every table above is on the device, cnt and h_n exist
+    int *cnt = nullptr;                   // [4]: kept keypoints
+    int *integ = nullptr;                 // (rows + 1) x (cols + 1)
+    size_t integ_cap = 0;
+    int kp_cap = 0, v0_cap = 0;           // rows the keypoint buffers / the values0 buffers (test hook: allocated on demand) hold
+    float *xy = nullptr, *size = nullptr, *angle = nullptr;
+    int *kept = nullptr, *kscale = nullptr, *values0 = nullptr;
+    uint8_t *desc = nullptr;
+    int *h_n = nullptr, *h_kept = nullptr, *h_values0 = nullptr;   // pinned: what brisk_finish_kernel writes for the host
+    float *h_angle = nullptr;
+    uint8_t *h_desc = nullptr;
+  } brisk;
   // SIFT detector + descriptor of the classic front end (sift.hip.h): the image, its pyramid (all Gaussian and DoG levels: what
   // spvo_sift_debug_level serves until the next call), the candidate and output lists; device buffers grow on demand, the host staging keeps its capacity
   struct SiftBufs {
@@ -562,6 +582,10 @@ void resize_tables(int dst_w, int src_w, int dst_h, int src_h, std::vector<int> 
 int classic_preprocess(spvo_ctx *c, const CropGeom &g, size_t stride);
 void classic_release(spvo_ctx *c);   // frees spvo_ctx::bin (spvo_destroy)
 void classic_release_slots(spvo_ctx *c);   // ... the part of it that is sized by the slot capacity
+// a host image (strided view) becomes the resident image of spvo_ctx::cls, every buffer of it grown to the shape (enqueued on the solver's stream)
+int classic_upload_image(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride);
+// ---- spvo_brisk.hip
+void brisk_release(spvo_ctx *c);     // frees spvo_ctx::brisk (spvo_destroy)
 // ---- spvo_sift.hip
 void sift_release(spvo_ctx *c);      // frees spvo_ctx::sift (spvo_destroy)
 void sift_invalidate_matches(spvo_ctx *c);   // the stored prematches of the SIFT slots are stale (spvo_set_prematch, spvo_set_match_fp8)

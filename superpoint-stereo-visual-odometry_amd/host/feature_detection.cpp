@@ -518,19 +518,24 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
 // there, so detectKeypoints keeps the descriptors for the describeKeypoints call that follows on the same image.  ShiTomasi + ORB
 // (the default constructor) and FAST + ORB go through spvo_gftt_detect / spvo_fast_detect and spvo_orb_describe (classic.cpp:32-47,
 // 66-68, 110-111); the image stays on the device between the two.  SIFT + SIFT goes through spvo_sift_detect, one pass like ORB: float
-// descriptors (n x 128 CV_32F), matched with NORM_L2 by spvo_match_l2.  BRISK and AKAZE are OpenCV features2d calls and stay unavailable,
-// and so does every other mix (SIFT keypoints with an ORB descriptor, ...).
+// descriptors (n x 128 CV_32F), matched with NORM_L2 by spvo_match_l2.  ShiTomasi + BRISK and FAST + BRISK go through the same detectors and
+// spvo_brisk_describe (cv::BRISK::create(30, 3, 1.0f)->compute, classic.cpp:56-65): 64-byte rows, matched with NORM_HAMMING.  The BRISK
+// detector and AKAZE are OpenCV features2d calls and stay unavailable, and so does every other mix (SIFT keypoints with an ORB descriptor, ...).
 bool ClassicFeatureFrontEnd::available() { return true; }
 static bool classic_detector_runs(DetectorType d) { return d == DetectorType::ORB || d == DetectorType::ShiTomasi || d == DetectorType::FAST; }
 static bool classic_sift_pair(DetectorType d, DescriptorType e) { return d == DetectorType::SIFT && e == DescriptorType::SIFT; }
-static bool classic_pair_runs(DetectorType d, DescriptorType e) { return classic_sift_pair(d, e) || (classic_detector_runs(d) && e == DescriptorType::ORB); }
+// BRISK is an extractor for given keypoints here (spvo_brisk_describe): it goes with the two detectors that hand keypoints over
+static bool classic_brisk_pair(DetectorType d, DescriptorType e) { return (d == DetectorType::ShiTomasi || d == DetectorType::FAST) && e == DescriptorType::BRISK; }
+static bool classic_pair_runs(DetectorType d, DescriptorType e) {
+  return classic_sift_pair(d, e) || (classic_detector_runs(d) && e == DescriptorType::ORB) || classic_brisk_pair(d, e);
+}
 void ClassicFeatureFrontEnd::initDetector() {
   if (!classic_detector_runs(detector_type_) && !classic_sift_pair(detector_type_, descriptor_type_))
     logError("[initDetector] only ORB, ShiTomasi, FAST and SIFT (with SIFT descriptors) run without OpenCV (build with SPVO_USE_OPENCV for the other detectors of classic.cpp:7-56)");
 }
 void ClassicFeatureFrontEnd::initDescriptor() {
-  if (descriptor_type_ != DescriptorType::ORB && !classic_sift_pair(detector_type_, descriptor_type_))
-    logError("[initDescriptor] only ORB, and SIFT on SIFT keypoints, run without OpenCV (build with SPVO_USE_OPENCV for the other descriptors of classic.cpp:58-79)");
+  if (descriptor_type_ != DescriptorType::ORB && !classic_sift_pair(detector_type_, descriptor_type_) && !classic_brisk_pair(detector_type_, descriptor_type_))
+    logError("[initDescriptor] only ORB, BRISK on ShiTomasi / FAST keypoints, and SIFT on SIFT keypoints, run without OpenCV (build with SPVO_USE_OPENCV for the other descriptors of classic.cpp:58-79)");
 }
 
 std::vector<cv::KeyPoint> ClassicFeatureFrontEnd::detectKeypoints(const cv::Mat &img) {
@@ -538,7 +543,7 @@ std::vector<cv::KeyPoint> ClassicFeatureFrontEnd::detectKeypoints(const cv::Mat 
   orb_desc_ = cv::Mat();
   detected_data_ = nullptr;
   if (!classic_pair_runs(detector_type_, descriptor_type_)) {
-    logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB, ShiTomasi and FAST with ORB descriptors and SIFT with SIFT descriptors run");
+    logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB, ShiTomasi and FAST with ORB descriptors, ShiTomasi and FAST with BRISK descriptors and SIFT with SIFT descriptors run");
     return keypoints;
   }
   if (!ensureContext()) return keypoints;
@@ -657,6 +662,39 @@ cv::Mat ClassicFeatureFrontEnd::describeKeypoints(std::vector<cv::KeyPoint> &key
     if (m) std::memcpy(d.ptr<uint8_t>(0), desc.ptr<uint8_t>(0), (size_t)m * 32);
     return d;
   }
+  if (classic_brisk_pair(detector_type_, descriptor_type_)) {
+    // cv::BRISK::create(30, 3, 1.0f)->compute(img, keypoints, descriptors), classic.cpp:56-65: every keypoint's own size (5: ShiTomasi, 7: FAST)
+    // picks its scale; the erase-and-angle handling is the ORB branch's (BRISK reports degrees, 0 .. 360)
+    if (!ensureContext()) return cv::Mat();
+    if (img.depth() != CV_8U || img.rows <= 0) {
+      logError("describeKeypoints: 8-bit single-channel image expected");
+      return cv::Mat();
+    }
+    const int n = (int)keypoints.size();
+    std::vector<float> xy((size_t)n * 2), size((size_t)n), angle((size_t)n);
+    std::vector<int32_t> kept((size_t)n);
+    for (int i = 0; i < n; ++i) { xy[2 * i] = keypoints[i].pt.x; xy[2 * i + 1] = keypoints[i].pt.y; size[i] = keypoints[i].size; }
+    cv::Mat desc(n, 64, CV_8UC1);
+    const bool resident = detected_data_ && detected_data_ == img.data && detected_rows_ == img.rows && detected_cols_ == img.cols;
+    int m = 0;
+    if (spvo_brisk_describe(ctx_, resident ? nullptr : img.ptr<uint8_t>(0), img.rows, img.cols, (size_t)img.step, xy.data(), size.data(), n, kept.data(), angle.data(),
+                            n ? desc.ptr<uint8_t>(0) : nullptr, nullptr, &m) != SPVO_OK) {
+      logError(std::string("spvo_brisk_describe: ") + spvo_last_error(ctx_));
+      keypoints.clear();
+      return cv::Mat();
+    }
+    std::vector<cv::KeyPoint> out;
+    out.reserve(m);
+    for (int i = 0; i < m; ++i) {
+      cv::KeyPoint k = keypoints[kept[i]];
+      k.angle = angle[i];
+      out.push_back(k);
+    }
+    keypoints.swap(out);
+    cv::Mat d(m, 64, CV_8UC1);
+    if (m) std::memcpy(d.ptr<uint8_t>(0), desc.ptr<uint8_t>(0), (size_t)m * 64);
+    return d;
+  }
   if (orb_desc_.rows != (int)keypoints.size()) {
     logError("describeKeypoints: call detectKeypoints on the same image first (ORB and SIFT detect and describe in one pass here)");
     return cv::Mat();
@@ -670,7 +708,7 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
     return;
   }
   if (!classic_pair_runs(detector_type_, descriptor_type_)) {
-    logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB, ShiTomasi and FAST with ORB descriptors and SIFT with SIFT descriptors run");
+    logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB, ShiTomasi and FAST with ORB descriptors, ShiTomasi and FAST with BRISK descriptors and SIFT with SIFT descriptors run");
     return;
   }
   if (!ensureContext()) return;   // no device: logged, nothing pushed (nn.cpp:53-55 convention)
@@ -680,7 +718,8 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
     preprocessImageImpl(img_l, projection_matrix_l_);
     preprocessImageImpl(img_r, projection_matrix_r_);
   }
-  if (!resident_ || !addStereoImagePairResident(img_l, img_r)) {
+  // (setDeviceResident with a BRISK descriptor: the binary slots hold 32-byte rows, so the pair takes the per-image path)
+  if (!resident_ || descriptor_type_ == DescriptorType::BRISK || !addStereoImagePairResident(img_l, img_r)) {
     cv::Mat *imgs[2] = {&img_l, &img_r};
     for (cv::Mat *im : imgs) {
       images_dq.push_back(*im);

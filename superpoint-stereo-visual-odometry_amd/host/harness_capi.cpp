@@ -265,6 +265,32 @@ int spvo_host_classic_default_probe(const uint8_t *img_l, const uint8_t *img_r, 
   return (int)fe.keypoints_dq.size();
 }
 
+// ... the same for ClassicFeatureFrontEnd(detector, descriptor, BF, NN, cross-check, ..) at the native resolution; counts[4] = the descriptor
+// matrix's columns (left image).  -1000000 / -1000001: no such detector / descriptor
+int spvo_host_classic_pair_probe(const char *detector_name, const char *descriptor_name, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, const double *P_l,
+                                 const double *P_r, int *counts, char *err, int cap) {
+  if (!detector_name || !detector_name_to_type.count(detector_name)) return -1000000;
+  if (!descriptor_name || !descriptor_name_to_type.count(descriptor_name)) return -1000001;
+  ClassicFeatureFrontEnd fe(detector_name_to_type.at(detector_name), descriptor_name_to_type.at(descriptor_name), matcher_name_to_type.at("BF"), selector_name_to_type.at("NN"), true,
+                            2.0f, 2.0f, 4, false, 0, 0);
+  cv::Mat l(rows, cols, CV_8UC1), r(rows, cols, CV_8UC1), pl(3, 4, CV_64FC1), pr(3, 4, CV_64FC1);
+  std::memcpy(l.data, img_l, (size_t)rows * cols);
+  std::memcpy(r.data, img_r, (size_t)rows * cols);
+  std::memcpy(pl.data, P_l, 12 * sizeof(double));
+  std::memcpy(pr.data, P_r, 12 * sizeof(double));
+  fe.addStereoImagePair(l, r, pl, pr);
+  std::strncpy(err, fe.lastError().c_str(), cap - 1);
+  err[cap - 1] = 0;
+  for (int i = 0; i < 5; ++i) counts[i] = 0;
+  if (fe.keypoints_dq.size() != fe.descriptors_dq.size()) return -1;
+  if (fe.keypoints_dq.size() >= 2) {
+    counts[0] = (int)fe.keypoints_dq.end()[-2].size(); counts[1] = fe.descriptors_dq.end()[-2].rows;
+    counts[2] = (int)fe.keypoints_dq.end()[-1].size(); counts[3] = fe.descriptors_dq.end()[-1].rows;
+    counts[4] = fe.descriptors_dq.end()[-2].cols;
+  }
+  return (int)fe.keypoints_dq.size();
+}
+
 // stereoCallback (node.cpp:150-262) replayed on a ClassicFeatureFrontEnd(detector, ORB, BF, selector, cross_check, stereo_threshold, ..)
 // exactly as node.cpp:353-360 constructs it, over n stereo pairs in host memory.  input_height / input_width 0 / 0: native resolution
 // (launch/visual_odometry_classic.launch); otherwise preprocessImageImpl runs first (classic.cpp:96-100).
@@ -306,13 +332,14 @@ static uint64_t digest_ints(const std::vector<int> &a, const std::vector<int> &b
   return h;
 }
 
-static int classic_sequence_run(const char *detector_name, int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l,
+static int classic_sequence_run(const char *detector_name, const char *descriptor_name, int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l,
                                 const double *P_r, int knn, int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats,
                                 double *seconds, int input_height, int input_width, uint64_t *digest) {
   if (!detector_name || !detector_name_to_type.count(detector_name)) return -1000000;
-  // "SIFT" means SIFT keypoints with SIFT descriptors (NORM_L2); every other detector goes with the ORB extractor
+  // descriptor_name NULL: "SIFT" means SIFT keypoints with SIFT descriptors (NORM_L2), every other detector goes with the ORB extractor
   const bool sift = detector_name_to_type.at(detector_name) == DetectorType::SIFT;
-  ClassicFeatureFrontEnd fe(detector_name_to_type.at(detector_name), descriptor_name_to_type.at(sift ? "SIFT" : "ORB"), matcher_name_to_type.at("BF"),
+  if (descriptor_name && !descriptor_name_to_type.count(descriptor_name)) return -1000001;
+  ClassicFeatureFrontEnd fe(detector_name_to_type.at(detector_name), descriptor_name_to_type.at(descriptor_name ? descriptor_name : sift ? "SIFT" : "ORB"), matcher_name_to_type.at("BF"),
                             selector_name_to_type.at(knn ? "KNN" : "NN"), cross_check != 0, stereo_threshold, stereo_threshold, refinement_degree, false, input_height,
                             input_width);
   timespec t0{}, t1{};
@@ -359,7 +386,7 @@ static int classic_sequence_run(const char *detector_name, int n, const uint8_t 
 int spvo_host_classic_sequence_ex(const char *detector_name, int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l,
                                   const double *P_r, int knn, int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats,
                                   double *seconds, int input_height, int input_width) {
-  return classic_sequence_run(detector_name, n, imgs_l, imgs_r, rows, cols, P_l, P_r, knn, cross_check, stereo_threshold, refinement_degree, warm, poses, stats, seconds, input_height,
+  return classic_sequence_run(detector_name, nullptr, n, imgs_l, imgs_r, rows, cols, P_l, P_r, knn, cross_check, stereo_threshold, refinement_degree, warm, poses, stats, seconds, input_height,
                               input_width, nullptr);
 }
 
@@ -367,8 +394,17 @@ int spvo_host_classic_sequence_ex(const char *detector_name, int n, const uint8_
 int spvo_host_classic_sequence_trace(const char *detector_name, int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l,
                                      const double *P_r, int knn, int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats,
                                      double *seconds, int input_height, int input_width, uint64_t *digest) {
-  return classic_sequence_run(detector_name, n, imgs_l, imgs_r, rows, cols, P_l, P_r, knn, cross_check, stereo_threshold, refinement_degree, warm, poses, stats, seconds, input_height,
+  return classic_sequence_run(detector_name, nullptr, n, imgs_l, imgs_r, rows, cols, P_l, P_r, knn, cross_check, stereo_threshold, refinement_degree, warm, poses, stats, seconds, input_height,
                               input_width, digest);
+}
+
+// ... with the descriptor named as well ("ORB", "BRISK", "SIFT"; -1000001: no such descriptor)
+int spvo_host_classic_sequence_desc(const char *detector_name, const char *descriptor_name, int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols,
+                                    const double *P_l, const double *P_r, int knn, int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses,
+                                    int *stats, double *seconds, int input_height, int input_width, uint64_t *digest) {
+  if (!descriptor_name) return -1000001;
+  return classic_sequence_run(detector_name, descriptor_name, n, imgs_l, imgs_r, rows, cols, P_l, P_r, knn, cross_check, stereo_threshold, refinement_degree, warm, poses, stats, seconds,
+                              input_height, input_width, digest);
 }
 
 // ClassicFeatureFrontEnd::setDeviceResident / setResidentCapacity for the front ends constructed afterwards (capacity <= 0: unchanged)

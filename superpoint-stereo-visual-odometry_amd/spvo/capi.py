@@ -80,7 +80,7 @@ SYMBOLS = [
     "spvo_default_config", "spvo_create", "spvo_destroy", "spvo_last_error", "spvo_load_weights", "spvo_engine_precision", "spvo_set_fp32_split",
     "spvo_preprocess", "spvo_forward", "spvo_debug_tensor", "spvo_heatmap", "spvo_nms",
     "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8",
-    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_detect_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
+    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_detect_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
     "spvo_profile_enable", "spvo_profile_reset", "spvo_profile_only", "spvo_profile_count", "spvo_profile_get", "spvo_profile_stage_kernel",
     "spvo_set_tuning", "spvo_get_tuning", "spvo_clear_tuning",
     "spvo_comm_unique_id", "spvo_comm_available", "spvo_comm_create", "spvo_comm_create_host", "spvo_comm_rank", "spvo_comm_world", "spvo_comm_destroy",
@@ -137,6 +137,8 @@ def load() -> C.CDLL:
     lib.spvo_gftt_last_rounds.argtypes = [vp, vp, ip]
     lib.spvo_fast_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, vp, vp, C.c_int, ip]
     lib.spvo_orb_describe.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, vp, vp, vp, ip]
+    lib.spvo_brisk_describe.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, C.c_int, vp, vp, vp, vp, ip]
+    lib.spvo_brisk_tables.argtypes = [C.c_int, vp, vp, vp, vp, vp]
     lib.spvo_sift_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, C.c_int, ip]
     lib.spvo_sift_debug_level.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, ip, ip]
     lib.spvo_sift_detect_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(SiftFeatures), C.POINTER(SiftFeatures)]
@@ -462,6 +464,36 @@ class Context:
         if img is not None:
             self._resident_shape = img.shape
         return dict(kept=kept[:m.value].copy(), angle=angle[:m.value].copy(), desc=desc[:m.value].copy())
+
+    def brisk_describe(self, img, xy: np.ndarray, size, shape=None, values0=False):
+        """BRISK descriptors of given keypoints (spvo_brisk_describe); size: per keypoint, or one for all.  img = None: the image of the
+        last gftt() / fast() / orb_describe() / brisk_describe() of this context, still on the device (shape as in orb_describe).
+        -> dict of kept [m] (indices into xy that survived the border rule), angle [m] degrees, desc [m,64] and, with values0, the 60
+        intensities at rotation 0 [m,60]."""
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        n = len(xy)
+        size = np.ascontiguousarray(np.broadcast_to(np.asarray(size, np.float32), (n,)))
+        kept = np.zeros(max(n, 1), np.int32)
+        angle = np.zeros(max(n, 1), np.float32)
+        desc = np.zeros((max(n, 1), 64), np.uint8)
+        v0 = np.zeros((max(n, 1), 60), np.int32) if values0 else None
+        m = C.c_int(0)
+        if img is None:
+            rows, cols = shape if shape is not None else getattr(self, "_resident_shape", (0, 0))
+            ptr, stride = None, 0
+            if rows <= 0 or cols <= 0:
+                rows = cols = 1            # nothing remembered: let the library answer (SPVO_ERR_STATE)
+        else:
+            img = _u8_rows(img)
+            (rows, cols), ptr, stride = img.shape, _ptr(img), img.strides[0]
+        self._check(self.lib.spvo_brisk_describe(self.h, ptr, rows, cols, stride, _ptr(xy), _ptr(size), n, _ptr(kept), _ptr(angle), _ptr(desc),
+                                                 _ptr(v0) if values0 else None, C.byref(m)))
+        if img is not None:
+            self._resident_shape = img.shape
+        out = dict(kept=kept[:m.value].copy(), angle=angle[:m.value].copy(), desc=desc[:m.value].copy())
+        if values0:
+            out["values0"] = v0[:m.value].copy()
+        return out
 
     def sift_detect(self, img: np.ndarray, cap: Optional[int] = None):
         """SIFT keypoints + descriptors of one u8 image (spvo_sift_detect): dict of kp [m] (SIFT_KP_DTYPE records), desc [m, 128] float32 (integers
@@ -857,3 +889,20 @@ def obs_array(X, uv, cam, inverse) -> np.ndarray:
         a["cam"] = np.asarray(cam, np.int32)
         a["inverse"] = np.asarray(inverse, np.int32)
     return a
+
+
+def brisk_tables(scales=range(64)):
+    """The BRISK extractor's tables (spvo_brisk_tables; no context, no device): dict of points [64,1024,60,3] (x, y, sigma; the slices of
+    `scales`, zeros elsewhere), short_pairs [512,2], long_pairs [870,4] (i, j, wdx, wdy), scale_list [64], size_list [64]."""
+    lib = load()
+    points = np.zeros((64, 1024, 60, 3), np.float32)
+    short = np.zeros((512, 2), np.int32)
+    long_ = np.zeros((870, 4), np.int32)
+    scale_list = np.zeros(64, np.float32)
+    size_list = np.zeros(64, np.int32)
+    rc = lib.spvo_brisk_tables(0, None, _ptr(short), _ptr(long_), _ptr(scale_list), _ptr(size_list))
+    for s in scales:
+        rc = rc or lib.spvo_brisk_tables(int(s), points[s].ctypes.data, None, None, None, None)
+    if rc:
+        raise SpvoError(rc, (lib.spvo_last_error(None) or b"").decode())
+    return dict(points=points, short_pairs=short, long_pairs=long_, scale_list=scale_list, size_list=size_list)

@@ -342,9 +342,10 @@ class FrontEnd:
 
 
 def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_threshold=2.0, refinement_degree=4, warm=0, detector="ORB", input_size=None, resident=False,
-                     resident_capacity=0, trace=False):
-    """stereoCallback replayed on ClassicFeatureFrontEnd(detector, ORB, BF, ...) (node.cpp:353-360) over host image pairs -- detector
-    "ORB", "ShiTomasi" or "FAST"; input_size None: at their native resolution, (height, width): through preprocessImageImpl first
+                     resident_capacity=0, trace=False, descriptor="ORB"):
+    """stereoCallback replayed on ClassicFeatureFrontEnd(detector, descriptor, BF, ...) (node.cpp:353-360) over host image pairs -- detector
+    "ORB", "ShiTomasi" or "FAST" with descriptor "ORB", "ShiTomasi" or "FAST" with descriptor "BRISK" (64-byte rows; with `resident` such a run
+    takes the per-image path), or detector "SIFT" (SIFT descriptors whatever `descriptor` says, as before); input_size None: at their native resolution, (height, width): through preprocessImageImpl first
     (classic.cpp:96-100).  Returns (poses [n, 7] = q xyzw + t of cam0_curr_T_cam0_prev, stats [n, 4] = keypoints L, R, stereo
     matches, PnP inliers, seconds spent on frames warm .. n-1).
     resident: ClassicFeatureFrontEnd::setDeviceResident for this run -- one spvo_classic_detect per pair, features and matching stay on the
@@ -356,6 +357,8 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     lib.spvo_host_classic_sequence_trace.restype = C.c_int
     lib.spvo_host_classic_sequence_trace.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                                      C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_void_p]
+    lib.spvo_host_classic_sequence_desc.restype = C.c_int
+    lib.spvo_host_classic_sequence_desc.argtypes = [C.c_char_p, C.c_char_p] + lib.spvo_host_classic_sequence_trace.argtypes[1:]
     lib.spvo_host_classic_set_resident.restype = None
     lib.spvo_host_classic_set_resident.argtypes = [C.c_int, C.c_int]
     n = len(frames)
@@ -373,12 +376,18 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     digest = np.zeros((n, 8), np.uint64) if trace else None     # NULL: nothing is digested (the digests are computed inside the timed loop)
     lib.spvo_host_classic_set_resident(int(bool(resident)), int(resident_capacity) if resident_capacity > 0 else 8192)
     try:
-        rc = lib.spvo_host_classic_sequence_trace(detector.encode(), n, pl, pr, rows, cols, Pl.ctypes.data, Pr.ctypes.data, 1 if selector == "KNN" else 0, int(cross_check),
-                                                  stereo_threshold, refinement_degree, warm, poses.ctypes.data, stats.ctypes.data, C.byref(sec), ih, iw, digest.ctypes.data if trace else None)
+        args = (n, pl, pr, rows, cols, Pl.ctypes.data, Pr.ctypes.data, 1 if selector == "KNN" else 0, int(cross_check), stereo_threshold, refinement_degree, warm,
+                poses.ctypes.data, stats.ctypes.data, C.byref(sec), ih, iw, digest.ctypes.data if trace else None)
+        if descriptor == "ORB" or detector == "SIFT":             # the export that pairs every detector with its default descriptor
+            rc = lib.spvo_host_classic_sequence_trace(detector.encode(), *args)
+        else:
+            rc = lib.spvo_host_classic_sequence_desc(detector.encode(), descriptor.encode(), *args)
     finally:
         lib.spvo_host_classic_set_resident(0, 8192)
     if rc == -1000000:
         raise ValueError("unknown detector %r" % (detector,))
+    if rc == -1000001:
+        raise ValueError("unknown descriptor %r" % (descriptor,))
     if rc != n:
         raise RuntimeError("classic front end failed at frame %d" % (-rc - 1))
     if trace:
@@ -399,4 +408,21 @@ def classic_default_probe(img_l, img_r, P_l, P_r):
     counts = np.zeros(4, np.int32)
     buf = C.create_string_buffer(512)
     rc = lib.spvo_host_classic_default_probe(l.ctypes.data, r.ctypes.data, l.shape[0], l.shape[1], Pl.ctypes.data, Pr.ctypes.data, counts.ctypes.data, buf, 512)
+    return rc, counts, buf.value.decode()
+
+
+def classic_pair_probe(detector, descriptor, img_l, img_r, P_l, P_r):
+    """ClassicFeatureFrontEnd(detector, descriptor, BF, NN, cross-check) at the native resolution offered one stereo pair.
+    -> (deque entries, [keypoints L, descriptor rows L, keypoints R, descriptor rows R, descriptor columns], the error it logged)"""
+    lib = load()
+    lib.spvo_host_classic_pair_probe.restype = C.c_int
+    lib.spvo_host_classic_pair_probe.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
+    l = np.ascontiguousarray(img_l, np.uint8)
+    r = np.ascontiguousarray(img_r, np.uint8)
+    Pl = np.ascontiguousarray(P_l, np.float64).reshape(12)
+    Pr = np.ascontiguousarray(P_r, np.float64).reshape(12)
+    counts = np.zeros(5, np.int32)
+    buf = C.create_string_buffer(512)
+    rc = lib.spvo_host_classic_pair_probe(detector.encode(), descriptor.encode(), l.ctypes.data, r.ctypes.data, l.shape[0], l.shape[1], Pl.ctypes.data, Pr.ctypes.data,
+                                          counts.ctypes.data, buf, 512)
     return rc, counts, buf.value.decode()

@@ -1,7 +1,8 @@
 """The classic front end on the GPU.
 
-python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST] [--resident]
-    ClassicFeatureFrontEnd(detector, ORB, BF, KNN) over the synthetic stream: frames/s of the synchronous stereoCallback;
+python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST] [--descriptor ORB|BRISK] [--resident]
+    ClassicFeatureFrontEnd(detector, descriptor, BF, KNN) over the synthetic stream: frames/s of the synchronous stereoCallback
+    (--descriptor BRISK: with --detector ShiTomasi or FAST);
     --resident: with ClassicFeatureFrontEnd::setDeviceResident (one spvo_classic_detect per pair, matching on the binary slots).
 python tools/classic_bench.py --detectors [--calls 200] [--warmup 20]
     per image at 1241 x 376: spvo_orb_detect (the yardstick, same run) beside spvo_gftt_detect + spvo_orb_describe and
@@ -11,6 +12,10 @@ python tools/classic_bench.py --leg gftt|fast|orb|sift [--calls 50]
     one leg alone, for rocprofv3 --kernel-trace --stats -- python tools/classic_bench.py --leg gftt
     (sift: spvo_sift_detect per image at 1241 x 376; the per-kernel split -- sift_blur_kernel / sift_extrema_kernel / sift_refine_kernel /
     sift_describe_kernel -- is the kernel trace's)
+python tools/classic_bench.py --leg brisk|orb_describe [--calls 50]
+    spvo_brisk_describe / spvo_orb_describe alone on the FAST keypoints of the 1241 x 376 sample (image passed with every call), for
+    rocprofv3 --kernel-trace --stats as above: brisk_integral_rows_kernel + brisk_integral_cols_kernel / brisk_compact_kernel /
+    brisk_describe_kernel is the split.  --leg brisk also prints the one-off cost: the table build and the first call's upload.
 python tools/classic_bench.py --leg match|match_slots [--selector NN|KNN] [--cross] [--calls 50]
     one matcher alone on the two resident ORB sets of the 1241 x 376 sample pair: spvo_match_hamming on the host copies (match_hamming_kernel<8>)
     or spvo_match_hamming_slots on the binary slots (match_hamming_tiled_kernel), for rocprofv3 --kernel-trace --stats as above.
@@ -28,9 +33,10 @@ from spvo import capi, host, synth
 ap = argparse.ArgumentParser()
 ap.add_argument("frames", nargs="?", type=int, default=60)
 ap.add_argument("--detector", default="ORB")
+ap.add_argument("--descriptor", default="ORB")
 ap.add_argument("--detectors", action="store_true")
 ap.add_argument("--resident", action="store_true")
-ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "match", "match_slots"])
+ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "orb_describe", "match", "match_slots"])
 ap.add_argument("--selector", default="KNN", choices=["NN", "KNN"])
 ap.add_argument("--cross", action="store_true")
 ap.add_argument("--calls", type=int, default=200)
@@ -56,6 +62,22 @@ if args.detectors or args.leg:
     def leg_sift():
         return ctx.sift_detect(img)["n"]
 
+    if args.leg in ("brisk", "orb_describe"):
+        kp = ctx.fast(img)["xy"]
+        if args.leg == "brisk":
+            t0 = time.perf_counter()
+            capi.brisk_tables(scales=())
+            t1 = time.perf_counter()
+            ctx.brisk_describe(img, kp, 7.0)
+            t2 = time.perf_counter()
+            print("BRISK one-off: table build %.1f ms; first spvo_brisk_describe of the context (47 MB table upload, buffers) %.1f ms" % (1e3 * (t1 - t0), 1e3 * (t2 - t1)))
+
+    def leg_brisk():
+        return len(ctx.brisk_describe(img, kp, 7.0)["kept"])
+
+    def leg_orb_describe():
+        return len(ctx.orb_describe(img, kp)["kept"])
+
     if args.leg in ("match", "match_slots"):
         img_r = np.ascontiguousarray(frames[0][1][:376, :1241])
         fl, fr = ctx.classic_detect(img, img_r, 0, 1, "ORB")
@@ -71,6 +93,8 @@ if args.detectors or args.leg:
 
     legs = dict(match=("spvo_match_hamming, %d x %d rows" % (len(fl["xy"]) if leg_match else 0, len(fr["xy"]) if leg_match else 0), leg_match),
                 match_slots=("spvo_match_hamming_slots, %d x %d rows" % (len(fl["xy"]) if leg_match else 0, len(fr["xy"]) if leg_match else 0), leg_match_slots),
+                brisk=("spvo_brisk_describe, %d FAST keypoints" % (len(kp) if args.leg == "brisk" else 0), leg_brisk),
+                orb_describe=("spvo_orb_describe, %d FAST keypoints" % (len(kp) if args.leg == "orb_describe" else 0), leg_orb_describe),
                 orb=("spvo_orb_detect", leg_orb), sift=("spvo_sift_detect", leg_sift), gftt=("spvo_gftt_detect + spvo_orb_describe", leg_gftt), fast=("spvo_fast_detect + spvo_orb_describe", leg_fast))
     for key in ([args.leg] if args.leg else ["orb", "gftt", "fast"]):
         name, fn = legs[key]
@@ -92,5 +116,5 @@ if args.detectors or args.leg:
 else:
     n = args.frames
     seq = [frames[i % 8] for i in range(n)]
-    p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5, detector=args.detector, resident=args.resident)
-    print("classic front end (%s%s) on the GPU: %.1f stereo frames/s (%.3f ms per pair), keypoints %d, stereo matches %d, inliers %d" % (args.detector, ", device-resident" if args.resident else "", (n - 5) / sec, 1e3 * sec / (n - 5), np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3])))
+    p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5, detector=args.detector, resident=args.resident, descriptor=args.descriptor)
+    print("classic front end (%s%s) on the GPU: %.1f stereo frames/s (%.3f ms per pair), keypoints %d, stereo matches %d, inliers %d" % (args.detector + ("" if args.descriptor == "ORB" else " + " + args.descriptor), ", device-resident" if args.resident else "", (n - 5) / sec, 1e3 * sec / (n - 5), np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3])))
