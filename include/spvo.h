@@ -322,22 +322,30 @@ int spvo_sift_debug_level(spvo_ctx *ctx, int octave, int layer, int dog, float *
 
 /* ------------------------------------------------------- classic front end: one submission per stereo pair, features resident
  * detectKeypoints + describeKeypoints of ClassicFeatureFrontEnd for BOTH images of a stereo pair in one call: ORB, or Shi-Tomasi /
- * FAST followed by the ORB extractor (the three pairs the per-image entry points above cover).  Both images go up through pinned
+ * FAST followed by the ORB extractor or by the BRISK extractor (the five pairs the per-image entry points above cover).  Both images go up through pinned
  * staging, the whole chain of both is enqueued without a host round trip -- for the two non-ORB kinds the keypoints go from the
  * detector to the extractor on the device, the extractor's border rule being an order-preserving compaction there -- and the call
  * waits once for the result, the features (before that, for whatever an earlier call left running on the solver's stream: its staging is reused).  They are left in two BINARY FEATURE SLOTS (0 .. 9; separate from the float slots of spvo_detect*,
- * used as a ring of pairs like those): keypoint records, 32-byte descriptor rows and the row count stay on the device for
- * spvo_match_hamming_slots.  What the host receives equals, byte for byte, what spvo_orb_detect -- or spvo_gftt_detect /
+ * used as a ring of pairs like those): keypoint records, descriptor rows (32 bytes; 64 for the two BRISK kinds -- a slot remembers its
+ * row width) and the row count stay on the device for spvo_match_hamming_slots.  What the host receives equals, byte for byte, what spvo_orb_detect -- or spvo_gftt_detect /
  * spvo_fast_detect followed by spvo_orb_describe(img = NULL) -- returns for the same image and parameters; for the two non-ORB kinds a
  * record carries the extractor's angle (radians), the DETECTOR's response and octave 0.
+ * The two BRISK kinds (SPVO_CLASSIC_GFTT_BRISK, SPVO_CLASSIC_FAST_BRISK): the detector's list stays on the device, the BRISK border rule
+ * for keypoints of size 5 (Shi-Tomasi) / 7 (FAST) is an order-preserving compaction there, and the host receives, byte for byte, what
+ * spvo_gftt_detect / spvo_fast_detect followed by spvo_brisk_describe(img = NULL, size = 5 / 7) returns with `kept` applied to the
+ * detector's xy and response: desc is [cap][64], a record carries the extractor's angle in DEGREES (0 .. 360, spvo_brisk_describe's
+ * float), the detector's x, y and response, octave 0.  Their first call in a context uploads the BRISK tables (spvo_brisk_describe).
  *   SPVO_ERR_CAPACITY  an image yields more rows than slot_capacity: out_*->n report the counts, both slots are left unfilled
  *                      (nothing is truncated: a shortened FAST list would not be the reference's)
  *   SPVO_ERR_STATE     a spvo_detect*_submit is in flight
- * (all ten slots share one allocation size: a call with a larger slot_capacity than any before re-allocates and EMPTIES every slot)
- *   SPVO_ERR_INVALID   bad or equal slots, slot_capacity outside 1 .. 2^22, sizes / parameters the per-image entry points refuse
+ * (all ten slots share one allocation size, for 64-byte rows whatever kind comes first: a call with a larger slot_capacity than any
+ * before re-allocates and EMPTIES every slot; a change of kind does not)
+ *   SPVO_ERR_INVALID   bad or equal slots, slot_capacity outside 1 .. 2^22, sizes / parameters the per-image entry points refuse (for the
+ *                      BRISK kinds also rows * cols * 255 >= 2^31: the int32 integral image)
  * With spvo_set_prematch enabled the two standard matches (slot_l -> slot_r, slot_l -> the previous call's slot_l) are enqueued in the
- * same submission behind the features; the call does not wait for them. */
-typedef enum { SPVO_CLASSIC_ORB = 0, SPVO_CLASSIC_GFTT_ORB = 1, SPVO_CLASSIC_FAST_ORB = 2 } spvo_classic_kind;
+ * same submission behind the features; the call does not wait for them.  A previous left slot of the other row width has no temporal
+ * match: it is skipped, not an error. */
+typedef enum { SPVO_CLASSIC_ORB = 0, SPVO_CLASSIC_GFTT_ORB = 1, SPVO_CLASSIC_FAST_ORB = 2, SPVO_CLASSIC_GFTT_BRISK = 3, SPVO_CLASSIC_FAST_BRISK = 4 } spvo_classic_kind;
 typedef struct {
   int kind;                               /* spvo_classic_kind */
   int nfeatures;                          /* ORB [2000] */
@@ -347,12 +355,18 @@ typedef struct {
 } spvo_classic_opts;
 /* the reference's parameters (feature_detection_classic.cpp:12-47) for `kind` */
 void spvo_default_classic_opts(spvo_classic_opts *o, int kind);
-typedef struct { int n; spvo_orb_keypoint *kp; uint8_t *desc; int cap; } spvo_classic_features;  /* n: out; min(n, cap) rows are written; desc, kp may be NULL */
+typedef struct { int n; spvo_orb_keypoint *kp; uint8_t *desc; int cap; } spvo_classic_features;  /* n: out; min(n, cap) rows are written; desc ([cap][32]; [cap][64] for the BRISK kinds), kp may be NULL */
 int spvo_classic_detect(spvo_ctx *ctx, const spvo_classic_opts *opts, const uint8_t *img_l, const uint8_t *img_r,
                         int rows, int cols, size_t stride, int slot_l, int slot_r,
                         spvo_classic_features *out_l, spvo_classic_features *out_r);
 /* rows a binary feature slot holds; SPVO_ERR_STATE for one that holds nothing (never filled, or left unfilled by SPVO_ERR_CAPACITY) */
 int spvo_classic_slot_rows(spvo_ctx *ctx, int slot, int *n);
+/* Caller-supplied rows into a binary slot (test hook: images cannot produce the rows the matcher's key layout has to survive --
+ * distance 512, exact ties): n rows (0 .. the current slot capacity; slots not allocated yet are allocated at the default 8192) of
+ * desc_bytes = 32 or 64 bytes are uploaded, the records are zeroed, the slot is marked filled with that row width, its generation is
+ * bumped and stored prematch results are dropped.  SPVO_ERR_INVALID for any other width or count, SPVO_ERR_STATE beside a
+ * spvo_detect*_submit in flight. */
+int spvo_classic_slot_fill_debug(spvo_ctx *ctx, int slot, const uint8_t *desc /* [n][desc_bytes] */, int n, int desc_bytes /* 32 or 64 */);
 
 /* spvo_match for rows of `dim` floats (1 .. 256; SIFT: 128): the rows are zero-padded to the 256 columns the matcher's kernels are
  * built for while they are uploaded, which changes no distance.  dim = 256 returns exactly what spvo_match returns.  Rows of integers
@@ -375,7 +389,8 @@ int spvo_match_slots(spvo_ctx *ctx, int slot_a, int slot_b, int selector, int cr
 /* spvo_match_hamming on the device-resident rows of two BINARY feature slots (spvo_classic_detect): nothing is packed or uploaded,
  * the kernel reads both row counts on the device.  Results equal spvo_match_hamming on the host copies of the two slots, index for
  * index and distance for distance.  Returns the result stored by spvo_classic_detect when spvo_set_prematch is on and this is exactly
- * that match of exactly those slot contents.  SPVO_ERR_STATE for a slot that holds nothing; spvo_match_slots on a binary slot number
+ * that match of exactly those slot contents.  Two slots of 64-byte rows (the BRISK kinds) are matched by the same kernel built for rows
+ * of 16 words; slots of different widths: SPVO_ERR_INVALID, the message names both.  SPVO_ERR_STATE for a slot that holds nothing; spvo_match_slots on a binary slot number
  * means the FLOAT slot of that number, as before. */
 int spvo_match_hamming_slots(spvo_ctx *ctx, int slot_a, int slot_b, int selector, int cross_check, float ratio,
                              int32_t *train_idx, float *distance);

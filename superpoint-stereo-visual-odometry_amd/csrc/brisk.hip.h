@@ -6,12 +6,15 @@
 //                                               a running sum down every column (exact integers: any order gives the same image)
 //   brisk_compact_kernel                        the border rule as an order-preserving compaction (cls_compact_kernel's scheme): the kept
 //                                               indices and their scale index
+//   brisk_compact_list_kernel                   the same walk on a detector's list whose length is on the device, one size for all
+//                                               (spvo_classic_detect's chain); brisk_slot_finish_kernel closes that chain
 //   brisk_describe_kernel                       one wave64 per kept keypoint at a time, four per workgroup: 60 box means at rotation 0, direction
 //                                               from the 870 long pairs, 60 box means at rotation theta, 512 short-pair bits
 //   brisk_finish_kernel                         count and results to pinned host memory, n_kept rows instead of a capacity-sized copy
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "spvo_types.hip.h"   // OrbKeypoint
 
 namespace spvo {
 
@@ -75,9 +78,10 @@ __device__ inline int brisk_scale_index(float size, const BriskParams &P) {
 }
 
 // choice 9 as an order-preserving compaction: ONE workgroup walks the list in chunks of 1024 with a running base (wave ballots + an LDS
-// prefix over the 16 waves).  kept[k] = index into xy of the k-th survivor, kscale[k] its scale index; out_cnt[0] = their number.
-__global__ __launch_bounds__(1024) void brisk_compact_kernel(const float *__restrict__ xy, const float *__restrict__ size, int n, int h, int w, BriskParams P,
-                                                             int *__restrict__ kept, int *__restrict__ kscale, int *__restrict__ out_cnt) {
+// prefix over the 16 waves).  scale_of(i) is keypoint i's scale index; of the survivors the first `cap` are handed to put(k, i, s) -- the k-th
+// survivor is keypoint i at scale s -- and ALL are counted: the return value (the same in every thread).
+template <typename ScaleOf, typename Put>
+__device__ __forceinline__ int brisk_compact_walk(const float *__restrict__ xy, int n, int h, int w, const BriskParams &P, int cap, ScaleOf scale_of, Put put) {
   __shared__ int s_wave[16];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int base = 0;
@@ -87,7 +91,7 @@ __global__ __launch_bounds__(1024) void brisk_compact_kernel(const float *__rest
     bool keep = false;
     if (i < n) {
       const float x = xy[2 * i], y = xy[2 * i + 1];
-      s = brisk_scale_index(size[i], P);
+      s = scale_of(i);
       const float b = (float)P.size_list[s];
       keep = x >= b && x < (float)w - b && y >= b && y < (float)h - b;   // (a NaN coordinate is dropped)
     }
@@ -103,10 +107,30 @@ __global__ __launch_bounds__(1024) void brisk_compact_kernel(const float *__rest
       tot += v;
     }
     off += __popcll(m & ((1ull << lane) - 1ull));
-    if (keep) { kept[off] = i; kscale[off] = s; }   // (off < n: at most n survive)
+    if (keep && off < cap) put(off, i, s);
     base += tot;
   }
+  return base;
+}
+
+// spvo_brisk_describe: n and a size per keypoint from the host.  kept[k] = index into xy of the k-th survivor, kscale[k] its scale index;
+// out_cnt[0] = their number (at most n survive: nothing is cut).
+__global__ __launch_bounds__(1024) void brisk_compact_kernel(const float *__restrict__ xy, const float *__restrict__ size, int n, int h, int w, BriskParams P,
+                                                             int *__restrict__ kept, int *__restrict__ kscale, int *__restrict__ out_cnt) {
+  const int base = brisk_compact_walk(xy, n, h, w, P, n, [&](int i) { return brisk_scale_index(size[i], P); }, [&](int k, int i, int s) { kept[k] = i; kscale[k] = s; });
   if (threadIdx.x == 0) out_cnt[0] = base;
+}
+
+// spvo_classic_detect: the detector's list as it lies on the device -- n = det_counters[2] keypoints in xy, their responses in resp -- and ONE
+// size for all of them (5: Shi-Tomasi, 7: FAST).  The detector's response goes along (kresp[k]), as in cls_compact_kernel, and overflow is
+// that kernel's too: survivors at or beyond `cap` are counted and not written.  out_cnt[0] = survivors in all (reaches the host),
+// out_cnt[2] = min(that, cap) = what brisk_describe_kernel describes.
+__global__ __launch_bounds__(1024) void brisk_compact_list_kernel(const float *__restrict__ xy, const float *__restrict__ resp, const int *__restrict__ det_counters, float size,
+                                                                  int h, int w, BriskParams P, int cap, int *__restrict__ kept, int *__restrict__ kscale,
+                                                                  float *__restrict__ kresp, int *__restrict__ out_cnt) {
+  const int s_all = brisk_scale_index(size, P);
+  const int base = brisk_compact_walk(xy, det_counters[2], h, w, P, cap, [&](int) { return s_all; }, [&](int k, int i, int s) { kept[k] = i; kscale[k] = s; kresp[k] = resp[i]; });
+  if (threadIdx.x == 0) { out_cnt[0] = base; out_cnt[2] = min(base, cap); }
 }
 
 // choices 10 and 11: the box mean of half-width sigma around (xf, yf).  Every index is clamped into the image: for a keypoint that passed
@@ -211,6 +235,27 @@ __global__ __launch_bounds__(256) void brisk_finish_kernel(const int *__restrict
   for (int i = tid; i < n * (BRISK_BYTES / 4); i += nth) h_desc[i] = desc[i];
   if (h_values0)
     for (int i = tid; i < n * BRISK_POINTS; i += nth) h_values0[i] = values0[i];
+}
+
+// The last launch of an image in spvo_classic_detect's chain: the slot's count and keypoint records on the device -- x, y the detector's,
+// the extractor's angle (degrees), the detector's response, octave 0 -- and the host's copy of the slot in pinned memory: count, records
+// and 64-byte rows, n rows of each.  h_n = {rows that passed the border rule, overflow flag of the detector}; the slot holds min(n, cap)
+// rows (n > cap: the caller reports SPVO_ERR_CAPACITY and the slot stays unfilled).
+__global__ __launch_bounds__(256) void brisk_slot_finish_kernel(const int *__restrict__ det_counters, const int *__restrict__ ext_cnt, const float *__restrict__ xy,
+                                                                const int *__restrict__ kept, const float *__restrict__ angle, const float *__restrict__ kresp,
+                                                                const uint4 *__restrict__ desc, int cap, OrbKeypoint *__restrict__ kps, int *__restrict__ d_n,
+                                                                int *__restrict__ h_n, OrbKeypoint *__restrict__ h_kp, uint4 *__restrict__ h_desc) {
+  const int n_all = ext_cnt[0], n = min(n_all, cap);
+  const int tid = blockIdx.x * 256 + threadIdx.x, nth = gridDim.x * 256;
+  if (tid == 0) { *d_n = n; h_n[0] = n_all; h_n[1] = det_counters[3]; }
+  for (int i = tid; i < n; i += nth) {
+    const int src = kept[i];
+    OrbKeypoint k;
+    k.x = xy[2 * src]; k.y = xy[2 * src + 1]; k.angle = angle[i]; k.response = kresp[i]; k.octave = 0;
+    kps[i] = k;
+    h_kp[i] = k;
+  }
+  for (int i = tid; i < n * (BRISK_BYTES / 16); i += nth) h_desc[i] = desc[i];
 }
 
 }  // namespace spvo

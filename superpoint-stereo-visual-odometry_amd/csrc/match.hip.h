@@ -786,14 +786,15 @@ __global__ __launch_bounds__(256) void match_hamming_cross_kernel(const unsigned
 }
 
 // ---------------------------------------------------------------------------
-// K12t: the Hamming matcher for DEVICE-RESIDENT rows of 8 words (the binary feature slots of spvo_classic_detect) -- modes, tie rules
+// K12t: the Hamming matcher for DEVICE-RESIDENT rows (the binary feature slots of spvo_classic_detect), written for rows of 8 words
+// (this description) and instantiated for rows of 16 words too (the note above the kernel) -- modes, tie rules
 // and results of K12h (match_hamming_kernel stays for spvo_match_hamming), but built for rows that are already on the device:
 //   * both row counts are read from device memory, so the launch can be enqueued behind the detector before the host knows them; the
 //     grid comes from the slots' capacity and surplus workgroups exit at once.
-//   * register blocking: a wave keeps HAM_R = 8 query rows in registers (wave-uniform, 64 words: they live in scalar registers) and
+//   * register blocking: a wave keeps HAM_R<8> = 8 query rows in registers (wave-uniform, 64 words: they live in scalar registers) and
 //     scores every train row it reads against all eight, so a train row costs one LDS read per 8 distances instead of one global
 //     read per distance.
-//   * LDS staging: the workgroup (4 waves, HAM_QB = 16 query rows: two groups of eight) walks the train set in tiles of HAM_T = 256
+//   * LDS staging: the workgroup (4 waves, HAM_QB<8> = 16 query rows: two groups of eight) walks the train set in tiles of HAM_T = 256
 //     rows.  A tile is loaded from global memory ONCE per workgroup with 16-byte loads (thread = row, coalesced) and stored word-major
 //     ([8][256] words, 8 KB), so that a wave reading 64 consecutive rows of one word hits 64 different banks -- row-major rows of 32
 //     bytes would put lanes l and l + 8 on the same banks.  The next tile's global loads are issued before the current tile is scored and
@@ -805,7 +806,11 @@ __global__ __launch_bounds__(256) void match_hamming_cross_kernel(const unsigned
 //   * (distance, row) is ONE unsigned key, distance << 22 | row: ham_less's order (lower distance, then lower row) is the key's,
 //     and a lane's running best two are min / max / min.  Rows beyond the count get the key ~0, which decodes to "none".
 // ---------------------------------------------------------------------------
-constexpr int HAM_R = 8, HAM_QB = 16, HAM_T = 256, HAM_SHIFT = 22;
+constexpr int HAM_T = 256, HAM_SHIFT = 22;
+// rows of NW words: a wave keeps 64 words of query rows (HAM_R<8> = 8 rows, HAM_R<16> = 4), a workgroup twice that many rows
+template <int NW> constexpr int HAM_R = 64 / NW;
+template <int NW> constexpr int HAM_QB = 2 * HAM_R<NW>;
+static_assert(((512u << HAM_SHIFT) | ((1u << HAM_SHIFT) - 1)) < ~0u && (512u << HAM_SHIFT) >> HAM_SHIFT == 512u, "the largest distance of a 64-byte row (512) must fit above the row bits and stay below the ~0 sentinel");
 
 __device__ __forceinline__ void ham_top2(uint32_t &m0, uint32_t &m1, uint32_t k0, uint32_t k1) {   // merges the sorted pair (k0 <= k1) into (m0 <= m1)
   const uint32_t hi = max(m0, k0);
@@ -813,38 +818,56 @@ __device__ __forceinline__ void ham_top2(uint32_t &m0, uint32_t &m1, uint32_t k0
   m1 = min(hi, min(m1, k1));
 }
 
+// NW = 8: the 32-byte slots, as described above.
+// NW = 16 (K12t16): the 64-byte slots of the BRISK kinds.  Same modes, tie rules and packed output; what changes is the blocking:
+//   * registers: 64 wave-uniform words are what the scalar file holds comfortably, so a wave keeps FOUR query rows of 16 words (8 x 16
+//     would need 128 and spill); a workgroup covers 8 query rows (two groups of four, two waves per group, each scoring half a tile).
+//   * LDS: the tile is word-major [16][256], double buffered: 32 KB + the merge scratch, so FOUR workgroups fit the 160 KB of a CU (16
+//     waves, 4 per SIMD).  That is enough because the grid is problem-bound as for NW = 8: 4000 query rows are 500 workgroups on 256
+//     CUs, two per CU.  A row is loaded once per workgroup with four 16-byte loads (thread = row).
+//   * key: distance <= 512 and 512 << 22 | row <= 0x803FFFFF < ~0u, so the 32-bit key and its sentinel stay (static_assert above).
+//   * cost per distance: 16 x (xor + bit count with accumulate) on the vector unit against one 64-byte LDS row read per 4 distances:
+//     the kernel is bound by the vector ALU, not by LDS or L2 (kernel table).
+template <int NW>
 __global__ __launch_bounds__(256) void match_hamming_tiled_kernel(const uint32_t *__restrict__ A, const int *__restrict__ na_ptr, const uint32_t *__restrict__ B,
                                                                   const int *__restrict__ nb_ptr, int cap, int mode, float ratio, int2 *__restrict__ out,
                                                                   unsigned long long *__restrict__ vote) {
-  __shared__ uint32_t tile[2][8][HAM_T];
-  __shared__ uint32_t s_merge[2][HAM_R][2];
+  static_assert(NW == 8 || NW == 16, "rows of 8 or 16 words");
+  constexpr int R = HAM_R<NW>;
+  __shared__ uint32_t tile[2][NW][HAM_T];
+  __shared__ uint32_t s_merge[2][R][2];
   const int na = min(*na_ptr, cap), nb = min(*nb_ptr, cap);
-  const int q0 = blockIdx.x * HAM_QB;
+  const int q0 = blockIdx.x * HAM_QB<NW>;
   if (q0 >= na) return;   // (the whole workgroup: no barrier is skipped by part of it)
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int group = wave >> 1, half = wave & 1;
-  const int qg = q0 + group * HAM_R;
-  uint32_t a[HAM_R][8], m0[HAM_R], m1[HAM_R];
+  const int qg = q0 + group * R;
+  uint32_t a[R][NW], m0[R], m1[R];
 #pragma unroll
-  for (int r = 0; r < HAM_R; ++r) {
-    const uint32_t *row = A + (size_t)min(qg + r, na - 1) * 8;   // (rows past the end repeat the last one; they are not written)
+  for (int r = 0; r < R; ++r) {
+    const uint32_t *row = A + (size_t)min(qg + r, na - 1) * NW;   // (rows past the end repeat the last one; they are not written)
 #pragma unroll
-    for (int w = 0; w < 8; ++w) a[r][w] = row[w];
+    for (int w = 0; w < NW; ++w) a[r][w] = row[w];
     m0[r] = m1[r] = ~0u;
   }
   const int ntiles = (nb + HAM_T - 1) / HAM_T;
-  uint4 v0 = make_uint4(0, 0, 0, 0), v1 = v0;
+  uint4 v[NW / 4];
+#pragma unroll
+  for (int k = 0; k < NW / 4; ++k) v[k] = make_uint4(0, 0, 0, 0);
   auto fetch = [&](int t) {
     const int row = t * HAM_T + (int)threadIdx.x;
     if (row < nb) {
-      const uint4 *p = reinterpret_cast<const uint4 *>(B + (size_t)row * 8);
-      v0 = p[0]; v1 = p[1];
+      const uint4 *p = reinterpret_cast<const uint4 *>(B + (size_t)row * NW);
+#pragma unroll
+      for (int k = 0; k < NW / 4; ++k) v[k] = p[k];
     }
   };
   auto stage = [&](int buf) {
     uint32_t(*tb)[HAM_T] = tile[buf];
-    tb[0][threadIdx.x] = v0.x; tb[1][threadIdx.x] = v0.y; tb[2][threadIdx.x] = v0.z; tb[3][threadIdx.x] = v0.w;
-    tb[4][threadIdx.x] = v1.x; tb[5][threadIdx.x] = v1.y; tb[6][threadIdx.x] = v1.z; tb[7][threadIdx.x] = v1.w;
+#pragma unroll
+    for (int k = 0; k < NW / 4; ++k) {
+      tb[4 * k][threadIdx.x] = v[k].x; tb[4 * k + 1][threadIdx.x] = v[k].y; tb[4 * k + 2][threadIdx.x] = v[k].z; tb[4 * k + 3][threadIdx.x] = v[k].w;
+    }
   };
   if (ntiles > 0) { fetch(0); stage(0); }
   __syncthreads();
@@ -854,15 +877,15 @@ __global__ __launch_bounds__(256) void match_hamming_tiled_kernel(const uint32_t
 #pragma unroll
     for (int s = 0; s < HAM_T / 128; ++s) {
       const int r_in = half * (HAM_T / 2) + s * 64 + lane, grow = t * HAM_T + r_in;
-      uint32_t b[8];
+      uint32_t b[NW];
 #pragma unroll
-      for (int w = 0; w < 8; ++w) b[w] = tb[w][r_in];
+      for (int w = 0; w < NW; ++w) b[w] = tb[w][r_in];
       const bool valid = grow < nb;
 #pragma unroll
-      for (int r = 0; r < HAM_R; ++r) {
+      for (int r = 0; r < R; ++r) {
         uint32_t d = 0;
 #pragma unroll
-        for (int w = 0; w < 8; ++w) d += __popc(b[w] ^ a[r][w]);
+        for (int w = 0; w < NW; ++w) d += __popc(b[w] ^ a[r][w]);
         const uint32_t key = valid ? ((d << HAM_SHIFT) | (uint32_t)grow) : ~0u;
         ham_top2(m0[r], m1[r], key, ~0u);
       }
@@ -872,7 +895,7 @@ __global__ __launch_bounds__(256) void match_hamming_tiled_kernel(const uint32_t
   }
   // the wave's 64 pairs -> one, then the two halves of the tile through LDS
 #pragma unroll
-  for (int r = 0; r < HAM_R; ++r) {
+  for (int r = 0; r < R; ++r) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
       const uint32_t k0 = (uint32_t)__shfl_xor((int)m0[r], o), k1 = (uint32_t)__shfl_xor((int)m1[r], o);
@@ -881,12 +904,12 @@ __global__ __launch_bounds__(256) void match_hamming_tiled_kernel(const uint32_t
   }
   if (half == 1 && lane == 0) {
 #pragma unroll
-    for (int r = 0; r < HAM_R; ++r) { s_merge[group][r][0] = m0[r]; s_merge[group][r][1] = m1[r]; }
+    for (int r = 0; r < R; ++r) { s_merge[group][r][0] = m0[r]; s_merge[group][r][1] = m1[r]; }
   }
   __syncthreads();
   if (half == 1 || lane != 0) return;
 #pragma unroll
-  for (int r = 0; r < HAM_R; ++r) {
+  for (int r = 0; r < R; ++r) {
     const int q = qg + r;
     if (q >= na) break;
     ham_top2(m0[r], m1[r], s_merge[group][r][0], s_merge[group][r][1]);

@@ -1,5 +1,6 @@
 // spvo_brisk.hip -- the classic front end's BRISK descriptor extractor on given keypoints (brisk.hip.h): the pattern tables (built once
-// per process on the host, in double, by the formulas tests/brisk_ref.py lists), spvo_brisk_tables and spvo_brisk_describe.  Runs on the
+// per process on the host, in double, by the formulas tests/brisk_ref.py lists), spvo_brisk_tables, spvo_brisk_describe and the extractor
+// as a link of spvo_classic_detect's chain (brisk_chain_ensure / brisk_chain_enqueue).  Runs on the
 // solver's stream (stream2) on the image the Shi-Tomasi / FAST detectors and the ORB extractor keep resident (spvo_ctx::cls) and owns
 // everything else it needs (spvo_ctx::brisk).
 #include "spvo_internal.hip.h"
@@ -163,6 +164,31 @@ void spvo_int::brisk_release(spvo_ctx *c) {
   dev_free(k.points, k.long_pairs, k.short_pairs, k.cnt, k.integ, k.xy, k.size, k.angle, k.kept, k.kscale, k.values0, k.desc);
   host_free(k.h_n, k.h_kept, k.h_angle, k.h_desc, k.h_values0);
   k.integ_cap = 0; k.kp_cap = k.v0_cap = 0; k.tables_ready = false;
+}
+
+int spvo_int::brisk_chain_ensure(spvo_ctx *c, int rows, int cols, int cap) {
+  if (int rc = brisk_ensure_tables(c)) return rc;
+  return brisk_ensure(c, rows, cols, cap, false);
+}
+
+// spvo_brisk_describe's launches without its two host round trips: the keypoints are the detector's list where it lies (cls.xy, cls.resp,
+// cls.counters), the rows go straight into the slot.  kept / kscale / angle and the integral image are shared by the two images of a pair,
+// which is correct in stream order.
+int spvo_int::brisk_chain_enqueue(spvo_ctx *c, int rows, int cols, float size, int cap, int most, const BriskChainOut &o) {
+  auto &b = c->cls;
+  auto &k = c->brisk;
+  hipStream_t st = c->stream2;
+  uint8_t *desc = reinterpret_cast<uint8_t *>(o.d_desc);
+  hipLaunchKernelGGL(brisk_integral_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.im, rows, cols, k.integ);
+  hipLaunchKernelGGL(brisk_integral_cols_kernel, dim3((cols + 1 + 255) / 256), dim3(256), 0, st, rows, cols, k.integ);
+  hipLaunchKernelGGL(brisk_compact_list_kernel, dim3(1), dim3(1024), 0, st, b.xy, b.resp, b.counters, size, rows, cols, brisk_tables().params, cap, k.kept, k.kscale, o.kresp, o.cnt);
+  // (the describe kernel reads its row count at cnt[0]: handed cnt + 2, it describes min(kept, cap) rows)
+  hipLaunchKernelGGL(brisk_describe_kernel, dim3(std::min((std::max(most, 1) + 3) / 4, BRISK_DESCRIBE_BLOCKS)), dim3(256), 0, st, b.im, k.integ, rows, cols, b.xy, k.kept, k.kscale, o.cnt + 2, k.points,
+                     k.long_pairs, k.short_pairs, k.angle, desc, nullptr);
+  hipLaunchKernelGGL(brisk_slot_finish_kernel, dim3(32), dim3(256), 0, st, b.counters, o.cnt, b.xy, k.kept, k.angle, o.kresp, reinterpret_cast<const uint4 *>(desc), cap, o.d_kp, o.d_n, o.h_n, o.h_kp,
+                     reinterpret_cast<uint4 *>(o.h_desc));
+  HIP_TRY(c, hipGetLastError());
+  return SPVO_OK;
 }
 
 extern "C" {

@@ -1,5 +1,6 @@
 // spvo_classic.hip -- the classic front end (ClassicFeatureFrontEnd, feature_detection_classic.cpp): the ORB detector / extractor (orb.hip.h),
-// the Shi-Tomasi and FAST detectors and the ORB extractor for given keypoints (classic_detect.hip.h), and spvo_preprocess for a context
+// the Shi-Tomasi and FAST detectors and the ORB extractor for given keypoints (classic_detect.hip.h), one submission per stereo pair into the
+// binary feature slots (spvo_classic_detect; its BRISK kinds hand the detector's list to spvo_brisk.hip), and spvo_preprocess for a context
 // without an engine.  Everything here runs on the solver's stream (stream2) and owns its buffers (spvo_ctx::orb, spvo_ctx::cls).
 #include "spvo_internal.hip.h"
 #include "orb.hip.h"
@@ -453,7 +454,7 @@ void spvo_int::classic_release_slots(spvo_ctx *c) {
   auto &bb = c->bin;
   for (BinarySlot &s : bb.slots) {
     dev_free(s.d_kp, s.d_desc, s.d_n);
-    s.filled = false; s.n = 0; ++s.gen;
+    s.filled = false; s.n = 0; s.row_bytes = 32; ++s.gen;
   }
   dev_free(bb.d_cnt, bb.d_kxy, bb.d_kresp, bb.d_vote);
   for (void *p : {(void *)bb.h_kp, (void *)bb.h_desc, (void *)bb.h_n, (void *)bb.h_match}) if (p) (void)hipHostFree(p);
@@ -475,7 +476,11 @@ void spvo_int::classic_release(spvo_ctx *c) {
 extern "C" {
 
 namespace {
-// the binary slots and the call's own buffers for `cap` rows per slot and images of `px` bytes; growing un-fills every slot
+constexpr int BIN_ROW_BYTES_MAX = 64;   // the widest row a binary slot holds (BRISK); the ORB extractor's rows are 32 bytes
+inline bool kind_is_brisk(int kind) { return kind == SPVO_CLASSIC_GFTT_BRISK || kind == SPVO_CLASSIC_FAST_BRISK; }
+inline bool kind_is_gftt(int kind) { return kind == SPVO_CLASSIC_GFTT_ORB || kind == SPVO_CLASSIC_GFTT_BRISK; }
+// the binary slots and the call's own buffers for `cap` rows per slot and images of `px` bytes; growing un-fills every slot.  Every slot and
+// both mirrors are sized for 64-byte rows whatever kind asks first: a BRISK kind's first call must not empty the slots the ORB kinds filled
 int bin_ensure(spvo_ctx *c, int cap, size_t px) {
   auto &bb = c->bin;
   if (!bb.ev_feat) {
@@ -494,12 +499,12 @@ int bin_ensure(spvo_ctx *c, int cap, size_t px) {
   classic_release_slots(c);
   int rc;
   for (BinarySlot &s : bb.slots)
-    if ((rc = dev_alloc(c, &s.d_kp, cap)) || (rc = dev_alloc(c, &s.d_desc, (size_t)cap * 8)) || (rc = dev_alloc(c, &s.d_n, 1))) return rc;
+    if ((rc = dev_alloc(c, &s.d_kp, cap)) || (rc = dev_alloc(c, &s.d_desc, (size_t)cap * (BIN_ROW_BYTES_MAX / 4))) || (rc = dev_alloc(c, &s.d_n, 1))) return rc;
   if ((rc = dev_alloc(c, &bb.d_cnt, 2 * CLS_COUNTER_INTS)) || (rc = dev_alloc(c, &bb.d_kxy, (size_t)2 * cap)) || (rc = dev_alloc(c, &bb.d_kresp, cap)) ||
       (rc = dev_alloc(c, &bb.d_vote, cap)))
     return rc;
   HIP_TRY(c, hipHostMalloc((void **)&bb.h_kp, (size_t)2 * cap * sizeof(OrbKeypoint)));
-  HIP_TRY(c, hipHostMalloc((void **)&bb.h_desc, (size_t)2 * cap * 32));
+  HIP_TRY(c, hipHostMalloc((void **)&bb.h_desc, (size_t)2 * cap * BIN_ROW_BYTES_MAX));
   HIP_TRY(c, hipHostMalloc((void **)&bb.h_n, 2 * 4 * sizeof(int)));
   HIP_TRY(c, hipHostMalloc((void **)&bb.h_match, (size_t)3 * cap * sizeof(int2)));
   for (int k = 0; k < 2; ++k) bb.mcache[k].h_out = bb.h_match + (size_t)k * cap;
@@ -526,6 +531,34 @@ int spvo_classic_slot_rows(spvo_ctx *c, int slot, int *n) {
   return SPVO_OK;
 }
 
+// test hook: caller-supplied rows into a binary slot, as if a spvo_classic_detect call of that row width had left them there
+int spvo_classic_slot_fill_debug(spvo_ctx *c, int slot, const uint8_t *desc, int n, int desc_bytes) {
+  if (!c || slot < 0 || slot >= N_BIN_SLOTS || n < 0 || (n > 0 && !desc)) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  if (desc_bytes != 32 && desc_bytes != 64) return fail(c, SPVO_ERR_INVALID, "spvo_classic_slot_fill_debug: rows of 32 or 64 bytes (got %d)", desc_bytes);
+  if (int rc = require_idle(c)) return rc;
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  auto &bb = c->bin;
+  if (bb.cap == 0) {
+    spvo_classic_opts dflt;
+    spvo_default_classic_opts(&dflt, SPVO_CLASSIC_ORB);
+    if (int rc = bin_ensure(c, dflt.slot_capacity, 0)) return rc;
+  }
+  if (n > bb.cap) return fail(c, SPVO_ERR_INVALID, "spvo_classic_slot_fill_debug: %d rows do not fit slots of %d", n, bb.cap);
+  HIP_TRY(c, hipStreamSynchronize(c->stream2));   // (a prematch of the slot's old rows may still run)
+  BinarySlot &s = bb.slots[slot];
+  s.filled = false; s.n = 0; ++s.gen;
+  for (auto &mc : bb.mcache) mc.valid = false;
+  hipStream_t st = c->stream2;
+  if (n > 0) {
+    HIP_TRY(c, hipMemsetAsync(s.d_kp, 0, (size_t)n * sizeof(OrbKeypoint), st));
+    HIP_TRY(c, hipMemcpyAsync(s.d_desc, desc, (size_t)n * desc_bytes, hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(c, hipMemcpyAsync(s.d_n, &n, sizeof n, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  s.n = n; s.row_bytes = desc_bytes; s.filled = true;
+  return SPVO_OK;
+}
+
 int spvo_classic_detect(spvo_ctx *c, const spvo_classic_opts *opts, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int slot_l, int slot_r,
                         spvo_classic_features *out_l, spvo_classic_features *out_r) {
   if (!c || !opts || !img_l || !img_r || !out_l || !out_r || rows <= 0 || cols <= 0 || stride < (size_t)cols) return fail(c, SPVO_ERR_INVALID, "bad argument");
@@ -538,14 +571,17 @@ int spvo_classic_detect(spvo_ctx *c, const spvo_classic_opts *opts, const uint8_
   // what the per-image entry points refuse
   if (kind == SPVO_CLASSIC_ORB) {
     if (opts->nfeatures <= 0) return fail(c, SPVO_ERR_INVALID, "bad argument");
-  } else if (kind == SPVO_CLASSIC_GFTT_ORB) {
+  } else if (kind_is_gftt(kind)) {
     if (rows < 8 || cols < 8 || !(opts->quality_level > 0)) return fail(c, SPVO_ERR_INVALID, "bad argument");
     if (opts->block_size != 5 || !(opts->min_distance >= 0 && opts->min_distance <= 15)) return fail(c, SPVO_ERR_INVALID, "spvo_classic_detect: block_size 5 and min_distance <= 15 only");
-  } else if (kind == SPVO_CLASSIC_FAST_ORB) {
+  } else if (kind == SPVO_CLASSIC_FAST_ORB || kind == SPVO_CLASSIC_FAST_BRISK) {
     if (opts->fast_threshold < 0 || opts->fast_threshold > 255) return fail(c, SPVO_ERR_INVALID, "bad argument");
   } else {
     return fail(c, SPVO_ERR_INVALID, "unknown kind %d", kind);
   }
+  const bool brisk = kind_is_brisk(kind);
+  if (brisk && (long long)rows * cols * 255 >= (1ll << 31)) return fail(c, SPVO_ERR_INVALID, "spvo_classic_detect: %d x %d pixels do not fit the int32 integral image", rows, cols);
+  const int row_bytes = brisk ? 64 : 32;
   if (!c->pendq.empty()) return fail(c, SPVO_ERR_STATE, "detector submissions are in flight: complete them with spvo_detect_wait first");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   out_l->n = out_r->n = 0;
@@ -560,11 +596,11 @@ int spvo_classic_detect(spvo_ctx *c, const spvo_classic_opts *opts, const uint8_
     if (int rc = orb_prepare(c, rows, cols, opts->nfeatures, plan)) return rc;
   } else {
     if (int rc = cls_ensure(c, rows, cols)) return rc;
-    if (int rc = orb_ensure_tables(c)) return rc;
+    if (int rc = brisk ? brisk_chain_ensure(c, rows, cols, cap) : orb_ensure_tables(c)) return rc;   // (the BRISK tables: a one-off 47 MB upload, before the chain)
   }
   // both slots are being rewritten: whatever was matched against their old contents is stale
   const int slots[2] = {slot_l, slot_r};
-  for (int sl : slots) { BinarySlot &s = bb.slots[sl]; s.filled = false; s.n = 0; ++s.gen; }
+  for (int sl : slots) { BinarySlot &s = bb.slots[sl]; s.filled = false; s.n = 0; s.row_bytes = row_bytes; ++s.gen; }
   for (auto &mc : bb.mcache) mc.valid = false;
   // pinned staging: both images with packed rows (of a strided view only the rows' own bytes are the caller's), one upload each
   HIP_TRY(c, hipStreamSynchronize(st));   // (the staging buffer and the mirrors are the previous call's until its work is done)
@@ -575,7 +611,7 @@ int spvo_classic_detect(spvo_ctx *c, const spvo_classic_opts *opts, const uint8_
     BinarySlot &s = bb.slots[slots[k]];
     int *h_n = bb.h_n + 4 * k;
     OrbKeypoint *h_kp = bb.h_kp + (size_t)k * cap;
-    uint4 *h_desc = reinterpret_cast<uint4 *>(bb.h_desc + (size_t)k * cap * 32);
+    uint4 *h_desc = reinterpret_cast<uint4 *>(bb.h_desc + (size_t)k * cap * row_bytes);
     if (kind == SPVO_CLASSIC_ORB) {
       HIP_TRY(c, hipMemcpyAsync(o.im, bb.h_img + k * px, px, hipMemcpyHostToDevice, st));
       const int kp_cap = std::min(opts->nfeatures, cap);   // (more than `cap` rows are an error below: the slot need not hold them)
@@ -586,14 +622,21 @@ int spvo_classic_detect(spvo_ctx *c, const spvo_classic_opts *opts, const uint8_
       b.rows = b.cols = 0;
       HIP_TRY(c, hipMemcpyAsync(b.im, bb.h_img + k * px, px, hipMemcpyHostToDevice, st));
       b.rows = rows; b.cols = cols;
-      if (int rc = kind == SPVO_CLASSIC_GFTT_ORB ? gftt_enqueue(c, rows, cols, opts->max_corners, opts->quality_level, opts->min_distance)
+      if (int rc = kind_is_gftt(kind) ? gftt_enqueue(c, rows, cols, opts->max_corners, opts->quality_level, opts->min_distance)
                                                  : fast_enqueue(c, rows, cols, opts->fast_threshold, opts->fast_nonmax))
         return rc;
       // detector -> extractor on the device: the border rule as an order-preserving compaction, then orb.hip.h's extractor on a one-level
       // OrbLevels whose keypoint list is the compacted one and whose count is the compaction's (spvo_orb_describe, without the host)
       int *cnt = bb.d_cnt + k * CLS_COUNTER_INTS;
+      const int most = kind_is_gftt(kind) && opts->max_corners > 0 ? std::min(cap, opts->max_corners) : cap;   // rows the extractor's grid covers
+      if (brisk) {
+        // the same hand-over to the BRISK extractor: its border rule (keypoint size 5 / 7, what detectKeypoints assigns) and the rest of
+        // spvo_brisk_describe's launches, 64-byte rows
+        const BriskChainOut bo{cnt, bb.d_kresp, s.d_kp, s.d_desc, s.d_n, h_n, h_kp, reinterpret_cast<uint8_t *>(h_desc)};
+        if (int rc = brisk_chain_enqueue(c, rows, cols, kind_is_gftt(kind) ? 5.0f : 7.0f, cap, most, bo)) return rc;
+        continue;
+      }
       hipLaunchKernelGGL(cls_compact_kernel, dim3(1), dim3(1024), 0, st, b.xy, b.resp, b.counters, rows, cols, ORB_EDGE, bb.d_kxy, bb.d_kresp, cap, cnt);
-      const int most = kind == SPVO_CLASSIC_GFTT_ORB && opts->max_corners > 0 ? std::min(cap, opts->max_corners) : cap;   // rows the extractor's grid covers
       OrbLevels lv{};
       OrbLevel &L = lv.l[0];
       L.im = b.im; L.score = b.score; L.blur = b.blur; L.tmp = b.tmp; L.out_xy = bb.d_kxy; L.counters = cnt;
@@ -611,7 +654,8 @@ int spvo_classic_detect(spvo_ctx *c, const spvo_classic_opts *opts, const uint8_
   // spvo_set_prematch: the two standard matches behind the features, counts read on the device (a pair that turns out not to fit its
   // slots is matched on whatever rows the slots hold; that result is dropped below)
   const int prev_l = bb.last_slot_l;
-  const bool temporal = prev_l >= 0 && prev_l != slot_l && prev_l != slot_r && bb.slots[prev_l].filled;
+  // (a previous left slot of the other row width has no temporal match: skipped, the synchronous call reports the widths when asked)
+  const bool temporal = prev_l >= 0 && prev_l != slot_l && prev_l != slot_r && bb.slots[prev_l].filled && bb.slots[prev_l].row_bytes == row_bytes;
   if (c->prematch) {
     if (int rc = enqueue_hamming_slots(c, slot_l, slot_r, c->pm_selector, c->pm_cross, c->pm_ratio, bb.mcache[0].h_out)) return rc;
     if (temporal)
@@ -633,7 +677,7 @@ int spvo_classic_detect(spvo_ctx *c, const spvo_classic_opts *opts, const uint8_
     s.n = outs[k]->n; s.filled = true;
     const int ncopy = std::min(s.n, outs[k]->cap);
     if (ncopy > 0 && outs[k]->kp) std::memcpy(outs[k]->kp, bb.h_kp + (size_t)k * cap, (size_t)ncopy * sizeof(OrbKeypoint));
-    if (ncopy > 0 && outs[k]->desc) std::memcpy(outs[k]->desc, bb.h_desc + (size_t)k * cap * 32, (size_t)ncopy * 32);
+    if (ncopy > 0 && outs[k]->desc) std::memcpy(outs[k]->desc, bb.h_desc + (size_t)k * cap * row_bytes, (size_t)ncopy * row_bytes);
   }
   if (c->prematch) {
     const BinarySlot &l = bb.slots[slot_l];

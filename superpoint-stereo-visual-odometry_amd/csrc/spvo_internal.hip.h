@@ -112,7 +112,8 @@ struct BinarySlot {
   int n = 0;
   bool filled = false;
   OrbKeypoint *d_kp = nullptr;   // [cap] x, y, angle, response, octave
-  uint32_t *d_desc = nullptr;    // [cap][8] the matcher's row format: 32 bytes are 8 words, nothing to pad
+  uint32_t *d_desc = nullptr;    // [cap][16] allocated for the widest row; the matcher's row format: row_bytes / 4 words back to back, nothing to pad
+  int row_bytes = 32;            // width of the rows it holds: 32 (the ORB extractor) or 64 (BRISK); two slots are matched only at one width
   int *d_n = nullptr;            // device copy of n (read by kernels enqueued before the host knows n)
   unsigned long long gen = 0;    // bumped whenever the slot is rewritten
 };
@@ -346,11 +347,11 @@ struct spvo_ctx {
     uint8_t *h_img = nullptr;            // pinned [2][img_cap]: both images of a call, rows packed
     size_t img_cap = 0;
     OrbKeypoint *h_kp = nullptr;         // pinned [2][cap]      what the finishing kernel of an image writes for the host:
-    uint8_t *h_desc = nullptr;           // pinned [2][cap][32]  keypoint records, descriptors,
+    uint8_t *h_desc = nullptr;           // pinned [2][cap][64]  keypoint records, descriptors ([2][cap][32] in its front part for the 32-byte kinds),
     int *h_n = nullptr;                  // pinned [2][4]        {rows found, overflow flag of the detector}
     int *d_cnt = nullptr;                // [2][CLS_COUNTER_INTS] the extractor's counter block per image (0: kept in all, 2: kept and described)
     int *d_kxy = nullptr;                // [cap][2] the kept keypoints of a Shi-Tomasi / FAST image (cls_compact_kernel), ...
-    float *d_kresp = nullptr;            // [cap]    ... and the detector's responses of those
+    float *d_kresp = nullptr;            // [cap]    ... and the detector's responses of those (also brisk_compact_list_kernel's)
     unsigned long long *d_vote = nullptr;   // [cap] cross-check votes
     int2 *h_match = nullptr;             // pinned [3][cap]: the two prematches, the synchronous call
     MatchCache mcache[2];                // [stereo, temporal]: slot numbers are BINARY slots
@@ -586,6 +587,19 @@ void classic_release_slots(spvo_ctx *c);   // ... the part of it that is sized b
 int classic_upload_image(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride);
 // ---- spvo_brisk.hip
 void brisk_release(spvo_ctx *c);     // frees spvo_ctx::brisk (spvo_destroy)
+// The extractor as a link of spvo_classic_detect's chain (kinds SPVO_CLASSIC_*_BRISK).  brisk_chain_ensure: the tables, the integral image
+// of a rows x cols image and the keypoint buffers for `cap` rows.  brisk_chain_enqueue, on the solver's stream behind a detector that left
+// its list in spvo_ctx::cls (xy, resp, counters[2]): integral image, border rule of keypoints of ONE `size` as a compaction that keeps at
+// most `cap` rows and counts all, descriptors of at most `most` <= cap rows into the slot, and the finish launch -- records, rows and
+// count of the slot, and their pinned mirrors (h_n = {rows that passed the border rule, overflow flag of the detector}).
+int brisk_chain_ensure(spvo_ctx *c, int rows, int cols, int cap);
+struct BriskChainOut {
+  int *cnt;               // [CLS_COUNTER_INTS] 0: kept in all, 2: kept and described
+  float *kresp;           // [cap] the detector's responses of the kept
+  OrbKeypoint *d_kp; uint32_t *d_desc; int *d_n;          // the slot
+  int *h_n; OrbKeypoint *h_kp; uint8_t *h_desc;           // its pinned mirrors
+};
+int brisk_chain_enqueue(spvo_ctx *c, int rows, int cols, float size, int cap, int most, const BriskChainOut &o);
 // ---- spvo_sift.hip
 void sift_release(spvo_ctx *c);      // frees spvo_ctx::sift (spvo_destroy)
 void sift_invalidate_matches(spvo_ctx *c);   // the stored prematches of the SIFT slots are stale (spvo_set_prematch, spvo_set_match_fp8)

@@ -156,7 +156,8 @@ int run_match(spvo_ctx *c, const MatchReq &r, int selector, int cross_check, flo
   return SPVO_OK;
 }
 
-// One Hamming match between two binary slots on the solver's stream, counts read on the device (match.hip.h K12t): the packed result
+// One Hamming match between two binary slots OF ONE ROW WIDTH on the solver's stream, counts read on the device (match.hip.h K12t, by the
+// slots' width the instantiation for 8 or for 16 words): the packed result
 // {train_idx, distance bits} of every row of slot_a lands in `host_out` (pinned).  NN + cross-check is cv::batchDistance's crosscheck as in
 // spvo_match_hamming: the train rows vote for their nearest query row, then every query row reads its vote.
 int enqueue_hamming_slots(spvo_ctx *c, int slot_a, int slot_b, int selector, int cross_check, float ratio, int2 *host_out) {
@@ -165,13 +166,20 @@ int enqueue_hamming_slots(spvo_ctx *c, int slot_a, int slot_b, int selector, int
   const BinarySlot &a = bb.slots[slot_a], &b = bb.slots[slot_b];
   hipStream_t st = c->stream2;
   const int cap = bb.cap;
-  const dim3 grid((cap + HAM_QB - 1) / HAM_QB);
+  if (a.row_bytes != b.row_bytes)
+    return fail(c, SPVO_ERR_INVALID, "binary slot %d holds rows of %d bytes, slot %d rows of %d bytes: only slots of one width are matched", slot_a, a.row_bytes, slot_b, b.row_bytes);
+  const bool wide = a.row_bytes == 64;
+  const dim3 grid(wide ? (cap + HAM_QB<16> - 1) / HAM_QB<16> : (cap + HAM_QB<8> - 1) / HAM_QB<8>);
+  auto launch = [&](const BinarySlot &q, const BinarySlot &t, int mode) {
+    if (wide) hipLaunchKernelGGL(match_hamming_tiled_kernel<16>, grid, dim3(256), 0, st, q.d_desc, q.d_n, t.d_desc, t.d_n, cap, mode, ratio, host_out, bb.d_vote);
+    else hipLaunchKernelGGL(match_hamming_tiled_kernel<8>, grid, dim3(256), 0, st, q.d_desc, q.d_n, t.d_desc, t.d_n, cap, mode, ratio, host_out, bb.d_vote);
+  };
   if (cross_check && selector == SPVO_SELECT_NN) {   // BFMatcher's crossCheck is off for knnMatch (base.cpp:27-28)
     HIP_TRY(c, hipMemsetAsync(bb.d_vote, 0xFF, (size_t)cap * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(match_hamming_tiled_kernel, grid, dim3(256), 0, st, b.d_desc, b.d_n, a.d_desc, a.d_n, cap, 2, ratio, host_out, bb.d_vote);
+    launch(b, a, 2);
     hipLaunchKernelGGL(match_hamming_cross_slots_kernel, dim3((cap + 255) / 256), dim3(256), 0, st, bb.d_vote, a.d_n, cap, host_out);
   } else {
-    hipLaunchKernelGGL(match_hamming_tiled_kernel, grid, dim3(256), 0, st, a.d_desc, a.d_n, b.d_desc, b.d_n, cap, selector == SPVO_SELECT_KNN ? 1 : 0, ratio, host_out, bb.d_vote);
+    launch(a, b, selector == SPVO_SELECT_KNN ? 1 : 0);
   }
   HIP_TRY(c, hipGetLastError());
   return SPVO_OK;
@@ -305,6 +313,8 @@ int spvo_match_hamming_slots(spvo_ctx *c, int slot_a, int slot_b, int selector, 
   auto &bb = c->bin;
   const BinarySlot &a = bb.slots[slot_a], &b = bb.slots[slot_b];
   if (!a.filled || !b.filled) return fail(c, SPVO_ERR_STATE, "binary slot %d holds no features (spvo_classic_detect fills it)", a.filled ? slot_b : slot_a);
+  if (a.row_bytes != b.row_bytes)
+    return fail(c, SPVO_ERR_INVALID, "binary slot %d holds rows of %d bytes, slot %d rows of %d bytes: only slots of one width are matched", slot_a, a.row_bytes, slot_b, b.row_bytes);
   if (a.n > 0 && (!train_idx || !distance)) return fail(c, SPVO_ERR_INVALID, "null output");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   const int cross = cross_check ? 1 : 0;

@@ -519,7 +519,9 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
 // (the default constructor) and FAST + ORB go through spvo_gftt_detect / spvo_fast_detect and spvo_orb_describe (classic.cpp:32-47,
 // 66-68, 110-111); the image stays on the device between the two.  SIFT + SIFT goes through spvo_sift_detect, one pass like ORB: float
 // descriptors (n x 128 CV_32F), matched with NORM_L2 by spvo_match_l2.  ShiTomasi + BRISK and FAST + BRISK go through the same detectors and
-// spvo_brisk_describe (cv::BRISK::create(30, 3, 1.0f)->compute, classic.cpp:56-65): 64-byte rows, matched with NORM_HAMMING.  The BRISK
+// spvo_brisk_describe (cv::BRISK::create(30, 3, 1.0f)->compute, classic.cpp:56-65): 64-byte rows, matched with NORM_HAMMING.  With
+// setDeviceResident every one of these pairs is one submission per stereo pair instead (spvo_classic_detect, kinds 0 .. 4, or
+// spvo_sift_detect_pair) and is matched in its slots -- the BRISK pairs by the 64-byte instantiation of the slot matcher.  The BRISK
 // detector and AKAZE are OpenCV features2d calls and stay unavailable, and so does every other mix (SIFT keypoints with an ORB descriptor, ...).
 bool ClassicFeatureFrontEnd::available() { return true; }
 static bool classic_detector_runs(DetectorType d) { return d == DetectorType::ORB || d == DetectorType::ShiTomasi || d == DetectorType::FAST; }
@@ -718,8 +720,7 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
     preprocessImageImpl(img_l, projection_matrix_l_);
     preprocessImageImpl(img_r, projection_matrix_r_);
   }
-  // (setDeviceResident with a BRISK descriptor: the binary slots hold 32-byte rows, so the pair takes the per-image path)
-  if (!resident_ || descriptor_type_ == DescriptorType::BRISK || !addStereoImagePairResident(img_l, img_r)) {
+  if (!resident_ || !addStereoImagePairResident(img_l, img_r)) {
     cv::Mat *imgs[2] = {&img_l, &img_r};
     for (cv::Mat *im : imgs) {
       images_dq.push_back(*im);
@@ -757,6 +758,7 @@ bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &img_l, cv::Mat 
       if (rc != SPVO_ERR_CAPACITY) logError(std::string("spvo_sift_detect_pair: ") + spvo_last_error(ctx_));
       return false;
     }
+    ++resident_ok_pairs_;
     cv::Mat *imgs[2] = {&img_l, &img_r};
     for (int k = 0; k < 2; ++k) {
       const int n = f[k].n;
@@ -781,13 +783,15 @@ bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &img_l, cv::Mat 
   }
   spvo_classic_opts opts;
   const bool orb = detector_type_ == DetectorType::ORB, gftt = detector_type_ == DetectorType::ShiTomasi;
-  spvo_default_classic_opts(&opts, orb ? SPVO_CLASSIC_ORB : gftt ? SPVO_CLASSIC_GFTT_ORB : SPVO_CLASSIC_FAST_ORB);
+  const bool brisk = classic_brisk_pair(detector_type_, descriptor_type_);
+  const size_t row_bytes = brisk ? 64 : 32;
+  spvo_default_classic_opts(&opts, orb ? SPVO_CLASSIC_ORB : brisk ? (gftt ? SPVO_CLASSIC_GFTT_BRISK : SPVO_CLASSIC_FAST_BRISK) : gftt ? SPVO_CLASSIC_GFTT_ORB : SPVO_CLASSIC_FAST_ORB);
   opts.slot_capacity = resident_capacity_;
   if (resident_pairs_ == 0) spvo_set_prematch(ctx_, 1, selector_type_ == SelectorType::KNN ? SPVO_SELECT_KNN : SPVO_SELECT_NN, matcher_cross_check_ ? 1 : 0, knn_threshold_);
   const int cap = std::max(resident_capacity_, 1);
   spvo_classic_features f[2];
   for (int k = 0; k < 2; ++k) {
-    if (resident_kp_[k].size() != (size_t)cap) { resident_kp_[k].resize((size_t)cap); resident_desc_[k].resize((size_t)cap * 32); }   // first pair only
+    if (resident_kp_[k].size() != (size_t)cap) { resident_kp_[k].resize((size_t)cap); resident_desc_[k].resize((size_t)cap * row_bytes); }   // first pair only
     f[k] = spvo_classic_features{0, resident_kp_[k].data(), resident_desc_[k].data(), cap};
   }
   const int slot_l = 2 * (int)(resident_pairs_ % 4), slot_r = slot_l + 1;
@@ -797,6 +801,7 @@ bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &img_l, cv::Mat 
     if (rc != SPVO_ERR_CAPACITY) logError(std::string("spvo_classic_detect: ") + spvo_last_error(ctx_));
     return false;
   }
+  ++resident_ok_pairs_;
   float level_scale[8];
   level_scale[0] = 1.f;
   for (int l = 1; l < 8; ++l) level_scale[l] = level_scale[l - 1] * 1.2f;
@@ -809,14 +814,18 @@ bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &img_l, cv::Mat 
       const spvo_orb_keypoint &p = resident_kp_[k][i];
       // size: 31 x the level's scale (ORB) / KeyPoint::convert(corners, keypoints, blockSize) / KeyPoint(x, y, 7.f, -1, score), as detectKeypoints
       cv::KeyPoint q(cv::Point2f(p.x, p.y), orb ? 31.f * level_scale[p.octave & 7] : gftt ? 5.f : 7.f);
-      q.angle = p.angle * 57.29577951308232f;   // cv::KeyPoint::angle is in degrees
-      if (q.angle < 0) q.angle += 360.f;
+      if (brisk) {
+        q.angle = p.angle;   // BRISK reports degrees, 0 .. 360: taken as it is, as describeKeypoints does
+      } else {
+        q.angle = p.angle * 57.29577951308232f;   // cv::KeyPoint::angle is in degrees
+        if (q.angle < 0) q.angle += 360.f;
+      }
       q.response = p.response;
       q.octave = p.octave;
       keypoints.push_back(q);
     }
-    cv::Mat d(n, 32, CV_8UC1);
-    if (n) std::memcpy(d.ptr<uint8_t>(0), resident_desc_[k].data(), (size_t)n * 32);
+    cv::Mat d(n, (int)row_bytes, CV_8UC1);
+    if (n) std::memcpy(d.ptr<uint8_t>(0), resident_desc_[k].data(), (size_t)n * row_bytes);
     images_dq.push_back(*imgs[k]);
     keypoints_dq.push_back(std::move(keypoints));
     descriptors_dq.push_back(d);

@@ -332,9 +332,12 @@ static uint64_t digest_ints(const std::vector<int> &a, const std::vector<int> &b
   return h;
 }
 
+static int g_classic_resident_pairs = 0;   // ClassicFeatureFrontEnd::residentPairs() of the last classic_sequence_run
+
 static int classic_sequence_run(const char *detector_name, const char *descriptor_name, int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l,
                                 const double *P_r, int knn, int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats,
                                 double *seconds, int input_height, int input_width, uint64_t *digest) {
+  g_classic_resident_pairs = 0;
   if (!detector_name || !detector_name_to_type.count(detector_name)) return -1000000;
   // descriptor_name NULL: "SIFT" means SIFT keypoints with SIFT descriptors (NORM_L2), every other detector goes with the ORB extractor
   const bool sift = detector_name_to_type.at(detector_name) == DetectorType::SIFT;
@@ -351,6 +354,7 @@ static int classic_sequence_run(const char *detector_name, const char *descripto
     std::memcpy(pl.data, P_l, 12 * sizeof(double));
     std::memcpy(pr.data, P_r, 12 * sizeof(double));
     fe.addStereoImagePair(l, r, pl, pr);
+    g_classic_resident_pairs = (int)fe.residentPairs();
     if (fe.keypoints_dq.size() < 2) return -(k + 1);
     fe.matchDescriptors(CURR_LEFT_CURR_RIGHT);
     double *p = poses + 7 * k;
@@ -406,6 +410,10 @@ int spvo_host_classic_sequence_desc(const char *detector_name, const char *descr
   return classic_sequence_run(detector_name, descriptor_name, n, imgs_l, imgs_r, rows, cols, P_l, P_r, knn, cross_check, stereo_threshold, refinement_degree, warm, poses, stats, seconds,
                               input_height, input_width, digest);
 }
+
+// pairs of the last spvo_host_classic_sequence_* run that stayed resident on the device (0 with setDeviceResident off; fewer than the
+// frames when pairs fell back to the per-image path)
+int spvo_host_classic_resident_pairs() { return g_classic_resident_pairs; }
 
 // ClassicFeatureFrontEnd::setDeviceResident / setResidentCapacity for the front ends constructed afterwards (capacity <= 0: unchanged)
 void spvo_host_classic_set_resident(int on, int capacity) {

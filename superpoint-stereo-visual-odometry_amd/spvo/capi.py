@@ -34,7 +34,8 @@ class ClassicFeatures(C.Structure):
     _fields_ = [("n", C.c_int), ("kp", C.c_void_p), ("desc", C.c_void_p), ("cap", C.c_int)]
 
 
-CLASSIC_KINDS = {"ORB": 0, "ShiTomasi": 1, "GFTT": 1, "FAST": 2}
+CLASSIC_KINDS = {"ORB": 0, "ShiTomasi": 1, "GFTT": 1, "FAST": 2, "ShiTomasi+BRISK": 3, "GFTT+BRISK": 3, "FAST+BRISK": 4}
+CLASSIC_BRISK_KINDS = (3, 4)          # spvo_classic_kind values whose rows are 64 bytes
 
 
 class SiftFeatures(C.Structure):
@@ -80,7 +81,7 @@ SYMBOLS = [
     "spvo_default_config", "spvo_create", "spvo_destroy", "spvo_last_error", "spvo_load_weights", "spvo_engine_precision", "spvo_set_fp32_split",
     "spvo_preprocess", "spvo_forward", "spvo_debug_tensor", "spvo_heatmap", "spvo_nms",
     "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8",
-    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_detect_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
+    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_detect_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
     "spvo_profile_enable", "spvo_profile_reset", "spvo_profile_only", "spvo_profile_count", "spvo_profile_get", "spvo_profile_stage_kernel",
     "spvo_set_tuning", "spvo_get_tuning", "spvo_clear_tuning",
     "spvo_comm_unique_id", "spvo_comm_available", "spvo_comm_create", "spvo_comm_create_host", "spvo_comm_rank", "spvo_comm_world", "spvo_comm_destroy",
@@ -151,6 +152,7 @@ def load() -> C.CDLL:
     lib.spvo_default_classic_opts.restype = None
     lib.spvo_classic_detect.argtypes = [vp, C.POINTER(ClassicOpts), vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.POINTER(ClassicFeatures), C.POINTER(ClassicFeatures)]
     lib.spvo_classic_slot_rows.argtypes = [vp, C.c_int, ip]
+    lib.spvo_classic_slot_fill_debug.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int]
     lib.spvo_match_hamming_slots.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]
     lib.spvo_triangulate.argtypes = [vp, dp, dp, vp, vp, C.c_int, vp]
     lib.spvo_pnp_ransac.argtypes = [vp, dp, vp, vp, C.c_int, C.POINTER(RansacOpts), dp, dp, vp, ip, ip]
@@ -581,9 +583,11 @@ class Context:
         return idx, dist
 
     def classic_detect(self, img_l, img_r, slot_l: int, slot_r: int, kind="ORB", **opts):
-        """One stereo pair through the classic front end's detector + ORB extractor into two binary feature slots (spvo_classic_detect).
-        kind "ORB", "ShiTomasi" or "FAST"; opts: fields of spvo_classic_opts that differ from the reference's parameters.
-        -> (left, right): dicts of xy [n,2], angle, response, octave, desc [n,32] -- the host's copy of what the slots hold.
+        """One stereo pair through the classic front end's detector + extractor into two binary feature slots (spvo_classic_detect).
+        kind "ORB", "ShiTomasi" or "FAST" (ORB extractor), "ShiTomasi+BRISK" or "FAST+BRISK"; opts: fields of spvo_classic_opts that differ
+        from the reference's parameters.
+        -> (left, right): dicts of xy [n,2], angle (radians; degrees for the BRISK kinds), response, octave, desc [n,32] ([n,64] for the BRISK
+        kinds) -- the host's copy of what the slots hold.
         On SPVO_ERR_CAPACITY the SpvoError carries the two counts as .counts."""
         o = ClassicOpts()
         self.lib.spvo_default_classic_opts(C.byref(o), CLASSIC_KINDS[kind] if isinstance(kind, str) else int(kind))
@@ -600,7 +604,7 @@ class Context:
         bufs, feats = [], []
         for _ in range(2):
             kp = np.zeros((cap, 5), np.float32)          # x, y, angle, response, octave (int32 bits)
-            desc = np.zeros((cap, 32), np.uint8)
+            desc = np.zeros((cap, 64 if o.kind in CLASSIC_BRISK_KINDS else 32), np.uint8)
             bufs.append((kp, desc))
             feats.append(ClassicFeatures(0, kp.ctypes.data, desc.ctypes.data, cap))
         rc = self.lib.spvo_classic_detect(self.h, C.byref(o), _ptr(l), _ptr(r), l.shape[0], l.shape[1], l.strides[0], slot_l, slot_r, C.byref(feats[0]), C.byref(feats[1]))
@@ -618,6 +622,13 @@ class Context:
         n = C.c_int(0)
         self._check(self.lib.spvo_classic_slot_rows(self.h, slot, C.byref(n)))
         return n.value
+
+    def classic_slot_fill(self, slot: int, desc: np.ndarray) -> None:
+        """Caller-supplied rows [n,32] or [n,64] u8 into a binary feature slot (spvo_classic_slot_fill_debug, a test hook)."""
+        desc = np.ascontiguousarray(desc, np.uint8)
+        if desc.ndim != 2:
+            raise ValueError("rows of 32 or 64 bytes expected: a 2-D array")
+        self._check(self.lib.spvo_classic_slot_fill_debug(self.h, slot, _ptr(desc) if len(desc) else None, len(desc), desc.shape[1]))
 
     def match_hamming_slots(self, slot_a: int, slot_b: int, selector="KNN", cross_check=False, ratio=0.8):
         """cv::BFMatcher(NORM_HAMMING) between two binary feature slots, on the device (spvo_match_hamming_slots)."""

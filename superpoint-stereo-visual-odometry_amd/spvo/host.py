@@ -344,12 +344,12 @@ class FrontEnd:
 def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_threshold=2.0, refinement_degree=4, warm=0, detector="ORB", input_size=None, resident=False,
                      resident_capacity=0, trace=False, descriptor="ORB"):
     """stereoCallback replayed on ClassicFeatureFrontEnd(detector, descriptor, BF, ...) (node.cpp:353-360) over host image pairs -- detector
-    "ORB", "ShiTomasi" or "FAST" with descriptor "ORB", "ShiTomasi" or "FAST" with descriptor "BRISK" (64-byte rows; with `resident` such a run
-    takes the per-image path), or detector "SIFT" (SIFT descriptors whatever `descriptor` says, as before); input_size None: at their native resolution, (height, width): through preprocessImageImpl first
+    "ORB", "ShiTomasi" or "FAST" with descriptor "ORB", "ShiTomasi" or "FAST" with descriptor "BRISK" (64-byte rows), or detector "SIFT" (SIFT descriptors whatever `descriptor` says, as before); input_size None: at their native resolution, (height, width): through preprocessImageImpl first
     (classic.cpp:96-100).  Returns (poses [n, 7] = q xyzw + t of cam0_curr_T_cam0_prev, stats [n, 4] = keypoints L, R, stereo
     matches, PnP inliers, seconds spent on frames warm .. n-1).
-    resident: ClassicFeatureFrontEnd::setDeviceResident for this run -- one spvo_classic_detect per pair, features and matching stay on the
-    device (resident_capacity > 0: rows per binary slot; a pair that does not fit falls back to the per-image path).
+    resident: ClassicFeatureFrontEnd::setDeviceResident for this run -- one spvo_classic_detect (SIFT: spvo_sift_detect_pair) per pair, features
+    and matching stay on the device, for every pair named above, BRISK included (resident_capacity > 0: rows per slot; a pair that does not
+    fit falls back to the per-image path; classic_resident_pairs() tells how many pairs of the run stayed resident).
     trace: a fourth value, digests [n, 8] uint64 of what every frame left in the front end (keypoints L, descriptors L, keypoints R,
     descriptors R, stereo matches, temporal matches, the previous frame's stereo matches + map, the inlier sets): equal digests = identical
     contents.  The digests are computed inside the timed loop, so `seconds` of a traced run is not a frame-rate figure."""
@@ -393,6 +393,15 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     if trace:
         return poses, stats, sec.value, digest
     return poses, stats, sec.value
+
+
+def classic_resident_pairs():
+    """Pairs of the last classic_sequence() run that stayed resident on the device (spvo_host_classic_resident_pairs): 0 without `resident`,
+    every frame when all fitted their slots, fewer when pairs fell back to the per-image path."""
+    lib = load()
+    lib.spvo_host_classic_resident_pairs.restype = C.c_int
+    lib.spvo_host_classic_resident_pairs.argtypes = []
+    return int(lib.spvo_host_classic_resident_pairs())
 
 
 def classic_default_probe(img_l, img_r, P_l, P_r):

@@ -4,6 +4,9 @@ python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST] [--descri
     ClassicFeatureFrontEnd(detector, descriptor, BF, KNN) over the synthetic stream: frames/s of the synchronous stereoCallback
     (--descriptor BRISK: with --detector ShiTomasi or FAST);
     --resident: with ClassicFeatureFrontEnd::setDeviceResident (one spvo_classic_detect per pair, matching on the binary slots).
+python tools/classic_bench.py [frames] --detector ShiTomasi|FAST|ORB --descriptor ORB|BRISK --ab ROUNDS
+    the same stream with setDeviceResident off and on, alternating, ROUNDS times each in one process: ms per pair of every run, the median
+    and the min .. max spread of each setting, and how many pairs of a resident run stayed resident.
 python tools/classic_bench.py --detectors [--calls 200] [--warmup 20]
     per image at 1241 x 376: spvo_orb_detect (the yardstick, same run) beside spvo_gftt_detect + spvo_orb_describe and
     spvo_fast_detect + spvo_orb_describe -- median, 10th / 90th percentile of the synchronous calls, keypoints, and how the
@@ -36,6 +39,7 @@ ap.add_argument("--detector", default="ORB")
 ap.add_argument("--descriptor", default="ORB")
 ap.add_argument("--detectors", action="store_true")
 ap.add_argument("--resident", action="store_true")
+ap.add_argument("--ab", type=int, default=0)
 ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "orb_describe", "match", "match_slots"])
 ap.add_argument("--selector", default="KNN", choices=["NN", "KNN"])
 ap.add_argument("--cross", action="store_true")
@@ -113,6 +117,22 @@ if args.detectors or args.leg:
         print("%-40s %d x %d: median %.3f ms (p10 %.3f, p90 %.3f) over %d calls, %d described keypoints / matches%s" % (name, img.shape[1], img.shape[0], np.median(ts), np.percentile(ts, 10),
                                                                                                       np.percentile(ts, 90), args.calls, n, extra))
     ctx.close()
+elif args.ab > 0:
+    n = args.frames
+    seq = [frames[i % 8] for i in range(n)]
+    name = args.detector + ("" if args.descriptor == "ORB" else " + " + args.descriptor)
+    ms = {False: [], True: []}
+    host.classic_sequence(seq[:8], P_l, P_r, "KNN", True, 2.0, 4, detector=args.detector, descriptor=args.descriptor)      # the process's one-off costs
+    for r in range(args.ab):
+        for resident in (False, True):
+            p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5, detector=args.detector, resident=resident, descriptor=args.descriptor)
+            ms[resident].append(1e3 * sec / (n - 5))
+            print("%s %dx%d round %d resident=%d: %.3f ms per pair over %d pairs, %d pairs resident, keypoints %d, stereo matches %d, inliers %d" % (
+                name, frames[0][0].shape[1], frames[0][0].shape[0], r, resident, ms[resident][-1], n - 5, host.classic_resident_pairs(), np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3])))
+    for resident in (False, True):
+        v = np.array(ms[resident])
+        print("%s resident=%d: median %.3f ms per pair (min %.3f, max %.3f over %d runs)" % (name, resident, np.median(v), v.min(), v.max(), len(v)))
+    print("%s resident / per-image = %.3f" % (name, np.median(ms[True]) / np.median(ms[False])))
 else:
     n = args.frames
     seq = [frames[i % 8] for i in range(n)]
