@@ -102,19 +102,11 @@ int brisk_ensure_tables(spvo_ctx *c) {
   if (!t.ok) return fail(c, SPVO_ERR_STATE, "BRISK: the pattern tables failed their own checks (512 short pairs, 870 long pairs, every sigma >= 0.5)");
   if (int rc = brisk_upload_tables(c, t)) {
     dev_free(k.points, k.long_pairs, k.short_pairs, k.cnt);
-    if (k.h_n) (void)hipHostFree(k.h_n);
-    k.h_n = nullptr;
+    host_free(k.h_n);
     return rc;
   }
   k.tables_ready = true;
   return SPVO_OK;
-}
-
-// pinned host buffers, where there is one, freed and forgotten
-template <typename T, typename... Rest>
-void host_free(T *&p, Rest *&...rest) {
-  if (p) { (void)hipHostFree(p); p = nullptr; }
-  if constexpr (sizeof...(rest) > 0) host_free(rest...);
 }
 
 // the integral image for rows x cols, the keypoint buffers and their pinned mirrors for n rows (grown geometrically: a keypoint count that
@@ -166,6 +158,11 @@ void spvo_int::brisk_release(spvo_ctx *c) {
   k.integ_cap = 0; k.kp_cap = k.v0_cap = 0; k.tables_ready = false;
 }
 
+int spvo_int::brisk_check_image(spvo_ctx *c, const char *who, int rows, int cols) {
+  if ((long long)rows * cols * 255 >= (1ll << 31)) return fail(c, SPVO_ERR_INVALID, "%s: %d x %d pixels do not fit the int32 integral image", who, rows, cols);
+  return SPVO_OK;
+}
+
 int spvo_int::brisk_chain_ensure(spvo_ctx *c, int rows, int cols, int cap) {
   if (int rc = brisk_ensure_tables(c)) return rc;
   return brisk_ensure(c, rows, cols, cap, false);
@@ -174,7 +171,7 @@ int spvo_int::brisk_chain_ensure(spvo_ctx *c, int rows, int cols, int cap) {
 // spvo_brisk_describe's launches without its two host round trips: the keypoints are the detector's list where it lies (cls.xy, cls.resp,
 // cls.counters), the rows go straight into the slot.  kept / kscale / angle and the integral image are shared by the two images of a pair,
 // which is correct in stream order.
-int spvo_int::brisk_chain_enqueue(spvo_ctx *c, int rows, int cols, float size, int cap, int most, const BriskChainOut &o) {
+int spvo_int::brisk_chain_enqueue(spvo_ctx *c, int rows, int cols, float size, int cap, int most, const ChainOut &o) {
   auto &b = c->cls;
   auto &k = c->brisk;
   hipStream_t st = c->stream2;
@@ -215,7 +212,7 @@ int spvo_brisk_describe(spvo_ctx *c, const uint8_t *img, int rows, int cols, siz
                         int32_t *values0, int *n_kept) {
   if (!c || !n_kept || rows <= 0 || cols <= 0 || n < 0 || (n > 0 && (!xy || !size || !kept || !desc)) || (img && stride < (size_t)cols)) return fail(c, SPVO_ERR_INVALID, "bad argument");
   *n_kept = 0;
-  if ((long long)rows * cols * 255 >= (1ll << 31)) return fail(c, SPVO_ERR_INVALID, "spvo_brisk_describe: %d x %d pixels do not fit the int32 integral image", rows, cols);
+  if (int rc = brisk_check_image(c, "spvo_brisk_describe", rows, cols)) return rc;
   for (int i = 0; i < n; ++i)
     if (!std::isfinite(size[i]) || !(size[i] > 0)) return fail(c, SPVO_ERR_INVALID, "spvo_brisk_describe: keypoint %d has size %g", i, (double)size[i]);
   if (int rc = require_idle(c)) return rc;

@@ -332,6 +332,30 @@ int fast_enqueue(spvo_ctx *c, int rows, int cols, int threshold, int nonmax_supp
   return SPVO_OK;
 }
 
+// What the per-image entry points refuse, for every entry point that runs the same detector (`who` names it in the error text)
+int gftt_check(spvo_ctx *c, const char *who, int rows, int cols, double quality_level, double min_distance, int block_size) {
+  if (rows < 8 || cols < 8 || !(quality_level > 0)) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  if (block_size != 5 || !(min_distance >= 0 && min_distance <= 15)) return fail(c, SPVO_ERR_INVALID, "%s: block_size 5 and min_distance <= 15 only", who);
+  return SPVO_OK;
+}
+int fast_check(spvo_ctx *c, int threshold) { return threshold < 0 || threshold > 255 ? fail(c, SPVO_ERR_INVALID, "bad argument") : SPVO_OK; }
+
+// orb.hip.h's extractor on a one-level OrbLevels over the resident image (spvo_ctx::cls) whose keypoint list is `out_xy` and whose count is
+// counters[2]: 7x7 blur of level 0, then direction + steered tests of the first `rows_covered` keypoints into d_kp / d_desc (kp_cap rows)
+void orb_extract_one_level(spvo_ctx *c, int rows, int cols, int *out_xy, int *counters, int rows_covered, OrbKeypoint *d_kp, uint8_t *d_desc, int kp_cap) {
+  auto &b = c->cls;
+  auto &o = c->orb;
+  hipStream_t st = c->stream2;
+  OrbLevels lv{};
+  OrbLevel &L = lv.l[0];
+  L.im = b.im; L.score = b.score; L.blur = b.blur; L.tmp = b.tmp; L.out_xy = out_xy; L.counters = counters;
+  L.h = rows; L.w = cols; L.want = rows_covered; L.cap = rows_covered; L.scale = 1.f;
+  const dim3 grid((cols + 63) / 64, (rows + 3) / 4, 1);
+  hipLaunchKernelGGL(orb_blur_h_kernel, grid, dim3(256), 0, st, lv, o.taps);
+  hipLaunchKernelGGL(orb_blur_v_kernel, grid, dim3(256), 0, st, lv, o.taps);
+  hipLaunchKernelGGL(orb_describe_kernel, dim3((rows_covered + 3) / 4, 1), dim3(256), 0, st, lv, o.disc, o.pattern, d_kp, d_desc, kp_cap);
+}
+
 // counters -> host, then min(n, cap) keypoints
 int cls_read_out(spvo_ctx *c, float *xy, float *response, int cap, int *n_out, const char *what) {
   auto &b = c->cls;
@@ -355,9 +379,8 @@ int cls_read_out(spvo_ctx *c, float *xy, float *response, int cap, int *n_out, c
 
 int spvo_gftt_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride, int max_corners, double quality_level, double min_distance, int block_size,
                      float *xy, float *response, int cap, int *n_out) {
-  if (!c || !img || !n_out || rows < 8 || cols < 8 || stride < (size_t)cols || cap < 0 || (cap > 0 && !xy) || !(quality_level > 0))
-    return fail(c, SPVO_ERR_INVALID, "bad argument");
-  if (block_size != 5 || !(min_distance >= 0 && min_distance <= 15)) return fail(c, SPVO_ERR_INVALID, "spvo_gftt_detect: block_size 5 and min_distance <= 15 only");
+  if (!c || !img || !n_out || stride < (size_t)cols || cap < 0 || (cap > 0 && !xy)) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  if (int rc = gftt_check(c, "spvo_gftt_detect", rows, cols, quality_level, min_distance, block_size)) return rc;
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   *n_out = 0;
   if (int rc = cls_prepare(c, img, rows, cols, stride)) return rc;
@@ -374,8 +397,8 @@ int spvo_gftt_last_rounds(spvo_ctx *c, int *undecided_after_launch /* [3] */, in
 
 int spvo_fast_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride, int threshold, int nonmax_suppression, float *xy, float *response, int cap,
                      int *n_out) {
-  if (!c || !img || !n_out || rows <= 0 || cols <= 0 || stride < (size_t)cols || cap < 0 || (cap > 0 && !xy) || threshold < 0 || threshold > 255)
-    return fail(c, SPVO_ERR_INVALID, "bad argument");
+  if (!c || !img || !n_out || rows <= 0 || cols <= 0 || stride < (size_t)cols || cap < 0 || (cap > 0 && !xy)) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  if (int rc = fast_check(c, threshold)) return rc;
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   *n_out = 0;
   if (int rc = cls_prepare(c, img, rows, cols, stride)) return rc;
@@ -426,15 +449,7 @@ int spvo_orb_describe(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_
   cnt[2] = nk;
   HIP_TRY(c, hipMemcpyAsync(b.counters, cnt, sizeof cnt, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(b.kp_xy, kxy.data(), (size_t)2 * nk * sizeof(int), hipMemcpyHostToDevice, st));
-  // orb.hip.h's extractor on a one-level OrbLevels whose keypoint list is the caller's: 7x7 blur of level 0, then direction + steered tests
-  OrbLevels lv{};
-  OrbLevel &L = lv.l[0];
-  L.im = b.im; L.score = b.score; L.blur = b.blur; L.tmp = b.tmp; L.out_xy = b.kp_xy; L.counters = b.counters;
-  L.h = rows; L.w = cols; L.want = nk; L.cap = nk; L.scale = 1.f;
-  const dim3 grid((cols + 63) / 64, (rows + 3) / 4, 1);
-  hipLaunchKernelGGL(orb_blur_h_kernel, grid, dim3(256), 0, st, lv, c->orb.taps);
-  hipLaunchKernelGGL(orb_blur_v_kernel, grid, dim3(256), 0, st, lv, c->orb.taps);
-  hipLaunchKernelGGL(orb_describe_kernel, dim3((nk + 3) / 4, 1), dim3(256), 0, st, lv, c->orb.disc, c->orb.pattern, b.kps, b.desc, nk);
+  orb_extract_one_level(c, rows, cols, b.kp_xy, b.counters, nk, b.kps, b.desc, nk);   // the keypoint list is the caller's
   HIP_TRY(c, hipGetLastError());
   std::vector<OrbKeypoint> kp((size_t)nk);
   HIP_TRY(c, hipMemcpyAsync(kp.data(), b.kps, (size_t)nk * sizeof(OrbKeypoint), hipMemcpyDeviceToHost, st));
@@ -454,23 +469,18 @@ void spvo_int::classic_release_slots(spvo_ctx *c) {
   auto &bb = c->bin;
   for (BinarySlot &s : bb.slots) {
     dev_free(s.d_kp, s.d_desc, s.d_n);
-    s.filled = false; s.n = 0; s.row_bytes = 32; ++s.gen;
+    slot_rewrite(s);
+    s.row_bytes = 32;
   }
   dev_free(bb.d_cnt, bb.d_kxy, bb.d_kresp, bb.d_vote);
-  for (void *p : {(void *)bb.h_kp, (void *)bb.h_desc, (void *)bb.h_n, (void *)bb.h_match}) if (p) (void)hipHostFree(p);
-  bb.h_kp = nullptr; bb.h_desc = nullptr; bb.h_n = nullptr; bb.h_match = nullptr;
-  for (auto &mc : bb.mcache) { mc.valid = false; mc.h_out = nullptr; }
-  bb.cap = 0; bb.last_slot_l = -1;
+  host_free(bb.h_kp, bb.h_desc, bb.h_n, bb.h_match);
+  bb.pair.mcache.invalidate();
+  bb.cap = 0; bb.pair.last_slot_l = -1;
 }
 
 void spvo_int::classic_release(spvo_ctx *c) {
-  auto &bb = c->bin;
   classic_release_slots(c);
-  if (bb.h_img) (void)hipHostFree(bb.h_img);
-  bb.h_img = nullptr; bb.img_cap = 0;
-  if (bb.ev_feat) (void)hipEventDestroy(bb.ev_feat);
-  if (bb.ev_match) (void)hipEventDestroy(bb.ev_match);
-  bb.ev_feat = bb.ev_match = nullptr;
+  c->bin.pair.release();
 }
 
 extern "C" {
@@ -483,17 +493,7 @@ inline bool kind_is_gftt(int kind) { return kind == SPVO_CLASSIC_GFTT_ORB || kin
 // both mirrors are sized for 64-byte rows whatever kind asks first: a BRISK kind's first call must not empty the slots the ORB kinds filled
 int bin_ensure(spvo_ctx *c, int cap, size_t px) {
   auto &bb = c->bin;
-  if (!bb.ev_feat) {
-    HIP_TRY(c, hipEventCreateWithFlags(&bb.ev_feat, hipEventDisableTiming));
-    HIP_TRY(c, hipEventCreateWithFlags(&bb.ev_match, hipEventDisableTiming));
-  }
-  if (px > bb.img_cap) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream2));
-    if (bb.h_img) (void)hipHostFree(bb.h_img);
-    bb.h_img = nullptr; bb.img_cap = 0;
-    HIP_TRY(c, hipHostMalloc((void **)&bb.h_img, 2 * px));
-    bb.img_cap = px;
-  }
+  if (int rc = bb.pair.ensure(c, px)) return rc;
   if (cap <= bb.cap) return SPVO_OK;
   HIP_TRY(c, hipStreamSynchronize(c->stream2));
   classic_release_slots(c);
@@ -507,7 +507,6 @@ int bin_ensure(spvo_ctx *c, int cap, size_t px) {
   HIP_TRY(c, hipHostMalloc((void **)&bb.h_desc, (size_t)2 * cap * BIN_ROW_BYTES_MAX));
   HIP_TRY(c, hipHostMalloc((void **)&bb.h_n, 2 * 4 * sizeof(int)));
   HIP_TRY(c, hipHostMalloc((void **)&bb.h_match, (size_t)3 * cap * sizeof(int2)));
-  for (int k = 0; k < 2; ++k) bb.mcache[k].h_out = bb.h_match + (size_t)k * cap;
   HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
   bb.cap = cap;
   return SPVO_OK;
@@ -546,8 +545,8 @@ int spvo_classic_slot_fill_debug(spvo_ctx *c, int slot, const uint8_t *desc, int
   if (n > bb.cap) return fail(c, SPVO_ERR_INVALID, "spvo_classic_slot_fill_debug: %d rows do not fit slots of %d", n, bb.cap);
   HIP_TRY(c, hipStreamSynchronize(c->stream2));   // (a prematch of the slot's old rows may still run)
   BinarySlot &s = bb.slots[slot];
-  s.filled = false; s.n = 0; ++s.gen;
-  for (auto &mc : bb.mcache) mc.valid = false;
+  slot_rewrite(s);
+  bb.pair.mcache.invalidate();
   hipStream_t st = c->stream2;
   if (n > 0) {
     HIP_TRY(c, hipMemsetAsync(s.d_kp, 0, (size_t)n * sizeof(OrbKeypoint), st));
@@ -559,119 +558,145 @@ int spvo_classic_slot_fill_debug(spvo_ctx *c, int slot, const uint8_t *desc, int
   return SPVO_OK;
 }
 
-int spvo_classic_detect(spvo_ctx *c, const spvo_classic_opts *opts, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int slot_l, int slot_r,
-                        spvo_classic_features *out_l, spvo_classic_features *out_r) {
-  if (!c || !opts || !img_l || !img_r || !out_l || !out_r || rows <= 0 || cols <= 0 || stride < (size_t)cols) return fail(c, SPVO_ERR_INVALID, "bad argument");
-  if (slot_l < 0 || slot_l >= N_BIN_SLOTS || slot_r < 0 || slot_r >= N_BIN_SLOTS || slot_l == slot_r) return fail(c, SPVO_ERR_INVALID, "bad slot");
-  spvo_classic_features *outs[2] = {out_l, out_r};
-  for (auto *o : outs)
-    if (o->cap < 0) return fail(c, SPVO_ERR_INVALID, "bad output buffer");
+namespace {
+// what spvo_classic_detect refuses of its options and of the image shape: the slot capacity, then what the kind's per-image entry points refuse
+int classic_check_opts(spvo_ctx *c, const spvo_classic_opts *opts, int rows, int cols) {
   const int kind = opts->kind, cap = opts->slot_capacity;
   if (cap <= 0 || cap > (1 << HAM_KEY_SHIFT)) return fail(c, SPVO_ERR_INVALID, "slot_capacity must be 1 .. %d", 1 << HAM_KEY_SHIFT);
-  // what the per-image entry points refuse
   if (kind == SPVO_CLASSIC_ORB) {
     if (opts->nfeatures <= 0) return fail(c, SPVO_ERR_INVALID, "bad argument");
   } else if (kind_is_gftt(kind)) {
-    if (rows < 8 || cols < 8 || !(opts->quality_level > 0)) return fail(c, SPVO_ERR_INVALID, "bad argument");
-    if (opts->block_size != 5 || !(opts->min_distance >= 0 && opts->min_distance <= 15)) return fail(c, SPVO_ERR_INVALID, "spvo_classic_detect: block_size 5 and min_distance <= 15 only");
+    if (int rc = gftt_check(c, "spvo_classic_detect", rows, cols, opts->quality_level, opts->min_distance, opts->block_size)) return rc;
   } else if (kind == SPVO_CLASSIC_FAST_ORB || kind == SPVO_CLASSIC_FAST_BRISK) {
-    if (opts->fast_threshold < 0 || opts->fast_threshold > 255) return fail(c, SPVO_ERR_INVALID, "bad argument");
+    if (int rc = fast_check(c, opts->fast_threshold)) return rc;
   } else {
     return fail(c, SPVO_ERR_INVALID, "unknown kind %d", kind);
   }
-  const bool brisk = kind_is_brisk(kind);
-  if (brisk && (long long)rows * cols * 255 >= (1ll << 31)) return fail(c, SPVO_ERR_INVALID, "spvo_classic_detect: %d x %d pixels do not fit the int32 integral image", rows, cols);
-  const int row_bytes = brisk ? 64 : 32;
-  if (!c->pendq.empty()) return fail(c, SPVO_ERR_STATE, "detector submissions are in flight: complete them with spvo_detect_wait first");
-  HIP_TRY(c, hipSetDevice(c->cfg.device));
-  out_l->n = out_r->n = 0;
-  hipStream_t st = c->stream2;
-  auto &bb = c->bin;
+  return kind_is_brisk(kind) ? brisk_check_image(c, "spvo_classic_detect", rows, cols) : SPVO_OK;
+}
+
+// every buffer a call of these options needs for a rows x cols pair (`plan`: the ORB kind's)
+int classic_pair_ensure(spvo_ctx *c, const spvo_classic_opts *opts, int rows, int cols, OrbPlan &plan) {
+  const int cap = opts->slot_capacity;
+  if (int rc = bin_ensure(c, cap, (size_t)rows * cols)) return rc;
+  if (opts->kind == SPVO_CLASSIC_ORB) return orb_prepare(c, rows, cols, opts->nfeatures, plan);
+  if (int rc = cls_ensure(c, rows, cols)) return rc;
+  return kind_is_brisk(opts->kind) ? brisk_chain_ensure(c, rows, cols, cap) : orb_ensure_tables(c);   // (the BRISK tables: a one-off 47 MB upload, before the chain)
+}
+
+// image k of the staged pair through the ORB detector + extractor into its slot
+int orb_pair_chain(spvo_ctx *c, const spvo_classic_opts *opts, const OrbPlan &plan, int rows, int cols, int k, const ChainOut &out) {
   auto &o = c->orb;
+  hipStream_t st = c->stream2;
+  const size_t px = (size_t)rows * cols;
+  const int cap = opts->slot_capacity;
+  HIP_TRY(c, hipMemcpyAsync(o.im, c->bin.pair.h_img + k * px, px, hipMemcpyHostToDevice, st));
+  const int kp_cap = std::min(opts->nfeatures, cap);   // (more than `cap` rows are an error of the call: the slot need not hold them)
+  if (int rc = orb_enqueue(c, plan, rows, cols, out.d_kp, reinterpret_cast<uint8_t *>(out.d_desc), kp_cap)) return rc;
+  hipLaunchKernelGGL(classic_finish_kernel, dim3(32), dim3(256), 0, st, o.counters, ORB_LEVELS, NMS_COUNTER_INTS, opts->nfeatures, nullptr, nullptr, nullptr, out.d_kp,
+                     reinterpret_cast<const uint4 *>(out.d_desc), cap, out.d_n, out.h_n, out.h_kp, reinterpret_cast<uint4 *>(out.h_desc));
+  return SPVO_OK;
+}
+
+// image k of the staged pair becomes the resident image of spvo_ctx::cls and goes through the Shi-Tomasi or FAST detector, which leaves its list there
+int detector_enqueue(spvo_ctx *c, const spvo_classic_opts *opts, int rows, int cols, int k) {
   auto &b = c->cls;
   const size_t px = (size_t)rows * cols;
-  if (int rc = bin_ensure(c, cap, px)) return rc;
-  OrbPlan plan;
-  if (kind == SPVO_CLASSIC_ORB) {
-    if (int rc = orb_prepare(c, rows, cols, opts->nfeatures, plan)) return rc;
-  } else {
-    if (int rc = cls_ensure(c, rows, cols)) return rc;
-    if (int rc = brisk ? brisk_chain_ensure(c, rows, cols, cap) : orb_ensure_tables(c)) return rc;   // (the BRISK tables: a one-off 47 MB upload, before the chain)
-  }
-  // both slots are being rewritten: whatever was matched against their old contents is stale
-  const int slots[2] = {slot_l, slot_r};
-  for (int sl : slots) { BinarySlot &s = bb.slots[sl]; s.filled = false; s.n = 0; s.row_bytes = row_bytes; ++s.gen; }
-  for (auto &mc : bb.mcache) mc.valid = false;
-  // pinned staging: both images with packed rows (of a strided view only the rows' own bytes are the caller's), one upload each
-  HIP_TRY(c, hipStreamSynchronize(st));   // (the staging buffer and the mirrors are the previous call's until its work is done)
-  const uint8_t *imgs[2] = {img_l, img_r};
-  for (int k = 0; k < 2; ++k)
-    for (int r = 0; r < rows; ++r) std::memcpy(bb.h_img + k * px + (size_t)r * cols, imgs[k] + (size_t)r * stride, cols);
-  for (int k = 0; k < 2; ++k) {
-    BinarySlot &s = bb.slots[slots[k]];
-    int *h_n = bb.h_n + 4 * k;
-    OrbKeypoint *h_kp = bb.h_kp + (size_t)k * cap;
-    uint4 *h_desc = reinterpret_cast<uint4 *>(bb.h_desc + (size_t)k * cap * row_bytes);
-    if (kind == SPVO_CLASSIC_ORB) {
-      HIP_TRY(c, hipMemcpyAsync(o.im, bb.h_img + k * px, px, hipMemcpyHostToDevice, st));
-      const int kp_cap = std::min(opts->nfeatures, cap);   // (more than `cap` rows are an error below: the slot need not hold them)
-      if (int rc = orb_enqueue(c, plan, rows, cols, s.d_kp, reinterpret_cast<uint8_t *>(s.d_desc), kp_cap)) return rc;
-      hipLaunchKernelGGL(classic_finish_kernel, dim3(32), dim3(256), 0, st, o.counters, ORB_LEVELS, NMS_COUNTER_INTS, opts->nfeatures, nullptr, nullptr, nullptr, s.d_kp,
-                         reinterpret_cast<const uint4 *>(s.d_desc), cap, s.d_n, h_n, h_kp, h_desc);
-    } else {
-      b.rows = b.cols = 0;
-      HIP_TRY(c, hipMemcpyAsync(b.im, bb.h_img + k * px, px, hipMemcpyHostToDevice, st));
-      b.rows = rows; b.cols = cols;
-      if (int rc = kind_is_gftt(kind) ? gftt_enqueue(c, rows, cols, opts->max_corners, opts->quality_level, opts->min_distance)
-                                                 : fast_enqueue(c, rows, cols, opts->fast_threshold, opts->fast_nonmax))
-        return rc;
-      // detector -> extractor on the device: the border rule as an order-preserving compaction, then orb.hip.h's extractor on a one-level
-      // OrbLevels whose keypoint list is the compacted one and whose count is the compaction's (spvo_orb_describe, without the host)
-      int *cnt = bb.d_cnt + k * CLS_COUNTER_INTS;
-      const int most = kind_is_gftt(kind) && opts->max_corners > 0 ? std::min(cap, opts->max_corners) : cap;   // rows the extractor's grid covers
-      if (brisk) {
-        // the same hand-over to the BRISK extractor: its border rule (keypoint size 5 / 7, what detectKeypoints assigns) and the rest of
-        // spvo_brisk_describe's launches, 64-byte rows
-        const BriskChainOut bo{cnt, bb.d_kresp, s.d_kp, s.d_desc, s.d_n, h_n, h_kp, reinterpret_cast<uint8_t *>(h_desc)};
-        if (int rc = brisk_chain_enqueue(c, rows, cols, kind_is_gftt(kind) ? 5.0f : 7.0f, cap, most, bo)) return rc;
-        continue;
-      }
-      hipLaunchKernelGGL(cls_compact_kernel, dim3(1), dim3(1024), 0, st, b.xy, b.resp, b.counters, rows, cols, ORB_EDGE, bb.d_kxy, bb.d_kresp, cap, cnt);
-      OrbLevels lv{};
-      OrbLevel &L = lv.l[0];
-      L.im = b.im; L.score = b.score; L.blur = b.blur; L.tmp = b.tmp; L.out_xy = bb.d_kxy; L.counters = cnt;
-      L.h = rows; L.w = cols; L.want = most; L.cap = most; L.scale = 1.f;
-      const dim3 grid((cols + 63) / 64, (rows + 3) / 4, 1);
-      hipLaunchKernelGGL(orb_blur_h_kernel, grid, dim3(256), 0, st, lv, o.taps);
-      hipLaunchKernelGGL(orb_blur_v_kernel, grid, dim3(256), 0, st, lv, o.taps);
-      hipLaunchKernelGGL(orb_describe_kernel, dim3((most + 3) / 4, 1), dim3(256), 0, st, lv, o.disc, o.pattern, s.d_kp, reinterpret_cast<uint8_t *>(s.d_desc), cap);
-      hipLaunchKernelGGL(classic_finish_kernel, dim3(32), dim3(256), 0, st, nullptr, 0, 0, 0, b.counters, cnt, bb.d_kresp, s.d_kp, reinterpret_cast<const uint4 *>(s.d_desc), cap,
-                         s.d_n, h_n, h_kp, h_desc);
-    }
-    HIP_TRY(c, hipGetLastError());
-  }
-  HIP_TRY(c, hipEventRecord(bb.ev_feat, st));
-  // spvo_set_prematch: the two standard matches behind the features, counts read on the device (a pair that turns out not to fit its
-  // slots is matched on whatever rows the slots hold; that result is dropped below)
-  const int prev_l = bb.last_slot_l;
-  // (a previous left slot of the other row width has no temporal match: skipped, the synchronous call reports the widths when asked)
-  const bool temporal = prev_l >= 0 && prev_l != slot_l && prev_l != slot_r && bb.slots[prev_l].filled && bb.slots[prev_l].row_bytes == row_bytes;
-  if (c->prematch) {
-    if (int rc = enqueue_hamming_slots(c, slot_l, slot_r, c->pm_selector, c->pm_cross, c->pm_ratio, bb.mcache[0].h_out)) return rc;
-    if (temporal)
-      if (int rc = enqueue_hamming_slots(c, slot_l, prev_l, c->pm_selector, c->pm_cross, c->pm_ratio, bb.mcache[1].h_out)) return rc;
-    HIP_TRY(c, hipEventRecord(bb.ev_match, st));
-  }
-  HIP_TRY(c, wait_event(bb.ev_feat));   // the one wait of the call: the matches go on behind it
-  bb.last_slot_l = -1;
+  b.rows = b.cols = 0;
+  HIP_TRY(c, hipMemcpyAsync(b.im, c->bin.pair.h_img + k * px, px, hipMemcpyHostToDevice, c->stream2));
+  b.rows = rows; b.cols = cols;
+  return kind_is_gftt(opts->kind) ? gftt_enqueue(c, rows, cols, opts->max_corners, opts->quality_level, opts->min_distance)
+                                  : fast_enqueue(c, rows, cols, opts->fast_threshold, opts->fast_nonmax);
+}
+// rows the extractor's grid covers behind that detector
+int detector_most(const spvo_classic_opts *opts) {
+  return kind_is_gftt(opts->kind) && opts->max_corners > 0 ? std::min(opts->slot_capacity, opts->max_corners) : opts->slot_capacity;
+}
+
+// detector -> ORB extractor on the device: the border rule as an order-preserving compaction, then the one-level extractor whose keypoint
+// list is the compacted one and whose count is the compaction's (spvo_orb_describe, without the host)
+int detector_orb_chain(spvo_ctx *c, const spvo_classic_opts *opts, int rows, int cols, int k, const ChainOut &out) {
+  if (int rc = detector_enqueue(c, opts, rows, cols, k)) return rc;
+  auto &b = c->cls;
+  hipStream_t st = c->stream2;
+  const int cap = opts->slot_capacity;
+  hipLaunchKernelGGL(cls_compact_kernel, dim3(1), dim3(1024), 0, st, b.xy, b.resp, b.counters, rows, cols, ORB_EDGE, c->bin.d_kxy, out.kresp, cap, out.cnt);
+  orb_extract_one_level(c, rows, cols, c->bin.d_kxy, out.cnt, detector_most(opts), out.d_kp, reinterpret_cast<uint8_t *>(out.d_desc), cap);
+  hipLaunchKernelGGL(classic_finish_kernel, dim3(32), dim3(256), 0, st, nullptr, 0, 0, 0, b.counters, out.cnt, out.kresp, out.d_kp, reinterpret_cast<const uint4 *>(out.d_desc), cap,
+                     out.d_n, out.h_n, out.h_kp, reinterpret_cast<uint4 *>(out.h_desc));
+  return SPVO_OK;
+}
+
+// the same hand-over to the BRISK extractor: its border rule (keypoint size 5 / 7, what detectKeypoints assigns) and the rest of
+// spvo_brisk_describe's launches, 64-byte rows
+int detector_brisk_chain(spvo_ctx *c, const spvo_classic_opts *opts, int rows, int cols, int k, const ChainOut &out) {
+  if (int rc = detector_enqueue(c, opts, rows, cols, k)) return rc;
+  return brisk_chain_enqueue(c, rows, cols, kind_is_gftt(opts->kind) ? 5.0f : 7.0f, opts->slot_capacity, detector_most(opts), out);
+}
+
+// the counts of both images from their mirrors; a pair that does not fit its slots is an error
+int classic_check_capacity(spvo_ctx *c, int cap, spvo_classic_features *const outs[2]) {
   int worst = SPVO_OK;
   for (int k = 0; k < 2; ++k) {
-    const int *h_n = bb.h_n + 4 * k;
+    const int *h_n = c->bin.h_n + 4 * k;
     outs[k]->n = h_n[0];
     if (h_n[1]) return fail(c, SPVO_ERR_CAPACITY, "spvo_classic_detect: corner buffer overflow in the %s image", k ? "right" : "left");
     if (h_n[0] > cap) worst = SPVO_ERR_CAPACITY;
   }
-  if (worst) return fail(c, worst, "spvo_classic_detect: %d / %d rows do not fit slots of %d (slot_capacity)", out_l->n, out_r->n, cap);
+  if (worst) return fail(c, worst, "spvo_classic_detect: %d / %d rows do not fit slots of %d (slot_capacity)", outs[0]->n, outs[1]->n, cap);
+  return SPVO_OK;
+}
+}  // namespace
+
+int spvo_classic_detect(spvo_ctx *c, const spvo_classic_opts *opts, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int slot_l, int slot_r,
+                        spvo_classic_features *out_l, spvo_classic_features *out_r) {
+  if (!c || !opts || !img_l || !img_r || !out_l || !out_r || rows <= 0 || cols <= 0 || stride < (size_t)cols) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  if (slot_l < 0 || slot_l >= N_BIN_SLOTS || slot_r < 0 || slot_r >= N_BIN_SLOTS || slot_l == slot_r) return fail(c, SPVO_ERR_INVALID, "bad slot");
+  spvo_classic_features *const outs[2] = {out_l, out_r};
+  for (auto *o : outs)
+    if (o->cap < 0) return fail(c, SPVO_ERR_INVALID, "bad output buffer");
+  if (int rc = classic_check_opts(c, opts, rows, cols)) return rc;
+  if (int rc = require_idle(c)) return rc;
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  out_l->n = out_r->n = 0;
+  hipStream_t st = c->stream2;
+  auto &bb = c->bin;
+  PairStage &ps = bb.pair;
+  const int kind = opts->kind, cap = opts->slot_capacity, row_bytes = kind_is_brisk(kind) ? 64 : 32;
+  OrbPlan plan;
+  if (int rc = classic_pair_ensure(c, opts, rows, cols, plan)) return rc;
+  // both slots are being rewritten: whatever was matched against their old contents is stale
+  const int slots[2] = {slot_l, slot_r};
+  for (int sl : slots) { slot_rewrite(bb.slots[sl]); bb.slots[sl].row_bytes = row_bytes; }
+  ps.mcache.invalidate();
+  // pinned staging: one upload per image
+  HIP_TRY(c, hipStreamSynchronize(st));   // (the staging buffer and the mirrors are the previous call's until its work is done)
+  ps.stage(img_l, img_r, rows, cols, stride);
+  for (int k = 0; k < 2; ++k) {
+    const BinarySlot &s = bb.slots[slots[k]];
+    const ChainOut out{bb.d_cnt + k * CLS_COUNTER_INTS, bb.d_kresp, s.d_kp, s.d_desc, s.d_n, bb.h_n + 4 * k, bb.h_kp + (size_t)k * cap, bb.h_desc + (size_t)k * cap * row_bytes};
+    if (int rc = kind == SPVO_CLASSIC_ORB ? orb_pair_chain(c, opts, plan, rows, cols, k, out)
+                 : row_bytes == 64        ? detector_brisk_chain(c, opts, rows, cols, k, out)
+                                          : detector_orb_chain(c, opts, rows, cols, k, out))
+      return rc;
+    HIP_TRY(c, hipGetLastError());
+  }
+  HIP_TRY(c, hipEventRecord(ps.ev_feat, st));
+  // spvo_set_prematch: the two standard matches behind the features, counts read on the device (a pair that turns out not to fit its
+  // slots is matched on whatever rows the slots hold; that result is dropped below).  They run on this stream, so ev_match is recorded
+  // here and nothing waits across streams.
+  // (a previous left slot of the other row width has no temporal match: skipped, the synchronous call reports the widths when asked)
+  const int prev = ps.last_slot_l;
+  const int partner[2] = {slot_r, ps.temporal_partner(slot_l, slot_r, prev >= 0 && bb.slots[prev].filled && bb.slots[prev].row_bytes == row_bytes)};
+  if (c->prematch) {
+    for (int k = 0; k < 2; ++k)
+      if (partner[k] >= 0)
+        if (int rc = enqueue_hamming_slots(c, slot_l, partner[k], c->pm_selector, c->pm_cross, c->pm_ratio, bb.h_match + (size_t)k * cap)) return rc;
+    HIP_TRY(c, hipEventRecord(ps.ev_match, st));
+  }
+  HIP_TRY(c, wait_event(ps.ev_feat));   // the one wait of the call: the matches go on behind it
+  ps.last_slot_l = -1;   // (the temporal partner is forgotten AFTER the wait here: a call that failed before it leaves the one it found)
+  if (int rc = classic_check_capacity(c, cap, outs)) return rc;
   for (int k = 0; k < 2; ++k) {
     BinarySlot &s = bb.slots[slots[k]];
     s.n = outs[k]->n; s.filled = true;
@@ -679,18 +704,11 @@ int spvo_classic_detect(spvo_ctx *c, const spvo_classic_opts *opts, const uint8_
     if (ncopy > 0 && outs[k]->kp) std::memcpy(outs[k]->kp, bb.h_kp + (size_t)k * cap, (size_t)ncopy * sizeof(OrbKeypoint));
     if (ncopy > 0 && outs[k]->desc) std::memcpy(outs[k]->desc, bb.h_desc + (size_t)k * cap * row_bytes, (size_t)ncopy * row_bytes);
   }
-  if (c->prematch) {
-    const BinarySlot &l = bb.slots[slot_l];
-    const int partner[2] = {slot_r, temporal ? prev_l : -1};
-    for (int k = 0; k < 2; ++k) {
-      MatchCache &mc = bb.mcache[k];
-      if (partner[k] < 0) continue;
-      mc.valid = true;
-      mc.slot_a = slot_l; mc.slot_b = partner[k]; mc.selector = c->pm_selector; mc.cross = c->pm_cross; mc.ratio = c->pm_ratio;
-      mc.gen_a = l.gen; mc.gen_b = bb.slots[partner[k]].gen;
-    }
-  }
-  bb.last_slot_l = slot_l;
+  if (c->prematch)
+    for (int k = 0; k < 2; ++k)
+      if (partner[k] >= 0)
+        ps.mcache.record(k, slot_l, partner[k], bb.slots[slot_l].gen, bb.slots[partner[k]].gen, c->pm_selector, c->pm_cross, c->pm_ratio, bb.h_match + (size_t)k * cap);
+  ps.last_slot_l = slot_l;
   return SPVO_OK;
 }
 

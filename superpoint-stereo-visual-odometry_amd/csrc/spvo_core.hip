@@ -268,17 +268,17 @@ int set_alloc(spvo_ctx *c, int index) {
 
 void set_release_images(SubmitSet &s) {
   dev_free(s.d_img);
-  if (s.h_img) { (void)hipHostFree(s.h_img); s.h_img = nullptr; }
+  host_free(s.h_img);
 }
 void set_release_match(SubmitSet &s) {
-  if (s.h_match_out) { (void)hipHostFree(s.h_match_out); s.h_match_out = nullptr; }
-  for (MatchCache &mc : s.mcache) { mc.valid = false; mc.h_out = nullptr; }
+  host_free(s.h_match_out);
+  s.mcache.invalidate();
 }
 void set_release(SubmitSet &s) {
   set_release_images(s); set_release_match(s); set_release_segments(s);
   for (NmsBuffers &b : s.nms) dev_free(b.state, b.cand, b.surv_key, b.rank, b.out_xy);
   dev_free(s.d_heat_base, s.d_resized);   // (d_heat and d_counters point into other allocations)
-  for (void *hp : {(void *)s.h_counters, (void *)s.h_xy, (void *)s.h_resized, (void *)s.h_desc}) if (hp) (void)hipHostFree(hp);
+  host_free(s.h_counters, s.h_xy, s.h_resized, s.h_desc);
   for (hipEvent_t e : {s.ev_net, s.ev_tail, s.ev_feat, s.ev_copy, s.ev_pre, s.ev_res, s.ev_up, s.ev_heads}) if (e) (void)hipEventDestroy(e);
   s = SubmitSet();
 }
@@ -466,9 +466,8 @@ void spvo_destroy(spvo_ctx *c) {
   for (SubmitSet &s : c->sets) set_release(s);
   for (auto &sl : c->slots) dev_free(sl.d_xy, sl.d_desc, sl.d_n, sl.d_sqn);
   for (int sl = 0; sl < spvo_ctx::SOLVE_BUFS; ++sl) {
-    for (void *dp : {(void *)c->x_counts[sl], (void *)c->x_poses[sl], (void *)c->x_obs[sl]}) if (dp) (void)hipFree(dp);
-    for (void *hp : {(void *)c->h_solve_in[sl], (void *)c->h_solve_res[sl], (void *)c->h_solve_o[sl]}) if (hp) (void)hipHostFree(hp);
-    for (void *dp : {(void *)c->d_solve_in[sl], (void *)c->d_solve_res[sl], (void *)c->d_solve_o[sl]}) if (dp) (void)hipFree(dp);
+    dev_free(c->x_counts[sl], c->x_poses[sl], c->x_obs[sl], c->d_solve_in[sl], c->d_solve_res[sl], c->d_solve_o[sl]);
+    host_free(c->h_solve_in[sl], c->h_solve_res[sl], c->h_solve_o[sl]);
   }
   if (c->d_ctl) (void)hipFree(c->d_ctl);
   dev_free(c->d_ham_a, c->d_ham_b, c->d_ham_idx, c->d_ham_dist, c->d_ham_vote);
@@ -479,7 +478,7 @@ void spvo_destroy(spvo_ctx *c) {
   brisk_release(c);
   auto &b = c->cls;
   dev_free(b.im, b.score, b.blur, b.src, b.state, b.desc, b.tmp, b.lam, b.xy, b.resp, b.keys, b.rank, b.cand, b.counters, b.kp_xy, b.kps, b.pre_out, b.pre_tab);
-  if (c->h_match_tmp) (void)hipHostFree(c->h_match_tmp);
+  host_free(c->h_match_tmp);
   if (c->stream_t) (void)hipStreamDestroy(c->stream_t);
   if (c->stream_tb) (void)hipStreamDestroy(c->stream_tb);
   if (c->stream) (void)hipStreamDestroy(c->stream);

@@ -390,16 +390,13 @@ static int enqueue_prematch(spvo_ctx *c, int slot_l, int slot_r, int prev_l, Sub
   const int partner[2] = {slot_r, prev_l};
   MatchReq req[2];
   int nj = 0;
+  set.mcache.invalidate();
   for (int k = 0; k < 2; ++k) {
-    MatchCache &mc = set.mcache[k];
-    mc.valid = false;
     if (partner[k] < 0) continue;
     FeatureSlot &a = c->slots[slot_l], &b = c->slots[partner[k]];
     req[nj] = MatchReq{a.d_desc, b.d_desc, cap, cap, a.d_n, b.d_n, a.d_sqn, b.d_sqn};
-    MatchCache &dst = set.mcache[nj];   // job nj's result lands in cache entry nj
-    dst.slot_a = slot_l; dst.slot_b = partner[k];
-    dst.selector = c->pm_selector; dst.cross = c->pm_cross; dst.ratio = c->pm_ratio;
-    dst.valid = true;   // generations are stamped after the slots' counts are known
+    // job nj's result lands in cache entry nj; the generations are provisional: they are stamped after the slots' counts are known
+    set.mcache.record(nj, slot_l, partner[k], a.gen, b.gen, c->pm_selector, c->pm_cross, c->pm_ratio, set.h_match_out + (size_t)nj * c->match_cap);
     ++nj;
   }
   if (nj == 0) return SPVO_OK;
@@ -446,7 +443,7 @@ static int detect_submit(spvo_ctx *c, const uint8_t *d_l, const uint8_t *d_r, in
   }
   const int ring = (int)(c->submit_count++ % RING);
   SubmitSet &set = c->sets[ring];
-  for (auto &mc : set.mcache) mc.valid = false;
+  set.mcache.invalidate();
   // The bulk results a host-image submission takes back (`extras`) are WRITTEN into the set's pinned mirrors by kernels (posted PCIe
   // writes), never copied behind events: a device-to-host copy waiting for its event occupies an SDMA queue, and the NEXT pair's image
   // upload queued on the same engine waits with it (round 3: bench.py's look-ahead leg 0.95 ms per frame, the same calls from
@@ -808,7 +805,7 @@ static int detect_wait(spvo_ctx *c, double P_l[12], double P_r[12], spvo_feature
     }
     if (res[i] && (pd.extras & 1)) std::memcpy(res[i], set.h_resized + (size_t)i * c->H * c->W, (size_t)c->H * c->W);
   }
-  for (auto &mc : set.mcache)
+  for (MatchCache &mc : set.mcache.e)
     if (mc.valid) { mc.gen_a = c->slots[mc.slot_a].gen; mc.gen_b = c->slots[mc.slot_b].gen; }
   if (mirrors)
     for (int i = 0; i < 2; ++i) {

@@ -96,47 +96,76 @@ struct Stage {
 
 struct Pending { int stage; hipEvent_t e0, e1; double flops = 0, bytes = 0; };
 
-struct FeatureSlot {
+// what every kind of feature slot keeps about its contents; the host's side of the resident-pair protocol
+struct SlotState {
   int n = 0;
-  bool filled = false;      // a submission has written (or is writing) this slot
+  bool filled = false;         // a submission / call has written (or is writing) this slot
+  int *d_n = nullptr;          // device copy of n (read by kernels enqueued before the host knows n)
+  unsigned long long gen = 0;  // bumped whenever the slot is rewritten
+};
+// the slot is being rewritten: it holds nothing, and whatever was matched against its old contents is stale
+inline void slot_rewrite(SlotState &s) { s.filled = false; s.n = 0; ++s.gen; }
+
+struct FeatureSlot : SlotState {
   int *d_xy = nullptr;      // [cap][2] int
   float *d_desc = nullptr;  // [cap][256]
-  int *d_n = nullptr;       // device copy of n (read by kernels enqueued before the host knows n)
   float *d_sqn = nullptr;   // [cap] squared norms of the descriptors (written by the sampler)
-  unsigned long long gen = 0;  // bumped whenever the slot is rewritten
 };
 
 // a classic stereo image's features, resident on the device (spvo_classic_detect -> spvo_match_hamming_slots); the buffers of all
 // binary slots have ONE capacity (spvo_ctx::bin.cap)
-struct BinarySlot {
-  int n = 0;
-  bool filled = false;
+struct BinarySlot : SlotState {
   OrbKeypoint *d_kp = nullptr;   // [cap] x, y, angle, response, octave
   uint32_t *d_desc = nullptr;    // [cap][16] allocated for the widest row; the matcher's row format: row_bytes / 4 words back to back, nothing to pad
   int row_bytes = 32;            // width of the rows it holds: 32 (the ORB extractor) or 64 (BRISK); two slots are matched only at one width
-  int *d_n = nullptr;            // device copy of n (read by kernels enqueued before the host knows n)
-  unsigned long long gen = 0;    // bumped whenever the slot is rewritten
 };
 
 // a SIFT stereo image's features, resident on the device (spvo_sift_detect_pair -> spvo_match_l2_slots) in the L2 matcher's row format; the
 // buffers of all SIFT slots have ONE capacity (spvo_ctx::sift.slot_cap)
-struct SiftSlot {
-  int n = 0;
-  bool filled = false;
+struct SiftSlot : SlotState {
   float *d_desc = nullptr;       // [cap][256] 128 integers as float, columns 128.. zero
   float *d_sqn = nullptr;        // [cap] squared norms (exact integers)
   SiftSrc *d_src = nullptr;      // [cap] candidate and angle every row came from
-  int *d_n = nullptr;            // device copy of n (read by kernels enqueued before the host knows n)
-  unsigned long long gen = 0;    // bumped whenever the slot is rewritten
 };
 
-// matches enqueued together with the detector (spvo_set_prematch); results live in pinned memory
+// a match enqueued together with the detector (spvo_set_prematch); the result lives in pinned memory
 struct MatchCache {
   bool valid = false;
   int slot_a = -1, slot_b = -1, selector = 0, cross = 0;
   float ratio = 0.f;
   unsigned long long gen_a = 0, gen_b = 0;
-  int2 *h_out = nullptr;      // pinned [cap] packed {train_idx, distance bits}
+  int2 *h_out = nullptr;      // pinned [cap] packed {train_idx, distance bits}; meaningful while `valid`
+};
+
+// the two prematches of one owner (a submission set, the binary slots, the SIFT slots); slot numbers are the owner's kind of slot
+struct PrematchCache {
+  MatchCache e[2];            // [stereo, temporal]
+  void invalidate() { for (MatchCache &m : e) m.valid = false; }
+  // the stored result of exactly this match of exactly these slot contents, or NULL
+  const MatchCache *find(int slot_a, int slot_b, unsigned long long gen_a, unsigned long long gen_b, int selector, int cross, float ratio) const {
+    for (const MatchCache &m : e)
+      if (m.valid && m.slot_a == slot_a && m.slot_b == slot_b && m.gen_a == gen_a && m.gen_b == gen_b && m.selector == selector && m.cross == cross && m.ratio == ratio) return &m;
+    return nullptr;
+  }
+  void record(int entry, int slot_a, int slot_b, unsigned long long gen_a, unsigned long long gen_b, int selector, int cross, float ratio, int2 *h_out) {
+    e[entry] = MatchCache{true, slot_a, slot_b, selector, cross, ratio, gen_a, gen_b, h_out};
+  }
+};
+
+// What a "stereo pair into two slots" entry point (spvo_classic_detect, spvo_sift_detect_pair) stages a call through: the pinned copy of
+// both images, the events the host and the matcher wait for, the temporal partner and the call's prematches.  Works on the solver's stream.
+struct PairStage {
+  uint8_t *h_img = nullptr;            // pinned [2][img_cap]: both images of a call, rows packed
+  size_t img_cap = 0;
+  hipEvent_t ev_feat = nullptr, ev_match = nullptr;   // features of the last call final / its prematches landed
+  int last_slot_l = -1;                // left slot of the previous call (temporal partner)
+  PrematchCache mcache;
+  int ensure(spvo_ctx *c, size_t px);  // the events on first use, h_img grown to images of `px` bytes
+  // both images with packed rows (of a strided view only the rows' own bytes are the caller's); h_img must be the caller's to write
+  void stage(const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride);
+  // the previous call's left slot if it survives this call and `partner_ok` (it is filled, and whatever else its kind of slot asks), else -1
+  int temporal_partner(int slot_l, int slot_r, bool partner_ok) const { return last_slot_l >= 0 && last_slot_l != slot_l && last_slot_l != slot_r && partner_ok ? last_slot_l : -1; }
+  void release();
 };
 
 struct MatchScratch {         // one set per concurrently enqueued match
@@ -176,7 +205,7 @@ struct SubmitSet {
   hipEvent_t ev_up = nullptr;    // a queued host-image submission's upload, on the solver's stream, has landed (its preprocess kernel waits for it)
   hipEvent_t ev_heads = nullptr; // the group's heads are done (tail_streams == 2, heads on the tail stream: the second pair's stream waits for it)
   GraphEntry seg_T[2], seg_H[2], seg_A, seg_B;   // launch segments: trunk / heads per pairs in the group (the set is the group's network set); the two halves of the set's tail
-  MatchCache mcache[2];          // [stereo, temporal]
+  PrematchCache mcache;
   int2 *h_match_out = nullptr;   // pinned [2][cap] (ensure_match)
 };
 
@@ -344,8 +373,7 @@ struct spvo_ctx {
   struct BinaryBufs {
     int cap = 0;
     BinarySlot slots[N_BIN_SLOTS];
-    uint8_t *h_img = nullptr;            // pinned [2][img_cap]: both images of a call, rows packed
-    size_t img_cap = 0;
+    PairStage pair;                      // (its prematches' slot numbers are BINARY slots)
     OrbKeypoint *h_kp = nullptr;         // pinned [2][cap]      what the finishing kernel of an image writes for the host:
     uint8_t *h_desc = nullptr;           // pinned [2][cap][64]  keypoint records, descriptors ([2][cap][32] in its front part for the 32-byte kinds),
     int *h_n = nullptr;                  // pinned [2][4]        {rows found, overflow flag of the detector}
@@ -354,9 +382,6 @@ struct spvo_ctx {
     float *d_kresp = nullptr;            // [cap]    ... and the detector's responses of those (also brisk_compact_list_kernel's)
     unsigned long long *d_vote = nullptr;   // [cap] cross-check votes
     int2 *h_match = nullptr;             // pinned [3][cap]: the two prematches, the synchronous call
-    MatchCache mcache[2];                // [stereo, temporal]: slot numbers are BINARY slots
-    hipEvent_t ev_feat = nullptr, ev_match = nullptr;   // features of the last call final / its prematches landed
-    int last_slot_l = -1;                // left slot of the previous call (temporal partner)
   } bin;
   // BRISK extractor for given keypoints (brisk.hip.h) on the image resident in `cls`: the pattern tables (uploaded on the first call), the
   // integral image, the keypoint list with its results and their pinned mirrors; buffers grow on demand
@@ -404,17 +429,13 @@ struct spvo_ctx {
     // matches enqueued with the detector (spvo_set_prematch).  Features on the solver's stream, matches where the L2 matcher runs (PostScope).
     int slot_cap = 0;
     SiftSlot slots[N_SIFT_SLOTS];
-    uint8_t *h_img = nullptr;            // pinned [2][h_img_cap]: both images of a call, rows packed
-    size_t h_img_cap = 0;
+    PairStage pair;                      // (its prematches' slot numbers are SIFT slots)
     SiftSrc *h_src = nullptr;            // pinned [2][slot_cap]      what sift_gather_kernel writes for the host: sources,
     float *hm_desc = nullptr;            // pinned [2][slot_cap][128] descriptors,
     int *h_n = nullptr;                  // pinned [2][4]             {final rows, candidates counted, raw rows counted}
     int2 *h_match = nullptr;             // pinned [2][h_match_cap]: the two prematches (enqueue_matches spaces its jobs by spvo_ctx::match_cap)
     int h_match_cap = 0;
-    MatchCache mcache[2];                // [stereo, temporal]: slot numbers are SIFT slots
-    hipEvent_t ev_feat = nullptr, ev_match = nullptr;   // features of the last call final / its prematches landed
-    bool match_pending = false;          // ev_match has been recorded: a later call's kernels wait for it before they rewrite a slot
-    int last_slot_l = -1;                // left slot of the previous call (temporal partner)
+    bool match_pending = false;          // pair.ev_match has been recorded: a later call's kernels wait for it before they rewrite a slot
   } sift;
   // Hamming matcher (classic front end's binary descriptors): rows padded to 16 words
   int ham_cap = 0;
@@ -486,6 +507,39 @@ template <typename T, typename... Rest>
 void dev_free(T *&p, Rest *&...rest) {
   if (p) { (void)hipFree(p); p = nullptr; }
   if constexpr (sizeof...(rest) > 0) dev_free(rest...);
+}
+
+// pinned host buffers, where there is one, freed and forgotten
+template <typename T, typename... Rest>
+void host_free(T *&p, Rest *&...rest) {
+  if (p) { (void)hipHostFree(p); p = nullptr; }
+  if constexpr (sizeof...(rest) > 0) host_free(rest...);
+}
+
+inline int PairStage::ensure(spvo_ctx *c, size_t px) {
+  if (!ev_feat) {
+    HIP_TRY(c, hipEventCreateWithFlags(&ev_feat, hipEventDisableTiming));
+    HIP_TRY(c, hipEventCreateWithFlags(&ev_match, hipEventDisableTiming));
+  }
+  if (px > img_cap) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream2));
+    host_free(h_img);
+    img_cap = 0;
+    HIP_TRY(c, hipHostMalloc((void **)&h_img, 2 * px));
+    img_cap = px;
+  }
+  return SPVO_OK;
+}
+inline void PairStage::stage(const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride) {
+  const uint8_t *imgs[2] = {img_l, img_r};
+  const size_t px = (size_t)rows * cols;
+  for (int k = 0; k < 2; ++k)
+    for (int r = 0; r < rows; ++r) std::memcpy(h_img + k * px + (size_t)r * cols, imgs[k] + (size_t)r * stride, cols);
+}
+inline void PairStage::release() {
+  host_free(h_img);
+  for (hipEvent_t *e : {&ev_feat, &ev_match}) if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }
+  img_cap = 0;
 }
 
 // the synchronous entry points that work in the submissions' buffers refuse to run beside them; a failed wait / record: "`what` failed"
@@ -587,22 +641,23 @@ void classic_release_slots(spvo_ctx *c);   // ... the part of it that is sized b
 int classic_upload_image(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride);
 // ---- spvo_brisk.hip
 void brisk_release(spvo_ctx *c);     // frees spvo_ctx::brisk (spvo_destroy)
+// what spvo_brisk_describe refuses of an image, for every entry point that runs the extractor (`who` names it in the error text)
+int brisk_check_image(spvo_ctx *c, const char *who, int rows, int cols);
 // The extractor as a link of spvo_classic_detect's chain (kinds SPVO_CLASSIC_*_BRISK).  brisk_chain_ensure: the tables, the integral image
 // of a rows x cols image and the keypoint buffers for `cap` rows.  brisk_chain_enqueue, on the solver's stream behind a detector that left
 // its list in spvo_ctx::cls (xy, resp, counters[2]): integral image, border rule of keypoints of ONE `size` as a compaction that keeps at
 // most `cap` rows and counts all, descriptors of at most `most` <= cap rows into the slot, and the finish launch -- records, rows and
 // count of the slot, and their pinned mirrors (h_n = {rows that passed the border rule, overflow flag of the detector}).
 int brisk_chain_ensure(spvo_ctx *c, int rows, int cols, int cap);
-struct BriskChainOut {
-  int *cnt;               // [CLS_COUNTER_INTS] 0: kept in all, 2: kept and described
+struct ChainOut {         // where image k of a spvo_classic_detect call leaves its rows (every chain's, the ORB kinds' included)
+  int *cnt;               // [CLS_COUNTER_INTS] the extractor's counter block: 0: kept in all, 2: kept and described
   float *kresp;           // [cap] the detector's responses of the kept
   OrbKeypoint *d_kp; uint32_t *d_desc; int *d_n;          // the slot
   int *h_n; OrbKeypoint *h_kp; uint8_t *h_desc;           // its pinned mirrors
 };
-int brisk_chain_enqueue(spvo_ctx *c, int rows, int cols, float size, int cap, int most, const BriskChainOut &o);
+int brisk_chain_enqueue(spvo_ctx *c, int rows, int cols, float size, int cap, int most, const ChainOut &o);
 // ---- spvo_sift.hip
 void sift_release(spvo_ctx *c);      // frees spvo_ctx::sift (spvo_destroy)
-void sift_invalidate_matches(spvo_ctx *c);   // the stored prematches of the SIFT slots are stale (spvo_set_prematch, spvo_set_match_fp8)
 // ---- spvo_match.hip
 int ensure_match(spvo_ctx *c, int na, int nb);
 struct MatchReq {

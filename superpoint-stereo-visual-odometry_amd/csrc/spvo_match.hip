@@ -12,16 +12,14 @@ int ensure_match(spvo_ctx *c, int na, int nb) {
   // every pointer is cleared as it is freed and the capacity drops to 0 first: an allocation failure further down leaves a
   // context that spvo_destroy (and a later, smaller request) can still handle
   c->match_cap = 0;
-  auto drop = [](auto *&p) { if (p) (void)hipFree(p); p = nullptr; };
-  drop(c->d_ma); drop(c->d_mb); drop(c->d_match_out);
+  dev_free(c->d_ma, c->d_mb, c->d_match_out);
   for (auto &set : c->ms)
     for (auto &m : set) {
-      drop(m.d_na); drop(m.d_nb); drop(m.d_best_d2); drop(m.d_dt); drop(m.d_cand); drop(m.d_meta); drop(m.d_best_idx); drop(m.d_train_best); drop(m.d_a8); drop(m.d_b8); drop(m.d_qa8); drop(m.d_qb8);
+      dev_free(m.d_na, m.d_nb, m.d_best_d2, m.d_dt, m.d_cand, m.d_meta, m.d_best_idx, m.d_train_best, m.d_a8, m.d_b8, m.d_qa8, m.d_qb8);
       m.d_out = nullptr;
     }
   for (SubmitSet &s : c->sets) set_release_match(s);
-  if (c->h_match_tmp) (void)hipHostFree(c->h_match_tmp);
-  c->h_match_tmp = nullptr;
+  host_free(c->h_match_tmp);
   int rc;
   if ((rc = dev_alloc(c, &c->d_ma, (size_t)cap * MATCH_D))) return rc;
   if ((rc = dev_alloc(c, &c->d_mb, (size_t)cap * MATCH_D))) return rc;
@@ -44,10 +42,7 @@ int ensure_match(spvo_ctx *c, int na, int nb) {
     if ((rc = dev_alloc(c, &m.d_qb8, cap))) return rc;
     m.d_out = c->d_match_out + (size_t)k4 * cap;
   }
-  for (SubmitSet &s : c->sets) {
-    HIP_TRY(c, hipHostMalloc((void **)&s.h_match_out, (size_t)2 * cap * sizeof(int2)));
-    for (int k = 0; k < 2; ++k) s.mcache[k].h_out = s.h_match_out + (size_t)k * cap;   // (not valid: set_release_match)
-  }
+  for (SubmitSet &s : c->sets) HIP_TRY(c, hipHostMalloc((void **)&s.h_match_out, (size_t)2 * cap * sizeof(int2)));
   HIP_TRY(c, hipHostMalloc((void **)&c->h_match_tmp, (size_t)cap * sizeof(int2)));
   c->match_cap = cap;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -235,8 +230,7 @@ int spvo_match_hamming(spvo_ctx *c, const uint8_t *desc_a, int na, const uint8_t
   const int need = std::max(na, nb);
   if (need > c->ham_cap) {
     HIP_TRY(c, hipStreamSynchronize(c->stream2));
-    for (void *p : {(void *)c->d_ham_a, (void *)c->d_ham_b, (void *)c->d_ham_idx, (void *)c->d_ham_dist, (void *)c->d_ham_vote}) if (p) (void)hipFree(p);
-    c->d_ham_a = c->d_ham_b = nullptr; c->d_ham_idx = nullptr; c->d_ham_dist = nullptr; c->d_ham_vote = nullptr;
+    dev_free(c->d_ham_a, c->d_ham_b, c->d_ham_idx, c->d_ham_dist, c->d_ham_vote);
     c->ham_cap = 0;
     const int cap = std::max(need, 2048);
     int rc;
@@ -283,16 +277,14 @@ int spvo_match_slots(spvo_ctx *c, int slot_a, int slot_b, int selector, int cros
     bool inflight = false;
     for (const auto &q : c->pendq) inflight |= q.ring == set;
     if (inflight) continue;   // that set belongs to a submission in flight
-    for (const auto &mc : c->sets[set].mcache)
-      if (mc.valid && mc.slot_a == slot_a && mc.slot_b == slot_b && mc.gen_a == a.gen && mc.gen_b == b.gen && mc.selector == selector &&
-          mc.cross == (cross_check ? 1 : 0) && mc.ratio == ratio) {
-        // the matches were enqueued behind the submission's features; spvo_detect_wait returned when the features were final
-        const double tw0 = diag_now_us();
-        HIP_TRY(c, wait_event(c->sets[set].ev_tail));
-        g_diag.iv_match += diag_now_us() - tw0;
-        if (a.n > 0) unpack_match(mc.h_out, a.n, train_idx, distance);
-        return SPVO_OK;
-      }
+    if (const MatchCache *mc = c->sets[set].mcache.find(slot_a, slot_b, a.gen, b.gen, selector, cross_check ? 1 : 0, ratio)) {
+      // the matches were enqueued behind the submission's features; spvo_detect_wait returned when the features were final
+      const double tw0 = diag_now_us();
+      HIP_TRY(c, wait_event(c->sets[set].ev_tail));
+      g_diag.iv_match += diag_now_us() - tw0;
+      if (a.n > 0) unpack_match(mc->h_out, a.n, train_idx, distance);
+      return SPVO_OK;
+    }
   }
   ++g_diag.match_miss;
   for (const auto &q : c->pendq)
@@ -318,12 +310,11 @@ int spvo_match_hamming_slots(spvo_ctx *c, int slot_a, int slot_b, int selector, 
   if (a.n > 0 && (!train_idx || !distance)) return fail(c, SPVO_ERR_INVALID, "null output");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   const int cross = cross_check ? 1 : 0;
-  for (const auto &mc : bb.mcache)
-    if (mc.valid && mc.slot_a == slot_a && mc.slot_b == slot_b && mc.gen_a == a.gen && mc.gen_b == b.gen && mc.selector == selector && mc.cross == cross && mc.ratio == ratio) {
-      HIP_TRY(c, wait_event(bb.ev_match));
-      unpack_match(mc.h_out, a.n, train_idx, distance);
-      return SPVO_OK;
-    }
+  if (const MatchCache *mc = bb.pair.mcache.find(slot_a, slot_b, a.gen, b.gen, selector, cross, ratio)) {
+    HIP_TRY(c, wait_event(bb.pair.ev_match));
+    unpack_match(mc->h_out, a.n, train_idx, distance);
+    return SPVO_OK;
+  }
   if (a.n == 0) return SPVO_OK;
   int2 *h = bb.h_match + (size_t)2 * bb.cap;
   if (int rc = enqueue_hamming_slots(c, slot_a, slot_b, selector, cross, ratio, h)) return rc;
@@ -348,15 +339,14 @@ int spvo_match_l2_slots(spvo_ctx *c, int slot_a, int slot_b, int selector, int c
   }
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   const int cross = cross_check ? 1 : 0;
-  for (const auto &mc : sf.mcache)
-    if (mc.valid && mc.slot_a == slot_a && mc.slot_b == slot_b && mc.gen_a == a.gen && mc.gen_b == b.gen && mc.selector == selector && mc.cross == cross && mc.ratio == ratio) {
-      HIP_TRY(c, wait_event(sf.ev_match));
-      unpack_match(mc.h_out, a.n, train_idx, distance);
-      return SPVO_OK;
-    }
+  if (const MatchCache *mc = sf.pair.mcache.find(slot_a, slot_b, a.gen, b.gen, selector, cross, ratio)) {
+    HIP_TRY(c, wait_event(sf.pair.ev_match));
+    unpack_match(mc->h_out, a.n, train_idx, distance);
+    return SPVO_OK;
+  }
   PostScope ps(c);   // behind the queued tails: they share the matcher's scratch
   if (int rc = ensure_match(c, a.n, b.n)) return rc;
-  HIP_TRY(c, hipStreamWaitEvent(c->post, sf.ev_feat, 0));   // behind the feature chain (the solver's stream)
+  HIP_TRY(c, hipStreamWaitEvent(c->post, sf.pair.ev_feat, 0));   // behind the feature chain (the solver's stream)
   return run_match(c, MatchReq{a.d_desc, b.d_desc, a.n, b.n, a.d_n, b.d_n, a.d_sqn, b.d_sqn}, selector, cross, ratio, train_idx, distance);
 }
 
@@ -367,19 +357,17 @@ int spvo_set_prematch(spvo_ctx *c, int enable, int selector, int cross_check, fl
   c->pm_selector = selector;
   c->pm_cross = cross_check ? 1 : 0;
   c->pm_ratio = ratio;
-  for (SubmitSet &s : c->sets)
-    for (auto &mc : s.mcache) mc.valid = false;
-  for (auto &mc : c->bin.mcache) mc.valid = false;
-  sift_invalidate_matches(c);
+  for (SubmitSet &s : c->sets) s.mcache.invalidate();
+  c->bin.pair.mcache.invalidate();
+  c->sift.pair.mcache.invalidate();
   return SPVO_OK;
 }
 
 int spvo_set_match_fp8(spvo_ctx *c, int enable) {
   if (!c) return fail(c, SPVO_ERR_INVALID, "null context");
   c->match_fp8 = enable != 0;
-  for (SubmitSet &s : c->sets)
-    for (auto &mc : s.mcache) mc.valid = false;
-  sift_invalidate_matches(c);
+  for (SubmitSet &s : c->sets) s.mcache.invalidate();
+  c->sift.pair.mcache.invalidate();   // (not the binary slots': a Hamming match does not depend on fp8)
   return SPVO_OK;
 }
 

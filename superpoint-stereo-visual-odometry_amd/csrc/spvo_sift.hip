@@ -14,6 +14,13 @@
 namespace {
 constexpr int SIFT_MIN_SIDE = 6;   // 2 x 6 = 12 > 2 x border: the first octave has an interior; the octave rule then gives >= 2 octaves
 
+// the images spvo_sift_detect and spvo_sift_detect_pair (`who`, for the error text) refuse
+int sift_check_image(spvo_ctx *c, const char *who, int rows, int cols) {
+  if (rows < SIFT_MIN_SIDE || cols < SIFT_MIN_SIDE) return fail(c, SPVO_ERR_INVALID, "%s: images of at least %d x %d (the first octave needs an interior)", who, SIFT_MIN_SIDE, SIFT_MIN_SIDE);
+  if ((size_t)rows * cols > ((size_t)1 << 26)) return fail(c, SPVO_ERR_INVALID, "%s: image too large", who);
+  return SPVO_OK;
+}
+
 // tests/sift_ref.py: blur_taps -- double on the host, rounded to float once
 bool sift_taps(double sigma, SiftTaps &tp) {
   const int r = (((int)std::nearbyint(sigma * 8 + 1) | 1) - 1) / 2;
@@ -183,28 +190,17 @@ void sift_release_slots(spvo_ctx *c) {
   auto &s = c->sift;
   for (SiftSlot &sl : s.slots) {
     dev_free(sl.d_desc, sl.d_sqn, sl.d_src, sl.d_n);
-    sl.filled = false; sl.n = 0; ++sl.gen;
+    slot_rewrite(sl);
   }
-  for (void *p : {(void *)s.h_src, (void *)s.hm_desc, (void *)s.h_n}) if (p) (void)hipHostFree(p);
-  s.h_src = nullptr; s.hm_desc = nullptr; s.h_n = nullptr;
-  for (auto &mc : s.mcache) mc.valid = false;
-  s.slot_cap = 0; s.last_slot_l = -1;
+  host_free(s.h_src, s.hm_desc, s.h_n);
+  s.pair.mcache.invalidate();
+  s.slot_cap = 0; s.pair.last_slot_l = -1;
 }
 
 // the SIFT slots and the call's own buffers for `cap` rows per slot and images of `px` bytes; growing un-fills every slot
 int sift_slots_ensure(spvo_ctx *c, int cap, size_t px) {
   auto &s = c->sift;
-  if (!s.ev_feat) {
-    HIP_TRY(c, hipEventCreateWithFlags(&s.ev_feat, hipEventDisableTiming));
-    HIP_TRY(c, hipEventCreateWithFlags(&s.ev_match, hipEventDisableTiming));
-  }
-  if (px > s.h_img_cap) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream2));
-    if (s.h_img) (void)hipHostFree(s.h_img);
-    s.h_img = nullptr; s.h_img_cap = 0;
-    HIP_TRY(c, hipHostMalloc((void **)&s.h_img, 2 * px));
-    s.h_img_cap = px;
-  }
+  if (int rc = s.pair.ensure(c, px)) return rc;
   if (cap <= s.slot_cap) return SPVO_OK;
   HIP_TRY(c, hipDeviceSynchronize());   // (a match may still read the slots where the L2 matcher runs)
   s.match_pending = false;
@@ -222,27 +218,20 @@ int sift_slots_ensure(spvo_ctx *c, int cap, size_t px) {
 }
 }  // namespace
 
-void spvo_int::sift_invalidate_matches(spvo_ctx *c) {
-  for (auto &mc : c->sift.mcache) mc.valid = false;
-}
-
 void spvo_int::sift_release(spvo_ctx *c) {
   auto &s = c->sift;
   sift_release_slots(c);
   dev_free(s.img, s.pyr, s.desc, s.cand_pos, s.cand_off, s.kp, s.counters, s.keys, s.sorted, s.order, s.ord_n);
-  for (void *p : {(void *)s.h_img, (void *)s.h_match}) if (p) (void)hipHostFree(p);
-  s.h_img = nullptr; s.h_match = nullptr; s.h_img_cap = 0; s.h_match_cap = 0;
-  if (s.ev_feat) (void)hipEventDestroy(s.ev_feat);
-  if (s.ev_match) (void)hipEventDestroy(s.ev_match);
-  s.ev_feat = s.ev_match = nullptr;
+  host_free(s.h_match);
+  s.h_match_cap = 0;
+  s.pair.release();
 }
 
 extern "C" {
 
 int spvo_sift_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride, spvo_sift_keypoint *kp_out, float *desc_out, int cap, int *n_out) {
   if (!c || !img || !n_out || rows <= 0 || cols <= 0 || stride < (size_t)cols || cap < 0 || (cap > 0 && (!kp_out || !desc_out))) return fail(c, SPVO_ERR_INVALID, "bad argument");
-  if (rows < SIFT_MIN_SIDE || cols < SIFT_MIN_SIDE) return fail(c, SPVO_ERR_INVALID, "spvo_sift_detect: images of at least %d x %d (the first octave needs an interior)", SIFT_MIN_SIDE, SIFT_MIN_SIDE);
-  if ((size_t)rows * cols > ((size_t)1 << 26)) return fail(c, SPVO_ERR_INVALID, "spvo_sift_detect: image too large");
+  if (int rc = sift_check_image(c, "spvo_sift_detect", rows, cols)) return rc;
   if (!c->pendq.empty()) return fail(c, SPVO_ERR_STATE, "detector submissions are in flight: complete them with spvo_detect_wait first");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   *n_out = 0;
@@ -323,13 +312,12 @@ int spvo_sift_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_
   for (auto *o : outs)
     if (o->cap < 0 || (o->cap > 0 && (!o->kp || !o->desc))) return fail(c, SPVO_ERR_INVALID, "bad output buffer");
   if (slot_capacity <= 0 || slot_capacity > SIFT_SLOT_MAX) return fail(c, SPVO_ERR_INVALID, "slot_capacity must be 1 .. %d", SIFT_SLOT_MAX);
-  // what spvo_sift_detect refuses
-  if (rows < SIFT_MIN_SIDE || cols < SIFT_MIN_SIDE) return fail(c, SPVO_ERR_INVALID, "spvo_sift_detect_pair: images of at least %d x %d (the first octave needs an interior)", SIFT_MIN_SIDE, SIFT_MIN_SIDE);
-  if ((size_t)rows * cols > ((size_t)1 << 26)) return fail(c, SPVO_ERR_INVALID, "spvo_sift_detect_pair: image too large");
+  if (int rc = sift_check_image(c, "spvo_sift_detect_pair", rows, cols)) return rc;
   if (!c->pendq.empty()) return fail(c, SPVO_ERR_STATE, "detector submissions are in flight: complete them with spvo_detect_wait first");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   out_l->n = out_r->n = 0;
   auto &s = c->sift;
+  PairStage &ps = s.pair;
   hipStream_t st = c->stream2;
   SiftPyr P{};
   const size_t pyr_floats = sift_plan(rows, cols, P), px = (size_t)rows * cols;
@@ -344,9 +332,9 @@ int spvo_sift_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_
     if (s.h_match_cap != c->match_cap) {
       HIP_TRY(c, hipDeviceSynchronize());
       s.match_pending = false;
-      if (s.h_match) (void)hipHostFree(s.h_match);
-      s.h_match = nullptr; s.h_match_cap = 0;
-      for (auto &mc : s.mcache) mc.valid = false;
+      host_free(s.h_match);
+      s.h_match_cap = 0;
+      ps.mcache.invalidate();
       HIP_TRY(c, hipHostMalloc((void **)&s.h_match, (size_t)2 * c->match_cap * sizeof(int2)));
       s.h_match_cap = c->match_cap;
     }
@@ -354,34 +342,31 @@ int spvo_sift_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_
   P.pyr = s.pyr;
   // both slots are being rewritten: whatever was matched against their old contents is stale
   const int slots[2] = {slot_l, slot_r};
-  for (int sl : slots) { SiftSlot &t = s.slots[sl]; t.filled = false; t.n = 0; ++t.gen; }
-  for (auto &mc : s.mcache) mc.valid = false;
-  const int prev_l = s.last_slot_l;
-  s.last_slot_l = -1;
+  for (int sl : slots) slot_rewrite(s.slots[sl]);
+  ps.mcache.invalidate();
+  // (the temporal partner is forgotten BEFORE staging here: a call that fails from now on leaves none for the next call)
+  const int partner[2] = {slot_r, ps.temporal_partner(slot_l, slot_r, ps.last_slot_l >= 0 && s.slots[ps.last_slot_l].filled)};
+  ps.last_slot_l = -1;
   HIP_TRY(c, hipStreamSynchronize(st));   // (the staging buffer and the mirrors are the previous call's until its work is done)
-  const uint8_t *imgs[2] = {img_l, img_r};
-  for (int k = 0; k < 2; ++k)
-    for (int r = 0; r < rows; ++r) std::memcpy(s.h_img + k * px + (size_t)r * cols, imgs[k] + (size_t)r * stride, cols);
-  const bool temporal = prev_l >= 0 && prev_l != slot_l && prev_l != slot_r && s.slots[prev_l].filled;
+  ps.stage(img_l, img_r, rows, cols, stride);
   int njobs = 0;
   for (int attempt = 0;; ++attempt) {
     // a match of an earlier call (or of the attempt before) may still read the slots where the L2 matcher runs
-    if (s.match_pending) HIP_TRY(c, hipStreamWaitEvent(st, s.ev_match, 0));
+    if (s.match_pending) HIP_TRY(c, hipStreamWaitEvent(st, ps.ev_match, 0));
     for (int k = 0; k < 2; ++k) {   // left chain, then the right one: the one resident pyramid is reused in stream order
       s.rows = s.cols = 0;
-      HIP_TRY(c, hipMemcpyAsync(s.img, s.h_img + k * px, px, hipMemcpyHostToDevice, st));
+      HIP_TRY(c, hipMemcpyAsync(s.img, ps.h_img + k * px, px, hipMemcpyHostToDevice, st));
       if (int rc = sift_enqueue_pyramid(c, rows, cols, P)) return rc;
       s.plan = P; s.rows = rows; s.cols = cols;
       if (int rc = sift_enqueue_features(c, P)) return rc;
       if (int rc = sift_enqueue_order(c, s.slots[slots[k]], k)) return rc;
     }
-    HIP_TRY(c, hipEventRecord(s.ev_feat, st));
+    HIP_TRY(c, hipEventRecord(ps.ev_feat, st));
     // spvo_set_prematch: the two standard matches as ONE set of launches behind the features, counts read on the device (a pair that turns
     // out not to fit its slots is matched on whatever rows the slots hold; that result is dropped below)
     njobs = 0;
     if (c->prematch) {
-      PostScope ps(c);
-      const int partner[2] = {slot_r, temporal ? prev_l : -1};
+      PostScope post(c);
       MatchReq req[2];
       const SiftSlot &a = s.slots[slot_l];
       for (int k = 0; k < 2; ++k) {
@@ -389,18 +374,18 @@ int spvo_sift_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_
         const SiftSlot &b = s.slots[partner[k]];
         req[njobs++] = MatchReq{a.d_desc, b.d_desc, cap, cap, a.d_n, b.d_n, a.d_sqn, b.d_sqn};
       }
-      HIP_TRY(c, hipStreamWaitEvent(c->post, s.ev_feat, 0));
+      HIP_TRY(c, hipStreamWaitEvent(c->post, ps.ev_feat, 0));
       if (int rc = enqueue_matches(c, req, njobs, c->pm_selector, c->pm_cross, c->pm_ratio, s.h_match)) return rc;
-      HIP_TRY(c, hipEventRecord(s.ev_match, c->post));
+      HIP_TRY(c, hipEventRecord(ps.ev_match, c->post));
       s.match_pending = true;
     }
-    HIP_TRY(c, wait_event(s.ev_feat));   // the one wait of the call: the matches go on behind it
+    HIP_TRY(c, wait_event(ps.ev_feat));   // the one wait of the call: the matches go on behind it
     int most = 0;
     for (int k = 0; k < 2; ++k) most = std::max(most, std::max(s.h_n[4 * k + 1], s.h_n[4 * k + 2]));
     if (most <= s.cand_cap) break;
     // more candidates (or raw rows) than the lists hold: grow them to what was counted and run the pair again (a second wait)
     if (attempt >= 2) return fail(c, SPVO_ERR_CAPACITY, "spvo_sift_detect_pair: %d candidates / keypoints do not fit", most);
-    if (s.match_pending) HIP_TRY(c, wait_event(s.ev_match));
+    if (s.match_pending) HIP_TRY(c, wait_event(ps.ev_match));
     if (int rc = sift_ensure(c, rows, cols, pyr_floats, most + 1024)) return rc;
     if (int rc = sift_order_ensure(c, s.cand_cap)) return rc;
   }
@@ -414,21 +399,14 @@ int spvo_sift_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_
     for (int i = 0; i < ncopy; ++i) outs[k]->kp[i] = sift_record(src[i].pos, src[i].off, __builtin_bit_cast(int, src[i].angle));
     if (ncopy > 0) std::memcpy(outs[k]->desc, s.hm_desc + (size_t)k * cap * 128, (size_t)ncopy * 128 * sizeof(float));
   }
-  if (c->prematch) {
-    const SiftSlot &l = s.slots[slot_l];
-    const int partner[2] = {slot_r, temporal ? prev_l : -1};
-    int job = 0;
-    for (int k = 0; k < 2; ++k) {
+  if (c->prematch)
+    for (int k = 0, job = 0; k < 2; ++k) {
       if (partner[k] < 0) continue;
-      MatchCache &mc = s.mcache[job];   // job `job`'s result lands in cache entry `job`
-      mc.valid = true;
-      mc.h_out = s.h_match + (size_t)job * c->match_cap;
-      mc.slot_a = slot_l; mc.slot_b = partner[k]; mc.selector = c->pm_selector; mc.cross = c->pm_cross; mc.ratio = c->pm_ratio;
-      mc.gen_a = l.gen; mc.gen_b = s.slots[partner[k]].gen;
+      // job `job`'s result lands in cache entry `job`
+      ps.mcache.record(job, slot_l, partner[k], s.slots[slot_l].gen, s.slots[partner[k]].gen, c->pm_selector, c->pm_cross, c->pm_ratio, s.h_match + (size_t)job * c->match_cap);
       ++job;
     }
-  }
-  s.last_slot_l = slot_l;
+  ps.last_slot_l = slot_l;
   return SPVO_OK;
 }
 

@@ -190,10 +190,8 @@ int spvo_solve_submit(spvo_ctx *c, const spvo_solve_input *in) {
     double *d_res[NB] = {}, *h_res[NB] = {};
     auto release = [&](char **di, double **dr, char **dout, char **hi, double **hr, char **hout) {
       for (int sl = 0; sl < NB; ++sl) {
-        for (void *hp : {(void *)hi[sl], (void *)hr[sl], (void *)hout[sl]}) if (hp) (void)hipHostFree(hp);
-        for (void *dp : {(void *)di[sl], (void *)dr[sl], (void *)dout[sl]}) if (dp) (void)hipFree(dp);
-        hi[sl] = hout[sl] = nullptr; hr[sl] = nullptr;
-        di[sl] = dout[sl] = nullptr; dr[sl] = nullptr;
+        host_free(hi[sl], hr[sl], hout[sl]);
+        dev_free(di[sl], dr[sl], dout[sl]);
       }
     };
     hipError_t he = hipSuccess;

@@ -173,6 +173,42 @@ def test_prematch_is_transparent(sample_images, sequence, mode):
         assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
 
 
+def test_binary_and_sift_prematches_stay_independent(sample_images):
+    """Binary slots 0 / 1 and SIFT slots 0 / 1 of one context hold a pair each, with their prematches stored: rewriting the SIFT slots or
+    switching the fp8 shortlist (which drops the stored L2 matches only) leaves the stored Hamming match what it was, and every result
+    equals a context's that stores nothing.  64 x 96 crops, slots of 256 rows; FAST + BRISK because the ORB extractor's 31-pixel border
+    leaves next to nothing of such a crop (the CPU references find 77 / 75 rows and more in these crops)."""
+    def crop(i, r, c):
+        return np.ascontiguousarray(sample_images[i][r:r + 64, c:c + 96])
+
+    def same(a, b):
+        return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+
+    first, second = (crop(0, 150, 420), crop(1, 150, 420)), (crop(2, 150, 420), crop(0, 150, 500))
+    on, off = make_ctx(), make_ctx()
+    try:
+        on.set_prematch(True, "KNN", False, 0.8)
+        for c in (on, off):
+            bl, _ = c.classic_detect(*first, 0, 1, "FAST+BRISK", slot_capacity=256)
+            sl, _ = c.sift_detect_pair(*first, 0, 1, slot_capacity=256)
+            assert len(bl["xy"]) > 20 and sl["n"] > 20
+        ham = on.match_hamming_slots(0, 1, "KNN", False, 0.8)
+        assert (ham[0] >= 0).any()
+        assert same(ham, off.match_hamming_slots(0, 1, "KNN", False, 0.8))
+        assert same(on.match_l2_slots(0, 1, "KNN", False, 0.8), off.match_l2_slots(0, 1, "KNN", False, 0.8))
+        for c in (on, off):                                            # the SIFT slots of the same numbers hold another pair now
+            c.sift_detect_pair(*second, 0, 1, slot_capacity=256)
+        assert same(on.match_hamming_slots(0, 1, "KNN", False, 0.8), ham)
+        on.set_match_fp8(True)
+        on.set_match_fp8(False)
+        assert same(on.match_hamming_slots(0, 1, "KNN", False, 0.8), ham)
+        l2 = off.match_l2_slots(0, 1, "KNN", False, 0.8)
+        assert (l2[0] >= 0).any() and same(on.match_l2_slots(0, 1, "KNN", False, 0.8), l2)
+    finally:
+        on.close()
+        off.close()
+
+
 def test_status_codes(sample_images, squeeze_weights_path, sequence):
     frames, _, P_l, P_r = sequence
     c = make_ctx(squeeze_weights_path)
