@@ -320,6 +320,31 @@ int spvo_sift_detect(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, size
  * of octave 0.. (octave 0 is the doubled image).  `out` (rows x cols floats) may be NULL to ask for the shape only. */
 int spvo_sift_debug_level(spvo_ctx *ctx, int octave, int layer, int dog, float *out, int *rows, int *cols);
 
+/* detectKeypoints for DetectorType::BRISK (cv::BRISK::create() -> detect, feature_detection_classic.cpp:9-11: threshold 30, 3 octaves, pattern
+ * scale 1) on one 8-bit image in host memory: the six-layer scale space (layer 1 = two-thirds of the image, layer i >= 2 = half of layer
+ * i - 2, cv::resize(INTER_AREA)'s arithmetic), the dense AGAST 9-16 score of every layer (the largest b at which the FAST-9/16 segment test
+ * still holds: one less than spvo_fast_detect's response) and the 5-8 score of the image for the virtual layer below it, candidates with
+ * score >= threshold that pass isMax2D, and per candidate refine3D (the top layer: getScoreMaxBelow and its own 3 x 3 patch): sub-pixel
+ * position, continuous scale between the layers, refined score; kept iff that score > threshold (the top layer keeps all).  OpenCV is not
+ * available to this build: the algorithm is OpenCV 4.x's as far as it is known, as restated by tests/brisk_detect_ref.py (its header lists
+ * every choice -- among them that a score read is a pure function of the layer, where OpenCV's depends on what earlier keypoints left in
+ * its cache), and the kernels reproduce that restatement bit for bit in every field.  A record is (x, y, size = 12 * scale, angle = -1,
+ * response = refined score, octave = layer 0..5); keypoints come layer by layer, within a layer in raster order of the candidate.  `n`
+ * receives their number, of which min(n, cap) are written; strided input is accepted; a layer too small to have an interior contributes
+ * nothing.  The image stays on the device for a spvo_brisk_describe(img = NULL) that follows, exactly as after spvo_fast_detect.
+ *   SPVO_ERR_INVALID   threshold outside 1 .. 255; octaves != 3 (only the reference's six layers are built); an image smaller than 8 x 8;
+ *                      rows * cols * 255 >= 2^31 (so that the spvo_brisk_describe that follows cannot fail on its int32 integral image)
+ *   SPVO_ERR_STATE     a spvo_detect*_submit is in flight; the candidate list overflowed (it holds one entry per interior pixel of every
+ *                      layer, so this reports a defect, not an input) */
+typedef spvo_sift_keypoint spvo_brisk_keypoint;
+int spvo_brisk_detect(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, size_t stride, int threshold, int octaves,
+                      spvo_brisk_keypoint *kp /* [cap] */, int cap, int *n);
+/* A layer of the scale space of this context's last spvo_brisk_detect (test hook): what = 0 the layer's image, 1 its AGAST 9-16 score map,
+ * 2 (layer 0 only) the 5-8 score map.  `out` (rows x cols bytes) may be NULL to ask for the shape only.  SPVO_ERR_STATE when no result is
+ * resident: no call yet, or any other call has since put an image into the context's resident image buffer (spvo_gftt_detect,
+ * spvo_fast_detect, spvo_orb_describe / spvo_brisk_describe with an image, spvo_classic_detect), the same image included. */
+int spvo_brisk_detect_debug_layer(spvo_ctx *ctx, int layer, int what, uint8_t *out, int *rows, int *cols);
+
 /* ------------------------------------------------------- classic front end: one submission per stereo pair, features resident
  * detectKeypoints + describeKeypoints of ClassicFeatureFrontEnd for BOTH images of a stereo pair in one call: ORB, or Shi-Tomasi /
  * FAST followed by the ORB extractor or by the BRISK extractor (the five pairs the per-image entry points above cover).  Both images go up through pinned

@@ -56,27 +56,7 @@ __global__ __launch_bounds__(256) void orb_fast_kernel(const OrbLevels lv, int t
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (L.want <= 0 || x >= w || y >= h) return;
   int best = 0;
-  if (x >= edge && x < w - edge && y >= edge && y < h - edge) {
-    const uint8_t *p = L.im + (size_t)y * w + x;
-    const int c = *p;
-    const int off[16] = {-3 * w, -3 * w + 1, -2 * w + 2, -w + 3, 3, w + 3, 2 * w + 2, 3 * w + 1, 3 * w, 3 * w - 1, 2 * w - 2, w - 3, -3, -w - 3, -2 * w - 2, -3 * w - 1};
-    int d[25];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) d[i] = (int)p[off[i]] - c;
-    const int nb = (d[0] > t) + (d[4] > t) + (d[8] > t) + (d[12] > t), nd = (d[0] < -t) + (d[4] < -t) + (d[8] < -t) + (d[12] < -t);
-    if (nb >= 2 || nd >= 2) {
-#pragma unroll
-      for (int i = 16; i < 25; ++i) d[i] = d[i - 16];
-#pragma unroll
-      for (int s = 0; s < 16; ++s) {
-        int mn = 255, mx = -255;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) { mn = min(mn, d[s + k]); mx = max(mx, d[s + k]); }
-        if (mn > t) best = max(best, mn);
-        if (-mx > t) best = max(best, -mx);
-      }
-    }
-  }
+  if (x >= edge && x < w - edge && y >= edge && y < h - edge) best = fast916_arc_score(L.im + (size_t)y * w + x, w, t);   // (spvo_types.hip.h)
   L.score[(size_t)y * w + x] = (uint8_t)best;
 }
 

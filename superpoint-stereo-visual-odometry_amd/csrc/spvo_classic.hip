@@ -259,6 +259,7 @@ int cls_ensure(spvo_ctx *c, int rows, int cols) {
   hipStream_t st = c->stream2;
   const size_t px = (size_t)rows * cols, state_bytes = (size_t)(rows + 2 * CLS_PAD) * cls_state_pitch(cols);
   b.rows = b.cols = 0;   // nothing resident until the upload below is enqueued
+  ++b.image_gen;
   if (px > b.px_cap || state_bytes > b.state_cap) {
     HIP_TRY(c, hipStreamSynchronize(st));
     dev_free(b.im, b.score, b.blur, b.state, b.tmp, b.lam, b.xy, b.resp, b.keys, b.rank, b.cand);
@@ -462,6 +463,9 @@ int spvo_orb_describe(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_
 }  // extern "C"
 
 int spvo_int::classic_upload_image(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride) { return cls_prepare(c, img, rows, cols, stride); }
+void spvo_int::classic_rank_enqueue(spvo_ctx *c, const unsigned long long *keys, int *rank, const int *n_ptr, int cap) {
+  hipLaunchKernelGGL(cls_rank_kernel, dim3(128), dim3(256), 0, c->stream2, keys, rank, n_ptr, cap);
+}
 
 // ---------------------------------------------------------------- one submission per stereo pair, features stay on the device
 // everything bin_ensure sizes by the slot capacity; the slots are empty afterwards

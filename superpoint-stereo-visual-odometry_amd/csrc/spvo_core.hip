@@ -476,6 +476,7 @@ void spvo_destroy(spvo_ctx *c) {
   dev_free(o.im, o.score, o.blur, o.src, o.tmp, o.pattern, o.taps, o.keys, o.rank, o.out_xy, o.counters, o.tab, o.disc, o.kps, o.desc);
   sift_release(c);
   brisk_release(c);
+  brisk_detect_release(c);
   auto &b = c->cls;
   dev_free(b.im, b.score, b.blur, b.src, b.state, b.desc, b.tmp, b.lam, b.xy, b.resp, b.keys, b.rank, b.cand, b.counters, b.kp_xy, b.kps, b.pre_out, b.pre_tab);
   host_free(c->h_match_tmp);

@@ -357,6 +357,7 @@ struct spvo_ctx {
     size_t px_cap = 0, state_cap = 0, src_cap = 0;
     int kp_cap = 0;
     int rows = 0, cols = 0;               // shape of the image in `im` (0: none resident)
+    unsigned image_gen = 0;               // bumped whenever `im` is about to receive another image (cls_ensure): who caches results about `im` compares it
     int state_rows = 0, state_cols = 0;   // shape the state map's padding was cleared for
     uint8_t *im = nullptr, *score = nullptr, *blur = nullptr, *src = nullptr, *state = nullptr, *desc = nullptr;
     float *tmp = nullptr, *lam = nullptr, *xy = nullptr, *resp = nullptr;
@@ -401,6 +402,24 @@ struct spvo_ctx {
     float *h_angle = nullptr;
     uint8_t *h_desc = nullptr;
   } brisk;
+  // BRISK detector (brisk_detect.hip.h) on the image resident in `cls` (its layer 0): layers 1-5, the score maps of all six and the 5-8
+  // map of layer 0 (what spvo_brisk_detect_debug_layer serves until the next call), the area taps of the shape, the candidate lists --
+  // sized from the image (a candidate per interior pixel of every layer), grown on demand
+  struct BriskDetBufs {
+    int rows = 0, cols = 0;               // shape the layout, the tables and (after a call) the maps belong to (0: none)
+    bool valid = false;                   // the maps of a completed spvo_brisk_detect are on the device ...
+    unsigned image_gen = 0;               // ... and belong to the image spvo_ctx::cls held at this generation
+    size_t px_cap = 0, tab_cap = 0;       // bytes of pyr / score each; entries of tabs
+    int cand_cap = 0;                     // candidates the lists hold (>= what the shape can yield: an interior pixel each)
+    uint8_t *pyr = nullptr, *score = nullptr;
+    BriskAreaTap *tabs = nullptr;
+    std::vector<BriskAreaTap> h_tabs;
+    unsigned long long *keys = nullptr;
+    int *rank = nullptr, *keep = nullptr, *counters = nullptr;
+    BriskDetKeypoint *rec = nullptr, *out = nullptr;
+    BriskDetLayers lv{};
+    BriskResizeJob jobs[BRISK_DET_LAYERS]{};   // jobs[i]: layer i from its source (i >= 1)
+  } brisk_det;
   // SIFT detector + descriptor of the classic front end (sift.hip.h): the image, its pyramid (all Gaussian and DoG levels: what
   // spvo_sift_debug_level serves until the next call), the candidate and output lists; device buffers grow on demand, the host staging keeps its capacity
   struct SiftBufs {
@@ -639,10 +658,15 @@ void classic_release(spvo_ctx *c);   // frees spvo_ctx::bin (spvo_destroy)
 void classic_release_slots(spvo_ctx *c);   // ... the part of it that is sized by the slot capacity
 // a host image (strided view) becomes the resident image of spvo_ctx::cls, every buffer of it grown to the shape (enqueued on the solver's stream)
 int classic_upload_image(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride);
+// cls_rank_kernel (classic_detect.hip.h) over a key list whose length lies in device memory, enqueued on the solver's stream: rank[i] += the
+// number of keys smaller than keys[i] (rank is zero between uses)
+void classic_rank_enqueue(spvo_ctx *c, const unsigned long long *keys, int *rank, const int *n_ptr, int cap);
 // ---- spvo_brisk.hip
 void brisk_release(spvo_ctx *c);     // frees spvo_ctx::brisk (spvo_destroy)
 // what spvo_brisk_describe refuses of an image, for every entry point that runs the extractor (`who` names it in the error text)
 int brisk_check_image(spvo_ctx *c, const char *who, int rows, int cols);
+// ---- spvo_brisk_detect.hip
+void brisk_detect_release(spvo_ctx *c);   // frees spvo_ctx::brisk_det (spvo_destroy)
 // The extractor as a link of spvo_classic_detect's chain (kinds SPVO_CLASSIC_*_BRISK).  brisk_chain_ensure: the tables, the integral image
 // of a rows x cols image and the keypoint buffers for `cap` rows.  brisk_chain_enqueue, on the solver's stream behind a detector that left
 // its list in spvo_ctx::cls (xy, resp, counters[2]): integral image, border rule of keypoints of ONE `size` as a compaction that keeps at

@@ -32,6 +32,33 @@ __device__ __forceinline__ unsigned long long rank_key(float conf, int x, int y,
 }
 constexpr int RANK_TILE = 1024;
 
+// FAST-9/16 on the Bresenham circle of radius 3 around *p (row pitch w, p at least 3 pixels inside): the smallest |difference| on the best arc
+// of nine contiguous circle pixels that are all brighter than the centre + t or all darker than the centre - t -- the largest threshold at
+// which the pixel is still a corner, plus one -- or 0 if there is no such arc.  orb_fast_kernel's score (ORB, FAST) and, at t = 0 and less
+// one, the BRISK detector's AGAST 9-16 score (brisk_detect.hip.h).
+__device__ __forceinline__ int fast916_arc_score(const uint8_t *p, int w, int t) {
+  int best = 0;
+  const int c = *p;
+  const int off[16] = {-3 * w, -3 * w + 1, -2 * w + 2, -w + 3, 3, w + 3, 2 * w + 2, 3 * w + 1, 3 * w, 3 * w - 1, 2 * w - 2, w - 3, -3, -w - 3, -2 * w - 2, -3 * w - 1};
+  int d[25];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) d[i] = (int)p[off[i]] - c;
+  const int nb = (d[0] > t) + (d[4] > t) + (d[8] > t) + (d[12] > t), nd = (d[0] < -t) + (d[4] < -t) + (d[8] < -t) + (d[12] < -t);
+  if (nb >= 2 || nd >= 2) {
+#pragma unroll
+    for (int i = 16; i < 25; ++i) d[i] = d[i - 16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+      int mn = 255, mx = -255;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) { mn = min(mn, d[s + k]); mx = max(mx, d[s + k]); }
+      if (mn > t) best = max(best, mn);
+      if (-mx > t) best = max(best, -mx);
+    }
+  }
+  return best;
+}
+
 // ---- K15 (odometry.hip.h)
 struct RansacWork {      // device scratch
   int *counts;           // [iterations]  (-1 = invalid hypothesis)
@@ -67,5 +94,15 @@ struct SiftPyr {
 // the ordering stage on the device (sift.hip.h): a raw row's sort key, and where a final row came from
 struct SiftKey { float x, y, size, angle, response; int32_t octave; };   // mirrors spvo_sift_keypoint (include/spvo.h)
 struct SiftSrc { int4 pos; float4 off; float angle; int pad[3]; };        // the candidate {octave, layer, row, column}, {xi, xr, xc, contrast}, the peak's angle
+
+// ---- BRISK detector (brisk_detect.hip.h): the six layers of the scale space (layer 0 is the resident image of spvo_ctx::cls), the tap runs
+// of cv::resize(INTER_AREA)'s general path, a down-sampling job and the keypoint record
+constexpr int BRISK_DET_LAYERS = 6, BRISK_DET_TAPS = 6;
+struct BriskDetLayer { uint8_t *im, *score; int h, w; float scale, offset; };
+struct BriskDetLayers { BriskDetLayer l[BRISK_DET_LAYERS]; uint8_t *score58; };   // score58: the AGAST 5-8 score of layer 0
+struct BriskAreaTap { int start, n; float a[BRISK_DET_TAPS]; };                    // sources start .. start + n - 1 with weights a[0 .. n - 1]
+struct BriskResizeJob { const uint8_t *src; uint8_t *dst; int sh, sw, dh, dw; const BriskAreaTap *xtab, *ytab; };   // tabs = NULL: the exact half
+struct BriskResizeJobs { BriskResizeJob j[2]; };
+struct BriskDetKeypoint { float x, y, size, angle, response; int32_t octave; };   // mirrors spvo_brisk_keypoint (include/spvo.h)
 
 }  // namespace spvo

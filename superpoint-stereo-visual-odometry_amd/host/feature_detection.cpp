@@ -521,23 +521,29 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
 // descriptors (n x 128 CV_32F), matched with NORM_L2 by spvo_match_l2.  ShiTomasi + BRISK and FAST + BRISK go through the same detectors and
 // spvo_brisk_describe (cv::BRISK::create(30, 3, 1.0f)->compute, classic.cpp:56-65): 64-byte rows, matched with NORM_HAMMING.  With
 // setDeviceResident every one of these pairs is one submission per stereo pair instead (spvo_classic_detect, kinds 0 .. 4, or
-// spvo_sift_detect_pair) and is matched in its slots -- the BRISK pairs by the 64-byte instantiation of the slot matcher.  The BRISK
-// detector and AKAZE are OpenCV features2d calls and stay unavailable, and so does every other mix (SIFT keypoints with an ORB descriptor, ...).
+// spvo_sift_detect_pair) and is matched in its slots -- the BRISK pairs by the 64-byte instantiation of the slot matcher.  BRISK + BRISK
+// goes through spvo_brisk_detect (cv::BRISK::create()->detect, classic.cpp:9-11) and spvo_brisk_describe with the detector's x, y and size,
+// per image only: with setDeviceResident it takes the per-image path and residentPairs() stays 0.  AKAZE is an OpenCV features2d call and
+// stays unavailable, and so does every other mix (BRISK keypoints with an ORB descriptor -- spvo_orb_describe refuses fractional
+// coordinates --, SIFT keypoints with an ORB descriptor, ...).
 bool ClassicFeatureFrontEnd::available() { return true; }
 static bool classic_detector_runs(DetectorType d) { return d == DetectorType::ORB || d == DetectorType::ShiTomasi || d == DetectorType::FAST; }
 static bool classic_sift_pair(DetectorType d, DescriptorType e) { return d == DetectorType::SIFT && e == DescriptorType::SIFT; }
 // BRISK is an extractor for given keypoints here (spvo_brisk_describe): it goes with the two detectors that hand keypoints over
 static bool classic_brisk_pair(DetectorType d, DescriptorType e) { return (d == DetectorType::ShiTomasi || d == DetectorType::FAST) && e == DescriptorType::BRISK; }
+// ... and with its own detector (spvo_brisk_detect), whose keypoints carry the sizes the pattern was designed for
+static bool classic_brisk_brisk(DetectorType d, DescriptorType e) { return d == DetectorType::BRISK && e == DescriptorType::BRISK; }
 static bool classic_pair_runs(DetectorType d, DescriptorType e) {
-  return classic_sift_pair(d, e) || (classic_detector_runs(d) && e == DescriptorType::ORB) || classic_brisk_pair(d, e);
+  return classic_sift_pair(d, e) || (classic_detector_runs(d) && e == DescriptorType::ORB) || classic_brisk_pair(d, e) || classic_brisk_brisk(d, e);
 }
 void ClassicFeatureFrontEnd::initDetector() {
-  if (!classic_detector_runs(detector_type_) && !classic_sift_pair(detector_type_, descriptor_type_))
-    logError("[initDetector] only ORB, ShiTomasi, FAST and SIFT (with SIFT descriptors) run without OpenCV (build with SPVO_USE_OPENCV for the other detectors of classic.cpp:7-56)");
+  if (!classic_detector_runs(detector_type_) && !classic_sift_pair(detector_type_, descriptor_type_) && !classic_brisk_brisk(detector_type_, descriptor_type_))
+    logError("[initDetector] only ORB, ShiTomasi, FAST, SIFT (with SIFT descriptors) and BRISK (with BRISK descriptors) run without OpenCV (build with SPVO_USE_OPENCV for the other detectors of classic.cpp:7-56)");
 }
 void ClassicFeatureFrontEnd::initDescriptor() {
-  if (descriptor_type_ != DescriptorType::ORB && !classic_sift_pair(detector_type_, descriptor_type_) && !classic_brisk_pair(detector_type_, descriptor_type_))
-    logError("[initDescriptor] only ORB, BRISK on ShiTomasi / FAST keypoints, and SIFT on SIFT keypoints, run without OpenCV (build with SPVO_USE_OPENCV for the other descriptors of classic.cpp:58-79)");
+  if (descriptor_type_ != DescriptorType::ORB && !classic_sift_pair(detector_type_, descriptor_type_) && !classic_brisk_pair(detector_type_, descriptor_type_) &&
+      !classic_brisk_brisk(detector_type_, descriptor_type_))
+    logError("[initDescriptor] only ORB, BRISK on ShiTomasi / FAST / BRISK keypoints, and SIFT on SIFT keypoints, run without OpenCV (build with SPVO_USE_OPENCV for the other descriptors of classic.cpp:58-79)");
 }
 
 std::vector<cv::KeyPoint> ClassicFeatureFrontEnd::detectKeypoints(const cv::Mat &img) {
@@ -545,7 +551,7 @@ std::vector<cv::KeyPoint> ClassicFeatureFrontEnd::detectKeypoints(const cv::Mat 
   orb_desc_ = cv::Mat();
   detected_data_ = nullptr;
   if (!classic_pair_runs(detector_type_, descriptor_type_)) {
-    logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB, ShiTomasi and FAST with ORB descriptors, ShiTomasi and FAST with BRISK descriptors and SIFT with SIFT descriptors run");
+    logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB, ShiTomasi and FAST with ORB descriptors, ShiTomasi, FAST and BRISK with BRISK descriptors and SIFT with SIFT descriptors run");
     return keypoints;
   }
   if (!ensureContext()) return keypoints;
@@ -578,6 +584,30 @@ std::vector<cv::KeyPoint> ClassicFeatureFrontEnd::detectKeypoints(const cv::Mat 
     }
     orb_desc_ = cv::Mat(n, 128, CV_32FC1);
     if (n) std::memcpy(orb_desc_.ptr<float>(0), desc.ptr<float>(0), (size_t)n * 128 * sizeof(float));
+    return keypoints;
+  }
+  if (detector_type_ == DetectorType::BRISK) {
+    // cv::BRISK::create(): threshold 30, 3 octaves (classic.cpp:9-11); the image stays on the device for describeKeypoints
+    int cap = 4096, n = 0;
+    std::vector<spvo_brisk_keypoint> kp;
+    for (;;) {
+      kp.resize((size_t)cap);
+      if (spvo_brisk_detect(ctx_, img.ptr<uint8_t>(0), img.rows, img.cols, (size_t)img.step, 30, 3, kp.data(), cap, &n) != SPVO_OK) {
+        logError(std::string("spvo_brisk_detect: ") + spvo_last_error(ctx_));
+        return keypoints;
+      }
+      if (n <= cap) break;
+      cap = n;   // more than the buffer held: once more with room for all
+    }
+    keypoints.reserve(n);
+    for (int i = 0; i < n; ++i) {
+      cv::KeyPoint k(cv::Point2f(kp[i].x, kp[i].y), kp[i].size);
+      k.angle = kp[i].angle;   // -1
+      k.response = kp[i].response;
+      k.octave = kp[i].octave;   // the layer, 0 .. 5
+      keypoints.push_back(k);
+    }
+    detected_data_ = img.data; detected_rows_ = img.rows; detected_cols_ = img.cols;
     return keypoints;
   }
   if (detector_type_ != DetectorType::ORB) {
@@ -664,9 +694,11 @@ cv::Mat ClassicFeatureFrontEnd::describeKeypoints(std::vector<cv::KeyPoint> &key
     if (m) std::memcpy(d.ptr<uint8_t>(0), desc.ptr<uint8_t>(0), (size_t)m * 32);
     return d;
   }
-  if (classic_brisk_pair(detector_type_, descriptor_type_)) {
-    // cv::BRISK::create(30, 3, 1.0f)->compute(img, keypoints, descriptors), classic.cpp:56-65: every keypoint's own size (5: ShiTomasi, 7: FAST)
-    // picks its scale; the erase-and-angle handling is the ORB branch's (BRISK reports degrees, 0 .. 360)
+  if (classic_brisk_pair(detector_type_, descriptor_type_) || classic_brisk_brisk(detector_type_, descriptor_type_)) {
+    // cv::BRISK::create(30, 3, 1.0f)->compute(img, keypoints, descriptors), classic.cpp:56-65: every keypoint's own size (5: ShiTomasi, 7: FAST,
+    // 12 x its scale: BRISK) picks its scale; the erase-and-angle handling is the ORB branch's (BRISK reports degrees, 0 .. 360), except that
+    // a BRISK keypoint keeps the angle its detector reports (-1)
+    const bool keep_angle = detector_type_ == DetectorType::BRISK;
     if (!ensureContext()) return cv::Mat();
     if (img.depth() != CV_8U || img.rows <= 0) {
       logError("describeKeypoints: 8-bit single-channel image expected");
@@ -689,7 +721,7 @@ cv::Mat ClassicFeatureFrontEnd::describeKeypoints(std::vector<cv::KeyPoint> &key
     out.reserve(m);
     for (int i = 0; i < m; ++i) {
       cv::KeyPoint k = keypoints[kept[i]];
-      k.angle = angle[i];
+      if (!keep_angle) k.angle = angle[i];
       out.push_back(k);
     }
     keypoints.swap(out);
@@ -710,7 +742,7 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
     return;
   }
   if (!classic_pair_runs(detector_type_, descriptor_type_)) {
-    logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB, ShiTomasi and FAST with ORB descriptors, ShiTomasi and FAST with BRISK descriptors and SIFT with SIFT descriptors run");
+    logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB, ShiTomasi and FAST with ORB descriptors, ShiTomasi, FAST and BRISK with BRISK descriptors and SIFT with SIFT descriptors run");
     return;
   }
   if (!ensureContext()) return;   // no device: logged, nothing pushed (nn.cpp:53-55 convention)
@@ -743,6 +775,7 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
 // pushed and the caller takes the per-image path (the pair does not fit its slots, or the call failed and the per-image path reports why).
 bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &img_l, cv::Mat &img_r) {
   if (img_l.depth() != CV_8U || img_l.rows <= 0 || img_r.depth() != CV_8U || (size_t)img_l.step != (size_t)img_r.step) return false;
+  if (classic_brisk_brisk(detector_type_, descriptor_type_)) return false;   // no slot kind for this pair: the per-image path, residentPairs() stays 0
   if (detector_type_ == DetectorType::SIFT) {
     if (resident_pairs_ == 0) spvo_set_prematch(ctx_, 1, selector_type_ == SelectorType::KNN ? SPVO_SELECT_KNN : SPVO_SELECT_NN, matcher_cross_check_ ? 1 : 0, knn_threshold_);
     const int cap = std::max(resident_capacity_, 1);

@@ -74,6 +74,7 @@ class SolveOutput(C.Structure):
 
 
 SIFT_KP_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("size", np.float32), ("angle", np.float32), ("response", np.float32), ("octave", np.int32)])   # spvo_sift_keypoint
+BRISK_KP_DTYPE = SIFT_KP_DTYPE   # spvo_brisk_keypoint: octave is the layer 0..5, angle is -1
 OBS_DTYPE = np.dtype([("X", np.float32, 3), ("uv", np.float32, 2), ("cam", np.int32), ("inverse", np.int32)])
 
 # every symbol include/spvo.h declares
@@ -81,7 +82,7 @@ SYMBOLS = [
     "spvo_default_config", "spvo_create", "spvo_destroy", "spvo_last_error", "spvo_load_weights", "spvo_engine_precision", "spvo_set_fp32_split",
     "spvo_preprocess", "spvo_forward", "spvo_debug_tensor", "spvo_heatmap", "spvo_nms",
     "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8",
-    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_detect_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
+    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_detect_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
     "spvo_profile_enable", "spvo_profile_reset", "spvo_profile_only", "spvo_profile_count", "spvo_profile_get", "spvo_profile_stage_kernel",
     "spvo_set_tuning", "spvo_get_tuning", "spvo_clear_tuning",
     "spvo_comm_unique_id", "spvo_comm_available", "spvo_comm_create", "spvo_comm_create_host", "spvo_comm_rank", "spvo_comm_world", "spvo_comm_destroy",
@@ -140,6 +141,8 @@ def load() -> C.CDLL:
     lib.spvo_orb_describe.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, vp, vp, vp, ip]
     lib.spvo_brisk_describe.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, C.c_int, vp, vp, vp, vp, ip]
     lib.spvo_brisk_tables.argtypes = [C.c_int, vp, vp, vp, vp, vp]
+    lib.spvo_brisk_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, vp, C.c_int, ip]
+    lib.spvo_brisk_detect_debug_layer.argtypes = [vp, C.c_int, C.c_int, vp, ip, ip]
     lib.spvo_sift_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, C.c_int, ip]
     lib.spvo_sift_debug_level.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, ip, ip]
     lib.spvo_sift_detect_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(SiftFeatures), C.POINTER(SiftFeatures)]
@@ -495,6 +498,29 @@ class Context:
         out = dict(kept=kept[:m.value].copy(), angle=angle[:m.value].copy(), desc=desc[:m.value].copy())
         if values0:
             out["values0"] = v0[:m.value].copy()
+        return out
+
+    def brisk_detect(self, img: np.ndarray, threshold: int = 30, octaves: int = 3, cap: Optional[int] = None):
+        """BRISK keypoints of one u8 image (spvo_brisk_detect): dict of kp [m] (BRISK_KP_DTYPE records: x, y, size, angle = -1, response,
+        octave = layer 0..5) and n, the number found; m = min(n, cap).  cap = None: all of them (a second call when the first buffer was too
+        small).  The image stays on the device for a brisk_describe(None, ..., shape=img.shape) that follows."""
+        img = _u8_rows(img)
+        want = 4096 if cap is None else int(cap)
+        while True:
+            kp = np.zeros(max(want, 1), BRISK_KP_DTYPE)
+            n = C.c_int(0)
+            self._check(self.lib.spvo_brisk_detect(self.h, _ptr(img), img.shape[0], img.shape[1], img.strides[0], int(threshold), int(octaves), _ptr(kp), want, C.byref(n)))
+            if cap is not None or n.value <= want:
+                return dict(kp=kp[:min(n.value, want)].copy(), n=n.value)
+            want = n.value
+
+    def brisk_detect_layer(self, layer: int, what: int = 0) -> np.ndarray:
+        """A layer of the last brisk_detect()'s scale space (spvo_brisk_detect_debug_layer): what = 0 the image, 1 the AGAST 9-16 score map,
+        2 (layer 0 only) the 5-8 score map."""
+        rows, cols = C.c_int(0), C.c_int(0)
+        self._check(self.lib.spvo_brisk_detect_debug_layer(self.h, layer, what, None, C.byref(rows), C.byref(cols)))
+        out = np.zeros((rows.value, cols.value), np.uint8)
+        self._check(self.lib.spvo_brisk_detect_debug_layer(self.h, layer, what, _ptr(out), C.byref(rows), C.byref(cols)))
         return out
 
     def sift_detect(self, img: np.ndarray, cap: Optional[int] = None):

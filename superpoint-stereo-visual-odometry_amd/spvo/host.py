@@ -344,11 +344,13 @@ class FrontEnd:
 def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_threshold=2.0, refinement_degree=4, warm=0, detector="ORB", input_size=None, resident=False,
                      resident_capacity=0, trace=False, descriptor="ORB"):
     """stereoCallback replayed on ClassicFeatureFrontEnd(detector, descriptor, BF, ...) (node.cpp:353-360) over host image pairs -- detector
-    "ORB", "ShiTomasi" or "FAST" with descriptor "ORB", "ShiTomasi" or "FAST" with descriptor "BRISK" (64-byte rows), or detector "SIFT" (SIFT descriptors whatever `descriptor` says, as before); input_size None: at their native resolution, (height, width): through preprocessImageImpl first
+    "ORB", "ShiTomasi" or "FAST" with descriptor "ORB", "ShiTomasi", "FAST" or "BRISK" with descriptor "BRISK" (64-byte rows; detector "BRISK" with
+    the default descriptor "ORB" does not run), or detector "SIFT" (SIFT descriptors whatever `descriptor` says, as before); input_size None: at their native resolution, (height, width): through preprocessImageImpl first
     (classic.cpp:96-100).  Returns (poses [n, 7] = q xyzw + t of cam0_curr_T_cam0_prev, stats [n, 4] = keypoints L, R, stereo
     matches, PnP inliers, seconds spent on frames warm .. n-1).
     resident: ClassicFeatureFrontEnd::setDeviceResident for this run -- one spvo_classic_detect (SIFT: spvo_sift_detect_pair) per pair, features
-    and matching stay on the device, for every pair named above, BRISK included (resident_capacity > 0: rows per slot; a pair that does not
+    and matching stay on the device, for every pair named above with BRISK descriptors on ShiTomasi / FAST keypoints included; "BRISK" + "BRISK" has no
+    slot kind yet and takes the per-image path, classic_resident_pairs() stays 0 (resident_capacity > 0: rows per slot; a pair that does not
     fit falls back to the per-image path; classic_resident_pairs() tells how many pairs of the run stayed resident).
     trace: a fourth value, digests [n, 8] uint64 of what every frame left in the front end (keypoints L, descriptors L, keypoints R,
     descriptors R, stereo matches, temporal matches, the previous frame's stereo matches + map, the inlier sets): equal digests = identical

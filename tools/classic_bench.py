@@ -1,8 +1,8 @@
 """The classic front end on the GPU.
 
-python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST] [--descriptor ORB|BRISK] [--resident]
+python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK] [--descriptor ORB|BRISK] [--resident]
     ClassicFeatureFrontEnd(detector, descriptor, BF, KNN) over the synthetic stream: frames/s of the synchronous stereoCallback
-    (--descriptor BRISK: with --detector ShiTomasi or FAST);
+    (--descriptor BRISK: with --detector ShiTomasi, FAST or BRISK; --detector BRISK: with --descriptor BRISK only);
     --resident: with ClassicFeatureFrontEnd::setDeviceResident (one spvo_classic_detect per pair, matching on the binary slots).
 python tools/classic_bench.py [frames] --detector ShiTomasi|FAST|ORB --descriptor ORB|BRISK --ab ROUNDS
     the same stream with setDeviceResident off and on, alternating, ROUNDS times each in one process: ms per pair of every run, the median
@@ -19,6 +19,10 @@ python tools/classic_bench.py --leg brisk|orb_describe [--calls 50]
     spvo_brisk_describe / spvo_orb_describe alone on the FAST keypoints of the 1241 x 376 sample (image passed with every call), for
     rocprofv3 --kernel-trace --stats as above: brisk_integral_rows_kernel + brisk_integral_cols_kernel / brisk_compact_kernel /
     brisk_describe_kernel is the split.  --leg brisk also prints the one-off cost: the table build and the first call's upload.
+python tools/classic_bench.py --leg brisk_detect [--calls 50]
+    spvo_brisk_detect (threshold 30) alone per image at 1241 x 376, for rocprofv3 --kernel-trace --stats as above: brisk_area_kernel /
+    brisk_half_kernel / brisk_score916_kernel / brisk_score58_kernel / brisk_collect_kernel / cls_rank_kernel / brisk_refine_kernel /
+    brisk_det_compact_kernel is the split.
 python tools/classic_bench.py --leg match|match_slots [--selector NN|KNN] [--cross] [--calls 50]
     one matcher alone on the two resident ORB sets of the 1241 x 376 sample pair: spvo_match_hamming on the host copies (match_hamming_kernel<8>)
     or spvo_match_hamming_slots on the binary slots (match_hamming_tiled_kernel), for rocprofv3 --kernel-trace --stats as above.
@@ -40,7 +44,7 @@ ap.add_argument("--descriptor", default="ORB")
 ap.add_argument("--detectors", action="store_true")
 ap.add_argument("--resident", action="store_true")
 ap.add_argument("--ab", type=int, default=0)
-ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "orb_describe", "match", "match_slots"])
+ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "brisk_detect", "orb_describe", "match", "match_slots"])
 ap.add_argument("--selector", default="KNN", choices=["NN", "KNN"])
 ap.add_argument("--cross", action="store_true")
 ap.add_argument("--calls", type=int, default=200)
@@ -79,6 +83,9 @@ if args.detectors or args.leg:
     def leg_brisk():
         return len(ctx.brisk_describe(img, kp, 7.0)["kept"])
 
+    def leg_brisk_detect():
+        return ctx.brisk_detect(img, 30)["n"]
+
     def leg_orb_describe():
         return len(ctx.orb_describe(img, kp)["kept"])
 
@@ -99,6 +106,7 @@ if args.detectors or args.leg:
                 match_slots=("spvo_match_hamming_slots, %d x %d rows" % (len(fl["xy"]) if leg_match else 0, len(fr["xy"]) if leg_match else 0), leg_match_slots),
                 brisk=("spvo_brisk_describe, %d FAST keypoints" % (len(kp) if args.leg == "brisk" else 0), leg_brisk),
                 orb_describe=("spvo_orb_describe, %d FAST keypoints" % (len(kp) if args.leg == "orb_describe" else 0), leg_orb_describe),
+                brisk_detect=("spvo_brisk_detect", leg_brisk_detect),
                 orb=("spvo_orb_detect", leg_orb), sift=("spvo_sift_detect", leg_sift), gftt=("spvo_gftt_detect + spvo_orb_describe", leg_gftt), fast=("spvo_fast_detect + spvo_orb_describe", leg_fast))
     for key in ([args.leg] if args.leg else ["orb", "gftt", "fast"]):
         name, fn = legs[key]
