@@ -342,7 +342,8 @@ int spvo_brisk_detect(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, siz
 /* A layer of the scale space of this context's last spvo_brisk_detect (test hook): what = 0 the layer's image, 1 its AGAST 9-16 score map,
  * 2 (layer 0 only) the 5-8 score map.  `out` (rows x cols bytes) may be NULL to ask for the shape only.  SPVO_ERR_STATE when no result is
  * resident: no call yet, or any other call has since put an image into the context's resident image buffer (spvo_gftt_detect,
- * spvo_fast_detect, spvo_orb_describe / spvo_brisk_describe with an image, spvo_classic_detect), the same image included. */
+ * spvo_fast_detect, spvo_orb_describe / spvo_brisk_describe with an image, spvo_classic_detect, spvo_brisk_detect_pair), the same image
+ * included. */
 int spvo_brisk_detect_debug_layer(spvo_ctx *ctx, int layer, int what, uint8_t *out, int *rows, int *cols);
 
 /* ------------------------------------------------------- classic front end: one submission per stereo pair, features resident
@@ -384,6 +385,27 @@ typedef struct { int n; spvo_orb_keypoint *kp; uint8_t *desc; int cap; } spvo_cl
 int spvo_classic_detect(spvo_ctx *ctx, const spvo_classic_opts *opts, const uint8_t *img_l, const uint8_t *img_r,
                         int rows, int cols, size_t stride, int slot_l, int slot_r,
                         spvo_classic_features *out_l, spvo_classic_features *out_r);
+/* The same for BRISK keypoints with BRISK descriptors (detectKeypoints + describeKeypoints of ClassicFeatureFrontEnd(BRISK, BRISK) for both
+ * images of a stereo pair): an entry point of its own, because a BRISK keypoint carries a size and spvo_classic_features' 20-byte records
+ * have no room for one.  It fills the same ring of ten BINARY slots with 64-byte rows, so spvo_match_hamming_slots, spvo_classic_slot_rows
+ * and spvo_set_prematch serve it as they serve spvo_classic_detect, and the temporal partner is shared with that call: any filled slot of
+ * 64-byte rows is one, a 32-byte one is skipped.  Both images go up through the pinned staging; per image the detector's chain, ONE
+ * order-preserving compaction that applies the detector's keep flag and the extractor's border rule at every keypoint's OWN scale index,
+ * the extractor and a finishing kernel are enqueued without a host round trip, and the call waits once.  Per image the host receives, byte
+ * for byte, what spvo_brisk_detect(img, threshold, octaves) followed by spvo_brisk_describe(img = NULL, the x, y and size of those
+ * keypoints) returns: a record is the detector's with `kept` applied -- x, y, size, response and octave = layer unchanged -- and `angle`
+ * replaced by the extractor's (degrees, 0 .. 360); desc holds the extractor's rows in the detector's order; out->n is the number that
+ * survived the border rule.  The slot's own record array holds (x, y, that angle, response, layer).
+ * Afterwards the context's resident image is the RIGHT one: spvo_brisk_describe(img = NULL) works on it, and spvo_brisk_detect_debug_layer
+ * answers SPVO_ERR_STATE.  The first BRISK call of a context uploads the tables (spvo_brisk_describe).
+ *   SPVO_ERR_INVALID   NULL arguments, cap < 0, bad or equal slots, slot_capacity outside 1 .. 2^22, whatever spvo_brisk_detect refuses
+ *   SPVO_ERR_STATE     a spvo_detect*_submit is in flight; the candidate list overflowed (a defect, not an input: spvo_brisk_detect)
+ *   SPVO_ERR_CAPACITY  an image yields more rows than slot_capacity: out_*->n report both counts, both slots are left unfilled, nothing
+ *                      is truncated (spvo_classic_detect's rule; so is the re-allocation by a larger slot_capacity than any before) */
+typedef struct { int n; spvo_brisk_keypoint *kp; uint8_t *desc /* [cap][64] */; int cap; } spvo_brisk_features;   /* n: out; min(n, cap) rows are written; kp, desc may be NULL */
+int spvo_brisk_detect_pair(spvo_ctx *ctx, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride,
+                           int threshold, int octaves, int slot_l, int slot_r, int slot_capacity,
+                           spvo_brisk_features *out_l, spvo_brisk_features *out_r);
 /* rows a binary feature slot holds; SPVO_ERR_STATE for one that holds nothing (never filled, or left unfilled by SPVO_ERR_CAPACITY) */
 int spvo_classic_slot_rows(spvo_ctx *ctx, int slot, int *n);
 /* Caller-supplied rows into a binary slot (test hook: images cannot produce the rows the matcher's key layout has to survive --

@@ -8,6 +8,9 @@
 //                                               indices and their scale index
 //   brisk_compact_list_kernel                   the same walk on a detector's list whose length is on the device, one size for all
 //                                               (spvo_classic_detect's chain); brisk_slot_finish_kernel closes that chain
+//   brisk_pair_compact_kernel                   the walk on the BRISK detector's own records where brisk_refine_kernel left them: the keep flag
+//                                               and the border rule of EVERY record's own scale index in one launch
+//                                               (spvo_brisk_detect_pair's chain); brisk_pair_finish_kernel closes that chain
 //   brisk_describe_kernel                       one wave64 per kept keypoint at a time, four per workgroup: 60 box means at rotation 0, direction
 //                                               from the 870 long pairs, 60 box means at rotation theta, 512 short-pair bits
 //   brisk_finish_kernel                         count and results to pinned host memory, n_kept rows instead of a capacity-sized copy
@@ -78,10 +81,11 @@ __device__ inline int brisk_scale_index(float size, const BriskParams &P) {
 }
 
 // choice 9 as an order-preserving compaction: ONE workgroup walks the list in chunks of 1024 with a running base (wave ballots + an LDS
-// prefix over the 16 waves).  scale_of(i) is keypoint i's scale index; of the survivors the first `cap` are handed to put(k, i, s) -- the k-th
-// survivor is keypoint i at scale s -- and ALL are counted: the return value (the same in every thread).
-template <typename ScaleOf, typename Put>
-__device__ __forceinline__ int brisk_compact_walk(const float *__restrict__ xy, int n, int h, int w, const BriskParams &P, int cap, ScaleOf scale_of, Put put) {
+// prefix over the 16 waves).  Keypoint i's coordinates are xy[stride * i], xy[stride * i + 1]; live(i) says whether it takes part at all (a
+// dead one's coordinates are not read), scale_of(i) is its scale index; of the survivors the first `cap` are handed to put(k, i, s) -- the
+// k-th survivor is keypoint i at scale s -- and ALL are counted: the return value (the same in every thread).
+template <typename Live, typename ScaleOf, typename Put>
+__device__ __forceinline__ int brisk_compact_walk_if(const float *__restrict__ xy, int stride, int n, int h, int w, const BriskParams &P, int cap, Live live, ScaleOf scale_of, Put put) {
   __shared__ int s_wave[16];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int base = 0;
@@ -89,8 +93,8 @@ __device__ __forceinline__ int brisk_compact_walk(const float *__restrict__ xy, 
     const int i = i0 + (int)threadIdx.x;
     int s = 0;
     bool keep = false;
-    if (i < n) {
-      const float x = xy[2 * i], y = xy[2 * i + 1];
+    if (i < n && live(i)) {
+      const float x = xy[(size_t)stride * i], y = xy[(size_t)stride * i + 1];
       s = scale_of(i);
       const float b = (float)P.size_list[s];
       keep = x >= b && x < (float)w - b && y >= b && y < (float)h - b;   // (a NaN coordinate is dropped)
@@ -112,6 +116,11 @@ __device__ __forceinline__ int brisk_compact_walk(const float *__restrict__ xy, 
   }
   return base;
 }
+// ... on a packed [n][2] list of which every keypoint takes part
+template <typename ScaleOf, typename Put>
+__device__ __forceinline__ int brisk_compact_walk(const float *__restrict__ xy, int n, int h, int w, const BriskParams &P, int cap, ScaleOf scale_of, Put put) {
+  return brisk_compact_walk_if(xy, 2, n, h, w, P, cap, [](int) { return true; }, scale_of, put);
+}
 
 // spvo_brisk_describe: n and a size per keypoint from the host.  kept[k] = index into xy of the k-th survivor, kscale[k] its scale index;
 // out_cnt[0] = their number (at most n survive: nothing is cut).
@@ -130,6 +139,28 @@ __global__ __launch_bounds__(1024) void brisk_compact_list_kernel(const float *_
                                                                   float *__restrict__ kresp, int *__restrict__ out_cnt) {
   const int s_all = brisk_scale_index(size, P);
   const int base = brisk_compact_walk(xy, det_counters[2], h, w, P, cap, [&](int) { return s_all; }, [&](int k, int i, int s) { kept[k] = i; kscale[k] = s; kresp[k] = resp[i]; });
+  if (threadIdx.x == 0) { out_cnt[0] = base; out_cnt[2] = min(base, cap); }
+}
+
+// spvo_brisk_detect_pair: the BRISK detector's records as brisk_refine_kernel left them -- rec[i] and keep[i] of the min(det_counters[1],
+// det_cap) candidates, in output order -- instead of brisk_det_compact_kernel, a download, an upload and brisk_compact_kernel: a record
+// survives iff its keep flag is set AND it passes the border rule of ITS OWN scale index (a BRISK keypoint carries its own size).  The k-th
+// survivor leaves what brisk_describe_kernel reads -- its coordinates in the packed list kxy[k], kept[k] = k, kscale[k] -- and its record
+// crec[k] for brisk_pair_finish_kernel.  Overflow and out_cnt as brisk_compact_list_kernel.
+static_assert(sizeof(BriskDetKeypoint) == 6 * sizeof(float), "a record is six words: x, y lead it");
+__global__ __launch_bounds__(1024) void brisk_pair_compact_kernel(const BriskDetKeypoint *__restrict__ rec, const int *__restrict__ keep, const int *__restrict__ det_counters,
+                                                                  int det_cap, int h, int w, BriskParams P, int cap, float *__restrict__ kxy, int *__restrict__ kept,
+                                                                  int *__restrict__ kscale, BriskDetKeypoint *__restrict__ crec, int *__restrict__ out_cnt) {
+  const int n = min(det_counters[1], det_cap);
+  const int base = brisk_compact_walk_if(
+      &rec->x, 6, n, h, w, P, cap, [&](int i) { return keep[i] != 0; }, [&](int i) { return brisk_scale_index(rec[i].size, P); },
+      [&](int k, int i, int s) {
+        const float x = rec[i].x, y = rec[i].y, size = rec[i].size, angle = rec[i].angle, response = rec[i].response;
+        const int32_t octave = rec[i].octave;
+        kxy[2 * k] = x; kxy[2 * k + 1] = y;
+        kept[k] = k; kscale[k] = s;
+        crec[k].x = x; crec[k].y = y; crec[k].size = size; crec[k].angle = angle; crec[k].response = response; crec[k].octave = octave;
+      });
   if (threadIdx.x == 0) { out_cnt[0] = base; out_cnt[2] = min(base, cap); }
 }
 
@@ -254,6 +285,26 @@ __global__ __launch_bounds__(256) void brisk_slot_finish_kernel(const int *__res
     k.x = xy[2 * src]; k.y = xy[2 * src + 1]; k.angle = angle[i]; k.response = kresp[i]; k.octave = 0;
     kps[i] = k;
     h_kp[i] = k;
+  }
+  for (int i = tid; i < n * (BRISK_BYTES / 16); i += nth) h_desc[i] = desc[i];
+}
+
+// The last launch of an image in spvo_brisk_detect_pair's chain: the slot's count and its 20-byte records (x, y, the extractor's angle,
+// response, layer), and the host's copy in pinned memory: count, the detector's 24-byte records with the extractor's angle (degrees) in
+// place of -1, and the 64-byte rows, n of each.  h_n and n as brisk_slot_finish_kernel.
+__global__ __launch_bounds__(256) void brisk_pair_finish_kernel(const int *__restrict__ det_counters, const int *__restrict__ ext_cnt, const BriskDetKeypoint *__restrict__ crec,
+                                                                const float *__restrict__ angle, const uint4 *__restrict__ desc, int cap, OrbKeypoint *__restrict__ kps,
+                                                                int *__restrict__ d_n, int *__restrict__ h_n, BriskDetKeypoint *__restrict__ h_kp, uint4 *__restrict__ h_desc) {
+  const int n_all = ext_cnt[0], n = min(n_all, cap);
+  const int tid = blockIdx.x * 256 + threadIdx.x, nth = gridDim.x * 256;
+  if (tid == 0) { *d_n = n; h_n[0] = n_all; h_n[1] = det_counters[3]; }
+  for (int i = tid; i < n; i += nth) {
+    BriskDetKeypoint r = crec[i];
+    r.angle = angle[i];
+    h_kp[i] = r;
+    OrbKeypoint k;
+    k.x = r.x; k.y = r.y; k.angle = r.angle; k.response = r.response; k.octave = r.octave;
+    kps[i] = k;
   }
   for (int i = tid; i < n * (BRISK_BYTES / 16); i += nth) h_desc[i] = desc[i];
 }

@@ -1,6 +1,7 @@
 // spvo_brisk.hip -- the classic front end's BRISK descriptor extractor on given keypoints (brisk.hip.h): the pattern tables (built once
 // per process on the host, in double, by the formulas tests/brisk_ref.py lists), spvo_brisk_tables, spvo_brisk_describe and the extractor
-// as a link of spvo_classic_detect's chain (brisk_chain_ensure / brisk_chain_enqueue).  Runs on the
+// as a link of spvo_classic_detect's chain (brisk_chain_ensure / brisk_chain_enqueue) and of spvo_brisk_detect_pair's
+// (brisk_pair_chain_enqueue).  Runs on the
 // solver's stream (stream2) on the image the Shi-Tomasi / FAST detectors and the ORB extractor keep resident (spvo_ctx::cls) and owns
 // everything else it needs (spvo_ctx::brisk).
 #include "spvo_internal.hip.h"
@@ -183,6 +184,26 @@ int spvo_int::brisk_chain_enqueue(spvo_ctx *c, int rows, int cols, float size, i
   hipLaunchKernelGGL(brisk_describe_kernel, dim3(std::min((std::max(most, 1) + 3) / 4, BRISK_DESCRIBE_BLOCKS)), dim3(256), 0, st, b.im, k.integ, rows, cols, b.xy, k.kept, k.kscale, o.cnt + 2, k.points,
                      k.long_pairs, k.short_pairs, k.angle, desc, nullptr);
   hipLaunchKernelGGL(brisk_slot_finish_kernel, dim3(32), dim3(256), 0, st, b.counters, o.cnt, b.xy, k.kept, k.angle, o.kresp, reinterpret_cast<const uint4 *>(desc), cap, o.d_kp, o.d_n, o.h_n, o.h_kp,
+                     reinterpret_cast<uint4 *>(o.h_desc));
+  HIP_TRY(c, hipGetLastError());
+  return SPVO_OK;
+}
+
+// The same behind the BRISK detector (spvo_brisk_detect_pair): the keypoints are the detector's records where brisk_refine_kernel left them,
+// each with a size of its own, so ONE launch applies the keep flag and the border rule and leaves the packed coordinate list the describe
+// kernel reads (spvo_ctx::brisk.xy: kept[k] = k); its grid is fixed by the slot capacity, the count is read on the device.
+int spvo_int::brisk_pair_chain_enqueue(spvo_ctx *c, int rows, int cols, int cap, const BriskDetKeypoint *rec, const int *keep, const int *det_counters, int det_cap,
+                                       BriskDetKeypoint *crec, const ChainOut &o, BriskDetKeypoint *h_kp) {
+  auto &b = c->cls;
+  auto &k = c->brisk;
+  hipStream_t st = c->stream2;
+  uint8_t *desc = reinterpret_cast<uint8_t *>(o.d_desc);
+  hipLaunchKernelGGL(brisk_integral_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.im, rows, cols, k.integ);
+  hipLaunchKernelGGL(brisk_integral_cols_kernel, dim3((cols + 1 + 255) / 256), dim3(256), 0, st, rows, cols, k.integ);
+  hipLaunchKernelGGL(brisk_pair_compact_kernel, dim3(1), dim3(1024), 0, st, rec, keep, det_counters, det_cap, rows, cols, brisk_tables().params, cap, k.xy, k.kept, k.kscale, crec, o.cnt);
+  hipLaunchKernelGGL(brisk_describe_kernel, dim3(std::min((cap + 3) / 4, BRISK_DESCRIBE_BLOCKS)), dim3(256), 0, st, b.im, k.integ, rows, cols, k.xy, k.kept, k.kscale, o.cnt + 2, k.points, k.long_pairs,
+                     k.short_pairs, k.angle, desc, nullptr);
+  hipLaunchKernelGGL(brisk_pair_finish_kernel, dim3(32), dim3(256), 0, st, det_counters, o.cnt, crec, k.angle, reinterpret_cast<const uint4 *>(desc), cap, o.d_kp, o.d_n, o.h_n, h_kp,
                      reinterpret_cast<uint4 *>(o.h_desc));
   HIP_TRY(c, hipGetLastError());
   return SPVO_OK;

@@ -1,7 +1,8 @@
 // spvo_brisk_detect.hip -- the classic front end's BRISK keypoint detector (brisk_detect.hip.h): the layout of the six layers and the area
-// taps of a shape (built on the host in double, by the formulas tests/brisk_detect_ref.py lists), spvo_brisk_detect and
-// spvo_brisk_detect_debug_layer.  Runs on the solver's stream (stream2) with the image resident in spvo_ctx::cls as layer 0 -- it stays
-// there for a spvo_brisk_describe(img = NULL) that follows -- and owns everything else it needs (spvo_ctx::brisk_det).
+// taps of a shape (built on the host in double, by the formulas tests/brisk_detect_ref.py lists), spvo_brisk_detect,
+// spvo_brisk_detect_debug_layer and spvo_brisk_detect_pair (detector + extractor of a stereo pair in one submission into two binary slots,
+// by spvo_classic_detect's resident-pair protocol).  Runs on the solver's stream (stream2) with the image resident in spvo_ctx::cls as
+// layer 0 -- it stays there for a spvo_brisk_describe(img = NULL) that follows -- and owns everything else it needs (spvo_ctx::brisk_det).
 #include "spvo_internal.hip.h"
 #include "brisk_detect.hip.h"
 
@@ -127,6 +128,31 @@ void bd_resize_group(spvo_ctx *c, int first, int count) {
   if (any_exact) hipLaunchKernelGGL(brisk_half_kernel, grid, dim3(256), 0, c->stream2, jobs);
   if (any_area) hipLaunchKernelGGL(brisk_area_kernel, grid, dim3(256), 0, c->stream2, jobs);
 }
+
+// the image resident in spvo_ctx::cls -> rec / keep of its candidates in output order, their number in counters[1] (bd_ensure has run)
+int bd_enqueue(spvo_ctx *c, int rows, int cols, int threshold) {
+  auto &d = c->brisk_det;
+  hipStream_t st = c->stream2;
+  HIP_TRY(c, hipMemsetAsync(d.counters, 0, BD_COUNTER_INTS * sizeof(int), st));
+  bd_resize_group(c, 1, 1);
+  bd_resize_group(c, 2, 2);
+  bd_resize_group(c, 4, 2);
+  const dim3 grid((cols + 63) / 64, (rows + 3) / 4, BRISK_DET_LAYERS), grid0(grid.x, grid.y, 1);
+  hipLaunchKernelGGL(brisk_score916_kernel, grid, dim3(256), 0, st, d.lv);
+  hipLaunchKernelGGL(brisk_score58_kernel, grid0, dim3(256), 0, st, d.lv);
+  hipLaunchKernelGGL(brisk_collect_kernel, grid, dim3(256), 0, st, d.lv, threshold, d.keys, d.cand_cap, d.counters);
+  classic_rank_enqueue(c, d.keys, d.rank, d.counters + 1, d.cand_cap);
+  hipLaunchKernelGGL(brisk_refine_kernel, dim3(64), dim3(256), 0, st, d.lv, threshold, d.keys, d.rank, d.cand_cap, d.counters, d.rec, d.keep);
+  return SPVO_OK;
+}
+
+// what spvo_brisk_detect refuses of its parameters and of the image shape (`who` names the entry point in the error text)
+int bd_check(spvo_ctx *c, const char *who, int rows, int cols, int threshold, int octaves) {
+  if (threshold < 1 || threshold > 255) return fail(c, SPVO_ERR_INVALID, "%s: threshold must be 1 .. 255", who);
+  if (octaves != 3) return fail(c, SPVO_ERR_INVALID, "%s: only octaves = 3 (six layers) is built", who);
+  if (rows < 8 || cols < 8) return fail(c, SPVO_ERR_INVALID, "%s: images of at least 8 x 8 only", who);
+  return brisk_check_image(c, who, rows, cols);
+}
 }  // namespace
 
 void spvo_int::brisk_detect_release(spvo_ctx *c) {
@@ -140,26 +166,14 @@ extern "C" {
 int spvo_brisk_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride, int threshold, int octaves, spvo_brisk_keypoint *kp, int cap, int *n_out) {
   if (!c || !img || !n_out || rows <= 0 || cols <= 0 || stride < (size_t)cols || cap < 0 || (cap > 0 && !kp)) return fail(c, SPVO_ERR_INVALID, "bad argument");
   *n_out = 0;
-  if (threshold < 1 || threshold > 255) return fail(c, SPVO_ERR_INVALID, "spvo_brisk_detect: threshold must be 1 .. 255");
-  if (octaves != 3) return fail(c, SPVO_ERR_INVALID, "spvo_brisk_detect: only octaves = 3 (six layers) is built");
-  if (rows < 8 || cols < 8) return fail(c, SPVO_ERR_INVALID, "spvo_brisk_detect: images of at least 8 x 8 only");
-  if (int rc = brisk_check_image(c, "spvo_brisk_detect", rows, cols)) return rc;
+  if (int rc = bd_check(c, "spvo_brisk_detect", rows, cols, threshold, octaves)) return rc;
   if (int rc = require_idle(c)) return rc;
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   hipStream_t st = c->stream2;
   if (int rc = classic_upload_image(c, img, rows, cols, stride)) return rc;
   if (int rc = bd_ensure(c, rows, cols)) return rc;
   auto &d = c->brisk_det;
-  HIP_TRY(c, hipMemsetAsync(d.counters, 0, BD_COUNTER_INTS * sizeof(int), st));
-  bd_resize_group(c, 1, 1);
-  bd_resize_group(c, 2, 2);
-  bd_resize_group(c, 4, 2);
-  const dim3 grid((cols + 63) / 64, (rows + 3) / 4, BRISK_DET_LAYERS), grid0(grid.x, grid.y, 1);
-  hipLaunchKernelGGL(brisk_score916_kernel, grid, dim3(256), 0, st, d.lv);
-  hipLaunchKernelGGL(brisk_score58_kernel, grid0, dim3(256), 0, st, d.lv);
-  hipLaunchKernelGGL(brisk_collect_kernel, grid, dim3(256), 0, st, d.lv, threshold, d.keys, d.cand_cap, d.counters);
-  classic_rank_enqueue(c, d.keys, d.rank, d.counters + 1, d.cand_cap);
-  hipLaunchKernelGGL(brisk_refine_kernel, dim3(64), dim3(256), 0, st, d.lv, threshold, d.keys, d.rank, d.cand_cap, d.counters, d.rec, d.keep);
+  if (int rc = bd_enqueue(c, rows, cols, threshold)) return rc;
   hipLaunchKernelGGL(brisk_det_compact_kernel, dim3(1), dim3(1024), 0, st, d.rec, d.keep, d.cand_cap, d.counters, d.out);
   HIP_TRY(c, hipGetLastError());
   int cnt[BD_COUNTER_INTS];
@@ -176,6 +190,81 @@ int spvo_brisk_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_
     HIP_TRY(c, hipMemcpyAsync(kp, d.out, (size_t)ncopy * sizeof(BriskDetKeypoint), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
   }
+  return SPVO_OK;
+}
+
+// One submission per stereo pair: spvo_classic_detect's protocol (PairStage, slot_rewrite, the prematch cache) around the detector's chain
+// up to brisk_refine_kernel and the extractor behind it (brisk_pair_chain_enqueue), image by image in stream order.  The scale space, the
+// candidate lists, the integral image, the extractor's lists and the detector's counter block are the left image's first and the right
+// image's afterwards: an image's finishing kernel has put its counts into the pinned h_n before the next image's clear.
+int spvo_brisk_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int threshold, int octaves, int slot_l, int slot_r,
+                           int slot_capacity, spvo_brisk_features *out_l, spvo_brisk_features *out_r) {
+  if (!c || !img_l || !img_r || !out_l || !out_r || rows <= 0 || cols <= 0 || stride < (size_t)cols) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  if (slot_l < 0 || slot_l >= N_BIN_SLOTS || slot_r < 0 || slot_r >= N_BIN_SLOTS || slot_l == slot_r) return fail(c, SPVO_ERR_INVALID, "bad slot");
+  spvo_brisk_features *const outs[2] = {out_l, out_r};
+  for (auto *o : outs)
+    if (o->cap < 0) return fail(c, SPVO_ERR_INVALID, "bad output buffer");
+  const int cap = slot_capacity;
+  if (cap <= 0 || cap > (1 << HAM_KEY_SHIFT)) return fail(c, SPVO_ERR_INVALID, "slot_capacity must be 1 .. %d", 1 << HAM_KEY_SHIFT);
+  if (int rc = bd_check(c, "spvo_brisk_detect_pair", rows, cols, threshold, octaves)) return rc;
+  if (int rc = require_idle(c)) return rc;
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  out_l->n = out_r->n = 0;
+  hipStream_t st = c->stream2;
+  auto &bb = c->bin;
+  auto &b = c->cls;
+  auto &d = c->brisk_det;
+  PairStage &ps = bb.pair;
+  constexpr int row_bytes = 64;
+  const size_t px = (size_t)rows * cols;
+  // every allocation and the 47 MB point table before the first launch of the chain; the image buffer before the layout that points into it
+  int rc;
+  if ((rc = classic_slots_ensure(c, cap, px)) || (rc = classic_image_ensure(c, rows, cols)) || (rc = brisk_chain_ensure(c, rows, cols, cap)) || (rc = bd_ensure(c, rows, cols))) return rc;
+  // both slots are being rewritten: whatever was matched against their old contents is stale
+  const int slots[2] = {slot_l, slot_r};
+  for (int sl : slots) { slot_rewrite(bb.slots[sl]); bb.slots[sl].row_bytes = row_bytes; }
+  ps.mcache.invalidate();
+  HIP_TRY(c, hipStreamSynchronize(st));   // (the staging buffer and the mirrors are the previous call's until its work is done)
+  ps.stage(img_l, img_r, rows, cols, stride);
+  for (int k = 0; k < 2; ++k) {
+    const BinarySlot &s = bb.slots[slots[k]];
+    b.rows = b.cols = 0;
+    HIP_TRY(c, hipMemcpyAsync(b.im, ps.h_img + k * px, px, hipMemcpyHostToDevice, st));
+    b.rows = rows; b.cols = cols;
+    if ((rc = bd_enqueue(c, rows, cols, threshold))) return rc;
+    const ChainOut out{bb.d_cnt + k * BIN_COUNTER_INTS, bb.d_kresp, s.d_kp, s.d_desc, s.d_n, bb.h_n + 4 * k, nullptr, bb.h_desc + (size_t)k * cap * row_bytes};
+    if ((rc = brisk_pair_chain_enqueue(c, rows, cols, cap, d.rec, d.keep, d.counters, d.cand_cap, d.out, out, bb.h_bkp + (size_t)k * cap))) return rc;
+  }
+  HIP_TRY(c, hipEventRecord(ps.ev_feat, st));
+  // spvo_set_prematch, as spvo_classic_detect: any filled slot of 64-byte rows is a temporal partner, whichever entry point filled it
+  const int prev = ps.last_slot_l;
+  const int partner[2] = {slot_r, ps.temporal_partner(slot_l, slot_r, prev >= 0 && bb.slots[prev].filled && bb.slots[prev].row_bytes == row_bytes)};
+  if (c->prematch) {
+    for (int k = 0; k < 2; ++k)
+      if (partner[k] >= 0)
+        if ((rc = enqueue_hamming_slots(c, slot_l, partner[k], c->pm_selector, c->pm_cross, c->pm_ratio, bb.h_match + (size_t)k * cap))) return rc;
+    HIP_TRY(c, hipEventRecord(ps.ev_match, st));
+  }
+  HIP_TRY(c, wait_event(ps.ev_feat));   // the one wait of the call: the matches go on behind it
+  ps.last_slot_l = -1;   // (forgotten AFTER the wait, as spvo_classic_detect: a call that failed before it leaves the partner it found)
+  for (int k = 0; k < 2; ++k) outs[k]->n = bb.h_n[4 * k];
+  // (the lists hold a candidate per interior pixel of every layer, so the flag cannot be set; were it, the counts would be wrong)
+  if (bb.h_n[1] || bb.h_n[5]) return fail(c, SPVO_ERR_STATE, "spvo_brisk_detect_pair: the candidate list overflowed although it is sized from the image");
+  if (outs[0]->n > cap || outs[1]->n > cap)
+    return fail(c, SPVO_ERR_CAPACITY, "spvo_brisk_detect_pair: %d / %d rows do not fit slots of %d (slot_capacity)", outs[0]->n, outs[1]->n, cap);
+  static_assert(sizeof(spvo_brisk_keypoint) == sizeof(BriskDetKeypoint), "record layout");
+  for (int k = 0; k < 2; ++k) {
+    BinarySlot &s = bb.slots[slots[k]];
+    s.n = outs[k]->n; s.filled = true;
+    const int ncopy = std::min(s.n, outs[k]->cap);
+    if (ncopy > 0 && outs[k]->kp) std::memcpy(outs[k]->kp, bb.h_bkp + (size_t)k * cap, (size_t)ncopy * sizeof(BriskDetKeypoint));
+    if (ncopy > 0 && outs[k]->desc) std::memcpy(outs[k]->desc, bb.h_desc + (size_t)k * cap * row_bytes, (size_t)ncopy * row_bytes);
+  }
+  if (c->prematch)
+    for (int k = 0; k < 2; ++k)
+      if (partner[k] >= 0)
+        ps.mcache.record(k, slot_l, partner[k], bb.slots[slot_l].gen, bb.slots[partner[k]].gen, c->pm_selector, c->pm_cross, c->pm_ratio, bb.h_match + (size_t)k * cap);
+  ps.last_slot_l = slot_l;
   return SPVO_OK;
 }
 

@@ -463,6 +463,7 @@ int spvo_orb_describe(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_
 }  // extern "C"
 
 int spvo_int::classic_upload_image(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride) { return cls_prepare(c, img, rows, cols, stride); }
+int spvo_int::classic_image_ensure(spvo_ctx *c, int rows, int cols) { return cls_ensure(c, rows, cols); }
 void spvo_int::classic_rank_enqueue(spvo_ctx *c, const unsigned long long *keys, int *rank, const int *n_ptr, int cap) {
   hipLaunchKernelGGL(cls_rank_kernel, dim3(128), dim3(256), 0, c->stream2, keys, rank, n_ptr, cap);
 }
@@ -477,7 +478,7 @@ void spvo_int::classic_release_slots(spvo_ctx *c) {
     s.row_bytes = 32;
   }
   dev_free(bb.d_cnt, bb.d_kxy, bb.d_kresp, bb.d_vote);
-  host_free(bb.h_kp, bb.h_desc, bb.h_n, bb.h_match);
+  host_free(bb.h_kp, bb.h_bkp, bb.h_desc, bb.h_n, bb.h_match);
   bb.pair.mcache.invalidate();
   bb.cap = 0; bb.pair.last_slot_l = -1;
 }
@@ -490,6 +491,7 @@ void spvo_int::classic_release(spvo_ctx *c) {
 extern "C" {
 
 namespace {
+static_assert(BIN_COUNTER_INTS == CLS_COUNTER_INTS, "an image's counter block in spvo_ctx::bin.d_cnt");
 constexpr int BIN_ROW_BYTES_MAX = 64;   // the widest row a binary slot holds (BRISK); the ORB extractor's rows are 32 bytes
 inline bool kind_is_brisk(int kind) { return kind == SPVO_CLASSIC_GFTT_BRISK || kind == SPVO_CLASSIC_FAST_BRISK; }
 inline bool kind_is_gftt(int kind) { return kind == SPVO_CLASSIC_GFTT_ORB || kind == SPVO_CLASSIC_GFTT_BRISK; }
@@ -508,6 +510,7 @@ int bin_ensure(spvo_ctx *c, int cap, size_t px) {
       (rc = dev_alloc(c, &bb.d_vote, cap)))
     return rc;
   HIP_TRY(c, hipHostMalloc((void **)&bb.h_kp, (size_t)2 * cap * sizeof(OrbKeypoint)));
+  HIP_TRY(c, hipHostMalloc((void **)&bb.h_bkp, (size_t)2 * cap * sizeof(BriskDetKeypoint)));
   HIP_TRY(c, hipHostMalloc((void **)&bb.h_desc, (size_t)2 * cap * BIN_ROW_BYTES_MAX));
   HIP_TRY(c, hipHostMalloc((void **)&bb.h_n, 2 * 4 * sizeof(int)));
   HIP_TRY(c, hipHostMalloc((void **)&bb.h_match, (size_t)3 * cap * sizeof(int2)));
@@ -717,3 +720,5 @@ int spvo_classic_detect(spvo_ctx *c, const spvo_classic_opts *opts, const uint8_
 }
 
 }  // extern "C"
+
+int spvo_int::classic_slots_ensure(spvo_ctx *c, int cap, size_t px) { return bin_ensure(c, cap, px); }

@@ -10,6 +10,7 @@
 //   spvo_classic.hip   the classic front end: ORB, Shi-Tomasi, FAST, the ORB extractor, preprocess without an engine
 //   spvo_sift.hip      the classic front end: SIFT detector + descriptor
 //   spvo_brisk.hip     the classic front end: BRISK descriptor extractor on given keypoints
+//   spvo_brisk_detect.hip   the classic front end: BRISK keypoint detector, and detector + extractor of a stereo pair into the binary slots
 //   spvo_match.hip     descriptor matching (L2, Hamming)
 //   spvo_solve.hip     triangulation, PnP-RANSAC, gating, Levenberg-Marquardt, the fused solve
 #pragma once
@@ -43,6 +44,7 @@ constexpr int N_SLOTS = 16;      // feature slots: 8 stereo pairs (previous, cur
 constexpr int N_BIN_SLOTS = 10;  // binary feature slots of the classic front end (spvo_classic_detect): a ring of stereo pairs, numbered like the float slots
 constexpr int N_SIFT_SLOTS = 10;   // SIFT feature slots (spvo_sift_detect_pair): a third ring of stereo pairs, numbered like the others
 constexpr int SIFT_SLOT_MAX = 32768;   // rows a SIFT slot may be asked to hold
+constexpr int BIN_COUNTER_INTS = 16;   // ints of an image's counter block in spvo_ctx::bin.d_cnt (= CLS_COUNTER_INTS, classic_detect.hip.h)
 constexpr int HAM_KEY_SHIFT = 22;   // the tiled Hamming matcher orders (distance, row) as ONE 32-bit key: distance << 22 | row, so a slot holds at most 2^22 rows
 
 struct Tensor {
@@ -378,6 +380,7 @@ struct spvo_ctx {
     OrbKeypoint *h_kp = nullptr;         // pinned [2][cap]      what the finishing kernel of an image writes for the host:
     uint8_t *h_desc = nullptr;           // pinned [2][cap][64]  keypoint records, descriptors ([2][cap][32] in its front part for the 32-byte kinds),
     int *h_n = nullptr;                  // pinned [2][4]        {rows found, overflow flag of the detector}
+    BriskDetKeypoint *h_bkp = nullptr;   // pinned [2][cap]      spvo_brisk_detect_pair's records (24 bytes: they carry a size), in the place of h_kp
     int *d_cnt = nullptr;                // [2][CLS_COUNTER_INTS] the extractor's counter block per image (0: kept in all, 2: kept and described)
     int *d_kxy = nullptr;                // [cap][2] the kept keypoints of a Shi-Tomasi / FAST image (cls_compact_kernel), ...
     float *d_kresp = nullptr;            // [cap]    ... and the detector's responses of those (also brisk_compact_list_kernel's)
@@ -658,6 +661,11 @@ void classic_release(spvo_ctx *c);   // frees spvo_ctx::bin (spvo_destroy)
 void classic_release_slots(spvo_ctx *c);   // ... the part of it that is sized by the slot capacity
 // a host image (strided view) becomes the resident image of spvo_ctx::cls, every buffer of it grown to the shape (enqueued on the solver's stream)
 int classic_upload_image(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride);
+// spvo_classic_detect's own preparations, for another entry point that fills the binary slots (spvo_brisk_detect_pair).  classic_slots_ensure:
+// the slots, the call's mirrors and the pinned staging for `cap` rows per slot and images of `px` bytes; a larger `cap` than any before
+// empties every slot.  classic_image_ensure: every buffer of spvo_ctx::cls grown to a rows x cols image; none is resident afterwards.
+int classic_slots_ensure(spvo_ctx *c, int cap, size_t px);
+int classic_image_ensure(spvo_ctx *c, int rows, int cols);
 // cls_rank_kernel (classic_detect.hip.h) over a key list whose length lies in device memory, enqueued on the solver's stream: rank[i] += the
 // number of keys smaller than keys[i] (rank is zero between uses)
 void classic_rank_enqueue(spvo_ctx *c, const unsigned long long *keys, int *rank, const int *n_ptr, int cap);
@@ -680,6 +688,12 @@ struct ChainOut {         // where image k of a spvo_classic_detect call leaves 
   int *h_n; OrbKeypoint *h_kp; uint8_t *h_desc;           // its pinned mirrors
 };
 int brisk_chain_enqueue(spvo_ctx *c, int rows, int cols, float size, int cap, int most, const ChainOut &o);
+// The extractor behind the BRISK detector (spvo_brisk_detect_pair), on the solver's stream behind brisk_refine_kernel: rec / keep of the
+// min(det_counters[1], det_cap) candidates -> integral image, keep flag + border rule of every record's own size as ONE compaction (at most
+// `cap` rows kept, all counted; compacted records in `crec`), descriptors with the count read on the device, and the finish launch: the
+// slot's count, 20-byte records and rows, the pinned mirrors o.h_n, o.h_desc and the 24-byte records in h_kp (o.h_kp, o.kresp: unused).
+int brisk_pair_chain_enqueue(spvo_ctx *c, int rows, int cols, int cap, const BriskDetKeypoint *rec, const int *keep, const int *det_counters, int det_cap, BriskDetKeypoint *crec,
+                             const ChainOut &o, BriskDetKeypoint *h_kp);
 // ---- spvo_sift.hip
 void sift_release(spvo_ctx *c);      // frees spvo_ctx::sift (spvo_destroy)
 // ---- spvo_match.hip

@@ -430,7 +430,9 @@ cv::Mat FeatureFrontEnd::visualizeInliers(const ImagePosition image_position) {
 // solveStereoOdometry (base.cpp:169-172) then behaves as the reference's does.
 static bool g_classic_resident = false;
 static int g_classic_resident_capacity = 8192;
+static bool g_classic_brisk_pair_resident = false;
 void ClassicFeatureFrontEnd::setDeviceResident(bool on) { g_classic_resident = on; }
+void ClassicFeatureFrontEnd::setBriskPairResident(bool on) { g_classic_brisk_pair_resident = on; }
 void ClassicFeatureFrontEnd::setResidentCapacity(int rows) { g_classic_resident_capacity = rows; }
 
 ClassicFeatureFrontEnd::ClassicFeatureFrontEnd()
@@ -447,6 +449,7 @@ ClassicFeatureFrontEnd::ClassicFeatureFrontEnd(const DetectorType detector_type,
   initMatcher();
   resident_ = g_classic_resident;
   resident_capacity_ = g_classic_resident_capacity;
+  brisk_pair_resident_ = g_classic_brisk_pair_resident;
 }
 
 ClassicFeatureFrontEnd::~ClassicFeatureFrontEnd() {
@@ -523,7 +526,8 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
 // setDeviceResident every one of these pairs is one submission per stereo pair instead (spvo_classic_detect, kinds 0 .. 4, or
 // spvo_sift_detect_pair) and is matched in its slots -- the BRISK pairs by the 64-byte instantiation of the slot matcher.  BRISK + BRISK
 // goes through spvo_brisk_detect (cv::BRISK::create()->detect, classic.cpp:9-11) and spvo_brisk_describe with the detector's x, y and size,
-// per image only: with setDeviceResident it takes the per-image path and residentPairs() stays 0.  AKAZE is an OpenCV features2d call and
+// per image: with setDeviceResident alone it takes the per-image path and residentPairs() stays 0; with setBriskPairResident as well it is
+// one spvo_brisk_detect_pair per stereo pair into the same binary slots (64-byte rows), matched there.  AKAZE is an OpenCV features2d call and
 // stays unavailable, and so does every other mix (BRISK keypoints with an ORB descriptor -- spvo_orb_describe refuses fractional
 // coordinates --, SIFT keypoints with an ORB descriptor, ...).
 bool ClassicFeatureFrontEnd::available() { return true; }
@@ -770,12 +774,52 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
   }
 }
 
-// setDeviceResident: the pair through ONE spvo_classic_detect (SIFT: spvo_sift_detect_pair) call into the next slot pair of the ring; the
+// setDeviceResident: the pair through ONE spvo_classic_detect (SIFT: spvo_sift_detect_pair; BRISK + BRISK with setBriskPairResident:
+// spvo_brisk_detect_pair) call into the next slot pair of the ring; the
 // deques are filled from what it hands out, which is what detectKeypoints + describeKeypoints produce image by image.  false: nothing was
 // pushed and the caller takes the per-image path (the pair does not fit its slots, or the call failed and the per-image path reports why).
 bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &img_l, cv::Mat &img_r) {
   if (img_l.depth() != CV_8U || img_l.rows <= 0 || img_r.depth() != CV_8U || (size_t)img_l.step != (size_t)img_r.step) return false;
-  if (classic_brisk_brisk(detector_type_, descriptor_type_)) return false;   // no slot kind for this pair: the per-image path, residentPairs() stays 0
+  if (classic_brisk_brisk(detector_type_, descriptor_type_)) {
+    if (!brisk_pair_resident_) return false;   // opt-in (setBriskPairResident): the per-image path, residentPairs() stays 0
+    if (resident_pairs_ == 0) spvo_set_prematch(ctx_, 1, selector_type_ == SelectorType::KNN ? SPVO_SELECT_KNN : SPVO_SELECT_NN, matcher_cross_check_ ? 1 : 0, knn_threshold_);
+    const int cap = std::max(resident_capacity_, 1);
+    spvo_brisk_features f[2];
+    for (int k = 0; k < 2; ++k) {
+      if (resident_sift_kp_[k].size() != (size_t)cap) { resident_sift_kp_[k].resize((size_t)cap); resident_desc_[k].resize((size_t)cap * 64); }   // first pair only
+      f[k] = spvo_brisk_features{0, resident_sift_kp_[k].data(), resident_desc_[k].data(), cap};
+    }
+    const int slot_l = 2 * (int)(resident_pairs_ % 4), slot_r = slot_l + 1;
+    ++resident_pairs_;
+    // cv::BRISK::create(): threshold 30, 3 octaves, as detectKeypoints
+    const int rc = spvo_brisk_detect_pair(ctx_, img_l.ptr<uint8_t>(0), img_r.ptr<uint8_t>(0), img_l.rows, img_l.cols, (size_t)img_l.step, 30, 3, slot_l, slot_r, resident_capacity_, &f[0], &f[1]);
+    if (rc != SPVO_OK) {
+      if (rc != SPVO_ERR_CAPACITY) logError(std::string("spvo_brisk_detect_pair: ") + spvo_last_error(ctx_));
+      return false;
+    }
+    ++resident_ok_pairs_;
+    cv::Mat *imgs[2] = {&img_l, &img_r};
+    for (int k = 0; k < 2; ++k) {
+      const int n = f[k].n;
+      std::vector<cv::KeyPoint> keypoints;
+      keypoints.reserve(n);
+      for (int i = 0; i < n; ++i) {   // as detectKeypoints + describeKeypoints leave them
+        const spvo_brisk_keypoint &p = resident_sift_kp_[k][i];
+        cv::KeyPoint q(cv::Point2f(p.x, p.y), p.size);
+        q.angle = -1.f;   // describeKeypoints keeps the angle the BRISK detector reports; the record's (the extractor's) stays with the slot
+        q.response = p.response;
+        q.octave = p.octave;   // the layer, 0 .. 5
+        keypoints.push_back(q);
+      }
+      cv::Mat d(n, 64, CV_8UC1);
+      if (n) std::memcpy(d.ptr<uint8_t>(0), resident_desc_[k].data(), (size_t)n * 64);
+      images_dq.push_back(*imgs[k]);
+      keypoints_dq.push_back(std::move(keypoints));
+      descriptors_dq.push_back(d);
+      bin_slots_dq_.push_back(k ? slot_r : slot_l);
+    }
+    return true;
+  }
   if (detector_type_ == DetectorType::SIFT) {
     if (resident_pairs_ == 0) spvo_set_prematch(ctx_, 1, selector_type_ == SelectorType::KNN ? SPVO_SELECT_KNN : SPVO_SELECT_NN, matcher_cross_check_ ? 1 : 0, knn_threshold_);
     const int cap = std::max(resident_capacity_, 1);

@@ -345,20 +345,24 @@ public:
   // descriptors_dq and every match are what they are with the option off (the default).  A pair with more rows than the slots hold
   // (setResidentCapacity; SPVO_ERR_CAPACITY) goes through the per-image path and is matched from the host matrices.  SIFT + SIFT does
   // the same through spvo_sift_detect_pair, the SIFT slots and spvo_match_l2_slots; ShiTomasi + BRISK and FAST + BRISK through the two BRISK
-  // kinds of spvo_classic_detect (64-byte rows in the same binary slots).
+  // kinds of spvo_classic_detect (64-byte rows in the same binary slots).  BRISK + BRISK takes the per-image path under setDeviceResident
+  // alone; with setBriskPairResident as well (opt-in, read at construction like the other two) it goes through spvo_brisk_detect_pair into
+  // the same binary slots.
   static void setDeviceResident(bool on);
   static void setResidentCapacity(int rows);   // rows per binary slot [8192]
-  // pairs that actually stayed resident (spvo_classic_detect / spvo_sift_detect_pair returned SPVO_OK): what tells the resident path from its fallback
+  static void setBriskPairResident(bool on);   // [off]
+  // pairs that actually stayed resident (spvo_classic_detect / spvo_sift_detect_pair / spvo_brisk_detect_pair returned SPVO_OK): what tells the resident path from its fallback
   unsigned residentPairs() const { return resident_ok_pairs_; }
 
 private:
   bool resident_ = false;
+  bool brisk_pair_resident_ = false;   // setBriskPairResident at construction
   int resident_capacity_ = 8192;
   unsigned resident_pairs_ = 0;   // pairs handed to spvo_classic_detect: pair k lives in slots 2 (k % 4), 2 (k % 4) + 1
   unsigned resident_ok_pairs_ = 0;   // ... of which the call returned SPVO_OK (residentPairs)
   std::vector<spvo_orb_keypoint> resident_kp_[2];   // what spvo_classic_detect hands out, resident_capacity_ rows per image: allocated once
   std::vector<uint8_t> resident_desc_[2];           // (rows of 32 bytes, of 64 with a BRISK descriptor)
-  std::vector<spvo_sift_keypoint> resident_sift_kp_[2];   // the same for spvo_sift_detect_pair
+  std::vector<spvo_sift_keypoint> resident_sift_kp_[2];   // the same for spvo_sift_detect_pair, and for spvo_brisk_detect_pair's records (the same layout; its rows: resident_desc_)
   std::vector<float> resident_sift_desc_[2];
   bool addStereoImagePairResident(cv::Mat &img_l, cv::Mat &img_r);
 #ifdef SPVO_USE_OPENCV

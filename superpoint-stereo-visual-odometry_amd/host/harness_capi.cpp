@@ -421,6 +421,10 @@ void spvo_host_classic_set_resident(int on, int capacity) {
   if (capacity > 0) ClassicFeatureFrontEnd::setResidentCapacity(capacity);
 }
 
+// ClassicFeatureFrontEnd::setBriskPairResident for the front ends constructed afterwards: BRISK + BRISK through spvo_brisk_detect_pair
+// when setDeviceResident is on as well
+void spvo_host_classic_set_brisk_resident(int on) { ClassicFeatureFrontEnd::setBriskPairResident(on != 0); }
+
 // the ORB + ORB front end at the native resolution (the export's first form)
 int spvo_host_classic_sequence(int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l, const double *P_r, int knn,
                                int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats, double *seconds) {

@@ -38,6 +38,10 @@ CLASSIC_KINDS = {"ORB": 0, "ShiTomasi": 1, "GFTT": 1, "FAST": 2, "ShiTomasi+BRIS
 CLASSIC_BRISK_KINDS = (3, 4)          # spvo_classic_kind values whose rows are 64 bytes
 
 
+class BriskFeatures(C.Structure):          # spvo_brisk_features
+    _fields_ = [("n", C.c_int), ("kp", C.c_void_p), ("desc", C.c_void_p), ("cap", C.c_int)]
+
+
 class SiftFeatures(C.Structure):
     _fields_ = [("n", C.c_int), ("kp", C.c_void_p), ("desc", C.c_void_p), ("cap", C.c_int)]
 
@@ -82,7 +86,7 @@ SYMBOLS = [
     "spvo_default_config", "spvo_create", "spvo_destroy", "spvo_last_error", "spvo_load_weights", "spvo_engine_precision", "spvo_set_fp32_split",
     "spvo_preprocess", "spvo_forward", "spvo_debug_tensor", "spvo_heatmap", "spvo_nms",
     "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8",
-    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_detect_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
+    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_detect_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
     "spvo_profile_enable", "spvo_profile_reset", "spvo_profile_only", "spvo_profile_count", "spvo_profile_get", "spvo_profile_stage_kernel",
     "spvo_set_tuning", "spvo_get_tuning", "spvo_clear_tuning",
     "spvo_comm_unique_id", "spvo_comm_available", "spvo_comm_create", "spvo_comm_create_host", "spvo_comm_rank", "spvo_comm_world", "spvo_comm_destroy",
@@ -143,6 +147,7 @@ def load() -> C.CDLL:
     lib.spvo_brisk_tables.argtypes = [C.c_int, vp, vp, vp, vp, vp]
     lib.spvo_brisk_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, vp, C.c_int, ip]
     lib.spvo_brisk_detect_debug_layer.argtypes = [vp, C.c_int, C.c_int, vp, ip, ip]
+    lib.spvo_brisk_detect_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(BriskFeatures), C.POINTER(BriskFeatures)]
     lib.spvo_sift_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, C.c_int, ip]
     lib.spvo_sift_debug_level.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, ip, ip]
     lib.spvo_sift_detect_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(SiftFeatures), C.POINTER(SiftFeatures)]
@@ -522,6 +527,36 @@ class Context:
         out = np.zeros((rows.value, cols.value), np.uint8)
         self._check(self.lib.spvo_brisk_detect_debug_layer(self.h, layer, what, _ptr(out), C.byref(rows), C.byref(cols)))
         return out
+
+    def brisk_detect_pair(self, img_l, img_r, slot_l: int, slot_r: int, threshold: int = 30, octaves: int = 3, slot_capacity: int = 8192, cap: Optional[int] = None):
+        """One stereo pair through the BRISK detector + extractor into two binary feature slots of 64-byte rows (spvo_brisk_detect_pair).
+        -> (left, right): dicts of kp [m] (BRISK_KP_DTYPE records: the detector's, with the extractor's angle in degrees), desc [m, 64] uint8
+        and n, the rows the slot holds; m = min(n, cap), cap = None: slot_capacity.  Strided views are accepted.
+        On SPVO_ERR_CAPACITY the SpvoError carries the two counts as .n_l, .n_r (and .counts)."""
+        l, r = _u8_rows(img_l), _u8_rows(img_r)
+        if l.shape != r.shape or l.strides[0] != r.strides[0]:
+            l, r = np.ascontiguousarray(l), np.ascontiguousarray(r)
+            if l.shape != r.shape:
+                raise ValueError("the two images of a pair must have one shape")
+        want = int(slot_capacity) if cap is None else int(cap)
+        bufs, feats = [], []
+        for _ in range(2):
+            kp = np.zeros(max(want, 1), BRISK_KP_DTYPE)
+            desc = np.zeros((max(want, 1), 64), np.uint8)
+            bufs.append((kp, desc))
+            feats.append(BriskFeatures(0, kp.ctypes.data, desc.ctypes.data, want))
+        rc = self.lib.spvo_brisk_detect_pair(self.h, _ptr(l), _ptr(r), l.shape[0], l.shape[1], l.strides[0], int(threshold), int(octaves), slot_l, slot_r, int(slot_capacity),
+                                             C.byref(feats[0]), C.byref(feats[1]))
+        if rc:
+            e = SpvoError(rc, self.lib.spvo_last_error(self.h).decode())
+            e.n_l, e.n_r = feats[0].n, feats[1].n
+            e.counts = (e.n_l, e.n_r)
+            raise e
+        out = []
+        for (kp, desc), f in zip(bufs, feats):
+            m = min(f.n, max(want, 0))
+            out.append(dict(kp=kp[:m].copy(), desc=desc[:m].copy(), n=f.n))
+        return out[0], out[1]
 
     def sift_detect(self, img: np.ndarray, cap: Optional[int] = None):
         """SIFT keypoints + descriptors of one u8 image (spvo_sift_detect): dict of kp [m] (SIFT_KP_DTYPE records), desc [m, 128] float32 (integers

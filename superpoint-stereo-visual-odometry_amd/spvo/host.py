@@ -342,15 +342,16 @@ class FrontEnd:
 
 
 def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_threshold=2.0, refinement_degree=4, warm=0, detector="ORB", input_size=None, resident=False,
-                     resident_capacity=0, trace=False, descriptor="ORB"):
+                     resident_capacity=0, trace=False, descriptor="ORB", brisk_resident=False):
     """stereoCallback replayed on ClassicFeatureFrontEnd(detector, descriptor, BF, ...) (node.cpp:353-360) over host image pairs -- detector
     "ORB", "ShiTomasi" or "FAST" with descriptor "ORB", "ShiTomasi", "FAST" or "BRISK" with descriptor "BRISK" (64-byte rows; detector "BRISK" with
     the default descriptor "ORB" does not run), or detector "SIFT" (SIFT descriptors whatever `descriptor` says, as before); input_size None: at their native resolution, (height, width): through preprocessImageImpl first
     (classic.cpp:96-100).  Returns (poses [n, 7] = q xyzw + t of cam0_curr_T_cam0_prev, stats [n, 4] = keypoints L, R, stereo
     matches, PnP inliers, seconds spent on frames warm .. n-1).
     resident: ClassicFeatureFrontEnd::setDeviceResident for this run -- one spvo_classic_detect (SIFT: spvo_sift_detect_pair) per pair, features
-    and matching stay on the device, for every pair named above with BRISK descriptors on ShiTomasi / FAST keypoints included; "BRISK" + "BRISK" has no
-    slot kind yet and takes the per-image path, classic_resident_pairs() stays 0 (resident_capacity > 0: rows per slot; a pair that does not
+    and matching stay on the device, for every pair named above with BRISK descriptors on ShiTomasi / FAST keypoints included; "BRISK" + "BRISK"
+    takes the per-image path and classic_resident_pairs() stays 0 unless brisk_resident (ClassicFeatureFrontEnd::setBriskPairResident) is set
+    as well: then it is one spvo_brisk_detect_pair per pair into the same binary slots (resident_capacity > 0: rows per slot; a pair that does not
     fit falls back to the per-image path; classic_resident_pairs() tells how many pairs of the run stayed resident).
     trace: a fourth value, digests [n, 8] uint64 of what every frame left in the front end (keypoints L, descriptors L, keypoints R,
     descriptors R, stereo matches, temporal matches, the previous frame's stereo matches + map, the inlier sets): equal digests = identical
@@ -363,6 +364,8 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     lib.spvo_host_classic_sequence_desc.argtypes = [C.c_char_p, C.c_char_p] + lib.spvo_host_classic_sequence_trace.argtypes[1:]
     lib.spvo_host_classic_set_resident.restype = None
     lib.spvo_host_classic_set_resident.argtypes = [C.c_int, C.c_int]
+    lib.spvo_host_classic_set_brisk_resident.restype = None
+    lib.spvo_host_classic_set_brisk_resident.argtypes = [C.c_int]
     n = len(frames)
     ls = [np.ascontiguousarray(f[0], np.uint8) for f in frames]
     rs = [np.ascontiguousarray(f[1], np.uint8) for f in frames]
@@ -377,6 +380,7 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     ih, iw = (0, 0) if input_size is None else (int(input_size[0]), int(input_size[1]))
     digest = np.zeros((n, 8), np.uint64) if trace else None     # NULL: nothing is digested (the digests are computed inside the timed loop)
     lib.spvo_host_classic_set_resident(int(bool(resident)), int(resident_capacity) if resident_capacity > 0 else 8192)
+    lib.spvo_host_classic_set_brisk_resident(int(bool(brisk_resident)))
     try:
         args = (n, pl, pr, rows, cols, Pl.ctypes.data, Pr.ctypes.data, 1 if selector == "KNN" else 0, int(cross_check), stereo_threshold, refinement_degree, warm,
                 poses.ctypes.data, stats.ctypes.data, C.byref(sec), ih, iw, digest.ctypes.data if trace else None)
@@ -386,6 +390,7 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
             rc = lib.spvo_host_classic_sequence_desc(detector.encode(), descriptor.encode(), *args)
     finally:
         lib.spvo_host_classic_set_resident(0, 8192)
+        lib.spvo_host_classic_set_brisk_resident(0)
     if rc == -1000000:
         raise ValueError("unknown detector %r" % (detector,))
     if rc == -1000001:

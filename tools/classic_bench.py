@@ -1,9 +1,10 @@
 """The classic front end on the GPU.
 
-python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK] [--descriptor ORB|BRISK] [--resident]
+python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK] [--descriptor ORB|BRISK] [--resident] [--brisk-resident]
     ClassicFeatureFrontEnd(detector, descriptor, BF, KNN) over the synthetic stream: frames/s of the synchronous stereoCallback
     (--descriptor BRISK: with --detector ShiTomasi, FAST or BRISK; --detector BRISK: with --descriptor BRISK only);
-    --resident: with ClassicFeatureFrontEnd::setDeviceResident (one spvo_classic_detect per pair, matching on the binary slots).
+    --resident: with ClassicFeatureFrontEnd::setDeviceResident (one spvo_classic_detect per pair, matching on the binary slots);
+    --brisk-resident: with setBriskPairResident as well (BRISK + BRISK through one spvo_brisk_detect_pair per pair; needs --resident).
 python tools/classic_bench.py [frames] --detector ShiTomasi|FAST|ORB --descriptor ORB|BRISK --ab ROUNDS
     the same stream with setDeviceResident off and on, alternating, ROUNDS times each in one process: ms per pair of every run, the median
     and the min .. max spread of each setting, and how many pairs of a resident run stayed resident.
@@ -23,6 +24,10 @@ python tools/classic_bench.py --leg brisk_detect [--calls 50]
     spvo_brisk_detect (threshold 30) alone per image at 1241 x 376, for rocprofv3 --kernel-trace --stats as above: brisk_area_kernel /
     brisk_half_kernel / brisk_score916_kernel / brisk_score58_kernel / brisk_collect_kernel / cls_rank_kernel / brisk_refine_kernel /
     brisk_det_compact_kernel is the split.
+python tools/classic_bench.py --leg brisk_pair [--calls 50]
+    spvo_brisk_detect_pair (threshold 30) alone on the 1241 x 376 sample pair, rotating through the slot ring, for rocprofv3 --kernel-trace
+    --stats as above: the detector's kernels up to brisk_refine_kernel, then brisk_integral_*_kernel / brisk_pair_compact_kernel /
+    brisk_describe_kernel / brisk_pair_finish_kernel, twice per call.
 python tools/classic_bench.py --leg match|match_slots [--selector NN|KNN] [--cross] [--calls 50]
     one matcher alone on the two resident ORB sets of the 1241 x 376 sample pair: spvo_match_hamming on the host copies (match_hamming_kernel<8>)
     or spvo_match_hamming_slots on the binary slots (match_hamming_tiled_kernel), for rocprofv3 --kernel-trace --stats as above.
@@ -43,8 +48,9 @@ ap.add_argument("--detector", default="ORB")
 ap.add_argument("--descriptor", default="ORB")
 ap.add_argument("--detectors", action="store_true")
 ap.add_argument("--resident", action="store_true")
+ap.add_argument("--brisk-resident", action="store_true")
 ap.add_argument("--ab", type=int, default=0)
-ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "brisk_detect", "orb_describe", "match", "match_slots"])
+ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "brisk_detect", "brisk_pair", "orb_describe", "match", "match_slots"])
 ap.add_argument("--selector", default="KNN", choices=["NN", "KNN"])
 ap.add_argument("--cross", action="store_true")
 ap.add_argument("--calls", type=int, default=200)
@@ -86,6 +92,17 @@ if args.detectors or args.leg:
     def leg_brisk_detect():
         return ctx.brisk_detect(img, 30)["n"]
 
+    pair_calls = [0]
+
+    def leg_brisk_pair():
+        k = pair_calls[0] % 4
+        pair_calls[0] += 1
+        fl, fr = ctx.brisk_detect_pair(img, pair_r, 2 * k, 2 * k + 1, 30)
+        return fl["n"] + fr["n"]
+
+    if args.leg == "brisk_pair":
+        pair_r = np.ascontiguousarray(frames[0][1][:376, :1241])
+
     def leg_orb_describe():
         return len(ctx.orb_describe(img, kp)["kept"])
 
@@ -106,7 +123,7 @@ if args.detectors or args.leg:
                 match_slots=("spvo_match_hamming_slots, %d x %d rows" % (len(fl["xy"]) if leg_match else 0, len(fr["xy"]) if leg_match else 0), leg_match_slots),
                 brisk=("spvo_brisk_describe, %d FAST keypoints" % (len(kp) if args.leg == "brisk" else 0), leg_brisk),
                 orb_describe=("spvo_orb_describe, %d FAST keypoints" % (len(kp) if args.leg == "orb_describe" else 0), leg_orb_describe),
-                brisk_detect=("spvo_brisk_detect", leg_brisk_detect),
+                brisk_detect=("spvo_brisk_detect", leg_brisk_detect), brisk_pair=("spvo_brisk_detect_pair (both images)", leg_brisk_pair),
                 orb=("spvo_orb_detect", leg_orb), sift=("spvo_sift_detect", leg_sift), gftt=("spvo_gftt_detect + spvo_orb_describe", leg_gftt), fast=("spvo_fast_detect + spvo_orb_describe", leg_fast))
     for key in ([args.leg] if args.leg else ["orb", "gftt", "fast"]):
         name, fn = legs[key]
@@ -144,5 +161,6 @@ elif args.ab > 0:
 else:
     n = args.frames
     seq = [frames[i % 8] for i in range(n)]
-    p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5, detector=args.detector, resident=args.resident, descriptor=args.descriptor)
-    print("classic front end (%s%s) on the GPU: %.1f stereo frames/s (%.3f ms per pair), keypoints %d, stereo matches %d, inliers %d" % (args.detector + ("" if args.descriptor == "ORB" else " + " + args.descriptor), ", device-resident" if args.resident else "", (n - 5) / sec, 1e3 * sec / (n - 5), np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3])))
+    p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5, detector=args.detector, resident=args.resident, descriptor=args.descriptor,
+                                        **(dict(brisk_resident=True) if args.brisk_resident else {}))
+    print("classic front end (%s%s) on the GPU: %.1f stereo frames/s (%.3f ms per pair), keypoints %d, stereo matches %d, inliers %d, %d pairs resident" % (args.detector + ("" if args.descriptor == "ORB" else " + " + args.descriptor), ", device-resident" if args.resident else "", (n - 5) / sec, 1e3 * sec / (n - 5), np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3]), host.classic_resident_pairs()))
