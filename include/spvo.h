@@ -346,6 +346,41 @@ int spvo_brisk_detect(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, siz
  * included. */
 int spvo_brisk_detect_debug_layer(spvo_ctx *ctx, int layer, int what, uint8_t *out, int *rows, int *cols);
 
+/* detectKeypoints for DetectorType::AKAZE (cv::AKAZE::create() -> detect, feature_detection_classic.cpp:26-28: 4 octaves of 4 sublevels,
+ * PM_G2 diffusivity, soffset 1.6, derivative factor 1.5, contrast percentile 0.7 over 300 bins, floor min_dthreshold 1e-5) on one 8-bit image
+ * in host memory: the nonlinear scale space (level 0 = the image / 255 blurred with sigma 1.6; every further level = the level before --
+ * half-sampled with cv::resize(INTER_AREA)'s arithmetic on a new octave -- diffused by its Fast Explicit Diffusion steps under the
+ * conductivity of its own sigma 1 blur), the scale-normalised Hessian determinant of every level, the candidates (above the threshold,
+ * strict 8-neighbour maxima, inside the descriptor border of their level) and their sub-pixel offsets on the device; the order-dependent
+ * suppression between candidates of the same and of neighbouring levels on the host, over the copied list.  Only the detector: the
+ * orientation and the MLDB descriptor are not built (OpenCV computes both in compute), so `angle` is 0 as detect leaves it.  OpenCV is not
+ * available to this build: the algorithm is OpenCV's as far as it is known, as restated by tests/akaze_ref.py (its header lists every rule
+ * and marks what is a decision of this project; it mixes OpenCV generations on purpose: 4.x's sigma_size^4 factor on the determinant, 3.x's
+ * reflect-101 blur border and sequential suppression), and the kernels reproduce that restatement bit for bit in every plane and in every field
+ * of a record: x, y, size = 2 * 1.5 * esigma, angle = 0, response = Ldet, octave, class_id = level 0 .. 15.  Keypoints come in the order
+ * the suppression leaves them.  `n` receives their number, of which min(n, cap) are written; strided input is accepted.  The image stays on
+ * the device for a spvo_brisk_describe(img = NULL) that follows, exactly as after spvo_fast_detect and spvo_brisk_detect.
+ *   SPVO_ERR_INVALID   a threshold that is not finite and positive; an image smaller than 16 x 16; rows * cols * 255 >= 2^31 (so that the
+ *                      spvo_brisk_describe that follows cannot fail on its int32 integral image)
+ *   SPVO_ERR_STATE     a spvo_detect*_submit is in flight; the candidate list overflowed (it is sized from the image, so this reports a
+ *                      defect, not an input) */
+typedef struct { float x, y, size, angle, response; int32_t octave, class_id; } spvo_akaze_keypoint;
+int spvo_akaze_detect(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, size_t stride, float threshold,
+                      spvo_akaze_keypoint *kp /* [cap] */, int cap, int *n);
+/* A level of the scale space of this context's last spvo_akaze_detect (test hook): what = 0 Lt, 1 Lsmooth, 2 Lflow (zeros on level 0, which
+ * has none), 3 Ldet.  `out` (rows x cols floats) may be NULL to ask for the shape only.  SPVO_ERR_INVALID for a level the image does not
+ * have; SPVO_ERR_STATE when no result is resident: no call yet, or any other call has since put an image into the context's resident
+ * image buffer, the same image included. */
+int spvo_akaze_debug_level(spvo_ctx *ctx, int level, int what, float *out, int *rows, int *cols);
+/* The contrast factor k of every octave of the last spvo_akaze_detect, as the kernels left it in device memory.  SPVO_ERR_STATE as above. */
+int spvo_akaze_last_contrast(spvo_ctx *ctx, float *k /* [4], per octave */, int *octaves);
+/* The detector's tables for a rows x cols image (no context, no device): per level its octave, esigma and sigma_size (up to 16 levels),
+ * the number of diffusion steps of each of the levels - 1 transitions and their sizes one transition after the other (`n_tau` receives
+ * their number, min(n_tau, tau_cap) are written), the centre and the taps of one side of the Gaussian kernels of sigma 1.6 (g0, 5 floats)
+ * and sigma 1 (g1, 3 floats).  Every array may be NULL.  SPVO_ERR_INVALID for an image smaller than 16 x 16. */
+int spvo_akaze_tables(int rows, int cols, int *levels, int32_t *octave, float *esigma, int32_t *sigma_size, int32_t *nsteps, float *tau, int tau_cap,
+                      int *n_tau, float *g0, float *g1);
+
 /* ------------------------------------------------------- classic front end: one submission per stereo pair, features resident
  * detectKeypoints + describeKeypoints of ClassicFeatureFrontEnd for BOTH images of a stereo pair in one call: ORB, or Shi-Tomasi /
  * FAST followed by the ORB extractor or by the BRISK extractor (the five pairs the per-image entry points above cover).  Both images go up through pinned

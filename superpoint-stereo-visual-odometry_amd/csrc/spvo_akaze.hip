@@ -1,0 +1,347 @@
+// spvo_akaze.hip -- the classic front end's AKAZE keypoint detector (akaze.hip.h): the tables of a shape (levels, FED step sizes, Gaussian
+// taps: built on the host by the formulas tests/akaze_ref.py lists, spvo_akaze_tables), the chain of launches of spvo_akaze_detect, the
+// order-dependent suppression between candidates on the host (rule 11: the restatement's loop over the copied candidate list), and the
+// test hooks.  Runs on the solver's stream (stream2) with the image resident in spvo_ctx::cls -- it stays there for a
+// spvo_brisk_describe(img = NULL) that follows -- and owns everything else it needs (spvo_ctx::akaze).
+#include "spvo_internal.hip.h"
+#include "akaze.hip.h"
+
+namespace {
+constexpr int AK_SUBLEVELS = 4;
+
+struct AkTables {
+  int n = 0, octaves = 0;
+  int oh[AKAZE_MAX_OCTAVES] = {0}, ow[AKAZE_MAX_OCTAVES] = {0};
+  int octave[AKAZE_MAX_LEVELS] = {0}, sigma_size[AKAZE_MAX_LEVELS] = {0}, nsteps[AKAZE_MAX_LEVELS] = {0};   // nsteps[i]: the transition i - 1 -> i
+  float esigma[AKAZE_MAX_LEVELS] = {0};
+  std::vector<float> tau;
+  AkazeTaps g0{}, g1{};
+};
+
+bool is_prime(int n) {
+  if (n < 2) return false;
+  for (int d = 2; d * d <= n; ++d)
+    if (n % d == 0) return false;
+  return true;
+}
+
+// rule 1: fed_tau_by_process_time(t, 1, 0.25, reordering) in float, appended to `out`; -> the number of steps
+int fed_tau(float t, std::vector<float> &out) {
+#pragma clang fp contract(off)
+  const float tau_max = 0.25f;
+  const int n = (int)std::ceil(sqrtf(3.0f * t / tau_max + 0.25f) - 0.5f - 1.0e-8f);
+  if (n <= 0) return 0;
+  const float scale = 3.0f * t / (tau_max * (float)(n * (n + 1)));
+  const float c = 1.0f / (4.0f * (float)n + 2.0f), d = scale * tau_max / 2.0f;
+  std::vector<float> tauh((size_t)n);
+  for (int k = 0; k < n; ++k) {
+    const float h = cosf((float)M_PI * (2.0f * (float)k + 1.0f) * c);
+    tauh[k] = d / (h * h);
+  }
+  const int kappa = n / 2;
+  int prime = n + 1;
+  while (!is_prime(prime)) ++prime;
+  for (int k = 0, l = 0; l < n; ++k, ++l) {
+    int index;
+    while ((index = ((k + 1) * kappa) % prime - 1) >= n) ++k;
+    out.push_back(tauh[index]);
+  }
+  return n;
+}
+
+// rule 2
+AkazeTaps gaussian_taps(double sigma) {
+  AkazeTaps t{};
+  const int ksize = (int)std::ceil(2.0 * (1.0 + (sigma - 0.8) / 0.3)) | 1;
+  t.r = std::min(ksize / 2, AKAZE_BLUR_R);
+  double v[2 * AKAZE_BLUR_R + 1], sum = 0;
+  for (int i = -t.r; i <= t.r; ++i) sum += v[i + t.r] = std::exp(-((double)i * i) / (2.0 * sigma * sigma));
+  for (int j = 0; j <= t.r; ++j) t.g[j] = (float)(v[j + t.r] / sum);
+  return t;
+}
+
+AkTables make_tables(int rows, int cols) {
+#pragma clang fp contract(off)
+  AkTables T;
+  for (int o = 0; o < AKAZE_MAX_OCTAVES; ++o) {
+    const int h = (int)(rows / (double)(1 << o)), w = (int)(cols / (double)(1 << o));
+    if (o > 0 && (w < 80 || h < 40)) break;
+    T.oh[o] = h; T.ow[o] = w; T.octaves = o + 1;
+    for (int j = 0; j < AK_SUBLEVELS; ++j, ++T.n) {
+      T.octave[T.n] = o;
+      T.esigma[T.n] = 1.6f * powf(2.f, (float)j / (float)AK_SUBLEVELS + (float)o);
+      T.sigma_size[T.n] = (int)std::nearbyint(T.esigma[T.n] * 1.5f / (float)(1 << o));
+    }
+  }
+  for (int i = 1; i < T.n; ++i) {
+    const float e1 = 0.5f * T.esigma[i] * T.esigma[i], e0 = 0.5f * T.esigma[i - 1] * T.esigma[i - 1];
+    T.nsteps[i] = fed_tau(e1 - e0, T.tau);
+  }
+  T.g0 = gaussian_taps(1.6);
+  T.g1 = gaussian_taps(1.0);
+  return T;
+}
+
+int level_border(int sigma_size) {
+#pragma clang fp contract(off)
+  return (int)std::nearbyint(10.0f * sqrtf(2.0f) * (float)sigma_size) + 1;
+}
+
+size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
+dim3 grid_of(int w, int h) { return dim3((w + 63) / 64, (h + 3) / 4, 1); }
+
+// layout, tables and buffers for a rows x cols image
+int ak_ensure(spvo_ctx *c, int rows, int cols) {
+  auto &d = c->akaze;
+  hipStream_t st = c->stream2;
+  d.valid = false;
+  if (!d.stat) {
+    if (int rc = dev_alloc(c, &d.stat, AKAZE_STAT_INTS)) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
+  }
+  if (d.rows == rows && d.cols == cols) return SPVO_OK;
+  d.rows = d.cols = 0;
+  const AkTables T = make_tables(rows, cols);
+  size_t planes = 0, tabs = 0, off[AKAZE_MAX_LEVELS], tab_off[AKAZE_MAX_OCTAVES] = {0};
+  long long cand = 0;
+  for (int i = 0; i < T.n; ++i) {
+    const int h = T.oh[T.octave[i]], w = T.ow[T.octave[i]], b = level_border(T.sigma_size[i]);
+    off[i] = planes;
+    planes += 4 * align64((size_t)h * w);
+    cand += (long long)((std::max(h - 2 * b, 0) + 1) / 2) * ((std::max(w - 2 * b, 0) + 1) / 2);   // strict maxima do not touch, diagonally either
+  }
+  bool exact[AKAZE_MAX_OCTAVES] = {false};
+  for (int o = 1; o < T.octaves; ++o) {
+    exact[o] = T.oh[o - 1] == 2 * T.oh[o] && T.ow[o - 1] == 2 * T.ow[o];
+    if (!exact[o]) { tab_off[o] = tabs; tabs += (size_t)T.ow[o] + T.oh[o]; }
+  }
+  d.h_tabs.assign(std::max<size_t>(tabs, 1), BriskAreaTap{});
+  for (int o = 1; o < T.octaves; ++o)
+    if (!exact[o] && !(brisk_area_tab(T.ow[o - 1], T.ow[o], d.h_tabs.data() + tab_off[o]) && brisk_area_tab(T.oh[o - 1], T.oh[o], d.h_tabs.data() + tab_off[o] + T.ow[o])))
+      return fail(c, SPVO_ERR_STATE, "AKAZE detector: the area taps of octave %d (%d x %d from %d x %d) failed their own checks", o, T.oh[o], T.ow[o], T.oh[o - 1], T.ow[o - 1]);
+  const size_t scratch = 3 * align64((size_t)rows * cols);
+  if (planes > d.plane_cap || scratch > d.scratch_cap || tabs > d.tab_cap || cand > d.cand_cap) {
+    HIP_TRY(c, hipStreamSynchronize(st));
+    dev_free(d.planes, d.scratch, d.tabs, d.keys, d.rank, d.rec);
+    const size_t np = std::max(planes, d.plane_cap), ns = std::max(scratch, d.scratch_cap), nt = std::max(std::max<size_t>(tabs, 1), d.tab_cap);
+    const int nc = (int)std::min<long long>(std::max<long long>(std::max<long long>(cand, 1), d.cand_cap), 0x7FFFFFFF);
+    d.plane_cap = d.scratch_cap = d.tab_cap = 0; d.cand_cap = 0;   // a failed allocation below leaves a context that spvo_destroy and a later call can still handle
+    int rc;
+    if ((rc = dev_alloc(c, &d.planes, np, false)) || (rc = dev_alloc(c, &d.scratch, ns, false)) || (rc = dev_alloc(c, &d.tabs, nt, false)) || (rc = dev_alloc(c, &d.keys, nc, false)) ||
+        (rc = dev_alloc(c, &d.rank, nc)) || (rc = dev_alloc(c, &d.rec, nc, false)))
+      return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    d.plane_cap = np; d.scratch_cap = ns; d.tab_cap = nt; d.cand_cap = nc;
+  }
+  HIP_TRY(c, hipMemcpyAsync(d.tabs, d.h_tabs.data(), d.h_tabs.size() * sizeof(BriskAreaTap), hipMemcpyHostToDevice, st));
+  d.lv = AkazeLevels{};
+  d.lv.n = T.n;
+  for (int i = 0; i < T.n; ++i) {
+    AkazeLevel &L = d.lv.l[i];
+    L.h = T.oh[T.octave[i]]; L.w = T.ow[T.octave[i]];
+    const size_t px = align64((size_t)L.h * L.w);
+    L.Lt = d.planes + off[i]; L.Lsmooth = L.Lt + px; L.Lflow = L.Lsmooth + px; L.Ldet = L.Lflow + px;
+    L.octave = T.octave[i]; L.sigma_size = T.sigma_size[i]; L.border = level_border(T.sigma_size[i]); L.esigma = T.esigma[i];
+    d.nsteps[i] = T.nsteps[i];
+  }
+  HIP_TRY(c, hipMemsetAsync(d.lv.l[0].Lflow, 0, (size_t)rows * cols * sizeof(float), st));   // level 0 has no flow: the plane reads as zeros
+  for (int o = 0; o < AKAZE_MAX_OCTAVES; ++o) {
+    d.xtab[o] = o >= 1 && o < T.octaves && !exact[o] ? d.tabs + tab_off[o] : nullptr;
+    d.ytab[o] = d.xtab[o] ? d.xtab[o] + T.ow[o] : nullptr;
+  }
+  d.octaves = T.octaves;
+  d.h_tau = T.tau;
+  d.g0 = T.g0; d.g1 = T.g1;
+  d.rows = rows; d.cols = cols;
+  return SPVO_OK;
+}
+
+// rule 11 over the candidates `cd` (level by level, raster order) -> the indices of the survivors, in the list's order
+void ak_suppress(const AkazeLevels &lv, const std::vector<AkazeCand> &cd, std::vector<int> &keep) {
+#pragma clang fp contract(off)
+  struct Aux { float x, y, size, response; int level, index; };
+  std::vector<Aux> aux;
+  aux.reserve(cd.size());
+  for (size_t i = 0; i < cd.size(); ++i) {
+    const AkazeCand &p = cd[i];
+    const float ratio = (float)(1 << p.octave), half = 0.5f * (ratio - 1.f), size = lv.l[p.class_id].esigma * 1.5f, size2 = size * size;
+    const float px = (float)p.col * ratio, py = (float)p.row * ratio;
+    size_t slot = aux.size();
+    bool drop = false;
+    for (size_t k = 0; k < aux.size(); ++k) {
+      if (aux[k].level != p.class_id && aux[k].level != p.class_id - 1) continue;
+      const float dx = px - aux[k].x, dy = py - aux[k].y;
+      const float dxx = dx * dx, dyy = dy * dy;
+      if (dxx + dyy <= size2) {
+        if (p.response > aux[k].response) slot = k; else drop = true;
+        break;
+      }
+    }
+    if (drop) continue;
+    const Aux a{px + half, py + half, size, p.response, p.class_id, (int)i};
+    if (slot == aux.size()) aux.push_back(a); else aux[slot] = a;
+  }
+  keep.clear();
+  for (size_t i = 0; i < aux.size(); ++i) {
+    bool repeated = false;
+    const float size2 = aux[i].size * aux[i].size;
+    for (size_t j = i + 1; j < aux.size() && !repeated; ++j) {
+      if (aux[j].level != aux[i].level + 1) continue;
+      const float dx = aux[i].x - aux[j].x, dy = aux[i].y - aux[j].y;
+      const float dxx = dx * dx, dyy = dy * dy;
+      repeated = dxx + dyy <= size2 && aux[i].response < aux[j].response;
+    }
+    if (!repeated) keep.push_back(aux[i].index);
+  }
+}
+}  // namespace
+
+void spvo_int::akaze_release(spvo_ctx *c) {
+  auto &d = c->akaze;
+  dev_free(d.planes, d.scratch, d.tabs, d.keys, d.rank, d.rec, d.stat);
+  d.plane_cap = d.scratch_cap = d.tab_cap = 0; d.cand_cap = 0; d.rows = d.cols = 0; d.valid = false;
+}
+
+extern "C" {
+
+int spvo_akaze_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride, float threshold, spvo_akaze_keypoint *kp, int cap, int *n_out) {
+  if (!c || !img || !n_out || rows <= 0 || cols <= 0 || stride < (size_t)cols || cap < 0 || (cap > 0 && !kp)) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  *n_out = 0;
+  if (!std::isfinite(threshold) || !(threshold > 0.f)) return fail(c, SPVO_ERR_INVALID, "spvo_akaze_detect: the threshold must be finite and positive");
+  if (rows < 16 || cols < 16) return fail(c, SPVO_ERR_INVALID, "spvo_akaze_detect: images of at least 16 x 16 only");
+  if (int rc = brisk_check_image(c, "spvo_akaze_detect", rows, cols)) return rc;
+  if (int rc = require_idle(c)) return rc;
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = c->stream2;
+  if (int rc = classic_upload_image(c, img, rows, cols, stride)) return rc;
+  if (int rc = ak_ensure(c, rows, cols)) return rc;
+  auto &d = c->akaze;
+  const AkazeLevels &lv = d.lv;
+  const size_t px0 = align64((size_t)rows * cols);
+  float *lx = d.scratch, *ly = d.scratch + px0, *ping = d.scratch + 2 * px0;
+  const dim3 blk(256);
+  auto blur_grid = [](int w, int h) { return dim3((w + AKAZE_TW - 1) / AKAZE_TW, (h + AKAZE_TH - 1) / AKAZE_TH, 1); };
+  HIP_TRY(c, hipMemsetAsync(d.stat, 0, AKAZE_STAT_INTS * sizeof(int), st));
+  // level 0 (rules 3, 4) and the contrast factor (rule 5; its sigma 1 blur borrows the first scratch plane)
+  hipLaunchKernelGGL(akaze_blur_kernel<uint8_t>, blur_grid(cols, rows), blk, 0, st, c->cls.im, lv.l[0].Lt, lv.l[0].Lsmooth, rows, cols, d.g0);
+  hipLaunchKernelGGL(akaze_blur_kernel<uint8_t>, blur_grid(cols, rows), blk, 0, st, c->cls.im, lx, (float *)nullptr, rows, cols, d.g1);
+  hipLaunchKernelGGL(akaze_gradmax_kernel, grid_of(cols, rows), blk, 0, st, lx, rows, cols, d.stat);
+  hipLaunchKernelGGL(akaze_hist_kernel, grid_of(cols, rows), blk, 0, st, lx, rows, cols, d.stat);
+  hipLaunchKernelGGL(akaze_contrast_finish_kernel, dim3(1), dim3(64), 0, st, rows, cols, d.octaves, d.stat);
+  // rules 6 - 8: every further level
+  size_t t0 = 0;
+  for (int i = 1; i < lv.n; ++i) {
+    const AkazeLevel &L = lv.l[i], &P = lv.l[i - 1];
+    const int n = d.nsteps[i];
+    const float *start = P.Lt;
+    if (L.octave > P.octave) {
+      float *half = (n % 2 == 0) ? L.Lt : ping;   // so that the last step's output is L.Lt
+      if (d.xtab[L.octave]) hipLaunchKernelGGL(akaze_area_kernel, grid_of(L.w, L.h), blk, 0, st, P.Lt, half, P.w, L.h, L.w, d.xtab[L.octave], d.ytab[L.octave]);
+      else hipLaunchKernelGGL(akaze_half_kernel, grid_of(L.w, L.h), blk, 0, st, P.Lt, half, P.w, L.h, L.w);
+      start = half;
+    }
+    hipLaunchKernelGGL(akaze_blur_kernel<float>, blur_grid(L.w, L.h), blk, 0, st, start, L.Lsmooth, (float *)nullptr, L.h, L.w, d.g1);
+    hipLaunchKernelGGL(akaze_flow_kernel, grid_of(L.w, L.h), blk, 0, st, L.Lsmooth, L.Lflow, L.h, L.w, d.stat + AKAZE_STAT_K + L.octave);
+    if (n == 0 && start != L.Lt) HIP_TRY(c, hipMemcpyAsync(L.Lt, start, (size_t)L.h * L.w * sizeof(float), hipMemcpyDeviceToDevice, st));
+    const float *in = start;
+    for (int s = 1; s <= n; ++s) {
+      float *out = ((n - s) % 2 == 0) ? L.Lt : ping;   // alternates, ends in L.Lt, and never equals `in`
+      hipLaunchKernelGGL(akaze_fed_kernel, grid_of(L.w, L.h), blk, 0, st, in, L.Lflow, out, L.h, L.w, 0.5f * d.h_tau[t0 + s - 1]);
+      in = out;
+    }
+    t0 += n;
+  }
+  // rule 9
+  for (int i = 0; i < lv.n; ++i) {
+    const AkazeLevel &L = lv.l[i];
+    const int s = L.sigma_size;
+    float norm, wn;
+    {
+#pragma clang fp contract(off)
+      const float w = 10.0f / 3.0f;
+      norm = 1.0f / ((2.0f * (float)s) * (w + 2.0f));
+      wn = w * norm;
+    }
+    hipLaunchKernelGGL(akaze_deriv_kernel, grid_of(L.w, L.h), blk, 0, st, L.Lsmooth, lx, ly, L.h, L.w, s, norm, wn);
+    hipLaunchKernelGGL(akaze_det_kernel, grid_of(L.w, L.h), blk, 0, st, lx, ly, L.Ldet, L.h, L.w, s, norm, wn, (float)(s * s * s * s));
+  }
+  // rules 10, 12, 13
+  for (int first = 0; first < lv.n; first += AK_SUBLEVELS) {   // one launch per octave; an octave with no room inside its smallest border has none
+    const AkazeLevel &L = lv.l[first];
+    if (L.h <= 2 * L.border || L.w <= 2 * L.border) continue;
+    dim3 eg = grid_of(L.w, L.h);
+    eg.z = std::min(AK_SUBLEVELS, lv.n - first);
+    hipLaunchKernelGGL(akaze_extrema_kernel, eg, blk, 0, st, lv, first, threshold, 1e-5f, d.keys, d.cand_cap, d.stat);
+  }
+  classic_rank_enqueue(c, d.keys, d.rank, d.stat + AKAZE_STAT_NCAND, d.cand_cap);
+  hipLaunchKernelGGL(akaze_refine_kernel, dim3(32), blk, 0, st, lv, d.keys, d.rank, d.cand_cap, d.stat, d.rec);
+  HIP_TRY(c, hipGetLastError());
+  int stat[AKAZE_STAT_HIST];
+  HIP_TRY(c, hipMemcpyAsync(stat, d.stat, sizeof stat, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  // (the list holds every strict maximum the borders leave room for, so the overflow flag cannot be set; were it, the count would be wrong)
+  if (stat[AKAZE_STAT_OVERFLOW] || stat[AKAZE_STAT_NCAND] > d.cand_cap) return fail(c, SPVO_ERR_STATE, "spvo_akaze_detect: the candidate list overflowed although it is sized from the image");
+  d.valid = true;
+  d.image_gen = c->cls.image_gen;
+  for (int o = 0; o < AKAZE_MAX_OCTAVES; ++o) std::memcpy(&d.k[o], &stat[AKAZE_STAT_K + o], sizeof(float));
+  d.h_cand.resize((size_t)stat[AKAZE_STAT_NCAND]);
+  if (!d.h_cand.empty()) {
+    HIP_TRY(c, hipMemcpyAsync(d.h_cand.data(), d.rec, d.h_cand.size() * sizeof(AkazeCand), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+  }
+  std::vector<int> keep;
+  ak_suppress(lv, d.h_cand, keep);
+  int n = 0;
+  static_assert(sizeof(spvo_akaze_keypoint) == 28 && sizeof(AkazeCand) == 40, "record layout");
+  for (int i : keep) {
+    if (!d.h_cand[i].ok) continue;
+    if (n < cap) std::memcpy(&kp[n], &d.h_cand[i], sizeof(spvo_akaze_keypoint));   // (the candidate's first seven fields are the record)
+    ++n;
+  }
+  *n_out = n;
+  return SPVO_OK;
+}
+
+int spvo_akaze_debug_level(spvo_ctx *c, int level, int what, float *out, int *rows, int *cols) {
+  if (!c || !rows || !cols || level < 0 || what < 0 || what > 3) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  auto &d = c->akaze;
+  if (!d.valid || d.image_gen != c->cls.image_gen || c->cls.rows != d.rows || c->cls.cols != d.cols) return fail(c, SPVO_ERR_STATE, "spvo_akaze_debug_level: no spvo_akaze_detect result is resident");
+  if (level >= d.lv.n) return fail(c, SPVO_ERR_INVALID, "spvo_akaze_debug_level: the scale space of this image has %d levels", d.lv.n);
+  if (int rc = require_idle(c)) return rc;
+  const AkazeLevel &L = d.lv.l[level];
+  *rows = L.h; *cols = L.w;
+  if (!out) return SPVO_OK;
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  const float *src = what == 0 ? L.Lt : what == 1 ? L.Lsmooth : what == 2 ? L.Lflow : L.Ldet;
+  HIP_TRY(c, hipMemcpyAsync(out, src, (size_t)L.h * L.w * sizeof(float), hipMemcpyDeviceToHost, c->stream2));
+  HIP_TRY(c, hipStreamSynchronize(c->stream2));
+  return SPVO_OK;
+}
+
+int spvo_akaze_last_contrast(spvo_ctx *c, float *k, int *octaves) {
+  if (!c || !k || !octaves) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  auto &d = c->akaze;
+  if (!d.valid || d.image_gen != c->cls.image_gen || c->cls.rows != d.rows || c->cls.cols != d.cols) return fail(c, SPVO_ERR_STATE, "spvo_akaze_last_contrast: no spvo_akaze_detect result is resident");
+  *octaves = d.octaves;
+  for (int o = 0; o < AKAZE_MAX_OCTAVES; ++o) k[o] = o < d.octaves ? d.k[o] : 0.f;
+  return SPVO_OK;
+}
+
+int spvo_akaze_tables(int rows, int cols, int *levels, int32_t *octave, float *esigma, int32_t *sigma_size, int32_t *nsteps, float *tau, int tau_cap, int *n_tau, float *g0, float *g1) {
+  if (rows < 16 || cols < 16 || !levels || !n_tau || tau_cap < 0) return SPVO_ERR_INVALID;
+  const AkTables T = make_tables(rows, cols);
+  *levels = T.n;
+  *n_tau = (int)T.tau.size();
+  for (int i = 0; i < T.n; ++i) {
+    if (octave) octave[i] = T.octave[i];
+    if (esigma) esigma[i] = T.esigma[i];
+    if (sigma_size) sigma_size[i] = T.sigma_size[i];
+    if (nsteps && i > 0) nsteps[i - 1] = T.nsteps[i];
+  }
+  if (tau) std::memcpy(tau, T.tau.data(), std::min<size_t>(T.tau.size(), (size_t)tau_cap) * sizeof(float));
+  if (g0) std::memcpy(g0, T.g0.g, (size_t)(T.g0.r + 1) * sizeof(float));
+  if (g1) std::memcpy(g1, T.g1.g, (size_t)(T.g1.r + 1) * sizeof(float));
+  return SPVO_OK;
+}
+
+}  // extern "C"

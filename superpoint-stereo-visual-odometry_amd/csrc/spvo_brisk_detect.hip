@@ -6,12 +6,9 @@
 #include "spvo_internal.hip.h"
 #include "brisk_detect.hip.h"
 
-namespace {
-constexpr int BD_COUNTER_INTS = 4;   // 1 candidates, 2 keypoints, 3 overflow
-
 // brisk_detect_ref.py choice 3: the taps of one axis; false if a run is longer than BRISK_DET_TAPS or not contiguous (cannot happen for the
-// two ratios of the scale space, both below 3)
-bool area_tab(int ssize, int dsize, BriskAreaTap *out) {
+// two ratios of the scale space, both below 3).  The AKAZE detector's octaves take the same path (spvo_akaze.hip).
+bool spvo_int::brisk_area_tab(int ssize, int dsize, BriskAreaTap *out) {
   const double scale = (double)ssize / (double)dsize;
   for (int d = 0; d < dsize; ++d) {
     const double fsx1 = (double)d * scale, fsx2 = fsx1 + scale, cell = std::min(scale, (double)ssize - fsx1);
@@ -32,6 +29,9 @@ bool area_tab(int ssize, int dsize, BriskAreaTap *out) {
   }
   return true;
 }
+
+namespace {
+constexpr int BD_COUNTER_INTS = 4;   // 1 candidates, 2 keypoints, 3 overflow
 
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
@@ -70,7 +70,7 @@ int bd_ensure(spvo_ctx *c, int rows, int cols) {
     d.h_tabs.assign(std::max<size_t>(tabs, 1), BriskAreaTap{});
     for (int i = 1; i < BRISK_DET_LAYERS; ++i) {
       const int s = i == 1 ? 0 : i - 2;
-      if (!exact[i] && !(area_tab(w[s], w[i], d.h_tabs.data() + tab_off[i]) && area_tab(h[s], h[i], d.h_tabs.data() + tab_off[i] + w[i])))
+      if (!exact[i] && !(brisk_area_tab(w[s], w[i], d.h_tabs.data() + tab_off[i]) && brisk_area_tab(h[s], h[i], d.h_tabs.data() + tab_off[i] + w[i])))
         return fail(c, SPVO_ERR_STATE, "BRISK detector: the area taps of layer %d (%d x %d from %d x %d) failed their own checks", i, h[i], w[i], h[s], w[s]);
     }
     if (pyr > d.px_cap || score > d.px_cap || tabs > d.tab_cap || cand > d.cand_cap) {

@@ -477,6 +477,7 @@ void spvo_destroy(spvo_ctx *c) {
   sift_release(c);
   brisk_release(c);
   brisk_detect_release(c);
+  akaze_release(c);
   auto &b = c->cls;
   dev_free(b.im, b.score, b.blur, b.src, b.state, b.desc, b.tmp, b.lam, b.xy, b.resp, b.keys, b.rank, b.cand, b.counters, b.kp_xy, b.kps, b.pre_out, b.pre_tab);
   host_free(c->h_match_tmp);

@@ -423,6 +423,29 @@ struct spvo_ctx {
     BriskDetLayers lv{};
     BriskResizeJob jobs[BRISK_DET_LAYERS]{};   // jobs[i]: layer i from its source (i >= 1)
   } brisk_det;
+  // AKAZE detector (akaze.hip.h) on the image resident in `cls`: the four planes of every level (what spvo_akaze_debug_level serves until the
+  // next call), three scratch planes of the image's size (the scaled first derivatives; the second buffer of the diffusion steps), the
+  // area taps of the octaves that are no exact halves, the candidate lists -- sized from the image, grown on demand -- and the tables
+  struct AkazeBufs {
+    int rows = 0, cols = 0;               // shape the layout and the tables belong to (0: none)
+    bool valid = false;                   // the planes of a completed spvo_akaze_detect are on the device ...
+    unsigned image_gen = 0;               // ... and belong to the image spvo_ctx::cls held at this generation
+    size_t plane_cap = 0, scratch_cap = 0, tab_cap = 0;   // floats of planes / scratch; entries of tabs
+    int cand_cap = 0;
+    float *planes = nullptr, *scratch = nullptr;
+    BriskAreaTap *tabs = nullptr;
+    std::vector<BriskAreaTap> h_tabs;
+    const BriskAreaTap *xtab[AKAZE_MAX_OCTAVES] = {nullptr}, *ytab[AKAZE_MAX_OCTAVES] = {nullptr};   // of octave o from o - 1 (NULL: the exact half)
+    unsigned long long *keys = nullptr;
+    int *rank = nullptr, *stat = nullptr;   // stat: AKAZE_STAT_* (spvo_types.hip.h)
+    AkazeCand *rec = nullptr;
+    std::vector<AkazeCand> h_cand;
+    AkazeLevels lv{};
+    int octaves = 0, nsteps[AKAZE_MAX_LEVELS] = {0};   // nsteps[i]: diffusion steps of the transition i - 1 -> i
+    std::vector<float> h_tau;                          // their sizes, transition after transition
+    AkazeTaps g0{}, g1{};                              // sigma 1.6 and sigma 1
+    float k[AKAZE_MAX_OCTAVES] = {0};                  // the last call's contrast factor per octave
+  } akaze;
   // SIFT detector + descriptor of the classic front end (sift.hip.h): the image, its pyramid (all Gaussian and DoG levels: what
   // spvo_sift_debug_level serves until the next call), the candidate and output lists; device buffers grow on demand, the host staging keeps its capacity
   struct SiftBufs {
@@ -675,6 +698,11 @@ void brisk_release(spvo_ctx *c);     // frees spvo_ctx::brisk (spvo_destroy)
 int brisk_check_image(spvo_ctx *c, const char *who, int rows, int cols);
 // ---- spvo_brisk_detect.hip
 void brisk_detect_release(spvo_ctx *c);   // frees spvo_ctx::brisk_det (spvo_destroy)
+// brisk_detect_ref.py choice 3: the taps of one axis of cv::resize(INTER_AREA)'s general path; false if a run is longer than BRISK_DET_TAPS
+// or not contiguous (cannot happen for ratios below 3)
+bool brisk_area_tab(int ssize, int dsize, BriskAreaTap *out);
+// ---- spvo_akaze.hip
+void akaze_release(spvo_ctx *c);   // frees spvo_ctx::akaze (spvo_destroy)
 // The extractor as a link of spvo_classic_detect's chain (kinds SPVO_CLASSIC_*_BRISK).  brisk_chain_ensure: the tables, the integral image
 // of a rows x cols image and the keypoint buffers for `cap` rows.  brisk_chain_enqueue, on the solver's stream behind a detector that left
 // its list in spvo_ctx::cls (xy, resp, counters[2]): integral image, border rule of keypoints of ONE `size` as a compaction that keeps at

@@ -527,27 +527,33 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
 // spvo_sift_detect_pair) and is matched in its slots -- the BRISK pairs by the 64-byte instantiation of the slot matcher.  BRISK + BRISK
 // goes through spvo_brisk_detect (cv::BRISK::create()->detect, classic.cpp:9-11) and spvo_brisk_describe with the detector's x, y and size,
 // per image: with setDeviceResident alone it takes the per-image path and residentPairs() stays 0; with setBriskPairResident as well it is
-// one spvo_brisk_detect_pair per stereo pair into the same binary slots (64-byte rows), matched there.  AKAZE is an OpenCV features2d call and
-// stays unavailable, and so does every other mix (BRISK keypoints with an ORB descriptor -- spvo_orb_describe refuses fractional
-// coordinates --, SIFT keypoints with an ORB descriptor, ...).
+// one spvo_brisk_detect_pair per stereo pair into the same binary slots (64-byte rows), matched there.  AKAZE + BRISK
+// goes through spvo_akaze_detect (cv::AKAZE::create()->detect, classic.cpp:26-28) and spvo_brisk_describe with the detector's x, y and size,
+// per image only: with setDeviceResident it takes the per-image path and residentPairs() stays 0.  The AKAZE (MLDB) descriptor is an OpenCV
+// features2d call and stays unavailable, and so does every other mix (BRISK or AKAZE keypoints with an ORB descriptor -- spvo_orb_describe
+// refuses fractional coordinates --, SIFT keypoints with an ORB descriptor, ...).
 bool ClassicFeatureFrontEnd::available() { return true; }
 static bool classic_detector_runs(DetectorType d) { return d == DetectorType::ORB || d == DetectorType::ShiTomasi || d == DetectorType::FAST; }
 static bool classic_sift_pair(DetectorType d, DescriptorType e) { return d == DetectorType::SIFT && e == DescriptorType::SIFT; }
-// BRISK is an extractor for given keypoints here (spvo_brisk_describe): it goes with the two detectors that hand keypoints over
-static bool classic_brisk_pair(DetectorType d, DescriptorType e) { return (d == DetectorType::ShiTomasi || d == DetectorType::FAST) && e == DescriptorType::BRISK; }
+// BRISK is an extractor for given keypoints here (spvo_brisk_describe): it goes with the three detectors that hand keypoints over (AKAZE's
+// carry a size of their own, as the reference lets any detector feed any extractor)
+static bool classic_brisk_pair(DetectorType d, DescriptorType e) {
+  return (d == DetectorType::ShiTomasi || d == DetectorType::FAST || d == DetectorType::AKAZE) && e == DescriptorType::BRISK;
+}
 // ... and with its own detector (spvo_brisk_detect), whose keypoints carry the sizes the pattern was designed for
 static bool classic_brisk_brisk(DetectorType d, DescriptorType e) { return d == DetectorType::BRISK && e == DescriptorType::BRISK; }
 static bool classic_pair_runs(DetectorType d, DescriptorType e) {
   return classic_sift_pair(d, e) || (classic_detector_runs(d) && e == DescriptorType::ORB) || classic_brisk_pair(d, e) || classic_brisk_brisk(d, e);
 }
 void ClassicFeatureFrontEnd::initDetector() {
-  if (!classic_detector_runs(detector_type_) && !classic_sift_pair(detector_type_, descriptor_type_) && !classic_brisk_brisk(detector_type_, descriptor_type_))
-    logError("[initDetector] only ORB, ShiTomasi, FAST, SIFT (with SIFT descriptors) and BRISK (with BRISK descriptors) run without OpenCV (build with SPVO_USE_OPENCV for the other detectors of classic.cpp:7-56)");
+  if (!classic_detector_runs(detector_type_) && !classic_sift_pair(detector_type_, descriptor_type_) && !classic_brisk_brisk(detector_type_, descriptor_type_) &&
+      !(detector_type_ == DetectorType::AKAZE && classic_brisk_pair(detector_type_, descriptor_type_)))
+    logError("[initDetector] only ORB, ShiTomasi, FAST, SIFT (with SIFT descriptors), BRISK and AKAZE (with BRISK descriptors) run without OpenCV (build with SPVO_USE_OPENCV for the other detectors of classic.cpp:7-56)");
 }
 void ClassicFeatureFrontEnd::initDescriptor() {
   if (descriptor_type_ != DescriptorType::ORB && !classic_sift_pair(detector_type_, descriptor_type_) && !classic_brisk_pair(detector_type_, descriptor_type_) &&
       !classic_brisk_brisk(detector_type_, descriptor_type_))
-    logError("[initDescriptor] only ORB, BRISK on ShiTomasi / FAST / BRISK keypoints, and SIFT on SIFT keypoints, run without OpenCV (build with SPVO_USE_OPENCV for the other descriptors of classic.cpp:58-79)");
+    logError("[initDescriptor] only ORB, BRISK on ShiTomasi / FAST / BRISK / AKAZE keypoints, and SIFT on SIFT keypoints, run without OpenCV (build with SPVO_USE_OPENCV for the other descriptors of classic.cpp:58-79, the AKAZE (MLDB) descriptor among them)");
 }
 
 std::vector<cv::KeyPoint> ClassicFeatureFrontEnd::detectKeypoints(const cv::Mat &img) {
@@ -555,7 +561,7 @@ std::vector<cv::KeyPoint> ClassicFeatureFrontEnd::detectKeypoints(const cv::Mat 
   orb_desc_ = cv::Mat();
   detected_data_ = nullptr;
   if (!classic_pair_runs(detector_type_, descriptor_type_)) {
-    logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB, ShiTomasi and FAST with ORB descriptors, ShiTomasi, FAST and BRISK with BRISK descriptors and SIFT with SIFT descriptors run");
+    logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB, ShiTomasi and FAST with ORB descriptors, ShiTomasi, FAST, BRISK and AKAZE with BRISK descriptors and SIFT with SIFT descriptors run");
     return keypoints;
   }
   if (!ensureContext()) return keypoints;
@@ -609,6 +615,32 @@ std::vector<cv::KeyPoint> ClassicFeatureFrontEnd::detectKeypoints(const cv::Mat 
       k.angle = kp[i].angle;   // -1
       k.response = kp[i].response;
       k.octave = kp[i].octave;   // the layer, 0 .. 5
+      keypoints.push_back(k);
+    }
+    detected_data_ = img.data; detected_rows_ = img.rows; detected_cols_ = img.cols;
+    return keypoints;
+  }
+  if (detector_type_ == DetectorType::AKAZE) {
+    // cv::AKAZE::create(): threshold 0.001 (classic.cpp:26-28); the image stays on the device for describeKeypoints.  A second pass of the
+    // loop runs the whole chain again, so the first buffer is generous: the 375 x 1242 sample gives 1442 keypoints
+    int cap = 16384, n = 0;
+    std::vector<spvo_akaze_keypoint> kp;
+    for (;;) {
+      kp.resize((size_t)cap);
+      if (spvo_akaze_detect(ctx_, img.ptr<uint8_t>(0), img.rows, img.cols, (size_t)img.step, 0.001f, kp.data(), cap, &n) != SPVO_OK) {
+        logError(std::string("spvo_akaze_detect: ") + spvo_last_error(ctx_));
+        return keypoints;
+      }
+      if (n <= cap) break;
+      cap = n;   // more than the buffer held: once more with room for all
+    }
+    keypoints.reserve(n);
+    for (int i = 0; i < n; ++i) {
+      cv::KeyPoint k(cv::Point2f(kp[i].x, kp[i].y), kp[i].size);
+      k.angle = kp[i].angle;   // 0: the orientation belongs to the descriptor stage
+      k.response = kp[i].response;
+      k.octave = kp[i].octave;
+      k.class_id = kp[i].class_id;   // the level, 0 .. 15
       keypoints.push_back(k);
     }
     detected_data_ = img.data; detected_rows_ = img.rows; detected_cols_ = img.cols;
@@ -700,7 +732,7 @@ cv::Mat ClassicFeatureFrontEnd::describeKeypoints(std::vector<cv::KeyPoint> &key
   }
   if (classic_brisk_pair(detector_type_, descriptor_type_) || classic_brisk_brisk(detector_type_, descriptor_type_)) {
     // cv::BRISK::create(30, 3, 1.0f)->compute(img, keypoints, descriptors), classic.cpp:56-65: every keypoint's own size (5: ShiTomasi, 7: FAST,
-    // 12 x its scale: BRISK) picks its scale; the erase-and-angle handling is the ORB branch's (BRISK reports degrees, 0 .. 360), except that
+    // 12 x its scale: BRISK, 3 x esigma: AKAZE) picks its scale; the erase-and-angle handling is the ORB branch's (BRISK reports degrees, 0 .. 360), except that
     // a BRISK keypoint keeps the angle its detector reports (-1)
     const bool keep_angle = detector_type_ == DetectorType::BRISK;
     if (!ensureContext()) return cv::Mat();
@@ -746,7 +778,7 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
     return;
   }
   if (!classic_pair_runs(detector_type_, descriptor_type_)) {
-    logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB, ShiTomasi and FAST with ORB descriptors, ShiTomasi, FAST and BRISK with BRISK descriptors and SIFT with SIFT descriptors run");
+    logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB, ShiTomasi and FAST with ORB descriptors, ShiTomasi, FAST, BRISK and AKAZE with BRISK descriptors and SIFT with SIFT descriptors run");
     return;
   }
   if (!ensureContext()) return;   // no device: logged, nothing pushed (nn.cpp:53-55 convention)
@@ -780,6 +812,7 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
 // pushed and the caller takes the per-image path (the pair does not fit its slots, or the call failed and the per-image path reports why).
 bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &img_l, cv::Mat &img_r) {
   if (img_l.depth() != CV_8U || img_l.rows <= 0 || img_r.depth() != CV_8U || (size_t)img_l.step != (size_t)img_r.step) return false;
+  if (detector_type_ == DetectorType::AKAZE) return false;   // no pair call yet: the per-image path, residentPairs() stays 0
   if (classic_brisk_brisk(detector_type_, descriptor_type_)) {
     if (!brisk_pair_resident_) return false;   // opt-in (setBriskPairResident): the per-image path, residentPairs() stays 0
     if (resident_pairs_ == 0) spvo_set_prematch(ctx_, 1, selector_type_ == SelectorType::KNN ? SPVO_SELECT_KNN : SPVO_SELECT_NN, matcher_cross_check_ ? 1 : 0, knn_threshold_);

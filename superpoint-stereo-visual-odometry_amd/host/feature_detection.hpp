@@ -96,6 +96,7 @@ struct KeyPoint {
   float angle = -1;      // degrees, as in OpenCV; -1 = not applicable
   float response = 0;
   int octave = 0;
+  int class_id = -1;     // AKAZE: the level of the scale space
   KeyPoint() = default;
   KeyPoint(Point2f p, float s) : pt(p), size(s) {}
 };

@@ -402,7 +402,7 @@ int spvo_host_classic_sequence_trace(const char *detector_name, int n, const uin
                               input_width, digest);
 }
 
-// ... with the descriptor named as well ("ORB", "BRISK", "SIFT"; -1000001: no such descriptor)
+// ... with the descriptor named as well ("ORB", "BRISK", "SIFT"; -1000001: no such descriptor): "BRISK" goes with ShiTomasi, FAST, BRISK and AKAZE keypoints
 int spvo_host_classic_sequence_desc(const char *detector_name, const char *descriptor_name, int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols,
                                     const double *P_l, const double *P_r, int knn, int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses,
                                     int *stats, double *seconds, int input_height, int input_width, uint64_t *digest) {

@@ -79,6 +79,7 @@ class SolveOutput(C.Structure):
 
 SIFT_KP_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("size", np.float32), ("angle", np.float32), ("response", np.float32), ("octave", np.int32)])   # spvo_sift_keypoint
 BRISK_KP_DTYPE = SIFT_KP_DTYPE   # spvo_brisk_keypoint: octave is the layer 0..5, angle is -1
+AKAZE_KP_DTYPE = np.dtype(SIFT_KP_DTYPE.descr + [("class_id", np.int32)])   # spvo_akaze_keypoint: class_id is the level 0..15, angle is 0
 OBS_DTYPE = np.dtype([("X", np.float32, 3), ("uv", np.float32, 2), ("cam", np.int32), ("inverse", np.int32)])
 
 # every symbol include/spvo.h declares
@@ -86,7 +87,7 @@ SYMBOLS = [
     "spvo_default_config", "spvo_create", "spvo_destroy", "spvo_last_error", "spvo_load_weights", "spvo_engine_precision", "spvo_set_fp32_split",
     "spvo_preprocess", "spvo_forward", "spvo_debug_tensor", "spvo_heatmap", "spvo_nms",
     "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8",
-    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_detect_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
+    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_detect_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
     "spvo_profile_enable", "spvo_profile_reset", "spvo_profile_only", "spvo_profile_count", "spvo_profile_get", "spvo_profile_stage_kernel",
     "spvo_set_tuning", "spvo_get_tuning", "spvo_clear_tuning",
     "spvo_comm_unique_id", "spvo_comm_available", "spvo_comm_create", "spvo_comm_create_host", "spvo_comm_rank", "spvo_comm_world", "spvo_comm_destroy",
@@ -148,6 +149,10 @@ def load() -> C.CDLL:
     lib.spvo_brisk_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, vp, C.c_int, ip]
     lib.spvo_brisk_detect_debug_layer.argtypes = [vp, C.c_int, C.c_int, vp, ip, ip]
     lib.spvo_brisk_detect_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(BriskFeatures), C.POINTER(BriskFeatures)]
+    lib.spvo_akaze_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_float, vp, C.c_int, ip]
+    lib.spvo_akaze_debug_level.argtypes = [vp, C.c_int, C.c_int, vp, ip, ip]
+    lib.spvo_akaze_last_contrast.argtypes = [vp, vp, ip]
+    lib.spvo_akaze_tables.argtypes = [C.c_int, C.c_int, ip, vp, vp, vp, vp, vp, C.c_int, ip, vp, vp]
     lib.spvo_sift_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, C.c_int, ip]
     lib.spvo_sift_debug_level.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, ip, ip]
     lib.spvo_sift_detect_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(SiftFeatures), C.POINTER(SiftFeatures)]
@@ -527,6 +532,36 @@ class Context:
         out = np.zeros((rows.value, cols.value), np.uint8)
         self._check(self.lib.spvo_brisk_detect_debug_layer(self.h, layer, what, _ptr(out), C.byref(rows), C.byref(cols)))
         return out
+
+    def akaze_detect(self, img: np.ndarray, threshold: float = 0.001, cap: Optional[int] = None):
+        """AKAZE keypoints of one u8 image (spvo_akaze_detect): dict of kp [m] (AKAZE_KP_DTYPE records: x, y, size, angle = 0, response,
+        octave, class_id = level) in the order the suppression leaves them, and n, the number found; m = min(n, cap).  cap = None: all of
+        them (a second call when the first buffer was too small).  The image stays on the device for a brisk_describe(None, ...,
+        shape=img.shape) that follows."""
+        img = _u8_rows(img)
+        want = 4096 if cap is None else int(cap)
+        while True:
+            kp = np.zeros(max(want, 1), AKAZE_KP_DTYPE)
+            n = C.c_int(0)
+            self._check(self.lib.spvo_akaze_detect(self.h, _ptr(img), img.shape[0], img.shape[1], img.strides[0], float(threshold), _ptr(kp), want, C.byref(n)))
+            if cap is not None or n.value <= want:
+                self._resident_shape = img.shape
+                return dict(kp=kp[:min(n.value, want)].copy(), n=n.value)
+            want = n.value
+
+    def akaze_level(self, level: int, what: int = 0) -> np.ndarray:
+        """A level of the last akaze_detect()'s scale space (spvo_akaze_debug_level): what = 0 Lt, 1 Lsmooth, 2 Lflow, 3 Ldet."""
+        rows, cols = C.c_int(0), C.c_int(0)
+        self._check(self.lib.spvo_akaze_debug_level(self.h, level, what, None, C.byref(rows), C.byref(cols)))
+        out = np.zeros((rows.value, cols.value), np.float32)
+        self._check(self.lib.spvo_akaze_debug_level(self.h, level, what, _ptr(out), C.byref(rows), C.byref(cols)))
+        return out
+
+    def akaze_last_contrast(self) -> np.ndarray:
+        """The contrast factor of every octave of the last akaze_detect() (spvo_akaze_last_contrast)."""
+        k, n = np.zeros(4, np.float32), C.c_int(0)
+        self._check(self.lib.spvo_akaze_last_contrast(self.h, _ptr(k), C.byref(n)))
+        return k[:n.value].copy()
 
     def brisk_detect_pair(self, img_l, img_r, slot_l: int, slot_r: int, threshold: int = 30, octaves: int = 3, slot_capacity: int = 8192, cap: Optional[int] = None):
         """One stereo pair through the BRISK detector + extractor into two binary feature slots of 64-byte rows (spvo_brisk_detect_pair).
@@ -961,6 +996,20 @@ def obs_array(X, uv, cam, inverse) -> np.ndarray:
         a["cam"] = np.asarray(cam, np.int32)
         a["inverse"] = np.asarray(inverse, np.int32)
     return a
+
+
+def akaze_tables(rows: int, cols: int):
+    """The AKAZE detector's tables for a rows x cols image (spvo_akaze_tables; no context, no device), in the layout of
+    tests/akaze_ref.py's make_tables: octave, esigma, sigma_size per level, nsteps per transition, tau (all step sizes), g0, g1."""
+    lib = load()
+    octave, esigma, sigma_size, nsteps = np.zeros(16, np.int32), np.zeros(16, np.float32), np.zeros(16, np.int32), np.zeros(15, np.int32)
+    tau, g0, g1 = np.zeros(1024, np.float32), np.zeros(5, np.float32), np.zeros(3, np.float32)
+    levels, n_tau = C.c_int(0), C.c_int(0)
+    rc = lib.spvo_akaze_tables(int(rows), int(cols), C.byref(levels), _ptr(octave), _ptr(esigma), _ptr(sigma_size), _ptr(nsteps), _ptr(tau), len(tau), C.byref(n_tau), _ptr(g0), _ptr(g1))
+    if rc or n_tau.value > len(tau):
+        raise SpvoError(rc or -1, "spvo_akaze_tables failed")
+    n = levels.value
+    return dict(octave=octave[:n].copy(), esigma=esigma[:n].copy(), sigma_size=sigma_size[:n].copy(), nsteps=nsteps[:max(n - 1, 0)].copy(), tau=tau[:n_tau.value].copy(), g0=g0, g1=g1)
 
 
 def brisk_tables(scales=range(64)):

@@ -344,12 +344,13 @@ class FrontEnd:
 def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_threshold=2.0, refinement_degree=4, warm=0, detector="ORB", input_size=None, resident=False,
                      resident_capacity=0, trace=False, descriptor="ORB", brisk_resident=False):
     """stereoCallback replayed on ClassicFeatureFrontEnd(detector, descriptor, BF, ...) (node.cpp:353-360) over host image pairs -- detector
-    "ORB", "ShiTomasi" or "FAST" with descriptor "ORB", "ShiTomasi", "FAST" or "BRISK" with descriptor "BRISK" (64-byte rows; detector "BRISK" with
-    the default descriptor "ORB" does not run), or detector "SIFT" (SIFT descriptors whatever `descriptor` says, as before); input_size None: at their native resolution, (height, width): through preprocessImageImpl first
+    "ORB", "ShiTomasi" or "FAST" with descriptor "ORB", "ShiTomasi", "FAST", "BRISK" or "AKAZE" with descriptor "BRISK" (64-byte rows; detector "BRISK"
+    or "AKAZE" with the default descriptor "ORB" does not run, nor does descriptor "AKAZE": the MLDB descriptor is not built), or detector "SIFT" (SIFT descriptors whatever `descriptor` says, as before); input_size None: at their native resolution, (height, width): through preprocessImageImpl first
     (classic.cpp:96-100).  Returns (poses [n, 7] = q xyzw + t of cam0_curr_T_cam0_prev, stats [n, 4] = keypoints L, R, stereo
     matches, PnP inliers, seconds spent on frames warm .. n-1).
     resident: ClassicFeatureFrontEnd::setDeviceResident for this run -- one spvo_classic_detect (SIFT: spvo_sift_detect_pair) per pair, features
-    and matching stay on the device, for every pair named above with BRISK descriptors on ShiTomasi / FAST keypoints included; "BRISK" + "BRISK"
+    and matching stay on the device, for every pair named above with BRISK descriptors on ShiTomasi / FAST keypoints included; "AKAZE" + "BRISK" always takes
+    the per-image path and classic_resident_pairs() stays 0; "BRISK" + "BRISK"
     takes the per-image path and classic_resident_pairs() stays 0 unless brisk_resident (ClassicFeatureFrontEnd::setBriskPairResident) is set
     as well: then it is one spvo_brisk_detect_pair per pair into the same binary slots (resident_capacity > 0: rows per slot; a pair that does not
     fit falls back to the per-image path; classic_resident_pairs() tells how many pairs of the run stayed resident).

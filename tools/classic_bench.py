@@ -1,8 +1,8 @@
 """The classic front end on the GPU.
 
-python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK] [--descriptor ORB|BRISK] [--resident] [--brisk-resident]
+python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK|AKAZE] [--descriptor ORB|BRISK] [--resident] [--brisk-resident]
     ClassicFeatureFrontEnd(detector, descriptor, BF, KNN) over the synthetic stream: frames/s of the synchronous stereoCallback
-    (--descriptor BRISK: with --detector ShiTomasi, FAST or BRISK; --detector BRISK: with --descriptor BRISK only);
+    (--descriptor BRISK: with --detector ShiTomasi, FAST, BRISK or AKAZE; --detector BRISK or AKAZE: with --descriptor BRISK only);
     --resident: with ClassicFeatureFrontEnd::setDeviceResident (one spvo_classic_detect per pair, matching on the binary slots);
     --brisk-resident: with setBriskPairResident as well (BRISK + BRISK through one spvo_brisk_detect_pair per pair; needs --resident).
 python tools/classic_bench.py [frames] --detector ShiTomasi|FAST|ORB --descriptor ORB|BRISK --ab ROUNDS
@@ -24,6 +24,11 @@ python tools/classic_bench.py --leg brisk_detect [--calls 50]
     spvo_brisk_detect (threshold 30) alone per image at 1241 x 376, for rocprofv3 --kernel-trace --stats as above: brisk_area_kernel /
     brisk_half_kernel / brisk_score916_kernel / brisk_score58_kernel / brisk_collect_kernel / cls_rank_kernel / brisk_refine_kernel /
     brisk_det_compact_kernel is the split.
+python tools/classic_bench.py --leg akaze_detect [--calls 50] [--yardstick]
+    spvo_akaze_detect (threshold 0.001) alone per image at 1241 x 376, for rocprofv3 --kernel-trace --stats as above: akaze_blur_kernel /
+    akaze_half_kernel or akaze_area_kernel / akaze_gradmax_kernel / akaze_hist_kernel / akaze_contrast_finish_kernel / akaze_flow_kernel /
+    akaze_fed_kernel / akaze_deriv_kernel / akaze_det_kernel / akaze_extrema_kernel / cls_rank_kernel / akaze_refine_kernel is the split.
+    Prints the launches of one call (from spvo_akaze_tables); --yardstick: spvo_sift_detect afterwards in the same run.
 python tools/classic_bench.py --leg brisk_pair [--calls 50]
     spvo_brisk_detect_pair (threshold 30) alone on the 1241 x 376 sample pair, rotating through the slot ring, for rocprofv3 --kernel-trace
     --stats as above: the detector's kernels up to brisk_refine_kernel, then brisk_integral_*_kernel / brisk_pair_compact_kernel /
@@ -50,9 +55,10 @@ ap.add_argument("--detectors", action="store_true")
 ap.add_argument("--resident", action="store_true")
 ap.add_argument("--brisk-resident", action="store_true")
 ap.add_argument("--ab", type=int, default=0)
-ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "brisk_detect", "brisk_pair", "orb_describe", "match", "match_slots"])
+ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "brisk_detect", "akaze_detect", "brisk_pair", "orb_describe", "match", "match_slots"])
 ap.add_argument("--selector", default="KNN", choices=["NN", "KNN"])
 ap.add_argument("--cross", action="store_true")
+ap.add_argument("--yardstick", action="store_true")
 ap.add_argument("--calls", type=int, default=200)
 ap.add_argument("--warmup", type=int, default=20)
 args = ap.parse_args()
@@ -92,6 +98,18 @@ if args.detectors or args.leg:
     def leg_brisk_detect():
         return ctx.brisk_detect(img, 30)["n"]
 
+    def leg_akaze_detect():
+        return ctx.akaze_detect(img)["n"]
+
+    if args.leg == "akaze_detect":
+        T = capi.akaze_tables(*img.shape)
+        new_octaves = int((np.diff(T["octave"]) > 0).sum())
+        # level 0 and the contrast factor: memset + 5; per transition blur + flow + its steps (+ the half-sampling); per level 2; extrema per
+        # octave with room inside the 29-pixel border, rank, refine
+        roomy = sum(1 for o in range(int(T["octave"].max()) + 1) if int(img.shape[0] / 2 ** o) > 58 and int(img.shape[1] / 2 ** o) > 58)
+        print("spvo_akaze_detect %d x %d: %d levels, %d diffusion steps, %d kernel launches and 1 memset per call" % (
+            img.shape[1], img.shape[0], len(T["octave"]), len(T["tau"]), 5 + 2 * (len(T["octave"]) - 1) + len(T["tau"]) + new_octaves + 2 * len(T["octave"]) + roomy + 2))
+
     pair_calls = [0]
 
     def leg_brisk_pair():
@@ -123,9 +141,9 @@ if args.detectors or args.leg:
                 match_slots=("spvo_match_hamming_slots, %d x %d rows" % (len(fl["xy"]) if leg_match else 0, len(fr["xy"]) if leg_match else 0), leg_match_slots),
                 brisk=("spvo_brisk_describe, %d FAST keypoints" % (len(kp) if args.leg == "brisk" else 0), leg_brisk),
                 orb_describe=("spvo_orb_describe, %d FAST keypoints" % (len(kp) if args.leg == "orb_describe" else 0), leg_orb_describe),
-                brisk_detect=("spvo_brisk_detect", leg_brisk_detect), brisk_pair=("spvo_brisk_detect_pair (both images)", leg_brisk_pair),
+                brisk_detect=("spvo_brisk_detect", leg_brisk_detect), akaze_detect=("spvo_akaze_detect", leg_akaze_detect), brisk_pair=("spvo_brisk_detect_pair (both images)", leg_brisk_pair),
                 orb=("spvo_orb_detect", leg_orb), sift=("spvo_sift_detect", leg_sift), gftt=("spvo_gftt_detect + spvo_orb_describe", leg_gftt), fast=("spvo_fast_detect + spvo_orb_describe", leg_fast))
-    for key in ([args.leg] if args.leg else ["orb", "gftt", "fast"]):
+    for key in ([args.leg] + (["sift"] if args.yardstick else []) if args.leg else ["orb", "gftt", "fast"]):
         name, fn = legs[key]
         for _ in range(args.warmup):
             n = fn()
