@@ -353,13 +353,14 @@ int spvo_brisk_detect_debug_layer(spvo_ctx *ctx, int layer, int what, uint8_t *o
  * conductivity of its own sigma 1 blur), the scale-normalised Hessian determinant of every level, the candidates (above the threshold,
  * strict 8-neighbour maxima, inside the descriptor border of their level) and their sub-pixel offsets on the device; the order-dependent
  * suppression between candidates of the same and of neighbouring levels on the host, over the copied list.  Only the detector: the
- * orientation and the MLDB descriptor are not built (OpenCV computes both in compute), so `angle` is 0 as detect leaves it.  OpenCV is not
+ * orientation and the MLDB descriptor are spvo_akaze_describe's (OpenCV computes both in compute), so `angle` is 0 as detect leaves it.  OpenCV is not
  * available to this build: the algorithm is OpenCV's as far as it is known, as restated by tests/akaze_ref.py (its header lists every rule
  * and marks what is a decision of this project; it mixes OpenCV generations on purpose: 4.x's sigma_size^4 factor on the determinant, 3.x's
  * reflect-101 blur border and sequential suppression), and the kernels reproduce that restatement bit for bit in every plane and in every field
  * of a record: x, y, size = 2 * 1.5 * esigma, angle = 0, response = Ldet, octave, class_id = level 0 .. 15.  Keypoints come in the order
  * the suppression leaves them.  `n` receives their number, of which min(n, cap) are written; strided input is accepted.  The image stays on
- * the device for a spvo_brisk_describe(img = NULL) that follows, exactly as after spvo_fast_detect and spvo_brisk_detect.
+ * the device for a spvo_brisk_describe(img = NULL) that follows, exactly as after spvo_fast_detect and spvo_brisk_detect, and the scale
+ * space for a spvo_akaze_describe(img = NULL).
  *   SPVO_ERR_INVALID   a threshold that is not finite and positive; an image smaller than 16 x 16; rows * cols * 255 >= 2^31 (so that the
  *                      spvo_brisk_describe that follows cannot fail on its int32 integral image)
  *   SPVO_ERR_STATE     a spvo_detect*_submit is in flight; the candidate list overflowed (it is sized from the image, so this reports a
@@ -370,7 +371,8 @@ int spvo_akaze_detect(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, siz
 /* A level of the scale space of this context's last spvo_akaze_detect (test hook): what = 0 Lt, 1 Lsmooth, 2 Lflow (zeros on level 0, which
  * has none), 3 Ldet.  `out` (rows x cols floats) may be NULL to ask for the shape only.  SPVO_ERR_INVALID for a level the image does not
  * have; SPVO_ERR_STATE when no result is resident: no call yet, or any other call has since put an image into the context's resident
- * image buffer, the same image included. */
+ * image buffer, the same image included, or a spvo_sift_detect / spvo_sift_detect_pair has run since (SIFT keeps an image of its own,
+ * but the last detector call owns what is resident). */
 int spvo_akaze_debug_level(spvo_ctx *ctx, int level, int what, float *out, int *rows, int *cols);
 /* The contrast factor k of every octave of the last spvo_akaze_detect, as the kernels left it in device memory.  SPVO_ERR_STATE as above. */
 int spvo_akaze_last_contrast(spvo_ctx *ctx, float *k /* [4], per octave */, int *octaves);
@@ -380,6 +382,28 @@ int spvo_akaze_last_contrast(spvo_ctx *ctx, float *k /* [4], per octave */, int 
  * and sigma 1 (g1, 3 floats).  Every array may be NULL.  SPVO_ERR_INVALID for an image smaller than 16 x 16. */
 int spvo_akaze_tables(int rows, int cols, int *levels, int32_t *octave, float *esigma, int32_t *sigma_size, int32_t *nsteps, float *tau, int tau_cap,
                       int *n_tau, float *g0, float *g1);
+/* describeKeypoints for DescriptorType::AKAZE (cv::AKAZE::create() -> compute, feature_detection_classic.cpp:69-70) on AKAZE keypoints: per
+ * record the main orientation (Compute_Main_Orientation: 109 Gaussian-weighted samples of the level's scaled first derivatives, their angle
+ * by fastAtan32f's polynomial, 42 sliding windows of pi / 3) and the full MLDB descriptor (pattern size 10, 3 channels: the mean of Lt and of
+ * the rotated derivatives over the cells of a 2 x 2, a 3 x 3 and a 4 x 4 grid, every pair of cells compared: 486 bits in
+ * SPVO_AKAZE_DESC_BYTES = 61 bytes, bits 6 and 7 of the last byte zero), one wave per keypoint in one launch.  The level is the record's
+ * class_id, as OpenCV requires.  No keypoint is dropped: `angle` receives n angles in degrees (0 .. 360; the angle that came in is ignored),
+ * `desc` n rows, for spvo_match_hamming with desc_bytes = 61.  OpenCV is not available to this build: the definition is
+ * tests/akaze_mldb_ref.py (its header lists every rule and marks what is a decision of this project -- chiefly that the grid is rotated by
+ * the winning window's normalised direction itself and not by cos / sin of its approximate angle, and that a sample outside the plane
+ * reads zero in the orientation and is skipped in the descriptor), which uses no transcendental function, and the kernel reproduces it
+ * bit for bit in every angle and every byte.
+ *   img == NULL   on the scale space left resident by this context's last spvo_akaze_detect or spvo_akaze_describe(img) of a rows x cols
+ *                 image (spvo_akaze_debug_level's rule of validity)
+ *   img != NULL   the scale space of img is built first, by spvo_akaze_detect's own chain without its extrema, and stays resident
+ * n == 0 is SPVO_OK (with an image, its scale space is still built).
+ *   SPVO_ERR_INVALID   nothing is written, uploaded or replaced: a record whose class_id is no level of a rows x cols image, whose octave is
+ *                      not that level's, whose x, y or size is not finite or whose size is not positive; an image smaller than 16 x 16
+ *   SPVO_ERR_STATE     a spvo_detect*_submit is in flight (outputs and the resident result stay as they were); img == NULL and no scale
+ *                      space of that shape is resident */
+#define SPVO_AKAZE_DESC_BYTES 61
+int spvo_akaze_describe(spvo_ctx *ctx, const uint8_t *img /* or NULL */, int rows, int cols, size_t stride,
+                        const spvo_akaze_keypoint *kp, int n, float *angle /* [n], degrees */, uint8_t *desc /* [n * 61] */);
 
 /* ------------------------------------------------------- classic front end: one submission per stereo pair, features resident
  * detectKeypoints + describeKeypoints of ClassicFeatureFrontEnd for BOTH images of a stereo pair in one call: ORB, or Shi-Tomasi /

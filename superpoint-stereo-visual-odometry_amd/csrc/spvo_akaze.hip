@@ -1,10 +1,12 @@
 // spvo_akaze.hip -- the classic front end's AKAZE keypoint detector (akaze.hip.h): the tables of a shape (levels, FED step sizes, Gaussian
 // taps: built on the host by the formulas tests/akaze_ref.py lists, spvo_akaze_tables), the chain of launches of spvo_akaze_detect, the
-// order-dependent suppression between candidates on the host (rule 11: the restatement's loop over the copied candidate list), and the
-// test hooks.  Runs on the solver's stream (stream2) with the image resident in spvo_ctx::cls -- it stays there for a
-// spvo_brisk_describe(img = NULL) that follows -- and owns everything else it needs (spvo_ctx::akaze).
+// order-dependent suppression between candidates on the host (rule 11: the restatement's loop over the copied candidate list), the
+// test hooks, and spvo_akaze_describe (akaze_mldb.hip.h: orientation and MLDB descriptor on the scale space that chain leaves resident).
+// Runs on the solver's stream (stream2) with the image resident in spvo_ctx::cls -- it stays there for a spvo_brisk_describe(img = NULL)
+// that follows -- and owns everything else it needs (spvo_ctx::akaze).
 #include "spvo_internal.hip.h"
 #include "akaze.hip.h"
+#include "akaze_mldb.hip.h"
 
 namespace {
 constexpr int AK_SUBLEVELS = 4;
@@ -107,7 +109,7 @@ int ak_ensure(spvo_ctx *c, int rows, int cols) {
   for (int i = 0; i < T.n; ++i) {
     const int h = T.oh[T.octave[i]], w = T.ow[T.octave[i]], b = level_border(T.sigma_size[i]);
     off[i] = planes;
-    planes += 4 * align64((size_t)h * w);
+    planes += 6 * align64((size_t)h * w);
     cand += (long long)((std::max(h - 2 * b, 0) + 1) / 2) * ((std::max(w - 2 * b, 0) + 1) / 2);   // strict maxima do not touch, diagonally either
   }
   bool exact[AKAZE_MAX_OCTAVES] = {false};
@@ -119,7 +121,7 @@ int ak_ensure(spvo_ctx *c, int rows, int cols) {
   for (int o = 1; o < T.octaves; ++o)
     if (!exact[o] && !(brisk_area_tab(T.ow[o - 1], T.ow[o], d.h_tabs.data() + tab_off[o]) && brisk_area_tab(T.oh[o - 1], T.oh[o], d.h_tabs.data() + tab_off[o] + T.ow[o])))
       return fail(c, SPVO_ERR_STATE, "AKAZE detector: the area taps of octave %d (%d x %d from %d x %d) failed their own checks", o, T.oh[o], T.ow[o], T.oh[o - 1], T.ow[o - 1]);
-  const size_t scratch = 3 * align64((size_t)rows * cols);
+  const size_t scratch = 2 * align64((size_t)rows * cols);
   if (planes > d.plane_cap || scratch > d.scratch_cap || tabs > d.tab_cap || cand > d.cand_cap) {
     HIP_TRY(c, hipStreamSynchronize(st));
     dev_free(d.planes, d.scratch, d.tabs, d.keys, d.rank, d.rec);
@@ -140,7 +142,7 @@ int ak_ensure(spvo_ctx *c, int rows, int cols) {
     AkazeLevel &L = d.lv.l[i];
     L.h = T.oh[T.octave[i]]; L.w = T.ow[T.octave[i]];
     const size_t px = align64((size_t)L.h * L.w);
-    L.Lt = d.planes + off[i]; L.Lsmooth = L.Lt + px; L.Lflow = L.Lsmooth + px; L.Ldet = L.Lflow + px;
+    L.Lt = d.planes + off[i]; L.Lsmooth = L.Lt + px; L.Lflow = L.Lsmooth + px; L.Ldet = L.Lflow + px; L.Lx = L.Ldet + px; L.Ly = L.Lx + px;
     L.octave = T.octave[i]; L.sigma_size = T.sigma_size[i]; L.border = level_border(T.sigma_size[i]); L.esigma = T.esigma[i];
     d.nsteps[i] = T.nsteps[i];
   }
@@ -194,39 +196,24 @@ void ak_suppress(const AkazeLevels &lv, const std::vector<AkazeCand> &cd, std::v
     if (!repeated) keep.push_back(aux[i].index);
   }
 }
-}  // namespace
-
-void spvo_int::akaze_release(spvo_ctx *c) {
-  auto &d = c->akaze;
-  dev_free(d.planes, d.scratch, d.tabs, d.keys, d.rank, d.rec, d.stat);
-  d.plane_cap = d.scratch_cap = d.tab_cap = 0; d.cand_cap = 0; d.rows = d.cols = 0; d.valid = false;
-}
-
-extern "C" {
-
-int spvo_akaze_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride, float threshold, spvo_akaze_keypoint *kp, int cap, int *n_out) {
-  if (!c || !img || !n_out || rows <= 0 || cols <= 0 || stride < (size_t)cols || cap < 0 || (cap > 0 && !kp)) return fail(c, SPVO_ERR_INVALID, "bad argument");
-  *n_out = 0;
-  if (!std::isfinite(threshold) || !(threshold > 0.f)) return fail(c, SPVO_ERR_INVALID, "spvo_akaze_detect: the threshold must be finite and positive");
-  if (rows < 16 || cols < 16) return fail(c, SPVO_ERR_INVALID, "spvo_akaze_detect: images of at least 16 x 16 only");
-  if (int rc = brisk_check_image(c, "spvo_akaze_detect", rows, cols)) return rc;
-  if (int rc = require_idle(c)) return rc;
-  HIP_TRY(c, hipSetDevice(c->cfg.device));
+// The chain both entry points share: the image into spvo_ctx::cls, the layout of its shape, and every launch up to rule 9 (all six planes
+// of every level), enqueued on the solver's stream.  The caller waits, and marks the result resident with ak_mark_resident.
+int ak_scale_space(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride) {
   hipStream_t st = c->stream2;
   if (int rc = classic_upload_image(c, img, rows, cols, stride)) return rc;
   if (int rc = ak_ensure(c, rows, cols)) return rc;
   auto &d = c->akaze;
   const AkazeLevels &lv = d.lv;
   const size_t px0 = align64((size_t)rows * cols);
-  float *lx = d.scratch, *ly = d.scratch + px0, *ping = d.scratch + 2 * px0;
+  float *blur1 = d.scratch, *ping = d.scratch + px0;
   const dim3 blk(256);
   auto blur_grid = [](int w, int h) { return dim3((w + AKAZE_TW - 1) / AKAZE_TW, (h + AKAZE_TH - 1) / AKAZE_TH, 1); };
   HIP_TRY(c, hipMemsetAsync(d.stat, 0, AKAZE_STAT_INTS * sizeof(int), st));
-  // level 0 (rules 3, 4) and the contrast factor (rule 5; its sigma 1 blur borrows the first scratch plane)
+  // level 0 (rules 3, 4) and the contrast factor (rule 5; its sigma 1 blur goes to the first scratch plane)
   hipLaunchKernelGGL(akaze_blur_kernel<uint8_t>, blur_grid(cols, rows), blk, 0, st, c->cls.im, lv.l[0].Lt, lv.l[0].Lsmooth, rows, cols, d.g0);
-  hipLaunchKernelGGL(akaze_blur_kernel<uint8_t>, blur_grid(cols, rows), blk, 0, st, c->cls.im, lx, (float *)nullptr, rows, cols, d.g1);
-  hipLaunchKernelGGL(akaze_gradmax_kernel, grid_of(cols, rows), blk, 0, st, lx, rows, cols, d.stat);
-  hipLaunchKernelGGL(akaze_hist_kernel, grid_of(cols, rows), blk, 0, st, lx, rows, cols, d.stat);
+  hipLaunchKernelGGL(akaze_blur_kernel<uint8_t>, blur_grid(cols, rows), blk, 0, st, c->cls.im, blur1, (float *)nullptr, rows, cols, d.g1);
+  hipLaunchKernelGGL(akaze_gradmax_kernel, grid_of(cols, rows), blk, 0, st, blur1, rows, cols, d.stat);
+  hipLaunchKernelGGL(akaze_hist_kernel, grid_of(cols, rows), blk, 0, st, blur1, rows, cols, d.stat);
   hipLaunchKernelGGL(akaze_contrast_finish_kernel, dim3(1), dim3(64), 0, st, rows, cols, d.octaves, d.stat);
   // rules 6 - 8: every further level
   size_t t0 = 0;
@@ -251,7 +238,7 @@ int spvo_akaze_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_
     }
     t0 += n;
   }
-  // rule 9
+  // rule 9: the first derivatives stay, per level, for spvo_akaze_describe
   for (int i = 0; i < lv.n; ++i) {
     const AkazeLevel &L = lv.l[i];
     const int s = L.sigma_size;
@@ -262,9 +249,48 @@ int spvo_akaze_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_
       norm = 1.0f / ((2.0f * (float)s) * (w + 2.0f));
       wn = w * norm;
     }
-    hipLaunchKernelGGL(akaze_deriv_kernel, grid_of(L.w, L.h), blk, 0, st, L.Lsmooth, lx, ly, L.h, L.w, s, norm, wn);
-    hipLaunchKernelGGL(akaze_det_kernel, grid_of(L.w, L.h), blk, 0, st, lx, ly, L.Ldet, L.h, L.w, s, norm, wn, (float)(s * s * s * s));
+    hipLaunchKernelGGL(akaze_deriv_kernel, grid_of(L.w, L.h), blk, 0, st, L.Lsmooth, L.Lx, L.Ly, L.h, L.w, s, norm, wn);
+    hipLaunchKernelGGL(akaze_det_kernel, grid_of(L.w, L.h), blk, 0, st, L.Lx, L.Ly, L.Ldet, L.h, L.w, s, norm, wn, (float)(s * s * s * s));
   }
+  HIP_TRY(c, hipGetLastError());
+  return SPVO_OK;
+}
+
+// after the wait: the planes belong to the image now resident; stat: the first AKAZE_STAT_HIST integers as the kernels left them
+void ak_mark_resident(spvo_ctx *c, const int *stat) {
+  auto &d = c->akaze;
+  d.valid = true;
+  d.image_gen = c->cls.image_gen;
+  for (int o = 0; o < AKAZE_MAX_OCTAVES; ++o) std::memcpy(&d.k[o], &stat[AKAZE_STAT_K + o], sizeof(float));
+}
+
+bool ak_resident(const spvo_ctx *c) {
+  const auto &d = c->akaze;
+  return d.valid && d.image_gen == c->cls.image_gen && c->cls.rows == d.rows && c->cls.cols == d.cols;
+}
+}  // namespace
+
+void spvo_int::akaze_release(spvo_ctx *c) {
+  auto &d = c->akaze;
+  dev_free(d.planes, d.scratch, d.tabs, d.keys, d.rank, d.rec, d.stat, d.d_kp, d.d_angle, d.d_desc);
+  d.plane_cap = d.scratch_cap = d.tab_cap = 0; d.cand_cap = d.kp_cap = 0; d.rows = d.cols = 0; d.valid = false;
+}
+
+extern "C" {
+
+int spvo_akaze_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride, float threshold, spvo_akaze_keypoint *kp, int cap, int *n_out) {
+  if (!c || !img || !n_out || rows <= 0 || cols <= 0 || stride < (size_t)cols || cap < 0 || (cap > 0 && !kp)) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  *n_out = 0;
+  if (!std::isfinite(threshold) || !(threshold > 0.f)) return fail(c, SPVO_ERR_INVALID, "spvo_akaze_detect: the threshold must be finite and positive");
+  if (rows < 16 || cols < 16) return fail(c, SPVO_ERR_INVALID, "spvo_akaze_detect: images of at least 16 x 16 only");
+  if (int rc = brisk_check_image(c, "spvo_akaze_detect", rows, cols)) return rc;
+  if (int rc = require_idle(c)) return rc;
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = c->stream2;
+  if (int rc = ak_scale_space(c, img, rows, cols, stride)) return rc;
+  auto &d = c->akaze;
+  const AkazeLevels &lv = d.lv;
+  const dim3 blk(256);
   // rules 10, 12, 13
   for (int first = 0; first < lv.n; first += AK_SUBLEVELS) {   // one launch per octave; an octave with no room inside its smallest border has none
     const AkazeLevel &L = lv.l[first];
@@ -281,9 +307,7 @@ int spvo_akaze_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_
   HIP_TRY(c, hipStreamSynchronize(st));
   // (the list holds every strict maximum the borders leave room for, so the overflow flag cannot be set; were it, the count would be wrong)
   if (stat[AKAZE_STAT_OVERFLOW] || stat[AKAZE_STAT_NCAND] > d.cand_cap) return fail(c, SPVO_ERR_STATE, "spvo_akaze_detect: the candidate list overflowed although it is sized from the image");
-  d.valid = true;
-  d.image_gen = c->cls.image_gen;
-  for (int o = 0; o < AKAZE_MAX_OCTAVES; ++o) std::memcpy(&d.k[o], &stat[AKAZE_STAT_K + o], sizeof(float));
+  ak_mark_resident(c, stat);
   d.h_cand.resize((size_t)stat[AKAZE_STAT_NCAND]);
   if (!d.h_cand.empty()) {
     HIP_TRY(c, hipMemcpyAsync(d.h_cand.data(), d.rec, d.h_cand.size() * sizeof(AkazeCand), hipMemcpyDeviceToHost, st));
@@ -305,7 +329,7 @@ int spvo_akaze_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_
 int spvo_akaze_debug_level(spvo_ctx *c, int level, int what, float *out, int *rows, int *cols) {
   if (!c || !rows || !cols || level < 0 || what < 0 || what > 3) return fail(c, SPVO_ERR_INVALID, "bad argument");
   auto &d = c->akaze;
-  if (!d.valid || d.image_gen != c->cls.image_gen || c->cls.rows != d.rows || c->cls.cols != d.cols) return fail(c, SPVO_ERR_STATE, "spvo_akaze_debug_level: no spvo_akaze_detect result is resident");
+  if (!ak_resident(c)) return fail(c, SPVO_ERR_STATE, "spvo_akaze_debug_level: no spvo_akaze_detect result is resident");
   if (level >= d.lv.n) return fail(c, SPVO_ERR_INVALID, "spvo_akaze_debug_level: the scale space of this image has %d levels", d.lv.n);
   if (int rc = require_idle(c)) return rc;
   const AkazeLevel &L = d.lv.l[level];
@@ -321,9 +345,70 @@ int spvo_akaze_debug_level(spvo_ctx *c, int level, int what, float *out, int *ro
 int spvo_akaze_last_contrast(spvo_ctx *c, float *k, int *octaves) {
   if (!c || !k || !octaves) return fail(c, SPVO_ERR_INVALID, "bad argument");
   auto &d = c->akaze;
-  if (!d.valid || d.image_gen != c->cls.image_gen || c->cls.rows != d.rows || c->cls.cols != d.cols) return fail(c, SPVO_ERR_STATE, "spvo_akaze_last_contrast: no spvo_akaze_detect result is resident");
+  if (!ak_resident(c)) return fail(c, SPVO_ERR_STATE, "spvo_akaze_last_contrast: no spvo_akaze_detect result is resident");
   *octaves = d.octaves;
   for (int o = 0; o < AKAZE_MAX_OCTAVES; ++o) k[o] = o < d.octaves ? d.k[o] : 0.f;
+  return SPVO_OK;
+}
+
+int spvo_akaze_describe(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride, const spvo_akaze_keypoint *kp, int n, float *angle, uint8_t *desc) {
+  if (!c || rows <= 0 || cols <= 0 || n < 0 || (n > 0 && (!kp || !angle || !desc)) || (img && stride < (size_t)cols)) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  if (rows < 16 || cols < 16) return fail(c, SPVO_ERR_INVALID, "spvo_akaze_describe: images of at least 16 x 16 only");
+  if (int rc = brisk_check_image(c, "spvo_akaze_describe", rows, cols)) return rc;
+  if (int rc = require_idle(c)) return rc;
+  auto &d = c->akaze;
+  if (!img && !(ak_resident(c) && d.rows == rows && d.cols == cols))
+    return fail(c, SPVO_ERR_STATE, "spvo_akaze_describe: no spvo_akaze_detect result of a %d x %d image is resident (call spvo_akaze_detect first, or pass the image)", rows, cols);
+  {
+    // every record against the levels of this shape, before anything is uploaded or written
+    int levels, octave[AKAZE_MAX_LEVELS];
+    if (d.rows == rows && d.cols == cols) {
+      levels = d.lv.n;
+      for (int i = 0; i < levels; ++i) octave[i] = d.lv.l[i].octave;
+    } else {
+      const AkTables T = make_tables(rows, cols);
+      levels = T.n;
+      std::memcpy(octave, T.octave, sizeof octave);
+    }
+    for (int i = 0; i < n; ++i) {
+      const spvo_akaze_keypoint &p = kp[i];
+      if (p.class_id < 0 || p.class_id >= levels) return fail(c, SPVO_ERR_INVALID, "spvo_akaze_describe: keypoint %d has class_id %d; the scale space of this image has %d levels", i, p.class_id, levels);
+      if (p.octave != octave[p.class_id]) return fail(c, SPVO_ERR_INVALID, "spvo_akaze_describe: keypoint %d has octave %d; level %d lies on octave %d", i, p.octave, p.class_id, octave[p.class_id]);
+      if (!std::isfinite(p.x) || !std::isfinite(p.y) || !std::isfinite(p.size) || !(p.size > 0.f))
+        return fail(c, SPVO_ERR_INVALID, "spvo_akaze_describe: keypoint %d is (%g, %g) of size %g", i, (double)p.x, (double)p.y, (double)p.size);
+    }
+  }
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = c->stream2;
+  if (img) {
+    if (int rc = ak_scale_space(c, img, rows, cols, stride)) return rc;
+    int stat[AKAZE_STAT_HIST];
+    HIP_TRY(c, hipMemcpyAsync(stat, d.stat, sizeof stat, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    ak_mark_resident(c, stat);
+  }
+  if (n == 0) return SPVO_OK;
+  if (n > d.kp_cap) {
+    HIP_TRY(c, hipStreamSynchronize(st));
+    dev_free(d.d_kp, d.d_angle, d.d_desc);
+    d.kp_cap = 0;
+    const int cap = std::max(n, 1024);
+    int rc;
+    if ((rc = dev_alloc(c, &d.d_kp, (size_t)cap, false)) || (rc = dev_alloc(c, &d.d_angle, (size_t)cap, false)) || (rc = dev_alloc(c, &d.d_desc, (size_t)cap * AKAZE_MLDB_BYTES, false))) return rc;
+    d.kp_cap = cap;
+  }
+  static_assert(sizeof(spvo_akaze_keypoint) == sizeof(AkazeKp) && SPVO_AKAZE_DESC_BYTES == AKAZE_MLDB_BYTES, "record layout");
+  HIP_TRY(c, hipMemcpyAsync(d.d_kp, kp, (size_t)n * sizeof(AkazeKp), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(akaze_describe_kernel, dim3(std::min(n, 4096)), dim3(64), 0, st, d.lv, d.d_kp, n, d.d_angle, d.d_desc);
+  HIP_TRY(c, hipGetLastError());
+  // into staging first: a failure below leaves the caller's buffers as they were
+  d.h_angle.resize((size_t)n);
+  d.h_desc.resize((size_t)n * AKAZE_MLDB_BYTES);
+  HIP_TRY(c, hipMemcpyAsync(d.h_angle.data(), d.d_angle, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(d.h_desc.data(), d.d_desc, (size_t)n * AKAZE_MLDB_BYTES, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  std::memcpy(angle, d.h_angle.data(), (size_t)n * sizeof(float));
+  std::memcpy(desc, d.h_desc.data(), (size_t)n * AKAZE_MLDB_BYTES);
   return SPVO_OK;
 }
 

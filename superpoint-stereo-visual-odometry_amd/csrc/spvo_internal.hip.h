@@ -423,9 +423,10 @@ struct spvo_ctx {
     BriskDetLayers lv{};
     BriskResizeJob jobs[BRISK_DET_LAYERS]{};   // jobs[i]: layer i from its source (i >= 1)
   } brisk_det;
-  // AKAZE detector (akaze.hip.h) on the image resident in `cls`: the four planes of every level (what spvo_akaze_debug_level serves until the
-  // next call), three scratch planes of the image's size (the scaled first derivatives; the second buffer of the diffusion steps), the
-  // area taps of the octaves that are no exact halves, the candidate lists -- sized from the image, grown on demand -- and the tables
+  // AKAZE detector (akaze.hip.h) on the image resident in `cls`: the six planes of every level (the four spvo_akaze_debug_level serves until
+  // the next call, and the scaled first derivatives Lx, Ly that spvo_akaze_describe samples), two scratch planes of the image's size (the
+  // contrast factor's sigma 1 blur; the second buffer of the diffusion steps), the area taps of the octaves that are no exact halves, the
+  // candidate lists -- sized from the image, grown on demand -- the tables, and the descriptor's keypoint, angle and row buffers
   struct AkazeBufs {
     int rows = 0, cols = 0;               // shape the layout and the tables belong to (0: none)
     bool valid = false;                   // the planes of a completed spvo_akaze_detect are on the device ...
@@ -445,6 +446,12 @@ struct spvo_ctx {
     std::vector<float> h_tau;                          // their sizes, transition after transition
     AkazeTaps g0{}, g1{};                              // sigma 1.6 and sigma 1
     float k[AKAZE_MAX_OCTAVES] = {0};                  // the last call's contrast factor per octave
+    AkazeKp *d_kp = nullptr;                           // spvo_akaze_describe (akaze_mldb.hip.h): records in, angles and 61-byte rows out
+    float *d_angle = nullptr;
+    uint8_t *d_desc = nullptr;
+    int kp_cap = 0;
+    std::vector<float> h_angle;                        // host staging of a call's results
+    std::vector<uint8_t> h_desc;
   } akaze;
   // SIFT detector + descriptor of the classic front end (sift.hip.h): the image, its pyramid (all Gaussian and DoG levels: what
   // spvo_sift_debug_level serves until the next call), the candidate and output lists; device buffers grow on demand, the host staging keeps its capacity

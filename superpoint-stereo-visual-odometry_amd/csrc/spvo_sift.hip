@@ -235,6 +235,7 @@ int spvo_sift_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t
   if (!c->pendq.empty()) return fail(c, SPVO_ERR_STATE, "detector submissions are in flight: complete them with spvo_detect_wait first");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   *n_out = 0;
+  c->akaze.valid = false;   // SIFT keeps an image of its own, but the last detector call owns what is resident: the AKAZE scale space's claim ends (spvo_akaze_describe(img = NULL))
   auto &s = c->sift;
   hipStream_t st = c->stream2;
   SiftPyr P{};
@@ -316,6 +317,7 @@ int spvo_sift_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_
   if (!c->pendq.empty()) return fail(c, SPVO_ERR_STATE, "detector submissions are in flight: complete them with spvo_detect_wait first");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   out_l->n = out_r->n = 0;
+  c->akaze.valid = false;   // as spvo_sift_detect: the AKAZE scale space's claim ends
   auto &s = c->sift;
   PairStage &ps = s.pair;
   hipStream_t st = c->stream2;

@@ -105,13 +105,16 @@ struct BriskResizeJob { const uint8_t *src; uint8_t *dst; int sh, sw, dh, dw; co
 struct BriskResizeJobs { BriskResizeJob j[2]; };
 struct BriskDetKeypoint { float x, y, size, angle, response; int32_t octave; };   // mirrors spvo_brisk_keypoint (include/spvo.h)
 
-// ---- AKAZE detector (akaze.hip.h): a level of the nonlinear scale space with its four resident planes, the symmetric half of a Gaussian
-// kernel, and a candidate as the extrema stage leaves it for the host's suppression (its first seven fields mirror spvo_akaze_keypoint)
+// ---- AKAZE detector (akaze.hip.h): a level of the nonlinear scale space with its resident planes (the four spvo_akaze_debug_level serves,
+// and the scaled first derivatives Lx, Ly of rule 9, which the descriptor of akaze_mldb.hip.h samples), the symmetric half of a Gaussian
+// kernel, a candidate as the extrema stage leaves it for the host's suppression (its first seven fields mirror spvo_akaze_keypoint), and
+// that record itself as the describe kernel reads it
 constexpr int AKAZE_MAX_LEVELS = 16, AKAZE_MAX_OCTAVES = 4, AKAZE_BLUR_R = 4, AKAZE_NBINS = 300;
-struct AkazeLevel { float *Lt, *Lsmooth, *Lflow, *Ldet; int h, w, octave, sigma_size, border; float esigma; };
+struct AkazeLevel { float *Lt, *Lsmooth, *Lflow, *Ldet, *Lx, *Ly; int h, w, octave, sigma_size, border; float esigma; };
 struct AkazeLevels { AkazeLevel l[AKAZE_MAX_LEVELS]; int n; };
 struct AkazeTaps { float g[AKAZE_BLUR_R + 1]; int r; };   // g[0] the centre, g[j] the taps at +- j, j <= r
 struct AkazeCand { float x, y, size, angle, response; int32_t octave, class_id, row, col, ok; };
+struct AkazeKp { float x, y, size, angle, response; int32_t octave, class_id; };
 // the integers of a call (one cleared allocation): candidates, overflow flag, bits of the gradient maximum, the contrast factor per octave
 // (float bits), the histogram
 constexpr int AKAZE_STAT_NCAND = 0, AKAZE_STAT_OVERFLOW = 1, AKAZE_STAT_MAX = 2, AKAZE_STAT_K = 4, AKAZE_STAT_HIST = 8, AKAZE_STAT_INTS = AKAZE_STAT_HIST + AKAZE_NBINS;

@@ -431,8 +431,10 @@ cv::Mat FeatureFrontEnd::visualizeInliers(const ImagePosition image_position) {
 static bool g_classic_resident = false;
 static int g_classic_resident_capacity = 8192;
 static bool g_classic_brisk_pair_resident = false;
+static bool g_classic_akaze_descriptor = false;
 void ClassicFeatureFrontEnd::setDeviceResident(bool on) { g_classic_resident = on; }
 void ClassicFeatureFrontEnd::setBriskPairResident(bool on) { g_classic_brisk_pair_resident = on; }
+void ClassicFeatureFrontEnd::setAkazeDescriptor(bool on) { g_classic_akaze_descriptor = on; }
 void ClassicFeatureFrontEnd::setResidentCapacity(int rows) { g_classic_resident_capacity = rows; }
 
 ClassicFeatureFrontEnd::ClassicFeatureFrontEnd()
@@ -444,6 +446,7 @@ ClassicFeatureFrontEnd::ClassicFeatureFrontEnd(const DetectorType detector_type,
                                                const int input_width)
     : FeatureFrontEnd(detector_type, descriptor_type, matcher_type, selector_type, cross_check, stereo_threshold, stereo_threshold, refinement_degree,
                       verbose, input_height, input_width) {
+  akaze_descriptor_ = g_classic_akaze_descriptor;   // (initDetector and initDescriptor ask whether the pair runs)
   initDetector();
   initDescriptor();
   initMatcher();
@@ -459,6 +462,7 @@ ClassicFeatureFrontEnd::~ClassicFeatureFrontEnd() {
 
 #ifdef SPVO_USE_OPENCV
 bool ClassicFeatureFrontEnd::available() { return true; }
+bool ClassicFeatureFrontEnd::pairRuns() const { return true; }
 bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &, cv::Mat &) { return false; }   // (the OpenCV detectors work on the host)
 
 void ClassicFeatureFrontEnd::initDetector() {   // parameters: classic.cpp:7-56
@@ -529,9 +533,12 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
 // per image: with setDeviceResident alone it takes the per-image path and residentPairs() stays 0; with setBriskPairResident as well it is
 // one spvo_brisk_detect_pair per stereo pair into the same binary slots (64-byte rows), matched there.  AKAZE + BRISK
 // goes through spvo_akaze_detect (cv::AKAZE::create()->detect, classic.cpp:26-28) and spvo_brisk_describe with the detector's x, y and size,
-// per image only: with setDeviceResident it takes the per-image path and residentPairs() stays 0.  The AKAZE (MLDB) descriptor is an OpenCV
-// features2d call and stays unavailable, and so does every other mix (BRISK or AKAZE keypoints with an ORB descriptor -- spvo_orb_describe
-// refuses fractional coordinates --, SIFT keypoints with an ORB descriptor, ...).
+// per image only: with setDeviceResident it takes the per-image path and residentPairs() stays 0.  AKAZE + AKAZE goes through
+// spvo_akaze_detect and spvo_akaze_describe (cv::AKAZE::create()->compute, classic.cpp:69-70: orientation and the 61-byte MLDB descriptor on
+// the scale space the detector left on the device), per image only as well, and only with setAkazeDescriptor (opt-in): without it the pair
+// is refused as before.  The AKAZE descriptor on any other detector's keypoints stays unavailable -- it needs the level in class_id, and
+// OpenCV's own assertion refuses such keypoints too -- and so does every other mix (BRISK or AKAZE keypoints with an ORB descriptor --
+// spvo_orb_describe refuses fractional coordinates --, SIFT keypoints with an ORB descriptor, ...).
 bool ClassicFeatureFrontEnd::available() { return true; }
 static bool classic_detector_runs(DetectorType d) { return d == DetectorType::ORB || d == DetectorType::ShiTomasi || d == DetectorType::FAST; }
 static bool classic_sift_pair(DetectorType d, DescriptorType e) { return d == DetectorType::SIFT && e == DescriptorType::SIFT; }
@@ -542,17 +549,21 @@ static bool classic_brisk_pair(DetectorType d, DescriptorType e) {
 }
 // ... and with its own detector (spvo_brisk_detect), whose keypoints carry the sizes the pattern was designed for
 static bool classic_brisk_brisk(DetectorType d, DescriptorType e) { return d == DetectorType::BRISK && e == DescriptorType::BRISK; }
+static bool classic_akaze_akaze(DetectorType d, DescriptorType e) { return d == DetectorType::AKAZE && e == DescriptorType::AKAZE; }   // with setAkazeDescriptor only
 static bool classic_pair_runs(DetectorType d, DescriptorType e) {
   return classic_sift_pair(d, e) || (classic_detector_runs(d) && e == DescriptorType::ORB) || classic_brisk_pair(d, e) || classic_brisk_brisk(d, e);
 }
+bool ClassicFeatureFrontEnd::pairRuns() const {
+  return classic_pair_runs(detector_type_, descriptor_type_) || (akaze_descriptor_ && classic_akaze_akaze(detector_type_, descriptor_type_));
+}
 void ClassicFeatureFrontEnd::initDetector() {
   if (!classic_detector_runs(detector_type_) && !classic_sift_pair(detector_type_, descriptor_type_) && !classic_brisk_brisk(detector_type_, descriptor_type_) &&
-      !(detector_type_ == DetectorType::AKAZE && classic_brisk_pair(detector_type_, descriptor_type_)))
+      !(detector_type_ == DetectorType::AKAZE && classic_brisk_pair(detector_type_, descriptor_type_)) && !(akaze_descriptor_ && classic_akaze_akaze(detector_type_, descriptor_type_)))
     logError("[initDetector] only ORB, ShiTomasi, FAST, SIFT (with SIFT descriptors), BRISK and AKAZE (with BRISK descriptors) run without OpenCV (build with SPVO_USE_OPENCV for the other detectors of classic.cpp:7-56)");
 }
 void ClassicFeatureFrontEnd::initDescriptor() {
   if (descriptor_type_ != DescriptorType::ORB && !classic_sift_pair(detector_type_, descriptor_type_) && !classic_brisk_pair(detector_type_, descriptor_type_) &&
-      !classic_brisk_brisk(detector_type_, descriptor_type_))
+      !classic_brisk_brisk(detector_type_, descriptor_type_) && !(akaze_descriptor_ && classic_akaze_akaze(detector_type_, descriptor_type_)))
     logError("[initDescriptor] only ORB, BRISK on ShiTomasi / FAST / BRISK / AKAZE keypoints, and SIFT on SIFT keypoints, run without OpenCV (build with SPVO_USE_OPENCV for the other descriptors of classic.cpp:58-79, the AKAZE (MLDB) descriptor among them)");
 }
 
@@ -560,7 +571,7 @@ std::vector<cv::KeyPoint> ClassicFeatureFrontEnd::detectKeypoints(const cv::Mat 
   std::vector<cv::KeyPoint> keypoints;
   orb_desc_ = cv::Mat();
   detected_data_ = nullptr;
-  if (!classic_pair_runs(detector_type_, descriptor_type_)) {
+  if (!pairRuns()) {
     logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB, ShiTomasi and FAST with ORB descriptors, ShiTomasi, FAST, BRISK and AKAZE with BRISK descriptors and SIFT with SIFT descriptors run");
     return keypoints;
   }
@@ -765,6 +776,30 @@ cv::Mat ClassicFeatureFrontEnd::describeKeypoints(std::vector<cv::KeyPoint> &key
     if (m) std::memcpy(d.ptr<uint8_t>(0), desc.ptr<uint8_t>(0), (size_t)m * 64);
     return d;
   }
+  if (akaze_descriptor_ && classic_akaze_akaze(detector_type_, descriptor_type_)) {
+    // cv::AKAZE::create()->compute(img, keypoints, descriptors), classic.cpp:69-70: every keypoint gets its main orientation (degrees) and a
+    // 61-byte row; none is erased.  The level comes from class_id, as in OpenCV.  On the image detectKeypoints just saw, the scale space is
+    // still on the device (img = NULL); any other image has it built first.
+    if (!ensureContext()) return cv::Mat();
+    if (img.depth() != CV_8U || img.rows <= 0) {
+      logError("describeKeypoints: 8-bit single-channel image expected");
+      return cv::Mat();
+    }
+    const int n = (int)keypoints.size();
+    std::vector<spvo_akaze_keypoint> kp((size_t)n);
+    std::vector<float> angle((size_t)n);
+    for (int i = 0; i < n; ++i)
+      kp[i] = spvo_akaze_keypoint{keypoints[i].pt.x, keypoints[i].pt.y, keypoints[i].size, keypoints[i].angle, keypoints[i].response, keypoints[i].octave, keypoints[i].class_id};
+    cv::Mat desc(n, SPVO_AKAZE_DESC_BYTES, CV_8UC1);
+    const bool resident = detected_data_ && detected_data_ == img.data && detected_rows_ == img.rows && detected_cols_ == img.cols;
+    if (spvo_akaze_describe(ctx_, resident ? nullptr : img.ptr<uint8_t>(0), img.rows, img.cols, (size_t)img.step, kp.data(), n, angle.data(), n ? desc.ptr<uint8_t>(0) : nullptr) != SPVO_OK) {
+      logError(std::string("spvo_akaze_describe: ") + spvo_last_error(ctx_));
+      keypoints.clear();
+      return cv::Mat();
+    }
+    for (int i = 0; i < n; ++i) keypoints[i].angle = angle[i];
+    return desc;
+  }
   if (orb_desc_.rows != (int)keypoints.size()) {
     logError("describeKeypoints: call detectKeypoints on the same image first (ORB and SIFT detect and describe in one pass here)");
     return cv::Mat();
@@ -777,7 +812,7 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
     logError("input images shape doesn't match!");
     return;
   }
-  if (!classic_pair_runs(detector_type_, descriptor_type_)) {
+  if (!pairRuns()) {
     logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB, ShiTomasi and FAST with ORB descriptors, ShiTomasi, FAST, BRISK and AKAZE with BRISK descriptors and SIFT with SIFT descriptors run");
     return;
   }

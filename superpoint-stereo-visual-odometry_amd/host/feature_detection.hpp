@@ -348,16 +348,22 @@ public:
   // the same through spvo_sift_detect_pair, the SIFT slots and spvo_match_l2_slots; ShiTomasi + BRISK and FAST + BRISK through the two BRISK
   // kinds of spvo_classic_detect (64-byte rows in the same binary slots).  BRISK + BRISK takes the per-image path under setDeviceResident
   // alone; with setBriskPairResident as well (opt-in, read at construction like the other two) it goes through spvo_brisk_detect_pair into
-  // the same binary slots.
+  // the same binary slots.  AKAZE keypoints take the per-image path whatever is set.
+  // setAkazeDescriptor (opt-in, read at construction like the others): AKAZE + AKAZE runs, through spvo_akaze_detect and
+  // spvo_akaze_describe (cv::AKAZE::create()->compute: orientation + the 61-byte MLDB descriptor), per image.  Off, that pair is refused
+  // as every pair that does not run is.
   static void setDeviceResident(bool on);
   static void setResidentCapacity(int rows);   // rows per binary slot [8192]
   static void setBriskPairResident(bool on);   // [off]
+  static void setAkazeDescriptor(bool on);     // [off]
   // pairs that actually stayed resident (spvo_classic_detect / spvo_sift_detect_pair / spvo_brisk_detect_pair returned SPVO_OK): what tells the resident path from its fallback
   unsigned residentPairs() const { return resident_ok_pairs_; }
 
 private:
   bool resident_ = false;
   bool brisk_pair_resident_ = false;   // setBriskPairResident at construction
+  bool akaze_descriptor_ = false;      // setAkazeDescriptor at construction
+  bool pairRuns() const;               // this detector / descriptor pair runs in this build
   int resident_capacity_ = 8192;
   unsigned resident_pairs_ = 0;   // pairs handed to spvo_classic_detect: pair k lives in slots 2 (k % 4), 2 (k % 4) + 1
   unsigned resident_ok_pairs_ = 0;   // ... of which the call returned SPVO_OK (residentPairs)

@@ -402,7 +402,8 @@ int spvo_host_classic_sequence_trace(const char *detector_name, int n, const uin
                               input_width, digest);
 }
 
-// ... with the descriptor named as well ("ORB", "BRISK", "SIFT"; -1000001: no such descriptor): "BRISK" goes with ShiTomasi, FAST, BRISK and AKAZE keypoints
+// ... with the descriptor named as well ("ORB", "BRISK", "SIFT", "AKAZE"; -1000001: no such descriptor): "BRISK" goes with ShiTomasi, FAST, BRISK and AKAZE keypoints,
+// "AKAZE" with AKAZE keypoints once spvo_host_classic_set_akaze_descriptor is on
 int spvo_host_classic_sequence_desc(const char *detector_name, const char *descriptor_name, int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols,
                                     const double *P_l, const double *P_r, int knn, int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses,
                                     int *stats, double *seconds, int input_height, int input_width, uint64_t *digest) {
@@ -424,6 +425,10 @@ void spvo_host_classic_set_resident(int on, int capacity) {
 // ClassicFeatureFrontEnd::setBriskPairResident for the front ends constructed afterwards: BRISK + BRISK through spvo_brisk_detect_pair
 // when setDeviceResident is on as well
 void spvo_host_classic_set_brisk_resident(int on) { ClassicFeatureFrontEnd::setBriskPairResident(on != 0); }
+
+// ClassicFeatureFrontEnd::setAkazeDescriptor for the front ends constructed afterwards: AKAZE + AKAZE runs (spvo_akaze_detect +
+// spvo_akaze_describe, 61-byte rows); off, that pair is refused
+void spvo_host_classic_set_akaze_descriptor(int on) { ClassicFeatureFrontEnd::setAkazeDescriptor(on != 0); }
 
 // the ORB + ORB front end at the native resolution (the export's first form)
 int spvo_host_classic_sequence(int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l, const double *P_r, int knn,

@@ -80,6 +80,7 @@ class SolveOutput(C.Structure):
 SIFT_KP_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("size", np.float32), ("angle", np.float32), ("response", np.float32), ("octave", np.int32)])   # spvo_sift_keypoint
 BRISK_KP_DTYPE = SIFT_KP_DTYPE   # spvo_brisk_keypoint: octave is the layer 0..5, angle is -1
 AKAZE_KP_DTYPE = np.dtype(SIFT_KP_DTYPE.descr + [("class_id", np.int32)])   # spvo_akaze_keypoint: class_id is the level 0..15, angle is 0
+AKAZE_DESC_BYTES = 61                                                       # SPVO_AKAZE_DESC_BYTES: the full MLDB descriptor, 486 bits
 OBS_DTYPE = np.dtype([("X", np.float32, 3), ("uv", np.float32, 2), ("cam", np.int32), ("inverse", np.int32)])
 
 # every symbol include/spvo.h declares
@@ -87,7 +88,7 @@ SYMBOLS = [
     "spvo_default_config", "spvo_create", "spvo_destroy", "spvo_last_error", "spvo_load_weights", "spvo_engine_precision", "spvo_set_fp32_split",
     "spvo_preprocess", "spvo_forward", "spvo_debug_tensor", "spvo_heatmap", "spvo_nms",
     "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8",
-    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_detect_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
+    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_akaze_describe", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_detect_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
     "spvo_profile_enable", "spvo_profile_reset", "spvo_profile_only", "spvo_profile_count", "spvo_profile_get", "spvo_profile_stage_kernel",
     "spvo_set_tuning", "spvo_get_tuning", "spvo_clear_tuning",
     "spvo_comm_unique_id", "spvo_comm_available", "spvo_comm_create", "spvo_comm_create_host", "spvo_comm_rank", "spvo_comm_world", "spvo_comm_destroy",
@@ -153,6 +154,7 @@ def load() -> C.CDLL:
     lib.spvo_akaze_debug_level.argtypes = [vp, C.c_int, C.c_int, vp, ip, ip]
     lib.spvo_akaze_last_contrast.argtypes = [vp, vp, ip]
     lib.spvo_akaze_tables.argtypes = [C.c_int, C.c_int, ip, vp, vp, vp, vp, vp, C.c_int, ip, vp, vp]
+    lib.spvo_akaze_describe.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, vp, vp]
     lib.spvo_sift_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, C.c_int, ip]
     lib.spvo_sift_debug_level.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, ip, ip]
     lib.spvo_sift_detect_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(SiftFeatures), C.POINTER(SiftFeatures)]
@@ -537,7 +539,7 @@ class Context:
         """AKAZE keypoints of one u8 image (spvo_akaze_detect): dict of kp [m] (AKAZE_KP_DTYPE records: x, y, size, angle = 0, response,
         octave, class_id = level) in the order the suppression leaves them, and n, the number found; m = min(n, cap).  cap = None: all of
         them (a second call when the first buffer was too small).  The image stays on the device for a brisk_describe(None, ...,
-        shape=img.shape) that follows."""
+        shape=img.shape) that follows, its scale space for an akaze_describe(None, kp)."""
         img = _u8_rows(img)
         want = 4096 if cap is None else int(cap)
         while True:
@@ -562,6 +564,28 @@ class Context:
         k, n = np.zeros(4, np.float32), C.c_int(0)
         self._check(self.lib.spvo_akaze_last_contrast(self.h, _ptr(k), C.byref(n)))
         return k[:n.value].copy()
+
+    def akaze_describe(self, img: Optional[np.ndarray], kp: np.ndarray, shape=None):
+        """Orientation and MLDB descriptor of AKAZE keypoints (spvo_akaze_describe): kp [n] AKAZE_KP_DTYPE records (class_id = level; the
+        angle that comes in is ignored) -> dict of angle [n] float32 degrees and desc [n, 61] uint8; no keypoint is dropped.  img None:
+        on the scale space the last akaze_detect() / akaze_describe(img, ...) left on the device (shape: that image's, default the
+        remembered one); otherwise the scale space of img is built first and stays."""
+        kp = np.ascontiguousarray(kp, AKAZE_KP_DTYPE)
+        n = len(kp)
+        angle = np.zeros(max(n, 1), np.float32)
+        desc = np.zeros((max(n, 1), AKAZE_DESC_BYTES), np.uint8)
+        if img is None:
+            rows, cols = shape if shape is not None else getattr(self, "_resident_shape", (0, 0))
+            ptr, stride = None, 0
+            if rows <= 0 or cols <= 0:
+                rows = cols = 16           # nothing remembered: let the library answer (SPVO_ERR_STATE)
+        else:
+            img = _u8_rows(img)
+            (rows, cols), ptr, stride = img.shape, _ptr(img), img.strides[0]
+        self._check(self.lib.spvo_akaze_describe(self.h, ptr, rows, cols, stride, _ptr(kp), n, _ptr(angle), _ptr(desc)))
+        if img is not None:
+            self._resident_shape = img.shape
+        return dict(angle=angle[:n].copy(), desc=desc[:n].copy())
 
     def brisk_detect_pair(self, img_l, img_r, slot_l: int, slot_r: int, threshold: int = 30, octaves: int = 3, slot_capacity: int = 8192, cap: Optional[int] = None):
         """One stereo pair through the BRISK detector + extractor into two binary feature slots of 64-byte rows (spvo_brisk_detect_pair).

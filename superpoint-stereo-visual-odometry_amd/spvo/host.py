@@ -342,14 +342,15 @@ class FrontEnd:
 
 
 def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_threshold=2.0, refinement_degree=4, warm=0, detector="ORB", input_size=None, resident=False,
-                     resident_capacity=0, trace=False, descriptor="ORB", brisk_resident=False):
+                     resident_capacity=0, trace=False, descriptor="ORB", brisk_resident=False, akaze_descriptor=False):
     """stereoCallback replayed on ClassicFeatureFrontEnd(detector, descriptor, BF, ...) (node.cpp:353-360) over host image pairs -- detector
     "ORB", "ShiTomasi" or "FAST" with descriptor "ORB", "ShiTomasi", "FAST", "BRISK" or "AKAZE" with descriptor "BRISK" (64-byte rows; detector "BRISK"
-    or "AKAZE" with the default descriptor "ORB" does not run, nor does descriptor "AKAZE": the MLDB descriptor is not built), or detector "SIFT" (SIFT descriptors whatever `descriptor` says, as before); input_size None: at their native resolution, (height, width): through preprocessImageImpl first
+    or "AKAZE" with the default descriptor "ORB" does not run; "AKAZE" with descriptor "AKAZE" -- orientation and the 61-byte MLDB rows of
+    spvo_akaze_describe -- runs with akaze_descriptor=True (ClassicFeatureFrontEnd::setAkazeDescriptor, reset afterwards) and is refused without), or detector "SIFT" (SIFT descriptors whatever `descriptor` says, as before); input_size None: at their native resolution, (height, width): through preprocessImageImpl first
     (classic.cpp:96-100).  Returns (poses [n, 7] = q xyzw + t of cam0_curr_T_cam0_prev, stats [n, 4] = keypoints L, R, stereo
     matches, PnP inliers, seconds spent on frames warm .. n-1).
     resident: ClassicFeatureFrontEnd::setDeviceResident for this run -- one spvo_classic_detect (SIFT: spvo_sift_detect_pair) per pair, features
-    and matching stay on the device, for every pair named above with BRISK descriptors on ShiTomasi / FAST keypoints included; "AKAZE" + "BRISK" always takes
+    and matching stay on the device, for every pair named above with BRISK descriptors on ShiTomasi / FAST keypoints included; "AKAZE" keypoints always take
     the per-image path and classic_resident_pairs() stays 0; "BRISK" + "BRISK"
     takes the per-image path and classic_resident_pairs() stays 0 unless brisk_resident (ClassicFeatureFrontEnd::setBriskPairResident) is set
     as well: then it is one spvo_brisk_detect_pair per pair into the same binary slots (resident_capacity > 0: rows per slot; a pair that does not
@@ -367,6 +368,8 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     lib.spvo_host_classic_set_resident.argtypes = [C.c_int, C.c_int]
     lib.spvo_host_classic_set_brisk_resident.restype = None
     lib.spvo_host_classic_set_brisk_resident.argtypes = [C.c_int]
+    lib.spvo_host_classic_set_akaze_descriptor.restype = None
+    lib.spvo_host_classic_set_akaze_descriptor.argtypes = [C.c_int]
     n = len(frames)
     ls = [np.ascontiguousarray(f[0], np.uint8) for f in frames]
     rs = [np.ascontiguousarray(f[1], np.uint8) for f in frames]
@@ -382,6 +385,7 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     digest = np.zeros((n, 8), np.uint64) if trace else None     # NULL: nothing is digested (the digests are computed inside the timed loop)
     lib.spvo_host_classic_set_resident(int(bool(resident)), int(resident_capacity) if resident_capacity > 0 else 8192)
     lib.spvo_host_classic_set_brisk_resident(int(bool(brisk_resident)))
+    lib.spvo_host_classic_set_akaze_descriptor(int(bool(akaze_descriptor)))
     try:
         args = (n, pl, pr, rows, cols, Pl.ctypes.data, Pr.ctypes.data, 1 if selector == "KNN" else 0, int(cross_check), stereo_threshold, refinement_degree, warm,
                 poses.ctypes.data, stats.ctypes.data, C.byref(sec), ih, iw, digest.ctypes.data if trace else None)
@@ -392,6 +396,7 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     finally:
         lib.spvo_host_classic_set_resident(0, 8192)
         lib.spvo_host_classic_set_brisk_resident(0)
+        lib.spvo_host_classic_set_akaze_descriptor(0)
     if rc == -1000000:
         raise ValueError("unknown detector %r" % (detector,))
     if rc == -1000001:
@@ -428,8 +433,9 @@ def classic_default_probe(img_l, img_r, P_l, P_r):
     return rc, counts, buf.value.decode()
 
 
-def classic_pair_probe(detector, descriptor, img_l, img_r, P_l, P_r):
+def classic_pair_probe(detector, descriptor, img_l, img_r, P_l, P_r, akaze_descriptor=False):
     """ClassicFeatureFrontEnd(detector, descriptor, BF, NN, cross-check) at the native resolution offered one stereo pair.
+    akaze_descriptor: ClassicFeatureFrontEnd::setAkazeDescriptor for this probe (AKAZE + AKAZE runs), reset afterwards.
     -> (deque entries, [keypoints L, descriptor rows L, keypoints R, descriptor rows R, descriptor columns], the error it logged)"""
     lib = load()
     lib.spvo_host_classic_pair_probe.restype = C.c_int
@@ -440,6 +446,12 @@ def classic_pair_probe(detector, descriptor, img_l, img_r, P_l, P_r):
     Pr = np.ascontiguousarray(P_r, np.float64).reshape(12)
     counts = np.zeros(5, np.int32)
     buf = C.create_string_buffer(512)
-    rc = lib.spvo_host_classic_pair_probe(detector.encode(), descriptor.encode(), l.ctypes.data, r.ctypes.data, l.shape[0], l.shape[1], Pl.ctypes.data, Pr.ctypes.data,
-                                          counts.ctypes.data, buf, 512)
+    lib.spvo_host_classic_set_akaze_descriptor.restype = None
+    lib.spvo_host_classic_set_akaze_descriptor.argtypes = [C.c_int]
+    lib.spvo_host_classic_set_akaze_descriptor(int(bool(akaze_descriptor)))
+    try:
+        rc = lib.spvo_host_classic_pair_probe(detector.encode(), descriptor.encode(), l.ctypes.data, r.ctypes.data, l.shape[0], l.shape[1], Pl.ctypes.data, Pr.ctypes.data,
+                                              counts.ctypes.data, buf, 512)
+    finally:
+        lib.spvo_host_classic_set_akaze_descriptor(0)
     return rc, counts, buf.value.decode()

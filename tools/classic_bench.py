@@ -1,8 +1,9 @@
 """The classic front end on the GPU.
 
-python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK|AKAZE] [--descriptor ORB|BRISK] [--resident] [--brisk-resident]
+python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK|AKAZE] [--descriptor ORB|BRISK|AKAZE] [--resident] [--brisk-resident]
     ClassicFeatureFrontEnd(detector, descriptor, BF, KNN) over the synthetic stream: frames/s of the synchronous stereoCallback
-    (--descriptor BRISK: with --detector ShiTomasi, FAST, BRISK or AKAZE; --detector BRISK or AKAZE: with --descriptor BRISK only);
+    (--descriptor BRISK: with --detector ShiTomasi, FAST, BRISK or AKAZE; --detector BRISK: with --descriptor BRISK only; --detector AKAZE:
+    with --descriptor BRISK or AKAZE -- the latter sets ClassicFeatureFrontEnd::setAkazeDescriptor for the run: 61-byte MLDB rows);
     --resident: with ClassicFeatureFrontEnd::setDeviceResident (one spvo_classic_detect per pair, matching on the binary slots);
     --brisk-resident: with setBriskPairResident as well (BRISK + BRISK through one spvo_brisk_detect_pair per pair; needs --resident).
 python tools/classic_bench.py [frames] --detector ShiTomasi|FAST|ORB --descriptor ORB|BRISK --ab ROUNDS
@@ -29,6 +30,10 @@ python tools/classic_bench.py --leg akaze_detect [--calls 50] [--yardstick]
     akaze_half_kernel or akaze_area_kernel / akaze_gradmax_kernel / akaze_hist_kernel / akaze_contrast_finish_kernel / akaze_flow_kernel /
     akaze_fed_kernel / akaze_deriv_kernel / akaze_det_kernel / akaze_extrema_kernel / cls_rank_kernel / akaze_refine_kernel is the split.
     Prints the launches of one call (from spvo_akaze_tables); --yardstick: spvo_sift_detect afterwards in the same run.
+python tools/classic_bench.py --leg akaze_describe [--calls 100]
+    spvo_akaze_describe alone on the detector's keypoints of the 1241 x 376 sample, for rocprofv3 --kernel-trace --stats as above
+    (akaze_describe_kernel: one launch), and in the same run its yardsticks: spvo_brisk_describe(img = NULL) on the same keypoints,
+    spvo_akaze_describe with the image passed (the scale space rebuilt: the detector's chain without its extrema), spvo_akaze_detect.
 python tools/classic_bench.py --leg brisk_pair [--calls 50]
     spvo_brisk_detect_pair (threshold 30) alone on the 1241 x 376 sample pair, rotating through the slot ring, for rocprofv3 --kernel-trace
     --stats as above: the detector's kernels up to brisk_refine_kernel, then brisk_integral_*_kernel / brisk_pair_compact_kernel /
@@ -55,7 +60,7 @@ ap.add_argument("--detectors", action="store_true")
 ap.add_argument("--resident", action="store_true")
 ap.add_argument("--brisk-resident", action="store_true")
 ap.add_argument("--ab", type=int, default=0)
-ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "brisk_detect", "akaze_detect", "brisk_pair", "orb_describe", "match", "match_slots"])
+ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "brisk_detect", "akaze_detect", "akaze_describe", "brisk_pair", "orb_describe", "match", "match_slots"])
 ap.add_argument("--selector", default="KNN", choices=["NN", "KNN"])
 ap.add_argument("--cross", action="store_true")
 ap.add_argument("--yardstick", action="store_true")
@@ -101,6 +106,19 @@ if args.detectors or args.leg:
     def leg_akaze_detect():
         return ctx.akaze_detect(img)["n"]
 
+    if args.leg == "akaze_describe":
+        akp = ctx.akaze_detect(img)["kp"]
+        axy = np.ascontiguousarray(np.stack([akp["x"], akp["y"]], 1))
+
+    def leg_akaze_describe():                          # on the scale space the last detect / describe(img) left
+        return len(ctx.akaze_describe(None, akp)["desc"])
+
+    def leg_akaze_brisk_null():                        # the yardstick: the BRISK extractor on the same keypoints, image resident
+        return len(ctx.brisk_describe(None, axy, akp["size"], shape=img.shape)["kept"])
+
+    def leg_akaze_describe_img():                      # the scale space rebuilt first
+        return len(ctx.akaze_describe(img, akp)["desc"])
+
     if args.leg == "akaze_detect":
         T = capi.akaze_tables(*img.shape)
         new_octaves = int((np.diff(T["octave"]) > 0).sum())
@@ -141,9 +159,14 @@ if args.detectors or args.leg:
                 match_slots=("spvo_match_hamming_slots, %d x %d rows" % (len(fl["xy"]) if leg_match else 0, len(fr["xy"]) if leg_match else 0), leg_match_slots),
                 brisk=("spvo_brisk_describe, %d FAST keypoints" % (len(kp) if args.leg == "brisk" else 0), leg_brisk),
                 orb_describe=("spvo_orb_describe, %d FAST keypoints" % (len(kp) if args.leg == "orb_describe" else 0), leg_orb_describe),
+                akaze_describe=("spvo_akaze_describe(NULL)", leg_akaze_describe), akaze_brisk_null=("spvo_brisk_describe(NULL), same keypoints", leg_akaze_brisk_null),
+                akaze_describe_img=("spvo_akaze_describe(img)", leg_akaze_describe_img),
                 brisk_detect=("spvo_brisk_detect", leg_brisk_detect), akaze_detect=("spvo_akaze_detect", leg_akaze_detect), brisk_pair=("spvo_brisk_detect_pair (both images)", leg_brisk_pair),
                 orb=("spvo_orb_detect", leg_orb), sift=("spvo_sift_detect", leg_sift), gftt=("spvo_gftt_detect + spvo_orb_describe", leg_gftt), fast=("spvo_fast_detect + spvo_orb_describe", leg_fast))
-    for key in ([args.leg] + (["sift"] if args.yardstick else []) if args.leg else ["orb", "gftt", "fast"]):
+    keys = [args.leg] + (["sift"] if args.yardstick else []) if args.leg else ["orb", "gftt", "fast"]
+    if args.leg == "akaze_describe":
+        keys = ["akaze_describe", "akaze_brisk_null", "akaze_describe_img", "akaze_detect"]
+    for key in keys:
         name, fn = legs[key]
         for _ in range(args.warmup):
             n = fn()
@@ -180,5 +203,5 @@ else:
     n = args.frames
     seq = [frames[i % 8] for i in range(n)]
     p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5, detector=args.detector, resident=args.resident, descriptor=args.descriptor,
-                                        **(dict(brisk_resident=True) if args.brisk_resident else {}))
+                                        akaze_descriptor=args.descriptor == "AKAZE", **(dict(brisk_resident=True) if args.brisk_resident else {}))
     print("classic front end (%s%s) on the GPU: %.1f stereo frames/s (%.3f ms per pair), keypoints %d, stereo matches %d, inliers %d, %d pairs resident" % (args.detector + ("" if args.descriptor == "ORB" else " + " + args.descriptor), ", device-resident" if args.resident else "", (n - 5) / sec, 1e3 * sec / (n - 5), np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3]), host.classic_resident_pairs()))
