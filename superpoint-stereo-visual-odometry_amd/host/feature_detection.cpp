@@ -424,562 +424,6 @@ cv::Mat FeatureFrontEnd::visualizeInliers(const ImagePosition image_position) {
   return images_dq.end()[image_position].clone();
 }
 
-// ------------------------------------------------------------------------- classic front end (classic.cpp)
-// The reference's constructor hands `stereo_threshold` to the base class a second time in the place of `min_disparity`
-// (hpp:203-206), so the classic launch file's min_disparity is never used; kept, because the stereo gate of
-// solveStereoOdometry (base.cpp:169-172) then behaves as the reference's does.
-static bool g_classic_resident = false;
-static int g_classic_resident_capacity = 8192;
-static bool g_classic_brisk_pair_resident = false;
-static bool g_classic_akaze_descriptor = false;
-void ClassicFeatureFrontEnd::setDeviceResident(bool on) { g_classic_resident = on; }
-void ClassicFeatureFrontEnd::setBriskPairResident(bool on) { g_classic_brisk_pair_resident = on; }
-void ClassicFeatureFrontEnd::setAkazeDescriptor(bool on) { g_classic_akaze_descriptor = on; }
-void ClassicFeatureFrontEnd::setResidentCapacity(int rows) { g_classic_resident_capacity = rows; }
-
-ClassicFeatureFrontEnd::ClassicFeatureFrontEnd()
-    : ClassicFeatureFrontEnd(DetectorType::ShiTomasi, DescriptorType::ORB, MatcherType::BF, SelectorType::NN, true, 2.0f, 1.0f, 4, true, 120, 392) {}
-
-ClassicFeatureFrontEnd::ClassicFeatureFrontEnd(const DetectorType detector_type, const DescriptorType descriptor_type, const MatcherType matcher_type,
-                                               const SelectorType selector_type, const bool cross_check, const float stereo_threshold,
-                                               const float /*min_disparity*/, const int refinement_degree, const bool verbose, const int input_height,
-                                               const int input_width)
-    : FeatureFrontEnd(detector_type, descriptor_type, matcher_type, selector_type, cross_check, stereo_threshold, stereo_threshold, refinement_degree,
-                      verbose, input_height, input_width) {
-  akaze_descriptor_ = g_classic_akaze_descriptor;   // (initDetector and initDescriptor ask whether the pair runs)
-  initDetector();
-  initDescriptor();
-  initMatcher();
-  resident_ = g_classic_resident;
-  resident_capacity_ = g_classic_resident_capacity;
-  brisk_pair_resident_ = g_classic_brisk_pair_resident;
-}
-
-ClassicFeatureFrontEnd::~ClassicFeatureFrontEnd() {
-  if (ctx_) spvo_destroy(ctx_);
-  ctx_ = nullptr;
-}
-
-#ifdef SPVO_USE_OPENCV
-bool ClassicFeatureFrontEnd::available() { return true; }
-bool ClassicFeatureFrontEnd::pairRuns() const { return true; }
-bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &, cv::Mat &) { return false; }   // (the OpenCV detectors work on the host)
-
-void ClassicFeatureFrontEnd::initDetector() {   // parameters: classic.cpp:7-56
-  if (detector_type_ == DetectorType::ORB) detector_ = cv::ORB::create(2000, 1.2f, 8, 31, 0, 2, cv::ORB::FAST_SCORE, 31, 20);
-  else if (detector_type_ == DetectorType::BRISK) detector_ = cv::BRISK::create();
-  else if (detector_type_ == DetectorType::AKAZE) detector_ = cv::AKAZE::create();
-  else if (detector_type_ == DetectorType::SIFT) detector_ = cv::SIFT::create();
-  else if (detector_type_ == DetectorType::FAST) detector_ = cv::FastFeatureDetector::create(10, true);
-  else if (detector_type_ == DetectorType::ShiTomasi) detector_ = cv::GFTTDetector::create(1000, 0.03, 7.5, 5, false, 0.04);
-  else logError("[initDetector] Detector is not implemented");
-}
-
-void ClassicFeatureFrontEnd::initDescriptor() {   // classic.cpp:58-79
-  if (descriptor_type_ == DescriptorType::ORB) extractor_ = cv::ORB::create();
-  else if (descriptor_type_ == DescriptorType::BRISK) extractor_ = cv::BRISK::create(30, 3, 1.0f);
-  else if (descriptor_type_ == DescriptorType::AKAZE) extractor_ = cv::AKAZE::create();
-  else if (descriptor_type_ == DescriptorType::SIFT) extractor_ = cv::SIFT::create();
-  else logError("[initDescriptor] Decscriptor is not implemented");
-}
-
-std::vector<cv::KeyPoint> ClassicFeatureFrontEnd::detectKeypoints(const cv::Mat &img) {
-  std::vector<cv::KeyPoint> keypoints;
-  if (detector_) detector_->detect(img, keypoints);
-  return keypoints;
-}
-
-cv::Mat ClassicFeatureFrontEnd::describeKeypoints(std::vector<cv::KeyPoint> &keypoints, const cv::Mat &img) {
-  cv::Mat descriptors;
-  if (extractor_) extractor_->compute(img, keypoints, descriptors);
-  return descriptors;
-}
-
-void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, const cv::Mat &projection_matrix_l, const cv::Mat &projection_matrix_r) {
-  if (img_l.rows != img_r.rows || img_l.cols != img_r.cols) {
-    logError("input images shape doesn't match!");
-    return;
-  }
-  projection_matrix_l_ = projection_matrix_l.clone();
-  projection_matrix_r_ = projection_matrix_r.clone();
-  if (input_height_ > 0 && input_width_ > 0) {   // 0 = native resolution (launch/visual_odometry_classic.launch)
-    preprocessImageImpl(img_l, projection_matrix_l_);
-    preprocessImageImpl(img_r, projection_matrix_r_);
-  }
-  cv::Mat *imgs[2] = {&img_l, &img_r};
-  for (cv::Mat *im : imgs) {
-    images_dq.push_back(*im);
-    keypoints_dq.push_back(detectKeypoints(*im));
-    descriptors_dq.push_back(describeKeypoints(keypoints_dq.back(), *im));
-  }
-  if (verbose_) logInfo(std::to_string(keypoints_dq.end()[-2].size()) + ", " + std::to_string(keypoints_dq.end()[-1].size()) + " keypoints for img_l and img_r");
-  while (images_dq.size() > NUM_IMAGE_POSITIONS) {
-    images_dq.pop_front();
-    keypoints_dq.pop_front();
-    descriptors_dq.pop_front();
-  }
-}
-#else
-// Without OpenCV: the detectors that need only a binary descriptor run on the GPU.  ORB + ORB (the reference's baseline
-// configuration, launch/visual_odometry_classic.launch) goes through spvo_orb_detect -- detection and description are one pass
-// there, so detectKeypoints keeps the descriptors for the describeKeypoints call that follows on the same image.  ShiTomasi + ORB
-// (the default constructor) and FAST + ORB go through spvo_gftt_detect / spvo_fast_detect and spvo_orb_describe (classic.cpp:32-47,
-// 66-68, 110-111); the image stays on the device between the two.  SIFT + SIFT goes through spvo_sift_detect, one pass like ORB: float
-// descriptors (n x 128 CV_32F), matched with NORM_L2 by spvo_match_l2.  ShiTomasi + BRISK and FAST + BRISK go through the same detectors and
-// spvo_brisk_describe (cv::BRISK::create(30, 3, 1.0f)->compute, classic.cpp:56-65): 64-byte rows, matched with NORM_HAMMING.  With
-// setDeviceResident every one of these pairs is one submission per stereo pair instead (spvo_classic_detect, kinds 0 .. 4, or
-// spvo_sift_detect_pair) and is matched in its slots -- the BRISK pairs by the 64-byte instantiation of the slot matcher.  BRISK + BRISK
-// goes through spvo_brisk_detect (cv::BRISK::create()->detect, classic.cpp:9-11) and spvo_brisk_describe with the detector's x, y and size,
-// per image: with setDeviceResident alone it takes the per-image path and residentPairs() stays 0; with setBriskPairResident as well it is
-// one spvo_brisk_detect_pair per stereo pair into the same binary slots (64-byte rows), matched there.  AKAZE + BRISK
-// goes through spvo_akaze_detect (cv::AKAZE::create()->detect, classic.cpp:26-28) and spvo_brisk_describe with the detector's x, y and size,
-// per image only: with setDeviceResident it takes the per-image path and residentPairs() stays 0.  AKAZE + AKAZE goes through
-// spvo_akaze_detect and spvo_akaze_describe (cv::AKAZE::create()->compute, classic.cpp:69-70: orientation and the 61-byte MLDB descriptor on
-// the scale space the detector left on the device), per image only as well, and only with setAkazeDescriptor (opt-in): without it the pair
-// is refused as before.  The AKAZE descriptor on any other detector's keypoints stays unavailable -- it needs the level in class_id, and
-// OpenCV's own assertion refuses such keypoints too -- and so does every other mix (BRISK or AKAZE keypoints with an ORB descriptor --
-// spvo_orb_describe refuses fractional coordinates --, SIFT keypoints with an ORB descriptor, ...).
-bool ClassicFeatureFrontEnd::available() { return true; }
-static bool classic_detector_runs(DetectorType d) { return d == DetectorType::ORB || d == DetectorType::ShiTomasi || d == DetectorType::FAST; }
-static bool classic_sift_pair(DetectorType d, DescriptorType e) { return d == DetectorType::SIFT && e == DescriptorType::SIFT; }
-// BRISK is an extractor for given keypoints here (spvo_brisk_describe): it goes with the three detectors that hand keypoints over (AKAZE's
-// carry a size of their own, as the reference lets any detector feed any extractor)
-static bool classic_brisk_pair(DetectorType d, DescriptorType e) {
-  return (d == DetectorType::ShiTomasi || d == DetectorType::FAST || d == DetectorType::AKAZE) && e == DescriptorType::BRISK;
-}
-// ... and with its own detector (spvo_brisk_detect), whose keypoints carry the sizes the pattern was designed for
-static bool classic_brisk_brisk(DetectorType d, DescriptorType e) { return d == DetectorType::BRISK && e == DescriptorType::BRISK; }
-static bool classic_akaze_akaze(DetectorType d, DescriptorType e) { return d == DetectorType::AKAZE && e == DescriptorType::AKAZE; }   // with setAkazeDescriptor only
-static bool classic_pair_runs(DetectorType d, DescriptorType e) {
-  return classic_sift_pair(d, e) || (classic_detector_runs(d) && e == DescriptorType::ORB) || classic_brisk_pair(d, e) || classic_brisk_brisk(d, e);
-}
-bool ClassicFeatureFrontEnd::pairRuns() const {
-  return classic_pair_runs(detector_type_, descriptor_type_) || (akaze_descriptor_ && classic_akaze_akaze(detector_type_, descriptor_type_));
-}
-void ClassicFeatureFrontEnd::initDetector() {
-  if (!classic_detector_runs(detector_type_) && !classic_sift_pair(detector_type_, descriptor_type_) && !classic_brisk_brisk(detector_type_, descriptor_type_) &&
-      !(detector_type_ == DetectorType::AKAZE && classic_brisk_pair(detector_type_, descriptor_type_)) && !(akaze_descriptor_ && classic_akaze_akaze(detector_type_, descriptor_type_)))
-    logError("[initDetector] only ORB, ShiTomasi, FAST, SIFT (with SIFT descriptors), BRISK and AKAZE (with BRISK descriptors) run without OpenCV (build with SPVO_USE_OPENCV for the other detectors of classic.cpp:7-56)");
-}
-void ClassicFeatureFrontEnd::initDescriptor() {
-  if (descriptor_type_ != DescriptorType::ORB && !classic_sift_pair(detector_type_, descriptor_type_) && !classic_brisk_pair(detector_type_, descriptor_type_) &&
-      !classic_brisk_brisk(detector_type_, descriptor_type_) && !(akaze_descriptor_ && classic_akaze_akaze(detector_type_, descriptor_type_)))
-    logError("[initDescriptor] only ORB, BRISK on ShiTomasi / FAST / BRISK / AKAZE keypoints, and SIFT on SIFT keypoints, run without OpenCV (build with SPVO_USE_OPENCV for the other descriptors of classic.cpp:58-79, the AKAZE (MLDB) descriptor among them)");
-}
-
-std::vector<cv::KeyPoint> ClassicFeatureFrontEnd::detectKeypoints(const cv::Mat &img) {
-  std::vector<cv::KeyPoint> keypoints;
-  orb_desc_ = cv::Mat();
-  detected_data_ = nullptr;
-  if (!pairRuns()) {
-    logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB, ShiTomasi and FAST with ORB descriptors, ShiTomasi, FAST, BRISK and AKAZE with BRISK descriptors and SIFT with SIFT descriptors run");
-    return keypoints;
-  }
-  if (!ensureContext()) return keypoints;
-  if (img.depth() != CV_8U || img.rows <= 0) {
-    logError("detectKeypoints: 8-bit single-channel image expected");
-    return keypoints;
-  }
-  if (detector_type_ == DetectorType::SIFT) {
-    // cv::SIFT::create(): detection and description are one pass (spvo_sift_detect), the descriptors wait for describeKeypoints
-    int cap = 4096, n = 0;
-    std::vector<spvo_sift_keypoint> kp;
-    cv::Mat desc;
-    for (;;) {
-      kp.resize((size_t)cap);
-      desc = cv::Mat(cap, 128, CV_32FC1);
-      if (spvo_sift_detect(ctx_, img.ptr<uint8_t>(0), img.rows, img.cols, (size_t)img.step, kp.data(), desc.ptr<float>(0), cap, &n) != SPVO_OK) {
-        logError(std::string("spvo_sift_detect: ") + spvo_last_error(ctx_));
-        return keypoints;
-      }
-      if (n <= cap) break;
-      cap = n;   // more than the buffers held: once more with room for all
-    }
-    keypoints.reserve(n);
-    for (int i = 0; i < n; ++i) {
-      cv::KeyPoint k(cv::Point2f(kp[i].x, kp[i].y), kp[i].size);
-      k.angle = kp[i].angle;
-      k.response = kp[i].response;
-      k.octave = kp[i].octave;
-      keypoints.push_back(k);
-    }
-    orb_desc_ = cv::Mat(n, 128, CV_32FC1);
-    if (n) std::memcpy(orb_desc_.ptr<float>(0), desc.ptr<float>(0), (size_t)n * 128 * sizeof(float));
-    return keypoints;
-  }
-  if (detector_type_ == DetectorType::BRISK) {
-    // cv::BRISK::create(): threshold 30, 3 octaves (classic.cpp:9-11); the image stays on the device for describeKeypoints
-    int cap = 4096, n = 0;
-    std::vector<spvo_brisk_keypoint> kp;
-    for (;;) {
-      kp.resize((size_t)cap);
-      if (spvo_brisk_detect(ctx_, img.ptr<uint8_t>(0), img.rows, img.cols, (size_t)img.step, 30, 3, kp.data(), cap, &n) != SPVO_OK) {
-        logError(std::string("spvo_brisk_detect: ") + spvo_last_error(ctx_));
-        return keypoints;
-      }
-      if (n <= cap) break;
-      cap = n;   // more than the buffer held: once more with room for all
-    }
-    keypoints.reserve(n);
-    for (int i = 0; i < n; ++i) {
-      cv::KeyPoint k(cv::Point2f(kp[i].x, kp[i].y), kp[i].size);
-      k.angle = kp[i].angle;   // -1
-      k.response = kp[i].response;
-      k.octave = kp[i].octave;   // the layer, 0 .. 5
-      keypoints.push_back(k);
-    }
-    detected_data_ = img.data; detected_rows_ = img.rows; detected_cols_ = img.cols;
-    return keypoints;
-  }
-  if (detector_type_ == DetectorType::AKAZE) {
-    // cv::AKAZE::create(): threshold 0.001 (classic.cpp:26-28); the image stays on the device for describeKeypoints.  A second pass of the
-    // loop runs the whole chain again, so the first buffer is generous: the 375 x 1242 sample gives 1442 keypoints
-    int cap = 16384, n = 0;
-    std::vector<spvo_akaze_keypoint> kp;
-    for (;;) {
-      kp.resize((size_t)cap);
-      if (spvo_akaze_detect(ctx_, img.ptr<uint8_t>(0), img.rows, img.cols, (size_t)img.step, 0.001f, kp.data(), cap, &n) != SPVO_OK) {
-        logError(std::string("spvo_akaze_detect: ") + spvo_last_error(ctx_));
-        return keypoints;
-      }
-      if (n <= cap) break;
-      cap = n;   // more than the buffer held: once more with room for all
-    }
-    keypoints.reserve(n);
-    for (int i = 0; i < n; ++i) {
-      cv::KeyPoint k(cv::Point2f(kp[i].x, kp[i].y), kp[i].size);
-      k.angle = kp[i].angle;   // 0: the orientation belongs to the descriptor stage
-      k.response = kp[i].response;
-      k.octave = kp[i].octave;
-      k.class_id = kp[i].class_id;   // the level, 0 .. 15
-      keypoints.push_back(k);
-    }
-    detected_data_ = img.data; detected_rows_ = img.rows; detected_cols_ = img.cols;
-    return keypoints;
-  }
-  if (detector_type_ != DetectorType::ORB) {
-    // cv::GFTTDetector::create(1000, 0.03, 7.5, 5, false, 0.04) / cv::FastFeatureDetector::create(10, true), classic.cpp:32-47
-    const bool gftt = detector_type_ == DetectorType::ShiTomasi;
-    const int cap = gftt ? 1000 : (img.rows / 2 + 1) * (img.cols / 2 + 1);
-    std::vector<float> xy((size_t)cap * 2), resp((size_t)cap);
-    int n = 0;
-    const int rc = gftt ? spvo_gftt_detect(ctx_, img.ptr<uint8_t>(0), img.rows, img.cols, (size_t)img.step, 1000, 0.03, 7.5, 5, xy.data(), resp.data(), cap, &n)
-                        : spvo_fast_detect(ctx_, img.ptr<uint8_t>(0), img.rows, img.cols, (size_t)img.step, 10, 1, xy.data(), resp.data(), cap, &n);
-    if (rc != SPVO_OK) {
-      logError(std::string(gftt ? "spvo_gftt_detect: " : "spvo_fast_detect: ") + spvo_last_error(ctx_));
-      return keypoints;
-    }
-    n = std::min(n, cap);
-    keypoints.reserve(n);
-    for (int i = 0; i < n; ++i) {
-      cv::KeyPoint k(cv::Point2f(xy[2 * i], xy[2 * i + 1]), gftt ? 5.f : 7.f);   // KeyPoint::convert(corners, keypoints, blockSize) / KeyPoint(x, y, 7.f, -1, score)
-      k.angle = -1.f;
-      k.response = resp[i];
-      k.octave = 0;
-      keypoints.push_back(k);
-    }
-    detected_data_ = img.data; detected_rows_ = img.rows; detected_cols_ = img.cols;
-    return keypoints;
-  }
-  constexpr int NFEATURES = 2000;   // classic.cpp:13
-  std::vector<spvo_orb_keypoint> kp(NFEATURES);
-  cv::Mat desc(NFEATURES, 32, CV_8UC1);
-  int n = 0;
-  if (spvo_orb_detect(ctx_, img.ptr<uint8_t>(0), img.rows, img.cols, (size_t)img.step, NFEATURES, kp.data(), desc.ptr<uint8_t>(0), NFEATURES, &n) != SPVO_OK) {
-    logError(std::string("spvo_orb_detect: ") + spvo_last_error(ctx_));
-    return keypoints;
-  }
-  keypoints.reserve(n);
-  float level_scale[8];
-  level_scale[0] = 1.f;
-  for (int l = 1; l < 8; ++l) level_scale[l] = level_scale[l - 1] * 1.2f;
-  for (int i = 0; i < n; ++i) {
-    cv::KeyPoint k(cv::Point2f(kp[i].x, kp[i].y), 31.f * level_scale[kp[i].octave & 7]);
-    k.angle = kp[i].angle * 57.29577951308232f;   // cv::KeyPoint::angle is in degrees
-    if (k.angle < 0) k.angle += 360.f;
-    k.response = kp[i].response;
-    k.octave = kp[i].octave;
-    keypoints.push_back(k);
-  }
-  orb_desc_ = cv::Mat(n, 32, CV_8UC1);
-  if (n) std::memcpy(orb_desc_.ptr<uint8_t>(0), desc.ptr<uint8_t>(0), (size_t)n * 32);
-  return keypoints;
-}
-
-cv::Mat ClassicFeatureFrontEnd::describeKeypoints(std::vector<cv::KeyPoint> &keypoints, const cv::Mat &img) {
-  if (detector_type_ != DetectorType::ORB && classic_detector_runs(detector_type_) && descriptor_type_ == DescriptorType::ORB) {
-    // cv::ORB::create()->compute(img, keypoints, descriptors), classic.cpp:66-68: keypoints too close to a border are ERASED from the
-    // caller's vector (it is passed by non-const reference, classic.cpp:110-111), so keypoints_dq and descriptors_dq stay aligned
-    if (!ensureContext()) return cv::Mat();
-    if (img.depth() != CV_8U || img.rows <= 0) {
-      logError("describeKeypoints: 8-bit single-channel image expected");
-      return cv::Mat();
-    }
-    const int n = (int)keypoints.size();
-    std::vector<float> xy((size_t)n * 2), angle((size_t)n);
-    std::vector<int32_t> kept((size_t)n);
-    for (int i = 0; i < n; ++i) { xy[2 * i] = keypoints[i].pt.x; xy[2 * i + 1] = keypoints[i].pt.y; }
-    cv::Mat desc(n, 32, CV_8UC1);
-    const bool resident = detected_data_ && detected_data_ == img.data && detected_rows_ == img.rows && detected_cols_ == img.cols;
-    int m = 0;
-    if (spvo_orb_describe(ctx_, resident ? nullptr : img.ptr<uint8_t>(0), img.rows, img.cols, (size_t)img.step, xy.data(), n, kept.data(), angle.data(),
-                          n ? desc.ptr<uint8_t>(0) : nullptr, &m) != SPVO_OK) {
-      logError(std::string("spvo_orb_describe: ") + spvo_last_error(ctx_));
-      keypoints.clear();
-      return cv::Mat();
-    }
-    std::vector<cv::KeyPoint> out;
-    out.reserve(m);
-    for (int i = 0; i < m; ++i) {
-      cv::KeyPoint k = keypoints[kept[i]];
-      k.angle = angle[i] * 57.29577951308232f;   // cv::KeyPoint::angle is in degrees
-      if (k.angle < 0) k.angle += 360.f;
-      out.push_back(k);
-    }
-    keypoints.swap(out);
-    cv::Mat d(m, 32, CV_8UC1);
-    if (m) std::memcpy(d.ptr<uint8_t>(0), desc.ptr<uint8_t>(0), (size_t)m * 32);
-    return d;
-  }
-  if (classic_brisk_pair(detector_type_, descriptor_type_) || classic_brisk_brisk(detector_type_, descriptor_type_)) {
-    // cv::BRISK::create(30, 3, 1.0f)->compute(img, keypoints, descriptors), classic.cpp:56-65: every keypoint's own size (5: ShiTomasi, 7: FAST,
-    // 12 x its scale: BRISK, 3 x esigma: AKAZE) picks its scale; the erase-and-angle handling is the ORB branch's (BRISK reports degrees, 0 .. 360), except that
-    // a BRISK keypoint keeps the angle its detector reports (-1)
-    const bool keep_angle = detector_type_ == DetectorType::BRISK;
-    if (!ensureContext()) return cv::Mat();
-    if (img.depth() != CV_8U || img.rows <= 0) {
-      logError("describeKeypoints: 8-bit single-channel image expected");
-      return cv::Mat();
-    }
-    const int n = (int)keypoints.size();
-    std::vector<float> xy((size_t)n * 2), size((size_t)n), angle((size_t)n);
-    std::vector<int32_t> kept((size_t)n);
-    for (int i = 0; i < n; ++i) { xy[2 * i] = keypoints[i].pt.x; xy[2 * i + 1] = keypoints[i].pt.y; size[i] = keypoints[i].size; }
-    cv::Mat desc(n, 64, CV_8UC1);
-    const bool resident = detected_data_ && detected_data_ == img.data && detected_rows_ == img.rows && detected_cols_ == img.cols;
-    int m = 0;
-    if (spvo_brisk_describe(ctx_, resident ? nullptr : img.ptr<uint8_t>(0), img.rows, img.cols, (size_t)img.step, xy.data(), size.data(), n, kept.data(), angle.data(),
-                            n ? desc.ptr<uint8_t>(0) : nullptr, nullptr, &m) != SPVO_OK) {
-      logError(std::string("spvo_brisk_describe: ") + spvo_last_error(ctx_));
-      keypoints.clear();
-      return cv::Mat();
-    }
-    std::vector<cv::KeyPoint> out;
-    out.reserve(m);
-    for (int i = 0; i < m; ++i) {
-      cv::KeyPoint k = keypoints[kept[i]];
-      if (!keep_angle) k.angle = angle[i];
-      out.push_back(k);
-    }
-    keypoints.swap(out);
-    cv::Mat d(m, 64, CV_8UC1);
-    if (m) std::memcpy(d.ptr<uint8_t>(0), desc.ptr<uint8_t>(0), (size_t)m * 64);
-    return d;
-  }
-  if (akaze_descriptor_ && classic_akaze_akaze(detector_type_, descriptor_type_)) {
-    // cv::AKAZE::create()->compute(img, keypoints, descriptors), classic.cpp:69-70: every keypoint gets its main orientation (degrees) and a
-    // 61-byte row; none is erased.  The level comes from class_id, as in OpenCV.  On the image detectKeypoints just saw, the scale space is
-    // still on the device (img = NULL); any other image has it built first.
-    if (!ensureContext()) return cv::Mat();
-    if (img.depth() != CV_8U || img.rows <= 0) {
-      logError("describeKeypoints: 8-bit single-channel image expected");
-      return cv::Mat();
-    }
-    const int n = (int)keypoints.size();
-    std::vector<spvo_akaze_keypoint> kp((size_t)n);
-    std::vector<float> angle((size_t)n);
-    for (int i = 0; i < n; ++i)
-      kp[i] = spvo_akaze_keypoint{keypoints[i].pt.x, keypoints[i].pt.y, keypoints[i].size, keypoints[i].angle, keypoints[i].response, keypoints[i].octave, keypoints[i].class_id};
-    cv::Mat desc(n, SPVO_AKAZE_DESC_BYTES, CV_8UC1);
-    const bool resident = detected_data_ && detected_data_ == img.data && detected_rows_ == img.rows && detected_cols_ == img.cols;
-    if (spvo_akaze_describe(ctx_, resident ? nullptr : img.ptr<uint8_t>(0), img.rows, img.cols, (size_t)img.step, kp.data(), n, angle.data(), n ? desc.ptr<uint8_t>(0) : nullptr) != SPVO_OK) {
-      logError(std::string("spvo_akaze_describe: ") + spvo_last_error(ctx_));
-      keypoints.clear();
-      return cv::Mat();
-    }
-    for (int i = 0; i < n; ++i) keypoints[i].angle = angle[i];
-    return desc;
-  }
-  if (orb_desc_.rows != (int)keypoints.size()) {
-    logError("describeKeypoints: call detectKeypoints on the same image first (ORB and SIFT detect and describe in one pass here)");
-    return cv::Mat();
-  }
-  return orb_desc_;
-}
-
-void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, const cv::Mat &projection_matrix_l, const cv::Mat &projection_matrix_r) {
-  if (img_l.rows != img_r.rows || img_l.cols != img_r.cols) {
-    logError("input images shape doesn't match!");
-    return;
-  }
-  if (!pairRuns()) {
-    logError("ClassicFeatureFrontEnd: this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only ORB, ShiTomasi and FAST with ORB descriptors, ShiTomasi, FAST, BRISK and AKAZE with BRISK descriptors and SIFT with SIFT descriptors run");
-    return;
-  }
-  if (!ensureContext()) return;   // no device: logged, nothing pushed (nn.cpp:53-55 convention)
-  projection_matrix_l_ = projection_matrix_l.clone();
-  projection_matrix_r_ = projection_matrix_r.clone();
-  if (input_height_ > 0 && input_width_ > 0) {   // 0 = native resolution (launch/visual_odometry_classic.launch)
-    preprocessImageImpl(img_l, projection_matrix_l_);
-    preprocessImageImpl(img_r, projection_matrix_r_);
-  }
-  if (!resident_ || !addStereoImagePairResident(img_l, img_r)) {
-    cv::Mat *imgs[2] = {&img_l, &img_r};
-    for (cv::Mat *im : imgs) {
-      images_dq.push_back(*im);
-      keypoints_dq.push_back(detectKeypoints(*im));
-      descriptors_dq.push_back(describeKeypoints(keypoints_dq.back(), *im));
-      if (resident_) bin_slots_dq_.push_back(-1);   // on the host only
-    }
-  }
-  if (verbose_) logInfo(std::to_string(keypoints_dq.end()[-2].size()) + ", " + std::to_string(keypoints_dq.end()[-1].size()) + " keypoints for img_l and img_r");
-  while (images_dq.size() > NUM_IMAGE_POSITIONS) {
-    images_dq.pop_front();
-    keypoints_dq.pop_front();
-    descriptors_dq.pop_front();
-    if (!bin_slots_dq_.empty()) bin_slots_dq_.pop_front();
-  }
-}
-
-// setDeviceResident: the pair through ONE spvo_classic_detect (SIFT: spvo_sift_detect_pair; BRISK + BRISK with setBriskPairResident:
-// spvo_brisk_detect_pair) call into the next slot pair of the ring; the
-// deques are filled from what it hands out, which is what detectKeypoints + describeKeypoints produce image by image.  false: nothing was
-// pushed and the caller takes the per-image path (the pair does not fit its slots, or the call failed and the per-image path reports why).
-bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &img_l, cv::Mat &img_r) {
-  if (img_l.depth() != CV_8U || img_l.rows <= 0 || img_r.depth() != CV_8U || (size_t)img_l.step != (size_t)img_r.step) return false;
-  if (detector_type_ == DetectorType::AKAZE) return false;   // no pair call yet: the per-image path, residentPairs() stays 0
-  if (classic_brisk_brisk(detector_type_, descriptor_type_)) {
-    if (!brisk_pair_resident_) return false;   // opt-in (setBriskPairResident): the per-image path, residentPairs() stays 0
-    if (resident_pairs_ == 0) spvo_set_prematch(ctx_, 1, selector_type_ == SelectorType::KNN ? SPVO_SELECT_KNN : SPVO_SELECT_NN, matcher_cross_check_ ? 1 : 0, knn_threshold_);
-    const int cap = std::max(resident_capacity_, 1);
-    spvo_brisk_features f[2];
-    for (int k = 0; k < 2; ++k) {
-      if (resident_sift_kp_[k].size() != (size_t)cap) { resident_sift_kp_[k].resize((size_t)cap); resident_desc_[k].resize((size_t)cap * 64); }   // first pair only
-      f[k] = spvo_brisk_features{0, resident_sift_kp_[k].data(), resident_desc_[k].data(), cap};
-    }
-    const int slot_l = 2 * (int)(resident_pairs_ % 4), slot_r = slot_l + 1;
-    ++resident_pairs_;
-    // cv::BRISK::create(): threshold 30, 3 octaves, as detectKeypoints
-    const int rc = spvo_brisk_detect_pair(ctx_, img_l.ptr<uint8_t>(0), img_r.ptr<uint8_t>(0), img_l.rows, img_l.cols, (size_t)img_l.step, 30, 3, slot_l, slot_r, resident_capacity_, &f[0], &f[1]);
-    if (rc != SPVO_OK) {
-      if (rc != SPVO_ERR_CAPACITY) logError(std::string("spvo_brisk_detect_pair: ") + spvo_last_error(ctx_));
-      return false;
-    }
-    ++resident_ok_pairs_;
-    cv::Mat *imgs[2] = {&img_l, &img_r};
-    for (int k = 0; k < 2; ++k) {
-      const int n = f[k].n;
-      std::vector<cv::KeyPoint> keypoints;
-      keypoints.reserve(n);
-      for (int i = 0; i < n; ++i) {   // as detectKeypoints + describeKeypoints leave them
-        const spvo_brisk_keypoint &p = resident_sift_kp_[k][i];
-        cv::KeyPoint q(cv::Point2f(p.x, p.y), p.size);
-        q.angle = -1.f;   // describeKeypoints keeps the angle the BRISK detector reports; the record's (the extractor's) stays with the slot
-        q.response = p.response;
-        q.octave = p.octave;   // the layer, 0 .. 5
-        keypoints.push_back(q);
-      }
-      cv::Mat d(n, 64, CV_8UC1);
-      if (n) std::memcpy(d.ptr<uint8_t>(0), resident_desc_[k].data(), (size_t)n * 64);
-      images_dq.push_back(*imgs[k]);
-      keypoints_dq.push_back(std::move(keypoints));
-      descriptors_dq.push_back(d);
-      bin_slots_dq_.push_back(k ? slot_r : slot_l);
-    }
-    return true;
-  }
-  if (detector_type_ == DetectorType::SIFT) {
-    if (resident_pairs_ == 0) spvo_set_prematch(ctx_, 1, selector_type_ == SelectorType::KNN ? SPVO_SELECT_KNN : SPVO_SELECT_NN, matcher_cross_check_ ? 1 : 0, knn_threshold_);
-    const int cap = std::max(resident_capacity_, 1);
-    spvo_sift_features f[2];
-    for (int k = 0; k < 2; ++k) {
-      if (resident_sift_kp_[k].size() != (size_t)cap) { resident_sift_kp_[k].resize((size_t)cap); resident_sift_desc_[k].resize((size_t)cap * 128); }   // first pair only
-      f[k] = spvo_sift_features{0, resident_sift_kp_[k].data(), resident_sift_desc_[k].data(), cap};
-    }
-    const int slot_l = 2 * (int)(resident_pairs_ % 4), slot_r = slot_l + 1;
-    ++resident_pairs_;
-    const int rc = spvo_sift_detect_pair(ctx_, img_l.ptr<uint8_t>(0), img_r.ptr<uint8_t>(0), img_l.rows, img_l.cols, (size_t)img_l.step, slot_l, slot_r, resident_capacity_, &f[0], &f[1]);
-    if (rc != SPVO_OK) {
-      if (rc != SPVO_ERR_CAPACITY) logError(std::string("spvo_sift_detect_pair: ") + spvo_last_error(ctx_));
-      return false;
-    }
-    ++resident_ok_pairs_;
-    cv::Mat *imgs[2] = {&img_l, &img_r};
-    for (int k = 0; k < 2; ++k) {
-      const int n = f[k].n;
-      std::vector<cv::KeyPoint> keypoints;
-      keypoints.reserve(n);
-      for (int i = 0; i < n; ++i) {   // as detectKeypoints
-        const spvo_sift_keypoint &p = resident_sift_kp_[k][i];
-        cv::KeyPoint q(cv::Point2f(p.x, p.y), p.size);
-        q.angle = p.angle;
-        q.response = p.response;
-        q.octave = p.octave;
-        keypoints.push_back(q);
-      }
-      cv::Mat d(n, 128, CV_32FC1);
-      if (n) std::memcpy(d.ptr<float>(0), resident_sift_desc_[k].data(), (size_t)n * 128 * sizeof(float));
-      images_dq.push_back(*imgs[k]);
-      keypoints_dq.push_back(std::move(keypoints));
-      descriptors_dq.push_back(d);
-      bin_slots_dq_.push_back(k ? slot_r : slot_l);
-    }
-    return true;
-  }
-  spvo_classic_opts opts;
-  const bool orb = detector_type_ == DetectorType::ORB, gftt = detector_type_ == DetectorType::ShiTomasi;
-  const bool brisk = classic_brisk_pair(detector_type_, descriptor_type_);
-  const size_t row_bytes = brisk ? 64 : 32;
-  spvo_default_classic_opts(&opts, orb ? SPVO_CLASSIC_ORB : brisk ? (gftt ? SPVO_CLASSIC_GFTT_BRISK : SPVO_CLASSIC_FAST_BRISK) : gftt ? SPVO_CLASSIC_GFTT_ORB : SPVO_CLASSIC_FAST_ORB);
-  opts.slot_capacity = resident_capacity_;
-  if (resident_pairs_ == 0) spvo_set_prematch(ctx_, 1, selector_type_ == SelectorType::KNN ? SPVO_SELECT_KNN : SPVO_SELECT_NN, matcher_cross_check_ ? 1 : 0, knn_threshold_);
-  const int cap = std::max(resident_capacity_, 1);
-  spvo_classic_features f[2];
-  for (int k = 0; k < 2; ++k) {
-    if (resident_kp_[k].size() != (size_t)cap) { resident_kp_[k].resize((size_t)cap); resident_desc_[k].resize((size_t)cap * row_bytes); }   // first pair only
-    f[k] = spvo_classic_features{0, resident_kp_[k].data(), resident_desc_[k].data(), cap};
-  }
-  const int slot_l = 2 * (int)(resident_pairs_ % 4), slot_r = slot_l + 1;
-  ++resident_pairs_;
-  const int rc = spvo_classic_detect(ctx_, &opts, img_l.ptr<uint8_t>(0), img_r.ptr<uint8_t>(0), img_l.rows, img_l.cols, (size_t)img_l.step, slot_l, slot_r, &f[0], &f[1]);
-  if (rc != SPVO_OK) {
-    if (rc != SPVO_ERR_CAPACITY) logError(std::string("spvo_classic_detect: ") + spvo_last_error(ctx_));
-    return false;
-  }
-  ++resident_ok_pairs_;
-  float level_scale[8];
-  level_scale[0] = 1.f;
-  for (int l = 1; l < 8; ++l) level_scale[l] = level_scale[l - 1] * 1.2f;
-  cv::Mat *imgs[2] = {&img_l, &img_r};
-  for (int k = 0; k < 2; ++k) {
-    const int n = f[k].n;
-    std::vector<cv::KeyPoint> keypoints;
-    keypoints.reserve(n);
-    for (int i = 0; i < n; ++i) {
-      const spvo_orb_keypoint &p = resident_kp_[k][i];
-      // size: 31 x the level's scale (ORB) / KeyPoint::convert(corners, keypoints, blockSize) / KeyPoint(x, y, 7.f, -1, score), as detectKeypoints
-      cv::KeyPoint q(cv::Point2f(p.x, p.y), orb ? 31.f * level_scale[p.octave & 7] : gftt ? 5.f : 7.f);
-      if (brisk) {
-        q.angle = p.angle;   // BRISK reports degrees, 0 .. 360: taken as it is, as describeKeypoints does
-      } else {
-        q.angle = p.angle * 57.29577951308232f;   // cv::KeyPoint::angle is in degrees
-        if (q.angle < 0) q.angle += 360.f;
-      }
-      q.response = p.response;
-      q.octave = p.octave;
-      keypoints.push_back(q);
-    }
-    cv::Mat d(n, (int)row_bytes, CV_8UC1);
-    if (n) std::memcpy(d.ptr<uint8_t>(0), resident_desc_[k].data(), (size_t)n * row_bytes);
-    images_dq.push_back(*imgs[k]);
-    keypoints_dq.push_back(std::move(keypoints));
-    descriptors_dq.push_back(d);
-    bin_slots_dq_.push_back(k ? slot_r : slot_l);
-  }
-  return true;
-}
-#endif
-
 // ------------------------------------------------------------------------- SuperPoint front end
 static std::string g_models_dir;
 static int g_max_keypoints = -1, g_match_fp8 = -1;

@@ -318,6 +318,8 @@ protected:
 //////////////////// Classic front end (hpp:184-235, classic.cpp) /////////////////////
 ///////////////////////////////////////////////////////////////////////////////////////
 
+struct ClassicPair;   // a row of the table of pairs that run without OpenCV (feature_detection_classic.cpp)
+
 // The CPU baseline of BASELINE config 1 (ORB / BRISK / AKAZE / SIFT / FAST / GFTT through cv::Feature2D).  Detection,
 // description and Hamming / L2 matching are OpenCV calls on the host, so the class does its work only in a build with
 // SPVO_USE_OPENCV; solveStereoOdometry still runs through the C ABI.  Without OpenCV (this image) the class keeps its
@@ -340,18 +342,14 @@ public:
   std::vector<cv::KeyPoint> detectKeypoints(const cv::Mat &img);
   cv::Mat describeKeypoints(std::vector<cv::KeyPoint> &keypoints, const cv::Mat &img);
   static bool available();   // false in a build without OpenCV
-  // Extension, set like SuperPointFeatureFrontEnd::setMatchFp8: before construction, for the front ends constructed afterwards.  On: a stereo
-  // pair is ONE spvo_classic_detect call into a rolling ring of four binary slot pairs, its features stay on the device and matchDescriptors
-  // runs spvo_match_hamming_slots on them, the two standard matches enqueued with the detector (spvo_set_prematch).  keypoints_dq,
-  // descriptors_dq and every match are what they are with the option off (the default).  A pair with more rows than the slots hold
-  // (setResidentCapacity; SPVO_ERR_CAPACITY) goes through the per-image path and is matched from the host matrices.  SIFT + SIFT does
-  // the same through spvo_sift_detect_pair, the SIFT slots and spvo_match_l2_slots; ShiTomasi + BRISK and FAST + BRISK through the two BRISK
-  // kinds of spvo_classic_detect (64-byte rows in the same binary slots).  BRISK + BRISK takes the per-image path under setDeviceResident
-  // alone; with setBriskPairResident as well (opt-in, read at construction like the other two) it goes through spvo_brisk_detect_pair into
-  // the same binary slots.  AKAZE keypoints take the per-image path whatever is set.
-  // setAkazeDescriptor (opt-in, read at construction like the others): AKAZE + AKAZE runs, through spvo_akaze_detect and
-  // spvo_akaze_describe (cv::AKAZE::create()->compute: orientation + the 61-byte MLDB descriptor), per image.  Off, that pair is refused
-  // as every pair that does not run is.
+  // Extensions, set like SuperPointFeatureFrontEnd::setMatchFp8: before construction, for the front ends constructed afterwards.  Which pairs
+  // they apply to is the table's to say (kClassicPairs, feature_detection_classic.cpp: a pair's resident route and the opt-in it needs).
+  // setDeviceResident: a stereo pair is ONE call of its route into a rolling ring of four slot pairs, its features stay on the device and
+  // matchDescriptors matches them there, the two standard matches enqueued with the detector (spvo_set_prematch).  keypoints_dq, descriptors_dq
+  // and every match are what they are with the option off (the default).  A pair with more rows than the slots hold (setResidentCapacity;
+  // SPVO_ERR_CAPACITY), and every pair without a route, goes through the per-image path and is matched from the host matrices.
+  // setBriskPairResident: BRISK + BRISK takes its route only with this as well.  setAkazeDescriptor: AKAZE + AKAZE runs (per image); off,
+  // that pair is refused as every pair that does not run is.
   static void setDeviceResident(bool on);
   static void setResidentCapacity(int rows);   // rows per binary slot [8192]
   static void setBriskPairResident(bool on);   // [off]
@@ -365,19 +363,20 @@ private:
   bool akaze_descriptor_ = false;      // setAkazeDescriptor at construction
   bool pairRuns() const;               // this detector / descriptor pair runs in this build
   int resident_capacity_ = 8192;
-  unsigned resident_pairs_ = 0;   // pairs handed to spvo_classic_detect: pair k lives in slots 2 (k % 4), 2 (k % 4) + 1
+  unsigned resident_pairs_ = 0;   // pairs handed to a resident route: pair k lives in slots 2 (k % 4), 2 (k % 4) + 1
   unsigned resident_ok_pairs_ = 0;   // ... of which the call returned SPVO_OK (residentPairs)
-  std::vector<spvo_orb_keypoint> resident_kp_[2];   // what spvo_classic_detect hands out, resident_capacity_ rows per image: allocated once
-  std::vector<uint8_t> resident_desc_[2];           // (rows of 32 bytes, of 64 with a BRISK descriptor)
-  std::vector<spvo_sift_keypoint> resident_sift_kp_[2];   // the same for spvo_sift_detect_pair, and for spvo_brisk_detect_pair's records (the same layout; its rows: resident_desc_)
-  std::vector<float> resident_sift_desc_[2];
   bool addStereoImagePairResident(cv::Mat &img_l, cv::Mat &img_r);
 #ifdef SPVO_USE_OPENCV
   cv::Ptr<cv::FeatureDetector> detector_;
   cv::Ptr<cv::DescriptorExtractor> extractor_;
 #else
+  const ClassicPair *pair() const;   // the table's row of this detector / descriptor pair, nullptr for one that does not run
+  // what a resident route hands out for one image -- resident_capacity_ keypoint records and descriptor rows of the pair's sizes: allocated once
+  struct Staging { std::vector<uint8_t> records, rows; };
+  Staging staging_[2];
+  template <class Features, class Call> bool residentPair(const ClassicPair &pair, cv::Mat &img_l, cv::Mat &img_r, const char *name, Call call);
   cv::Mat orb_desc_;   // descriptors of the image detectKeypoints saw last (spvo_orb_detect / spvo_sift_detect: one pass for both)
-  // ShiTomasi / FAST: the image detectKeypoints saw last is still on the device; describeKeypoints on the same image does not upload it again
+  // the image detectKeypoints saw last is still on the device (unless it was described in the same pass); describeKeypoints on the same image does not upload it again
   const void *detected_data_ = nullptr;
   int detected_rows_ = 0, detected_cols_ = 0;
 #endif

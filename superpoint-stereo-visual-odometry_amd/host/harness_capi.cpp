@@ -296,24 +296,24 @@ int spvo_host_classic_pair_probe(const char *detector_name, const char *descript
 // (launch/visual_odometry_classic.launch); otherwise preprocessImageImpl runs first (classic.cpp:96-100).
 // poses: n x 7 (q xyzw, t of cam0_curr_T_cam0_prev; identity for frame 0); stats: n x 4 (keypoints left, right, stereo matches,
 // PnP inliers); seconds: wall time of frames warm .. n-1.  Returns the number of frames processed, negative on failure.
-// digest (may be NULL): n x 8 FNV-1a sums of what a frame left in the front end -- keypoints left, descriptors left, keypoints right, descriptors
-// right, the stereo matches, the temporal matches, the previous frame's stereo matches (the third list) and the map derived from them, the two
-// inlier sets -- so that two runs can be compared for identity without shipping every deque entry.  Computed inside the timed loop: a run
-// with digests is not a frame-rate measurement.
+// digest (may be NULL): n x 8 FNV-1a sums of what a frame left in the front end -- keypoints left (every field, class_id included), descriptors left
+// (every byte of every row: cols x element size), keypoints right, descriptors right, the stereo matches, the temporal matches, the previous
+// frame's stereo matches (the third list) and the map derived from them, the two inlier sets -- so that two runs can be compared for identity
+// without shipping every deque entry.  Computed inside the timed loop: a run with digests is not a frame-rate measurement.
 static void fnv(uint64_t &h, const void *p, size_t n) {
   const unsigned char *b = static_cast<const unsigned char *>(p);
   for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; }
 }
 static uint64_t digest_keypoints(const std::vector<cv::KeyPoint> &v) {
   uint64_t h = 1469598103934665603ull;
-  for (const cv::KeyPoint &k : v) { fnv(h, &k.pt.x, 4); fnv(h, &k.pt.y, 4); fnv(h, &k.size, 4); fnv(h, &k.angle, 4); fnv(h, &k.response, 4); fnv(h, &k.octave, 4); }
+  for (const cv::KeyPoint &k : v) { fnv(h, &k.pt.x, 4); fnv(h, &k.pt.y, 4); fnv(h, &k.size, 4); fnv(h, &k.angle, 4); fnv(h, &k.response, 4); fnv(h, &k.octave, 4); fnv(h, &k.class_id, 4); }
   const size_t n = v.size();
   fnv(h, &n, sizeof n);
   return h;
 }
 static uint64_t digest_rows(const cv::Mat &m) {
   uint64_t h = 1469598103934665603ull;
-  for (int r = 0; r < m.rows; ++r) fnv(h, m.ptr<uint8_t>(r), (size_t)m.cols);
+  for (int r = 0; r < m.rows; ++r) fnv(h, m.ptr<uint8_t>(r), (size_t)m.cols * m.elemSize());
   fnv(h, &m.rows, sizeof m.rows);
   return h;
 }

@@ -166,7 +166,7 @@ def test_host_library_and_a_node_like_caller_compile_against_both_type_sets(open
     if not shutil.which("g++"):
         pytest.skip("no g++")
     flags = ["-DSPVO_USE_OPENCV", "-I" + os.path.join(ROOT, "tests", "mock_ros")] if opencv else []
-    for src in ("feature_detection.cpp", "vo_io.cpp", "harness_capi.cpp", os.path.join(ROOT, "tests", "boundary_node_caller.cpp")):
+    for src in ("feature_detection.cpp", "feature_detection_classic.cpp", "vo_io.cpp", "harness_capi.cpp", os.path.join(ROOT, "tests", "boundary_node_caller.cpp")):
         path = src if os.path.isabs(src) else os.path.join(HOST, src)
         r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Werror", "-I" + HOST] + flags + [path],
                            capture_output=True, text=True)
