@@ -342,7 +342,8 @@ int spvo_brisk_detect(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, siz
 /* A layer of the scale space of this context's last spvo_brisk_detect (test hook): what = 0 the layer's image, 1 its AGAST 9-16 score map,
  * 2 (layer 0 only) the 5-8 score map.  `out` (rows x cols bytes) may be NULL to ask for the shape only.  SPVO_ERR_STATE when no result is
  * resident: no call yet, or any other call has since put an image into the context's resident image buffer (spvo_gftt_detect,
- * spvo_fast_detect, spvo_orb_describe / spvo_brisk_describe with an image, spvo_classic_detect, spvo_brisk_detect_pair), the same image
+ * spvo_fast_detect, spvo_orb_describe / spvo_brisk_describe with an image, spvo_classic_detect, spvo_brisk_detect_pair,
+ * spvo_akaze_detect_pair), the same image
  * included. */
 int spvo_brisk_detect_debug_layer(spvo_ctx *ctx, int layer, int what, uint8_t *out, int *rows, int *cols);
 
@@ -411,8 +412,8 @@ int spvo_akaze_describe(spvo_ctx *ctx, const uint8_t *img /* or NULL */, int row
  * staging, the whole chain of both is enqueued without a host round trip -- for the two non-ORB kinds the keypoints go from the
  * detector to the extractor on the device, the extractor's border rule being an order-preserving compaction there -- and the call
  * waits once for the result, the features (before that, for whatever an earlier call left running on the solver's stream: its staging is reused).  They are left in two BINARY FEATURE SLOTS (0 .. 9; separate from the float slots of spvo_detect*,
- * used as a ring of pairs like those): keypoint records, descriptor rows (32 bytes; 64 for the two BRISK kinds -- a slot remembers its
- * row width) and the row count stay on the device for spvo_match_hamming_slots.  What the host receives equals, byte for byte, what spvo_orb_detect -- or spvo_gftt_detect /
+ * used as a ring of pairs like those): keypoint records, descriptor rows (32 bytes; 64 for the two BRISK kinds; 61 for
+ * spvo_akaze_detect_pair, stored in 64 -- a slot remembers its row width) and the row count stay on the device for spvo_match_hamming_slots.  What the host receives equals, byte for byte, what spvo_orb_detect -- or spvo_gftt_detect /
  * spvo_fast_detect followed by spvo_orb_describe(img = NULL) -- returns for the same image and parameters; for the two non-ORB kinds a
  * record carries the extractor's angle (radians), the DETECTOR's response and octave 0.
  * The two BRISK kinds (SPVO_CLASSIC_GFTT_BRISK, SPVO_CLASSIC_FAST_BRISK): the detector's list stays on the device, the BRISK border rule
@@ -429,7 +430,7 @@ int spvo_akaze_describe(spvo_ctx *ctx, const uint8_t *img /* or NULL */, int row
  *                      BRISK kinds also rows * cols * 255 >= 2^31: the int32 integral image)
  * With spvo_set_prematch enabled the two standard matches (slot_l -> slot_r, slot_l -> the previous call's slot_l) are enqueued in the
  * same submission behind the features; the call does not wait for them.  A previous left slot of the other row width has no temporal
- * match: it is skipped, not an error. */
+ * match: it is skipped, not an error (so is a slot of 61-byte rows that spvo_akaze_detect_pair filled). */
 typedef enum { SPVO_CLASSIC_ORB = 0, SPVO_CLASSIC_GFTT_ORB = 1, SPVO_CLASSIC_FAST_ORB = 2, SPVO_CLASSIC_GFTT_BRISK = 3, SPVO_CLASSIC_FAST_BRISK = 4 } spvo_classic_kind;
 typedef struct {
   int kind;                               /* spvo_classic_kind */
@@ -448,7 +449,7 @@ int spvo_classic_detect(spvo_ctx *ctx, const spvo_classic_opts *opts, const uint
  * images of a stereo pair): an entry point of its own, because a BRISK keypoint carries a size and spvo_classic_features' 20-byte records
  * have no room for one.  It fills the same ring of ten BINARY slots with 64-byte rows, so spvo_match_hamming_slots, spvo_classic_slot_rows
  * and spvo_set_prematch serve it as they serve spvo_classic_detect, and the temporal partner is shared with that call: any filled slot of
- * 64-byte rows is one, a 32-byte one is skipped.  Both images go up through the pinned staging; per image the detector's chain, ONE
+ * 64-byte rows is one, a 32-byte or a 61-byte one is skipped.  Both images go up through the pinned staging; per image the detector's chain, ONE
  * order-preserving compaction that applies the detector's keep flag and the extractor's border rule at every keypoint's OWN scale index,
  * the extractor and a finishing kernel are enqueued without a host round trip, and the call waits once.  Per image the host receives, byte
  * for byte, what spvo_brisk_detect(img, threshold, octaves) followed by spvo_brisk_describe(img = NULL, the x, y and size of those
@@ -465,6 +466,39 @@ typedef struct { int n; spvo_brisk_keypoint *kp; uint8_t *desc /* [cap][64] */; 
 int spvo_brisk_detect_pair(spvo_ctx *ctx, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride,
                            int threshold, int octaves, int slot_l, int slot_r, int slot_capacity,
                            spvo_brisk_features *out_l, spvo_brisk_features *out_r);
+/* The same for AKAZE keypoints with AKAZE descriptors (detectKeypoints + describeKeypoints of ClassicFeatureFrontEnd(AKAZE, AKAZE) for both
+ * images of a stereo pair).  It fills the same ring of ten BINARY slots with 61-byte rows: a slot stores such a row in the 16 words the
+ * matcher's wide kernel reads, bytes 61 .. 63 zero, which changes no distance, and remembers the width 61.  spvo_match_hamming_slots,
+ * spvo_classic_slot_rows and spvo_set_prematch serve it as they serve spvo_classic_detect; the temporal partner is any filled slot of
+ * 61-byte rows, a slot of another width (ORB's 32, BRISK's 64) is skipped.  Both images go up through the pinned staging; per image the
+ * scale space and the candidates of spvo_akaze_detect, the order-dependent suppression between candidates ON THE DEVICE (one wave walks
+ * the candidates in order and scans the list by ballots, one thread per entry runs the second pass, an order-preserving compaction keeps
+ * the survivors whose offsets passed), spvo_akaze_describe's kernel on those records with the count read on the device, and a finishing
+ * kernel are enqueued without a host round trip, left image first, and the call waits once.  Per image the host receives, byte for byte,
+ * what spvo_akaze_detect(img, threshold) followed by spvo_akaze_describe(img = NULL, those keypoints) returns: the records in the
+ * detector's order with `angle` replaced by the descriptor's (degrees), the packed 61-byte rows; out->n is the count, of which
+ * min(n, cap) rows are written.  The slot's own record array holds (x, y, that angle, response, level).
+ * Afterwards the context's resident image and scale space are the RIGHT image's: spvo_akaze_describe(img = NULL),
+ * spvo_brisk_describe(img = NULL), spvo_akaze_debug_level and spvo_akaze_last_contrast answer for it.
+ * The suppression is quadratic in the candidates in the worst case, as spvo_akaze_detect's host loop is.
+ *   SPVO_ERR_INVALID   NULL arguments, cap < 0, bad or equal slots, slot_capacity outside 1 .. 2^22, whatever spvo_akaze_detect refuses
+ *   SPVO_ERR_STATE     a spvo_detect*_submit is in flight (outputs and slots stay as they were); the candidate list overflowed (a
+ *                      defect, not an input: spvo_akaze_detect)
+ *   SPVO_ERR_CAPACITY  an image yields more rows than slot_capacity: out_*->n report both counts, both slots are left unfilled, nothing
+ *                      is truncated (spvo_classic_detect's rule; so is the re-allocation by a larger slot_capacity than any before) */
+typedef struct { int n; spvo_akaze_keypoint *kp; uint8_t *desc /* [cap][61] */; int cap; } spvo_akaze_features;   /* n: out; min(n, cap) rows are written; kp, desc may be NULL */
+int spvo_akaze_detect_pair(spvo_ctx *ctx, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride,
+                           float threshold, int slot_l, int slot_r, int slot_capacity,
+                           spvo_akaze_features *out_l, spvo_akaze_features *out_r);
+/* The device suppression of spvo_akaze_detect_pair on a caller's candidate list (test hook: images do not reach a slot replaced twice,
+ * a removal by the second pass or a candidate whose offsets failed): exactly those kernels, for the level tables of a rows x cols image
+ * and no image.  `cand` lists the candidates as the detector would, level by level; `keep` receives the indices of those that stay, in
+ * output order, `n_keep` their number (a candidate with ok = 0 suppresses others and is dropped at the end).  A resident scale space is
+ * not touched.  SPVO_ERR_INVALID for a level the shape does not have, for levels that are not non-decreasing along the list and for a
+ * shape smaller than 16 x 16; SPVO_ERR_STATE beside a spvo_detect*_submit in flight. */
+typedef struct { int32_t level, row, col; float response; int32_t ok; } spvo_akaze_candidate;
+int spvo_akaze_suppress_debug(spvo_ctx *ctx, int rows, int cols, const spvo_akaze_candidate *cand, int n,
+                              int32_t *keep /* [n] */, int *n_keep);
 /* rows a binary feature slot holds; SPVO_ERR_STATE for one that holds nothing (never filled, or left unfilled by SPVO_ERR_CAPACITY) */
 int spvo_classic_slot_rows(spvo_ctx *ctx, int slot, int *n);
 /* Caller-supplied rows into a binary slot (test hook: images cannot produce the rows the matcher's key layout has to survive --
@@ -495,8 +529,8 @@ int spvo_match_slots(spvo_ctx *ctx, int slot_a, int slot_b, int selector, int cr
 /* spvo_match_hamming on the device-resident rows of two BINARY feature slots (spvo_classic_detect): nothing is packed or uploaded,
  * the kernel reads both row counts on the device.  Results equal spvo_match_hamming on the host copies of the two slots, index for
  * index and distance for distance.  Returns the result stored by spvo_classic_detect when spvo_set_prematch is on and this is exactly
- * that match of exactly those slot contents.  Two slots of 64-byte rows (the BRISK kinds) are matched by the same kernel built for rows
- * of 16 words; slots of different widths: SPVO_ERR_INVALID, the message names both.  SPVO_ERR_STATE for a slot that holds nothing; spvo_match_slots on a binary slot number
+ * that match of exactly those slot contents.  Two slots of rows wider than 32 bytes (BRISK's 64, AKAZE's 61 with three zero bytes behind) are matched by the same kernel built for rows
+ * of 16 words; slots of different widths (a 61-byte slot against a 64-byte one included): SPVO_ERR_INVALID, the message names both.  SPVO_ERR_STATE for a slot that holds nothing; spvo_match_slots on a binary slot number
  * means the FLOAT slot of that number, as before. */
 int spvo_match_hamming_slots(spvo_ctx *ctx, int slot_a, int slot_b, int selector, int cross_check, float ratio,
                              int32_t *train_idx, float *distance);

@@ -90,7 +90,11 @@ __device__ __forceinline__ int akaze_inside(float yr, float xr, int h, int w) {
   return (int)yr * w + (int)xr;
 }
 
-__global__ __launch_bounds__(64) void akaze_describe_kernel(const AkazeLevels lv, const AkazeKp *__restrict__ kp, int n, float *__restrict__ angle, uint8_t *__restrict__ desc) {
+// n_ptr == NULL: the n records of the host's list.  Otherwise the list was left on the device (spvo_akaze_detect_pair) and the first
+// min(*n_ptr, n) records are described, n being what the buffers hold.
+__global__ __launch_bounds__(64) void akaze_describe_kernel(const AkazeLevels lv, const AkazeKp *__restrict__ kp, int n, const int *__restrict__ n_ptr, float *__restrict__ angle,
+                                                            uint8_t *__restrict__ desc) {
+  if (n_ptr) n = min(n, *n_ptr);
   __shared__ float s_rx[AKAZE_ORI_SAMPLES], s_ry[AKAZE_ORI_SAMPLES], s_ang[AKAZE_ORI_SAMPLES], s_val[3 * AKAZE_MLDB_CELLS];
   const int lane = threadIdx.x;
   const AkazeMldbTab &T = akaze_mldb_tab;

@@ -1,12 +1,15 @@
 // spvo_akaze.hip -- the classic front end's AKAZE keypoint detector (akaze.hip.h): the tables of a shape (levels, FED step sizes, Gaussian
 // taps: built on the host by the formulas tests/akaze_ref.py lists, spvo_akaze_tables), the chain of launches of spvo_akaze_detect, the
 // order-dependent suppression between candidates on the host (rule 11: the restatement's loop over the copied candidate list), the
-// test hooks, and spvo_akaze_describe (akaze_mldb.hip.h: orientation and MLDB descriptor on the scale space that chain leaves resident).
+// test hooks, spvo_akaze_describe (akaze_mldb.hip.h: orientation and MLDB descriptor on the scale space that chain leaves resident), and
+// spvo_akaze_detect_pair (detector + descriptor of a stereo pair in one submission into two binary slots of 61-byte rows, by
+// spvo_classic_detect's resident-pair protocol, with rule 11 on the device: akaze_suppress.hip.h).
 // Runs on the solver's stream (stream2) with the image resident in spvo_ctx::cls -- it stays there for a spvo_brisk_describe(img = NULL)
 // that follows -- and owns everything else it needs (spvo_ctx::akaze).
 #include "spvo_internal.hip.h"
 #include "akaze.hip.h"
 #include "akaze_mldb.hip.h"
+#include "akaze_suppress.hip.h"
 
 namespace {
 constexpr int AK_SUBLEVELS = 4;
@@ -198,10 +201,15 @@ void ak_suppress(const AkazeLevels &lv, const std::vector<AkazeCand> &cd, std::v
 }
 // The chain both entry points share: the image into spvo_ctx::cls, the layout of its shape, and every launch up to rule 9 (all six planes
 // of every level), enqueued on the solver's stream.  The caller waits, and marks the result resident with ak_mark_resident.
+int ak_scale_enqueue(spvo_ctx *c, int rows, int cols);
 int ak_scale_space(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride) {
-  hipStream_t st = c->stream2;
   if (int rc = classic_upload_image(c, img, rows, cols, stride)) return rc;
   if (int rc = ak_ensure(c, rows, cols)) return rc;
+  return ak_scale_enqueue(c, rows, cols);
+}
+// the launches of that chain on the image resident in spvo_ctx::cls (ak_ensure has run for its shape)
+int ak_scale_enqueue(spvo_ctx *c, int rows, int cols) {
+  hipStream_t st = c->stream2;
   auto &d = c->akaze;
   const AkazeLevels &lv = d.lv;
   const size_t px0 = align64((size_t)rows * cols);
@@ -268,12 +276,63 @@ bool ak_resident(const spvo_ctx *c) {
   const auto &d = c->akaze;
   return d.valid && d.image_gen == c->cls.image_gen && c->cls.rows == d.rows && c->cls.cols == d.cols;
 }
+
+// what spvo_akaze_detect refuses of its parameters and of the image shape (`who` names the entry point in the error text)
+int ak_check(spvo_ctx *c, const char *who, int rows, int cols, float threshold) {
+  if (!std::isfinite(threshold) || !(threshold > 0.f)) return fail(c, SPVO_ERR_INVALID, "%s: the threshold must be finite and positive", who);
+  if (rows < 16 || cols < 16) return fail(c, SPVO_ERR_INVALID, "%s: images of at least 16 x 16 only", who);
+  return brisk_check_image(c, who, rows, cols);
+}
+
+// the descriptor's record, angle and row buffers for n keypoints
+int ak_kp_ensure(spvo_ctx *c, int n) {
+  auto &d = c->akaze;
+  if (n <= d.kp_cap) return SPVO_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream2));
+  dev_free(d.d_kp, d.d_angle, d.d_desc);
+  d.kp_cap = 0;
+  const int cap = std::max(n, 1024);
+  int rc;
+  if ((rc = dev_alloc(c, &d.d_kp, (size_t)cap, false)) || (rc = dev_alloc(c, &d.d_angle, (size_t)cap, false)) || (rc = dev_alloc(c, &d.d_desc, (size_t)cap * AKAZE_MLDB_BYTES, false))) return rc;
+  d.kp_cap = cap;
+  return SPVO_OK;
+}
+
+// the buffers of the device suppression for lists of n candidates
+int ak_sup_ensure(spvo_ctx *c, int n) {
+  auto &d = c->akaze;
+  if (!d.sup_cnt) {
+    if (int rc = dev_alloc(c, &d.sup_cnt, AKAZE_SUP_INTS)) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
+  }
+  if (n <= d.sup_cap) return SPVO_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream2));
+  dev_free(d.sup_list, d.sup_idx, d.sup_keep, d.sup_src, d.sup_kp);
+  d.sup_cap = 0;
+  const size_t cap = (size_t)std::max(n, 1024);
+  int rc;
+  if ((rc = dev_alloc(c, &d.sup_list, cap, false)) || (rc = dev_alloc(c, &d.sup_idx, cap, false)) || (rc = dev_alloc(c, &d.sup_keep, cap, false)) || (rc = dev_alloc(c, &d.sup_src, cap, false)) ||
+      (rc = dev_alloc(c, &d.sup_kp, cap, false)))
+    return rc;
+  d.sup_cap = (int)cap;
+  return SPVO_OK;
+}
+
+// rule 11 and rule 13's flag on the device: the candidates rec[0 .. min(*n_ptr, cap)) -> sup_kp / sup_src, their number in
+// sup_cnt[AKAZE_SUP_KEPT] (ak_sup_ensure(cap) has run; only esigma of lv's levels is read)
+void ak_suppress_enqueue(spvo_ctx *c, const AkazeLevels &lv, const AkazeCand *rec, const int *n_ptr, int cap) {
+  auto &d = c->akaze;
+  hipStream_t st = c->stream2;
+  hipLaunchKernelGGL(akaze_suppress_first_kernel, dim3(1), dim3(64), 0, st, lv, rec, n_ptr, cap, d.sup_list, d.sup_idx, d.sup_cnt);
+  hipLaunchKernelGGL(akaze_suppress_second_kernel, dim3(std::min((cap + 255) / 256, 256)), dim3(256), 0, st, lv, rec, d.sup_list, d.sup_idx, d.sup_cnt, cap, d.sup_keep);
+  hipLaunchKernelGGL(akaze_suppress_compact_kernel, dim3(1), dim3(1024), 0, st, rec, d.sup_idx, d.sup_keep, cap, d.sup_cnt, d.sup_kp, d.sup_src);
+}
 }  // namespace
 
 void spvo_int::akaze_release(spvo_ctx *c) {
   auto &d = c->akaze;
-  dev_free(d.planes, d.scratch, d.tabs, d.keys, d.rank, d.rec, d.stat, d.d_kp, d.d_angle, d.d_desc);
-  d.plane_cap = d.scratch_cap = d.tab_cap = 0; d.cand_cap = d.kp_cap = 0; d.rows = d.cols = 0; d.valid = false;
+  dev_free(d.planes, d.scratch, d.tabs, d.keys, d.rank, d.rec, d.stat, d.d_kp, d.d_angle, d.d_desc, d.sup_list, d.sup_idx, d.sup_keep, d.sup_src, d.sup_cnt, d.sup_kp);
+  d.plane_cap = d.scratch_cap = d.tab_cap = 0; d.cand_cap = d.kp_cap = d.sup_cap = 0; d.rows = d.cols = 0; d.valid = false;
 }
 
 extern "C" {
@@ -388,18 +447,10 @@ int spvo_akaze_describe(spvo_ctx *c, const uint8_t *img, int rows, int cols, siz
     ak_mark_resident(c, stat);
   }
   if (n == 0) return SPVO_OK;
-  if (n > d.kp_cap) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    dev_free(d.d_kp, d.d_angle, d.d_desc);
-    d.kp_cap = 0;
-    const int cap = std::max(n, 1024);
-    int rc;
-    if ((rc = dev_alloc(c, &d.d_kp, (size_t)cap, false)) || (rc = dev_alloc(c, &d.d_angle, (size_t)cap, false)) || (rc = dev_alloc(c, &d.d_desc, (size_t)cap * AKAZE_MLDB_BYTES, false))) return rc;
-    d.kp_cap = cap;
-  }
+  if (int rc = ak_kp_ensure(c, n)) return rc;
   static_assert(sizeof(spvo_akaze_keypoint) == sizeof(AkazeKp) && SPVO_AKAZE_DESC_BYTES == AKAZE_MLDB_BYTES, "record layout");
   HIP_TRY(c, hipMemcpyAsync(d.d_kp, kp, (size_t)n * sizeof(AkazeKp), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(akaze_describe_kernel, dim3(std::min(n, 4096)), dim3(64), 0, st, d.lv, d.d_kp, n, d.d_angle, d.d_desc);
+  hipLaunchKernelGGL(akaze_describe_kernel, dim3(std::min(n, 4096)), dim3(64), 0, st, d.lv, d.d_kp, n, (const int *)nullptr, d.d_angle, d.d_desc);
   HIP_TRY(c, hipGetLastError());
   // into staging first: a failure below leaves the caller's buffers as they were
   d.h_angle.resize((size_t)n);
@@ -409,6 +460,149 @@ int spvo_akaze_describe(spvo_ctx *c, const uint8_t *img, int rows, int cols, siz
   HIP_TRY(c, hipStreamSynchronize(st));
   std::memcpy(angle, d.h_angle.data(), (size_t)n * sizeof(float));
   std::memcpy(desc, d.h_desc.data(), (size_t)n * AKAZE_MLDB_BYTES);
+  return SPVO_OK;
+}
+
+// Rule 11 on the device for a caller's candidate list (test hook): exactly the kernels spvo_akaze_detect_pair runs behind
+// akaze_refine_kernel, on records built from (level, row, col, response, ok) and the level tables of a rows x cols image.  Nothing of a
+// resident scale space is touched.
+int spvo_akaze_suppress_debug(spvo_ctx *c, int rows, int cols, const spvo_akaze_candidate *cand, int n, int32_t *keep, int *n_keep) {
+  if (!c || !n_keep || n < 0 || (n > 0 && (!cand || !keep))) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  *n_keep = 0;
+  if (rows < 16 || cols < 16) return fail(c, SPVO_ERR_INVALID, "spvo_akaze_suppress_debug: images of at least 16 x 16 only");
+  const AkTables T = make_tables(rows, cols);
+  std::vector<AkazeCand> h((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const spvo_akaze_candidate &p = cand[i];
+    if (p.level < 0 || p.level >= T.n) return fail(c, SPVO_ERR_INVALID, "spvo_akaze_suppress_debug: candidate %d has level %d; the scale space of this shape has %d levels", i, p.level, T.n);
+    if (i > 0 && p.level < cand[i - 1].level) return fail(c, SPVO_ERR_INVALID, "spvo_akaze_suppress_debug: candidate %d has level %d behind level %d (the list goes level by level)", i, p.level, cand[i - 1].level);
+    h[i] = AkazeCand{0.f, 0.f, 0.f, 0.f, p.response, T.octave[p.level], p.level, p.row, p.col, p.ok ? 1 : 0};
+  }
+  if (int rc = require_idle(c)) return rc;
+  if (n == 0) return SPVO_OK;
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = c->stream2;
+  auto &d = c->akaze;
+  if (int rc = ak_sup_ensure(c, n)) return rc;
+  AkazeLevels lv{};
+  lv.n = T.n;
+  for (int i = 0; i < T.n; ++i) { lv.l[i].octave = T.octave[i]; lv.l[i].esigma = T.esigma[i]; }
+  AkazeCand *rec = nullptr;
+  if (int rc = dev_alloc(c, &rec, (size_t)n, false)) return rc;
+  int cnt[AKAZE_SUP_INTS] = {0, 0, n, 0};
+  std::vector<int> src((size_t)n);
+  hipError_t e = hipMemcpyAsync(rec, h.data(), (size_t)n * sizeof(AkazeCand), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d.sup_cnt, cnt, sizeof cnt, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    ak_suppress_enqueue(c, lv, rec, d.sup_cnt + 2, n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(cnt, d.sup_cnt, sizeof cnt, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(src.data(), d.sup_src, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st);
+  const hipError_t e2 = hipStreamSynchronize(st);
+  dev_free(rec);
+  HIP_TRY(c, e);
+  HIP_TRY(c, e2);
+  const int m = std::min(std::max(cnt[AKAZE_SUP_KEPT], 0), n);
+  std::memcpy(keep, src.data(), (size_t)m * sizeof(int));
+  *n_keep = m;
+  return SPVO_OK;
+}
+
+// One submission per stereo pair: spvo_brisk_detect_pair's protocol (PairStage, slot_rewrite, the prematch cache) around the detector's
+// chain up to akaze_refine_kernel, rule 11 on the device, the descriptor on the compacted records and a finishing kernel, image by image
+// in stream order.  The scale space, the candidate lists, the suppression's lists and the descriptor's buffers are the left image's first
+// and the right image's afterwards: an image's finishing kernel has put its counts into the pinned h_n before the next image's clear.
+int spvo_akaze_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, float threshold, int slot_l, int slot_r, int slot_capacity,
+                           spvo_akaze_features *out_l, spvo_akaze_features *out_r) {
+  if (!c || !img_l || !img_r || !out_l || !out_r || rows <= 0 || cols <= 0 || stride < (size_t)cols) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  if (slot_l < 0 || slot_l >= N_BIN_SLOTS || slot_r < 0 || slot_r >= N_BIN_SLOTS || slot_l == slot_r) return fail(c, SPVO_ERR_INVALID, "bad slot");
+  spvo_akaze_features *const outs[2] = {out_l, out_r};
+  for (auto *o : outs)
+    if (o->cap < 0) return fail(c, SPVO_ERR_INVALID, "bad output buffer");
+  const int cap = slot_capacity;
+  if (cap <= 0 || cap > (1 << HAM_KEY_SHIFT)) return fail(c, SPVO_ERR_INVALID, "slot_capacity must be 1 .. %d", 1 << HAM_KEY_SHIFT);
+  if (int rc = ak_check(c, "spvo_akaze_detect_pair", rows, cols, threshold)) return rc;
+  if (int rc = require_idle(c)) return rc;
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  out_l->n = out_r->n = 0;
+  hipStream_t st = c->stream2;
+  auto &bb = c->bin;
+  auto &b = c->cls;
+  auto &d = c->akaze;
+  PairStage &ps = bb.pair;
+  constexpr int row_bytes = AKAZE_MLDB_BYTES;
+  const size_t px = (size_t)rows * cols;
+  // every allocation before the first launch of the chain; the image buffer before the layout of its shape
+  int rc;
+  if ((rc = classic_slots_ensure(c, cap, px)) || (rc = classic_image_ensure(c, rows, cols)) || (rc = ak_ensure(c, rows, cols)) || (rc = ak_sup_ensure(c, d.cand_cap)) || (rc = ak_kp_ensure(c, cap)))
+    return rc;
+  // both slots are being rewritten: whatever was matched against their old contents is stale
+  const int slots[2] = {slot_l, slot_r};
+  for (int sl : slots) { slot_rewrite(bb.slots[sl]); bb.slots[sl].row_bytes = row_bytes; }
+  ps.mcache.invalidate();
+  HIP_TRY(c, hipStreamSynchronize(st));   // (the staging buffer and the mirrors are the previous call's until its work is done)
+  ps.stage(img_l, img_r, rows, cols, stride);
+  const AkazeLevels &lv = d.lv;
+  const dim3 blk(256);
+  for (int k = 0; k < 2; ++k) {
+    const BinarySlot &s = bb.slots[slots[k]];
+    b.rows = b.cols = 0;
+    HIP_TRY(c, hipMemcpyAsync(b.im, ps.h_img + k * px, px, hipMemcpyHostToDevice, st));
+    b.rows = rows; b.cols = cols;
+    if ((rc = ak_scale_enqueue(c, rows, cols))) return rc;
+    // rules 10, 12, 13: spvo_akaze_detect's launches
+    for (int first = 0; first < lv.n; first += AK_SUBLEVELS) {
+      const AkazeLevel &L = lv.l[first];
+      if (L.h <= 2 * L.border || L.w <= 2 * L.border) continue;
+      dim3 eg = grid_of(L.w, L.h);
+      eg.z = std::min(AK_SUBLEVELS, lv.n - first);
+      hipLaunchKernelGGL(akaze_extrema_kernel, eg, blk, 0, st, lv, first, threshold, 1e-5f, d.keys, d.cand_cap, d.stat);
+    }
+    classic_rank_enqueue(c, d.keys, d.rank, d.stat + AKAZE_STAT_NCAND, d.cand_cap);
+    hipLaunchKernelGGL(akaze_refine_kernel, dim3(32), blk, 0, st, lv, d.keys, d.rank, d.cand_cap, d.stat, d.rec);
+    // rule 11, then the descriptor on what it leaves, the count read on the device
+    ak_suppress_enqueue(c, lv, d.rec, d.stat + AKAZE_STAT_NCAND, d.cand_cap);
+    hipLaunchKernelGGL(akaze_describe_kernel, dim3(std::min(cap, 4096)), dim3(64), 0, st, lv, d.sup_kp, cap, d.sup_cnt + AKAZE_SUP_KEPT, d.d_angle, d.d_desc);
+    hipLaunchKernelGGL(akaze_pair_finish_kernel, dim3(32), blk, 0, st, d.stat, d.cand_cap, d.sup_cnt, d.sup_kp, d.d_angle, d.d_desc, cap, s.d_kp, s.d_desc, s.d_n, bb.h_n + 4 * k, bb.h_n + 8 + 4 * k,
+                       bb.h_akp + (size_t)k * cap, bb.h_desc + (size_t)k * cap * row_bytes);
+    HIP_TRY(c, hipGetLastError());
+  }
+  HIP_TRY(c, hipEventRecord(ps.ev_feat, st));
+  // spvo_set_prematch, as spvo_classic_detect: any filled slot of 61-byte rows is a temporal partner, a slot of another width is skipped
+  const int prev = ps.last_slot_l;
+  const int partner[2] = {slot_r, ps.temporal_partner(slot_l, slot_r, prev >= 0 && bb.slots[prev].filled && bb.slots[prev].row_bytes == row_bytes)};
+  if (c->prematch) {
+    for (int k = 0; k < 2; ++k)
+      if (partner[k] >= 0)
+        if ((rc = enqueue_hamming_slots(c, slot_l, partner[k], c->pm_selector, c->pm_cross, c->pm_ratio, bb.h_match + (size_t)k * cap))) return rc;
+    HIP_TRY(c, hipEventRecord(ps.ev_match, st));
+  }
+  HIP_TRY(c, wait_event(ps.ev_feat));   // the one wait of the call: the matches go on behind it
+  ps.last_slot_l = -1;   // (forgotten AFTER the wait, as spvo_classic_detect: a call that failed before it leaves the partner it found)
+  for (int k = 0; k < 2; ++k) outs[k]->n = bb.h_n[4 * k];
+  // (the list holds every strict maximum the borders leave room for, so the flag cannot be set; were it, the counts would be wrong)
+  if (bb.h_n[1] || bb.h_n[5]) return fail(c, SPVO_ERR_STATE, "spvo_akaze_detect_pair: the candidate list overflowed although it is sized from the image");
+  {   // the right image's scale space is resident (ak_mark_resident: the contrast factors sit where stat keeps them)
+    int stat[AKAZE_STAT_HIST] = {0};
+    std::memcpy(&stat[AKAZE_STAT_K], bb.h_n + 8 + 4, AKAZE_MAX_OCTAVES * sizeof(int));
+    ak_mark_resident(c, stat);
+  }
+  if (outs[0]->n > cap || outs[1]->n > cap)
+    return fail(c, SPVO_ERR_CAPACITY, "spvo_akaze_detect_pair: %d / %d rows do not fit slots of %d (slot_capacity)", outs[0]->n, outs[1]->n, cap);
+  static_assert(sizeof(spvo_akaze_keypoint) == sizeof(AkazeKp), "record layout");
+  for (int k = 0; k < 2; ++k) {
+    BinarySlot &s = bb.slots[slots[k]];
+    s.n = outs[k]->n; s.filled = true;
+    const int ncopy = std::min(s.n, outs[k]->cap);
+    if (ncopy > 0 && outs[k]->kp) std::memcpy(outs[k]->kp, bb.h_akp + (size_t)k * cap, (size_t)ncopy * sizeof(AkazeKp));
+    if (ncopy > 0 && outs[k]->desc) std::memcpy(outs[k]->desc, bb.h_desc + (size_t)k * cap * row_bytes, (size_t)ncopy * row_bytes);
+  }
+  if (c->prematch)
+    for (int k = 0; k < 2; ++k)
+      if (partner[k] >= 0)
+        ps.mcache.record(k, slot_l, partner[k], bb.slots[slot_l].gen, bb.slots[partner[k]].gen, c->pm_selector, c->pm_cross, c->pm_ratio, bb.h_match + (size_t)k * cap);
+  ps.last_slot_l = slot_l;
   return SPVO_OK;
 }
 

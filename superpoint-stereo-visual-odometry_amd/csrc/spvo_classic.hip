@@ -478,7 +478,7 @@ void spvo_int::classic_release_slots(spvo_ctx *c) {
     s.row_bytes = 32;
   }
   dev_free(bb.d_cnt, bb.d_kxy, bb.d_kresp, bb.d_vote);
-  host_free(bb.h_kp, bb.h_bkp, bb.h_desc, bb.h_n, bb.h_match);
+  host_free(bb.h_kp, bb.h_bkp, bb.h_akp, bb.h_desc, bb.h_n, bb.h_match);
   bb.pair.mcache.invalidate();
   bb.cap = 0; bb.pair.last_slot_l = -1;
 }
@@ -492,7 +492,7 @@ extern "C" {
 
 namespace {
 static_assert(BIN_COUNTER_INTS == CLS_COUNTER_INTS, "an image's counter block in spvo_ctx::bin.d_cnt");
-constexpr int BIN_ROW_BYTES_MAX = 64;   // the widest row a binary slot holds (BRISK); the ORB extractor's rows are 32 bytes
+constexpr int BIN_ROW_BYTES_MAX = 64;   // the widest row a binary slot holds (BRISK; AKAZE's 61 bytes are stored in 64); the ORB extractor's rows are 32 bytes
 inline bool kind_is_brisk(int kind) { return kind == SPVO_CLASSIC_GFTT_BRISK || kind == SPVO_CLASSIC_FAST_BRISK; }
 inline bool kind_is_gftt(int kind) { return kind == SPVO_CLASSIC_GFTT_ORB || kind == SPVO_CLASSIC_GFTT_BRISK; }
 // the binary slots and the call's own buffers for `cap` rows per slot and images of `px` bytes; growing un-fills every slot.  Every slot and
@@ -512,7 +512,8 @@ int bin_ensure(spvo_ctx *c, int cap, size_t px) {
   HIP_TRY(c, hipHostMalloc((void **)&bb.h_kp, (size_t)2 * cap * sizeof(OrbKeypoint)));
   HIP_TRY(c, hipHostMalloc((void **)&bb.h_bkp, (size_t)2 * cap * sizeof(BriskDetKeypoint)));
   HIP_TRY(c, hipHostMalloc((void **)&bb.h_desc, (size_t)2 * cap * BIN_ROW_BYTES_MAX));
-  HIP_TRY(c, hipHostMalloc((void **)&bb.h_n, 2 * 4 * sizeof(int)));
+  HIP_TRY(c, hipHostMalloc((void **)&bb.h_akp, (size_t)2 * cap * sizeof(AkazeKp)));
+  HIP_TRY(c, hipHostMalloc((void **)&bb.h_n, 4 * 4 * sizeof(int)));
   HIP_TRY(c, hipHostMalloc((void **)&bb.h_match, (size_t)3 * cap * sizeof(int2)));
   HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
   bb.cap = cap;

@@ -118,8 +118,9 @@ struct FeatureSlot : SlotState {
 // binary slots have ONE capacity (spvo_ctx::bin.cap)
 struct BinarySlot : SlotState {
   OrbKeypoint *d_kp = nullptr;   // [cap] x, y, angle, response, octave
-  uint32_t *d_desc = nullptr;    // [cap][16] allocated for the widest row; the matcher's row format: row_bytes / 4 words back to back, nothing to pad
-  int row_bytes = 32;            // width of the rows it holds: 32 (the ORB extractor) or 64 (BRISK); two slots are matched only at one width
+  uint32_t *d_desc = nullptr;    // [cap][16] allocated for the widest row; the matcher's row format: 8 words back to back for 32-byte rows, 16 for wider ones
+  int row_bytes = 32;            // width of the rows it holds: 32 (the ORB extractor), 64 (BRISK) or 61 (AKAZE: stored in 16 words, bytes 61 .. 63 zero);
+                                 // two slots are matched only at one width
 };
 
 // a SIFT stereo image's features, resident on the device (spvo_sift_detect_pair -> spvo_match_l2_slots) in the L2 matcher's row format; the
@@ -379,8 +380,9 @@ struct spvo_ctx {
     PairStage pair;                      // (its prematches' slot numbers are BINARY slots)
     OrbKeypoint *h_kp = nullptr;         // pinned [2][cap]      what the finishing kernel of an image writes for the host:
     uint8_t *h_desc = nullptr;           // pinned [2][cap][64]  keypoint records, descriptors ([2][cap][32] in its front part for the 32-byte kinds),
-    int *h_n = nullptr;                  // pinned [2][4]        {rows found, overflow flag of the detector}
+    int *h_n = nullptr;                  // pinned [2][4]        {rows found, overflow flag of the detector}; behind them [2][4] the contrast factors spvo_akaze_detect_pair reports
     BriskDetKeypoint *h_bkp = nullptr;   // pinned [2][cap]      spvo_brisk_detect_pair's records (24 bytes: they carry a size), in the place of h_kp
+    AkazeKp *h_akp = nullptr;            // pinned [2][cap]      spvo_akaze_detect_pair's records (28 bytes: size and level), in the place of h_kp
     int *d_cnt = nullptr;                // [2][CLS_COUNTER_INTS] the extractor's counter block per image (0: kept in all, 2: kept and described)
     int *d_kxy = nullptr;                // [cap][2] the kept keypoints of a Shi-Tomasi / FAST image (cls_compact_kernel), ...
     float *d_kresp = nullptr;            // [cap]    ... and the detector's responses of those (also brisk_compact_list_kernel's)
@@ -452,6 +454,12 @@ struct spvo_ctx {
     int kp_cap = 0;
     std::vector<float> h_angle;                        // host staging of a call's results
     std::vector<uint8_t> h_desc;
+    // rule 11 on the device (akaze_suppress.hip.h; spvo_akaze_detect_pair, spvo_akaze_suppress_debug): the list of the first loop and the
+    // candidate of every entry, the keep flags, the compacted records with their candidates' indices, and the counts
+    int sup_cap = 0;
+    float4 *sup_list = nullptr;
+    int *sup_idx = nullptr, *sup_keep = nullptr, *sup_src = nullptr, *sup_cnt = nullptr;   // sup_cnt: AKAZE_SUP_*
+    AkazeKp *sup_kp = nullptr;
   } akaze;
   // SIFT detector + descriptor of the classic front end (sift.hip.h): the image, its pyramid (all Gaussian and DoG levels: what
   // spvo_sift_debug_level serves until the next call), the candidate and output lists; device buffers grow on demand, the host staging keeps its capacity

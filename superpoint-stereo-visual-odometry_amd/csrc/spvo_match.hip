@@ -152,7 +152,7 @@ int run_match(spvo_ctx *c, const MatchReq &r, int selector, int cross_check, flo
 }
 
 // One Hamming match between two binary slots OF ONE ROW WIDTH on the solver's stream, counts read on the device (match.hip.h K12t, by the
-// slots' width the instantiation for 8 or for 16 words): the packed result
+// slots' width the instantiation for 8 words, or for 16 for any width above 32 bytes): the packed result
 // {train_idx, distance bits} of every row of slot_a lands in `host_out` (pinned).  NN + cross-check is cv::batchDistance's crosscheck as in
 // spvo_match_hamming: the train rows vote for their nearest query row, then every query row reads its vote.
 int enqueue_hamming_slots(spvo_ctx *c, int slot_a, int slot_b, int selector, int cross_check, float ratio, int2 *host_out) {
@@ -163,7 +163,7 @@ int enqueue_hamming_slots(spvo_ctx *c, int slot_a, int slot_b, int selector, int
   const int cap = bb.cap;
   if (a.row_bytes != b.row_bytes)
     return fail(c, SPVO_ERR_INVALID, "binary slot %d holds rows of %d bytes, slot %d rows of %d bytes: only slots of one width are matched", slot_a, a.row_bytes, slot_b, b.row_bytes);
-  const bool wide = a.row_bytes == 64;
+  const bool wide = a.row_bytes > 32;   // (BRISK's 64 bytes, AKAZE's 61 in 16 words)
   const dim3 grid(wide ? (cap + HAM_QB<16> - 1) / HAM_QB<16> : (cap + HAM_QB<8> - 1) / HAM_QB<8>);
   auto launch = [&](const BinarySlot &q, const BinarySlot &t, int mode) {
     if (wide) hipLaunchKernelGGL(match_hamming_tiled_kernel<16>, grid, dim3(256), 0, st, q.d_desc, q.d_n, t.d_desc, t.d_n, cap, mode, ratio, host_out, bb.d_vote);

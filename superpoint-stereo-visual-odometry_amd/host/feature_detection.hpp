@@ -349,18 +349,21 @@ public:
   // and every match are what they are with the option off (the default).  A pair with more rows than the slots hold (setResidentCapacity;
   // SPVO_ERR_CAPACITY), and every pair without a route, goes through the per-image path and is matched from the host matrices.
   // setBriskPairResident: BRISK + BRISK takes its route only with this as well.  setAkazeDescriptor: AKAZE + AKAZE runs (per image); off,
-  // that pair is refused as every pair that does not run is.
+  // that pair is refused as every pair that does not run is.  setAkazePairResident: AKAZE + AKAZE takes its route (spvo_akaze_detect_pair)
+  // only with this as well as setAkazeDescriptor and setDeviceResident.
   static void setDeviceResident(bool on);
   static void setResidentCapacity(int rows);   // rows per binary slot [8192]
   static void setBriskPairResident(bool on);   // [off]
   static void setAkazeDescriptor(bool on);     // [off]
-  // pairs that actually stayed resident (spvo_classic_detect / spvo_sift_detect_pair / spvo_brisk_detect_pair returned SPVO_OK): what tells the resident path from its fallback
+  static void setAkazePairResident(bool on);   // [off]
+  // pairs that actually stayed resident (spvo_classic_detect / spvo_sift_detect_pair / spvo_brisk_detect_pair / spvo_akaze_detect_pair returned SPVO_OK): what tells the resident path from its fallback
   unsigned residentPairs() const { return resident_ok_pairs_; }
 
 private:
   bool resident_ = false;
   bool brisk_pair_resident_ = false;   // setBriskPairResident at construction
   bool akaze_descriptor_ = false;      // setAkazeDescriptor at construction
+  bool akaze_pair_resident_ = false;   // setAkazePairResident at construction
   bool pairRuns() const;               // this detector / descriptor pair runs in this build
   int resident_capacity_ = 8192;
   unsigned resident_pairs_ = 0;   // pairs handed to a resident route: pair k lives in slots 2 (k % 4), 2 (k % 4) + 1

@@ -12,9 +12,11 @@ static bool g_classic_resident = false;
 static int g_classic_resident_capacity = 8192;
 static bool g_classic_brisk_pair_resident = false;
 static bool g_classic_akaze_descriptor = false;
+static bool g_classic_akaze_pair_resident = false;
 void ClassicFeatureFrontEnd::setDeviceResident(bool on) { g_classic_resident = on; }
 void ClassicFeatureFrontEnd::setBriskPairResident(bool on) { g_classic_brisk_pair_resident = on; }
 void ClassicFeatureFrontEnd::setAkazeDescriptor(bool on) { g_classic_akaze_descriptor = on; }
+void ClassicFeatureFrontEnd::setAkazePairResident(bool on) { g_classic_akaze_pair_resident = on; }
 void ClassicFeatureFrontEnd::setResidentCapacity(int rows) { g_classic_resident_capacity = rows; }
 
 #ifdef SPVO_USE_OPENCV
@@ -85,8 +87,8 @@ bool ClassicFeatureFrontEnd::available() { return true; }
 
 enum class Detect { Orb, Gftt, Fast, Sift, Brisk, Akaze };       // detectKeypoints: spvo_<this>_detect
 enum class Describe { WithDetector, Orb, Brisk, Akaze };         // describeKeypoints: the rows detectKeypoints kept, or spvo_<this>_describe on the given keypoints
-enum class Route { None, Classic, SiftPair, BriskPair };         // setDeviceResident: the per-image path, spvo_classic_detect (kind), spvo_sift_detect_pair, spvo_brisk_detect_pair
-enum class OptIn { None, AkazeDescriptor, BriskPairResident };   // setAkazeDescriptor: to run at all; setBriskPairResident: to stay resident
+enum class Route { None, Classic, SiftPair, BriskPair, AkazePair };   // setDeviceResident: the per-image path, spvo_classic_detect (kind), spvo_sift_detect_pair, spvo_brisk_detect_pair, spvo_akaze_detect_pair
+enum class OptIn { None, AkazeDescriptor, BriskPairResident, AkazePairResident };   // to run at all: setAkazeDescriptor; to stay resident: setBriskPairResident, setAkazePairResident
 
 struct ClassicPair {
   DetectorType detector;
@@ -97,19 +99,20 @@ struct ClassicPair {
   int cols, type;        // a descriptor row; CV_8UC1 rows are matched with NORM_HAMMING, CV_32FC1 rows with NORM_L2
   Route route;
   int kind;              // Route::Classic: the spvo_classic_kind
-  OptIn opt_in;
+  OptIn opt_in;          // what the pair needs to run at all ...
+  OptIn resident_opt_in; // ... and what its route needs beside setDeviceResident
   size_t rowBytes() const { return (size_t)cols * (type == CV_32FC1 ? sizeof(float) : 1); }
 };
 static const ClassicPair kClassicPairs[] = {
-    {DetectorType::ORB, DescriptorType::ORB, Detect::Orb, 0.f, Describe::WithDetector, 32, CV_8UC1, Route::Classic, SPVO_CLASSIC_ORB, OptIn::None},
-    {DetectorType::ShiTomasi, DescriptorType::ORB, Detect::Gftt, 5.f, Describe::Orb, 32, CV_8UC1, Route::Classic, SPVO_CLASSIC_GFTT_ORB, OptIn::None},
-    {DetectorType::FAST, DescriptorType::ORB, Detect::Fast, 7.f, Describe::Orb, 32, CV_8UC1, Route::Classic, SPVO_CLASSIC_FAST_ORB, OptIn::None},
-    {DetectorType::ShiTomasi, DescriptorType::BRISK, Detect::Gftt, 5.f, Describe::Brisk, 64, CV_8UC1, Route::Classic, SPVO_CLASSIC_GFTT_BRISK, OptIn::None},
-    {DetectorType::FAST, DescriptorType::BRISK, Detect::Fast, 7.f, Describe::Brisk, 64, CV_8UC1, Route::Classic, SPVO_CLASSIC_FAST_BRISK, OptIn::None},
-    {DetectorType::BRISK, DescriptorType::BRISK, Detect::Brisk, 0.f, Describe::Brisk, 64, CV_8UC1, Route::BriskPair, 0, OptIn::BriskPairResident},
-    {DetectorType::AKAZE, DescriptorType::BRISK, Detect::Akaze, 0.f, Describe::Brisk, 64, CV_8UC1, Route::None, 0, OptIn::None},
-    {DetectorType::AKAZE, DescriptorType::AKAZE, Detect::Akaze, 0.f, Describe::Akaze, SPVO_AKAZE_DESC_BYTES, CV_8UC1, Route::None, 0, OptIn::AkazeDescriptor},
-    {DetectorType::SIFT, DescriptorType::SIFT, Detect::Sift, 0.f, Describe::WithDetector, 128, CV_32FC1, Route::SiftPair, 0, OptIn::None},
+    {DetectorType::ORB, DescriptorType::ORB, Detect::Orb, 0.f, Describe::WithDetector, 32, CV_8UC1, Route::Classic, SPVO_CLASSIC_ORB, OptIn::None, OptIn::None},
+    {DetectorType::ShiTomasi, DescriptorType::ORB, Detect::Gftt, 5.f, Describe::Orb, 32, CV_8UC1, Route::Classic, SPVO_CLASSIC_GFTT_ORB, OptIn::None, OptIn::None},
+    {DetectorType::FAST, DescriptorType::ORB, Detect::Fast, 7.f, Describe::Orb, 32, CV_8UC1, Route::Classic, SPVO_CLASSIC_FAST_ORB, OptIn::None, OptIn::None},
+    {DetectorType::ShiTomasi, DescriptorType::BRISK, Detect::Gftt, 5.f, Describe::Brisk, 64, CV_8UC1, Route::Classic, SPVO_CLASSIC_GFTT_BRISK, OptIn::None, OptIn::None},
+    {DetectorType::FAST, DescriptorType::BRISK, Detect::Fast, 7.f, Describe::Brisk, 64, CV_8UC1, Route::Classic, SPVO_CLASSIC_FAST_BRISK, OptIn::None, OptIn::None},
+    {DetectorType::BRISK, DescriptorType::BRISK, Detect::Brisk, 0.f, Describe::Brisk, 64, CV_8UC1, Route::BriskPair, 0, OptIn::None, OptIn::BriskPairResident},
+    {DetectorType::AKAZE, DescriptorType::BRISK, Detect::Akaze, 0.f, Describe::Brisk, 64, CV_8UC1, Route::None, 0, OptIn::None, OptIn::None},
+    {DetectorType::AKAZE, DescriptorType::AKAZE, Detect::Akaze, 0.f, Describe::Akaze, SPVO_AKAZE_DESC_BYTES, CV_8UC1, Route::AkazePair, 0, OptIn::AkazeDescriptor, OptIn::AkazePairResident},
+    {DetectorType::SIFT, DescriptorType::SIFT, Detect::Sift, 0.f, Describe::WithDetector, 128, CV_32FC1, Route::SiftPair, 0, OptIn::None, OptIn::None},
 };
 
 // the row of a pair that runs, or nullptr
@@ -444,7 +447,7 @@ bool ClassicFeatureFrontEnd::residentPair(const ClassicPair &p, cv::Mat &img_l, 
 bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &img_l, cv::Mat &img_r) {
   if (!image_ok(img_l) || !image_ok(img_r) || (size_t)img_l.step != (size_t)img_r.step) return false;
   const ClassicPair &p = *pair();   // (addStereoImagePair has asked pairRuns)
-  if (p.route == Route::None || (p.opt_in == OptIn::BriskPairResident && !brisk_pair_resident_)) return false;
+  if (p.route == Route::None || (p.resident_opt_in == OptIn::BriskPairResident && !brisk_pair_resident_) || (p.resident_opt_in == OptIn::AkazePairResident && !akaze_pair_resident_)) return false;
   const uint8_t *l = img_l.ptr<uint8_t>(0), *r = img_r.ptr<uint8_t>(0);
   const int rows = img_l.rows, cols = img_l.cols;
   const size_t step = (size_t)img_l.step;
@@ -464,6 +467,10 @@ bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &img_l, cv::Mat 
   case Route::BriskPair:   // cv::BRISK::create(): threshold 30, 3 octaves, as detectKeypoints
     return residentPair<spvo_brisk_features>(p, img_l, img_r, "spvo_brisk_detect_pair", [&](int slot_l, int slot_r, spvo_brisk_features *f) {
       return spvo_brisk_detect_pair(ctx_, l, r, rows, cols, step, 30, 3, slot_l, slot_r, resident_capacity_, &f[0], &f[1]);
+    });
+  case Route::AkazePair:   // cv::AKAZE::create(): threshold 0.001, as detectKeypoints
+    return residentPair<spvo_akaze_features>(p, img_l, img_r, "spvo_akaze_detect_pair", [&](int slot_l, int slot_r, spvo_akaze_features *f) {
+      return spvo_akaze_detect_pair(ctx_, l, r, rows, cols, step, 0.001f, slot_l, slot_r, resident_capacity_, &f[0], &f[1]);
     });
   case Route::None:
     break;
@@ -494,6 +501,7 @@ ClassicFeatureFrontEnd::ClassicFeatureFrontEnd(const DetectorType detector_type,
   resident_ = g_classic_resident;
   resident_capacity_ = g_classic_resident_capacity;
   brisk_pair_resident_ = g_classic_brisk_pair_resident;
+  akaze_pair_resident_ = g_classic_akaze_pair_resident;
 }
 
 ClassicFeatureFrontEnd::~ClassicFeatureFrontEnd() {

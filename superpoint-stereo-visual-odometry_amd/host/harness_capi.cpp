@@ -430,6 +430,10 @@ void spvo_host_classic_set_brisk_resident(int on) { ClassicFeatureFrontEnd::setB
 // spvo_akaze_describe, 61-byte rows); off, that pair is refused
 void spvo_host_classic_set_akaze_descriptor(int on) { ClassicFeatureFrontEnd::setAkazeDescriptor(on != 0); }
 
+// ClassicFeatureFrontEnd::setAkazePairResident for the front ends constructed afterwards: AKAZE + AKAZE through spvo_akaze_detect_pair
+// (with spvo_host_classic_set_akaze_descriptor and the resident option of the sequence run)
+void spvo_host_classic_set_akaze_resident(int on) { ClassicFeatureFrontEnd::setAkazePairResident(on != 0); }
+
 // the ORB + ORB front end at the native resolution (the export's first form)
 int spvo_host_classic_sequence(int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l, const double *P_r, int knn,
                                int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats, double *seconds) {

@@ -42,6 +42,10 @@ class BriskFeatures(C.Structure):          # spvo_brisk_features
     _fields_ = [("n", C.c_int), ("kp", C.c_void_p), ("desc", C.c_void_p), ("cap", C.c_int)]
 
 
+class AkazeFeatures(C.Structure):          # spvo_akaze_features
+    _fields_ = [("n", C.c_int), ("kp", C.c_void_p), ("desc", C.c_void_p), ("cap", C.c_int)]
+
+
 class SiftFeatures(C.Structure):
     _fields_ = [("n", C.c_int), ("kp", C.c_void_p), ("desc", C.c_void_p), ("cap", C.c_int)]
 
@@ -80,6 +84,7 @@ class SolveOutput(C.Structure):
 SIFT_KP_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("size", np.float32), ("angle", np.float32), ("response", np.float32), ("octave", np.int32)])   # spvo_sift_keypoint
 BRISK_KP_DTYPE = SIFT_KP_DTYPE   # spvo_brisk_keypoint: octave is the layer 0..5, angle is -1
 AKAZE_KP_DTYPE = np.dtype(SIFT_KP_DTYPE.descr + [("class_id", np.int32)])   # spvo_akaze_keypoint: class_id is the level 0..15, angle is 0
+AKAZE_CAND_DTYPE = np.dtype([("level", np.int32), ("row", np.int32), ("col", np.int32), ("response", np.float32), ("ok", np.int32)])   # spvo_akaze_candidate
 AKAZE_DESC_BYTES = 61                                                       # SPVO_AKAZE_DESC_BYTES: the full MLDB descriptor, 486 bits
 OBS_DTYPE = np.dtype([("X", np.float32, 3), ("uv", np.float32, 2), ("cam", np.int32), ("inverse", np.int32)])
 
@@ -88,7 +93,7 @@ SYMBOLS = [
     "spvo_default_config", "spvo_create", "spvo_destroy", "spvo_last_error", "spvo_load_weights", "spvo_engine_precision", "spvo_set_fp32_split",
     "spvo_preprocess", "spvo_forward", "spvo_debug_tensor", "spvo_heatmap", "spvo_nms",
     "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8",
-    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_akaze_describe", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_detect_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
+    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_akaze_describe", "spvo_akaze_detect_pair", "spvo_akaze_suppress_debug", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_detect_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
     "spvo_profile_enable", "spvo_profile_reset", "spvo_profile_only", "spvo_profile_count", "spvo_profile_get", "spvo_profile_stage_kernel",
     "spvo_set_tuning", "spvo_get_tuning", "spvo_clear_tuning",
     "spvo_comm_unique_id", "spvo_comm_available", "spvo_comm_create", "spvo_comm_create_host", "spvo_comm_rank", "spvo_comm_world", "spvo_comm_destroy",
@@ -155,6 +160,8 @@ def load() -> C.CDLL:
     lib.spvo_akaze_last_contrast.argtypes = [vp, vp, ip]
     lib.spvo_akaze_tables.argtypes = [C.c_int, C.c_int, ip, vp, vp, vp, vp, vp, C.c_int, ip, vp, vp]
     lib.spvo_akaze_describe.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, vp, vp]
+    lib.spvo_akaze_detect_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(AkazeFeatures), C.POINTER(AkazeFeatures)]
+    lib.spvo_akaze_suppress_debug.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, ip]
     lib.spvo_sift_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, C.c_int, ip]
     lib.spvo_sift_debug_level.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, ip, ip]
     lib.spvo_sift_detect_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(SiftFeatures), C.POINTER(SiftFeatures)]
@@ -616,6 +623,46 @@ class Context:
             m = min(f.n, max(want, 0))
             out.append(dict(kp=kp[:m].copy(), desc=desc[:m].copy(), n=f.n))
         return out[0], out[1]
+
+    def akaze_detect_pair(self, img_l, img_r, slot_l: int, slot_r: int, threshold: float = 0.001, slot_capacity: int = 8192, cap: Optional[int] = None):
+        """One stereo pair through the AKAZE detector + descriptor into two binary feature slots of 61-byte rows (spvo_akaze_detect_pair).
+        -> (left, right): dicts of kp [m] (AKAZE_KP_DTYPE records: the detector's, with the descriptor's angle in degrees), desc [m, 61] uint8
+        and n, the rows the slot holds; m = min(n, cap), cap = None: slot_capacity.  Strided views are accepted.  Afterwards the right
+        image and its scale space are resident (akaze_describe(None, ...), akaze_level).
+        On SPVO_ERR_CAPACITY the SpvoError carries the two counts as .n_l, .n_r (and .counts)."""
+        l, r = _u8_rows(img_l), _u8_rows(img_r)
+        if l.shape != r.shape or l.strides[0] != r.strides[0]:
+            l, r = np.ascontiguousarray(l), np.ascontiguousarray(r)
+            if l.shape != r.shape:
+                raise ValueError("the two images of a pair must have one shape")
+        want = int(slot_capacity) if cap is None else int(cap)
+        bufs, feats = [], []
+        for _ in range(2):
+            kp = np.zeros(max(want, 1), AKAZE_KP_DTYPE)
+            desc = np.zeros((max(want, 1), AKAZE_DESC_BYTES), np.uint8)
+            bufs.append((kp, desc))
+            feats.append(AkazeFeatures(0, kp.ctypes.data, desc.ctypes.data, want))
+        rc = self.lib.spvo_akaze_detect_pair(self.h, _ptr(l), _ptr(r), l.shape[0], l.shape[1], l.strides[0], float(threshold), slot_l, slot_r, int(slot_capacity),
+                                             C.byref(feats[0]), C.byref(feats[1]))
+        if rc:
+            e = SpvoError(rc, self.lib.spvo_last_error(self.h).decode())
+            e.n_l, e.n_r = feats[0].n, feats[1].n
+            e.counts = (e.n_l, e.n_r)
+            raise e
+        self._resident_shape = r.shape
+        out = []
+        for (kp, desc), f in zip(bufs, feats):
+            m = min(f.n, max(want, 0))
+            out.append(dict(kp=kp[:m].copy(), desc=desc[:m].copy(), n=f.n))
+        return out[0], out[1]
+
+    def akaze_suppress_debug(self, rows: int, cols: int, cand: np.ndarray) -> np.ndarray:
+        """The device suppression of akaze_detect_pair on a candidate list (spvo_akaze_suppress_debug): cand [n] AKAZE_CAND_DTYPE records
+        (level, row, col, response, ok), level by level, for the level tables of a rows x cols image -> the indices that stay, in output order."""
+        cand = np.ascontiguousarray(cand, AKAZE_CAND_DTYPE)
+        keep, n = np.zeros(max(len(cand), 1), np.int32), C.c_int(0)
+        self._check(self.lib.spvo_akaze_suppress_debug(self.h, int(rows), int(cols), _ptr(cand), len(cand), _ptr(keep), C.byref(n)))
+        return keep[:n.value].copy()
 
     def sift_detect(self, img: np.ndarray, cap: Optional[int] = None):
         """SIFT keypoints + descriptors of one u8 image (spvo_sift_detect): dict of kp [m] (SIFT_KP_DTYPE records), desc [m, 128] float32 (integers

@@ -342,7 +342,7 @@ class FrontEnd:
 
 
 def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_threshold=2.0, refinement_degree=4, warm=0, detector="ORB", input_size=None, resident=False,
-                     resident_capacity=0, trace=False, descriptor="ORB", brisk_resident=False, akaze_descriptor=False):
+                     resident_capacity=0, trace=False, descriptor="ORB", brisk_resident=False, akaze_descriptor=False, akaze_resident=False):
     """stereoCallback replayed on ClassicFeatureFrontEnd(detector, descriptor, BF, ...) (node.cpp:353-360) over host image pairs -- detector
     "ORB", "ShiTomasi" or "FAST" with descriptor "ORB", "ShiTomasi", "FAST", "BRISK" or "AKAZE" with descriptor "BRISK" (64-byte rows; detector "BRISK"
     or "AKAZE" with the default descriptor "ORB" does not run; "AKAZE" with descriptor "AKAZE" -- orientation and the 61-byte MLDB rows of
@@ -350,8 +350,10 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     (classic.cpp:96-100).  Returns (poses [n, 7] = q xyzw + t of cam0_curr_T_cam0_prev, stats [n, 4] = keypoints L, R, stereo
     matches, PnP inliers, seconds spent on frames warm .. n-1).
     resident: ClassicFeatureFrontEnd::setDeviceResident for this run -- one spvo_classic_detect (SIFT: spvo_sift_detect_pair) per pair, features
-    and matching stay on the device, for every pair named above with BRISK descriptors on ShiTomasi / FAST keypoints included; "AKAZE" keypoints always take
-    the per-image path and classic_resident_pairs() stays 0; "BRISK" + "BRISK"
+    and matching stay on the device, for every pair named above with BRISK descriptors on ShiTomasi / FAST keypoints included; "AKAZE" + "BRISK" always takes
+    the per-image path and classic_resident_pairs() stays 0, and so does "AKAZE" + "AKAZE" unless akaze_resident
+    (ClassicFeatureFrontEnd::setAkazePairResident, reset afterwards) is set as well: then it is one spvo_akaze_detect_pair per pair into the
+    binary slots, 61-byte rows; "BRISK" + "BRISK"
     takes the per-image path and classic_resident_pairs() stays 0 unless brisk_resident (ClassicFeatureFrontEnd::setBriskPairResident) is set
     as well: then it is one spvo_brisk_detect_pair per pair into the same binary slots (resident_capacity > 0: rows per slot; a pair that does not
     fit falls back to the per-image path; classic_resident_pairs() tells how many pairs of the run stayed resident).
@@ -368,6 +370,8 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     lib.spvo_host_classic_set_resident.argtypes = [C.c_int, C.c_int]
     lib.spvo_host_classic_set_brisk_resident.restype = None
     lib.spvo_host_classic_set_brisk_resident.argtypes = [C.c_int]
+    lib.spvo_host_classic_set_akaze_resident.restype = None
+    lib.spvo_host_classic_set_akaze_resident.argtypes = [C.c_int]
     lib.spvo_host_classic_set_akaze_descriptor.restype = None
     lib.spvo_host_classic_set_akaze_descriptor.argtypes = [C.c_int]
     n = len(frames)
@@ -385,6 +389,7 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     digest = np.zeros((n, 8), np.uint64) if trace else None     # NULL: nothing is digested (the digests are computed inside the timed loop)
     lib.spvo_host_classic_set_resident(int(bool(resident)), int(resident_capacity) if resident_capacity > 0 else 8192)
     lib.spvo_host_classic_set_brisk_resident(int(bool(brisk_resident)))
+    lib.spvo_host_classic_set_akaze_resident(int(bool(akaze_resident)))
     lib.spvo_host_classic_set_akaze_descriptor(int(bool(akaze_descriptor)))
     try:
         args = (n, pl, pr, rows, cols, Pl.ctypes.data, Pr.ctypes.data, 1 if selector == "KNN" else 0, int(cross_check), stereo_threshold, refinement_degree, warm,
@@ -396,6 +401,7 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     finally:
         lib.spvo_host_classic_set_resident(0, 8192)
         lib.spvo_host_classic_set_brisk_resident(0)
+        lib.spvo_host_classic_set_akaze_resident(0)
         lib.spvo_host_classic_set_akaze_descriptor(0)
     if rc == -1000000:
         raise ValueError("unknown detector %r" % (detector,))

@@ -1,11 +1,12 @@
 """The classic front end on the GPU.
 
-python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK|AKAZE] [--descriptor ORB|BRISK|AKAZE] [--resident] [--brisk-resident]
+python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK|AKAZE] [--descriptor ORB|BRISK|AKAZE] [--resident] [--brisk-resident] [--akaze-resident]
     ClassicFeatureFrontEnd(detector, descriptor, BF, KNN) over the synthetic stream: frames/s of the synchronous stereoCallback
     (--descriptor BRISK: with --detector ShiTomasi, FAST, BRISK or AKAZE; --detector BRISK: with --descriptor BRISK only; --detector AKAZE:
     with --descriptor BRISK or AKAZE -- the latter sets ClassicFeatureFrontEnd::setAkazeDescriptor for the run: 61-byte MLDB rows);
     --resident: with ClassicFeatureFrontEnd::setDeviceResident (one spvo_classic_detect per pair, matching on the binary slots);
     --brisk-resident: with setBriskPairResident as well (BRISK + BRISK through one spvo_brisk_detect_pair per pair; needs --resident).
+    --akaze-resident: with setAkazePairResident as well (AKAZE + AKAZE through one spvo_akaze_detect_pair per pair; needs --resident).
 python tools/classic_bench.py [frames] --detector ShiTomasi|FAST|ORB --descriptor ORB|BRISK --ab ROUNDS
     the same stream with setDeviceResident off and on, alternating, ROUNDS times each in one process: ms per pair of every run, the median
     and the min .. max spread of each setting, and how many pairs of a resident run stayed resident.
@@ -38,6 +39,11 @@ python tools/classic_bench.py --leg brisk_pair [--calls 50]
     spvo_brisk_detect_pair (threshold 30) alone on the 1241 x 376 sample pair, rotating through the slot ring, for rocprofv3 --kernel-trace
     --stats as above: the detector's kernels up to brisk_refine_kernel, then brisk_integral_*_kernel / brisk_pair_compact_kernel /
     brisk_describe_kernel / brisk_pair_finish_kernel, twice per call.
+python tools/classic_bench.py --leg akaze_pair [--calls 100]
+    spvo_akaze_detect_pair (threshold 0.001) alone on the 1241 x 376 sample pair -- BOTH images per call -- rotating through the slot ring,
+    for rocprofv3 --kernel-trace --stats as above: the detector's kernels up to akaze_refine_kernel, then akaze_suppress_first_kernel /
+    akaze_suppress_second_kernel / akaze_suppress_compact_kernel / akaze_describe_kernel / akaze_pair_finish_kernel, twice per call.
+    Its yardsticks are --leg akaze_detect and --leg akaze_describe: two per-image detects plus two describes.
 python tools/classic_bench.py --leg match|match_slots [--selector NN|KNN] [--cross] [--calls 50]
     one matcher alone on the two resident ORB sets of the 1241 x 376 sample pair: spvo_match_hamming on the host copies (match_hamming_kernel<8>)
     or spvo_match_hamming_slots on the binary slots (match_hamming_tiled_kernel), for rocprofv3 --kernel-trace --stats as above.
@@ -59,8 +65,9 @@ ap.add_argument("--descriptor", default="ORB")
 ap.add_argument("--detectors", action="store_true")
 ap.add_argument("--resident", action="store_true")
 ap.add_argument("--brisk-resident", action="store_true")
+ap.add_argument("--akaze-resident", action="store_true")
 ap.add_argument("--ab", type=int, default=0)
-ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "brisk_detect", "akaze_detect", "akaze_describe", "brisk_pair", "orb_describe", "match", "match_slots"])
+ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "brisk_detect", "akaze_detect", "akaze_describe", "akaze_pair", "brisk_pair", "orb_describe", "match", "match_slots"])
 ap.add_argument("--selector", default="KNN", choices=["NN", "KNN"])
 ap.add_argument("--cross", action="store_true")
 ap.add_argument("--yardstick", action="store_true")
@@ -136,7 +143,13 @@ if args.detectors or args.leg:
         fl, fr = ctx.brisk_detect_pair(img, pair_r, 2 * k, 2 * k + 1, 30)
         return fl["n"] + fr["n"]
 
-    if args.leg == "brisk_pair":
+    def leg_akaze_pair():
+        k = pair_calls[0] % 4
+        pair_calls[0] += 1
+        fl, fr = ctx.akaze_detect_pair(img, pair_r, 2 * k, 2 * k + 1)
+        return fl["n"] + fr["n"]
+
+    if args.leg in ("brisk_pair", "akaze_pair"):
         pair_r = np.ascontiguousarray(frames[0][1][:376, :1241])
 
     def leg_orb_describe():
@@ -162,6 +175,7 @@ if args.detectors or args.leg:
                 akaze_describe=("spvo_akaze_describe(NULL)", leg_akaze_describe), akaze_brisk_null=("spvo_brisk_describe(NULL), same keypoints", leg_akaze_brisk_null),
                 akaze_describe_img=("spvo_akaze_describe(img)", leg_akaze_describe_img),
                 brisk_detect=("spvo_brisk_detect", leg_brisk_detect), akaze_detect=("spvo_akaze_detect", leg_akaze_detect), brisk_pair=("spvo_brisk_detect_pair (both images)", leg_brisk_pair),
+                akaze_pair=("spvo_akaze_detect_pair (both images)", leg_akaze_pair),
                 orb=("spvo_orb_detect", leg_orb), sift=("spvo_sift_detect", leg_sift), gftt=("spvo_gftt_detect + spvo_orb_describe", leg_gftt), fast=("spvo_fast_detect + spvo_orb_describe", leg_fast))
     keys = [args.leg] + (["sift"] if args.yardstick else []) if args.leg else ["orb", "gftt", "fast"]
     if args.leg == "akaze_describe":
@@ -203,5 +217,5 @@ else:
     n = args.frames
     seq = [frames[i % 8] for i in range(n)]
     p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5, detector=args.detector, resident=args.resident, descriptor=args.descriptor,
-                                        akaze_descriptor=args.descriptor == "AKAZE", **(dict(brisk_resident=True) if args.brisk_resident else {}))
+                                        akaze_descriptor=args.descriptor == "AKAZE", **(dict(brisk_resident=True) if args.brisk_resident else {}), **(dict(akaze_resident=True) if args.akaze_resident else {}))
     print("classic front end (%s%s) on the GPU: %.1f stereo frames/s (%.3f ms per pair), keypoints %d, stereo matches %d, inliers %d, %d pairs resident" % (args.detector + ("" if args.descriptor == "ORB" else " + " + args.descriptor), ", device-resident" if args.resident else "", (n - 5) / sec, 1e3 * sec / (n - 5), np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3]), host.classic_resident_pairs()))
