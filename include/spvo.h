@@ -317,8 +317,32 @@ typedef struct {
 int spvo_sift_detect(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, size_t stride,
                      spvo_sift_keypoint *kp, float *desc /* [cap][128] */, int cap, int *n);
 /* A level of the pyramid of this context's last spvo_sift_detect (test hook): Gaussian layer 0..5, or with `dog` difference layer 0..4,
- * of octave 0.. (octave 0 is the doubled image).  `out` (rows x cols floats) may be NULL to ask for the shape only. */
+ * of octave 0.. (octave 0 is the doubled image).  `out` (rows x cols floats) may be NULL to ask for the shape only.  It also serves the
+ * Gaussian-only pyramid of the last spvo_sift_describe, below: octave index 0 is then that call's first octave (the doubled image only if
+ * the list held an octave -1, else the image at its own size), and dog = 1 is SPVO_ERR_STATE. */
 int spvo_sift_debug_level(spvo_ctx *ctx, int octave, int layer, int dog, float *out, int *rows, int *cols);
+/* describeKeypoints for DescriptorType::SIFT on keypoints the extractor did not detect itself (cv::SIFT::create()->compute,
+ * feature_detection_classic.cpp:71-73, 110-111: SIFT::detectAndCompute with useProvidedKeypoints) -- what ShiTomasi / FAST / ORB / BRISK /
+ * AKAZE + SIFT run.  OpenCV is not available to this build: the rule is OpenCV 4.5.4's as far as it is known, as restated by
+ * tests/sift_describe_ref.py (its header lists every choice).  Per record the packed `octave` field gives o = its low byte, sign-extended,
+ * and layer = its second byte (a detector that leaves octave = 0 gets octave 0, layer 0); the Gaussian pyramid is built for the octaves
+ * min(0, min o) .. max o -- from the doubled image only if some o is -1, else from the image at its own size blurred once with
+ * sqrt(1.6^2 - 0.5^2) -- with spvo_sift_detect's taps, pass rule and decimation and no difference of Gaussians, bit for bit the
+ * restatement's; the descriptor is spvo_sift_detect's (the same device code per sample) at the point (x, y) / 2^o rounded half to even on
+ * layer `layer` of octave o, with scale size / 2^o / 2 and orientation 360 - angle (angle = -1, which detectors without an orientation
+ * report, is legal).  No keypoint is erased and none is re-ordered: row i of `desc` belongs to record i; a patch without a valid sample
+ * gives a row of zeros.  The sums take no float atomics and a fixed order: one image and list always give the same bytes.
+ *   img == NULL   the u8 image left resident by this context's last spvo_gftt_detect / spvo_fast_detect / spvo_brisk_detect /
+ *                 spvo_akaze_detect / spvo_orb_describe / spvo_brisk_describe / spvo_sift_describe(img) (spvo_brisk_describe's rule;
+ *                 spvo_orb_detect and spvo_sift_detect keep images of their own and leave none there)
+ *   img != NULL   img is uploaded first and stays resident
+ * n == 0 is SPVO_OK.  Runs on the solver's stream; scratch lives in the context and grows on shape change.
+ *   SPVO_ERR_INVALID   nothing is written, uploaded or replaced: a record whose x, y, size or angle is not finite or whose size is not
+ *                      positive, an unpacked octave < -1, a layer > 5, an octave whose level would be empty (min(rows, cols) >> o < 1)
+ *                      or more than 16 octaves, an image spvo_sift_detect refuses
+ *   SPVO_ERR_STATE     a spvo_detect*_submit is in flight; img == NULL and no image of that shape is resident */
+int spvo_sift_describe(spvo_ctx *ctx, const uint8_t *img /* or NULL */, int rows, int cols, size_t stride,
+                       const spvo_sift_keypoint *kp, int n, float *desc /* [n][128] */);
 
 /* detectKeypoints for DetectorType::BRISK (cv::BRISK::create() -> detect, feature_detection_classic.cpp:9-11: threshold 30, 3 octaves, pattern
  * scale 1) on one 8-bit image in host memory: the six-layer scale space (layer 1 = two-thirds of the image, layer i >= 2 = half of layer
@@ -342,7 +366,7 @@ int spvo_brisk_detect(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, siz
 /* A layer of the scale space of this context's last spvo_brisk_detect (test hook): what = 0 the layer's image, 1 its AGAST 9-16 score map,
  * 2 (layer 0 only) the 5-8 score map.  `out` (rows x cols bytes) may be NULL to ask for the shape only.  SPVO_ERR_STATE when no result is
  * resident: no call yet, or any other call has since put an image into the context's resident image buffer (spvo_gftt_detect,
- * spvo_fast_detect, spvo_orb_describe / spvo_brisk_describe with an image, spvo_classic_detect, spvo_brisk_detect_pair,
+ * spvo_fast_detect, spvo_orb_describe / spvo_brisk_describe / spvo_sift_describe with an image, spvo_classic_detect, spvo_brisk_detect_pair,
  * spvo_akaze_detect_pair), the same image
  * included. */
 int spvo_brisk_detect_debug_layer(spvo_ctx *ctx, int layer, int what, uint8_t *out, int *rows, int *cols);

@@ -13,6 +13,10 @@
 // per peak through a second counter).  The host copies the records once, builds the keypoints, sorts them by OpenCV's total order and
 // drops duplicates (spvo_sift.hip): n is a few thousand.  spvo_sift_detect_pair does that on the device instead (the ordering kernels at
 // the end of this file) and keeps the features in a slot.
+// The extractor on GIVEN keypoints (spvo_sift_describe, tests/sift_describe_ref.py): sift_blur_kernel x 6 per octave the list names, without
+// the differences (MODE 3: the base at the image's own size when no record lies on octave -1) -> sift_describe_given_kernel, a wave per
+// record with the per-sample device code of sift_describe_kernel (sift_patch, sift_patch_sample, sift_share_bin, sift_desc_store) and sums
+// of its own that take no turns.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -54,7 +58,8 @@ __device__ __forceinline__ float sift_upsample(const uint8_t *img, int sh, int s
 
 // One separable blur, rows then columns, both from LDS.  MODE 0: src is a level of the same size.  MODE 1: src is layer 3 of the octave
 // below (sh x sw), read at every second pixel; the decimated image itself is stored as layer 0 (g0).  MODE 2: src is the u8 image
-// (sh x sw), upsampled 2x on the fly.  dog (may be NULL) receives dst - source: the difference of Gaussians this layer completes.
+// (sh x sw), upsampled 2x on the fly.  MODE 3: src is the u8 image at its own size (spvo_sift_describe on a list without octave -1).  dog (may
+// be NULL) receives dst - source: the difference of Gaussians this layer completes.
 template <int MODE>
 __global__ __launch_bounds__(256) void sift_blur_kernel(const void *__restrict__ src_, int sh, int sw, float *__restrict__ dst, float *__restrict__ dog,
                                                         float *__restrict__ g0, int h, int w, SiftTaps tp) {
@@ -69,7 +74,8 @@ __global__ __launch_bounds__(256) void sift_blur_kernel(const void *__restrict__
     float v;
     if (MODE == 0) v = static_cast<const float *>(src_)[(size_t)gy * w + gx];
     else if (MODE == 1) v = static_cast<const float *>(src_)[(size_t)(2 * gy) * sw + 2 * gx];
-    else v = sift_upsample(static_cast<const uint8_t *>(src_), sh, sw, gy, gx);
+    else if (MODE == 2) v = sift_upsample(static_cast<const uint8_t *>(src_), sh, sw, gy, gx);
+    else v = (float)static_cast<const uint8_t *>(src_)[(size_t)gy * sw + gx];
     tile[ty][tx] = v;
   }
   __syncthreads();
@@ -191,6 +197,80 @@ __device__ __forceinline__ float sift_wave_sum(float v) {   // every lane gets t
   return v;
 }
 
+// ---- stage 6 of tests/sift_ref.py, the device code both describe kernels share: the frame of a patch, one sample of it, and the last
+// step from the 128 sums to the stored row.  How the samples' eight contributions are ADDED is each kernel's own business.
+struct SiftPatch { int px, py, radius; float ori, cos_t, sin_t; };
+
+// the patch of a keypoint at (px, py) of an h x w level with scale scl and `angle` (degrees, cv::KeyPoint's)
+__device__ __forceinline__ SiftPatch sift_patch(float scl, float angle, int px, int py, int h, int w) {
+  SiftPatch t;
+  float ori = 360.f - angle;
+  if (fabsf(ori - 360.f) < 1.1920929e-7f) ori = 0.f;
+  const float hist_width = 3.f * scl;
+  int radius = (int)rintf(hist_width * 1.4142135623730951f * 5.f * 0.5f);
+  radius = min(radius, (int)sqrt((double)w * w + (double)h * h));
+  t.px = px; t.py = py; t.radius = radius; t.ori = ori;
+  t.cos_t = cosf(ori * 0.017453292519943295f) / hist_width;
+  t.sin_t = sinf(ori * 0.017453292519943295f) / hist_width;
+  return t;
+}
+
+// the sample at offset (di, dj): false when it contributes nothing; else the bins (r0, c0 in -1..3, o0 in -1..7) and the eight trilinear
+// shares v[e], share e for sift_share_bin(r0, c0, o0, e)
+__device__ __forceinline__ bool sift_patch_sample(const float *__restrict__ G, int h, int w, const SiftPatch &t, bool in_range, int di, int dj, int &r0, int &c0, int &o0,
+                                                  float (&v)[8]) {
+  const int y = t.py + di, x = t.px + dj;
+  const float cos_t = t.cos_t, sin_t = t.sin_t, ori = t.ori;
+  const float c_rot = dj * cos_t - di * sin_t, r_rot = dj * sin_t + di * cos_t;
+  float rbin = r_rot + 1.5f, cbin = c_rot + 1.5f;
+  const bool ok = in_range && rbin > -1.f && rbin < 4.f && cbin > -1.f && cbin < 4.f && y > 0 && y < h - 1 && x > 0 && x < w - 1;
+  r0 = 0; c0 = 0; o0 = 0;
+  if (ok) {
+    const float *g = G + (size_t)y * w + x;
+    const float dx = g[1] - g[-1], dy = g[-w] - g[w];
+    float ang = atan2f(dy, dx) * 57.29577951308232f;
+    if (ang < 0.f) ang += 360.f;
+    const float mag = sqrtf(dx * dx + dy * dy) * expf((c_rot * c_rot + r_rot * r_rot) * -0.125f);
+    float obin = (ang - ori) * (8.f / 360.f);
+    const float fr = floorf(rbin), fc = floorf(cbin), fo = floorf(obin);
+    rbin -= fr; cbin -= fc; obin -= fo;
+    r0 = (int)fr; c0 = (int)fc; o0 = (int)fo;
+    if (o0 < 0) o0 += 8;
+    if (o0 >= 8) o0 -= 8;
+    // (one wrap, as the rule has it: an orientation of 361 -- angle -1 -- leaves o0 = -1 for gradient angles below one degree, see
+    // sift_share_bin; an orientation outside -360 .. 720, for which the rule defines nothing, is wrapped all the way)
+    if (o0 < -1 || o0 > 7) o0 &= 7;
+    const float v_r1 = mag * rbin, v_r0 = mag - v_r1;
+    const float v_rc11 = v_r1 * cbin, v_rc10 = v_r1 - v_rc11, v_rc01 = v_r0 * cbin, v_rc00 = v_r0 - v_rc01;
+    v[1] = v_rc00 * obin; v[0] = v_rc00 - v[1];
+    v[3] = v_rc01 * obin; v[2] = v_rc01 - v[3];
+    v[5] = v_rc10 * obin; v[4] = v_rc10 - v[5];
+    v[7] = v_rc11 * obin; v[6] = v_rc11 - v[7];
+  }
+  return ok;
+}
+
+// the bin (0 .. 127) share e of a sample is added to, or -1 when it falls into the border the rule discards.  The rule's histogram is
+// hist[(r + 1) * 6 + (c + 1)][o] with TEN orientation slots per cell, slots 8 and 9 folded into 0 and 1 at the end: o0 = -1 makes the
+// first share of a pair land in slot 9 of the cell BEFORE (r, c) -- orientation 1 of column c - 1, or nowhere when that is the border --
+// and the second in slot 0 of (r, c).  tests/sift_ref.py and OpenCV index the same way; with an orientation below 360 o0 is 0 .. 7.
+__device__ __forceinline__ int sift_share_bin(int r0, int c0, int o0, int e) {
+  const int rr = r0 + (e >> 2);
+  int cc = c0 + ((e >> 1) & 1), oo = o0 + (e & 1);
+  if (oo < 0) { cc -= 1; oo = 1; }
+  else oo &= 7;
+  return rr >= 0 && rr < 4 && cc >= 0 && cc < 4 ? (rr * 4 + cc) * 8 + oo : -1;
+}
+
+// bins `lane` (d0) and `lane + 64` (d1) of the 128 sums -> the row: 0.2 clamp, x512, round, saturate
+__device__ __forceinline__ void sift_desc_store(float d0, float d1, float *__restrict__ row, int lane) {
+  const float thr2 = sqrtf(sift_wave_sum(d0 * d0 + d1 * d1)) * 0.2f;
+  d0 = fminf(d0, thr2); d1 = fminf(d1, thr2);
+  const float nrm = 512.f / fmaxf(sqrtf(sift_wave_sum(d0 * d0 + d1 * d1)), 1.1920929e-7f);
+  row[lane] = fminf(fmaxf(rintf(d0 * nrm), 0.f), 255.f);
+  row[64 + lane] = fminf(fmaxf(rintf(d1 * nrm), 0.f), 255.f);
+}
+
 // Orientation and descriptor of every surviving candidate: one wave (= one workgroup) per candidate, lanes over the patch.  A peak of the
 // smoothed 36-bin histogram is one keypoint: row `slot` (counter[1], which keeps counting beyond kp_cap) of kp = {candidate, angle bits}
 // and of desc (128 integers 0..255 as float).
@@ -270,48 +350,22 @@ __global__ __launch_bounds__(64) void sift_describe_kernel(SiftPyr P, const int4
       b = b < 0.f ? 36.f + b : (b >= 36.f ? b - 36.f : b);
       float angle = 360.f - 10.f * b;
       if (fabsf(angle - 360.f) < 1.1920929e-7f) angle = 0.f;
-      float ori = 360.f - angle;
-      if (fabsf(ori - 360.f) < 1.1920929e-7f) ori = 0.f;
       const int px = __float2int_rn(add_rn((float)c, f.z)), py = __float2int_rn(add_rn((float)r, f.y));
-      const float hist_width = 3.f * scl;
-      int radius = (int)rintf(hist_width * 1.4142135623730951f * 5.f * 0.5f);
-      radius = min(radius, (int)sqrt((double)w * w + (double)h * h));
-      const float cos_t = cosf(ori * 0.017453292519943295f) / hist_width, sin_t = sinf(ori * 0.017453292519943295f) / hist_width;
-      const int side = 2 * radius + 1, total = side * side;
+      const SiftPatch pt = sift_patch(scl, angle, px, py, h, w);
+      const int radius = pt.radius, side = 2 * radius + 1, total = side * side;
       for (int k = lane; k < 128 * SIFT_COLS; k += 64) hist[k] = 0.f;
       __syncthreads();
       for (int k0 = 0; k0 < total; k0 += 64) {
-        const int k = k0 + lane, di = k / side - radius, dj = k % side - radius, y = py + di, x = px + dj;
-        const float c_rot = dj * cos_t - di * sin_t, r_rot = dj * sin_t + di * cos_t;
-        float rbin = r_rot + 1.5f, cbin = c_rot + 1.5f;
-        const bool ok = k < total && rbin > -1.f && rbin < 4.f && cbin > -1.f && cbin < 4.f && y > 0 && y < h - 1 && x > 0 && x < w - 1;
-        int r0 = 0, c0 = 0, o0 = 0;
+        const int k = k0 + lane, di = k / side - radius, dj = k % side - radius;
+        int r0, c0, o0;
         float v[8];
-        if (ok) {
-          const float *g = G + (size_t)y * w + x;
-          const float dx = g[1] - g[-1], dy = g[-w] - g[w];
-          float ang = atan2f(dy, dx) * 57.29577951308232f;
-          if (ang < 0.f) ang += 360.f;
-          const float mag = sqrtf(dx * dx + dy * dy) * expf((c_rot * c_rot + r_rot * r_rot) * -0.125f);
-          float obin = (ang - ori) * (8.f / 360.f);
-          const float fr = floorf(rbin), fc = floorf(cbin), fo = floorf(obin);
-          rbin -= fr; cbin -= fc; obin -= fo;
-          r0 = (int)fr; c0 = (int)fc; o0 = (int)fo;
-          if (o0 < 0) o0 += 8;
-          if (o0 >= 8) o0 -= 8;
-          const float v_r1 = mag * rbin, v_r0 = mag - v_r1;
-          const float v_rc11 = v_r1 * cbin, v_rc10 = v_r1 - v_rc11, v_rc01 = v_r0 * cbin, v_rc00 = v_r0 - v_rc01;
-          v[1] = v_rc00 * obin; v[0] = v_rc00 - v[1];
-          v[3] = v_rc01 * obin; v[2] = v_rc01 - v[3];
-          v[5] = v_rc10 * obin; v[4] = v_rc10 - v[5];
-          v[7] = v_rc11 * obin; v[6] = v_rc11 - v[7];
-        }
+        const bool ok = sift_patch_sample(G, h, w, pt, k < total, di, dj, r0, c0, o0, v);
         for (int tn = 0; tn < 4; ++tn) {
           if (ok && turn == tn) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-              const int rr = r0 + (e >> 2), cc = c0 + ((e >> 1) & 1), oo = (o0 + (e & 1)) & 7;
-              if (rr >= 0 && rr < 4 && cc >= 0 && cc < 4) hist[((rr * 4 + cc) * 8 + oo) * SIFT_COLS + col] += v[e];
+              const int bin = sift_share_bin(r0, c0, o0, e);
+              if (bin >= 0) hist[bin * SIFT_COLS + col] += v[e];
             }
           }
           __syncthreads();
@@ -319,15 +373,96 @@ __global__ __launch_bounds__(64) void sift_describe_kernel(SiftPyr P, const int4
       }
       float d0 = 0.f, d1 = 0.f;
       for (int k = 0; k < SIFT_COLS; ++k) { d0 += hist[lane * SIFT_COLS + k]; d1 += hist[(lane + 64) * SIFT_COLS + k]; }
-      const float thr2 = sqrtf(sift_wave_sum(d0 * d0 + d1 * d1)) * 0.2f;
-      d0 = fminf(d0, thr2); d1 = fminf(d1, thr2);
-      const float nrm = 512.f / fmaxf(sqrtf(sift_wave_sum(d0 * d0 + d1 * d1)), 1.1920929e-7f);
-      desc[(size_t)slot * 128 + lane] = fminf(fmaxf(rintf(d0 * nrm), 0.f), 255.f);
-      desc[(size_t)slot * 128 + 64 + lane] = fminf(fmaxf(rintf(d1 * nrm), 0.f), 255.f);
+      sift_desc_store(d0, d1, desc + (size_t)slot * 128, lane);
       if (lane == 0) kp[slot] = make_int2(i, __float_as_int(angle));
       __syncthreads();   // (hist is cleared for the next peak / candidate)
     }
     __syncthreads();   // (sm_base, sm_h are rewritten by the next candidate)
+  }
+}
+
+// The descriptor of GIVEN keypoints (spvo_sift_describe: tests/sift_describe_ref.py): one wave (= one workgroup) per record, row i for
+// record i.  The pyramid is Gaussian-only and starts at octave `first` (0 or -1): a record's level is octave o - first, layer `layer` of
+// its packed field; point, scale and orientation by the restatement's choice 5 in separately rounded operations.  The patch is walked in
+// tiles of 16 x 4 samples over the rows and columns that lie inside the level (a radius reaches the level's diagonal: no sample index is
+// ever formed, so nothing overflows), and the samples are those of sift_patch_sample.  The sums are deterministic and take no turns:
+//   FORM 0   a lane adds into a column of its own, hist[bin][lane] (128 x 64 floats = 32 KB; bank = lane: never a conflict); at the end lane b
+//            sums row b and row b + 64 starting at column b (bank b + l: no conflict either), a fixed order per bin
+//   FORM 1   the tile's samples are staged in LDS (bins packed in a word, eight shares), lane b owns bins b and b + 64 in registers and
+//            walks the tile's valid samples in lane order, adding the share that falls into its bin (the measurement's other form)
+template <int FORM>
+__global__ __launch_bounds__(64) void sift_describe_given_kernel(SiftPyr P, int first, const SiftKey *__restrict__ kp, int n, float *__restrict__ desc) {
+  constexpr int TW = 16, TH = 4;
+  __shared__ float lds[FORM == 0 ? 128 * 64 : 8 * 64];
+  __shared__ int code[64];
+  const int lane = threadIdx.x;
+  for (int i = blockIdx.x; i < n; i += gridDim.x) {
+    const SiftKey k = kp[i];
+    int o = k.octave & 255;
+    if (o >= 128) o -= 256;
+    const int layer = (k.octave >> 8) & 255, lvl = o - first, h = P.h[lvl], w = P.w[lvl];
+    const float scale = __int_as_float((127 - o) << 23);   // 1 / 2^o, 2^-o: exact
+    const float *G = P.pyr + P.g_off[lvl] + (size_t)layer * h * w;
+    const int px = __float2int_rn(mul_rn(k.x, scale)), py = __float2int_rn(mul_rn(k.y, scale));
+    const float scl = mul_rn(mul_rn(k.size, scale), 0.5f);
+    const SiftPatch pt = sift_patch(scl, k.angle, px, py, h, w);
+    // rows and columns of the patch that hold pixels with all four neighbours (64-bit: a point may lie anywhere)
+    const long long i0 = max(-(long long)pt.radius, 1ll - py), i1 = min((long long)pt.radius, (long long)h - 2 - py);
+    const long long j0 = max(-(long long)pt.radius, 1ll - px), j1 = min((long long)pt.radius, (long long)w - 2 - px);
+    const int ni = i0 <= i1 ? (int)(i1 - i0 + 1) : 0, nj = j0 <= j1 ? (int)(j1 - j0 + 1) : 0;   // (<= h, <= w)
+    const int di0 = ni ? (int)i0 : 0, dj0 = nj ? (int)j0 : 0, ly = lane >> 4, lx = lane & 15;
+    float d0 = 0.f, d1 = 0.f;
+    if (FORM == 0) {
+      for (int q = lane; q < 128 * 64; q += 64) lds[q] = 0.f;
+      __syncthreads();
+    }
+    for (int ty = 0; ty < ni && nj > 0; ty += TH)
+      for (int tx = 0; tx < nj; tx += TW) {
+        const int a = ty + ly, b = tx + lx;
+        int r0, c0, o0;
+        float v[8];
+        const bool ok = sift_patch_sample(G, h, w, pt, a < ni && b < nj, di0 + a, dj0 + b, r0, c0, o0, v);
+        if (FORM == 0) {
+          if (ok) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+              const int bin = sift_share_bin(r0, c0, o0, e);
+              if (bin >= 0) lds[bin * 64 + lane] += v[e];
+            }
+          }
+        } else {
+          unsigned long long m = __ballot(ok);
+          if (m == 0) continue;   // (the same in every lane)
+          code[lane] = (r0 + 1) | ((c0 + 1) << 4) | ((o0 + 1) << 8);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) lds[e * 64 + lane] = ok ? v[e] : 0.f;
+          __syncthreads();
+          while (m) {
+            const int s = __ffsll((long long)m) - 1;
+            m &= m - 1;
+            const int cd = code[s], sr = (cd & 15) - 1, sc = ((cd >> 4) & 15) - 1, so = (cd >> 8) - 1, O = lane & 7;
+            // (sift_share_bin read backwards: which share of sample s falls into orientation O of this lane's column)
+            const int dO = so >= 0 ? ((O - so) & 7) : (O == 0 ? 1 : (O == 1 ? 0 : 2)), dc = ((lane >> 3) & 3) - sc + (so < 0 && O == 1 ? 1 : 0);
+            const int dr0 = (lane >> 5) - sr, dr1 = dr0 + 2;
+            if ((unsigned)dc < 2u && dO < 2) {
+              const int e = dc * 2 + dO;
+              if ((unsigned)dr0 < 2u) d0 += lds[(dr0 * 4 + e) * 64 + s];
+              if ((unsigned)dr1 < 2u) d1 += lds[(dr1 * 4 + e) * 64 + s];
+            }
+          }
+          __syncthreads();   // (the staging is rewritten by the next tile)
+        }
+      }
+    if (FORM == 0) {
+      __syncthreads();
+      for (int l = 0; l < 64; ++l) {
+        const int cidx = (lane + l) & 63;
+        d0 += lds[lane * 64 + cidx];
+        d1 += lds[(lane + 64) * 64 + cidx];
+      }
+      __syncthreads();   // (the columns are cleared for the next record)
+    }
+    sift_desc_store(d0, d1, desc + (size_t)i * 128, lane);
   }
 }
 

@@ -466,6 +466,11 @@ struct spvo_ctx {
   struct SiftBufs {
     int rows = 0, cols = 0;               // shape of the image whose pyramid is resident (0: none)
     SiftPyr plan{};
+    bool gauss_only = false;              // the resident pyramid is spvo_sift_describe's: Gaussian levels only, octave index 0 = octave `first`
+    int first = -1;
+    SiftKey *given_kp = nullptr;          // spvo_sift_describe: the caller's records and their rows, `given_cap` of each
+    float *given_desc = nullptr;
+    int given_cap = 0;
     size_t img_cap = 0, pyr_cap = 0;      // bytes / floats
     int cand_cap = 0;                     // candidates, and output rows, the lists hold
     uint8_t *img = nullptr;

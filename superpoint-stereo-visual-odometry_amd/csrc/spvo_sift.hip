@@ -6,6 +6,8 @@
 // of the two: the host's records are built by ONE function (sift_record) from {candidate, offsets, angle bits}, which the device hands
 // over per final row; the device-computed size is a sort key only, and rows of one candidate get identical keys on the device as on the
 // host, so ties and duplicates are the same.  Runs on the solver's stream (stream2), like the rest of the classic front end.
+// spvo_sift_describe is the extractor alone on a caller's records: it reads the u8 image the Shi-Tomasi / FAST / BRISK / AKAZE detectors and
+// the other extractors keep resident (spvo_ctx::cls), builds a Gaussian-only pyramid in the same buffer and describes in one launch.
 #include "spvo_internal.hip.h"
 #include "sift.hip.h"
 
@@ -79,13 +81,14 @@ int sift_ensure(spvo_ctx *c, int rows, int cols, size_t pyr_floats, int cand_cap
   return SPVO_OK;
 }
 
-// the pyramid of the resident image: 1 + 5 launches per octave, every difference of Gaussians written by the blur that completes it
-int sift_enqueue_pyramid(spvo_ctx *c, int rows, int cols, const SiftPyr &P) {
-  auto &s = c->sift;
+// the pyramid of the u8 image `src` (rows x cols, packed): 1 + 5 launches per octave.  doubled: the base is the 2x upsampled image (first
+// octave -1), else the image at its own size (first octave 0: spvo_sift_describe).  with_dog: every difference of Gaussians is written by
+// the blur that completes it; without, P holds Gaussian levels only
+int sift_enqueue_pyramid(spvo_ctx *c, const uint8_t *src, int rows, int cols, const SiftPyr &P, bool doubled = true, bool with_dog = true) {
   hipStream_t st = c->stream2;
   const double k = std::pow(2.0, 1.0 / 3.0), sigma = 1.6;
   SiftTaps tp[SIFT_GAUSS];
-  if (!sift_taps(std::sqrt(std::max(sigma * sigma - 4 * 0.5 * 0.5, 0.01)), tp[0])) return fail(c, SPVO_ERR_INVALID, "spvo_sift_detect: blur radius above %d", SIFT_MAX_R);
+  if (!sift_taps(std::sqrt(std::max(sigma * sigma - (doubled ? 4 : 1) * 0.5 * 0.5, 0.01)), tp[0])) return fail(c, SPVO_ERR_INVALID, "spvo_sift_detect: blur radius above %d", SIFT_MAX_R);
   for (int i = 1; i < SIFT_GAUSS; ++i) {
     const double prev = std::pow(k, (double)(i - 1)) * sigma, total = prev * k;
     if (!sift_taps(std::sqrt(total * total - prev * prev), tp[i])) return fail(c, SPVO_ERR_INVALID, "spvo_sift_detect: blur radius above %d", SIFT_MAX_R);
@@ -93,18 +96,19 @@ int sift_enqueue_pyramid(spvo_ctx *c, int rows, int cols, const SiftPyr &P) {
   for (int o = 0; o < P.n_oct; ++o) {
     const int h = P.h[o], w = P.w[o];
     const size_t lvl = (size_t)h * w;
-    float *G = P.pyr + P.g_off[o], *D = P.pyr + P.d_off[o];
+    float *G = P.pyr + P.g_off[o], *D = with_dog ? P.pyr + P.d_off[o] : nullptr;
     const dim3 grid((w + SIFT_TW - 1) / SIFT_TW, (h + SIFT_TH - 1) / SIFT_TH);
     if (o == 0) {
-      hipLaunchKernelGGL(sift_blur_kernel<2>, grid, dim3(256), 0, st, (const void *)s.img, rows, cols, G, (float *)nullptr, (float *)nullptr, h, w, tp[0]);
+      if (doubled) hipLaunchKernelGGL(sift_blur_kernel<2>, grid, dim3(256), 0, st, (const void *)src, rows, cols, G, (float *)nullptr, (float *)nullptr, h, w, tp[0]);
+      else hipLaunchKernelGGL(sift_blur_kernel<3>, grid, dim3(256), 0, st, (const void *)src, rows, cols, G, (float *)nullptr, (float *)nullptr, h, w, tp[0]);
       hipLaunchKernelGGL(sift_blur_kernel<0>, grid, dim3(256), 0, st, (const void *)G, h, w, G + lvl, D, (float *)nullptr, h, w, tp[1]);
     } else {
       const float *below = P.pyr + P.g_off[o - 1] + (size_t)SIFT_LAYERS * P.h[o - 1] * P.w[o - 1];
       hipLaunchKernelGGL(sift_blur_kernel<1>, grid, dim3(256), 0, st, (const void *)below, P.h[o - 1], P.w[o - 1], G + lvl, D, G, h, w, tp[1]);
     }
     for (int i = 2; i < SIFT_GAUSS; ++i)
-      hipLaunchKernelGGL(sift_blur_kernel<0>, grid, dim3(256), 0, st, (const void *)(G + (size_t)(i - 1) * lvl), h, w, G + (size_t)i * lvl, D + (size_t)(i - 1) * lvl, (float *)nullptr, h, w,
-                         tp[i]);
+      hipLaunchKernelGGL(sift_blur_kernel<0>, grid, dim3(256), 0, st, (const void *)(G + (size_t)(i - 1) * lvl), h, w, G + (size_t)i * lvl, D ? D + (size_t)(i - 1) * lvl : nullptr, (float *)nullptr,
+                         h, w, tp[i]);
   }
   HIP_TRY(c, hipGetLastError());
   return SPVO_OK;
@@ -221,7 +225,8 @@ int sift_slots_ensure(spvo_ctx *c, int cap, size_t px) {
 void spvo_int::sift_release(spvo_ctx *c) {
   auto &s = c->sift;
   sift_release_slots(c);
-  dev_free(s.img, s.pyr, s.desc, s.cand_pos, s.cand_off, s.kp, s.counters, s.keys, s.sorted, s.order, s.ord_n);
+  dev_free(s.img, s.pyr, s.desc, s.cand_pos, s.cand_off, s.kp, s.counters, s.keys, s.sorted, s.order, s.ord_n, s.given_kp, s.given_desc);
+  s.given_cap = 0;
   host_free(s.h_match);
   s.h_match_cap = 0;
   s.pair.release();
@@ -245,8 +250,8 @@ int spvo_sift_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t
   if (int rc = sift_ensure(c, rows, cols, pyr_floats, cand_cap)) return rc;
   P.pyr = s.pyr;
   HIP_TRY(c, hipMemcpy2DAsync(s.img, cols, img, stride, cols, rows, hipMemcpyHostToDevice, st));
-  if (int rc = sift_enqueue_pyramid(c, rows, cols, P)) return rc;
-  s.plan = P; s.rows = rows; s.cols = cols;
+  if (int rc = sift_enqueue_pyramid(c, s.img, rows, cols, P)) return rc;
+  s.plan = P; s.rows = rows; s.cols = cols; s.gauss_only = false;
   int cnt[4] = {0, 0, 0, 0};
   for (int attempt = 0;; ++attempt) {
     if (int rc = sift_enqueue_features(c, P)) return rc;
@@ -358,8 +363,8 @@ int spvo_sift_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_
     for (int k = 0; k < 2; ++k) {   // left chain, then the right one: the one resident pyramid is reused in stream order
       s.rows = s.cols = 0;
       HIP_TRY(c, hipMemcpyAsync(s.img, ps.h_img + k * px, px, hipMemcpyHostToDevice, st));
-      if (int rc = sift_enqueue_pyramid(c, rows, cols, P)) return rc;
-      s.plan = P; s.rows = rows; s.cols = cols;
+      if (int rc = sift_enqueue_pyramid(c, s.img, rows, cols, P)) return rc;
+      s.plan = P; s.rows = rows; s.cols = cols; s.gauss_only = false;
       if (int rc = sift_enqueue_features(c, P)) return rc;
       if (int rc = sift_enqueue_order(c, s.slots[slots[k]], k)) return rc;
     }
@@ -412,6 +417,80 @@ int spvo_sift_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_
   return SPVO_OK;
 }
 
+// tests/sift_describe_ref.py.  Everything a record can be refused for is checked on the host before anything is touched; the kernel then
+// indexes levels that exist.
+int spvo_sift_describe(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride, const spvo_sift_keypoint *kp, int n, float *desc) {
+  static_assert(sizeof(spvo_sift_keypoint) == sizeof(SiftKey), "keypoint records differ");
+  if (!c || rows <= 0 || cols <= 0 || n < 0 || (n > 0 && (!kp || !desc)) || (img && stride < (size_t)cols)) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  if (int rc = sift_check_image(c, "spvo_sift_describe", rows, cols)) return rc;
+  int lo = 0, hi = 0;   // the octaves the list spans, 0 included
+  for (int i = 0; i < n; ++i) {
+    const spvo_sift_keypoint &k = kp[i];
+    if (!std::isfinite(k.x) || !std::isfinite(k.y) || !std::isfinite(k.size) || !std::isfinite(k.angle) || !(k.size > 0))
+      return fail(c, SPVO_ERR_INVALID, "spvo_sift_describe: keypoint %d has x %g, y %g, size %g, angle %g", i, (double)k.x, (double)k.y, (double)k.size, (double)k.angle);
+    int o = k.octave & 255;
+    if (o >= 128) o -= 256;
+    const int layer = (k.octave >> 8) & 255;
+    if (o < -1 || layer >= SIFT_GAUSS) return fail(c, SPVO_ERR_INVALID, "spvo_sift_describe: keypoint %d has octave %d, layer %d (octaves from -1, layers 0 .. %d)", i, o, layer, SIFT_GAUSS - 1);
+    if (o > 0 && (o >= 31 || (std::min(rows, cols) >> o) < 1)) return fail(c, SPVO_ERR_INVALID, "spvo_sift_describe: keypoint %d: a %d x %d image has no octave %d", i, rows, cols, o);
+    lo = std::min(lo, o); hi = std::max(hi, o);
+  }
+  const int first = lo, n_oct = hi - lo + 1;
+  if (n_oct > SIFT_MAX_OCT) return fail(c, SPVO_ERR_INVALID, "spvo_sift_describe: %d octaves (at most %d)", n_oct, SIFT_MAX_OCT);
+  if (int rc = require_idle(c)) return rc;
+  auto &b = c->cls;
+  if (!img && (b.rows != rows || b.cols != cols))
+    return fail(c, SPVO_ERR_STATE, "spvo_sift_describe: no image of %d x %d is resident (call a detector first, or pass the image)", rows, cols);
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = c->stream2;
+  if (img) {
+    if (int rc = classic_upload_image(c, img, rows, cols, stride)) return rc;
+  }
+  if (n == 0) {
+    HIP_TRY(c, hipStreamSynchronize(st));   // (the caller's image may be in flight)
+    return SPVO_OK;
+  }
+  auto &s = c->sift;
+  SiftPyr P{};
+  P.n_oct = n_oct;
+  size_t pyr_floats = 0;
+  for (int o = 0, h = first < 0 ? 2 * rows : rows, w = first < 0 ? 2 * cols : cols; o < n_oct; ++o, h /= 2, w /= 2) {
+    P.h[o] = h; P.w[o] = w;
+    P.g_off[o] = (long long)pyr_floats; P.d_off[o] = 0;
+    pyr_floats += (size_t)SIFT_GAUSS * h * w;
+  }
+  s.rows = s.cols = 0;   // nothing resident until the pyramid is enqueued
+  if (pyr_floats > s.pyr_cap) {
+    HIP_TRY(c, hipStreamSynchronize(st));
+    dev_free(s.pyr);
+    s.pyr_cap = 0;
+    if (int rc = dev_alloc(c, &s.pyr, pyr_floats, false)) return rc;
+    s.pyr_cap = pyr_floats;
+  }
+  if (n > s.given_cap) {
+    HIP_TRY(c, hipStreamSynchronize(st));
+    dev_free(s.given_kp, s.given_desc);
+    const int cap = (int)std::min<long long>(std::max<long long>(n, 2ll * s.given_cap), 0x7FFFFFFF);   // (grown geometrically: a count that creeps up reallocates rarely)
+    s.given_cap = 0;
+    int rc;
+    if ((rc = dev_alloc(c, &s.given_kp, cap, false)) || (rc = dev_alloc(c, &s.given_desc, (size_t)cap * 128, false))) return rc;
+    s.given_cap = cap;
+  }
+  P.pyr = s.pyr;
+  HIP_TRY(c, hipMemcpyAsync(s.given_kp, kp, (size_t)n * sizeof(SiftKey), hipMemcpyHostToDevice, st));
+  if (int rc = sift_enqueue_pyramid(c, b.im, rows, cols, P, first < 0, false)) return rc;
+  s.plan = P; s.rows = rows; s.cols = cols; s.gauss_only = true; s.first = first;
+  // (diagnostic, tuning "sift_describe_form": 1 = the staged form NOTES.md measures against the columns)
+  if (tuning("sift_describe_form", 0) == 1)
+    hipLaunchKernelGGL(sift_describe_given_kernel<1>, dim3(std::min(n, 65536)), dim3(64), 0, st, P, first, (const SiftKey *)s.given_kp, n, s.given_desc);
+  else
+    hipLaunchKernelGGL(sift_describe_given_kernel<0>, dim3(std::min(n, 65536)), dim3(64), 0, st, P, first, (const SiftKey *)s.given_kp, n, s.given_desc);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(desc, s.given_desc, (size_t)n * 128 * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));   // the one wait of the call
+  return SPVO_OK;
+}
+
 int spvo_sift_order_debug(spvo_ctx *c, const spvo_sift_keypoint *rec, int n, int32_t *order, int *n_kept) {
   static_assert(sizeof(spvo_sift_keypoint) == sizeof(SiftKey), "keypoint records differ");
   if (!c || !n_kept || n < 0 || n > (1 << 20) || (n > 0 && (!rec || !order))) return fail(c, SPVO_ERR_INVALID, "bad argument");
@@ -436,6 +515,7 @@ int spvo_sift_debug_level(spvo_ctx *c, int octave, int layer, int dog, float *ou
   if (!c) return fail(c, SPVO_ERR_INVALID, "null context");
   auto &s = c->sift;
   if (s.rows == 0) return fail(c, SPVO_ERR_STATE, "spvo_sift_debug_level: no pyramid is resident (call spvo_sift_detect first)");
+  if (dog && s.gauss_only) return fail(c, SPVO_ERR_STATE, "spvo_sift_debug_level: the resident pyramid is spvo_sift_describe's, which builds no difference of Gaussians");
   if (octave < 0 || octave >= s.plan.n_oct || layer < 0 || layer >= (dog ? SIFT_DOG : SIFT_GAUSS)) return fail(c, SPVO_ERR_INVALID, "spvo_sift_debug_level: no such level");
   const int h = s.plan.h[octave], w = s.plan.w[octave];
   if (rows) *rows = h;

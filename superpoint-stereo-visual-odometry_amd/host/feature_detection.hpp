@@ -378,7 +378,7 @@ private:
   struct Staging { std::vector<uint8_t> records, rows; };
   Staging staging_[2];
   template <class Features, class Call> bool residentPair(const ClassicPair &pair, cv::Mat &img_l, cv::Mat &img_r, const char *name, Call call);
-  cv::Mat orb_desc_;   // descriptors of the image detectKeypoints saw last (spvo_orb_detect / spvo_sift_detect: one pass for both)
+  cv::Mat orb_desc_;   // descriptors of the image detectKeypoints saw last (ORB + ORB, SIFT + SIFT: spvo_orb_detect / spvo_sift_detect, one pass for both)
   // the image detectKeypoints saw last is still on the device (unless it was described in the same pass); describeKeypoints on the same image does not upload it again
   const void *detected_data_ = nullptr;
   int detected_rows_ = 0, detected_cols_ = 0;

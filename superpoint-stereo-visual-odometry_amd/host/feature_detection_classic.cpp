@@ -79,14 +79,15 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
   }
 }
 #else
-// Without OpenCV the pairs of kClassicPairs run, on the GPU, and every other combination is refused.  What the table cannot say: ORB and
-// SIFT describe in the detector's pass, so detectKeypoints keeps the rows for the describeKeypoints call that follows on the same image;
-// every other detector leaves the image (AKAZE: its scale space) on the device for the extractor.  The AKAZE extractor needs the level in
+// Without OpenCV the pairs of kClassicPairs run, on the GPU, and every other combination is refused.  What the table cannot say: ORB + ORB and
+// SIFT + SIFT describe in the detector's pass, so detectKeypoints keeps the rows for the describeKeypoints call that follows on the same image;
+// every other detector leaves the image (AKAZE: its scale space) on the device for the extractor -- except ORB, which keeps a pyramid of its
+// own: ORB + SIFT uploads the image a second time.  The AKAZE extractor needs the level in
 // class_id, which only AKAZE keypoints carry -- OpenCV's own assertion refuses the others too.
 bool ClassicFeatureFrontEnd::available() { return true; }
 
 enum class Detect { Orb, Gftt, Fast, Sift, Brisk, Akaze };       // detectKeypoints: spvo_<this>_detect
-enum class Describe { WithDetector, Orb, Brisk, Akaze };         // describeKeypoints: the rows detectKeypoints kept, or spvo_<this>_describe on the given keypoints
+enum class Describe { WithDetector, Orb, Brisk, Akaze, Sift };   // describeKeypoints: the rows detectKeypoints kept, or spvo_<this>_describe on the given keypoints
 enum class Route { None, Classic, SiftPair, BriskPair, AkazePair };   // setDeviceResident: the per-image path, spvo_classic_detect (kind), spvo_sift_detect_pair, spvo_brisk_detect_pair, spvo_akaze_detect_pair
 enum class OptIn { None, AkazeDescriptor, BriskPairResident, AkazePairResident };   // to run at all: setAkazeDescriptor; to stay resident: setBriskPairResident, setAkazePairResident
 
@@ -113,6 +114,11 @@ static const ClassicPair kClassicPairs[] = {
     {DetectorType::AKAZE, DescriptorType::BRISK, Detect::Akaze, 0.f, Describe::Brisk, 64, CV_8UC1, Route::None, 0, OptIn::None, OptIn::None},
     {DetectorType::AKAZE, DescriptorType::AKAZE, Detect::Akaze, 0.f, Describe::Akaze, SPVO_AKAZE_DESC_BYTES, CV_8UC1, Route::AkazePair, 0, OptIn::AkazeDescriptor, OptIn::AkazePairResident},
     {DetectorType::SIFT, DescriptorType::SIFT, Detect::Sift, 0.f, Describe::WithDetector, 128, CV_32FC1, Route::SiftPair, 0, OptIn::None, OptIn::None},
+    {DetectorType::ShiTomasi, DescriptorType::SIFT, Detect::Gftt, 5.f, Describe::Sift, 128, CV_32FC1, Route::None, 0, OptIn::None, OptIn::None},
+    {DetectorType::FAST, DescriptorType::SIFT, Detect::Fast, 7.f, Describe::Sift, 128, CV_32FC1, Route::None, 0, OptIn::None, OptIn::None},
+    {DetectorType::ORB, DescriptorType::SIFT, Detect::Orb, 0.f, Describe::Sift, 128, CV_32FC1, Route::None, 0, OptIn::None, OptIn::None},
+    {DetectorType::BRISK, DescriptorType::SIFT, Detect::Brisk, 0.f, Describe::Sift, 128, CV_32FC1, Route::None, 0, OptIn::None, OptIn::None},
+    {DetectorType::AKAZE, DescriptorType::SIFT, Detect::Akaze, 0.f, Describe::Sift, 128, CV_32FC1, Route::None, 0, OptIn::None, OptIn::None},
 };
 
 // the row of a pair that runs, or nullptr
@@ -233,12 +239,12 @@ std::vector<cv::KeyPoint> ClassicFeatureFrontEnd::detectKeypoints(const cv::Mat 
   case Detect::Orb: {
     constexpr int NFEATURES = 2000;   // classic.cpp:13
     std::vector<spvo_orb_keypoint> kp(NFEATURES);
-    cv::Mat desc(NFEATURES, p->cols, p->type);
+    cv::Mat desc(NFEATURES, 32, CV_8UC1);   // ORB's own rows, whatever the pair's extractor is
     call = "spvo_orb_detect";
     rc = spvo_orb_detect(ctx_, px, img.rows, img.cols, step, NFEATURES, kp.data(), desc.ptr<uint8_t>(0), NFEATURES, &n);
     if (rc == SPVO_OK) {
       keypoints = to_keypoints(kp.data(), n, *p);
-      orb_desc_ = copy_rows(desc.data, n, *p);
+      if (p->describe == Describe::WithDetector) orb_desc_ = copy_rows(desc.data, n, *p);   // (ORB + SIFT: the rows are not kept)
     }
     break;
   }
@@ -300,7 +306,8 @@ std::vector<cv::KeyPoint> ClassicFeatureFrontEnd::detectKeypoints(const cv::Mat 
     logError(std::string(call) + ": " + spvo_last_error(ctx_));
     return keypoints;
   }
-  if (p->describe != Describe::WithDetector) { detected_data_ = img.data; detected_rows_ = img.rows; detected_cols_ = img.cols; }   // still on the device for describeKeypoints
+  // (spvo_orb_detect works on a pyramid of its own and leaves no image where the extractors look for one)
+  if (p->describe != Describe::WithDetector && p->detect != Detect::Orb) { detected_data_ = img.data; detected_rows_ = img.rows; detected_cols_ = img.cols; }   // still on the device for describeKeypoints
   return keypoints;
 }
 
@@ -328,7 +335,16 @@ cv::Mat ClassicFeatureFrontEnd::describeKeypoints(std::vector<cv::KeyPoint> &key
   uint8_t *rows = n ? desc.ptr<uint8_t>(0) : nullptr;
   const char *call;
   int rc;
-  if (p->describe == Describe::Akaze) {
+  if (p->describe == Describe::Sift) {
+    // cv::SIFT::create()->compute(img, keypoints, descriptors), classic.cpp:71-73: the keypoints go in as they are -- pt, size, angle in
+    // degrees (-1 from the detectors that report none), response, octave -- every one gets a row of 128 floats, none is erased and no angle
+    // is changed
+    std::vector<spvo_sift_keypoint> kp((size_t)n);
+    for (int i = 0; i < n; ++i) kp[i] = spvo_sift_keypoint{keypoints[i].pt.x, keypoints[i].pt.y, keypoints[i].size, keypoints[i].angle, keypoints[i].response, keypoints[i].octave};
+    call = "spvo_sift_describe";
+    rc = spvo_sift_describe(ctx_, px, img.rows, img.cols, step, kp.data(), n, n ? desc.ptr<float>(0) : nullptr);
+    if (rc == SPVO_OK) return desc;
+  } else if (p->describe == Describe::Akaze) {
     // cv::AKAZE::create()->compute(img, keypoints, descriptors), classic.cpp:69-70: every keypoint gets its main orientation (degrees) and a
     // 61-byte row; none is erased.  The level comes from class_id, as in OpenCV.
     std::vector<spvo_akaze_keypoint> kp((size_t)n);

@@ -403,7 +403,8 @@ int spvo_host_classic_sequence_trace(const char *detector_name, int n, const uin
 }
 
 // ... with the descriptor named as well ("ORB", "BRISK", "SIFT", "AKAZE"; -1000001: no such descriptor): "BRISK" goes with ShiTomasi, FAST, BRISK and AKAZE keypoints,
-// "AKAZE" with AKAZE keypoints once spvo_host_classic_set_akaze_descriptor is on
+// "AKAZE" with AKAZE keypoints once spvo_host_classic_set_akaze_descriptor is on;
+// "SIFT" with ShiTomasi, FAST, ORB, BRISK and AKAZE keypoints (spvo_sift_describe: 128 floats per row, NORM_L2, the per-image path)
 int spvo_host_classic_sequence_desc(const char *detector_name, const char *descriptor_name, int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols,
                                     const double *P_l, const double *P_r, int knn, int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses,
                                     int *stats, double *seconds, int input_height, int input_width, uint64_t *digest) {

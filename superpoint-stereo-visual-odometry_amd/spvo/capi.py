@@ -93,7 +93,7 @@ SYMBOLS = [
     "spvo_default_config", "spvo_create", "spvo_destroy", "spvo_last_error", "spvo_load_weights", "spvo_engine_precision", "spvo_set_fp32_split",
     "spvo_preprocess", "spvo_forward", "spvo_debug_tensor", "spvo_heatmap", "spvo_nms",
     "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8",
-    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_akaze_describe", "spvo_akaze_detect_pair", "spvo_akaze_suppress_debug", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_detect_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
+    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_akaze_describe", "spvo_akaze_detect_pair", "spvo_akaze_suppress_debug", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_describe", "spvo_sift_detect_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
     "spvo_profile_enable", "spvo_profile_reset", "spvo_profile_only", "spvo_profile_count", "spvo_profile_get", "spvo_profile_stage_kernel",
     "spvo_set_tuning", "spvo_get_tuning", "spvo_clear_tuning",
     "spvo_comm_unique_id", "spvo_comm_available", "spvo_comm_create", "spvo_comm_create_host", "spvo_comm_rank", "spvo_comm_world", "spvo_comm_destroy",
@@ -164,6 +164,7 @@ def load() -> C.CDLL:
     lib.spvo_akaze_suppress_debug.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, ip]
     lib.spvo_sift_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, C.c_int, ip]
     lib.spvo_sift_debug_level.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, ip, ip]
+    lib.spvo_sift_describe.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, vp]
     lib.spvo_sift_detect_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(SiftFeatures), C.POINTER(SiftFeatures)]
     lib.spvo_sift_slot_rows.argtypes = [vp, C.c_int, ip]
     lib.spvo_match_l2_slots.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]
@@ -679,8 +680,29 @@ class Context:
                 return dict(kp=kp[:m].copy(), desc=desc[:m].copy(), n=n.value)
             want = n.value
 
+    def sift_describe(self, img, kp: np.ndarray, shape=None) -> np.ndarray:
+        """SIFT descriptors of given keypoints (spvo_sift_describe): kp [n] SIFT_KP_DTYPE records (x, y, size, angle in degrees, response,
+        packed octave) -> desc [n, 128] float32 (integers 0..255), row i for record i; nothing is erased.  img = None: the image of the last
+        gftt() / fast() / brisk_detect() / akaze_detect() / *_describe(img) of this context, still on the device (shape as in brisk_describe)."""
+        kp = np.ascontiguousarray(kp, SIFT_KP_DTYPE).reshape(-1)
+        n = len(kp)
+        desc = np.zeros((max(n, 1), 128), np.float32)
+        if img is None:
+            rows, cols = shape if shape is not None else getattr(self, "_resident_shape", (0, 0))
+            ptr, stride = None, 0
+            if rows <= 0 or cols <= 0:
+                rows = cols = 1            # nothing remembered: let the library answer
+        else:
+            img = _u8_rows(img)
+            (rows, cols), ptr, stride = img.shape, _ptr(img), img.strides[0]
+        self._check(self.lib.spvo_sift_describe(self.h, ptr, rows, cols, stride, _ptr(kp), n, _ptr(desc)))
+        if img is not None:
+            self._resident_shape = img.shape
+        return desc[:n].copy()
+
     def sift_level(self, octave: int, layer: int, dog: bool = False) -> np.ndarray:
-        """A Gaussian (layer 0..5) or difference-of-Gaussians (dog: 0..4) level of the last sift_detect()'s pyramid (spvo_sift_debug_level)."""
+        """A Gaussian (layer 0..5) or difference-of-Gaussians (dog: 0..4) level of the last sift_detect()'s pyramid (spvo_sift_debug_level); after
+        sift_describe() a Gaussian level of ITS pyramid, octave 0 being that call's first octave (dog: SPVO_ERR_STATE)."""
         rows, cols = C.c_int(0), C.c_int(0)
         self._check(self.lib.spvo_sift_debug_level(self.h, octave, layer, int(bool(dog)), None, C.byref(rows), C.byref(cols)))
         out = np.zeros((rows.value, cols.value), np.float32)

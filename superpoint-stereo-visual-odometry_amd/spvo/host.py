@@ -346,7 +346,9 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     """stereoCallback replayed on ClassicFeatureFrontEnd(detector, descriptor, BF, ...) (node.cpp:353-360) over host image pairs -- detector
     "ORB", "ShiTomasi" or "FAST" with descriptor "ORB", "ShiTomasi", "FAST", "BRISK" or "AKAZE" with descriptor "BRISK" (64-byte rows; detector "BRISK"
     or "AKAZE" with the default descriptor "ORB" does not run; "AKAZE" with descriptor "AKAZE" -- orientation and the 61-byte MLDB rows of
-    spvo_akaze_describe -- runs with akaze_descriptor=True (ClassicFeatureFrontEnd::setAkazeDescriptor, reset afterwards) and is refused without), or detector "SIFT" (SIFT descriptors whatever `descriptor` says, as before); input_size None: at their native resolution, (height, width): through preprocessImageImpl first
+    spvo_akaze_describe -- runs with akaze_descriptor=True (ClassicFeatureFrontEnd::setAkazeDescriptor, reset afterwards) and is refused without), "ShiTomasi", "FAST", "ORB",
+    "BRISK" or "AKAZE" with descriptor "SIFT" (spvo_sift_describe on the detector's keypoints as they are: 128 floats per row, matched with
+    NORM_L2; always the per-image path, classic_resident_pairs() stays 0), or detector "SIFT" (SIFT descriptors whatever `descriptor` says, as before); input_size None: at their native resolution, (height, width): through preprocessImageImpl first
     (classic.cpp:96-100).  Returns (poses [n, 7] = q xyzw + t of cam0_curr_T_cam0_prev, stats [n, 4] = keypoints L, R, stereo
     matches, PnP inliers, seconds spent on frames warm .. n-1).
     resident: ClassicFeatureFrontEnd::setDeviceResident for this run -- one spvo_classic_detect (SIFT: spvo_sift_detect_pair) per pair, features

@@ -1,9 +1,10 @@
 """The classic front end on the GPU.
 
-python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK|AKAZE] [--descriptor ORB|BRISK|AKAZE] [--resident] [--brisk-resident] [--akaze-resident]
+python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK|AKAZE] [--descriptor ORB|BRISK|AKAZE|SIFT] [--resident] [--brisk-resident] [--akaze-resident]
     ClassicFeatureFrontEnd(detector, descriptor, BF, KNN) over the synthetic stream: frames/s of the synchronous stereoCallback
     (--descriptor BRISK: with --detector ShiTomasi, FAST, BRISK or AKAZE; --detector BRISK: with --descriptor BRISK only; --detector AKAZE:
     with --descriptor BRISK or AKAZE -- the latter sets ClassicFeatureFrontEnd::setAkazeDescriptor for the run: 61-byte MLDB rows);
+    --descriptor SIFT: with any of the five detectors (spvo_sift_describe; always the per-image path);
     --resident: with ClassicFeatureFrontEnd::setDeviceResident (one spvo_classic_detect per pair, matching on the binary slots);
     --brisk-resident: with setBriskPairResident as well (BRISK + BRISK through one spvo_brisk_detect_pair per pair; needs --resident).
     --akaze-resident: with setAkazePairResident as well (AKAZE + AKAZE through one spvo_akaze_detect_pair per pair; needs --resident).
@@ -44,6 +45,12 @@ python tools/classic_bench.py --leg akaze_pair [--calls 100]
     for rocprofv3 --kernel-trace --stats as above: the detector's kernels up to akaze_refine_kernel, then akaze_suppress_first_kernel /
     akaze_suppress_second_kernel / akaze_suppress_compact_kernel / akaze_describe_kernel / akaze_pair_finish_kernel, twice per call.
     Its yardsticks are --leg akaze_detect and --leg akaze_describe: two per-image detects plus two describes.
+python tools/classic_bench.py --leg fast_sift|sift_describe [--calls 50] [--form 0|1] [--yardstick]
+    FAST + SIFT per image at 1241 x 376, for rocprofv3 --kernel-trace --stats as above.  sift_describe: spvo_sift_describe alone on the FAST
+    keypoints of the sample (size 7, angle -1, octave 0; image passed with every call): sift_blur_kernel x 6 / sift_describe_given_kernel is
+    the split.  fast_sift: spvo_fast_detect + spvo_sift_describe(img = NULL), what ClassicFeatureFrontEnd(FAST, SIFT) runs per image.
+    --form 1: tuning "sift_describe_form" = 1, the staged form of the sums instead of the columns.  --yardstick (fast_sift): afterwards, in the
+    same run, ms per pair through the host class for FAST + SIFT, SIFT + SIFT and FAST + BRISK over the synthetic stream.
 python tools/classic_bench.py --leg match|match_slots [--selector NN|KNN] [--cross] [--calls 50]
     one matcher alone on the two resident ORB sets of the 1241 x 376 sample pair: spvo_match_hamming on the host copies (match_hamming_kernel<8>)
     or spvo_match_hamming_slots on the binary slots (match_hamming_tiled_kernel), for rocprofv3 --kernel-trace --stats as above.
@@ -67,7 +74,8 @@ ap.add_argument("--resident", action="store_true")
 ap.add_argument("--brisk-resident", action="store_true")
 ap.add_argument("--akaze-resident", action="store_true")
 ap.add_argument("--ab", type=int, default=0)
-ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "brisk_detect", "akaze_detect", "akaze_describe", "akaze_pair", "brisk_pair", "orb_describe", "match", "match_slots"])
+ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "brisk_detect", "akaze_detect", "akaze_describe", "akaze_pair", "brisk_pair", "orb_describe", "fast_sift", "sift_describe", "match", "match_slots"])
+ap.add_argument("--form", type=int, default=0, choices=[0, 1])
 ap.add_argument("--selector", default="KNN", choices=["NN", "KNN"])
 ap.add_argument("--cross", action="store_true")
 ap.add_argument("--yardstick", action="store_true")
@@ -93,6 +101,23 @@ if args.detectors or args.leg:
 
     def leg_sift():
         return ctx.sift_detect(img)["n"]
+
+    if args.leg in ("fast_sift", "sift_describe"):
+        capi.set_tuning("sift_describe_form", args.form)
+
+    def fast_records(f):                               # KeyPoint(x, y, 7.f, -1, score), octave 0
+        rec = np.zeros(len(f["xy"]), capi.SIFT_KP_DTYPE)
+        rec["x"], rec["y"], rec["size"], rec["angle"], rec["response"] = f["xy"][:, 0], f["xy"][:, 1], 7.0, -1.0, f["response"]
+        return rec
+
+    if args.leg == "sift_describe":
+        srec = fast_records(ctx.fast(img))
+
+    def leg_sift_describe():
+        return len(ctx.sift_describe(img, srec))
+
+    def leg_fast_sift():
+        return len(ctx.sift_describe(None, fast_records(ctx.fast(img)), shape=img.shape))
 
     if args.leg in ("brisk", "orb_describe"):
         kp = ctx.fast(img)["xy"]
@@ -176,8 +201,10 @@ if args.detectors or args.leg:
                 akaze_describe_img=("spvo_akaze_describe(img)", leg_akaze_describe_img),
                 brisk_detect=("spvo_brisk_detect", leg_brisk_detect), akaze_detect=("spvo_akaze_detect", leg_akaze_detect), brisk_pair=("spvo_brisk_detect_pair (both images)", leg_brisk_pair),
                 akaze_pair=("spvo_akaze_detect_pair (both images)", leg_akaze_pair),
+                sift_describe=("spvo_sift_describe, %d FAST keypoints, form %d" % (len(srec) if args.leg == "sift_describe" else 0, args.form), leg_sift_describe),
+                fast_sift=("spvo_fast_detect + spvo_sift_describe(NULL), form %d" % args.form, leg_fast_sift),
                 orb=("spvo_orb_detect", leg_orb), sift=("spvo_sift_detect", leg_sift), gftt=("spvo_gftt_detect + spvo_orb_describe", leg_gftt), fast=("spvo_fast_detect + spvo_orb_describe", leg_fast))
-    keys = [args.leg] + (["sift"] if args.yardstick else []) if args.leg else ["orb", "gftt", "fast"]
+    keys = [args.leg] + (["sift"] if args.yardstick and args.leg != "fast_sift" else []) if args.leg else ["orb", "gftt", "fast"]
     if args.leg == "akaze_describe":
         keys = ["akaze_describe", "akaze_brisk_null", "akaze_describe_img", "akaze_detect"]
     for key in keys:
@@ -197,6 +224,14 @@ if args.detectors or args.leg:
         print("%-40s %d x %d: median %.3f ms (p10 %.3f, p90 %.3f) over %d calls, %d described keypoints / matches%s" % (name, img.shape[1], img.shape[0], np.median(ts), np.percentile(ts, 10),
                                                                                                       np.percentile(ts, 90), args.calls, n, extra))
     ctx.close()
+    if args.leg == "fast_sift" and args.yardstick:     # the host class, ms per pair, in the same run
+        seq = [frames[i % 8] for i in range(args.frames)]
+        for det, des in (("FAST", "SIFT"), ("SIFT", "SIFT"), ("FAST", "BRISK")):
+            host.classic_sequence(seq[:3], P_l, P_r, "KNN", True, 2.0, 4, detector=det, descriptor=des)      # the one-off costs
+            p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5, detector=det, descriptor=des)
+            print("host class %s + %s %dx%d: %.3f ms per pair over %d pairs, keypoints %d, stereo matches %d, inliers %d" % (
+                det, des, frames[0][0].shape[1], frames[0][0].shape[0], 1e3 * sec / (len(seq) - 5), len(seq) - 5, np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3])))
+    capi.set_tuning("sift_describe_form", 0)
 elif args.ab > 0:
     n = args.frames
     seq = [frames[i % 8] for i in range(n)]
