@@ -455,7 +455,10 @@ int spvo_akaze_describe(spvo_ctx *ctx, const uint8_t *img /* or NULL */, int row
  * With spvo_set_prematch enabled the two standard matches (slot_l -> slot_r, slot_l -> the previous call's slot_l) are enqueued in the
  * same submission behind the features; the call does not wait for them.  A previous left slot of the other row width has no temporal
  * match: it is skipped, not an error (so is a slot of 61-byte rows that spvo_akaze_detect_pair filled). */
-typedef enum { SPVO_CLASSIC_ORB = 0, SPVO_CLASSIC_GFTT_ORB = 1, SPVO_CLASSIC_FAST_ORB = 2, SPVO_CLASSIC_GFTT_BRISK = 3, SPVO_CLASSIC_FAST_BRISK = 4 } spvo_classic_kind;
+/* (kinds 5 and 6, Shi-Tomasi / FAST keypoints with SIFT descriptors, are spvo_classic_sift_pair's, below the SIFT slots: their rows are 128
+ * floats, which spvo_classic_features and the binary slots do not hold.  spvo_classic_detect answers SPVO_ERR_INVALID for them.) */
+typedef enum { SPVO_CLASSIC_ORB = 0, SPVO_CLASSIC_GFTT_ORB = 1, SPVO_CLASSIC_FAST_ORB = 2, SPVO_CLASSIC_GFTT_BRISK = 3, SPVO_CLASSIC_FAST_BRISK = 4,
+               SPVO_CLASSIC_GFTT_SIFT = 5, SPVO_CLASSIC_FAST_SIFT = 6 } spvo_classic_kind;
 typedef struct {
   int kind;                               /* spvo_classic_kind */
   int nfeatures;                          /* ORB [2000] */
@@ -578,6 +581,33 @@ int spvo_match_hamming_slots(spvo_ctx *ctx, int slot_a, int slot_b, int selector
 typedef struct { int n; spvo_sift_keypoint *kp; float *desc /* [cap][128] */; int cap; } spvo_sift_features;   /* n: out; min(n, cap) rows are written */
 int spvo_sift_detect_pair(spvo_ctx *ctx, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride,
                           int slot_l, int slot_r, int slot_capacity, spvo_sift_features *out_l, spvo_sift_features *out_r);
+/* Shi-Tomasi / FAST keypoints with SIFT descriptors (ClassicFeatureFrontEnd(ShiTomasi or FAST, SIFT)) for BOTH images of a stereo pair in
+ * one call, into the same ring of ten SIFT slots: opts->kind is SPVO_CLASSIC_GFTT_SIFT or SPVO_CLASSIC_FAST_SIFT, the detector's parameters
+ * and slot_capacity (1 .. 32768) are the other fields (spvo_default_classic_opts).  Both images go up through pinned staging.  Per image,
+ * left first, on the solver's stream and without a host round trip: the image becomes the context's resident u8 image and goes through the
+ * detector's chain (spvo_gftt_detect's / spvo_fast_detect's launches); the SIFT base level ALONE is built from it (one blur at the
+ * image's own size: every record of these detectors lies on octave 0, layer 0); spvo_sift_describe's kernel runs on the detector's list
+ * where it lies -- a record is {x, y, size 5 (Shi-Tomasi) or 7 (FAST), angle -1, the detector's response, octave 0}, the count is read
+ * on the device, a fixed number of waves strides over the records -- and writes rows (256 floats, columns 128.. zero), squared norms,
+ * records and the count into the slot and into pinned mirrors.  The call waits once, for the features of both images.
+ * spvo_match_l2_slots, spvo_sift_slot_rows and spvo_set_prematch serve the slots as they serve spvo_sift_detect_pair's, with the same
+ * temporal partner: any filled SIFT slot is one, whichever of the two calls filled it.
+ *   Byte equality: per image the host receives, byte for byte, what spvo_gftt_detect / spvo_fast_detect with the same parameters returns
+ *   followed by spvo_sift_describe(img = NULL) on the records above -- the records ClassicFeatureFrontEnd builds from its cv::KeyPoints.
+ *   Records come in the detector's order, none is erased; out->n is the count, of which min(n, cap) rows are written.
+ *   An image without a keypoint fills its slot with 0 rows: SPVO_OK, and spvo_match_l2_slots treats it as any empty slot.
+ * Afterwards the resident u8 image is the RIGHT image: spvo_sift_describe(img = NULL), spvo_orb_describe(NULL) and
+ * spvo_brisk_describe(NULL) work on it.  No SIFT pyramid is resident (spvo_sift_debug_level: SPVO_ERR_STATE), and the AKAZE scale
+ * space's claim ends, as after spvo_sift_detect_pair.  A slot_capacity larger than any before empties every SIFT slot (the rule above).
+ *   SPVO_ERR_CAPACITY  an image yields more rows than slot_capacity: out_*->n report both counts, both slots are left unfilled, nothing
+ *                      is truncated
+ *   SPVO_ERR_INVALID   nothing is written or touched: NULL arguments, a kind other than 5 / 6, bad or equal slots, slot_capacity outside
+ *                      1 .. 32768, cap < 0, whatever spvo_gftt_detect / spvo_fast_detect and spvo_sift_describe refuse of the shape
+ *                      or the parameters
+ *   SPVO_ERR_STATE     a spvo_detect*_submit is in flight */
+int spvo_classic_sift_pair(spvo_ctx *ctx, const spvo_classic_opts *opts /* kind 5 or 6 */, const uint8_t *img_l, const uint8_t *img_r,
+                           int rows, int cols, size_t stride, int slot_l, int slot_r,
+                           spvo_sift_features *out_l, spvo_sift_features *out_r);
 /* rows a SIFT slot holds; SPVO_ERR_STATE for one that holds nothing (never filled, or left unfilled by SPVO_ERR_CAPACITY) */
 int spvo_sift_slot_rows(spvo_ctx *ctx, int slot, int *n);
 /* spvo_match_l2(dim = 128) on the device-resident rows of two SIFT slots: nothing is uploaded, no norm is recomputed.  Results equal
@@ -596,7 +626,7 @@ int spvo_sift_order_debug(spvo_ctx *ctx, const spvo_sift_keypoint *rec, int n, i
  * parameters in the same GPU submission, and spvo_match_slots returns the stored result when it
  * is asked for exactly that match (same slots, same slot contents, same parameters).  Results
  * are identical with it on or off.  spvo_classic_detect / spvo_match_hamming_slots do the same on the
- * binary slots, spvo_sift_detect_pair / spvo_match_l2_slots on the SIFT slots. */
+ * binary slots, spvo_sift_detect_pair and spvo_classic_sift_pair / spvo_match_l2_slots on the SIFT slots. */
 int spvo_set_prematch(spvo_ctx *ctx, int enable, int selector, int cross_check, float ratio);
 
 /* Extension (BASELINE config 5): build the matcher's candidate shortlist with an fp8 (e4m3) distance GEMM instead of

@@ -16,7 +16,8 @@
 // The extractor on GIVEN keypoints (spvo_sift_describe, tests/sift_describe_ref.py): sift_blur_kernel x 6 per octave the list names, without
 // the differences (MODE 3: the base at the image's own size when no record lies on octave -1) -> sift_describe_given_kernel, a wave per
 // record with the per-sample device code of sift_describe_kernel (sift_patch, sift_patch_sample, sift_share_bin, sift_desc_store) and sums
-// of its own that take no turns.
+// of its own that take no turns.  The same kernel behind a Shi-Tomasi / FAST detector (spvo_classic_sift_pair): its IO parameter reads the
+// detector's list where it lies and writes the rows into a SIFT slot and the host's mirrors; only the base level is built for it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -262,13 +263,18 @@ __device__ __forceinline__ int sift_share_bin(int r0, int c0, int o0, int e) {
   return rr >= 0 && rr < 4 && cc >= 0 && cc < 4 ? (rr * 4 + cc) * 8 + oo : -1;
 }
 
-// bins `lane` (d0) and `lane + 64` (d1) of the 128 sums -> the row: 0.2 clamp, x512, round, saturate
-__device__ __forceinline__ void sift_desc_store(float d0, float d1, float *__restrict__ row, int lane) {
+// bins `lane` (d0) and `lane + 64` (d1) of the 128 sums -> the row's columns `lane` and `lane + 64`: 0.2 clamp, x512, round, saturate
+__device__ __forceinline__ void sift_desc_finish(float &d0, float &d1) {
   const float thr2 = sqrtf(sift_wave_sum(d0 * d0 + d1 * d1)) * 0.2f;
   d0 = fminf(d0, thr2); d1 = fminf(d1, thr2);
   const float nrm = 512.f / fmaxf(sqrtf(sift_wave_sum(d0 * d0 + d1 * d1)), 1.1920929e-7f);
-  row[lane] = fminf(fmaxf(rintf(d0 * nrm), 0.f), 255.f);
-  row[64 + lane] = fminf(fmaxf(rintf(d1 * nrm), 0.f), 255.f);
+  d0 = fminf(fmaxf(rintf(d0 * nrm), 0.f), 255.f);
+  d1 = fminf(fmaxf(rintf(d1 * nrm), 0.f), 255.f);
+}
+__device__ __forceinline__ void sift_desc_store(float d0, float d1, float *__restrict__ row, int lane) {
+  sift_desc_finish(d0, d1);
+  row[lane] = d0;
+  row[64 + lane] = d1;
 }
 
 // Orientation and descriptor of every surviving candidate: one wave (= one workgroup) per candidate, lanes over the patch.  A peak of the
@@ -390,14 +396,57 @@ __global__ __launch_bounds__(64) void sift_describe_kernel(SiftPyr P, const int4
 //            sums row b and row b + 64 starting at column b (bank b + l: no conflict either), a fixed order per bin
 //   FORM 1   the tile's samples are staged in LDS (bins packed in a word, eight shares), lane b owns bins b and b + 64 in registers and
 //            walks the tile's valid samples in lane order, adding the share that falls into its bin (the measurement's other form)
-template <int FORM>
-__global__ __launch_bounds__(64) void sift_describe_given_kernel(SiftPyr P, int first, const SiftKey *__restrict__ kp, int n, float *__restrict__ desc) {
+// Where the records come from and where the rows go is the kernel's IO parameter:
+//   SiftGivenIO     spvo_sift_describe: the caller's records, rows of 128 floats back to back
+//   SiftDetectorIO  spvo_classic_sift_pair: the list a Shi-Tomasi / FAST detector left on the device (xy, resp, counters[2]) as records
+//                   {x, y, size, -1, response, 0}, the count read here; row i goes into a SIFT slot in the L2 matcher's format (pitch 256,
+//                   columns 128.. zero, the squared norm: integers <= 255, exact in any order) with its record, the same to the host's
+//                   pinned mirrors (pitch 128) -- sift_gather_kernel's part for spvo_sift_detect_pair.  The slot takes min(count, slot_cap)
+//                   rows; the host is told the detector's full count and its overflow flag
+struct SiftGivenIO {
+  const SiftKey *kp;
+  int n;
+  float *desc;
+  __device__ __forceinline__ int begin() const { return n; }
+  __device__ __forceinline__ SiftKey record(int i) const { return kp[i]; }
+  __device__ __forceinline__ void store(int i, const SiftKey &, float d0, float d1, int lane) const { sift_desc_store(d0, d1, desc + (size_t)i * 128, lane); }
+};
+struct SiftDetectorIO {
+  const float *xy, *resp;   // [n][2], [n]
+  const int *counters;      // the detector's block: [2] keypoints, [3] overflow flag
+  SiftKey proto;            // what every record of the list shares: size, angle, octave (kernel arguments, so that nothing of a record is a compile-time
+                            // constant the optimiser could fold sift_patch's cosf / sinf with: the arithmetic stays spvo_sift_describe's)
+  int slot_cap;
+  float *s_desc, *s_sqn;
+  SiftKey *s_rec;
+  int *d_n;
+  float *h_desc;
+  SiftKey *h_rec;
+  int *h_n;                 // {keypoints (may exceed slot_cap), overflow flag, 0}
+  __device__ __forceinline__ int begin() const {   // the rows this launch describes; the counts to the slot and the host
+    const int n_all = counters[2], n = min(n_all, slot_cap);
+    if (blockIdx.x == 0 && threadIdx.x == 0) { *d_n = n; h_n[0] = n_all; h_n[1] = counters[3]; h_n[2] = 0; }
+    return n;
+  }
+  __device__ __forceinline__ SiftKey record(int i) const { return SiftKey{xy[2 * i], xy[2 * i + 1], proto.size, proto.angle, resp[i], proto.octave}; }
+  __device__ __forceinline__ void store(int i, const SiftKey &k, float d0, float d1, int lane) const {
+    sift_desc_finish(d0, d1);
+    float *row = s_desc + (size_t)i * 256, *hrow = h_desc + (size_t)i * 128;
+    row[lane] = d0; row[64 + lane] = d1; row[128 + lane] = 0.f; row[192 + lane] = 0.f;
+    hrow[lane] = d0; hrow[64 + lane] = d1;
+    const float sq = sift_wave_sum(d0 * d0 + d1 * d1);
+    if (lane == 0) { s_sqn[i] = sq; s_rec[i] = k; h_rec[i] = k; }
+  }
+};
+
+template <int FORM, class IO>
+__global__ __launch_bounds__(64) void sift_describe_given_kernel(SiftPyr P, int first, IO io) {
   constexpr int TW = 16, TH = 4;
   __shared__ float lds[FORM == 0 ? 128 * 64 : 8 * 64];
   __shared__ int code[64];
-  const int lane = threadIdx.x;
+  const int lane = threadIdx.x, n = io.begin();
   for (int i = blockIdx.x; i < n; i += gridDim.x) {
-    const SiftKey k = kp[i];
+    const SiftKey k = io.record(i);
     int o = k.octave & 255;
     if (o >= 128) o -= 256;
     const int layer = (k.octave >> 8) & 255, lvl = o - first, h = P.h[lvl], w = P.w[lvl];
@@ -462,7 +511,7 @@ __global__ __launch_bounds__(64) void sift_describe_given_kernel(SiftPyr P, int 
       }
       __syncthreads();   // (the columns are cleared for the next record)
     }
-    sift_desc_store(d0, d1, desc + (size_t)i * 128, lane);
+    io.store(i, k, d0, d1, lane);
   }
 }
 

@@ -1,7 +1,7 @@
 // spvo_classic.hip -- the classic front end (ClassicFeatureFrontEnd, feature_detection_classic.cpp): the ORB detector / extractor (orb.hip.h),
 // the Shi-Tomasi and FAST detectors and the ORB extractor for given keypoints (classic_detect.hip.h), one submission per stereo pair into the
-// binary feature slots (spvo_classic_detect; its BRISK kinds hand the detector's list to spvo_brisk.hip), and spvo_preprocess for a context
-// without an engine.  Everything here runs on the solver's stream (stream2) and owns its buffers (spvo_ctx::orb, spvo_ctx::cls).
+// binary feature slots (spvo_classic_detect; its BRISK kinds hand the detector's list to spvo_brisk.hip, and spvo_sift.hip takes the same
+// detector link for spvo_classic_sift_pair), and spvo_preprocess for a context without an engine.  Everything here runs on the solver's stream (stream2) and owns its buffers (spvo_ctx::orb, spvo_ctx::cls).
 #include "spvo_internal.hip.h"
 #include "orb.hip.h"
 #include "classic_detect.hip.h"
@@ -494,7 +494,8 @@ namespace {
 static_assert(BIN_COUNTER_INTS == CLS_COUNTER_INTS, "an image's counter block in spvo_ctx::bin.d_cnt");
 constexpr int BIN_ROW_BYTES_MAX = 64;   // the widest row a binary slot holds (BRISK; AKAZE's 61 bytes are stored in 64); the ORB extractor's rows are 32 bytes
 inline bool kind_is_brisk(int kind) { return kind == SPVO_CLASSIC_GFTT_BRISK || kind == SPVO_CLASSIC_FAST_BRISK; }
-inline bool kind_is_gftt(int kind) { return kind == SPVO_CLASSIC_GFTT_ORB || kind == SPVO_CLASSIC_GFTT_BRISK; }
+inline bool kind_is_gftt(int kind) { return kind == SPVO_CLASSIC_GFTT_ORB || kind == SPVO_CLASSIC_GFTT_BRISK || kind == SPVO_CLASSIC_GFTT_SIFT; }
+inline bool kind_is_sift(int kind) { return kind == SPVO_CLASSIC_GFTT_SIFT || kind == SPVO_CLASSIC_FAST_SIFT; }   // float rows into the SIFT slots: spvo_classic_sift_pair's
 // the binary slots and the call's own buffers for `cap` rows per slot and images of `px` bytes; growing un-fills every slot.  Every slot and
 // both mirrors are sized for 64-byte rows whatever kind asks first: a BRISK kind's first call must not empty the slots the ORB kinds filled
 int bin_ensure(spvo_ctx *c, int cap, size_t px) {
@@ -570,6 +571,7 @@ namespace {
 // what spvo_classic_detect refuses of its options and of the image shape: the slot capacity, then what the kind's per-image entry points refuse
 int classic_check_opts(spvo_ctx *c, const spvo_classic_opts *opts, int rows, int cols) {
   const int kind = opts->kind, cap = opts->slot_capacity;
+  if (kind_is_sift(kind)) return fail(c, SPVO_ERR_INVALID, "spvo_classic_detect: kind %d leaves rows of 128 floats, which no binary slot holds: call spvo_classic_sift_pair", kind);
   if (cap <= 0 || cap > (1 << HAM_KEY_SHIFT)) return fail(c, SPVO_ERR_INVALID, "slot_capacity must be 1 .. %d", 1 << HAM_KEY_SHIFT);
   if (kind == SPVO_CLASSIC_ORB) {
     if (opts->nfeatures <= 0) return fail(c, SPVO_ERR_INVALID, "bad argument");
@@ -606,12 +608,12 @@ int orb_pair_chain(spvo_ctx *c, const spvo_classic_opts *opts, const OrbPlan &pl
   return SPVO_OK;
 }
 
-// image k of the staged pair becomes the resident image of spvo_ctx::cls and goes through the Shi-Tomasi or FAST detector, which leaves its list there
-int detector_enqueue(spvo_ctx *c, const spvo_classic_opts *opts, int rows, int cols, int k) {
+// a staged image (pinned, rows packed) becomes the resident image of spvo_ctx::cls and goes through the Shi-Tomasi or FAST detector, which leaves its list there
+int detector_enqueue(spvo_ctx *c, const spvo_classic_opts *opts, const uint8_t *h_img, int rows, int cols) {
   auto &b = c->cls;
   const size_t px = (size_t)rows * cols;
   b.rows = b.cols = 0;
-  HIP_TRY(c, hipMemcpyAsync(b.im, c->bin.pair.h_img + k * px, px, hipMemcpyHostToDevice, c->stream2));
+  HIP_TRY(c, hipMemcpyAsync(b.im, h_img, px, hipMemcpyHostToDevice, c->stream2));
   b.rows = rows; b.cols = cols;
   return kind_is_gftt(opts->kind) ? gftt_enqueue(c, rows, cols, opts->max_corners, opts->quality_level, opts->min_distance)
                                   : fast_enqueue(c, rows, cols, opts->fast_threshold, opts->fast_nonmax);
@@ -624,7 +626,7 @@ int detector_most(const spvo_classic_opts *opts) {
 // detector -> ORB extractor on the device: the border rule as an order-preserving compaction, then the one-level extractor whose keypoint
 // list is the compacted one and whose count is the compaction's (spvo_orb_describe, without the host)
 int detector_orb_chain(spvo_ctx *c, const spvo_classic_opts *opts, int rows, int cols, int k, const ChainOut &out) {
-  if (int rc = detector_enqueue(c, opts, rows, cols, k)) return rc;
+  if (int rc = detector_enqueue(c, opts, c->bin.pair.h_img + k * ((size_t)rows * cols), rows, cols)) return rc;
   auto &b = c->cls;
   hipStream_t st = c->stream2;
   const int cap = opts->slot_capacity;
@@ -638,7 +640,7 @@ int detector_orb_chain(spvo_ctx *c, const spvo_classic_opts *opts, int rows, int
 // the same hand-over to the BRISK extractor: its border rule (keypoint size 5 / 7, what detectKeypoints assigns) and the rest of
 // spvo_brisk_describe's launches, 64-byte rows
 int detector_brisk_chain(spvo_ctx *c, const spvo_classic_opts *opts, int rows, int cols, int k, const ChainOut &out) {
-  if (int rc = detector_enqueue(c, opts, rows, cols, k)) return rc;
+  if (int rc = detector_enqueue(c, opts, c->bin.pair.h_img + k * ((size_t)rows * cols), rows, cols)) return rc;
   return brisk_chain_enqueue(c, rows, cols, kind_is_gftt(opts->kind) ? 5.0f : 7.0f, opts->slot_capacity, detector_most(opts), out);
 }
 
@@ -723,3 +725,11 @@ int spvo_classic_detect(spvo_ctx *c, const spvo_classic_opts *opts, const uint8_
 }  // extern "C"
 
 int spvo_int::classic_slots_ensure(spvo_ctx *c, int cap, size_t px) { return bin_ensure(c, cap, px); }
+int spvo_int::classic_detector_check(spvo_ctx *c, const char *who, const spvo_classic_opts *opts, int rows, int cols) {
+  return kind_is_gftt(opts->kind) ? gftt_check(c, who, rows, cols, opts->quality_level, opts->min_distance, opts->block_size) : fast_check(c, opts->fast_threshold);
+}
+int spvo_int::classic_detector_enqueue(spvo_ctx *c, const spvo_classic_opts *opts, const uint8_t *h_img, int rows, int cols) {
+  if (int rc = detector_enqueue(c, opts, h_img, rows, cols)) return rc;
+  HIP_TRY(c, hipGetLastError());
+  return SPVO_OK;
+}

@@ -8,7 +8,7 @@
 //   spvo_net_i8.hip    INT8 engines
 //   spvo_detect.hip    preprocess, heat map / NMS / sampling, the detector submissions, spvo_forward
 //   spvo_classic.hip   the classic front end: ORB, Shi-Tomasi, FAST, the ORB extractor, preprocess without an engine
-//   spvo_sift.hip      the classic front end: SIFT detector + descriptor
+//   spvo_sift.hip      the classic front end: SIFT detector + descriptor, the extractor on given keypoints and behind the Shi-Tomasi / FAST detectors
 //   spvo_brisk.hip     the classic front end: BRISK descriptor extractor on given keypoints
 //   spvo_brisk_detect.hip   the classic front end: BRISK keypoint detector, and detector + extractor of a stereo pair into the binary slots
 //   spvo_match.hip     descriptor matching (L2, Hamming)
@@ -128,7 +128,7 @@ struct BinarySlot : SlotState {
 struct SiftSlot : SlotState {
   float *d_desc = nullptr;       // [cap][256] 128 integers as float, columns 128.. zero
   float *d_sqn = nullptr;        // [cap] squared norms (exact integers)
-  SiftSrc *d_src = nullptr;      // [cap] candidate and angle every row came from
+  SiftSrc *d_src = nullptr;      // [cap] candidate and angle every row came from (spvo_classic_sift_pair: its 24-byte record, a SiftKey, back to back)
 };
 
 // a match enqueued together with the detector (spvo_set_prematch); the result lives in pinned memory
@@ -495,7 +495,7 @@ struct spvo_ctx {
     int slot_cap = 0;
     SiftSlot slots[N_SIFT_SLOTS];
     PairStage pair;                      // (its prematches' slot numbers are SIFT slots)
-    SiftSrc *h_src = nullptr;            // pinned [2][slot_cap]      what sift_gather_kernel writes for the host: sources,
+    SiftSrc *h_src = nullptr;            // pinned [2][slot_cap]      what sift_gather_kernel writes for the host: sources (spvo_classic_sift_pair: SiftKey records in each half's front),
     float *hm_desc = nullptr;            // pinned [2][slot_cap][128] descriptors,
     int *h_n = nullptr;                  // pinned [2][4]             {final rows, candidates counted, raw rows counted}
     int2 *h_match = nullptr;             // pinned [2][h_match_cap]: the two prematches (enqueue_matches spaces its jobs by spvo_ctx::match_cap)
@@ -709,6 +709,12 @@ int classic_upload_image(spvo_ctx *c, const uint8_t *img, int rows, int cols, si
 // empties every slot.  classic_image_ensure: every buffer of spvo_ctx::cls grown to a rows x cols image; none is resident afterwards.
 int classic_slots_ensure(spvo_ctx *c, int cap, size_t px);
 int classic_image_ensure(spvo_ctx *c, int rows, int cols);
+// The Shi-Tomasi / FAST detector as the first link of another unit's chain (spvo_classic_sift_pair; the kinds whose detector is one of the
+// two).  classic_detector_check: what spvo_gftt_detect / spvo_fast_detect refuse of these options and this shape.  classic_detector_enqueue,
+// behind classic_image_ensure: the staged image `h_img` (pinned, rows packed) becomes the resident image and goes through the detector on
+// the solver's stream; the list stays in spvo_ctx::cls (xy, resp, counters[2]; counters[3]: the key buffer overflowed).
+int classic_detector_check(spvo_ctx *c, const char *who, const spvo_classic_opts *opts, int rows, int cols);
+int classic_detector_enqueue(spvo_ctx *c, const spvo_classic_opts *opts, const uint8_t *h_img, int rows, int cols);
 // cls_rank_kernel (classic_detect.hip.h) over a key list whose length lies in device memory, enqueued on the solver's stream: rank[i] += the
 // number of keys smaller than keys[i] (rank is zero between uses)
 void classic_rank_enqueue(spvo_ctx *c, const unsigned long long *keys, int *rank, const int *n_ptr, int cap);

@@ -8,6 +8,9 @@
 // host, so ties and duplicates are the same.  Runs on the solver's stream (stream2), like the rest of the classic front end.
 // spvo_sift_describe is the extractor alone on a caller's records: it reads the u8 image the Shi-Tomasi / FAST / BRISK / AKAZE detectors and
 // the other extractors keep resident (spvo_ctx::cls), builds a Gaussian-only pyramid in the same buffer and describes in one launch.
+// spvo_classic_sift_pair is that extractor behind the Shi-Tomasi / FAST detector for both images of a stereo pair, the list never leaving
+// the device: detector chain (spvo_classic.hip), base level, the describe kernel into a SIFT slot; spvo_sift_detect_pair's staging, slots,
+// prematch and temporal partner.
 #include "spvo_internal.hip.h"
 #include "sift.hip.h"
 
@@ -16,7 +19,7 @@
 namespace {
 constexpr int SIFT_MIN_SIDE = 6;   // 2 x 6 = 12 > 2 x border: the first octave has an interior; the octave rule then gives >= 2 octaves
 
-// the images spvo_sift_detect and spvo_sift_detect_pair (`who`, for the error text) refuse
+// the images spvo_sift_detect, spvo_sift_detect_pair, spvo_sift_describe and spvo_classic_sift_pair (`who`, for the error text) refuse
 int sift_check_image(spvo_ctx *c, const char *who, int rows, int cols) {
   if (rows < SIFT_MIN_SIDE || cols < SIFT_MIN_SIDE) return fail(c, SPVO_ERR_INVALID, "%s: images of at least %d x %d (the first octave needs an interior)", who, SIFT_MIN_SIDE, SIFT_MIN_SIDE);
   if ((size_t)rows * cols > ((size_t)1 << 26)) return fail(c, SPVO_ERR_INVALID, "%s: image too large", who);
@@ -83,8 +86,9 @@ int sift_ensure(spvo_ctx *c, int rows, int cols, size_t pyr_floats, int cand_cap
 
 // the pyramid of the u8 image `src` (rows x cols, packed): 1 + 5 launches per octave.  doubled: the base is the 2x upsampled image (first
 // octave -1), else the image at its own size (first octave 0: spvo_sift_describe).  with_dog: every difference of Gaussians is written by
-// the blur that completes it; without, P holds Gaussian levels only
-int sift_enqueue_pyramid(spvo_ctx *c, const uint8_t *src, int rows, int cols, const SiftPyr &P, bool doubled = true, bool with_dog = true) {
+// the blur that completes it; without, P holds Gaussian levels only.  base_only: ONE launch, layer 0 of the first octave (records that all lie
+// there: spvo_classic_sift_pair)
+int sift_enqueue_pyramid(spvo_ctx *c, const uint8_t *src, int rows, int cols, const SiftPyr &P, bool doubled = true, bool with_dog = true, bool base_only = false) {
   hipStream_t st = c->stream2;
   const double k = std::pow(2.0, 1.0 / 3.0), sigma = 1.6;
   SiftTaps tp[SIFT_GAUSS];
@@ -101,6 +105,7 @@ int sift_enqueue_pyramid(spvo_ctx *c, const uint8_t *src, int rows, int cols, co
     if (o == 0) {
       if (doubled) hipLaunchKernelGGL(sift_blur_kernel<2>, grid, dim3(256), 0, st, (const void *)src, rows, cols, G, (float *)nullptr, (float *)nullptr, h, w, tp[0]);
       else hipLaunchKernelGGL(sift_blur_kernel<3>, grid, dim3(256), 0, st, (const void *)src, rows, cols, G, (float *)nullptr, (float *)nullptr, h, w, tp[0]);
+      if (base_only) break;
       hipLaunchKernelGGL(sift_blur_kernel<0>, grid, dim3(256), 0, st, (const void *)G, h, w, G + lvl, D, (float *)nullptr, h, w, tp[1]);
     } else {
       const float *below = P.pyr + P.g_off[o - 1] + (size_t)SIFT_LAYERS * P.h[o - 1] * P.w[o - 1];
@@ -220,6 +225,54 @@ int sift_slots_ensure(spvo_ctx *c, int cap, size_t px) {
   s.slot_cap = cap;
   return SPVO_OK;
 }
+
+// spvo_set_prematch for an entry point that fills two SIFT slots (spvo_sift_detect_pair, spvo_classic_sift_pair), in three steps.  The
+// matches are enqueued before the counts are known: scratch for full slots, results spaced by the matcher's capacity
+int sift_prematch_ensure(spvo_ctx *c) {
+  auto &s = c->sift;
+  if (!c->prematch) return SPVO_OK;
+  if (int rc = ensure_match(c, s.slot_cap, s.slot_cap)) return rc;
+  if (s.h_match_cap != c->match_cap) {
+    HIP_TRY(c, hipDeviceSynchronize());
+    s.match_pending = false;
+    host_free(s.h_match);
+    s.h_match_cap = 0;
+    s.pair.mcache.invalidate();
+    HIP_TRY(c, hipHostMalloc((void **)&s.h_match, (size_t)2 * c->match_cap * sizeof(int2)));
+    s.h_match_cap = c->match_cap;
+  }
+  return SPVO_OK;
+}
+// ... the two standard matches (slot_l -> partner[0], the stereo one, and -> partner[1], the temporal one, or -1) as ONE set of launches
+// behind the features (pair.ev_feat, recorded by the caller), counts read on the device
+int sift_enqueue_prematch(spvo_ctx *c, int slot_l, const int partner[2]) {
+  auto &s = c->sift;
+  if (!c->prematch) return SPVO_OK;
+  PostScope post(c);
+  MatchReq req[2];
+  int njobs = 0;
+  const SiftSlot &a = s.slots[slot_l];
+  for (int k = 0; k < 2; ++k) {
+    if (partner[k] < 0) continue;
+    const SiftSlot &b = s.slots[partner[k]];
+    req[njobs++] = MatchReq{a.d_desc, b.d_desc, s.slot_cap, s.slot_cap, a.d_n, b.d_n, a.d_sqn, b.d_sqn};
+  }
+  HIP_TRY(c, hipStreamWaitEvent(c->post, s.pair.ev_feat, 0));
+  if (int rc = enqueue_matches(c, req, njobs, c->pm_selector, c->pm_cross, c->pm_ratio, s.h_match)) return rc;
+  HIP_TRY(c, hipEventRecord(s.pair.ev_match, c->post));
+  s.match_pending = true;
+  return SPVO_OK;
+}
+// ... and, once both slots are filled, where their results will be: job `job`'s lands in cache entry `job`
+void sift_record_prematch(spvo_ctx *c, int slot_l, const int partner[2]) {
+  auto &s = c->sift;
+  if (!c->prematch) return;
+  for (int k = 0, job = 0; k < 2; ++k) {
+    if (partner[k] < 0) continue;
+    s.pair.mcache.record(job, slot_l, partner[k], s.slots[slot_l].gen, s.slots[partner[k]].gen, c->pm_selector, c->pm_cross, c->pm_ratio, s.h_match + (size_t)job * c->match_cap);
+    ++job;
+  }
+}
 }  // namespace
 
 void spvo_int::sift_release(spvo_ctx *c) {
@@ -334,18 +387,7 @@ int spvo_sift_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_
   if (int rc = sift_order_ensure(c, s.cand_cap)) return rc;
   if (int rc = sift_slots_ensure(c, slot_capacity, px)) return rc;
   const int cap = s.slot_cap;
-  if (c->prematch) {   // the matches are enqueued before the counts are known: scratch for full slots, results spaced by the matcher's capacity
-    if (int rc = ensure_match(c, cap, cap)) return rc;
-    if (s.h_match_cap != c->match_cap) {
-      HIP_TRY(c, hipDeviceSynchronize());
-      s.match_pending = false;
-      host_free(s.h_match);
-      s.h_match_cap = 0;
-      ps.mcache.invalidate();
-      HIP_TRY(c, hipHostMalloc((void **)&s.h_match, (size_t)2 * c->match_cap * sizeof(int2)));
-      s.h_match_cap = c->match_cap;
-    }
-  }
+  if (int rc = sift_prematch_ensure(c)) return rc;
   P.pyr = s.pyr;
   // both slots are being rewritten: whatever was matched against their old contents is stale
   const int slots[2] = {slot_l, slot_r};
@@ -356,7 +398,6 @@ int spvo_sift_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_
   ps.last_slot_l = -1;
   HIP_TRY(c, hipStreamSynchronize(st));   // (the staging buffer and the mirrors are the previous call's until its work is done)
   ps.stage(img_l, img_r, rows, cols, stride);
-  int njobs = 0;
   for (int attempt = 0;; ++attempt) {
     // a match of an earlier call (or of the attempt before) may still read the slots where the L2 matcher runs
     if (s.match_pending) HIP_TRY(c, hipStreamWaitEvent(st, ps.ev_match, 0));
@@ -369,23 +410,7 @@ int spvo_sift_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_
       if (int rc = sift_enqueue_order(c, s.slots[slots[k]], k)) return rc;
     }
     HIP_TRY(c, hipEventRecord(ps.ev_feat, st));
-    // spvo_set_prematch: the two standard matches as ONE set of launches behind the features, counts read on the device (a pair that turns
-    // out not to fit its slots is matched on whatever rows the slots hold; that result is dropped below)
-    njobs = 0;
-    if (c->prematch) {
-      PostScope post(c);
-      MatchReq req[2];
-      const SiftSlot &a = s.slots[slot_l];
-      for (int k = 0; k < 2; ++k) {
-        if (partner[k] < 0) continue;
-        const SiftSlot &b = s.slots[partner[k]];
-        req[njobs++] = MatchReq{a.d_desc, b.d_desc, cap, cap, a.d_n, b.d_n, a.d_sqn, b.d_sqn};
-      }
-      HIP_TRY(c, hipStreamWaitEvent(c->post, ps.ev_feat, 0));
-      if (int rc = enqueue_matches(c, req, njobs, c->pm_selector, c->pm_cross, c->pm_ratio, s.h_match)) return rc;
-      HIP_TRY(c, hipEventRecord(ps.ev_match, c->post));
-      s.match_pending = true;
-    }
+    if (int rc = sift_enqueue_prematch(c, slot_l, partner)) return rc;   // (a pair that turns out not to fit its slots: that result is dropped below)
     HIP_TRY(c, wait_event(ps.ev_feat));   // the one wait of the call: the matches go on behind it
     int most = 0;
     for (int k = 0; k < 2; ++k) most = std::max(most, std::max(s.h_n[4 * k + 1], s.h_n[4 * k + 2]));
@@ -406,13 +431,100 @@ int spvo_sift_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_
     for (int i = 0; i < ncopy; ++i) outs[k]->kp[i] = sift_record(src[i].pos, src[i].off, __builtin_bit_cast(int, src[i].angle));
     if (ncopy > 0) std::memcpy(outs[k]->desc, s.hm_desc + (size_t)k * cap * 128, (size_t)ncopy * 128 * sizeof(float));
   }
-  if (c->prematch)
-    for (int k = 0, job = 0; k < 2; ++k) {
-      if (partner[k] < 0) continue;
-      // job `job`'s result lands in cache entry `job`
-      ps.mcache.record(job, slot_l, partner[k], s.slots[slot_l].gen, s.slots[partner[k]].gen, c->pm_selector, c->pm_cross, c->pm_ratio, s.h_match + (size_t)job * c->match_cap);
-      ++job;
+  sift_record_prematch(c, slot_l, partner);
+  ps.last_slot_l = slot_l;
+  return SPVO_OK;
+}
+
+// Shi-Tomasi / FAST + SIFT of a stereo pair into two SIFT slots.  Per image: the detector's chain on the resident u8 image (spvo_classic.hip),
+// the SIFT base level of that image -- every record lies on octave 0, layer 0 -- and sift_describe_given_kernel on the detector's list,
+// whose sink is the slot and the pinned mirrors.  A slot's d_src and the mirror h_src hold the 24-byte RECORDS here (SiftKey), not sources.
+// The grid is fixed: four waves per CU stride over the records, whose number only the device knows (32 KB of LDS per wave: five per CU fit
+// on paper and measure 18 % slower than four, NOTES.md).
+int spvo_classic_sift_pair(spvo_ctx *c, const spvo_classic_opts *opts, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int slot_l, int slot_r,
+                           spvo_sift_features *out_l, spvo_sift_features *out_r) {
+  static_assert(sizeof(SiftKey) <= sizeof(SiftSrc) && sizeof(spvo_sift_keypoint) == sizeof(SiftKey), "a slot's source array holds the records");
+  if (!c || !opts || !img_l || !img_r || !out_l || !out_r || rows <= 0 || cols <= 0 || stride < (size_t)cols) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  const int kind = opts->kind, cap = opts->slot_capacity;
+  if (kind != SPVO_CLASSIC_GFTT_SIFT && kind != SPVO_CLASSIC_FAST_SIFT)
+    return fail(c, SPVO_ERR_INVALID, "spvo_classic_sift_pair: kind %d (SPVO_CLASSIC_GFTT_SIFT or SPVO_CLASSIC_FAST_SIFT; the other kinds are spvo_classic_detect's)", kind);
+  if (slot_l < 0 || slot_l >= N_SIFT_SLOTS || slot_r < 0 || slot_r >= N_SIFT_SLOTS || slot_l == slot_r) return fail(c, SPVO_ERR_INVALID, "bad slot");
+  spvo_sift_features *outs[2] = {out_l, out_r};
+  for (auto *o : outs)
+    if (o->cap < 0 || (o->cap > 0 && (!o->kp || !o->desc))) return fail(c, SPVO_ERR_INVALID, "bad output buffer");
+  if (cap <= 0 || cap > SIFT_SLOT_MAX) return fail(c, SPVO_ERR_INVALID, "slot_capacity must be 1 .. %d", SIFT_SLOT_MAX);
+  if (int rc = classic_detector_check(c, "spvo_classic_sift_pair", opts, rows, cols)) return rc;
+  if (int rc = sift_check_image(c, "spvo_classic_sift_pair", rows, cols)) return rc;
+  if (int rc = require_idle(c)) return rc;
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  out_l->n = out_r->n = 0;
+  c->akaze.valid = false;   // as spvo_sift_detect_pair: the AKAZE scale space's claim ends
+  auto &s = c->sift;
+  PairStage &ps = s.pair;
+  hipStream_t st = c->stream2;
+  const size_t px = (size_t)rows * cols;
+  s.rows = s.cols = 0;   // the pyramid buffer holds one level of each image in turn: nothing spvo_sift_debug_level could serve
+  if (int rc = classic_image_ensure(c, rows, cols)) return rc;
+  if (px > s.pyr_cap) {
+    HIP_TRY(c, hipStreamSynchronize(st));
+    dev_free(s.pyr);
+    s.pyr_cap = 0;
+    if (int rc = dev_alloc(c, &s.pyr, px, false)) return rc;
+    s.pyr_cap = px;
+  }
+  if (int rc = sift_slots_ensure(c, cap, px)) return rc;
+  if (int rc = sift_prematch_ensure(c)) return rc;
+  SiftPyr P{};
+  P.n_oct = 1; P.h[0] = rows; P.w[0] = cols; P.pyr = s.pyr;
+  // both slots are being rewritten: whatever was matched against their old contents is stale
+  const int slots[2] = {slot_l, slot_r};
+  for (int sl : slots) slot_rewrite(s.slots[sl]);
+  ps.mcache.invalidate();
+  // (the temporal partner is forgotten BEFORE staging, as in spvo_sift_detect_pair: a call that fails from now on leaves none for the next call)
+  const int partner[2] = {slot_r, ps.temporal_partner(slot_l, slot_r, ps.last_slot_l >= 0 && s.slots[ps.last_slot_l].filled)};
+  ps.last_slot_l = -1;
+  HIP_TRY(c, hipStreamSynchronize(st));   // (the staging buffer and the mirrors are the previous call's until its work is done)
+  ps.stage(img_l, img_r, rows, cols, stride);
+  // a match of an earlier call may still read the slots where the L2 matcher runs
+  if (s.match_pending) HIP_TRY(c, hipStreamWaitEvent(st, ps.ev_match, 0));
+  const int waves = std::min(std::max(tuning("sift_pair_waves_per_cu", 4), 1), 64) * c->num_cus;   // (diagnostic: the grid NOTES.md measures the default against)
+  for (int k = 0; k < 2; ++k) {   // left chain, then the right one: the resident image, the detector's list and the base level are reused in stream order
+    if (int rc = classic_detector_enqueue(c, opts, ps.h_img + k * px, rows, cols)) return rc;
+    if (int rc = sift_enqueue_pyramid(c, c->cls.im, rows, cols, P, false, false, true)) return rc;
+    const SiftSlot &t = s.slots[slots[k]];
+    const SiftDetectorIO io{c->cls.xy,
+                            c->cls.resp,
+                            c->cls.counters,
+                            SiftKey{0.f, 0.f, kind == SPVO_CLASSIC_GFTT_SIFT ? 5.f : 7.f, -1.f, 0.f, 0},   // KeyPoint::convert(corners, keypoints, blockSize = 5) / KeyPoint(x, y, 7.f, -1, score)
+                            cap,
+                            t.d_desc,
+                            t.d_sqn,
+                            reinterpret_cast<SiftKey *>(t.d_src),
+                            t.d_n,
+                            s.hm_desc + (size_t)k * s.slot_cap * 128,
+                            reinterpret_cast<SiftKey *>(s.h_src + (size_t)k * s.slot_cap),
+                            s.h_n + 4 * k};
+    hipLaunchKernelGGL((sift_describe_given_kernel<0, SiftDetectorIO>), dim3(waves), dim3(64), 0, st, P, 0, io);
+    HIP_TRY(c, hipGetLastError());
+  }
+  HIP_TRY(c, hipEventRecord(ps.ev_feat, st));
+  if (int rc = sift_enqueue_prematch(c, slot_l, partner)) return rc;   // (a pair that turns out not to fit its slots: that result is dropped below)
+  HIP_TRY(c, wait_event(ps.ev_feat));   // the one wait of the call: the matches go on behind it
+  for (int k = 0; k < 2; ++k) {
+    outs[k]->n = s.h_n[4 * k];
+    if (s.h_n[4 * k + 1]) return fail(c, SPVO_ERR_CAPACITY, "spvo_classic_sift_pair: key buffer overflow in the %s image", k ? "right" : "left");
+  }
+  if (out_l->n > cap || out_r->n > cap) return fail(c, SPVO_ERR_CAPACITY, "spvo_classic_sift_pair: %d / %d rows do not fit slots of %d (slot_capacity)", out_l->n, out_r->n, cap);
+  for (int k = 0; k < 2; ++k) {
+    SiftSlot &t = s.slots[slots[k]];
+    t.n = outs[k]->n; t.filled = true;
+    const int ncopy = std::min(t.n, outs[k]->cap);
+    if (ncopy > 0) {
+      std::memcpy(outs[k]->kp, s.h_src + (size_t)k * s.slot_cap, (size_t)ncopy * sizeof(SiftKey));
+      std::memcpy(outs[k]->desc, s.hm_desc + (size_t)k * s.slot_cap * 128, (size_t)ncopy * 128 * sizeof(float));
     }
+  }
+  sift_record_prematch(c, slot_l, partner);
   ps.last_slot_l = slot_l;
   return SPVO_OK;
 }
@@ -482,9 +594,9 @@ int spvo_sift_describe(spvo_ctx *c, const uint8_t *img, int rows, int cols, size
   s.plan = P; s.rows = rows; s.cols = cols; s.gauss_only = true; s.first = first;
   // (diagnostic, tuning "sift_describe_form": 1 = the staged form NOTES.md measures against the columns)
   if (tuning("sift_describe_form", 0) == 1)
-    hipLaunchKernelGGL(sift_describe_given_kernel<1>, dim3(std::min(n, 65536)), dim3(64), 0, st, P, first, (const SiftKey *)s.given_kp, n, s.given_desc);
+    hipLaunchKernelGGL((sift_describe_given_kernel<1, SiftGivenIO>), dim3(std::min(n, 65536)), dim3(64), 0, st, P, first, SiftGivenIO{s.given_kp, n, s.given_desc});
   else
-    hipLaunchKernelGGL(sift_describe_given_kernel<0>, dim3(std::min(n, 65536)), dim3(64), 0, st, P, first, (const SiftKey *)s.given_kp, n, s.given_desc);
+    hipLaunchKernelGGL((sift_describe_given_kernel<0, SiftGivenIO>), dim3(std::min(n, 65536)), dim3(64), 0, st, P, first, SiftGivenIO{s.given_kp, n, s.given_desc});
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(desc, s.given_desc, (size_t)n * 128 * sizeof(float), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));   // the one wait of the call

@@ -350,13 +350,16 @@ public:
   // SPVO_ERR_CAPACITY), and every pair without a route, goes through the per-image path and is matched from the host matrices.
   // setBriskPairResident: BRISK + BRISK takes its route only with this as well.  setAkazeDescriptor: AKAZE + AKAZE runs (per image); off,
   // that pair is refused as every pair that does not run is.  setAkazePairResident: AKAZE + AKAZE takes its route (spvo_akaze_detect_pair)
-  // only with this as well as setAkazeDescriptor and setDeviceResident.
+  // only with this as well as setAkazeDescriptor and setDeviceResident.  setSiftDescribeResident: ShiTomasi + SIFT and FAST + SIFT take
+  // their route (spvo_classic_sift_pair: detector, SIFT base level and descriptor on the device, rows into the SIFT slots) only with this as
+  // well as setDeviceResident; the other detectors with the SIFT extractor have no route.
   static void setDeviceResident(bool on);
   static void setResidentCapacity(int rows);   // rows per binary slot [8192]
   static void setBriskPairResident(bool on);   // [off]
   static void setAkazeDescriptor(bool on);     // [off]
   static void setAkazePairResident(bool on);   // [off]
-  // pairs that actually stayed resident (spvo_classic_detect / spvo_sift_detect_pair / spvo_brisk_detect_pair / spvo_akaze_detect_pair returned SPVO_OK): what tells the resident path from its fallback
+  static void setSiftDescribeResident(bool on);   // [off]
+  // pairs that actually stayed resident (spvo_classic_detect / spvo_sift_detect_pair / spvo_brisk_detect_pair / spvo_akaze_detect_pair / spvo_classic_sift_pair returned SPVO_OK): what tells the resident path from its fallback
   unsigned residentPairs() const { return resident_ok_pairs_; }
 
 private:
@@ -364,6 +367,7 @@ private:
   bool brisk_pair_resident_ = false;   // setBriskPairResident at construction
   bool akaze_descriptor_ = false;      // setAkazeDescriptor at construction
   bool akaze_pair_resident_ = false;   // setAkazePairResident at construction
+  bool sift_describe_resident_ = false;   // setSiftDescribeResident at construction
   bool pairRuns() const;               // this detector / descriptor pair runs in this build
   int resident_capacity_ = 8192;
   unsigned resident_pairs_ = 0;   // pairs handed to a resident route: pair k lives in slots 2 (k % 4), 2 (k % 4) + 1

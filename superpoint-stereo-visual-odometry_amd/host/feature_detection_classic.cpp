@@ -13,10 +13,12 @@ static int g_classic_resident_capacity = 8192;
 static bool g_classic_brisk_pair_resident = false;
 static bool g_classic_akaze_descriptor = false;
 static bool g_classic_akaze_pair_resident = false;
+static bool g_classic_sift_describe_resident = false;
 void ClassicFeatureFrontEnd::setDeviceResident(bool on) { g_classic_resident = on; }
 void ClassicFeatureFrontEnd::setBriskPairResident(bool on) { g_classic_brisk_pair_resident = on; }
 void ClassicFeatureFrontEnd::setAkazeDescriptor(bool on) { g_classic_akaze_descriptor = on; }
 void ClassicFeatureFrontEnd::setAkazePairResident(bool on) { g_classic_akaze_pair_resident = on; }
+void ClassicFeatureFrontEnd::setSiftDescribeResident(bool on) { g_classic_sift_describe_resident = on; }
 void ClassicFeatureFrontEnd::setResidentCapacity(int rows) { g_classic_resident_capacity = rows; }
 
 #ifdef SPVO_USE_OPENCV
@@ -88,8 +90,8 @@ bool ClassicFeatureFrontEnd::available() { return true; }
 
 enum class Detect { Orb, Gftt, Fast, Sift, Brisk, Akaze };       // detectKeypoints: spvo_<this>_detect
 enum class Describe { WithDetector, Orb, Brisk, Akaze, Sift };   // describeKeypoints: the rows detectKeypoints kept, or spvo_<this>_describe on the given keypoints
-enum class Route { None, Classic, SiftPair, BriskPair, AkazePair };   // setDeviceResident: the per-image path, spvo_classic_detect (kind), spvo_sift_detect_pair, spvo_brisk_detect_pair, spvo_akaze_detect_pair
-enum class OptIn { None, AkazeDescriptor, BriskPairResident, AkazePairResident };   // to run at all: setAkazeDescriptor; to stay resident: setBriskPairResident, setAkazePairResident
+enum class Route { None, Classic, SiftPair, BriskPair, AkazePair, ClassicSift };   // setDeviceResident: the per-image path, spvo_classic_detect (kind), spvo_sift_detect_pair, spvo_brisk_detect_pair, spvo_akaze_detect_pair, spvo_classic_sift_pair (kind)
+enum class OptIn { None, AkazeDescriptor, BriskPairResident, AkazePairResident, SiftDescribeResident };   // to run at all: setAkazeDescriptor; to stay resident: setBriskPairResident, setAkazePairResident, setSiftDescribeResident
 
 struct ClassicPair {
   DetectorType detector;
@@ -99,7 +101,7 @@ struct ClassicPair {
   Describe describe;
   int cols, type;        // a descriptor row; CV_8UC1 rows are matched with NORM_HAMMING, CV_32FC1 rows with NORM_L2
   Route route;
-  int kind;              // Route::Classic: the spvo_classic_kind
+  int kind;              // Route::Classic, Route::ClassicSift: the spvo_classic_kind
   OptIn opt_in;          // what the pair needs to run at all ...
   OptIn resident_opt_in; // ... and what its route needs beside setDeviceResident
   size_t rowBytes() const { return (size_t)cols * (type == CV_32FC1 ? sizeof(float) : 1); }
@@ -114,8 +116,8 @@ static const ClassicPair kClassicPairs[] = {
     {DetectorType::AKAZE, DescriptorType::BRISK, Detect::Akaze, 0.f, Describe::Brisk, 64, CV_8UC1, Route::None, 0, OptIn::None, OptIn::None},
     {DetectorType::AKAZE, DescriptorType::AKAZE, Detect::Akaze, 0.f, Describe::Akaze, SPVO_AKAZE_DESC_BYTES, CV_8UC1, Route::AkazePair, 0, OptIn::AkazeDescriptor, OptIn::AkazePairResident},
     {DetectorType::SIFT, DescriptorType::SIFT, Detect::Sift, 0.f, Describe::WithDetector, 128, CV_32FC1, Route::SiftPair, 0, OptIn::None, OptIn::None},
-    {DetectorType::ShiTomasi, DescriptorType::SIFT, Detect::Gftt, 5.f, Describe::Sift, 128, CV_32FC1, Route::None, 0, OptIn::None, OptIn::None},
-    {DetectorType::FAST, DescriptorType::SIFT, Detect::Fast, 7.f, Describe::Sift, 128, CV_32FC1, Route::None, 0, OptIn::None, OptIn::None},
+    {DetectorType::ShiTomasi, DescriptorType::SIFT, Detect::Gftt, 5.f, Describe::Sift, 128, CV_32FC1, Route::ClassicSift, SPVO_CLASSIC_GFTT_SIFT, OptIn::None, OptIn::SiftDescribeResident},
+    {DetectorType::FAST, DescriptorType::SIFT, Detect::Fast, 7.f, Describe::Sift, 128, CV_32FC1, Route::ClassicSift, SPVO_CLASSIC_FAST_SIFT, OptIn::None, OptIn::SiftDescribeResident},
     {DetectorType::ORB, DescriptorType::SIFT, Detect::Orb, 0.f, Describe::Sift, 128, CV_32FC1, Route::None, 0, OptIn::None, OptIn::None},
     {DetectorType::BRISK, DescriptorType::SIFT, Detect::Brisk, 0.f, Describe::Sift, 128, CV_32FC1, Route::None, 0, OptIn::None, OptIn::None},
     {DetectorType::AKAZE, DescriptorType::SIFT, Detect::Akaze, 0.f, Describe::Sift, 128, CV_32FC1, Route::None, 0, OptIn::None, OptIn::None},
@@ -177,7 +179,8 @@ static cv::KeyPoint to_keypoint(float x, float y, float response, const ClassicP
   k.octave = 0;
   return k;
 }
-static cv::KeyPoint to_keypoint(const spvo_sift_keypoint &r, const ClassicPair &p) {   // SIFT, and BRISK's records of the same layout
+static cv::KeyPoint to_keypoint(const spvo_sift_keypoint &r, const ClassicPair &p) {   // SIFT, BRISK's records of the same layout, and spvo_classic_sift_pair's
+                                                                                       // (size 5 / 7, angle -1, octave 0: what to_keypoint(x, y, response, p) builds)
   cv::KeyPoint k(cv::Point2f(r.x, r.y), r.size);
   // a BRISK keypoint keeps the angle its detector reports, -1; the record of spvo_brisk_detect_pair carries the extractor's, which stays with the slot
   k.angle = p.detect == Detect::Brisk ? -1.f : r.angle;
@@ -463,7 +466,9 @@ bool ClassicFeatureFrontEnd::residentPair(const ClassicPair &p, cv::Mat &img_l, 
 bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &img_l, cv::Mat &img_r) {
   if (!image_ok(img_l) || !image_ok(img_r) || (size_t)img_l.step != (size_t)img_r.step) return false;
   const ClassicPair &p = *pair();   // (addStereoImagePair has asked pairRuns)
-  if (p.route == Route::None || (p.resident_opt_in == OptIn::BriskPairResident && !brisk_pair_resident_) || (p.resident_opt_in == OptIn::AkazePairResident && !akaze_pair_resident_)) return false;
+  if (p.route == Route::None || (p.resident_opt_in == OptIn::BriskPairResident && !brisk_pair_resident_) || (p.resident_opt_in == OptIn::AkazePairResident && !akaze_pair_resident_) ||
+      (p.resident_opt_in == OptIn::SiftDescribeResident && !sift_describe_resident_))
+    return false;
   const uint8_t *l = img_l.ptr<uint8_t>(0), *r = img_r.ptr<uint8_t>(0);
   const int rows = img_l.rows, cols = img_l.cols;
   const size_t step = (size_t)img_l.step;
@@ -488,6 +493,14 @@ bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &img_l, cv::Mat 
     return residentPair<spvo_akaze_features>(p, img_l, img_r, "spvo_akaze_detect_pair", [&](int slot_l, int slot_r, spvo_akaze_features *f) {
       return spvo_akaze_detect_pair(ctx_, l, r, rows, cols, step, 0.001f, slot_l, slot_r, resident_capacity_, &f[0], &f[1]);
     });
+  case Route::ClassicSift: {   // the detector's parameters are detectKeypoints': spvo_default_classic_opts
+    spvo_classic_opts opts;
+    spvo_default_classic_opts(&opts, p.kind);
+    opts.slot_capacity = resident_capacity_;
+    return residentPair<spvo_sift_features>(p, img_l, img_r, "spvo_classic_sift_pair", [&](int slot_l, int slot_r, spvo_sift_features *f) {
+      return spvo_classic_sift_pair(ctx_, &opts, l, r, rows, cols, step, slot_l, slot_r, &f[0], &f[1]);
+    });
+  }
   case Route::None:
     break;
   }
@@ -518,6 +531,7 @@ ClassicFeatureFrontEnd::ClassicFeatureFrontEnd(const DetectorType detector_type,
   resident_capacity_ = g_classic_resident_capacity;
   brisk_pair_resident_ = g_classic_brisk_pair_resident;
   akaze_pair_resident_ = g_classic_akaze_pair_resident;
+  sift_describe_resident_ = g_classic_sift_describe_resident;
 }
 
 ClassicFeatureFrontEnd::~ClassicFeatureFrontEnd() {

@@ -435,6 +435,10 @@ void spvo_host_classic_set_akaze_descriptor(int on) { ClassicFeatureFrontEnd::se
 // (with spvo_host_classic_set_akaze_descriptor and the resident option of the sequence run)
 void spvo_host_classic_set_akaze_resident(int on) { ClassicFeatureFrontEnd::setAkazePairResident(on != 0); }
 
+// ClassicFeatureFrontEnd::setSiftDescribeResident for the front ends constructed afterwards: ShiTomasi + SIFT and FAST + SIFT through
+// spvo_classic_sift_pair when the resident option of the sequence run is on as well
+void spvo_host_classic_set_sift_describe_resident(int on) { ClassicFeatureFrontEnd::setSiftDescribeResident(on != 0); }
+
 // the ORB + ORB front end at the native resolution (the export's first form)
 int spvo_host_classic_sequence(int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l, const double *P_r, int knn,
                                int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats, double *seconds) {

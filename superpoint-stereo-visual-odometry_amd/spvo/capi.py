@@ -36,6 +36,7 @@ class ClassicFeatures(C.Structure):
 
 CLASSIC_KINDS = {"ORB": 0, "ShiTomasi": 1, "GFTT": 1, "FAST": 2, "ShiTomasi+BRISK": 3, "GFTT+BRISK": 3, "FAST+BRISK": 4}
 CLASSIC_BRISK_KINDS = (3, 4)          # spvo_classic_kind values whose rows are 64 bytes
+CLASSIC_SIFT_KINDS = {"ShiTomasi": 5, "GFTT": 5, "FAST": 6}   # spvo_classic_kind values of spvo_classic_sift_pair, by detector
 
 
 class BriskFeatures(C.Structure):          # spvo_brisk_features
@@ -93,7 +94,7 @@ SYMBOLS = [
     "spvo_default_config", "spvo_create", "spvo_destroy", "spvo_last_error", "spvo_load_weights", "spvo_engine_precision", "spvo_set_fp32_split",
     "spvo_preprocess", "spvo_forward", "spvo_debug_tensor", "spvo_heatmap", "spvo_nms",
     "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8",
-    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_akaze_describe", "spvo_akaze_detect_pair", "spvo_akaze_suppress_debug", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_describe", "spvo_sift_detect_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
+    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_akaze_describe", "spvo_akaze_detect_pair", "spvo_akaze_suppress_debug", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_describe", "spvo_sift_detect_pair", "spvo_classic_sift_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
     "spvo_profile_enable", "spvo_profile_reset", "spvo_profile_only", "spvo_profile_count", "spvo_profile_get", "spvo_profile_stage_kernel",
     "spvo_set_tuning", "spvo_get_tuning", "spvo_clear_tuning",
     "spvo_comm_unique_id", "spvo_comm_available", "spvo_comm_create", "spvo_comm_create_host", "spvo_comm_rank", "spvo_comm_world", "spvo_comm_destroy",
@@ -166,6 +167,7 @@ def load() -> C.CDLL:
     lib.spvo_sift_debug_level.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, ip, ip]
     lib.spvo_sift_describe.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, vp]
     lib.spvo_sift_detect_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(SiftFeatures), C.POINTER(SiftFeatures)]
+    lib.spvo_classic_sift_pair.argtypes = [vp, C.POINTER(ClassicOpts), vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.POINTER(SiftFeatures), C.POINTER(SiftFeatures)]
     lib.spvo_sift_slot_rows.argtypes = [vp, C.c_int, ip]
     lib.spvo_match_l2_slots.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]
     lib.spvo_sift_order_debug.argtypes = [vp, vp, C.c_int, vp, ip]
@@ -730,6 +732,42 @@ class Context:
             e = SpvoError(rc, self.lib.spvo_last_error(self.h).decode())
             e.counts = (feats[0].n, feats[1].n)
             raise e
+        out = []
+        for (kp, desc), f in zip(bufs, feats):
+            m = min(f.n, want)
+            out.append(dict(kp=kp[:m].copy(), desc=desc[:m].copy(), n=f.n))
+        return out[0], out[1]
+
+    def classic_sift_pair(self, img_l, img_r, slot_l: int, slot_r: int, kind="FAST", cap: Optional[int] = None, **opts):
+        """One stereo pair through the Shi-Tomasi ("ShiTomasi") or FAST ("FAST") detector and the SIFT extractor into two SIFT slots
+        (spvo_classic_sift_pair); kind may also be a spvo_classic_kind number.  opts: fields of spvo_classic_opts that differ from the
+        reference's parameters (slot_capacity among them); cap: rows the host buffers take (None: slot_capacity, i.e. all).
+        -> (left, right): dicts like sift_detect's -- kp [m] SIFT_KP_DTYPE records {x, y, 5 or 7, -1, response, 0} in the detector's order,
+        desc [m, 128], n -- the host's copy of what the slots hold.  On SPVO_ERR_CAPACITY the SpvoError carries the two counts as .counts."""
+        o = ClassicOpts()
+        self.lib.spvo_default_classic_opts(C.byref(o), CLASSIC_SIFT_KINDS[kind] if isinstance(kind, str) else int(kind))
+        for k, v in opts.items():
+            if not hasattr(o, k):
+                raise TypeError(k)
+            setattr(o, k, v)
+        l, r = _u8_rows(img_l), _u8_rows(img_r)
+        if l.shape != r.shape or l.strides[0] != r.strides[0]:
+            l, r = np.ascontiguousarray(l), np.ascontiguousarray(r)
+            if l.shape != r.shape:
+                raise ValueError("the two images of a pair must have one shape")
+        want = max(int(o.slot_capacity), 1) if cap is None else int(cap)
+        bufs, feats = [], []
+        for _ in range(2):
+            kp = np.zeros(max(want, 1), SIFT_KP_DTYPE)
+            desc = np.zeros((max(want, 1), 128), np.float32)
+            bufs.append((kp, desc))
+            feats.append(SiftFeatures(0, kp.ctypes.data, desc.ctypes.data, want))
+        rc = self.lib.spvo_classic_sift_pair(self.h, C.byref(o), _ptr(l), _ptr(r), l.shape[0], l.shape[1], l.strides[0], slot_l, slot_r, C.byref(feats[0]), C.byref(feats[1]))
+        if rc:
+            e = SpvoError(rc, self.lib.spvo_last_error(self.h).decode())
+            e.counts = (feats[0].n, feats[1].n)
+            raise e
+        self._resident_shape = l.shape
         out = []
         for (kp, desc), f in zip(bufs, feats):
             m = min(f.n, want)

@@ -342,13 +342,15 @@ class FrontEnd:
 
 
 def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_threshold=2.0, refinement_degree=4, warm=0, detector="ORB", input_size=None, resident=False,
-                     resident_capacity=0, trace=False, descriptor="ORB", brisk_resident=False, akaze_descriptor=False, akaze_resident=False):
+                     resident_capacity=0, trace=False, descriptor="ORB", brisk_resident=False, akaze_descriptor=False, akaze_resident=False, sift_describe_resident=False):
     """stereoCallback replayed on ClassicFeatureFrontEnd(detector, descriptor, BF, ...) (node.cpp:353-360) over host image pairs -- detector
     "ORB", "ShiTomasi" or "FAST" with descriptor "ORB", "ShiTomasi", "FAST", "BRISK" or "AKAZE" with descriptor "BRISK" (64-byte rows; detector "BRISK"
     or "AKAZE" with the default descriptor "ORB" does not run; "AKAZE" with descriptor "AKAZE" -- orientation and the 61-byte MLDB rows of
     spvo_akaze_describe -- runs with akaze_descriptor=True (ClassicFeatureFrontEnd::setAkazeDescriptor, reset afterwards) and is refused without), "ShiTomasi", "FAST", "ORB",
     "BRISK" or "AKAZE" with descriptor "SIFT" (spvo_sift_describe on the detector's keypoints as they are: 128 floats per row, matched with
-    NORM_L2; always the per-image path, classic_resident_pairs() stays 0), or detector "SIFT" (SIFT descriptors whatever `descriptor` says, as before); input_size None: at their native resolution, (height, width): through preprocessImageImpl first
+    NORM_L2; the per-image path and classic_resident_pairs() stays 0 -- except "ShiTomasi" and "FAST" with sift_describe_resident=True
+    (ClassicFeatureFrontEnd::setSiftDescribeResident, reset afterwards) and resident=True: then it is one spvo_classic_sift_pair per pair into the
+    SIFT slots), or detector "SIFT" (SIFT descriptors whatever `descriptor` says, as before); input_size None: at their native resolution, (height, width): through preprocessImageImpl first
     (classic.cpp:96-100).  Returns (poses [n, 7] = q xyzw + t of cam0_curr_T_cam0_prev, stats [n, 4] = keypoints L, R, stereo
     matches, PnP inliers, seconds spent on frames warm .. n-1).
     resident: ClassicFeatureFrontEnd::setDeviceResident for this run -- one spvo_classic_detect (SIFT: spvo_sift_detect_pair) per pair, features
@@ -376,6 +378,8 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     lib.spvo_host_classic_set_akaze_resident.argtypes = [C.c_int]
     lib.spvo_host_classic_set_akaze_descriptor.restype = None
     lib.spvo_host_classic_set_akaze_descriptor.argtypes = [C.c_int]
+    lib.spvo_host_classic_set_sift_describe_resident.restype = None
+    lib.spvo_host_classic_set_sift_describe_resident.argtypes = [C.c_int]
     n = len(frames)
     ls = [np.ascontiguousarray(f[0], np.uint8) for f in frames]
     rs = [np.ascontiguousarray(f[1], np.uint8) for f in frames]
@@ -393,6 +397,7 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     lib.spvo_host_classic_set_brisk_resident(int(bool(brisk_resident)))
     lib.spvo_host_classic_set_akaze_resident(int(bool(akaze_resident)))
     lib.spvo_host_classic_set_akaze_descriptor(int(bool(akaze_descriptor)))
+    lib.spvo_host_classic_set_sift_describe_resident(int(bool(sift_describe_resident)))
     try:
         args = (n, pl, pr, rows, cols, Pl.ctypes.data, Pr.ctypes.data, 1 if selector == "KNN" else 0, int(cross_check), stereo_threshold, refinement_degree, warm,
                 poses.ctypes.data, stats.ctypes.data, C.byref(sec), ih, iw, digest.ctypes.data if trace else None)
@@ -405,6 +410,7 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
         lib.spvo_host_classic_set_brisk_resident(0)
         lib.spvo_host_classic_set_akaze_resident(0)
         lib.spvo_host_classic_set_akaze_descriptor(0)
+        lib.spvo_host_classic_set_sift_describe_resident(0)
     if rc == -1000000:
         raise ValueError("unknown detector %r" % (detector,))
     if rc == -1000001:

@@ -1,13 +1,15 @@
 """The classic front end on the GPU.
 
-python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK|AKAZE] [--descriptor ORB|BRISK|AKAZE|SIFT] [--resident] [--brisk-resident] [--akaze-resident]
+python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK|AKAZE] [--descriptor ORB|BRISK|AKAZE|SIFT] [--resident] [--brisk-resident] [--akaze-resident] [--sift-resident]
     ClassicFeatureFrontEnd(detector, descriptor, BF, KNN) over the synthetic stream: frames/s of the synchronous stereoCallback
     (--descriptor BRISK: with --detector ShiTomasi, FAST, BRISK or AKAZE; --detector BRISK: with --descriptor BRISK only; --detector AKAZE:
     with --descriptor BRISK or AKAZE -- the latter sets ClassicFeatureFrontEnd::setAkazeDescriptor for the run: 61-byte MLDB rows);
-    --descriptor SIFT: with any of the five detectors (spvo_sift_describe; always the per-image path);
+    --descriptor SIFT: with any of the five detectors (spvo_sift_describe; the per-image path, but see --sift-resident);
     --resident: with ClassicFeatureFrontEnd::setDeviceResident (one spvo_classic_detect per pair, matching on the binary slots);
     --brisk-resident: with setBriskPairResident as well (BRISK + BRISK through one spvo_brisk_detect_pair per pair; needs --resident).
     --akaze-resident: with setAkazePairResident as well (AKAZE + AKAZE through one spvo_akaze_detect_pair per pair; needs --resident).
+    --sift-resident: with setSiftDescribeResident as well (ShiTomasi / FAST + SIFT through one spvo_classic_sift_pair per pair; needs --resident;
+    also taken by --ab for its resident runs).
 python tools/classic_bench.py [frames] --detector ShiTomasi|FAST|ORB --descriptor ORB|BRISK --ab ROUNDS
     the same stream with setDeviceResident off and on, alternating, ROUNDS times each in one process: ms per pair of every run, the median
     and the min .. max spread of each setting, and how many pairs of a resident run stayed resident.
@@ -45,12 +47,17 @@ python tools/classic_bench.py --leg akaze_pair [--calls 100]
     for rocprofv3 --kernel-trace --stats as above: the detector's kernels up to akaze_refine_kernel, then akaze_suppress_first_kernel /
     akaze_suppress_second_kernel / akaze_suppress_compact_kernel / akaze_describe_kernel / akaze_pair_finish_kernel, twice per call.
     Its yardsticks are --leg akaze_detect and --leg akaze_describe: two per-image detects plus two describes.
-python tools/classic_bench.py --leg fast_sift|sift_describe [--calls 50] [--form 0|1] [--yardstick]
+python tools/classic_bench.py --leg fast_sift|gftt_sift|sift_describe [--calls 50] [--form 0|1] [--yardstick] [--sift-resident]
     FAST + SIFT per image at 1241 x 376, for rocprofv3 --kernel-trace --stats as above.  sift_describe: spvo_sift_describe alone on the FAST
     keypoints of the sample (size 7, angle -1, octave 0; image passed with every call): sift_blur_kernel x 6 / sift_describe_given_kernel is
     the split.  fast_sift: spvo_fast_detect + spvo_sift_describe(img = NULL), what ClassicFeatureFrontEnd(FAST, SIFT) runs per image.
     --form 1: tuning "sift_describe_form" = 1, the staged form of the sums instead of the columns.  --yardstick (fast_sift): afterwards, in the
     same run, ms per pair through the host class for FAST + SIFT, SIFT + SIFT and FAST + BRISK over the synthetic stream.
+    gftt_sift: the same with spvo_gftt_detect and size 5.  --sift-resident (fast_sift, gftt_sift): the leg is ONE spvo_classic_sift_pair on the
+    sample pair -- BOTH images per call, rotating through the slot ring -- instead of the two per-image calls: the detector's kernels, one
+    sift_blur_kernel and sift_describe_given_kernel, twice per call; with --yardstick the host class runs that detector + SIFT with
+    setDeviceResident and setSiftDescribeResident and says how many pairs stayed resident.  --waves N: tuning "sift_pair_waves_per_cu" = N,
+    the descriptor kernel's fixed grid of N waves per CU instead of the default.
 python tools/classic_bench.py --leg match|match_slots [--selector NN|KNN] [--cross] [--calls 50]
     one matcher alone on the two resident ORB sets of the 1241 x 376 sample pair: spvo_match_hamming on the host copies (match_hamming_kernel<8>)
     or spvo_match_hamming_slots on the binary slots (match_hamming_tiled_kernel), for rocprofv3 --kernel-trace --stats as above.
@@ -73,9 +80,11 @@ ap.add_argument("--detectors", action="store_true")
 ap.add_argument("--resident", action="store_true")
 ap.add_argument("--brisk-resident", action="store_true")
 ap.add_argument("--akaze-resident", action="store_true")
+ap.add_argument("--sift-resident", action="store_true")
 ap.add_argument("--ab", type=int, default=0)
-ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "brisk_detect", "akaze_detect", "akaze_describe", "akaze_pair", "brisk_pair", "orb_describe", "fast_sift", "sift_describe", "match", "match_slots"])
+ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "brisk_detect", "akaze_detect", "akaze_describe", "akaze_pair", "brisk_pair", "orb_describe", "fast_sift", "gftt_sift", "sift_describe", "match", "match_slots"])
 ap.add_argument("--form", type=int, default=0, choices=[0, 1])
+ap.add_argument("--waves", type=int, default=0)
 ap.add_argument("--selector", default="KNN", choices=["NN", "KNN"])
 ap.add_argument("--cross", action="store_true")
 ap.add_argument("--yardstick", action="store_true")
@@ -102,12 +111,14 @@ if args.detectors or args.leg:
     def leg_sift():
         return ctx.sift_detect(img)["n"]
 
-    if args.leg in ("fast_sift", "sift_describe"):
+    if args.leg in ("fast_sift", "gftt_sift", "sift_describe"):
         capi.set_tuning("sift_describe_form", args.form)
+        if args.waves > 0:
+            capi.set_tuning("sift_pair_waves_per_cu", args.waves)
 
-    def fast_records(f):                               # KeyPoint(x, y, 7.f, -1, score), octave 0
+    def fast_records(f, size=7.0):                     # KeyPoint(x, y, 7.f, -1, score), octave 0 (Shi-Tomasi: size 5)
         rec = np.zeros(len(f["xy"]), capi.SIFT_KP_DTYPE)
-        rec["x"], rec["y"], rec["size"], rec["angle"], rec["response"] = f["xy"][:, 0], f["xy"][:, 1], 7.0, -1.0, f["response"]
+        rec["x"], rec["y"], rec["size"], rec["angle"], rec["response"] = f["xy"][:, 0], f["xy"][:, 1], size, -1.0, f["response"]
         return rec
 
     if args.leg == "sift_describe":
@@ -118,6 +129,15 @@ if args.detectors or args.leg:
 
     def leg_fast_sift():
         return len(ctx.sift_describe(None, fast_records(ctx.fast(img)), shape=img.shape))
+
+    def leg_gftt_sift():
+        return len(ctx.sift_describe(None, fast_records(ctx.gftt(img), 5.0), shape=img.shape))
+
+    def leg_sift_pair():                               # --sift-resident: both images in one call
+        k = pair_calls[0] % 4
+        pair_calls[0] += 1
+        fl, fr = ctx.classic_sift_pair(img, pair_r, 2 * k, 2 * k + 1, kind="FAST" if args.leg == "fast_sift" else "ShiTomasi")
+        return fl["n"] + fr["n"]
 
     if args.leg in ("brisk", "orb_describe"):
         kp = ctx.fast(img)["xy"]
@@ -174,7 +194,7 @@ if args.detectors or args.leg:
         fl, fr = ctx.akaze_detect_pair(img, pair_r, 2 * k, 2 * k + 1)
         return fl["n"] + fr["n"]
 
-    if args.leg in ("brisk_pair", "akaze_pair"):
+    if args.leg in ("brisk_pair", "akaze_pair", "fast_sift", "gftt_sift"):
         pair_r = np.ascontiguousarray(frames[0][1][:376, :1241])
 
     def leg_orb_describe():
@@ -203,8 +223,11 @@ if args.detectors or args.leg:
                 akaze_pair=("spvo_akaze_detect_pair (both images)", leg_akaze_pair),
                 sift_describe=("spvo_sift_describe, %d FAST keypoints, form %d" % (len(srec) if args.leg == "sift_describe" else 0, args.form), leg_sift_describe),
                 fast_sift=("spvo_fast_detect + spvo_sift_describe(NULL), form %d" % args.form, leg_fast_sift),
+                gftt_sift=("spvo_gftt_detect + spvo_sift_describe(NULL), form %d" % args.form, leg_gftt_sift),
                 orb=("spvo_orb_detect", leg_orb), sift=("spvo_sift_detect", leg_sift), gftt=("spvo_gftt_detect + spvo_orb_describe", leg_gftt), fast=("spvo_fast_detect + spvo_orb_describe", leg_fast))
-    keys = [args.leg] + (["sift"] if args.yardstick and args.leg != "fast_sift" else []) if args.leg else ["orb", "gftt", "fast"]
+    if args.sift_resident and args.leg in ("fast_sift", "gftt_sift"):
+        legs[args.leg] = ("spvo_classic_sift_pair (%s, both images)" % ("FAST" if args.leg == "fast_sift" else "ShiTomasi"), leg_sift_pair)
+    keys = [args.leg] + (["sift"] if args.yardstick and args.leg not in ("fast_sift", "gftt_sift") else []) if args.leg else ["orb", "gftt", "fast"]
     if args.leg == "akaze_describe":
         keys = ["akaze_describe", "akaze_brisk_null", "akaze_describe_img", "akaze_detect"]
     for key in keys:
@@ -224,13 +247,16 @@ if args.detectors or args.leg:
         print("%-40s %d x %d: median %.3f ms (p10 %.3f, p90 %.3f) over %d calls, %d described keypoints / matches%s" % (name, img.shape[1], img.shape[0], np.median(ts), np.percentile(ts, 10),
                                                                                                       np.percentile(ts, 90), args.calls, n, extra))
     ctx.close()
-    if args.leg == "fast_sift" and args.yardstick:     # the host class, ms per pair, in the same run
+    if args.leg in ("fast_sift", "gftt_sift") and args.yardstick:     # the host class, ms per pair, in the same run
         seq = [frames[i % 8] for i in range(args.frames)]
-        for det, des in (("FAST", "SIFT"), ("SIFT", "SIFT"), ("FAST", "BRISK")):
-            host.classic_sequence(seq[:3], P_l, P_r, "KNN", True, 2.0, 4, detector=det, descriptor=des)      # the one-off costs
-            p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5, detector=det, descriptor=des)
-            print("host class %s + %s %dx%d: %.3f ms per pair over %d pairs, keypoints %d, stereo matches %d, inliers %d" % (
-                det, des, frames[0][0].shape[1], frames[0][0].shape[0], 1e3 * sec / (len(seq) - 5), len(seq) - 5, np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3])))
+        own = "FAST" if args.leg == "fast_sift" else "ShiTomasi"
+        res = dict(resident=True, sift_describe_resident=True) if args.sift_resident else {}
+        for det, des in ((own, "SIFT"),) if args.sift_resident or own != "FAST" else (("FAST", "SIFT"), ("SIFT", "SIFT"), ("FAST", "BRISK")):
+            host.classic_sequence(seq[:3], P_l, P_r, "KNN", True, 2.0, 4, detector=det, descriptor=des, **res)      # the one-off costs
+            p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5, detector=det, descriptor=des, **res)
+            print("host class %s + %s %dx%d: %.3f ms per pair over %d pairs, keypoints %d, stereo matches %d, inliers %d, %d pairs resident" % (
+                det, des, frames[0][0].shape[1], frames[0][0].shape[0], 1e3 * sec / (len(seq) - 5), len(seq) - 5, np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3]),
+                host.classic_resident_pairs()))
     capi.set_tuning("sift_describe_form", 0)
 elif args.ab > 0:
     n = args.frames
@@ -240,7 +266,8 @@ elif args.ab > 0:
     host.classic_sequence(seq[:8], P_l, P_r, "KNN", True, 2.0, 4, detector=args.detector, descriptor=args.descriptor)      # the process's one-off costs
     for r in range(args.ab):
         for resident in (False, True):
-            p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5, detector=args.detector, resident=resident, descriptor=args.descriptor)
+            p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5, detector=args.detector, resident=resident, descriptor=args.descriptor,
+                                                sift_describe_resident=resident and args.sift_resident)
             ms[resident].append(1e3 * sec / (n - 5))
             print("%s %dx%d round %d resident=%d: %.3f ms per pair over %d pairs, %d pairs resident, keypoints %d, stereo matches %d, inliers %d" % (
                 name, frames[0][0].shape[1], frames[0][0].shape[0], r, resident, ms[resident][-1], n - 5, host.classic_resident_pairs(), np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3])))
@@ -252,5 +279,6 @@ else:
     n = args.frames
     seq = [frames[i % 8] for i in range(n)]
     p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5, detector=args.detector, resident=args.resident, descriptor=args.descriptor,
-                                        akaze_descriptor=args.descriptor == "AKAZE", **(dict(brisk_resident=True) if args.brisk_resident else {}), **(dict(akaze_resident=True) if args.akaze_resident else {}))
+                                        akaze_descriptor=args.descriptor == "AKAZE", **(dict(brisk_resident=True) if args.brisk_resident else {}), **(dict(akaze_resident=True) if args.akaze_resident else {}),
+                                        **(dict(sift_describe_resident=True) if args.sift_resident else {}))
     print("classic front end (%s%s) on the GPU: %.1f stereo frames/s (%.3f ms per pair), keypoints %d, stereo matches %d, inliers %d, %d pairs resident" % (args.detector + ("" if args.descriptor == "ORB" else " + " + args.descriptor), ", device-resident" if args.resident else "", (n - 5) / sec, 1e3 * sec / (n - 5), np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3]), host.classic_resident_pairs()))
