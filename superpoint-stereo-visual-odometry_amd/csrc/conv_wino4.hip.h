@@ -35,11 +35,17 @@
 //     waves of a SIMD do half a transform;
 //   * a wave's issue priority falls as it advances through an item (WINO4_PRIO below), so that the two waves of a SIMD reach the
 //     item's barrier together;
+//   * the matrix stream of an item waits only for the operand piece it is about to use: the operand reads (and the transform's three row
+//     reads) are issued by inline assembly and waited for by s_waitcnt lgkmcnt(N) with N counted at compile time (ITEM = 1, see
+//     WINO4_ITEM_LEAD below); the compiler's own placement drained the LDS queue six times per item.  Measured on one MI355X, same
+//     box, old item against new: conv1b 403 -> 390 us inside the benchmark, matrix stream 3425 -> 3317 cycles per item
+//     (profiles/wino4_item_*);
 //   * the inverse transform (36 -> 16 per output channel and tile) runs in registers, as before.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
+#include <utility>
 #include <vector>
 #include "conv_mfma.hip.h"
 
@@ -73,6 +79,20 @@
 #endif
 #ifndef WINO4_H2_STRIDE
 #define WINO4_H2_STRIDE 8
+#endif
+// The item with counted operand waits (template flag ITEM = 1, the default; 0 = the item as it was, for A/B runs and the bit-for-bit test:
+// spvo_set_tuning "wino4_item").  Same matrix instructions, same order, same operands.  What differs is how a wave waits for its operand
+// reads.  In the ITEM = 0 form the compiler places the waits, and because the transform steps (with LDS operations of their own) sit in
+// wave-uniform branches it falls back to s_waitcnt lgkmcnt(0) at the joins: six full drains per item, each of which also waits for the
+// reads issued one or two matrix instructions earlier, the very latency LEAD was meant to cover.  In the ITEM = 1 form the operand reads
+// are ds_read_b128 / ds_read_b64 in inline assembly, which the compiler's wait insertion does not see, and before the matrix instruction
+// that first uses a piece stands s_waitcnt lgkmcnt(N) with N = the number of operand reads issued, in program order, behind the later of the
+// two pieces it needs (wino4_wait_count below).  LDS operations return in order, so every LDS operation the transform adds in between
+// only makes the true number outstanding larger than N: the wait errs on the safe side.  The compiler's own waits (for the transform's
+// reads) count only what it tracks and are for the same reason never too loose.  The half-used B pieces (4 and 9: positions 16 and
+// 17) are read as 8 bytes, so that no read's destination overlaps an older read's; the role predicate is scalar arithmetic.
+#ifndef WINO4_ITEM_LEAD
+#define WINO4_ITEM_LEAD 6
 #endif
 #ifndef WINO4_ABL
 #define WINO4_ABL 0   // measurement builds only (tools/wino_bench.hip): 1 no input transform, 2 no filter staging, 4 no raw staging, 8 operands read once, 16 no stores
@@ -158,12 +178,37 @@ __device__ __forceinline__ void wino4_out4(const wino4_f32x2 m0, const wino4_f32
   y[3] = __builtin_elementwise_fma(wino4_f32x2{8.f, 8.f}, d, b) + m5;
 }
 
-template <bool POOL, bool RELU, int TAG = 0, int TB = 2>
+// ---- operand reads of an item in program order (ITEM = 1): the matrix instructions run p = 0 .. 35; slot q holds the read of A piece q / 4
+// when q % 4 == 0, then the read of B piece wino4_b_piece(q) when q is that piece's first position.  Slots 0 .. LEAD - 1 are issued in
+// front of the item, slot p + LEAD behind matrix instruction p.
+constexpr int wino4_b_piece(int p) { return 5 * (p / 18) + ((p % 18) >> 2); }
+constexpr bool wino4_slot_reads_a(int q) { return (q & 3) == 0; }
+constexpr bool wino4_slot_reads_b(int q) { return q == 0 || wino4_b_piece(q) != wino4_b_piece(q - 1); }
+constexpr int wino4_reads_before(int q_end) {   // reads in slots 0 .. q_end - 1
+  int n = 0;
+  for (int q = 0; q < q_end && q < 36; ++q) n += (wino4_slot_reads_a(q) ? 1 : 0) + (wino4_slot_reads_b(q) ? 1 : 0);
+  return n;
+}
+constexpr int wino4_first_slot_b(int piece) { return 18 * (piece / 5) + 4 * (piece % 5); }
+// operand reads that may still be in flight when matrix instruction p starts: those issued behind the later of its two pieces
+constexpr int wino4_wait_count(int p, int lead) {
+  const int issued = wino4_reads_before(p + lead);
+  const int qa = p & ~3, qb = wino4_first_slot_b(wino4_b_piece(p));
+  const int ia = wino4_reads_before(qa);                                          // index of the A piece's read
+  const int ib = wino4_reads_before(qb) + (wino4_slot_reads_a(qb) ? 1 : 0);       // index of the B piece's read (behind the slot's A read)
+  const int n = issued - 1 - (ia > ib ? ia : ib);
+  return n < 0 ? 0 : (n > 15 ? 15 : n);                                           // lgkmcnt is a 4-bit field
+}
+template <class F, int... P>
+__device__ __forceinline__ void wino4_for_each(F &&f, std::integer_sequence<int, P...>) { (f(std::integral_constant<int, P>{}), ...); }
+
+template <bool POOL, bool RELU, int TAG = 0, int TB = 2, bool ITEM = true>
 __global__ __launch_bounds__(256 * TB, TB) void conv_wino4_kernel(const ConvArgs a) {
   using T = Wino4TileT<TB>;
   constexpr int CK = T::CK, LW = T::LW, LH = T::LH, LW4 = LW / 4, NTH = T::NTH;
   constexpr int IN_V4 = T::IN_FLOATS / 4;        // 720 (400) 16-byte pieces per raw tile
   constexpr int U_V4 = T::U_FLOATS / 4;          // 2304 per filter slab
+  constexpr bool NEW_ITEM = ITEM && !(WINO4_ABL & 8);   // (the read-once ablation exists in the earlier item only)
   constexpr int NIT_U = (U_V4 + NTH - 1) / NTH;  // 5, the last one by threads 0..255 (9, all full)
   typedef float f32x2 __attribute__((ext_vector_type(2)));
   typedef float f32x4v __attribute__((ext_vector_type(4)));
@@ -235,6 +280,7 @@ __global__ __launch_bounds__(256 * TB, TB) void conv_wino4_kernel(const ConvArgs
   float xr[3][6];        // rows after the row pass; xr[r][0..2] stay, xr[r][3..5] are swapped with the partner's
   f32x4v xa[3];
   float xs0[3], xs1[3];
+  f32x2 xs2[3];          // (ITEM = 1, inside an item: xs0 and xs1 of a row as they come from one ds_read2_b32)
   auto xf_step = [&](const float *raw, float *vb, int st) {
     if (st < 3) {
       const float *d = raw + raw_off + st * LW;
@@ -363,7 +409,8 @@ __global__ __launch_bounds__(256 * TB, TB) void conv_wino4_kernel(const ConvArgs
       constexpr bool FIRST = decltype(first_tag)::value;   // the tile's first chunk: C = 0 in every accumulator's (only) instruction
       // group k & 1 (waves 0-3 / 4-7) does the first half of item k + 2's transform, the other group the second half of item k + 1's
       // (wave-uniform: a scalar branch per step)
-      const bool XF = __builtin_amdgcn_readfirstlane((wave >> TB) == (k & 1) ? 1 : 0) != 0;
+      // (ITEM = 1: from the two scalars, so that the per-step branches are s_cmp / s_cbranch_scc without vector instructions)
+      const bool XF = NEW_ITEM ? (((wave >> TB) ^ k) & 1) == 0 : __builtin_amdgcn_readfirstlane((wave >> TB) == (k & 1) ? 1 : 0) != 0;
 #ifdef WINO_STAMPS
       const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -391,52 +438,128 @@ __global__ __launch_bounds__(256 * TB, TB) void conv_wino4_kernel(const ConvArgs
       const f32x4v *vb4 = reinterpret_cast<const f32x4v *>(vb) + b_lane;
       // 36 matrix instructions in the order p' = 18 h + q (q = 3 i + c; position 6 i + 3 h + c); operands: A piece p' / 4 (9 reads),
       // B piece 5 h + q / 4 (10 reads), each read LEAD instructions before its first use
-      constexpr int LEAD = WINO4_LEAD;
-      f32x4v av[9], bv[10];
-      auto b_piece = [](int p) { return 5 * (p / 18) + ((p % 18) >> 2); };
+      if constexpr (NEW_ITEM) {
+        // operand reads the compiler does not track + counted waits (see WINO4_ITEM_LEAD above); B pieces 4 and 9 as 8 bytes in bh[h]
+        constexpr int LEAD = WINO4_ITEM_LEAD;
+        static_assert(LEAD >= 1 && LEAD <= 36, "WINO4_ITEM_LEAD");
+        static_assert(WINO4_PRIO <= 1, "the other priority schedules exist in the ITEM = 0 form only");
+        f32x4v av[9], bv[10];
+        f32x2 bh[2];
+        static_assert(WINO4_H1_STEPS >= 6, "the row reads and the row pass that waits for them run in one item");
+        // the role as a scalar, compared afresh at every step: s_cmp + s_cbranch_scc, no lane mask kept in a register pair and no vector
+        // instructions (the empty asm keeps the compiler from merging the comparisons into such a mask)
+        const int xf_s = ((wave >> TB) ^ k ^ 1) & 1;
+        auto is_xf = [xf_s]() __attribute__((always_inline)) { int t = xf_s; asm volatile("" : "+s"(t)); return t != 0; };
+        const unsigned ra = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)(raw_next2 + raw_off);
+        const unsigned ua = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)ub4;
+        const unsigned va = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)vb4;
+        auto read_slot = [&av, &bv, &bh, ua, va](auto qc) __attribute__((always_inline)) {
+          constexpr int q = decltype(qc)::value;
+          if constexpr (q < 36 && wino4_slot_reads_a(q)) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(av[q >> 2]) : "v"(ua), "n"((q >> 2) * 256 * 16));
+          constexpr int j = wino4_b_piece(q < 36 ? q : 35);
+          if constexpr (q < 36 && wino4_slot_reads_b(q) && j % 5 == 4) asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(bh[j / 5]) : "v"(va), "n"(j * 64 * TB * 16));
+          if constexpr (q < 36 && wino4_slot_reads_b(q) && j % 5 != 4) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bv[j]) : "v"(va), "n"(j * 64 * TB * 16));
+        };
+        auto step = [&](auto pc) __attribute__((always_inline)) {
+          constexpr int p = decltype(pc)::value;
+          constexpr int ph = p / 18, pq = p % 18, pos = 6 * (pq / 3) + 3 * ph + pq % 3, bj = wino4_b_piece(p);
+          constexpr bool half = bj % 5 == 4;
+          // the first use of a piece: wait for it (the asm's operands tie the wait between the reads and the matrix instruction)
+          if constexpr (wino4_slot_reads_a(p) || wino4_slot_reads_b(p)) {
+            if constexpr (half) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(av[p >> 2]), "+v"(bh[bj / 5]) : "n"(wino4_wait_count(p, LEAD)));
+            else asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(av[p >> 2]), "+v"(bv[bj]) : "n"(wino4_wait_count(p, LEAD)));
+          }
+          const float a_op = av[p >> 2][p & 3];
+          float b_op;
+          if constexpr (half) b_op = bh[bj / 5][pq & 3];
+          else b_op = bv[bj][pq & 3];
+#if WINO4_PRIO
+          if constexpr (p == 0) asm volatile("s_setprio 3");
+          if constexpr (p == 9) asm volatile("s_setprio 2");
+          if constexpr (p == 18) asm volatile("s_setprio 1");
+          if constexpr (p == 27) asm volatile("s_setprio 0");
+#endif
+          if (FIRST) acc[pos] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_op, b_op, f32x4v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+          else acc[pos] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_op, b_op, acc[pos], 0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);
+          if (!(WINO4_ABL & 2) && p == 1 && cu.id < n_tiles) issue_u(cu.t, cu.chunk, u_next);
+          if (!(WINO4_ABL & 4) && p == 4 && cr.id < n_tiles) issue_raw(cr.t, cr.chunk, raw_next3);
+          read_slot(std::integral_constant<int, p + LEAD>{});
+          // the transform: H1 of item k + 2 (its three row reads the same way: issued untracked in steps 0..2, waited for by count in front
+          // of the row pass of steps 3..5) or H2 of item k + 1
+          if constexpr (!(WINO4_ABL & 1) && p >= WINO4_H1_START && p < WINO4_H1_START + WINO4_H1_STEPS * WINO4_H1_STRIDE && (p - WINO4_H1_START) % WINO4_H1_STRIDE == 0) {
+            constexpr int st = (p - WINO4_H1_START) / WINO4_H1_STRIDE;
+            if (is_xf()) {
+              if constexpr (st < 3) {
+                asm volatile("ds_read2_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(xs2[st]) : "v"(ra), "n"(st * LW), "n"(st * LW + 5));
+                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xa[st]) : "v"(ra), "n"((st * LW + 1) * 4));
+              } else {
+                if constexpr (st < 6) {
+                  // behind row st - 3's reads: the operand reads of the slots up to this one's, and two reads per later row
+                  constexpr int p_rd = p - 3 * WINO4_H1_STRIDE;
+                  constexpr int n = wino4_reads_before(p + LEAD + 1) - wino4_reads_before(p_rd + LEAD + 1) + 2 * (5 - st);
+                  asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(xs2[st - 3]), "+v"(xa[st - 3]) : "n"(n > 15 ? 15 : n));
+                  xs0[st - 3] = xs2[st - 3][0];
+                  xs1[st - 3] = xs2[st - 3][1];
+                }
+                xf_step(raw_next2, v_next, st);
+              }
+            }
+          }
+          if constexpr (!(WINO4_ABL & 1) && p >= WINO4_H2_START && p < WINO4_H2_START + (10 - WINO4_H1_STEPS) * WINO4_H2_STRIDE && (p - WINO4_H2_START) % WINO4_H2_STRIDE == 0)
+            if (!is_xf()) xf_step(raw_next2, v_next, WINO4_H1_STEPS + (p - WINO4_H2_START) / WINO4_H2_STRIDE);
+          __builtin_amdgcn_sched_barrier(0);
+        };
+        wino4_for_each(read_slot, std::make_integer_sequence<int, LEAD>{});
+        wino4_for_each(step, std::make_integer_sequence<int, 36>{});
+      } else {
+        constexpr int LEAD = WINO4_LEAD;
+        f32x4v av[9], bv[10];
+        auto b_piece = [](int p) { return 5 * (p / 18) + ((p % 18) >> 2); };
 #pragma unroll
-      for (int p = 0; p < ((WINO4_ABL & 8) ? 36 : LEAD); ++p) {
-        if ((WINO4_ABL & 8) && k > 0) break;
-        if ((p & 3) == 0) av[p >> 2] = ub4[(p >> 2) * 256];
-        if (p == 0 || b_piece(p) != b_piece(p - 1)) bv[b_piece(p)] = vb4[b_piece(p) * (64 * TB)];
-      }
+        for (int p = 0; p < ((WINO4_ABL & 8) ? 36 : LEAD); ++p) {
+          if ((WINO4_ABL & 8) && k > 0) break;
+          if ((p & 3) == 0) av[p >> 2] = ub4[(p >> 2) * 256];
+          if (p == 0 || b_piece(p) != b_piece(p - 1)) bv[b_piece(p)] = vb4[b_piece(p) * (64 * TB)];
+        }
 #pragma unroll
-      for (int p = 0; p < 36; ++p) {
-        const int ph = p / 18, pq = p % 18, pos = 6 * (pq / 3) + 3 * ph + pq % 3;
-        const float a_op = av[p >> 2][p & 3], b_op = bv[b_piece(p)][pq & 3];
+        for (int p = 0; p < 36; ++p) {
+          const int ph = p / 18, pq = p % 18, pos = 6 * (pq / 3) + 3 * ph + pq % 3;
+          const float a_op = av[p >> 2][p & 3], b_op = bv[b_piece(p)][pq & 3];
 #if WINO4_PRIO
 #if WINO4_PRIO == 1
-        if (p == 0) asm volatile("s_setprio 3");
-        if (p == 9) asm volatile("s_setprio 2");
-        if (p == 18) asm volatile("s_setprio 1");
-        if (p == 27) asm volatile("s_setprio 0");
+          if (p == 0) asm volatile("s_setprio 3");
+          if (p == 9) asm volatile("s_setprio 2");
+          if (p == 18) asm volatile("s_setprio 1");
+          if (p == 27) asm volatile("s_setprio 0");
 #elif WINO4_PRIO == 2   // the younger wave of a SIMD (tb = 1) keeps each level longer
-        if (p == 0) asm volatile("s_setprio 3");
-        if (tb == 0) { if (p == 6) asm volatile("s_setprio 2"); if (p == 15) asm volatile("s_setprio 1"); if (p == 24) asm volatile("s_setprio 0"); }
-        else { if (p == 12) asm volatile("s_setprio 2"); if (p == 24) asm volatile("s_setprio 1"); }
+          if (p == 0) asm volatile("s_setprio 3");
+          if (tb == 0) { if (p == 6) asm volatile("s_setprio 2"); if (p == 15) asm volatile("s_setprio 1"); if (p == 24) asm volatile("s_setprio 0"); }
+          else { if (p == 12) asm volatile("s_setprio 2"); if (p == 24) asm volatile("s_setprio 1"); }
 #elif WINO4_PRIO == 3   // two levels only: high in the first half of the item
-        if (p == 0) asm volatile("s_setprio 1");
-        if (p == 18) asm volatile("s_setprio 0");
+          if (p == 0) asm volatile("s_setprio 1");
+          if (p == 18) asm volatile("s_setprio 0");
 #elif WINO4_PRIO == 4   // older wave one level below the younger one throughout, both falling
-        if (tb == 0) { if (p == 0) asm volatile("s_setprio 2"); if (p == 12) asm volatile("s_setprio 1"); if (p == 24) asm volatile("s_setprio 0"); }
-        else { if (p == 0) asm volatile("s_setprio 3"); if (p == 12) asm volatile("s_setprio 2"); if (p == 24) asm volatile("s_setprio 1"); }
+          if (tb == 0) { if (p == 0) asm volatile("s_setprio 2"); if (p == 12) asm volatile("s_setprio 1"); if (p == 24) asm volatile("s_setprio 0"); }
+          else { if (p == 0) asm volatile("s_setprio 3"); if (p == 12) asm volatile("s_setprio 2"); if (p == 24) asm volatile("s_setprio 1"); }
 #endif
 #endif
-        if (FIRST) acc[pos] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_op, b_op, f32x4v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-        else acc[pos] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_op, b_op, acc[pos], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (!(WINO4_ABL & 2) && p == 1 && cu.id < n_tiles) issue_u(cu.t, cu.chunk, u_next);
-        if (!(WINO4_ABL & 4) && p == 4 && cr.id < n_tiles) issue_raw(cr.t, cr.chunk, raw_next3);
-        const int q = p + LEAD;
-        if (!(WINO4_ABL & 8) && q < 36) {
-          if ((q & 3) == 0) av[q >> 2] = ub4[(q >> 2) * 256];
-          if (b_piece(q) != b_piece(q - 1)) bv[b_piece(q)] = vb4[b_piece(q) * (64 * TB)];
+          if (FIRST) acc[pos] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_op, b_op, f32x4v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+          else acc[pos] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_op, b_op, acc[pos], 0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);
+          if (!(WINO4_ABL & 2) && p == 1 && cu.id < n_tiles) issue_u(cu.t, cu.chunk, u_next);
+          if (!(WINO4_ABL & 4) && p == 4 && cr.id < n_tiles) issue_raw(cr.t, cr.chunk, raw_next3);
+          const int q = p + LEAD;
+          if (!(WINO4_ABL & 8) && q < 36) {
+            if ((q & 3) == 0) av[q >> 2] = ub4[(q >> 2) * 256];
+            if (b_piece(q) != b_piece(q - 1)) bv[b_piece(q)] = vb4[b_piece(q) * (64 * TB)];
+          }
+          if (!(WINO4_ABL & 1) && XF && p >= WINO4_H1_START && p < WINO4_H1_START + WINO4_H1_STEPS * WINO4_H1_STRIDE && (p - WINO4_H1_START) % WINO4_H1_STRIDE == 0)
+            xf_step(raw_next2, v_next, (p - WINO4_H1_START) / WINO4_H1_STRIDE);                          // H1 of item k + 2
+          if (!(WINO4_ABL & 1) && !XF && p >= WINO4_H2_START && p < WINO4_H2_START + (10 - WINO4_H1_STEPS) * WINO4_H2_STRIDE && (p - WINO4_H2_START) % WINO4_H2_STRIDE == 0)
+            xf_step(raw_next2, v_next, WINO4_H1_STEPS + (p - WINO4_H2_START) / WINO4_H2_STRIDE);        // H2 of item k + 1 (registers of this wave's H1 in the item before)
+          __builtin_amdgcn_sched_barrier(0);
         }
-        if (!(WINO4_ABL & 1) && XF && p >= WINO4_H1_START && p < WINO4_H1_START + WINO4_H1_STEPS * WINO4_H1_STRIDE && (p - WINO4_H1_START) % WINO4_H1_STRIDE == 0)
-          xf_step(raw_next2, v_next, (p - WINO4_H1_START) / WINO4_H1_STRIDE);                          // H1 of item k + 2
-        if (!(WINO4_ABL & 1) && !XF && p >= WINO4_H2_START && p < WINO4_H2_START + (10 - WINO4_H1_STEPS) * WINO4_H2_STRIDE && (p - WINO4_H2_START) % WINO4_H2_STRIDE == 0)
-          xf_step(raw_next2, v_next, WINO4_H1_STEPS + (p - WINO4_H2_START) / WINO4_H2_STRIDE);        // H2 of item k + 1 (registers of this wave's H1 in the item before)
-        __builtin_amdgcn_sched_barrier(0);
       }
       advance(cu);
       advance(cr);

@@ -39,7 +39,7 @@ int stage_id(spvo_ctx *c, const std::string &name) {
 
 // ---- diagnostic switches (include/spvo.h: spvo_set_tuning).  One process-wide table, filled by explicit calls only.
 namespace {
-const char *const kTuningNames[] = {"winograd", "wino4", "wino_narrow", "wino_dynamic", "winograd_min_tiles", "wino4_min_tiles", "merge_siblings", "heads_fused",
+const char *const kTuningNames[] = {"winograd", "wino4", "wino4_item", "wino_narrow", "wino_dynamic", "winograd_min_tiles", "wino4_min_tiles", "merge_siblings", "heads_fused",
                                     "heads_on_net", "heads_split", "match_fused", "fp32_split", "prematch", "spin_wait", "trunk_timing", "solve_timing", "nms_first", "upload_side", "inject_launch_failure", "int8_fused", "pair_always", "preprocess_fused", "heads_keep_raw", "tail_streams", "solve_collect_first", "graphs", "solve_fuse", "solve_keep", "sift_describe_form", "sift_pair_waves_per_cu"};
 constexpr int kTuningCount = sizeof kTuningNames / sizeof kTuningNames[0];
 std::mutex g_tuning_mutex;
@@ -864,7 +864,7 @@ int spvo_load_weights(spvo_ctx *c, const char *path) {
       // CUs): F(4x4,3x3) (conv_wino4.hip.h: 36 multiplies per 4x4 outputs instead of F(2x2)'s 64) where the layer has that many
       // 16 x 32 tiles; else F(2x2,3x3) (conv_wino2.hip.h) on 8 x 32 tiles of 64 output channels; else its narrow form (32 output
       // channels per workgroup: conv4a / conv4b at 45x147 are 120 wide tiles on 256 CUs); else the direct kernel.
-      // Diagnostic switches (spvo_set_tuning): "winograd" = 0 direct kernels only, "wino4" = 0 F(2x2) only, "wino_narrow" = 0,
+      // Diagnostic switches (spvo_set_tuning): "winograd" = 0 direct kernels only, "wino4" = 0 F(2x2) only, "wino4_item" = 0 the F(4x4) item without counted operand waits, "wino_narrow" = 0,
       // "winograd_min_tiles" / "wino4_min_tiles" the thresholds, "wino_dynamic" = 0 static tile assignment.
       {
         const bool wino_on = tuning("winograd", 1) != 0;
@@ -881,6 +881,7 @@ int spvo_load_weights(spvo_ctx *c, const char *path) {
         const long t4 = (long)((ti.W + Wino4Tile::TW - 1) / Wino4Tile::TW) * ((ti.H + Wino4Tile::TH - 1) / Wino4Tile::TH) * op.co_tiles * c->cfg.max_batch;
         if (t4 >= tuning("wino4_min_tiles", 3 * c->num_cus / 4)) {
           op.wino4 = true;
+          op.wino4_item = tuning("wino4_item", 1) != 0;   // 0: the item with the compiler's operand waits (conv_wino4.hip.h), for A/B runs
           op.ck = Wino4Tile::CK;
           op.n_chunks = op.cin / Wino4Tile::CK;
           const std::vector<float> pk = pack_conv_weights_wino4(w, b, op.cout, op.cin);

@@ -92,11 +92,12 @@ int launch_conv_wino_sel(spvo_ctx *c, const ConvArgs &args, bool relu, bool pool
 }
 
 // conv_wino4.hip.h: Winograd F(4x4,3x3), 16 x 32 output tiles, 8 waves, one workgroup per CU
-template <bool POOL, bool RELU, int TAG>
+// (ITEM: the item with counted operand waits, or the earlier one -- spvo_set_tuning "wino4_item", read when the engine is loaded)
+template <bool POOL, bool RELU, int TAG, bool ITEM>
 int launch_conv_wino4_instance(spvo_ctx *c, const ConvArgs &args, hipStream_t stream) {
   static bool ready[64] = {};
   const int dev = c->cfg.device & 63;
-  auto k = conv_wino4_kernel<POOL, RELU, TAG>;
+  auto k = conv_wino4_kernel<POOL, RELU, TAG, 2, ITEM>;
   if (!ready[dev]) {
     HIP_TRY(c, hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, Wino4Tile::LDS_BYTES));
     ready[dev] = true;
@@ -111,15 +112,20 @@ int launch_conv_wino4_instance(spvo_ctx *c, const ConvArgs &args, hipStream_t st
   return SPVO_OK;
 }
 
-int launch_conv_wino4(spvo_ctx *c, const ConvArgs &a, int batch, bool relu, bool pool, bool dominant, hipStream_t stream) {
+template <bool ITEM>
+int launch_conv_wino4_sel(spvo_ctx *c, const ConvArgs &args, bool relu, bool pool, bool dominant, hipStream_t stream) {
+  if (dominant && relu) return pool ? launch_conv_wino4_instance<true, true, 1, ITEM>(c, args, stream) : launch_conv_wino4_instance<false, true, 1, ITEM>(c, args, stream);
+  if (pool) return relu ? launch_conv_wino4_instance<true, true, 0, ITEM>(c, args, stream) : launch_conv_wino4_instance<true, false, 0, ITEM>(c, args, stream);
+  return relu ? launch_conv_wino4_instance<false, true, 0, ITEM>(c, args, stream) : launch_conv_wino4_instance<false, false, 0, ITEM>(c, args, stream);
+}
+
+int launch_conv_wino4(spvo_ctx *c, const ConvArgs &a, int batch, bool relu, bool pool, bool dominant, bool new_item, hipStream_t stream) {
   ConvArgs args = a;
   args.tiles_x = (a.W + Wino4Tile::TW - 1) / Wino4Tile::TW;
   args.tiles_y = (a.H + Wino4Tile::TH - 1) / Wino4Tile::TH;
   args.batch = batch;
   if (pool && ((a.H | a.W) & 1)) return fail(c, SPVO_ERR_INVALID, "F(4x4) kernel: pooled layer with odd size");   // (the plan loader keeps those on the other kernels)
-  if (dominant && relu) return pool ? launch_conv_wino4_instance<true, true, 1>(c, args, stream) : launch_conv_wino4_instance<false, true, 1>(c, args, stream);
-  if (pool) return relu ? launch_conv_wino4_instance<true, true, 0>(c, args, stream) : launch_conv_wino4_instance<true, false, 0>(c, args, stream);
-  return relu ? launch_conv_wino4_instance<false, true, 0>(c, args, stream) : launch_conv_wino4_instance<false, false, 0>(c, args, stream);
+  return new_item ? launch_conv_wino4_sel<true>(c, args, relu, pool, dominant, stream) : launch_conv_wino4_sel<false>(c, args, relu, pool, dominant, stream);
 }
 
 int launch_conv_wino(spvo_ctx *c, const ConvArgs &a, int batch, bool relu, bool pool, bool dominant, bool narrow, hipStream_t stream) {
@@ -170,7 +176,7 @@ int launch_conv(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t stre
   a.tiles_x = a.tiles_y = 0;
   a.batch = batch;
   a.sched = op.d_sched;
-  if (op.wino4) return launch_conv_wino4(c, a, batch, relu, pool, op.dominant, stream);
+  if (op.wino4) return launch_conv_wino4(c, a, batch, relu, pool, op.dominant, op.wino4_item, stream);
   if (op.wino) return launch_conv_wino(c, a, batch, relu, pool, op.dominant, op.wino_narrow, stream);
   const int key = op.ks * 10000 + op.ck * 100 + op.wr * 20 + op.wc * 2 + (pool ? 1 : 0);   // ks, ck, wr, wc, pool
   if (epi) {

@@ -16,7 +16,10 @@
 #ifndef WINO4_TB
 #define WINO4_TB 2   // -DWINO4_TB=1: the 4-wave form (8 x 32 outputs per workgroup)
 #endif
-#define KERNEL(P, R, T, O) conv_wino4_kernel<P, R, T, WINO4_TB>
+#ifndef WINO4_ITEM
+#define WINO4_ITEM 1   // -DWINO4_ITEM=0: the item with the compiler's operand waits (the library's "wino4_item" switch)
+#endif
+#define KERNEL(P, R, T, O) conv_wino4_kernel<P, R, T, WINO4_TB, WINO4_ITEM != 0>
 #define PACK pack_conv_weights_wino4
 #define THREADS (256 * WINO4_TB)
 #define COT 64
@@ -122,6 +125,32 @@ int main(int argc, char **argv) {
   float ms;
   CK(hipEventElapsedTime(&ms, e0, e1));
   const double us = ms * 1e3 / reps, fl = 2.0 * batch * H * W * (double)cout * cin * 9;
+#if defined(WINO4)
+  // WINO_ITEM_AB=<rounds>: both items of the F(4x4) kernel in ONE process, alternately, `reps` launches per block: the same-box, same-clock
+  // comparison (separate processes differ by ~1 % among themselves)
+  if (getenv("WINO_ITEM_AB")) {
+    auto launch_item = [&](bool item) {
+#define WINO_AB_LAUNCH(P) do { if (item) hipLaunchKernelGGL((conv_wino4_kernel<P, true, 0, WINO4_TB, true>), dim3(grid), dim3(THREADS), LDSB, 0, a); \
+                               else hipLaunchKernelGGL((conv_wino4_kernel<P, true, 0, WINO4_TB, false>), dim3(grid), dim3(THREADS), LDSB, 0, a); } while (0)
+      if (pool) WINO_AB_LAUNCH(true); else WINO_AB_LAUNCH(false);
+#undef WINO_AB_LAUNCH
+    };
+    CK(hipFuncSetAttribute((const void *)conv_wino4_kernel<true, true, 0, WINO4_TB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
+    CK(hipFuncSetAttribute((const void *)conv_wino4_kernel<true, true, 0, WINO4_TB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
+    CK(hipFuncSetAttribute((const void *)conv_wino4_kernel<false, true, 0, WINO4_TB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
+    CK(hipFuncSetAttribute((const void *)conv_wino4_kernel<false, true, 0, WINO4_TB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
+    for (int r = 0; r < atoi(getenv("WINO_ITEM_AB")); ++r)
+      for (int item = 0; item < 2; ++item) {
+        launch_item(item != 0);
+        CK(hipEventRecord(e0));
+        for (int i = 0; i < reps; ++i) launch_item(item != 0);
+        CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
+        float ab_ms;
+        CK(hipEventElapsedTime(&ab_ms, e0, e1));
+        printf("  block %d item %d: %8.2f us\n", r, item, ab_ms * 1e3 / reps);
+      }
+  }
+#endif
 #ifdef WINO_STAMPS
   {
     unsigned long long *d_st;
