@@ -273,6 +273,31 @@ int spvo_fast_detect(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, size
 int spvo_orb_describe(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, size_t stride, const float *xy /* [n][2] */, int n,
                       int32_t *kept /* [n] */, float *angle /* [n] rad, may be NULL */, uint8_t *desc /* [n][32] */, int *n_kept);
 
+/* The same extractor on keypoints that carry an octave (cv::ORB::create()->compute on BRISK or AKAZE keypoints: KeyPoint::octave names
+ * the pyramid level, scale 1.2^octave) at any coordinates.  OpenCV is not available to this build: the rule is OpenCV's as far as it is
+ * known, as restated by tests/orb_octaves_ref.py (its header lists every choice), and the kernels reproduce that restatement bit for
+ * bit.  The levels are spvo_orb_detect's (same scales, sizes and resize), built up to the largest octave named; of them only those that
+ * hold a kept keypoint are smoothed.  The 31-pixel border rule is applied at LEVEL 0 to the coordinates rounded half to even; the kept
+ * keypoints are grouped by octave, ascending, stable within an octave: `kept` receives the indices into xy in output order (ascending
+ * only if the list was sorted by octave), `n_kept` their number, row i of `desc` / `angle` belongs to keypoint kept[i].  On its level a
+ * keypoint lies at rint((x, y) / scale), clamped into the level; direction (always recomputed) and the 256 tests are spvo_orb_detect's
+ * arithmetic on the same tables.  From level 3 on a kept keypoint can lie closer to its level's border than the patch reaches (15
+ * pixels for the direction, at most 19 for a test point): the level and the smoothed level are then read at BORDER_REFLECT_101 indices
+ * (OpenCV reflects the unsmoothed level into a padded border and smooths that: a documented deviation, like the test-pair table).  A
+ * keypoint that spvo_orb_detect reports on any level, fed back with its x, y and octave, gets the same 32 bytes and the same direction;
+ * a list at octave 0 with integer coordinates gets spvo_orb_describe's output.
+ *   img == NULL   the u8 image left resident by this context's last spvo_gftt_detect / spvo_fast_detect / spvo_brisk_detect /
+ *                 spvo_akaze_detect / spvo_*_describe (spvo_brisk_describe's rule); it stays resident
+ *   img != NULL   img is uploaded first and stays resident
+ * n == 0 is SPVO_OK with n_kept = 0.  Refusals are decided before anything on the device or in the outputs is touched:
+ *   SPVO_ERR_INVALID   an octave outside 0..7, a coordinate that is not finite, n < 0, a named octave whose level is smaller than 32
+ *                      pixels in either dimension (with that minimum one reflection always suffices)
+ *   SPVO_ERR_STATE     a spvo_detect*_submit is in flight; img == NULL and no image of that shape is resident */
+int spvo_orb_describe_octaves(spvo_ctx *ctx, const uint8_t *img /* or NULL */, int rows, int cols, size_t stride,
+                              const float *xy /* [n][2] */, const int32_t *octave /* [n] */, int n,
+                              int32_t *kept /* [n] */, float *angle /* [n] rad, may be NULL */,
+                              uint8_t *desc /* [n][32] */, int *n_kept);
+
 /* describeKeypoints for DescriptorType::BRISK (cv::BRISK::create(30, 3, 1.0f)->compute, feature_detection_classic.cpp:56-65, 110-111) on
  * keypoints at any position and size: per keypoint the scale index from `size`, the border rule of that scale (dropped keypoints leave
  * the list, order-preserving: `kept` receives the surviving indices into xy, ascending, `n_kept` their number), the direction from

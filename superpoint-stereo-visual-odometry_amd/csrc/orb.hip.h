@@ -210,4 +210,67 @@ __global__ __launch_bounds__(256) void orb_describe_kernel(const OrbLevels lv, c
   }
 }
 
+// ---- the extractor on GIVEN keypoints that carry an octave (spvo_orb_describe_octaves; tests/orb_octaves_ref.py is the definition)
+constexpr int ORB_REACH = 19;       // the farthest a read lies from the keypoint: 15 for the disc, 13 sqrt 2 rounded for a test point (the pattern is clipped to +-13)
+constexpr int ORB_MIN_LEVEL = 32;   // the smallest level the call accepts: one reflection always lands inside
+
+// BORDER_REFLECT_101 index into 0 .. n - 1 (n >= ORB_MIN_LEVEL, the overshoot at most ORB_REACH); the clamp keeps whatever index inside
+__device__ __forceinline__ int orb_reflect101(int i, int n) {
+  i = i < 0 ? -i : i;
+  i = i >= n ? 2 * (n - 1) - i : i;
+  return min(max(i, 0), n - 1);
+}
+
+// orb_describe_kernel's arithmetic for one keypoint, one wave: REFLECT = false is its instruction stream (every read lies inside the
+// level), REFLECT = true reads the level and the smoothed level at reflected indices
+template <bool REFLECT>
+__device__ __forceinline__ void orb_describe_given_one(const uint8_t *__restrict__ im, const uint8_t *__restrict__ blur, int h, int w, int cx, int cy, int lane,
+                                                       const signed char *__restrict__ disc, const float *__restrict__ pattern, float *__restrict__ angle, uint8_t *__restrict__ desc) {
+  auto at = [&](const uint8_t *p, int x, int y) -> int {
+    if (REFLECT) { x = orb_reflect101(x, w); y = orb_reflect101(y, h); }
+    return p[(size_t)y * w + x];
+  };
+  int m10 = 0, m01 = 0;
+  for (int p = lane; p < ORB_DISC; p += 64) {
+    const int dx = disc[2 * p], dy = disc[2 * p + 1];
+    const int v = at(im, cx + dx, cy + dy);
+    m10 += dx * v;
+    m01 += dy * v;
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) { m10 += __shfl_xor(m10, o); m01 += __shfl_xor(m01, o); }
+  const float fx = (float)m10, fy = (float)m01;
+  const float nrm = __fsqrt_rn(add_rn(mul_rn(fx, fx), mul_rn(fy, fy)));
+  const float ca = nrm > 0.f ? __fdiv_rn(fx, nrm) : 1.f, sa = nrm > 0.f ? __fdiv_rn(fy, nrm) : 0.f;
+  unsigned bits = 0;   // tests 4 lane .. 4 lane + 3
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float4 pt = reinterpret_cast<const float4 *>(pattern)[4 * lane + j];
+    const int x1 = cx + (int)floorf(add_rn(add_rn(mul_rn(pt.x, ca), -mul_rn(pt.y, sa)), 0.5f)), y1 = cy + (int)floorf(add_rn(add_rn(mul_rn(pt.x, sa), mul_rn(pt.y, ca)), 0.5f));
+    const int x2 = cx + (int)floorf(add_rn(add_rn(mul_rn(pt.z, ca), -mul_rn(pt.w, sa)), 0.5f)), y2 = cy + (int)floorf(add_rn(add_rn(mul_rn(pt.z, sa), mul_rn(pt.w, ca)), 0.5f));
+    bits |= (at(blur, x1, y1) < at(blur, x2, y2) ? 1u : 0u) << j;
+  }
+  const unsigned hi = __shfl_down(bits, 1);   // byte m = tests 8 m .. 8 m + 7 = lanes 2 m (low nibble) and 2 m + 1
+  if (!(lane & 1)) desc[lane >> 1] = (uint8_t)(bits | (hi << 4));
+  if (lane == 0) *angle = atan2f(sa, ca);
+}
+
+// One wave per keypoint, four per workgroup: rec = (cx, cy, level) per keypoint, already in output order and clamped into its level; the
+// levels' images, smoothed images and shapes come from lv.  A wave picks its indexing once: a keypoint within ORB_REACH pixels of its
+// level's border reads at reflected indices, every other one runs orb_describe_kernel's stream.  No response is written: the caller's
+// keypoints keep theirs.
+__global__ __launch_bounds__(256) void orb_describe_given_kernel(const OrbLevels lv, const int *__restrict__ rec, int n, const signed char *__restrict__ disc,
+                                                                 const float *__restrict__ pattern, float *__restrict__ angle, uint8_t *__restrict__ desc) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const int cx = __builtin_amdgcn_readfirstlane(rec[3 * i]), cy = __builtin_amdgcn_readfirstlane(rec[3 * i + 1]);
+  const int level = __builtin_amdgcn_readfirstlane(rec[3 * i + 2]) & (ORB_LEVELS - 1);
+  const OrbLevel &L = lv.l[level];
+  const int h = L.h, w = L.w;
+  const bool near = cx < ORB_REACH || cx >= w - ORB_REACH || cy < ORB_REACH || cy >= h - ORB_REACH;   // (the same in every lane)
+  if (near) orb_describe_given_one<true>(L.im, L.blur, h, w, cx, cy, lane, disc, pattern, angle + i, desc + (size_t)i * 32);
+  else orb_describe_given_one<false>(L.im, L.blur, h, w, cx, cy, lane, disc, pattern, angle + i, desc + (size_t)i * 32);
+}
+
 }  // namespace spvo

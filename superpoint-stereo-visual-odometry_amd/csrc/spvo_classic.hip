@@ -1,5 +1,5 @@
 // spvo_classic.hip -- the classic front end (ClassicFeatureFrontEnd, feature_detection_classic.cpp): the ORB detector / extractor (orb.hip.h),
-// the Shi-Tomasi and FAST detectors and the ORB extractor for given keypoints (classic_detect.hip.h), one submission per stereo pair into the
+// the Shi-Tomasi and FAST detectors and the ORB extractor for given keypoints (classic_detect.hip.h; at the keypoints' octaves: spvo_orb_describe_octaves), one submission per stereo pair into the
 // binary feature slots (spvo_classic_detect; its BRISK kinds hand the detector's list to spvo_brisk.hip, and spvo_sift.hip takes the same
 // detector link for spvo_classic_sift_pair), and spvo_preprocess for a context without an engine.  Everything here runs on the solver's stream (stream2) and owns its buffers (spvo_ctx::orb, spvo_ctx::cls).
 #include "spvo_internal.hip.h"
@@ -457,6 +457,105 @@ int spvo_orb_describe(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_
   HIP_TRY(c, hipMemcpyAsync(desc, b.desc, (size_t)nk * 32, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
   if (angle) for (int i = 0; i < nk; ++i) angle[i] = kp[i].angle;
+  return SPVO_OK;
+}
+
+// The extractor on keypoints that carry an octave (tests/orb_octaves_ref.py is the definition).  Level 0 is the resident image itself
+// (spvo_ctx::cls: its image, smoothed image and scratch), levels 1 .. top live in spvo_ctx::orb's pyramid buffers, whose geometry and
+// resize tables are orb_prepare's -- the levels are spvo_orb_detect's by construction.  At most 7 resize launches, the two smoothing
+// launches (a level without a kept keypoint has want = 0 and is skipped) and one describe launch, one wait at the end.
+int spvo_orb_describe_octaves(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride, const float *xy, const int32_t *octave, int n, int32_t *kept, float *angle,
+                              uint8_t *desc, int *n_kept) {
+  if (!c || !n_kept || rows <= 0 || cols <= 0 || n < 0 || (n > 0 && (!xy || !octave || !kept || !desc)) || (img && stride < (size_t)cols)) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  // every refusal first: nothing on the device and nothing in the outputs is touched by a call that fails here
+  float lscale[ORB_LEVELS];
+  int ph[ORB_LEVELS], pw[ORB_LEVELS], per_level[ORB_LEVELS] = {0};
+  {
+    float scale = 1.f;
+    for (int l = 0; l < ORB_LEVELS; ++l, scale *= 1.2f) {   // (orb_prepare's geometry; spvo_orb_detect's)
+      lscale[l] = scale;
+      ph[l] = (int)std::lround(rows / scale); pw[l] = (int)std::lround(cols / scale);
+    }
+  }
+  for (int i = 0; i < n; ++i) {
+    const int o = octave[i];
+    if (o < 0 || o >= ORB_LEVELS) return fail(c, SPVO_ERR_INVALID, "spvo_orb_describe_octaves: keypoint %d has octave %d; the pyramid has levels 0 .. %d", i, o, ORB_LEVELS - 1);
+    if (!std::isfinite(xy[2 * i]) || !std::isfinite(xy[2 * i + 1]))
+      return fail(c, SPVO_ERR_INVALID, "spvo_orb_describe_octaves: keypoint %d is (%g, %g)", i, (double)xy[2 * i], (double)xy[2 * i + 1]);
+    if (ph[o] < ORB_MIN_LEVEL || pw[o] < ORB_MIN_LEVEL)
+      return fail(c, SPVO_ERR_INVALID, "spvo_orb_describe_octaves: keypoint %d names octave %d, whose level is %d x %d: levels of at least %d x %d only", i, o, ph[o], pw[o], ORB_MIN_LEVEL,
+                  ORB_MIN_LEVEL);
+  }
+  if (int rc = require_idle(c)) return rc;
+  auto &b = c->cls;
+  if (!img && (b.rows != rows || b.cols != cols))
+    return fail(c, SPVO_ERR_STATE, "spvo_orb_describe_octaves: no image of %d x %d is resident (call a detector first, or pass the image)", rows, cols);
+  // cv::ORB::compute: the border rule at level 0 (coordinates rounded half to even), then the survivors grouped by level, stable
+  std::vector<int> pass;
+  pass.reserve((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const float xi = std::rint(xy[2 * i]), yi = std::rint(xy[2 * i + 1]);
+    if (xi < (float)ORB_EDGE || xi >= (float)(cols - ORB_EDGE) || yi < (float)ORB_EDGE || yi >= (float)(rows - ORB_EDGE)) continue;
+    pass.push_back(i);
+    ++per_level[octave[i]];
+  }
+  const int nk = (int)pass.size();
+  int first[ORB_LEVELS], top = 0;
+  for (int l = 0, at = 0; l < ORB_LEVELS; ++l) {
+    first[l] = at;
+    at += per_level[l];
+    if (per_level[l]) top = l;
+  }
+  std::vector<int> rec((size_t)3 * nk);
+  for (int i : pass) {   // (a kept keypoint lies within the level-0 image, so x / scale fits an int)
+    const int l = octave[i], r = first[l]++;
+    kept[r] = i;
+    rec[3 * r] = std::min(std::max((int)std::rint(xy[2 * i] / lscale[l]), 0), pw[l] - 1);
+    rec[3 * r + 1] = std::min(std::max((int)std::rint(xy[2 * i + 1] / lscale[l]), 0), ph[l] - 1);
+    rec[3 * r + 2] = l;
+  }
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = c->stream2;
+  if (img) {
+    if (int rc = cls_prepare(c, img, rows, cols, stride)) return rc;
+  }
+  *n_kept = nk;
+  if (nk == 0) {
+    HIP_TRY(c, hipStreamSynchronize(st));   // (the caller's image may be in flight)
+    return SPVO_OK;
+  }
+  auto &o = c->orb;
+  OrbPlan plan;
+  if (int rc = orb_prepare(c, rows, cols, 1, plan)) return rc;   // (no keypoint buffer of spvo_orb_detect's is used: nfeatures 1 grows none)
+  if (nk > b.oct_cap) {
+    HIP_TRY(c, hipStreamSynchronize(st));
+    dev_free(b.oct_rec, b.oct_angle, b.oct_desc);
+    b.oct_cap = 0;
+    int rc;
+    if ((rc = dev_alloc(c, &b.oct_rec, (size_t)3 * nk)) || (rc = dev_alloc(c, &b.oct_angle, (size_t)nk)) || (rc = dev_alloc(c, &b.oct_desc, (size_t)nk * 32))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    b.oct_cap = nk;
+  }
+  HIP_TRY(c, hipMemcpyAsync(b.oct_rec, rec.data(), rec.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  OrbLevels lv{};
+  for (int l = 0; l <= top; ++l) {
+    OrbLevel &L = lv.l[l];
+    if (l == 0) { L.im = b.im; L.blur = b.blur; L.tmp = b.tmp; }
+    else { L.im = o.im + plan.off[l]; L.blur = o.blur + plan.off[l]; L.tmp = o.tmp + plan.off[l]; }
+    L.h = plan.ph[l]; L.w = plan.pw[l]; L.scale = plan.lscale[l];
+    L.want = L.cap = per_level[l];
+    if (l > 0)
+      hipLaunchKernelGGL(orb_resize_kernel, dim3((L.w + 63) / 64, (L.h + 3) / 4), dim3(256), 0, st, lv.l[l - 1].im, plan.ph[l - 1], plan.pw[l - 1], plan.pw[l - 1], L.im, L.h, L.w,
+                         o.tab + plan.toff[l]);
+  }
+  const dim3 grid((cols + 63) / 64, (rows + 3) / 4, top + 1);
+  hipLaunchKernelGGL(orb_blur_h_kernel, grid, dim3(256), 0, st, lv, o.taps);
+  hipLaunchKernelGGL(orb_blur_v_kernel, grid, dim3(256), 0, st, lv, o.taps);
+  hipLaunchKernelGGL(orb_describe_given_kernel, dim3((nk + 3) / 4), dim3(256), 0, st, lv, b.oct_rec, nk, o.disc, o.pattern, b.oct_angle, b.oct_desc);
+  HIP_TRY(c, hipGetLastError());
+  if (angle) HIP_TRY(c, hipMemcpyAsync(angle, b.oct_angle, (size_t)nk * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(desc, b.oct_desc, (size_t)nk * 32, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));   // the one wait of the call
   return SPVO_OK;
 }
 

@@ -479,7 +479,7 @@ void spvo_destroy(spvo_ctx *c) {
   brisk_detect_release(c);
   akaze_release(c);
   auto &b = c->cls;
-  dev_free(b.im, b.score, b.blur, b.src, b.state, b.desc, b.tmp, b.lam, b.xy, b.resp, b.keys, b.rank, b.cand, b.counters, b.kp_xy, b.kps, b.pre_out, b.pre_tab);
+  dev_free(b.im, b.score, b.blur, b.src, b.state, b.desc, b.tmp, b.lam, b.xy, b.resp, b.keys, b.rank, b.cand, b.counters, b.kp_xy, b.kps, b.oct_rec, b.oct_angle, b.oct_desc, b.pre_out, b.pre_tab);
   host_free(c->h_match_tmp);
   if (c->stream_t) (void)hipStreamDestroy(c->stream_t);
   if (c->stream_tb) (void)hipStreamDestroy(c->stream_tb);

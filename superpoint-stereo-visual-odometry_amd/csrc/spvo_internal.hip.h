@@ -368,6 +368,10 @@ struct spvo_ctx {
     unsigned long long *keys = nullptr;
     int *rank = nullptr, *cand = nullptr, *counters = nullptr, *kp_xy = nullptr;
     OrbKeypoint *kps = nullptr;
+    int oct_cap = 0;                      // spvo_orb_describe_octaves: rows its three buffers hold -- records (cx, cy, level) in output order,
+    int *oct_rec = nullptr;               // the directions and the 32-byte rows
+    float *oct_angle = nullptr;
+    uint8_t *oct_desc = nullptr;
     uint8_t *pre_out = nullptr;           // spvo_preprocess of a context without an engine (the classic front end at a fixed input size): resized image,
     int *pre_tab = nullptr;               // resize tables of the crop pre_crop_rows x pre_crop_cols
     int pre_crop_rows = 0, pre_crop_cols = 0;

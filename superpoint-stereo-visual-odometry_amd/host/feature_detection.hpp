@@ -352,13 +352,16 @@ public:
   // that pair is refused as every pair that does not run is.  setAkazePairResident: AKAZE + AKAZE takes its route (spvo_akaze_detect_pair)
   // only with this as well as setAkazeDescriptor and setDeviceResident.  setSiftDescribeResident: ShiTomasi + SIFT and FAST + SIFT take
   // their route (spvo_classic_sift_pair: detector, SIFT base level and descriptor on the device, rows into the SIFT slots) only with this as
-  // well as setDeviceResident; the other detectors with the SIFT extractor have no route.
+  // well as setDeviceResident; the other detectors with the SIFT extractor have no route.  setOrbExtractorOctaves: BRISK + ORB and AKAZE + ORB
+  // run (per image, no route: spvo_orb_describe_octaves on the level KeyPoint::octave names); off, both are refused as before and the
+  // refusal does not list them.
   static void setDeviceResident(bool on);
   static void setResidentCapacity(int rows);   // rows per binary slot [8192]
   static void setBriskPairResident(bool on);   // [off]
   static void setAkazeDescriptor(bool on);     // [off]
   static void setAkazePairResident(bool on);   // [off]
   static void setSiftDescribeResident(bool on);   // [off]
+  static void setOrbExtractorOctaves(bool on);    // [off]
   // pairs that actually stayed resident (spvo_classic_detect / spvo_sift_detect_pair / spvo_brisk_detect_pair / spvo_akaze_detect_pair / spvo_classic_sift_pair returned SPVO_OK): what tells the resident path from its fallback
   unsigned residentPairs() const { return resident_ok_pairs_; }
 
@@ -368,6 +371,7 @@ private:
   bool akaze_descriptor_ = false;      // setAkazeDescriptor at construction
   bool akaze_pair_resident_ = false;   // setAkazePairResident at construction
   bool sift_describe_resident_ = false;   // setSiftDescribeResident at construction
+  bool orb_octaves_ = false;           // setOrbExtractorOctaves at construction
   bool pairRuns() const;               // this detector / descriptor pair runs in this build
   int resident_capacity_ = 8192;
   unsigned resident_pairs_ = 0;   // pairs handed to a resident route: pair k lives in slots 2 (k % 4), 2 (k % 4) + 1

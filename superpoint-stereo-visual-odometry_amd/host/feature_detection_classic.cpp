@@ -14,11 +14,13 @@ static bool g_classic_brisk_pair_resident = false;
 static bool g_classic_akaze_descriptor = false;
 static bool g_classic_akaze_pair_resident = false;
 static bool g_classic_sift_describe_resident = false;
+static bool g_classic_orb_octaves = false;
 void ClassicFeatureFrontEnd::setDeviceResident(bool on) { g_classic_resident = on; }
 void ClassicFeatureFrontEnd::setBriskPairResident(bool on) { g_classic_brisk_pair_resident = on; }
 void ClassicFeatureFrontEnd::setAkazeDescriptor(bool on) { g_classic_akaze_descriptor = on; }
 void ClassicFeatureFrontEnd::setAkazePairResident(bool on) { g_classic_akaze_pair_resident = on; }
 void ClassicFeatureFrontEnd::setSiftDescribeResident(bool on) { g_classic_sift_describe_resident = on; }
+void ClassicFeatureFrontEnd::setOrbExtractorOctaves(bool on) { g_classic_orb_octaves = on; }
 void ClassicFeatureFrontEnd::setResidentCapacity(int rows) { g_classic_resident_capacity = rows; }
 
 #ifdef SPVO_USE_OPENCV
@@ -91,7 +93,7 @@ bool ClassicFeatureFrontEnd::available() { return true; }
 enum class Detect { Orb, Gftt, Fast, Sift, Brisk, Akaze };       // detectKeypoints: spvo_<this>_detect
 enum class Describe { WithDetector, Orb, Brisk, Akaze, Sift };   // describeKeypoints: the rows detectKeypoints kept, or spvo_<this>_describe on the given keypoints
 enum class Route { None, Classic, SiftPair, BriskPair, AkazePair, ClassicSift };   // setDeviceResident: the per-image path, spvo_classic_detect (kind), spvo_sift_detect_pair, spvo_brisk_detect_pair, spvo_akaze_detect_pair, spvo_classic_sift_pair (kind)
-enum class OptIn { None, AkazeDescriptor, BriskPairResident, AkazePairResident, SiftDescribeResident };   // to run at all: setAkazeDescriptor; to stay resident: setBriskPairResident, setAkazePairResident, setSiftDescribeResident
+enum class OptIn { None, AkazeDescriptor, OrbOctaves, BriskPairResident, AkazePairResident, SiftDescribeResident };   // to run at all: setAkazeDescriptor, setOrbExtractorOctaves; to stay resident: setBriskPairResident, setAkazePairResident, setSiftDescribeResident
 
 struct ClassicPair {
   DetectorType detector;
@@ -121,15 +123,18 @@ static const ClassicPair kClassicPairs[] = {
     {DetectorType::ORB, DescriptorType::SIFT, Detect::Orb, 0.f, Describe::Sift, 128, CV_32FC1, Route::None, 0, OptIn::None, OptIn::None},
     {DetectorType::BRISK, DescriptorType::SIFT, Detect::Brisk, 0.f, Describe::Sift, 128, CV_32FC1, Route::None, 0, OptIn::None, OptIn::None},
     {DetectorType::AKAZE, DescriptorType::SIFT, Detect::Akaze, 0.f, Describe::Sift, 128, CV_32FC1, Route::None, 0, OptIn::None, OptIn::None},
+    // the ORB extractor on keypoints that carry an octave (spvo_orb_describe_octaves): only with setOrbExtractorOctaves, and listed only then
+    {DetectorType::BRISK, DescriptorType::ORB, Detect::Brisk, 0.f, Describe::Orb, 32, CV_8UC1, Route::None, 0, OptIn::OrbOctaves, OptIn::None},
+    {DetectorType::AKAZE, DescriptorType::ORB, Detect::Akaze, 0.f, Describe::Orb, 32, CV_8UC1, Route::None, 0, OptIn::OrbOctaves, OptIn::None},
 };
 
 // the row of a pair that runs, or nullptr
-static const ClassicPair *find_pair(DetectorType d, DescriptorType e, bool akaze_descriptor) {
+static const ClassicPair *find_pair(DetectorType d, DescriptorType e, bool akaze_descriptor, bool orb_octaves) {
   for (const ClassicPair &p : kClassicPairs)
-    if (p.detector == d && p.descriptor == e && (p.opt_in != OptIn::AkazeDescriptor || akaze_descriptor)) return &p;
+    if (p.detector == d && p.descriptor == e && (p.opt_in != OptIn::AkazeDescriptor || akaze_descriptor) && (p.opt_in != OptIn::OrbOctaves || orb_octaves)) return &p;
   return nullptr;
 }
-const ClassicPair *ClassicFeatureFrontEnd::pair() const { return find_pair(detector_type_, descriptor_type_, akaze_descriptor_); }
+const ClassicPair *ClassicFeatureFrontEnd::pair() const { return find_pair(detector_type_, descriptor_type_, akaze_descriptor_, orb_octaves_); }
 bool ClassicFeatureFrontEnd::pairRuns() const { return pair() != nullptr; }
 
 template <class Names, class T> static std::string name_of(const Names &names, T type) {
@@ -137,21 +142,23 @@ template <class Names, class T> static std::string name_of(const Names &names, T
     if (kv.second == type) return kv.first;
   return "?";
 }
-// what a pair that does not run is told: the table's rows
-static std::string refusal() {
+// what a pair that does not run is told: the table's rows (those behind setOrbExtractorOctaves only while that switch is on)
+static std::string refusal(bool orb_octaves) {
   std::string s = "this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only these pairs run: ";
-  for (const ClassicPair &p : kClassicPairs)
+  for (const ClassicPair &p : kClassicPairs) {
+    if (p.opt_in == OptIn::OrbOctaves && !orb_octaves) continue;
     s += std::string(&p == kClassicPairs ? "" : ", ") + name_of(detector_name_to_type, p.detector) + " + " + name_of(descriptor_name_to_type, p.descriptor) +
          (p.opt_in == OptIn::AkazeDescriptor ? " (with setAkazeDescriptor)" : "");
+  }
   return s;
 }
 // Of a pair that does not run, the detector is at fault unless it runs with the ORB extractor, and the descriptor unless it runs on ORB
 // keypoints (ORB + ORB is the reference's baseline, launch/visual_odometry_classic.launch)
 void ClassicFeatureFrontEnd::initDetector() {
-  if (!pair() && !find_pair(detector_type_, DescriptorType::ORB, akaze_descriptor_)) logError("[initDetector] " + refusal());
+  if (!pair() && !find_pair(detector_type_, DescriptorType::ORB, akaze_descriptor_, orb_octaves_)) logError("[initDetector] " + refusal(orb_octaves_));
 }
 void ClassicFeatureFrontEnd::initDescriptor() {
-  if (!pair() && !find_pair(DetectorType::ORB, descriptor_type_, akaze_descriptor_)) logError("[initDescriptor] " + refusal());
+  if (!pair() && !find_pair(DetectorType::ORB, descriptor_type_, akaze_descriptor_, orb_octaves_)) logError("[initDescriptor] " + refusal(orb_octaves_));
 }
 
 // ---- records -> cv::KeyPoint: one conversion per record type, for the per-image path and the resident one alike
@@ -226,7 +233,7 @@ std::vector<cv::KeyPoint> ClassicFeatureFrontEnd::detectKeypoints(const cv::Mat 
   detected_data_ = nullptr;
   const ClassicPair *p = pair();
   if (!p) {
-    logError("ClassicFeatureFrontEnd: " + refusal());
+    logError("ClassicFeatureFrontEnd: " + refusal(orb_octaves_));
     return keypoints;
   }
   if (!ensureContext()) return keypoints;
@@ -364,17 +371,21 @@ cv::Mat ClassicFeatureFrontEnd::describeKeypoints(std::vector<cv::KeyPoint> &key
     // border are ERASED from the caller's vector (it is passed by non-const reference, classic.cpp:110-111), so keypoints_dq and descriptors_dq
     // stay aligned.  BRISK: every keypoint's own size (5: ShiTomasi, 7: FAST, 12 x its scale: BRISK, 3 x esigma: AKAZE) picks its scale, and the
     // angle comes in degrees, 0 .. 360 -- except that a BRISK keypoint keeps the angle its detector reports (-1)
-    const bool brisk = p->describe == Describe::Brisk;
+    // ORB on BRISK / AKAZE keypoints (the rows behind setOrbExtractorOctaves): KeyPoint::octave names the pyramid level, the survivors come
+    // grouped by level as OpenCV leaves them
+    const bool brisk = p->describe == Describe::Brisk, octaves = p->opt_in == OptIn::OrbOctaves;
     std::vector<float> xy((size_t)n * 2), size(brisk ? (size_t)n : 0);
-    std::vector<int32_t> kept((size_t)n);
+    std::vector<int32_t> kept((size_t)n), octave(octaves ? (size_t)n : 0);
     for (int i = 0; i < n; ++i) {
       xy[2 * i] = keypoints[i].pt.x; xy[2 * i + 1] = keypoints[i].pt.y;
       if (brisk) size[i] = keypoints[i].size;
+      if (octaves) octave[i] = keypoints[i].octave;
     }
     int m = 0;
-    call = brisk ? "spvo_brisk_describe" : "spvo_orb_describe";
-    rc = brisk ? spvo_brisk_describe(ctx_, px, img.rows, img.cols, step, xy.data(), size.data(), n, kept.data(), angle.data(), rows, nullptr, &m)
-               : spvo_orb_describe(ctx_, px, img.rows, img.cols, step, xy.data(), n, kept.data(), angle.data(), rows, &m);
+    call = brisk ? "spvo_brisk_describe" : octaves ? "spvo_orb_describe_octaves" : "spvo_orb_describe";
+    rc = brisk     ? spvo_brisk_describe(ctx_, px, img.rows, img.cols, step, xy.data(), size.data(), n, kept.data(), angle.data(), rows, nullptr, &m)
+         : octaves ? spvo_orb_describe_octaves(ctx_, px, img.rows, img.cols, step, xy.data(), octave.data(), n, kept.data(), angle.data(), rows, &m)
+                   : spvo_orb_describe(ctx_, px, img.rows, img.cols, step, xy.data(), n, kept.data(), angle.data(), rows, &m);
     if (rc == SPVO_OK) {
       std::vector<cv::KeyPoint> out;
       out.reserve(m);
@@ -399,7 +410,7 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
     return;
   }
   if (!pairRuns()) {
-    logError("ClassicFeatureFrontEnd: " + refusal());
+    logError("ClassicFeatureFrontEnd: " + refusal(orb_octaves_));
     return;
   }
   if (!ensureContext()) return;   // no device: logged, nothing pushed (nn.cpp:53-55 convention)
@@ -521,6 +532,7 @@ ClassicFeatureFrontEnd::ClassicFeatureFrontEnd(const DetectorType detector_type,
     : FeatureFrontEnd(detector_type, descriptor_type, matcher_type, selector_type, cross_check, stereo_threshold, stereo_threshold, refinement_degree,
                       verbose, input_height, input_width) {
   akaze_descriptor_ = g_classic_akaze_descriptor;   // (initDetector and initDescriptor ask whether the pair runs)
+  orb_octaves_ = g_classic_orb_octaves;
   initDetector();
   initDescriptor();
   initMatcher();

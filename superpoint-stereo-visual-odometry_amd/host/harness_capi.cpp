@@ -439,6 +439,10 @@ void spvo_host_classic_set_akaze_resident(int on) { ClassicFeatureFrontEnd::setA
 // spvo_classic_sift_pair when the resident option of the sequence run is on as well
 void spvo_host_classic_set_sift_describe_resident(int on) { ClassicFeatureFrontEnd::setSiftDescribeResident(on != 0); }
 
+// ClassicFeatureFrontEnd::setOrbExtractorOctaves for the front ends constructed afterwards: BRISK + ORB and AKAZE + ORB run
+// (spvo_orb_describe_octaves on the detector's keypoints at their octaves, the per-image path); off, both pairs are refused
+void spvo_host_classic_set_orb_octaves(int on) { ClassicFeatureFrontEnd::setOrbExtractorOctaves(on != 0); }
+
 // the ORB + ORB front end at the native resolution (the export's first form)
 int spvo_host_classic_sequence(int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l, const double *P_r, int knn,
                                int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats, double *seconds) {

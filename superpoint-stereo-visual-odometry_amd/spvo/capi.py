@@ -94,7 +94,7 @@ SYMBOLS = [
     "spvo_default_config", "spvo_create", "spvo_destroy", "spvo_last_error", "spvo_load_weights", "spvo_engine_precision", "spvo_set_fp32_split",
     "spvo_preprocess", "spvo_forward", "spvo_debug_tensor", "spvo_heatmap", "spvo_nms",
     "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8",
-    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_akaze_describe", "spvo_akaze_detect_pair", "spvo_akaze_suppress_debug", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_describe", "spvo_sift_detect_pair", "spvo_classic_sift_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
+    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_orb_describe_octaves", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_akaze_describe", "spvo_akaze_detect_pair", "spvo_akaze_suppress_debug", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_describe", "spvo_sift_detect_pair", "spvo_classic_sift_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
     "spvo_profile_enable", "spvo_profile_reset", "spvo_profile_only", "spvo_profile_count", "spvo_profile_get", "spvo_profile_stage_kernel",
     "spvo_set_tuning", "spvo_get_tuning", "spvo_clear_tuning",
     "spvo_comm_unique_id", "spvo_comm_available", "spvo_comm_create", "spvo_comm_create_host", "spvo_comm_rank", "spvo_comm_world", "spvo_comm_destroy",
@@ -151,6 +151,7 @@ def load() -> C.CDLL:
     lib.spvo_gftt_last_rounds.argtypes = [vp, vp, ip]
     lib.spvo_fast_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, vp, vp, C.c_int, ip]
     lib.spvo_orb_describe.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, vp, vp, vp, ip]
+    lib.spvo_orb_describe_octaves.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, C.c_int, vp, vp, vp, ip]
     lib.spvo_brisk_describe.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, C.c_int, vp, vp, vp, vp, ip]
     lib.spvo_brisk_tables.argtypes = [C.c_int, vp, vp, vp, vp, vp]
     lib.spvo_brisk_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, vp, C.c_int, ip]
@@ -488,6 +489,31 @@ class Context:
             img = _u8_rows(img)
             (rows, cols), ptr, stride = img.shape, _ptr(img), img.strides[0]
         self._check(self.lib.spvo_orb_describe(self.h, ptr, rows, cols, stride, _ptr(xy), n, _ptr(kept), _ptr(angle), _ptr(desc), C.byref(m)))
+        if img is not None:
+            self._resident_shape = img.shape
+        return dict(kept=kept[:m.value].copy(), angle=angle[:m.value].copy(), desc=desc[:m.value].copy())
+
+    def orb_describe_octaves(self, img, xy: np.ndarray, octave, shape=None):
+        """ORB descriptors of given keypoints on the pyramid level their octave names (spvo_orb_describe_octaves); octave: per keypoint,
+        or one for all.  img = None: the image the last detector or describe call of this context left on the device (shape as in
+        orb_describe).  -> dict of kept [m] (indices into xy that survived the 31-pixel border rule at level 0, grouped by octave), angle [m]
+        rad, desc [m,32]."""
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        n = len(xy)
+        octave = np.ascontiguousarray(np.broadcast_to(np.asarray(octave, np.int32), (n,)))
+        kept = np.zeros(max(n, 1), np.int32)
+        angle = np.zeros(max(n, 1), np.float32)
+        desc = np.zeros((max(n, 1), 32), np.uint8)
+        m = C.c_int(0)
+        if img is None:
+            rows, cols = shape if shape is not None else getattr(self, "_resident_shape", (0, 0))
+            ptr, stride = None, 0
+            if rows <= 0 or cols <= 0:
+                rows = cols = 1            # nothing remembered: let the library answer (SPVO_ERR_STATE)
+        else:
+            img = _u8_rows(img)
+            (rows, cols), ptr, stride = img.shape, _ptr(img), img.strides[0]
+        self._check(self.lib.spvo_orb_describe_octaves(self.h, ptr, rows, cols, stride, _ptr(xy), _ptr(octave), n, _ptr(kept), _ptr(angle), _ptr(desc), C.byref(m)))
         if img is not None:
             self._resident_shape = img.shape
         return dict(kept=kept[:m.value].copy(), angle=angle[:m.value].copy(), desc=desc[:m.value].copy())

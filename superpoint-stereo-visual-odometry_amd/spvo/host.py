@@ -342,10 +342,12 @@ class FrontEnd:
 
 
 def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_threshold=2.0, refinement_degree=4, warm=0, detector="ORB", input_size=None, resident=False,
-                     resident_capacity=0, trace=False, descriptor="ORB", brisk_resident=False, akaze_descriptor=False, akaze_resident=False, sift_describe_resident=False):
+                     resident_capacity=0, trace=False, descriptor="ORB", brisk_resident=False, akaze_descriptor=False, akaze_resident=False, sift_describe_resident=False, orb_octaves=False):
     """stereoCallback replayed on ClassicFeatureFrontEnd(detector, descriptor, BF, ...) (node.cpp:353-360) over host image pairs -- detector
     "ORB", "ShiTomasi" or "FAST" with descriptor "ORB", "ShiTomasi", "FAST", "BRISK" or "AKAZE" with descriptor "BRISK" (64-byte rows; detector "BRISK"
-    or "AKAZE" with the default descriptor "ORB" does not run; "AKAZE" with descriptor "AKAZE" -- orientation and the 61-byte MLDB rows of
+    or "AKAZE" with the default descriptor "ORB" runs only with orb_octaves=True (ClassicFeatureFrontEnd::setOrbExtractorOctaves, reset afterwards:
+    spvo_orb_describe_octaves on the level each keypoint's octave names, the per-image path, classic_resident_pairs() stays 0) and is refused
+    without; "AKAZE" with descriptor "AKAZE" -- orientation and the 61-byte MLDB rows of
     spvo_akaze_describe -- runs with akaze_descriptor=True (ClassicFeatureFrontEnd::setAkazeDescriptor, reset afterwards) and is refused without), "ShiTomasi", "FAST", "ORB",
     "BRISK" or "AKAZE" with descriptor "SIFT" (spvo_sift_describe on the detector's keypoints as they are: 128 floats per row, matched with
     NORM_L2; the per-image path and classic_resident_pairs() stays 0 -- except "ShiTomasi" and "FAST" with sift_describe_resident=True
@@ -380,6 +382,8 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     lib.spvo_host_classic_set_akaze_descriptor.argtypes = [C.c_int]
     lib.spvo_host_classic_set_sift_describe_resident.restype = None
     lib.spvo_host_classic_set_sift_describe_resident.argtypes = [C.c_int]
+    lib.spvo_host_classic_set_orb_octaves.restype = None
+    lib.spvo_host_classic_set_orb_octaves.argtypes = [C.c_int]
     n = len(frames)
     ls = [np.ascontiguousarray(f[0], np.uint8) for f in frames]
     rs = [np.ascontiguousarray(f[1], np.uint8) for f in frames]
@@ -398,6 +402,7 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     lib.spvo_host_classic_set_akaze_resident(int(bool(akaze_resident)))
     lib.spvo_host_classic_set_akaze_descriptor(int(bool(akaze_descriptor)))
     lib.spvo_host_classic_set_sift_describe_resident(int(bool(sift_describe_resident)))
+    lib.spvo_host_classic_set_orb_octaves(int(bool(orb_octaves)))
     try:
         args = (n, pl, pr, rows, cols, Pl.ctypes.data, Pr.ctypes.data, 1 if selector == "KNN" else 0, int(cross_check), stereo_threshold, refinement_degree, warm,
                 poses.ctypes.data, stats.ctypes.data, C.byref(sec), ih, iw, digest.ctypes.data if trace else None)
@@ -411,6 +416,7 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
         lib.spvo_host_classic_set_akaze_resident(0)
         lib.spvo_host_classic_set_akaze_descriptor(0)
         lib.spvo_host_classic_set_sift_describe_resident(0)
+        lib.spvo_host_classic_set_orb_octaves(0)
     if rc == -1000000:
         raise ValueError("unknown detector %r" % (detector,))
     if rc == -1000001:
@@ -447,9 +453,10 @@ def classic_default_probe(img_l, img_r, P_l, P_r):
     return rc, counts, buf.value.decode()
 
 
-def classic_pair_probe(detector, descriptor, img_l, img_r, P_l, P_r, akaze_descriptor=False):
+def classic_pair_probe(detector, descriptor, img_l, img_r, P_l, P_r, akaze_descriptor=False, orb_octaves=False):
     """ClassicFeatureFrontEnd(detector, descriptor, BF, NN, cross-check) at the native resolution offered one stereo pair.
     akaze_descriptor: ClassicFeatureFrontEnd::setAkazeDescriptor for this probe (AKAZE + AKAZE runs), reset afterwards.
+    orb_octaves: ClassicFeatureFrontEnd::setOrbExtractorOctaves for this probe (BRISK + ORB and AKAZE + ORB run), reset afterwards.
     -> (deque entries, [keypoints L, descriptor rows L, keypoints R, descriptor rows R, descriptor columns], the error it logged)"""
     lib = load()
     lib.spvo_host_classic_pair_probe.restype = C.c_int
@@ -463,9 +470,13 @@ def classic_pair_probe(detector, descriptor, img_l, img_r, P_l, P_r, akaze_descr
     lib.spvo_host_classic_set_akaze_descriptor.restype = None
     lib.spvo_host_classic_set_akaze_descriptor.argtypes = [C.c_int]
     lib.spvo_host_classic_set_akaze_descriptor(int(bool(akaze_descriptor)))
+    lib.spvo_host_classic_set_orb_octaves.restype = None
+    lib.spvo_host_classic_set_orb_octaves.argtypes = [C.c_int]
+    lib.spvo_host_classic_set_orb_octaves(int(bool(orb_octaves)))
     try:
         rc = lib.spvo_host_classic_pair_probe(detector.encode(), descriptor.encode(), l.ctypes.data, r.ctypes.data, l.shape[0], l.shape[1], Pl.ctypes.data, Pr.ctypes.data,
                                               counts.ctypes.data, buf, 512)
     finally:
         lib.spvo_host_classic_set_akaze_descriptor(0)
+        lib.spvo_host_classic_set_orb_octaves(0)
     return rc, counts, buf.value.decode()

@@ -25,6 +25,12 @@ python tools/classic_bench.py --leg brisk|orb_describe [--calls 50]
     spvo_brisk_describe / spvo_orb_describe alone on the FAST keypoints of the 1241 x 376 sample (image passed with every call), for
     rocprofv3 --kernel-trace --stats as above: brisk_integral_rows_kernel + brisk_integral_cols_kernel / brisk_compact_kernel /
     brisk_describe_kernel is the split.  --leg brisk also prints the one-off cost: the table build and the first call's upload.
+python tools/classic_bench.py --leg orb_octaves [--calls 100]
+    spvo_orb_describe_octaves alone on the BRISK detector's keypoints (octaves 0..5) of the 1241 x 376 sample, image passed with every
+    call and on the resident image (img = NULL), for rocprofv3 --kernel-trace --stats as above (orb_resize_kernel x top octave /
+    orb_blur_h_kernel / orb_blur_v_kernel / orb_describe_given_kernel is the split), and in the same run its yardstick:
+    spvo_orb_describe on the FAST keypoints of the same image.  The whole pair through the host class: --detector BRISK|AKAZE
+    --descriptor ORB --orb-octaves (ClassicFeatureFrontEnd::setOrbExtractorOctaves for the run).
 python tools/classic_bench.py --leg brisk_detect [--calls 50]
     spvo_brisk_detect (threshold 30) alone per image at 1241 x 376, for rocprofv3 --kernel-trace --stats as above: brisk_area_kernel /
     brisk_half_kernel / brisk_score916_kernel / brisk_score58_kernel / brisk_collect_kernel / cls_rank_kernel / brisk_refine_kernel /
@@ -81,8 +87,9 @@ ap.add_argument("--resident", action="store_true")
 ap.add_argument("--brisk-resident", action="store_true")
 ap.add_argument("--akaze-resident", action="store_true")
 ap.add_argument("--sift-resident", action="store_true")
+ap.add_argument("--orb-octaves", action="store_true")
 ap.add_argument("--ab", type=int, default=0)
-ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "brisk_detect", "akaze_detect", "akaze_describe", "akaze_pair", "brisk_pair", "orb_describe", "fast_sift", "gftt_sift", "sift_describe", "match", "match_slots"])
+ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "brisk_detect", "akaze_detect", "akaze_describe", "akaze_pair", "brisk_pair", "orb_describe", "orb_octaves", "fast_sift", "gftt_sift", "sift_describe", "match", "match_slots"])
 ap.add_argument("--form", type=int, default=0, choices=[0, 1])
 ap.add_argument("--waves", type=int, default=0)
 ap.add_argument("--selector", default="KNN", choices=["NN", "KNN"])
@@ -139,7 +146,7 @@ if args.detectors or args.leg:
         fl, fr = ctx.classic_sift_pair(img, pair_r, 2 * k, 2 * k + 1, kind="FAST" if args.leg == "fast_sift" else "ShiTomasi")
         return fl["n"] + fr["n"]
 
-    if args.leg in ("brisk", "orb_describe"):
+    if args.leg in ("brisk", "orb_describe", "orb_octaves"):
         kp = ctx.fast(img)["xy"]
         if args.leg == "brisk":
             t0 = time.perf_counter()
@@ -200,6 +207,17 @@ if args.detectors or args.leg:
     def leg_orb_describe():
         return len(ctx.orb_describe(img, kp)["kept"])
 
+    if args.leg == "orb_octaves":
+        bkp = ctx.brisk_detect(img, 30)["kp"]
+        bxy = np.ascontiguousarray(np.stack([bkp["x"], bkp["y"]], 1))
+        print("BRISK keypoints %d, per octave %s" % (len(bkp), np.bincount(bkp["octave"], minlength=6).tolist()))
+
+    def leg_orb_octaves():
+        return len(ctx.orb_describe_octaves(img, bxy, bkp["octave"])["kept"])
+
+    def leg_orb_octaves_null():                        # on the image the call before left resident
+        return len(ctx.orb_describe_octaves(None, bxy, bkp["octave"], shape=img.shape)["kept"])
+
     if args.leg in ("match", "match_slots"):
         img_r = np.ascontiguousarray(frames[0][1][:376, :1241])
         fl, fr = ctx.classic_detect(img, img_r, 0, 1, "ORB")
@@ -216,7 +234,8 @@ if args.detectors or args.leg:
     legs = dict(match=("spvo_match_hamming, %d x %d rows" % (len(fl["xy"]) if leg_match else 0, len(fr["xy"]) if leg_match else 0), leg_match),
                 match_slots=("spvo_match_hamming_slots, %d x %d rows" % (len(fl["xy"]) if leg_match else 0, len(fr["xy"]) if leg_match else 0), leg_match_slots),
                 brisk=("spvo_brisk_describe, %d FAST keypoints" % (len(kp) if args.leg == "brisk" else 0), leg_brisk),
-                orb_describe=("spvo_orb_describe, %d FAST keypoints" % (len(kp) if args.leg == "orb_describe" else 0), leg_orb_describe),
+                orb_describe=("spvo_orb_describe, %d FAST keypoints" % (len(kp) if args.leg in ("orb_describe", "orb_octaves") else 0), leg_orb_describe),
+                orb_octaves=("spvo_orb_describe_octaves(img), BRISK keypoints", leg_orb_octaves), orb_octaves_null=("spvo_orb_describe_octaves(NULL), BRISK keypoints", leg_orb_octaves_null),
                 akaze_describe=("spvo_akaze_describe(NULL)", leg_akaze_describe), akaze_brisk_null=("spvo_brisk_describe(NULL), same keypoints", leg_akaze_brisk_null),
                 akaze_describe_img=("spvo_akaze_describe(img)", leg_akaze_describe_img),
                 brisk_detect=("spvo_brisk_detect", leg_brisk_detect), akaze_detect=("spvo_akaze_detect", leg_akaze_detect), brisk_pair=("spvo_brisk_detect_pair (both images)", leg_brisk_pair),
@@ -230,6 +249,8 @@ if args.detectors or args.leg:
     keys = [args.leg] + (["sift"] if args.yardstick and args.leg not in ("fast_sift", "gftt_sift") else []) if args.leg else ["orb", "gftt", "fast"]
     if args.leg == "akaze_describe":
         keys = ["akaze_describe", "akaze_brisk_null", "akaze_describe_img", "akaze_detect"]
+    if args.leg == "orb_octaves":
+        keys = ["orb_octaves", "orb_octaves_null", "orb_describe"]
     for key in keys:
         name, fn = legs[key]
         for _ in range(args.warmup):
@@ -280,5 +301,5 @@ else:
     seq = [frames[i % 8] for i in range(n)]
     p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5, detector=args.detector, resident=args.resident, descriptor=args.descriptor,
                                         akaze_descriptor=args.descriptor == "AKAZE", **(dict(brisk_resident=True) if args.brisk_resident else {}), **(dict(akaze_resident=True) if args.akaze_resident else {}),
-                                        **(dict(sift_describe_resident=True) if args.sift_resident else {}))
+                                        **(dict(sift_describe_resident=True) if args.sift_resident else {}), **(dict(orb_octaves=True) if args.orb_octaves else {}))
     print("classic front end (%s%s) on the GPU: %.1f stereo frames/s (%.3f ms per pair), keypoints %d, stereo matches %d, inliers %d, %d pairs resident" % (args.detector + ("" if args.descriptor == "ORB" else " + " + args.descriptor), ", device-resident" if args.resident else "", (n - 5) / sec, 1e3 * sec / (n - 5), np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3]), host.classic_resident_pairs()))
