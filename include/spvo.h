@@ -835,6 +835,13 @@ int spvo_profile_get(spvo_ctx *ctx, int i, char *name, size_t name_cap, double *
  * "conv_mfma_kernel", "conv_f16_kernel", ...), and how many multiply-adds the matrix pipe executes per multiply-add of the
  * direct convolution (Winograd F(4x4,3x3): 0.25, F(2x2,3x3): 4/9, split bf16x3 mode: 6, otherwise 1). */
 int spvo_profile_stage_kernel(spvo_ctx *ctx, const char *stage, char *name, size_t name_cap, double *executed_per_algorithmic);
+/* Which TILE VARIANT of conv_mfma_kernel / conv_f16_kernel / conv_i8_kernel / conv_s3_kernel the loaded engine runs a "conv:<op index>"
+ * stage on -- the launchers' dispatch key: info[0] = kernel size (1 or 3), [1] = input channels per chunk, [2] = wr, [3] = wc (the tile is
+ * 4 wr rows x 32 wc columns of pixels), [4] = 1 for a layer with the 2x2 pooling fused -- and the persistent grid of that stage's most
+ * recent launch: [5] = tiles, [6] = workgroups (0, 0 before any launch).  A layer that runs no tile variant (a Winograd layer, a
+ * single-channel stem, a layer merged into its sibling's launch, an INT8 depthwise + pointwise block in one launch, the fused
+ * heads) reports info[0 .. 4] = 0. */
+int spvo_profile_stage_variant(spvo_ctx *ctx, const char *stage, int info[7]);
 
 /* ------------------------------------------------------- diagnostic switches (A/B measurements, parity debugging)
  * Which kernels / streams an engine uses is decided by the library from the plan and the sizes.  The decisions can be overridden
@@ -842,7 +849,7 @@ int spvo_profile_stage_kernel(spvo_ctx *ctx, const char *stage, char *name, size
  * of the process that hosts it (a ROS node) cannot change kernels by accident.  Process-wide; a value takes effect for contexts
  * created / engines loaded afterwards.  `name` is one of the names INTEGRATION.md lists ("winograd", "wino4", "wino4_item", "wino_narrow",
  * "wino_dynamic", "winograd_min_tiles", "wino4_min_tiles", "merge_siblings", "heads_fused", "heads_on_net", "heads_split",
- * "match_fused", "fp32_split", "prematch", "spin_wait", "trunk_timing", "solve_timing", "nms_first", "upload_side"); SPVO_ERR_INVALID for any other.
+ * "match_fused", "fp32_split", "prematch", "spin_wait", "trunk_timing", "solve_timing", "nms_first", "upload_side", "conv_variant"); SPVO_ERR_INVALID for any other.
  * spvo_get_tuning returns the value set, or `dflt`; spvo_clear_tuning forgets every value. */
 int spvo_set_tuning(const char *name, int value);
 int spvo_get_tuning(const char *name, int dflt);

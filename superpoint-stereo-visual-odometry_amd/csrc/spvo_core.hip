@@ -40,7 +40,7 @@ int stage_id(spvo_ctx *c, const std::string &name) {
 // ---- diagnostic switches (include/spvo.h: spvo_set_tuning).  One process-wide table, filled by explicit calls only.
 namespace {
 const char *const kTuningNames[] = {"winograd", "wino4", "wino4_item", "wino_narrow", "wino_dynamic", "winograd_min_tiles", "wino4_min_tiles", "merge_siblings", "heads_fused",
-                                    "heads_on_net", "heads_split", "match_fused", "fp32_split", "prematch", "spin_wait", "trunk_timing", "solve_timing", "nms_first", "upload_side", "inject_launch_failure", "int8_fused", "pair_always", "preprocess_fused", "heads_keep_raw", "tail_streams", "solve_collect_first", "graphs", "solve_fuse", "solve_keep", "sift_describe_form", "sift_pair_waves_per_cu"};
+                                    "heads_on_net", "heads_split", "match_fused", "fp32_split", "prematch", "spin_wait", "trunk_timing", "solve_timing", "nms_first", "upload_side", "inject_launch_failure", "int8_fused", "pair_always", "preprocess_fused", "heads_keep_raw", "tail_streams", "solve_collect_first", "graphs", "solve_fuse", "solve_keep", "sift_describe_form", "sift_pair_waves_per_cu", "conv_variant"};
 constexpr int kTuningCount = sizeof kTuningNames / sizeof kTuningNames[0];
 std::mutex g_tuning_mutex;
 bool g_tuning_set[kTuningCount] = {};
@@ -119,11 +119,19 @@ void choose_variant(int ks, int H, int W, int co_tiles, int batch, bool pool, in
   static const Cand k1[] = {{2, 2, 16, 1.0 / 1.00}, {1, 2, 16, 1.0 / 1.03}, {2, 1, 16, 1.0 / 1.03}, {1, 1, 16, 1.0 / 1.06}};
   const Cand *cands = ks == 3 ? k3 : k1;
   const int nc = 4;
+  // tuning "conv_variant" = 10 * wr + wc (diagnostic; read when an engine is loaded): that tile for every layer where it is one of the
+  // candidates below, so that a test can run each variant against the oracle; where it is not, and for any other value, the model decides
+  auto offered = [&](const Cand &v) {
+    if (pool && v.wr != 2) return false;             // a 2x2 pooling window lives in one wave
+    return !(ks == 1 && !pool && v.wr == 2 && v.wc == 1);
+  };
+  const int forced = tuning("conv_variant", 0);
+  bool forced_ok = false;
+  for (int i = 0; i < nc; ++i) forced_ok |= offered(cands[i]) && 10 * cands[i].wr + cands[i].wc == forced;
   double best = 1e300;
   for (int i = 0; i < nc; ++i) {
     const Cand &v = cands[i];
-    if (pool && v.wr != 2) continue;                 // a 2x2 pooling window lives in one wave
-    if (ks == 1 && !pool && v.wr == 2 && v.wc == 1) continue;
+    if (!offered(v) || (forced_ok && 10 * v.wr + v.wc != forced)) continue;
     const int th = 4 * v.wr, tw = 32 * v.wc;
     const int tx = (W + tw - 1) / tw, ty = (H + th - 1) / th;
     const long tiles = (long)tx * ty * co_tiles * batch;
@@ -1105,6 +1113,23 @@ int spvo_profile_stage_kernel(spvo_ctx *c, const char *stage, char *name, size_t
     return SPVO_OK;
   }
   return fail(c, SPVO_ERR_INVALID, "no layer of the loaded engine is timed under that stage name");
+}
+
+int spvo_profile_stage_variant(spvo_ctx *c, const char *stage, int info[7]) {
+  if (!c || !stage || !info) return fail(c, SPVO_ERR_INVALID, "null argument");
+  for (size_t i = 0; i < c->ops.size(); ++i) {
+    const Op &op = c->ops[i];
+    if (op.type != OP_CONV || op.stage < 0 || op.stage >= (int)c->stages.size() || c->stages[op.stage].name != stage) continue;
+    for (int q = 0; q < 7; ++q) info[q] = 0;
+    const bool in_heads = c->heads_fused && i >= c->head_start;
+    // (the layers that run no instance of the tiled kernels: spvo_net_*.hip, launch_conv*)
+    if (op.cin > 1 && !op.merged && !op.wino && !op.wino4 && op.fused_dw < 0 && !op.fused_away && !in_heads) {
+      info[0] = op.ks; info[1] = op.ck; info[2] = op.wr; info[3] = op.wc; info[4] = (op.flags & FLAG_POOL) ? 1 : 0;
+      info[5] = op.launch_tiles; info[6] = op.launch_wgs;
+    }
+    return SPVO_OK;
+  }
+  return fail(c, SPVO_ERR_INVALID, "no convolution of the loaded engine is timed under that stage name");
 }
 
 }  // extern "C"

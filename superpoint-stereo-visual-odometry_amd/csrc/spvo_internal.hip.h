@@ -87,6 +87,7 @@ struct Op {
   float inv_s_out = 0.f, s_res = 0.f;
   double flops_per_image = 0;
   int stage = -1;
+  mutable int launch_tiles = 0, launch_wgs = 0;   // tiled kernels: tiles and workgroups of this op's most recent launch (spvo_profile_stage_variant)
 };
 
 struct Stage {
@@ -283,6 +284,7 @@ struct spvo_ctx {
   bool split_req = false;          // spvo_set_fp32_split / SPVO_FP32_SPLIT: FP32 engines loaded from now on run on the bf16x3 kernels
   bool s3 = false;                 // the loaded FP32 engine runs in split mode
   size_t head_start = 0;           // ops [head_start, end) = the 1x1 heads + L2 norm: a submission runs them on the tail stream
+  int launch_tiles = 0, launch_wgs = 0;   // what the tiled kernels' launchers (launch_conv*_instance) last enqueued; launch_op copies them to its op
   // launch segments replayed from HIP graphs (launch_segments.hip.h; the entries are the sets': SubmitSet::seg_*): on for FP16 / INT8 engines (tuning "graphs": 0 off, 2 on for every engine)
   bool use_graphs = false;
   LaunchRecorder rec;

@@ -23,6 +23,7 @@ int launch_conv_instance(spvo_ctx *c, ConvArgs args, hipStream_t stream) {
   // persistent grid: what the chip holds at once; each workgroup walks tiles with that stride
   const int n_tiles = args.tiles_x * args.tiles_y * args.co_tiles * args.batch;
   const int grid = std::min(n_tiles, c->num_cus * per_cu[dev]);
+  c->launch_tiles = n_tiles; c->launch_wgs = grid;
   hipLaunchKernelGGL(k, dim3(grid), dim3(256), T::LDS_BYTES, stream, args);
   HIP_TRY(c, hipGetLastError());
   return SPVO_OK;
@@ -227,8 +228,11 @@ int launch_op(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t stream
       return launch_conv8(c, op, img0, batch, stream);
     }
     ScopedStage st(c, op.stage, op.flops_per_image * batch, bytes, stream);
-    return c->int8 ? launch_conv8(c, op, img0, batch, stream) : c->fp16 ? launch_conv16(c, op, img0, batch, stream)
-           : c->s3 ? launch_conv_s3(c, op, img0, batch, stream) : launch_conv(c, op, img0, batch, stream);
+    c->launch_tiles = c->launch_wgs = 0;
+    const int rc = c->int8 ? launch_conv8(c, op, img0, batch, stream) : c->fp16 ? launch_conv16(c, op, img0, batch, stream)
+                   : c->s3 ? launch_conv_s3(c, op, img0, batch, stream) : launch_conv(c, op, img0, batch, stream);
+    op.launch_tiles = c->launch_tiles; op.launch_wgs = c->launch_wgs;   // (spvo_profile_stage_variant; 0, 0 from the launchers of other kernels)
+    return rc;
   }
   const float *tin = ring_ptr(c, ti, img0);
   float *tout = ring_ptr(c, to, img0);

@@ -20,7 +20,8 @@ int launch_conv_s3_instance(spvo_ctx *c, ConvArgsS3 args, hipStream_t stream) {
   args.tiles_x = (args.W + T::TW - 1) / T::TW;
   args.tiles_y = (args.H + T::TH - 1) / T::TH;
   const int n_tiles = args.tiles_x * args.tiles_y * args.co_tiles * args.batch;
-  hipLaunchKernelGGL(k, dim3(std::min(n_tiles, c->num_cus * per_cu[dev])), dim3(256), T::LDS_BYTES, stream, args);
+  c->launch_tiles = n_tiles; c->launch_wgs = std::min(n_tiles, c->num_cus * per_cu[dev]);
+  hipLaunchKernelGGL(k, dim3(c->launch_wgs), dim3(256), T::LDS_BYTES, stream, args);
   HIP_TRY(c, hipGetLastError());
   return SPVO_OK;
 }

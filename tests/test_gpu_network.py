@@ -379,7 +379,7 @@ def test_fp16_engine_matches_fp16_oracle(graph, H, W, batch, vgg_plan, squeeze_p
 @pytest.mark.parametrize("graph,H,W,batch", [("mbv1", 192, 640, 2), ("mbv2", 192, 640, 2), ("mbv1", 360, 1176, 2), ("vgg", 120, 392, 2)])
 def test_int8_engine_is_bit_exact(graph, H, W, batch, vgg_plan, sample_images, tmp_path):
     """BASELINE config 5: INT8 engines.  The arithmetic is defined by oracle/net_int8.py (exact int32 accumulation,
-    separately rounded fp32 multiply / add in the requantisation), so every int8 tensor and the fp32 detector
+    then ONE fp32 fused multiply-add per requantisation with 1 / s_out folded into its constants), so every int8 tensor and the fp32 detector
     output must agree with the oracle BIT FOR BIT; only the L2-normalised descriptors (a float reduction whose
     order differs) carry a tolerance, 1e-5."""
     import copy, os
