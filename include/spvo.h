@@ -551,6 +551,47 @@ int spvo_akaze_detect_pair(spvo_ctx *ctx, const uint8_t *img_l, const uint8_t *i
 typedef struct { int32_t level, row, col; float response; int32_t ok; } spvo_akaze_candidate;
 int spvo_akaze_suppress_debug(spvo_ctx *ctx, int rows, int cols, const spvo_akaze_candidate *cand, int n,
                               int32_t *keep /* [n] */, int *n_keep);
+/* The three binary pairs whose detector reports an octave and whose extractor is another algorithm's, pair-resident: BRISK + ORB,
+ * AKAZE + ORB (both with the octave-aware ORB extractor of spvo_orb_describe_octaves) and AKAZE + BRISK.  Each follows
+ * spvo_brisk_detect_pair / spvo_akaze_detect_pair in protocol -- the pinned staging, the left image's chain then the right's on the
+ * solver's stream, one wait, the ring of ten BINARY slots, spvo_match_hamming_slots, spvo_classic_slot_rows, spvo_set_prematch,
+ * SPVO_ERR_CAPACITY with both counts and both slots left unfilled, re-allocation by a larger slot_capacity than any before -- and the
+ * temporal partner is any filled slot of the same row width: a slot of 32-byte rows that spvo_classic_detect(ORB / GFTT+ORB / FAST+ORB)
+ * filled partners with an ORB pair's, a slot spvo_brisk_detect_pair filled with spvo_akaze_brisk_pair's; another width is skipped.
+ * Afterwards the resident image (AKAZE: and the scale space) is the RIGHT image's.  Per image the host receives, byte for byte:
+ *   spvo_brisk_orb_pair    spvo_brisk_detect(img, threshold, octaves), then spvo_orb_describe_octaves(img = NULL, its x, y, octave):
+ *                          the records kp[kept] with `angle` = the extractor's radians, the 32-byte rows in `kept` order, n = n_kept
+ *   spvo_akaze_orb_pair    spvo_akaze_detect(img, threshold), then the same
+ *   spvo_akaze_brisk_pair  spvo_akaze_detect(img, threshold), then spvo_brisk_describe(img = NULL, its x, y, size): the records kp[kept]
+ *                          with `angle` = the extractor's degrees, class_id and octave unchanged, the 64-byte rows
+ * The slot's own records hold (x, y, that angle, response, octave).  The ORB pairs replace the host steps of spvo_orb_describe_octaves by
+ * a link on the device: one workgroup reads the detector's list where it lies (BRISK: the keep flag applies), applies the border rule at
+ * level 0 and groups the survivors by octave, stable, in two walks; levels 1 .. max_octave are built and levels 0 .. max_octave smoothed
+ * whether a keypoint names them or not (max_octave: 5 for BRISK, the octave of the shape's last level for AKAZE -- the host does not know
+ * the counts); the describe kernel reads the row count on the device.  spvo_akaze_brisk_pair presents the records the suppression kept to
+ * spvo_brisk_detect_pair's compaction, describe and finishing launches.
+ *   SPVO_ERR_INVALID   what the sibling refuses (spvo_brisk_orb_pair: octaves != 3 too); the ORB pairs: level max_octave of the shape is
+ *                      smaller than 32 in a dimension (the text names the level and its size) -- in the place of the per-keypoint
+ *                      refusal of spvo_orb_describe_octaves, which the host can no longer evaluate.  Decided before anything is touched.
+ *   SPVO_ERR_STATE, SPVO_ERR_CAPACITY  as the siblings */
+int spvo_brisk_orb_pair(spvo_ctx *ctx, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride,
+                        int threshold, int octaves, int slot_l, int slot_r, int slot_capacity,
+                        spvo_brisk_features *out_l, spvo_brisk_features *out_r);   /* desc [cap][32] */
+int spvo_akaze_orb_pair(spvo_ctx *ctx, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride,
+                        float threshold, int slot_l, int slot_r, int slot_capacity,
+                        spvo_akaze_features *out_l, spvo_akaze_features *out_r);   /* desc [cap][32] */
+int spvo_akaze_brisk_pair(spvo_ctx *ctx, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride,
+                          float threshold, int slot_l, int slot_r, int slot_capacity,
+                          spvo_akaze_features *out_l, spvo_akaze_features *out_r);   /* desc [cap][64] */
+/* The ORB pairs' device link and describe kernel on a caller's list against the image already resident (test hook: images do not reach
+ * octaves that do not ascend along the list, octaves 6 and 7, or keep flags between survivors).  No detector runs, no slot is touched, the
+ * image stays resident.  The outputs equal spvo_orb_describe_octaves(img = NULL) on the list without its keep == 0 records (keep = NULL:
+ * all take part), with `kept` naming the original indices.  SPVO_ERR_INVALID for max_octave outside 0 .. 7, an octave outside
+ * 0 .. max_octave, a coordinate that is not finite, and a level max_octave smaller than 32 in a dimension; SPVO_ERR_STATE without a
+ * resident image of that shape or beside a spvo_detect*_submit in flight. */
+int spvo_orb_octaves_link_debug(spvo_ctx *ctx, int rows, int cols, const float *xy /* [n][2] */, const int32_t *octave /* [n] */,
+                                const uint8_t *keep /* [n] or NULL */, int n, int max_octave,
+                                int32_t *kept /* [n] */, float *angle /* [n], may be NULL */, uint8_t *desc /* [n][32] */, int *n_kept);
 /* rows a binary feature slot holds; SPVO_ERR_STATE for one that holds nothing (never filled, or left unfilled by SPVO_ERR_CAPACITY) */
 int spvo_classic_slot_rows(spvo_ctx *ctx, int slot, int *n);
 /* Caller-supplied rows into a binary slot (test hook: images cannot produce the rows the matcher's key layout has to survive --

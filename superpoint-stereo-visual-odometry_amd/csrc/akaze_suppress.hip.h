@@ -237,4 +237,37 @@ __global__ __launch_bounds__(256) void akaze_pair_finish_kernel(const int *__res
   for (int i = tid; i < n * 61; i += nth) h_desc[i] = desc[i];
 }
 
+// spvo_akaze_brisk_pair: the records the compaction kept, presented as a BRISK detector's list to brisk_pair_chain_enqueue -- 24-byte
+// records (x, y, size, response, octave) with every keep flag set, and its counter block (1: the list's length, 3: the overflow flag of
+// the candidate list).  A record's `angle` word carries the level (class_id) as integer bits: the chain copies the word untouched into its
+// compacted record, its own mirror and the slot take the extractor's angle, and akaze_brisk_finish_kernel reads the level back.
+__global__ __launch_bounds__(256) void akaze_present_brisk_kernel(const int *__restrict__ stat, int cand_cap, const int *__restrict__ cnt, const AkazeKp *__restrict__ kp, int cap,
+                                                                  BriskDetKeypoint *__restrict__ rec, int *__restrict__ keep, int *__restrict__ det_counters) {
+  const int n = min(max(cnt[AKAZE_SUP_KEPT], 0), cap);
+  const int tid = blockIdx.x * 256 + threadIdx.x, nth = gridDim.x * 256;
+  if (tid == 0) {
+    det_counters[0] = 0; det_counters[1] = n; det_counters[2] = 0;
+    det_counters[3] = stat[AKAZE_STAT_OVERFLOW] || stat[AKAZE_STAT_NCAND] > cand_cap;
+  }
+  for (int i = tid; i < n; i += nth) {
+    const AkazeKp r = kp[i];
+    rec[i] = BriskDetKeypoint{r.x, r.y, r.size, __int_as_float(r.class_id), r.response, r.octave};
+    keep[i] = 1;
+  }
+}
+
+// ... and the last launch of an image in that chain, behind brisk_pair_finish_kernel: the host's 28-byte records -- the detector's, with the
+// extractor's angle (degrees) in place of 0 -- for the rows the slot holds, and the contrast factors
+__global__ __launch_bounds__(256) void akaze_brisk_finish_kernel(const int *__restrict__ stat, const int *__restrict__ ext_cnt, const BriskDetKeypoint *__restrict__ crec,
+                                                                 const float *__restrict__ angle, int cap, int *__restrict__ h_k, AkazeKp *__restrict__ h_kp) {
+  const int n = min(ext_cnt[0], cap);
+  const int tid = blockIdx.x * 256 + threadIdx.x, nth = gridDim.x * 256;
+  if (tid == 0)
+    for (int o = 0; o < AKAZE_MAX_OCTAVES; ++o) h_k[o] = stat[AKAZE_STAT_K + o];
+  for (int i = tid; i < n; i += nth) {
+    const BriskDetKeypoint r = crec[i];
+    h_kp[i] = AkazeKp{r.x, r.y, r.size, angle[i], r.response, r.octave, __float_as_int(r.angle)};
+  }
+}
+
 }  // namespace spvo

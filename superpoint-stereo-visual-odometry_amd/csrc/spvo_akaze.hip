@@ -3,7 +3,8 @@
 // order-dependent suppression between candidates on the host (rule 11: the restatement's loop over the copied candidate list), the
 // test hooks, spvo_akaze_describe (akaze_mldb.hip.h: orientation and MLDB descriptor on the scale space that chain leaves resident), and
 // spvo_akaze_detect_pair (detector + descriptor of a stereo pair in one submission into two binary slots of 61-byte rows, by
-// spvo_classic_detect's resident-pair protocol, with rule 11 on the device: akaze_suppress.hip.h).
+// spvo_classic_detect's resident-pair protocol, with rule 11 on the device: akaze_suppress.hip.h; spvo_akaze_orb_pair and
+// spvo_akaze_brisk_pair: the same call with the octave-aware ORB extractor or the BRISK extractor behind rule 11).
 // Runs on the solver's stream (stream2) with the image resident in spvo_ctx::cls -- it stays there for a spvo_brisk_describe(img = NULL)
 // that follows -- and owns everything else it needs (spvo_ctx::akaze).
 #include "spvo_internal.hip.h"
@@ -318,6 +319,26 @@ int ak_sup_ensure(spvo_ctx *c, int n) {
   return SPVO_OK;
 }
 
+// spvo_akaze_brisk_pair: the BRISK extractor's tables and buffers for `cap` rows of a rows x cols image, and the lists that present the
+// suppression's survivors to it (ak_sup_ensure has run: as many records as the suppression can keep, and no fewer than `cap`)
+int ak_brisk_ensure(spvo_ctx *c, int rows, int cols, int cap) {
+  auto &d = c->akaze;
+  if (int rc = brisk_chain_ensure(c, rows, cols, cap)) return rc;
+  const int n = std::max(d.sup_cap, cap);
+  if (!d.brk_cnt) {
+    if (int rc = dev_alloc(c, &d.brk_cnt, 4)) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
+  }
+  if (n <= d.brk_cap) return SPVO_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream2));
+  dev_free(d.brk_rec, d.brk_crec, d.brk_keep);
+  d.brk_cap = 0;
+  int rc;
+  if ((rc = dev_alloc(c, &d.brk_rec, (size_t)n, false)) || (rc = dev_alloc(c, &d.brk_crec, (size_t)n, false)) || (rc = dev_alloc(c, &d.brk_keep, (size_t)n, false))) return rc;
+  d.brk_cap = n;
+  return SPVO_OK;
+}
+
 // rule 11 and rule 13's flag on the device: the candidates rec[0 .. min(*n_ptr, cap)) -> sup_kp / sup_src, their number in
 // sup_cnt[AKAZE_SUP_KEPT] (ak_sup_ensure(cap) has run; only esigma of lv's levels is read)
 void ak_suppress_enqueue(spvo_ctx *c, const AkazeLevels &lv, const AkazeCand *rec, const int *n_ptr, int cap) {
@@ -331,8 +352,8 @@ void ak_suppress_enqueue(spvo_ctx *c, const AkazeLevels &lv, const AkazeCand *re
 
 void spvo_int::akaze_release(spvo_ctx *c) {
   auto &d = c->akaze;
-  dev_free(d.planes, d.scratch, d.tabs, d.keys, d.rank, d.rec, d.stat, d.d_kp, d.d_angle, d.d_desc, d.sup_list, d.sup_idx, d.sup_keep, d.sup_src, d.sup_cnt, d.sup_kp);
-  d.plane_cap = d.scratch_cap = d.tab_cap = 0; d.cand_cap = d.kp_cap = d.sup_cap = 0; d.rows = d.cols = 0; d.valid = false;
+  dev_free(d.planes, d.scratch, d.tabs, d.keys, d.rank, d.rec, d.stat, d.d_kp, d.d_angle, d.d_desc, d.sup_list, d.sup_idx, d.sup_keep, d.sup_src, d.sup_cnt, d.sup_kp, d.brk_rec, d.brk_crec, d.brk_keep, d.brk_cnt);
+  d.plane_cap = d.scratch_cap = d.tab_cap = 0; d.cand_cap = d.kp_cap = d.sup_cap = d.brk_cap = 0; d.rows = d.cols = 0; d.valid = false;
 }
 
 extern "C" {
@@ -513,8 +534,14 @@ int spvo_akaze_suppress_debug(spvo_ctx *c, int rows, int cols, const spvo_akaze_
 // chain up to akaze_refine_kernel, rule 11 on the device, the descriptor on the compacted records and a finishing kernel, image by image
 // in stream order.  The scale space, the candidate lists, the suppression's lists and the descriptor's buffers are the left image's first
 // and the right image's afterwards: an image's finishing kernel has put its counts into the pinned h_n before the next image's clear.
-int spvo_akaze_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, float threshold, int slot_l, int slot_r, int slot_capacity,
-                           spvo_akaze_features *out_l, spvo_akaze_features *out_r) {
+// The extractor behind rule 11 is the call's: MLDB (spvo_akaze_detect_pair, 61-byte rows), the octave-aware ORB extractor on the kept
+// records (spvo_akaze_orb_pair: orb_link.hip.h through spvo_classic.hip, 32-byte rows), or the BRISK extractor (spvo_akaze_brisk_pair:
+// the kept records presented to brisk_pair_chain_enqueue as a detector's list, 64-byte rows).
+}  // extern "C"
+namespace {
+enum class AkExtract { Mldb, Orb, Brisk };
+int akaze_pair(spvo_ctx *c, const char *who, AkExtract ex, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, float threshold, int slot_l, int slot_r,
+               int slot_capacity, spvo_akaze_features *out_l, spvo_akaze_features *out_r) {
   if (!c || !img_l || !img_r || !out_l || !out_r || rows <= 0 || cols <= 0 || stride < (size_t)cols) return fail(c, SPVO_ERR_INVALID, "bad argument");
   if (slot_l < 0 || slot_l >= N_BIN_SLOTS || slot_r < 0 || slot_r >= N_BIN_SLOTS || slot_l == slot_r) return fail(c, SPVO_ERR_INVALID, "bad slot");
   spvo_akaze_features *const outs[2] = {out_l, out_r};
@@ -522,7 +549,11 @@ int spvo_akaze_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img
     if (o->cap < 0) return fail(c, SPVO_ERR_INVALID, "bad output buffer");
   const int cap = slot_capacity;
   if (cap <= 0 || cap > (1 << HAM_KEY_SHIFT)) return fail(c, SPVO_ERR_INVALID, "slot_capacity must be 1 .. %d", 1 << HAM_KEY_SHIFT);
-  if (int rc = ak_check(c, "spvo_akaze_detect_pair", rows, cols, threshold)) return rc;
+  if (int rc = ak_check(c, who, rows, cols, threshold)) return rc;
+  // a kept record's octave is at most that of the shape's last level
+  const int max_octave = ex == AkExtract::Orb ? ((c->akaze.rows == rows && c->akaze.cols == cols) ? c->akaze.octaves : make_tables(rows, cols).octaves) - 1 : 0;
+  if (ex == AkExtract::Orb)
+    if (int rc = orb_link_check(c, who, rows, cols, max_octave)) return rc;
   if (int rc = require_idle(c)) return rc;
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   out_l->n = out_r->n = 0;
@@ -531,11 +562,12 @@ int spvo_akaze_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img
   auto &b = c->cls;
   auto &d = c->akaze;
   PairStage &ps = bb.pair;
-  constexpr int row_bytes = AKAZE_MLDB_BYTES;
+  const int row_bytes = ex == AkExtract::Mldb ? AKAZE_MLDB_BYTES : ex == AkExtract::Orb ? 32 : 64;
   const size_t px = (size_t)rows * cols;
   // every allocation before the first launch of the chain; the image buffer before the layout of its shape
   int rc;
-  if ((rc = classic_slots_ensure(c, cap, px)) || (rc = classic_image_ensure(c, rows, cols)) || (rc = ak_ensure(c, rows, cols)) || (rc = ak_sup_ensure(c, d.cand_cap)) || (rc = ak_kp_ensure(c, cap)))
+  if ((rc = classic_slots_ensure(c, cap, px)) || (rc = classic_image_ensure(c, rows, cols)) || (rc = ak_ensure(c, rows, cols)) || (rc = ak_sup_ensure(c, d.cand_cap)) ||
+      (rc = ex == AkExtract::Mldb ? ak_kp_ensure(c, cap) : ex == AkExtract::Orb ? orb_link_ensure(c, rows, cols, cap) : ak_brisk_ensure(c, rows, cols, cap)))
     return rc;
   // both slots are being rewritten: whatever was matched against their old contents is stale
   const int slots[2] = {slot_l, slot_r};
@@ -563,13 +595,29 @@ int spvo_akaze_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img
     hipLaunchKernelGGL(akaze_refine_kernel, dim3(32), blk, 0, st, lv, d.keys, d.rank, d.cand_cap, d.stat, d.rec);
     // rule 11, then the descriptor on what it leaves, the count read on the device
     ak_suppress_enqueue(c, lv, d.rec, d.stat + AKAZE_STAT_NCAND, d.cand_cap);
-    hipLaunchKernelGGL(akaze_describe_kernel, dim3(std::min(cap, 4096)), dim3(64), 0, st, lv, d.sup_kp, cap, d.sup_cnt + AKAZE_SUP_KEPT, d.d_angle, d.d_desc);
-    hipLaunchKernelGGL(akaze_pair_finish_kernel, dim3(32), blk, 0, st, d.stat, d.cand_cap, d.sup_cnt, d.sup_kp, d.d_angle, d.d_desc, cap, s.d_kp, s.d_desc, s.d_n, bb.h_n + 4 * k, bb.h_n + 8 + 4 * k,
-                       bb.h_akp + (size_t)k * cap, bb.h_desc + (size_t)k * cap * row_bytes);
+    int *h_n = bb.h_n + 4 * k, *h_k = bb.h_n + 8 + 4 * k;
+    AkazeKp *h_akp = bb.h_akp + (size_t)k * cap;
+    uint8_t *h_desc = bb.h_desc + (size_t)k * cap * row_bytes;
+    if (ex == AkExtract::Mldb) {
+      hipLaunchKernelGGL(akaze_describe_kernel, dim3(std::min(cap, 4096)), dim3(64), 0, st, lv, d.sup_kp, cap, d.sup_cnt + AKAZE_SUP_KEPT, d.d_angle, d.d_desc);
+      hipLaunchKernelGGL(akaze_pair_finish_kernel, dim3(32), blk, 0, st, d.stat, d.cand_cap, d.sup_cnt, d.sup_kp, d.d_angle, d.d_desc, cap, s.d_kp, s.d_desc, s.d_n, h_n, h_k, h_akp, h_desc);
+    } else if (ex == AkExtract::Orb) {
+      static_assert(offsetof(AkazeKp, x) == 0 && offsetof(AkazeKp, y) == 4 && offsetof(AkazeKp, octave) == 20, "record layout");
+      const OrbLinkSrc src{reinterpret_cast<const char *>(d.sup_kp), (int)sizeof(AkazeKp), 0, 4, 20, nullptr, d.sup_cnt + AKAZE_SUP_KEPT, d.sup_cap};
+      if ((rc = orb_link_enqueue(c, rows, cols, max_octave, src, cap, reinterpret_cast<uint8_t *>(s.d_desc)))) return rc;
+      orb_link_finish_akaze(c, d.sup_kp, d.stat, d.cand_cap, cap, s.d_kp, s.d_desc, s.d_n, h_n, h_k, h_akp, h_desc);
+    } else {
+      // the kept records as a BRISK detector's list, every keep flag set; the tested compaction, describe and finishing launches follow
+      // (their 24-byte mirror goes to h_bkp and is not handed out), then the 28-byte mirror
+      hipLaunchKernelGGL(akaze_present_brisk_kernel, dim3(32), blk, 0, st, d.stat, d.cand_cap, d.sup_cnt, d.sup_kp, d.brk_cap, d.brk_rec, d.brk_keep, d.brk_cnt);
+      const ChainOut out{bb.d_cnt + k * BIN_COUNTER_INTS, bb.d_kresp, s.d_kp, s.d_desc, s.d_n, h_n, nullptr, h_desc};
+      if ((rc = brisk_pair_chain_enqueue(c, rows, cols, cap, d.brk_rec, d.brk_keep, d.brk_cnt, d.brk_cap, d.brk_crec, out, bb.h_bkp + (size_t)k * cap))) return rc;
+      hipLaunchKernelGGL(akaze_brisk_finish_kernel, dim3(32), blk, 0, st, d.stat, out.cnt, d.brk_crec, c->brisk.angle, cap, h_k, h_akp);
+    }
     HIP_TRY(c, hipGetLastError());
   }
   HIP_TRY(c, hipEventRecord(ps.ev_feat, st));
-  // spvo_set_prematch, as spvo_classic_detect: any filled slot of 61-byte rows is a temporal partner, a slot of another width is skipped
+  // spvo_set_prematch, as spvo_classic_detect: any filled slot of the same row width is a temporal partner, a slot of another width is skipped
   const int prev = ps.last_slot_l;
   const int partner[2] = {slot_r, ps.temporal_partner(slot_l, slot_r, prev >= 0 && bb.slots[prev].filled && bb.slots[prev].row_bytes == row_bytes)};
   if (c->prematch) {
@@ -582,14 +630,13 @@ int spvo_akaze_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img
   ps.last_slot_l = -1;   // (forgotten AFTER the wait, as spvo_classic_detect: a call that failed before it leaves the partner it found)
   for (int k = 0; k < 2; ++k) outs[k]->n = bb.h_n[4 * k];
   // (the list holds every strict maximum the borders leave room for, so the flag cannot be set; were it, the counts would be wrong)
-  if (bb.h_n[1] || bb.h_n[5]) return fail(c, SPVO_ERR_STATE, "spvo_akaze_detect_pair: the candidate list overflowed although it is sized from the image");
+  if (bb.h_n[1] || bb.h_n[5]) return fail(c, SPVO_ERR_STATE, "%s: the candidate list overflowed although it is sized from the image", who);
   {   // the right image's scale space is resident (ak_mark_resident: the contrast factors sit where stat keeps them)
     int stat[AKAZE_STAT_HIST] = {0};
     std::memcpy(&stat[AKAZE_STAT_K], bb.h_n + 8 + 4, AKAZE_MAX_OCTAVES * sizeof(int));
     ak_mark_resident(c, stat);
   }
-  if (outs[0]->n > cap || outs[1]->n > cap)
-    return fail(c, SPVO_ERR_CAPACITY, "spvo_akaze_detect_pair: %d / %d rows do not fit slots of %d (slot_capacity)", outs[0]->n, outs[1]->n, cap);
+  if (outs[0]->n > cap || outs[1]->n > cap) return fail(c, SPVO_ERR_CAPACITY, "%s: %d / %d rows do not fit slots of %d (slot_capacity)", who, outs[0]->n, outs[1]->n, cap);
   static_assert(sizeof(spvo_akaze_keypoint) == sizeof(AkazeKp), "record layout");
   for (int k = 0; k < 2; ++k) {
     BinarySlot &s = bb.slots[slots[k]];
@@ -604,6 +651,27 @@ int spvo_akaze_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img
         ps.mcache.record(k, slot_l, partner[k], bb.slots[slot_l].gen, bb.slots[partner[k]].gen, c->pm_selector, c->pm_cross, c->pm_ratio, bb.h_match + (size_t)k * cap);
   ps.last_slot_l = slot_l;
   return SPVO_OK;
+}
+}  // namespace
+extern "C" {
+
+int spvo_akaze_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, float threshold, int slot_l, int slot_r, int slot_capacity,
+                           spvo_akaze_features *out_l, spvo_akaze_features *out_r) {
+  return akaze_pair(c, "spvo_akaze_detect_pair", AkExtract::Mldb, img_l, img_r, rows, cols, stride, threshold, slot_l, slot_r, slot_capacity, out_l, out_r);
+}
+
+// The AKAZE detector with the ORB extractor at the keypoints' octaves, pair-resident: per image what spvo_akaze_detect followed by
+// spvo_orb_describe_octaves(img = NULL) hands out, byte for byte, in slots of 32-byte rows
+int spvo_akaze_orb_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, float threshold, int slot_l, int slot_r, int slot_capacity,
+                        spvo_akaze_features *out_l, spvo_akaze_features *out_r) {
+  return akaze_pair(c, "spvo_akaze_orb_pair", AkExtract::Orb, img_l, img_r, rows, cols, stride, threshold, slot_l, slot_r, slot_capacity, out_l, out_r);
+}
+
+// The AKAZE detector with the BRISK extractor, pair-resident: per image what spvo_akaze_detect followed by spvo_brisk_describe(img = NULL)
+// on its x, y, size hands out, byte for byte, in slots of 64-byte rows
+int spvo_akaze_brisk_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, float threshold, int slot_l, int slot_r, int slot_capacity,
+                          spvo_akaze_features *out_l, spvo_akaze_features *out_r) {
+  return akaze_pair(c, "spvo_akaze_brisk_pair", AkExtract::Brisk, img_l, img_r, rows, cols, stride, threshold, slot_l, slot_r, slot_capacity, out_l, out_r);
 }
 
 int spvo_akaze_tables(int rows, int cols, int *levels, int32_t *octave, float *esigma, int32_t *sigma_size, int32_t *nsteps, float *tau, int tau_cap, int *n_tau, float *g0, float *g1) {

@@ -1,7 +1,7 @@
 // spvo_brisk_detect.hip -- the classic front end's BRISK keypoint detector (brisk_detect.hip.h): the layout of the six layers and the area
 // taps of a shape (built on the host in double, by the formulas tests/brisk_detect_ref.py lists), spvo_brisk_detect,
 // spvo_brisk_detect_debug_layer and spvo_brisk_detect_pair (detector + extractor of a stereo pair in one submission into two binary slots,
-// by spvo_classic_detect's resident-pair protocol).  Runs on the solver's stream (stream2) with the image resident in spvo_ctx::cls as
+// by spvo_classic_detect's resident-pair protocol; spvo_brisk_orb_pair: the same call with the octave-aware ORB extractor behind the detector).  Runs on the solver's stream (stream2) with the image resident in spvo_ctx::cls as
 // layer 0 -- it stays there for a spvo_brisk_describe(img = NULL) that follows -- and owns everything else it needs (spvo_ctx::brisk_det).
 #include "spvo_internal.hip.h"
 #include "brisk_detect.hip.h"
@@ -197,8 +197,13 @@ int spvo_brisk_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_
 // up to brisk_refine_kernel and the extractor behind it (brisk_pair_chain_enqueue), image by image in stream order.  The scale space, the
 // candidate lists, the integral image, the extractor's lists and the detector's counter block are the left image's first and the right
 // image's afterwards: an image's finishing kernel has put its counts into the pinned h_n before the next image's clear.
-int spvo_brisk_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int threshold, int octaves, int slot_l, int slot_r,
-                           int slot_capacity, spvo_brisk_features *out_l, spvo_brisk_features *out_r) {
+// orb = true (spvo_brisk_orb_pair): the extractor behind the detector is the octave-aware ORB one (orb_link.hip.h through spvo_classic.hip)
+// on the records where brisk_refine_kernel left them, rows of 32 bytes; everything else is the same call.
+}  // extern "C"
+namespace {
+constexpr int BRISK_ORB_MAX_OCTAVE = BRISK_DET_LAYERS - 1;   // a BRISK keypoint's octave is its layer, 0 .. 5
+int brisk_pair(spvo_ctx *c, const char *who, bool orb, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int threshold, int octaves, int slot_l, int slot_r,
+               int slot_capacity, spvo_brisk_features *out_l, spvo_brisk_features *out_r) {
   if (!c || !img_l || !img_r || !out_l || !out_r || rows <= 0 || cols <= 0 || stride < (size_t)cols) return fail(c, SPVO_ERR_INVALID, "bad argument");
   if (slot_l < 0 || slot_l >= N_BIN_SLOTS || slot_r < 0 || slot_r >= N_BIN_SLOTS || slot_l == slot_r) return fail(c, SPVO_ERR_INVALID, "bad slot");
   spvo_brisk_features *const outs[2] = {out_l, out_r};
@@ -206,7 +211,9 @@ int spvo_brisk_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img
     if (o->cap < 0) return fail(c, SPVO_ERR_INVALID, "bad output buffer");
   const int cap = slot_capacity;
   if (cap <= 0 || cap > (1 << HAM_KEY_SHIFT)) return fail(c, SPVO_ERR_INVALID, "slot_capacity must be 1 .. %d", 1 << HAM_KEY_SHIFT);
-  if (int rc = bd_check(c, "spvo_brisk_detect_pair", rows, cols, threshold, octaves)) return rc;
+  if (int rc = bd_check(c, who, rows, cols, threshold, octaves)) return rc;
+  if (orb)
+    if (int rc = orb_link_check(c, who, rows, cols, BRISK_ORB_MAX_OCTAVE)) return rc;
   if (int rc = require_idle(c)) return rc;
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   out_l->n = out_r->n = 0;
@@ -215,11 +222,13 @@ int spvo_brisk_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img
   auto &b = c->cls;
   auto &d = c->brisk_det;
   PairStage &ps = bb.pair;
-  constexpr int row_bytes = 64;
+  const int row_bytes = orb ? 32 : 64;
   const size_t px = (size_t)rows * cols;
   // every allocation and the 47 MB point table before the first launch of the chain; the image buffer before the layout that points into it
   int rc;
-  if ((rc = classic_slots_ensure(c, cap, px)) || (rc = classic_image_ensure(c, rows, cols)) || (rc = brisk_chain_ensure(c, rows, cols, cap)) || (rc = bd_ensure(c, rows, cols))) return rc;
+  if ((rc = classic_slots_ensure(c, cap, px)) || (rc = classic_image_ensure(c, rows, cols)) || (rc = orb ? orb_link_ensure(c, rows, cols, cap) : brisk_chain_ensure(c, rows, cols, cap)) ||
+      (rc = bd_ensure(c, rows, cols)))
+    return rc;
   // both slots are being rewritten: whatever was matched against their old contents is stale
   const int slots[2] = {slot_l, slot_r};
   for (int sl : slots) { slot_rewrite(bb.slots[sl]); bb.slots[sl].row_bytes = row_bytes; }
@@ -233,10 +242,18 @@ int spvo_brisk_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img
     b.rows = rows; b.cols = cols;
     if ((rc = bd_enqueue(c, rows, cols, threshold))) return rc;
     const ChainOut out{bb.d_cnt + k * BIN_COUNTER_INTS, bb.d_kresp, s.d_kp, s.d_desc, s.d_n, bb.h_n + 4 * k, nullptr, bb.h_desc + (size_t)k * cap * row_bytes};
-    if ((rc = brisk_pair_chain_enqueue(c, rows, cols, cap, d.rec, d.keep, d.counters, d.cand_cap, d.out, out, bb.h_bkp + (size_t)k * cap))) return rc;
+    if (!orb) {
+      if ((rc = brisk_pair_chain_enqueue(c, rows, cols, cap, d.rec, d.keep, d.counters, d.cand_cap, d.out, out, bb.h_bkp + (size_t)k * cap))) return rc;
+      continue;
+    }
+    static_assert(offsetof(BriskDetKeypoint, x) == 0 && offsetof(BriskDetKeypoint, y) == 4 && offsetof(BriskDetKeypoint, octave) == 20, "record layout");
+    const OrbLinkSrc src{reinterpret_cast<const char *>(d.rec), (int)sizeof(BriskDetKeypoint), 0, 4, 20, d.keep, d.counters + 1, d.cand_cap};
+    if ((rc = orb_link_enqueue(c, rows, cols, BRISK_ORB_MAX_OCTAVE, src, cap, reinterpret_cast<uint8_t *>(s.d_desc)))) return rc;
+    orb_link_finish_brisk(c, d.rec, d.counters, cap, s.d_kp, s.d_desc, s.d_n, out.h_n, bb.h_bkp + (size_t)k * cap, out.h_desc);
+    HIP_TRY(c, hipGetLastError());
   }
   HIP_TRY(c, hipEventRecord(ps.ev_feat, st));
-  // spvo_set_prematch, as spvo_classic_detect: any filled slot of 64-byte rows is a temporal partner, whichever entry point filled it
+  // spvo_set_prematch, as spvo_classic_detect: any filled slot of the same row width is a temporal partner, whichever entry point filled it
   const int prev = ps.last_slot_l;
   const int partner[2] = {slot_r, ps.temporal_partner(slot_l, slot_r, prev >= 0 && bb.slots[prev].filled && bb.slots[prev].row_bytes == row_bytes)};
   if (c->prematch) {
@@ -249,9 +266,8 @@ int spvo_brisk_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img
   ps.last_slot_l = -1;   // (forgotten AFTER the wait, as spvo_classic_detect: a call that failed before it leaves the partner it found)
   for (int k = 0; k < 2; ++k) outs[k]->n = bb.h_n[4 * k];
   // (the lists hold a candidate per interior pixel of every layer, so the flag cannot be set; were it, the counts would be wrong)
-  if (bb.h_n[1] || bb.h_n[5]) return fail(c, SPVO_ERR_STATE, "spvo_brisk_detect_pair: the candidate list overflowed although it is sized from the image");
-  if (outs[0]->n > cap || outs[1]->n > cap)
-    return fail(c, SPVO_ERR_CAPACITY, "spvo_brisk_detect_pair: %d / %d rows do not fit slots of %d (slot_capacity)", outs[0]->n, outs[1]->n, cap);
+  if (bb.h_n[1] || bb.h_n[5]) return fail(c, SPVO_ERR_STATE, "%s: the candidate list overflowed although it is sized from the image", who);
+  if (outs[0]->n > cap || outs[1]->n > cap) return fail(c, SPVO_ERR_CAPACITY, "%s: %d / %d rows do not fit slots of %d (slot_capacity)", who, outs[0]->n, outs[1]->n, cap);
   static_assert(sizeof(spvo_brisk_keypoint) == sizeof(BriskDetKeypoint), "record layout");
   for (int k = 0; k < 2; ++k) {
     BinarySlot &s = bb.slots[slots[k]];
@@ -266,6 +282,20 @@ int spvo_brisk_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img
         ps.mcache.record(k, slot_l, partner[k], bb.slots[slot_l].gen, bb.slots[partner[k]].gen, c->pm_selector, c->pm_cross, c->pm_ratio, bb.h_match + (size_t)k * cap);
   ps.last_slot_l = slot_l;
   return SPVO_OK;
+}
+}  // namespace
+extern "C" {
+
+int spvo_brisk_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int threshold, int octaves, int slot_l, int slot_r,
+                           int slot_capacity, spvo_brisk_features *out_l, spvo_brisk_features *out_r) {
+  return brisk_pair(c, "spvo_brisk_detect_pair", false, img_l, img_r, rows, cols, stride, threshold, octaves, slot_l, slot_r, slot_capacity, out_l, out_r);
+}
+
+// The BRISK detector with the ORB extractor at the keypoints' octaves, pair-resident: per image what spvo_brisk_detect followed by
+// spvo_orb_describe_octaves(img = NULL) hands out, byte for byte, in slots of 32-byte rows
+int spvo_brisk_orb_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int threshold, int octaves, int slot_l, int slot_r,
+                        int slot_capacity, spvo_brisk_features *out_l, spvo_brisk_features *out_r) {
+  return brisk_pair(c, "spvo_brisk_orb_pair", true, img_l, img_r, rows, cols, stride, threshold, octaves, slot_l, slot_r, slot_capacity, out_l, out_r);
 }
 
 int spvo_brisk_detect_debug_layer(spvo_ctx *c, int layer, int what, uint8_t *out, int *rows, int *cols) {

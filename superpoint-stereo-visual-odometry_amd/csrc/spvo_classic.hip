@@ -1,9 +1,11 @@
 // spvo_classic.hip -- the classic front end (ClassicFeatureFrontEnd, feature_detection_classic.cpp): the ORB detector / extractor (orb.hip.h),
 // the Shi-Tomasi and FAST detectors and the ORB extractor for given keypoints (classic_detect.hip.h; at the keypoints' octaves: spvo_orb_describe_octaves), one submission per stereo pair into the
 // binary feature slots (spvo_classic_detect; its BRISK kinds hand the detector's list to spvo_brisk.hip, and spvo_sift.hip takes the same
-// detector link for spvo_classic_sift_pair), and spvo_preprocess for a context without an engine.  Everything here runs on the solver's stream (stream2) and owns its buffers (spvo_ctx::orb, spvo_ctx::cls).
+// detector link for spvo_classic_sift_pair), the ORB extractor as a device link behind a detector that reports octaves (orb_link.hip.h: orb_link_* for
+// spvo_brisk_orb_pair / spvo_akaze_orb_pair, and the test hook spvo_orb_octaves_link_debug), and spvo_preprocess for a context without an engine.  Everything here runs on the solver's stream (stream2) and owns its buffers (spvo_ctx::orb, spvo_ctx::cls).
 #include "spvo_internal.hip.h"
 #include "orb.hip.h"
+#include "orb_link.hip.h"
 #include "classic_detect.hip.h"
 
 namespace {
@@ -556,6 +558,148 @@ int spvo_orb_describe_octaves(spvo_ctx *c, const uint8_t *img, int rows, int col
   if (angle) HIP_TRY(c, hipMemcpyAsync(angle, b.oct_angle, (size_t)nk * sizeof(float), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipMemcpyAsync(desc, b.oct_desc, (size_t)nk * 32, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));   // the one wait of the call
+  return SPVO_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the same extractor behind a detector's list on the device (orb_link.hip.h)
+namespace {
+// the link's buffers for `cap` rows (and, for the test hook, a list of `n_src` records with its keep flags)
+int orb_link_buffers(spvo_ctx *c, int cap, int n_src) {
+  auto &b = c->cls;
+  if (!b.lnk_cnt) {
+    if (int rc = dev_alloc(c, &b.lnk_cnt, ORB_LINK_INTS)) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
+  }
+  if (cap > b.lnk_cap) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream2));
+    dev_free(b.lnk_kept, b.lnk_rec, b.lnk_angle, b.lnk_desc);
+    b.lnk_cap = 0;
+    int rc;
+    if ((rc = dev_alloc(c, &b.lnk_kept, (size_t)cap, false)) || (rc = dev_alloc(c, &b.lnk_rec, (size_t)3 * cap, false)) || (rc = dev_alloc(c, &b.lnk_angle, (size_t)cap, false)) ||
+        (rc = dev_alloc(c, &b.lnk_desc, (size_t)cap * 32, false)))
+      return rc;
+    b.lnk_cap = cap;
+  }
+  if (n_src > b.lnk_src_cap) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream2));
+    dev_free(b.lnk_src, b.lnk_keep);
+    b.lnk_src_cap = 0;
+    int rc;
+    if ((rc = dev_alloc(c, &b.lnk_src, (size_t)3 * n_src, false)) || (rc = dev_alloc(c, &b.lnk_keep, (size_t)n_src, false))) return rc;
+    b.lnk_src_cap = n_src;
+  }
+  return SPVO_OK;
+}
+}  // namespace
+
+int spvo_int::orb_link_check(spvo_ctx *c, const char *who, int rows, int cols, int max_octave) {
+  if (max_octave < 0 || max_octave >= ORB_LEVELS) return fail(c, SPVO_ERR_INVALID, "%s: max_octave %d; the pyramid has levels 0 .. %d", who, max_octave, ORB_LEVELS - 1);
+  float scale = 1.f;
+  for (int l = 0; l < max_octave; ++l) scale *= 1.2f;   // (orb_prepare's geometry)
+  const int h = (int)std::lround(rows / scale), w = (int)std::lround(cols / scale);
+  if (h < ORB_MIN_LEVEL || w < ORB_MIN_LEVEL)
+    return fail(c, SPVO_ERR_INVALID, "%s: level %d of a %d x %d image is %d x %d: levels of at least %d x %d only", who, max_octave, rows, cols, h, w, ORB_MIN_LEVEL, ORB_MIN_LEVEL);
+  return SPVO_OK;
+}
+
+int spvo_int::orb_link_ensure(spvo_ctx *c, int rows, int cols, int cap) {
+  OrbPlan plan;
+  if (int rc = orb_prepare(c, rows, cols, 1, plan)) return rc;   // (no keypoint buffer of spvo_orb_detect's is used: nfeatures 1 grows none)
+  return orb_link_buffers(c, cap, 0);
+}
+
+// Smoothing: EVERY level 0 .. max_octave is built and smoothed, whether a record names it or not -- the host cannot know the counts, and a
+// level's bytes do not depend on who reads them, so the rows equal spvo_orb_describe_octaves', which skips what lies above its `top`.
+int spvo_int::orb_link_enqueue(spvo_ctx *c, int rows, int cols, int max_octave, const OrbLinkSrc &src, int cap, uint8_t *desc) {
+  auto &b = c->cls;
+  auto &o = c->orb;
+  hipStream_t st = c->stream2;
+  OrbPlan plan;
+  if (int rc = orb_prepare(c, rows, cols, 1, plan)) return rc;   // (sized by orb_link_ensure: the plan only)
+  OrbLinkGeom g{};
+  OrbLevels lv{};
+  for (int l = 0; l < ORB_LEVELS; ++l) { g.h[l] = plan.ph[l]; g.w[l] = plan.pw[l]; g.lscale[l] = plan.lscale[l]; }
+  hipLaunchKernelGGL(orb_link_group_kernel, dim3(1), dim3(1024), 0, st, src, rows, cols, std::min(max_octave, ORB_LEVELS - 1), g, cap, b.lnk_kept, b.lnk_rec, b.lnk_cnt);
+  for (int l = 0; l <= max_octave; ++l) {
+    OrbLevel &L = lv.l[l];
+    if (l == 0) { L.im = b.im; L.blur = b.blur; L.tmp = b.tmp; }
+    else { L.im = o.im + plan.off[l]; L.blur = o.blur + plan.off[l]; L.tmp = o.tmp + plan.off[l]; }
+    L.h = plan.ph[l]; L.w = plan.pw[l]; L.scale = plan.lscale[l];
+    L.want = L.cap = 1;
+    if (l > 0)
+      hipLaunchKernelGGL(orb_resize_kernel, dim3((L.w + 63) / 64, (L.h + 3) / 4), dim3(256), 0, st, lv.l[l - 1].im, plan.ph[l - 1], plan.pw[l - 1], plan.pw[l - 1], L.im, L.h, L.w,
+                         o.tab + plan.toff[l]);
+  }
+  const dim3 grid((cols + 63) / 64, (rows + 3) / 4, max_octave + 1);
+  hipLaunchKernelGGL(orb_blur_h_kernel, grid, dim3(256), 0, st, lv, o.taps);
+  hipLaunchKernelGGL(orb_blur_v_kernel, grid, dim3(256), 0, st, lv, o.taps);
+  hipLaunchKernelGGL(orb_link_describe_kernel, dim3(std::min((cap + 3) / 4, 1024)), dim3(256), 0, st, lv, b.lnk_rec, b.lnk_cnt, cap, o.disc, o.pattern, b.lnk_angle, desc);
+  HIP_TRY(c, hipGetLastError());
+  return SPVO_OK;
+}
+
+void spvo_int::orb_link_finish_brisk(spvo_ctx *c, const BriskDetKeypoint *src, const int *det_counters, int cap, OrbKeypoint *d_kp, const uint32_t *d_desc, int *d_n, int *h_n,
+                                     BriskDetKeypoint *h_kp, uint8_t *h_desc) {
+  auto &b = c->cls;
+  hipLaunchKernelGGL(orb_link_finish_kernel<BriskDetKeypoint>, dim3(32), dim3(256), 0, c->stream2, src, b.lnk_kept, b.lnk_cnt, b.lnk_angle, reinterpret_cast<const uint4 *>(d_desc), cap,
+                     det_counters, (const int *)nullptr, 0, d_kp, d_n, h_n, (int *)nullptr, h_kp, reinterpret_cast<uint4 *>(h_desc));
+}
+void spvo_int::orb_link_finish_akaze(spvo_ctx *c, const AkazeKp *src, const int *stat, int cand_cap, int cap, OrbKeypoint *d_kp, const uint32_t *d_desc, int *d_n, int *h_n, int *h_k,
+                                     AkazeKp *h_kp, uint8_t *h_desc) {
+  auto &b = c->cls;
+  hipLaunchKernelGGL(orb_link_finish_kernel<AkazeKp>, dim3(32), dim3(256), 0, c->stream2, src, b.lnk_kept, b.lnk_cnt, b.lnk_angle, reinterpret_cast<const uint4 *>(d_desc), cap,
+                     (const int *)nullptr, stat, cand_cap, d_kp, d_n, h_n, h_k, h_kp, reinterpret_cast<uint4 *>(h_desc));
+}
+
+extern "C" {
+
+// Test hook: exactly the link's kernels and the describe kernel on a caller's list against the image already resident -- no detector runs,
+// no slot is touched, the image stays.  The list goes up as 12-byte records (x, y, octave) with its keep flags as integers; its length lies
+// in the link's counter block.
+int spvo_orb_octaves_link_debug(spvo_ctx *c, int rows, int cols, const float *xy, const int32_t *octave, const uint8_t *keep, int n, int max_octave, int32_t *kept, float *angle,
+                                uint8_t *desc, int *n_kept) {
+  if (!c || !n_kept || rows <= 0 || cols <= 0 || n < 0 || (n > 0 && (!xy || !octave || !kept || !desc))) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  if (int rc = orb_link_check(c, "spvo_orb_octaves_link_debug", rows, cols, max_octave)) return rc;
+  for (int i = 0; i < n; ++i) {
+    if (octave[i] < 0 || octave[i] > max_octave)
+      return fail(c, SPVO_ERR_INVALID, "spvo_orb_octaves_link_debug: keypoint %d has octave %d; max_octave is %d", i, octave[i], max_octave);
+    if (!std::isfinite(xy[2 * i]) || !std::isfinite(xy[2 * i + 1]))
+      return fail(c, SPVO_ERR_INVALID, "spvo_orb_octaves_link_debug: keypoint %d is (%g, %g)", i, (double)xy[2 * i], (double)xy[2 * i + 1]);
+  }
+  if (int rc = require_idle(c)) return rc;
+  auto &b = c->cls;
+  if (b.rows != rows || b.cols != cols) return fail(c, SPVO_ERR_STATE, "spvo_orb_octaves_link_debug: no image of %d x %d is resident (call a detector first)", rows, cols);
+  *n_kept = 0;
+  if (n == 0) return SPVO_OK;
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = c->stream2;
+  OrbPlan plan;
+  if (int rc = orb_prepare(c, rows, cols, 1, plan)) return rc;
+  if (int rc = orb_link_buffers(c, n, n)) return rc;
+  std::vector<int> rec((size_t)3 * n), flags(keep ? (size_t)n : 0);
+  for (int i = 0; i < n; ++i) {
+    std::memcpy(&rec[3 * i], &xy[2 * i], 2 * sizeof(float));
+    rec[3 * i + 2] = octave[i];
+    if (keep) flags[i] = keep[i] ? 1 : 0;
+  }
+  HIP_TRY(c, hipMemcpyAsync(b.lnk_src, rec.data(), rec.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  if (keep) HIP_TRY(c, hipMemcpyAsync(b.lnk_keep, flags.data(), flags.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(b.lnk_cnt + ORB_LINK_N, &n, sizeof n, hipMemcpyHostToDevice, st));
+  const OrbLinkSrc src{reinterpret_cast<const char *>(b.lnk_src), 12, 0, 4, 8, keep ? b.lnk_keep : nullptr, b.lnk_cnt + ORB_LINK_N, n};
+  if (int rc = orb_link_enqueue(c, rows, cols, max_octave, src, n, b.lnk_desc)) return rc;
+  int cnt[ORB_LINK_INTS];
+  HIP_TRY(c, hipMemcpyAsync(cnt, b.lnk_cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  const int m = std::min(std::max(cnt[ORB_LINK_TOTAL], 0), n);
+  if (m > 0) {
+    HIP_TRY(c, hipMemcpyAsync(kept, b.lnk_kept, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (angle) HIP_TRY(c, hipMemcpyAsync(angle, b.lnk_angle, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(desc, b.lnk_desc, (size_t)m * 32, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+  }
+  *n_kept = m;
   return SPVO_OK;
 }
 

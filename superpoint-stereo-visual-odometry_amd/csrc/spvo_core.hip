@@ -488,6 +488,7 @@ void spvo_destroy(spvo_ctx *c) {
   akaze_release(c);
   auto &b = c->cls;
   dev_free(b.im, b.score, b.blur, b.src, b.state, b.desc, b.tmp, b.lam, b.xy, b.resp, b.keys, b.rank, b.cand, b.counters, b.kp_xy, b.kps, b.oct_rec, b.oct_angle, b.oct_desc, b.pre_out, b.pre_tab);
+  dev_free(b.lnk_kept, b.lnk_rec, b.lnk_cnt, b.lnk_src, b.lnk_keep, b.lnk_angle, b.lnk_desc);
   host_free(c->h_match_tmp);
   if (c->stream_t) (void)hipStreamDestroy(c->stream_t);
   if (c->stream_tb) (void)hipStreamDestroy(c->stream_tb);

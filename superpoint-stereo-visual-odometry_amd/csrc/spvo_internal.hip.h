@@ -374,6 +374,12 @@ struct spvo_ctx {
     int *oct_rec = nullptr;               // the directions and the 32-byte rows
     float *oct_angle = nullptr;
     uint8_t *oct_desc = nullptr;
+    // the device link of orb_link.hip.h (spvo_brisk_orb_pair, spvo_akaze_orb_pair, spvo_orb_octaves_link_debug): `lnk_cap` rows of source
+    // indices, (cx, cy, level) records and directions, the counts (ORB_LINK_*), and the test hook's own list and rows
+    int lnk_cap = 0, lnk_src_cap = 0;
+    int *lnk_kept = nullptr, *lnk_rec = nullptr, *lnk_cnt = nullptr, *lnk_src = nullptr, *lnk_keep = nullptr;
+    float *lnk_angle = nullptr;
+    uint8_t *lnk_desc = nullptr;
     uint8_t *pre_out = nullptr;           // spvo_preprocess of a context without an engine (the classic front end at a fixed input size): resized image,
     int *pre_tab = nullptr;               // resize tables of the crop pre_crop_rows x pre_crop_cols
     int pre_crop_rows = 0, pre_crop_cols = 0;
@@ -467,6 +473,11 @@ struct spvo_ctx {
     float4 *sup_list = nullptr;
     int *sup_idx = nullptr, *sup_keep = nullptr, *sup_src = nullptr, *sup_cnt = nullptr;   // sup_cnt: AKAZE_SUP_*
     AkazeKp *sup_kp = nullptr;
+    // spvo_akaze_brisk_pair: the kept records as the BRISK extractor's chain reads a detector's list (brisk_pair_chain_enqueue) -- records,
+    // keep flags, the counter block, the compacted records -- `brk_cap` of each
+    int brk_cap = 0;
+    BriskDetKeypoint *brk_rec = nullptr, *brk_crec = nullptr;
+    int *brk_keep = nullptr, *brk_cnt = nullptr;
   } akaze;
   // SIFT detector + descriptor of the classic front end (sift.hip.h): the image, its pyramid (all Gaussian and DoG levels: what
   // spvo_sift_debug_level serves until the next call), the candidate and output lists; device buffers grow on demand, the host staging keeps its capacity
@@ -725,6 +736,20 @@ int classic_detector_enqueue(spvo_ctx *c, const spvo_classic_opts *opts, const u
 // cls_rank_kernel (classic_detect.hip.h) over a key list whose length lies in device memory, enqueued on the solver's stream: rank[i] += the
 // number of keys smaller than keys[i] (rank is zero between uses)
 void classic_rank_enqueue(spvo_ctx *c, const unsigned long long *keys, int *rank, const int *n_ptr, int cap);
+// The octave-aware ORB extractor as a link behind a detector that left records with an octave on the device (orb_link.hip.h;
+// spvo_brisk_orb_pair, spvo_akaze_orb_pair).  orb_link_check: refuses a shape whose level `max_octave` is smaller than the extractor
+// accepts (`who` names the entry point).  orb_link_ensure: the pyramid, its tables and the link's buffers for `cap` rows.  orb_link_enqueue,
+// on the solver's stream with the image resident in spvo_ctx::cls: border rule + stable grouping by octave, levels 1 .. max_octave, the
+// smoothing of levels 0 .. max_octave, the 32-byte rows of min(rows found, cap) records into `desc`; kept / angle / counts stay in
+// spvo_ctx::cls (lnk_*).  orb_link_finish_*: the finishing launch of an image -- slot count and records, the pinned mirrors (h_n = {rows
+// found, overflow flag of the detector}; AKAZE: the contrast factors in h_k).
+int orb_link_check(spvo_ctx *c, const char *who, int rows, int cols, int max_octave);
+int orb_link_ensure(spvo_ctx *c, int rows, int cols, int cap);
+int orb_link_enqueue(spvo_ctx *c, int rows, int cols, int max_octave, const OrbLinkSrc &src, int cap, uint8_t *desc);
+void orb_link_finish_brisk(spvo_ctx *c, const BriskDetKeypoint *src, const int *det_counters, int cap, OrbKeypoint *d_kp, const uint32_t *d_desc, int *d_n, int *h_n,
+                           BriskDetKeypoint *h_kp, uint8_t *h_desc);
+void orb_link_finish_akaze(spvo_ctx *c, const AkazeKp *src, const int *stat, int cand_cap, int cap, OrbKeypoint *d_kp, const uint32_t *d_desc, int *d_n, int *h_n, int *h_k,
+                           AkazeKp *h_kp, uint8_t *h_desc);
 // ---- spvo_brisk.hip
 void brisk_release(spvo_ctx *c);     // frees spvo_ctx::brisk (spvo_destroy)
 // what spvo_brisk_describe refuses of an image, for every entry point that runs the extractor (`who` names it in the error text)

@@ -119,4 +119,9 @@ struct AkazeKp { float x, y, size, angle, response; int32_t octave, class_id; };
 // (float bits), the histogram
 constexpr int AKAZE_STAT_NCAND = 0, AKAZE_STAT_OVERFLOW = 1, AKAZE_STAT_MAX = 2, AKAZE_STAT_K = 4, AKAZE_STAT_HIST = 8, AKAZE_STAT_INTS = AKAZE_STAT_HIST + AKAZE_NBINS;
 
+// ---- the link from a detector's record list to the octave-aware ORB extractor (orb_link.hip.h): where the list lies -- records of
+// `stride` bytes with x, y (float) and the octave (int32) at byte offsets, an optional keep flag per record, the list's length on the
+// device and what the buffer holds at most
+struct OrbLinkSrc { const char *rec; int stride, off_x, off_y, off_octave; const int *keep; const int *n_ptr; int n_cap; };
+
 }  // namespace spvo

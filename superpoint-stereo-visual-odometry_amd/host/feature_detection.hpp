@@ -353,8 +353,10 @@ public:
   // only with this as well as setAkazeDescriptor and setDeviceResident.  setSiftDescribeResident: ShiTomasi + SIFT and FAST + SIFT take
   // their route (spvo_classic_sift_pair: detector, SIFT base level and descriptor on the device, rows into the SIFT slots) only with this as
   // well as setDeviceResident; the other detectors with the SIFT extractor have no route.  setOrbExtractorOctaves: BRISK + ORB and AKAZE + ORB
-  // run (per image, no route: spvo_orb_describe_octaves on the level KeyPoint::octave names); off, both are refused as before and the
-  // refusal does not list them.
+  // run (per image: spvo_orb_describe_octaves on the level KeyPoint::octave names); off, both are refused as before and the
+  // refusal does not list them.  setOctavePairsResident: BRISK + ORB, AKAZE + ORB (both still need setOrbExtractorOctaves to run at all) and
+  // AKAZE + BRISK take their routes (spvo_brisk_orb_pair, spvo_akaze_orb_pair, spvo_akaze_brisk_pair) only with this as well as
+  // setDeviceResident; a shape an ORB pair call refuses (its top pyramid level below 32 x 32) takes the per-image path and is not counted.
   static void setDeviceResident(bool on);
   static void setResidentCapacity(int rows);   // rows per binary slot [8192]
   static void setBriskPairResident(bool on);   // [off]
@@ -362,7 +364,8 @@ public:
   static void setAkazePairResident(bool on);   // [off]
   static void setSiftDescribeResident(bool on);   // [off]
   static void setOrbExtractorOctaves(bool on);    // [off]
-  // pairs that actually stayed resident (spvo_classic_detect / spvo_sift_detect_pair / spvo_brisk_detect_pair / spvo_akaze_detect_pair / spvo_classic_sift_pair returned SPVO_OK): what tells the resident path from its fallback
+  static void setOctavePairsResident(bool on);    // [off]
+  // pairs that actually stayed resident (spvo_classic_detect / spvo_sift_detect_pair / spvo_brisk_detect_pair / spvo_akaze_detect_pair / spvo_classic_sift_pair / spvo_brisk_orb_pair / spvo_akaze_orb_pair / spvo_akaze_brisk_pair returned SPVO_OK): what tells the resident path from its fallback
   unsigned residentPairs() const { return resident_ok_pairs_; }
 
 private:
@@ -372,6 +375,7 @@ private:
   bool akaze_pair_resident_ = false;   // setAkazePairResident at construction
   bool sift_describe_resident_ = false;   // setSiftDescribeResident at construction
   bool orb_octaves_ = false;           // setOrbExtractorOctaves at construction
+  bool octave_pairs_resident_ = false;   // setOctavePairsResident at construction
   bool pairRuns() const;               // this detector / descriptor pair runs in this build
   int resident_capacity_ = 8192;
   unsigned resident_pairs_ = 0;   // pairs handed to a resident route: pair k lives in slots 2 (k % 4), 2 (k % 4) + 1

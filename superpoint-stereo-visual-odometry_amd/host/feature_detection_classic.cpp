@@ -4,6 +4,7 @@
 #include "feature_detection.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <type_traits>
 
@@ -15,12 +16,14 @@ static bool g_classic_akaze_descriptor = false;
 static bool g_classic_akaze_pair_resident = false;
 static bool g_classic_sift_describe_resident = false;
 static bool g_classic_orb_octaves = false;
+static bool g_classic_octave_pairs_resident = false;
 void ClassicFeatureFrontEnd::setDeviceResident(bool on) { g_classic_resident = on; }
 void ClassicFeatureFrontEnd::setBriskPairResident(bool on) { g_classic_brisk_pair_resident = on; }
 void ClassicFeatureFrontEnd::setAkazeDescriptor(bool on) { g_classic_akaze_descriptor = on; }
 void ClassicFeatureFrontEnd::setAkazePairResident(bool on) { g_classic_akaze_pair_resident = on; }
 void ClassicFeatureFrontEnd::setSiftDescribeResident(bool on) { g_classic_sift_describe_resident = on; }
 void ClassicFeatureFrontEnd::setOrbExtractorOctaves(bool on) { g_classic_orb_octaves = on; }
+void ClassicFeatureFrontEnd::setOctavePairsResident(bool on) { g_classic_octave_pairs_resident = on; }
 void ClassicFeatureFrontEnd::setResidentCapacity(int rows) { g_classic_resident_capacity = rows; }
 
 #ifdef SPVO_USE_OPENCV
@@ -92,8 +95,8 @@ bool ClassicFeatureFrontEnd::available() { return true; }
 
 enum class Detect { Orb, Gftt, Fast, Sift, Brisk, Akaze };       // detectKeypoints: spvo_<this>_detect
 enum class Describe { WithDetector, Orb, Brisk, Akaze, Sift };   // describeKeypoints: the rows detectKeypoints kept, or spvo_<this>_describe on the given keypoints
-enum class Route { None, Classic, SiftPair, BriskPair, AkazePair, ClassicSift };   // setDeviceResident: the per-image path, spvo_classic_detect (kind), spvo_sift_detect_pair, spvo_brisk_detect_pair, spvo_akaze_detect_pair, spvo_classic_sift_pair (kind)
-enum class OptIn { None, AkazeDescriptor, OrbOctaves, BriskPairResident, AkazePairResident, SiftDescribeResident };   // to run at all: setAkazeDescriptor, setOrbExtractorOctaves; to stay resident: setBriskPairResident, setAkazePairResident, setSiftDescribeResident
+enum class Route { None, Classic, SiftPair, BriskPair, AkazePair, ClassicSift, BriskOrbPair, AkazeOrbPair, AkazeBriskPair };   // setDeviceResident: the per-image path, spvo_classic_detect (kind), spvo_sift_detect_pair, spvo_brisk_detect_pair, spvo_akaze_detect_pair, spvo_classic_sift_pair (kind), spvo_brisk_orb_pair, spvo_akaze_orb_pair, spvo_akaze_brisk_pair
+enum class OptIn { None, AkazeDescriptor, OrbOctaves, BriskPairResident, AkazePairResident, SiftDescribeResident, OctavePairsResident };   // to run at all: setAkazeDescriptor, setOrbExtractorOctaves; to stay resident: setBriskPairResident, setAkazePairResident, setSiftDescribeResident, setOctavePairsResident
 
 struct ClassicPair {
   DetectorType detector;
@@ -115,7 +118,7 @@ static const ClassicPair kClassicPairs[] = {
     {DetectorType::ShiTomasi, DescriptorType::BRISK, Detect::Gftt, 5.f, Describe::Brisk, 64, CV_8UC1, Route::Classic, SPVO_CLASSIC_GFTT_BRISK, OptIn::None, OptIn::None},
     {DetectorType::FAST, DescriptorType::BRISK, Detect::Fast, 7.f, Describe::Brisk, 64, CV_8UC1, Route::Classic, SPVO_CLASSIC_FAST_BRISK, OptIn::None, OptIn::None},
     {DetectorType::BRISK, DescriptorType::BRISK, Detect::Brisk, 0.f, Describe::Brisk, 64, CV_8UC1, Route::BriskPair, 0, OptIn::None, OptIn::BriskPairResident},
-    {DetectorType::AKAZE, DescriptorType::BRISK, Detect::Akaze, 0.f, Describe::Brisk, 64, CV_8UC1, Route::None, 0, OptIn::None, OptIn::None},
+    {DetectorType::AKAZE, DescriptorType::BRISK, Detect::Akaze, 0.f, Describe::Brisk, 64, CV_8UC1, Route::AkazeBriskPair, 0, OptIn::None, OptIn::OctavePairsResident},
     {DetectorType::AKAZE, DescriptorType::AKAZE, Detect::Akaze, 0.f, Describe::Akaze, SPVO_AKAZE_DESC_BYTES, CV_8UC1, Route::AkazePair, 0, OptIn::AkazeDescriptor, OptIn::AkazePairResident},
     {DetectorType::SIFT, DescriptorType::SIFT, Detect::Sift, 0.f, Describe::WithDetector, 128, CV_32FC1, Route::SiftPair, 0, OptIn::None, OptIn::None},
     {DetectorType::ShiTomasi, DescriptorType::SIFT, Detect::Gftt, 5.f, Describe::Sift, 128, CV_32FC1, Route::ClassicSift, SPVO_CLASSIC_GFTT_SIFT, OptIn::None, OptIn::SiftDescribeResident},
@@ -124,8 +127,8 @@ static const ClassicPair kClassicPairs[] = {
     {DetectorType::BRISK, DescriptorType::SIFT, Detect::Brisk, 0.f, Describe::Sift, 128, CV_32FC1, Route::None, 0, OptIn::None, OptIn::None},
     {DetectorType::AKAZE, DescriptorType::SIFT, Detect::Akaze, 0.f, Describe::Sift, 128, CV_32FC1, Route::None, 0, OptIn::None, OptIn::None},
     // the ORB extractor on keypoints that carry an octave (spvo_orb_describe_octaves): only with setOrbExtractorOctaves, and listed only then
-    {DetectorType::BRISK, DescriptorType::ORB, Detect::Brisk, 0.f, Describe::Orb, 32, CV_8UC1, Route::None, 0, OptIn::OrbOctaves, OptIn::None},
-    {DetectorType::AKAZE, DescriptorType::ORB, Detect::Akaze, 0.f, Describe::Orb, 32, CV_8UC1, Route::None, 0, OptIn::OrbOctaves, OptIn::None},
+    {DetectorType::BRISK, DescriptorType::ORB, Detect::Brisk, 0.f, Describe::Orb, 32, CV_8UC1, Route::BriskOrbPair, 0, OptIn::OrbOctaves, OptIn::OctavePairsResident},
+    {DetectorType::AKAZE, DescriptorType::ORB, Detect::Akaze, 0.f, Describe::Orb, 32, CV_8UC1, Route::AkazeOrbPair, 0, OptIn::OrbOctaves, OptIn::OctavePairsResident},
 };
 
 // the row of a pair that runs, or nullptr
@@ -166,7 +169,8 @@ static float orb_degrees(float radians) {   // spvo_orb_* report radians; cv::Ke
   const float a = radians * 57.29577951308232f;
   return a < 0 ? a + 360.f : a;
 }
-static cv::KeyPoint to_keypoint(const spvo_orb_keypoint &r, const ClassicPair &p) {
+// (extracted: the record is a pair call's and carries its extractor's angle, not the detector's)
+static cv::KeyPoint to_keypoint(const spvo_orb_keypoint &r, const ClassicPair &p, bool /*extracted*/) {
   static const std::array<float, 8> level_scale = [] {   // cv::ORB::create(2000, 1.2f, 8, ..)
     std::array<float, 8> s{};
     s[0] = 1.f;
@@ -186,27 +190,28 @@ static cv::KeyPoint to_keypoint(float x, float y, float response, const ClassicP
   k.octave = 0;
   return k;
 }
-static cv::KeyPoint to_keypoint(const spvo_sift_keypoint &r, const ClassicPair &p) {   // SIFT, BRISK's records of the same layout, and spvo_classic_sift_pair's
+static cv::KeyPoint to_keypoint(const spvo_sift_keypoint &r, const ClassicPair &p, bool extracted) {   // SIFT, BRISK's records of the same layout, and spvo_classic_sift_pair's
                                                                                        // (size 5 / 7, angle -1, octave 0: what to_keypoint(x, y, response, p) builds)
   cv::KeyPoint k(cv::Point2f(r.x, r.y), r.size);
-  // a BRISK keypoint keeps the angle its detector reports, -1; the record of spvo_brisk_detect_pair carries the extractor's, which stays with the slot
-  k.angle = p.detect == Detect::Brisk ? -1.f : r.angle;
+  // a BRISK keypoint keeps the angle its detector reports, -1; the record of spvo_brisk_detect_pair carries the extractor's, which stays with the slot.
+  // The ORB extractor's angle replaces it (spvo_brisk_orb_pair's record: radians), as describeKeypoints does
+  k.angle = extracted && p.describe == Describe::Orb ? orb_degrees(r.angle) : p.detect == Detect::Brisk ? -1.f : r.angle;
   k.response = r.response;
   k.octave = r.octave;   // BRISK: the layer, 0 .. 5
   return k;
 }
-static cv::KeyPoint to_keypoint(const spvo_akaze_keypoint &r, const ClassicPair &) {
+static cv::KeyPoint to_keypoint(const spvo_akaze_keypoint &r, const ClassicPair &p, bool extracted) {
   cv::KeyPoint k(cv::Point2f(r.x, r.y), r.size);
-  k.angle = r.angle;   // 0: the orientation belongs to the descriptor stage
+  k.angle = extracted && p.describe == Describe::Orb ? orb_degrees(r.angle) : r.angle;   // the detector's 0 (the orientation belongs to the descriptor stage), a pair call's degrees, or spvo_akaze_orb_pair's radians
   k.response = r.response;
   k.octave = r.octave;
   k.class_id = r.class_id;   // the level, 0 .. 15
   return k;
 }
-template <class Record> static std::vector<cv::KeyPoint> to_keypoints(const Record *r, int n, const ClassicPair &p) {
+template <class Record> static std::vector<cv::KeyPoint> to_keypoints(const Record *r, int n, const ClassicPair &p, bool extracted = false) {
   std::vector<cv::KeyPoint> keypoints;
   keypoints.reserve(n);
-  for (int i = 0; i < n; ++i) keypoints.push_back(to_keypoint(r[i], p));
+  for (int i = 0; i < n; ++i) keypoints.push_back(to_keypoint(r[i], p, extracted));
   return keypoints;
 }
 // the first n of a buffer of the pair's descriptor rows, as a matrix of their own
@@ -465,11 +470,18 @@ bool ClassicFeatureFrontEnd::residentPair(const ClassicPair &p, cv::Mat &img_l, 
   cv::Mat *imgs[2] = {&img_l, &img_r};
   for (int k = 0; k < 2; ++k) {
     images_dq.push_back(*imgs[k]);
-    keypoints_dq.push_back(to_keypoints(f[k].kp, f[k].n, p));
+    keypoints_dq.push_back(to_keypoints(f[k].kp, f[k].n, p, true));
     descriptors_dq.push_back(copy_rows(f[k].desc, f[k].n, p));
     bin_slots_dq_.push_back(slots[k]);
   }
   return true;
+}
+
+// is level `octave` of spvo_orb_describe_octaves' pyramid (scale 1.2 per level, sizes rounded) at least the 32 x 32 the extractor accepts?
+static bool orb_level_ok(int rows, int cols, int octave) {
+  float scale = 1.f;
+  for (int l = 0; l < octave; ++l) scale *= 1.2f;
+  return std::lround(rows / scale) >= 32 && std::lround(cols / scale) >= 32;
 }
 
 // setDeviceResident: the pair through its route (residentPair).  false: nothing was pushed and the caller takes the per-image path -- the pair
@@ -478,7 +490,7 @@ bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &img_l, cv::Mat 
   if (!image_ok(img_l) || !image_ok(img_r) || (size_t)img_l.step != (size_t)img_r.step) return false;
   const ClassicPair &p = *pair();   // (addStereoImagePair has asked pairRuns)
   if (p.route == Route::None || (p.resident_opt_in == OptIn::BriskPairResident && !brisk_pair_resident_) || (p.resident_opt_in == OptIn::AkazePairResident && !akaze_pair_resident_) ||
-      (p.resident_opt_in == OptIn::SiftDescribeResident && !sift_describe_resident_))
+      (p.resident_opt_in == OptIn::SiftDescribeResident && !sift_describe_resident_) || (p.resident_opt_in == OptIn::OctavePairsResident && !octave_pairs_resident_))
     return false;
   const uint8_t *l = img_l.ptr<uint8_t>(0), *r = img_r.ptr<uint8_t>(0);
   const int rows = img_l.rows, cols = img_l.cols;
@@ -512,6 +524,27 @@ bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &img_l, cv::Mat 
       return spvo_classic_sift_pair(ctx_, &opts, l, r, rows, cols, step, slot_l, slot_r, &f[0], &f[1]);
     });
   }
+  // The ORB pairs refuse a shape whose pyramid level at the detector's highest octave (BRISK: layer 5; AKAZE: the octave of the shape's last
+  // level) is smaller than 32 x 32, where the per-image path asks only about the levels its keypoints name: such a shape takes that path, uncounted
+  case Route::BriskOrbPair:
+    if (!orb_level_ok(rows, cols, 5)) return false;
+    return residentPair<spvo_brisk_features>(p, img_l, img_r, "spvo_brisk_orb_pair", [&](int slot_l, int slot_r, spvo_brisk_features *f) {
+      return spvo_brisk_orb_pair(ctx_, l, r, rows, cols, step, 30, 3, slot_l, slot_r, resident_capacity_, &f[0], &f[1]);
+    });
+  case Route::AkazeOrbPair: {
+    int levels = 0, n_tau = 0;
+    int32_t octave[16] = {0};
+    if (rows < 16 || cols < 16 || spvo_akaze_tables(rows, cols, &levels, octave, nullptr, nullptr, nullptr, nullptr, 0, &n_tau, nullptr, nullptr) != SPVO_OK || levels < 1 ||
+        !orb_level_ok(rows, cols, octave[levels - 1]))
+      return false;
+    return residentPair<spvo_akaze_features>(p, img_l, img_r, "spvo_akaze_orb_pair", [&](int slot_l, int slot_r, spvo_akaze_features *f) {
+      return spvo_akaze_orb_pair(ctx_, l, r, rows, cols, step, 0.001f, slot_l, slot_r, resident_capacity_, &f[0], &f[1]);
+    });
+  }
+  case Route::AkazeBriskPair:
+    return residentPair<spvo_akaze_features>(p, img_l, img_r, "spvo_akaze_brisk_pair", [&](int slot_l, int slot_r, spvo_akaze_features *f) {
+      return spvo_akaze_brisk_pair(ctx_, l, r, rows, cols, step, 0.001f, slot_l, slot_r, resident_capacity_, &f[0], &f[1]);
+    });
   case Route::None:
     break;
   }
@@ -544,6 +577,7 @@ ClassicFeatureFrontEnd::ClassicFeatureFrontEnd(const DetectorType detector_type,
   brisk_pair_resident_ = g_classic_brisk_pair_resident;
   akaze_pair_resident_ = g_classic_akaze_pair_resident;
   sift_describe_resident_ = g_classic_sift_describe_resident;
+  octave_pairs_resident_ = g_classic_octave_pairs_resident;
 }
 
 ClassicFeatureFrontEnd::~ClassicFeatureFrontEnd() {

@@ -443,6 +443,10 @@ void spvo_host_classic_set_sift_describe_resident(int on) { ClassicFeatureFrontE
 // (spvo_orb_describe_octaves on the detector's keypoints at their octaves, the per-image path); off, both pairs are refused
 void spvo_host_classic_set_orb_octaves(int on) { ClassicFeatureFrontEnd::setOrbExtractorOctaves(on != 0); }
 
+// ClassicFeatureFrontEnd::setOctavePairsResident for the front ends constructed afterwards: BRISK + ORB, AKAZE + ORB and AKAZE + BRISK
+// through one spvo_brisk_orb_pair / spvo_akaze_orb_pair / spvo_akaze_brisk_pair per pair when setDeviceResident is on as well (off by default)
+void spvo_host_classic_set_octave_pairs_resident(int on) { ClassicFeatureFrontEnd::setOctavePairsResident(on != 0); }
+
 // the ORB + ORB front end at the native resolution (the export's first form)
 int spvo_host_classic_sequence(int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l, const double *P_r, int knn,
                                int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats, double *seconds) {

@@ -94,7 +94,7 @@ SYMBOLS = [
     "spvo_default_config", "spvo_create", "spvo_destroy", "spvo_last_error", "spvo_load_weights", "spvo_engine_precision", "spvo_set_fp32_split",
     "spvo_preprocess", "spvo_forward", "spvo_debug_tensor", "spvo_heatmap", "spvo_nms",
     "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8",
-    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_orb_describe_octaves", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_akaze_describe", "spvo_akaze_detect_pair", "spvo_akaze_suppress_debug", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_describe", "spvo_sift_detect_pair", "spvo_classic_sift_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
+    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_orb_describe_octaves", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_akaze_describe", "spvo_akaze_detect_pair", "spvo_akaze_suppress_debug", "spvo_brisk_orb_pair", "spvo_akaze_orb_pair", "spvo_akaze_brisk_pair", "spvo_orb_octaves_link_debug", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_describe", "spvo_sift_detect_pair", "spvo_classic_sift_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
     "spvo_profile_enable", "spvo_profile_reset", "spvo_profile_only", "spvo_profile_count", "spvo_profile_get", "spvo_profile_stage_kernel", "spvo_profile_stage_variant",
     "spvo_set_tuning", "spvo_get_tuning", "spvo_clear_tuning",
     "spvo_comm_unique_id", "spvo_comm_available", "spvo_comm_create", "spvo_comm_create_host", "spvo_comm_rank", "spvo_comm_world", "spvo_comm_destroy",
@@ -164,6 +164,9 @@ def load() -> C.CDLL:
     lib.spvo_akaze_describe.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, vp, vp]
     lib.spvo_akaze_detect_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(AkazeFeatures), C.POINTER(AkazeFeatures)]
     lib.spvo_akaze_suppress_debug.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, ip]
+    lib.spvo_brisk_orb_pair.argtypes = lib.spvo_brisk_detect_pair.argtypes
+    lib.spvo_akaze_orb_pair.argtypes = lib.spvo_akaze_brisk_pair.argtypes = lib.spvo_akaze_detect_pair.argtypes
+    lib.spvo_orb_octaves_link_debug.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, ip]
     lib.spvo_sift_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, C.c_int, ip]
     lib.spvo_sift_debug_level.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, ip, ip]
     lib.spvo_sift_describe.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, vp]
@@ -685,6 +688,70 @@ class Context:
             m = min(f.n, max(want, 0))
             out.append(dict(kp=kp[:m].copy(), desc=desc[:m].copy(), n=f.n))
         return out[0], out[1]
+
+    def _octave_pair(self, call, kp_dtype, features, desc_bytes, img_l, img_r, params, slot_l, slot_r, slot_capacity, cap):
+        """brisk_detect_pair's protocol around one of the three pair calls whose extractor is another algorithm's."""
+        l, r = _u8_rows(img_l), _u8_rows(img_r)
+        if l.shape != r.shape or l.strides[0] != r.strides[0]:
+            l, r = np.ascontiguousarray(l), np.ascontiguousarray(r)
+            if l.shape != r.shape:
+                raise ValueError("the two images of a pair must have one shape")
+        want = int(slot_capacity) if cap is None else int(cap)
+        bufs, feats = [], []
+        for _ in range(2):
+            kp = np.zeros(max(want, 1), kp_dtype)
+            desc = np.zeros((max(want, 1), desc_bytes), np.uint8)
+            bufs.append((kp, desc))
+            feats.append(features(0, kp.ctypes.data, desc.ctypes.data, want))
+        rc = call(self.h, _ptr(l), _ptr(r), l.shape[0], l.shape[1], l.strides[0], *params, slot_l, slot_r, int(slot_capacity), C.byref(feats[0]), C.byref(feats[1]))
+        if rc:
+            e = SpvoError(rc, self.lib.spvo_last_error(self.h).decode())
+            e.n_l, e.n_r = feats[0].n, feats[1].n
+            e.counts = (e.n_l, e.n_r)
+            raise e
+        self._resident_shape = r.shape
+        out = []
+        for (kp, desc), f in zip(bufs, feats):
+            m = min(f.n, max(want, 0))
+            out.append(dict(kp=kp[:m].copy(), desc=desc[:m].copy(), n=f.n))
+        return out[0], out[1]
+
+    def brisk_orb_pair(self, img_l, img_r, slot_l: int, slot_r: int, threshold: int = 30, octaves: int = 3, slot_capacity: int = 8192, cap: Optional[int] = None):
+        """One stereo pair through the BRISK detector and the ORB extractor at the keypoints' octaves into two binary feature slots of
+        32-byte rows (spvo_brisk_orb_pair).  -> (left, right): dicts of kp [m] (BRISK_KP_DTYPE records: the detector's that survived the
+        extractor's border rule, grouped by octave, with the extractor's angle in radians), desc [m, 32] uint8 and n, as brisk_detect_pair.
+        Afterwards the right image is resident.  On SPVO_ERR_CAPACITY the SpvoError carries the two counts as .n_l, .n_r (and .counts)."""
+        return self._octave_pair(self.lib.spvo_brisk_orb_pair, BRISK_KP_DTYPE, BriskFeatures, 32, img_l, img_r, (int(threshold), int(octaves)), slot_l, slot_r, slot_capacity, cap)
+
+    def akaze_orb_pair(self, img_l, img_r, slot_l: int, slot_r: int, threshold: float = 0.001, slot_capacity: int = 8192, cap: Optional[int] = None):
+        """The same behind the AKAZE detector (spvo_akaze_orb_pair): kp [m] AKAZE_KP_DTYPE records with the extractor's angle in radians,
+        desc [m, 32].  Afterwards the right image and its scale space are resident."""
+        return self._octave_pair(self.lib.spvo_akaze_orb_pair, AKAZE_KP_DTYPE, AkazeFeatures, 32, img_l, img_r, (float(threshold),), slot_l, slot_r, slot_capacity, cap)
+
+    def akaze_brisk_pair(self, img_l, img_r, slot_l: int, slot_r: int, threshold: float = 0.001, slot_capacity: int = 8192, cap: Optional[int] = None):
+        """One stereo pair through the AKAZE detector and the BRISK extractor into two binary feature slots of 64-byte rows
+        (spvo_akaze_brisk_pair): kp [m] AKAZE_KP_DTYPE records that survived the extractor's border rule, in the detector's order, with the
+        extractor's angle in degrees, desc [m, 64].  Afterwards the right image and its scale space are resident."""
+        return self._octave_pair(self.lib.spvo_akaze_brisk_pair, AKAZE_KP_DTYPE, AkazeFeatures, 64, img_l, img_r, (float(threshold),), slot_l, slot_r, slot_capacity, cap)
+
+    def orb_octaves_link_debug(self, xy: np.ndarray, octave, keep=None, max_octave: int = 7, shape=None):
+        """The ORB pairs' device link and describe kernel on a caller's list against the resident image (spvo_orb_octaves_link_debug):
+        xy [n, 2], octave per keypoint (or one for all), keep [n] flags or None, shape as in orb_describe.  -> dict of kept [m] (indices
+        into xy), angle [m] rad, desc [m, 32], as orb_describe_octaves(None, ...) on the list without its keep == 0 records."""
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        n = len(xy)
+        octave = np.ascontiguousarray(np.broadcast_to(np.asarray(octave, np.int32), (n,)))
+        flags = None if keep is None else np.ascontiguousarray(np.asarray(keep) != 0, np.uint8).reshape(n)
+        kept = np.zeros(max(n, 1), np.int32)
+        angle = np.zeros(max(n, 1), np.float32)
+        desc = np.zeros((max(n, 1), 32), np.uint8)
+        m = C.c_int(0)
+        rows, cols = shape if shape is not None else getattr(self, "_resident_shape", (0, 0))
+        if rows <= 0 or cols <= 0:
+            rows = cols = 64               # nothing remembered: let the library answer (SPVO_ERR_STATE)
+        self._check(self.lib.spvo_orb_octaves_link_debug(self.h, int(rows), int(cols), _ptr(xy), _ptr(octave), None if flags is None else _ptr(flags), n, int(max_octave), _ptr(kept),
+                                                         _ptr(angle), _ptr(desc), C.byref(m)))
+        return dict(kept=kept[:m.value].copy(), angle=angle[:m.value].copy(), desc=desc[:m.value].copy())
 
     def akaze_suppress_debug(self, rows: int, cols: int, cand: np.ndarray) -> np.ndarray:
         """The device suppression of akaze_detect_pair on a candidate list (spvo_akaze_suppress_debug): cand [n] AKAZE_CAND_DTYPE records

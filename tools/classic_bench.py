@@ -1,6 +1,6 @@
 """The classic front end on the GPU.
 
-python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK|AKAZE] [--descriptor ORB|BRISK|AKAZE|SIFT] [--resident] [--brisk-resident] [--akaze-resident] [--sift-resident]
+python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK|AKAZE] [--descriptor ORB|BRISK|AKAZE|SIFT] [--resident] [--brisk-resident] [--akaze-resident] [--sift-resident] [--orb-octaves] [--octave-pairs-resident]
     ClassicFeatureFrontEnd(detector, descriptor, BF, KNN) over the synthetic stream: frames/s of the synchronous stereoCallback
     (--descriptor BRISK: with --detector ShiTomasi, FAST, BRISK or AKAZE; --detector BRISK: with --descriptor BRISK only; --detector AKAZE:
     with --descriptor BRISK or AKAZE -- the latter sets ClassicFeatureFrontEnd::setAkazeDescriptor for the run: 61-byte MLDB rows);
@@ -53,6 +53,15 @@ python tools/classic_bench.py --leg akaze_pair [--calls 100]
     for rocprofv3 --kernel-trace --stats as above: the detector's kernels up to akaze_refine_kernel, then akaze_suppress_first_kernel /
     akaze_suppress_second_kernel / akaze_suppress_compact_kernel / akaze_describe_kernel / akaze_pair_finish_kernel, twice per call.
     Its yardsticks are --leg akaze_detect and --leg akaze_describe: two per-image detects plus two describes.
+python tools/classic_bench.py --leg brisk_orb_pair|akaze_orb_pair|akaze_brisk_pair [--calls 100]
+    spvo_brisk_orb_pair / spvo_akaze_orb_pair / spvo_akaze_brisk_pair on the 1241 x 376 sample pair -- BOTH images per call -- rotating
+    through the slot ring, and ALTERNATING with it call by call in the same run its yardstick, the per-image sequence of both images:
+    spvo_brisk_detect / spvo_akaze_detect, then spvo_orb_describe_octaves(img = NULL) / spvo_brisk_describe(img = NULL) on its keypoints.
+    For rocprofv3 --kernel-trace --stats as above (--no-yardstick: the pair call alone): behind the detector's kernels
+    orb_link_group_kernel / orb_resize_kernel x max octave / orb_blur_h_kernel / orb_blur_v_kernel / orb_link_describe_kernel /
+    orb_link_finish_kernel, or akaze_present_brisk_kernel / brisk_integral_*_kernel / brisk_pair_compact_kernel / brisk_describe_kernel /
+    brisk_pair_finish_kernel / akaze_brisk_finish_kernel, twice per call.  The whole pair through the host class: --detector BRISK|AKAZE
+    --descriptor ORB|BRISK [--orb-octaves] --resident --octave-pairs-resident (ClassicFeatureFrontEnd::setOctavePairsResident for the run).
 python tools/classic_bench.py --leg fast_sift|gftt_sift|sift_describe [--calls 50] [--form 0|1] [--yardstick] [--sift-resident]
     FAST + SIFT per image at 1241 x 376, for rocprofv3 --kernel-trace --stats as above.  sift_describe: spvo_sift_describe alone on the FAST
     keypoints of the sample (size 7, angle -1, octave 0; image passed with every call): sift_blur_kernel x 6 / sift_describe_given_kernel is
@@ -88,8 +97,10 @@ ap.add_argument("--brisk-resident", action="store_true")
 ap.add_argument("--akaze-resident", action="store_true")
 ap.add_argument("--sift-resident", action="store_true")
 ap.add_argument("--orb-octaves", action="store_true")
+ap.add_argument("--octave-pairs-resident", action="store_true")
+ap.add_argument("--no-yardstick", action="store_true")
 ap.add_argument("--ab", type=int, default=0)
-ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "brisk_detect", "akaze_detect", "akaze_describe", "akaze_pair", "brisk_pair", "orb_describe", "orb_octaves", "fast_sift", "gftt_sift", "sift_describe", "match", "match_slots"])
+ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "brisk_detect", "akaze_detect", "akaze_describe", "akaze_pair", "brisk_pair", "brisk_orb_pair", "akaze_orb_pair", "akaze_brisk_pair", "orb_describe", "orb_octaves", "fast_sift", "gftt_sift", "sift_describe", "match", "match_slots"])
 ap.add_argument("--form", type=int, default=0, choices=[0, 1])
 ap.add_argument("--waves", type=int, default=0)
 ap.add_argument("--selector", default="KNN", choices=["NN", "KNN"])
@@ -201,8 +212,24 @@ if args.detectors or args.leg:
         fl, fr = ctx.akaze_detect_pair(img, pair_r, 2 * k, 2 * k + 1)
         return fl["n"] + fr["n"]
 
-    if args.leg in ("brisk_pair", "akaze_pair", "fast_sift", "gftt_sift"):
+    OCTAVE_PAIRS = ("brisk_orb_pair", "akaze_orb_pair", "akaze_brisk_pair")
+    if args.leg in ("brisk_pair", "akaze_pair", "fast_sift", "gftt_sift") + OCTAVE_PAIRS:
         pair_r = np.ascontiguousarray(frames[0][1][:376, :1241])
+
+    def leg_octave_pair():                             # both images in one call
+        k = pair_calls[0] % 4
+        pair_calls[0] += 1
+        fl, fr = getattr(ctx, args.leg)(img, pair_r, 2 * k, 2 * k + 1)
+        return fl["n"] + fr["n"]
+
+    def leg_octave_pair_per_image():                   # its yardstick: detector, then the extractor on the resident image, per image
+        n = 0
+        for im in (img, pair_r):
+            kp = (ctx.brisk_detect(im, 30) if args.leg == "brisk_orb_pair" else ctx.akaze_detect(im))["kp"]
+            xy = np.stack([kp["x"], kp["y"]], 1)
+            d = ctx.brisk_describe(None, xy, kp["size"], shape=im.shape) if args.leg == "akaze_brisk_pair" else ctx.orb_describe_octaves(None, xy, kp["octave"], shape=im.shape)
+            n += len(d["kept"])
+        return n
 
     def leg_orb_describe():
         return len(ctx.orb_describe(img, kp)["kept"])
@@ -240,6 +267,7 @@ if args.detectors or args.leg:
                 akaze_describe_img=("spvo_akaze_describe(img)", leg_akaze_describe_img),
                 brisk_detect=("spvo_brisk_detect", leg_brisk_detect), akaze_detect=("spvo_akaze_detect", leg_akaze_detect), brisk_pair=("spvo_brisk_detect_pair (both images)", leg_brisk_pair),
                 akaze_pair=("spvo_akaze_detect_pair (both images)", leg_akaze_pair),
+                octave_pair=("spvo_%s (both images)" % args.leg, leg_octave_pair), octave_pair_per_image=("its per-image sequence (both images)", leg_octave_pair_per_image),
                 sift_describe=("spvo_sift_describe, %d FAST keypoints, form %d" % (len(srec) if args.leg == "sift_describe" else 0, args.form), leg_sift_describe),
                 fast_sift=("spvo_fast_detect + spvo_sift_describe(NULL), form %d" % args.form, leg_fast_sift),
                 gftt_sift=("spvo_gftt_detect + spvo_sift_describe(NULL), form %d" % args.form, leg_gftt_sift),
@@ -251,15 +279,27 @@ if args.detectors or args.leg:
         keys = ["akaze_describe", "akaze_brisk_null", "akaze_describe_img", "akaze_detect"]
     if args.leg == "orb_octaves":
         keys = ["orb_octaves", "orb_octaves_null", "orb_describe"]
+    if args.leg in OCTAVE_PAIRS:                       # the two sides alternate call by call
+        keys = ["octave_pair"] + ([] if args.no_yardstick else ["octave_pair_per_image"])
+        alt, counts = {k: [] for k in keys}, {}
+        for i in range(args.warmup + args.calls):
+            for k in keys:
+                t0 = time.perf_counter()
+                counts[k] = legs[k][1]()
+                if i >= args.warmup:
+                    alt[k].append(1e3 * (time.perf_counter() - t0))
     for key in keys:
         name, fn = legs[key]
-        for _ in range(args.warmup):
-            n = fn()
-        ts = []
-        for _ in range(args.calls):
-            t0 = time.perf_counter()
-            n = fn()
-            ts.append(1e3 * (time.perf_counter() - t0))
+        if args.leg in OCTAVE_PAIRS:
+            ts, n = alt[key], counts[key]
+        else:
+            for _ in range(args.warmup):
+                n = fn()
+            ts = []
+            for _ in range(args.calls):
+                t0 = time.perf_counter()
+                n = fn()
+                ts.append(1e3 * (time.perf_counter() - t0))
         ts = np.array(ts)
         extra = ""
         if key == "gftt":
@@ -301,5 +341,6 @@ else:
     seq = [frames[i % 8] for i in range(n)]
     p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5, detector=args.detector, resident=args.resident, descriptor=args.descriptor,
                                         akaze_descriptor=args.descriptor == "AKAZE", **(dict(brisk_resident=True) if args.brisk_resident else {}), **(dict(akaze_resident=True) if args.akaze_resident else {}),
-                                        **(dict(sift_describe_resident=True) if args.sift_resident else {}), **(dict(orb_octaves=True) if args.orb_octaves else {}))
+                                        **(dict(sift_describe_resident=True) if args.sift_resident else {}), **(dict(orb_octaves=True) if args.orb_octaves else {}),
+                                        **(dict(octave_pairs_resident=True) if args.octave_pairs_resident else {}))
     print("classic front end (%s%s) on the GPU: %.1f stereo frames/s (%.3f ms per pair), keypoints %d, stereo matches %d, inliers %d, %d pairs resident" % (args.detector + ("" if args.descriptor == "ORB" else " + " + args.descriptor), ", device-resident" if args.resident else "", (n - 5) / sec, 1e3 * sec / (n - 5), np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3]), host.classic_resident_pairs()))
