@@ -674,6 +674,53 @@ int spvo_sift_detect_pair(spvo_ctx *ctx, const uint8_t *img_l, const uint8_t *im
 int spvo_classic_sift_pair(spvo_ctx *ctx, const spvo_classic_opts *opts /* kind 5 or 6 */, const uint8_t *img_l, const uint8_t *img_r,
                            int rows, int cols, size_t stride, int slot_l, int slot_r,
                            spvo_sift_features *out_l, spvo_sift_features *out_r);
+/* BRISK / AKAZE keypoints with SIFT descriptors (ClassicFeatureFrontEnd(BRISK or AKAZE, SIFT)) for BOTH images of a stereo pair in one
+ * call, into the same ring of ten SIFT slots.  Both calls follow spvo_classic_sift_pair in protocol: the pinned staging, the left image's
+ * chain then the right's on the solver's stream without a host round trip, one wait; slot rows of 256 floats (columns 128.. zero), squared
+ * norms, SiftKey records and the count; spvo_match_l2_slots, spvo_sift_slot_rows and spvo_set_prematch; any filled SIFT slot as temporal
+ * partner, whichever call filled it; slot_capacity 1 .. 32768, a larger one than any before emptying every SIFT slot.  Per image:
+ *   1. the detector: spvo_brisk_detect's launches up to the refined records with their keep flags / spvo_akaze_detect_pair's launches
+ *      through the suppression on the device, which leaves the kept records and their count there;
+ *   2. a Gaussian-only SIFT pyramid of the resident u8 image at its own size for octaves 0 .. max_octave -- 5 for BRISK, the octave of the
+ *      shape's last level for AKAZE: the host does not know which octaves hold keypoints -- reduced to what is read: every record of these
+ *      detectors has layer 0 and an octave derives from layer 3 of the one below, so layers 0 .. 3 of every octave but the last and layer 0
+ *      of the last (a layer depends only on the one before: these levels are bit for bit spvo_sift_describe's);
+ *   3. spvo_sift_describe's kernel on the detector's records where they lie (byte stride and field offsets; BRISK: the kept records in the
+ *      detector's order, by a compaction of indices on the device), the count read on the device, spvo_classic_sift_pair's fixed grid;
+ *   4. its sink: the slot, and pinned mirrors of the rows and of the detector's OWN record, unchanged -- 24 bytes for BRISK
+ *      (spvo_brisk_keypoint is spvo_sift_keypoint), 28 bytes with class_id for AKAZE.  The extractor changes no angle and erases nothing.
+ *   Byte equality: per image the host receives, byte for byte, what spvo_brisk_detect(img, threshold, octaves) / spvo_akaze_detect(img,
+ *   threshold) returns followed by spvo_sift_describe(img = NULL) on exactly those records (AKAZE: on {x, y, size, angle, response,
+ *   octave} of them; class_id is not passed); row i belongs to record i.  An image without a keypoint fills its slot with 0 rows: SPVO_OK.
+ * Afterwards the resident u8 image is the RIGHT image's (spvo_sift_describe(img = NULL), spvo_brisk_describe(NULL) work on it); BRISK:
+ * spvo_brisk_detect_debug_layer answers SPVO_ERR_STATE, as after spvo_brisk_detect_pair; AKAZE: the right image's scale space is resident,
+ * as after spvo_akaze_orb_pair; no SIFT pyramid is resident (spvo_sift_debug_level: SPVO_ERR_STATE).
+ * ORB + SIFT has no such call: the ORB detector keeps a pyramid and an image of its own, not the shared resident image, and its records
+ * name octaves up to 7.
+ *   SPVO_ERR_CAPACITY  an image yields more rows than slot_capacity: out_*->n report both counts, both slots are left unfilled, nothing
+ *                      is truncated
+ *   SPVO_ERR_INVALID   nothing is written or touched: NULL arguments, cap < 0 or a positive cap with a NULL buffer, bad or equal slots,
+ *                      slot_capacity outside 1 .. 32768, whatever spvo_brisk_detect_pair / spvo_akaze_detect_pair and spvo_sift_describe
+ *                      refuse of the shape or the parameters, and min(rows, cols) >> max_octave < 1 (the text names the octave; for BRISK
+ *                      a dimension below 32) -- in the place of spvo_sift_describe's per-keypoint refusal, which the host can no longer
+ *                      evaluate
+ *   SPVO_ERR_STATE     a spvo_detect*_submit is in flight; the detector's candidate list overflowed (it is sized from the image) */
+int spvo_brisk_sift_pair(spvo_ctx *ctx, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride,
+                         int threshold, int octaves, int slot_l, int slot_r, int slot_capacity,
+                         spvo_sift_features *out_l, spvo_sift_features *out_r);
+typedef struct { int n; spvo_akaze_keypoint *kp; float *desc /* [cap][128] */; int cap; } spvo_akaze_sift_features;   /* n: out; min(n, cap) rows are written */
+int spvo_akaze_sift_pair(spvo_ctx *ctx, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride,
+                         float threshold, int slot_l, int slot_r, int slot_capacity,
+                         spvo_akaze_sift_features *out_l, spvo_akaze_sift_features *out_r);
+/* The link of the two calls above -- compaction by keep flags, the reduced pyramid for octaves 0 .. max_octave, the describe launch on
+ * the fixed grid with the count read on the device -- on a caller's list against the u8 image already resident, of shape rows x cols
+ * (test hook: lists no image gives).  No detector runs, no slot is touched, the image stays resident.  keep = NULL: all records take
+ * part; `kept` names the original indices, and the rows equal spvo_sift_describe(img = NULL) on the kept records.
+ *   SPVO_ERR_INVALID   max_octave outside 0 .. 15 or naming an empty level; a record whose unpacked octave is outside 0 .. max_octave or
+ *                      whose layer is not 0; a field spvo_sift_describe refuses.  Nothing is written.
+ *   SPVO_ERR_STATE     no image of that shape is resident; a spvo_detect*_submit is in flight */
+int spvo_sift_link_debug(spvo_ctx *ctx, int rows, int cols, const spvo_sift_keypoint *kp, const uint8_t *keep /* [n] or NULL */,
+                         int n, int max_octave, int32_t *kept /* [n] */, float *desc /* [n][128] */, int *n_kept);
 /* rows a SIFT slot holds; SPVO_ERR_STATE for one that holds nothing (never filled, or left unfilled by SPVO_ERR_CAPACITY) */
 int spvo_sift_slot_rows(spvo_ctx *ctx, int slot, int *n);
 /* spvo_match_l2(dim = 128) on the device-resident rows of two SIFT slots: nothing is uploaded, no norm is recomputed.  Results equal

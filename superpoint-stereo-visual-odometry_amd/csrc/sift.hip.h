@@ -18,6 +18,8 @@
 // record with the per-sample device code of sift_describe_kernel (sift_patch, sift_patch_sample, sift_share_bin, sift_desc_store) and sums
 // of its own that take no turns.  The same kernel behind a Shi-Tomasi / FAST detector (spvo_classic_sift_pair): its IO parameter reads the
 // detector's list where it lies and writes the rows into a SIFT slot and the host's mirrors; only the base level is built for it.
+// And behind the BRISK / AKAZE detector (spvo_brisk_sift_pair, spvo_akaze_sift_pair): SiftLinkIO reads records that carry an octave
+// through a byte stride and field offsets; sift_link_compact_kernel turns BRISK's keep flags into the list of indices it walks.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -438,6 +440,91 @@ struct SiftDetectorIO {
     if (lane == 0) { s_sqn[i] = sq; s_rec[i] = k; h_rec[i] = k; }
   }
 };
+//   SiftLinkIO      spvo_brisk_sift_pair, spvo_akaze_sift_pair, spvo_sift_link_debug: the records of a detector that reports an octave,
+//                   read where they lie through SiftLinkSrc's byte stride and field offsets (kernel arguments: nothing of a record is a
+//                   compile-time constant, as above).  Row r describes record kept[r] (sift_link_compact_kernel's list: BRISK's keep
+//                   flags, the hook's) or record r (kept = NULL: AKAZE's suppression left a compacted list); the count is read here.
+//                   The sink is SiftDetectorIO's -- slot rows, squared norms, SiftKey records, the count; pinned rows and h_n = {rows in
+//                   all, the detector's overflow flag, 0} -- except that the host's mirror receives the detector's OWN record, all
+//                   `stride` bytes of it, unchanged (AKAZE: with class_id; its contrast factors go to h_k).  The hook has no slot and
+//                   no mirror of records: s_desc, h_rec and h_n are NULL, h_desc is its device buffer
+struct SiftLinkIO {
+  SiftLinkSrc s;
+  const int *kept, *n_kept;   // sift_link_compact_kernel's list and its length, or NULL
+  int max_octave, slot_cap;   // the last octave of the pyramid the launch reads
+  float *s_desc, *s_sqn;
+  SiftKey *s_rec;
+  int *d_n;
+  float *h_desc;
+  char *h_rec;                // [slot_cap][s.stride]
+  int *h_n, *h_k;
+  __device__ __forceinline__ int begin() const {
+    const int n_all = kept ? *n_kept : min(max(*s.n_ptr, 0), s.n_cap), n = min(n_all, slot_cap);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      if (d_n) *d_n = n;
+      if (h_n) {
+        h_n[0] = n_all; h_n[2] = 0;
+        if (s.stat) {
+          h_n[1] = s.stat[AKAZE_STAT_OVERFLOW] || s.stat[AKAZE_STAT_NCAND] > s.cand_cap;
+          for (int o = 0; o < AKAZE_MAX_OCTAVES; ++o) h_k[o] = s.stat[AKAZE_STAT_K + o];
+        } else {
+          h_n[1] = s.det_counters ? s.det_counters[3] : 0;
+        }
+      }
+    }
+    return n;
+  }
+  __device__ __forceinline__ const char *at(int i) const { return s.rec + (size_t)(kept ? kept[i] : i) * s.stride; }
+  __device__ __forceinline__ SiftKey record(int i) const {
+    const char *p = at(i);
+    int oct = *reinterpret_cast<const int *>(p + s.off_octave);
+    // (no detector reports another octave or a layer, and the hook refuses them: nothing may name a level that was not built)
+    if ((oct & 255) > max_octave || ((oct >> 8) & 255) != 0) oct = 0;
+    return SiftKey{*reinterpret_cast<const float *>(p + s.off_x),    *reinterpret_cast<const float *>(p + s.off_y),        *reinterpret_cast<const float *>(p + s.off_size),
+                   *reinterpret_cast<const float *>(p + s.off_angle), *reinterpret_cast<const float *>(p + s.off_response), oct};
+  }
+  __device__ __forceinline__ void store(int i, const SiftKey &k, float d0, float d1, int lane) const {
+    sift_desc_finish(d0, d1);
+    float *hrow = h_desc + (size_t)i * 128;
+    hrow[lane] = d0; hrow[64 + lane] = d1;
+    if (s_desc) {
+      float *row = s_desc + (size_t)i * 256;
+      row[lane] = d0; row[64 + lane] = d1; row[128 + lane] = 0.f; row[192 + lane] = 0.f;
+      const float sq = sift_wave_sum(d0 * d0 + d1 * d1);
+      if (lane == 0) { s_sqn[i] = sq; s_rec[i] = k; }
+    }
+    if (h_rec && lane < (s.stride >> 2)) reinterpret_cast<int *>(h_rec + (size_t)i * s.stride)[lane] = reinterpret_cast<const int *>(at(i))[lane];
+  }
+};
+
+// kept[0 .. *n_out) = the indices i < min(*n_ptr, n_cap) with keep[i] != 0 (keep = NULL: every index), ascending: ONE workgroup walks the
+// list in chunks of 1024 with a running base (brisk_det_compact_kernel's compaction, of indices)
+__global__ __launch_bounds__(1024) void sift_link_compact_kernel(const int *__restrict__ keep, const int *__restrict__ n_ptr, int n_cap, int *__restrict__ kept,
+                                                                 int *__restrict__ n_out) {
+  __shared__ int s_wave[16];
+  const int n = min(max(*n_ptr, 0), n_cap);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int base = 0;
+  for (int i0 = 0; i0 < n; i0 += 1024) {
+    const int i = i0 + (int)threadIdx.x;
+    const bool kp = i < n && (!keep || keep[i] != 0);
+    const unsigned long long m = __ballot(kp);
+    __syncthreads();   // (the previous chunk's sums have been read)
+    if (lane == 0) s_wave[wave] = __popcll(m);
+    __syncthreads();
+    int off = base, tot = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const int v = s_wave[k];
+      off += k < wave ? v : 0;
+      tot += v;
+    }
+    off += __popcll(m & ((1ull << lane) - 1ull));
+    if (kp) kept[off] = i;   // (off <= i < n_cap)
+    base += tot;
+  }
+  if (threadIdx.x == 0) *n_out = base;
+}
 
 template <int FORM, class IO>
 __global__ __launch_bounds__(64) void sift_describe_given_kernel(SiftPyr P, int first, IO io) {

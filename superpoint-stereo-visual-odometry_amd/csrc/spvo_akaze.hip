@@ -536,7 +536,8 @@ int spvo_akaze_suppress_debug(spvo_ctx *c, int rows, int cols, const spvo_akaze_
 // and the right image's afterwards: an image's finishing kernel has put its counts into the pinned h_n before the next image's clear.
 // The extractor behind rule 11 is the call's: MLDB (spvo_akaze_detect_pair, 61-byte rows), the octave-aware ORB extractor on the kept
 // records (spvo_akaze_orb_pair: orb_link.hip.h through spvo_classic.hip, 32-byte rows), or the BRISK extractor (spvo_akaze_brisk_pair:
-// the kept records presented to brisk_pair_chain_enqueue as a detector's list, 64-byte rows).
+// the kept records presented to brisk_pair_chain_enqueue as a detector's list, 64-byte rows).  spvo_akaze_sift_pair, below, runs the
+// same detector launches as the first link of spvo_sift.hip's sift_link_pair, into the SIFT slots.
 }  // extern "C"
 namespace {
 enum class AkExtract { Mldb, Orb, Brisk };
@@ -672,6 +673,61 @@ int spvo_akaze_orb_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r,
 int spvo_akaze_brisk_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, float threshold, int slot_l, int slot_r, int slot_capacity,
                           spvo_akaze_features *out_l, spvo_akaze_features *out_r) {
   return akaze_pair(c, "spvo_akaze_brisk_pair", AkExtract::Brisk, img_l, img_r, rows, cols, stride, threshold, slot_l, slot_r, slot_capacity, out_l, out_r);
+}
+
+// The AKAZE detector with the SIFT extractor, pair-resident in the SIFT slots: per image what spvo_akaze_detect followed by
+// spvo_sift_describe(img = NULL) on {x, y, size, angle, response, octave} of its records hands out, byte for byte; the host's records keep
+// their class_id.  The protocol is sift_link_pair's (spvo_sift.hip); the detector's part is akaze_pair's chain through ak_suppress_enqueue,
+// which leaves sup_kp and the AKAZE_SUP_KEPT count on the device.  A kept record's octave is at most that of the shape's last level, so the
+// pyramid is built up to it.  Afterwards the right image's scale space is resident, as after spvo_akaze_orb_pair.
+int spvo_akaze_sift_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, float threshold, int slot_l, int slot_r, int slot_capacity,
+                         spvo_akaze_sift_features *out_l, spvo_akaze_sift_features *out_r) {
+  if (!c || !img_l || !img_r || !out_l || !out_r || rows <= 0 || cols <= 0 || stride < (size_t)cols) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  static_assert(sizeof(spvo_akaze_keypoint) == sizeof(AkazeKp), "record layout");
+  const char *who = "spvo_akaze_sift_pair";
+  auto &d = c->akaze;
+  auto &b = c->cls;
+  SiftLinkDetector det;
+  det.who = who;
+  det.max_octave = ((d.rows == rows && d.cols == cols) ? d.octaves : make_tables(rows, cols).octaves) - 1;   // (make_tables takes any positive shape)
+  det.check = [&]() -> int { return ak_check(c, who, rows, cols, threshold); };
+  det.prepare = [&](SiftLinkSrc &src) -> int {
+    int rc;
+    if ((rc = ak_ensure(c, rows, cols)) || (rc = ak_sup_ensure(c, d.cand_cap))) return rc;
+    src = SiftLinkSrc{reinterpret_cast<const char *>(d.sup_kp), (int)sizeof(AkazeKp), (int)offsetof(AkazeKp, x), (int)offsetof(AkazeKp, y), (int)offsetof(AkazeKp, size),
+                      (int)offsetof(AkazeKp, angle), (int)offsetof(AkazeKp, response), (int)offsetof(AkazeKp, octave), nullptr, d.sup_cnt + AKAZE_SUP_KEPT, d.sup_cap, nullptr, d.stat,
+                      d.cand_cap};
+    return SPVO_OK;
+  };
+  det.enqueue = [&](const uint8_t *h_img) -> int {
+    hipStream_t st = c->stream2;
+    const AkazeLevels &lv = d.lv;
+    b.rows = b.cols = 0;
+    HIP_TRY(c, hipMemcpyAsync(b.im, h_img, (size_t)rows * cols, hipMemcpyHostToDevice, st));
+    b.rows = rows; b.cols = cols;
+    if (int rc = ak_scale_enqueue(c, rows, cols)) return rc;
+    // rules 10, 12, 13: spvo_akaze_detect's launches, then rule 11 on the device
+    for (int first = 0; first < lv.n; first += AK_SUBLEVELS) {
+      const AkazeLevel &L = lv.l[first];
+      if (L.h <= 2 * L.border || L.w <= 2 * L.border) continue;
+      dim3 eg = grid_of(L.w, L.h);
+      eg.z = std::min(AK_SUBLEVELS, lv.n - first);
+      hipLaunchKernelGGL(akaze_extrema_kernel, eg, dim3(256), 0, st, lv, first, threshold, 1e-5f, d.keys, d.cand_cap, d.stat);
+    }
+    classic_rank_enqueue(c, d.keys, d.rank, d.stat + AKAZE_STAT_NCAND, d.cand_cap);
+    hipLaunchKernelGGL(akaze_refine_kernel, dim3(32), dim3(256), 0, st, lv, d.keys, d.rank, d.cand_cap, d.stat, d.rec);
+    ak_suppress_enqueue(c, lv, d.rec, d.stat + AKAZE_STAT_NCAND, d.cand_cap);
+    HIP_TRY(c, hipGetLastError());
+    return SPVO_OK;
+  };
+  const SiftLinkOut outs[2] = {{&out_l->n, out_l->kp, out_l->desc, out_l->cap}, {&out_r->n, out_r->kp, out_r->desc, out_r->cap}};
+  const int rc = sift_link_pair(c, det, img_l, img_r, rows, cols, stride, slot_l, slot_r, slot_capacity, outs);
+  if (rc == SPVO_OK || rc == SPVO_ERR_CAPACITY) {   // (both are answered behind the wait) the right image's scale space is resident (ak_mark_resident: the contrast factors sit where stat keeps them)
+    int stat[AKAZE_STAT_HIST] = {0};
+    std::memcpy(&stat[AKAZE_STAT_K], c->sift.h_n + 8 + 4, AKAZE_MAX_OCTAVES * sizeof(int));
+    ak_mark_resident(c, stat);
+  }
+  return rc;
 }
 
 int spvo_akaze_tables(int rows, int cols, int *levels, int32_t *octave, float *esigma, int32_t *sigma_size, int32_t *nsteps, float *tau, int tau_cap, int *n_tau, float *g0, float *g1) {

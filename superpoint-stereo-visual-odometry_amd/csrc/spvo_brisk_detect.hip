@@ -1,7 +1,8 @@
 // spvo_brisk_detect.hip -- the classic front end's BRISK keypoint detector (brisk_detect.hip.h): the layout of the six layers and the area
 // taps of a shape (built on the host in double, by the formulas tests/brisk_detect_ref.py lists), spvo_brisk_detect,
 // spvo_brisk_detect_debug_layer and spvo_brisk_detect_pair (detector + extractor of a stereo pair in one submission into two binary slots,
-// by spvo_classic_detect's resident-pair protocol; spvo_brisk_orb_pair: the same call with the octave-aware ORB extractor behind the detector).  Runs on the solver's stream (stream2) with the image resident in spvo_ctx::cls as
+// by spvo_classic_detect's resident-pair protocol; spvo_brisk_orb_pair: the same call with the octave-aware ORB extractor behind the detector;
+// spvo_brisk_sift_pair: the detector as the first link of spvo_sift.hip's sift_link_pair, into two SIFT slots).  Runs on the solver's stream (stream2) with the image resident in spvo_ctx::cls as
 // layer 0 -- it stays there for a spvo_brisk_describe(img = NULL) that follows -- and owns everything else it needs (spvo_ctx::brisk_det).
 #include "spvo_internal.hip.h"
 #include "brisk_detect.hip.h"
@@ -296,6 +297,38 @@ int spvo_brisk_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img
 int spvo_brisk_orb_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int threshold, int octaves, int slot_l, int slot_r,
                         int slot_capacity, spvo_brisk_features *out_l, spvo_brisk_features *out_r) {
   return brisk_pair(c, "spvo_brisk_orb_pair", true, img_l, img_r, rows, cols, stride, threshold, octaves, slot_l, slot_r, slot_capacity, out_l, out_r);
+}
+
+// The BRISK detector with the SIFT extractor, pair-resident in the SIFT slots: per image what spvo_brisk_detect followed by
+// spvo_sift_describe(img = NULL) on its records hands out, byte for byte.  The protocol is sift_link_pair's (spvo_sift.hip); the detector's
+// part is bd_check, bd_ensure and, per image, the upload and bd_enqueue -- the chain up to the refined records with their keep flags, which
+// the link compacts in the detector's order.  A keypoint's octave is its layer, 0 .. 5, so the pyramid is built for octaves 0 .. 5.
+int spvo_brisk_sift_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int threshold, int octaves, int slot_l, int slot_r,
+                         int slot_capacity, spvo_sift_features *out_l, spvo_sift_features *out_r) {
+  if (!c || !img_l || !img_r || !out_l || !out_r || rows <= 0 || cols <= 0 || stride < (size_t)cols) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  static_assert(sizeof(spvo_sift_keypoint) == sizeof(BriskDetKeypoint), "record layout");
+  const char *who = "spvo_brisk_sift_pair";
+  auto &d = c->brisk_det;
+  auto &b = c->cls;
+  SiftLinkDetector det;
+  det.who = who;
+  det.max_octave = BRISK_DET_LAYERS - 1;
+  det.check = [&]() -> int { return bd_check(c, who, rows, cols, threshold, octaves); };
+  det.prepare = [&](SiftLinkSrc &src) -> int {
+    if (int rc = bd_ensure(c, rows, cols)) return rc;
+    src = SiftLinkSrc{reinterpret_cast<const char *>(d.rec), (int)sizeof(BriskDetKeypoint), (int)offsetof(BriskDetKeypoint, x), (int)offsetof(BriskDetKeypoint, y),
+                      (int)offsetof(BriskDetKeypoint, size), (int)offsetof(BriskDetKeypoint, angle), (int)offsetof(BriskDetKeypoint, response), (int)offsetof(BriskDetKeypoint, octave),
+                      d.keep, d.counters + 1, d.cand_cap, d.counters, nullptr, 0};
+    return SPVO_OK;
+  };
+  det.enqueue = [&](const uint8_t *h_img) -> int {
+    b.rows = b.cols = 0;
+    HIP_TRY(c, hipMemcpyAsync(b.im, h_img, (size_t)rows * cols, hipMemcpyHostToDevice, c->stream2));
+    b.rows = rows; b.cols = cols;
+    return bd_enqueue(c, rows, cols, threshold);
+  };
+  const SiftLinkOut outs[2] = {{&out_l->n, out_l->kp, out_l->desc, out_l->cap}, {&out_r->n, out_r->kp, out_r->desc, out_r->cap}};
+  return sift_link_pair(c, det, img_l, img_r, rows, cols, stride, slot_l, slot_r, slot_capacity, outs);
 }
 
 int spvo_brisk_detect_debug_layer(spvo_ctx *c, int layer, int what, uint8_t *out, int *rows, int *cols) {

@@ -25,6 +25,7 @@
 #include <string>
 #include <vector>
 #include <deque>
+#include <functional>
 #include <time.h>
 
 #include "../../include/spvo.h"
@@ -515,10 +516,14 @@ struct spvo_ctx {
     PairStage pair;                      // (its prematches' slot numbers are SIFT slots)
     SiftSrc *h_src = nullptr;            // pinned [2][slot_cap]      what sift_gather_kernel writes for the host: sources (spvo_classic_sift_pair: SiftKey records in each half's front),
     float *hm_desc = nullptr;            // pinned [2][slot_cap][128] descriptors,
-    int *h_n = nullptr;                  // pinned [2][4]             {final rows, candidates counted, raw rows counted}
+    int *h_n = nullptr;                  // pinned [2][4]             {final rows, candidates counted, raw rows counted}; behind them [2][4] the contrast factors spvo_akaze_sift_pair reports
     int2 *h_match = nullptr;             // pinned [2][h_match_cap]: the two prematches (enqueue_matches spaces its jobs by spvo_ctx::match_cap)
     int h_match_cap = 0;
     bool match_pending = false;          // pair.ev_match has been recorded: a later call's kernels wait for it before they rewrite a slot
+    // the link behind a detector that reports an octave (spvo_brisk_sift_pair, spvo_akaze_sift_pair, spvo_sift_link_debug): the indices
+    // sift_link_compact_kernel keeps, `lnk_cap` of them, its counts {kept, the hook's list length}, and the hook's keep flags
+    int lnk_cap = 0, lnk_keep_cap = 0;
+    int *lnk_kept = nullptr, *lnk_cnt = nullptr, *lnk_keep = nullptr;
   } sift;
   // Hamming matcher (classic front end's binary descriptors): rows padded to 16 words
   int ham_cap = 0;
@@ -782,6 +787,22 @@ int brisk_pair_chain_enqueue(spvo_ctx *c, int rows, int cols, int cap, const Bri
                              const ChainOut &o, BriskDetKeypoint *h_kp);
 // ---- spvo_sift.hip
 void sift_release(spvo_ctx *c);      // frees spvo_ctx::sift (spvo_destroy)
+// The SIFT extractor as a link behind a detector that left records with an octave on the device (sift.hip.h: SiftLinkIO;
+// spvo_brisk_sift_pair, spvo_akaze_sift_pair).  sift_link_pair is the whole call around the detector -- spvo_classic_sift_pair's protocol:
+// slots, capacity, staging, temporal partner, prematch, one wait -- so that neither detector object copies it; the detector is three
+// functions.  Every refusal comes before anything is touched, every allocation (`prepare` included) before the first launch.
+struct SiftLinkDetector {
+  const char *who;                                   // the entry point, for the error text
+  int max_octave;                                    // the pyramid is built for octaves 0 .. max_octave, whichever the records name
+  std::function<int()> check;                        // what the detector's sibling refuses of its parameters and the shape
+  std::function<int(SiftLinkSrc &)> prepare;         // behind classic_image_ensure: the detector's buffers for the shape; where its list will lie
+  std::function<int(const uint8_t *)> enqueue;       // the staged image (pinned, rows packed) becomes the resident one and goes through the detector's chain
+};
+struct SiftLinkOut { int *n; void *kp; float *desc; int cap; };   // spvo_sift_features / spvo_akaze_sift_features, whose records differ
+// (SPVO_OK and SPVO_ERR_CAPACITY are answered behind the call's one wait: the chains of both images have run, and an AKAZE sink has left
+// image k's contrast factors in spvo_ctx::sift.h_n + 8 + 4 k)
+int sift_link_pair(spvo_ctx *c, const SiftLinkDetector &det, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int slot_l, int slot_r, int slot_capacity,
+                   const SiftLinkOut outs[2]);
 // ---- spvo_match.hip
 int ensure_match(spvo_ctx *c, int na, int nb);
 struct MatchReq {

@@ -11,6 +11,10 @@
 // spvo_classic_sift_pair is that extractor behind the Shi-Tomasi / FAST detector for both images of a stereo pair, the list never leaving
 // the device: detector chain (spvo_classic.hip), base level, the describe kernel into a SIFT slot; spvo_sift_detect_pair's staging, slots,
 // prematch and temporal partner.
+// sift_link_pair is the same protocol around a detector that reports an octave (BRISK, AKAZE: spvo_brisk_sift_pair and spvo_akaze_sift_pair
+// in the detectors' objects hand it their chain as three functions): the extractor's pyramid for octaves 0 .. the detector's highest,
+// reduced to the levels a layer-0 record reads, and the describe kernel on the records where they lie (SiftLinkIO).  spvo_sift_link_debug
+// runs that link on a caller's list.
 #include "spvo_internal.hip.h"
 #include "sift.hip.h"
 
@@ -87,8 +91,10 @@ int sift_ensure(spvo_ctx *c, int rows, int cols, size_t pyr_floats, int cand_cap
 // the pyramid of the u8 image `src` (rows x cols, packed): 1 + 5 launches per octave.  doubled: the base is the 2x upsampled image (first
 // octave -1), else the image at its own size (first octave 0: spvo_sift_describe).  with_dog: every difference of Gaussians is written by
 // the blur that completes it; without, P holds Gaussian levels only.  base_only: ONE launch, layer 0 of the first octave (records that all lie
-// there: spvo_classic_sift_pair)
-int sift_enqueue_pyramid(spvo_ctx *c, const uint8_t *src, int rows, int cols, const SiftPyr &P, bool doubled = true, bool with_dog = true, bool base_only = false) {
+// there: spvo_classic_sift_pair).  link: only the levels a list reads whose records all have layer 0 -- layers 0 .. 3 of every octave
+// but the last (the next octave derives from layer 3) and layer 0 of the last (layer 1 comes with the same launch when the octave is not
+// the first); a layer depends only on the one before, so these are bit for bit the levels of the full pyramid
+int sift_enqueue_pyramid(spvo_ctx *c, const uint8_t *src, int rows, int cols, const SiftPyr &P, bool doubled = true, bool with_dog = true, bool base_only = false, bool link = false) {
   hipStream_t st = c->stream2;
   const double k = std::pow(2.0, 1.0 / 3.0), sigma = 1.6;
   SiftTaps tp[SIFT_GAUSS];
@@ -102,16 +108,17 @@ int sift_enqueue_pyramid(spvo_ctx *c, const uint8_t *src, int rows, int cols, co
     const size_t lvl = (size_t)h * w;
     float *G = P.pyr + P.g_off[o], *D = with_dog ? P.pyr + P.d_off[o] : nullptr;
     const dim3 grid((w + SIFT_TW - 1) / SIFT_TW, (h + SIFT_TH - 1) / SIFT_TH);
+    const int top = !link ? SIFT_GAUSS - 1 : o == P.n_oct - 1 ? 0 : SIFT_LAYERS;   // the highest layer built
     if (o == 0) {
       if (doubled) hipLaunchKernelGGL(sift_blur_kernel<2>, grid, dim3(256), 0, st, (const void *)src, rows, cols, G, (float *)nullptr, (float *)nullptr, h, w, tp[0]);
       else hipLaunchKernelGGL(sift_blur_kernel<3>, grid, dim3(256), 0, st, (const void *)src, rows, cols, G, (float *)nullptr, (float *)nullptr, h, w, tp[0]);
-      if (base_only) break;
+      if (base_only || top == 0) break;
       hipLaunchKernelGGL(sift_blur_kernel<0>, grid, dim3(256), 0, st, (const void *)G, h, w, G + lvl, D, (float *)nullptr, h, w, tp[1]);
     } else {
       const float *below = P.pyr + P.g_off[o - 1] + (size_t)SIFT_LAYERS * P.h[o - 1] * P.w[o - 1];
       hipLaunchKernelGGL(sift_blur_kernel<1>, grid, dim3(256), 0, st, (const void *)below, P.h[o - 1], P.w[o - 1], G + lvl, D, G, h, w, tp[1]);
     }
-    for (int i = 2; i < SIFT_GAUSS; ++i)
+    for (int i = 2; i <= top; ++i)
       hipLaunchKernelGGL(sift_blur_kernel<0>, grid, dim3(256), 0, st, (const void *)(G + (size_t)(i - 1) * lvl), h, w, G + (size_t)i * lvl, D ? D + (size_t)(i - 1) * lvl : nullptr, (float *)nullptr,
                          h, w, tp[i]);
   }
@@ -220,7 +227,7 @@ int sift_slots_ensure(spvo_ctx *c, int cap, size_t px) {
       return rc;
   HIP_TRY(c, hipHostMalloc((void **)&s.h_src, (size_t)2 * cap * sizeof(SiftSrc)));
   HIP_TRY(c, hipHostMalloc((void **)&s.hm_desc, (size_t)2 * cap * 128 * sizeof(float)));
-  HIP_TRY(c, hipHostMalloc((void **)&s.h_n, 2 * 4 * sizeof(int)));
+  HIP_TRY(c, hipHostMalloc((void **)&s.h_n, 4 * 4 * sizeof(int)));
   HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
   s.slot_cap = cap;
   return SPVO_OK;
@@ -273,13 +280,178 @@ void sift_record_prematch(spvo_ctx *c, int slot_l, const int partner[2]) {
     ++job;
   }
 }
+
+// spvo_sift_describe's (and spvo_sift_link_debug's) device copies of a caller's n records and their rows
+int sift_given_ensure(spvo_ctx *c, int n) {
+  auto &s = c->sift;
+  if (n <= s.given_cap) return SPVO_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream2));
+  dev_free(s.given_kp, s.given_desc);
+  const int cap = (int)std::min<long long>(std::max<long long>(n, 2ll * s.given_cap), 0x7FFFFFFF);   // (grown geometrically: a count that creeps up reallocates rarely)
+  s.given_cap = 0;
+  int rc;
+  if ((rc = dev_alloc(c, &s.given_kp, cap, false)) || (rc = dev_alloc(c, &s.given_desc, (size_t)cap * 128, false))) return rc;
+  s.given_cap = cap;
+  return SPVO_OK;
+}
+
+// the pyramid buffer grown to `pyr_floats`
+int sift_pyr_ensure(spvo_ctx *c, size_t pyr_floats) {
+  auto &s = c->sift;
+  if (pyr_floats <= s.pyr_cap) return SPVO_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream2));
+  dev_free(s.pyr);
+  s.pyr_cap = 0;
+  if (int rc = dev_alloc(c, &s.pyr, pyr_floats, false)) return rc;
+  s.pyr_cap = pyr_floats;
+  return SPVO_OK;
+}
+
+// ---- the link behind a detector whose records carry an octave (spvo_brisk_sift_pair, spvo_akaze_sift_pair, spvo_sift_link_debug)
+// the Gaussian-only pyramid of a rows x cols image at its own size, octaves 0 .. max_octave: spvo_sift_describe's layout with first = 0
+size_t sift_link_plan(int rows, int cols, int max_octave, SiftPyr &P) {
+  P = SiftPyr{};
+  P.n_oct = max_octave + 1;
+  size_t off = 0;
+  for (int o = 0, h = rows, w = cols; o <= max_octave; ++o, h /= 2, w /= 2) {
+    P.h[o] = h; P.w[o] = w;
+    P.g_off[o] = (long long)off; P.d_off[o] = 0;
+    off += (size_t)SIFT_GAUSS * h * w;
+  }
+  return off;
+}
+
+// the host cannot see which octaves the records name, so the shape must have every octave the pyramid is built for
+int sift_link_check_octave(spvo_ctx *c, const char *who, int rows, int cols, int max_octave) {
+  if (max_octave < 0 || max_octave >= SIFT_MAX_OCT) return fail(c, SPVO_ERR_INVALID, "%s: max_octave must be 0 .. %d", who, SIFT_MAX_OCT - 1);
+  if ((std::min(rows, cols) >> max_octave) < 1)
+    return fail(c, SPVO_ERR_INVALID, "%s: a %d x %d image has no octave %d (the pyramid is built up to it, whichever octaves the keypoints name)", who, rows, cols, max_octave);
+  return SPVO_OK;
+}
+
+// the pyramid buffer, the counts and room for `list_cap` kept indices
+int sift_link_ensure(spvo_ctx *c, size_t pyr_floats, int list_cap) {
+  auto &s = c->sift;
+  if (int rc = sift_pyr_ensure(c, pyr_floats)) return rc;
+  if (!s.lnk_cnt) {
+    if (int rc = dev_alloc(c, &s.lnk_cnt, 4)) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
+  }
+  if (list_cap > s.lnk_cap) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream2));
+    dev_free(s.lnk_kept);
+    s.lnk_cap = 0;
+    if (int rc = dev_alloc(c, &s.lnk_kept, (size_t)list_cap, false)) return rc;
+    s.lnk_cap = list_cap;
+  }
+  return SPVO_OK;
+}
+
+// Behind a detector's chain on the image resident in spvo_ctx::cls: the keep flags as a list of indices (where the list has flags or
+// `compact` asks for the list anyway), the pyramid's levels that are read, and the describe launch on spvo_classic_sift_pair's fixed grid --
+// FORM 0, the kernel body of spvo_sift_describe -- with the count read on the device
+int sift_link_enqueue(spvo_ctx *c, int rows, int cols, const SiftPyr &P, SiftLinkIO io, bool compact) {
+  auto &s = c->sift;
+  hipStream_t st = c->stream2;
+  if (io.s.keep || compact) {
+    hipLaunchKernelGGL(sift_link_compact_kernel, dim3(1), dim3(1024), 0, st, io.s.keep, io.s.n_ptr, std::min(io.s.n_cap, s.lnk_cap), s.lnk_kept, s.lnk_cnt);
+    io.kept = s.lnk_kept; io.n_kept = s.lnk_cnt;
+  } else {
+    io.kept = io.n_kept = nullptr;
+  }
+  if (int rc = sift_enqueue_pyramid(c, c->cls.im, rows, cols, P, false, false, false, true)) return rc;
+  io.max_octave = P.n_oct - 1;
+  const int waves = std::min(std::max(tuning("sift_pair_waves_per_cu", 4), 1), 64) * c->num_cus;   // (diagnostic: the grid NOTES.md measures the default against)
+  hipLaunchKernelGGL((sift_describe_given_kernel<0, SiftLinkIO>), dim3(waves), dim3(64), 0, st, P, 0, io);
+  HIP_TRY(c, hipGetLastError());
+  return SPVO_OK;
+}
 }  // namespace
+
+// A detector that reports an octave + SIFT of a stereo pair into two SIFT slots: spvo_classic_sift_pair's protocol around the detector's
+// chain (det.enqueue) and sift_link_enqueue, image by image in stream order.  The detector's lists, the kept indices and the pyramid are
+// the left image's first and the right image's afterwards: the describe launch of an image, the last of its chain, has put its counts
+// into the pinned h_n before the next image's chain clears anything.  A slot's d_src holds the SiftKey records; the mirror h_src holds the
+// detector's own records, `stride` bytes each.
+int spvo_int::sift_link_pair(spvo_ctx *c, const SiftLinkDetector &det, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int slot_l, int slot_r,
+                             int slot_capacity, const SiftLinkOut outs[2]) {
+  static_assert(sizeof(SiftKey) <= sizeof(SiftSrc) && sizeof(AkazeKp) <= sizeof(SiftSrc), "a slot's source array and its mirror hold the records");
+  const char *who = det.who;
+  if (slot_l < 0 || slot_l >= N_SIFT_SLOTS || slot_r < 0 || slot_r >= N_SIFT_SLOTS || slot_l == slot_r) return fail(c, SPVO_ERR_INVALID, "bad slot");
+  for (int k = 0; k < 2; ++k)
+    if (outs[k].cap < 0 || (outs[k].cap > 0 && (!outs[k].kp || !outs[k].desc))) return fail(c, SPVO_ERR_INVALID, "bad output buffer");
+  const int cap = slot_capacity;
+  if (cap <= 0 || cap > SIFT_SLOT_MAX) return fail(c, SPVO_ERR_INVALID, "slot_capacity must be 1 .. %d", SIFT_SLOT_MAX);
+  if (int rc = det.check()) return rc;
+  if (int rc = sift_check_image(c, who, rows, cols)) return rc;
+  if (int rc = sift_link_check_octave(c, who, rows, cols, det.max_octave)) return rc;
+  if (int rc = require_idle(c)) return rc;
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  *outs[0].n = *outs[1].n = 0;
+  auto &s = c->sift;
+  PairStage &ps = s.pair;
+  hipStream_t st = c->stream2;
+  const size_t px = (size_t)rows * cols;
+  s.rows = s.cols = 0;   // the pyramid buffer holds the levels that are read of each image in turn: nothing spvo_sift_debug_level could serve
+  SiftPyr P{};
+  const size_t pyr_floats = sift_link_plan(rows, cols, det.max_octave, P);
+  SiftLinkSrc src{};
+  // every allocation before the first launch of the chain; the image buffer before the detector's layout, which points into it
+  int rc;
+  if ((rc = classic_image_ensure(c, rows, cols)) || (rc = det.prepare(src))) return rc;
+  if (src.stride <= 0 || src.stride % 4 || src.stride > (int)sizeof(SiftSrc)) return fail(c, SPVO_ERR_STATE, "%s: records of %d bytes", who, src.stride);
+  if ((rc = sift_link_ensure(c, pyr_floats, src.keep ? src.n_cap : 0)) || (rc = sift_slots_ensure(c, cap, px)) || (rc = sift_prematch_ensure(c))) return rc;
+  P.pyr = s.pyr;
+  // both slots are being rewritten: whatever was matched against their old contents is stale
+  const int slots[2] = {slot_l, slot_r};
+  for (int sl : slots) slot_rewrite(s.slots[sl]);
+  ps.mcache.invalidate();
+  // (the temporal partner is forgotten BEFORE staging, as in spvo_sift_detect_pair: a call that fails from now on leaves none for the next call)
+  const int partner[2] = {slot_r, ps.temporal_partner(slot_l, slot_r, ps.last_slot_l >= 0 && s.slots[ps.last_slot_l].filled)};
+  ps.last_slot_l = -1;
+  HIP_TRY(c, hipStreamSynchronize(st));   // (the staging buffer and the mirrors are the previous call's until its work is done)
+  ps.stage(img_l, img_r, rows, cols, stride);
+  // a match of an earlier call may still read the slots where the L2 matcher runs
+  if (s.match_pending) HIP_TRY(c, hipStreamWaitEvent(st, ps.ev_match, 0));
+  char *const h_rec = reinterpret_cast<char *>(s.h_src);
+  for (int k = 0; k < 2; ++k) {   // left chain, then the right one
+    if ((rc = det.enqueue(ps.h_img + k * px))) return rc;
+    const SiftSlot &t = s.slots[slots[k]];
+    SiftLinkIO io{};
+    io.s = src;
+    io.slot_cap = cap;
+    io.s_desc = t.d_desc; io.s_sqn = t.d_sqn; io.s_rec = reinterpret_cast<SiftKey *>(t.d_src); io.d_n = t.d_n;
+    io.h_desc = s.hm_desc + (size_t)k * s.slot_cap * 128;
+    io.h_rec = h_rec + (size_t)k * s.slot_cap * sizeof(SiftSrc);
+    io.h_n = s.h_n + 4 * k; io.h_k = s.h_n + 8 + 4 * k;
+    if ((rc = sift_link_enqueue(c, rows, cols, P, io, false))) return rc;
+  }
+  HIP_TRY(c, hipEventRecord(ps.ev_feat, st));
+  if ((rc = sift_enqueue_prematch(c, slot_l, partner))) return rc;   // (a pair that turns out not to fit its slots: that result is dropped below)
+  HIP_TRY(c, wait_event(ps.ev_feat));   // the one wait of the call: the matches go on behind it
+  for (int k = 0; k < 2; ++k) *outs[k].n = s.h_n[4 * k];
+  // (the detectors size their lists from the image, so the flag cannot be set; were it, the counts would be wrong)
+  if (s.h_n[1] || s.h_n[5]) return fail(c, SPVO_ERR_STATE, "%s: the candidate list overflowed although it is sized from the image", who);
+  if (*outs[0].n > cap || *outs[1].n > cap) return fail(c, SPVO_ERR_CAPACITY, "%s: %d / %d rows do not fit slots of %d (slot_capacity)", who, *outs[0].n, *outs[1].n, cap);
+  for (int k = 0; k < 2; ++k) {
+    SiftSlot &t = s.slots[slots[k]];
+    t.n = *outs[k].n; t.filled = true;
+    const int ncopy = std::min(t.n, outs[k].cap);
+    if (ncopy > 0) {
+      std::memcpy(outs[k].kp, h_rec + (size_t)k * s.slot_cap * sizeof(SiftSrc), (size_t)ncopy * src.stride);
+      std::memcpy(outs[k].desc, s.hm_desc + (size_t)k * s.slot_cap * 128, (size_t)ncopy * 128 * sizeof(float));
+    }
+  }
+  sift_record_prematch(c, slot_l, partner);
+  ps.last_slot_l = slot_l;
+  return SPVO_OK;
+}
 
 void spvo_int::sift_release(spvo_ctx *c) {
   auto &s = c->sift;
   sift_release_slots(c);
-  dev_free(s.img, s.pyr, s.desc, s.cand_pos, s.cand_off, s.kp, s.counters, s.keys, s.sorted, s.order, s.ord_n, s.given_kp, s.given_desc);
-  s.given_cap = 0;
+  dev_free(s.img, s.pyr, s.desc, s.cand_pos, s.cand_off, s.kp, s.counters, s.keys, s.sorted, s.order, s.ord_n, s.given_kp, s.given_desc, s.lnk_kept, s.lnk_cnt, s.lnk_keep);
+  s.given_cap = s.lnk_cap = s.lnk_keep_cap = 0;
   host_free(s.h_match);
   s.h_match_cap = 0;
   s.pair.release();
@@ -465,13 +637,7 @@ int spvo_classic_sift_pair(spvo_ctx *c, const spvo_classic_opts *opts, const uin
   const size_t px = (size_t)rows * cols;
   s.rows = s.cols = 0;   // the pyramid buffer holds one level of each image in turn: nothing spvo_sift_debug_level could serve
   if (int rc = classic_image_ensure(c, rows, cols)) return rc;
-  if (px > s.pyr_cap) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    dev_free(s.pyr);
-    s.pyr_cap = 0;
-    if (int rc = dev_alloc(c, &s.pyr, px, false)) return rc;
-    s.pyr_cap = px;
-  }
+  if (int rc = sift_pyr_ensure(c, px)) return rc;
   if (int rc = sift_slots_ensure(c, cap, px)) return rc;
   if (int rc = sift_prematch_ensure(c)) return rc;
   SiftPyr P{};
@@ -572,22 +738,8 @@ int spvo_sift_describe(spvo_ctx *c, const uint8_t *img, int rows, int cols, size
     pyr_floats += (size_t)SIFT_GAUSS * h * w;
   }
   s.rows = s.cols = 0;   // nothing resident until the pyramid is enqueued
-  if (pyr_floats > s.pyr_cap) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    dev_free(s.pyr);
-    s.pyr_cap = 0;
-    if (int rc = dev_alloc(c, &s.pyr, pyr_floats, false)) return rc;
-    s.pyr_cap = pyr_floats;
-  }
-  if (n > s.given_cap) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    dev_free(s.given_kp, s.given_desc);
-    const int cap = (int)std::min<long long>(std::max<long long>(n, 2ll * s.given_cap), 0x7FFFFFFF);   // (grown geometrically: a count that creeps up reallocates rarely)
-    s.given_cap = 0;
-    int rc;
-    if ((rc = dev_alloc(c, &s.given_kp, cap, false)) || (rc = dev_alloc(c, &s.given_desc, (size_t)cap * 128, false))) return rc;
-    s.given_cap = cap;
-  }
+  if (int rc = sift_pyr_ensure(c, pyr_floats)) return rc;
+  if (int rc = sift_given_ensure(c, n)) return rc;
   P.pyr = s.pyr;
   HIP_TRY(c, hipMemcpyAsync(s.given_kp, kp, (size_t)n * sizeof(SiftKey), hipMemcpyHostToDevice, st));
   if (int rc = sift_enqueue_pyramid(c, b.im, rows, cols, P, first < 0, false)) return rc;
@@ -600,6 +752,73 @@ int spvo_sift_describe(spvo_ctx *c, const uint8_t *img, int rows, int cols, size
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(desc, s.given_desc, (size_t)n * 128 * sizeof(float), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));   // the one wait of the call
+  return SPVO_OK;
+}
+
+// The link of spvo_brisk_sift_pair / spvo_akaze_sift_pair on a caller's list (test hook): sift_link_enqueue -- compaction by the keep flags,
+// the levels that are read of octaves 0 .. max_octave, the describe launch on the fixed grid with the count read on the device -- against the
+// image already resident.  Everything a record can be refused for is checked before anything is touched.
+int spvo_sift_link_debug(spvo_ctx *c, int rows, int cols, const spvo_sift_keypoint *kp, const uint8_t *keep, int n, int max_octave, int32_t *kept, float *desc, int *n_kept) {
+  static_assert(sizeof(spvo_sift_keypoint) == sizeof(SiftKey), "keypoint records differ");
+  if (!c || !n_kept || rows <= 0 || cols <= 0 || n < 0 || (n > 0 && (!kp || !kept || !desc))) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  if (int rc = sift_check_image(c, "spvo_sift_link_debug", rows, cols)) return rc;
+  if (int rc = sift_link_check_octave(c, "spvo_sift_link_debug", rows, cols, max_octave)) return rc;
+  for (int i = 0; i < n; ++i) {
+    const spvo_sift_keypoint &k = kp[i];
+    if (!std::isfinite(k.x) || !std::isfinite(k.y) || !std::isfinite(k.size) || !std::isfinite(k.angle) || !(k.size > 0))
+      return fail(c, SPVO_ERR_INVALID, "spvo_sift_link_debug: keypoint %d has x %g, y %g, size %g, angle %g", i, (double)k.x, (double)k.y, (double)k.size, (double)k.angle);
+    int o = k.octave & 255;
+    if (o >= 128) o -= 256;
+    const int layer = (k.octave >> 8) & 255;
+    if (o < 0 || o > max_octave || layer != 0)
+      return fail(c, SPVO_ERR_INVALID, "spvo_sift_link_debug: keypoint %d has octave %d, layer %d (octaves 0 .. %d, layer 0: the link builds no other level)", i, o, layer, max_octave);
+  }
+  if (int rc = require_idle(c)) return rc;
+  auto &b = c->cls;
+  if (b.rows != rows || b.cols != cols) return fail(c, SPVO_ERR_STATE, "spvo_sift_link_debug: no image of %d x %d is resident (call a detector first)", rows, cols);
+  *n_kept = 0;
+  if (n == 0) return SPVO_OK;
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  auto &s = c->sift;
+  hipStream_t st = c->stream2;
+  SiftPyr P{};
+  const size_t pyr_floats = sift_link_plan(rows, cols, max_octave, P);
+  s.rows = s.cols = 0;   // the pyramid buffer will hold the levels the link reads: nothing spvo_sift_debug_level could serve
+  int rc;
+  if ((rc = sift_link_ensure(c, pyr_floats, n)) || (rc = sift_given_ensure(c, n))) return rc;
+  if (keep && n > s.lnk_keep_cap) {
+    HIP_TRY(c, hipStreamSynchronize(st));
+    dev_free(s.lnk_keep);
+    s.lnk_keep_cap = 0;
+    if ((rc = dev_alloc(c, &s.lnk_keep, (size_t)n, false))) return rc;
+    s.lnk_keep_cap = n;
+  }
+  P.pyr = s.pyr;
+  std::vector<int> flags, h_kept((size_t)n);
+  std::vector<float> h_desc((size_t)n * 128);
+  HIP_TRY(c, hipStreamSynchronize(st));   // (the pageable copies below read the caller's and these buffers when they are enqueued)
+  HIP_TRY(c, hipMemcpyAsync(s.given_kp, kp, (size_t)n * sizeof(SiftKey), hipMemcpyHostToDevice, st));
+  if (keep) {
+    flags.assign(keep, keep + n);
+    HIP_TRY(c, hipMemcpyAsync(s.lnk_keep, flags.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(c, hipMemcpyAsync(s.lnk_cnt + 1, &n, sizeof(int), hipMemcpyHostToDevice, st));
+  SiftLinkIO io{};
+  io.s = SiftLinkSrc{reinterpret_cast<const char *>(s.given_kp), (int)sizeof(SiftKey), (int)offsetof(SiftKey, x), (int)offsetof(SiftKey, y), (int)offsetof(SiftKey, size),
+                     (int)offsetof(SiftKey, angle), (int)offsetof(SiftKey, response), (int)offsetof(SiftKey, octave), keep ? s.lnk_keep : nullptr, s.lnk_cnt + 1, n, nullptr, nullptr, 0};
+  io.slot_cap = n;
+  io.h_desc = s.given_desc;
+  if ((rc = sift_link_enqueue(c, rows, cols, P, io, true))) return rc;
+  // into staging first: a failure below leaves the caller's buffers as they were
+  int m = 0;
+  HIP_TRY(c, hipMemcpyAsync(&m, s.lnk_cnt, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(h_kept.data(), s.lnk_kept, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(h_desc.data(), s.given_desc, (size_t)n * 128 * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));   // the one wait of the call
+  m = std::min(std::max(m, 0), n);
+  std::memcpy(kept, h_kept.data(), (size_t)m * sizeof(int));
+  std::memcpy(desc, h_desc.data(), (size_t)m * 128 * sizeof(float));
+  *n_kept = m;
   return SPVO_OK;
 }
 

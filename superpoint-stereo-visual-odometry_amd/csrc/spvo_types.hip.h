@@ -124,4 +124,17 @@ constexpr int AKAZE_STAT_NCAND = 0, AKAZE_STAT_OVERFLOW = 1, AKAZE_STAT_MAX = 2,
 // device and what the buffer holds at most
 struct OrbLinkSrc { const char *rec; int stride, off_x, off_y, off_octave; const int *keep; const int *n_ptr; int n_cap; };
 
+// ---- the link from a detector's record list to the SIFT extractor (sift.hip.h: spvo_brisk_sift_pair, spvo_akaze_sift_pair,
+// spvo_sift_link_debug): the same description of where the list lies, with every field the extractor reads (x, y, size, angle, response:
+// float; octave: int32) at its byte offset -- `stride` is a multiple of 4, the whole record travels to the host's mirror -- and where the
+// detector's overflow flag is: det_counters[3] (BRISK), or stat (AKAZE_STAT_*) against cand_cap (AKAZE), or neither
+struct SiftLinkSrc {
+  const char *rec;
+  int stride, off_x, off_y, off_size, off_angle, off_response, off_octave;
+  const int *keep, *n_ptr;
+  int n_cap;
+  const int *det_counters, *stat;
+  int cand_cap;
+};
+
 }  // namespace spvo

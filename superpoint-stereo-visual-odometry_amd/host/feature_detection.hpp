@@ -357,6 +357,11 @@ public:
   // refusal does not list them.  setOctavePairsResident: BRISK + ORB, AKAZE + ORB (both still need setOrbExtractorOctaves to run at all) and
   // AKAZE + BRISK take their routes (spvo_brisk_orb_pair, spvo_akaze_orb_pair, spvo_akaze_brisk_pair) only with this as well as
   // setDeviceResident; a shape an ORB pair call refuses (its top pyramid level below 32 x 32) takes the per-image path and is not counted.
+  // setSiftOctavePairsResident: BRISK + SIFT and AKAZE + SIFT take their routes (spvo_brisk_sift_pair, spvo_akaze_sift_pair: detector, the
+  // levels of the SIFT pyramid its records can name and the descriptor on the device, rows into the SIFT slots) only with this as well as
+  // setDeviceResident -- a switch of its own, so that no combination of the earlier switches changes route; a shape the pair call refuses
+  // (it lacks the detector's highest octave: BRISK 5, AKAZE that of the shape's last level) takes the per-image path and is not counted.
+  // ORB + SIFT has no route: the ORB detector keeps a pyramid and an image of its own, and its records name octaves up to 7.
   static void setDeviceResident(bool on);
   static void setResidentCapacity(int rows);   // rows per binary slot [8192]
   static void setBriskPairResident(bool on);   // [off]
@@ -365,7 +370,8 @@ public:
   static void setSiftDescribeResident(bool on);   // [off]
   static void setOrbExtractorOctaves(bool on);    // [off]
   static void setOctavePairsResident(bool on);    // [off]
-  // pairs that actually stayed resident (spvo_classic_detect / spvo_sift_detect_pair / spvo_brisk_detect_pair / spvo_akaze_detect_pair / spvo_classic_sift_pair / spvo_brisk_orb_pair / spvo_akaze_orb_pair / spvo_akaze_brisk_pair returned SPVO_OK): what tells the resident path from its fallback
+  static void setSiftOctavePairsResident(bool on);   // [off]
+  // pairs that actually stayed resident (spvo_classic_detect / spvo_sift_detect_pair / spvo_brisk_detect_pair / spvo_akaze_detect_pair / spvo_classic_sift_pair / spvo_brisk_orb_pair / spvo_akaze_orb_pair / spvo_akaze_brisk_pair / spvo_brisk_sift_pair / spvo_akaze_sift_pair returned SPVO_OK): what tells the resident path from its fallback
   unsigned residentPairs() const { return resident_ok_pairs_; }
 
 private:
@@ -376,6 +382,7 @@ private:
   bool sift_describe_resident_ = false;   // setSiftDescribeResident at construction
   bool orb_octaves_ = false;           // setOrbExtractorOctaves at construction
   bool octave_pairs_resident_ = false;   // setOctavePairsResident at construction
+  bool sift_octave_pairs_resident_ = false;   // setSiftOctavePairsResident at construction
   bool pairRuns() const;               // this detector / descriptor pair runs in this build
   int resident_capacity_ = 8192;
   unsigned resident_pairs_ = 0;   // pairs handed to a resident route: pair k lives in slots 2 (k % 4), 2 (k % 4) + 1

@@ -17,6 +17,7 @@ static bool g_classic_akaze_pair_resident = false;
 static bool g_classic_sift_describe_resident = false;
 static bool g_classic_orb_octaves = false;
 static bool g_classic_octave_pairs_resident = false;
+static bool g_classic_sift_octave_pairs_resident = false;
 void ClassicFeatureFrontEnd::setDeviceResident(bool on) { g_classic_resident = on; }
 void ClassicFeatureFrontEnd::setBriskPairResident(bool on) { g_classic_brisk_pair_resident = on; }
 void ClassicFeatureFrontEnd::setAkazeDescriptor(bool on) { g_classic_akaze_descriptor = on; }
@@ -24,6 +25,7 @@ void ClassicFeatureFrontEnd::setAkazePairResident(bool on) { g_classic_akaze_pai
 void ClassicFeatureFrontEnd::setSiftDescribeResident(bool on) { g_classic_sift_describe_resident = on; }
 void ClassicFeatureFrontEnd::setOrbExtractorOctaves(bool on) { g_classic_orb_octaves = on; }
 void ClassicFeatureFrontEnd::setOctavePairsResident(bool on) { g_classic_octave_pairs_resident = on; }
+void ClassicFeatureFrontEnd::setSiftOctavePairsResident(bool on) { g_classic_sift_octave_pairs_resident = on; }
 void ClassicFeatureFrontEnd::setResidentCapacity(int rows) { g_classic_resident_capacity = rows; }
 
 #ifdef SPVO_USE_OPENCV
@@ -95,8 +97,8 @@ bool ClassicFeatureFrontEnd::available() { return true; }
 
 enum class Detect { Orb, Gftt, Fast, Sift, Brisk, Akaze };       // detectKeypoints: spvo_<this>_detect
 enum class Describe { WithDetector, Orb, Brisk, Akaze, Sift };   // describeKeypoints: the rows detectKeypoints kept, or spvo_<this>_describe on the given keypoints
-enum class Route { None, Classic, SiftPair, BriskPair, AkazePair, ClassicSift, BriskOrbPair, AkazeOrbPair, AkazeBriskPair };   // setDeviceResident: the per-image path, spvo_classic_detect (kind), spvo_sift_detect_pair, spvo_brisk_detect_pair, spvo_akaze_detect_pair, spvo_classic_sift_pair (kind), spvo_brisk_orb_pair, spvo_akaze_orb_pair, spvo_akaze_brisk_pair
-enum class OptIn { None, AkazeDescriptor, OrbOctaves, BriskPairResident, AkazePairResident, SiftDescribeResident, OctavePairsResident };   // to run at all: setAkazeDescriptor, setOrbExtractorOctaves; to stay resident: setBriskPairResident, setAkazePairResident, setSiftDescribeResident, setOctavePairsResident
+enum class Route { None, Classic, SiftPair, BriskPair, AkazePair, ClassicSift, BriskOrbPair, AkazeOrbPair, AkazeBriskPair, BriskSiftPair, AkazeSiftPair };   // setDeviceResident: the per-image path, spvo_classic_detect (kind), spvo_sift_detect_pair, spvo_brisk_detect_pair, spvo_akaze_detect_pair, spvo_classic_sift_pair (kind), spvo_brisk_orb_pair, spvo_akaze_orb_pair, spvo_akaze_brisk_pair, spvo_brisk_sift_pair, spvo_akaze_sift_pair
+enum class OptIn { None, AkazeDescriptor, OrbOctaves, BriskPairResident, AkazePairResident, SiftDescribeResident, OctavePairsResident, SiftOctavePairsResident };   // to run at all: setAkazeDescriptor, setOrbExtractorOctaves; to stay resident: setBriskPairResident, setAkazePairResident, setSiftDescribeResident, setOctavePairsResident, setSiftOctavePairsResident
 
 struct ClassicPair {
   DetectorType detector;
@@ -123,9 +125,10 @@ static const ClassicPair kClassicPairs[] = {
     {DetectorType::SIFT, DescriptorType::SIFT, Detect::Sift, 0.f, Describe::WithDetector, 128, CV_32FC1, Route::SiftPair, 0, OptIn::None, OptIn::None},
     {DetectorType::ShiTomasi, DescriptorType::SIFT, Detect::Gftt, 5.f, Describe::Sift, 128, CV_32FC1, Route::ClassicSift, SPVO_CLASSIC_GFTT_SIFT, OptIn::None, OptIn::SiftDescribeResident},
     {DetectorType::FAST, DescriptorType::SIFT, Detect::Fast, 7.f, Describe::Sift, 128, CV_32FC1, Route::ClassicSift, SPVO_CLASSIC_FAST_SIFT, OptIn::None, OptIn::SiftDescribeResident},
+    // (ORB + SIFT has no route: the ORB detector keeps a pyramid and an image of its own, not the shared resident image, and its records name octaves up to 7)
     {DetectorType::ORB, DescriptorType::SIFT, Detect::Orb, 0.f, Describe::Sift, 128, CV_32FC1, Route::None, 0, OptIn::None, OptIn::None},
-    {DetectorType::BRISK, DescriptorType::SIFT, Detect::Brisk, 0.f, Describe::Sift, 128, CV_32FC1, Route::None, 0, OptIn::None, OptIn::None},
-    {DetectorType::AKAZE, DescriptorType::SIFT, Detect::Akaze, 0.f, Describe::Sift, 128, CV_32FC1, Route::None, 0, OptIn::None, OptIn::None},
+    {DetectorType::BRISK, DescriptorType::SIFT, Detect::Brisk, 0.f, Describe::Sift, 128, CV_32FC1, Route::BriskSiftPair, 0, OptIn::None, OptIn::SiftOctavePairsResident},
+    {DetectorType::AKAZE, DescriptorType::SIFT, Detect::Akaze, 0.f, Describe::Sift, 128, CV_32FC1, Route::AkazeSiftPair, 0, OptIn::None, OptIn::SiftOctavePairsResident},
     // the ORB extractor on keypoints that carry an octave (spvo_orb_describe_octaves): only with setOrbExtractorOctaves, and listed only then
     {DetectorType::BRISK, DescriptorType::ORB, Detect::Brisk, 0.f, Describe::Orb, 32, CV_8UC1, Route::BriskOrbPair, 0, OptIn::OrbOctaves, OptIn::OctavePairsResident},
     {DetectorType::AKAZE, DescriptorType::ORB, Detect::Akaze, 0.f, Describe::Orb, 32, CV_8UC1, Route::AkazeOrbPair, 0, OptIn::OrbOctaves, OptIn::OctavePairsResident},
@@ -490,7 +493,8 @@ bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &img_l, cv::Mat 
   if (!image_ok(img_l) || !image_ok(img_r) || (size_t)img_l.step != (size_t)img_r.step) return false;
   const ClassicPair &p = *pair();   // (addStereoImagePair has asked pairRuns)
   if (p.route == Route::None || (p.resident_opt_in == OptIn::BriskPairResident && !brisk_pair_resident_) || (p.resident_opt_in == OptIn::AkazePairResident && !akaze_pair_resident_) ||
-      (p.resident_opt_in == OptIn::SiftDescribeResident && !sift_describe_resident_) || (p.resident_opt_in == OptIn::OctavePairsResident && !octave_pairs_resident_))
+      (p.resident_opt_in == OptIn::SiftDescribeResident && !sift_describe_resident_) || (p.resident_opt_in == OptIn::OctavePairsResident && !octave_pairs_resident_) ||
+      (p.resident_opt_in == OptIn::SiftOctavePairsResident && !sift_octave_pairs_resident_))
     return false;
   const uint8_t *l = img_l.ptr<uint8_t>(0), *r = img_r.ptr<uint8_t>(0);
   const int rows = img_l.rows, cols = img_l.cols;
@@ -545,6 +549,24 @@ bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &img_l, cv::Mat 
     return residentPair<spvo_akaze_features>(p, img_l, img_r, "spvo_akaze_brisk_pair", [&](int slot_l, int slot_r, spvo_akaze_features *f) {
       return spvo_akaze_brisk_pair(ctx_, l, r, rows, cols, step, 0.001f, slot_l, slot_r, resident_capacity_, &f[0], &f[1]);
     });
+  // The SIFT pairs build the extractor's pyramid up to the detector's highest octave (BRISK: 5; AKAZE: that of the shape's last level) and
+  // refuse a shape without that octave, where the per-image path asks only about the octaves its keypoints name: such a shape takes that
+  // path, uncounted (the orb_level_ok precedent)
+  case Route::BriskSiftPair:
+    if ((std::min(rows, cols) >> 5) < 1) return false;
+    return residentPair<spvo_sift_features>(p, img_l, img_r, "spvo_brisk_sift_pair", [&](int slot_l, int slot_r, spvo_sift_features *f) {
+      return spvo_brisk_sift_pair(ctx_, l, r, rows, cols, step, 30, 3, slot_l, slot_r, resident_capacity_, &f[0], &f[1]);
+    });
+  case Route::AkazeSiftPair: {
+    int levels = 0, n_tau = 0;
+    int32_t octave[16] = {0};
+    if (rows < 16 || cols < 16 || spvo_akaze_tables(rows, cols, &levels, octave, nullptr, nullptr, nullptr, nullptr, 0, &n_tau, nullptr, nullptr) != SPVO_OK || levels < 1 ||
+        (std::min(rows, cols) >> octave[levels - 1]) < 1)
+      return false;
+    return residentPair<spvo_akaze_sift_features>(p, img_l, img_r, "spvo_akaze_sift_pair", [&](int slot_l, int slot_r, spvo_akaze_sift_features *f) {
+      return spvo_akaze_sift_pair(ctx_, l, r, rows, cols, step, 0.001f, slot_l, slot_r, resident_capacity_, &f[0], &f[1]);
+    });
+  }
   case Route::None:
     break;
   }
@@ -578,6 +600,7 @@ ClassicFeatureFrontEnd::ClassicFeatureFrontEnd(const DetectorType detector_type,
   akaze_pair_resident_ = g_classic_akaze_pair_resident;
   sift_describe_resident_ = g_classic_sift_describe_resident;
   octave_pairs_resident_ = g_classic_octave_pairs_resident;
+  sift_octave_pairs_resident_ = g_classic_sift_octave_pairs_resident;
 }
 
 ClassicFeatureFrontEnd::~ClassicFeatureFrontEnd() {

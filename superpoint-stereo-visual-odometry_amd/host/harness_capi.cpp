@@ -447,6 +447,10 @@ void spvo_host_classic_set_orb_octaves(int on) { ClassicFeatureFrontEnd::setOrbE
 // through one spvo_brisk_orb_pair / spvo_akaze_orb_pair / spvo_akaze_brisk_pair per pair when setDeviceResident is on as well (off by default)
 void spvo_host_classic_set_octave_pairs_resident(int on) { ClassicFeatureFrontEnd::setOctavePairsResident(on != 0); }
 
+// ClassicFeatureFrontEnd::setSiftOctavePairsResident for the front ends constructed afterwards: BRISK + SIFT and AKAZE + SIFT through one
+// spvo_brisk_sift_pair / spvo_akaze_sift_pair per pair when setDeviceResident is on as well (off by default)
+void spvo_host_classic_set_sift_octave_pairs_resident(int on) { ClassicFeatureFrontEnd::setSiftOctavePairsResident(on != 0); }
+
 // the ORB + ORB front end at the native resolution (the export's first form)
 int spvo_host_classic_sequence(int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l, const double *P_r, int knn,
                                int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats, double *seconds) {

@@ -51,6 +51,10 @@ class SiftFeatures(C.Structure):
     _fields_ = [("n", C.c_int), ("kp", C.c_void_p), ("desc", C.c_void_p), ("cap", C.c_int)]
 
 
+class AkazeSiftFeatures(C.Structure):      # spvo_akaze_sift_features: AKAZE records (28 bytes), rows of 128 floats
+    _fields_ = [("n", C.c_int), ("kp", C.c_void_p), ("desc", C.c_void_p), ("cap", C.c_int)]
+
+
 class DetectMirrors(C.Structure):
     _fields_ = [("n", C.c_int * 2), ("xy", C.POINTER(C.c_float) * 2), ("desc", C.POINTER(C.c_float) * 2), ("resized", C.POINTER(C.c_uint8) * 2), ("token", C.c_int)]
 
@@ -94,7 +98,7 @@ SYMBOLS = [
     "spvo_default_config", "spvo_create", "spvo_destroy", "spvo_last_error", "spvo_load_weights", "spvo_engine_precision", "spvo_set_fp32_split",
     "spvo_preprocess", "spvo_forward", "spvo_debug_tensor", "spvo_heatmap", "spvo_nms",
     "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8",
-    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_orb_describe_octaves", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_akaze_describe", "spvo_akaze_detect_pair", "spvo_akaze_suppress_debug", "spvo_brisk_orb_pair", "spvo_akaze_orb_pair", "spvo_akaze_brisk_pair", "spvo_orb_octaves_link_debug", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_describe", "spvo_sift_detect_pair", "spvo_classic_sift_pair", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
+    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_orb_describe_octaves", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_akaze_describe", "spvo_akaze_detect_pair", "spvo_akaze_suppress_debug", "spvo_brisk_orb_pair", "spvo_akaze_orb_pair", "spvo_akaze_brisk_pair", "spvo_orb_octaves_link_debug", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_describe", "spvo_sift_detect_pair", "spvo_classic_sift_pair", "spvo_brisk_sift_pair", "spvo_akaze_sift_pair", "spvo_sift_link_debug", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
     "spvo_profile_enable", "spvo_profile_reset", "spvo_profile_only", "spvo_profile_count", "spvo_profile_get", "spvo_profile_stage_kernel", "spvo_profile_stage_variant",
     "spvo_set_tuning", "spvo_get_tuning", "spvo_clear_tuning",
     "spvo_comm_unique_id", "spvo_comm_available", "spvo_comm_create", "spvo_comm_create_host", "spvo_comm_rank", "spvo_comm_world", "spvo_comm_destroy",
@@ -171,6 +175,9 @@ def load() -> C.CDLL:
     lib.spvo_sift_debug_level.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, ip, ip]
     lib.spvo_sift_describe.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, vp]
     lib.spvo_sift_detect_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(SiftFeatures), C.POINTER(SiftFeatures)]
+    lib.spvo_brisk_sift_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(SiftFeatures), C.POINTER(SiftFeatures)]
+    lib.spvo_akaze_sift_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(AkazeSiftFeatures), C.POINTER(AkazeSiftFeatures)]
+    lib.spvo_sift_link_debug.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, ip]
     lib.spvo_classic_sift_pair.argtypes = [vp, C.POINTER(ClassicOpts), vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.POINTER(SiftFeatures), C.POINTER(SiftFeatures)]
     lib.spvo_sift_slot_rows.argtypes = [vp, C.c_int, ip]
     lib.spvo_match_l2_slots.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]
@@ -867,6 +874,62 @@ class Context:
             m = min(f.n, want)
             out.append(dict(kp=kp[:m].copy(), desc=desc[:m].copy(), n=f.n))
         return out[0], out[1]
+
+    def _sift_octave_pair(self, call, kp_dtype, features, img_l, img_r, params, slot_l, slot_r, slot_capacity, cap):
+        """classic_sift_pair's protocol around one of the two pair calls whose detector reports an octave."""
+        l, r = _u8_rows(img_l), _u8_rows(img_r)
+        if l.shape != r.shape or l.strides[0] != r.strides[0]:
+            l, r = np.ascontiguousarray(l), np.ascontiguousarray(r)
+            if l.shape != r.shape:
+                raise ValueError("the two images of a pair must have one shape")
+        want = int(slot_capacity) if cap is None else int(cap)
+        bufs, feats = [], []
+        for _ in range(2):
+            kp = np.zeros(max(want, 1), kp_dtype)
+            desc = np.zeros((max(want, 1), 128), np.float32)
+            bufs.append((kp, desc))
+            feats.append(features(0, kp.ctypes.data, desc.ctypes.data, want))
+        rc = call(self.h, _ptr(l), _ptr(r), l.shape[0], l.shape[1], l.strides[0], *params, slot_l, slot_r, int(slot_capacity), C.byref(feats[0]), C.byref(feats[1]))
+        if rc:
+            e = SpvoError(rc, self.lib.spvo_last_error(self.h).decode())
+            e.n_l, e.n_r = feats[0].n, feats[1].n
+            e.counts = (e.n_l, e.n_r)
+            raise e
+        self._resident_shape = r.shape
+        out = []
+        for (kp, desc), f in zip(bufs, feats):
+            m = min(f.n, max(want, 0))
+            out.append(dict(kp=kp[:m].copy(), desc=desc[:m].copy(), n=f.n))
+        return out[0], out[1]
+
+    def brisk_sift_pair(self, img_l, img_r, slot_l: int, slot_r: int, threshold: int = 30, octaves: int = 3, slot_capacity: int = 8192, cap: Optional[int] = None):
+        """One stereo pair through the BRISK detector and the SIFT extractor into two SIFT slots (spvo_brisk_sift_pair).  -> (left, right):
+        dicts of kp [m] (BRISK_KP_DTYPE: the detector's records, unchanged), desc [m, 128] float32 and n -- per image what brisk_detect()
+        followed by sift_describe(None, its records) returns.  Afterwards the right image is resident.  On SPVO_ERR_CAPACITY the SpvoError
+        carries the two counts as .counts."""
+        return self._sift_octave_pair(self.lib.spvo_brisk_sift_pair, BRISK_KP_DTYPE, SiftFeatures, img_l, img_r, (int(threshold), int(octaves)), slot_l, slot_r, slot_capacity, cap)
+
+    def akaze_sift_pair(self, img_l, img_r, slot_l: int, slot_r: int, threshold: float = 0.001, slot_capacity: int = 8192, cap: Optional[int] = None):
+        """The same behind the AKAZE detector (spvo_akaze_sift_pair): kp [m] AKAZE_KP_DTYPE records, unchanged (class_id included), desc
+        [m, 128] -- per image what akaze_detect() followed by sift_describe(None, its records without class_id) returns.  Afterwards the
+        right image and its scale space are resident."""
+        return self._sift_octave_pair(self.lib.spvo_akaze_sift_pair, AKAZE_KP_DTYPE, AkazeSiftFeatures, img_l, img_r, (float(threshold),), slot_l, slot_r, slot_capacity, cap)
+
+    def sift_link_debug(self, kp: np.ndarray, keep=None, max_octave: int = 5, shape=None):
+        """The two calls' device link and describe launch on a caller's list against the resident image (spvo_sift_link_debug): kp [n]
+        SIFT_KP_DTYPE records, keep [n] flags or None, shape as in sift_describe.  -> dict of kept [m] (indices into kp) and desc [m, 128],
+        as sift_describe(None, kp[kept])."""
+        kp = np.ascontiguousarray(kp, SIFT_KP_DTYPE).reshape(-1)
+        n = len(kp)
+        flags = None if keep is None else np.ascontiguousarray(np.asarray(keep) != 0, np.uint8).reshape(n)
+        kept = np.zeros(max(n, 1), np.int32)
+        desc = np.zeros((max(n, 1), 128), np.float32)
+        m = C.c_int(0)
+        rows, cols = shape if shape is not None else getattr(self, "_resident_shape", (0, 0))
+        if rows <= 0 or cols <= 0:
+            rows = cols = 64               # nothing remembered: let the library answer (SPVO_ERR_STATE)
+        self._check(self.lib.spvo_sift_link_debug(self.h, int(rows), int(cols), _ptr(kp), None if flags is None else _ptr(flags), n, int(max_octave), _ptr(kept), _ptr(desc), C.byref(m)))
+        return dict(kept=kept[:m.value].copy(), desc=desc[:m.value].copy())
 
     def sift_slot_rows(self, slot: int) -> int:
         n = C.c_int(0)

@@ -343,7 +343,7 @@ class FrontEnd:
 
 def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_threshold=2.0, refinement_degree=4, warm=0, detector="ORB", input_size=None, resident=False,
                      resident_capacity=0, trace=False, descriptor="ORB", brisk_resident=False, akaze_descriptor=False, akaze_resident=False, sift_describe_resident=False, orb_octaves=False,
-                     octave_pairs_resident=False):
+                     octave_pairs_resident=False, sift_octave_pairs_resident=False):
     """stereoCallback replayed on ClassicFeatureFrontEnd(detector, descriptor, BF, ...) (node.cpp:353-360) over host image pairs -- detector
     "ORB", "ShiTomasi" or "FAST" with descriptor "ORB", "ShiTomasi", "FAST", "BRISK" or "AKAZE" with descriptor "BRISK" (64-byte rows; detector "BRISK"
     or "AKAZE" with the default descriptor "ORB" runs only with orb_octaves=True (ClassicFeatureFrontEnd::setOrbExtractorOctaves, reset afterwards:
@@ -367,6 +367,9 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     octave_pairs_resident (ClassicFeatureFrontEnd::setOctavePairsResident, reset afterwards) with resident=True: "BRISK" + "ORB" and
     "AKAZE" + "ORB" (both still need orb_octaves=True) and "AKAZE" + "BRISK" are one spvo_brisk_orb_pair / spvo_akaze_orb_pair /
     spvo_akaze_brisk_pair per pair into the binary slots; without it the three take the per-image path, as said above.
+    sift_octave_pairs_resident (ClassicFeatureFrontEnd::setSiftOctavePairsResident, reset afterwards) with resident=True: "BRISK" + "SIFT"
+    and "AKAZE" + "SIFT" are one spvo_brisk_sift_pair / spvo_akaze_sift_pair per pair into the SIFT slots; without it both take the
+    per-image path and are matched from the host copies.  "ORB" + "SIFT" has no resident route.
     trace: a fourth value, digests [n, 8] uint64 of what every frame left in the front end (keypoints L, descriptors L, keypoints R,
     descriptors R, stereo matches, temporal matches, the previous frame's stereo matches + map, the inlier sets): equal digests = identical
     contents.  The digests are computed inside the timed loop, so `seconds` of a traced run is not a frame-rate figure."""
@@ -390,6 +393,8 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     lib.spvo_host_classic_set_orb_octaves.argtypes = [C.c_int]
     lib.spvo_host_classic_set_octave_pairs_resident.restype = None
     lib.spvo_host_classic_set_octave_pairs_resident.argtypes = [C.c_int]
+    lib.spvo_host_classic_set_sift_octave_pairs_resident.restype = None
+    lib.spvo_host_classic_set_sift_octave_pairs_resident.argtypes = [C.c_int]
     n = len(frames)
     ls = [np.ascontiguousarray(f[0], np.uint8) for f in frames]
     rs = [np.ascontiguousarray(f[1], np.uint8) for f in frames]
@@ -410,6 +415,7 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     lib.spvo_host_classic_set_sift_describe_resident(int(bool(sift_describe_resident)))
     lib.spvo_host_classic_set_orb_octaves(int(bool(orb_octaves)))
     lib.spvo_host_classic_set_octave_pairs_resident(int(bool(octave_pairs_resident)))
+    lib.spvo_host_classic_set_sift_octave_pairs_resident(int(bool(sift_octave_pairs_resident)))
     try:
         args =(n, pl, pr, rows, cols, Pl.ctypes.data, Pr.ctypes.data, 1 if selector == "KNN" else 0, int(cross_check), stereo_threshold, refinement_degree, warm,
                 poses.ctypes.data, stats.ctypes.data, C.byref(sec), ih, iw, digest.ctypes.data if trace else None)
@@ -425,6 +431,7 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
         lib.spvo_host_classic_set_sift_describe_resident(0)
         lib.spvo_host_classic_set_orb_octaves(0)
         lib.spvo_host_classic_set_octave_pairs_resident(0)
+        lib.spvo_host_classic_set_sift_octave_pairs_resident(0)
     if rc == -1000000:
         raise ValueError("unknown detector %r" % (detector,))
     if rc == -1000001:

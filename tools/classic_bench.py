@@ -1,6 +1,6 @@
 """The classic front end on the GPU.
 
-python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK|AKAZE] [--descriptor ORB|BRISK|AKAZE|SIFT] [--resident] [--brisk-resident] [--akaze-resident] [--sift-resident] [--orb-octaves] [--octave-pairs-resident]
+python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK|AKAZE] [--descriptor ORB|BRISK|AKAZE|SIFT] [--resident] [--brisk-resident] [--akaze-resident] [--sift-resident] [--orb-octaves] [--octave-pairs-resident] [--sift-octave-pairs-resident]
     ClassicFeatureFrontEnd(detector, descriptor, BF, KNN) over the synthetic stream: frames/s of the synchronous stereoCallback
     (--descriptor BRISK: with --detector ShiTomasi, FAST, BRISK or AKAZE; --detector BRISK: with --descriptor BRISK only; --detector AKAZE:
     with --descriptor BRISK or AKAZE -- the latter sets ClassicFeatureFrontEnd::setAkazeDescriptor for the run: 61-byte MLDB rows);
@@ -10,9 +10,12 @@ python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK|AKAZ
     --akaze-resident: with setAkazePairResident as well (AKAZE + AKAZE through one spvo_akaze_detect_pair per pair; needs --resident).
     --sift-resident: with setSiftDescribeResident as well (ShiTomasi / FAST + SIFT through one spvo_classic_sift_pair per pair; needs --resident;
     also taken by --ab for its resident runs).
-python tools/classic_bench.py [frames] --detector ShiTomasi|FAST|ORB --descriptor ORB|BRISK --ab ROUNDS
+    --sift-octave-pairs-resident: with setSiftOctavePairsResident as well (BRISK / AKAZE + SIFT through one spvo_brisk_sift_pair /
+    spvo_akaze_sift_pair per pair; needs --resident; also taken by --ab for its resident runs).
+python tools/classic_bench.py [frames] --detector ShiTomasi|FAST|ORB|BRISK|AKAZE --descriptor ORB|BRISK|SIFT --ab ROUNDS [--sift-resident] [--sift-octave-pairs-resident] [--waves N]
     the same stream with setDeviceResident off and on, alternating, ROUNDS times each in one process: ms per pair of every run, the median
-    and the min .. max spread of each setting, and how many pairs of a resident run stayed resident.
+    and the min .. max spread of each setting, and how many pairs of a resident run stayed resident.  --waves N: tuning
+    "sift_pair_waves_per_cu" = N for the SIFT pair calls of the resident runs.
 python tools/classic_bench.py --detectors [--calls 200] [--warmup 20]
     per image at 1241 x 376: spvo_orb_detect (the yardstick, same run) beside spvo_gftt_detect + spvo_orb_describe and
     spvo_fast_detect + spvo_orb_describe -- median, 10th / 90th percentile of the synchronous calls, keypoints, and how the
@@ -98,6 +101,7 @@ ap.add_argument("--akaze-resident", action="store_true")
 ap.add_argument("--sift-resident", action="store_true")
 ap.add_argument("--orb-octaves", action="store_true")
 ap.add_argument("--octave-pairs-resident", action="store_true")
+ap.add_argument("--sift-octave-pairs-resident", action="store_true")
 ap.add_argument("--no-yardstick", action="store_true")
 ap.add_argument("--ab", type=int, default=0)
 ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "brisk_detect", "akaze_detect", "akaze_describe", "akaze_pair", "brisk_pair", "brisk_orb_pair", "akaze_orb_pair", "akaze_brisk_pair", "orb_describe", "orb_octaves", "fast_sift", "gftt_sift", "sift_describe", "match", "match_slots"])
@@ -320,6 +324,8 @@ if args.detectors or args.leg:
                 host.classic_resident_pairs()))
     capi.set_tuning("sift_describe_form", 0)
 elif args.ab > 0:
+    if args.waves > 0:
+        capi.set_tuning("sift_pair_waves_per_cu", args.waves)
     n = args.frames
     seq = [frames[i % 8] for i in range(n)]
     name = args.detector + ("" if args.descriptor == "ORB" else " + " + args.descriptor)
@@ -328,7 +334,8 @@ elif args.ab > 0:
     for r in range(args.ab):
         for resident in (False, True):
             p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5, detector=args.detector, resident=resident, descriptor=args.descriptor,
-                                                sift_describe_resident=resident and args.sift_resident)
+                                                sift_describe_resident=resident and args.sift_resident,
+                                                sift_octave_pairs_resident=resident and args.sift_octave_pairs_resident)
             ms[resident].append(1e3 * sec / (n - 5))
             print("%s %dx%d round %d resident=%d: %.3f ms per pair over %d pairs, %d pairs resident, keypoints %d, stereo matches %d, inliers %d" % (
                 name, frames[0][0].shape[1], frames[0][0].shape[0], r, resident, ms[resident][-1], n - 5, host.classic_resident_pairs(), np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3])))
@@ -342,5 +349,6 @@ else:
     p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5, detector=args.detector, resident=args.resident, descriptor=args.descriptor,
                                         akaze_descriptor=args.descriptor == "AKAZE", **(dict(brisk_resident=True) if args.brisk_resident else {}), **(dict(akaze_resident=True) if args.akaze_resident else {}),
                                         **(dict(sift_describe_resident=True) if args.sift_resident else {}), **(dict(orb_octaves=True) if args.orb_octaves else {}),
-                                        **(dict(octave_pairs_resident=True) if args.octave_pairs_resident else {}))
+                                        **(dict(octave_pairs_resident=True) if args.octave_pairs_resident else {}),
+                                        **(dict(sift_octave_pairs_resident=True) if args.sift_octave_pairs_resident else {}))
     print("classic front end (%s%s) on the GPU: %.1f stereo frames/s (%.3f ms per pair), keypoints %d, stereo matches %d, inliers %d, %d pairs resident" % (args.detector + ("" if args.descriptor == "ORB" else " + " + args.descriptor), ", device-resident" if args.resident else "", (n - 5) / sec, 1e3 * sec / (n - 5), np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3]), host.classic_resident_pairs()))
