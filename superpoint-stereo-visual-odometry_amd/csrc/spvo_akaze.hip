@@ -3,11 +3,12 @@
 // order-dependent suppression between candidates on the host (rule 11: the restatement's loop over the copied candidate list), the
 // test hooks, spvo_akaze_describe (akaze_mldb.hip.h: orientation and MLDB descriptor on the scale space that chain leaves resident), and
 // spvo_akaze_detect_pair (detector + descriptor of a stereo pair in one submission into two binary slots of 61-byte rows, by
-// spvo_classic_detect's resident-pair protocol, with rule 11 on the device: akaze_suppress.hip.h; spvo_akaze_orb_pair and
+// the resident-pair protocol of pair_call.hip.h, with rule 11 on the device: akaze_suppress.hip.h; spvo_akaze_orb_pair and
 // spvo_akaze_brisk_pair: the same call with the octave-aware ORB extractor or the BRISK extractor behind rule 11).
 // Runs on the solver's stream (stream2) with the image resident in spvo_ctx::cls -- it stays there for a spvo_brisk_describe(img = NULL)
 // that follows -- and owns everything else it needs (spvo_ctx::akaze).
 #include "spvo_internal.hip.h"
+#include "pair_call.hip.h"
 #include "akaze.hip.h"
 #include "akaze_mldb.hip.h"
 #include "akaze_suppress.hip.h"
@@ -348,6 +349,42 @@ void ak_suppress_enqueue(spvo_ctx *c, const AkazeLevels &lv, const AkazeCand *re
   hipLaunchKernelGGL(akaze_suppress_second_kernel, dim3(std::min((cap + 255) / 256, 256)), dim3(256), 0, st, lv, rec, d.sup_list, d.sup_idx, d.sup_cnt, cap, d.sup_keep);
   hipLaunchKernelGGL(akaze_suppress_compact_kernel, dim3(1), dim3(1024), 0, st, rec, d.sup_idx, d.sup_keep, cap, d.sup_cnt, d.sup_kp, d.sup_src);
 }
+
+// rules 10, 12, 13 behind the scale space (spvo_akaze_detect and every pair call): extrema -- one launch per octave; an octave with no room
+// inside its smallest border has none --, rank, refinement -> the candidates in rec, their number in stat[AKAZE_STAT_NCAND]
+void ak_extrema_enqueue(spvo_ctx *c, float threshold) {
+  auto &d = c->akaze;
+  hipStream_t st = c->stream2;
+  const AkazeLevels &lv = d.lv;
+  for (int first = 0; first < lv.n; first += AK_SUBLEVELS) {
+    const AkazeLevel &L = lv.l[first];
+    if (L.h <= 2 * L.border || L.w <= 2 * L.border) continue;
+    dim3 eg = grid_of(L.w, L.h);
+    eg.z = std::min(AK_SUBLEVELS, lv.n - first);
+    hipLaunchKernelGGL(akaze_extrema_kernel, eg, dim3(256), 0, st, lv, first, threshold, 1e-5f, d.keys, d.cand_cap, d.stat);
+  }
+  classic_rank_enqueue(c, d.keys, d.rank, d.stat + AKAZE_STAT_NCAND, d.cand_cap);
+  hipLaunchKernelGGL(akaze_refine_kernel, dim3(32), dim3(256), 0, st, lv, d.keys, d.rank, d.cand_cap, d.stat, d.rec);
+}
+
+// A pair call's detector chain (the binary pairs and spvo_akaze_sift_pair): a staged image becomes the resident one, its scale space, the
+// launches above and rule 11 on the device, which leaves sup_kp and the AKAZE_SUP_KEPT count for the extractor behind it
+int ak_staged_enqueue(spvo_ctx *c, const uint8_t *h_img, int rows, int cols, float threshold) {
+  auto &d = c->akaze;
+  if (int rc = classic_image_from_staged(c, h_img, rows, cols)) return rc;
+  if (int rc = ak_scale_enqueue(c, rows, cols)) return rc;
+  ak_extrema_enqueue(c, threshold);
+  ak_suppress_enqueue(c, d.lv, d.rec, d.stat + AKAZE_STAT_NCAND, d.cand_cap);
+  return SPVO_OK;
+}
+
+// behind a pair call's wait: the right image's scale space is resident.  h_n: the family's pinned count block, where the finishing launch of
+// image k left its contrast factors at h_n + 8 + 4 k (ak_mark_resident reads them where stat keeps them)
+void ak_mark_right_resident(spvo_ctx *c, const int *h_n) {
+  int stat[AKAZE_STAT_HIST] = {0};
+  std::memcpy(&stat[AKAZE_STAT_K], h_n + 8 + 4, AKAZE_MAX_OCTAVES * sizeof(int));
+  ak_mark_resident(c, stat);
+}
 }  // namespace
 
 void spvo_int::akaze_release(spvo_ctx *c) {
@@ -370,17 +407,7 @@ int spvo_akaze_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_
   if (int rc = ak_scale_space(c, img, rows, cols, stride)) return rc;
   auto &d = c->akaze;
   const AkazeLevels &lv = d.lv;
-  const dim3 blk(256);
-  // rules 10, 12, 13
-  for (int first = 0; first < lv.n; first += AK_SUBLEVELS) {   // one launch per octave; an octave with no room inside its smallest border has none
-    const AkazeLevel &L = lv.l[first];
-    if (L.h <= 2 * L.border || L.w <= 2 * L.border) continue;
-    dim3 eg = grid_of(L.w, L.h);
-    eg.z = std::min(AK_SUBLEVELS, lv.n - first);
-    hipLaunchKernelGGL(akaze_extrema_kernel, eg, blk, 0, st, lv, first, threshold, 1e-5f, d.keys, d.cand_cap, d.stat);
-  }
-  classic_rank_enqueue(c, d.keys, d.rank, d.stat + AKAZE_STAT_NCAND, d.cand_cap);
-  hipLaunchKernelGGL(akaze_refine_kernel, dim3(32), blk, 0, st, lv, d.keys, d.rank, d.cand_cap, d.stat, d.rec);
+  ak_extrema_enqueue(c, threshold);
   HIP_TRY(c, hipGetLastError());
   int stat[AKAZE_STAT_HIST];
   HIP_TRY(c, hipMemcpyAsync(stat, d.stat, sizeof stat, hipMemcpyDeviceToHost, st));
@@ -530,8 +557,8 @@ int spvo_akaze_suppress_debug(spvo_ctx *c, int rows, int cols, const spvo_akaze_
   return SPVO_OK;
 }
 
-// One submission per stereo pair: spvo_brisk_detect_pair's protocol (PairStage, slot_rewrite, the prematch cache) around the detector's
-// chain up to akaze_refine_kernel, rule 11 on the device, the descriptor on the compacted records and a finishing kernel, image by image
+// One submission per stereo pair: the resident-pair protocol (PairCall on the binary slots, pair_call.hip.h) around the detector's chain
+// through rule 11 on the device (ak_staged_enqueue), the descriptor on the compacted records and a finishing kernel, image by image
 // in stream order.  The scale space, the candidate lists, the suppression's lists and the descriptor's buffers are the left image's first
 // and the right image's afterwards: an image's finishing kernel has put its counts into the pinned h_n before the next image's clear.
 // The extractor behind rule 11 is the call's: MLDB (spvo_akaze_detect_pair, 61-byte rows), the octave-aware ORB extractor on the kept
@@ -544,58 +571,29 @@ enum class AkExtract { Mldb, Orb, Brisk };
 int akaze_pair(spvo_ctx *c, const char *who, AkExtract ex, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, float threshold, int slot_l, int slot_r,
                int slot_capacity, spvo_akaze_features *out_l, spvo_akaze_features *out_r) {
   if (!c || !img_l || !img_r || !out_l || !out_r || rows <= 0 || cols <= 0 || stride < (size_t)cols) return fail(c, SPVO_ERR_INVALID, "bad argument");
-  if (slot_l < 0 || slot_l >= N_BIN_SLOTS || slot_r < 0 || slot_r >= N_BIN_SLOTS || slot_l == slot_r) return fail(c, SPVO_ERR_INVALID, "bad slot");
-  spvo_akaze_features *const outs[2] = {out_l, out_r};
-  for (auto *o : outs)
-    if (o->cap < 0) return fail(c, SPVO_ERR_INVALID, "bad output buffer");
-  const int cap = slot_capacity;
-  if (cap <= 0 || cap > (1 << HAM_KEY_SHIFT)) return fail(c, SPVO_ERR_INVALID, "slot_capacity must be 1 .. %d", 1 << HAM_KEY_SHIFT);
-  if (int rc = ak_check(c, who, rows, cols, threshold)) return rc;
+  const int cap = slot_capacity, row_bytes = ex == AkExtract::Mldb ? AKAZE_MLDB_BYTES : ex == AkExtract::Orb ? 32 : 64;
+  PairCall<BinPairFamily> pc(c, who, BinPairFamily{row_bytes}, pair_out(out_l), pair_out(out_r));
+  int rc;
+  if ((rc = pc.check(slot_l, slot_r)) || (rc = pc.check_capacity(cap)) || (rc = ak_check(c, who, rows, cols, threshold))) return rc;
   // a kept record's octave is at most that of the shape's last level
   const int max_octave = ex == AkExtract::Orb ? ((c->akaze.rows == rows && c->akaze.cols == cols) ? c->akaze.octaves : make_tables(rows, cols).octaves) - 1 : 0;
   if (ex == AkExtract::Orb)
-    if (int rc = orb_link_check(c, who, rows, cols, max_octave)) return rc;
-  if (int rc = require_idle(c)) return rc;
-  HIP_TRY(c, hipSetDevice(c->cfg.device));
-  out_l->n = out_r->n = 0;
+    if ((rc = orb_link_check(c, who, rows, cols, max_octave))) return rc;
+  if ((rc = pc.open())) return rc;
   hipStream_t st = c->stream2;
   auto &bb = c->bin;
-  auto &b = c->cls;
   auto &d = c->akaze;
-  PairStage &ps = bb.pair;
-  const int row_bytes = ex == AkExtract::Mldb ? AKAZE_MLDB_BYTES : ex == AkExtract::Orb ? 32 : 64;
-  const size_t px = (size_t)rows * cols;
   // every allocation before the first launch of the chain; the image buffer before the layout of its shape
-  int rc;
-  if ((rc = classic_slots_ensure(c, cap, px)) || (rc = classic_image_ensure(c, rows, cols)) || (rc = ak_ensure(c, rows, cols)) || (rc = ak_sup_ensure(c, d.cand_cap)) ||
+  if ((rc = classic_slots_ensure(c, cap, (size_t)rows * cols)) || (rc = classic_image_ensure(c, rows, cols)) || (rc = ak_ensure(c, rows, cols)) || (rc = ak_sup_ensure(c, d.cand_cap)) ||
       (rc = ex == AkExtract::Mldb ? ak_kp_ensure(c, cap) : ex == AkExtract::Orb ? orb_link_ensure(c, rows, cols, cap) : ak_brisk_ensure(c, rows, cols, cap)))
     return rc;
-  // both slots are being rewritten: whatever was matched against their old contents is stale
-  const int slots[2] = {slot_l, slot_r};
-  for (int sl : slots) { slot_rewrite(bb.slots[sl]); bb.slots[sl].row_bytes = row_bytes; }
-  ps.mcache.invalidate();
-  HIP_TRY(c, hipStreamSynchronize(st));   // (the staging buffer and the mirrors are the previous call's until its work is done)
-  ps.stage(img_l, img_r, rows, cols, stride);
+  if ((rc = pc.load(img_l, img_r, rows, cols, stride))) return rc;
   const AkazeLevels &lv = d.lv;
   const dim3 blk(256);
   for (int k = 0; k < 2; ++k) {
-    const BinarySlot &s = bb.slots[slots[k]];
-    b.rows = b.cols = 0;
-    HIP_TRY(c, hipMemcpyAsync(b.im, ps.h_img + k * px, px, hipMemcpyHostToDevice, st));
-    b.rows = rows; b.cols = cols;
-    if ((rc = ak_scale_enqueue(c, rows, cols))) return rc;
-    // rules 10, 12, 13: spvo_akaze_detect's launches
-    for (int first = 0; first < lv.n; first += AK_SUBLEVELS) {
-      const AkazeLevel &L = lv.l[first];
-      if (L.h <= 2 * L.border || L.w <= 2 * L.border) continue;
-      dim3 eg = grid_of(L.w, L.h);
-      eg.z = std::min(AK_SUBLEVELS, lv.n - first);
-      hipLaunchKernelGGL(akaze_extrema_kernel, eg, blk, 0, st, lv, first, threshold, 1e-5f, d.keys, d.cand_cap, d.stat);
-    }
-    classic_rank_enqueue(c, d.keys, d.rank, d.stat + AKAZE_STAT_NCAND, d.cand_cap);
-    hipLaunchKernelGGL(akaze_refine_kernel, dim3(32), blk, 0, st, lv, d.keys, d.rank, d.cand_cap, d.stat, d.rec);
-    // rule 11, then the descriptor on what it leaves, the count read on the device
-    ak_suppress_enqueue(c, lv, d.rec, d.stat + AKAZE_STAT_NCAND, d.cand_cap);
+    const BinarySlot &s = bb.slots[pc.slots[k]];
+    // the detector through rule 11, then the descriptor on what it leaves, the count read on the device
+    if ((rc = ak_staged_enqueue(c, pc.image(k), rows, cols, threshold))) return rc;
     int *h_n = bb.h_n + 4 * k, *h_k = bb.h_n + 8 + 4 * k;
     AkazeKp *h_akp = bb.h_akp + (size_t)k * cap;
     uint8_t *h_desc = bb.h_desc + (size_t)k * cap * row_bytes;
@@ -617,41 +615,16 @@ int akaze_pair(spvo_ctx *c, const char *who, AkExtract ex, const uint8_t *img_l,
     }
     HIP_TRY(c, hipGetLastError());
   }
-  HIP_TRY(c, hipEventRecord(ps.ev_feat, st));
-  // spvo_set_prematch, as spvo_classic_detect: any filled slot of the same row width is a temporal partner, a slot of another width is skipped
-  const int prev = ps.last_slot_l;
-  const int partner[2] = {slot_r, ps.temporal_partner(slot_l, slot_r, prev >= 0 && bb.slots[prev].filled && bb.slots[prev].row_bytes == row_bytes)};
-  if (c->prematch) {
-    for (int k = 0; k < 2; ++k)
-      if (partner[k] >= 0)
-        if ((rc = enqueue_hamming_slots(c, slot_l, partner[k], c->pm_selector, c->pm_cross, c->pm_ratio, bb.h_match + (size_t)k * cap))) return rc;
-    HIP_TRY(c, hipEventRecord(ps.ev_match, st));
-  }
-  HIP_TRY(c, wait_event(ps.ev_feat));   // the one wait of the call: the matches go on behind it
-  ps.last_slot_l = -1;   // (forgotten AFTER the wait, as spvo_classic_detect: a call that failed before it leaves the partner it found)
-  for (int k = 0; k < 2; ++k) outs[k]->n = bb.h_n[4 * k];
-  // (the list holds every strict maximum the borders leave room for, so the flag cannot be set; were it, the counts would be wrong)
+  if ((rc = pc.submit())) return rc;
+  pc.count(0); pc.count(1);
+  // (kept: the AKAZE callers answer a detector overflow with SPVO_ERR_STATE -- the list holds every strict maximum the borders leave room
+  // for, so the flag cannot be set; were it, the counts would be wrong)
   if (bb.h_n[1] || bb.h_n[5]) return fail(c, SPVO_ERR_STATE, "%s: the candidate list overflowed although it is sized from the image", who);
-  {   // the right image's scale space is resident (ak_mark_resident: the contrast factors sit where stat keeps them)
-    int stat[AKAZE_STAT_HIST] = {0};
-    std::memcpy(&stat[AKAZE_STAT_K], bb.h_n + 8 + 4, AKAZE_MAX_OCTAVES * sizeof(int));
-    ak_mark_resident(c, stat);
-  }
-  if (outs[0]->n > cap || outs[1]->n > cap) return fail(c, SPVO_ERR_CAPACITY, "%s: %d / %d rows do not fit slots of %d (slot_capacity)", who, outs[0]->n, outs[1]->n, cap);
+  ak_mark_right_resident(c, bb.h_n);   // (kept: also when the capacity rule below answers SPVO_ERR_CAPACITY)
   static_assert(sizeof(spvo_akaze_keypoint) == sizeof(AkazeKp), "record layout");
-  for (int k = 0; k < 2; ++k) {
-    BinarySlot &s = bb.slots[slots[k]];
-    s.n = outs[k]->n; s.filled = true;
-    const int ncopy = std::min(s.n, outs[k]->cap);
-    if (ncopy > 0 && outs[k]->kp) std::memcpy(outs[k]->kp, bb.h_akp + (size_t)k * cap, (size_t)ncopy * sizeof(AkazeKp));
-    if (ncopy > 0 && outs[k]->desc) std::memcpy(outs[k]->desc, bb.h_desc + (size_t)k * cap * row_bytes, (size_t)ncopy * row_bytes);
-  }
-  if (c->prematch)
-    for (int k = 0; k < 2; ++k)
-      if (partner[k] >= 0)
-        ps.mcache.record(k, slot_l, partner[k], bb.slots[slot_l].gen, bb.slots[partner[k]].gen, c->pm_selector, c->pm_cross, c->pm_ratio, bb.h_match + (size_t)k * cap);
-  ps.last_slot_l = slot_l;
-  return SPVO_OK;
+  const PairMirror mirrors[2] = {{bb.h_akp, sizeof(AkazeKp), bb.h_desc, (size_t)row_bytes},
+                                 {bb.h_akp + cap, sizeof(AkazeKp), bb.h_desc + (size_t)cap * row_bytes, (size_t)row_bytes}};
+  return pc.commit(mirrors);
 }
 }  // namespace
 extern "C" {
@@ -677,7 +650,7 @@ int spvo_akaze_brisk_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_
 
 // The AKAZE detector with the SIFT extractor, pair-resident in the SIFT slots: per image what spvo_akaze_detect followed by
 // spvo_sift_describe(img = NULL) on {x, y, size, angle, response, octave} of its records hands out, byte for byte; the host's records keep
-// their class_id.  The protocol is sift_link_pair's (spvo_sift.hip); the detector's part is akaze_pair's chain through ak_suppress_enqueue,
+// their class_id.  The call is sift_link_pair's (spvo_sift.hip); the detector's part is akaze_pair's chain, ak_staged_enqueue,
 // which leaves sup_kp and the AKAZE_SUP_KEPT count on the device.  A kept record's octave is at most that of the shape's last level, so the
 // pyramid is built up to it.  Afterwards the right image's scale space is resident, as after spvo_akaze_orb_pair.
 int spvo_akaze_sift_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, float threshold, int slot_l, int slot_r, int slot_capacity,
@@ -686,7 +659,6 @@ int spvo_akaze_sift_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r
   static_assert(sizeof(spvo_akaze_keypoint) == sizeof(AkazeKp), "record layout");
   const char *who = "spvo_akaze_sift_pair";
   auto &d = c->akaze;
-  auto &b = c->cls;
   SiftLinkDetector det;
   det.who = who;
   det.max_octave = ((d.rows == rows && d.cols == cols) ? d.octaves : make_tables(rows, cols).octaves) - 1;   // (make_tables takes any positive shape)
@@ -700,33 +672,13 @@ int spvo_akaze_sift_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r
     return SPVO_OK;
   };
   det.enqueue = [&](const uint8_t *h_img) -> int {
-    hipStream_t st = c->stream2;
-    const AkazeLevels &lv = d.lv;
-    b.rows = b.cols = 0;
-    HIP_TRY(c, hipMemcpyAsync(b.im, h_img, (size_t)rows * cols, hipMemcpyHostToDevice, st));
-    b.rows = rows; b.cols = cols;
-    if (int rc = ak_scale_enqueue(c, rows, cols)) return rc;
-    // rules 10, 12, 13: spvo_akaze_detect's launches, then rule 11 on the device
-    for (int first = 0; first < lv.n; first += AK_SUBLEVELS) {
-      const AkazeLevel &L = lv.l[first];
-      if (L.h <= 2 * L.border || L.w <= 2 * L.border) continue;
-      dim3 eg = grid_of(L.w, L.h);
-      eg.z = std::min(AK_SUBLEVELS, lv.n - first);
-      hipLaunchKernelGGL(akaze_extrema_kernel, eg, dim3(256), 0, st, lv, first, threshold, 1e-5f, d.keys, d.cand_cap, d.stat);
-    }
-    classic_rank_enqueue(c, d.keys, d.rank, d.stat + AKAZE_STAT_NCAND, d.cand_cap);
-    hipLaunchKernelGGL(akaze_refine_kernel, dim3(32), dim3(256), 0, st, lv, d.keys, d.rank, d.cand_cap, d.stat, d.rec);
-    ak_suppress_enqueue(c, lv, d.rec, d.stat + AKAZE_STAT_NCAND, d.cand_cap);
+    if (int rc = ak_staged_enqueue(c, h_img, rows, cols, threshold)) return rc;
     HIP_TRY(c, hipGetLastError());
     return SPVO_OK;
   };
-  const SiftLinkOut outs[2] = {{&out_l->n, out_l->kp, out_l->desc, out_l->cap}, {&out_r->n, out_r->kp, out_r->desc, out_r->cap}};
-  const int rc = sift_link_pair(c, det, img_l, img_r, rows, cols, stride, slot_l, slot_r, slot_capacity, outs);
-  if (rc == SPVO_OK || rc == SPVO_ERR_CAPACITY) {   // (both are answered behind the wait) the right image's scale space is resident (ak_mark_resident: the contrast factors sit where stat keeps them)
-    int stat[AKAZE_STAT_HIST] = {0};
-    std::memcpy(&stat[AKAZE_STAT_K], c->sift.h_n + 8 + 4, AKAZE_MAX_OCTAVES * sizeof(int));
-    ak_mark_resident(c, stat);
-  }
+  const int rc = sift_link_pair(c, det, img_l, img_r, rows, cols, stride, slot_l, slot_r, slot_capacity, pair_out(out_l), pair_out(out_r));
+  // (kept: both SPVO_OK and SPVO_ERR_CAPACITY are answered behind the wait, and after either the right image's scale space is resident)
+  if (rc == SPVO_OK || rc == SPVO_ERR_CAPACITY) ak_mark_right_resident(c, c->sift.h_n);
   return rc;
 }
 

@@ -1,10 +1,11 @@
 // spvo_brisk_detect.hip -- the classic front end's BRISK keypoint detector (brisk_detect.hip.h): the layout of the six layers and the area
 // taps of a shape (built on the host in double, by the formulas tests/brisk_detect_ref.py lists), spvo_brisk_detect,
 // spvo_brisk_detect_debug_layer and spvo_brisk_detect_pair (detector + extractor of a stereo pair in one submission into two binary slots,
-// by spvo_classic_detect's resident-pair protocol; spvo_brisk_orb_pair: the same call with the octave-aware ORB extractor behind the detector;
+// by the resident-pair protocol of pair_call.hip.h; spvo_brisk_orb_pair: the same call with the octave-aware ORB extractor behind the detector;
 // spvo_brisk_sift_pair: the detector as the first link of spvo_sift.hip's sift_link_pair, into two SIFT slots).  Runs on the solver's stream (stream2) with the image resident in spvo_ctx::cls as
 // layer 0 -- it stays there for a spvo_brisk_describe(img = NULL) that follows -- and owns everything else it needs (spvo_ctx::brisk_det).
 #include "spvo_internal.hip.h"
+#include "pair_call.hip.h"
 #include "brisk_detect.hip.h"
 
 // brisk_detect_ref.py choice 3: the taps of one axis; false if a run is longer than BRISK_DET_TAPS or not contiguous (cannot happen for the
@@ -146,6 +147,11 @@ int bd_enqueue(spvo_ctx *c, int rows, int cols, int threshold) {
   hipLaunchKernelGGL(brisk_refine_kernel, dim3(64), dim3(256), 0, st, d.lv, threshold, d.keys, d.rank, d.cand_cap, d.counters, d.rec, d.keep);
   return SPVO_OK;
 }
+// a pair call's first link (spvo_brisk_detect_pair, spvo_brisk_orb_pair, spvo_brisk_sift_pair): a staged image becomes the resident one and goes through that chain
+int bd_staged_enqueue(spvo_ctx *c, const uint8_t *h_img, int rows, int cols, int threshold) {
+  if (int rc = classic_image_from_staged(c, h_img, rows, cols)) return rc;
+  return bd_enqueue(c, rows, cols, threshold);
+}
 
 // what spvo_brisk_detect refuses of its parameters and of the image shape (`who` names the entry point in the error text)
 int bd_check(spvo_ctx *c, const char *who, int rows, int cols, int threshold, int octaves) {
@@ -194,7 +200,7 @@ int spvo_brisk_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_
   return SPVO_OK;
 }
 
-// One submission per stereo pair: spvo_classic_detect's protocol (PairStage, slot_rewrite, the prematch cache) around the detector's chain
+// One submission per stereo pair: the resident-pair protocol (PairCall on the binary slots, pair_call.hip.h) around the detector's chain
 // up to brisk_refine_kernel and the extractor behind it (brisk_pair_chain_enqueue), image by image in stream order.  The scale space, the
 // candidate lists, the integral image, the extractor's lists and the detector's counter block are the left image's first and the right
 // image's afterwards: an image's finishing kernel has put its counts into the pinned h_n before the next image's clear.
@@ -206,42 +212,23 @@ constexpr int BRISK_ORB_MAX_OCTAVE = BRISK_DET_LAYERS - 1;   // a BRISK keypoint
 int brisk_pair(spvo_ctx *c, const char *who, bool orb, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int threshold, int octaves, int slot_l, int slot_r,
                int slot_capacity, spvo_brisk_features *out_l, spvo_brisk_features *out_r) {
   if (!c || !img_l || !img_r || !out_l || !out_r || rows <= 0 || cols <= 0 || stride < (size_t)cols) return fail(c, SPVO_ERR_INVALID, "bad argument");
-  if (slot_l < 0 || slot_l >= N_BIN_SLOTS || slot_r < 0 || slot_r >= N_BIN_SLOTS || slot_l == slot_r) return fail(c, SPVO_ERR_INVALID, "bad slot");
-  spvo_brisk_features *const outs[2] = {out_l, out_r};
-  for (auto *o : outs)
-    if (o->cap < 0) return fail(c, SPVO_ERR_INVALID, "bad output buffer");
-  const int cap = slot_capacity;
-  if (cap <= 0 || cap > (1 << HAM_KEY_SHIFT)) return fail(c, SPVO_ERR_INVALID, "slot_capacity must be 1 .. %d", 1 << HAM_KEY_SHIFT);
-  if (int rc = bd_check(c, who, rows, cols, threshold, octaves)) return rc;
-  if (orb)
-    if (int rc = orb_link_check(c, who, rows, cols, BRISK_ORB_MAX_OCTAVE)) return rc;
-  if (int rc = require_idle(c)) return rc;
-  HIP_TRY(c, hipSetDevice(c->cfg.device));
-  out_l->n = out_r->n = 0;
-  hipStream_t st = c->stream2;
-  auto &bb = c->bin;
-  auto &b = c->cls;
-  auto &d = c->brisk_det;
-  PairStage &ps = bb.pair;
-  const int row_bytes = orb ? 32 : 64;
-  const size_t px = (size_t)rows * cols;
-  // every allocation and the 47 MB point table before the first launch of the chain; the image buffer before the layout that points into it
+  const int cap = slot_capacity, row_bytes = orb ? 32 : 64;
+  PairCall<BinPairFamily> pc(c, who, BinPairFamily{row_bytes}, pair_out(out_l), pair_out(out_r));
   int rc;
-  if ((rc = classic_slots_ensure(c, cap, px)) || (rc = classic_image_ensure(c, rows, cols)) || (rc = orb ? orb_link_ensure(c, rows, cols, cap) : brisk_chain_ensure(c, rows, cols, cap)) ||
-      (rc = bd_ensure(c, rows, cols)))
+  if ((rc = pc.check(slot_l, slot_r)) || (rc = pc.check_capacity(cap)) || (rc = bd_check(c, who, rows, cols, threshold, octaves))) return rc;
+  if (orb)
+    if ((rc = orb_link_check(c, who, rows, cols, BRISK_ORB_MAX_OCTAVE))) return rc;
+  if ((rc = pc.open())) return rc;
+  auto &bb = c->bin;
+  auto &d = c->brisk_det;
+  // every allocation and the 47 MB point table before the first launch of the chain; the image buffer before the layout that points into it
+  if ((rc = classic_slots_ensure(c, cap, (size_t)rows * cols)) || (rc = classic_image_ensure(c, rows, cols)) ||
+      (rc = orb ? orb_link_ensure(c, rows, cols, cap) : brisk_chain_ensure(c, rows, cols, cap)) || (rc = bd_ensure(c, rows, cols)))
     return rc;
-  // both slots are being rewritten: whatever was matched against their old contents is stale
-  const int slots[2] = {slot_l, slot_r};
-  for (int sl : slots) { slot_rewrite(bb.slots[sl]); bb.slots[sl].row_bytes = row_bytes; }
-  ps.mcache.invalidate();
-  HIP_TRY(c, hipStreamSynchronize(st));   // (the staging buffer and the mirrors are the previous call's until its work is done)
-  ps.stage(img_l, img_r, rows, cols, stride);
+  if ((rc = pc.load(img_l, img_r, rows, cols, stride))) return rc;
   for (int k = 0; k < 2; ++k) {
-    const BinarySlot &s = bb.slots[slots[k]];
-    b.rows = b.cols = 0;
-    HIP_TRY(c, hipMemcpyAsync(b.im, ps.h_img + k * px, px, hipMemcpyHostToDevice, st));
-    b.rows = rows; b.cols = cols;
-    if ((rc = bd_enqueue(c, rows, cols, threshold))) return rc;
+    const BinarySlot &s = bb.slots[pc.slots[k]];
+    if ((rc = bd_staged_enqueue(c, pc.image(k), rows, cols, threshold))) return rc;
     const ChainOut out{bb.d_cnt + k * BIN_COUNTER_INTS, bb.d_kresp, s.d_kp, s.d_desc, s.d_n, bb.h_n + 4 * k, nullptr, bb.h_desc + (size_t)k * cap * row_bytes};
     if (!orb) {
       if ((rc = brisk_pair_chain_enqueue(c, rows, cols, cap, d.rec, d.keep, d.counters, d.cand_cap, d.out, out, bb.h_bkp + (size_t)k * cap))) return rc;
@@ -253,36 +240,15 @@ int brisk_pair(spvo_ctx *c, const char *who, bool orb, const uint8_t *img_l, con
     orb_link_finish_brisk(c, d.rec, d.counters, cap, s.d_kp, s.d_desc, s.d_n, out.h_n, bb.h_bkp + (size_t)k * cap, out.h_desc);
     HIP_TRY(c, hipGetLastError());
   }
-  HIP_TRY(c, hipEventRecord(ps.ev_feat, st));
-  // spvo_set_prematch, as spvo_classic_detect: any filled slot of the same row width is a temporal partner, whichever entry point filled it
-  const int prev = ps.last_slot_l;
-  const int partner[2] = {slot_r, ps.temporal_partner(slot_l, slot_r, prev >= 0 && bb.slots[prev].filled && bb.slots[prev].row_bytes == row_bytes)};
-  if (c->prematch) {
-    for (int k = 0; k < 2; ++k)
-      if (partner[k] >= 0)
-        if ((rc = enqueue_hamming_slots(c, slot_l, partner[k], c->pm_selector, c->pm_cross, c->pm_ratio, bb.h_match + (size_t)k * cap))) return rc;
-    HIP_TRY(c, hipEventRecord(ps.ev_match, st));
-  }
-  HIP_TRY(c, wait_event(ps.ev_feat));   // the one wait of the call: the matches go on behind it
-  ps.last_slot_l = -1;   // (forgotten AFTER the wait, as spvo_classic_detect: a call that failed before it leaves the partner it found)
-  for (int k = 0; k < 2; ++k) outs[k]->n = bb.h_n[4 * k];
-  // (the lists hold a candidate per interior pixel of every layer, so the flag cannot be set; were it, the counts would be wrong)
+  if ((rc = pc.submit())) return rc;
+  pc.count(0); pc.count(1);
+  // (kept: the BRISK callers answer a detector overflow with SPVO_ERR_STATE -- the lists hold a candidate per interior pixel of every layer,
+  // so the flag cannot be set; were it, the counts would be wrong)
   if (bb.h_n[1] || bb.h_n[5]) return fail(c, SPVO_ERR_STATE, "%s: the candidate list overflowed although it is sized from the image", who);
-  if (outs[0]->n > cap || outs[1]->n > cap) return fail(c, SPVO_ERR_CAPACITY, "%s: %d / %d rows do not fit slots of %d (slot_capacity)", who, outs[0]->n, outs[1]->n, cap);
   static_assert(sizeof(spvo_brisk_keypoint) == sizeof(BriskDetKeypoint), "record layout");
-  for (int k = 0; k < 2; ++k) {
-    BinarySlot &s = bb.slots[slots[k]];
-    s.n = outs[k]->n; s.filled = true;
-    const int ncopy = std::min(s.n, outs[k]->cap);
-    if (ncopy > 0 && outs[k]->kp) std::memcpy(outs[k]->kp, bb.h_bkp + (size_t)k * cap, (size_t)ncopy * sizeof(BriskDetKeypoint));
-    if (ncopy > 0 && outs[k]->desc) std::memcpy(outs[k]->desc, bb.h_desc + (size_t)k * cap * row_bytes, (size_t)ncopy * row_bytes);
-  }
-  if (c->prematch)
-    for (int k = 0; k < 2; ++k)
-      if (partner[k] >= 0)
-        ps.mcache.record(k, slot_l, partner[k], bb.slots[slot_l].gen, bb.slots[partner[k]].gen, c->pm_selector, c->pm_cross, c->pm_ratio, bb.h_match + (size_t)k * cap);
-  ps.last_slot_l = slot_l;
-  return SPVO_OK;
+  const PairMirror mirrors[2] = {{bb.h_bkp, sizeof(BriskDetKeypoint), bb.h_desc, (size_t)row_bytes},
+                                 {bb.h_bkp + cap, sizeof(BriskDetKeypoint), bb.h_desc + (size_t)cap * row_bytes, (size_t)row_bytes}};
+  return pc.commit(mirrors);
 }
 }  // namespace
 extern "C" {
@@ -300,8 +266,8 @@ int spvo_brisk_orb_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r,
 }
 
 // The BRISK detector with the SIFT extractor, pair-resident in the SIFT slots: per image what spvo_brisk_detect followed by
-// spvo_sift_describe(img = NULL) on its records hands out, byte for byte.  The protocol is sift_link_pair's (spvo_sift.hip); the detector's
-// part is bd_check, bd_ensure and, per image, the upload and bd_enqueue -- the chain up to the refined records with their keep flags, which
+// spvo_sift_describe(img = NULL) on its records hands out, byte for byte.  The call is sift_link_pair's (spvo_sift.hip); the detector's
+// part is bd_check, bd_ensure and, per image, bd_staged_enqueue -- the chain up to the refined records with their keep flags, which
 // the link compacts in the detector's order.  A keypoint's octave is its layer, 0 .. 5, so the pyramid is built for octaves 0 .. 5.
 int spvo_brisk_sift_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int threshold, int octaves, int slot_l, int slot_r,
                          int slot_capacity, spvo_sift_features *out_l, spvo_sift_features *out_r) {
@@ -309,7 +275,6 @@ int spvo_brisk_sift_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r
   static_assert(sizeof(spvo_sift_keypoint) == sizeof(BriskDetKeypoint), "record layout");
   const char *who = "spvo_brisk_sift_pair";
   auto &d = c->brisk_det;
-  auto &b = c->cls;
   SiftLinkDetector det;
   det.who = who;
   det.max_octave = BRISK_DET_LAYERS - 1;
@@ -321,14 +286,8 @@ int spvo_brisk_sift_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r
                       d.keep, d.counters + 1, d.cand_cap, d.counters, nullptr, 0};
     return SPVO_OK;
   };
-  det.enqueue = [&](const uint8_t *h_img) -> int {
-    b.rows = b.cols = 0;
-    HIP_TRY(c, hipMemcpyAsync(b.im, h_img, (size_t)rows * cols, hipMemcpyHostToDevice, c->stream2));
-    b.rows = rows; b.cols = cols;
-    return bd_enqueue(c, rows, cols, threshold);
-  };
-  const SiftLinkOut outs[2] = {{&out_l->n, out_l->kp, out_l->desc, out_l->cap}, {&out_r->n, out_r->kp, out_r->desc, out_r->cap}};
-  return sift_link_pair(c, det, img_l, img_r, rows, cols, stride, slot_l, slot_r, slot_capacity, outs);
+  det.enqueue = [&](const uint8_t *h_img) -> int { return bd_staged_enqueue(c, h_img, rows, cols, threshold); };
+  return sift_link_pair(c, det, img_l, img_r, rows, cols, stride, slot_l, slot_r, slot_capacity, pair_out(out_l), pair_out(out_r));
 }
 
 int spvo_brisk_detect_debug_layer(spvo_ctx *c, int layer, int what, uint8_t *out, int *rows, int *cols) {

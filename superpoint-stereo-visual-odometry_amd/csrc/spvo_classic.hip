@@ -4,6 +4,7 @@
 // detector link for spvo_classic_sift_pair), the ORB extractor as a device link behind a detector that reports octaves (orb_link.hip.h: orb_link_* for
 // spvo_brisk_orb_pair / spvo_akaze_orb_pair, and the test hook spvo_orb_octaves_link_debug), and spvo_preprocess for a context without an engine.  Everything here runs on the solver's stream (stream2) and owns its buffers (spvo_ctx::orb, spvo_ctx::cls).
 #include "spvo_internal.hip.h"
+#include "pair_call.hip.h"
 #include "orb.hip.h"
 #include "orb_link.hip.h"
 #include "classic_detect.hip.h"
@@ -218,6 +219,32 @@ int orb_enqueue(spvo_ctx *c, const OrbPlan &p, int rows, int cols, OrbKeypoint *
   }
   HIP_TRY(c, hipGetLastError());
   return SPVO_OK;
+}
+
+// The extractor's levels 0 .. top of the image resident in spvo_ctx::cls (spvo_orb_describe_octaves, orb_link_enqueue): level 0 is that image
+// itself (its image, smoothed image and scratch), levels 1 .. top live in spvo_ctx::orb's pyramid buffers with orb_prepare's geometry and
+// resize tables.  At most 7 resize launches, then the two smoothing launches over all of them; want[l] = 0 skips the smoothing of level l
+// (a level's bytes do not depend on who reads them).  -> the levels, for the describe launch that follows
+// (static: this namespace lies inside extern "C", where the library would export the name; its exported symbols stay as they are)
+static OrbLevels orb_levels_enqueue(spvo_ctx *c, const OrbPlan &plan, int rows, int cols, int top, const int *want) {
+  auto &b = c->cls;
+  auto &o = c->orb;
+  hipStream_t st = c->stream2;
+  OrbLevels lv{};
+  for (int l = 0; l <= top; ++l) {
+    OrbLevel &L = lv.l[l];
+    if (l == 0) { L.im = b.im; L.blur = b.blur; L.tmp = b.tmp; }
+    else { L.im = o.im + plan.off[l]; L.blur = o.blur + plan.off[l]; L.tmp = o.tmp + plan.off[l]; }
+    L.h = plan.ph[l]; L.w = plan.pw[l]; L.scale = plan.lscale[l];
+    L.want = L.cap = want[l];
+    if (l > 0)
+      hipLaunchKernelGGL(orb_resize_kernel, dim3((L.w + 63) / 64, (L.h + 3) / 4), dim3(256), 0, st, lv.l[l - 1].im, plan.ph[l - 1], plan.pw[l - 1], plan.pw[l - 1], L.im, L.h, L.w,
+                         o.tab + plan.toff[l]);
+  }
+  const dim3 grid((cols + 63) / 64, (rows + 3) / 4, top + 1);
+  hipLaunchKernelGGL(orb_blur_h_kernel, grid, dim3(256), 0, st, lv, o.taps);
+  hipLaunchKernelGGL(orb_blur_v_kernel, grid, dim3(256), 0, st, lv, o.taps);
+  return lv;
 }
 }  // namespace
 
@@ -539,20 +566,7 @@ int spvo_orb_describe_octaves(spvo_ctx *c, const uint8_t *img, int rows, int col
     b.oct_cap = nk;
   }
   HIP_TRY(c, hipMemcpyAsync(b.oct_rec, rec.data(), rec.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  OrbLevels lv{};
-  for (int l = 0; l <= top; ++l) {
-    OrbLevel &L = lv.l[l];
-    if (l == 0) { L.im = b.im; L.blur = b.blur; L.tmp = b.tmp; }
-    else { L.im = o.im + plan.off[l]; L.blur = o.blur + plan.off[l]; L.tmp = o.tmp + plan.off[l]; }
-    L.h = plan.ph[l]; L.w = plan.pw[l]; L.scale = plan.lscale[l];
-    L.want = L.cap = per_level[l];
-    if (l > 0)
-      hipLaunchKernelGGL(orb_resize_kernel, dim3((L.w + 63) / 64, (L.h + 3) / 4), dim3(256), 0, st, lv.l[l - 1].im, plan.ph[l - 1], plan.pw[l - 1], plan.pw[l - 1], L.im, L.h, L.w,
-                         o.tab + plan.toff[l]);
-  }
-  const dim3 grid((cols + 63) / 64, (rows + 3) / 4, top + 1);
-  hipLaunchKernelGGL(orb_blur_h_kernel, grid, dim3(256), 0, st, lv, o.taps);
-  hipLaunchKernelGGL(orb_blur_v_kernel, grid, dim3(256), 0, st, lv, o.taps);
+  const OrbLevels lv = orb_levels_enqueue(c, plan, rows, cols, top, per_level);   // (a level without a kept keypoint is not smoothed)
   hipLaunchKernelGGL(orb_describe_given_kernel, dim3((nk + 3) / 4), dim3(256), 0, st, lv, b.oct_rec, nk, o.disc, o.pattern, b.oct_angle, b.oct_desc);
   HIP_TRY(c, hipGetLastError());
   if (angle) HIP_TRY(c, hipMemcpyAsync(angle, b.oct_angle, (size_t)nk * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -619,22 +633,11 @@ int spvo_int::orb_link_enqueue(spvo_ctx *c, int rows, int cols, int max_octave, 
   OrbPlan plan;
   if (int rc = orb_prepare(c, rows, cols, 1, plan)) return rc;   // (sized by orb_link_ensure: the plan only)
   OrbLinkGeom g{};
-  OrbLevels lv{};
   for (int l = 0; l < ORB_LEVELS; ++l) { g.h[l] = plan.ph[l]; g.w[l] = plan.pw[l]; g.lscale[l] = plan.lscale[l]; }
   hipLaunchKernelGGL(orb_link_group_kernel, dim3(1), dim3(1024), 0, st, src, rows, cols, std::min(max_octave, ORB_LEVELS - 1), g, cap, b.lnk_kept, b.lnk_rec, b.lnk_cnt);
-  for (int l = 0; l <= max_octave; ++l) {
-    OrbLevel &L = lv.l[l];
-    if (l == 0) { L.im = b.im; L.blur = b.blur; L.tmp = b.tmp; }
-    else { L.im = o.im + plan.off[l]; L.blur = o.blur + plan.off[l]; L.tmp = o.tmp + plan.off[l]; }
-    L.h = plan.ph[l]; L.w = plan.pw[l]; L.scale = plan.lscale[l];
-    L.want = L.cap = 1;
-    if (l > 0)
-      hipLaunchKernelGGL(orb_resize_kernel, dim3((L.w + 63) / 64, (L.h + 3) / 4), dim3(256), 0, st, lv.l[l - 1].im, plan.ph[l - 1], plan.pw[l - 1], plan.pw[l - 1], L.im, L.h, L.w,
-                         o.tab + plan.toff[l]);
-  }
-  const dim3 grid((cols + 63) / 64, (rows + 3) / 4, max_octave + 1);
-  hipLaunchKernelGGL(orb_blur_h_kernel, grid, dim3(256), 0, st, lv, o.taps);
-  hipLaunchKernelGGL(orb_blur_v_kernel, grid, dim3(256), 0, st, lv, o.taps);
+  int smoothed[ORB_LEVELS];
+  std::fill(smoothed, smoothed + ORB_LEVELS, 1);
+  const OrbLevels lv = orb_levels_enqueue(c, plan, rows, cols, max_octave, smoothed);
   hipLaunchKernelGGL(orb_link_describe_kernel, dim3(std::min((cap + 3) / 4, 1024)), dim3(256), 0, st, lv, b.lnk_rec, b.lnk_cnt, cap, o.disc, o.pattern, b.lnk_angle, desc);
   HIP_TRY(c, hipGetLastError());
   return SPVO_OK;
@@ -707,6 +710,13 @@ int spvo_orb_octaves_link_debug(spvo_ctx *c, int rows, int cols, const float *xy
 
 int spvo_int::classic_upload_image(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride) { return cls_prepare(c, img, rows, cols, stride); }
 int spvo_int::classic_image_ensure(spvo_ctx *c, int rows, int cols) { return cls_ensure(c, rows, cols); }
+int spvo_int::classic_image_from_staged(spvo_ctx *c, const uint8_t *h_img, int rows, int cols) {
+  auto &b = c->cls;
+  b.rows = b.cols = 0;   // nothing resident until the upload is enqueued
+  HIP_TRY(c, hipMemcpyAsync(b.im, h_img, (size_t)rows * cols, hipMemcpyHostToDevice, c->stream2));
+  b.rows = rows; b.cols = cols;
+  return SPVO_OK;
+}
 void spvo_int::classic_rank_enqueue(spvo_ctx *c, const unsigned long long *keys, int *rank, const int *n_ptr, int cap) {
   hipLaunchKernelGGL(cls_rank_kernel, dim3(128), dim3(256), 0, c->stream2, keys, rank, n_ptr, cap);
 }
@@ -811,11 +821,9 @@ int spvo_classic_slot_fill_debug(spvo_ctx *c, int slot, const uint8_t *desc, int
 }
 
 namespace {
-// what spvo_classic_detect refuses of its options and of the image shape: the slot capacity, then what the kind's per-image entry points refuse
+// what spvo_classic_detect refuses of its options and of the image shape behind the slot capacity: what the kind's per-image entry points refuse
 int classic_check_opts(spvo_ctx *c, const spvo_classic_opts *opts, int rows, int cols) {
-  const int kind = opts->kind, cap = opts->slot_capacity;
-  if (kind_is_sift(kind)) return fail(c, SPVO_ERR_INVALID, "spvo_classic_detect: kind %d leaves rows of 128 floats, which no binary slot holds: call spvo_classic_sift_pair", kind);
-  if (cap <= 0 || cap > (1 << HAM_KEY_SHIFT)) return fail(c, SPVO_ERR_INVALID, "slot_capacity must be 1 .. %d", 1 << HAM_KEY_SHIFT);
+  const int kind = opts->kind;
   if (kind == SPVO_CLASSIC_ORB) {
     if (opts->nfeatures <= 0) return fail(c, SPVO_ERR_INVALID, "bad argument");
   } else if (kind_is_gftt(kind)) {
@@ -853,11 +861,7 @@ int orb_pair_chain(spvo_ctx *c, const spvo_classic_opts *opts, const OrbPlan &pl
 
 // a staged image (pinned, rows packed) becomes the resident image of spvo_ctx::cls and goes through the Shi-Tomasi or FAST detector, which leaves its list there
 int detector_enqueue(spvo_ctx *c, const spvo_classic_opts *opts, const uint8_t *h_img, int rows, int cols) {
-  auto &b = c->cls;
-  const size_t px = (size_t)rows * cols;
-  b.rows = b.cols = 0;
-  HIP_TRY(c, hipMemcpyAsync(b.im, h_img, px, hipMemcpyHostToDevice, c->stream2));
-  b.rows = rows; b.cols = cols;
+  if (int rc = classic_image_from_staged(c, h_img, rows, cols)) return rc;
   return kind_is_gftt(opts->kind) ? gftt_enqueue(c, rows, cols, opts->max_corners, opts->quality_level, opts->min_distance)
                                   : fast_enqueue(c, rows, cols, opts->fast_threshold, opts->fast_nonmax);
 }
@@ -887,16 +891,13 @@ int detector_brisk_chain(spvo_ctx *c, const spvo_classic_opts *opts, int rows, i
   return brisk_chain_enqueue(c, rows, cols, kind_is_gftt(opts->kind) ? 5.0f : 7.0f, opts->slot_capacity, detector_most(opts), out);
 }
 
-// the counts of both images from their mirrors; a pair that does not fit its slots is an error
-int classic_check_capacity(spvo_ctx *c, int cap, spvo_classic_features *const outs[2]) {
-  int worst = SPVO_OK;
+// the counts of both images from their mirrors, image by image (kept: this entry point answers a detector overflow with SPVO_ERR_CAPACITY;
+// whether the pair fits its slots is the protocol's rule, PairCall::commit)
+int classic_check_capacity(spvo_ctx *c, PairCall<BinPairFamily> &pc) {
   for (int k = 0; k < 2; ++k) {
-    const int *h_n = c->bin.h_n + 4 * k;
-    outs[k]->n = h_n[0];
-    if (h_n[1]) return fail(c, SPVO_ERR_CAPACITY, "spvo_classic_detect: corner buffer overflow in the %s image", k ? "right" : "left");
-    if (h_n[0] > cap) worst = SPVO_ERR_CAPACITY;
+    pc.count(k);
+    if (c->bin.h_n[4 * k + 1]) return fail(c, SPVO_ERR_CAPACITY, "spvo_classic_detect: corner buffer overflow in the %s image", k ? "right" : "left");
   }
-  if (worst) return fail(c, worst, "spvo_classic_detect: %d / %d rows do not fit slots of %d (slot_capacity)", outs[0]->n, outs[1]->n, cap);
   return SPVO_OK;
 }
 }  // namespace
@@ -904,29 +905,20 @@ int classic_check_capacity(spvo_ctx *c, int cap, spvo_classic_features *const ou
 int spvo_classic_detect(spvo_ctx *c, const spvo_classic_opts *opts, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int slot_l, int slot_r,
                         spvo_classic_features *out_l, spvo_classic_features *out_r) {
   if (!c || !opts || !img_l || !img_r || !out_l || !out_r || rows <= 0 || cols <= 0 || stride < (size_t)cols) return fail(c, SPVO_ERR_INVALID, "bad argument");
-  if (slot_l < 0 || slot_l >= N_BIN_SLOTS || slot_r < 0 || slot_r >= N_BIN_SLOTS || slot_l == slot_r) return fail(c, SPVO_ERR_INVALID, "bad slot");
-  spvo_classic_features *const outs[2] = {out_l, out_r};
-  for (auto *o : outs)
-    if (o->cap < 0) return fail(c, SPVO_ERR_INVALID, "bad output buffer");
-  if (int rc = classic_check_opts(c, opts, rows, cols)) return rc;
-  if (int rc = require_idle(c)) return rc;
-  HIP_TRY(c, hipSetDevice(c->cfg.device));
-  out_l->n = out_r->n = 0;
-  hipStream_t st = c->stream2;
-  auto &bb = c->bin;
-  PairStage &ps = bb.pair;
   const int kind = opts->kind, cap = opts->slot_capacity, row_bytes = kind_is_brisk(kind) ? 64 : 32;
+  PairCall<BinPairFamily> pc(c, "spvo_classic_detect", BinPairFamily{row_bytes}, pair_out(out_l), pair_out(out_r));
+  if (int rc = pc.check(slot_l, slot_r)) return rc;
+  // (kept: a SIFT kind is refused before the capacity is looked at; then what the kind's per-image entry points refuse)
+  if (kind_is_sift(kind)) return fail(c, SPVO_ERR_INVALID, "spvo_classic_detect: kind %d leaves rows of 128 floats, which no binary slot holds: call spvo_classic_sift_pair", kind);
+  if (int rc = pc.check_capacity(cap)) return rc;
+  if (int rc = classic_check_opts(c, opts, rows, cols)) return rc;
+  if (int rc = pc.open()) return rc;
+  auto &bb = c->bin;
   OrbPlan plan;
   if (int rc = classic_pair_ensure(c, opts, rows, cols, plan)) return rc;
-  // both slots are being rewritten: whatever was matched against their old contents is stale
-  const int slots[2] = {slot_l, slot_r};
-  for (int sl : slots) { slot_rewrite(bb.slots[sl]); bb.slots[sl].row_bytes = row_bytes; }
-  ps.mcache.invalidate();
-  // pinned staging: one upload per image
-  HIP_TRY(c, hipStreamSynchronize(st));   // (the staging buffer and the mirrors are the previous call's until its work is done)
-  ps.stage(img_l, img_r, rows, cols, stride);
+  if (int rc = pc.load(img_l, img_r, rows, cols, stride)) return rc;
   for (int k = 0; k < 2; ++k) {
-    const BinarySlot &s = bb.slots[slots[k]];
+    const BinarySlot &s = bb.slots[pc.slots[k]];
     const ChainOut out{bb.d_cnt + k * CLS_COUNTER_INTS, bb.d_kresp, s.d_kp, s.d_desc, s.d_n, bb.h_n + 4 * k, bb.h_kp + (size_t)k * cap, bb.h_desc + (size_t)k * cap * row_bytes};
     if (int rc = kind == SPVO_CLASSIC_ORB ? orb_pair_chain(c, opts, plan, rows, cols, k, out)
                  : row_bytes == 64        ? detector_brisk_chain(c, opts, rows, cols, k, out)
@@ -934,35 +926,11 @@ int spvo_classic_detect(spvo_ctx *c, const spvo_classic_opts *opts, const uint8_
       return rc;
     HIP_TRY(c, hipGetLastError());
   }
-  HIP_TRY(c, hipEventRecord(ps.ev_feat, st));
-  // spvo_set_prematch: the two standard matches behind the features, counts read on the device (a pair that turns out not to fit its
-  // slots is matched on whatever rows the slots hold; that result is dropped below).  They run on this stream, so ev_match is recorded
-  // here and nothing waits across streams.
-  // (a previous left slot of the other row width has no temporal match: skipped, the synchronous call reports the widths when asked)
-  const int prev = ps.last_slot_l;
-  const int partner[2] = {slot_r, ps.temporal_partner(slot_l, slot_r, prev >= 0 && bb.slots[prev].filled && bb.slots[prev].row_bytes == row_bytes)};
-  if (c->prematch) {
-    for (int k = 0; k < 2; ++k)
-      if (partner[k] >= 0)
-        if (int rc = enqueue_hamming_slots(c, slot_l, partner[k], c->pm_selector, c->pm_cross, c->pm_ratio, bb.h_match + (size_t)k * cap)) return rc;
-    HIP_TRY(c, hipEventRecord(ps.ev_match, st));
-  }
-  HIP_TRY(c, wait_event(ps.ev_feat));   // the one wait of the call: the matches go on behind it
-  ps.last_slot_l = -1;   // (the temporal partner is forgotten AFTER the wait here: a call that failed before it leaves the one it found)
-  if (int rc = classic_check_capacity(c, cap, outs)) return rc;
-  for (int k = 0; k < 2; ++k) {
-    BinarySlot &s = bb.slots[slots[k]];
-    s.n = outs[k]->n; s.filled = true;
-    const int ncopy = std::min(s.n, outs[k]->cap);
-    if (ncopy > 0 && outs[k]->kp) std::memcpy(outs[k]->kp, bb.h_kp + (size_t)k * cap, (size_t)ncopy * sizeof(OrbKeypoint));
-    if (ncopy > 0 && outs[k]->desc) std::memcpy(outs[k]->desc, bb.h_desc + (size_t)k * cap * row_bytes, (size_t)ncopy * row_bytes);
-  }
-  if (c->prematch)
-    for (int k = 0; k < 2; ++k)
-      if (partner[k] >= 0)
-        ps.mcache.record(k, slot_l, partner[k], bb.slots[slot_l].gen, bb.slots[partner[k]].gen, c->pm_selector, c->pm_cross, c->pm_ratio, bb.h_match + (size_t)k * cap);
-  ps.last_slot_l = slot_l;
-  return SPVO_OK;
+  if (int rc = pc.submit()) return rc;
+  if (int rc = classic_check_capacity(c, pc)) return rc;
+  const PairMirror mirrors[2] = {{bb.h_kp, sizeof(OrbKeypoint), bb.h_desc, (size_t)row_bytes},
+                                 {bb.h_kp + cap, sizeof(OrbKeypoint), bb.h_desc + (size_t)cap * row_bytes, (size_t)row_bytes}};
+  return pc.commit(mirrors);
 }
 
 }  // extern "C"

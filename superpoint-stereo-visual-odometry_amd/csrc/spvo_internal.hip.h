@@ -7,10 +7,16 @@
 //   spvo_net_f16.hip   FP16 engines                     spvo_net_s3.hip   FP32 engines in split (bf16x3) mode
 //   spvo_net_i8.hip    INT8 engines
 //   spvo_detect.hip    preprocess, heat map / NMS / sampling, the detector submissions, spvo_forward
-//   spvo_classic.hip   the classic front end: ORB, Shi-Tomasi, FAST, the ORB extractor, preprocess without an engine
-//   spvo_sift.hip      the classic front end: SIFT detector + descriptor, the extractor on given keypoints and behind the Shi-Tomasi / FAST detectors
-//   spvo_brisk.hip     the classic front end: BRISK descriptor extractor on given keypoints
-//   spvo_brisk_detect.hip   the classic front end: BRISK keypoint detector, and detector + extractor of a stereo pair into the binary slots
+//   spvo_classic.hip   the classic front end: ORB, Shi-Tomasi, FAST, the ORB extractor (on given keypoints, at their octaves, as a device link), the
+//                      binary slots and spvo_classic_detect, preprocess without an engine
+//   spvo_sift.hip      the classic front end: SIFT detector + descriptor, the extractor on given keypoints, the SIFT slots and the three pair calls that fill
+//                      them (spvo_sift_detect_pair, spvo_classic_sift_pair, sift_link_pair behind the BRISK / AKAZE detectors)
+//   spvo_brisk.hip     the classic front end: BRISK descriptor extractor on given keypoints and as a link of the pair calls' chains
+//   spvo_brisk_detect.hip   the classic front end: BRISK keypoint detector, and its stereo-pair calls (BRISK / ORB rows into the binary slots, SIFT rows into the SIFT slots)
+//   spvo_akaze.hip     the classic front end: AKAZE keypoint detector and MLDB descriptor, and its stereo-pair calls (MLDB / ORB / BRISK rows into the binary
+//                      slots, SIFT rows into the SIFT slots)
+//   pair_call.hip.h    the resident stereo-pair protocol all of those pair calls run through (PairCall: refusals, staging, temporal partner, prematch, the
+//                      one wait, capacity rule, slot bookkeeping), with the binary slots' side of it; the SIFT slots' side is in spvo_sift.hip
 //   spvo_match.hip     descriptor matching (L2, Hamming)
 //   spvo_solve.hip     triangulation, PnP-RANSAC, gating, Levenberg-Marquardt, the fused solve
 #pragma once
@@ -158,8 +164,9 @@ struct PrematchCache {
   }
 };
 
-// What a "stereo pair into two slots" entry point (spvo_classic_detect, spvo_sift_detect_pair) stages a call through: the pinned copy of
-// both images, the events the host and the matcher wait for, the temporal partner and the call's prematches.  Works on the solver's stream.
+// What a "stereo pair into two slots" entry point stages a call through: the pinned copy of both images, the events the host and the
+// matcher wait for, the temporal partner and the call's prematches.  Works on the solver's stream.  One per family of slots (spvo_ctx::bin,
+// spvo_ctx::sift); the protocol that drives it is PairCall (pair_call.hip.h), the only caller of stage and temporal_partner.
 struct PairStage {
   uint8_t *h_img = nullptr;            // pinned [2][img_cap]: both images of a call, rows packed
   size_t img_cap = 0;
@@ -173,6 +180,10 @@ struct PairStage {
   int temporal_partner(int slot_l, int slot_r, bool partner_ok) const { return last_slot_l >= 0 && last_slot_l != slot_l && last_slot_l != slot_r && partner_ok ? last_slot_l : -1; }
   void release();
 };
+// one image's output struct of such an entry point (spvo_classic_features, spvo_brisk_features, spvo_akaze_features, spvo_sift_features,
+// spvo_akaze_sift_features: one layout, records and rows that differ)
+struct PairOut { int *n; void *kp; void *desc; int cap; };
+template <class T> inline PairOut pair_out(T *o) { return PairOut{&o->n, o->kp, o->desc, o->cap}; }
 
 struct MatchScratch {         // one set per concurrently enqueued match
   float *d_na = nullptr, *d_nb = nullptr, *d_best_d2 = nullptr;
@@ -727,6 +738,9 @@ void classic_release(spvo_ctx *c);   // frees spvo_ctx::bin (spvo_destroy)
 void classic_release_slots(spvo_ctx *c);   // ... the part of it that is sized by the slot capacity
 // a host image (strided view) becomes the resident image of spvo_ctx::cls, every buffer of it grown to the shape (enqueued on the solver's stream)
 int classic_upload_image(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride);
+// a staged image (pinned, rows packed: PairCall::image) becomes the resident image of spvo_ctx::cls, behind classic_image_ensure for its shape
+// (enqueued on the solver's stream); the first link of every pair call's chain whose detector reads spvo_ctx::cls
+int classic_image_from_staged(spvo_ctx *c, const uint8_t *h_img, int rows, int cols);
 // spvo_classic_detect's own preparations, for another entry point that fills the binary slots (spvo_brisk_detect_pair).  classic_slots_ensure:
 // the slots, the call's mirrors and the pinned staging for `cap` rows per slot and images of `px` bytes; a larger `cap` than any before
 // empties every slot.  classic_image_ensure: every buffer of spvo_ctx::cls grown to a rows x cols image; none is resident afterwards.
@@ -788,9 +802,9 @@ int brisk_pair_chain_enqueue(spvo_ctx *c, int rows, int cols, int cap, const Bri
 // ---- spvo_sift.hip
 void sift_release(spvo_ctx *c);      // frees spvo_ctx::sift (spvo_destroy)
 // The SIFT extractor as a link behind a detector that left records with an octave on the device (sift.hip.h: SiftLinkIO;
-// spvo_brisk_sift_pair, spvo_akaze_sift_pair).  sift_link_pair is the whole call around the detector -- spvo_classic_sift_pair's protocol:
-// slots, capacity, staging, temporal partner, prematch, one wait -- so that neither detector object copies it; the detector is three
-// functions.  Every refusal comes before anything is touched, every allocation (`prepare` included) before the first launch.
+// spvo_brisk_sift_pair, spvo_akaze_sift_pair).  sift_link_pair is the whole call around the detector -- a PairCall on the SIFT slots
+// (pair_call.hip.h) with the link's allocations and chains -- so that neither detector object needs the SIFT unit's internals; the detector
+// is three functions.  Every refusal comes before anything is touched, every allocation (`prepare` included) before the first launch.
 struct SiftLinkDetector {
   const char *who;                                   // the entry point, for the error text
   int max_octave;                                    // the pyramid is built for octaves 0 .. max_octave, whichever the records name
@@ -798,11 +812,10 @@ struct SiftLinkDetector {
   std::function<int(SiftLinkSrc &)> prepare;         // behind classic_image_ensure: the detector's buffers for the shape; where its list will lie
   std::function<int(const uint8_t *)> enqueue;       // the staged image (pinned, rows packed) becomes the resident one and goes through the detector's chain
 };
-struct SiftLinkOut { int *n; void *kp; float *desc; int cap; };   // spvo_sift_features / spvo_akaze_sift_features, whose records differ
 // (SPVO_OK and SPVO_ERR_CAPACITY are answered behind the call's one wait: the chains of both images have run, and an AKAZE sink has left
 // image k's contrast factors in spvo_ctx::sift.h_n + 8 + 4 k)
 int sift_link_pair(spvo_ctx *c, const SiftLinkDetector &det, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int slot_l, int slot_r, int slot_capacity,
-                   const SiftLinkOut outs[2]);
+                   const PairOut &out_l, const PairOut &out_r);
 // ---- spvo_match.hip
 int ensure_match(spvo_ctx *c, int na, int nb);
 struct MatchReq {

@@ -9,13 +9,15 @@
 // spvo_sift_describe is the extractor alone on a caller's records: it reads the u8 image the Shi-Tomasi / FAST / BRISK / AKAZE detectors and
 // the other extractors keep resident (spvo_ctx::cls), builds a Gaussian-only pyramid in the same buffer and describes in one launch.
 // spvo_classic_sift_pair is that extractor behind the Shi-Tomasi / FAST detector for both images of a stereo pair, the list never leaving
-// the device: detector chain (spvo_classic.hip), base level, the describe kernel into a SIFT slot; spvo_sift_detect_pair's staging, slots,
-// prematch and temporal partner.
-// sift_link_pair is the same protocol around a detector that reports an octave (BRISK, AKAZE: spvo_brisk_sift_pair and spvo_akaze_sift_pair
+// the device: detector chain (spvo_classic.hip), base level, the describe kernel into a SIFT slot.
+// sift_link_pair is such a call around a detector that reports an octave (BRISK, AKAZE: spvo_brisk_sift_pair and spvo_akaze_sift_pair
 // in the detectors' objects hand it their chain as three functions): the extractor's pyramid for octaves 0 .. the detector's highest,
 // reduced to the levels a layer-0 record reads, and the describe kernel on the records where they lie (SiftLinkIO).  spvo_sift_link_debug
 // runs that link on a caller's list.
+// All three pair calls are a PairCall<SiftPairFamily> (pair_call.hip.h: staging, slots, temporal partner, prematch, the one wait, the
+// capacity rule) around their own allocations and chains.
 #include "spvo_internal.hip.h"
+#include "pair_call.hip.h"
 #include "sift.hip.h"
 
 #include <numeric>
@@ -233,7 +235,7 @@ int sift_slots_ensure(spvo_ctx *c, int cap, size_t px) {
   return SPVO_OK;
 }
 
-// spvo_set_prematch for an entry point that fills two SIFT slots (spvo_sift_detect_pair, spvo_classic_sift_pair), in three steps.  The
+// spvo_set_prematch for an entry point that fills two SIFT slots, in three steps (the other two: SiftPairFamily).  The
 // matches are enqueued before the counts are known: scratch for full slots, results spaced by the matcher's capacity
 int sift_prematch_ensure(spvo_ctx *c) {
   auto &s = c->sift;
@@ -250,35 +252,56 @@ int sift_prematch_ensure(spvo_ctx *c) {
   }
   return SPVO_OK;
 }
-// ... the two standard matches (slot_l -> partner[0], the stereo one, and -> partner[1], the temporal one, or -1) as ONE set of launches
-// behind the features (pair.ev_feat, recorded by the caller), counts read on the device
-int sift_enqueue_prematch(spvo_ctx *c, int slot_l, const int partner[2]) {
-  auto &s = c->sift;
-  if (!c->prematch) return SPVO_OK;
-  PostScope post(c);
-  MatchReq req[2];
-  int njobs = 0;
-  const SiftSlot &a = s.slots[slot_l];
-  for (int k = 0; k < 2; ++k) {
-    if (partner[k] < 0) continue;
-    const SiftSlot &b = s.slots[partner[k]];
-    req[njobs++] = MatchReq{a.d_desc, b.d_desc, s.slot_cap, s.slot_cap, a.d_n, b.d_n, a.d_sqn, b.d_sqn};
+// The SIFT slots' side of the resident-pair protocol (pair_call.hip.h lists what a family is): features on the solver's stream, matches
+// where the L2 matcher runs (PostScope), so the chains wait for the matches of the call before
+struct SiftPairFamily {
+  static constexpr int SLOTS = N_SIFT_SLOTS, CAP_MAX = SIFT_SLOT_MAX;
+  static constexpr bool OUT_NEEDS_BUFFERS = true, FORGETS_AFTER_WAIT = false;
+  static PairStage &pair(spvo_ctx *c) { return c->sift.pair; }
+  static const int *h_n(spvo_ctx *c) { return c->sift.h_n; }
+  static SlotState &slot(spvo_ctx *c, int i) { return c->sift.slots[i]; }
+  static void rewrite(spvo_ctx *c, int i) { slot_rewrite(c->sift.slots[i]); }
+  static bool partner_ok(spvo_ctx *c, int prev) { return c->sift.slots[prev].filled; }
+  // a match of an earlier call (or of spvo_sift_detect_pair's attempt before) may still read the slots where the L2 matcher runs
+  static int before_chains(spvo_ctx *c) {
+    if (c->sift.match_pending) HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->sift.pair.ev_match, 0));
+    return SPVO_OK;
   }
-  HIP_TRY(c, hipStreamWaitEvent(c->post, s.pair.ev_feat, 0));
-  if (int rc = enqueue_matches(c, req, njobs, c->pm_selector, c->pm_cross, c->pm_ratio, s.h_match)) return rc;
-  HIP_TRY(c, hipEventRecord(s.pair.ev_match, c->post));
-  s.match_pending = true;
-  return SPVO_OK;
-}
-// ... and, once both slots are filled, where their results will be: job `job`'s lands in cache entry `job`
-void sift_record_prematch(spvo_ctx *c, int slot_l, const int partner[2]) {
-  auto &s = c->sift;
-  if (!c->prematch) return;
-  for (int k = 0, job = 0; k < 2; ++k) {
-    if (partner[k] < 0) continue;
-    s.pair.mcache.record(job, slot_l, partner[k], s.slots[slot_l].gen, s.slots[partner[k]].gen, c->pm_selector, c->pm_cross, c->pm_ratio, s.h_match + (size_t)job * c->match_cap);
-    ++job;
+  // the two standard matches (slot_l -> partner[0], the stereo one, and -> partner[1], the temporal one, or -1) as ONE set of launches
+  // behind the features (pair.ev_feat), counts read on the device
+  static int enqueue_prematch(spvo_ctx *c, int slot_l, const int partner[2], int) {
+    auto &s = c->sift;
+    if (!c->prematch) return SPVO_OK;
+    PostScope post(c);
+    MatchReq req[2];
+    int njobs = 0;
+    const SiftSlot &a = s.slots[slot_l];
+    for (int k = 0; k < 2; ++k) {
+      if (partner[k] < 0) continue;
+      const SiftSlot &b = s.slots[partner[k]];
+      req[njobs++] = MatchReq{a.d_desc, b.d_desc, s.slot_cap, s.slot_cap, a.d_n, b.d_n, a.d_sqn, b.d_sqn};
+    }
+    HIP_TRY(c, hipStreamWaitEvent(c->post, s.pair.ev_feat, 0));
+    if (int rc = enqueue_matches(c, req, njobs, c->pm_selector, c->pm_cross, c->pm_ratio, s.h_match)) return rc;
+    HIP_TRY(c, hipEventRecord(s.pair.ev_match, c->post));
+    s.match_pending = true;
+    return SPVO_OK;
   }
+  // ... and, once both slots are filled, where their results will be: job `job`'s lands in cache entry `job`
+  static void record_prematch(spvo_ctx *c, int slot_l, const int partner[2], int) {
+    auto &s = c->sift;
+    if (!c->prematch) return;
+    for (int k = 0, job = 0; k < 2; ++k) {
+      if (partner[k] < 0) continue;
+      s.pair.mcache.record(job, slot_l, partner[k], s.slots[slot_l].gen, s.slots[partner[k]].gen, c->pm_selector, c->pm_cross, c->pm_ratio, s.h_match + (size_t)job * c->match_cap);
+      ++job;
+    }
+  }
+};
+// the mirrors commit copies image k's rows from: records of `kp_bytes` in each half's front of h_src (NULL: the caller converts), rows of 128 floats
+PairMirror sift_mirror(spvo_ctx *c, int k, bool records, size_t kp_bytes) {
+  auto &s = c->sift;
+  return PairMirror{records ? s.h_src + (size_t)k * s.slot_cap : nullptr, kp_bytes, s.hm_desc + (size_t)k * s.slot_cap * 128, 128 * sizeof(float)};
 }
 
 // spvo_sift_describe's (and spvo_sift_link_debug's) device copies of a caller's n records and their rows
@@ -374,49 +397,30 @@ int sift_link_enqueue(spvo_ctx *c, int rows, int cols, const SiftPyr &P, SiftLin
 // into the pinned h_n before the next image's chain clears anything.  A slot's d_src holds the SiftKey records; the mirror h_src holds the
 // detector's own records, `stride` bytes each.
 int spvo_int::sift_link_pair(spvo_ctx *c, const SiftLinkDetector &det, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int slot_l, int slot_r,
-                             int slot_capacity, const SiftLinkOut outs[2]) {
+                             int slot_capacity, const PairOut &out_l, const PairOut &out_r) {
   static_assert(sizeof(SiftKey) <= sizeof(SiftSrc) && sizeof(AkazeKp) <= sizeof(SiftSrc), "a slot's source array and its mirror hold the records");
   const char *who = det.who;
-  if (slot_l < 0 || slot_l >= N_SIFT_SLOTS || slot_r < 0 || slot_r >= N_SIFT_SLOTS || slot_l == slot_r) return fail(c, SPVO_ERR_INVALID, "bad slot");
-  for (int k = 0; k < 2; ++k)
-    if (outs[k].cap < 0 || (outs[k].cap > 0 && (!outs[k].kp || !outs[k].desc))) return fail(c, SPVO_ERR_INVALID, "bad output buffer");
   const int cap = slot_capacity;
-  if (cap <= 0 || cap > SIFT_SLOT_MAX) return fail(c, SPVO_ERR_INVALID, "slot_capacity must be 1 .. %d", SIFT_SLOT_MAX);
-  if (int rc = det.check()) return rc;
-  if (int rc = sift_check_image(c, who, rows, cols)) return rc;
-  if (int rc = sift_link_check_octave(c, who, rows, cols, det.max_octave)) return rc;
-  if (int rc = require_idle(c)) return rc;
-  HIP_TRY(c, hipSetDevice(c->cfg.device));
-  *outs[0].n = *outs[1].n = 0;
+  PairCall<SiftPairFamily> pc(c, who, SiftPairFamily{}, out_l, out_r);
+  int rc;
+  if ((rc = pc.check(slot_l, slot_r)) || (rc = pc.check_capacity(cap)) || (rc = det.check()) || (rc = sift_check_image(c, who, rows, cols)) ||
+      (rc = sift_link_check_octave(c, who, rows, cols, det.max_octave)) || (rc = pc.open()))
+    return rc;
   auto &s = c->sift;
-  PairStage &ps = s.pair;
-  hipStream_t st = c->stream2;
-  const size_t px = (size_t)rows * cols;
   s.rows = s.cols = 0;   // the pyramid buffer holds the levels that are read of each image in turn: nothing spvo_sift_debug_level could serve
   SiftPyr P{};
   const size_t pyr_floats = sift_link_plan(rows, cols, det.max_octave, P);
   SiftLinkSrc src{};
   // every allocation before the first launch of the chain; the image buffer before the detector's layout, which points into it
-  int rc;
   if ((rc = classic_image_ensure(c, rows, cols)) || (rc = det.prepare(src))) return rc;
   if (src.stride <= 0 || src.stride % 4 || src.stride > (int)sizeof(SiftSrc)) return fail(c, SPVO_ERR_STATE, "%s: records of %d bytes", who, src.stride);
-  if ((rc = sift_link_ensure(c, pyr_floats, src.keep ? src.n_cap : 0)) || (rc = sift_slots_ensure(c, cap, px)) || (rc = sift_prematch_ensure(c))) return rc;
+  if ((rc = sift_link_ensure(c, pyr_floats, src.keep ? src.n_cap : 0)) || (rc = sift_slots_ensure(c, cap, (size_t)rows * cols)) || (rc = sift_prematch_ensure(c))) return rc;
   P.pyr = s.pyr;
-  // both slots are being rewritten: whatever was matched against their old contents is stale
-  const int slots[2] = {slot_l, slot_r};
-  for (int sl : slots) slot_rewrite(s.slots[sl]);
-  ps.mcache.invalidate();
-  // (the temporal partner is forgotten BEFORE staging, as in spvo_sift_detect_pair: a call that fails from now on leaves none for the next call)
-  const int partner[2] = {slot_r, ps.temporal_partner(slot_l, slot_r, ps.last_slot_l >= 0 && s.slots[ps.last_slot_l].filled)};
-  ps.last_slot_l = -1;
-  HIP_TRY(c, hipStreamSynchronize(st));   // (the staging buffer and the mirrors are the previous call's until its work is done)
-  ps.stage(img_l, img_r, rows, cols, stride);
-  // a match of an earlier call may still read the slots where the L2 matcher runs
-  if (s.match_pending) HIP_TRY(c, hipStreamWaitEvent(st, ps.ev_match, 0));
+  if ((rc = pc.load(img_l, img_r, rows, cols, stride))) return rc;
   char *const h_rec = reinterpret_cast<char *>(s.h_src);
   for (int k = 0; k < 2; ++k) {   // left chain, then the right one
-    if ((rc = det.enqueue(ps.h_img + k * px))) return rc;
-    const SiftSlot &t = s.slots[slots[k]];
+    if ((rc = det.enqueue(pc.image(k)))) return rc;
+    const SiftSlot &t = s.slots[pc.slots[k]];
     SiftLinkIO io{};
     io.s = src;
     io.slot_cap = cap;
@@ -426,25 +430,13 @@ int spvo_int::sift_link_pair(spvo_ctx *c, const SiftLinkDetector &det, const uin
     io.h_n = s.h_n + 4 * k; io.h_k = s.h_n + 8 + 4 * k;
     if ((rc = sift_link_enqueue(c, rows, cols, P, io, false))) return rc;
   }
-  HIP_TRY(c, hipEventRecord(ps.ev_feat, st));
-  if ((rc = sift_enqueue_prematch(c, slot_l, partner))) return rc;   // (a pair that turns out not to fit its slots: that result is dropped below)
-  HIP_TRY(c, wait_event(ps.ev_feat));   // the one wait of the call: the matches go on behind it
-  for (int k = 0; k < 2; ++k) *outs[k].n = s.h_n[4 * k];
-  // (the detectors size their lists from the image, so the flag cannot be set; were it, the counts would be wrong)
+  if ((rc = pc.submit())) return rc;
+  pc.count(0); pc.count(1);
+  // (kept: the BRISK and AKAZE callers answer a detector overflow with SPVO_ERR_STATE -- the detectors size their lists from the image, so
+  // the flag cannot be set; were it, the counts would be wrong)
   if (s.h_n[1] || s.h_n[5]) return fail(c, SPVO_ERR_STATE, "%s: the candidate list overflowed although it is sized from the image", who);
-  if (*outs[0].n > cap || *outs[1].n > cap) return fail(c, SPVO_ERR_CAPACITY, "%s: %d / %d rows do not fit slots of %d (slot_capacity)", who, *outs[0].n, *outs[1].n, cap);
-  for (int k = 0; k < 2; ++k) {
-    SiftSlot &t = s.slots[slots[k]];
-    t.n = *outs[k].n; t.filled = true;
-    const int ncopy = std::min(t.n, outs[k].cap);
-    if (ncopy > 0) {
-      std::memcpy(outs[k].kp, h_rec + (size_t)k * s.slot_cap * sizeof(SiftSrc), (size_t)ncopy * src.stride);
-      std::memcpy(outs[k].desc, s.hm_desc + (size_t)k * s.slot_cap * 128, (size_t)ncopy * 128 * sizeof(float));
-    }
-  }
-  sift_record_prematch(c, slot_l, partner);
-  ps.last_slot_l = slot_l;
-  return SPVO_OK;
+  const PairMirror mirrors[2] = {sift_mirror(c, 0, true, (size_t)src.stride), sift_mirror(c, 1, true, (size_t)src.stride)};   // (the detector's own records)
+  return pc.commit(mirrors);
 }
 
 void spvo_int::sift_release(spvo_ctx *c) {
@@ -538,73 +530,46 @@ int spvo_sift_slot_rows(spvo_ctx *c, int slot, int *n) {
 int spvo_sift_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int slot_l, int slot_r, int slot_capacity,
                           spvo_sift_features *out_l, spvo_sift_features *out_r) {
   if (!c || !img_l || !img_r || !out_l || !out_r || rows <= 0 || cols <= 0 || stride < (size_t)cols) return fail(c, SPVO_ERR_INVALID, "bad argument");
-  if (slot_l < 0 || slot_l >= N_SIFT_SLOTS || slot_r < 0 || slot_r >= N_SIFT_SLOTS || slot_l == slot_r) return fail(c, SPVO_ERR_INVALID, "bad slot");
-  spvo_sift_features *outs[2] = {out_l, out_r};
-  for (auto *o : outs)
-    if (o->cap < 0 || (o->cap > 0 && (!o->kp || !o->desc))) return fail(c, SPVO_ERR_INVALID, "bad output buffer");
-  if (slot_capacity <= 0 || slot_capacity > SIFT_SLOT_MAX) return fail(c, SPVO_ERR_INVALID, "slot_capacity must be 1 .. %d", SIFT_SLOT_MAX);
-  if (int rc = sift_check_image(c, "spvo_sift_detect_pair", rows, cols)) return rc;
-  if (!c->pendq.empty()) return fail(c, SPVO_ERR_STATE, "detector submissions are in flight: complete them with spvo_detect_wait first");
-  HIP_TRY(c, hipSetDevice(c->cfg.device));
-  out_l->n = out_r->n = 0;
+  PairCall<SiftPairFamily> pc(c, "spvo_sift_detect_pair", SiftPairFamily{}, pair_out(out_l), pair_out(out_r));
+  int rc;
+  if ((rc = pc.check(slot_l, slot_r)) || (rc = pc.check_capacity(slot_capacity)) || (rc = sift_check_image(c, pc.who, rows, cols)) || (rc = pc.open())) return rc;
   c->akaze.valid = false;   // as spvo_sift_detect: the AKAZE scale space's claim ends
   auto &s = c->sift;
-  PairStage &ps = s.pair;
   hipStream_t st = c->stream2;
   SiftPyr P{};
   const size_t pyr_floats = sift_plan(rows, cols, P), px = (size_t)rows * cols;
   s.rows = s.cols = 0;   // nothing resident until a pyramid is enqueued
   const int cand_cap = std::max(s.cand_cap, std::max(8192, (int)((size_t)4 * rows * cols / 16)));
-  if (int rc = sift_ensure(c, rows, cols, pyr_floats, cand_cap)) return rc;
-  if (int rc = sift_order_ensure(c, s.cand_cap)) return rc;
-  if (int rc = sift_slots_ensure(c, slot_capacity, px)) return rc;
-  const int cap = s.slot_cap;
-  if (int rc = sift_prematch_ensure(c)) return rc;
+  if ((rc = sift_ensure(c, rows, cols, pyr_floats, cand_cap)) || (rc = sift_order_ensure(c, s.cand_cap)) || (rc = sift_slots_ensure(c, slot_capacity, px))) return rc;
+  pc.cap = s.slot_cap;   // (kept: this entry point's capacity rule is the slots' own capacity, the largest slot_capacity seen: what sift_gather_kernel truncates at)
+  if ((rc = sift_prematch_ensure(c))) return rc;
   P.pyr = s.pyr;
-  // both slots are being rewritten: whatever was matched against their old contents is stale
-  const int slots[2] = {slot_l, slot_r};
-  for (int sl : slots) slot_rewrite(s.slots[sl]);
-  ps.mcache.invalidate();
-  // (the temporal partner is forgotten BEFORE staging here: a call that fails from now on leaves none for the next call)
-  const int partner[2] = {slot_r, ps.temporal_partner(slot_l, slot_r, ps.last_slot_l >= 0 && s.slots[ps.last_slot_l].filled)};
-  ps.last_slot_l = -1;
-  HIP_TRY(c, hipStreamSynchronize(st));   // (the staging buffer and the mirrors are the previous call's until its work is done)
-  ps.stage(img_l, img_r, rows, cols, stride);
+  if ((rc = pc.load(img_l, img_r, rows, cols, stride))) return rc;
   for (int attempt = 0;; ++attempt) {
-    // a match of an earlier call (or of the attempt before) may still read the slots where the L2 matcher runs
-    if (s.match_pending) HIP_TRY(c, hipStreamWaitEvent(st, ps.ev_match, 0));
     for (int k = 0; k < 2; ++k) {   // left chain, then the right one: the one resident pyramid is reused in stream order
       s.rows = s.cols = 0;
-      HIP_TRY(c, hipMemcpyAsync(s.img, ps.h_img + k * px, px, hipMemcpyHostToDevice, st));
-      if (int rc = sift_enqueue_pyramid(c, s.img, rows, cols, P)) return rc;
+      HIP_TRY(c, hipMemcpyAsync(s.img, pc.image(k), px, hipMemcpyHostToDevice, st));
+      if ((rc = sift_enqueue_pyramid(c, s.img, rows, cols, P))) return rc;
       s.plan = P; s.rows = rows; s.cols = cols; s.gauss_only = false;
-      if (int rc = sift_enqueue_features(c, P)) return rc;
-      if (int rc = sift_enqueue_order(c, s.slots[slots[k]], k)) return rc;
+      if ((rc = sift_enqueue_features(c, P)) || (rc = sift_enqueue_order(c, s.slots[pc.slots[k]], k))) return rc;
     }
-    HIP_TRY(c, hipEventRecord(ps.ev_feat, st));
-    if (int rc = sift_enqueue_prematch(c, slot_l, partner)) return rc;   // (a pair that turns out not to fit its slots: that result is dropped below)
-    HIP_TRY(c, wait_event(ps.ev_feat));   // the one wait of the call: the matches go on behind it
+    if ((rc = pc.submit())) return rc;
     int most = 0;
     for (int k = 0; k < 2; ++k) most = std::max(most, std::max(s.h_n[4 * k + 1], s.h_n[4 * k + 2]));
     if (most <= s.cand_cap) break;
     // more candidates (or raw rows) than the lists hold: grow them to what was counted and run the pair again (a second wait)
     if (attempt >= 2) return fail(c, SPVO_ERR_CAPACITY, "spvo_sift_detect_pair: %d candidates / keypoints do not fit", most);
-    if (s.match_pending) HIP_TRY(c, wait_event(ps.ev_match));
-    if (int rc = sift_ensure(c, rows, cols, pyr_floats, most + 1024)) return rc;
-    if (int rc = sift_order_ensure(c, s.cand_cap)) return rc;
+    if (s.match_pending) HIP_TRY(c, wait_event(s.pair.ev_match));
+    if ((rc = sift_ensure(c, rows, cols, pyr_floats, most + 1024)) || (rc = sift_order_ensure(c, s.cand_cap)) || (rc = SiftPairFamily::before_chains(c))) return rc;
   }
-  for (int k = 0; k < 2; ++k) outs[k]->n = s.h_n[4 * k];
-  if (out_l->n > cap || out_r->n > cap) return fail(c, SPVO_ERR_CAPACITY, "spvo_sift_detect_pair: %d / %d rows do not fit slots of %d (slot_capacity)", out_l->n, out_r->n, cap);
+  pc.count(0); pc.count(1);
+  const PairMirror mirrors[2] = {sift_mirror(c, 0, false, 0), sift_mirror(c, 1, false, 0)};   // (the records are built from the sources below)
+  if ((rc = pc.commit(mirrors))) return rc;
+  spvo_sift_features *const outs[2] = {out_l, out_r};
   for (int k = 0; k < 2; ++k) {
-    SiftSlot &t = s.slots[slots[k]];
-    t.n = outs[k]->n; t.filled = true;
-    const int ncopy = std::min(t.n, outs[k]->cap);
-    const SiftSrc *src = s.h_src + (size_t)k * cap;
-    for (int i = 0; i < ncopy; ++i) outs[k]->kp[i] = sift_record(src[i].pos, src[i].off, __builtin_bit_cast(int, src[i].angle));
-    if (ncopy > 0) std::memcpy(outs[k]->desc, s.hm_desc + (size_t)k * cap * 128, (size_t)ncopy * 128 * sizeof(float));
+    const SiftSrc *src = s.h_src + (size_t)k * s.slot_cap;
+    for (int i = 0, n = pc.ncopy(k); i < n; ++i) outs[k]->kp[i] = sift_record(src[i].pos, src[i].off, __builtin_bit_cast(int, src[i].angle));
   }
-  sift_record_prematch(c, slot_l, partner);
-  ps.last_slot_l = slot_l;
   return SPVO_OK;
 }
 
@@ -620,44 +585,25 @@ int spvo_classic_sift_pair(spvo_ctx *c, const spvo_classic_opts *opts, const uin
   const int kind = opts->kind, cap = opts->slot_capacity;
   if (kind != SPVO_CLASSIC_GFTT_SIFT && kind != SPVO_CLASSIC_FAST_SIFT)
     return fail(c, SPVO_ERR_INVALID, "spvo_classic_sift_pair: kind %d (SPVO_CLASSIC_GFTT_SIFT or SPVO_CLASSIC_FAST_SIFT; the other kinds are spvo_classic_detect's)", kind);
-  if (slot_l < 0 || slot_l >= N_SIFT_SLOTS || slot_r < 0 || slot_r >= N_SIFT_SLOTS || slot_l == slot_r) return fail(c, SPVO_ERR_INVALID, "bad slot");
-  spvo_sift_features *outs[2] = {out_l, out_r};
-  for (auto *o : outs)
-    if (o->cap < 0 || (o->cap > 0 && (!o->kp || !o->desc))) return fail(c, SPVO_ERR_INVALID, "bad output buffer");
-  if (cap <= 0 || cap > SIFT_SLOT_MAX) return fail(c, SPVO_ERR_INVALID, "slot_capacity must be 1 .. %d", SIFT_SLOT_MAX);
-  if (int rc = classic_detector_check(c, "spvo_classic_sift_pair", opts, rows, cols)) return rc;
-  if (int rc = sift_check_image(c, "spvo_classic_sift_pair", rows, cols)) return rc;
-  if (int rc = require_idle(c)) return rc;
-  HIP_TRY(c, hipSetDevice(c->cfg.device));
-  out_l->n = out_r->n = 0;
+  PairCall<SiftPairFamily> pc(c, "spvo_classic_sift_pair", SiftPairFamily{}, pair_out(out_l), pair_out(out_r));
+  int rc;
+  if ((rc = pc.check(slot_l, slot_r)) || (rc = pc.check_capacity(cap)) || (rc = classic_detector_check(c, pc.who, opts, rows, cols)) || (rc = sift_check_image(c, pc.who, rows, cols)) ||
+      (rc = pc.open()))
+    return rc;
   c->akaze.valid = false;   // as spvo_sift_detect_pair: the AKAZE scale space's claim ends
   auto &s = c->sift;
-  PairStage &ps = s.pair;
   hipStream_t st = c->stream2;
   const size_t px = (size_t)rows * cols;
   s.rows = s.cols = 0;   // the pyramid buffer holds one level of each image in turn: nothing spvo_sift_debug_level could serve
-  if (int rc = classic_image_ensure(c, rows, cols)) return rc;
-  if (int rc = sift_pyr_ensure(c, px)) return rc;
-  if (int rc = sift_slots_ensure(c, cap, px)) return rc;
-  if (int rc = sift_prematch_ensure(c)) return rc;
+  if ((rc = classic_image_ensure(c, rows, cols)) || (rc = sift_pyr_ensure(c, px)) || (rc = sift_slots_ensure(c, cap, px)) || (rc = sift_prematch_ensure(c))) return rc;
   SiftPyr P{};
   P.n_oct = 1; P.h[0] = rows; P.w[0] = cols; P.pyr = s.pyr;
-  // both slots are being rewritten: whatever was matched against their old contents is stale
-  const int slots[2] = {slot_l, slot_r};
-  for (int sl : slots) slot_rewrite(s.slots[sl]);
-  ps.mcache.invalidate();
-  // (the temporal partner is forgotten BEFORE staging, as in spvo_sift_detect_pair: a call that fails from now on leaves none for the next call)
-  const int partner[2] = {slot_r, ps.temporal_partner(slot_l, slot_r, ps.last_slot_l >= 0 && s.slots[ps.last_slot_l].filled)};
-  ps.last_slot_l = -1;
-  HIP_TRY(c, hipStreamSynchronize(st));   // (the staging buffer and the mirrors are the previous call's until its work is done)
-  ps.stage(img_l, img_r, rows, cols, stride);
-  // a match of an earlier call may still read the slots where the L2 matcher runs
-  if (s.match_pending) HIP_TRY(c, hipStreamWaitEvent(st, ps.ev_match, 0));
+  if ((rc = pc.load(img_l, img_r, rows, cols, stride))) return rc;
   const int waves = std::min(std::max(tuning("sift_pair_waves_per_cu", 4), 1), 64) * c->num_cus;   // (diagnostic: the grid NOTES.md measures the default against)
   for (int k = 0; k < 2; ++k) {   // left chain, then the right one: the resident image, the detector's list and the base level are reused in stream order
-    if (int rc = classic_detector_enqueue(c, opts, ps.h_img + k * px, rows, cols)) return rc;
-    if (int rc = sift_enqueue_pyramid(c, c->cls.im, rows, cols, P, false, false, true)) return rc;
-    const SiftSlot &t = s.slots[slots[k]];
+    if ((rc = classic_detector_enqueue(c, opts, pc.image(k), rows, cols))) return rc;
+    if ((rc = sift_enqueue_pyramid(c, c->cls.im, rows, cols, P, false, false, true))) return rc;
+    const SiftSlot &t = s.slots[pc.slots[k]];
     const SiftDetectorIO io{c->cls.xy,
                             c->cls.resp,
                             c->cls.counters,
@@ -673,26 +619,14 @@ int spvo_classic_sift_pair(spvo_ctx *c, const spvo_classic_opts *opts, const uin
     hipLaunchKernelGGL((sift_describe_given_kernel<0, SiftDetectorIO>), dim3(waves), dim3(64), 0, st, P, 0, io);
     HIP_TRY(c, hipGetLastError());
   }
-  HIP_TRY(c, hipEventRecord(ps.ev_feat, st));
-  if (int rc = sift_enqueue_prematch(c, slot_l, partner)) return rc;   // (a pair that turns out not to fit its slots: that result is dropped below)
-  HIP_TRY(c, wait_event(ps.ev_feat));   // the one wait of the call: the matches go on behind it
+  if ((rc = pc.submit())) return rc;
+  // (kept: this entry point answers a detector overflow with SPVO_ERR_CAPACITY, image by image as the counts are taken)
   for (int k = 0; k < 2; ++k) {
-    outs[k]->n = s.h_n[4 * k];
+    pc.count(k);
     if (s.h_n[4 * k + 1]) return fail(c, SPVO_ERR_CAPACITY, "spvo_classic_sift_pair: key buffer overflow in the %s image", k ? "right" : "left");
   }
-  if (out_l->n > cap || out_r->n > cap) return fail(c, SPVO_ERR_CAPACITY, "spvo_classic_sift_pair: %d / %d rows do not fit slots of %d (slot_capacity)", out_l->n, out_r->n, cap);
-  for (int k = 0; k < 2; ++k) {
-    SiftSlot &t = s.slots[slots[k]];
-    t.n = outs[k]->n; t.filled = true;
-    const int ncopy = std::min(t.n, outs[k]->cap);
-    if (ncopy > 0) {
-      std::memcpy(outs[k]->kp, s.h_src + (size_t)k * s.slot_cap, (size_t)ncopy * sizeof(SiftKey));
-      std::memcpy(outs[k]->desc, s.hm_desc + (size_t)k * s.slot_cap * 128, (size_t)ncopy * 128 * sizeof(float));
-    }
-  }
-  sift_record_prematch(c, slot_l, partner);
-  ps.last_slot_l = slot_l;
-  return SPVO_OK;
+  const PairMirror mirrors[2] = {sift_mirror(c, 0, true, sizeof(SiftKey)), sift_mirror(c, 1, true, sizeof(SiftKey))};
+  return pc.commit(mirrors);
 }
 
 // tests/sift_describe_ref.py.  Everything a record can be refused for is checked on the host before anything is touched; the kernel then

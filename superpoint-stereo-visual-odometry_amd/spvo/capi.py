@@ -639,30 +639,32 @@ class Context:
         -> (left, right): dicts of kp [m] (BRISK_KP_DTYPE records: the detector's, with the extractor's angle in degrees), desc [m, 64] uint8
         and n, the rows the slot holds; m = min(n, cap), cap = None: slot_capacity.  Strided views are accepted.
         On SPVO_ERR_CAPACITY the SpvoError carries the two counts as .n_l, .n_r (and .counts)."""
+        want = int(slot_capacity) if cap is None else int(cap)
+        return self._pair_call(self.lib.spvo_brisk_detect_pair, (), (int(threshold), int(octaves), slot_l, slot_r, int(slot_capacity)), img_l, img_r, BRISK_KP_DTYPE, (np.uint8, 64),
+                               BriskFeatures, want, resident=False)
+
+    def _pair_call(self, call, head, tail, img_l, img_r, kp_dtype, row_dtype, features, want, resident):
+        """The Python side of one stereo-pair call, whichever entry point it is: call(ctx, *head, left, right, rows, cols, stride, *tail,
+        out_l, out_r).  Both images as u8 rows of one shape and stride; per image a buffer of max(want, 1) records (kp_dtype) and as many
+        rows (row_dtype, e.g. (np.uint8, 64)) behind a `features` struct of cap = want; on failure an SpvoError that carries the two counts
+        as .n_l, .n_r and .counts.  resident: the call leaves the right image resident, which the *_describe(None, ...) methods and the
+        debug hooks look up as _resident_shape.  -> (left, right): dicts of kp [m], desc [m, ...] and n, m = min(n, want)."""
         l, r = _u8_rows(img_l), _u8_rows(img_r)
         if l.shape != r.shape or l.strides[0] != r.strides[0]:
             l, r = np.ascontiguousarray(l), np.ascontiguousarray(r)
             if l.shape != r.shape:
                 raise ValueError("the two images of a pair must have one shape")
-        want = int(slot_capacity) if cap is None else int(cap)
-        bufs, feats = [], []
-        for _ in range(2):
-            kp = np.zeros(max(want, 1), BRISK_KP_DTYPE)
-            desc = np.zeros((max(want, 1), 64), np.uint8)
-            bufs.append((kp, desc))
-            feats.append(BriskFeatures(0, kp.ctypes.data, desc.ctypes.data, want))
-        rc = self.lib.spvo_brisk_detect_pair(self.h, _ptr(l), _ptr(r), l.shape[0], l.shape[1], l.strides[0], int(threshold), int(octaves), slot_l, slot_r, int(slot_capacity),
-                                             C.byref(feats[0]), C.byref(feats[1]))
+        bufs = [(np.zeros(max(want, 1), np.dtype(kp_dtype)), np.zeros(max(want, 1), np.dtype(row_dtype))) for _ in range(2)]
+        feats = [features(0, kp.ctypes.data, desc.ctypes.data, want) for kp, desc in bufs]
+        rc = call(self.h, *head, _ptr(l), _ptr(r), l.shape[0], l.shape[1], l.strides[0], *tail, C.byref(feats[0]), C.byref(feats[1]))
         if rc:
             e = SpvoError(rc, self.lib.spvo_last_error(self.h).decode())
             e.n_l, e.n_r = feats[0].n, feats[1].n
             e.counts = (e.n_l, e.n_r)
             raise e
-        out = []
-        for (kp, desc), f in zip(bufs, feats):
-            m = min(f.n, max(want, 0))
-            out.append(dict(kp=kp[:m].copy(), desc=desc[:m].copy(), n=f.n))
-        return out[0], out[1]
+        if resident:
+            self._resident_shape = r.shape
+        return tuple(dict(kp=kp[:min(f.n, max(want, 0))].copy(), desc=desc[:min(f.n, max(want, 0))].copy(), n=f.n) for (kp, desc), f in zip(bufs, feats))
 
     def akaze_detect_pair(self, img_l, img_r, slot_l: int, slot_r: int, threshold: float = 0.001, slot_capacity: int = 8192, cap: Optional[int] = None):
         """One stereo pair through the AKAZE detector + descriptor into two binary feature slots of 61-byte rows (spvo_akaze_detect_pair).
@@ -670,58 +672,14 @@ class Context:
         and n, the rows the slot holds; m = min(n, cap), cap = None: slot_capacity.  Strided views are accepted.  Afterwards the right
         image and its scale space are resident (akaze_describe(None, ...), akaze_level).
         On SPVO_ERR_CAPACITY the SpvoError carries the two counts as .n_l, .n_r (and .counts)."""
-        l, r = _u8_rows(img_l), _u8_rows(img_r)
-        if l.shape != r.shape or l.strides[0] != r.strides[0]:
-            l, r = np.ascontiguousarray(l), np.ascontiguousarray(r)
-            if l.shape != r.shape:
-                raise ValueError("the two images of a pair must have one shape")
         want = int(slot_capacity) if cap is None else int(cap)
-        bufs, feats = [], []
-        for _ in range(2):
-            kp = np.zeros(max(want, 1), AKAZE_KP_DTYPE)
-            desc = np.zeros((max(want, 1), AKAZE_DESC_BYTES), np.uint8)
-            bufs.append((kp, desc))
-            feats.append(AkazeFeatures(0, kp.ctypes.data, desc.ctypes.data, want))
-        rc = self.lib.spvo_akaze_detect_pair(self.h, _ptr(l), _ptr(r), l.shape[0], l.shape[1], l.strides[0], float(threshold), slot_l, slot_r, int(slot_capacity),
-                                             C.byref(feats[0]), C.byref(feats[1]))
-        if rc:
-            e = SpvoError(rc, self.lib.spvo_last_error(self.h).decode())
-            e.n_l, e.n_r = feats[0].n, feats[1].n
-            e.counts = (e.n_l, e.n_r)
-            raise e
-        self._resident_shape = r.shape
-        out = []
-        for (kp, desc), f in zip(bufs, feats):
-            m = min(f.n, max(want, 0))
-            out.append(dict(kp=kp[:m].copy(), desc=desc[:m].copy(), n=f.n))
-        return out[0], out[1]
+        return self._pair_call(self.lib.spvo_akaze_detect_pair, (), (float(threshold), slot_l, slot_r, int(slot_capacity)), img_l, img_r, AKAZE_KP_DTYPE, (np.uint8, AKAZE_DESC_BYTES),
+                               AkazeFeatures, want, resident=True)
 
     def _octave_pair(self, call, kp_dtype, features, desc_bytes, img_l, img_r, params, slot_l, slot_r, slot_capacity, cap):
         """brisk_detect_pair's protocol around one of the three pair calls whose extractor is another algorithm's."""
-        l, r = _u8_rows(img_l), _u8_rows(img_r)
-        if l.shape != r.shape or l.strides[0] != r.strides[0]:
-            l, r = np.ascontiguousarray(l), np.ascontiguousarray(r)
-            if l.shape != r.shape:
-                raise ValueError("the two images of a pair must have one shape")
         want = int(slot_capacity) if cap is None else int(cap)
-        bufs, feats = [], []
-        for _ in range(2):
-            kp = np.zeros(max(want, 1), kp_dtype)
-            desc = np.zeros((max(want, 1), desc_bytes), np.uint8)
-            bufs.append((kp, desc))
-            feats.append(features(0, kp.ctypes.data, desc.ctypes.data, want))
-        rc = call(self.h, _ptr(l), _ptr(r), l.shape[0], l.shape[1], l.strides[0], *params, slot_l, slot_r, int(slot_capacity), C.byref(feats[0]), C.byref(feats[1]))
-        if rc:
-            e = SpvoError(rc, self.lib.spvo_last_error(self.h).decode())
-            e.n_l, e.n_r = feats[0].n, feats[1].n
-            e.counts = (e.n_l, e.n_r)
-            raise e
-        self._resident_shape = r.shape
-        out = []
-        for (kp, desc), f in zip(bufs, feats):
-            m = min(f.n, max(want, 0))
-            out.append(dict(kp=kp[:m].copy(), desc=desc[:m].copy(), n=f.n))
-        return out[0], out[1]
+        return self._pair_call(call, (), (*params, slot_l, slot_r, int(slot_capacity)), img_l, img_r, kp_dtype, (np.uint8, desc_bytes), features, want, resident=True)
 
     def brisk_orb_pair(self, img_l, img_r, slot_l: int, slot_r: int, threshold: int = 30, octaves: int = 3, slot_capacity: int = 8192, cap: Optional[int] = None):
         """One stereo pair through the BRISK detector and the ORB extractor at the keypoints' octaves into two binary feature slots of
@@ -816,28 +774,8 @@ class Context:
         """One stereo pair through the SIFT detector + descriptor into two SIFT slots (spvo_sift_detect_pair) -> (left, right): dicts like
         sift_detect's -- the host's copy of what the slots hold; cap: rows the host buffers take (None: slot_capacity, i.e. all).
         On SPVO_ERR_CAPACITY the SpvoError carries the two counts as .counts."""
-        l, r = _u8_rows(img_l), _u8_rows(img_r)
-        if l.shape != r.shape or l.strides[0] != r.strides[0]:
-            l, r = np.ascontiguousarray(l), np.ascontiguousarray(r)
-            if l.shape != r.shape:
-                raise ValueError("the two images of a pair must have one shape")
-        want = max(int(slot_capacity), 1) if cap is None else int(cap)
-        bufs, feats = [], []
-        for _ in range(2):
-            kp = np.zeros(max(want, 1), SIFT_KP_DTYPE)
-            desc = np.zeros((max(want, 1), 128), np.float32)
-            bufs.append((kp, desc))
-            feats.append(SiftFeatures(0, kp.ctypes.data, desc.ctypes.data, want))
-        rc = self.lib.spvo_sift_detect_pair(self.h, _ptr(l), _ptr(r), l.shape[0], l.shape[1], l.strides[0], slot_l, slot_r, int(slot_capacity), C.byref(feats[0]), C.byref(feats[1]))
-        if rc:
-            e = SpvoError(rc, self.lib.spvo_last_error(self.h).decode())
-            e.counts = (feats[0].n, feats[1].n)
-            raise e
-        out = []
-        for (kp, desc), f in zip(bufs, feats):
-            m = min(f.n, want)
-            out.append(dict(kp=kp[:m].copy(), desc=desc[:m].copy(), n=f.n))
-        return out[0], out[1]
+        want = max(int(slot_capacity), 1) if cap is None else int(cap)   # (at least 1: a slot_capacity the library refuses is refused as that, not as a bad buffer)
+        return self._pair_call(self.lib.spvo_sift_detect_pair, (), (slot_l, slot_r, int(slot_capacity)), img_l, img_r, SIFT_KP_DTYPE, (np.float32, 128), SiftFeatures, want, resident=False)
 
     def classic_sift_pair(self, img_l, img_r, slot_l: int, slot_r: int, kind="FAST", cap: Optional[int] = None, **opts):
         """One stereo pair through the Shi-Tomasi ("ShiTomasi") or FAST ("FAST") detector and the SIFT extractor into two SIFT slots
@@ -851,56 +789,13 @@ class Context:
             if not hasattr(o, k):
                 raise TypeError(k)
             setattr(o, k, v)
-        l, r = _u8_rows(img_l), _u8_rows(img_r)
-        if l.shape != r.shape or l.strides[0] != r.strides[0]:
-            l, r = np.ascontiguousarray(l), np.ascontiguousarray(r)
-            if l.shape != r.shape:
-                raise ValueError("the two images of a pair must have one shape")
-        want = max(int(o.slot_capacity), 1) if cap is None else int(cap)
-        bufs, feats = [], []
-        for _ in range(2):
-            kp = np.zeros(max(want, 1), SIFT_KP_DTYPE)
-            desc = np.zeros((max(want, 1), 128), np.float32)
-            bufs.append((kp, desc))
-            feats.append(SiftFeatures(0, kp.ctypes.data, desc.ctypes.data, want))
-        rc = self.lib.spvo_classic_sift_pair(self.h, C.byref(o), _ptr(l), _ptr(r), l.shape[0], l.shape[1], l.strides[0], slot_l, slot_r, C.byref(feats[0]), C.byref(feats[1]))
-        if rc:
-            e = SpvoError(rc, self.lib.spvo_last_error(self.h).decode())
-            e.counts = (feats[0].n, feats[1].n)
-            raise e
-        self._resident_shape = l.shape
-        out = []
-        for (kp, desc), f in zip(bufs, feats):
-            m = min(f.n, want)
-            out.append(dict(kp=kp[:m].copy(), desc=desc[:m].copy(), n=f.n))
-        return out[0], out[1]
+        want = max(int(o.slot_capacity), 1) if cap is None else int(cap)   # (at least 1: as sift_detect_pair)
+        return self._pair_call(self.lib.spvo_classic_sift_pair, (C.byref(o),), (slot_l, slot_r), img_l, img_r, SIFT_KP_DTYPE, (np.float32, 128), SiftFeatures, want, resident=True)
 
     def _sift_octave_pair(self, call, kp_dtype, features, img_l, img_r, params, slot_l, slot_r, slot_capacity, cap):
         """classic_sift_pair's protocol around one of the two pair calls whose detector reports an octave."""
-        l, r = _u8_rows(img_l), _u8_rows(img_r)
-        if l.shape != r.shape or l.strides[0] != r.strides[0]:
-            l, r = np.ascontiguousarray(l), np.ascontiguousarray(r)
-            if l.shape != r.shape:
-                raise ValueError("the two images of a pair must have one shape")
         want = int(slot_capacity) if cap is None else int(cap)
-        bufs, feats = [], []
-        for _ in range(2):
-            kp = np.zeros(max(want, 1), kp_dtype)
-            desc = np.zeros((max(want, 1), 128), np.float32)
-            bufs.append((kp, desc))
-            feats.append(features(0, kp.ctypes.data, desc.ctypes.data, want))
-        rc = call(self.h, _ptr(l), _ptr(r), l.shape[0], l.shape[1], l.strides[0], *params, slot_l, slot_r, int(slot_capacity), C.byref(feats[0]), C.byref(feats[1]))
-        if rc:
-            e = SpvoError(rc, self.lib.spvo_last_error(self.h).decode())
-            e.n_l, e.n_r = feats[0].n, feats[1].n
-            e.counts = (e.n_l, e.n_r)
-            raise e
-        self._resident_shape = r.shape
-        out = []
-        for (kp, desc), f in zip(bufs, feats):
-            m = min(f.n, max(want, 0))
-            out.append(dict(kp=kp[:m].copy(), desc=desc[:m].copy(), n=f.n))
-        return out[0], out[1]
+        return self._pair_call(call, (), (*params, slot_l, slot_r, int(slot_capacity)), img_l, img_r, kp_dtype, (np.float32, 128), features, want, resident=True)
 
     def brisk_sift_pair(self, img_l, img_r, slot_l: int, slot_r: int, threshold: int = 30, octaves: int = 3, slot_capacity: int = 8192, cap: Optional[int] = None):
         """One stereo pair through the BRISK detector and the SIFT extractor into two SIFT slots (spvo_brisk_sift_pair).  -> (left, right):
@@ -979,28 +874,11 @@ class Context:
             if not hasattr(o, k):
                 raise TypeError(k)
             setattr(o, k, v)
-        l, r = _u8_rows(img_l), _u8_rows(img_r)
-        if l.shape != r.shape or l.strides[0] != r.strides[0]:
-            l, r = np.ascontiguousarray(l), np.ascontiguousarray(r)
-            if l.shape != r.shape:
-                raise ValueError("the two images of a pair must have one shape")
         cap = max(int(o.slot_capacity), 1)
-        bufs, feats = [], []
-        for _ in range(2):
-            kp = np.zeros((cap, 5), np.float32)          # x, y, angle, response, octave (int32 bits)
-            desc = np.zeros((cap, 64 if o.kind in CLASSIC_BRISK_KINDS else 32), np.uint8)
-            bufs.append((kp, desc))
-            feats.append(ClassicFeatures(0, kp.ctypes.data, desc.ctypes.data, cap))
-        rc = self.lib.spvo_classic_detect(self.h, C.byref(o), _ptr(l), _ptr(r), l.shape[0], l.shape[1], l.strides[0], slot_l, slot_r, C.byref(feats[0]), C.byref(feats[1]))
-        if rc:
-            e = SpvoError(rc, self.lib.spvo_last_error(self.h).decode())
-            e.counts = (feats[0].n, feats[1].n)
-            raise e
-        out = []
-        for (kp, desc), f in zip(bufs, feats):
-            k = f.n
-            out.append(dict(xy=kp[:k, :2].copy(), angle=kp[:k, 2].copy(), response=kp[:k, 3].copy(), octave=kp[:k, 4].copy().view(np.int32), desc=desc[:k].copy()))
-        return out[0], out[1]
+        kp_rec = (np.float32, 5)                          # x, y, angle, response, octave (int32 bits)
+        pair = self._pair_call(self.lib.spvo_classic_detect, (C.byref(o),), (slot_l, slot_r), img_l, img_r, kp_rec, (np.uint8, 64 if o.kind in CLASSIC_BRISK_KINDS else 32), ClassicFeatures,
+                               cap, resident=False)       # (a call that succeeds fits its slots, so every row comes back)
+        return tuple(dict(xy=f["kp"][:, :2].copy(), angle=f["kp"][:, 2].copy(), response=f["kp"][:, 3].copy(), octave=f["kp"][:, 4].copy().view(np.int32), desc=f["desc"]) for f in pair)
 
     def classic_slot_rows(self, slot: int) -> int:
         n = C.c_int(0)
