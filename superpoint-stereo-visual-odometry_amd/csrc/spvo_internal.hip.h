@@ -2,10 +2,14 @@
 // records, error / profiling helpers and the functions one unit offers the others.  Not installed, not part of the C ABI
 // (include/spvo.h is); everything here has hidden visibility.
 //
-//   spvo_core.hip      context and submission-set (SubmitSet) life cycle, launch segments, engine files (plan loader, weight repacking), profiling entry points
-//   spvo_net_f32.hip   FP32 engines: direct + Winograd convolution launchers, the layer executor (run_ops)
+//   spvo_core.hip      context and submission-set (SubmitSet) life cycle, tuning switches, launch segments, profiling entry points
+//   engine_file.h      an engine file's bytes -> records, with every check that needs the file alone (plain C++: no HIP)
+//   spvo_plan.hip      the plan loader (spvo_load_weights) as a list of steps: records -> tensors and ops, storage classes, heads, activations,
+//                      the part of preparing a layer that every engine kind shares, placement; choose_variant, free_plan
+//   spvo_net_f32.hip   FP32 engines: what the loader prepares of a layer (Winograd choice, packers, the fused tail of FP32 / FP16 engines), direct +
+//                      Winograd convolution launchers, the layer executor (run_ops)
 //   spvo_net_f16.hip   FP16 engines                     spvo_net_s3.hip   FP32 engines in split (bf16x3) mode
-//   spvo_net_i8.hip    INT8 engines
+//   spvo_net_i8.hip    INT8 engines (each: a layer's preparation beside its launcher -- the tiles choose_variant offers are the launcher's cases)
 //   spvo_detect.hip    preprocess, heat map / NMS / sampling, the detector submissions, spvo_forward
 //   spvo_classic.hip   the classic front end: ORB, Shi-Tomasi, FAST, the ORB extractor (on given keypoints, at their octaves, as a device link), the
 //                      binary slots and spvo_classic_detect, preprocess without an engine
@@ -36,6 +40,7 @@
 
 #include "../../include/spvo.h"
 #include "spvo_types.hip.h"
+#include "engine_file.h"
 
 #pragma GCC visibility push(hidden)
 namespace spvo { struct BriskLongPair; struct BriskShortPair; }   // brisk.hip.h
@@ -66,9 +71,7 @@ struct Tensor {
   size_t per_image = 0;  // floats
 };
 
-enum { OP_CONV = 1, OP_MAXPOOL = 2, OP_L2NORM = 3, OP_DWCONV = 4 };
-enum { FLAG_RELU = 1, FLAG_POOL = 2, FLAG_BN = 4, FLAG_ADD = 8 };
-
+// (OP_*, FLAG_*: engine_file.h)
 struct Op {
   int type = 0, in = 0, out = 0, out_c_off = 0, in_c_off = 0, cin = 0, cout = 0, ks = 0, flags = 0;
   int ck = 0, n_chunks = 0, co_tiles = 0, wr = 0, wc = 0;
@@ -601,6 +604,17 @@ int dev_alloc(spvo_ctx *c, T **p, size_t count, bool zero = true) {
   return SPVO_OK;
 }
 
+// a device buffer of its own for `count` values of the host's, copied synchronously (the plan loader's sources are temporaries)
+template <typename T>
+int upload(spvo_ctx *c, T **p, const T *src, size_t count) {
+  const int rc = dev_alloc(c, p, count, false);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpy(*p, src, count * sizeof(T), hipMemcpyHostToDevice));
+  return SPVO_OK;
+}
+template <typename T>
+int upload(spvo_ctx *c, T **p, const std::vector<T> &v) { return upload(c, p, v.data(), v.size()); }
+
 // frees device buffers, where there is one, and forgets them
 template <typename T, typename... Rest>
 void dev_free(T *&p, Rest *&...rest) {
@@ -708,8 +722,29 @@ struct PostScope {
   ~PostScope() { c->post = c->stream; }
 };
 
+// The launcher of one instance `k` of the tiled convolution kernels (conv_mfma / conv_f16 / conv_bf16x3 / conv_i8 .hip.h; T: its tile).
+// Persistent grid: what the chip holds at once -- the instance's resident workgroups per CU, asked once per device -- and each workgroup
+// walks tiles with that stride.  Leaves the tiles and workgroups of the launch in the context (launch_op copies them to its op).
+template <class T, auto k, class Args>
+int launch_persistent_tiles(spvo_ctx *c, Args args, hipStream_t stream) {
+  static int per_cu[64] = {};   // resident workgroups per CU of this instance, per device
+  const int dev = c->cfg.device & 63;
+  if (!per_cu[dev]) {
+    HIP_TRY(c, hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
+    int n = 0;
+    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k, 256, T::LDS_BYTES));
+    per_cu[dev] = std::max(n, 1);
+  }
+  args.tiles_x = (args.W + T::TW - 1) / T::TW;
+  args.tiles_y = (args.H + T::TH - 1) / T::TH;
+  const int n_tiles = args.tiles_x * args.tiles_y * args.co_tiles * args.batch;
+  c->launch_tiles = n_tiles; c->launch_wgs = std::min(n_tiles, c->num_cus * per_cu[dev]);
+  hipLaunchKernelGGL(k, dim3(c->launch_wgs), dim3(256), T::LDS_BYTES, stream, args);
+  HIP_TRY(c, hipGetLastError());
+  return SPVO_OK;
+}
+
 // ---- spvo_core.hip
-void free_plan(spvo_ctx *c);
 // a submission set's life cycle: set_alloc creates what every set has from spvo_create on; set_release frees ALL a set holds and forgets it
 // (the one list of its members), through the three helpers for what is allocated lazily and re-allocated when it grows
 int set_alloc(spvo_ctx *c, int index);
@@ -717,7 +752,25 @@ void set_release(SubmitSet &s);
 void set_release_images(SubmitSet &s);     // h_img, d_img (ensure_host_sets)
 void set_release_match(SubmitSet &s);      // h_match_out and the cache entries that point into it (ensure_match)
 void set_release_segments(SubmitSet &s);   // the graphs of its launch segments (seg_free_all)
+// ---- spvo_plan.hip
+void free_plan(spvo_ctx *c);
+// a tiled layer's co_tiles and tile (wr, wc) -- it offers the tiles the launchers' `switch (key)` tables have a case for; returns the channels
+// per chunk of the FP32 direct kernel (the other kinds chunk by their own rule)
+int choose_variant(const spvo_ctx *c, Op &op, const Tensor &ti, bool split = false);
+int upload_stem(spvo_ctx *c, Op &op, const float *w, const float *b);   // d_w, d_b of a plain single-channel-input layer: OIHW weights and bias as they are
+// ops head_start .. + 2 are convPb `cin` -> 65 into output_det, convDb `cin` -> 256 (both 1x1, plain, on 1/8-size tensors) and its L2 norm into output_desc
+bool tail_is_plain(const spvo_ctx *c, int cin);
 // ---- spvo_net_*.hip
+// What the plan loader prepares of convolution `i` for its engine kind, beside the launcher that runs it, after the common part (spvo_plan.hip:
+// prepare_conv): the kind's refusals, chunking, tile variant, repacked weights.  `w`, `b`: OIHW weights and bias (a merged sibling's appended)
+int prepare_conv_f32(spvo_ctx *c, unsigned i, const float *w, const float *b);
+int prepare_conv_f16(spvo_ctx *c, unsigned i, const float *w, const float *b);
+int prepare_conv_s3(spvo_ctx *c, unsigned i, const float *w, const float *b);
+int prepare_conv_i8(spvo_ctx *c, unsigned i, const float *w, const float *b);
+int prepare_dwconv_i8(spvo_ctx *c, unsigned i, const float *w, const float *b);
+// the tail as one launch where it is the plain one (tail_is_plain + the kind's own terms): FP32 and FP16 / INT8 engines.  rp, rd: convPb's, convDb's records
+int fuse_tail_f32(spvo_ctx *c, const float *payload, const EngineOp &rp, const EngineOp &rd);
+int fuse_tail_i8(spvo_ctx *c, const float *payload, const EngineOp &rp, const EngineOp &rd);
 int launch_conv16(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t stream);
 int launch_conv_s3(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t stream);
 int launch_conv8(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t stream);

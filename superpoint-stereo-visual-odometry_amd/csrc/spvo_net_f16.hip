@@ -1,29 +1,37 @@
-// spvo_net_f16.hip -- FP16 engines (conv_f16.hip.h): kernel launchers.
+// spvo_net_f16.hip -- FP16 engines (conv_f16.hip.h): what the plan loader prepares of a layer, and the kernel launchers.
 #include "spvo_internal.hip.h"
 #include "conv_f16.hip.h"
 
 namespace spvo_int {
 
 // ---------------------------------------------------------------- FP16 engines
-template <int KS, int CKG, int WR, int WC, bool POOL, bool RELU, bool OUT_F32, int EPI = 0>
-int launch_conv16_instance(spvo_ctx *c, ConvArgs16 args, hipStream_t stream) {
-  using T = ConvTile16<KS, CKG, WR, WC>;
-  auto k = conv_f16_kernel<KS, CKG, WR, WC, POOL, RELU, OUT_F32, EPI>;
-  static int per_cu[64] = {};
-  const int dev = c->cfg.device & 63;
-  if (!per_cu[dev]) {
-    HIP_TRY(c, hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
-    int n = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k, 256, T::LDS_BYTES));
-    per_cu[dev] = std::max(n, 1);
+// what the plan loader prepares of a convolution (spvo_plan.hip); `ckg` groups of 8 channels per chunk: the second digit of launch_conv16's keys
+int prepare_conv_f16(spvo_ctx *c, unsigned i, const float *w, const float *b) {
+  Op &op = c->ops[i];
+  const Tensor &ti = c->tensors[op.in], &to = c->tensors[op.out];
+  const bool bn = op.flags & FLAG_BN, add = op.flags & FLAG_ADD, pool = op.flags & FLAG_POOL;
+  if (ti.f16 != (op.cin != 1)) return fail(c, SPVO_ERR_IO, "op %u: FP16 engine: a %d-channel input tensor stored as %s", i, op.cin, ti.f16 ? "fp16" : "fp32");
+  if (op.cin == 1) {   // fp32 plane in: fp32 arithmetic on fp16-rounded weights, fp16 values out
+    if (pool || add || (to.f16 && (op.out_c_off % 8))) return fail(c, SPVO_ERR_IO, "op %u: unsupported single-channel-input layer for FP16", i);
+    std::vector<float> wr((size_t)op.cout * op.ks * op.ks);
+    for (size_t q = 0; q < wr.size(); ++q) wr[q] = (float)(_Float16)w[q];
+    return upload_stem(c, op, wr.data(), b);
   }
-  args.tiles_x = (args.W + T::TW - 1) / T::TW;
-  args.tiles_y = (args.H + T::TH - 1) / T::TH;
-  const int n_tiles = args.tiles_x * args.tiles_y * args.co_tiles * args.batch;
-  c->launch_tiles = n_tiles; c->launch_wgs = std::min(n_tiles, c->num_cus * per_cu[dev]);
-  hipLaunchKernelGGL(k, dim3(c->launch_wgs), dim3(256), T::LDS_BYTES, stream, args);
-  HIP_TRY(c, hipGetLastError());
-  return SPVO_OK;
+  const int ckg = (op.ks == 3 || op.cin % 32) ? 2 : 4;   // 16 channels per chunk; 32 for 1x1 layers when they divide
+  if (op.cin % (8 * ckg) || op.in_c_off % 8) return fail(c, SPVO_ERR_IO, "op %u: cin %d / channel offset %d do not fit the FP16 chunking (%d)", i, op.cin, op.in_c_off, 8 * ckg);
+  if (to.f16 && ((op.cout % 8) || (op.out_c_off % 8))) return fail(c, SPVO_ERR_IO, "op %u: cout %d / channel offset %d are not multiples of 8", i, op.cout, op.out_c_off);
+  if ((bn || add) && !to.f16) return fail(c, SPVO_ERR_IO, "op %u: BatchNorm / residual epilogue with an fp32 output", i);
+  if (add && (!c->tensors[op.residual].f16 || c->tensors[op.residual].ch != op.cout)) return fail(c, SPVO_ERR_IO, "op %u: residual tensor is not a %d-channel fp16 tensor", i, op.cout);
+  if (!to.f16 && pool) return fail(c, SPVO_ERR_IO, "op %u: pooled fp32 output", i);
+  op.ck = 8 * ckg;
+  op.n_chunks = op.cin / op.ck;
+  choose_variant(c, op, ti);
+  return upload(c, &op.d_w16, pack_conv_weights_f16(w, b, op.cout, op.cin, op.ks, ckg));
+}
+
+template <int KS, int CKG, int WR, int WC, bool POOL, bool RELU, bool OUT_F32, int EPI = 0>
+int launch_conv16_instance(spvo_ctx *c, const ConvArgs16 &args, hipStream_t stream) {
+  return launch_persistent_tiles<ConvTile16<KS, CKG, WR, WC>, conv_f16_kernel<KS, CKG, WR, WC, POOL, RELU, OUT_F32, EPI>>(c, args, stream);
 }
 
 template <int KS, int CKG, int WR, int WC, bool POOL>

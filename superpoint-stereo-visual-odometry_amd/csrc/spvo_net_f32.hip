@@ -1,4 +1,5 @@
-// spvo_net_f32.hip -- FP32 engines: launchers of the direct (conv_mfma.hip.h) and Winograd (conv_wino2 / conv_wino4.hip.h) convolution kernels and the
+// spvo_net_f32.hip -- FP32 engines: what the plan loader prepares of a layer (Winograd choice, the three packers; the fused tail of FP32 and
+// FP16 engines), launchers of the direct (conv_mfma.hip.h) and Winograd (conv_wino2 / conv_wino4.hip.h) convolution kernels and the
 // layer executor that walks a plan (replaces the TensorRT enqueue at feature_detection_neural_network.cpp:169).
 #include "spvo_internal.hip.h"
 #include "conv_mfma.hip.h"
@@ -8,34 +9,83 @@
 
 namespace spvo_int {
 
-template <int KS, int CK, int WR, int WC, bool POOL, bool RELU, int EPI = 0, int MINW = 1, int TAG = 0>
-int launch_conv_instance(spvo_ctx *c, ConvArgs args, hipStream_t stream) {
-  using T = ConvTile<KS, CK, WR, WC>;
-  auto k = conv_mfma_kernel<KS, CK, WR, WC, POOL, RELU, MINW, 0, EPI, TAG>;
-  static int per_cu[64] = {};   // resident workgroups per CU of this instance, per device
-  const int dev = c->cfg.device & 63;
-  if (!per_cu[dev]) {
-    HIP_TRY(c, hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
-    int n = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k, 256, T::LDS_BYTES));
-    per_cu[dev] = std::max(n, 1);
+// ---------------------------------------------------------------- what the plan loader prepares of an FP32 engine's layers (spvo_plan.hip)
+int prepare_conv_f32(spvo_ctx *c, unsigned i, const float *w, const float *b) {
+  Op &op = c->ops[i];
+  const Tensor &ti = c->tensors[op.in];
+  const bool bn = op.flags & FLAG_BN, add = op.flags & FLAG_ADD, pool = op.flags & FLAG_POOL;
+  if (op.cin == 1) {
+    if (pool || add) return fail(c, SPVO_ERR_IO, "op %u: single-channel-input layers have no pooling / residual form", i);
+    return upload_stem(c, op, w, b);
   }
-  // persistent grid: what the chip holds at once; each workgroup walks tiles with that stride
-  const int n_tiles = args.tiles_x * args.tiles_y * args.co_tiles * args.batch;
-  const int grid = std::min(n_tiles, c->num_cus * per_cu[dev]);
-  c->launch_tiles = n_tiles; c->launch_wgs = grid;
-  hipLaunchKernelGGL(k, dim3(grid), dim3(256), T::LDS_BYTES, stream, args);
-  HIP_TRY(c, hipGetLastError());
-  return SPVO_OK;
+  op.ck = choose_variant(c, op, ti);
+  // Winograd for the plain 3x3 layers (no BatchNorm / residual epilogue; a pooled layer needs even sizes: the pooling window lies
+  // inside a Winograd tile).  Which form, by the number of workgroups the layer gives on this chip (`min_tiles`, default 3/4 of the
+  // CUs): F(4x4,3x3) (conv_wino4.hip.h: 36 multiplies per 4x4 outputs instead of F(2x2)'s 64) where the layer has that many
+  // 16 x 32 tiles; else F(2x2,3x3) (conv_wino2.hip.h) on 8 x 32 tiles of 64 output channels; else its narrow form (32 output
+  // channels per workgroup: conv4a / conv4b at 45x147 are 120 wide tiles on 256 CUs); else the direct kernel.
+  // Diagnostic switches (spvo_set_tuning): "winograd" = 0 direct kernels only, "wino4" = 0 F(2x2) only, "wino4_item" = 0 the F(4x4) item without counted operand waits, "wino_narrow" = 0,
+  // "winograd_min_tiles" / "wino4_min_tiles" the thresholds, "wino_dynamic" = 0 static tile assignment.
+  {
+    const bool wino_on = tuning("winograd", 1) != 0;
+    const long wtiles = (long)((ti.W + WinoTile::TW - 1) / WinoTile::TW) * ((ti.H + WinoTile::TH - 1) / WinoTile::TH) * op.co_tiles * c->cfg.max_batch;
+    const long min_tiles = tuning("winograd_min_tiles", 3 * c->num_cus / 4);
+    const bool eligible = wino_on && op.ks == 3 && !bn && !add && (op.cin % WinoTile::CK) == 0 && (!pool || ((ti.H % 2) == 0 && (ti.W % 2) == 0));
+    op.wino = eligible && wtiles >= min_tiles;
+    // (narrow form: a workgroup's chain of items is as long as the layer's K whatever the number of workgroups, so half a chip of them
+    // still beats the direct kernel -- conv4a / conv4b at 30 x 98 cells, the reference's 240 x 784 engines: 128 workgroups, 45 -> 30 us)
+    if (eligible && !op.wino && tuning("wino_narrow", 1) && (op.cout % 32) == 0 && 3 * wtiles >= min_tiles) op.wino = op.wino_narrow = true;
+  }
+  const bool dynamic_tiles = tuning("wino_dynamic", 1) != 0;
+  int rc;
+  if (op.wino && !op.wino_narrow && (op.cin % Wino4Tile::CK) == 0 && (((ti.H | ti.W) & 1) == 0 || !pool) && tuning("wino4", 1)) {
+    const long t4 = (long)((ti.W + Wino4Tile::TW - 1) / Wino4Tile::TW) * ((ti.H + Wino4Tile::TH - 1) / Wino4Tile::TH) * op.co_tiles * c->cfg.max_batch;
+    if (t4 >= tuning("wino4_min_tiles", 3 * c->num_cus / 4)) {
+      op.wino4 = true;
+      op.wino4_item = tuning("wino4_item", 1) != 0;   // 0: the item with the compiler's operand waits (conv_wino4.hip.h), for A/B runs
+      op.ck = Wino4Tile::CK;
+      op.n_chunks = op.cin / Wino4Tile::CK;
+      if ((rc = upload(c, &op.d_w, pack_conv_weights_wino4(w, b, op.cout, op.cin)))) return rc;
+      return dynamic_tiles ? dev_alloc(c, &op.d_sched, 16) : SPVO_OK;
+    }
+  }
+  if (op.wino) {
+    op.ck = WinoTile::CK;
+    op.n_chunks = op.cin / op.ck;
+    if (op.wino_narrow) op.co_tiles = op.cout / 32;
+    if ((rc = upload(c, &op.d_w, pack_conv_weights_wino2(w, b, op.cout, op.cin, op.wino_narrow ? 32 : CO_TILE)))) return rc;
+    return dynamic_tiles ? dev_alloc(c, &op.d_sched, 16) : SPVO_OK;
+  }
+  if (op.cin % op.ck) return fail(c, SPVO_ERR_IO, "op %u: cin %d is not a multiple of %d", i, op.cin, op.ck);
+  op.n_chunks = op.cin / op.ck;
+  // repack OIHW + bias -> [co_tile][chunk][(tap, ci) rows + bias row][64]
+  std::vector<float> bp((size_t)op.co_tiles * CO_TILE, 0.f);
+  for (int o = 0; o < op.cout; ++o) bp[o] = b[o];
+  if ((rc = upload(c, &op.d_w, pack_conv_weights(w, b, op.cout, op.cin, op.ks, op.ck)))) return rc;
+  return upload(c, &op.d_b, bp);
+}
+
+// FP32 and FP16 engines (the latter: the loader wave converts the C8 fp16 activations, the weights are the fp16-rounded ones): the tail
+// as one launch of heads_fused_kernel (heads.hip.h; launch_heads below).  (The two branches may read one tensor -- the VGG plan's merged
+// convPa + convDa output -- or two.)
+int fuse_tail_f32(spvo_ctx *c, const float *payload, const EngineOp &rp, const EngineOp &rd) {
+  const Op &pb = c->ops[c->head_start], &db = c->ops[c->head_start + 1];
+  const bool plain = tail_is_plain(c, HEADS_CIN) && !c->tensors[pb.in].nhwc && !c->tensors[db.in].nhwc && !pb.merged && !db.merged &&
+                     c->tensors[pb.in].f16 == c->fp16 && c->tensors[db.in].f16 == c->fp16 && (!c->fp16 || ((pb.in_c_off | db.in_c_off) % 8) == 0);
+  if (!plain) return SPVO_OK;
+  const int rc = upload(c, &c->d_heads_w, pack_heads_weights(payload + rp.w_off, payload + rp.b_off, pb.cout, payload + rd.w_off, payload + rd.b_off, c->fp16));
+  if (!rc) c->heads_fused = true;
+  return rc;
+}
+
+// ---------------------------------------------------------------- launchers
+template <int KS, int CK, int WR, int WC, bool POOL, bool RELU, int EPI = 0, int MINW = 1, int TAG = 0>
+int launch_conv_instance(spvo_ctx *c, const ConvArgs &args, hipStream_t stream) {
+  return launch_persistent_tiles<ConvTile<KS, CK, WR, WC>, conv_mfma_kernel<KS, CK, WR, WC, POOL, RELU, MINW, 0, EPI, TAG>>(c, args, stream);
 }
 
 template <int KS, int CK, int WR, int WC, bool POOL, int MINW = 1>
-int launch_conv_variant(spvo_ctx *c, const ConvArgs &a, int batch, bool relu, hipStream_t stream, bool dominant = false) {
-  using T = ConvTile<KS, CK, WR, WC>;
-  ConvArgs args = a;
-  args.tiles_x = (a.W + T::TW - 1) / T::TW;
-  args.tiles_y = (a.H + T::TH - 1) / T::TH;
-  args.batch = batch;
+int launch_conv_variant(spvo_ctx *c, const ConvArgs &args, bool relu, hipStream_t stream, bool dominant = false) {
   if constexpr (KS == 3) {
     if (dominant && relu) return launch_conv_instance<KS, CK, WR, WC, POOL, true, 0, MINW, 1>(c, args, stream);   // own kernel name
   }
@@ -45,12 +95,7 @@ int launch_conv_variant(spvo_ctx *c, const ConvArgs &a, int batch, bool relu, hi
 
 // MobileNet 1x1 layers: EPI 1 = ReLU, BatchNorm, ReLU (mbv1); EPI 2 = residual add, ReLU (mbv2)
 template <int WR, int WC, bool POOL>
-int launch_conv_epi(spvo_ctx *c, const ConvArgs &a, int batch, int epi, hipStream_t stream) {
-  using T = ConvTile<1, 16, WR, WC>;
-  ConvArgs args = a;
-  args.tiles_x = (a.W + T::TW - 1) / T::TW;
-  args.tiles_y = (a.H + T::TH - 1) / T::TH;
-  args.batch = batch;
+int launch_conv_epi(spvo_ctx *c, const ConvArgs &args, int epi, hipStream_t stream) {
   return epi == 1 ? launch_conv_instance<1, 16, WR, WC, POOL, true, 1>(c, args, stream)
                   : launch_conv_instance<1, 16, WR, WC, POOL, false, 2>(c, args, stream);
 }
@@ -184,26 +229,26 @@ int launch_conv(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t stre
     a.bn_scale = op.d_bn_scale; a.bn_shift = op.d_bn_shift;
     if (epi == 2) a.residual = ring_ptr(c, c->tensors[op.residual], img0);
     switch (key) {
-      case 11644: return launch_conv_epi<2, 2, false>(c, a, batch, epi, stream);
-      case 11624: return launch_conv_epi<1, 2, false>(c, a, batch, epi, stream);
-      case 11622: return launch_conv_epi<1, 1, false>(c, a, batch, epi, stream);
-      case 11645: return launch_conv_epi<2, 2, true>(c, a, batch, epi, stream);
-      case 11643: return launch_conv_epi<2, 1, true>(c, a, batch, epi, stream);
+      case 11644: return launch_conv_epi<2, 2, false>(c, a, epi, stream);
+      case 11624: return launch_conv_epi<1, 2, false>(c, a, epi, stream);
+      case 11622: return launch_conv_epi<1, 1, false>(c, a, epi, stream);
+      case 11645: return launch_conv_epi<2, 2, true>(c, a, epi, stream);
+      case 11643: return launch_conv_epi<2, 1, true>(c, a, epi, stream);
       default: return fail(c, SPVO_ERR_INVALID, "no conv kernel variant for key %d with epilogue %d", key, epi);
     }
   }
   switch (key) {   // third template argument of the launch helper = waves per SIMD the register budget allows
-    case 30844: return launch_conv_variant<3, 8, 2, 2, false, 1>(c, a, batch, relu, stream, op.dominant);
-    case 30842: return launch_conv_variant<3, 8, 2, 1, false, 2>(c, a, batch, relu, stream, op.dominant);
-    case 30824: return launch_conv_variant<3, 8, 1, 2, false, 2>(c, a, batch, relu, stream, op.dominant);
-    case 30822: return launch_conv_variant<3, 8, 1, 1, false, 4>(c, a, batch, relu, stream, op.dominant);
-    case 30845: return launch_conv_variant<3, 8, 2, 2, true, 1>(c, a, batch, relu, stream, op.dominant);
-    case 30843: return launch_conv_variant<3, 8, 2, 1, true, 2>(c, a, batch, relu, stream, op.dominant);
-    case 11644: return launch_conv_variant<1, 16, 2, 2, false>(c, a, batch, relu, stream);
-    case 11624: return launch_conv_variant<1, 16, 1, 2, false>(c, a, batch, relu, stream);
-    case 11622: return launch_conv_variant<1, 16, 1, 1, false>(c, a, batch, relu, stream);
-    case 11645: return launch_conv_variant<1, 16, 2, 2, true>(c, a, batch, relu, stream);
-    case 11643: return launch_conv_variant<1, 16, 2, 1, true>(c, a, batch, relu, stream);
+    case 30844: return launch_conv_variant<3, 8, 2, 2, false, 1>(c, a, relu, stream, op.dominant);
+    case 30842: return launch_conv_variant<3, 8, 2, 1, false, 2>(c, a, relu, stream, op.dominant);
+    case 30824: return launch_conv_variant<3, 8, 1, 2, false, 2>(c, a, relu, stream, op.dominant);
+    case 30822: return launch_conv_variant<3, 8, 1, 1, false, 4>(c, a, relu, stream, op.dominant);
+    case 30845: return launch_conv_variant<3, 8, 2, 2, true, 1>(c, a, relu, stream, op.dominant);
+    case 30843: return launch_conv_variant<3, 8, 2, 1, true, 2>(c, a, relu, stream, op.dominant);
+    case 11644: return launch_conv_variant<1, 16, 2, 2, false>(c, a, relu, stream);
+    case 11624: return launch_conv_variant<1, 16, 1, 2, false>(c, a, relu, stream);
+    case 11622: return launch_conv_variant<1, 16, 1, 1, false>(c, a, relu, stream);
+    case 11645: return launch_conv_variant<1, 16, 2, 2, true>(c, a, relu, stream);
+    case 11643: return launch_conv_variant<1, 16, 2, 1, true>(c, a, relu, stream);
     default: return fail(c, SPVO_ERR_INVALID, "no conv kernel variant for key %d", key);
   }
 }

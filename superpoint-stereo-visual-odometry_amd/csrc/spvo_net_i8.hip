@@ -1,4 +1,4 @@
-// spvo_net_i8.hip -- INT8 engines (conv_i8.hip.h): kernel launchers.
+// spvo_net_i8.hip -- INT8 engines (conv_i8.hip.h): what the plan loader prepares of a layer and of the tail, the fusion plan, and the kernel launchers.
 #include "spvo_internal.hip.h"
 #include "conv_i8.hip.h"
 #include "conv_i8_fused.hip.h"
@@ -7,25 +7,89 @@
 namespace spvo_int {
 
 // ---------------------------------------------------------------- INT8 engines
-template <int KS, int CKG, int WR, int WC, bool POOL, bool RELU, bool OUT_F32, int EPI = 0>
-int launch_conv8_instance(spvo_ctx *c, ConvArgs8 args, hipStream_t stream) {
-  using T = ConvTile8<KS, CKG, WR, WC>;
-  auto k = conv_i8_kernel<KS, CKG, WR, WC, POOL, RELU, OUT_F32, EPI>;
-  static int per_cu[64] = {};
-  const int dev = c->cfg.device & 63;
-  if (!per_cu[dev]) {
-    HIP_TRY(c, hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
-    int n = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k, 256, T::LDS_BYTES));
-    per_cu[dev] = std::max(n, 1);
+// what the plan loader prepares of a depthwise 3x3 convolution (spvo_plan.hip)
+int prepare_dwconv_i8(spvo_ctx *c, unsigned i, const float *w, const float *b) {
+  Op &op = c->ops[i];
+  const Tensor &ti = c->tensors[op.in], &to = c->tensors[op.out];
+  if (!ti.i8 || !to.i8) return fail(c, SPVO_ERR_IO, "op %u: depthwise convolution of an INT8 engine needs channel counts that are multiples of 16", i);
+  std::vector<int8_t> wq;
+  std::vector<float> ws;
+  quantize_conv_weights(w, op.cout, 9, wq, ws);
+  const std::vector<int> wq32(wq.begin(), wq.end());
+  // r = fma(f32(acc), qm, bias) with 1 / s_out folded into both constants (oracle/net_int8.py: FOLDING): the kernels' final multiply is by 1
+  std::vector<float> qm(op.cout), bq(op.cout);
+  const float inv_dw = 1.f / to.scale;
+  for (int o = 0; o < op.cout; ++o) { qm[o] = ws[o] * ti.scale; qm[o] = qm[o] * inv_dw; bq[o] = b[o] * inv_dw; }
+  op.inv_s_out = 1.f;
+  int rc = upload(c, &op.d_wq32, wq32);
+  if (rc || (rc = upload(c, &op.d_wsel, pack_dw_wsel(wq.data(), op.cout))) || (rc = upload(c, &op.d_qm, qm))) return rc;
+  return upload(c, &op.d_b, bq);
+}
+
+// ... of a convolution; `ckg` groups of 16 channels per chunk: the second digit of launch_conv8's keys
+int prepare_conv_i8(spvo_ctx *c, unsigned i, const float *w, const float *b) {
+  Op &op = c->ops[i];
+  const Tensor &ti = c->tensors[op.in], &to = c->tensors[op.out];
+  const bool bn = op.flags & FLAG_BN, add = op.flags & FLAG_ADD, pool = op.flags & FLAG_POOL;
+  if (ti.i8 != (op.cin != 1)) return fail(c, SPVO_ERR_IO, "op %u: INT8 engine: a %d-channel input tensor stored as %s", i, op.cin, ti.i8 ? "int8" : "fp32");
+  // FOLDING (oracle/net_int8.py): quantised output, no residual, and an affine to fold into (the accumulator's, or a BatchNorm --
+  // folded where its constants are built, spvo_plan.hip): the kernels then multiply by 1 at the end
+  const bool fold = to.i8 && !add && (op.cin > 1 || bn);
+  const float inv_fold = to.i8 ? 1.f / to.scale : 0.f;
+  op.inv_s_out = fold ? 1.f : inv_fold;
+  if (op.cin == 1) {   // fp32 stem
+    if (pool || add || (to.i8 && ((op.out_c_off % 16) || (op.cout % 16)))) return fail(c, SPVO_ERR_IO, "op %u: unsupported single-channel-input layer for INT8", i);
+    return upload_stem(c, op, w, b);
   }
-  args.tiles_x = (args.W + T::TW - 1) / T::TW;
-  args.tiles_y = (args.H + T::TH - 1) / T::TH;
-  const int n_tiles = args.tiles_x * args.tiles_y * args.co_tiles * args.batch;
-  c->launch_tiles = n_tiles; c->launch_wgs = std::min(n_tiles, c->num_cus * per_cu[dev]);
-  hipLaunchKernelGGL(k, dim3(c->launch_wgs), dim3(256), T::LDS_BYTES, stream, args);
-  HIP_TRY(c, hipGetLastError());
+  const int ckg = (op.ks == 3 || op.cin % 64) ? 2 : 4;   // 32 channels per chunk; 64 for 1x1 layers when they divide
+  if (op.cin % (16 * ckg) || op.in_c_off % 16) return fail(c, SPVO_ERR_IO, "op %u: cin %d / channel offset %d do not fit the INT8 chunking (%d)", i, op.cin, op.in_c_off, 16 * ckg);
+  if (to.i8 && ((op.cout % 16) || (op.out_c_off % 16))) return fail(c, SPVO_ERR_IO, "op %u: cout %d / channel offset %d are not multiples of 16", i, op.cout, op.out_c_off);
+  if (!to.i8 && (pool || bn || add)) return fail(c, SPVO_ERR_IO, "op %u: pooled / BatchNorm / residual layer with an fp32 output", i);
+  if (add) {
+    const Tensor &tr = c->tensors[op.residual];
+    if (!tr.i8 || tr.ch != op.cout) return fail(c, SPVO_ERR_IO, "op %u: residual tensor is not a %d-channel int8 tensor", i, op.cout);
+    op.s_res = tr.scale;
+  }
+  op.ck = 16 * ckg;
+  op.n_chunks = op.cin / op.ck;
+  choose_variant(c, op, ti);
+  std::vector<int8_t> wq;
+  std::vector<float> ws;
+  quantize_conv_weights(w, op.cout, op.cin * op.ks * op.ks, wq, ws);
+  std::vector<float> qm((size_t)op.co_tiles * CO_TILE, 0.f), bp((size_t)op.co_tiles * CO_TILE, 0.f);
+  for (int o = 0; o < op.cout; ++o) {
+    qm[o] = ws[o] * ti.scale; bp[o] = b[o];
+    if (fold && !bn) { qm[o] = qm[o] * inv_fold; bp[o] = bp[o] * inv_fold; }   // (with a BatchNorm the BatchNorm's constants carry the factor)
+  }
+  int rc = upload(c, &op.d_w8, pack_conv_weights_i8(wq.data(), op.cout, op.cin, op.ks, ckg));
+  if (rc || (rc = upload(c, &op.d_qm, qm))) return rc;
+  return upload(c, &op.d_b, bp);
+}
+
+// The tail as ONE launch of heads_i8_kernel (heads_i8.hip.h; launch_heads8 below) -- int8 C16 activations of both branches in, fp32 detector
+// planes, un-normalised and normalised descriptors out: oracle/net_int8.py's arithmetic for a layer with an fp32 output
+int fuse_tail_i8(spvo_ctx *c, const float *payload, const EngineOp &rp, const EngineOp &rd) {
+  const Op &pb = c->ops[c->head_start], &db = c->ops[c->head_start + 1];
+  const bool plain = tail_is_plain(c, HEADS8_CIN) && c->tensors[pb.in].i8 && c->tensors[db.in].i8 && !c->tensors[pb.out].i8 && !c->tensors[db.out].i8 &&
+                     ((pb.in_c_off | db.in_c_off) % 16) == 0;
+  if (!plain) return SPVO_OK;
+  std::vector<int8_t> wq_p, wq_d;
+  std::vector<float> ws_p, ws_d;
+  quantize_conv_weights(payload + rp.w_off, pb.cout, pb.cin, wq_p, ws_p);
+  quantize_conv_weights(payload + rd.w_off, db.cout, db.cin, wq_d, ws_d);
+  std::vector<float> qm((size_t)HEADS8_UNITS * 16, 0.f), bp((size_t)HEADS8_UNITS * 16, 0.f);
+  const float *b_p = payload + rp.b_off, *b_d = payload + rd.b_off;
+  for (int o = 0; o < pb.cout; ++o) { qm[o] = ws_p[o] * c->tensors[pb.in].scale; bp[o] = b_p[o]; }
+  for (int o = 0; o < db.cout; ++o) { qm[16 * HEADS8_DET_UNITS + o] = ws_d[o] * c->tensors[db.in].scale; bp[16 * HEADS8_DET_UNITS + o] = b_d[o]; }
+  int rc = upload(c, &c->d_heads_w8, pack_heads_weights_i8(wq_p.data(), pb.cout, wq_d.data()));
+  if (rc || (rc = upload(c, &c->d_heads_qm, qm)) || (rc = upload(c, &c->d_heads_b, bp))) return rc;
+  c->heads_fused = true;
   return SPVO_OK;
+}
+
+template <int KS, int CKG, int WR, int WC, bool POOL, bool RELU, bool OUT_F32, int EPI = 0>
+int launch_conv8_instance(spvo_ctx *c, const ConvArgs8 &args, hipStream_t stream) {
+  return launch_persistent_tiles<ConvTile8<KS, CKG, WR, WC>, conv_i8_kernel<KS, CKG, WR, WC, POOL, RELU, OUT_F32, EPI>>(c, args, stream);
 }
 
 template <int KS, int CKG, int WR, int WC, bool POOL>

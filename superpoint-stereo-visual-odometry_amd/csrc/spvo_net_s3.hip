@@ -1,29 +1,35 @@
-// spvo_net_s3.hip -- FP32 engines in split mode (conv_bf16x3.hip.h): kernel launchers.
+// spvo_net_s3.hip -- FP32 engines in split mode (conv_bf16x3.hip.h): what the plan loader prepares of a layer, and the kernel launchers.
 #include "spvo_internal.hip.h"
 #include "conv_bf16x3.hip.h"
 
 namespace spvo_int {
 
 // ---------------------------------------------------------------- FP32 engines in split mode (bf16x3)
-template <int KS, int CKG, int WR, int WC, bool POOL, bool RELU, bool OUT_F32>
-int launch_conv_s3_instance(spvo_ctx *c, ConvArgsS3 args, hipStream_t stream) {
-  using T = ConvTileS3<KS, CKG, WR, WC>;
-  auto k = conv_s3_kernel<KS, CKG, WR, WC, POOL, RELU, OUT_F32>;
-  static int per_cu[64] = {};
-  const int dev = c->cfg.device & 63;
-  if (!per_cu[dev]) {
-    HIP_TRY(c, hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
-    int n = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k, 256, T::LDS_BYTES));
-    per_cu[dev] = std::max(n, 1);
+// what the plan loader prepares of a convolution (spvo_plan.hip); `ckg` groups of 8 channels per chunk: 1 for the 3x3 instances launch_conv_s3
+// has, 2 for the 1x1 ones
+int prepare_conv_s3(spvo_ctx *c, unsigned i, const float *w, const float *b) {
+  Op &op = c->ops[i];
+  const Tensor &ti = c->tensors[op.in], &to = c->tensors[op.out];
+  const bool bn = op.flags & FLAG_BN, add = op.flags & FLAG_ADD, pool = op.flags & FLAG_POOL;
+  if (bn || add) return fail(c, SPVO_ERR_IO, "op %u: split-fp32 mode has no BatchNorm / residual epilogue", i);
+  if (ti.s3 != (op.cin != 1)) return fail(c, SPVO_ERR_IO, "op %u: split-fp32 mode: unexpected storage of the input tensor", i);
+  if (to.s3 && ((op.cout % 8) || (op.out_c_off % 8))) return fail(c, SPVO_ERR_IO, "op %u: cout %d / channel offset %d are not multiples of 8", i, op.cout, op.out_c_off);
+  if (!to.s3 && pool) return fail(c, SPVO_ERR_IO, "op %u: pooled fp32 output", i);
+  if (op.cin == 1) {
+    if (pool || !to.s3) return fail(c, SPVO_ERR_IO, "op %u: unsupported single-channel-input layer for split-fp32 mode", i);
+    return upload_stem(c, op, w, b);
   }
-  args.tiles_x = (args.W + T::TW - 1) / T::TW;
-  args.tiles_y = (args.H + T::TH - 1) / T::TH;
-  const int n_tiles = args.tiles_x * args.tiles_y * args.co_tiles * args.batch;
-  c->launch_tiles = n_tiles; c->launch_wgs = std::min(n_tiles, c->num_cus * per_cu[dev]);
-  hipLaunchKernelGGL(k, dim3(c->launch_wgs), dim3(256), T::LDS_BYTES, stream, args);
-  HIP_TRY(c, hipGetLastError());
-  return SPVO_OK;
+  const int ckg = op.ks == 3 ? 1 : 2;
+  if (op.cin % (8 * ckg) || op.in_c_off % 8) return fail(c, SPVO_ERR_IO, "op %u: cin %d / channel offset %d do not fit the split-fp32 chunking (%d)", i, op.cin, op.in_c_off, 8 * ckg);
+  op.ck = 8 * ckg;
+  op.n_chunks = op.cin / op.ck;
+  choose_variant(c, op, ti, true);
+  return upload(c, &op.d_ws3, pack_conv_weights_s3(w, b, op.cout, op.cin, op.ks, ckg));
+}
+
+template <int KS, int CKG, int WR, int WC, bool POOL, bool RELU, bool OUT_F32>
+int launch_conv_s3_instance(spvo_ctx *c, const ConvArgsS3 &args, hipStream_t stream) {
+  return launch_persistent_tiles<ConvTileS3<KS, CKG, WR, WC>, conv_s3_kernel<KS, CKG, WR, WC, POOL, RELU, OUT_F32>>(c, args, stream);
 }
 
 template <int KS, int CKG, int WR, int WC, bool POOL>
