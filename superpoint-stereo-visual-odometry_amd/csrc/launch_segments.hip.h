@@ -92,11 +92,11 @@ inline void launch_kernel(void (*k)(KArgs...), dim3 grid, dim3 block, size_t lds
   (void)hipLaunchKernel((const void *)k, grid, block, params, lds, stream);
 }
 // stream operations that are not kernel launches close an open segment first (defined before the macros below rename the calls)
-template <typename... A> inline hipError_t guarded_memset_async(A... a) { rec_poison(); return hipMemsetAsync(a...); }
-template <typename... A> inline hipError_t guarded_memcpy_async(A... a) { rec_poison(); return hipMemcpyAsync(a...); }
-template <typename... A> inline hipError_t guarded_event_record(A... a) { rec_poison(); return hipEventRecord(a...); }
-template <typename... A> inline hipError_t guarded_stream_wait_event(A... a) { rec_poison(); return hipStreamWaitEvent(a...); }
-template <typename... A> inline hipError_t guarded_stream_synchronize(A... a) { rec_poison(); return hipStreamSynchronize(a...); }
+template <typename... A> inline hipError_t guarded_memset_async(A &&...a) { rec_poison(); return hipMemsetAsync(std::forward<A>(a)...); }
+template <typename... A> inline hipError_t guarded_memcpy_async(A &&...a) { rec_poison(); return hipMemcpyAsync(std::forward<A>(a)...); }
+template <typename... A> inline hipError_t guarded_event_record(A &&...a) { rec_poison(); return hipEventRecord(std::forward<A>(a)...); }
+template <typename... A> inline hipError_t guarded_stream_wait_event(A &&...a) { rec_poison(); return hipStreamWaitEvent(std::forward<A>(a)...); }
+template <typename... A> inline hipError_t guarded_stream_synchronize(A &&...a) { rec_poison(); return hipStreamSynchronize(std::forward<A>(a)...); }
 }  // namespace spvo_int
 #undef hipLaunchKernelGGL
 #define hipLaunchKernelGGL(kernel, grid, block, lds, stream, ...) ::spvo_int::launch_kernel(kernel, grid, block, lds, stream, ##__VA_ARGS__)

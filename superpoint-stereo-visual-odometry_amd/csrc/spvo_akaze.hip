@@ -102,10 +102,8 @@ int ak_ensure(spvo_ctx *c, int rows, int cols) {
   auto &d = c->akaze;
   hipStream_t st = c->stream2;
   d.valid = false;
-  if (!d.stat) {
-    if (int rc = dev_alloc(c, &d.stat, AKAZE_STAT_INTS)) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
-  }
+  if (!d.stat)
+    if (int rc = grow(c, wait_for_nothing(), {zeroed(d.stat, AKAZE_STAT_INTS)})) return rc;
   if (d.rows == rows && d.cols == cols) return SPVO_OK;
   d.rows = d.cols = 0;
   const AkTables T = make_tables(rows, cols);
@@ -128,16 +126,10 @@ int ak_ensure(spvo_ctx *c, int rows, int cols) {
       return fail(c, SPVO_ERR_STATE, "AKAZE detector: the area taps of octave %d (%d x %d from %d x %d) failed their own checks", o, T.oh[o], T.ow[o], T.oh[o - 1], T.ow[o - 1]);
   const size_t scratch = 2 * align64((size_t)rows * cols);
   if (planes > d.plane_cap || scratch > d.scratch_cap || tabs > d.tab_cap || cand > d.cand_cap) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    dev_free(d.planes, d.scratch, d.tabs, d.keys, d.rank, d.rec);
     const size_t np = std::max(planes, d.plane_cap), ns = std::max(scratch, d.scratch_cap), nt = std::max(std::max<size_t>(tabs, 1), d.tab_cap);
     const int nc = (int)std::min<long long>(std::max<long long>(std::max<long long>(cand, 1), d.cand_cap), 0x7FFFFFFF);
     d.plane_cap = d.scratch_cap = d.tab_cap = 0; d.cand_cap = 0;   // a failed allocation below leaves a context that spvo_destroy and a later call can still handle
-    int rc;
-    if ((rc = dev_alloc(c, &d.planes, np, false)) || (rc = dev_alloc(c, &d.scratch, ns, false)) || (rc = dev_alloc(c, &d.tabs, nt, false)) || (rc = dev_alloc(c, &d.keys, nc, false)) ||
-        (rc = dev_alloc(c, &d.rank, nc)) || (rc = dev_alloc(c, &d.rec, nc, false)))
-      return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (int rc = grow(c, wait_for(st), {plain(d.planes, np), plain(d.scratch, ns), plain(d.tabs, nt), plain(d.keys, nc), zeroed(d.rank, nc), plain(d.rec, nc)})) return rc;
     d.plane_cap = np; d.scratch_cap = ns; d.tab_cap = nt; d.cand_cap = nc;
   }
   HIP_TRY(c, hipMemcpyAsync(d.tabs, d.h_tabs.data(), d.h_tabs.size() * sizeof(BriskAreaTap), hipMemcpyHostToDevice, st));
@@ -290,12 +282,9 @@ int ak_check(spvo_ctx *c, const char *who, int rows, int cols, float threshold) 
 int ak_kp_ensure(spvo_ctx *c, int n) {
   auto &d = c->akaze;
   if (n <= d.kp_cap) return SPVO_OK;
-  HIP_TRY(c, hipStreamSynchronize(c->stream2));
-  dev_free(d.d_kp, d.d_angle, d.d_desc);
   d.kp_cap = 0;
   const int cap = std::max(n, 1024);
-  int rc;
-  if ((rc = dev_alloc(c, &d.d_kp, (size_t)cap, false)) || (rc = dev_alloc(c, &d.d_angle, (size_t)cap, false)) || (rc = dev_alloc(c, &d.d_desc, (size_t)cap * AKAZE_MLDB_BYTES, false))) return rc;
+  if (int rc = grow(c, wait_for(c->stream2), {plain(d.d_kp, (size_t)cap), plain(d.d_angle, (size_t)cap), plain(d.d_desc, (size_t)cap * AKAZE_MLDB_BYTES)})) return rc;
   d.kp_cap = cap;
   return SPVO_OK;
 }
@@ -303,19 +292,12 @@ int ak_kp_ensure(spvo_ctx *c, int n) {
 // the buffers of the device suppression for lists of n candidates
 int ak_sup_ensure(spvo_ctx *c, int n) {
   auto &d = c->akaze;
-  if (!d.sup_cnt) {
-    if (int rc = dev_alloc(c, &d.sup_cnt, AKAZE_SUP_INTS)) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
-  }
+  if (!d.sup_cnt)
+    if (int rc = grow(c, wait_for_nothing(), {zeroed(d.sup_cnt, AKAZE_SUP_INTS)})) return rc;
   if (n <= d.sup_cap) return SPVO_OK;
-  HIP_TRY(c, hipStreamSynchronize(c->stream2));
-  dev_free(d.sup_list, d.sup_idx, d.sup_keep, d.sup_src, d.sup_kp);
   d.sup_cap = 0;
   const size_t cap = (size_t)std::max(n, 1024);
-  int rc;
-  if ((rc = dev_alloc(c, &d.sup_list, cap, false)) || (rc = dev_alloc(c, &d.sup_idx, cap, false)) || (rc = dev_alloc(c, &d.sup_keep, cap, false)) || (rc = dev_alloc(c, &d.sup_src, cap, false)) ||
-      (rc = dev_alloc(c, &d.sup_kp, cap, false)))
-    return rc;
+  if (int rc = grow(c, wait_for(c->stream2), {plain(d.sup_list, cap), plain(d.sup_idx, cap), plain(d.sup_keep, cap), plain(d.sup_src, cap), plain(d.sup_kp, cap)})) return rc;
   d.sup_cap = (int)cap;
   return SPVO_OK;
 }
@@ -326,16 +308,11 @@ int ak_brisk_ensure(spvo_ctx *c, int rows, int cols, int cap) {
   auto &d = c->akaze;
   if (int rc = brisk_chain_ensure(c, rows, cols, cap)) return rc;
   const int n = std::max(d.sup_cap, cap);
-  if (!d.brk_cnt) {
-    if (int rc = dev_alloc(c, &d.brk_cnt, 4)) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
-  }
+  if (!d.brk_cnt)
+    if (int rc = grow(c, wait_for_nothing(), {zeroed(d.brk_cnt, 4)})) return rc;
   if (n <= d.brk_cap) return SPVO_OK;
-  HIP_TRY(c, hipStreamSynchronize(c->stream2));
-  dev_free(d.brk_rec, d.brk_crec, d.brk_keep);
   d.brk_cap = 0;
-  int rc;
-  if ((rc = dev_alloc(c, &d.brk_rec, (size_t)n, false)) || (rc = dev_alloc(c, &d.brk_crec, (size_t)n, false)) || (rc = dev_alloc(c, &d.brk_keep, (size_t)n, false))) return rc;
+  if (int rc = grow(c, wait_for(c->stream2), {plain(d.brk_rec, (size_t)n), plain(d.brk_crec, (size_t)n), plain(d.brk_keep, (size_t)n)})) return rc;
   d.brk_cap = n;
   return SPVO_OK;
 }
@@ -386,12 +363,6 @@ void ak_mark_right_resident(spvo_ctx *c, const int *h_n) {
   ak_mark_resident(c, stat);
 }
 }  // namespace
-
-void spvo_int::akaze_release(spvo_ctx *c) {
-  auto &d = c->akaze;
-  dev_free(d.planes, d.scratch, d.tabs, d.keys, d.rank, d.rec, d.stat, d.d_kp, d.d_angle, d.d_desc, d.sup_list, d.sup_idx, d.sup_keep, d.sup_src, d.sup_cnt, d.sup_kp, d.brk_rec, d.brk_crec, d.brk_keep, d.brk_cnt);
-  d.plane_cap = d.scratch_cap = d.tab_cap = 0; d.cand_cap = d.kp_cap = d.sup_cap = d.brk_cap = 0; d.rows = d.cols = 0; d.valid = false;
-}
 
 extern "C" {
 
@@ -535,8 +506,8 @@ int spvo_akaze_suppress_debug(spvo_ctx *c, int rows, int cols, const spvo_akaze_
   AkazeLevels lv{};
   lv.n = T.n;
   for (int i = 0; i < T.n; ++i) { lv.l[i].octave = T.octave[i]; lv.l[i].esigma = T.esigma[i]; }
-  AkazeCand *rec = nullptr;
-  if (int rc = dev_alloc(c, &rec, (size_t)n, false)) return rc;
+  DevBuf<AkazeCand> rec;   // (the hook's own list: freed when the call returns, behind its wait)
+  if (int rc = grow(c, wait_for_nothing(), {plain(rec, (size_t)n)})) return rc;
   int cnt[AKAZE_SUP_INTS] = {0, 0, n, 0};
   std::vector<int> src((size_t)n);
   hipError_t e = hipMemcpyAsync(rec, h.data(), (size_t)n * sizeof(AkazeCand), hipMemcpyHostToDevice, st);
@@ -548,7 +519,6 @@ int spvo_akaze_suppress_debug(spvo_ctx *c, int rows, int cols, const spvo_akaze_
   if (e == hipSuccess) e = hipMemcpyAsync(cnt, d.sup_cnt, sizeof cnt, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipMemcpyAsync(src.data(), d.sup_src, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st);
   const hipError_t e2 = hipStreamSynchronize(st);
-  dev_free(rec);
   HIP_TRY(c, e);
   HIP_TRY(c, e2);
   const int m = std::min(std::max(cnt[AKAZE_SUP_KEPT], 0), n);
@@ -602,8 +572,8 @@ int akaze_pair(spvo_ctx *c, const char *who, AkExtract ex, const uint8_t *img_l,
       hipLaunchKernelGGL(akaze_pair_finish_kernel, dim3(32), blk, 0, st, d.stat, d.cand_cap, d.sup_cnt, d.sup_kp, d.d_angle, d.d_desc, cap, s.d_kp, s.d_desc, s.d_n, h_n, h_k, h_akp, h_desc);
     } else if (ex == AkExtract::Orb) {
       static_assert(offsetof(AkazeKp, x) == 0 && offsetof(AkazeKp, y) == 4 && offsetof(AkazeKp, octave) == 20, "record layout");
-      const OrbLinkSrc src{reinterpret_cast<const char *>(d.sup_kp), (int)sizeof(AkazeKp), 0, 4, 20, nullptr, d.sup_cnt + AKAZE_SUP_KEPT, d.sup_cap};
-      if ((rc = orb_link_enqueue(c, rows, cols, max_octave, src, cap, reinterpret_cast<uint8_t *>(s.d_desc)))) return rc;
+      const OrbLinkSrc src{reinterpret_cast<const char *>(d.sup_kp.get()), (int)sizeof(AkazeKp), 0, 4, 20, nullptr, d.sup_cnt + AKAZE_SUP_KEPT, d.sup_cap};
+      if ((rc = orb_link_enqueue(c, rows, cols, max_octave, src, cap, reinterpret_cast<uint8_t *>(s.d_desc.get())))) return rc;
       orb_link_finish_akaze(c, d.sup_kp, d.stat, d.cand_cap, cap, s.d_kp, s.d_desc, s.d_n, h_n, h_k, h_akp, h_desc);
     } else {
       // the kept records as a BRISK detector's list, every keep flag set; the tested compaction, describe and finishing launches follow
@@ -666,7 +636,7 @@ int spvo_akaze_sift_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r
   det.prepare = [&](SiftLinkSrc &src) -> int {
     int rc;
     if ((rc = ak_ensure(c, rows, cols)) || (rc = ak_sup_ensure(c, d.cand_cap))) return rc;
-    src = SiftLinkSrc{reinterpret_cast<const char *>(d.sup_kp), (int)sizeof(AkazeKp), (int)offsetof(AkazeKp, x), (int)offsetof(AkazeKp, y), (int)offsetof(AkazeKp, size),
+    src = SiftLinkSrc{reinterpret_cast<const char *>(d.sup_kp.get()), (int)sizeof(AkazeKp), (int)offsetof(AkazeKp, x), (int)offsetof(AkazeKp, y), (int)offsetof(AkazeKp, size),
                       (int)offsetof(AkazeKp, angle), (int)offsetof(AkazeKp, response), (int)offsetof(AkazeKp, octave), nullptr, d.sup_cnt + AKAZE_SUP_KEPT, d.sup_cap, nullptr, d.stat,
                       d.cand_cap};
     return SPVO_OK;

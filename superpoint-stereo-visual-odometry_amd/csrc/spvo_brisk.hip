@@ -81,19 +81,15 @@ const BriskHostTables &brisk_tables() {
 }
 
 // the tables on the device: uploaded on a context's first BRISK call (the point table is 47 MB: a one-off cost, include/spvo.h).  A call that
-// fails half way leaves nothing behind: tables_ready is set last, and the next call starts over.
+// fails half way is started over by the next: tables_ready is set last, and the grow list frees what the failed call left.
 int brisk_upload_tables(spvo_ctx *c, const BriskHostTables &t) {
   auto &k = c->brisk;
-  int rc;
-  if ((rc = dev_alloc(c, &k.points, t.points.size(), false)) || (rc = dev_alloc(c, &k.long_pairs, BRISK_LONG, false)) || (rc = dev_alloc(c, &k.short_pairs, BRISK_SHORT, false)) ||
-      (rc = dev_alloc(c, &k.cnt, 4)))
-    return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
+  if (int rc = grow(c, wait_for_nothing(), {plain(k.points, t.points.size()), plain(k.long_pairs, BRISK_LONG), plain(k.short_pairs, BRISK_SHORT), zeroed(k.cnt, 4)})) return rc;
+  k.h_n.reset();   // (re-allocated behind the uploads, below)
   HIP_TRY(c, hipMemcpy(k.points, t.points.data(), t.points.size() * sizeof(float), hipMemcpyHostToDevice));
   HIP_TRY(c, hipMemcpy(k.long_pairs, t.long_pairs, sizeof t.long_pairs, hipMemcpyHostToDevice));
   HIP_TRY(c, hipMemcpy(k.short_pairs, t.short_pairs, sizeof t.short_pairs, hipMemcpyHostToDevice));
-  HIP_TRY(c, hipHostMalloc((void **)&k.h_n, 4 * sizeof(int)));
-  return SPVO_OK;
+  return grow(c, wait_for_nothing(), {plain(k.h_n, 4)});
 }
 
 int brisk_ensure_tables(spvo_ctx *c) {
@@ -101,11 +97,7 @@ int brisk_ensure_tables(spvo_ctx *c) {
   if (k.tables_ready) return SPVO_OK;
   const BriskHostTables &t = brisk_tables();
   if (!t.ok) return fail(c, SPVO_ERR_STATE, "BRISK: the pattern tables failed their own checks (512 short pairs, 870 long pairs, every sigma >= 0.5)");
-  if (int rc = brisk_upload_tables(c, t)) {
-    dev_free(k.points, k.long_pairs, k.short_pairs, k.cnt);
-    host_free(k.h_n);
-    return rc;
-  }
+  if (int rc = brisk_upload_tables(c, t)) return rc;
   k.tables_ready = true;
   return SPVO_OK;
 }
@@ -116,48 +108,25 @@ int brisk_ensure(spvo_ctx *c, int rows, int cols, int n, bool want_values0) {
   auto &k = c->brisk;
   hipStream_t st = c->stream2;
   const size_t need = (size_t)(rows + 1) * (cols + 1);
-  if (need > k.integ_cap) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    dev_free(k.integ);
-    k.integ_cap = 0;
-    if (int rc = dev_alloc(c, &k.integ, need, false)) return rc;
-    k.integ_cap = need;
-  }
+  if (need > k.integ.count())
+    if (int rc = grow(c, wait_for(st), {plain(k.integ, need)})) return rc;
   if (n > k.kp_cap) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    dev_free(k.xy, k.size, k.angle, k.kept, k.kscale, k.desc);
-    host_free(k.h_kept, k.h_angle, k.h_desc);
     const int cap = (int)std::min<long long>(std::max<long long>(n, 2ll * k.kp_cap), 0x7FFFFFFF);
     k.kp_cap = 0;   // a failed allocation below leaves a context that spvo_destroy and a later call can still handle
-    int rc;
-    if ((rc = dev_alloc(c, &k.xy, (size_t)2 * cap, false)) || (rc = dev_alloc(c, &k.size, cap, false)) || (rc = dev_alloc(c, &k.angle, cap, false)) || (rc = dev_alloc(c, &k.kept, cap, false)) ||
-        (rc = dev_alloc(c, &k.kscale, cap, false)) || (rc = dev_alloc(c, &k.desc, (size_t)cap * BRISK_BYTES, false)))
+    if (int rc = grow(c, wait_for(st), {plain(k.xy, (size_t)2 * cap), plain(k.size, cap), plain(k.angle, cap), plain(k.kept, cap), plain(k.kscale, cap), plain(k.desc, (size_t)cap * BRISK_BYTES),
+                                        plain(k.h_kept, cap), plain(k.h_angle, cap), plain(k.h_desc, (size_t)cap * BRISK_BYTES)}))
       return rc;
-    HIP_TRY(c, hipHostMalloc((void **)&k.h_kept, (size_t)cap * sizeof(int)));
-    HIP_TRY(c, hipHostMalloc((void **)&k.h_angle, (size_t)cap * sizeof(float)));
-    HIP_TRY(c, hipHostMalloc((void **)&k.h_desc, (size_t)cap * BRISK_BYTES));
     k.kp_cap = cap;
   }
   if (want_values0 && n > k.v0_cap) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    dev_free(k.values0);
-    host_free(k.h_values0);
     const int cap = std::max(n, k.kp_cap);
     k.v0_cap = 0;
-    if (int rc = dev_alloc(c, &k.values0, (size_t)cap * BRISK_POINTS, false)) return rc;
-    HIP_TRY(c, hipHostMalloc((void **)&k.h_values0, (size_t)cap * BRISK_POINTS * sizeof(int)));
+    if (int rc = grow(c, wait_for(st), {plain(k.values0, (size_t)cap * BRISK_POINTS), plain(k.h_values0, (size_t)cap * BRISK_POINTS)})) return rc;
     k.v0_cap = cap;
   }
   return SPVO_OK;
 }
 }  // namespace
-
-void spvo_int::brisk_release(spvo_ctx *c) {
-  auto &k = c->brisk;
-  dev_free(k.points, k.long_pairs, k.short_pairs, k.cnt, k.integ, k.xy, k.size, k.angle, k.kept, k.kscale, k.values0, k.desc);
-  host_free(k.h_n, k.h_kept, k.h_angle, k.h_desc, k.h_values0);
-  k.integ_cap = 0; k.kp_cap = k.v0_cap = 0; k.tables_ready = false;
-}
 
 int spvo_int::brisk_check_image(spvo_ctx *c, const char *who, int rows, int cols) {
   if ((long long)rows * cols * 255 >= (1ll << 31)) return fail(c, SPVO_ERR_INVALID, "%s: %d x %d pixels do not fit the int32 integral image", who, rows, cols);
@@ -259,8 +228,8 @@ int spvo_brisk_describe(spvo_ctx *c, const uint8_t *img, int rows, int cols, siz
   hipLaunchKernelGGL(brisk_compact_kernel, dim3(1), dim3(1024), 0, st, k.xy, k.size, n, rows, cols, brisk_tables().params, k.kept, k.kscale, k.cnt);
   hipLaunchKernelGGL(brisk_describe_kernel, dim3(std::min((n + 3) / 4, BRISK_DESCRIBE_BLOCKS)), dim3(256), 0, st, b.im, k.integ, rows, cols, k.xy, k.kept, k.kscale, k.cnt, k.points, k.long_pairs, k.short_pairs, k.angle,
                      k.desc, values0 ? k.values0 : nullptr);
-  hipLaunchKernelGGL(brisk_finish_kernel, dim3(32), dim3(256), 0, st, k.cnt, k.kept, k.angle, reinterpret_cast<const uint32_t *>(k.desc), values0 ? k.values0 : nullptr, k.h_n, k.h_kept, k.h_angle,
-                     reinterpret_cast<uint32_t *>(k.h_desc), values0 ? k.h_values0 : nullptr);
+  hipLaunchKernelGGL(brisk_finish_kernel, dim3(32), dim3(256), 0, st, k.cnt, k.kept, k.angle, reinterpret_cast<const uint32_t *>(k.desc.get()), values0 ? k.values0.get() : nullptr, k.h_n, k.h_kept, k.h_angle,
+                     reinterpret_cast<uint32_t *>(k.h_desc.get()), values0 ? k.h_values0.get() : nullptr);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(st));   // the one wait of the call
   const int m = std::min(std::max(k.h_n[0], 0), n);

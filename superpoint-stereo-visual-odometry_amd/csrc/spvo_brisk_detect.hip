@@ -42,10 +42,8 @@ int bd_ensure(spvo_ctx *c, int rows, int cols) {
   auto &d = c->brisk_det;
   hipStream_t st = c->stream2;
   d.valid = false;
-  if (!d.counters) {
-    if (int rc = dev_alloc(c, &d.counters, BD_COUNTER_INTS)) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
-  }
+  if (!d.counters)
+    if (int rc = grow(c, wait_for_nothing(), {zeroed(d.counters, BD_COUNTER_INTS)})) return rc;
   int h[BRISK_DET_LAYERS], w[BRISK_DET_LAYERS];
   h[0] = rows; w[0] = cols;
   h[1] = 2 * (rows / 3); w[1] = 2 * (cols / 3);
@@ -76,16 +74,12 @@ int bd_ensure(spvo_ctx *c, int rows, int cols) {
         return fail(c, SPVO_ERR_STATE, "BRISK detector: the area taps of layer %d (%d x %d from %d x %d) failed their own checks", i, h[i], w[i], h[s], w[s]);
     }
     if (pyr > d.px_cap || score > d.px_cap || tabs > d.tab_cap || cand > d.cand_cap) {
-      HIP_TRY(c, hipStreamSynchronize(st));
-      dev_free(d.pyr, d.score, d.tabs, d.keys, d.rank, d.keep, d.rec, d.out);
       const size_t npx = std::max(std::max(pyr, score), d.px_cap), ntab = std::max(std::max<size_t>(tabs, 1), d.tab_cap);
       const int ncand = (int)std::min<long long>(std::max<long long>(std::max<long long>(cand, 1), d.cand_cap), 0x7FFFFFFF);
       d.px_cap = d.tab_cap = 0; d.cand_cap = 0;   // a failed allocation below leaves a context that spvo_destroy and a later call can still handle
-      int rc;
-      if ((rc = dev_alloc(c, &d.pyr, npx, false)) || (rc = dev_alloc(c, &d.score, npx, false)) || (rc = dev_alloc(c, &d.tabs, ntab, false)) || (rc = dev_alloc(c, &d.keys, ncand, false)) ||
-          (rc = dev_alloc(c, &d.rank, ncand)) || (rc = dev_alloc(c, &d.keep, ncand, false)) || (rc = dev_alloc(c, &d.rec, ncand, false)) || (rc = dev_alloc(c, &d.out, ncand, false)))
+      if (int rc = grow(c, wait_for(st), {plain(d.pyr, npx), plain(d.score, npx), plain(d.tabs, ntab), plain(d.keys, ncand), zeroed(d.rank, ncand), plain(d.keep, ncand), plain(d.rec, ncand),
+                                          plain(d.out, ncand)}))
         return rc;
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
       d.px_cap = npx; d.tab_cap = ntab; d.cand_cap = ncand;
     }
     HIP_TRY(c, hipMemcpyAsync(d.tabs, d.h_tabs.data(), d.h_tabs.size() * sizeof(BriskAreaTap), hipMemcpyHostToDevice, st));
@@ -162,12 +156,6 @@ int bd_check(spvo_ctx *c, const char *who, int rows, int cols, int threshold, in
 }
 }  // namespace
 
-void spvo_int::brisk_detect_release(spvo_ctx *c) {
-  auto &d = c->brisk_det;
-  dev_free(d.pyr, d.score, d.tabs, d.keys, d.rank, d.keep, d.counters, d.rec, d.out);
-  d.px_cap = d.tab_cap = 0; d.cand_cap = 0; d.rows = d.cols = 0; d.valid = false;
-}
-
 extern "C" {
 
 int spvo_brisk_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride, int threshold, int octaves, spvo_brisk_keypoint *kp, int cap, int *n_out) {
@@ -235,8 +223,8 @@ int brisk_pair(spvo_ctx *c, const char *who, bool orb, const uint8_t *img_l, con
       continue;
     }
     static_assert(offsetof(BriskDetKeypoint, x) == 0 && offsetof(BriskDetKeypoint, y) == 4 && offsetof(BriskDetKeypoint, octave) == 20, "record layout");
-    const OrbLinkSrc src{reinterpret_cast<const char *>(d.rec), (int)sizeof(BriskDetKeypoint), 0, 4, 20, d.keep, d.counters + 1, d.cand_cap};
-    if ((rc = orb_link_enqueue(c, rows, cols, BRISK_ORB_MAX_OCTAVE, src, cap, reinterpret_cast<uint8_t *>(s.d_desc)))) return rc;
+    const OrbLinkSrc src{reinterpret_cast<const char *>(d.rec.get()), (int)sizeof(BriskDetKeypoint), 0, 4, 20, d.keep, d.counters + 1, d.cand_cap};
+    if ((rc = orb_link_enqueue(c, rows, cols, BRISK_ORB_MAX_OCTAVE, src, cap, reinterpret_cast<uint8_t *>(s.d_desc.get())))) return rc;
     orb_link_finish_brisk(c, d.rec, d.counters, cap, s.d_kp, s.d_desc, s.d_n, out.h_n, bb.h_bkp + (size_t)k * cap, out.h_desc);
     HIP_TRY(c, hipGetLastError());
   }
@@ -281,7 +269,7 @@ int spvo_brisk_sift_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r
   det.check = [&]() -> int { return bd_check(c, who, rows, cols, threshold, octaves); };
   det.prepare = [&](SiftLinkSrc &src) -> int {
     if (int rc = bd_ensure(c, rows, cols)) return rc;
-    src = SiftLinkSrc{reinterpret_cast<const char *>(d.rec), (int)sizeof(BriskDetKeypoint), (int)offsetof(BriskDetKeypoint, x), (int)offsetof(BriskDetKeypoint, y),
+    src = SiftLinkSrc{reinterpret_cast<const char *>(d.rec.get()), (int)sizeof(BriskDetKeypoint), (int)offsetof(BriskDetKeypoint, x), (int)offsetof(BriskDetKeypoint, y),
                       (int)offsetof(BriskDetKeypoint, size), (int)offsetof(BriskDetKeypoint, angle), (int)offsetof(BriskDetKeypoint, response), (int)offsetof(BriskDetKeypoint, octave),
                       d.keep, d.counters + 1, d.cand_cap, d.counters, nullptr, 0};
     return SPVO_OK;

@@ -12,15 +12,10 @@
 namespace {
 // a host image of a strided view into the packed rows of `dst`, through the staging buffer `src` (grown on demand).  Of a strided view
 // (a cv::Mat ROI) only (rows - 1) * stride + cols bytes are the caller's: the last row's padding may lie beyond the end of the parent allocation
-int upload_strided(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride, uint8_t *&src, size_t &src_cap, uint8_t *dst, hipStream_t st) {
+int upload_strided(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride, DevBuf<uint8_t> &src, uint8_t *dst, hipStream_t st) {
   const size_t src_bytes = (size_t)(rows - 1) * stride + cols;
-  if (src_bytes > src_cap) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    dev_free(src);
-    src_cap = 0;
-    if (int rc = dev_alloc(c, &src, src_bytes, false)) return rc;
-    src_cap = src_bytes;
-  }
+  if (src_bytes > src.count())
+    if (int rc = grow(c, wait_for(st), {plain(src, src_bytes)})) return rc;
   HIP_TRY(c, hipMemcpyAsync(src, img, src_bytes, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpy2DAsync(dst, cols, src, stride, cols, rows, hipMemcpyDeviceToDevice, st));
   return SPVO_OK;
@@ -33,8 +28,7 @@ int spvo_int::classic_preprocess(spvo_ctx *c, const CropGeom &g, size_t stride) 
   auto &b = c->cls;
   const int H = c->H, W = c->W;
   if (!b.pre_out) {
-    int rc;
-    if ((rc = dev_alloc(c, &b.pre_out, (size_t)H * W)) || (rc = dev_alloc(c, &b.pre_tab, (size_t)3 * (H + W)))) return rc;
+    if (int rc = grow(c, wait_for_nothing(), {zeroed(b.pre_out, (size_t)H * W), zeroed(b.pre_tab, (size_t)3 * (H + W))})) return rc;
     b.pre_crop_rows = b.pre_crop_cols = 0;
   }
   const uint8_t *src = c->d_img[0] + (size_t)g.row_off * stride + g.col_off;
@@ -89,9 +83,7 @@ int orb_ensure_tables(spvo_ctx *c) {
   std::vector<signed char> disc;
   float taps[7];
   orb_host_tables(pat, taps, disc);
-  int rc;
-  if ((rc = dev_alloc(c, &o.pattern, 1024)) || (rc = dev_alloc(c, &o.taps, 8)) || (rc = dev_alloc(c, &o.disc, disc.size()))) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (int rc = grow(c, wait_for_nothing(), {zeroed(o.pattern, 1024), zeroed(o.taps, 8), zeroed(o.disc, disc.size())})) return rc;
   HIP_TRY(c, hipMemcpy(o.pattern, pat.data(), 1024 * 4, hipMemcpyHostToDevice));
   HIP_TRY(c, hipMemcpy(o.taps, taps, 7 * 4, hipMemcpyHostToDevice));
   HIP_TRY(c, hipMemcpy(o.disc, disc.data(), disc.size(), hipMemcpyHostToDevice));
@@ -153,18 +145,13 @@ int orb_prepare(spvo_ctx *c, int rows, int cols, int nfeatures, OrbPlan &p) {
   }
   const size_t need_pyr = off[ORB_LEVELS] + 256;
   if (need_pyr > o.pyr_cap || need_keys > o.key_cap || need_tab > o.tab_cap || kp_cap > o.kp_cap) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    dev_free(o.im, o.score, o.blur, o.tmp, o.keys, o.rank, o.out_xy, o.counters, o.tab, o.kps, o.desc);
     const size_t pyr = std::max(need_pyr, o.pyr_cap), kall = std::max(need_keys, o.key_cap), tabn = std::max(need_tab, o.tab_cap);
     const int kpn = std::max(kp_cap, o.kp_cap);
     o.pyr_cap = o.key_cap = o.tab_cap = 0; o.kp_cap = 0;   // a failed allocation below leaves a context that spvo_destroy and a later call can still handle
-    int rc;
-    if ((rc = dev_alloc(c, &o.im, pyr)) || (rc = dev_alloc(c, &o.score, pyr)) || (rc = dev_alloc(c, &o.blur, pyr)) || (rc = dev_alloc(c, &o.tmp, pyr)) ||
-        (rc = dev_alloc(c, &o.keys, kall)) || (rc = dev_alloc(c, &o.rank, kall)) || (rc = dev_alloc(c, &o.out_xy, 2 * kall)) ||
-        (rc = dev_alloc(c, &o.counters, (size_t)ORB_LEVELS * NMS_COUNTER_INTS)) || (rc = dev_alloc(c, &o.tab, tabn)) || (rc = dev_alloc(c, &o.kps, kpn)) ||
-        (rc = dev_alloc(c, &o.desc, (size_t)kpn * 32)))
+    if (int rc = grow(c, wait_for(st), {zeroed(o.im, pyr), zeroed(o.score, pyr), zeroed(o.blur, pyr), zeroed(o.tmp, pyr), zeroed(o.keys, kall), zeroed(o.rank, kall),
+                                        zeroed(o.out_xy, 2 * kall), zeroed(o.counters, (size_t)ORB_LEVELS * NMS_COUNTER_INTS), zeroed(o.tab, tabn), zeroed(o.kps, kpn),
+                                        zeroed(o.desc, (size_t)kpn * 32)}))
       return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
     o.pyr_cap = pyr; o.key_cap = kall; o.tab_cap = tabn; o.kp_cap = kpn;
     o.tab_rows = o.tab_cols = 0;
   }
@@ -259,7 +246,7 @@ int spvo_orb_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t 
   const int kp_cap = nfeatures;
   OrbPlan plan;
   if (int rc = orb_prepare(c, rows, cols, nfeatures, plan)) return rc;
-  if (int rc = upload_strided(c, img, rows, cols, stride, o.src, o.src_cap, o.im, st)) return rc;   // level 0: the image, rows packed
+  if (int rc = upload_strided(c, img, rows, cols, stride, o.src, o.im, st)) return rc;   // level 0: the image, rows packed
   if (int rc = orb_enqueue(c, plan, rows, cols, o.kps, o.desc, kp_cap)) return rc;
   int cnt[ORB_LEVELS * NMS_COUNTER_INTS];
   HIP_TRY(c, hipMemcpyAsync(cnt, o.counters, sizeof cnt, hipMemcpyDeviceToHost, st));
@@ -290,24 +277,15 @@ int cls_ensure(spvo_ctx *c, int rows, int cols) {
   b.rows = b.cols = 0;   // nothing resident until the upload below is enqueued
   ++b.image_gen;
   if (px > b.px_cap || state_bytes > b.state_cap) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    dev_free(b.im, b.score, b.blur, b.state, b.tmp, b.lam, b.xy, b.resp, b.keys, b.rank, b.cand);
     const size_t npx = std::max(px, b.px_cap), nst = std::max(state_bytes, b.state_cap);
     b.px_cap = b.state_cap = 0;   // a failed allocation below leaves a context that spvo_destroy and a later call can still handle
     b.state_rows = b.state_cols = 0;
-    int rc;
-    if ((rc = dev_alloc(c, &b.im, npx + 256)) || (rc = dev_alloc(c, &b.score, npx + 256)) || (rc = dev_alloc(c, &b.blur, npx + 256)) || (rc = dev_alloc(c, &b.state, nst)) ||
-        (rc = dev_alloc(c, &b.tmp, npx)) || (rc = dev_alloc(c, &b.lam, npx)) || (rc = dev_alloc(c, &b.xy, 2 * npx)) || (rc = dev_alloc(c, &b.resp, npx)) ||
-        (rc = dev_alloc(c, &b.keys, npx)) || (rc = dev_alloc(c, &b.rank, npx)) || (rc = dev_alloc(c, &b.cand, npx)))
+    if (int rc = grow(c, wait_for(st), {zeroed(b.im, npx + 256), zeroed(b.score, npx + 256), zeroed(b.blur, npx + 256), zeroed(b.state, nst), zeroed(b.tmp, npx), zeroed(b.lam, npx),
+                                        zeroed(b.xy, 2 * npx), zeroed(b.resp, npx), zeroed(b.keys, npx), zeroed(b.rank, npx), zeroed(b.cand, npx)}))
       return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
     b.px_cap = npx; b.state_cap = nst;
   }
-  if (!b.counters) {
-    int rc = dev_alloc(c, &b.counters, CLS_COUNTER_INTS);
-    if (rc) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
+  if (!b.counters) return grow(c, wait_for_nothing(), {zeroed(b.counters, CLS_COUNTER_INTS)});
   return SPVO_OK;
 }
 
@@ -315,7 +293,7 @@ int cls_ensure(spvo_ctx *c, int rows, int cols) {
 int cls_prepare(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride) {
   auto &b = c->cls;
   if (int rc = cls_ensure(c, rows, cols)) return rc;
-  if (int rc = upload_strided(c, img, rows, cols, stride, b.src, b.src_cap, b.im, c->stream2)) return rc;
+  if (int rc = upload_strided(c, img, rows, cols, stride, b.src, b.im, c->stream2)) return rc;
   b.rows = rows; b.cols = cols;
   return SPVO_OK;
 }
@@ -467,12 +445,8 @@ int spvo_orb_describe(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_
   }
   if (int rc = orb_ensure_tables(c)) return rc;
   if (nk > b.kp_cap) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    dev_free(b.kp_xy, b.kps, b.desc);
     b.kp_cap = 0;
-    int rc;
-    if ((rc = dev_alloc(c, &b.kp_xy, (size_t)2 * nk)) || (rc = dev_alloc(c, &b.kps, (size_t)nk)) || (rc = dev_alloc(c, &b.desc, (size_t)nk * 32))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (int rc = grow(c, wait_for(st), {zeroed(b.kp_xy, (size_t)2 * nk), zeroed(b.kps, (size_t)nk), zeroed(b.desc, (size_t)nk * 32)})) return rc;
     b.kp_cap = nk;
   }
   int cnt[CLS_COUNTER_INTS] = {0};
@@ -557,12 +531,8 @@ int spvo_orb_describe_octaves(spvo_ctx *c, const uint8_t *img, int rows, int col
   OrbPlan plan;
   if (int rc = orb_prepare(c, rows, cols, 1, plan)) return rc;   // (no keypoint buffer of spvo_orb_detect's is used: nfeatures 1 grows none)
   if (nk > b.oct_cap) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    dev_free(b.oct_rec, b.oct_angle, b.oct_desc);
     b.oct_cap = 0;
-    int rc;
-    if ((rc = dev_alloc(c, &b.oct_rec, (size_t)3 * nk)) || (rc = dev_alloc(c, &b.oct_angle, (size_t)nk)) || (rc = dev_alloc(c, &b.oct_desc, (size_t)nk * 32))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (int rc = grow(c, wait_for(st), {zeroed(b.oct_rec, (size_t)3 * nk), zeroed(b.oct_angle, (size_t)nk), zeroed(b.oct_desc, (size_t)nk * 32)})) return rc;
     b.oct_cap = nk;
   }
   HIP_TRY(c, hipMemcpyAsync(b.oct_rec, rec.data(), rec.size() * sizeof(int), hipMemcpyHostToDevice, st));
@@ -582,26 +552,16 @@ namespace {
 // the link's buffers for `cap` rows (and, for the test hook, a list of `n_src` records with its keep flags)
 int orb_link_buffers(spvo_ctx *c, int cap, int n_src) {
   auto &b = c->cls;
-  if (!b.lnk_cnt) {
-    if (int rc = dev_alloc(c, &b.lnk_cnt, ORB_LINK_INTS)) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
-  }
+  if (!b.lnk_cnt)
+    if (int rc = grow(c, wait_for_nothing(), {zeroed(b.lnk_cnt, ORB_LINK_INTS)})) return rc;
   if (cap > b.lnk_cap) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream2));
-    dev_free(b.lnk_kept, b.lnk_rec, b.lnk_angle, b.lnk_desc);
     b.lnk_cap = 0;
-    int rc;
-    if ((rc = dev_alloc(c, &b.lnk_kept, (size_t)cap, false)) || (rc = dev_alloc(c, &b.lnk_rec, (size_t)3 * cap, false)) || (rc = dev_alloc(c, &b.lnk_angle, (size_t)cap, false)) ||
-        (rc = dev_alloc(c, &b.lnk_desc, (size_t)cap * 32, false)))
-      return rc;
+    if (int rc = grow(c, wait_for(c->stream2), {plain(b.lnk_kept, (size_t)cap), plain(b.lnk_rec, (size_t)3 * cap), plain(b.lnk_angle, (size_t)cap), plain(b.lnk_desc, (size_t)cap * 32)})) return rc;
     b.lnk_cap = cap;
   }
   if (n_src > b.lnk_src_cap) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream2));
-    dev_free(b.lnk_src, b.lnk_keep);
     b.lnk_src_cap = 0;
-    int rc;
-    if ((rc = dev_alloc(c, &b.lnk_src, (size_t)3 * n_src, false)) || (rc = dev_alloc(c, &b.lnk_keep, (size_t)n_src, false))) return rc;
+    if (int rc = grow(c, wait_for(c->stream2), {plain(b.lnk_src, (size_t)3 * n_src), plain(b.lnk_keep, (size_t)n_src)})) return rc;
     b.lnk_src_cap = n_src;
   }
   return SPVO_OK;
@@ -690,7 +650,7 @@ int spvo_orb_octaves_link_debug(spvo_ctx *c, int rows, int cols, const float *xy
   HIP_TRY(c, hipMemcpyAsync(b.lnk_src, rec.data(), rec.size() * sizeof(int), hipMemcpyHostToDevice, st));
   if (keep) HIP_TRY(c, hipMemcpyAsync(b.lnk_keep, flags.data(), flags.size() * sizeof(int), hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(b.lnk_cnt + ORB_LINK_N, &n, sizeof n, hipMemcpyHostToDevice, st));
-  const OrbLinkSrc src{reinterpret_cast<const char *>(b.lnk_src), 12, 0, 4, 8, keep ? b.lnk_keep : nullptr, b.lnk_cnt + ORB_LINK_N, n};
+  const OrbLinkSrc src{reinterpret_cast<const char *>(b.lnk_src.get()), 12, 0, 4, 8, keep ? b.lnk_keep.get() : nullptr, b.lnk_cnt + ORB_LINK_N, n};
   if (int rc = orb_link_enqueue(c, rows, cols, max_octave, src, n, b.lnk_desc)) return rc;
   int cnt[ORB_LINK_INTS];
   HIP_TRY(c, hipMemcpyAsync(cnt, b.lnk_cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
@@ -722,16 +682,13 @@ void spvo_int::classic_rank_enqueue(spvo_ctx *c, const unsigned long long *keys,
 }
 
 // ---------------------------------------------------------------- one submission per stereo pair, features stay on the device
-// everything bin_ensure sizes by the slot capacity; the slots are empty afterwards
+// what bin_ensure forgets when it re-allocates everything the slot capacity sizes: the slots are empty afterwards
 void spvo_int::classic_release_slots(spvo_ctx *c) {
   auto &bb = c->bin;
   for (BinarySlot &s : bb.slots) {
-    dev_free(s.d_kp, s.d_desc, s.d_n);
     slot_rewrite(s);
     s.row_bytes = 32;
   }
-  dev_free(bb.d_cnt, bb.d_kxy, bb.d_kresp, bb.d_vote);
-  host_free(bb.h_kp, bb.h_bkp, bb.h_akp, bb.h_desc, bb.h_n, bb.h_match);
   bb.pair.mcache.invalidate();
   bb.cap = 0; bb.pair.last_slot_l = -1;
 }
@@ -757,19 +714,12 @@ int bin_ensure(spvo_ctx *c, int cap, size_t px) {
   if (cap <= bb.cap) return SPVO_OK;
   HIP_TRY(c, hipStreamSynchronize(c->stream2));
   classic_release_slots(c);
-  int rc;
-  for (BinarySlot &s : bb.slots)
-    if ((rc = dev_alloc(c, &s.d_kp, cap)) || (rc = dev_alloc(c, &s.d_desc, (size_t)cap * (BIN_ROW_BYTES_MAX / 4))) || (rc = dev_alloc(c, &s.d_n, 1))) return rc;
-  if ((rc = dev_alloc(c, &bb.d_cnt, 2 * CLS_COUNTER_INTS)) || (rc = dev_alloc(c, &bb.d_kxy, (size_t)2 * cap)) || (rc = dev_alloc(c, &bb.d_kresp, cap)) ||
-      (rc = dev_alloc(c, &bb.d_vote, cap)))
-    return rc;
-  HIP_TRY(c, hipHostMalloc((void **)&bb.h_kp, (size_t)2 * cap * sizeof(OrbKeypoint)));
-  HIP_TRY(c, hipHostMalloc((void **)&bb.h_bkp, (size_t)2 * cap * sizeof(BriskDetKeypoint)));
-  HIP_TRY(c, hipHostMalloc((void **)&bb.h_desc, (size_t)2 * cap * BIN_ROW_BYTES_MAX));
-  HIP_TRY(c, hipHostMalloc((void **)&bb.h_akp, (size_t)2 * cap * sizeof(AkazeKp)));
-  HIP_TRY(c, hipHostMalloc((void **)&bb.h_n, 4 * 4 * sizeof(int)));
-  HIP_TRY(c, hipHostMalloc((void **)&bb.h_match, (size_t)3 * cap * sizeof(int2)));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
+  std::vector<GrowEntry> list;
+  for (BinarySlot &s : bb.slots) list.insert(list.end(), {zeroed(s.d_kp, cap), zeroed(s.d_desc, (size_t)cap * (BIN_ROW_BYTES_MAX / 4)), zeroed(s.d_n, 1)});
+  list.insert(list.end(), {zeroed(bb.d_cnt, 2 * CLS_COUNTER_INTS), zeroed(bb.d_kxy, (size_t)2 * cap), zeroed(bb.d_kresp, cap), zeroed(bb.d_vote, cap), plain(bb.h_kp, (size_t)2 * cap),
+                           plain(bb.h_bkp, (size_t)2 * cap), plain(bb.h_desc, (size_t)2 * cap * BIN_ROW_BYTES_MAX), plain(bb.h_akp, (size_t)2 * cap), plain(bb.h_n, 4 * 4),
+                           plain(bb.h_match, (size_t)3 * cap)});
+  if (int rc = grow(c, wait_for_nothing(), list)) return rc;
   bb.cap = cap;
   return SPVO_OK;
 }

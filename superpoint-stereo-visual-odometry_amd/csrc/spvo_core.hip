@@ -358,23 +358,18 @@ int spvo_create(const spvo_config *cfg, spvo_ctx **out) {
   c->surv_cap = ((c->H + cell - 1) / cell) * ((c->W + cell - 1) / cell) + 64;
   do {
     if ((rc = dev_check(c, hipEventCreateWithFlags(&c->ev_post, hipEventDisableTiming), "hipEventCreate")) || (rc = dev_check(c, hipEventCreateWithFlags(&c->ev_post_b, hipEventDisableTiming), "hipEventCreate"))) break;
-    if ((rc = dev_alloc(c, &c->d_dense_in, c->B * hw))) break;
-    if ((rc = dev_alloc(c, &c->d_det_dense, (size_t)c->B * 65 * c->Hc * c->Wc))) break;
-    if ((rc = dev_alloc(c, &c->d_counters_all, (size_t)(RING + 1) * 2 * NMS_COUNTER_INTS))) break;   // RING submission sets, stand-alone
+    if ((rc = grow(c, wait_for_nothing(), {zeroed(c->d_dense_in, c->B * hw), zeroed(c->d_det_dense, (size_t)c->B * 65 * c->Hc * c->Wc),
+                                           zeroed(c->d_counters_all, (size_t)(RING + 1) * 2 * NMS_COUNTER_INTS)})))   // RING submission sets, stand-alone
+      break;
     c->d_counters_alone = c->d_counters_all + (size_t)RING * 2 * NMS_COUNTER_INTS;
     for (int r = 0; r < RING && !rc; ++r) rc = set_alloc(c, r);
     if (rc) break;
-    if ((rc = dev_alloc(c, &c->d_resized, 2 * hw))) break;
-    if ((rc = dev_alloc(c, &c->d_tab, (size_t)3 * (c->H + c->W)))) break;
-    for (int i = 0; i < N_SLOTS && !rc; ++i) {
-      if ((rc = dev_alloc(c, &c->slots[i].d_xy, (size_t)cap * 2))) break;
-      if ((rc = dev_alloc(c, &c->slots[i].d_desc, (size_t)cap * 256))) break;
-      if ((rc = dev_alloc(c, &c->slots[i].d_n, 1))) break;
-      if ((rc = dev_alloc(c, &c->slots[i].d_sqn, cap + 4))) break;   // K12b reads the norms four at a time
-    }
-    if (rc) break;
-    if ((rc = dev_alloc(c, &c->d_xy_tmp, (size_t)cap * 2))) break;
-    if ((rc = dev_alloc(c, &c->d_desc_tmp, (size_t)cap * 256))) break;
+    // (two lists, around the sets: the order of allocation decides where the buffers land, and is kept)
+    std::vector<GrowEntry> list{zeroed(c->d_resized, 2 * hw), zeroed(c->d_tab, (size_t)3 * (c->H + c->W))};
+    for (FeatureSlot &sl : c->slots)
+      list.insert(list.end(), {zeroed(sl.d_xy, (size_t)cap * 2), zeroed(sl.d_desc, (size_t)cap * 256), zeroed(sl.d_n, 1), zeroed(sl.d_sqn, cap + 4)});   // K12b reads the norms four at a time
+    list.insert(list.end(), {zeroed(c->d_xy_tmp, (size_t)cap * 2), zeroed(c->d_desc_tmp, (size_t)cap * 256)});
+    if ((rc = grow(c, wait_for_nothing(), list))) break;
     if ((rc = ensure_match(c, cap, cap))) break;
   } while (0);
   if (rc) {
@@ -403,37 +398,14 @@ void spvo_destroy(spvo_ctx *c) {
   if (c->tdiag.base) (void)hipEventDestroy(c->tdiag.base);
   for (auto e : c->free_events) (void)hipEventDestroy(e);
   free_plan(c);
-  void *ptrs[] = {c->d_dense_in, c->d_det_dense, c->d_resized, c->d_tab, c->d_img[0], c->d_img[1], c->d_xy_tmp, c->d_desc_tmp,
-                  c->d_ma, c->d_mb, c->d_match_out, c->d_counters_all,
-                  c->d_P, c->d_pts_a, c->d_pts_b, c->d_xyz, c->rw.counts, c->rw.poses, c->rw.result, c->rw.inliers, c->d_obs, c->d_refine};
-  for (void *p : ptrs) if (p) (void)hipFree(p);
-  for (auto &set : c->ms)
-    for (auto &m : set)
-      dev_free(m.d_na, m.d_nb, m.d_best_d2, m.d_dt, m.d_cand, m.d_meta, m.d_best_idx, m.d_train_best, m.d_a8, m.d_b8, m.d_qa8, m.d_qb8);
   for (SubmitSet &s : c->sets) set_release(s);
-  for (auto &sl : c->slots) dev_free(sl.d_xy, sl.d_desc, sl.d_n, sl.d_sqn);
-  for (int sl = 0; sl < spvo_ctx::SOLVE_BUFS; ++sl) {
-    dev_free(c->x_counts[sl], c->x_poses[sl], c->x_obs[sl], c->d_solve_in[sl], c->d_solve_res[sl], c->d_solve_o[sl]);
-    host_free(c->h_solve_in[sl], c->h_solve_res[sl], c->h_solve_o[sl]);
-  }
-  if (c->d_ctl) (void)hipFree(c->d_ctl);
-  dev_free(c->d_ham_a, c->d_ham_b, c->d_ham_idx, c->d_ham_dist, c->d_ham_vote);
   classic_release(c);
-  auto &o = c->orb;
-  dev_free(o.im, o.score, o.blur, o.src, o.tmp, o.pattern, o.taps, o.keys, o.rank, o.out_xy, o.counters, o.tab, o.disc, o.kps, o.desc);
   sift_release(c);
-  brisk_release(c);
-  brisk_detect_release(c);
-  akaze_release(c);
-  auto &b = c->cls;
-  dev_free(b.im, b.score, b.blur, b.src, b.state, b.desc, b.tmp, b.lam, b.xy, b.resp, b.keys, b.rank, b.cand, b.counters, b.kp_xy, b.kps, b.oct_rec, b.oct_angle, b.oct_desc, b.pre_out, b.pre_tab);
-  dev_free(b.lnk_kept, b.lnk_rec, b.lnk_cnt, b.lnk_src, b.lnk_keep, b.lnk_angle, b.lnk_desc);
-  host_free(c->h_match_tmp);
   if (c->stream_t) (void)hipStreamDestroy(c->stream_t);
   if (c->stream_tb) (void)hipStreamDestroy(c->stream_tb);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   if (c->stream2) (void)hipStreamDestroy(c->stream2);
-  delete c;
+  delete c;   // frees every buffer the context owns (DevBuf / PinBuf members), its device still current
 }
 
 int spvo_set_fp32_split(spvo_ctx *c, int enable) {

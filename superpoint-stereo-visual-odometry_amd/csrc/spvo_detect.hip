@@ -85,14 +85,10 @@ static ResizeTab resize_tab(const spvo_ctx *c) {
   return t;
 }
 
-// the stand-alone entry points' staging for two input images of `bytes` each (a failed allocation leaves the capacity at 0)
+// the stand-alone entry points' staging for two input images of `bytes` each (a failed allocation leaves both empty)
 static int ensure_img_staging(spvo_ctx *c, size_t bytes) {
-  if (bytes <= c->img_cap) return SPVO_OK;
-  dev_free(c->d_img[0], c->d_img[1]);
-  c->img_cap = 0;
-  for (int i = 0; i < 2; ++i) { int rc = dev_alloc(c, &c->d_img[i], bytes, false); if (rc) return rc; }
-  c->img_cap = bytes;
-  return SPVO_OK;
+  if (bytes <= c->d_img[1].count()) return SPVO_OK;
+  return grow(c, wait_for_nothing(), {plain(c->d_img[0], bytes), plain(c->d_img[1], bytes)});
 }
 
 // one launch for `count` images (d_src0, d_src1) into slots slot0, slot0 + 1 of the resized-image buffer and the input tensor
@@ -294,15 +290,14 @@ int spvo_debug_tensor(spvo_ctx *c, int tensor_id, int batch, float *out, size_t 
     HIP_TRY(c, hipMemcpy(out, t.d, need * sizeof(float), hipMemcpyDeviceToHost));
     return SPVO_OK;
   }
-  float *tmp = nullptr;
-  HIP_TRY(c, hipMalloc((void **)&tmp, need * sizeof(float)));
+  DevBuf<float> tmp;   // (the call's own: freed when it returns, behind its wait)
+  if (int rc = grow(c, wait_for_nothing(), {plain(tmp, need)})) return rc;
   if (t.i8) launch_unpad_c16(t, batch, tmp, c->stream);
   else if (t.s3) launch_unpad_s3(t, batch, tmp, c->stream);
   else if (t.f16) launch_unpad_c8(t, batch, tmp, c->stream);
   else hipLaunchKernelGGL(unpad_kernel, dim3((t.W + 63) / 64, (t.H + 3) / 4, batch * t.ch), dim3(256), 0, c->stream, t.d, tmp, t.ch, t.H, t.W, t.hp, t.wp);
   hipError_t e = hipMemcpyAsync(out, tmp, need * sizeof(float), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(tmp);
   if (e != hipSuccess) return fail(c, SPVO_ERR_DEVICE, "debug copy failed: %s", hipGetErrorString(e));
   return SPVO_OK;
 }

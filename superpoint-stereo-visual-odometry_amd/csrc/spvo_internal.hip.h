@@ -4,6 +4,8 @@
 //
 //   spvo_core.hip      context and submission-set (SubmitSet) life cycle, tuning switches, launch segments, profiling entry points
 //   engine_file.h      an engine file's bytes -> records, with every check that needs the file alone (plain C++: no HIP)
+//   dev_buf.h          the buffers that grow on demand: the owning pointer (Buf; here DevBuf / PinBuf) and the grow protocol (grow_list; here grow),
+//                      plain C++ with the memory as a policy (no HIP)
 //   spvo_plan.hip      the plan loader (spvo_load_weights) as a list of steps: records -> tensors and ops, storage classes, heads, activations,
 //                      the part of preparing a layer that every engine kind shares, placement; choose_variant, free_plan
 //   spvo_net_f32.hip   FP32 engines: what the loader prepares of a layer (Winograd choice, packers, the fused tail of FP32 / FP16 engines), direct +
@@ -43,12 +45,28 @@
 #include "engine_file.h"
 
 #pragma GCC visibility push(hidden)
+#include "dev_buf.h"   // (inside the hidden region: its types name no exported symbol)
 namespace spvo { struct BriskLongPair; struct BriskShortPair; }   // brisk.hip.h
 using namespace spvo;
 
 #include "launch_segments.hip.h"
 
 namespace spvo_int {
+
+// where the owned buffers' memory comes from (dev_buf.h): the device's, pinned host memory
+struct DevMem {
+  static constexpr const char *alloc_call = "hipMalloc", *clear_call = "hipMemsetAsync";
+  static int alloc(void **p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+  static void release(void *p) { (void)hipFree(p); }
+  static int clear(void *p, size_t bytes, void *stream) { return (int)hipMemsetAsync(p, 0, bytes, (hipStream_t)stream); }
+};
+struct PinnedMem {
+  static constexpr const char *alloc_call = "hipHostMalloc";
+  static int alloc(void **p, size_t bytes) { return (int)hipHostMalloc(p, bytes); }
+  static void release(void *p) { (void)hipHostFree(p); }
+};
+template <class T> using DevBuf = Buf<T, DevMem>;
+template <class T> using PinBuf = Buf<T, PinnedMem>;
 
 constexpr int RING = 8;          // buffer sets a detector submission owns (network outputs, heat map, NMS state, counters, host mirrors)
 constexpr int MAX_INFLIGHT = 6;  // detector submissions that may be queued at once (< RING - 1: the sets of the pairs just completed still serve their matches and mirrors)
@@ -114,23 +132,23 @@ struct Pending { int stage; hipEvent_t e0, e1; double flops = 0, bytes = 0; };
 struct SlotState {
   int n = 0;
   bool filled = false;         // a submission / call has written (or is writing) this slot
-  int *d_n = nullptr;          // device copy of n (read by kernels enqueued before the host knows n)
+  DevBuf<int> d_n;             // device copy of n (read by kernels enqueued before the host knows n)
   unsigned long long gen = 0;  // bumped whenever the slot is rewritten
 };
 // the slot is being rewritten: it holds nothing, and whatever was matched against its old contents is stale
 inline void slot_rewrite(SlotState &s) { s.filled = false; s.n = 0; ++s.gen; }
 
 struct FeatureSlot : SlotState {
-  int *d_xy = nullptr;      // [cap][2] int
-  float *d_desc = nullptr;  // [cap][256]
-  float *d_sqn = nullptr;   // [cap] squared norms of the descriptors (written by the sampler)
+  DevBuf<int> d_xy;         // [cap][2] int
+  DevBuf<float> d_desc;     // [cap][256]
+  DevBuf<float> d_sqn;      // [cap] squared norms of the descriptors (written by the sampler)
 };
 
 // a classic stereo image's features, resident on the device (spvo_classic_detect -> spvo_match_hamming_slots); the buffers of all
 // binary slots have ONE capacity (spvo_ctx::bin.cap)
 struct BinarySlot : SlotState {
-  OrbKeypoint *d_kp = nullptr;   // [cap] x, y, angle, response, octave
-  uint32_t *d_desc = nullptr;    // [cap][16] allocated for the widest row; the matcher's row format: 8 words back to back for 32-byte rows, 16 for wider ones
+  DevBuf<OrbKeypoint> d_kp;      // [cap] x, y, angle, response, octave
+  DevBuf<uint32_t> d_desc;       // [cap][16] allocated for the widest row; the matcher's row format: 8 words back to back for 32-byte rows, 16 for wider ones
   int row_bytes = 32;            // width of the rows it holds: 32 (the ORB extractor), 64 (BRISK) or 61 (AKAZE: stored in 16 words, bytes 61 .. 63 zero);
                                  // two slots are matched only at one width
 };
@@ -138,9 +156,9 @@ struct BinarySlot : SlotState {
 // a SIFT stereo image's features, resident on the device (spvo_sift_detect_pair -> spvo_match_l2_slots) in the L2 matcher's row format; the
 // buffers of all SIFT slots have ONE capacity (spvo_ctx::sift.slot_cap)
 struct SiftSlot : SlotState {
-  float *d_desc = nullptr;       // [cap][256] 128 integers as float, columns 128.. zero
-  float *d_sqn = nullptr;        // [cap] squared norms (exact integers)
-  SiftSrc *d_src = nullptr;      // [cap] candidate and angle every row came from (spvo_classic_sift_pair: its 24-byte record, a SiftKey, back to back)
+  DevBuf<float> d_desc;          // [cap][256] 128 integers as float, columns 128.. zero
+  DevBuf<float> d_sqn;           // [cap] squared norms (exact integers)
+  DevBuf<SiftSrc> d_src;         // [cap] candidate and angle every row came from (spvo_classic_sift_pair: its 24-byte record, a SiftKey, back to back)
 };
 
 // a match enqueued together with the detector (spvo_set_prematch); the result lives in pinned memory
@@ -171,8 +189,7 @@ struct PrematchCache {
 // matcher wait for, the temporal partner and the call's prematches.  Works on the solver's stream.  One per family of slots (spvo_ctx::bin,
 // spvo_ctx::sift); the protocol that drives it is PairCall (pair_call.hip.h), the only caller of stage and temporal_partner.
 struct PairStage {
-  uint8_t *h_img = nullptr;            // pinned [2][img_cap]: both images of a call, rows packed
-  size_t img_cap = 0;
+  PinBuf<uint8_t> h_img;               // pinned [2][px]: both images of a call, rows packed (px: the largest image so far)
   hipEvent_t ev_feat = nullptr, ev_match = nullptr;   // features of the last call final / its prematches landed
   int last_slot_l = -1;                // left slot of the previous call (temporal partner)
   PrematchCache mcache;
@@ -189,14 +206,14 @@ struct PairOut { int *n; void *kp; void *desc; int cap; };
 template <class T> inline PairOut pair_out(T *o) { return PairOut{&o->n, o->kp, o->desc, o->cap}; }
 
 struct MatchScratch {         // one set per concurrently enqueued match
-  float *d_na = nullptr, *d_nb = nullptr, *d_best_d2 = nullptr;
-  float *d_dt = nullptr;      // [cap][match_ldt(cap)] approximate squared distances of every pair (K12a -> K12b; the fp8 shortlist mode)
-  int2 *d_cand = nullptr;     // [cap][nt][MATCH_C] a tile's survivors per query row (fused K12a -> K12m), nt = ceil(cap / 128)
-  int4 *d_meta = nullptr;     // [cap][nt] survivor count and the two smallest upper bounds per (row, tile)
-  int *d_best_idx = nullptr;
-  unsigned long long *d_train_best = nullptr;
-  unsigned char *d_a8 = nullptr, *d_b8 = nullptr;   // fp8 copies of both sides (spvo_set_match_fp8)
-  float2 *d_qa8 = nullptr, *d_qb8 = nullptr;        // [cap] {|x - x8|, |x8|} per row of those copies: the certificate of the exact second pass
+  DevBuf<float> d_na, d_nb, d_best_d2;
+  DevBuf<float> d_dt;         // [cap][match_ldt(cap)] approximate squared distances of every pair (K12a -> K12b; the fp8 shortlist mode)
+  DevBuf<int2> d_cand;        // [cap][nt][MATCH_C] a tile's survivors per query row (fused K12a -> K12m), nt = ceil(cap / 128)
+  DevBuf<int4> d_meta;        // [cap][nt] survivor count and the two smallest upper bounds per (row, tile)
+  DevBuf<int> d_best_idx;
+  DevBuf<unsigned long long> d_train_best;
+  DevBuf<unsigned char> d_a8, d_b8;                 // fp8 copies of both sides (spvo_set_match_fp8)
+  DevBuf<float2> d_qa8, d_qb8;                      // [cap] {|x - x8|, |x8|} per row of those copies: the certificate of the exact second pass
   int2 *d_out = nullptr;      // packed result, points into spvo_ctx::d_match_out
 };
 
@@ -318,27 +335,26 @@ struct spvo_ctx {
   int last_batch = 0;
 
   // post-processing buffers
-  float *d_dense_in = nullptr;   // [B][H][W] staging for spvo_forward
-  float *d_det_dense = nullptr;  // [B][65][Hc][Wc]
+  DevBuf<float> d_dense_in;      // [B][H][W] staging for spvo_forward
+  DevBuf<float> d_det_dense;     // [B][65][Hc][Wc]
   int surv_cap = 0;
   int nms_first = 4;             // NMS launches enqueued with a submission: nms_first - 1 round launches (4 in-kernel rounds each) + the finishing kernel; what that leaves undecided is continued by the host (nms_settle)
-  uint8_t *d_img[2] = {nullptr, nullptr};
-  size_t img_cap = 0;
-  uint8_t *d_resized = nullptr;  // [2][H][W]
-  int *d_tab = nullptr;          // resize tables: xi,xa0,xa1 [W] ; yi,yb0,yb1 [H]
+  DevBuf<uint8_t> d_img[2];      // the stand-alone entry points' staging for two input images, grown with them
+  DevBuf<uint8_t> d_resized;     // [2][H][W]
+  DevBuf<int> d_tab;             // resize tables: xi,xa0,xa1 [W] ; yi,yb0,yb1 [H]
   int tab_rows = -1, tab_cols = -1;
   FeatureSlot slots[N_SLOTS];
-  int *d_xy_tmp = nullptr;       // [cap][2] for spvo_sample_descriptors
-  float *d_desc_tmp = nullptr;   // [cap][256]
+  DevBuf<int> d_xy_tmp;          // [cap][2] for spvo_sample_descriptors
+  DevBuf<float> d_desc_tmp;      // [cap][256]
   int last_slot_l = -1;          // left slot of the previous submission (temporal partner)
 
   // matching scratch
   int match_cap = 0;
-  float *d_ma = nullptr, *d_mb = nullptr;
+  DevBuf<float> d_ma, d_mb;
   MatchScratch ms[2][2];         // [tail stream][stereo, temporal]
-  int2 *d_match_out = nullptr;   // [2][cap]: both jobs' results leave in one copy
-  int2 *h_match_tmp = nullptr;   // pinned [cap] for the synchronous entry points
-  int *d_counters_all = nullptr; // [RING sets + 1 stand-alone block][2 images][NMS_COUNTER_INTS]: ONE zeroed allocation (a tail zeroes the block of the set behind it)
+  DevBuf<int2> d_match_out;      // [2][cap]: both jobs' results leave in one copy
+  PinBuf<int2> h_match_tmp;      // pinned [cap] for the synchronous entry points
+  DevBuf<int> d_counters_all;    // [RING sets + 1 stand-alone block][2 images][NMS_COUNTER_INTS]: ONE zeroed allocation (a tail zeroes the block of the set behind it)
   int *d_counters_alone = nullptr;   // ... its last block: the stand-alone entry points' (standalone(), below)
   SubmitSet sets[RING];          // submission n works in sets[n % RING]
   size_t img_cap_r = 0;          // bytes per image in the sets' h_img / d_img
@@ -351,52 +367,55 @@ struct spvo_ctx {
 
   // odometry scratch
   int odo_cap = 0, ransac_cap = 0, obs_cap = 0;
-  double *d_P = nullptr;         // Pl[12], Pr[12], K[9], prior[6], start[7]
-  float *d_pts_a = nullptr, *d_pts_b = nullptr, *d_xyz = nullptr;
-  RansacWork rw{};
-  ObsDev *d_obs = nullptr;
-  RefineOut *d_refine = nullptr;
+  DevBuf<double> d_P;            // Pl[12], Pr[12], K[9], prior[6], start[7]
+  DevBuf<float> d_pts_a, d_pts_b, d_xyz;
+  struct RansacBufs {            // RansacWork's buffers, and the record the kernels take of them
+    DevBuf<int> counts, inliers;
+    DevBuf<double> poses, result;
+    RansacWork work() const { return RansacWork{counts, poses, result, inliers}; }
+  } rw;
+  DevBuf<ObsDev> d_obs;
+  DevBuf<RefineOut> d_refine;
   // ORB detector / extractor of the classic front end (orb.hip.h): buffers grow on demand
   struct OrbBufs {
     size_t pyr_cap = 0;       // bytes per pyramid buffer (all levels side by side), key / rank entries, resize-table ints the buffers hold:
     size_t key_cap = 0;       // each is compared with what an image NEEDS (they depend on rows and cols separately, not on rows x cols)
     size_t tab_cap = 0;
     int kp_cap = 0;
-    uint8_t *im = nullptr, *score = nullptr, *blur = nullptr, *src = nullptr;   // im: all pyramid levels back to back
-    float *tmp = nullptr, *pattern = nullptr, *taps = nullptr;
-    unsigned long long *keys = nullptr;
-    int *rank = nullptr, *out_xy = nullptr, *counters = nullptr, *tab = nullptr;
-    signed char *disc = nullptr;
-    OrbKeypoint *kps = nullptr;
-    uint8_t *desc = nullptr;
-    size_t src_cap = 0;
+    DevBuf<uint8_t> im, score, blur, src;   // im: all pyramid levels back to back; src: the strided upload's staging, of its own size
+    DevBuf<float> tmp, pattern, taps;
+    DevBuf<unsigned long long> keys;
+    DevBuf<int> rank, out_xy, counters, tab;
+    DevBuf<signed char> disc;
+    DevBuf<OrbKeypoint> kps;
+    DevBuf<uint8_t> desc;
     int tab_rows = 0, tab_cols = 0;   // image size the resize tables in `tab` belong to
   } orb;
   // Shi-Tomasi / FAST detectors and the ORB extractor for given keypoints (classic_detect.hip.h): one image resident at a time,
   // buffers grow with the image (per-pixel ones with rows x cols, the state map with its padded shape) and the keypoint list
   struct ClassicBufs {
-    size_t px_cap = 0, state_cap = 0, src_cap = 0;
+    size_t px_cap = 0, state_cap = 0;
     int kp_cap = 0;
     int rows = 0, cols = 0;               // shape of the image in `im` (0: none resident)
     unsigned image_gen = 0;               // bumped whenever `im` is about to receive another image (cls_ensure): who caches results about `im` compares it
     int state_rows = 0, state_cols = 0;   // shape the state map's padding was cleared for
-    uint8_t *im = nullptr, *score = nullptr, *blur = nullptr, *src = nullptr, *state = nullptr, *desc = nullptr;
-    float *tmp = nullptr, *lam = nullptr, *xy = nullptr, *resp = nullptr;
-    unsigned long long *keys = nullptr;
-    int *rank = nullptr, *cand = nullptr, *counters = nullptr, *kp_xy = nullptr;
-    OrbKeypoint *kps = nullptr;
+    DevBuf<uint8_t> im, score, blur, src, state, desc;
+    DevBuf<float> tmp, lam, xy, resp;
+    DevBuf<unsigned long long> keys;
+    DevBuf<int> rank, cand, counters, kp_xy;
+    DevBuf<OrbKeypoint> kps;
     int oct_cap = 0;                      // spvo_orb_describe_octaves: rows its three buffers hold -- records (cx, cy, level) in output order,
-    int *oct_rec = nullptr;               // the directions and the 32-byte rows
-    float *oct_angle = nullptr;
-    uint8_t *oct_desc = nullptr;
+    DevBuf<int> oct_rec;                  // the directions and the 32-byte rows
+    DevBuf<float> oct_angle;
+    DevBuf<uint8_t> oct_desc;
     // the device link of orb_link.hip.h (spvo_brisk_orb_pair, spvo_akaze_orb_pair, spvo_orb_octaves_link_debug): `lnk_cap` rows of source
     // indices, (cx, cy, level) records and directions, the counts (ORB_LINK_*), and the test hook's own list and rows
     int lnk_cap = 0, lnk_src_cap = 0;
-    int *lnk_kept = nullptr, *lnk_rec = nullptr, *lnk_cnt = nullptr, *lnk_src = nullptr, *lnk_keep = nullptr;
-    float *lnk_angle = nullptr;
-    uint8_t *lnk_desc = nullptr;
-    uint8_t *pre_out = nullptr;           // spvo_preprocess of a context without an engine (the classic front end at a fixed input size): resized image,
-    int *pre_tab = nullptr;               // resize tables of the crop pre_crop_rows x pre_crop_cols
+    DevBuf<int> lnk_kept, lnk_rec, lnk_cnt, lnk_src, lnk_keep;
+    DevBuf<float> lnk_angle;
+    DevBuf<uint8_t> lnk_desc;
+    DevBuf<uint8_t> pre_out;              // spvo_preprocess of a context without an engine (the classic front end at a fixed input size): resized image,
+    DevBuf<int> pre_tab;                  // resize tables of the crop pre_crop_rows x pre_crop_cols
     int pre_crop_rows = 0, pre_crop_cols = 0;
     int last_counters[16] = {0};          // the counter block of the last spvo_gftt_detect (rounds, undecided after each launch)
   } cls;
@@ -406,34 +425,33 @@ struct spvo_ctx {
     int cap = 0;
     BinarySlot slots[N_BIN_SLOTS];
     PairStage pair;                      // (its prematches' slot numbers are BINARY slots)
-    OrbKeypoint *h_kp = nullptr;         // pinned [2][cap]      what the finishing kernel of an image writes for the host:
-    uint8_t *h_desc = nullptr;           // pinned [2][cap][64]  keypoint records, descriptors ([2][cap][32] in its front part for the 32-byte kinds),
-    int *h_n = nullptr;                  // pinned [2][4]        {rows found, overflow flag of the detector}; behind them [2][4] the contrast factors spvo_akaze_detect_pair reports
-    BriskDetKeypoint *h_bkp = nullptr;   // pinned [2][cap]      spvo_brisk_detect_pair's records (24 bytes: they carry a size), in the place of h_kp
-    AkazeKp *h_akp = nullptr;            // pinned [2][cap]      spvo_akaze_detect_pair's records (28 bytes: size and level), in the place of h_kp
-    int *d_cnt = nullptr;                // [2][CLS_COUNTER_INTS] the extractor's counter block per image (0: kept in all, 2: kept and described)
-    int *d_kxy = nullptr;                // [cap][2] the kept keypoints of a Shi-Tomasi / FAST image (cls_compact_kernel), ...
-    float *d_kresp = nullptr;            // [cap]    ... and the detector's responses of those (also brisk_compact_list_kernel's)
-    unsigned long long *d_vote = nullptr;   // [cap] cross-check votes
-    int2 *h_match = nullptr;             // pinned [3][cap]: the two prematches, the synchronous call
+    PinBuf<OrbKeypoint> h_kp;            // pinned [2][cap]      what the finishing kernel of an image writes for the host:
+    PinBuf<uint8_t> h_desc;              // pinned [2][cap][64]  keypoint records, descriptors ([2][cap][32] in its front part for the 32-byte kinds),
+    PinBuf<int> h_n;                     // pinned [2][4]        {rows found, overflow flag of the detector}; behind them [2][4] the contrast factors spvo_akaze_detect_pair reports
+    PinBuf<BriskDetKeypoint> h_bkp;      // pinned [2][cap]      spvo_brisk_detect_pair's records (24 bytes: they carry a size), in the place of h_kp
+    PinBuf<AkazeKp> h_akp;               // pinned [2][cap]      spvo_akaze_detect_pair's records (28 bytes: size and level), in the place of h_kp
+    DevBuf<int> d_cnt;                   // [2][CLS_COUNTER_INTS] the extractor's counter block per image (0: kept in all, 2: kept and described)
+    DevBuf<int> d_kxy;                   // [cap][2] the kept keypoints of a Shi-Tomasi / FAST image (cls_compact_kernel), ...
+    DevBuf<float> d_kresp;               // [cap]    ... and the detector's responses of those (also brisk_compact_list_kernel's)
+    DevBuf<unsigned long long> d_vote;   // [cap] cross-check votes
+    PinBuf<int2> h_match;                // pinned [3][cap]: the two prematches, the synchronous call
   } bin;
   // BRISK extractor for given keypoints (brisk.hip.h) on the image resident in `cls`: the pattern tables (uploaded on the first call), the
   // integral image, the keypoint list with its results and their pinned mirrors; buffers grow on demand
   struct BriskBufs {
-    float *points = nullptr;              // [64][1024][60][3] x, y, sigma
-    BriskLongPair *long_pairs = nullptr;
-    BriskShortPair *short_pairs = nullptr;
+    DevBuf<float> points;                 // [64][1024][60][3] x, y, sigma
+    DevBuf<BriskLongPair> long_pairs;
+    DevBuf<BriskShortPair> short_pairs;
     bool tables_ready = false;            // set last: every table above is on the device, cnt and h_n exist
-    int *cnt = nullptr;                   // [4]: kept keypoints
-    int *integ = nullptr;                 // (rows + 1) x (cols + 1)
-    size_t integ_cap = 0;
+    DevBuf<int> cnt;                      // [4]: kept keypoints
+    DevBuf<int> integ;                    // (rows + 1) x (cols + 1), or what a larger image before needed
     int kp_cap = 0, v0_cap = 0;           // rows the keypoint buffers / the values0 buffers (test hook: allocated on demand) hold
-    float *xy = nullptr, *size = nullptr, *angle = nullptr;
-    int *kept = nullptr, *kscale = nullptr, *values0 = nullptr;
-    uint8_t *desc = nullptr;
-    int *h_n = nullptr, *h_kept = nullptr, *h_values0 = nullptr;   // pinned: what brisk_finish_kernel writes for the host
-    float *h_angle = nullptr;
-    uint8_t *h_desc = nullptr;
+    DevBuf<float> xy, size, angle;
+    DevBuf<int> kept, kscale, values0;
+    DevBuf<uint8_t> desc;
+    PinBuf<int> h_n, h_kept, h_values0;   // pinned: what brisk_finish_kernel writes for the host
+    PinBuf<float> h_angle;
+    PinBuf<uint8_t> h_desc;
   } brisk;
   // BRISK detector (brisk_detect.hip.h) on the image resident in `cls` (its layer 0): layers 1-5, the score maps of all six and the 5-8
   // map of layer 0 (what spvo_brisk_detect_debug_layer serves until the next call), the area taps of the shape, the candidate lists --
@@ -444,12 +462,12 @@ struct spvo_ctx {
     unsigned image_gen = 0;               // ... and belong to the image spvo_ctx::cls held at this generation
     size_t px_cap = 0, tab_cap = 0;       // bytes of pyr / score each; entries of tabs
     int cand_cap = 0;                     // candidates the lists hold (>= what the shape can yield: an interior pixel each)
-    uint8_t *pyr = nullptr, *score = nullptr;
-    BriskAreaTap *tabs = nullptr;
+    DevBuf<uint8_t> pyr, score;
+    DevBuf<BriskAreaTap> tabs;
     std::vector<BriskAreaTap> h_tabs;
-    unsigned long long *keys = nullptr;
-    int *rank = nullptr, *keep = nullptr, *counters = nullptr;
-    BriskDetKeypoint *rec = nullptr, *out = nullptr;
+    DevBuf<unsigned long long> keys;
+    DevBuf<int> rank, keep, counters;
+    DevBuf<BriskDetKeypoint> rec, out;
     BriskDetLayers lv{};
     BriskResizeJob jobs[BRISK_DET_LAYERS]{};   // jobs[i]: layer i from its source (i >= 1)
   } brisk_det;
@@ -463,36 +481,36 @@ struct spvo_ctx {
     unsigned image_gen = 0;               // ... and belong to the image spvo_ctx::cls held at this generation
     size_t plane_cap = 0, scratch_cap = 0, tab_cap = 0;   // floats of planes / scratch; entries of tabs
     int cand_cap = 0;
-    float *planes = nullptr, *scratch = nullptr;
-    BriskAreaTap *tabs = nullptr;
+    DevBuf<float> planes, scratch;
+    DevBuf<BriskAreaTap> tabs;
     std::vector<BriskAreaTap> h_tabs;
     const BriskAreaTap *xtab[AKAZE_MAX_OCTAVES] = {nullptr}, *ytab[AKAZE_MAX_OCTAVES] = {nullptr};   // of octave o from o - 1 (NULL: the exact half)
-    unsigned long long *keys = nullptr;
-    int *rank = nullptr, *stat = nullptr;   // stat: AKAZE_STAT_* (spvo_types.hip.h)
-    AkazeCand *rec = nullptr;
+    DevBuf<unsigned long long> keys;
+    DevBuf<int> rank, stat;                 // stat: AKAZE_STAT_* (spvo_types.hip.h)
+    DevBuf<AkazeCand> rec;
     std::vector<AkazeCand> h_cand;
     AkazeLevels lv{};
     int octaves = 0, nsteps[AKAZE_MAX_LEVELS] = {0};   // nsteps[i]: diffusion steps of the transition i - 1 -> i
     std::vector<float> h_tau;                          // their sizes, transition after transition
     AkazeTaps g0{}, g1{};                              // sigma 1.6 and sigma 1
     float k[AKAZE_MAX_OCTAVES] = {0};                  // the last call's contrast factor per octave
-    AkazeKp *d_kp = nullptr;                           // spvo_akaze_describe (akaze_mldb.hip.h): records in, angles and 61-byte rows out
-    float *d_angle = nullptr;
-    uint8_t *d_desc = nullptr;
+    DevBuf<AkazeKp> d_kp;                              // spvo_akaze_describe (akaze_mldb.hip.h): records in, angles and 61-byte rows out
+    DevBuf<float> d_angle;
+    DevBuf<uint8_t> d_desc;
     int kp_cap = 0;
     std::vector<float> h_angle;                        // host staging of a call's results
     std::vector<uint8_t> h_desc;
     // rule 11 on the device (akaze_suppress.hip.h; spvo_akaze_detect_pair, spvo_akaze_suppress_debug): the list of the first loop and the
     // candidate of every entry, the keep flags, the compacted records with their candidates' indices, and the counts
     int sup_cap = 0;
-    float4 *sup_list = nullptr;
-    int *sup_idx = nullptr, *sup_keep = nullptr, *sup_src = nullptr, *sup_cnt = nullptr;   // sup_cnt: AKAZE_SUP_*
-    AkazeKp *sup_kp = nullptr;
+    DevBuf<float4> sup_list;
+    DevBuf<int> sup_idx, sup_keep, sup_src, sup_cnt;   // sup_cnt: AKAZE_SUP_*
+    DevBuf<AkazeKp> sup_kp;
     // spvo_akaze_brisk_pair: the kept records as the BRISK extractor's chain reads a detector's list (brisk_pair_chain_enqueue) -- records,
     // keep flags, the counter block, the compacted records -- `brk_cap` of each
     int brk_cap = 0;
-    BriskDetKeypoint *brk_rec = nullptr, *brk_crec = nullptr;
-    int *brk_keep = nullptr, *brk_cnt = nullptr;
+    DevBuf<BriskDetKeypoint> brk_rec, brk_crec;
+    DevBuf<int> brk_keep, brk_cnt;
   } akaze;
   // SIFT detector + descriptor of the classic front end (sift.hip.h): the image, its pyramid (all Gaussian and DoG levels: what
   // spvo_sift_debug_level serves until the next call), the candidate and output lists; device buffers grow on demand, the host staging keeps its capacity
@@ -501,17 +519,16 @@ struct spvo_ctx {
     SiftPyr plan{};
     bool gauss_only = false;              // the resident pyramid is spvo_sift_describe's: Gaussian levels only, octave index 0 = octave `first`
     int first = -1;
-    SiftKey *given_kp = nullptr;          // spvo_sift_describe: the caller's records and their rows, `given_cap` of each
-    float *given_desc = nullptr;
+    DevBuf<SiftKey> given_kp;             // spvo_sift_describe: the caller's records and their rows, `given_cap` of each
+    DevBuf<float> given_desc;
     int given_cap = 0;
-    size_t img_cap = 0, pyr_cap = 0;      // bytes / floats
     int cand_cap = 0;                     // candidates, and output rows, the lists hold
-    uint8_t *img = nullptr;
-    float *pyr = nullptr, *desc = nullptr;
-    int4 *cand_pos = nullptr;             // {octave, layer (0: rejected), row, column}
-    float4 *cand_off = nullptr;           // {xi, xr, xc, contrast}
-    int2 *kp = nullptr;                   // {candidate, angle bits}
-    int *counters = nullptr;              // [4]: candidates, output rows
+    DevBuf<uint8_t> img;
+    DevBuf<float> pyr, desc;
+    DevBuf<int4> cand_pos;                // {octave, layer (0: rejected), row, column}
+    DevBuf<float4> cand_off;              // {xi, xr, xc, contrast}
+    DevBuf<int2> kp;                      // {candidate, angle bits}
+    DevBuf<int> counters;                 // [4]: candidates, output rows
     std::vector<int4> h_pos;
     std::vector<float4> h_off;
     std::vector<int2> h_kp;
@@ -520,31 +537,31 @@ struct spvo_ctx {
     std::vector<int> h_order;
     // the ordering stage on the device (sift.hip.h: spvo_sift_detect_pair, spvo_sift_order_debug), `ord_cap` raw rows
     int ord_cap = 0;
-    SiftKey *keys = nullptr;
-    int *sorted = nullptr, *order = nullptr;   // raw row at every sorted position / at every final position
-    int *ord_n = nullptr;                      // [2]: final rows; spvo_sift_order_debug's n
+    DevBuf<SiftKey> keys;
+    DevBuf<int> sorted, order;                 // raw row at every sorted position / at every final position
+    DevBuf<int> ord_n;                         // [2]: final rows; spvo_sift_order_debug's n
     // spvo_sift_detect_pair / spvo_match_l2_slots: the SIFT slots (`slot_cap` rows each), the call's pinned staging and mirrors and the two
     // matches enqueued with the detector (spvo_set_prematch).  Features on the solver's stream, matches where the L2 matcher runs (PostScope).
     int slot_cap = 0;
     SiftSlot slots[N_SIFT_SLOTS];
     PairStage pair;                      // (its prematches' slot numbers are SIFT slots)
-    SiftSrc *h_src = nullptr;            // pinned [2][slot_cap]      what sift_gather_kernel writes for the host: sources (spvo_classic_sift_pair: SiftKey records in each half's front),
-    float *hm_desc = nullptr;            // pinned [2][slot_cap][128] descriptors,
-    int *h_n = nullptr;                  // pinned [2][4]             {final rows, candidates counted, raw rows counted}; behind them [2][4] the contrast factors spvo_akaze_sift_pair reports
-    int2 *h_match = nullptr;             // pinned [2][h_match_cap]: the two prematches (enqueue_matches spaces its jobs by spvo_ctx::match_cap)
+    PinBuf<SiftSrc> h_src;               // pinned [2][slot_cap]      what sift_gather_kernel writes for the host: sources (spvo_classic_sift_pair: SiftKey records in each half's front),
+    PinBuf<float> hm_desc;               // pinned [2][slot_cap][128] descriptors,
+    PinBuf<int> h_n;                     // pinned [2][4]             {final rows, candidates counted, raw rows counted}; behind them [2][4] the contrast factors spvo_akaze_sift_pair reports
+    PinBuf<int2> h_match;                // pinned [2][h_match_cap]: the two prematches (enqueue_matches spaces its jobs by spvo_ctx::match_cap)
     int h_match_cap = 0;
     bool match_pending = false;          // pair.ev_match has been recorded: a later call's kernels wait for it before they rewrite a slot
     // the link behind a detector that reports an octave (spvo_brisk_sift_pair, spvo_akaze_sift_pair, spvo_sift_link_debug): the indices
     // sift_link_compact_kernel keeps, `lnk_cap` of them, its counts {kept, the hook's list length}, and the hook's keep flags
-    int lnk_cap = 0, lnk_keep_cap = 0;
-    int *lnk_kept = nullptr, *lnk_cnt = nullptr, *lnk_keep = nullptr;
+    int lnk_cap = 0;
+    DevBuf<int> lnk_kept, lnk_cnt, lnk_keep;
   } sift;
   // Hamming matcher (classic front end's binary descriptors): rows padded to 16 words
   int ham_cap = 0;
-  uint32_t *d_ham_a = nullptr, *d_ham_b = nullptr;
-  int *d_ham_idx = nullptr;
-  float *d_ham_dist = nullptr;
-  unsigned long long *d_ham_vote = nullptr;
+  DevBuf<uint32_t> d_ham_a, d_ham_b;
+  DevBuf<int> d_ham_idx;
+  DevBuf<float> d_ham_dist;
+  DevBuf<unsigned long long> d_ham_vote;
   // fused solve: one packed input, one packed result -- per buffer SET: up to three solves may be pending (spvo_solve_submit .. _wait), a frame's
   // chain enqueued before the previous frames' have been collected; the sets rotate, so the previous solve's points (prev_index) sit in the set before.
   // The TAIL kernel of a solve submitted with `late_prior` is held back (tail_deferred) and goes out in ONE launch with the hypotheses of the next
@@ -555,19 +572,22 @@ struct spvo_ctx {
   int tail_slot = -1;                     // ... its set, and its arguments (SolveTailArgs, odometry.hip.h: plain data)
   alignas(16) char tail_args[320];
   int solve_fuse = 1;                     // tuning "solve_fuse" (read at spvo_create): 0 = every tail is launched with its own submission
-  int *x_counts[SOLVE_BUFS] = {};         // RANSAC scratch of sets 1 .. (set 0: rw): a solve's hypotheses are written while its predecessor's are read
-  double *x_poses[SOLVE_BUFS] = {};
-  ObsDev *x_obs[SOLVE_BUFS] = {};         // residual blocks of sets 1 .. (set 0: d_obs)
+  DevBuf<int> x_counts[SOLVE_BUFS];       // RANSAC scratch of sets 1 .. (set 0: rw): a solve's hypotheses are written while its predecessor's are read
+  DevBuf<double> x_poses[SOLVE_BUFS];
+  DevBuf<ObsDev> x_obs[SOLVE_BUFS];       // residual blocks of sets 1 .. (set 0: d_obs)
   struct SolvePending { int n = 0, refinement_degree = 0, slot = 0, frame_count = 0; bool late = false; double rvec[3] = {0, 0, 0}, tvec[3] = {0, 0, 0}; };
   std::deque<SolvePending> solve_q;     // oldest first, at most SOLVE_SLOTS
   int solve_next_slot = 0;
   int solve_last_slot = -1, solve_last_n = 0;   // the most recent submission: where its triangulated points are and how many
   hipEvent_t ev_solve[SOLVE_BUFS] = {};
   int solve_cap = 0;
-  char *d_solve_in[SOLVE_BUFS] = {}, *h_solve_in[SOLVE_BUFS] = {};      // 64 doubles + 12*cap words
-  double *d_solve_res[SOLVE_BUFS] = {}, *h_solve_res[SOLVE_BUFS] = {};  // ransac[8] gate[16] refine[12] + pad
-  char *d_solve_o[SOLVE_BUFS] = {}, *h_solve_o[SOLVE_BUFS] = {};        // xyz [3n] floats, inliers [n] ints
-  int *d_ctl = nullptr;                   // [SOLVE_BUFS][4]
+  struct SolveSet {                       // one of the SOLVE_BUFS sets, device and pinned
+    DevBuf<char> d_in, d_o;               // 64 doubles + 12*cap words / xyz [3n] floats, inliers [n] ints
+    DevBuf<double> d_res;                 // ransac[8] gate[16] refine[12] + pad
+    PinBuf<char> h_in, h_o;
+    PinBuf<double> h_res;
+  } solve_set[SOLVE_BUFS];
+  DevBuf<int> d_ctl;                      // [SOLVE_BUFS][4]
 
   // profiling
   bool prof = false;
@@ -597,6 +617,9 @@ int fail(spvo_ctx *c, int code, const char *fmt, ...);
                   __FILE__, __LINE__);                                                       \
   } while (0)
 
+// raw device / pinned pointers, for what is not an owned buffer: the engine plan (Tensor::d / dr[], the Op weight pointers: free_plan),
+// SubmitSet's members (set_alloc, set_release*).  Everything else that grows on demand or is allocated on first use is a DevBuf / PinBuf
+// and goes through grow(), below.
 template <typename T>
 int dev_alloc(spvo_ctx *c, T **p, size_t count, bool zero = true) {
   HIP_TRY(c, hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T)));
@@ -629,18 +652,31 @@ void host_free(T *&p, Rest *&...rest) {
   if constexpr (sizeof...(rest) > 0) host_free(rest...);
 }
 
+// ---- the grow protocol of the owned buffers (DevBuf / PinBuf), written once.  Every block that re-allocates a group says what to wait
+// for first -- a stream, the whole device, nothing -- and lists its buffers, each zeroed() or plain(); grow() waits, frees every
+// buffer of the list, allocates every one, and waits for the network stream if any was zeroed (the clearing runs there).  A failed
+// allocation leaves every buffer of the list empty (dev_buf.h) and answers SPVO_ERR_DEVICE with the failing call's text -- a context
+// that spvo_destroy and a later call can still handle, provided the caller set its capacity fields to 0 before the call.
+// The order of a list is the order of allocation, and that decides where the buffers land: a list is not re-sorted.
+struct GrowWait { hipStream_t stream = nullptr; };
+inline GrowWait wait_for(hipStream_t s) { return GrowWait{s}; }
+inline GrowWait wait_for_nothing() { return GrowWait{}; }
+template <class T> GrowEntry zeroed(DevBuf<T> &b, size_t count) { return grow_entry<true>(b, count); }
+template <class T, class P> GrowEntry plain(Buf<T, P> &b, size_t count) { return grow_entry<false>(b, count); }
+inline int grow(spvo_ctx *c, GrowWait w, const std::vector<GrowEntry> &list) {
+  if (w.stream) HIP_TRY(c, hipStreamSynchronize(w.stream));
+  const GrowResult r = grow_list(list, c->stream);
+  if (r.code) return fail(c, SPVO_ERR_DEVICE, "%s failed: %s (%s:%d)", r.call, hipGetErrorString((hipError_t)r.code), __FILE__, __LINE__);
+  if (r.cleared) HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SPVO_OK;
+}
+
 inline int PairStage::ensure(spvo_ctx *c, size_t px) {
   if (!ev_feat) {
     HIP_TRY(c, hipEventCreateWithFlags(&ev_feat, hipEventDisableTiming));
     HIP_TRY(c, hipEventCreateWithFlags(&ev_match, hipEventDisableTiming));
   }
-  if (px > img_cap) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream2));
-    host_free(h_img);
-    img_cap = 0;
-    HIP_TRY(c, hipHostMalloc((void **)&h_img, 2 * px));
-    img_cap = px;
-  }
+  if (2 * px > h_img.count()) return grow(c, wait_for(c->stream2), {plain(h_img, 2 * px)});
   return SPVO_OK;
 }
 inline void PairStage::stage(const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride) {
@@ -650,9 +686,7 @@ inline void PairStage::stage(const uint8_t *img_l, const uint8_t *img_r, int row
     for (int r = 0; r < rows; ++r) std::memcpy(h_img + k * px + (size_t)r * cols, imgs[k] + (size_t)r * stride, cols);
 }
 inline void PairStage::release() {
-  host_free(h_img);
   for (hipEvent_t *e : {&ev_feat, &ev_match}) if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }
-  img_cap = 0;
 }
 
 // the synchronous entry points that work in the submissions' buffers refuse to run beside them; a failed wait / record: "`what` failed"
@@ -787,8 +821,8 @@ int run_network(spvo_ctx *c, int batch);
 void resize_tables(int dst_w, int src_w, int dst_h, int src_h, std::vector<int> &out);
 // ---- spvo_classic.hip: spvo_preprocess of a context without an engine (d_img[0] -> cls.pre_out, enqueued on the network stream)
 int classic_preprocess(spvo_ctx *c, const CropGeom &g, size_t stride);
-void classic_release(spvo_ctx *c);   // frees spvo_ctx::bin (spvo_destroy)
-void classic_release_slots(spvo_ctx *c);   // ... the part of it that is sized by the slot capacity
+void classic_release(spvo_ctx *c);   // what spvo_ctx::bin holds besides memory: its events (spvo_destroy)
+void classic_release_slots(spvo_ctx *c);   // every binary slot emptied and back to 32-byte rows, the prematches forgotten
 // a host image (strided view) becomes the resident image of spvo_ctx::cls, every buffer of it grown to the shape (enqueued on the solver's stream)
 int classic_upload_image(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride);
 // a staged image (pinned, rows packed: PairCall::image) becomes the resident image of spvo_ctx::cls, behind classic_image_ensure for its shape
@@ -823,16 +857,13 @@ void orb_link_finish_brisk(spvo_ctx *c, const BriskDetKeypoint *src, const int *
 void orb_link_finish_akaze(spvo_ctx *c, const AkazeKp *src, const int *stat, int cand_cap, int cap, OrbKeypoint *d_kp, const uint32_t *d_desc, int *d_n, int *h_n, int *h_k,
                            AkazeKp *h_kp, uint8_t *h_desc);
 // ---- spvo_brisk.hip
-void brisk_release(spvo_ctx *c);     // frees spvo_ctx::brisk (spvo_destroy)
 // what spvo_brisk_describe refuses of an image, for every entry point that runs the extractor (`who` names it in the error text)
 int brisk_check_image(spvo_ctx *c, const char *who, int rows, int cols);
 // ---- spvo_brisk_detect.hip
-void brisk_detect_release(spvo_ctx *c);   // frees spvo_ctx::brisk_det (spvo_destroy)
 // brisk_detect_ref.py choice 3: the taps of one axis of cv::resize(INTER_AREA)'s general path; false if a run is longer than BRISK_DET_TAPS
 // or not contiguous (cannot happen for ratios below 3)
 bool brisk_area_tab(int ssize, int dsize, BriskAreaTap *out);
 // ---- spvo_akaze.hip
-void akaze_release(spvo_ctx *c);   // frees spvo_ctx::akaze (spvo_destroy)
 // The extractor as a link of spvo_classic_detect's chain (kinds SPVO_CLASSIC_*_BRISK).  brisk_chain_ensure: the tables, the integral image
 // of a rows x cols image and the keypoint buffers for `cap` rows.  brisk_chain_enqueue, on the solver's stream behind a detector that left
 // its list in spvo_ctx::cls (xy, resp, counters[2]): integral image, border rule of keypoints of ONE `size` as a compaction that keeps at
@@ -853,7 +884,7 @@ int brisk_chain_enqueue(spvo_ctx *c, int rows, int cols, float size, int cap, in
 int brisk_pair_chain_enqueue(spvo_ctx *c, int rows, int cols, int cap, const BriskDetKeypoint *rec, const int *keep, const int *det_counters, int det_cap, BriskDetKeypoint *crec,
                              const ChainOut &o, BriskDetKeypoint *h_kp);
 // ---- spvo_sift.hip
-void sift_release(spvo_ctx *c);      // frees spvo_ctx::sift (spvo_destroy)
+void sift_release(spvo_ctx *c);      // what spvo_ctx::sift holds besides memory: its events (spvo_destroy)
 // The SIFT extractor as a link behind a detector that left records with an octave on the device (sift.hip.h: SiftLinkIO;
 // spvo_brisk_sift_pair, spvo_akaze_sift_pair).  sift_link_pair is the whole call around the detector -- a PairCall on the SIFT slots
 // (pair_call.hip.h) with the link's allocations and chains -- so that neither detector object needs the SIFT unit's internals; the detector

@@ -9,43 +9,26 @@ int ensure_match(spvo_ctx *c, int na, int nb) {
   if (need <= c->match_cap) return SPVO_OK;
   const int cap = std::max(need, std::max(c->cfg.max_keypoints, 1024));
   HIP_TRY(c, hipDeviceSynchronize());
-  // every pointer is cleared as it is freed and the capacity drops to 0 first: an allocation failure further down leaves a
-  // context that spvo_destroy (and a later, smaller request) can still handle
+  // the capacity drops to 0 first: an allocation failure further down leaves a context that spvo_destroy (and a later, smaller
+  // request) can still handle
   c->match_cap = 0;
-  dev_free(c->d_ma, c->d_mb, c->d_match_out);
-  for (auto &set : c->ms)
-    for (auto &m : set) {
-      dev_free(m.d_na, m.d_nb, m.d_best_d2, m.d_dt, m.d_cand, m.d_meta, m.d_best_idx, m.d_train_best, m.d_a8, m.d_b8, m.d_qa8, m.d_qb8);
-      m.d_out = nullptr;
-    }
   for (SubmitSet &s : c->sets) set_release_match(s);
-  host_free(c->h_match_tmp);
-  int rc;
-  if ((rc = dev_alloc(c, &c->d_ma, (size_t)cap * MATCH_D))) return rc;
-  if ((rc = dev_alloc(c, &c->d_mb, (size_t)cap * MATCH_D))) return rc;
-  if ((rc = dev_alloc(c, &c->d_match_out, (size_t)4 * cap))) return rc;
-  for (int k4 = 0; k4 < 4; ++k4) {
-    const int k = k4 & 1;
-    MatchScratch &m = c->ms[k4 >> 1][k];
-    if ((rc = dev_alloc(c, &m.d_na, cap + 4))) return rc;   // K12b reads the norms four at a time
-    if ((rc = dev_alloc(c, &m.d_nb, cap + 4))) return rc;
-    if ((rc = dev_alloc(c, &m.d_best_d2, (size_t)cap * 2))) return rc;
-    if ((rc = dev_alloc(c, &m.d_dt, (size_t)cap * match_ldt(cap)))) return rc;
-    const size_t nt = (size_t)(cap + MATCH_TT - 1) / MATCH_TT;
-    if ((rc = dev_alloc(c, &m.d_cand, (size_t)cap * nt * MATCH_C))) return rc;
-    if ((rc = dev_alloc(c, &m.d_meta, (size_t)cap * nt))) return rc;
-    if ((rc = dev_alloc(c, &m.d_best_idx, (size_t)cap * 2))) return rc;
-    if ((rc = dev_alloc(c, &m.d_train_best, cap))) return rc;
-    if ((rc = dev_alloc(c, &m.d_a8, (size_t)cap * MATCH_D))) return rc;
-    if ((rc = dev_alloc(c, &m.d_b8, (size_t)cap * MATCH_D))) return rc;
-    if ((rc = dev_alloc(c, &m.d_qa8, cap))) return rc;
-    if ((rc = dev_alloc(c, &m.d_qb8, cap))) return rc;
-    m.d_out = c->d_match_out + (size_t)k4 * cap;
-  }
+  std::vector<GrowEntry> list{zeroed(c->d_ma, (size_t)cap * MATCH_D), zeroed(c->d_mb, (size_t)cap * MATCH_D), zeroed(c->d_match_out, (size_t)4 * cap)};
+  const size_t nt = (size_t)(cap + MATCH_TT - 1) / MATCH_TT;
+  for (auto &set : c->ms)
+    for (MatchScratch &m : set) {
+      m.d_out = nullptr;
+      list.insert(list.end(), {zeroed(m.d_na, cap + 4), zeroed(m.d_nb, cap + 4),   // K12b reads the norms four at a time
+                               zeroed(m.d_best_d2, (size_t)cap * 2), zeroed(m.d_dt, (size_t)cap * match_ldt(cap)), zeroed(m.d_cand, (size_t)cap * nt * MATCH_C),
+                               zeroed(m.d_meta, (size_t)cap * nt), zeroed(m.d_best_idx, (size_t)cap * 2), zeroed(m.d_train_best, cap), zeroed(m.d_a8, (size_t)cap * MATCH_D),
+                               zeroed(m.d_b8, (size_t)cap * MATCH_D), zeroed(m.d_qa8, cap), zeroed(m.d_qb8, cap)});
+    }
+  c->h_match_tmp.reset();   // (re-allocated behind the sets' mirrors, below)
+  if (int rc = grow(c, wait_for_nothing(), list)) return rc;
+  for (int k4 = 0; k4 < 4; ++k4) c->ms[k4 >> 1][k4 & 1].d_out = c->d_match_out + (size_t)k4 * cap;
   for (SubmitSet &s : c->sets) HIP_TRY(c, hipHostMalloc((void **)&s.h_match_out, (size_t)2 * cap * sizeof(int2)));
-  HIP_TRY(c, hipHostMalloc((void **)&c->h_match_tmp, (size_t)cap * sizeof(int2)));
+  if (int rc = grow(c, wait_for_nothing(), {plain(c->h_match_tmp, cap)})) return rc;
   c->match_cap = cap;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
   return SPVO_OK;
 }
 
@@ -229,15 +212,11 @@ int spvo_match_hamming(spvo_ctx *c, const uint8_t *desc_a, int na, const uint8_t
   const int nw = desc_bytes <= 32 ? 8 : 16;
   const int need = std::max(na, nb);
   if (need > c->ham_cap) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream2));
-    dev_free(c->d_ham_a, c->d_ham_b, c->d_ham_idx, c->d_ham_dist, c->d_ham_vote);
     c->ham_cap = 0;
     const int cap = std::max(need, 2048);
-    int rc;
-    if ((rc = dev_alloc(c, &c->d_ham_a, (size_t)cap * 16)) || (rc = dev_alloc(c, &c->d_ham_b, (size_t)cap * 16)) || (rc = dev_alloc(c, &c->d_ham_idx, cap)) ||
-        (rc = dev_alloc(c, &c->d_ham_dist, cap)) || (rc = dev_alloc(c, &c->d_ham_vote, cap)))
+    if (int rc = grow(c, wait_for(c->stream2), {zeroed(c->d_ham_a, (size_t)cap * 16), zeroed(c->d_ham_b, (size_t)cap * 16), zeroed(c->d_ham_idx, cap), zeroed(c->d_ham_dist, cap),
+                                                zeroed(c->d_ham_vote, cap)}))
       return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
     c->ham_cap = cap;
   }
   // rows zero-padded to nw words: padding bits are equal on both sides and add nothing to a distance

@@ -65,28 +65,16 @@ int sift_ensure(spvo_ctx *c, int rows, int cols, size_t pyr_floats, int cand_cap
   auto &s = c->sift;
   hipStream_t st = c->stream2;
   const size_t px = (size_t)rows * cols;
-  if (px > s.img_cap || pyr_floats > s.pyr_cap) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    dev_free(s.img, s.pyr);
-    const size_t npx = std::max(px, s.img_cap), npyr = std::max(pyr_floats, s.pyr_cap);
-    s.img_cap = s.pyr_cap = 0;   // a failed allocation below leaves a context that spvo_destroy and a later call can still handle
-    int rc;
-    if ((rc = dev_alloc(c, &s.img, npx, false)) || (rc = dev_alloc(c, &s.pyr, npyr, false))) return rc;
-    s.img_cap = npx; s.pyr_cap = npyr;
+  if (px > s.img.count() || pyr_floats > s.pyr.count()) {
+    const size_t npx = std::max(px, s.img.count()), npyr = std::max(pyr_floats, s.pyr.count());
+    if (int rc = grow(c, wait_for(st), {plain(s.img, npx), plain(s.pyr, npyr)})) return rc;
   }
   if (cand_cap > s.cand_cap) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    dev_free(s.cand_pos, s.cand_off, s.kp, s.desc);
     s.cand_cap = 0;
-    int rc;
-    if ((rc = dev_alloc(c, &s.cand_pos, cand_cap, false)) || (rc = dev_alloc(c, &s.cand_off, cand_cap, false)) || (rc = dev_alloc(c, &s.kp, cand_cap, false)) ||
-        (rc = dev_alloc(c, &s.desc, (size_t)cand_cap * 128, false)))
-      return rc;
+    if (int rc = grow(c, wait_for(st), {plain(s.cand_pos, cand_cap), plain(s.cand_off, cand_cap), plain(s.kp, cand_cap), plain(s.desc, (size_t)cand_cap * 128)})) return rc;
     s.cand_cap = cand_cap;
   }
-  if (!s.counters) {
-    if (int rc = dev_alloc(c, &s.counters, 4, false)) return rc;
-  }
+  if (!s.counters) return grow(c, wait_for_nothing(), {plain(s.counters, 4)});
   return SPVO_OK;
 }
 
@@ -164,15 +152,11 @@ spvo_sift_keypoint sift_record(const int4 &p, const float4 &f, int angle_bits) {
 // the ordering stage's scratch for `n` raw rows
 int sift_order_ensure(spvo_ctx *c, int n) {
   auto &s = c->sift;
-  if (!s.ord_n) {
-    if (int rc = dev_alloc(c, &s.ord_n, 2, false)) return rc;
-  }
+  if (!s.ord_n)
+    if (int rc = grow(c, wait_for_nothing(), {plain(s.ord_n, 2)})) return rc;
   if (n <= s.ord_cap) return SPVO_OK;
-  HIP_TRY(c, hipStreamSynchronize(c->stream2));
-  dev_free(s.keys, s.sorted, s.order);
   s.ord_cap = 0;
-  int rc;
-  if ((rc = dev_alloc(c, &s.keys, n, false)) || (rc = dev_alloc(c, &s.sorted, n, false)) || (rc = dev_alloc(c, &s.order, n, false))) return rc;
+  if (int rc = grow(c, wait_for(c->stream2), {plain(s.keys, n), plain(s.sorted, n), plain(s.order, n)})) return rc;
   s.ord_cap = n;
   return SPVO_OK;
 }
@@ -203,14 +187,10 @@ int sift_enqueue_order(spvo_ctx *c, SiftSlot &slot, int k) {
   return SPVO_OK;
 }
 
-// everything sized by the slot capacity; the slots are empty afterwards
+// what sift_slots_ensure forgets when it re-allocates everything the slot capacity sizes: the slots are empty afterwards
 void sift_release_slots(spvo_ctx *c) {
   auto &s = c->sift;
-  for (SiftSlot &sl : s.slots) {
-    dev_free(sl.d_desc, sl.d_sqn, sl.d_src, sl.d_n);
-    slot_rewrite(sl);
-  }
-  host_free(s.h_src, s.hm_desc, s.h_n);
+  for (SiftSlot &sl : s.slots) slot_rewrite(sl);
   s.pair.mcache.invalidate();
   s.slot_cap = 0; s.pair.last_slot_l = -1;
 }
@@ -223,14 +203,10 @@ int sift_slots_ensure(spvo_ctx *c, int cap, size_t px) {
   HIP_TRY(c, hipDeviceSynchronize());   // (a match may still read the slots where the L2 matcher runs)
   s.match_pending = false;
   sift_release_slots(c);
-  int rc;
-  for (SiftSlot &sl : s.slots)
-    if ((rc = dev_alloc(c, &sl.d_desc, (size_t)cap * 256)) || (rc = dev_alloc(c, &sl.d_sqn, (size_t)cap + 4)) || (rc = dev_alloc(c, &sl.d_src, cap)) || (rc = dev_alloc(c, &sl.d_n, 1)))
-      return rc;
-  HIP_TRY(c, hipHostMalloc((void **)&s.h_src, (size_t)2 * cap * sizeof(SiftSrc)));
-  HIP_TRY(c, hipHostMalloc((void **)&s.hm_desc, (size_t)2 * cap * 128 * sizeof(float)));
-  HIP_TRY(c, hipHostMalloc((void **)&s.h_n, 4 * 4 * sizeof(int)));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
+  std::vector<GrowEntry> list;
+  for (SiftSlot &sl : s.slots) list.insert(list.end(), {zeroed(sl.d_desc, (size_t)cap * 256), zeroed(sl.d_sqn, (size_t)cap + 4), zeroed(sl.d_src, cap), zeroed(sl.d_n, 1)});
+  list.insert(list.end(), {plain(s.h_src, (size_t)2 * cap), plain(s.hm_desc, (size_t)2 * cap * 128), plain(s.h_n, 4 * 4)});
+  if (int rc = grow(c, wait_for_nothing(), list)) return rc;
   s.slot_cap = cap;
   return SPVO_OK;
 }
@@ -244,10 +220,9 @@ int sift_prematch_ensure(spvo_ctx *c) {
   if (s.h_match_cap != c->match_cap) {
     HIP_TRY(c, hipDeviceSynchronize());
     s.match_pending = false;
-    host_free(s.h_match);
     s.h_match_cap = 0;
     s.pair.mcache.invalidate();
-    HIP_TRY(c, hipHostMalloc((void **)&s.h_match, (size_t)2 * c->match_cap * sizeof(int2)));
+    if (int rc = grow(c, wait_for_nothing(), {plain(s.h_match, (size_t)2 * c->match_cap)})) return rc;
     s.h_match_cap = c->match_cap;
   }
   return SPVO_OK;
@@ -308,12 +283,9 @@ PairMirror sift_mirror(spvo_ctx *c, int k, bool records, size_t kp_bytes) {
 int sift_given_ensure(spvo_ctx *c, int n) {
   auto &s = c->sift;
   if (n <= s.given_cap) return SPVO_OK;
-  HIP_TRY(c, hipStreamSynchronize(c->stream2));
-  dev_free(s.given_kp, s.given_desc);
   const int cap = (int)std::min<long long>(std::max<long long>(n, 2ll * s.given_cap), 0x7FFFFFFF);   // (grown geometrically: a count that creeps up reallocates rarely)
   s.given_cap = 0;
-  int rc;
-  if ((rc = dev_alloc(c, &s.given_kp, cap, false)) || (rc = dev_alloc(c, &s.given_desc, (size_t)cap * 128, false))) return rc;
+  if (int rc = grow(c, wait_for(c->stream2), {plain(s.given_kp, cap), plain(s.given_desc, (size_t)cap * 128)})) return rc;
   s.given_cap = cap;
   return SPVO_OK;
 }
@@ -321,13 +293,8 @@ int sift_given_ensure(spvo_ctx *c, int n) {
 // the pyramid buffer grown to `pyr_floats`
 int sift_pyr_ensure(spvo_ctx *c, size_t pyr_floats) {
   auto &s = c->sift;
-  if (pyr_floats <= s.pyr_cap) return SPVO_OK;
-  HIP_TRY(c, hipStreamSynchronize(c->stream2));
-  dev_free(s.pyr);
-  s.pyr_cap = 0;
-  if (int rc = dev_alloc(c, &s.pyr, pyr_floats, false)) return rc;
-  s.pyr_cap = pyr_floats;
-  return SPVO_OK;
+  if (pyr_floats <= s.pyr.count()) return SPVO_OK;
+  return grow(c, wait_for(c->stream2), {plain(s.pyr, pyr_floats)});
 }
 
 // ---- the link behind a detector whose records carry an octave (spvo_brisk_sift_pair, spvo_akaze_sift_pair, spvo_sift_link_debug)
@@ -356,15 +323,11 @@ int sift_link_check_octave(spvo_ctx *c, const char *who, int rows, int cols, int
 int sift_link_ensure(spvo_ctx *c, size_t pyr_floats, int list_cap) {
   auto &s = c->sift;
   if (int rc = sift_pyr_ensure(c, pyr_floats)) return rc;
-  if (!s.lnk_cnt) {
-    if (int rc = dev_alloc(c, &s.lnk_cnt, 4)) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (dev_alloc clears on the network stream)
-  }
+  if (!s.lnk_cnt)
+    if (int rc = grow(c, wait_for_nothing(), {zeroed(s.lnk_cnt, 4)})) return rc;
   if (list_cap > s.lnk_cap) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream2));
-    dev_free(s.lnk_kept);
     s.lnk_cap = 0;
-    if (int rc = dev_alloc(c, &s.lnk_kept, (size_t)list_cap, false)) return rc;
+    if (int rc = grow(c, wait_for(c->stream2), {plain(s.lnk_kept, (size_t)list_cap)})) return rc;
     s.lnk_cap = list_cap;
   }
   return SPVO_OK;
@@ -417,14 +380,14 @@ int spvo_int::sift_link_pair(spvo_ctx *c, const SiftLinkDetector &det, const uin
   if ((rc = sift_link_ensure(c, pyr_floats, src.keep ? src.n_cap : 0)) || (rc = sift_slots_ensure(c, cap, (size_t)rows * cols)) || (rc = sift_prematch_ensure(c))) return rc;
   P.pyr = s.pyr;
   if ((rc = pc.load(img_l, img_r, rows, cols, stride))) return rc;
-  char *const h_rec = reinterpret_cast<char *>(s.h_src);
+  char *const h_rec = reinterpret_cast<char *>(s.h_src.get());
   for (int k = 0; k < 2; ++k) {   // left chain, then the right one
     if ((rc = det.enqueue(pc.image(k)))) return rc;
     const SiftSlot &t = s.slots[pc.slots[k]];
     SiftLinkIO io{};
     io.s = src;
     io.slot_cap = cap;
-    io.s_desc = t.d_desc; io.s_sqn = t.d_sqn; io.s_rec = reinterpret_cast<SiftKey *>(t.d_src); io.d_n = t.d_n;
+    io.s_desc = t.d_desc; io.s_sqn = t.d_sqn; io.s_rec = reinterpret_cast<SiftKey *>(t.d_src.get()); io.d_n = t.d_n;
     io.h_desc = s.hm_desc + (size_t)k * s.slot_cap * 128;
     io.h_rec = h_rec + (size_t)k * s.slot_cap * sizeof(SiftSrc);
     io.h_n = s.h_n + 4 * k; io.h_k = s.h_n + 8 + 4 * k;
@@ -442,10 +405,6 @@ int spvo_int::sift_link_pair(spvo_ctx *c, const SiftLinkDetector &det, const uin
 void spvo_int::sift_release(spvo_ctx *c) {
   auto &s = c->sift;
   sift_release_slots(c);
-  dev_free(s.img, s.pyr, s.desc, s.cand_pos, s.cand_off, s.kp, s.counters, s.keys, s.sorted, s.order, s.ord_n, s.given_kp, s.given_desc, s.lnk_kept, s.lnk_cnt, s.lnk_keep);
-  s.given_cap = s.lnk_cap = s.lnk_keep_cap = 0;
-  host_free(s.h_match);
-  s.h_match_cap = 0;
   s.pair.release();
 }
 
@@ -611,7 +570,7 @@ int spvo_classic_sift_pair(spvo_ctx *c, const spvo_classic_opts *opts, const uin
                             cap,
                             t.d_desc,
                             t.d_sqn,
-                            reinterpret_cast<SiftKey *>(t.d_src),
+                            reinterpret_cast<SiftKey *>(t.d_src.get()),
                             t.d_n,
                             s.hm_desc + (size_t)k * s.slot_cap * 128,
                             reinterpret_cast<SiftKey *>(s.h_src + (size_t)k * s.slot_cap),
@@ -720,13 +679,8 @@ int spvo_sift_link_debug(spvo_ctx *c, int rows, int cols, const spvo_sift_keypoi
   s.rows = s.cols = 0;   // the pyramid buffer will hold the levels the link reads: nothing spvo_sift_debug_level could serve
   int rc;
   if ((rc = sift_link_ensure(c, pyr_floats, n)) || (rc = sift_given_ensure(c, n))) return rc;
-  if (keep && n > s.lnk_keep_cap) {
-    HIP_TRY(c, hipStreamSynchronize(st));
-    dev_free(s.lnk_keep);
-    s.lnk_keep_cap = 0;
-    if ((rc = dev_alloc(c, &s.lnk_keep, (size_t)n, false))) return rc;
-    s.lnk_keep_cap = n;
-  }
+  if (keep && (size_t)n > s.lnk_keep.count())
+    if ((rc = grow(c, wait_for(st), {plain(s.lnk_keep, (size_t)n)}))) return rc;
   P.pyr = s.pyr;
   std::vector<int> flags, h_kept((size_t)n);
   std::vector<float> h_desc((size_t)n * 128);
@@ -738,7 +692,7 @@ int spvo_sift_link_debug(spvo_ctx *c, int rows, int cols, const spvo_sift_keypoi
   }
   HIP_TRY(c, hipMemcpyAsync(s.lnk_cnt + 1, &n, sizeof(int), hipMemcpyHostToDevice, st));
   SiftLinkIO io{};
-  io.s = SiftLinkSrc{reinterpret_cast<const char *>(s.given_kp), (int)sizeof(SiftKey), (int)offsetof(SiftKey, x), (int)offsetof(SiftKey, y), (int)offsetof(SiftKey, size),
+  io.s = SiftLinkSrc{reinterpret_cast<const char *>(s.given_kp.get()), (int)sizeof(SiftKey), (int)offsetof(SiftKey, x), (int)offsetof(SiftKey, y), (int)offsetof(SiftKey, size),
                      (int)offsetof(SiftKey, angle), (int)offsetof(SiftKey, response), (int)offsetof(SiftKey, octave), keep ? s.lnk_keep : nullptr, s.lnk_cnt + 1, n, nullptr, nullptr, 0};
   io.slot_cap = n;
   io.h_desc = s.given_desc;

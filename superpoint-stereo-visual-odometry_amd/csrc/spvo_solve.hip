@@ -5,47 +5,31 @@
 namespace spvo_int {
 
 int ensure_odometry(spvo_ctx *c, int n, int iterations, int n_obs) {
-  int rc;
-  if (!c->d_P) {
-    if ((rc = dev_alloc(c, &c->d_P, 64))) return rc;
-    if ((rc = dev_alloc(c, &c->rw.result, 8))) return rc;
-    if ((rc = dev_alloc(c, &c->d_refine, 1))) return rc;
-  }
-  // a buffer is cleared as it is freed and its capacity drops to 0 before the reallocation: a failure half-way leaves a context
-  // that spvo_destroy and a later call can still handle
-  auto drop = [](auto *&p) { if (p) (void)hipFree(p); p = nullptr; };
+  if (!c->d_P)
+    if (int rc = grow(c, wait_for_nothing(), {zeroed(c->d_P, 64), zeroed(c->rw.result, 8), zeroed(c->d_refine, 1)})) return rc;
+  // a capacity drops to 0 before its group is re-allocated: a failure leaves a context that spvo_destroy and a later call can still handle
+  // (nothing to wait for: the callers have drained what reads these buffers)
   if (n > c->odo_cap) {
     const int cap = std::max(n, 2048);
     c->odo_cap = 0;
-    drop(c->d_pts_a); drop(c->d_pts_b); drop(c->d_xyz); drop(c->rw.inliers);
-    if ((rc = dev_alloc(c, &c->d_pts_a, (size_t)cap * 3))) return rc;
-    if ((rc = dev_alloc(c, &c->d_pts_b, (size_t)cap * 3))) return rc;
-    if ((rc = dev_alloc(c, &c->d_xyz, (size_t)cap * 3))) return rc;
-    if ((rc = dev_alloc(c, &c->rw.inliers, cap))) return rc;
+    if (int rc = grow(c, wait_for_nothing(), {zeroed(c->d_pts_a, (size_t)cap * 3), zeroed(c->d_pts_b, (size_t)cap * 3), zeroed(c->d_xyz, (size_t)cap * 3), zeroed(c->rw.inliers, cap)})) return rc;
     c->odo_cap = cap;
   }
   if (iterations > c->ransac_cap) {
     const int cap = std::max(iterations, 512);
     c->ransac_cap = 0;
-    drop(c->rw.counts); drop(c->rw.poses);
-    if ((rc = dev_alloc(c, &c->rw.counts, cap))) return rc;
-    if ((rc = dev_alloc(c, &c->rw.poses, (size_t)cap * 7))) return rc;
-    for (int sl = 1; sl < spvo_ctx::SOLVE_BUFS; ++sl) {   // (the fused solve's sets 1 ..: spvo_solve_submit)
-      drop(c->x_counts[sl]); drop(c->x_poses[sl]);
-      if ((rc = dev_alloc(c, &c->x_counts[sl], cap))) return rc;
-      if ((rc = dev_alloc(c, &c->x_poses[sl], (size_t)cap * 7))) return rc;
-    }
+    std::vector<GrowEntry> list{zeroed(c->rw.counts, cap), zeroed(c->rw.poses, (size_t)cap * 7)};
+    for (int sl = 1; sl < spvo_ctx::SOLVE_BUFS; ++sl)   // (the fused solve's sets 1 ..: spvo_solve_submit)
+      list.insert(list.end(), {zeroed(c->x_counts[sl], cap), zeroed(c->x_poses[sl], (size_t)cap * 7)});
+    if (int rc = grow(c, wait_for_nothing(), list)) return rc;
     c->ransac_cap = cap;
   }
   if (n_obs > c->obs_cap) {
     const int cap = std::max(n_obs, 8192);
     c->obs_cap = 0;
-    drop(c->d_obs);
-    if ((rc = dev_alloc(c, &c->d_obs, cap))) return rc;
-    for (int sl = 1; sl < spvo_ctx::SOLVE_BUFS; ++sl) {
-      drop(c->x_obs[sl]);
-      if ((rc = dev_alloc(c, &c->x_obs[sl], cap))) return rc;
-    }
+    std::vector<GrowEntry> list{zeroed(c->d_obs, cap)};
+    for (int sl = 1; sl < spvo_ctx::SOLVE_BUFS; ++sl) list.push_back(zeroed(c->x_obs[sl], cap));
+    if (int rc = grow(c, wait_for_nothing(), list)) return rc;
     c->obs_cap = cap;
   }
   return SPVO_OK;
@@ -97,8 +81,8 @@ int spvo_pnp_ransac(spvo_ctx *c, const double K[9], const float *xyz, const floa
   HIP_TRY(c, hipMemcpyAsync(c->d_pts_b, xy, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
   {
     ScopedStage st(c, stage_id(c, "ransac"));
-    hipLaunchKernelGGL(ransac_hypothesis_kernel, dim3(o.iterations), dim3(64), 0, c->stream, c->d_P + 24, c->d_pts_a, c->d_pts_b, n, c->d_P + 33, o.seed, o.reproj_error * o.reproj_error, c->rw);
-    hipLaunchKernelGGL(ransac_select_kernel, dim3(1), dim3(SOLVE_TAIL_THREADS), 0, c->stream, c->d_P + 24, c->d_pts_a, c->d_pts_b, n, c->d_P + 33, o.iterations, o.reproj_error * o.reproj_error, c->rw);
+    hipLaunchKernelGGL(ransac_hypothesis_kernel, dim3(o.iterations), dim3(64), 0, c->stream, c->d_P + 24, c->d_pts_a, c->d_pts_b, n, c->d_P + 33, o.seed, o.reproj_error * o.reproj_error, c->rw.work());
+    hipLaunchKernelGGL(ransac_select_kernel, dim3(1), dim3(SOLVE_TAIL_THREADS), 0, c->stream, c->d_P + 24, c->d_pts_a, c->d_pts_b, n, c->d_P + 33, o.iterations, o.reproj_error * o.reproj_error, c->rw.work());
   }
   HIP_TRY(c, hipGetLastError());
   double res[8];
@@ -175,9 +159,9 @@ int spvo_solve_submit(spvo_ctx *c, const spvo_solve_input *in) {
   for (int k = 0; k < 3; ++k) { pend.rvec[k] = in->rvec_pred[k]; pend.tvec[k] = in->tvec_pred[k]; }
   // this call runs on the context's second stream so that it overlaps a detector submission in
   // flight; buffers only grow on first use (then everything is drained once)
-  const bool grow = n > c->odo_cap || in->ransac.iterations > c->ransac_cap || 4 * n > c->obs_cap || !c->d_P || n > c->solve_cap || !c->solve_cap;
-  if (grow && !c->solve_q.empty()) return fail(c, SPVO_ERR_STATE, "the solver's buffers have to grow for %d correspondences: complete the pending solve first", n);
-  if (grow) HIP_TRY(c, hipDeviceSynchronize());
+  const bool growing = n > c->odo_cap || in->ransac.iterations > c->ransac_cap || 4 * n > c->obs_cap || !c->d_P || n > c->solve_cap || !c->solve_cap;
+  if (growing && !c->solve_q.empty()) return fail(c, SPVO_ERR_STATE, "the solver's buffers have to grow for %d correspondences: complete the pending solve first", n);
+  if (growing) HIP_TRY(c, hipDeviceSynchronize());
   int rc = ensure_odometry(c, std::max(n, 1), in->ransac.iterations, 4 * std::max(n, 1));
   if (rc) return rc;
   if (n > c->solve_cap || !c->solve_cap) {
@@ -186,37 +170,22 @@ int spvo_solve_submit(spvo_ctx *c, const spvo_solve_input *in) {
     const int cap = std::max(std::max(n, 2048), c->cfg.max_keypoints);
     const size_t in_bytes = 64 * sizeof(double) + (size_t)12 * cap * 4, o_bytes = (size_t)4 * cap * 4;
     constexpr int NB = spvo_ctx::SOLVE_BUFS;
-    char *d_in[NB] = {}, *h_in[NB] = {}, *d_o[NB] = {}, *h_o[NB] = {};
-    double *d_res[NB] = {}, *h_res[NB] = {};
-    auto release = [&](char **di, double **dr, char **dout, char **hi, double **hr, char **hout) {
-      for (int sl = 0; sl < NB; ++sl) {
-        host_free(hi[sl], hr[sl], hout[sl]);
-        dev_free(di[sl], dr[sl], dout[sl]);
-      }
-    };
-    hipError_t he = hipSuccess;
-    for (int sl = 0; sl < NB && !rc && he == hipSuccess; ++sl) {
-      if ((rc = dev_alloc(c, &d_in[sl], in_bytes)) || (rc = dev_alloc(c, &d_res[sl], 40)) || (rc = dev_alloc(c, &d_o[sl], o_bytes))) break;
-      if ((he = hipHostMalloc((void **)&h_in[sl], in_bytes)) != hipSuccess || (he = hipHostMalloc((void **)&h_res[sl], 40 * sizeof(double))) != hipSuccess) break;
-      he = hipHostMalloc((void **)&h_o[sl], o_bytes);
-    }
+    spvo_ctx::SolveSet fresh[NB];   // (free themselves on every way out)
+    std::vector<GrowEntry> list;
+    for (spvo_ctx::SolveSet &f : fresh)
+      list.insert(list.end(), {zeroed(f.d_in, in_bytes), zeroed(f.d_res, 40), zeroed(f.d_o, o_bytes), plain(f.h_in, in_bytes), plain(f.h_res, 40), plain(f.h_o, o_bytes)});
+    if ((rc = grow(c, wait_for_nothing(), list))) return rc;
     const int last = c->solve_last_slot;
-    if (!rc && he == hipSuccess && last >= 0 && c->solve_last_n > 0)
-      he = hipMemcpyAsync(d_o[last], c->d_solve_o[last], (size_t)3 * c->solve_last_n * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
-    if (!rc && he == hipSuccess) he = hipStreamSynchronize(c->stream);
-    if (rc || he != hipSuccess) {
-      release(d_in, d_res, d_o, h_in, h_res, h_o);
-      return rc ? rc : fail(c, SPVO_ERR_DEVICE, "growing the solver's buffers to %d correspondences: %s", cap, hipGetErrorString(he));
-    }
-    release(c->d_solve_in, c->d_solve_res, c->d_solve_o, c->h_solve_in, c->h_solve_res, c->h_solve_o);
-    for (int sl = 0; sl < NB; ++sl) {
-      c->d_solve_in[sl] = d_in[sl]; c->d_solve_res[sl] = d_res[sl]; c->d_solve_o[sl] = d_o[sl];
-      c->h_solve_in[sl] = h_in[sl]; c->h_solve_res[sl] = h_res[sl]; c->h_solve_o[sl] = h_o[sl];
-    }
-    if (!c->d_ctl && (rc = dev_alloc(c, &c->d_ctl, 4 * NB))) return rc;
+    hipError_t he = hipSuccess;
+    if (last >= 0 && c->solve_last_n > 0)
+      he = hipMemcpyAsync(fresh[last].d_o, c->solve_set[last].d_o, (size_t)3 * c->solve_last_n * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+    if (he != hipSuccess) return fail(c, SPVO_ERR_DEVICE, "growing the solver's buffers to %d correspondences: %s", cap, hipGetErrorString(he));
+    for (int sl = 0; sl < NB; ++sl) c->solve_set[sl] = std::move(fresh[sl]);
+    if (!c->d_ctl && (rc = grow(c, wait_for_nothing(), {zeroed(c->d_ctl, 4 * NB)}))) return rc;
     c->solve_cap = cap;
   }
-  if (grow) HIP_TRY(c, hipDeviceSynchronize());
+  if (growing) HIP_TRY(c, hipDeviceSynchronize());
   const int sl = c->solve_next_slot;
   pend.slot = sl;
   const bool solve_timing = c->solve_timing != 0;   // diagnostic (read at spvo_create): host time per phase of this call
@@ -225,7 +194,7 @@ int spvo_solve_submit(spvo_ctx *c, const spvo_solve_input *in) {
   auto now_us = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3; };
   const double tm0 = solve_timing ? now_us() : 0;
   // ---- pack: 64 doubles, then cl cr pl pr [2n each], prev_xyz [3n], prev_valid or prev_index [n]
-  double *hdr = (double *)c->h_solve_in[sl];
+  double *hdr = (double *)c->solve_set[sl].h_in.get();
   std::memset(hdr, 0, 64 * sizeof(double));
   for (int k = 0; k < 12; ++k) { hdr[k] = in->P_l[k]; hdr[12 + k] = in->P_r[k]; }
   const int kidx[9] = {0, 1, 2, 4, 5, 6, 8, 9, 10};
@@ -235,7 +204,7 @@ int spvo_solve_submit(spvo_ctx *c, const spvo_solve_input *in) {
     hdr[39] = in->frame_count; hdr[41] = 8.0; hdr[42] = 0.1; hdr[43] = 10; hdr[44] = 1;   // hpp:145-147
   }
   hdr[40] = in->refinement_degree;
-  float *fw = (float *)(c->h_solve_in[sl] + 64 * sizeof(double));
+  float *fw = (float *)(c->solve_set[sl].h_in.get() + 64 * sizeof(double));
   if (n > 0) {
     std::memcpy(fw, in->xy_cl, (size_t)2 * n * 4);
     std::memcpy(fw + 2 * n, in->xy_cr, (size_t)2 * n * 4);
@@ -249,33 +218,33 @@ int spvo_solve_submit(spvo_ctx *c, const spvo_solve_input *in) {
   } else if (have_index && n > 0) {
     std::memcpy(fw + 11 * n, in->prev_index, (size_t)n * 4);
   }
-  const float *prev_pts = have_index ? (const float *)c->d_solve_o[c->solve_last_slot] : nullptr;   // (the set before this one: nothing rewrites it while this solve is pending)
+  const float *prev_pts = have_index ? (const float *)c->solve_set[c->solve_last_slot].d_o.get() : nullptr;   // (the set before this one: nothing rewrites it while this solve is pending)
   if (n > 0) {
     const size_t used = 64 * sizeof(double) + (size_t)12 * n * 4;
     const double tm1 = solve_timing ? now_us() : 0;
-    const double *dh = (const double *)c->d_solve_in[sl];
-    const float *df = (const float *)(c->d_solve_in[sl] + 64 * sizeof(double));
-    float *d_xyz = (float *)c->d_solve_o[sl];
-    int *d_inl = (int *)(c->d_solve_o[sl]) + 3 * n;
-    RansacWork rw = c->rw;
+    const double *dh = (const double *)c->solve_set[sl].d_in.get();
+    const float *df = (const float *)(c->solve_set[sl].d_in.get() + 64 * sizeof(double));
+    float *d_xyz = (float *)c->solve_set[sl].d_o.get();
+    int *d_inl = (int *)(c->solve_set[sl].d_o.get()) + 3 * n;
+    RansacWork rw = c->rw.work();
     if (sl) { rw.counts = c->x_counts[sl]; rw.poses = c->x_poses[sl]; }
-    rw.result = c->d_solve_res[sl];
+    rw.result = c->solve_set[sl].d_res;
     rw.inliers = d_inl;
     const double thr2 = in->ransac.reproj_error * in->ransac.reproj_error;
     {
       ScopedStage st(c, stage_id(c, "solve"), 0, 0, c->stream2);
       // (the inputs travel inside the first kernel, the results inside the last one: see odometry.hip.h)
-      hipLaunchKernelGGL(solve_in_triangulate_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream2, reinterpret_cast<const uint4 *>(c->h_solve_in[sl]),
-                         reinterpret_cast<uint4 *>(c->d_solve_in[sl]), (int)(used / 16), n, d_xyz);
+      hipLaunchKernelGGL(solve_in_triangulate_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream2, reinterpret_cast<const uint4 *>(c->solve_set[sl].h_in.get()),
+                         reinterpret_cast<uint4 *>(c->solve_set[sl].d_in.get()), (int)(used / 16), n, d_xyz);
       if (n >= 4) {
         SolveTailArgs ta;   // selection + refit, residual blocks, refinement, results to the pinned buffers: one launch (odometry.hip.h)
         ta.hdr = dh; ta.xyz = d_xyz; ta.xy_cl = df; ta.xy_cr = df + 2 * n; ta.xy_pl = df + 4 * n; ta.xy_pr = df + 6 * n;
         ta.prev_xyz = have_prev ? df + 8 * n : nullptr; ta.prev_valid = have_prev ? (const int *)(df + 11 * n) : nullptr;
         ta.prev_index = have_index ? (const int *)(df + 11 * n) : nullptr; ta.prev_pts = prev_pts;
         ta.n = n; ta.iterations = in->ransac.iterations; ta.thr2 = thr2; ta.w = rw;
-        ta.obs = sl ? c->x_obs[sl] : c->d_obs; ta.ctl = c->d_ctl + 4 * sl; ta.res = c->d_solve_res[sl];
+        ta.obs = sl ? c->x_obs[sl] : c->d_obs; ta.ctl = c->d_ctl + 4 * sl; ta.res = c->solve_set[sl].d_res;
         ta.max_iterations = in->refine.max_iterations; ta.huber_delta = in->refine.huber_delta;
-        ta.d_o = reinterpret_cast<const unsigned *>(c->d_solve_o[sl]); ta.h_o = reinterpret_cast<unsigned *>(c->h_solve_o[sl]); ta.o_words = 4 * n; ta.h_res = c->h_solve_res[sl];
+        ta.d_o = reinterpret_cast<const unsigned *>(c->solve_set[sl].d_o.get()); ta.h_o = reinterpret_cast<unsigned *>(c->solve_set[sl].h_o.get()); ta.o_words = 4 * n; ta.h_res = c->solve_set[sl].h_res;
         // The hypotheses of THIS solve -- in one launch with the tail of the solve submitted before, if that one is still held back
         // (solve_hyp_tail_kernel: the two overlap; ev_solve of the older solve is recorded behind the launch) ...
         if (c->tail_deferred) {
@@ -303,7 +272,7 @@ int spvo_solve_submit(spvo_ctx *c, const spvo_solve_input *in) {
       }
       HIP_TRY(c, hipGetLastError());
     }
-    if (n < 4) HIP_TRY(c, hipMemcpyAsync(c->h_solve_o[sl], c->d_solve_o[sl], (size_t)4 * n * 4, hipMemcpyDeviceToHost, c->stream2));   // (no model possible: only the points travel)
+    if (n < 4) HIP_TRY(c, hipMemcpyAsync(c->solve_set[sl].h_o, c->solve_set[sl].d_o, (size_t)4 * n * 4, hipMemcpyDeviceToHost, c->stream2));   // (no model possible: only the points travel)
     if (!c->ev_solve[sl]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_solve[sl], hipEventDisableTiming));
     if (!(c->tail_deferred && c->tail_slot == sl)) HIP_TRY(c, hipEventRecord(c->ev_solve[sl], c->stream2));   // (a held-back tail: the event follows its launch)
     if (solve_timing) {
@@ -364,12 +333,12 @@ static int solve_wait_impl(spvo_ctx *c, const double *prior_rvec, const double *
     g_diag.max_solve_wait = std::max(g_diag.max_solve_wait, diag_now_us() - tw0);
     g_diag.iv_solve += diag_now_us() - tw0;
   }
-  std::memcpy(xyz, c->h_solve_o[sl], (size_t)3 * n * 4);
+  std::memcpy(xyz, c->solve_set[sl].h_o, (size_t)3 * n * 4);
   if (n < 4) { prior_pose(); return SPVO_OK; }                                      // no model possible: prior is kept
-  const double *res = c->h_solve_res[sl], *gate = res + 8, *ref = res + 24;
+  const double *res = c->solve_set[sl].h_res, *gate = res + 8, *ref = res + 24;
   out->pnp_ok = res[6] != 0;
   out->n_inliers = (int)res[7];
-  if (out->n_inliers > 0) std::memcpy(inliers, (const int *)c->h_solve_o[sl] + 3 * n, (size_t)out->n_inliers * 4);
+  if (out->n_inliers > 0) std::memcpy(inliers, (const int *)c->solve_set[sl].h_o.get() + 3 * n, (size_t)out->n_inliers * 4);
   // the gate (base.cpp:241-272; constants hpp:145-147): acceleration against the prediction; rejected or no model => the prediction is returned
   constexpr double TIME_INTERVAL = 0.1, MAX_ACCELERATION = 8.0;
   constexpr int IGNORE_FRAME_COUNT = 10;
