@@ -749,6 +749,17 @@ int spvo_set_prematch(spvo_ctx *ctx, int enable, int selector, int cross_check, 
 int spvo_set_match_fp8(spvo_ctx *ctx, int enable);
 /* 1 / 0: the fp8 shortlist is on / off in this context (what the host class's setMatchFp8 asked for); negative: error. */
 int spvo_get_match_fp8(const spvo_ctx *ctx);
+/* Which kernels the most recent L2 match of this context ran (read-only; for tests, which otherwise cannot tell the matcher's three
+ * forms apart: their results are identical).  info = {fp8, fused, NCH, jobs}:
+ *   fp8    1: fp8 shortlist GEMM + the two-pass re-rank (spvo_set_match_fp8)
+ *   fused  1: the distance tile is reduced in LDS and a merge kernel finishes the row (the default up to a matcher capacity of 64
+ *             column tiles = 8192 rows); 0: every distance goes to memory and the re-rank kernel reads the row back (fp8, capacities
+ *             beyond 8192 rows, tuning "match_fused" = 0)
+ *   NCH    re-rank instantiation: 4 = rows of up to 1024 columns held in registers, 0 = chunked with a ring queue (always 0 when fused;
+ *             with NN + cross_check the sides are swapped, so the QUERY count decides)
+ *   jobs   matches in that launch set (1, or 2 for a detector call's prematch); 0: this context has not matched yet
+ * A call that returns without a launch (an empty side, a result served from a prematch) leaves the record as it was. */
+int spvo_match_last_form(spvo_ctx *ctx, int info[4]);
 
 /* cv::triangulatePoints + convertPointsFromHomogeneous (base.cpp:211-223):
  * DLT null vector of the 4x4 system in f64, stored f32, then x/w.

@@ -45,10 +45,13 @@ def best_two(d2: np.ndarray):
 
 
 def bf_match(desc_a: np.ndarray, desc_b: np.ndarray, selector: str = "KNN", cross_check: bool = False,
-             ratio: float = 0.8):
+             ratio: float = 0.8, d2: np.ndarray | None = None):
     """Returns (train_idx int32 [na] with -1 = no match, distance f32 [na]: the matched pair's distance where
     train_idx >= 0; for NN without cross-check and KNN the nearest neighbour's distance everywhere; 0 for rows a
     cross-check left unmatched).
+
+    d2: sq_distances(desc_a, desc_b) where the caller has it already (several selectors on one pair of inputs); it is
+    not modified.
 
     train_idx is exactly maps_of_indices[match_type] of base.cpp:483-491; the
     DMatch list of the reference is {(i, train_idx[i], distance[i]) : train_idx[i] >= 0}
@@ -57,7 +60,9 @@ def bf_match(desc_a: np.ndarray, desc_b: np.ndarray, selector: str = "KNN", cros
     na, nb = len(desc_a), len(desc_b)
     if na == 0 or nb == 0:
         return np.full(na, -1, np.int32), np.zeros(na, np.float32)
-    d2 = sq_distances(desc_a, desc_b)
+    if d2 is None:
+        d2 = sq_distances(desc_a, desc_b)
+    assert d2.shape == (na, nb) and d2.dtype == np.float32
     v0, v1, i0, i1 = best_two(d2)
     d0 = np.sqrt(v0.astype(np.float32))
     d1 = np.sqrt(v1.astype(np.float32))

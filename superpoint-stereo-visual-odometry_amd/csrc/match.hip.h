@@ -92,7 +92,14 @@ __global__ __launch_bounds__(256) void row_sqnorm_kernel(const float *__restrict
 
 // fp8 copy of descriptor rows for the fp8 shortlist GEMM (BASELINE config 5): x * 16 rounded to OCP e4m3 (unit-norm
 // descriptors have entries around 1/16, so the scale puts them in the format's normal range).  One wave per row.
+// Range: e4m3's largest finite value is 448, so entries up to |x| = 28 convert as they are.  Beyond that the conversion does NOT
+// saturate on its own -- v_cvt_pk_fp8_f32 returns NaN (measured on gfx950: SIFT rows, randn * 10), and a NaN entry makes the row's
+// dt8, norms and E8 NaN, every comparison of both passes false, the row unmatched -- so 16 x is clamped to +-448 first.  The copy
+// stays finite, |x - x8| (below) carries the saturation error, E8 stays a rigorous bound and pass 2 simply re-scores more columns:
+// exact for any finite input, a pruning GEMM only for |x| <= 28.  (A per-row scale would keep large rows pruned; not done.)
 constexpr float MATCH_FP8_SCALE = 16.f;
+constexpr float MATCH_FP8_MAX = 448.f;
+__device__ __forceinline__ float match_fp8_operand(float x) { return __builtin_amdgcn_fmed3f(x * MATCH_FP8_SCALE, -MATCH_FP8_MAX, MATCH_FP8_MAX); }
 __global__ __launch_bounds__(256) void desc_to_fp8_kernel(const float *__restrict__ x, int n_host, const int *__restrict__ n_ptr,
                                                           unsigned char *__restrict__ out, float2 *__restrict__ qnorm) {
   const int n = dev_count(n_host, n_ptr);
@@ -101,8 +108,8 @@ __global__ __launch_bounds__(256) void desc_to_fp8_kernel(const float *__restric
   if (r >= n) return;
   const float4 v = *(const float4 *)(x + (size_t)r * MATCH_D + lane * 4);
   int pk = 0;
-  pk = __builtin_amdgcn_cvt_pk_fp8_f32(v.x * MATCH_FP8_SCALE, v.y * MATCH_FP8_SCALE, pk, false);
-  pk = __builtin_amdgcn_cvt_pk_fp8_f32(v.z * MATCH_FP8_SCALE, v.w * MATCH_FP8_SCALE, pk, true);
+  pk = __builtin_amdgcn_cvt_pk_fp8_f32(match_fp8_operand(v.x), match_fp8_operand(v.y), pk, false);
+  pk = __builtin_amdgcn_cvt_pk_fp8_f32(match_fp8_operand(v.z), match_fp8_operand(v.w), pk, true);
   reinterpret_cast<int *>(out + (size_t)r * MATCH_D)[lane] = pk;
   // norms of the copy and of what the rounding took away (the copy read back exactly as the matrix cores will see it)
   const float inv = 1.f / MATCH_FP8_SCALE;

@@ -361,6 +361,7 @@ struct spvo_ctx {
   bool host_sets_ready = false;  // d_resized / h_resized / h_desc of EVERY set are allocated
   hipEvent_t ev_post = nullptr, ev_post_b = nullptr;    // PostScope: orders a synchronous entry point behind what is left on the tail stream(s)
   bool match_fp8 = false;        // fp8 shortlist GEMM (approximate; spvo_set_match_fp8)
+  int match_form[4] = {0, 0, 0, 0};   // {fp8, fused, NCH of the re-rank, jobs} of the most recent enqueue_matches (spvo_match_last_form); jobs = 0: none yet
   bool prematch = false;
   int pm_selector = SPVO_SELECT_KNN, pm_cross = 0;
   float pm_ratio = 0.8f;

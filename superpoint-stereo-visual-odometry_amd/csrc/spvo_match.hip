@@ -105,6 +105,8 @@ int enqueue_matches(spvo_ctx *c, const MatchReq *req_in, int njobs, int selector
     const dim3 gr((na_max + 3) / 4, njobs);
     // rows of up to 1024 columns stay in registers between the two passes of the re-rank (8 chunks for 2048 columns
     // measured 2.4x SLOWER than the chunked form: 232 registers, 70 KB of LDS)
+    const int nch = !fused && nb_max <= 1024 ? 4 : 0;
+    c->match_form[0] = c->match_fp8 ? 1 : 0; c->match_form[1] = fused ? 1 : 0; c->match_form[2] = nch; c->match_form[3] = njobs;   // spvo_match_last_form
     if (fused) hipLaunchKernelGGL(match_merge_kernel<>, gr, dim3(256), sizeof(MatchRerankLds<0>), c->post, jobs, nt_stride, ldt, MATCH_ERR_REL, selector, cross_check, ratio);
     else if (nb_max <= 1024) hipLaunchKernelGGL(match_rerank_kernel<4>, gr, dim3(256), sizeof(MatchRerankLds<4>), c->post, jobs, ldt, err, selector, cross_check, ratio);
     else hipLaunchKernelGGL(match_rerank_kernel<0>, gr, dim3(256), sizeof(MatchRerankLds<0>), c->post, jobs, ldt, err, selector, cross_check, ratio);
@@ -351,5 +353,11 @@ int spvo_set_match_fp8(spvo_ctx *c, int enable) {
 }
 
 int spvo_get_match_fp8(const spvo_ctx *c) { return c ? (c->match_fp8 ? 1 : 0) : SPVO_ERR_INVALID; }
+
+int spvo_match_last_form(spvo_ctx *c, int info[4]) {
+  if (!c || !info) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  for (int i = 0; i < 4; ++i) info[i] = c->match_form[i];
+  return SPVO_OK;
+}
 
 }  // extern "C"

@@ -97,7 +97,7 @@ OBS_DTYPE = np.dtype([("X", np.float32, 3), ("uv", np.float32, 2), ("cam", np.in
 SYMBOLS = [
     "spvo_default_config", "spvo_create", "spvo_destroy", "spvo_last_error", "spvo_load_weights", "spvo_engine_precision", "spvo_set_fp32_split",
     "spvo_preprocess", "spvo_forward", "spvo_debug_tensor", "spvo_heatmap", "spvo_nms",
-    "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8",
+    "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8", "spvo_match_last_form",
     "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_orb_describe_octaves", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_akaze_describe", "spvo_akaze_detect_pair", "spvo_akaze_suppress_debug", "spvo_brisk_orb_pair", "spvo_akaze_orb_pair", "spvo_akaze_brisk_pair", "spvo_orb_octaves_link_debug", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_describe", "spvo_sift_detect_pair", "spvo_classic_sift_pair", "spvo_brisk_sift_pair", "spvo_akaze_sift_pair", "spvo_sift_link_debug", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
     "spvo_profile_enable", "spvo_profile_reset", "spvo_profile_only", "spvo_profile_count", "spvo_profile_get", "spvo_profile_stage_kernel", "spvo_profile_stage_variant",
     "spvo_set_tuning", "spvo_get_tuning", "spvo_clear_tuning",
@@ -148,6 +148,7 @@ def load() -> C.CDLL:
     lib.spvo_clear_tuning.restype = None
     lib.spvo_match.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]
     lib.spvo_match_slots.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]
+    lib.spvo_match_last_form.argtypes = [vp, ip]
     lib.spvo_match_hamming.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]
     lib.spvo_orb_detect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, vp, vp, C.c_int, ip]
     lib.spvo_orb_tables.argtypes = [vp, vp]
@@ -374,6 +375,12 @@ class Context:
         rc = self.lib.spvo_get_match_fp8(self.h)
         self._check(min(rc, 0))
         return rc == 1
+
+    def match_last_form(self) -> dict:
+        """Which kernels the most recent L2 match ran (spvo_match_last_form): fp8 / fused as bool, nch 4 or 0, jobs (0: none yet)."""
+        info = (C.c_int * 4)()
+        self._check(self.lib.spvo_match_last_form(self.h, info))
+        return dict(fp8=bool(info[0]), fused=bool(info[1]), nch=int(info[2]), jobs=int(info[3]))
 
     def engine_precision(self) -> str:
         rc = self.lib.spvo_engine_precision(self.h)

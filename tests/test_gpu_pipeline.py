@@ -515,7 +515,9 @@ def test_fp8_shortlist_matcher(ctx_squeeze, stereo_pair):
     """BASELINE config 5: the shortlist of the matcher from an fp8 (e4m3) distance GEMM.  The GEMM only prunes: pass 1 re-scores
     a statistical window canonically, pass 2 every column whose RIGOROUS lower bound (per-row norms of the fp8 rounding residuals,
     csrc/match.hip.h: MATCH_ERR_REL_FP8) does not exceed the second canonical distance found.  So indices AND distances equal
-    the brute-force oracle's on every row, confident or borderline -- KNN ratio test and plain NN."""
+    the brute-force oracle's on every row, confident or borderline -- KNN ratio test and plain NN.  Here: REAL descriptors, read where
+    the detector left them (spvo_match_slots: device rows, the slots' own squared norms).  Rows handed over by the caller -- the
+    synthetic 700 x 650 case this test used to hold, and the adversarial ones -- are in tests/test_gpu_match.py under its fp8 form."""
     frames, _, P_l, P_r = stereo_pair
     L, R = frames[0]
     out = ctx_squeeze.detect(L, R, P_l, P_r, 0, 1)
@@ -525,24 +527,17 @@ def test_fp8_shortlist_matcher(ctx_squeeze, stereo_pair):
     try:
         ctx_squeeze.set_match_fp8(True)
         idx, d = ctx_squeeze.match_slots(0, 1, n)
+        form_knn = ctx_squeeze.match_last_form()
         nn_idx, nn_d = ctx_squeeze.match_slots(0, 1, n, "NN", False)
-        # descriptors handed over by the caller (spvo_match) take the same path; a near-duplicate cluster widens every window
-        rng = np.random.RandomState(3)
-        a = rng.randn(700, 256).astype(np.float32)
-        a /= np.linalg.norm(a, axis=1, keepdims=True)
-        b = np.concatenate([a[:300] + 0.02 * rng.randn(300, 256).astype(np.float32), np.repeat(a[300:301], 200, 0) + 1e-3 * rng.randn(200, 256).astype(np.float32),
-                            rng.randn(150, 256).astype(np.float32)])
-        b /= np.linalg.norm(b, axis=1, keepdims=True)
-        b = b.astype(np.float32)
-        sidx, sd = ctx_squeeze.match(a, b)
+        form_nn = ctx_squeeze.match_last_form()
     finally:
         ctx_squeeze.set_match_fp8(False)
     assert (ridx >= 0).sum() > 300
+    assert form_knn == form_nn == dict(fp8=True, fused=False, nch=4 if len(out["xy_r"]) <= 1024 else 0, jobs=1)
     assert np.array_equal(idx, ridx) and np.array_equal(d, rd)
     assert np.array_equal(nn_idx, r_nn) and np.array_equal(nn_d, r_nnd)
-    s_ridx, s_rd = matching.bf_match(a, b, "KNN", False, 0.8)
-    assert np.array_equal(sidx, s_ridx) and np.array_equal(sd, s_rd)
     idx2, d2_ = ctx_squeeze.match_slots(0, 1, n)                              # back to the fp32 shortlist: the same again
+    assert not ctx_squeeze.match_last_form()["fp8"]
     assert np.array_equal(idx2, ridx) and np.array_equal(d2_, rd)
 
 
