@@ -19,6 +19,7 @@
 #include <stdint.h>
 #include "conv_mfma.hip.h"    // mul_rn, add_rn, sub_rn
 #include "spvo_types.hip.h"   // AkazeLevel(s), AkazeTaps, AkazeCand, BriskAreaTap, AKAZE_*
+#include "list_steps.hip.h"   // wave_append
 
 namespace spvo {
 
@@ -219,14 +220,8 @@ __global__ __launch_bounds__(256) void akaze_extrema_kernel(const AkazeLevels lv
     const int w = L.w;
     keep = v > threshold && v >= floor_threshold && v > p[-1] && v > p[1] && v > p[-w - 1] && v > p[-w] && v > p[-w + 1] && v > p[w - 1] && v > p[w] && v > p[w + 1];
   }
-  const unsigned long long m = __ballot(keep);
-  if (!m) return;
-  const int lane = threadIdx.x & 63;
-  int base = 0;
-  if (lane == 0) base = atomicAdd(&stat[AKAZE_STAT_NCAND], __popcll(m));
-  base = __shfl(base, 0);
+  const int slot = wave_append(keep, &stat[AKAZE_STAT_NCAND]);
   if (!keep) return;
-  const int slot = base + __popcll(m & ((1ull << lane) - 1ull));
   if (slot >= cap) { stat[AKAZE_STAT_OVERFLOW] = 1; return; }
   keys[slot] = ((unsigned long long)level << 32) | (unsigned)(y * L.w + x);
 }

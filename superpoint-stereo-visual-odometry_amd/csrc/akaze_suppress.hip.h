@@ -11,7 +11,7 @@
 //                 entries keeps the set of levels and the range of y ever written to it, and a scan visits only the chunks that held L or
 //                 L - 1 at a y the candidate can reach; in global memory it starts at the lowest position ever written with one of the two.
 //   second loop   one thread per entry i scans the entries j > i of the next level, tile by tile through LDS
-//   compaction    brisk_det_compact_kernel's walk: survivors whose candidate has `ok` set, as AkazeKp records, with their number
+//   compaction    list_steps.hip.h's walk: survivors whose candidate has `ok` set, as AkazeKp records, with their number
 // The candidate's position goes in WITHOUT the half-pixel shift of its octave against stored positions that carry it, and with the
 // candidate's size^2; the second loop compares stored positions with entry i's size^2.  Both asymmetries are the restatement's.
 // Every float operation is a separately rounded IEEE one (mul_rn / add_rn / sub_rn), as the host loop under fp contract(off).
@@ -21,6 +21,7 @@
 #include <stdint.h>
 #include "conv_mfma.hip.h"    // mul_rn, add_rn, sub_rn
 #include "spvo_types.hip.h"   // AkazeLevels, AkazeCand, AkazeKp
+#include "list_steps.hip.h"   // stable_compact_walk
 
 namespace spvo {
 
@@ -170,36 +171,17 @@ __global__ __launch_bounds__(256) void akaze_suppress_second_kernel(const AkazeL
   }
 }
 
-// the kept entries, order-preserving: ONE workgroup walks the list in chunks of 1024 with a running base (brisk_det_compact_kernel's walk).
+// the kept entries, order-preserving: ONE workgroup walks the list (stable_compact_walk, list_steps.hip.h).
 // out[k]: the record of the k-th kept candidate (its first seven fields), src[k]: that candidate's index.  cnt[AKAZE_SUP_KEPT] = their number.
 __global__ __launch_bounds__(1024) void akaze_suppress_compact_kernel(const AkazeCand *__restrict__ rec, const int *__restrict__ idx, const int *__restrict__ keep, int cap,
                                                                       int *__restrict__ cnt, AkazeKp *__restrict__ out, int *__restrict__ src) {
-  __shared__ int s_wave[16];
-  const int n = min(cnt[AKAZE_SUP_LEN], cap);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int base = 0;
-  for (int i0 = 0; i0 < n; i0 += 1024) {
-    const int i = i0 + (int)threadIdx.x;
-    const bool kp = i < n && keep[i] != 0;
-    const unsigned long long m = __ballot(kp);
-    __syncthreads();   // (the previous chunk's sums have been read)
-    if (lane == 0) s_wave[wave] = __popcll(m);
-    __syncthreads();
-    int off = base, tot = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const int v = s_wave[k];
-      off += k < wave ? v : 0;
-      tot += v;
-    }
-    off += __popcll(m & ((1ull << lane) - 1ull));
-    if (kp) {
-      const AkazeCand c = rec[idx[i]];
-      out[off] = AkazeKp{c.x, c.y, c.size, c.angle, c.response, c.octave, c.class_id};
-      src[off] = idx[i];
-    }
-    base += tot;
-  }
+  const int base = stable_compact_walk(
+      min(cnt[AKAZE_SUP_LEN], cap), [&](int i) { return keep[i] != 0; },
+      [&](int off, int i) {
+        const AkazeCand c = rec[idx[i]];
+        out[off] = AkazeKp{c.x, c.y, c.size, c.angle, c.response, c.octave, c.class_id};
+        src[off] = idx[i];
+      });
   if (threadIdx.x == 0) cnt[AKAZE_SUP_KEPT] = base;
 }
 

@@ -4,7 +4,7 @@
 // no atomics on floats, no order-dependent sums): two calls return identical bytes.
 //   brisk_integral_rows_kernel / _cols_kernel   the (rows + 1) x (cols + 1) int32 integral image: a wave-level scan along every row, then
 //                                               a running sum down every column (exact integers: any order gives the same image)
-//   brisk_compact_kernel                        the border rule as an order-preserving compaction (cls_compact_kernel's scheme): the kept
+//   brisk_compact_kernel                        the border rule as an order-preserving compaction (list_steps.hip.h's walk): the kept
 //                                               indices and their scale index
 //   brisk_compact_list_kernel                   the same walk on a detector's list whose length is on the device, one size for all
 //                                               (spvo_classic_detect's chain); brisk_slot_finish_kernel closes that chain
@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "spvo_types.hip.h"   // OrbKeypoint
+#include "list_steps.hip.h"   // stable_compact_walk
 
 namespace spvo {
 
@@ -80,41 +81,23 @@ __device__ inline int brisk_scale_index(float size, const BriskParams &P) {
   return s >= (double)BRISK_SCALES ? BRISK_SCALES - 1 : (int)s;
 }
 
-// choice 9 as an order-preserving compaction: ONE workgroup walks the list in chunks of 1024 with a running base (wave ballots + an LDS
-// prefix over the 16 waves).  Keypoint i's coordinates are xy[stride * i], xy[stride * i + 1]; live(i) says whether it takes part at all (a
+// choice 9 as an order-preserving compaction by ONE workgroup (stable_compact_walk, list_steps.hip.h): the border rule on top of the walk.
+// Keypoint i's coordinates are xy[stride * i], xy[stride * i + 1]; live(i) says whether it takes part at all (a
 // dead one's coordinates are not read), scale_of(i) is its scale index; of the survivors the first `cap` are handed to put(k, i, s) -- the
 // k-th survivor is keypoint i at scale s -- and ALL are counted: the return value (the same in every thread).
 template <typename Live, typename ScaleOf, typename Put>
 __device__ __forceinline__ int brisk_compact_walk_if(const float *__restrict__ xy, int stride, int n, int h, int w, const BriskParams &P, int cap, Live live, ScaleOf scale_of, Put put) {
-  __shared__ int s_wave[16];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int base = 0;
-  for (int i0 = 0; i0 < n; i0 += 1024) {
-    const int i = i0 + (int)threadIdx.x;
-    int s = 0;
-    bool keep = false;
-    if (i < n && live(i)) {
-      const float x = xy[(size_t)stride * i], y = xy[(size_t)stride * i + 1];
-      s = scale_of(i);
-      const float b = (float)P.size_list[s];
-      keep = x >= b && x < (float)w - b && y >= b && y < (float)h - b;   // (a NaN coordinate is dropped)
-    }
-    const unsigned long long m = __ballot(keep);
-    __syncthreads();   // (the previous chunk's sums have been read)
-    if (lane == 0) s_wave[wave] = __popcll(m);
-    __syncthreads();
-    int off = base, tot = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const int v = s_wave[k];
-      off += k < wave ? v : 0;
-      tot += v;
-    }
-    off += __popcll(m & ((1ull << lane) - 1ull));
-    if (keep && off < cap) put(off, i, s);
-    base += tot;
-  }
-  return base;
+  int s = 0;   // keypoint i's scale index, from the rule to put
+  return stable_compact_walk(
+      n,
+      [&](int i) {
+        if (!live(i)) return false;
+        const float x = xy[(size_t)stride * i], y = xy[(size_t)stride * i + 1];
+        s = scale_of(i);
+        const float b = (float)P.size_list[s];
+        return x >= b && x < (float)w - b && y >= b && y < (float)h - b;   // (a NaN coordinate is dropped)
+      },
+      [&](int k, int i) { if (k < cap) put(k, i, s); });
 }
 // ... on a packed [n][2] list of which every keypoint takes part
 template <typename ScaleOf, typename Put>

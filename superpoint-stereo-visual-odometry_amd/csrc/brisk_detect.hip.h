@@ -14,7 +14,7 @@
 //   refinement  ONE CANDIDATE PER LANE: the windows searched in the layers above and below hold at most 4 x 4 positions of 4 bytes each
 //               (choice 10) and the search is sequential by nature (running maximum, tie rule in raster order): there is nothing for a
 //               wave to share.  refine3D / the top layer's path -> a record and a keep flag at the candidate's rank
-//   compaction  order-preserving, one workgroup (cls_compact_kernel's walk)
+//   compaction  order-preserving, one workgroup (list_steps.hip.h's walk)
 // Integer stages are exact by nature; every float operation is a separately rounded IEEE one in the restatement's order (mul_rn /
 // add_rn / __fdiv_rn, the three double steps of choice 10 with __dmul_rn / __dadd_rn / __ddiv_rn): no contraction, no fast-math.
 #pragma once
@@ -22,6 +22,7 @@
 #include <stdint.h>
 #include "conv_mfma.hip.h"    // mul_rn, add_rn
 #include "spvo_types.hip.h"   // fast916_arc_score, BriskDetLayers, BriskDetKeypoint
+#include "list_steps.hip.h"   // wave_append, stable_compact_walk
 
 namespace spvo {
 
@@ -131,14 +132,8 @@ __global__ __launch_bounds__(256) void brisk_collect_kernel(const BriskDetLayers
       }
     }
   }
-  const unsigned long long m = __ballot(keep);
-  if (!m) return;
-  const int lane = threadIdx.x & 63;
-  int base = 0;
-  if (lane == __ffsll((long long)m) - 1) base = atomicAdd(&counters[1], __popcll(m));
-  base = __shfl(base, __ffsll((long long)m) - 1);
+  const int slot = wave_append(keep, &counters[1]);
   if (!keep) return;
-  const int slot = base + __popcll(m & ((1ull << lane) - 1ull));
   if (slot < cap) keys[slot] = ((unsigned long long)blockIdx.z << 32) | (unsigned)(y * w + x);
   else counters[3] = 1;
 }
@@ -391,32 +386,10 @@ __global__ __launch_bounds__(256) void brisk_refine_kernel(const BriskDetLayers 
   }
 }
 
-// the kept records, order-preserving: ONE workgroup walks the list in chunks of 1024 with a running base (cls_compact_kernel's compaction).
-// counters[2] = the number kept.
+// the kept records, order-preserving: ONE workgroup walks the list (stable_compact_walk, list_steps.hip.h).  counters[2] = the number kept.
 __global__ __launch_bounds__(1024) void brisk_det_compact_kernel(const BriskDetKeypoint *__restrict__ rec, const int *__restrict__ keep, int cap, int *__restrict__ counters,
                                                                  BriskDetKeypoint *__restrict__ out) {
-  __shared__ int s_wave[16];
-  const int n = min(counters[1], cap);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int base = 0;
-  for (int i0 = 0; i0 < n; i0 += 1024) {
-    const int i = i0 + (int)threadIdx.x;
-    const bool kp = i < n && keep[i] != 0;
-    const unsigned long long m = __ballot(kp);
-    __syncthreads();   // (the previous chunk's sums have been read)
-    if (lane == 0) s_wave[wave] = __popcll(m);
-    __syncthreads();
-    int off = base, tot = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const int v = s_wave[k];
-      off += k < wave ? v : 0;
-      tot += v;
-    }
-    off += __popcll(m & ((1ull << lane) - 1ull));
-    if (kp) out[off] = rec[i];
-    base += tot;
-  }
+  const int base = stable_compact_walk(min(counters[1], cap), [&](int i) { return keep[i] != 0; }, [&](int off, int i) { out[off] = rec[i]; });
   if (threadIdx.x == 0) counters[2] = base;
 }
 

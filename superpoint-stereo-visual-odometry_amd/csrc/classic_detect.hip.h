@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "orb.hip.h"
+#include "list_steps.hip.h"   // workgroup_append, wave_append, rank_by_counting, stable_compact_walk
 
 namespace spvo {
 
@@ -98,13 +99,10 @@ __global__ __launch_bounds__(256) void gftt_response_kernel(const uint8_t *__res
 }
 
 // Choice 3: candidates -> state map (UNDECIDED / NONE for every pixel of the image) + candidate list, one atomic per workgroup
-// (wave ballots + LDS prefix, as nms_threshold_kernel)
+// (workgroup_append, list_steps.hip.h)
 __global__ __launch_bounds__(256) void gftt_collect_kernel(const float *__restrict__ lam, int h, int w, double quality, uint8_t *__restrict__ state, int *__restrict__ cand,
                                                            int *__restrict__ counters) {
-  __shared__ int s_wave[4];
-  __shared__ int s_base;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int x = blockIdx.x * 64 + lane, y = blockIdx.y * 4 + wave;
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   const float thr = (float)((double)__uint_as_float((unsigned)counters[4]) * quality);
   bool c = false;
   if (x >= 1 && x < w - 1 && y >= 1 && y < h - 1) {
@@ -113,19 +111,8 @@ __global__ __launch_bounds__(256) void gftt_collect_kernel(const float *__restri
     c = v > thr && v >= p[-w - 1] && v >= p[-w] && v >= p[-w + 1] && v >= p[-1] && v >= p[1] && v >= p[w - 1] && v >= p[w] && v >= p[w + 1];
   }
   if (x < w && y < h) state[(size_t)(y + CLS_PAD) * cls_state_pitch(w) + x + CLS_PAD] = c ? ST_UNDECIDED : ST_NONE;
-  const unsigned long long m = __ballot(c);
-  if (lane == 0) s_wave[wave] = __popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int tot = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    s_base = tot ? atomicAdd(&counters[0], tot) : 0;
-  }
-  __syncthreads();
-  if (c) {
-    int off = s_base + __popcll(m & ((1ull << lane) - 1ull));
-    for (int k = 0; k < wave; ++k) off += s_wave[k];
-    cand[off] = y * w + x;   // (at most (h - 2)(w - 2) candidates: the list holds h w)
-  }
+  const int slot = workgroup_append(c, &counters[0]);
+  if (c) cand[slot] = y * w + x;   // (at most (h - 2)(w - 2) candidates: the list holds h w)
 }
 
 // Choice 4 as a key: smaller = earlier.  Higher response first; of equal responses the later raster position first.
@@ -217,28 +204,9 @@ __global__ __launch_bounds__(1024) void gftt_finish_kernel(const float *__restri
   if (threadIdx.x == 0) counters[5] = rounds;
 }
 
-// rank by counting (orb_rank_kernel / nms_rank_kernel) over one key list whose length lies in device memory
+// rank by counting (rank_by_counting, list_steps.hip.h) over one key list whose length lies in device memory
 __global__ __launch_bounds__(256) void cls_rank_kernel(const unsigned long long *__restrict__ keys, int *__restrict__ rank, const int *__restrict__ n_ptr, int cap) {
-  __shared__ __attribute__((aligned(16))) unsigned long long tile[RANK_TILE];
-  const int n = min(*n_ptr, cap);
-  const int nbi = (n + 255) / 256, nbj = (n + RANK_TILE - 1) / RANK_TILE;
-  for (int b = blockIdx.x; b < nbi * nbj; b += gridDim.x) {
-    const int bi = b % nbi, j0 = (b / nbi) * RANK_TILE;
-    __syncthreads();
-    for (int t = threadIdx.x; t < RANK_TILE; t += 256) tile[t] = (j0 + t < n) ? keys[j0 + t] : ~0ull;
-    __syncthreads();
-    const int i = bi * 256 + threadIdx.x;
-    if (i >= n) continue;
-    const unsigned long long key = keys[i];
-    int cnt = 0;
-    const ulonglong2 *t2 = (const ulonglong2 *)tile;
-#pragma unroll 8
-    for (int t = 0; t < RANK_TILE / 2; ++t) {
-      const ulonglong2 v = t2[t];
-      cnt += (v.x < key ? 1 : 0) + (v.y < key ? 1 : 0);
-    }
-    if (cnt) atomicAdd(&rank[i], cnt);
-  }
+  rank_by_counting(keys, rank, min(*n_ptr, cap));
 }
 
 // the first max_corners kept in rank order -> xy (float), response (lambda2 x scale); counters[2] = how many
@@ -259,8 +227,8 @@ __global__ __launch_bounds__(256) void gftt_write_kernel(const float *__restrict
   }
 }
 
-// Choice 6: FAST corners of the score map -> keys (raster index << 32 | score), one atomic per wave (orb_collect_kernel's compaction;
-// the suppression rule differs: strictly greater than all eight neighbours).  The score map is 0 in the 3-pixel border.
+// Choice 6: FAST corners of the score map -> keys (raster index << 32 | score), one atomic per wave (wave_append, list_steps.hip.h;
+// the suppression rule differs from orb_collect_kernel's: strictly greater than all eight neighbours).  The score map is 0 in the 3-pixel border.
 __global__ __launch_bounds__(256) void fast_collect_kernel(const uint8_t *__restrict__ score, int h, int w, int nonmax, unsigned long long *__restrict__ keys, int cap,
                                                            int *__restrict__ counters) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -275,14 +243,8 @@ __global__ __launch_bounds__(256) void fast_collect_kernel(const uint8_t *__rest
       for (int dx = -1; dx <= 1; ++dx)
         if ((dy || dx) && (int)score[(size_t)(y + dy) * w + x + dx] >= s) keep = false;
   }
-  const unsigned long long m = __ballot(keep);
-  if (!m) return;
-  const int lane = threadIdx.x & 63;
-  int base = 0;
-  if (lane == __ffsll((long long)m) - 1) base = atomicAdd(&counters[1], __popcll(m));
-  base = __shfl(base, __ffsll((long long)m) - 1);
+  const int slot = wave_append(keep, &counters[1]);
   if (!keep) return;
-  const int slot = base + __popcll(m & ((1ull << lane) - 1ull));
   if (slot < cap) keys[slot] = ((unsigned long long)(unsigned)(y * w + x) << 32) | (unsigned)s;
   else counters[3] = 1;
 }
@@ -306,40 +268,22 @@ __global__ __launch_bounds__(256) void fast_write_kernel(int w, const unsigned l
 // ---- spvo_classic_detect: detector -> extractor -> feature slot without the host in between
 // cv::ORB::compute's border rule on the device (what spvo_orb_describe does on the host around its launch): of the n = counters[2] keypoints
 // in xy, those at least `edge` pixels from every border, ORDER-PRESERVING, as the extractor's integer list + the detector's responses.
-// ONE workgroup walks the list in chunks of 1024 with a running base: wave ballots + an LDS prefix over the 16 waves (gftt_collect_kernel's
-// compaction, made stable by the fixed chunk order).  out_cnt[0] = kept in all, out_cnt[2] = min(kept, cap) = what orb_describe_kernel describes.
+// ONE workgroup walks the list (stable_compact_walk, list_steps.hip.h).  out_cnt[0] = kept in all, out_cnt[2] = min(kept, cap) = what
+// orb_describe_kernel describes.
 __global__ __launch_bounds__(1024) void cls_compact_kernel(const float *__restrict__ xy, const float *__restrict__ resp, const int *__restrict__ counters, int h, int w, int edge,
                                                            int *__restrict__ kxy, float *__restrict__ kresp, int cap, int *__restrict__ out_cnt) {
-  __shared__ int s_wave[16];
-  const int n = counters[2];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int base = 0;
-  for (int i0 = 0; i0 < n; i0 += 1024) {
-    const int i = i0 + (int)threadIdx.x;
-    int x = 0, y = 0;
-    bool keep = false;
-    if (i < n) {
-      x = (int)xy[2 * i]; y = (int)xy[2 * i + 1];
-      keep = !(x < edge || x >= w - edge || y < edge || y >= h - edge);
-    }
-    const unsigned long long m = __ballot(keep);
-    __syncthreads();   // (the previous chunk's sums have been read)
-    if (lane == 0) s_wave[wave] = __popcll(m);
-    __syncthreads();
-    int off = base, tot = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const int v = s_wave[k];
-      off += k < wave ? v : 0;
-      tot += v;
-    }
-    off += __popcll(m & ((1ull << lane) - 1ull));
-    if (keep && off < cap) {
-      kxy[2 * off] = x; kxy[2 * off + 1] = y;
-      kresp[off] = resp[i];
-    }
-    base += tot;
-  }
+  int x = 0, y = 0;   // keypoint i's integer coordinates, from keep(i) to put(off, i)
+  const int base = stable_compact_walk(
+      counters[2],
+      [&](int i) {
+        x = (int)xy[2 * i]; y = (int)xy[2 * i + 1];
+        return !(x < edge || x >= w - edge || y < edge || y >= h - edge);
+      },
+      [&](int off, int i) {
+        if (off >= cap) return;
+        kxy[2 * off] = x; kxy[2 * off + 1] = y;
+        kresp[off] = resp[i];
+      });
   if (threadIdx.x == 0) { out_cnt[0] = base; out_cnt[2] = min(base, cap); }
 }
 

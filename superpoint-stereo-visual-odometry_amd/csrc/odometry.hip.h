@@ -484,6 +484,7 @@ __device__ __forceinline__ void ransac_select_body(const double *Kd, const float
   quat_to_rot(s_pose, R);
   t[0] = s_pose[4]; t[1] = s_pose[5]; t[2] = s_pose[6];
   // ordered compaction of the inlier indices
+  // (not list_steps.hip.h's stable_compact_walk: NT threads, and the running base lives in LDS with its barriers placed for the refit below)
   for (int base = 0; base < n; base += NT) {
     const int i = base + tid;
     const bool in = (i < n) && reproj_inlier(K, R, t, xyz + 3 * i, xy + 2 * i, thr2);

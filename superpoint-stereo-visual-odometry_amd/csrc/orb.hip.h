@@ -14,7 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "conv_mfma.hip.h"    // mul_rn, add_rn
-#include "spvo_types.hip.h"   // rank_key, RANK_TILE, ST_*, OrbKeypoint
+#include "spvo_types.hip.h"   // rank_key, ST_*, OrbKeypoint
+#include "list_steps.hip.h"   // wave_append, rank_by_counting
 
 namespace spvo {
 
@@ -80,45 +81,19 @@ __global__ __launch_bounds__(256) void orb_collect_kernel(const OrbLevels lv) {
           if ((int)score[(size_t)(y + dy) * w + x + dx] >= s + later) is_max = false;
         }
   }
-  // one atomic per wave: the survivors of a wave take consecutive slots
-  const unsigned long long m = __ballot(is_max);
-  if (!m) return;
-  const int lane = threadIdx.x & 63;
-  int base = 0;
-  if (lane == __ffsll((long long)m) - 1) base = atomicAdd(&L.counters[1], __popcll(m));
-  base = __shfl(base, __ffsll((long long)m) - 1);
+  const int slot = wave_append(is_max, &L.counters[1]);   // one atomic per wave: the survivors of a wave take consecutive slots
   if (!is_max) return;
-  const int slot = base + __popcll(m & ((1ull << lane) - 1ull));
   if (slot < L.cap) L.keys[slot] = rank_key((float)s, x, y, h);   // (0xFFFFFFFF - bits(response)) << 32 | x h + y: smaller = earlier
   else L.counters[3] = 1;
 }
 
-// K9's rank-by-counting (nms_rank_kernel) with a grid that does not depend on the buffers' capacity: a level has anything between
-// no corner and one per 2x2 pixels.  A fixed number of workgroups per level walks the (256 keys) x (1024-key tile) blocks that the
-// survivor count on the device calls for.
+// rank by counting (rank_by_counting, list_steps.hip.h) with a grid that does not depend on the buffers' capacity: a level has anything
+// between no corner and one per 2x2 pixels.  A fixed number of workgroups per level walks the blocks that the survivor count on the
+// device calls for.
 __global__ __launch_bounds__(256) void orb_rank_kernel(const OrbLevels lv) {
-  __shared__ __attribute__((aligned(16))) unsigned long long tile[RANK_TILE];
   const OrbLevel L = lv.l[blockIdx.y];
   if (L.want <= 0) return;
-  const int n = min(L.counters[1], L.cap);
-  const int nbi = (n + 255) / 256, nbj = (n + RANK_TILE - 1) / RANK_TILE;
-  for (int b = blockIdx.x; b < nbi * nbj; b += gridDim.x) {
-    const int bi = b % nbi, j0 = (b / nbi) * RANK_TILE;
-    __syncthreads();
-    for (int t = threadIdx.x; t < RANK_TILE; t += 256) tile[t] = (j0 + t < n) ? L.keys[j0 + t] : ~0ull;
-    __syncthreads();
-    const int i = bi * 256 + threadIdx.x;
-    if (i >= n) continue;
-    const unsigned long long key = L.keys[i];
-    int cnt = 0;
-    const ulonglong2 *t2 = (const ulonglong2 *)tile;
-#pragma unroll 8
-    for (int t = 0; t < RANK_TILE / 2; ++t) {
-      const ulonglong2 v = t2[t];
-      cnt += (v.x < key ? 1 : 0) + (v.y < key ? 1 : 0);
-    }
-    if (cnt) atomicAdd(&L.rank[i], cnt);
-  }
+  rank_by_counting(L.keys, L.rank, min(L.counters[1], L.cap));
 }
 
 // positions from ranks: the first `want` of a level in (response, index) order

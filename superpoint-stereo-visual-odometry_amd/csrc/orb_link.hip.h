@@ -29,7 +29,8 @@ __device__ __forceinline__ bool orb_link_pass(const OrbLinkSrc &s, int i, int n,
   return xi >= (float)ORB_EDGE && xi < (float)(cols - ORB_EDGE) && yi >= (float)ORB_EDGE && yi < (float)(rows - ORB_EDGE);
 }
 
-// ONE workgroup, two walks over the list in chunks of 1024 (brisk_det_compact_kernel's walk, per octave): the first counts the passing
+// (not list_steps.hip.h's stable_compact_walk: a base per octave, which takes a counting walk before the placing one)
+// ONE workgroup, two walks over the list in chunks of 1024 (that header's walk, per octave): the first counts the passing
 // records of every octave, the second gives each passing record the row first[octave] + the number of earlier passing records of its
 // octave -- per-wave ballots, a [16 waves][8 octaves] table in LDS per chunk, a running base per octave.  Row r: kept[r] = the record's
 // index in the list, rec[3 r ..] = (cx, cy, level) clamped into the level.

@@ -10,6 +10,7 @@
 #include <stdint.h>
 #include "conv_mfma.hip.h"
 #include "spvo_types.hip.h"
+#include "list_steps.hip.h"   // workgroup_append, rank_by_counting
 
 namespace spvo {
 
@@ -165,40 +166,27 @@ __global__ __launch_bounds__(256) void heatmap_kernel(const float *__restrict__ 
 // ---------------------------------------------------------------------------
 // (ST_*, NMS_PAD, NMS_COUNTER_INTS, nms_state_pitch, NmsBuffers, NmsPair, rank_key, RANK_TILE: spvo_types.hip.h)
 
-// K8: threshold + stream compaction.  One atomic per workgroup (wave ballots + LDS prefix), so
+// K8: threshold + stream compaction.  One atomic per workgroup (workgroup_append, list_steps.hip.h), so
 // the candidate list comes out grouped by 64x4-pixel tiles: neighbours in the image are
 // neighbours in the list, which keeps most NMS decisions inside one workgroup of K10.
 __global__ __launch_bounds__(256) void nms_threshold_kernel(const float *__restrict__ heat, int H,
                                                             int W, float thresh, NmsPair np) {
-  __shared__ int s_wave[4];
-  __shared__ int s_base;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int x = blockIdx.x * 64 + lane;
-  const int y = blockIdx.y * 4 + wave;
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
   const NmsBuffers nb = np.b[blockIdx.z];
   const bool valid = x < W && y < H;
   const int p = y * W + x;
   const bool c = valid && heat[(size_t)blockIdx.z * H * W + p] > thresh;  // strict, nn.cpp:203
   if (valid) nb.state[(y + NMS_PAD) * nms_state_pitch(W) + x + NMS_PAD] = c ? ST_UNDECIDED : ST_NONE;
-  const unsigned long long m = __ballot(c);
-  if (lane == 0) s_wave[wave] = __popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int tot = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    s_base = tot ? atomicAdd(&nb.counters[0], tot) : 0;
-  }
-  __syncthreads();
-  if (c) {
-    int off = s_base + __popcll(m & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; ++w) off += s_wave[w];
-    nb.cand[off] = p;
-  }
+  const int slot = workgroup_append(c, &nb.counters[0]);
+  if (c) nb.cand[slot] = p;
 }
 
 // K7 + K8 fused (product path): one thread per coarse cell computes its 8x8 block of the heat
 // map, writes it, writes the NMS state bytes and appends its candidates to the list.  ONE atomic
 // per workgroup (256 cells = 16 384 pixels): 72 atomics per stereo pair instead of one per
 // 64x4 tile, and no separate pass over the heat map.
+// (not list_steps.hip.h's workgroup_append: a thread brings up to 64 candidates, so the prefix is an inclusive scan of counts)
 __global__ __launch_bounds__(256) void heatmap_nms_kernel(const float *__restrict__ det,
                                                           float *__restrict__ heat, int Hc, int Wc,
                                                           int hp, int wp, float thresh, NmsPair np) {
@@ -499,33 +487,14 @@ __global__ __launch_bounds__(256) void nms_collect_kernel(const float *__restric
   }
 }
 
-// K9: rank by counting -- the output position of a survivor is the number of survivors with a
+// K9: rank by counting (rank_by_counting, list_steps.hip.h) -- the output position of a survivor is the number of survivors with a
 // smaller key.  2-D decomposition: block (bi, bj) counts 256 keys against a 1024-key LDS tile (RANK_TILE).
 // The grid does not depend on the buffer's capacity (one survivor per 5x5 cell at most: 17 k; a few thousand in practice): a fixed
 // number of workgroups per image walks the blocks the survivor count on the device calls for -- a capacity-sized grid is 2278
 // workgroups per launch, most of which only start and exit, next to convolutions whose workgroups need whole CUs.
 __global__ __launch_bounds__(256) void nms_rank_kernel(int surv_cap, NmsPair np) {
-  __shared__ __attribute__((aligned(16))) unsigned long long tile[RANK_TILE];
   const NmsBuffers nb = np.b[blockIdx.y];
-  const int n = min(nb.counters[1], surv_cap);
-  const int nbi = (n + 255) / 256, nbj = (n + RANK_TILE - 1) / RANK_TILE;
-  for (int b = blockIdx.x; b < nbi * nbj; b += gridDim.x) {
-    const int bi = b % nbi, j0 = (b / nbi) * RANK_TILE;
-    __syncthreads();
-    for (int t = threadIdx.x; t < RANK_TILE; t += 256) tile[t] = (j0 + t < n) ? nb.surv_key[j0 + t] : ~0ull;
-    __syncthreads();
-    const int i = bi * 256 + threadIdx.x;
-    if (i >= n) continue;
-    const unsigned long long key = nb.surv_key[i];
-    int cnt = 0;
-    const ulonglong2 *t2 = (const ulonglong2 *)tile;
-#pragma unroll 8
-    for (int t = 0; t < RANK_TILE / 2; ++t) {
-      const ulonglong2 v = t2[t];
-      cnt += (v.x < key ? 1 : 0) + (v.y < key ? 1 : 0);
-    }
-    if (cnt) atomicAdd(&nb.rank[i], cnt);
-  }
+  rank_by_counting(nb.surv_key, nb.rank, min(nb.counters[1], surv_cap));
 }
 
 // host_counters: the set's pinned mirror of the counter blocks ([image][NMS_COUNTER_INTS]); this kernel is the last one that changes a

@@ -25,6 +25,7 @@
 #include <stdint.h>
 #include "conv_mfma.hip.h"    // mul_rn, add_rn, sub_rn
 #include "spvo_types.hip.h"   // SiftPyr
+#include "list_steps.hip.h"   // stable_compact_walk
 
 namespace spvo {
 
@@ -498,31 +499,11 @@ struct SiftLinkIO {
 };
 
 // kept[0 .. *n_out) = the indices i < min(*n_ptr, n_cap) with keep[i] != 0 (keep = NULL: every index), ascending: ONE workgroup walks the
-// list in chunks of 1024 with a running base (brisk_det_compact_kernel's compaction, of indices)
+// list (stable_compact_walk, list_steps.hip.h, of indices)
 __global__ __launch_bounds__(1024) void sift_link_compact_kernel(const int *__restrict__ keep, const int *__restrict__ n_ptr, int n_cap, int *__restrict__ kept,
                                                                  int *__restrict__ n_out) {
-  __shared__ int s_wave[16];
-  const int n = min(max(*n_ptr, 0), n_cap);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int base = 0;
-  for (int i0 = 0; i0 < n; i0 += 1024) {
-    const int i = i0 + (int)threadIdx.x;
-    const bool kp = i < n && (!keep || keep[i] != 0);
-    const unsigned long long m = __ballot(kp);
-    __syncthreads();   // (the previous chunk's sums have been read)
-    if (lane == 0) s_wave[wave] = __popcll(m);
-    __syncthreads();
-    int off = base, tot = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const int v = s_wave[k];
-      off += k < wave ? v : 0;
-      tot += v;
-    }
-    off += __popcll(m & ((1ull << lane) - 1ull));
-    if (kp) kept[off] = i;   // (off <= i < n_cap)
-    base += tot;
-  }
+  const int base = stable_compact_walk(
+      min(max(*n_ptr, 0), n_cap), [&](int i) { return !keep || keep[i] != 0; }, [&](int off, int i) { kept[off] = i; });   // (off <= i < n_cap)
   if (threadIdx.x == 0) *n_out = base;
 }
 
@@ -608,11 +589,11 @@ __global__ __launch_bounds__(64) void sift_describe_given_kernel(SiftPyr P, int 
 //   sift_key_kernel     a thread per raw row: its key (x, y, size, angle, response, octave) from the candidate, with the arithmetic of
 //                       spvo_sift.hip's sift_record (separately rounded float operations; `size` through a double pow -- a SORT KEY only:
 //                       rows of one candidate get one size, so ties and duplicates are those of the host's keys)
-//   sift_rank_kernel    rank by counting (cls_rank_kernel's idiom): a tile of keys in LDS, every row counts the rows in front of it under
+//   sift_rank_kernel    rank by counting: a tile of keys in LDS, every row counts the rows in front of it under
 //                       the host comparator (float != and <, so -0 = 0); rows equal in all six fields go by raw index: a permutation
 //   sift_unique_kernel  cv::KeyPointsFilter::removeDuplicatedSorted: a sorted row whose (x, y, size, angle) equal its predecessor's is
 //                       dropped (equality is transitive and equal rows are adjacent: the predecessor stands for the last kept row);
-//                       order-preserving prefix by one workgroup in chunks of 1024 with a running base (cls_compact_kernel's)
+//                       order-preserving, by one workgroup (stable_compact_walk, list_steps.hip.h)
 //   sift_gather_kernel  a wave per final row: descriptor (pitch 256, columns 128.. zero), squared norm (an exact integer < 2^24) and source
 //                       into the slot, the same to the host's pinned mirrors, the counts to both
 // Every length is read from device memory and clamped to the list's capacity (the counters keep counting beyond it).
@@ -639,6 +620,7 @@ __global__ __launch_bounds__(256) void sift_key_kernel(const int4 *__restrict__ 
   }
 }
 
+// (not list_steps.hip.h's rank_by_counting: the order is a six-field comparison with a tie rule, not a 64-bit key)
 // sorted[rank of raw row i] = i.  A workgroup takes 256 rows and walks all keys in LDS tiles; every lane reads the same tile entry (a broadcast)
 __global__ __launch_bounds__(256) void sift_rank_kernel(const SiftKey *__restrict__ keys, const int *__restrict__ n_ptr, int cap, int *__restrict__ sorted) {
   __shared__ float tx[SIFT_ORD_TILE], ty[SIFT_ORD_TILE], ts[SIFT_ORD_TILE], ta[SIFT_ORD_TILE], tr[SIFT_ORD_TILE];
@@ -678,37 +660,16 @@ __global__ __launch_bounds__(256) void sift_rank_kernel(const SiftKey *__restric
 // order[0 .. *n_out) = the raw rows that stay, in output order
 __global__ __launch_bounds__(1024) void sift_unique_kernel(const SiftKey *__restrict__ keys, const int *__restrict__ sorted, const int *__restrict__ n_ptr, int cap,
                                                            int *__restrict__ order, int *__restrict__ n_out) {
-  __shared__ int s_wave[16];
-  const int n = min(*n_ptr, cap);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int base = 0;
-  for (int s0 = 0; s0 < n; s0 += 1024) {
-    const int s = s0 + (int)threadIdx.x;
-    int raw = 0;
-    bool keep = false;
-    if (s < n) {
-      raw = sorted[s];
-      keep = true;
-      if (s > 0) {
+  int raw = 0;   // the raw row at sorted position s, from keep(s) to put(o, s)
+  const int base = stable_compact_walk(
+      min(*n_ptr, cap),
+      [&](int s) {
+        raw = sorted[s];
+        if (s == 0) return true;
         const SiftKey a = keys[sorted[s - 1]], b = keys[raw];
-        keep = !(a.x == b.x && a.y == b.y && a.size == b.size && a.angle == b.angle);
-      }
-    }
-    const unsigned long long m = __ballot(keep);
-    __syncthreads();   // (the previous chunk's sums have been read)
-    if (lane == 0) s_wave[wave] = __popcll(m);
-    __syncthreads();
-    int o = base, tot = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const int v = s_wave[k];
-      o += k < wave ? v : 0;
-      tot += v;
-    }
-    o += __popcll(m & ((1ull << lane) - 1ull));
-    if (keep) order[o] = raw;   // (o <= s < n)
-    base += tot;
-  }
+        return !(a.x == b.x && a.y == b.y && a.size == b.size && a.angle == b.angle);
+      },
+      [&](int o, int) { order[o] = raw; });   // (o <= s < n)
   if (threadIdx.x == 0) *n_out = base;
 }
 

@@ -23,6 +23,8 @@
 //                      slots, SIFT rows into the SIFT slots)
 //   pair_call.hip.h    the resident stereo-pair protocol all of those pair calls run through (PairCall: refusals, staging, temporal partner, prematch, the
 //                      one wait, capacity rule, slot bookkeeping), with the binary slots' side of it; the SIFT slots' side is in spvo_sift.hip
+//   list_steps.hip.h   the keypoint-list steps the detectors' and extractors' kernels share: append per wave / per workgroup, rank by counting, the
+//                      one-workgroup order-preserving compaction (device functions that take lambdas; included by the kernel headers that use them)
 //   spvo_match.hip     descriptor matching (L2, Hamming)
 //   spvo_solve.hip     triangulation, PnP-RANSAC, gating, Levenberg-Marquardt, the fused solve
 #pragma once
