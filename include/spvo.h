@@ -628,6 +628,27 @@ int spvo_match_slots(spvo_ctx *ctx, int slot_a, int slot_b, int selector, int cr
 int spvo_match_hamming_slots(spvo_ctx *ctx, int slot_a, int slot_b, int selector, int cross_check, float ratio,
                              int32_t *train_idx, float *distance);
 
+/* MatcherType::FLANN on BINARY descriptors.  The reference's matchDescriptors converts both descriptor matrices to CV_32F and hands them
+ * to cv::FlannBasedMatcher (base.cpp:29-32, 444-451): an L2 search over the descriptor BYTES taken as numbers 0 .. 255 -- not a Hamming
+ * search -- through two randomized KD-trees, approximate and not reproducible.  This library computes what those trees approximate: the
+ * EXACT L2 nearest neighbours, oracle/matching.py's bf_match on the rows cast to float32, index for index and distance for distance as
+ * bits (squared distances <= 64 * 255^2 < 2^24 are exact integers; distance = sqrtf of them).  Parity with cv::FlannBasedMatcher is
+ * therefore unpinned.  Arguments, the 1 .. 64-byte limit, empty sides, stream and buffers as spvo_match_hamming; selector / cross_check /
+ * ratio as in spvo_match (FLANN itself has no cross-check: the host front end passes 0).  Equals spvo_match_l2 on the float casts. */
+int spvo_match_l2_u8(spvo_ctx *ctx, const uint8_t *desc_a, int na, const uint8_t *desc_b, int nb, int desc_bytes,
+                     int selector, int cross_check, float ratio, int32_t *train_idx, float *distance);
+/* spvo_match_l2_u8 on the device-resident rows of two binary slots, counts read on the device; the rules of spvo_match_hamming_slots
+ * (widths, unfilled slots, their messages).  Returns the result a pair call stored when spvo_set_prematch is on, the prematch norm is
+ * SPVO_NORM_L2 and this is exactly that match of exactly those slot contents; computes on the spot otherwise. */
+int spvo_match_l2_u8_slots(spvo_ctx *ctx, int slot_a, int slot_b, int selector, int cross_check, float ratio,
+                           int32_t *train_idx, float *distance);
+/* Which matcher the binary pair calls (spvo_classic_detect, spvo_brisk_detect_pair, spvo_akaze_detect_pair and their variants) enqueue
+ * behind their features under spvo_set_prematch: SPVO_NORM_HAMMING (the default: spvo_match_hamming_slots is served) or SPVO_NORM_L2
+ * (spvo_match_l2_u8_slots is served).  A stored result is served only to a query of the norm that produced it; changing the norm drops
+ * the stored results.  SPVO_ERR_INVALID for any other value. */
+typedef enum { SPVO_NORM_HAMMING = 0, SPVO_NORM_L2 = 1 } spvo_binary_norm;
+int spvo_set_binary_prematch_norm(spvo_ctx *ctx, int norm);
+
 /* ------------------------------------------------------- SIFT: one submission per stereo pair, features resident
  * spvo_sift_detect for BOTH images of a stereo pair in one call.  Both images go up through pinned staging; the chain -- the left image's
  * pyramid, features and ORDERING, then the right image's, the one resident pyramid reused in stream order -- is enqueued on the solver's

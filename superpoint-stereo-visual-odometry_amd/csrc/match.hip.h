@@ -941,4 +941,176 @@ __global__ __launch_bounds__(256) void match_hamming_cross_slots_kernel(const un
   out[q] = make_int2(hit ? (int)(key & 0xFFFFFFFFull) : -1, hit ? __float_as_int((float)(unsigned)(key >> 32)) : 0);
 }
 
+// ---------------------------------------------------------------------------
+// K12u: MatcherType::FLANN on binary descriptor rows -- the EXACT L2 nearest neighbours of the rows' BYTES taken as numbers 0 .. 255, which
+// is what cv::FlannBasedMatcher approximates after matchDescriptors has converted both matrices to CV_32F (base.cpp:29-32, 444-451).  Not a
+// Hamming search.  Integer work on the int8 matrix cores, exact by nature, so one pass as K12h / K12t:
+//   * arithmetic: with a' = a xor 0x80 read as int8 (= a - 128) differences are unchanged and d2 = |a'|^2 + |b'|^2 - 2 a'.b' exactly in int32
+//     (|a'|^2 <= 64 * 128^2 = 2^20).  d2 <= 64 * 255^2 = 4 161 600 < 2^22: exact in float32 too, in any summation order, so the result is
+//     oracle/matching.py's bf_match on the float casts bit for bit.  The distance handed out is sqrtf((float)d2), K12b's sqrtf.
+//   * blocking: a workgroup (4 waves) owns U8L2_QT = 16 query rows = the M of ONE v_mfma_i32_16x16x64_i8, whose K = 64 is exactly one
+//     64-byte row; every wave keeps the same A operand (lane l: row l & 15, bytes 16 (l >> 4) .. + 15, one 16-byte load) and the rows'
+//     norms in registers for the whole kernel.  The train set is walked in tiles of U8L2_TT = 256 rows = 16 blocks of 16, four per wave:
+//     one ds_read_b128 and one matrix instruction give a lane the dot products of four query rows (4 (l >> 4) + r) with one train row.
+//     Rows of 32 bytes (PITCH = 32) use the same instruction with lanes 32 .. 63 feeding zeros: the kernel is bound by the epilogue's
+//     vector instructions, not by the matrix pipe, so the 32x32x32 form would change nothing that matters (not measured).
+//   * staging: the tile is fetched ONCE per workgroup with coalesced 16-byte loads (thread = 16 consecutive bytes of the tile), goes to LDS
+//     in the signed domain with bytes W .. PITCH - 1 cleared, and the rows' integer norms are computed in the same pass (the 2 or 4 lanes
+//     of a row combined by shuffles).  The next tile's loads are issued before the current tile is scored and land in the other of two
+//     buffers: one barrier per tile.  LDS: 2 x (16 KB + 1 KB) + 1 KB = 35 KB at PITCH 64, 19 KB at PITCH 32; no distance reaches HBM.
+//   * epilogue, in registers: d2 = na + nb - 2 dot, then the lane's running best two per query row.  A lane meets its train rows in
+//     ascending order, so a strict '<' on d2 alone IS the (d2, index) order there; the 16 lanes of a query row, the four waves (through
+//     LDS) and nothing else are merged under that order as 64-bit keys d2 << 32 | row (a 32-bit key does not hold 22 + 22 bits).
+//   * modes, sentinel and packed output {train_idx, distance bits} of K12t; mode 2 casts the vote d2 << 32 | row, read out by
+//     match_l2u8_cross_kernel.  Row counts by value or through device pointers (dev_count), both capped by `cap`.
+//   * bound: 2000 x 2000 rows are 125 workgroups on 256 CUs -- problem-bound occupancy as K12t; per 16 x 16 block one matrix instruction
+//     against ~40 vector instructions of epilogue.
+//   * compiler report (gfx950, -O3): PITCH 64: 102 VGPRs + 4 AGPRs, 37 SGPRs, 35840 bytes LDS, 0 bytes scratch, 4 waves / SIMD; PITCH 32: 88 VGPRs +
+//     4 AGPRs, 19456 bytes LDS, 0 bytes scratch, 5 waves / SIMD (the four blocks of a tile step are unrolled and their operands read ahead).
+//     Four workgroups of PITCH 64 fit a CU by LDS and by registers alike; the grid gives a CU one.
+// ---------------------------------------------------------------------------
+constexpr int U8L2_QT = 16, U8L2_TT = 256;
+constexpr unsigned long long U8L2_NONE = 0x7FFFFFFFFFFFFFFFull;   // {d2 = INT_MAX, row = -1}: above every real key
+typedef int u8l2_i4 __attribute__((ext_vector_type(4)));
+
+// 16 bytes of a row that start at byte p0 of it: into the signed domain, bytes from W on cleared
+__device__ __forceinline__ u8l2_i4 u8l2_signed(u8l2_i4 v, int p0, int W) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int left = W - (p0 + 4 * e);
+    const uint32_t mask = left >= 4 ? ~0u : (left <= 0 ? 0u : (1u << (8 * left)) - 1u);
+    v[e] = (int)(((uint32_t)v[e] ^ 0x80808080u) & mask);
+  }
+  return v;
+}
+__device__ __forceinline__ int u8l2_sqnorm(u8l2_i4 v) {
+  int s = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int b = (int)(int8_t)((uint32_t)v[e] >> (8 * k));
+      s += b * b;
+    }
+  return s;
+}
+__device__ __forceinline__ void u8l2_top2(unsigned long long &m0, unsigned long long &m1, unsigned long long k0, unsigned long long k1) {   // ham_top2 on 64-bit keys
+  const unsigned long long hi = max(m0, k0);
+  m0 = min(m0, k0);
+  m1 = min(hi, min(m1, k1));
+}
+
+template <int PITCH>
+__global__ __launch_bounds__(256) void match_l2u8_kernel(const uint32_t *__restrict__ A, int na_host, const int *__restrict__ na_ptr, const uint32_t *__restrict__ B, int nb_host,
+                                                         const int *__restrict__ nb_ptr, int cap, int W, int mode, float ratio, int2 *__restrict__ out,
+                                                         unsigned long long *__restrict__ vote) {
+  static_assert(PITCH == 32 || PITCH == 64, "rows 32 or 64 bytes apart");
+  constexpr int CH = PITCH / 16;   // 16-byte pieces of a row
+  __shared__ u8l2_i4 tile[2][U8L2_TT * CH];
+  __shared__ int tnorm[2][U8L2_TT];
+  __shared__ unsigned long long s_merge[4][U8L2_QT][2];
+  const int na = min(dev_count(na_host, na_ptr), cap), nb = min(dev_count(nb_host, nb_ptr), cap);
+  const int q0 = blockIdx.x * U8L2_QT;
+  if (q0 >= na) return;   // (the whole workgroup: no barrier is skipped by part of it)
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int col = lane & 15, kq = lane >> 4;
+  // the A operand and the query rows' norms (rows past the end repeat the last one; they are not written)
+  u8l2_i4 av = {0, 0, 0, 0};
+  if (kq < CH) av = u8l2_signed(*reinterpret_cast<const u8l2_i4 *>(A + (size_t)min(q0 + col, na - 1) * (PITCH / 4) + 4 * kq), 16 * kq, W);
+  int nrm = u8l2_sqnorm(av);
+  nrm += __shfl_xor(nrm, 16);
+  nrm += __shfl_xor(nrm, 32);
+  int nq[4], d0[4], d1[4], i0[4], i1[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    nq[r] = __shfl(nrm, 4 * kq + r);
+    d0[r] = d1[r] = 0x7FFFFFFF;
+    i0[r] = i1[r] = -1;
+  }
+  const int ntiles = (nb + U8L2_TT - 1) / U8L2_TT;
+  // thread -> piece tid + 256 k of the tile: row tid / CH + k (256 / CH), piece tid % CH
+  const int srow = tid / CH, spiece = tid % CH;
+  u8l2_i4 pre[CH];
+  auto fetch = [&](int t) {
+#pragma unroll
+    for (int k = 0; k < CH; ++k) {
+      const int row = t * U8L2_TT + srow + k * (256 / CH);
+      pre[k] = u8l2_i4{0, 0, 0, 0};
+      if (row < nb) pre[k] = *reinterpret_cast<const u8l2_i4 *>(B + (size_t)row * (PITCH / 4) + 4 * spiece);
+    }
+  };
+  auto stage = [&](int buf) {
+#pragma unroll
+    for (int k = 0; k < CH; ++k) {
+      const u8l2_i4 v = u8l2_signed(pre[k], 16 * spiece, W);
+      int s = u8l2_sqnorm(v);
+#pragma unroll
+      for (int o = 1; o < CH; o <<= 1) s += __shfl_xor(s, o);
+      const int row = srow + k * (256 / CH);
+      tile[buf][row * CH + spiece] = v;
+      if (spiece == 0) tnorm[buf][row] = s;
+    }
+  };
+  if (ntiles > 0) { fetch(0); stage(0); }
+  __syncthreads();
+  for (int t = 0; t < ntiles; ++t) {
+    if (t + 1 < ntiles) fetch(t + 1);
+    const int buf = t & 1;
+#pragma unroll
+    for (int j = 0; j < U8L2_TT / 64; ++j) {
+      const int r_in = 16 * (wave * (U8L2_TT / 64) + j) + col, grow = t * U8L2_TT + r_in;
+      if (grow - col >= nb) break;   // (wave-uniform: the whole block lies beyond the count)
+      u8l2_i4 bv = {0, 0, 0, 0};
+      if (kq < CH) bv = tile[buf][r_in * CH + kq];
+      const int nbv = tnorm[buf][r_in];
+      const u8l2_i4 dot = __builtin_amdgcn_mfma_i32_16x16x64_i8(av, bv, u8l2_i4{0, 0, 0, 0}, 0, 0, 0);
+      const bool valid = grow < nb;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int d = valid ? nq[r] + nbv - 2 * dot[r] : 0x7FFFFFFF;
+        if (d < d0[r]) { d1[r] = d0[r]; i1[r] = i0[r]; d0[r] = d; i0[r] = grow; }
+        else if (d < d1[r]) { d1[r] = d; i1[r] = grow; }
+      }
+    }
+    if (t + 1 < ntiles) stage((t + 1) & 1);
+    __syncthreads();
+  }
+  // the 16 lanes of a query row -> one pair, then the four waves through LDS
+  unsigned long long m0[4], m1[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    m0[r] = ((unsigned long long)(unsigned)d0[r] << 32) | (unsigned)i0[r];
+    m1[r] = ((unsigned long long)(unsigned)d1[r] << 32) | (unsigned)i1[r];
+#pragma unroll
+    for (int o = 8; o >= 1; o >>= 1) {
+      const unsigned long long k0 = __shfl_xor(m0[r], o), k1 = __shfl_xor(m1[r], o);
+      u8l2_top2(m0[r], m1[r], k0, k1);
+    }
+    if (col == 0) { s_merge[wave][4 * kq + r][0] = m0[r]; s_merge[wave][4 * kq + r][1] = m1[r]; }
+  }
+  __syncthreads();
+  const int q = q0 + tid;
+  if (tid >= U8L2_QT || q >= na) return;
+  unsigned long long b0 = s_merge[0][tid][0], b1 = s_merge[0][tid][1];
+#pragma unroll
+  for (int w = 1; w < 4; ++w) u8l2_top2(b0, b1, s_merge[w][tid][0], s_merge[w][tid][1]);
+  const int bi0 = b0 == U8L2_NONE ? -1 : (int)(b0 & 0xFFFFFFFFull), bi1 = b1 == U8L2_NONE ? -1 : (int)(b1 & 0xFFFFFFFFull);
+  if (mode == 2) {
+    if (bi0 >= 0) atomicMin(&vote[bi0], (b0 & 0xFFFFFFFF00000000ull) | (unsigned)q);
+    return;
+  }
+  const float s0 = sqrtf((float)(int)(b0 >> 32)), s1 = sqrtf((float)(int)(b1 >> 32));
+  const int idx = mode == 0 ? bi0 : ((bi1 >= 0 && s0 < mul_rn(ratio, s1)) ? bi0 : -1);   // base.cpp:469
+  out[q] = make_int2(idx, bi0 >= 0 ? __float_as_int(s0) : 0);
+}
+
+// the cross-check's second half for K12u: every query row reads its vote {d2, train row}
+__global__ __launch_bounds__(256) void match_l2u8_cross_kernel(const unsigned long long *__restrict__ vote, int na_host, const int *__restrict__ na_ptr, int cap, int2 *__restrict__ out) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= min(dev_count(na_host, na_ptr), cap)) return;
+  const unsigned long long key = vote[q];
+  const bool hit = key != ~0ull;
+  out[q] = make_int2(hit ? (int)(key & 0xFFFFFFFFull) : -1, hit ? __float_as_int(sqrtf((float)(unsigned)(key >> 32))) : 0);
+}
+
 }  // namespace spvo

@@ -106,7 +106,7 @@ struct PairCall {
   }
 };
 
-// the binary slots (spvo_ctx::bin): rows of `row_bytes`, matched by enqueue_hamming_slots on the solver's stream, results in h_match + k * cap
+// the binary slots (spvo_ctx::bin): rows of `row_bytes`, matched by enqueue_binary_prematch (Hamming, or byte-L2 under SPVO_NORM_L2) on the solver's stream, results in h_match + k * cap
 struct BinPairFamily {
   int row_bytes;
   static constexpr int SLOTS = N_BIN_SLOTS, CAP_MAX = 1 << HAM_KEY_SHIFT;
@@ -123,7 +123,7 @@ struct BinPairFamily {
     if (!c->prematch) return SPVO_OK;
     for (int k = 0; k < 2; ++k)
       if (partner[k] >= 0)
-        if (int rc = enqueue_hamming_slots(c, slot_l, partner[k], c->pm_selector, c->pm_cross, c->pm_ratio, c->bin.h_match + (size_t)k * cap)) return rc;
+        if (int rc = enqueue_binary_prematch(c, slot_l, partner[k], c->bin.h_match + (size_t)k * cap)) return rc;
     HIP_TRY(c, hipEventRecord(c->bin.pair.ev_match, c->stream2));
     return SPVO_OK;
   }
@@ -132,7 +132,7 @@ struct BinPairFamily {
     auto &bb = c->bin;
     for (int k = 0; k < 2; ++k)
       if (partner[k] >= 0)
-        bb.pair.mcache.record(k, slot_l, partner[k], bb.slots[slot_l].gen, bb.slots[partner[k]].gen, c->pm_selector, c->pm_cross, c->pm_ratio, bb.h_match + (size_t)k * cap);
+        bb.pair.mcache.record(k, slot_l, partner[k], bb.slots[slot_l].gen, bb.slots[partner[k]].gen, c->pm_selector, c->pm_cross, c->pm_ratio, bb.h_match + (size_t)k * cap, c->bin_pm_norm);
   }
 };
 

@@ -170,6 +170,7 @@ struct MatchCache {
   float ratio = 0.f;
   unsigned long long gen_a = 0, gen_b = 0;
   int2 *h_out = nullptr;      // pinned [cap] packed {train_idx, distance bits}; meaningful while `valid`
+  int norm = 0;               // binary slots: SPVO_NORM_HAMMING or SPVO_NORM_L2, the matcher that produced it (0 for the float owners)
 };
 
 // the two prematches of one owner (a submission set, the binary slots, the SIFT slots); slot numbers are the owner's kind of slot
@@ -177,13 +178,14 @@ struct PrematchCache {
   MatchCache e[2];            // [stereo, temporal]
   void invalidate() { for (MatchCache &m : e) m.valid = false; }
   // the stored result of exactly this match of exactly these slot contents, or NULL
-  const MatchCache *find(int slot_a, int slot_b, unsigned long long gen_a, unsigned long long gen_b, int selector, int cross, float ratio) const {
+  const MatchCache *find(int slot_a, int slot_b, unsigned long long gen_a, unsigned long long gen_b, int selector, int cross, float ratio, int norm = 0) const {
     for (const MatchCache &m : e)
-      if (m.valid && m.slot_a == slot_a && m.slot_b == slot_b && m.gen_a == gen_a && m.gen_b == gen_b && m.selector == selector && m.cross == cross && m.ratio == ratio) return &m;
+      if (m.valid && m.slot_a == slot_a && m.slot_b == slot_b && m.gen_a == gen_a && m.gen_b == gen_b && m.selector == selector && m.cross == cross && m.ratio == ratio && m.norm == norm)
+        return &m;
     return nullptr;
   }
-  void record(int entry, int slot_a, int slot_b, unsigned long long gen_a, unsigned long long gen_b, int selector, int cross, float ratio, int2 *h_out) {
-    e[entry] = MatchCache{true, slot_a, slot_b, selector, cross, ratio, gen_a, gen_b, h_out};
+  void record(int entry, int slot_a, int slot_b, unsigned long long gen_a, unsigned long long gen_b, int selector, int cross, float ratio, int2 *h_out, int norm = 0) {
+    e[entry] = MatchCache{true, slot_a, slot_b, selector, cross, ratio, gen_a, gen_b, h_out, norm};
   }
 };
 
@@ -565,6 +567,8 @@ struct spvo_ctx {
   DevBuf<int> d_ham_idx;
   DevBuf<float> d_ham_dist;
   DevBuf<unsigned long long> d_ham_vote;
+  DevBuf<int2> d_ham_out;                 // spvo_match_l2_u8's packed result
+  int bin_pm_norm = SPVO_NORM_HAMMING;    // spvo_set_binary_prematch_norm: the matcher a binary pair call enqueues behind its features
   // fused solve: one packed input, one packed result -- per buffer SET: up to three solves may be pending (spvo_solve_submit .. _wait), a frame's
   // chain enqueued before the previous frames' have been collected; the sets rotate, so the previous solve's points (prev_index) sit in the set before.
   // The TAIL kernel of a solve submitted with `late_prior` is held back (tail_deferred) and goes out in ONE launch with the hypotheses of the next
@@ -914,6 +918,8 @@ struct MatchReq {
 int enqueue_matches(spvo_ctx *c, const MatchReq *req_in, int njobs, int selector, int cross_check, float ratio, int2 *host_out);
 // one Hamming match between two binary slots, enqueued on the solver's stream with the counts read on the device; packed result -> host_out (pinned)
 int enqueue_hamming_slots(spvo_ctx *c, int slot_a, int slot_b, int selector, int cross_check, float ratio, int2 *host_out);
+int enqueue_l2u8_slots(spvo_ctx *c, int slot_a, int slot_b, int selector, int cross_check, float ratio, int2 *host_out);   // the same under the byte-L2 norm (K12u)
+int enqueue_binary_prematch(spvo_ctx *c, int slot_a, int slot_b, int2 *host_out);   // spvo_set_prematch's match under spvo_set_binary_prematch_norm's norm
 
 }  // namespace spvo_int
 #pragma GCC visibility pop

@@ -165,6 +165,64 @@ int enqueue_hamming_slots(spvo_ctx *c, int slot_a, int slot_b, int selector, int
   return SPVO_OK;
 }
 
+// The launches of one byte-L2 match (match.hip.h K12u) on `st`: rows `row_bytes` wide lying 32 (row_bytes <= 32) or 64 bytes apart, `cap`
+// rows at most on either side, the packed result of every row of `a` into `out` (device or pinned memory, cap entries).  U8Rows::n is the
+// host's count, or with n_ptr set an upper bound that sizes the grid.  FLANN has no cross-check; the mode exists for the C ABI's argument.
+struct U8Rows { const uint32_t *rows; int n; const int *n_ptr; };
+static int enqueue_l2u8(spvo_ctx *c, hipStream_t st, const U8Rows &a, const U8Rows &b, int cap, int row_bytes, int selector, int cross_check, float ratio, int2 *out,
+                        unsigned long long *vote) {
+  const bool wide = row_bytes > 32;
+  auto launch = [&](const U8Rows &q, const U8Rows &t, int mode) {
+    const dim3 grid((q.n + U8L2_QT - 1) / U8L2_QT);
+    if (wide) hipLaunchKernelGGL(match_l2u8_kernel<64>, grid, dim3(256), 0, st, q.rows, q.n, q.n_ptr, t.rows, t.n, t.n_ptr, cap, row_bytes, mode, ratio, out, vote);
+    else hipLaunchKernelGGL(match_l2u8_kernel<32>, grid, dim3(256), 0, st, q.rows, q.n, q.n_ptr, t.rows, t.n, t.n_ptr, cap, row_bytes, mode, ratio, out, vote);
+  };
+  if (cross_check && selector == SPVO_SELECT_NN) {
+    HIP_TRY(c, hipMemsetAsync(vote, 0xFF, (size_t)a.n * sizeof(unsigned long long), st));
+    launch(b, a, 2);   // every train row votes for its nearest query row
+    hipLaunchKernelGGL(match_l2u8_cross_kernel, dim3((a.n + 255) / 256), dim3(256), 0, st, vote, a.n, a.n_ptr, cap, out);
+  } else {
+    launch(a, b, selector == SPVO_SELECT_KNN ? 1 : 0);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return SPVO_OK;
+}
+
+// enqueue_hamming_slots for the byte-L2 norm: the same slots, stream, vote scratch and result format
+int enqueue_l2u8_slots(spvo_ctx *c, int slot_a, int slot_b, int selector, int cross_check, float ratio, int2 *host_out) {
+  auto &bb = c->bin;
+  const BinarySlot &a = bb.slots[slot_a], &b = bb.slots[slot_b];
+  if (a.row_bytes != b.row_bytes)
+    return fail(c, SPVO_ERR_INVALID, "binary slot %d holds rows of %d bytes, slot %d rows of %d bytes: only slots of one width are matched", slot_a, a.row_bytes, slot_b, b.row_bytes);
+  return enqueue_l2u8(c, c->stream2, U8Rows{a.d_desc, bb.cap, a.d_n}, U8Rows{b.d_desc, bb.cap, b.d_n}, bb.cap, a.row_bytes, selector, cross_check, ratio, host_out, bb.d_vote);
+}
+
+// the match a binary pair call enqueues behind its features: spvo_set_binary_prematch_norm's choice
+int enqueue_binary_prematch(spvo_ctx *c, int slot_a, int slot_b, int2 *host_out) {
+  return c->bin_pm_norm == SPVO_NORM_L2 ? enqueue_l2u8_slots(c, slot_a, slot_b, c->pm_selector, c->pm_cross, c->pm_ratio, host_out)
+                                        : enqueue_hamming_slots(c, slot_a, slot_b, c->pm_selector, c->pm_cross, c->pm_ratio, host_out);
+}
+
+// Host rows of desc_bytes bytes for the two byte matchers: d_ham_a / d_ham_b grown on demand, the rows zero-padded to nw words (pa, pb:
+// the packed copies, the caller's until the stream has been waited for) and sent up on the solver's stream.
+static int upload_byte_rows(spvo_ctx *c, const uint8_t *desc_a, int na, const uint8_t *desc_b, int nb, int desc_bytes, int nw, std::vector<uint32_t> &pa, std::vector<uint32_t> &pb) {
+  const int need = std::max(na, nb);
+  if (need > c->ham_cap) {
+    c->ham_cap = 0;
+    const int cap = std::max(need, 2048);
+    if (int rc = grow(c, wait_for(c->stream2), {zeroed(c->d_ham_a, (size_t)cap * 16), zeroed(c->d_ham_b, (size_t)cap * 16), zeroed(c->d_ham_idx, cap), zeroed(c->d_ham_dist, cap),
+                                                zeroed(c->d_ham_vote, cap), zeroed(c->d_ham_out, cap)}))
+      return rc;
+    c->ham_cap = cap;
+  }
+  pa.assign((size_t)na * nw, 0u); pb.assign((size_t)nb * nw, 0u);
+  for (int i = 0; i < na; ++i) std::memcpy(&pa[(size_t)i * nw], desc_a + (size_t)i * desc_bytes, desc_bytes);
+  for (int i = 0; i < nb; ++i) std::memcpy(&pb[(size_t)i * nw], desc_b + (size_t)i * desc_bytes, desc_bytes);
+  HIP_TRY(c, hipMemcpyAsync(c->d_ham_a, pa.data(), pa.size() * 4, hipMemcpyHostToDevice, c->stream2));
+  HIP_TRY(c, hipMemcpyAsync(c->d_ham_b, pb.data(), pb.size() * 4, hipMemcpyHostToDevice, c->stream2));
+  return SPVO_OK;
+}
+
 }  // namespace spvo_int
 
 // ===========================================================================
@@ -212,22 +270,10 @@ int spvo_match_hamming(spvo_ctx *c, const uint8_t *desc_a, int na, const uint8_t
   }
   HIP_TRY(c, hipSetDevice(c->cfg.device));
   const int nw = desc_bytes <= 32 ? 8 : 16;
-  const int need = std::max(na, nb);
-  if (need > c->ham_cap) {
-    c->ham_cap = 0;
-    const int cap = std::max(need, 2048);
-    if (int rc = grow(c, wait_for(c->stream2), {zeroed(c->d_ham_a, (size_t)cap * 16), zeroed(c->d_ham_b, (size_t)cap * 16), zeroed(c->d_ham_idx, cap), zeroed(c->d_ham_dist, cap),
-                                                zeroed(c->d_ham_vote, cap)}))
-      return rc;
-    c->ham_cap = cap;
-  }
   // rows zero-padded to nw words: padding bits are equal on both sides and add nothing to a distance
-  std::vector<uint32_t> pa((size_t)na * nw, 0u), pb((size_t)nb * nw, 0u);
-  for (int i = 0; i < na; ++i) std::memcpy(&pa[(size_t)i * nw], desc_a + (size_t)i * desc_bytes, desc_bytes);
-  for (int i = 0; i < nb; ++i) std::memcpy(&pb[(size_t)i * nw], desc_b + (size_t)i * desc_bytes, desc_bytes);
+  std::vector<uint32_t> pa, pb;
+  if (int rc = upload_byte_rows(c, desc_a, na, desc_b, nb, desc_bytes, nw, pa, pb)) return rc;
   hipStream_t st = c->stream2;   // the solver's stream: overlaps detector submissions in flight
-  HIP_TRY(c, hipMemcpyAsync(c->d_ham_a, pa.data(), pa.size() * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemcpyAsync(c->d_ham_b, pb.data(), pb.size() * 4, hipMemcpyHostToDevice, st));
   const bool cross = cross_check && selector == SPVO_SELECT_NN;   // BFMatcher's crossCheck is off for knnMatch (base.cpp:27-28)
   auto launch = [&](const uint32_t *A, int n_a, const uint32_t *B, int n_b, int mode) {
     if (nw == 8) hipLaunchKernelGGL(match_hamming_kernel<8>, dim3((n_a + 3) / 4), dim3(256), 0, st, A, n_a, B, n_b, mode, ratio, c->d_ham_idx, c->d_ham_dist, c->d_ham_vote);
@@ -301,6 +347,66 @@ int spvo_match_hamming_slots(spvo_ctx *c, int slot_a, int slot_b, int selector, 
   if (int rc = enqueue_hamming_slots(c, slot_a, slot_b, selector, cross, ratio, h)) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream2));
   unpack_match(h, a.n, train_idx, distance);
+  return SPVO_OK;
+}
+
+// MatcherType::FLANN on binary descriptors: the exact L2 nearest neighbours of the rows' bytes (match.hip.h K12u).  spvo_match_hamming's
+// argument rules, buffers and stream.
+int spvo_match_l2_u8(spvo_ctx *c, const uint8_t *desc_a, int na, const uint8_t *desc_b, int nb, int desc_bytes, int selector, int cross_check, float ratio,
+                     int32_t *train_idx, float *distance) {
+  if (!c || na < 0 || nb < 0 || (na > 0 && (!desc_a || !train_idx || !distance)) || (nb > 0 && !desc_b)) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  if (selector != SPVO_SELECT_NN && selector != SPVO_SELECT_KNN) return fail(c, SPVO_ERR_INVALID, "bad selector");
+  if (desc_bytes <= 0 || desc_bytes > 64) return fail(c, SPVO_ERR_INVALID, "binary descriptors of 1 .. 64 bytes are supported (got %d)", desc_bytes);
+  if (na == 0) return SPVO_OK;
+  if (nb == 0) {
+    for (int i = 0; i < na; ++i) { train_idx[i] = -1; distance[i] = 0.f; }
+    return SPVO_OK;
+  }
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  std::vector<uint32_t> pa, pb;
+  if (int rc = upload_byte_rows(c, desc_a, na, desc_b, nb, desc_bytes, desc_bytes <= 32 ? 8 : 16, pa, pb)) return rc;
+  hipStream_t st = c->stream2;
+  if (int rc = enqueue_l2u8(c, st, U8Rows{c->d_ham_a, na, nullptr}, U8Rows{c->d_ham_b, nb, nullptr}, c->ham_cap, desc_bytes, selector, cross_check ? 1 : 0, ratio, c->d_ham_out,
+                            c->d_ham_vote))
+    return rc;
+  std::vector<int2> packed(na);
+  HIP_TRY(c, hipMemcpyAsync(packed.data(), c->d_ham_out, (size_t)na * sizeof(int2), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  unpack_match(packed.data(), na, train_idx, distance);
+  return SPVO_OK;
+}
+
+// spvo_match_l2_u8 on two binary slots.  Served from the call's prematch when that ran under SPVO_NORM_L2 and is exactly this match of
+// exactly these slot contents, computed on the spot otherwise.
+int spvo_match_l2_u8_slots(spvo_ctx *c, int slot_a, int slot_b, int selector, int cross_check, float ratio, int32_t *train_idx, float *distance) {
+  if (!c || slot_a < 0 || slot_a >= N_BIN_SLOTS || slot_b < 0 || slot_b >= N_BIN_SLOTS) return fail(c, SPVO_ERR_INVALID, "bad slot");
+  if (selector != SPVO_SELECT_NN && selector != SPVO_SELECT_KNN) return fail(c, SPVO_ERR_INVALID, "bad selector");
+  auto &bb = c->bin;
+  const BinarySlot &a = bb.slots[slot_a], &b = bb.slots[slot_b];
+  if (!a.filled || !b.filled) return fail(c, SPVO_ERR_STATE, "binary slot %d holds no features (spvo_classic_detect fills it)", a.filled ? slot_b : slot_a);
+  if (a.row_bytes != b.row_bytes)
+    return fail(c, SPVO_ERR_INVALID, "binary slot %d holds rows of %d bytes, slot %d rows of %d bytes: only slots of one width are matched", slot_a, a.row_bytes, slot_b, b.row_bytes);
+  if (a.n > 0 && (!train_idx || !distance)) return fail(c, SPVO_ERR_INVALID, "null output");
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  const int cross = cross_check ? 1 : 0;
+  if (const MatchCache *mc = bb.pair.mcache.find(slot_a, slot_b, a.gen, b.gen, selector, cross, ratio, SPVO_NORM_L2)) {
+    HIP_TRY(c, wait_event(bb.pair.ev_match));
+    unpack_match(mc->h_out, a.n, train_idx, distance);
+    return SPVO_OK;
+  }
+  if (a.n == 0) return SPVO_OK;
+  int2 *h = bb.h_match + (size_t)2 * bb.cap;
+  if (int rc = enqueue_l2u8_slots(c, slot_a, slot_b, selector, cross, ratio, h)) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream2));
+  unpack_match(h, a.n, train_idx, distance);
+  return SPVO_OK;
+}
+
+int spvo_set_binary_prematch_norm(spvo_ctx *c, int norm) {
+  if (!c) return fail(c, SPVO_ERR_INVALID, "null context");
+  if (norm != SPVO_NORM_HAMMING && norm != SPVO_NORM_L2) return fail(c, SPVO_ERR_INVALID, "bad norm %d (SPVO_NORM_HAMMING or SPVO_NORM_L2)", norm);
+  c->bin_pm_norm = norm;
+  c->bin.pair.mcache.invalidate();
   return SPVO_OK;
 }
 

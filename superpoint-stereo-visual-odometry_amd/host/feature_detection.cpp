@@ -76,8 +76,26 @@ void FeatureFrontEnd::initMatcher() {
     matcher_hamming_ = descriptor_type_ != DescriptorType::SIFT && descriptor_type_ != DescriptorType::SuperPoint;
     matcher_ready_ = true;
   } else {
-    logError("[initMatcher] FLANN matcher is not implemented on the GPU path (base.cpp:29-32); use BF");
+    // cv::FlannBasedMatcher (base.cpp:29-32): an L2 search whatever the descriptor, without a cross-check (the argument is not looked at).
+    // Its two randomized KD-trees are approximate and not reproducible; what runs here is the exact search they approximate (parity with
+    // the trees unpinned, like USAC_ACCURATE).  SIFT and SuperPoint rows take BF's L2 routes; binary rows are matched on their BYTES as
+    // numbers: spvo_match_l2_u8 on the host matrices, spvo_match_l2_u8_slots on resident pairs.
+    matcher_flann_ = true;
+    matcher_cross_check_ = false;
+    matcher_hamming_ = descriptor_type_ != DescriptorType::SIFT && descriptor_type_ != DescriptorType::SuperPoint;
+    matcher_ready_ = true;
   }
+}
+
+// a CV_8U descriptor matrix as CV_32F, value for value: matchDescriptors' in-place conversion under FLANN (base.cpp:444-451)
+static cv::Mat float_rows(const cv::Mat &m) {
+  cv::Mat f(m.rows, m.cols, CV_32F);
+  for (int r = 0; r < m.rows; ++r) {
+    const uint8_t *s = m.ptr<uint8_t>(r);
+    float *d = f.ptr<float>(r);
+    for (int c = 0; c < m.cols; ++c) d[c] = (float)s[c];
+  }
+  return f;
 }
 
 static int g_device = -1;   // FeatureFrontEnd::setDevice
@@ -185,7 +203,37 @@ void FeatureFrontEnd::matchDescriptors(const MatchType match_type) {
   std::vector<float> dist(std::max(n0, 1), 0.f);
   const int sel = selector_type_ == SelectorType::KNN ? SPVO_SELECT_KNN : SPVO_SELECT_NN;
   int rc;
-  if (matcher_hamming_) {   // binary descriptors: host matrices (CV_8U, one row per keypoint), packed row by row if they are views
+  if (matcher_hamming_ && matcher_flann_) {   // binary descriptors under FLANN: L2 on the bytes; CV_8U matrices, or CV_32F ones an earlier call converted
+    cv::Mat &d0 = descriptors_dq.end()[p0], &d1 = descriptors_dq.end()[p1];
+    const int nbytes = d0.rows ? d0.cols : d1.cols;
+    auto depth_ok = [](const cv::Mat &m) { return m.rows == 0 || m.depth() == CV_8U || m.depth() == CV_32F; };
+    if (!depth_ok(d0) || !depth_ok(d1) || (d0.rows && d1.rows && d0.cols != d1.cols) || d0.rows != n0 || nbytes > 64) {
+      logError("matchDescriptors: binary descriptors expected (CV_8U or converted to CV_32F, one row per keypoint, equal widths of at most 64)");
+      return;
+    }
+    const bool resident = bin_slots_dq_.size() == keypoints_dq.size() && bin_slots_dq_.end()[p0] >= 0 && bin_slots_dq_.end()[p1] >= 0;
+    const bool bytes0 = d0.rows == 0 || d0.depth() == CV_8U, bytes1 = d1.rows == 0 || d1.depth() == CV_8U;
+    if (resident) {   // the slots hold the bytes whatever has become of the host matrices
+      rc = spvo_match_l2_u8_slots(ctx_, bin_slots_dq_.end()[p0], bin_slots_dq_.end()[p1], sel, 0, knn_threshold_, train.data(), dist.data());
+    } else if (bytes0 && bytes1) {
+      auto rows_of = [nbytes](const cv::Mat &m, std::vector<uint8_t> &buf) -> const uint8_t * {
+        if (m.rows == 0) return nullptr;
+        if ((size_t)m.step == (size_t)nbytes) return m.ptr<uint8_t>(0);
+        buf.resize((size_t)m.rows * nbytes);
+        for (int r = 0; r < m.rows; ++r) std::memcpy(buf.data() + (size_t)r * nbytes, m.ptr<uint8_t>(r), nbytes);
+        return buf.data();
+      };
+      std::vector<uint8_t> b0, b1;
+      rc = spvo_match_l2_u8(ctx_, rows_of(d0, b0), d0.rows, rows_of(d1, b1), d1.rows, std::max(nbytes, 1), sel, 0, knn_threshold_, train.data(), dist.data());
+    } else {   // one side was converted by an earlier call (the previous left image, every frame): the float matcher on both -- the same answer, exactly
+      if (d0.rows && d0.depth() == CV_8U) d0 = float_rows(d0);
+      if (d1.rows && d1.depth() == CV_8U) d1 = float_rows(d1);
+      rc = spvo_match_l2(ctx_, d0.rows ? d0.ptr<float>(0) : nullptr, d0.rows, d1.rows ? d1.ptr<float>(0) : nullptr, d1.rows, std::max(nbytes, 1), sel, 0, knn_threshold_, train.data(),
+                         dist.data());
+    }
+    if (d0.depth() == CV_8U) d0 = float_rows(d0);   // what the reference leaves in descriptors_dq
+    if (d1.depth() == CV_8U) d1 = float_rows(d1);
+  } else if (matcher_hamming_) {   // binary descriptors: host matrices (CV_8U, one row per keypoint), packed row by row if they are views
     const cv::Mat &d0 = descriptors_dq.end()[p0], &d1 = descriptors_dq.end()[p1];
     const int nbytes = d0.rows ? d0.cols : d1.cols;
     auto rows_of = [nbytes](const cv::Mat &m, std::vector<uint8_t> &buf) -> const uint8_t * {

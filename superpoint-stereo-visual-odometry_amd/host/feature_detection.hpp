@@ -279,7 +279,9 @@ protected:
   double solve_timing_acc_[3] = {0, 0, 0};
   long solve_timing_calls_ = 0;
   std::vector<float> solve_pts3d_;
-  bool matcher_hamming_ = false;   // NORM_HAMMING descriptors of the classic front end (base.cpp:13-28): spvo_match_hamming
+  bool matcher_hamming_ = false;   // binary descriptors of the classic front end (base.cpp:13-28): spvo_match_hamming under BF, spvo_match_l2_u8 under FLANN
+  bool matcher_flann_ = false;     // MatcherType::FLANN (base.cpp:29-32): the exact L2 search its KD-trees approximate; no cross-check; matchDescriptors leaves
+                                   // both descriptor matrices CV_32F, as the reference's in-place conversion does (base.cpp:444-451)
   // creates ctx_ without an engine: preprocessImageImpl and solveStereoOdometry of a front end that has no network
   bool ensureContext();
 

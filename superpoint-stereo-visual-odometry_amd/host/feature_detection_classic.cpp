@@ -454,7 +454,10 @@ bool ClassicFeatureFrontEnd::residentPair(const ClassicPair &p, cv::Mat &img_l, 
   using Record = typename std::remove_pointer<decltype(Features::kp)>::type;
   using Element = typename std::remove_pointer<decltype(Features::desc)>::type;
   // the two standard matches go out with the detector from now on
-  if (resident_pairs_ == 0) spvo_set_prematch(ctx_, 1, selector_type_ == SelectorType::KNN ? SPVO_SELECT_KNN : SPVO_SELECT_NN, matcher_cross_check_ ? 1 : 0, knn_threshold_);
+  if (resident_pairs_ == 0) {
+    spvo_set_prematch(ctx_, 1, selector_type_ == SelectorType::KNN ? SPVO_SELECT_KNN : SPVO_SELECT_NN, matcher_cross_check_ ? 1 : 0, knn_threshold_);
+    if (matcher_flann_) spvo_set_binary_prematch_norm(ctx_, SPVO_NORM_L2);   // (the SIFT slots' prematch is L2 either way)
+  }
   const int cap = std::max(resident_capacity_, 1);
   Features f[2];
   for (int k = 0; k < 2; ++k) {

@@ -18,6 +18,17 @@ void *spvo_host_create(const char *models_dir, const char *prefix, const char *m
   return fe;
 }
 
+// ... with the matcher named ("BF", "FLANN"; NULL for an unknown name): MatcherType::FLANN runs the exact L2 search on the same slots, without a cross-check
+void *spvo_host_create_matcher(const char *matcher_name, const char *models_dir, const char *prefix, const char *machine, int selector_knn, int cross_check, int batch, int height,
+                               int width, float conf_thresh, int dist_thresh, int border_remove, float stereo_threshold, float min_disparity, int refinement_degree, int verbose,
+                               int precision) {
+  if (!matcher_name || !matcher_name_to_type.count(matcher_name)) return nullptr;
+  SuperPointFeatureFrontEnd::setModelsDir(models_dir ? models_dir : "");
+  return new SuperPointFeatureFrontEnd(matcher_name_to_type.at(matcher_name), selector_knn ? SelectorType::KNN : SelectorType::NN, cross_check != 0, prefix, batch, machine,
+                                       precision == 2 ? TRT_INT8 : precision == 1 ? TRT_FP16 : TRT_FP32, height, width, conf_thresh, dist_thresh, /*num_threads=*/6, border_remove,
+                                       stereo_threshold, min_disparity, refinement_degree, verbose != 0);
+}
+
 // the class-level options of the host mirror (feature_detection.hpp: setDevice, setMaxKeypoints, setMatchFp8): for the front ends created
 // afterwards; a negative value hands the decision back to the environment variable
 void spvo_host_set_options(int device, int max_keypoints, int match_fp8) {
@@ -243,6 +254,71 @@ int spvo_host_classic_match(int knn, int cross_check, int match_type, const uint
   return (int)m.size();
 }
 
+// What initMatcher makes of (detector, descriptor, matcher, selector, cross_check), without a device: 0 and an empty `err` when the front end's
+// construction logged nothing, 1 and the text it logged otherwise; -1000000 .. -1000003 for an unknown detector / descriptor / matcher / selector
+// name.  "SuperPoint" + "SuperPoint" constructs the base class alone (the network front end would load its engine); every other pair the classic one.
+int spvo_host_matcher_probe(const char *detector_name, const char *descriptor_name, const char *matcher_name, const char *selector_name, int cross_check, char *err, int cap) {
+  if (!detector_name || !detector_name_to_type.count(detector_name)) return -1000000;
+  if (!descriptor_name || !descriptor_name_to_type.count(descriptor_name)) return -1000001;
+  if (!matcher_name || !matcher_name_to_type.count(matcher_name)) return -1000002;
+  if (!selector_name || !selector_name_to_type.count(selector_name)) return -1000003;
+  const DetectorType det = detector_name_to_type.at(detector_name);
+  const DescriptorType desc = descriptor_name_to_type.at(descriptor_name);
+  const MatcherType mt = matcher_name_to_type.at(matcher_name);
+  const SelectorType st = selector_name_to_type.at(selector_name);
+  std::string logged;
+  if (desc == DescriptorType::SuperPoint) {
+    struct MatcherOnly : FeatureFrontEnd {
+      using FeatureFrontEnd::FeatureFrontEnd;
+      void addStereoImagePair(cv::Mat &, cv::Mat &, const cv::Mat &, const cv::Mat &) override {}
+    } fe(det, desc, mt, st, cross_check != 0, 2.0f, 2.0f, 4, false, 0, 0);
+    fe.initMatcher();
+    logged = fe.lastError();
+  } else {
+    ClassicFeatureFrontEnd fe(det, desc, mt, st, cross_check != 0, 2.0f, 2.0f, 4, false, 0, 0);
+    logged = fe.lastError();
+  }
+  if (err && cap > 0) {
+    std::strncpy(err, logged.c_str(), cap - 1);
+    err[cap - 1] = 0;
+  }
+  return logged.empty() ? 0 : 1;
+}
+
+// spvo_host_classic_match with the descriptor and the matcher named and several matchDescriptors calls on ONE front end: rows of `cols` elements of
+// `elem` bytes (1: CV_8U, 4: CV_32F) are pushed as in spvo_host_classic_match, then matchDescriptors(match_types[k]) runs for k = 0 .. n_matches - 1 in
+// that order (a later call meets what an earlier one left in descriptors_dq).  map_out: n_matches x cap, sizes_out[k] the size of call k's map;
+// depths_out[4]: each deque entry's depth() after the last call (CV_8U 0, CV_32F 5).  Returns 0, 1 if the front end logged an error (in `err`), or
+// -1000001 / -1000002 for an unknown descriptor / matcher name.
+int spvo_host_classic_match_matcher(const char *descriptor_name, const char *matcher_name, int knn, int cross_check, int n_matches, const int *match_types, const void *const desc[4],
+                                    const int n[4], int cols, int elem, int *map_out, int *sizes_out, int cap, int *depths_out, char *err, int err_cap) {
+  if (!descriptor_name || !descriptor_name_to_type.count(descriptor_name)) return -1000001;
+  if (!matcher_name || !matcher_name_to_type.count(matcher_name)) return -1000002;
+  const DescriptorType dt = descriptor_name_to_type.at(descriptor_name);
+  ClassicFeatureFrontEnd fe(dt == DescriptorType::SIFT ? DetectorType::SIFT : detector_name_to_type.at("ORB"), dt, matcher_name_to_type.at(matcher_name),
+                            selector_name_to_type.at(knn ? "KNN" : "NN"), cross_check != 0, 2.0f, 2.0f, 4, false, 0, 0);
+  for (int i = 0; i < 4; ++i) {
+    cv::Mat d(n[i], cols, elem == 4 ? CV_32FC1 : CV_8UC1);
+    if (n[i]) std::memcpy(d.data, desc[i], (size_t)n[i] * cols * elem);
+    std::vector<cv::KeyPoint> kp((size_t)n[i]);
+    fe.keypoints_dq.push_back(kp);
+    fe.descriptors_dq.push_back(d);
+    fe.images_dq.push_back(cv::Mat());
+  }
+  for (int k = 0; k < n_matches; ++k) {
+    fe.matchDescriptors((MatchType)match_types[k]);
+    const std::vector<int> &m = fe.mapsOfIndices().at((MatchType)match_types[k]);
+    for (int i = 0; i < (int)m.size() && i < cap; ++i) map_out[(size_t)k * cap + i] = m[i];
+    sizes_out[k] = (int)m.size();
+  }
+  for (int i = 0; i < 4; ++i) depths_out[i] = fe.descriptors_dq[i].depth();
+  if (err && err_cap > 0) {
+    std::strncpy(err, fe.lastError().c_str(), err_cap - 1);
+    err[err_cap - 1] = 0;
+  }
+  return fe.lastError().empty() ? 0 : 1;
+}
+
 // the default-constructed classic front end (hpp: ShiTomasi + ORB, BF, NN, cross-check, 120 x 392) offered one stereo pair of
 // rows x cols: returns the number of deque entries it produced (negative: the deques are not aligned), the keypoint / descriptor
 // row counts of the pair in counts[4] (keypoints L, descriptors L, keypoints R, descriptors R) and the error it logged
@@ -334,7 +410,7 @@ static uint64_t digest_ints(const std::vector<int> &a, const std::vector<int> &b
 
 static int g_classic_resident_pairs = 0;   // ClassicFeatureFrontEnd::residentPairs() of the last classic_sequence_run
 
-static int classic_sequence_run(const char *detector_name, const char *descriptor_name, int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l,
+static int classic_sequence_run(const char *detector_name, const char *descriptor_name, const char *matcher_name, int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l,
                                 const double *P_r, int knn, int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats,
                                 double *seconds, int input_height, int input_width, uint64_t *digest) {
   g_classic_resident_pairs = 0;
@@ -342,7 +418,8 @@ static int classic_sequence_run(const char *detector_name, const char *descripto
   // descriptor_name NULL: "SIFT" means SIFT keypoints with SIFT descriptors (NORM_L2), every other detector goes with the ORB extractor
   const bool sift = detector_name_to_type.at(detector_name) == DetectorType::SIFT;
   if (descriptor_name && !descriptor_name_to_type.count(descriptor_name)) return -1000001;
-  ClassicFeatureFrontEnd fe(detector_name_to_type.at(detector_name), descriptor_name_to_type.at(descriptor_name ? descriptor_name : sift ? "SIFT" : "ORB"), matcher_name_to_type.at("BF"),
+  if (!matcher_name_to_type.count(matcher_name)) return -1000002;
+  ClassicFeatureFrontEnd fe(detector_name_to_type.at(detector_name), descriptor_name_to_type.at(descriptor_name ? descriptor_name : sift ? "SIFT" : "ORB"), matcher_name_to_type.at(matcher_name),
                             selector_name_to_type.at(knn ? "KNN" : "NN"), cross_check != 0, stereo_threshold, stereo_threshold, refinement_degree, false, input_height,
                             input_width);
   timespec t0{}, t1{};
@@ -390,7 +467,7 @@ static int classic_sequence_run(const char *detector_name, const char *descripto
 int spvo_host_classic_sequence_ex(const char *detector_name, int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l,
                                   const double *P_r, int knn, int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats,
                                   double *seconds, int input_height, int input_width) {
-  return classic_sequence_run(detector_name, nullptr, n, imgs_l, imgs_r, rows, cols, P_l, P_r, knn, cross_check, stereo_threshold, refinement_degree, warm, poses, stats, seconds, input_height,
+  return classic_sequence_run(detector_name, nullptr, "BF", n, imgs_l, imgs_r, rows, cols, P_l, P_r, knn, cross_check, stereo_threshold, refinement_degree, warm, poses, stats, seconds, input_height,
                               input_width, nullptr);
 }
 
@@ -398,7 +475,7 @@ int spvo_host_classic_sequence_ex(const char *detector_name, int n, const uint8_
 int spvo_host_classic_sequence_trace(const char *detector_name, int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l,
                                      const double *P_r, int knn, int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats,
                                      double *seconds, int input_height, int input_width, uint64_t *digest) {
-  return classic_sequence_run(detector_name, nullptr, n, imgs_l, imgs_r, rows, cols, P_l, P_r, knn, cross_check, stereo_threshold, refinement_degree, warm, poses, stats, seconds, input_height,
+  return classic_sequence_run(detector_name, nullptr, "BF", n, imgs_l, imgs_r, rows, cols, P_l, P_r, knn, cross_check, stereo_threshold, refinement_degree, warm, poses, stats, seconds, input_height,
                               input_width, digest);
 }
 
@@ -409,8 +486,18 @@ int spvo_host_classic_sequence_desc(const char *detector_name, const char *descr
                                     const double *P_l, const double *P_r, int knn, int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses,
                                     int *stats, double *seconds, int input_height, int input_width, uint64_t *digest) {
   if (!descriptor_name) return -1000001;
-  return classic_sequence_run(detector_name, descriptor_name, n, imgs_l, imgs_r, rows, cols, P_l, P_r, knn, cross_check, stereo_threshold, refinement_degree, warm, poses, stats, seconds,
+  return classic_sequence_run(detector_name, descriptor_name, "BF", n, imgs_l, imgs_r, rows, cols, P_l, P_r, knn, cross_check, stereo_threshold, refinement_degree, warm, poses, stats, seconds,
                               input_height, input_width, digest);
+}
+
+// ... with the matcher named as well ("BF", "FLANN"; -1000002: no such matcher)
+int spvo_host_classic_sequence_matcher(const char *detector_name, const char *descriptor_name, const char *matcher_name, int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r,
+                                       int rows, int cols, const double *P_l, const double *P_r, int knn, int cross_check, float stereo_threshold, int refinement_degree, int warm,
+                                       double *poses, int *stats, double *seconds, int input_height, int input_width, uint64_t *digest) {
+  if (!descriptor_name) return -1000001;
+  if (!matcher_name) return -1000002;
+  return classic_sequence_run(detector_name, descriptor_name, matcher_name, n, imgs_l, imgs_r, rows, cols, P_l, P_r, knn, cross_check, stereo_threshold, refinement_degree, warm, poses, stats,
+                              seconds, input_height, input_width, digest);
 }
 
 // pairs of the last spvo_host_classic_sequence_* run that stayed resident on the device (0 with setDeviceResident off; fewer than the

@@ -98,7 +98,7 @@ SYMBOLS = [
     "spvo_default_config", "spvo_create", "spvo_destroy", "spvo_last_error", "spvo_load_weights", "spvo_engine_precision", "spvo_set_fp32_split",
     "spvo_preprocess", "spvo_forward", "spvo_debug_tensor", "spvo_heatmap", "spvo_nms",
     "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8", "spvo_match_last_form",
-    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_orb_describe_octaves", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_akaze_describe", "spvo_akaze_detect_pair", "spvo_akaze_suppress_debug", "spvo_brisk_orb_pair", "spvo_akaze_orb_pair", "spvo_akaze_brisk_pair", "spvo_orb_octaves_link_debug", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_describe", "spvo_sift_detect_pair", "spvo_classic_sift_pair", "spvo_brisk_sift_pair", "spvo_akaze_sift_pair", "spvo_sift_link_debug", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
+    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_orb_describe_octaves", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_akaze_describe", "spvo_akaze_detect_pair", "spvo_akaze_suppress_debug", "spvo_brisk_orb_pair", "spvo_akaze_orb_pair", "spvo_akaze_brisk_pair", "spvo_orb_octaves_link_debug", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_describe", "spvo_sift_detect_pair", "spvo_classic_sift_pair", "spvo_brisk_sift_pair", "spvo_akaze_sift_pair", "spvo_sift_link_debug", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_match_l2_u8", "spvo_match_l2_u8_slots", "spvo_set_binary_prematch_norm", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
     "spvo_profile_enable", "spvo_profile_reset", "spvo_profile_only", "spvo_profile_count", "spvo_profile_get", "spvo_profile_stage_kernel", "spvo_profile_stage_variant",
     "spvo_set_tuning", "spvo_get_tuning", "spvo_clear_tuning",
     "spvo_comm_unique_id", "spvo_comm_available", "spvo_comm_create", "spvo_comm_create_host", "spvo_comm_rank", "spvo_comm_world", "spvo_comm_destroy",
@@ -191,6 +191,9 @@ def load() -> C.CDLL:
     lib.spvo_classic_slot_rows.argtypes = [vp, C.c_int, ip]
     lib.spvo_classic_slot_fill_debug.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int]
     lib.spvo_match_hamming_slots.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]
+    lib.spvo_match_l2_u8.argtypes = lib.spvo_match_hamming.argtypes
+    lib.spvo_match_l2_u8_slots.argtypes = lib.spvo_match_hamming_slots.argtypes
+    lib.spvo_set_binary_prematch_norm.argtypes = [vp, C.c_int]
     lib.spvo_triangulate.argtypes = [vp, dp, dp, vp, vp, C.c_int, vp]
     lib.spvo_pnp_ransac.argtypes = [vp, dp, vp, vp, C.c_int, C.POINTER(RansacOpts), dp, dp, vp, ip, ip]
     lib.spvo_pnp_refine.argtypes = [vp, dp, dp, vp, C.c_int, C.POINTER(RefineOpts), dp, dp,
@@ -920,6 +923,32 @@ class Context:
         self._check(self.lib.spvo_match_hamming(self.h, _ptr(a), len(a), _ptr(b), len(b), nbytes, 1 if selector == "KNN" else 0,
                                                 int(cross_check), ratio, _ptr(idx), _ptr(dist)))
         return idx, dist
+
+    def match_l2_u8(self, a: np.ndarray, b: np.ndarray, selector="KNN", cross_check=False, ratio=0.8):
+        """MatcherType::FLANN on u8 descriptor rows: the exact L2 nearest neighbours of the bytes as numbers (spvo_match_l2_u8)."""
+        a = np.ascontiguousarray(a, np.uint8)
+        b = np.ascontiguousarray(b, np.uint8)
+        nbytes = a.shape[1] if a.ndim == 2 and a.shape[1] else (b.shape[1] if b.ndim == 2 and b.shape[1] else 32)
+        a = a.reshape(len(a), nbytes)
+        b = b.reshape(len(b), nbytes)
+        idx = np.full(len(a), -1, np.int32)
+        dist = np.zeros(len(a), np.float32)
+        self._check(self.lib.spvo_match_l2_u8(self.h, _ptr(a), len(a), _ptr(b), len(b), nbytes, 1 if selector == "KNN" else 0,
+                                              int(cross_check), ratio, _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    def match_l2_u8_slots(self, slot_a: int, slot_b: int, selector="KNN", cross_check=False, ratio=0.8):
+        """spvo_match_l2_u8 between two binary feature slots, on the device (spvo_match_l2_u8_slots)."""
+        n = self.classic_slot_rows(slot_a)
+        self.classic_slot_rows(slot_b)
+        idx = np.full(max(n, 1), -1, np.int32)
+        dist = np.zeros(max(n, 1), np.float32)
+        self._check(self.lib.spvo_match_l2_u8_slots(self.h, slot_a, slot_b, 1 if selector == "KNN" else 0, int(cross_check), ratio, _ptr(idx), _ptr(dist)))
+        return idx[:n], dist[:n]
+
+    def set_binary_prematch_norm(self, norm="HAMMING"):
+        """Which matcher the binary pair calls enqueue behind their features (spvo_set_binary_prematch_norm): "HAMMING" (default) or "L2"."""
+        self._check(self.lib.spvo_set_binary_prematch_norm(self.h, {"HAMMING": 0, "L2": 1}[norm]))
 
     def match(self, a: np.ndarray, b: np.ndarray, selector="KNN", cross_check=False, ratio=0.8):
         a = np.ascontiguousarray(a, np.float32).reshape(-1, 256)

@@ -3,6 +3,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -25,6 +26,8 @@ def load():
         lib.spvo_host_create.restype = vp
         lib.spvo_host_create.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_float, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int]
+        lib.spvo_host_create_matcher.restype = vp
+        lib.spvo_host_create_matcher.argtypes = [C.c_char_p] + lib.spvo_host_create.argtypes
         lib.spvo_host_destroy.argtypes = [vp]
         lib.spvo_host_set_options.argtypes = [C.c_int, C.c_int, C.c_int]
         lib.spvo_host_set_options.restype = None
@@ -128,9 +131,10 @@ class FrontEnd:
 
     def __init__(self, models_dir, prefix="superpoint_pretrained", machine="laptop", selector="KNN", cross_check=True,
                  batch=2, height=360, width=1176, conf_thresh=0.015, dist_thresh=4, border_remove=4,
-                 stereo_threshold=2.0, min_disparity=0.25, refinement_degree=4, verbose=False, precision="FP32"):
+                 stereo_threshold=2.0, min_disparity=0.25, refinement_degree=4, verbose=False, precision="FP32", matcher="BF"):
         self.lib = load()
-        self.h = self.lib.spvo_host_create(models_dir.encode(), prefix.encode(), machine.encode(),
+        create = self.lib.spvo_host_create if matcher == "BF" else functools.partial(self.lib.spvo_host_create_matcher, matcher.encode())
+        self.h = create(models_dir.encode(), prefix.encode(), machine.encode(),
                                            1 if selector == "KNN" else 0, int(cross_check), batch, height, width,
                                            conf_thresh, dist_thresh, border_remove, stereo_threshold, min_disparity,
                                            refinement_degree, int(verbose), {"FP32": 0, "FP16": 1, "INT8": 2}[precision])
@@ -343,8 +347,9 @@ class FrontEnd:
 
 def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_threshold=2.0, refinement_degree=4, warm=0, detector="ORB", input_size=None, resident=False,
                      resident_capacity=0, trace=False, descriptor="ORB", brisk_resident=False, akaze_descriptor=False, akaze_resident=False, sift_describe_resident=False, orb_octaves=False,
-                     octave_pairs_resident=False, sift_octave_pairs_resident=False):
-    """stereoCallback replayed on ClassicFeatureFrontEnd(detector, descriptor, BF, ...) (node.cpp:353-360) over host image pairs -- detector
+                     octave_pairs_resident=False, sift_octave_pairs_resident=False, matcher="BF"):
+    """matcher: "BF", or "FLANN" (spvo_host_classic_sequence_matcher: the exact L2 search on the descriptor bytes, no cross-check).
+    stereoCallback replayed on ClassicFeatureFrontEnd(detector, descriptor, BF, ...) (node.cpp:353-360) over host image pairs -- detector
     "ORB", "ShiTomasi" or "FAST" with descriptor "ORB", "ShiTomasi", "FAST", "BRISK" or "AKAZE" with descriptor "BRISK" (64-byte rows; detector "BRISK"
     or "AKAZE" with the default descriptor "ORB" runs only with orb_octaves=True (ClassicFeatureFrontEnd::setOrbExtractorOctaves, reset afterwards:
     spvo_orb_describe_octaves on the level each keypoint's octave names, the per-image path, classic_resident_pairs() stays 0) and is refused
@@ -379,6 +384,8 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
                                                      C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_void_p]
     lib.spvo_host_classic_sequence_desc.restype = C.c_int
     lib.spvo_host_classic_sequence_desc.argtypes = [C.c_char_p, C.c_char_p] + lib.spvo_host_classic_sequence_trace.argtypes[1:]
+    lib.spvo_host_classic_sequence_matcher.restype = C.c_int
+    lib.spvo_host_classic_sequence_matcher.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p] + lib.spvo_host_classic_sequence_trace.argtypes[1:]
     lib.spvo_host_classic_set_resident.restype = None
     lib.spvo_host_classic_set_resident.argtypes = [C.c_int, C.c_int]
     lib.spvo_host_classic_set_brisk_resident.restype = None
@@ -419,7 +426,9 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     try:
         args =(n, pl, pr, rows, cols, Pl.ctypes.data, Pr.ctypes.data, 1 if selector == "KNN" else 0, int(cross_check), stereo_threshold, refinement_degree, warm,
                 poses.ctypes.data, stats.ctypes.data, C.byref(sec), ih, iw, digest.ctypes.data if trace else None)
-        if descriptor == "ORB" or detector == "SIFT":             # the export that pairs every detector with its default descriptor
+        if matcher != "BF":
+            rc = lib.spvo_host_classic_sequence_matcher(detector.encode(), ("SIFT" if detector == "SIFT" else descriptor).encode(), matcher.encode(), *args)
+        elif descriptor == "ORB" or detector == "SIFT":             # the export that pairs every detector with its default descriptor
             rc = lib.spvo_host_classic_sequence_trace(detector.encode(), *args)
         else:
             rc = lib.spvo_host_classic_sequence_desc(detector.encode(), descriptor.encode(), *args)
@@ -436,6 +445,8 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
         raise ValueError("unknown detector %r" % (detector,))
     if rc == -1000001:
         raise ValueError("unknown descriptor %r" % (descriptor,))
+    if rc == -1000002:
+        raise ValueError("unknown matcher %r" % (matcher,))
     if rc != n:
         raise RuntimeError("classic front end failed at frame %d" % (-rc - 1))
     if trace:
@@ -495,3 +506,42 @@ def classic_pair_probe(detector, descriptor, img_l, img_r, P_l, P_r, akaze_descr
         lib.spvo_host_classic_set_akaze_descriptor(0)
         lib.spvo_host_classic_set_orb_octaves(0)
     return rc, counts, buf.value.decode()
+
+
+def matcher_probe(detector, descriptor, matcher, selector, cross_check=False):
+    """What initMatcher makes of FeatureFrontEnd(detector, descriptor, matcher, selector, cross_check), without a device
+    (spvo_host_matcher_probe) -> (0 if nothing was logged else 1, the error logged); ValueError for an unknown name."""
+    lib = load()
+    lib.spvo_host_matcher_probe.restype = C.c_int
+    lib.spvo_host_matcher_probe.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int]
+    buf = C.create_string_buffer(512)
+    rc = lib.spvo_host_matcher_probe(detector.encode(), descriptor.encode(), matcher.encode(), selector.encode(), int(bool(cross_check)), buf, 512)
+    if rc <= -1000000:
+        raise ValueError("unknown %s name" % ("detector", "descriptor", "matcher", "selector")[-1000000 - rc])
+    return rc, buf.value.decode()
+
+
+def classic_match(sets, match_types, descriptor="ORB", matcher="BF", selector="KNN", cross_check=False):
+    """ClassicFeatureFrontEnd(.., descriptor, matcher, selector, cross_check) with four feature sets pushed into its deques (prevL, prevR,
+    currL, currR: [n, cols] uint8 or float32 rows) and matchDescriptors(t) run for every t of match_types in order on that ONE front end
+    (spvo_host_classic_match_matcher) -> (the maps, one per call; each deque entry's depth() afterwards: 0 CV_8U, 5 CV_32F; the error logged)."""
+    lib = load()
+    lib.spvo_host_classic_match_matcher.restype = C.c_int
+    lib.spvo_host_classic_match_matcher.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int,
+                                                    C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_char_p, C.c_int]
+    dtype = np.float32 if sets[0].dtype == np.float32 else np.uint8
+    sets = [np.ascontiguousarray(s, dtype) for s in sets]
+    cols = max(s.shape[1] for s in sets)
+    ptrs = (C.c_void_p * 4)(*[s.ctypes.data for s in sets])
+    ns = (C.c_int * 4)(*[len(s) for s in sets])
+    types = np.ascontiguousarray(match_types, np.int32)
+    cap = max(max(len(s) for s in sets), 1)
+    maps = np.full((len(types), cap), -7, np.int32)
+    sizes = np.zeros(len(types), np.int32)
+    depths = np.full(4, -1, np.int32)
+    buf = C.create_string_buffer(512)
+    rc = lib.spvo_host_classic_match_matcher(descriptor.encode(), matcher.encode(), 1 if selector == "KNN" else 0, int(bool(cross_check)), len(types), types.ctypes.data, ptrs, ns,
+                                             cols, sets[0].dtype.itemsize, maps.ctypes.data, sizes.ctypes.data, cap, depths.ctypes.data, buf, 512)
+    if rc < 0:
+        raise ValueError("unknown descriptor or matcher name")
+    return [maps[k, :sizes[k]].copy() for k in range(len(types))], depths, buf.value.decode()
