@@ -962,6 +962,13 @@ int spvo_profile_stage_kernel(spvo_ctx *ctx, const char *stage, char *name, size
  * single-channel stem, a layer merged into its sibling's launch, an INT8 depthwise + pointwise block in one launch, the fused
  * heads) reports info[0 .. 4] = 0. */
 int spvo_profile_stage_variant(spvo_ctx *ctx, const char *stage, int info[7]);
+/* What the launches that spvo_profile_stage_variant leaves out last ran.  stage = "conv:<index of a pointwise op>": info[0] = 1 once the
+ * INT8 depthwise + pointwise block ran as one launch of dwpw_i8_kernel<G, STEM, POOL, EPI> (0: the op runs layer by layer, or has not run
+ * yet -- then all of info is 0), [1] = G (16-channel groups of the depthwise layer: 4 or 8), [2] = STEM (the fp32 stem in the same launch),
+ * [3] = POOL, [4] = EPI (1: BatchNorm), [5] = tiles of 64 output channels, and of the most recent launch [6] = tiles of 8 x 32 pixels,
+ * [7] = workgroups.  stage = "heads": info[0] = 1 once the fused tail ran, [1] = 1 heads_fused_kernel<false> (FP32 engines), 2
+ * heads_fused_kernel<true> (FP16), 3 heads_i8_kernel, [6] = pixel tiles (16 pixels; INT8: 32), [7] = workgroups; [2 .. 5] = 0. */
+int spvo_profile_stage_fused(spvo_ctx *ctx, const char *stage, int info[8]);
 
 /* ------------------------------------------------------- diagnostic switches (A/B measurements, parity debugging)
  * Which kernels / streams an engine uses is decided by the library from the plan and the sizes.  The decisions can be overridden

@@ -59,7 +59,39 @@ def fma32(a, b, c) -> np.ndarray:
     """IEEE-754 fusedMultiplyAdd of fp32 arrays, correctly rounded (what v_fma_f32 / std::fmaf compute): the product of two 24-bit
     significands is exact in float64; the sum with c is rounded to 53 bits ROUND-TO-ODD (TwoSum gives the rounding error exactly: when the
     sum is inexact and its last bit is even, step to the neighbour on the error's side), and rounding that to fp32 is then the correctly
-    rounded result -- 53 >= 2 * 24 + 2 bits make the double rounding innocuous (Boldo & Melquiond)."""
+    rounded result -- 53 >= 2 * 24 + 2 bits make the double rounding innocuous (Boldo & Melquiond).
+
+    The function is elementwise, so a large array is evaluated in slabs of about 2^17 elements on a few threads: the dozen float64
+    temporaries of a slab stay in cache (a level-0 tensor of two 120 x 392 images is 48 MB per temporary otherwise), and numpy
+    releases the interpreter lock inside them.  Same operations per element, same bits."""
+    a, b, c = (np.asarray(v, np.float32) for v in (a, b, c))
+    shape = np.broadcast_shapes(a.shape, b.shape, c.shape)
+    if len(shape) < 2 or int(np.prod(shape)) < (1 << 18):
+        return _fma32_slab(a, b, c)
+    av, bv, cv = (np.broadcast_to(v, shape) for v in (a, b, c))
+    out = np.empty(shape, f32)
+    step = max(1, (1 << 17) // max(1, int(np.prod(shape[2:]))))
+
+    def slab(ij):
+        i, j = ij
+        out[i, j:j + step] = _fma32_slab(av[i, j:j + step], bv[i, j:j + step], cv[i, j:j + step])
+
+    list(_slab_pool().map(slab, [(i, j) for i in range(shape[0]) for j in range(0, shape[1], step)]))
+    return out
+
+
+_pool = []
+
+
+def _slab_pool():
+    if not _pool:
+        import os
+        from concurrent.futures import ThreadPoolExecutor
+        _pool.append(ThreadPoolExecutor(max_workers=max(1, min(8, os.cpu_count() or 1))))
+    return _pool[0]
+
+
+def _fma32_slab(a, b, c) -> np.ndarray:
     a64, b64, c64 = (np.asarray(v, np.float32).astype(np.float64) for v in (a, b, c))
     p = a64 * b64
     s = p + c64

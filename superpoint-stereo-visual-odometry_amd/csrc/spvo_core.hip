@@ -526,4 +526,24 @@ int spvo_profile_stage_variant(spvo_ctx *c, const char *stage, int info[7]) {
   return fail(c, SPVO_ERR_INVALID, "no convolution of the loaded engine is timed under that stage name");
 }
 
+int spvo_profile_stage_fused(spvo_ctx *c, const char *stage, int info[8]) {
+  if (!c || !stage || !info) return fail(c, SPVO_ERR_INVALID, "null argument");
+  for (int q = 0; q < 8; ++q) info[q] = 0;
+  if (!std::strcmp(stage, "heads")) {
+    if (!c->weights) return fail(c, SPVO_ERR_STATE, "no engine is loaded");
+    if (c->heads_fused && c->heads_kind) { info[0] = 1; info[1] = c->heads_kind; info[6] = c->heads_tiles; info[7] = c->heads_wgs; }
+    return SPVO_OK;
+  }
+  for (size_t i = 0; i < c->ops.size(); ++i) {
+    const Op &op = c->ops[i];
+    if (op.type != OP_CONV || op.stage < 0 || op.stage >= (int)c->stages.size() || c->stages[op.stage].name != stage) continue;
+    if (op.fused_dw >= 0 && op.launch_block) {
+      info[0] = 1; info[1] = op.launch_block / 1000; info[2] = op.launch_block / 100 % 10; info[3] = op.launch_block / 10 % 10; info[4] = op.launch_block % 10;
+      info[5] = op.cout / 64; info[6] = op.launch_tiles; info[7] = op.launch_wgs;
+    }
+    return SPVO_OK;
+  }
+  return fail(c, SPVO_ERR_INVALID, "no convolution of the loaded engine is timed under that stage name");
+}
+
 }  // extern "C"

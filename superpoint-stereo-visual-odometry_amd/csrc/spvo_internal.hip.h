@@ -118,6 +118,7 @@ struct Op {
   double flops_per_image = 0;
   int stage = -1;
   mutable int launch_tiles = 0, launch_wgs = 0;   // tiled kernels: tiles and workgroups of this op's most recent launch (spvo_profile_stage_variant)
+  mutable int launch_block = 0;                   // INT8 fused block: the dwpw_i8_kernel instance of that launch, 1000 G + 100 STEM + 10 POOL + EPI (spvo_profile_stage_fused)
 };
 
 struct Stage {
@@ -321,6 +322,8 @@ struct spvo_ctx {
   bool s3 = false;                 // the loaded FP32 engine runs in split mode
   size_t head_start = 0;           // ops [head_start, end) = the 1x1 heads + L2 norm: a submission runs them on the tail stream
   int launch_tiles = 0, launch_wgs = 0;   // what the tiled kernels' launchers (launch_conv*_instance) last enqueued; launch_op copies them to its op
+  int launch_block = 0;                   // ... and launch_dwpw8_instance: its instance (Op::launch_block)
+  int heads_kind = 0, heads_tiles = 0, heads_wgs = 0;   // the fused tail's most recent launch (launch_heads, launch_heads8): 1 = heads_fused_kernel<false>, 2 = <true>, 3 = heads_i8_kernel
   // launch segments replayed from HIP graphs (launch_segments.hip.h; the entries are the sets': SubmitSet::seg_*): on for FP16 / INT8 engines (tuning "graphs": 0 off, 2 on for every engine)
   bool use_graphs = false;
   LaunchRecorder rec;

@@ -270,7 +270,9 @@ int launch_op(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t stream
       double fl = op.flops_per_image + dw.flops_per_image, by = (double)t0.ch * t0.H * t0.W * esz(t0) + (double)op.cout * to.H * to.W * esz(to);
       if (op.fused_stem) fl += c->ops[0].flops_per_image + c->ops[1].flops_per_image;
       ScopedStage st(c, op.stage, fl * batch, batch * by + (double)op.cout * op.cin + 9.0 * dw.cout, stream);
-      return launch_conv8(c, op, img0, batch, stream);
+      const int rc = launch_conv8(c, op, img0, batch, stream);
+      op.launch_tiles = c->launch_tiles; op.launch_wgs = c->launch_wgs; op.launch_block = c->launch_block;   // (spvo_profile_stage_fused)
+      return rc;
     }
     ScopedStage st(c, op.stage, op.flops_per_image * batch, bytes, stream);
     c->launch_tiles = c->launch_wgs = 0;
@@ -328,6 +330,7 @@ int launch_heads(spvo_ctx *c, int batch, hipStream_t stream) {
   // one workgroup per CU: each takes an equal share of the 16-pixel tiles of all images (heads.hip.h)
   const int ntiles = (batch * ti.H * ti.W + 15) / 16;
   const dim3 grid(std::min(c->num_cus, (ntiles + 1) / 2));
+  c->heads_kind = f16 ? 2 : 1; c->heads_tiles = ntiles; c->heads_wgs = (int)grid.x;   // (spvo_profile_stage_fused)
   if (f16) hipLaunchKernelGGL(heads_fused_kernel<true>, grid, dim3(HEADS_THREADS), HEADS_LDS_BYTES, stream, a);
   else hipLaunchKernelGGL(heads_fused_kernel<false>, grid, dim3(HEADS_THREADS), HEADS_LDS_BYTES, stream, a);
   HIP_TRY(c, hipGetLastError());

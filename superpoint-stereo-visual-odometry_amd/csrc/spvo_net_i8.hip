@@ -146,7 +146,9 @@ static int launch_dwpw8_instance(spvo_ctx *c, const DwPwArgs8 &a, hipStream_t st
   const int n_tiles = a.tiles_x * a.tiles_y * a.batch;
   const int force = tuning("int8_fused", 1);   // (measurements: 2, 3, 4 = one, two, three workgroups per CU)
   const int wg_per_cu = force > 1 ? force - 1 : per_cu[dev];
-  hipLaunchKernelGGL(k, dim3(std::min(n_tiles, c->num_cus * wg_per_cu)), dim3(DWPW_THREADS), T::LDS_BYTES, stream, a);
+  c->launch_tiles = n_tiles; c->launch_wgs = std::min(n_tiles, c->num_cus * wg_per_cu);
+  c->launch_block = 1000 * G + 100 * (STEM ? 1 : 0) + 10 * (POOL ? 1 : 0) + EPI;   // (spvo_profile_stage_fused)
+  hipLaunchKernelGGL(k, dim3(c->launch_wgs), dim3(DWPW_THREADS), T::LDS_BYTES, stream, a);
   HIP_TRY(c, hipGetLastError());
   return SPVO_OK;
 }
@@ -267,6 +269,7 @@ int launch_heads8(spvo_ctx *c, int batch, hipStream_t stream) {
   const double hbytes = batch * ((double)(pb.cin + db.cin) * ti.H * ti.W + (double)(pb.cout + (a.desc_raw ? 2 : 1) * db.cout) * ti.H * ti.W * 4) + (double)(pb.cout * pb.cin + db.cout * db.cin);
   ScopedStage st(c, stage_id(c, "heads"), (pb.flops_per_image + db.flops_per_image) * batch, hbytes, stream);
   const int ntiles = (batch * ti.H * ti.W + 31) / 32;
+  c->heads_kind = 3; c->heads_tiles = c->heads_wgs = ntiles;   // (spvo_profile_stage_fused)
   hipLaunchKernelGGL(heads_i8_kernel<>, dim3(ntiles), dim3(HEADS8_THREADS), 0, stream, a);
   HIP_TRY(c, hipGetLastError());
   return SPVO_OK;

@@ -16,6 +16,7 @@ void free_plan(spvo_ctx *c) {
   for (auto &o : c->ops) dev_free(o.d_w, o.d_b, o.d_bn_scale, o.d_bn_shift, o.d_w16, o.d_w8, o.d_ws3, o.d_wq32, o.d_wsel, o.d_qm, o.d_sched);
   dev_free(c->d_heads_w, c->d_heads_w8, c->d_heads_qm, c->d_heads_b);
   c->heads_fused = false;
+  c->heads_kind = c->heads_tiles = c->heads_wgs = 0;
   c->tensors.clear(); c->ops.clear(); c->weights = false; c->fp16 = false; c->int8 = false; c->s3 = false;
 }
 

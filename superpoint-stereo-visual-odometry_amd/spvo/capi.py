@@ -99,7 +99,7 @@ SYMBOLS = [
     "spvo_preprocess", "spvo_forward", "spvo_debug_tensor", "spvo_heatmap", "spvo_nms",
     "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8", "spvo_match_last_form",
     "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_orb_describe_octaves", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_akaze_describe", "spvo_akaze_detect_pair", "spvo_akaze_suppress_debug", "spvo_brisk_orb_pair", "spvo_akaze_orb_pair", "spvo_akaze_brisk_pair", "spvo_orb_octaves_link_debug", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_describe", "spvo_sift_detect_pair", "spvo_classic_sift_pair", "spvo_brisk_sift_pair", "spvo_akaze_sift_pair", "spvo_sift_link_debug", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_match_l2_u8", "spvo_match_l2_u8_slots", "spvo_set_binary_prematch_norm", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
-    "spvo_profile_enable", "spvo_profile_reset", "spvo_profile_only", "spvo_profile_count", "spvo_profile_get", "spvo_profile_stage_kernel", "spvo_profile_stage_variant",
+    "spvo_profile_enable", "spvo_profile_reset", "spvo_profile_only", "spvo_profile_count", "spvo_profile_get", "spvo_profile_stage_kernel", "spvo_profile_stage_variant", "spvo_profile_stage_fused",
     "spvo_set_tuning", "spvo_get_tuning", "spvo_clear_tuning",
     "spvo_comm_unique_id", "spvo_comm_available", "spvo_comm_create", "spvo_comm_create_host", "spvo_comm_rank", "spvo_comm_world", "spvo_comm_destroy",
     "spvo_pose_allgather", "spvo_pose_allgather_n",
@@ -213,6 +213,7 @@ def load() -> C.CDLL:
     lib.spvo_profile_get.argtypes = [vp, C.c_int, C.c_char_p, C.c_size_t, dp, C.POINTER(C.c_longlong), dp, dp]
     lib.spvo_profile_stage_kernel.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_size_t, dp]
     lib.spvo_profile_stage_variant.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int)]
+    lib.spvo_profile_stage_fused.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int)]
     lib.spvo_comm_unique_id.argtypes = [vp]
     lib.spvo_comm_create.argtypes = [C.c_int, C.c_int, C.c_int, vp, C.POINTER(vp)]
     lib.spvo_comm_create_host.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(vp)]
@@ -1108,6 +1109,17 @@ class Context:
         if info[0] == 0:
             return None
         return dict(ks=info[0], ck=info[1], wr=info[2], wc=info[3], pool=bool(info[4]), tiles=info[5], wgs=info[6])
+
+    def stage_fused(self, stage):
+        """What a fused launch last ran.  "conv:<pointwise op>": dict(G, STEM, POOL, EPI, co_tiles, tiles, wgs) of the INT8 block kernel's
+        instance and grid; "heads": dict(kind = 1 fp32 / 2 fp16 / 3 int8 fused tail, tiles, wgs).  None where no fused launch ran (yet)."""
+        info = (C.c_int * 8)()
+        self._check(self.lib.spvo_profile_stage_fused(self.h, stage.encode(), info))
+        if info[0] == 0:
+            return None
+        if stage == "heads":
+            return dict(kind=info[1], tiles=info[6], wgs=info[7])
+        return dict(G=info[1], STEM=info[2], POOL=info[3], EPI=info[4], co_tiles=info[5], tiles=info[6], wgs=info[7])
 
 
 def set_tuning(name: str, value: int):

@@ -24,7 +24,7 @@ from tests import conv_variant_cases as cvc
 
 pytestmark = pytest.mark.gpu
 
-ENGINE_TUNING = {"FP32": dict(winograd=0, heads_fused=0), "FP16": dict(heads_fused=0), "INT8": dict(heads_fused=0)}   # ("int8_fused" stays at its default)
+ENGINE_TUNING = {"FP32": dict(winograd=0, heads_fused=0), "FP16": dict(heads_fused=0), "INT8": dict(heads_fused=0)}   # (the fused tails, and the fused INT8 blocks, which these plans do not contain: tests/test_gpu_fused_blocks.py)
 VARIANTS = [0, 11, 12, 21, 22]                                   # 0 = unset: the model's choice
 CONFIGS = {                                                      # plan, H, W, batch, max_batch
     "edge-104x200": ("edge", 104, 200, 2, 2),
