@@ -90,6 +90,18 @@ __device__ __forceinline__ void glds16(const float *src, float *lds_wave_base) {
       (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, 0);
 }
 
+// The same load as "wave-uniform 64-bit base + 32-bit lane offset": global_load_lds_dwordx4 vOff, s[base:base+1], no vector
+// instruction for the address.  Instruction selection takes that form only when it sees add(uniform base, zext(lane offset)) in
+// the block of the load; a lane offset that never changes has its zero-extension hoisted out of the loop, and a base + constant
+// is reassociated behind the lane offset, and then every load gets a 64-bit vector add in front (v_lshl_add_u64).  The two
+// empty statements keep both values opaque up to this point and emit nothing.  `lane_off` is passed by reference and stays the
+// caller's one register (a copy would cost the v_mov this saves).
+__device__ __forceinline__ void glds16_sv(const char *uniform_base, unsigned &lane_off, float *lds_wave_base) {
+  asm volatile("" : "+s"(uniform_base));
+  asm volatile("" : "+v"(lane_off));
+  glds16(reinterpret_cast<const float *>(uniform_base + lane_off), lds_wave_base);
+}
+
 template <int KS, int CK, int WR, int WC>
 struct ConvTile {
   static constexpr int TH = 4 * WR;

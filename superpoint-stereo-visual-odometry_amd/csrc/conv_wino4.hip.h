@@ -39,7 +39,7 @@
 //     reads) are issued by inline assembly and waited for by s_waitcnt lgkmcnt(N) with N counted at compile time (ITEM = 1, see
 //     WINO4_ITEM_LEAD below); the compiler's own placement drained the LDS queue six times per item.  Measured on one MI355X, same
 //     box, old item against new: conv1b 403 -> 390 us inside the benchmark, matrix stream 3425 -> 3317 cycles per item
-//     (profiles/wino4_item_*);
+//     (profiles/wino4_item_*); ITEM = 2, the default, also issues the item's LDS-DMA from a scalar base and a lane offset (below);
 //   * the inverse transform (36 -> 16 per output channel and tile) runs in registers, as before.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -80,7 +80,7 @@
 #ifndef WINO4_H2_STRIDE
 #define WINO4_H2_STRIDE 8
 #endif
-// The item with counted operand waits (template flag ITEM = 1, the default; 0 = the item as it was, for A/B runs and the bit-for-bit test:
+// The item with counted operand waits (template parameter ITEM = 1; 0 = the item as it was, for A/B runs and the bit-for-bit test:
 // spvo_set_tuning "wino4_item").  Same matrix instructions, same order, same operands.  What differs is how a wave waits for its operand
 // reads.  In the ITEM = 0 form the compiler places the waits, and because the transform steps (with LDS operations of their own) sit in
 // wave-uniform branches it falls back to s_waitcnt lgkmcnt(0) at the joins: six full drains per item, each of which also waits for the
@@ -91,6 +91,17 @@
 // only makes the true number outstanding larger than N: the wait errs on the safe side.  The compiler's own waits (for the transform's
 // reads) count only what it tracks and are for the same reason never too loose.  The half-used B pieces (4 and 9: positions 16 and
 // 17) are read as 8 bytes, so that no read's destination overlaps an older read's; the role predicate is scalar arithmetic.
+//
+// ITEM = 2 (the default) is ITEM = 1 with its LDS-DMA issued as global_load_lds_dwordx4 vOff, s[base:base+1]: the scalar 64-bit base of the
+// chunk / tile, advanced by scalar adds (also from one of the five filter pieces to the next: 8192 bytes do not fit the immediate), and the
+// thread's 32-bit lane offset, which never changes (glds16_sv, conv_mfma.hip.h).  fp32 matrix and vector instructions share the issue, and
+// ITEM = 1 has a 64-bit vector add (v_lshl_add_u64) in front of each of the item's seven loads, which computes an address and no result.
+// Nothing else differs.  The loads remain the compiler's builtin: it still counts vmcnt for them and still writes M0 in front of each.
+// WAIT RULE, unchanged: the kernel waits for its LDS-DMA only by the explicit s_waitcnt vmcnt(0) at every item's start and in front of the
+// epilogue; nothing else may rely on staged data.  Measured, same box, items alternating in one process: conv1b 379 -> 367 us, matrix
+// stream 3313 -> 3225 cycles per item.  (The other address arithmetic of the item -- LDS addresses of the buffers k & 1, the copies that
+// assemble packed operands in the transform -- was taken out too, measured step by step, and put back: NOTES.md, "F(4x4) item: LDS-DMA
+// from a scalar base".)
 #ifndef WINO4_ITEM_LEAD
 #define WINO4_ITEM_LEAD 6
 #endif
@@ -202,13 +213,13 @@ constexpr int wino4_wait_count(int p, int lead) {
 template <class F, int... P>
 __device__ __forceinline__ void wino4_for_each(F &&f, std::integer_sequence<int, P...>) { (f(std::integral_constant<int, P>{}), ...); }
 
-template <bool POOL, bool RELU, int TAG = 0, int TB = 2, bool ITEM = true>
+template <bool POOL, bool RELU, int TAG = 0, int TB = 2, int ITEM = 2>
 __global__ __launch_bounds__(256 * TB, TB) void conv_wino4_kernel(const ConvArgs a) {
   using T = Wino4TileT<TB>;
   constexpr int CK = T::CK, LW = T::LW, LH = T::LH, LW4 = LW / 4, NTH = T::NTH;
   constexpr int IN_V4 = T::IN_FLOATS / 4;        // 720 (400) 16-byte pieces per raw tile
   constexpr int U_V4 = T::U_FLOATS / 4;          // 2304 per filter slab
-  constexpr bool NEW_ITEM = ITEM && !(WINO4_ABL & 8);   // (the read-once ablation exists in the earlier item only)
+  constexpr bool NEW_ITEM = ITEM != 0 && !(WINO4_ABL & 8);   // (the read-once ablation exists in the earlier item only)
   constexpr int NIT_U = (U_V4 + NTH - 1) / NTH;  // 5, the last one by threads 0..255 (9, all full)
   typedef float f32x2 __attribute__((ext_vector_type(2)));
   typedef float f32x4v __attribute__((ext_vector_type(4)));
@@ -252,19 +263,32 @@ __global__ __launch_bounds__(256 * TB, TB) void conv_wino4_kernel(const ConvArgs
     return 4u * (unsigned)(ci * (int)in_plane + r * a.in_wp + q * 4);
   };
   constexpr int R0 = NTH - 256;   // first thread that carries a second raw piece
-  const unsigned roff0 = raw_piece_off(tid), roff1 = raw_piece_off(NTH + (tid - R0));
+  unsigned roff0 = raw_piece_off(tid), roff1 = raw_piece_off(NTH + (tid - R0));   // (not const: ITEM = 2 passes them through glds16_sv)
   const bool raw2 = tid >= R0 && NTH + (tid - R0) < IN_V4;
   auto issue_raw = [&](const TileRef &t, int chunk, float *buf) {
     const char *inb = reinterpret_cast<const char *>(t.in_base + (size_t)chunk * CK * in_plane);
     glds16(reinterpret_cast<const float *>(inb + roff0), buf + (wave * 64) * 4);
     if (raw2) glds16(reinterpret_cast<const float *>(inb + roff1), buf + (NTH + (wave - R0 / 64) * 64) * 4);
   };
-  const unsigned uoff = 16u * (unsigned)tid;
+  unsigned uoff = 16u * (unsigned)tid;
   auto issue_u = [&](const TileRef &t, int chunk, float *buf) {
     const char *wb = reinterpret_cast<const char *>(t.w_base + (size_t)chunk * T::U_FLOATS);
 #pragma unroll
     for (int it = 0; it < NIT_U; ++it)
       if (it < NIT_U - 1 || tid < U_V4 - (NIT_U - 1) * NTH) glds16(reinterpret_cast<const float *>(wb + (uoff + 16u * NTH * it)), buf + (it * NTH + wave * 64) * 4);
+  };
+  // ITEM = 2: the same pieces as "scalar base + lane offset" (glds16_sv), no vector instruction for an address.  A filter piece advances
+  // the scalar base: its 8192-byte step fits neither the instruction's immediate nor, without a vector add, the lane offset.
+  auto issue_raw2 = [&](const TileRef &t, int chunk, float *buf) {
+    const char *inb = reinterpret_cast<const char *>(t.in_base + (size_t)chunk * CK * in_plane);
+    glds16_sv(inb, roff0, buf + (wave * 64) * 4);
+    if (raw2) glds16_sv(inb, roff1, buf + (NTH + (wave - R0 / 64) * 64) * 4);
+  };
+  auto issue_u2 = [&](const TileRef &t, int chunk, float *buf) {
+    const char *wb = reinterpret_cast<const char *>(t.w_base + (size_t)chunk * T::U_FLOATS);
+#pragma unroll
+    for (int it = 0; it < NIT_U; ++it)
+      if (it < NIT_U - 1 || tid < U_V4 - (NIT_U - 1) * NTH) glds16_sv(wb + (size_t)16 * NTH * it, uoff, buf + (it * NTH + wave * 64) * 4);
   };
 
   // ---- input transform: two threads per patch.  u = tid & 255: input channel = u >> 6 (= wave & 3), tile = lane & 31 (tile row
@@ -482,8 +506,8 @@ __global__ __launch_bounds__(256 * TB, TB) void conv_wino4_kernel(const ConvArgs
           if (FIRST) acc[pos] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_op, b_op, f32x4v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
           else acc[pos] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_op, b_op, acc[pos], 0, 0, 0);
           __builtin_amdgcn_sched_barrier(0);
-          if (!(WINO4_ABL & 2) && p == 1 && cu.id < n_tiles) issue_u(cu.t, cu.chunk, u_next);
-          if (!(WINO4_ABL & 4) && p == 4 && cr.id < n_tiles) issue_raw(cr.t, cr.chunk, raw_next3);
+          if (!(WINO4_ABL & 2) && p == 1 && cu.id < n_tiles) { if constexpr (ITEM == 2) issue_u2(cu.t, cu.chunk, u_next); else issue_u(cu.t, cu.chunk, u_next); }
+          if (!(WINO4_ABL & 4) && p == 4 && cr.id < n_tiles) { if constexpr (ITEM == 2) issue_raw2(cr.t, cr.chunk, raw_next3); else issue_raw(cr.t, cr.chunk, raw_next3); }
           read_slot(std::integral_constant<int, p + LEAD>{});
           // the transform: H1 of item k + 2 (its three row reads the same way: issued untracked in steps 0..2, waited for by count in front
           // of the row pass of steps 3..5) or H2 of item k + 1

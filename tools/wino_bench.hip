@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <cmath>
 #include <random>
 #include <vector>
@@ -17,9 +18,9 @@
 #define WINO4_TB 2   // -DWINO4_TB=1: the 4-wave form (8 x 32 outputs per workgroup)
 #endif
 #ifndef WINO4_ITEM
-#define WINO4_ITEM 1   // -DWINO4_ITEM=0: the item with the compiler's operand waits (the library's "wino4_item" switch)
+#define WINO4_ITEM 2   // -DWINO4_ITEM=1: LDS-DMA with a vector address; 0: also the compiler's operand waits (the library's "wino4_item" switch)
 #endif
-#define KERNEL(P, R, T, O) conv_wino4_kernel<P, R, T, WINO4_TB, WINO4_ITEM != 0>
+#define KERNEL(P, R, T, O) conv_wino4_kernel<P, R, T, WINO4_TB, WINO4_ITEM>
 #define PACK pack_conv_weights_wino4
 #define THREADS (256 * WINO4_TB)
 #define COT 64
@@ -126,29 +127,45 @@ int main(int argc, char **argv) {
   CK(hipEventElapsedTime(&ms, e0, e1));
   const double us = ms * 1e3 / reps, fl = 2.0 * batch * H * W * (double)cout * cin * 9;
 #if defined(WINO4)
-  // WINO_ITEM_AB=<rounds>: both items of the F(4x4) kernel in ONE process, alternately, `reps` launches per block: the same-box, same-clock
-  // comparison (separate processes differ by ~1 % among themselves)
+  // WINO_ITEM_AB=<rounds>: the three items of the F(4x4) kernel in ONE process, alternately, `reps` launches per block: the same-box,
+  // same-clock comparison (separate processes differ by ~1 % among themselves).  Afterwards one launch of each item into a cleared output:
+  // all must agree bit for bit.
   if (getenv("WINO_ITEM_AB")) {
-    auto launch_item = [&](bool item) {
-#define WINO_AB_LAUNCH(P) do { if (item) hipLaunchKernelGGL((conv_wino4_kernel<P, true, 0, WINO4_TB, true>), dim3(grid), dim3(THREADS), LDSB, 0, a); \
-                               else hipLaunchKernelGGL((conv_wino4_kernel<P, true, 0, WINO4_TB, false>), dim3(grid), dim3(THREADS), LDSB, 0, a); } while (0)
-      if (pool) WINO_AB_LAUNCH(true); else WINO_AB_LAUNCH(false);
+#define WINO_AB_ITEMS(X) X(0) X(1) X(2)
+    std::vector<int> items;
+#define WINO_AB_LIST(I) items.push_back(I);
+    WINO_AB_ITEMS(WINO_AB_LIST)
+#undef WINO_AB_LIST
+    auto launch_item = [&](int item) {
+#define WINO_AB_LAUNCH(I) if (item == I) { if (pool) hipLaunchKernelGGL((conv_wino4_kernel<true, true, 0, WINO4_TB, I>), dim3(grid), dim3(THREADS), LDSB, 0, a); \
+                                           else hipLaunchKernelGGL((conv_wino4_kernel<false, true, 0, WINO4_TB, I>), dim3(grid), dim3(THREADS), LDSB, 0, a); }
+      WINO_AB_ITEMS(WINO_AB_LAUNCH)
 #undef WINO_AB_LAUNCH
     };
-    CK(hipFuncSetAttribute((const void *)conv_wino4_kernel<true, true, 0, WINO4_TB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
-    CK(hipFuncSetAttribute((const void *)conv_wino4_kernel<true, true, 0, WINO4_TB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
-    CK(hipFuncSetAttribute((const void *)conv_wino4_kernel<false, true, 0, WINO4_TB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
-    CK(hipFuncSetAttribute((const void *)conv_wino4_kernel<false, true, 0, WINO4_TB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
+#define WINO_AB_ATTR(I) CK(hipFuncSetAttribute((const void *)conv_wino4_kernel<true, true, 0, WINO4_TB, I>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB)); \
+                        CK(hipFuncSetAttribute((const void *)conv_wino4_kernel<false, true, 0, WINO4_TB, I>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
+    WINO_AB_ITEMS(WINO_AB_ATTR)
+#undef WINO_AB_ATTR
     for (int r = 0; r < atoi(getenv("WINO_ITEM_AB")); ++r)
-      for (int item = 0; item < 2; ++item) {
-        launch_item(item != 0);
+      for (int item : items) {
+        launch_item(item);
         CK(hipEventRecord(e0));
-        for (int i = 0; i < reps; ++i) launch_item(item != 0);
+        for (int i = 0; i < reps; ++i) launch_item(item);
         CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
         float ab_ms;
         CK(hipEventElapsedTime(&ab_ms, e0, e1));
         printf("  block %d item %d: %8.2f us\n", r, item, ab_ms * 1e3 / reps);
       }
+    std::vector<float> ref(out_n), got(out_n);
+    for (int item : items) {
+      CK(hipMemset(d_out, 0, out_n * 4));
+      launch_item(item);
+      CK(hipDeviceSynchronize());
+      CK(hipMemcpy(item != items[0] ? got.data() : ref.data(), d_out, out_n * 4, hipMemcpyDeviceToHost));
+      if (item != items[0]) printf("  item %d against item %d: %s\n", item, items[0], memcmp(ref.data(), got.data(), out_n * 4) ? "DIFFERENT BITS" : "same bits");
+    }
+    launch();   // (the sampled check below reads the default item's output)
+    CK(hipDeviceSynchronize());
   }
 #endif
 #ifdef WINO_STAMPS
