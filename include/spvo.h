@@ -716,8 +716,7 @@ int spvo_classic_sift_pair(spvo_ctx *ctx, const spvo_classic_opts *opts /* kind 
  * Afterwards the resident u8 image is the RIGHT image's (spvo_sift_describe(img = NULL), spvo_brisk_describe(NULL) work on it); BRISK:
  * spvo_brisk_detect_debug_layer answers SPVO_ERR_STATE, as after spvo_brisk_detect_pair; AKAZE: the right image's scale space is resident,
  * as after spvo_akaze_orb_pair; no SIFT pyramid is resident (spvo_sift_debug_level: SPVO_ERR_STATE).
- * ORB + SIFT has no such call: the ORB detector keeps a pyramid and an image of its own, not the shared resident image, and its records
- * name octaves up to 7.
+ * (ORB + SIFT: spvo_orb_sift_pair, below.)
  *   SPVO_ERR_CAPACITY  an image yields more rows than slot_capacity: out_*->n report both counts, both slots are left unfilled, nothing
  *                      is truncated
  *   SPVO_ERR_INVALID   nothing is written or touched: NULL arguments, cap < 0 or a positive cap with a NULL buffer, bad or equal slots,
@@ -733,6 +732,36 @@ typedef struct { int n; spvo_akaze_keypoint *kp; float *desc /* [cap][128] */; i
 int spvo_akaze_sift_pair(spvo_ctx *ctx, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride,
                          float threshold, int slot_l, int slot_r, int slot_capacity,
                          spvo_akaze_sift_features *out_l, spvo_akaze_sift_features *out_r);
+/* The ORB detector in front of another algorithm's extractor, pair-resident: ORB + BRISK into the ring of ten BINARY slots (64-byte rows,
+ * spvo_brisk_detect_pair's protocol) and ORB + SIFT into the ring of ten SIFT slots (spvo_brisk_sift_pair's protocol).  Per image, left
+ * first, on the solver's stream and without a host round trip: the staged image becomes the context's resident u8 image; spvo_orb_detect's
+ * launches run with THAT image as level 0 of the pyramid (levels 1 .. 7 and the detector's maps stay its own; ORB's own rows are not kept);
+ * one kernel turns the detector's list into 24-byte records {x, y, size = 31 * 1.2^octave (the repeated float product), angle in degrees
+ * 0 .. 360, response, octave} -- n = min(the eight levels' counts, nfeatures) -- and the extractor's chain reads them where they lie:
+ *   spvo_orb_brisk_pair  the integral image, the border rule at every record's own size as one order-preserving compaction, the rows with
+ *                        the count read on the device, the finish launch.  Byte equality: what spvo_orb_detect(img, nfeatures) followed
+ *                        by spvo_brisk_describe(its x, y, those sizes) returns -- the records [kept] with `angle` = the extractor's
+ *                        degrees, the 64-byte rows.  The slot's own records hold (x, y, that angle, response, octave).
+ *   spvo_orb_sift_pair   the reduced Gaussian pyramid for octaves 0 .. max_octave and spvo_sift_describe's kernel on all records;
+ *                        max_octave is the highest ORB level of the shape that can hold a keypoint (more than 64 pixels in both
+ *                        dimensions at scale 1.2^l), 0 if none can, and every such shape has SIFT's octave max_octave.  Byte equality:
+ *                        spvo_orb_detect followed by spvo_sift_describe on exactly those records; none is erased, no angle changes.
+ * An image without a keypoint -- a shape without a level that can hold one included -- fills its slot with 0 rows: SPVO_OK.  Afterwards
+ * the resident u8 image is the RIGHT image (spvo_brisk_describe(NULL), spvo_sift_describe(NULL), spvo_orb_describe(NULL) work on it).
+ * spvo_set_prematch, the temporal partner (any filled slot of the ring and, for the binary ring, of 64-byte rows, whichever call filled
+ * it) and the re-allocation by a larger slot_capacity than any before are the siblings'.
+ *   SPVO_ERR_INVALID   nothing is written or touched: NULL arguments, bad or equal slots, slot_capacity outside 1 .. 32768,
+ *                      nfeatures <= 0, cap < 0 (SIFT: or a positive cap with a NULL buffer), what spvo_brisk_describe (BRISK call) /
+ *                      spvo_sift_describe (SIFT call) refuse of the shape
+ *   SPVO_ERR_STATE     a spvo_detect*_submit is in flight (outputs and slots stay as they were)
+ *   SPVO_ERR_CAPACITY  a level's corner buffer overflowed (spvo_orb_detect's answer), or an image yields more rows than slot_capacity:
+ *                      out_*->n report both counts, both slots are left unfilled, nothing is truncated */
+int spvo_orb_brisk_pair(spvo_ctx *ctx, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride,
+                        int nfeatures, int slot_l, int slot_r, int slot_capacity,
+                        spvo_brisk_features *out_l, spvo_brisk_features *out_r);   /* desc [cap][64] */
+int spvo_orb_sift_pair(spvo_ctx *ctx, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride,
+                       int nfeatures, int slot_l, int slot_r, int slot_capacity,
+                       spvo_sift_features *out_l, spvo_sift_features *out_r);
 /* The link of the two calls above -- compaction by keep flags, the reduced pyramid for octaves 0 .. max_octave, the describe launch on
  * the fixed grid with the count read on the device -- on a caller's list against the u8 image already resident, of shape rows x cols
  * (test hook: lists no image gives).  No detector runs, no slot is touched, the image stays resident.  keep = NULL: all records take

@@ -160,4 +160,39 @@ __global__ __launch_bounds__(256) void orb_link_finish_kernel(const Rec *__restr
   for (int i = tid; i < n * 2; i += nth) h_desc[i] = desc[i];
 }
 
+// The other direction (spvo_orb_brisk_pair, spvo_orb_sift_pair): the ORB DETECTOR's list, where orb_describe_kernel left it, in the form the
+// BRISK extractor's chain and the SIFT link read a detector's list -- what spvo_orb_detect and the host's to_keypoint do between them.
+//   n        = min(sum of the eight levels' counters[l][2], kp_cap), spvo_orb_detect's `base`
+//   rec[i]   = {x, y, 31 * level_scale[octave], the angle in degrees, response, octave}: the bytes of the host's conversion -- ONE float
+//              multiply each for size and angle, then + 360 for a negative angle, every operation rounded on its own (mul_rn / add_rn,
+//              conv_mfma.hip.h: a contracted multiply-add differs in the last bit, and HIP's __fmul_rn / __fadd_rn do not prevent one)
+//   keep[i]  = 1
+//   cnt      = a BRISK detector's counter block: [1] = n, [3] = the OR of the levels' overflow flags (cnt[2] = n as well)
+// level_scale: the host's repeated * 1.2f, passed by value.
+struct OrbLevelScale { float s[ORB_LEVELS]; };
+__global__ __launch_bounds__(256) void orb_records_kernel(const OrbKeypoint *__restrict__ kps, const int *__restrict__ counters, int kp_cap, const OrbLevelScale ls,
+                                                          BriskDetKeypoint *__restrict__ rec, int *__restrict__ keep, int *__restrict__ cnt) {
+  int total = 0, overflow = 0;
+#pragma unroll
+  for (int l = 0; l < ORB_LEVELS; ++l) {
+    total += counters[l * NMS_COUNTER_INTS + 2];
+    overflow |= counters[l * NMS_COUNTER_INTS + 3];
+  }
+  const int n = min(max(total, 0), kp_cap);
+  const int tid = blockIdx.x * 256 + threadIdx.x, nth = gridDim.x * 256;
+  if (tid == 0) { cnt[0] = 0; cnt[1] = n; cnt[2] = n; cnt[3] = overflow != 0; }
+  for (int i = tid; i < n; i += nth) {
+    const OrbKeypoint k = kps[i];
+    const float deg = mul_rn(k.angle, 57.29577951308232f);
+    BriskDetKeypoint r;
+    r.x = k.x; r.y = k.y;
+    r.size = mul_rn(31.f, ls.s[k.octave & (ORB_LEVELS - 1)]);
+    r.angle = deg < 0 ? add_rn(deg, 360.f) : deg;
+    r.response = k.response;
+    r.octave = k.octave;
+    rec[i] = r;
+    keep[i] = 1;
+  }
+}
+
 }  // namespace spvo

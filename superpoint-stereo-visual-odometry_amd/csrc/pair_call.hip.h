@@ -1,6 +1,6 @@
 // pair_call.hip.h -- the resident stereo-pair protocol, written once: what every entry point that takes a stereo pair, fills two device
 // slots and returns after one wait does around its own per-image chains (spvo_classic_detect; spvo_brisk_detect_pair and spvo_akaze_detect_pair
-// with their ORB / BRISK extractor variants; spvo_sift_detect_pair, spvo_classic_sift_pair and sift_link_pair).  Host code only.
+// with their ORB / BRISK extractor variants; spvo_orb_brisk_pair; spvo_sift_detect_pair, spvo_classic_sift_pair and sift_link_pair).  Host code only.
 //
 // A call is a PairCall<Family> whose methods are the protocol's phases, in this order; the caller's own refusals, allocations and chains
 // stand between them as ordinary code:

@@ -2,7 +2,8 @@
 // the Shi-Tomasi and FAST detectors and the ORB extractor for given keypoints (classic_detect.hip.h; at the keypoints' octaves: spvo_orb_describe_octaves), one submission per stereo pair into the
 // binary feature slots (spvo_classic_detect; its BRISK kinds hand the detector's list to spvo_brisk.hip, and spvo_sift.hip takes the same
 // detector link for spvo_classic_sift_pair), the ORB extractor as a device link behind a detector that reports octaves (orb_link.hip.h: orb_link_* for
-// spvo_brisk_orb_pair / spvo_akaze_orb_pair, and the test hook spvo_orb_octaves_link_debug), and spvo_preprocess for a context without an engine.  Everything here runs on the solver's stream (stream2) and owns its buffers (spvo_ctx::orb, spvo_ctx::cls).
+// spvo_brisk_orb_pair / spvo_akaze_orb_pair, and the test hook spvo_orb_octaves_link_debug), the ORB detector in front of the BRISK extractor's chain and of the SIFT link
+// (spvo_orb_brisk_pair, spvo_orb_sift_pair: orb_records_kernel), and spvo_preprocess for a context without an engine.  Everything here runs on the solver's stream (stream2) and owns its buffers (spvo_ctx::orb, spvo_ctx::cls).
 #include "spvo_internal.hip.h"
 #include "pair_call.hip.h"
 #include "orb.hip.h"
@@ -171,10 +172,11 @@ int orb_prepare(spvo_ctx *c, int rows, int cols, int nfeatures, OrbPlan &p) {
   return orb_ensure_tables(c);
 }
 
-// The image in level 0 (o.im) -> keypoint records and descriptors in `kps` / `desc` (kp_cap rows), enqueued without a host round trip:
-// the pyramid level by level, then every stage once for all levels; one counter block per level, a level's keypoints land behind
-// those of the levels below (orb_describe_kernel sums their counts)
-int orb_enqueue(spvo_ctx *c, const OrbPlan &p, int rows, int cols, OrbKeypoint *kps, uint8_t *desc, int kp_cap) {
+// The image in level 0 (`im0`: o.im, or the resident image of spvo_ctx::cls for the pair calls whose extractor looks there -- levels 1 .. 7
+// and level 0's score / blur / tmp are ORB's own either way) -> keypoint records and descriptors in `kps` / `desc` (kp_cap rows), enqueued
+// without a host round trip: the pyramid level by level, then every stage once for all levels; one counter block per level, a level's
+// keypoints land behind those of the levels below (orb_describe_kernel sums their counts)
+int orb_enqueue(spvo_ctx *c, const OrbPlan &p, int rows, int cols, uint8_t *im0, OrbKeypoint *kps, uint8_t *desc, int kp_cap) {
   hipStream_t st = c->stream2;
   auto &o = c->orb;
   const int *ph = p.ph, *pw = p.pw;
@@ -185,13 +187,13 @@ int orb_enqueue(spvo_ctx *c, const OrbPlan &p, int rows, int cols, OrbKeypoint *
   for (int l = 0; l < ORB_LEVELS; ++l) {
     OrbLevel &L = lv.l[l];
     const int lcap = std::min(p.surv_cap, (ph[l] / 2 + 1) * (pw[l] / 2 + 1));
-    L.im = o.im + p.off[l]; L.score = o.score + p.off[l]; L.blur = o.blur + p.off[l]; L.tmp = o.tmp + p.off[l];
+    L.im = l == 0 ? im0 : o.im + p.off[l]; L.score = o.score + p.off[l]; L.blur = o.blur + p.off[l]; L.tmp = o.tmp + p.off[l];
     L.keys = o.keys + koff; L.rank = o.rank + koff; L.out_xy = o.out_xy + 2 * koff; L.counters = o.counters + l * NMS_COUNTER_INTS;
     L.h = ph[l]; L.w = pw[l]; L.cap = lcap; L.scale = p.lscale[l];
     L.want = (ph[l] <= 2 * ORB_EDGE + 2 || pw[l] <= 2 * ORB_EDGE + 2) ? 0 : p.want[l];
     want_max = std::max(want_max, L.want);
     koff += lcap;
-    if (l > 0) hipLaunchKernelGGL(orb_resize_kernel, dim3((pw[l] + 63) / 64, (ph[l] + 3) / 4), dim3(256), 0, st, o.im + p.off[l - 1], ph[l - 1], pw[l - 1], pw[l - 1], L.im, ph[l], pw[l],
+    if (l > 0) hipLaunchKernelGGL(orb_resize_kernel, dim3((pw[l] + 63) / 64, (ph[l] + 3) / 4), dim3(256), 0, st, lv.l[l - 1].im, ph[l - 1], pw[l - 1], pw[l - 1], L.im, ph[l], pw[l],
                                   o.tab + p.toff[l]);
   }
   if (want_max > 0) {
@@ -247,7 +249,7 @@ int spvo_orb_detect(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t 
   OrbPlan plan;
   if (int rc = orb_prepare(c, rows, cols, nfeatures, plan)) return rc;
   if (int rc = upload_strided(c, img, rows, cols, stride, o.src, o.im, st)) return rc;   // level 0: the image, rows packed
-  if (int rc = orb_enqueue(c, plan, rows, cols, o.kps, o.desc, kp_cap)) return rc;
+  if (int rc = orb_enqueue(c, plan, rows, cols, o.im, o.kps, o.desc, kp_cap)) return rc;
   int cnt[ORB_LEVELS * NMS_COUNTER_INTS];
   HIP_TRY(c, hipMemcpyAsync(cnt, o.counters, sizeof cnt, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
@@ -803,7 +805,7 @@ int orb_pair_chain(spvo_ctx *c, const spvo_classic_opts *opts, const OrbPlan &pl
   const int cap = opts->slot_capacity;
   HIP_TRY(c, hipMemcpyAsync(o.im, c->bin.pair.h_img + k * px, px, hipMemcpyHostToDevice, st));
   const int kp_cap = std::min(opts->nfeatures, cap);   // (more than `cap` rows are an error of the call: the slot need not hold them)
-  if (int rc = orb_enqueue(c, plan, rows, cols, out.d_kp, reinterpret_cast<uint8_t *>(out.d_desc), kp_cap)) return rc;
+  if (int rc = orb_enqueue(c, plan, rows, cols, o.im, out.d_kp, reinterpret_cast<uint8_t *>(out.d_desc), kp_cap)) return rc;
   hipLaunchKernelGGL(classic_finish_kernel, dim3(32), dim3(256), 0, st, o.counters, ORB_LEVELS, NMS_COUNTER_INTS, opts->nfeatures, nullptr, nullptr, nullptr, out.d_kp,
                      reinterpret_cast<const uint4 *>(out.d_desc), cap, out.d_n, out.h_n, out.h_kp, reinterpret_cast<uint4 *>(out.h_desc));
   return SPVO_OK;
@@ -881,6 +883,108 @@ int spvo_classic_detect(spvo_ctx *c, const spvo_classic_opts *opts, const uint8_
   const PairMirror mirrors[2] = {{bb.h_kp, sizeof(OrbKeypoint), bb.h_desc, (size_t)row_bytes},
                                  {bb.h_kp + cap, sizeof(OrbKeypoint), bb.h_desc + (size_t)cap * row_bytes, (size_t)row_bytes}};
   return pc.commit(mirrors);
+}
+
+// ---------------------------------------------------------------- the ORB detector in front of another algorithm's extractor, pair-resident
+namespace {
+// the highest level of a rows x cols image that can hold a keypoint (orb_enqueue's rule for L.want, orb_prepare's geometry), or 0 if none can
+int orb_top_level(int rows, int cols) {
+  int top = 0;
+  float scale = 1.f;
+  for (int l = 0; l < ORB_LEVELS; ++l, scale *= 1.2f) {
+    const int h = (int)std::lround(rows / scale), w = (int)std::lround(cols / scale);
+    if (h > 2 * ORB_EDGE + 2 && w > 2 * ORB_EDGE + 2) top = l;
+  }
+  return top;
+}
+
+// the record buffers of orb_records_kernel for `n` records
+int orb_records_ensure(spvo_ctx *c, int n) {
+  auto &o = c->orb;
+  if (n <= o.rec_cap) return SPVO_OK;
+  o.rec_cap = 0;
+  if (int rc = grow(c, wait_for(c->stream2), {plain(o.rec, (size_t)n), plain(o.crec, (size_t)n), plain(o.rec_keep, (size_t)n), zeroed(o.rec_cnt, 4)})) return rc;
+  o.rec_cap = n;
+  return SPVO_OK;
+}
+
+// A pair call's first link: the staged image becomes the resident image of spvo_ctx::cls, goes through spvo_orb_detect's launches with that
+// image as level 0 (ORB's own rows go to o.desc and are not read), and orb_records_kernel leaves the list in o.rec / o.rec_keep / o.rec_cnt
+int orb_staged_enqueue(spvo_ctx *c, const OrbPlan &plan, const uint8_t *h_img, int rows, int cols, int nfeatures) {
+  auto &o = c->orb;
+  if (int rc = classic_image_from_staged(c, h_img, rows, cols)) return rc;
+  if (int rc = orb_enqueue(c, plan, rows, cols, c->cls.im, o.kps, o.desc, nfeatures)) return rc;
+  OrbLevelScale ls;
+  for (int l = 0; l < ORB_LEVELS; ++l) ls.s[l] = l == 0 ? 1.f : ls.s[l - 1] * 1.2f;   // (the host's to_keypoint: repeated * 1.2f)
+  hipLaunchKernelGGL(orb_records_kernel, dim3(8), dim3(256), 0, c->stream2, o.kps, o.counters, nfeatures, ls, o.rec, o.rec_keep, o.rec_cnt);
+  HIP_TRY(c, hipGetLastError());
+  return SPVO_OK;
+}
+}  // namespace
+
+// ORB keypoints with BRISK descriptors, pair-resident in the binary slots (64-byte rows): per image what spvo_orb_detect(img, nfeatures)
+// followed by spvo_brisk_describe on its x, y and 31 * 1.2^octave hands out, byte for byte.  spvo_brisk_detect_pair's protocol; the chain of
+// an image is staged image -> resident image -> orb_enqueue -> orb_records_kernel -> brisk_pair_chain_enqueue.
+int spvo_orb_brisk_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int nfeatures, int slot_l, int slot_r, int slot_capacity,
+                        spvo_brisk_features *out_l, spvo_brisk_features *out_r) {
+  if (!c || !img_l || !img_r || !out_l || !out_r || rows <= 0 || cols <= 0 || stride < (size_t)cols) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  const char *who = "spvo_orb_brisk_pair";
+  const int cap = slot_capacity, row_bytes = 64;
+  PairCall<BinPairFamily> pc(c, who, BinPairFamily{row_bytes}, pair_out(out_l), pair_out(out_r));
+  int rc;
+  if ((rc = pc.check(slot_l, slot_r)) || (rc = pc.check_capacity(cap))) return rc;
+  if (cap > 32768) return fail(c, SPVO_ERR_INVALID, "%s: slot_capacity must be 1 .. 32768", who);
+  if (nfeatures <= 0) return fail(c, SPVO_ERR_INVALID, "%s: nfeatures must be positive", who);
+  if ((rc = brisk_check_image(c, who, rows, cols)) || (rc = pc.open())) return rc;
+  auto &bb = c->bin;
+  auto &o = c->orb;
+  OrbPlan plan;
+  // every allocation and the BRISK point table before the first launch of the chain
+  if ((rc = bin_ensure(c, cap, (size_t)rows * cols)) || (rc = cls_ensure(c, rows, cols)) || (rc = brisk_chain_ensure(c, rows, cols, cap)) ||
+      (rc = orb_prepare(c, rows, cols, nfeatures, plan)) || (rc = orb_records_ensure(c, nfeatures)))
+    return rc;
+  if ((rc = pc.load(img_l, img_r, rows, cols, stride))) return rc;
+  for (int k = 0; k < 2; ++k) {
+    const BinarySlot &s = bb.slots[pc.slots[k]];
+    if ((rc = orb_staged_enqueue(c, plan, pc.image(k), rows, cols, nfeatures))) return rc;
+    const ChainOut out{bb.d_cnt + k * BIN_COUNTER_INTS, bb.d_kresp, s.d_kp, s.d_desc, s.d_n, bb.h_n + 4 * k, nullptr, bb.h_desc + (size_t)k * cap * row_bytes};
+    if ((rc = brisk_pair_chain_enqueue(c, rows, cols, cap, o.rec, o.rec_keep, o.rec_cnt, nfeatures, o.crec, out, bb.h_bkp + (size_t)k * cap))) return rc;
+  }
+  if ((rc = pc.submit())) return rc;
+  pc.count(0); pc.count(1);
+  // (spvo_orb_detect's answer: a level found more corners than its buffer holds -- an input's doing, not a defect)
+  if (bb.h_n[1] || bb.h_n[5]) return fail(c, SPVO_ERR_CAPACITY, "%s: corner buffer overflow in the %s image", who, bb.h_n[1] ? "left" : "right");
+  static_assert(sizeof(spvo_brisk_keypoint) == sizeof(BriskDetKeypoint), "record layout");
+  const PairMirror mirrors[2] = {{bb.h_bkp, sizeof(BriskDetKeypoint), bb.h_desc, (size_t)row_bytes},
+                                 {bb.h_bkp + cap, sizeof(BriskDetKeypoint), bb.h_desc + (size_t)cap * row_bytes, (size_t)row_bytes}};
+  return pc.commit(mirrors);
+}
+
+// ORB keypoints with SIFT descriptors, pair-resident in the SIFT slots: per image what spvo_orb_detect(img, nfeatures) followed by
+// spvo_sift_describe on its records {x, y, 31 * 1.2^octave, degrees, response, octave} hands out, byte for byte.  The call is
+// sift_link_pair's (spvo_sift.hip); the pyramid is built for octaves 0 .. the highest level of the shape that can hold a keypoint.
+int spvo_orb_sift_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int nfeatures, int slot_l, int slot_r, int slot_capacity,
+                       spvo_sift_features *out_l, spvo_sift_features *out_r) {
+  if (!c || !img_l || !img_r || !out_l || !out_r || rows <= 0 || cols <= 0 || stride < (size_t)cols) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  static_assert(sizeof(spvo_sift_keypoint) == sizeof(BriskDetKeypoint), "record layout");
+  const char *who = "spvo_orb_sift_pair";
+  auto &o = c->orb;
+  OrbPlan plan;
+  SiftLinkDetector det;
+  det.who = who;
+  det.max_octave = orb_top_level(rows, cols);
+  det.overflow_is_capacity = true;
+  det.check = [&]() -> int { return nfeatures <= 0 ? fail(c, SPVO_ERR_INVALID, "%s: nfeatures must be positive", who) : SPVO_OK; };
+  det.prepare = [&](SiftLinkSrc &src) -> int {
+    if (int rc = orb_prepare(c, rows, cols, nfeatures, plan)) return rc;
+    if (int rc = orb_records_ensure(c, nfeatures)) return rc;
+    src = SiftLinkSrc{reinterpret_cast<const char *>(o.rec.get()), (int)sizeof(BriskDetKeypoint), (int)offsetof(BriskDetKeypoint, x), (int)offsetof(BriskDetKeypoint, y),
+                      (int)offsetof(BriskDetKeypoint, size), (int)offsetof(BriskDetKeypoint, angle), (int)offsetof(BriskDetKeypoint, response), (int)offsetof(BriskDetKeypoint, octave),
+                      nullptr, o.rec_cnt + 1, nfeatures, o.rec_cnt, nullptr, 0};   // (every record is kept: no flags, no compaction)
+    return SPVO_OK;
+  };
+  det.enqueue = [&](const uint8_t *h_img) -> int { return orb_staged_enqueue(c, plan, h_img, rows, cols, nfeatures); };
+  return sift_link_pair(c, det, img_l, img_r, rows, cols, stride, slot_l, slot_r, slot_capacity, pair_out(out_l), pair_out(out_r));
 }
 
 }  // extern "C"

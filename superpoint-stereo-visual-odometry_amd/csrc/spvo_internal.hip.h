@@ -398,6 +398,11 @@ struct spvo_ctx {
     DevBuf<OrbKeypoint> kps;
     DevBuf<uint8_t> desc;
     int tab_rows = 0, tab_cols = 0;   // image size the resize tables in `tab` belong to
+    // spvo_orb_brisk_pair / spvo_orb_sift_pair (orb_records_kernel, orb_link.hip.h): the detector's list as the BRISK extractor's chain and the
+    // SIFT link read one -- 24-byte records, keep flags, a BRISK detector's counter block, the chain's compacted records -- `rec_cap` of each
+    int rec_cap = 0;
+    DevBuf<BriskDetKeypoint> rec, crec;
+    DevBuf<int> rec_keep, rec_cnt;
   } orb;
   // Shi-Tomasi / FAST detectors and the ORB extractor for given keypoints (classic_detect.hip.h): one image resident at a time,
   // buffers grow with the image (per-pixel ones with rows x cols, the state map with its padded shape) and the keypoint list
@@ -896,7 +901,7 @@ int brisk_pair_chain_enqueue(spvo_ctx *c, int rows, int cols, int cap, const Bri
 // ---- spvo_sift.hip
 void sift_release(spvo_ctx *c);      // what spvo_ctx::sift holds besides memory: its events (spvo_destroy)
 // The SIFT extractor as a link behind a detector that left records with an octave on the device (sift.hip.h: SiftLinkIO;
-// spvo_brisk_sift_pair, spvo_akaze_sift_pair).  sift_link_pair is the whole call around the detector -- a PairCall on the SIFT slots
+// spvo_brisk_sift_pair, spvo_akaze_sift_pair, spvo_orb_sift_pair).  sift_link_pair is the whole call around the detector -- a PairCall on the SIFT slots
 // (pair_call.hip.h) with the link's allocations and chains -- so that neither detector object needs the SIFT unit's internals; the detector
 // is three functions.  Every refusal comes before anything is touched, every allocation (`prepare` included) before the first launch.
 struct SiftLinkDetector {
@@ -905,6 +910,7 @@ struct SiftLinkDetector {
   std::function<int()> check;                        // what the detector's sibling refuses of its parameters and the shape
   std::function<int(SiftLinkSrc &)> prepare;         // behind classic_image_ensure: the detector's buffers for the shape; where its list will lie
   std::function<int(const uint8_t *)> enqueue;       // the staged image (pinned, rows packed) becomes the resident one and goes through the detector's chain
+  bool overflow_is_capacity = false;                 // a set overflow flag is an input's doing (ORB's corner buffers): SPVO_ERR_CAPACITY, not the defect the others report
 };
 // (SPVO_OK and SPVO_ERR_CAPACITY are answered behind the call's one wait: the chains of both images have run, and an AKAZE sink has left
 // image k's contrast factors in spvo_ctx::sift.h_n + 8 + 4 k)

@@ -397,6 +397,7 @@ int spvo_int::sift_link_pair(spvo_ctx *c, const SiftLinkDetector &det, const uin
   pc.count(0); pc.count(1);
   // (kept: the BRISK and AKAZE callers answer a detector overflow with SPVO_ERR_STATE -- the detectors size their lists from the image, so
   // the flag cannot be set; were it, the counts would be wrong)
+  if ((s.h_n[1] || s.h_n[5]) && det.overflow_is_capacity) return fail(c, SPVO_ERR_CAPACITY, "%s: corner buffer overflow in the %s image", who, s.h_n[1] ? "left" : "right");
   if (s.h_n[1] || s.h_n[5]) return fail(c, SPVO_ERR_STATE, "%s: the candidate list overflowed although it is sized from the image", who);
   const PairMirror mirrors[2] = {sift_mirror(c, 0, true, (size_t)src.stride), sift_mirror(c, 1, true, (size_t)src.stride)};   // (the detector's own records)
   return pc.commit(mirrors);

@@ -127,7 +127,7 @@ struct OrbLinkSrc { const char *rec; int stride, off_x, off_y, off_octave; const
 // ---- the link from a detector's record list to the SIFT extractor (sift.hip.h: spvo_brisk_sift_pair, spvo_akaze_sift_pair,
 // spvo_sift_link_debug): the same description of where the list lies, with every field the extractor reads (x, y, size, angle, response:
 // float; octave: int32) at its byte offset -- `stride` is a multiple of 4, the whole record travels to the host's mirror -- and where the
-// detector's overflow flag is: det_counters[3] (BRISK), or stat (AKAZE_STAT_*) against cand_cap (AKAZE), or neither
+// detector's overflow flag is: det_counters[3] (BRISK; ORB through orb_records_kernel's block), or stat (AKAZE_STAT_*) against cand_cap (AKAZE), or neither
 struct SiftLinkSrc {
   const char *rec;
   int stride, off_x, off_y, off_size, off_angle, off_response, off_octave;

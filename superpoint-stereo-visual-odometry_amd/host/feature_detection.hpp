@@ -321,6 +321,7 @@ protected:
 ///////////////////////////////////////////////////////////////////////////////////////
 
 struct ClassicPair;   // a row of the table of pairs that run without OpenCV (feature_detection_classic.cpp)
+struct ClassicOptIns;   // the run-at-all switches a front end read at construction (feature_detection_classic.cpp)
 
 // The CPU baseline of BASELINE config 1 (ORB / BRISK / AKAZE / SIFT / FAST / GFTT through cv::Feature2D).  Detection,
 // description and Hamming / L2 matching are OpenCV calls on the host, so the class does its work only in a build with
@@ -363,7 +364,11 @@ public:
   // levels of the SIFT pyramid its records can name and the descriptor on the device, rows into the SIFT slots) only with this as well as
   // setDeviceResident -- a switch of its own, so that no combination of the earlier switches changes route; a shape the pair call refuses
   // (it lacks the detector's highest octave: BRISK 5, AKAZE that of the shape's last level) takes the per-image path and is not counted.
-  // ORB + SIFT has no route: the ORB detector keeps a pyramid and an image of its own, and its records name octaves up to 7.
+  // setOrbBriskExtractor: ORB + BRISK runs (per image: spvo_orb_detect, then spvo_brisk_describe at every keypoint's size 31 x 1.2^octave);
+  // off, the pair is refused as before and the refusal does not list it.  setOrbPairsResident: ORB + BRISK (which still needs
+  // setOrbBriskExtractor to run at all) and ORB + SIFT take their routes (spvo_orb_brisk_pair, spvo_orb_sift_pair: the ORB detector on the
+  // shared resident image, its list turned into the extractor's records on the device) only with this as well as setDeviceResident -- a
+  // switch of its own again; no shape the per-image path accepts is refused.
   static void setDeviceResident(bool on);
   static void setResidentCapacity(int rows);   // rows per binary slot [8192]
   static void setBriskPairResident(bool on);   // [off]
@@ -373,7 +378,9 @@ public:
   static void setOrbExtractorOctaves(bool on);    // [off]
   static void setOctavePairsResident(bool on);    // [off]
   static void setSiftOctavePairsResident(bool on);   // [off]
-  // pairs that actually stayed resident (spvo_classic_detect / spvo_sift_detect_pair / spvo_brisk_detect_pair / spvo_akaze_detect_pair / spvo_classic_sift_pair / spvo_brisk_orb_pair / spvo_akaze_orb_pair / spvo_akaze_brisk_pair / spvo_brisk_sift_pair / spvo_akaze_sift_pair returned SPVO_OK): what tells the resident path from its fallback
+  static void setOrbBriskExtractor(bool on);      // [off]
+  static void setOrbPairsResident(bool on);       // [off]
+  // pairs that actually stayed resident (spvo_classic_detect / spvo_sift_detect_pair / spvo_brisk_detect_pair / spvo_akaze_detect_pair / spvo_classic_sift_pair / spvo_brisk_orb_pair / spvo_akaze_orb_pair / spvo_akaze_brisk_pair / spvo_brisk_sift_pair / spvo_akaze_sift_pair / spvo_orb_brisk_pair / spvo_orb_sift_pair returned SPVO_OK): what tells the resident path from its fallback
   unsigned residentPairs() const { return resident_ok_pairs_; }
 
 private:
@@ -385,6 +392,8 @@ private:
   bool orb_octaves_ = false;           // setOrbExtractorOctaves at construction
   bool octave_pairs_resident_ = false;   // setOctavePairsResident at construction
   bool sift_octave_pairs_resident_ = false;   // setSiftOctavePairsResident at construction
+  bool orb_brisk_ = false;             // setOrbBriskExtractor at construction
+  bool orb_pairs_resident_ = false;    // setOrbPairsResident at construction
   bool pairRuns() const;               // this detector / descriptor pair runs in this build
   int resident_capacity_ = 8192;
   unsigned resident_pairs_ = 0;   // pairs handed to a resident route: pair k lives in slots 2 (k % 4), 2 (k % 4) + 1
@@ -395,6 +404,7 @@ private:
   cv::Ptr<cv::DescriptorExtractor> extractor_;
 #else
   const ClassicPair *pair() const;   // the table's row of this detector / descriptor pair, nullptr for one that does not run
+  ClassicOptIns optIns() const;      // setAkazeDescriptor, setOrbExtractorOctaves, setOrbBriskExtractor as read at construction
   // what a resident route hands out for one image -- resident_capacity_ keypoint records and descriptor rows of the pair's sizes: allocated once
   struct Staging { std::vector<uint8_t> records, rows; };
   Staging staging_[2];

@@ -18,6 +18,8 @@ static bool g_classic_sift_describe_resident = false;
 static bool g_classic_orb_octaves = false;
 static bool g_classic_octave_pairs_resident = false;
 static bool g_classic_sift_octave_pairs_resident = false;
+static bool g_classic_orb_brisk = false;
+static bool g_classic_orb_pairs_resident = false;
 void ClassicFeatureFrontEnd::setDeviceResident(bool on) { g_classic_resident = on; }
 void ClassicFeatureFrontEnd::setBriskPairResident(bool on) { g_classic_brisk_pair_resident = on; }
 void ClassicFeatureFrontEnd::setAkazeDescriptor(bool on) { g_classic_akaze_descriptor = on; }
@@ -26,6 +28,8 @@ void ClassicFeatureFrontEnd::setSiftDescribeResident(bool on) { g_classic_sift_d
 void ClassicFeatureFrontEnd::setOrbExtractorOctaves(bool on) { g_classic_orb_octaves = on; }
 void ClassicFeatureFrontEnd::setOctavePairsResident(bool on) { g_classic_octave_pairs_resident = on; }
 void ClassicFeatureFrontEnd::setSiftOctavePairsResident(bool on) { g_classic_sift_octave_pairs_resident = on; }
+void ClassicFeatureFrontEnd::setOrbBriskExtractor(bool on) { g_classic_orb_brisk = on; }
+void ClassicFeatureFrontEnd::setOrbPairsResident(bool on) { g_classic_orb_pairs_resident = on; }
 void ClassicFeatureFrontEnd::setResidentCapacity(int rows) { g_classic_resident_capacity = rows; }
 
 #ifdef SPVO_USE_OPENCV
@@ -91,14 +95,15 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
 // Without OpenCV the pairs of kClassicPairs run, on the GPU, and every other combination is refused.  What the table cannot say: ORB + ORB and
 // SIFT + SIFT describe in the detector's pass, so detectKeypoints keeps the rows for the describeKeypoints call that follows on the same image;
 // every other detector leaves the image (AKAZE: its scale space) on the device for the extractor -- except ORB, which keeps a pyramid of its
-// own: ORB + SIFT uploads the image a second time.  The AKAZE extractor needs the level in
+// own: the per-image path of ORB + SIFT and ORB + BRISK uploads the image a second time (their resident routes, spvo_orb_sift_pair and
+// spvo_orb_brisk_pair, run the detector on the shared resident image).  The AKAZE extractor needs the level in
 // class_id, which only AKAZE keypoints carry -- OpenCV's own assertion refuses the others too.
 bool ClassicFeatureFrontEnd::available() { return true; }
 
 enum class Detect { Orb, Gftt, Fast, Sift, Brisk, Akaze };       // detectKeypoints: spvo_<this>_detect
 enum class Describe { WithDetector, Orb, Brisk, Akaze, Sift };   // describeKeypoints: the rows detectKeypoints kept, or spvo_<this>_describe on the given keypoints
-enum class Route { None, Classic, SiftPair, BriskPair, AkazePair, ClassicSift, BriskOrbPair, AkazeOrbPair, AkazeBriskPair, BriskSiftPair, AkazeSiftPair };   // setDeviceResident: the per-image path, spvo_classic_detect (kind), spvo_sift_detect_pair, spvo_brisk_detect_pair, spvo_akaze_detect_pair, spvo_classic_sift_pair (kind), spvo_brisk_orb_pair, spvo_akaze_orb_pair, spvo_akaze_brisk_pair, spvo_brisk_sift_pair, spvo_akaze_sift_pair
-enum class OptIn { None, AkazeDescriptor, OrbOctaves, BriskPairResident, AkazePairResident, SiftDescribeResident, OctavePairsResident, SiftOctavePairsResident };   // to run at all: setAkazeDescriptor, setOrbExtractorOctaves; to stay resident: setBriskPairResident, setAkazePairResident, setSiftDescribeResident, setOctavePairsResident, setSiftOctavePairsResident
+enum class Route { None, Classic, SiftPair, BriskPair, AkazePair, ClassicSift, BriskOrbPair, AkazeOrbPair, AkazeBriskPair, BriskSiftPair, AkazeSiftPair, OrbBriskPair, OrbSiftPair };   // setDeviceResident: the per-image path, spvo_classic_detect (kind), spvo_sift_detect_pair, spvo_brisk_detect_pair, spvo_akaze_detect_pair, spvo_classic_sift_pair (kind), spvo_brisk_orb_pair, spvo_akaze_orb_pair, spvo_akaze_brisk_pair, spvo_brisk_sift_pair, spvo_akaze_sift_pair, spvo_orb_brisk_pair, spvo_orb_sift_pair
+enum class OptIn { None, AkazeDescriptor, OrbOctaves, BriskPairResident, AkazePairResident, SiftDescribeResident, OctavePairsResident, SiftOctavePairsResident, OrbBrisk, OrbPairsResident };   // to run at all: setAkazeDescriptor, setOrbExtractorOctaves, setOrbBriskExtractor; to stay resident: setBriskPairResident, setAkazePairResident, setSiftDescribeResident, setOctavePairsResident, setSiftOctavePairsResident, setOrbPairsResident
 
 struct ClassicPair {
   DetectorType detector;
@@ -125,22 +130,30 @@ static const ClassicPair kClassicPairs[] = {
     {DetectorType::SIFT, DescriptorType::SIFT, Detect::Sift, 0.f, Describe::WithDetector, 128, CV_32FC1, Route::SiftPair, 0, OptIn::None, OptIn::None},
     {DetectorType::ShiTomasi, DescriptorType::SIFT, Detect::Gftt, 5.f, Describe::Sift, 128, CV_32FC1, Route::ClassicSift, SPVO_CLASSIC_GFTT_SIFT, OptIn::None, OptIn::SiftDescribeResident},
     {DetectorType::FAST, DescriptorType::SIFT, Detect::Fast, 7.f, Describe::Sift, 128, CV_32FC1, Route::ClassicSift, SPVO_CLASSIC_FAST_SIFT, OptIn::None, OptIn::SiftDescribeResident},
-    // (ORB + SIFT has no route: the ORB detector keeps a pyramid and an image of its own, not the shared resident image, and its records name octaves up to 7)
-    {DetectorType::ORB, DescriptorType::SIFT, Detect::Orb, 0.f, Describe::Sift, 128, CV_32FC1, Route::None, 0, OptIn::None, OptIn::None},
+    // (spvo_orb_sift_pair runs the ORB detector on the shared resident image; the per-image path keeps spvo_orb_detect's own pyramid and image)
+    {DetectorType::ORB, DescriptorType::SIFT, Detect::Orb, 0.f, Describe::Sift, 128, CV_32FC1, Route::OrbSiftPair, 0, OptIn::None, OptIn::OrbPairsResident},
     {DetectorType::BRISK, DescriptorType::SIFT, Detect::Brisk, 0.f, Describe::Sift, 128, CV_32FC1, Route::BriskSiftPair, 0, OptIn::None, OptIn::SiftOctavePairsResident},
     {DetectorType::AKAZE, DescriptorType::SIFT, Detect::Akaze, 0.f, Describe::Sift, 128, CV_32FC1, Route::AkazeSiftPair, 0, OptIn::None, OptIn::SiftOctavePairsResident},
     // the ORB extractor on keypoints that carry an octave (spvo_orb_describe_octaves): only with setOrbExtractorOctaves, and listed only then
     {DetectorType::BRISK, DescriptorType::ORB, Detect::Brisk, 0.f, Describe::Orb, 32, CV_8UC1, Route::BriskOrbPair, 0, OptIn::OrbOctaves, OptIn::OctavePairsResident},
     {DetectorType::AKAZE, DescriptorType::ORB, Detect::Akaze, 0.f, Describe::Orb, 32, CV_8UC1, Route::AkazeOrbPair, 0, OptIn::OrbOctaves, OptIn::OctavePairsResident},
+    // the BRISK extractor on ORB keypoints (size 31 x 1.2^octave): only with setOrbBriskExtractor, and listed only then
+    {DetectorType::ORB, DescriptorType::BRISK, Detect::Orb, 0.f, Describe::Brisk, 64, CV_8UC1, Route::OrbBriskPair, 0, OptIn::OrbBrisk, OptIn::OrbPairsResident},
 };
+// the run-at-all switches of a front end, as its constructor read them
+struct ClassicOptIns { bool akaze_descriptor, orb_octaves, orb_brisk; };
+static bool opted_in(const ClassicPair &p, const ClassicOptIns &o) {
+  return (p.opt_in != OptIn::AkazeDescriptor || o.akaze_descriptor) && (p.opt_in != OptIn::OrbOctaves || o.orb_octaves) && (p.opt_in != OptIn::OrbBrisk || o.orb_brisk);
+}
 
 // the row of a pair that runs, or nullptr
-static const ClassicPair *find_pair(DetectorType d, DescriptorType e, bool akaze_descriptor, bool orb_octaves) {
+static const ClassicPair *find_pair(DetectorType d, DescriptorType e, const ClassicOptIns &o) {
   for (const ClassicPair &p : kClassicPairs)
-    if (p.detector == d && p.descriptor == e && (p.opt_in != OptIn::AkazeDescriptor || akaze_descriptor) && (p.opt_in != OptIn::OrbOctaves || orb_octaves)) return &p;
+    if (p.detector == d && p.descriptor == e && opted_in(p, o)) return &p;
   return nullptr;
 }
-const ClassicPair *ClassicFeatureFrontEnd::pair() const { return find_pair(detector_type_, descriptor_type_, akaze_descriptor_, orb_octaves_); }
+ClassicOptIns ClassicFeatureFrontEnd::optIns() const { return ClassicOptIns{akaze_descriptor_, orb_octaves_, orb_brisk_}; }
+const ClassicPair *ClassicFeatureFrontEnd::pair() const { return find_pair(detector_type_, descriptor_type_, optIns()); }
 bool ClassicFeatureFrontEnd::pairRuns() const { return pair() != nullptr; }
 
 template <class Names, class T> static std::string name_of(const Names &names, T type) {
@@ -148,11 +161,11 @@ template <class Names, class T> static std::string name_of(const Names &names, T
     if (kv.second == type) return kv.first;
   return "?";
 }
-// what a pair that does not run is told: the table's rows (those behind setOrbExtractorOctaves only while that switch is on)
-static std::string refusal(bool orb_octaves) {
+// what a pair that does not run is told: the table's rows (those behind setOrbExtractorOctaves / setOrbBriskExtractor only while that switch is on)
+static std::string refusal(const ClassicOptIns &o) {
   std::string s = "this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only these pairs run: ";
   for (const ClassicPair &p : kClassicPairs) {
-    if (p.opt_in == OptIn::OrbOctaves && !orb_octaves) continue;
+    if ((p.opt_in == OptIn::OrbOctaves && !o.orb_octaves) || (p.opt_in == OptIn::OrbBrisk && !o.orb_brisk)) continue;
     s += std::string(&p == kClassicPairs ? "" : ", ") + name_of(detector_name_to_type, p.detector) + " + " + name_of(descriptor_name_to_type, p.descriptor) +
          (p.opt_in == OptIn::AkazeDescriptor ? " (with setAkazeDescriptor)" : "");
   }
@@ -161,10 +174,10 @@ static std::string refusal(bool orb_octaves) {
 // Of a pair that does not run, the detector is at fault unless it runs with the ORB extractor, and the descriptor unless it runs on ORB
 // keypoints (ORB + ORB is the reference's baseline, launch/visual_odometry_classic.launch)
 void ClassicFeatureFrontEnd::initDetector() {
-  if (!pair() && !find_pair(detector_type_, DescriptorType::ORB, akaze_descriptor_, orb_octaves_)) logError("[initDetector] " + refusal(orb_octaves_));
+  if (!pair() && !find_pair(detector_type_, DescriptorType::ORB, optIns())) logError("[initDetector] " + refusal(optIns()));
 }
 void ClassicFeatureFrontEnd::initDescriptor() {
-  if (!pair() && !find_pair(DetectorType::ORB, descriptor_type_, akaze_descriptor_, orb_octaves_)) logError("[initDescriptor] " + refusal(orb_octaves_));
+  if (!pair() && !find_pair(DetectorType::ORB, descriptor_type_, optIns())) logError("[initDescriptor] " + refusal(optIns()));
 }
 
 // ---- records -> cv::KeyPoint: one conversion per record type, for the per-image path and the resident one alike
@@ -181,7 +194,8 @@ static cv::KeyPoint to_keypoint(const spvo_orb_keypoint &r, const ClassicPair &p
     return s;
   }();
   cv::KeyPoint k(cv::Point2f(r.x, r.y), p.detect == Detect::Orb ? 31.f * level_scale[r.octave & 7] : p.keypoint_size);
-  k.angle = p.describe == Describe::Brisk ? r.angle : orb_degrees(r.angle);   // (the BRISK kinds of spvo_classic_detect report the extractor's degrees, taken as they are)
+  // (the BRISK kinds of spvo_classic_detect report the extractor's degrees, taken as they are; ORB + BRISK's record is spvo_orb_detect's: radians)
+  k.angle = p.describe == Describe::Brisk && p.detect != Detect::Orb ? r.angle : orb_degrees(r.angle);
   k.response = r.response;
   k.octave = r.octave;
   return k;
@@ -241,7 +255,7 @@ std::vector<cv::KeyPoint> ClassicFeatureFrontEnd::detectKeypoints(const cv::Mat 
   detected_data_ = nullptr;
   const ClassicPair *p = pair();
   if (!p) {
-    logError("ClassicFeatureFrontEnd: " + refusal(orb_octaves_));
+    logError("ClassicFeatureFrontEnd: " + refusal(optIns()));
     return keypoints;
   }
   if (!ensureContext()) return keypoints;
@@ -262,7 +276,7 @@ std::vector<cv::KeyPoint> ClassicFeatureFrontEnd::detectKeypoints(const cv::Mat 
     rc = spvo_orb_detect(ctx_, px, img.rows, img.cols, step, NFEATURES, kp.data(), desc.ptr<uint8_t>(0), NFEATURES, &n);
     if (rc == SPVO_OK) {
       keypoints = to_keypoints(kp.data(), n, *p);
-      if (p->describe == Describe::WithDetector) orb_desc_ = copy_rows(desc.data, n, *p);   // (ORB + SIFT: the rows are not kept)
+      if (p->describe == Describe::WithDetector) orb_desc_ = copy_rows(desc.data, n, *p);   // (ORB + SIFT, ORB + BRISK: the rows are not kept)
     }
     break;
   }
@@ -377,7 +391,7 @@ cv::Mat ClassicFeatureFrontEnd::describeKeypoints(std::vector<cv::KeyPoint> &key
   } else {
     // cv::ORB::create()->compute (classic.cpp:66-68) / cv::BRISK::create(30, 3, 1.0f)->compute (classic.cpp:56-65): keypoints too close to a
     // border are ERASED from the caller's vector (it is passed by non-const reference, classic.cpp:110-111), so keypoints_dq and descriptors_dq
-    // stay aligned.  BRISK: every keypoint's own size (5: ShiTomasi, 7: FAST, 12 x its scale: BRISK, 3 x esigma: AKAZE) picks its scale, and the
+    // stay aligned.  BRISK: every keypoint's own size (5: ShiTomasi, 7: FAST, 12 x its scale: BRISK, 3 x esigma: AKAZE, 31 x 1.2^octave: ORB) picks its scale, and the
     // angle comes in degrees, 0 .. 360 -- except that a BRISK keypoint keeps the angle its detector reports (-1)
     // ORB on BRISK / AKAZE keypoints (the rows behind setOrbExtractorOctaves): KeyPoint::octave names the pyramid level, the survivors come
     // grouped by level as OpenCV leaves them
@@ -418,7 +432,7 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
     return;
   }
   if (!pairRuns()) {
-    logError("ClassicFeatureFrontEnd: " + refusal(orb_octaves_));
+    logError("ClassicFeatureFrontEnd: " + refusal(optIns()));
     return;
   }
   if (!ensureContext()) return;   // no device: logged, nothing pushed (nn.cpp:53-55 convention)
@@ -497,7 +511,7 @@ bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &img_l, cv::Mat 
   const ClassicPair &p = *pair();   // (addStereoImagePair has asked pairRuns)
   if (p.route == Route::None || (p.resident_opt_in == OptIn::BriskPairResident && !brisk_pair_resident_) || (p.resident_opt_in == OptIn::AkazePairResident && !akaze_pair_resident_) ||
       (p.resident_opt_in == OptIn::SiftDescribeResident && !sift_describe_resident_) || (p.resident_opt_in == OptIn::OctavePairsResident && !octave_pairs_resident_) ||
-      (p.resident_opt_in == OptIn::SiftOctavePairsResident && !sift_octave_pairs_resident_))
+      (p.resident_opt_in == OptIn::SiftOctavePairsResident && !sift_octave_pairs_resident_) || (p.resident_opt_in == OptIn::OrbPairsResident && !orb_pairs_resident_))
     return false;
   const uint8_t *l = img_l.ptr<uint8_t>(0), *r = img_r.ptr<uint8_t>(0);
   const int rows = img_l.rows, cols = img_l.cols;
@@ -570,6 +584,16 @@ bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &img_l, cv::Mat 
       return spvo_akaze_sift_pair(ctx_, l, r, rows, cols, step, 0.001f, slot_l, slot_r, resident_capacity_, &f[0], &f[1]);
     });
   }
+  // cv::ORB::create(2000, ..), as detectKeypoints.  No shape is refused that the per-image path accepts: the pyramid is built up to the
+  // highest level that can hold a keypoint, and SIFT's octave of that number exists for every such shape
+  case Route::OrbBriskPair:
+    return residentPair<spvo_brisk_features>(p, img_l, img_r, "spvo_orb_brisk_pair", [&](int slot_l, int slot_r, spvo_brisk_features *f) {
+      return spvo_orb_brisk_pair(ctx_, l, r, rows, cols, step, 2000, slot_l, slot_r, resident_capacity_, &f[0], &f[1]);
+    });
+  case Route::OrbSiftPair:
+    return residentPair<spvo_sift_features>(p, img_l, img_r, "spvo_orb_sift_pair", [&](int slot_l, int slot_r, spvo_sift_features *f) {
+      return spvo_orb_sift_pair(ctx_, l, r, rows, cols, step, 2000, slot_l, slot_r, resident_capacity_, &f[0], &f[1]);
+    });
   case Route::None:
     break;
   }
@@ -591,6 +615,7 @@ ClassicFeatureFrontEnd::ClassicFeatureFrontEnd(const DetectorType detector_type,
                       verbose, input_height, input_width) {
   akaze_descriptor_ = g_classic_akaze_descriptor;   // (initDetector and initDescriptor ask whether the pair runs)
   orb_octaves_ = g_classic_orb_octaves;
+  orb_brisk_ = g_classic_orb_brisk;
   initDetector();
   initDescriptor();
   initMatcher();
@@ -604,6 +629,7 @@ ClassicFeatureFrontEnd::ClassicFeatureFrontEnd(const DetectorType detector_type,
   sift_describe_resident_ = g_classic_sift_describe_resident;
   octave_pairs_resident_ = g_classic_octave_pairs_resident;
   sift_octave_pairs_resident_ = g_classic_sift_octave_pairs_resident;
+  orb_pairs_resident_ = g_classic_orb_pairs_resident;
 }
 
 ClassicFeatureFrontEnd::~ClassicFeatureFrontEnd() {

@@ -538,6 +538,14 @@ void spvo_host_classic_set_octave_pairs_resident(int on) { ClassicFeatureFrontEn
 // spvo_brisk_sift_pair / spvo_akaze_sift_pair per pair when setDeviceResident is on as well (off by default)
 void spvo_host_classic_set_sift_octave_pairs_resident(int on) { ClassicFeatureFrontEnd::setSiftOctavePairsResident(on != 0); }
 
+// ClassicFeatureFrontEnd::setOrbBriskExtractor for the front ends constructed afterwards: ORB + BRISK runs (spvo_brisk_describe on the ORB
+// detector's keypoints at their sizes 31 x 1.2^octave, the per-image path); off, the pair is refused
+void spvo_host_classic_set_orb_brisk(int on) { ClassicFeatureFrontEnd::setOrbBriskExtractor(on != 0); }
+
+// ClassicFeatureFrontEnd::setOrbPairsResident for the front ends constructed afterwards: ORB + BRISK and ORB + SIFT through one
+// spvo_orb_brisk_pair / spvo_orb_sift_pair per pair when setDeviceResident is on as well (off by default)
+void spvo_host_classic_set_orb_pairs_resident(int on) { ClassicFeatureFrontEnd::setOrbPairsResident(on != 0); }
+
 // the ORB + ORB front end at the native resolution (the export's first form)
 int spvo_host_classic_sequence(int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l, const double *P_r, int knn,
                                int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats, double *seconds) {

@@ -98,7 +98,7 @@ SYMBOLS = [
     "spvo_default_config", "spvo_create", "spvo_destroy", "spvo_last_error", "spvo_load_weights", "spvo_engine_precision", "spvo_set_fp32_split",
     "spvo_preprocess", "spvo_forward", "spvo_debug_tensor", "spvo_heatmap", "spvo_nms",
     "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8", "spvo_match_last_form",
-    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_orb_describe_octaves", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_akaze_describe", "spvo_akaze_detect_pair", "spvo_akaze_suppress_debug", "spvo_brisk_orb_pair", "spvo_akaze_orb_pair", "spvo_akaze_brisk_pair", "spvo_orb_octaves_link_debug", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_describe", "spvo_sift_detect_pair", "spvo_classic_sift_pair", "spvo_brisk_sift_pair", "spvo_akaze_sift_pair", "spvo_sift_link_debug", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_match_l2_u8", "spvo_match_l2_u8_slots", "spvo_set_binary_prematch_norm", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
+    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_orb_describe_octaves", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_akaze_describe", "spvo_akaze_detect_pair", "spvo_akaze_suppress_debug", "spvo_brisk_orb_pair", "spvo_akaze_orb_pair", "spvo_akaze_brisk_pair", "spvo_orb_octaves_link_debug", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_describe", "spvo_sift_detect_pair", "spvo_classic_sift_pair", "spvo_brisk_sift_pair", "spvo_akaze_sift_pair", "spvo_orb_brisk_pair", "spvo_orb_sift_pair", "spvo_sift_link_debug", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_match_l2_u8", "spvo_match_l2_u8_slots", "spvo_set_binary_prematch_norm", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
     "spvo_profile_enable", "spvo_profile_reset", "spvo_profile_only", "spvo_profile_count", "spvo_profile_get", "spvo_profile_stage_kernel", "spvo_profile_stage_variant", "spvo_profile_stage_fused",
     "spvo_set_tuning", "spvo_get_tuning", "spvo_clear_tuning",
     "spvo_comm_unique_id", "spvo_comm_available", "spvo_comm_create", "spvo_comm_create_host", "spvo_comm_rank", "spvo_comm_world", "spvo_comm_destroy",
@@ -178,6 +178,8 @@ def load() -> C.CDLL:
     lib.spvo_sift_detect_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(SiftFeatures), C.POINTER(SiftFeatures)]
     lib.spvo_brisk_sift_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(SiftFeatures), C.POINTER(SiftFeatures)]
     lib.spvo_akaze_sift_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(AkazeSiftFeatures), C.POINTER(AkazeSiftFeatures)]
+    lib.spvo_orb_brisk_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(BriskFeatures), C.POINTER(BriskFeatures)]
+    lib.spvo_orb_sift_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(SiftFeatures), C.POINTER(SiftFeatures)]
     lib.spvo_sift_link_debug.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, ip]
     lib.spvo_classic_sift_pair.argtypes = [vp, C.POINTER(ClassicOpts), vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.POINTER(SiftFeatures), C.POINTER(SiftFeatures)]
     lib.spvo_sift_slot_rows.argtypes = [vp, C.c_int, ip]
@@ -820,6 +822,21 @@ class Context:
         [m, 128] -- per image what akaze_detect() followed by sift_describe(None, its records without class_id) returns.  Afterwards the
         right image and its scale space are resident."""
         return self._sift_octave_pair(self.lib.spvo_akaze_sift_pair, AKAZE_KP_DTYPE, AkazeSiftFeatures, img_l, img_r, (float(threshold),), slot_l, slot_r, slot_capacity, cap)
+
+    def orb_brisk_pair(self, img_l, img_r, slot_l: int, slot_r: int, nfeatures: int = 2000, slot_capacity: int = 8192, cap: Optional[int] = None):
+        """One stereo pair through the ORB detector and the BRISK extractor into two binary feature slots of 64-byte rows
+        (spvo_orb_brisk_pair).  -> (left, right): dicts of kp [m] (BRISK_KP_DTYPE: x, y, size 31 * 1.2^octave, the extractor's angle in
+        degrees, response, octave -- the detector's records that survived the extractor's border rule, in the detector's order), desc
+        [m, 64] uint8 and n -- per image what orb_detect() followed by brisk_describe(img, its xy, those sizes) returns.  Afterwards the
+        right image is resident.  On SPVO_ERR_CAPACITY the SpvoError carries the two counts as .n_l, .n_r (and .counts)."""
+        return self._octave_pair(self.lib.spvo_orb_brisk_pair, BRISK_KP_DTYPE, BriskFeatures, 64, img_l, img_r, (int(nfeatures),), slot_l, slot_r, slot_capacity, cap)
+
+    def orb_sift_pair(self, img_l, img_r, slot_l: int, slot_r: int, nfeatures: int = 2000, slot_capacity: int = 8192, cap: Optional[int] = None):
+        """One stereo pair through the ORB detector and the SIFT extractor into two SIFT slots (spvo_orb_sift_pair).  -> (left, right):
+        dicts of kp [m] (SIFT_KP_DTYPE: x, y, size 31 * 1.2^octave, the detector's angle in degrees, response, octave), desc [m, 128]
+        float32 and n -- per image what orb_detect() followed by sift_describe(img, those records) returns; nothing is erased.
+        Afterwards the right image is resident.  On SPVO_ERR_CAPACITY the SpvoError carries the two counts as .counts."""
+        return self._sift_octave_pair(self.lib.spvo_orb_sift_pair, SIFT_KP_DTYPE, SiftFeatures, img_l, img_r, (int(nfeatures),), slot_l, slot_r, slot_capacity, cap)
 
     def sift_link_debug(self, kp: np.ndarray, keep=None, max_octave: int = 5, shape=None):
         """The two calls' device link and describe launch on a caller's list against the resident image (spvo_sift_link_debug): kp [n]

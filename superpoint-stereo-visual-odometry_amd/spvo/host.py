@@ -347,7 +347,7 @@ class FrontEnd:
 
 def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_threshold=2.0, refinement_degree=4, warm=0, detector="ORB", input_size=None, resident=False,
                      resident_capacity=0, trace=False, descriptor="ORB", brisk_resident=False, akaze_descriptor=False, akaze_resident=False, sift_describe_resident=False, orb_octaves=False,
-                     octave_pairs_resident=False, sift_octave_pairs_resident=False, matcher="BF"):
+                     octave_pairs_resident=False, sift_octave_pairs_resident=False, matcher="BF", orb_brisk=False, orb_pairs_resident=False):
     """matcher: "BF", or "FLANN" (spvo_host_classic_sequence_matcher: the exact L2 search on the descriptor bytes, no cross-check).
     stereoCallback replayed on ClassicFeatureFrontEnd(detector, descriptor, BF, ...) (node.cpp:353-360) over host image pairs -- detector
     "ORB", "ShiTomasi" or "FAST" with descriptor "ORB", "ShiTomasi", "FAST", "BRISK" or "AKAZE" with descriptor "BRISK" (64-byte rows; detector "BRISK"
@@ -374,7 +374,12 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     spvo_akaze_brisk_pair per pair into the binary slots; without it the three take the per-image path, as said above.
     sift_octave_pairs_resident (ClassicFeatureFrontEnd::setSiftOctavePairsResident, reset afterwards) with resident=True: "BRISK" + "SIFT"
     and "AKAZE" + "SIFT" are one spvo_brisk_sift_pair / spvo_akaze_sift_pair per pair into the SIFT slots; without it both take the
-    per-image path and are matched from the host copies.  "ORB" + "SIFT" has no resident route.
+    per-image path and are matched from the host copies.
+    orb_brisk (ClassicFeatureFrontEnd::setOrbBriskExtractor, reset afterwards): "ORB" + "BRISK" runs -- per image spvo_orb_detect, then
+    spvo_brisk_describe at every keypoint's size 31 x 1.2^octave -- and is refused without.  orb_pairs_resident
+    (ClassicFeatureFrontEnd::setOrbPairsResident, reset afterwards) with resident=True: "ORB" + "BRISK" (which still needs orb_brisk=True) and
+    "ORB" + "SIFT" are one spvo_orb_brisk_pair / spvo_orb_sift_pair per pair into the binary / the SIFT slots; without it both take the
+    per-image path.
     trace: a fourth value, digests [n, 8] uint64 of what every frame left in the front end (keypoints L, descriptors L, keypoints R,
     descriptors R, stereo matches, temporal matches, the previous frame's stereo matches + map, the inlier sets): equal digests = identical
     contents.  The digests are computed inside the timed loop, so `seconds` of a traced run is not a frame-rate figure."""
@@ -402,6 +407,10 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     lib.spvo_host_classic_set_octave_pairs_resident.argtypes = [C.c_int]
     lib.spvo_host_classic_set_sift_octave_pairs_resident.restype = None
     lib.spvo_host_classic_set_sift_octave_pairs_resident.argtypes = [C.c_int]
+    lib.spvo_host_classic_set_orb_brisk.restype = None
+    lib.spvo_host_classic_set_orb_brisk.argtypes = [C.c_int]
+    lib.spvo_host_classic_set_orb_pairs_resident.restype = None
+    lib.spvo_host_classic_set_orb_pairs_resident.argtypes = [C.c_int]
     n = len(frames)
     ls = [np.ascontiguousarray(f[0], np.uint8) for f in frames]
     rs = [np.ascontiguousarray(f[1], np.uint8) for f in frames]
@@ -423,6 +432,8 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     lib.spvo_host_classic_set_orb_octaves(int(bool(orb_octaves)))
     lib.spvo_host_classic_set_octave_pairs_resident(int(bool(octave_pairs_resident)))
     lib.spvo_host_classic_set_sift_octave_pairs_resident(int(bool(sift_octave_pairs_resident)))
+    lib.spvo_host_classic_set_orb_brisk(int(bool(orb_brisk)))
+    lib.spvo_host_classic_set_orb_pairs_resident(int(bool(orb_pairs_resident)))
     try:
         args =(n, pl, pr, rows, cols, Pl.ctypes.data, Pr.ctypes.data, 1 if selector == "KNN" else 0, int(cross_check), stereo_threshold, refinement_degree, warm,
                 poses.ctypes.data, stats.ctypes.data, C.byref(sec), ih, iw, digest.ctypes.data if trace else None)
@@ -441,6 +452,8 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
         lib.spvo_host_classic_set_orb_octaves(0)
         lib.spvo_host_classic_set_octave_pairs_resident(0)
         lib.spvo_host_classic_set_sift_octave_pairs_resident(0)
+        lib.spvo_host_classic_set_orb_brisk(0)
+        lib.spvo_host_classic_set_orb_pairs_resident(0)
     if rc == -1000000:
         raise ValueError("unknown detector %r" % (detector,))
     if rc == -1000001:
@@ -479,10 +492,11 @@ def classic_default_probe(img_l, img_r, P_l, P_r):
     return rc, counts, buf.value.decode()
 
 
-def classic_pair_probe(detector, descriptor, img_l, img_r, P_l, P_r, akaze_descriptor=False, orb_octaves=False):
+def classic_pair_probe(detector, descriptor, img_l, img_r, P_l, P_r, akaze_descriptor=False, orb_octaves=False, orb_brisk=False):
     """ClassicFeatureFrontEnd(detector, descriptor, BF, NN, cross-check) at the native resolution offered one stereo pair.
     akaze_descriptor: ClassicFeatureFrontEnd::setAkazeDescriptor for this probe (AKAZE + AKAZE runs), reset afterwards.
     orb_octaves: ClassicFeatureFrontEnd::setOrbExtractorOctaves for this probe (BRISK + ORB and AKAZE + ORB run), reset afterwards.
+    orb_brisk: ClassicFeatureFrontEnd::setOrbBriskExtractor for this probe (ORB + BRISK runs), reset afterwards.
     -> (deque entries, [keypoints L, descriptor rows L, keypoints R, descriptor rows R, descriptor columns], the error it logged)"""
     lib = load()
     lib.spvo_host_classic_pair_probe.restype = C.c_int
@@ -499,12 +513,16 @@ def classic_pair_probe(detector, descriptor, img_l, img_r, P_l, P_r, akaze_descr
     lib.spvo_host_classic_set_orb_octaves.restype = None
     lib.spvo_host_classic_set_orb_octaves.argtypes = [C.c_int]
     lib.spvo_host_classic_set_orb_octaves(int(bool(orb_octaves)))
+    lib.spvo_host_classic_set_orb_brisk.restype = None
+    lib.spvo_host_classic_set_orb_brisk.argtypes = [C.c_int]
+    lib.spvo_host_classic_set_orb_brisk(int(bool(orb_brisk)))
     try:
         rc = lib.spvo_host_classic_pair_probe(detector.encode(), descriptor.encode(), l.ctypes.data, r.ctypes.data, l.shape[0], l.shape[1], Pl.ctypes.data, Pr.ctypes.data,
                                               counts.ctypes.data, buf, 512)
     finally:
         lib.spvo_host_classic_set_akaze_descriptor(0)
         lib.spvo_host_classic_set_orb_octaves(0)
+        lib.spvo_host_classic_set_orb_brisk(0)
     return rc, counts, buf.value.decode()
 
 

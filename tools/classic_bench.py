@@ -1,6 +1,6 @@
 """The classic front end on the GPU.
 
-python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK|AKAZE] [--descriptor ORB|BRISK|AKAZE|SIFT] [--resident] [--brisk-resident] [--akaze-resident] [--sift-resident] [--orb-octaves] [--octave-pairs-resident] [--sift-octave-pairs-resident]
+python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK|AKAZE] [--descriptor ORB|BRISK|AKAZE|SIFT] [--resident] [--brisk-resident] [--akaze-resident] [--sift-resident] [--orb-octaves] [--octave-pairs-resident] [--sift-octave-pairs-resident] [--orb-brisk] [--orb-pairs-resident]
     ClassicFeatureFrontEnd(detector, descriptor, BF, KNN) over the synthetic stream: frames/s of the synchronous stereoCallback
     (--descriptor BRISK: with --detector ShiTomasi, FAST, BRISK or AKAZE; --detector BRISK: with --descriptor BRISK only; --detector AKAZE:
     with --descriptor BRISK or AKAZE -- the latter sets ClassicFeatureFrontEnd::setAkazeDescriptor for the run: 61-byte MLDB rows);
@@ -12,7 +12,9 @@ python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK|AKAZ
     also taken by --ab for its resident runs).
     --sift-octave-pairs-resident: with setSiftOctavePairsResident as well (BRISK / AKAZE + SIFT through one spvo_brisk_sift_pair /
     spvo_akaze_sift_pair per pair; needs --resident; also taken by --ab for its resident runs).
-python tools/classic_bench.py [frames] --detector ShiTomasi|FAST|ORB|BRISK|AKAZE --descriptor ORB|BRISK|SIFT --ab ROUNDS [--sift-resident] [--sift-octave-pairs-resident] [--waves N]
+    --orb-brisk: with setOrbBriskExtractor (ORB + BRISK runs at all); --orb-pairs-resident: with setOrbPairsResident as well (ORB + BRISK /
+    ORB + SIFT through one spvo_orb_brisk_pair / spvo_orb_sift_pair per pair; needs --resident; also taken by --ab for its resident runs).
+python tools/classic_bench.py [frames] --detector ShiTomasi|FAST|ORB|BRISK|AKAZE --descriptor ORB|BRISK|SIFT --ab ROUNDS [--sift-resident] [--sift-octave-pairs-resident] [--orb-brisk] [--orb-pairs-resident] [--waves N]
     the same stream with setDeviceResident off and on, alternating, ROUNDS times each in one process: ms per pair of every run, the median
     and the min .. max spread of each setting, and how many pairs of a resident run stayed resident.  --waves N: tuning
     "sift_pair_waves_per_cu" = N for the SIFT pair calls of the resident runs.
@@ -65,6 +67,14 @@ python tools/classic_bench.py --leg brisk_orb_pair|akaze_orb_pair|akaze_brisk_pa
     orb_link_finish_kernel, or akaze_present_brisk_kernel / brisk_integral_*_kernel / brisk_pair_compact_kernel / brisk_describe_kernel /
     brisk_pair_finish_kernel / akaze_brisk_finish_kernel, twice per call.  The whole pair through the host class: --detector BRISK|AKAZE
     --descriptor ORB|BRISK [--orb-octaves] --resident --octave-pairs-resident (ClassicFeatureFrontEnd::setOctavePairsResident for the run).
+python tools/classic_bench.py --leg orb_brisk_pair|orb_sift_pair [--calls 100]
+    spvo_orb_brisk_pair / spvo_orb_sift_pair on the 1241 x 376 sample pair -- BOTH images per call -- rotating through the slot ring, and
+    ALTERNATING with it call by call in the same run its yardstick, the per-image route of both images: spvo_orb_detect, the records
+    converted on the host, then spvo_brisk_describe / spvo_sift_describe with the image passed again (spvo_orb_detect leaves none
+    resident).  For rocprofv3 --kernel-trace --stats as above (--no-yardstick: the pair call alone): behind spvo_orb_detect's kernels
+    orb_records_kernel, then brisk_integral_*_kernel / brisk_pair_compact_kernel / brisk_describe_kernel / brisk_pair_finish_kernel, or
+    sift_blur_kernel x the reduced pyramid / sift_describe_given_kernel, twice per call.  The whole pair through the host class:
+    --detector ORB --descriptor BRISK|SIFT [--orb-brisk] --resident --orb-pairs-resident, or --ab.
 python tools/classic_bench.py --leg fast_sift|gftt_sift|sift_describe [--calls 50] [--form 0|1] [--yardstick] [--sift-resident]
     FAST + SIFT per image at 1241 x 376, for rocprofv3 --kernel-trace --stats as above.  sift_describe: spvo_sift_describe alone on the FAST
     keypoints of the sample (size 7, angle -1, octave 0; image passed with every call): sift_blur_kernel x 6 / sift_describe_given_kernel is
@@ -102,9 +112,11 @@ ap.add_argument("--sift-resident", action="store_true")
 ap.add_argument("--orb-octaves", action="store_true")
 ap.add_argument("--octave-pairs-resident", action="store_true")
 ap.add_argument("--sift-octave-pairs-resident", action="store_true")
+ap.add_argument("--orb-brisk", action="store_true")
+ap.add_argument("--orb-pairs-resident", action="store_true")
 ap.add_argument("--no-yardstick", action="store_true")
 ap.add_argument("--ab", type=int, default=0)
-ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "brisk_detect", "akaze_detect", "akaze_describe", "akaze_pair", "brisk_pair", "brisk_orb_pair", "akaze_orb_pair", "akaze_brisk_pair", "orb_describe", "orb_octaves", "fast_sift", "gftt_sift", "sift_describe", "match", "match_slots"])
+ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "brisk_detect", "akaze_detect", "akaze_describe", "akaze_pair", "brisk_pair", "brisk_orb_pair", "akaze_orb_pair", "akaze_brisk_pair", "orb_brisk_pair", "orb_sift_pair", "orb_describe", "orb_octaves", "fast_sift", "gftt_sift", "sift_describe", "match", "match_slots"])
 ap.add_argument("--form", type=int, default=0, choices=[0, 1])
 ap.add_argument("--waves", type=int, default=0)
 ap.add_argument("--selector", default="KNN", choices=["NN", "KNN"])
@@ -216,7 +228,8 @@ if args.detectors or args.leg:
         fl, fr = ctx.akaze_detect_pair(img, pair_r, 2 * k, 2 * k + 1)
         return fl["n"] + fr["n"]
 
-    OCTAVE_PAIRS = ("brisk_orb_pair", "akaze_orb_pair", "akaze_brisk_pair")
+    ORB_PAIRS = ("orb_brisk_pair", "orb_sift_pair")
+    OCTAVE_PAIRS = ("brisk_orb_pair", "akaze_orb_pair", "akaze_brisk_pair") + ORB_PAIRS
     if args.leg in ("brisk_pair", "akaze_pair", "fast_sift", "gftt_sift") + OCTAVE_PAIRS:
         pair_r = np.ascontiguousarray(frames[0][1][:376, :1241])
 
@@ -226,9 +239,23 @@ if args.detectors or args.leg:
         fl, fr = getattr(ctx, args.leg)(img, pair_r, 2 * k, 2 * k + 1)
         return fl["n"] + fr["n"]
 
+    def orb_records(o):                                # the host's to_keypoint: size 31 x 1.2^octave (repeated float product), degrees 0 .. 360
+        scale = np.ones(8, np.float32)
+        for l in range(1, 8):
+            scale[l] = scale[l - 1] * np.float32(1.2)
+        rec = np.zeros(len(o["xy"]), capi.SIFT_KP_DTYPE)
+        deg = o["angle"] * np.float32(57.29577951308232)
+        rec["x"], rec["y"], rec["size"], rec["response"], rec["octave"] = o["xy"][:, 0], o["xy"][:, 1], np.float32(31) * scale[o["octave"] & 7], o["response"], o["octave"]
+        rec["angle"] = np.where(deg < 0, deg + np.float32(360), deg)
+        return rec
+
     def leg_octave_pair_per_image():                   # its yardstick: detector, then the extractor on the resident image, per image
         n = 0
         for im in (img, pair_r):
+            if args.leg in ORB_PAIRS:                  # (spvo_orb_detect leaves no image resident: the extractor takes it again)
+                rec = orb_records(ctx.orb(im))
+                n += len(ctx.sift_describe(im, rec)) if args.leg == "orb_sift_pair" else len(ctx.brisk_describe(im, np.stack([rec["x"], rec["y"]], 1), rec["size"])["kept"])
+                continue
             kp = (ctx.brisk_detect(im, 30) if args.leg == "brisk_orb_pair" else ctx.akaze_detect(im))["kp"]
             xy = np.stack([kp["x"], kp["y"]], 1)
             d = ctx.brisk_describe(None, xy, kp["size"], shape=im.shape) if args.leg == "akaze_brisk_pair" else ctx.orb_describe_octaves(None, xy, kp["octave"], shape=im.shape)
@@ -330,12 +357,13 @@ elif args.ab > 0:
     seq = [frames[i % 8] for i in range(n)]
     name = args.detector + ("" if args.descriptor == "ORB" else " + " + args.descriptor)
     ms = {False: [], True: []}
-    host.classic_sequence(seq[:8], P_l, P_r, "KNN", True, 2.0, 4, detector=args.detector, descriptor=args.descriptor)      # the process's one-off costs
+    host.classic_sequence(seq[:8], P_l, P_r, "KNN", True, 2.0, 4, detector=args.detector, descriptor=args.descriptor, orb_brisk=args.orb_brisk)      # the process's one-off costs
     for r in range(args.ab):
         for resident in (False, True):
             p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5, detector=args.detector, resident=resident, descriptor=args.descriptor,
                                                 sift_describe_resident=resident and args.sift_resident,
-                                                sift_octave_pairs_resident=resident and args.sift_octave_pairs_resident)
+                                                sift_octave_pairs_resident=resident and args.sift_octave_pairs_resident, orb_brisk=args.orb_brisk,
+                                                orb_pairs_resident=resident and args.orb_pairs_resident)
             ms[resident].append(1e3 * sec / (n - 5))
             print("%s %dx%d round %d resident=%d: %.3f ms per pair over %d pairs, %d pairs resident, keypoints %d, stereo matches %d, inliers %d" % (
                 name, frames[0][0].shape[1], frames[0][0].shape[0], r, resident, ms[resident][-1], n - 5, host.classic_resident_pairs(), np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3])))
@@ -350,5 +378,6 @@ else:
                                         akaze_descriptor=args.descriptor == "AKAZE", **(dict(brisk_resident=True) if args.brisk_resident else {}), **(dict(akaze_resident=True) if args.akaze_resident else {}),
                                         **(dict(sift_describe_resident=True) if args.sift_resident else {}), **(dict(orb_octaves=True) if args.orb_octaves else {}),
                                         **(dict(octave_pairs_resident=True) if args.octave_pairs_resident else {}),
-                                        **(dict(sift_octave_pairs_resident=True) if args.sift_octave_pairs_resident else {}))
+                                        **(dict(sift_octave_pairs_resident=True) if args.sift_octave_pairs_resident else {}), orb_brisk=args.orb_brisk,
+                                        orb_pairs_resident=args.orb_pairs_resident)
     print("classic front end (%s%s) on the GPU: %.1f stereo frames/s (%.3f ms per pair), keypoints %d, stereo matches %d, inliers %d, %d pairs resident" % (args.detector + ("" if args.descriptor == "ORB" else " + " + args.descriptor), ", device-resident" if args.resident else "", (n - 5) / sec, 1e3 * sec / (n - 5), np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3]), host.classic_resident_pairs()))
