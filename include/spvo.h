@@ -1006,7 +1006,8 @@ int spvo_profile_stage_fused(spvo_ctx *ctx, const char *stage, int info[8]);
  * created / engines loaded afterwards.  `name` is one of the names INTEGRATION.md lists ("winograd", "wino4", "wino4_item", "wino_narrow",
  * "wino_dynamic", "winograd_min_tiles", "wino4_min_tiles", "merge_siblings", "heads_fused", "heads_on_net", "heads_split",
  * "match_fused", "fp32_split", "prematch", "spin_wait", "trunk_timing", "solve_timing", "nms_first", "upload_side", "conv_variant"); SPVO_ERR_INVALID for any other.
- * spvo_get_tuning returns the value set, or `dflt`; spvo_clear_tuning forgets every value. */
+ * spvo_get_tuning returns the value set, or `dflt`; spvo_clear_tuning forgets every value.
+ * "wino4_item" selects the item of the F(4x4,3x3) kernel: 3 (the default), 2, 1 or 0, oldest last; all four give the same bits. */
 int spvo_set_tuning(const char *name, int value);
 int spvo_get_tuning(const char *name, int dflt);
 void spvo_clear_tuning(void);

@@ -39,7 +39,8 @@
 //     reads) are issued by inline assembly and waited for by s_waitcnt lgkmcnt(N) with N counted at compile time (ITEM = 1, see
 //     WINO4_ITEM_LEAD below); the compiler's own placement drained the LDS queue six times per item.  Measured on one MI355X, same
 //     box, old item against new: conv1b 403 -> 390 us inside the benchmark, matrix stream 3425 -> 3317 cycles per item
-//     (profiles/wino4_item_*); ITEM = 2, the default, also issues the item's LDS-DMA from a scalar base and a lane offset (below);
+//     (profiles/wino4_item_*); ITEM = 2 also issues the item's LDS-DMA from a scalar base and a lane offset, and ITEM = 3, the default, cuts
+//     the item's scalar and no-result instructions (both below);
 //   * the inverse transform (36 -> 16 per output channel and tile) runs in registers, as before.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -92,7 +93,7 @@
 // reads) count only what it tracks and are for the same reason never too loose.  The half-used B pieces (4 and 9: positions 16 and
 // 17) are read as 8 bytes, so that no read's destination overlaps an older read's; the role predicate is scalar arithmetic.
 //
-// ITEM = 2 (the default) is ITEM = 1 with its LDS-DMA issued as global_load_lds_dwordx4 vOff, s[base:base+1]: the scalar 64-bit base of the
+// ITEM = 2 is ITEM = 1 with its LDS-DMA issued as global_load_lds_dwordx4 vOff, s[base:base+1]: the scalar 64-bit base of the
 // chunk / tile, advanced by scalar adds (also from one of the five filter pieces to the next: 8192 bytes do not fit the immediate), and the
 // thread's 32-bit lane offset, which never changes (glds16_sv, conv_mfma.hip.h).  fp32 matrix and vector instructions share the issue, and
 // ITEM = 1 has a 64-bit vector add (v_lshl_add_u64) in front of each of the item's seven loads, which computes an address and no result.
@@ -105,8 +106,34 @@
 #ifndef WINO4_ITEM_LEAD
 #define WINO4_ITEM_LEAD 6
 #endif
+//
+// ITEM = 3 is ITEM = 2 with the instructions of the item that compute no value of the result cut down, in steps that can be switched one by one
+// (WINO4_ITEM3_STEPS, a mask; measurement builds of tools/wino_bench.hip instantiate ITEM = 16 + mask to time each step on top of the ones before):
+//    1  the two 64-bit DMA bases (filter slab of the filter cursor, raw tile of the raw cursor) are RUNNING pointers: one scalar add when the
+//       cursor steps to the next chunk, a fresh base when it steps to the next tile, instead of base + chunk * stride (64-bit multiplies) in
+//       every item; the five filter pieces chain their base (+ 8192 each) through one register pair; the LDS side (M0) is a scalar that
+//       swaps between the two buffers by one subtraction per item.  glds16_sv's form of the load is kept (wino4_glds16_run): the builtin,
+//       so the compiler owns M0 and counts vmcnt, and the WAIT RULE above holds word for word;
+//    2  the role test launders ONE scalar in place (no copy in front of every s_cmp), and that scalar flips by one s_xor per item;
+//    4  the counted operand wait has its pieces as INPUTS only: read -> wait is ordered by data dependence, wait -> matrix instruction by the
+//       order of volatile statements and the scheduling barrier around every matrix instruction.  (As in / out operands the wait counted as a
+//       writer of the matrix instruction's sources and the hazard recogniser put an s_nop behind each of the 14.)  tools/wino4_wait_check.py
+//       checks on the listing that no instruction touches a pending read's destination;
+//    8  LDS addresses are kept, not rebuilt: wave group g = (wave >> TB) & 1 does H1 exactly in the items with k & 1 == g and H2 in the others, so
+//       the raw tile it reads and the V buffer it writes are ALWAYS buffer g -- two addresses computed once; the two operand bases swap
+//       between their buffers by one vector subtraction each per item (base = sum of the two - base);
+//   16  the row pass of H1 is written out, one v_fma_f32 / v_fmamk_f32 / v_add_f32 / v_sub_f32 per operation of wino4_in6, so that the compiler
+//       cannot pair them into v_pk_fma_f32 (dearer beside matrix instructions than the two it replaces) and assemble the pairs with moves.
+// Same matrix instructions, same order, same operands, same transform arithmetic: the same bits as items 0 - 2.  One body, as before.
+// A wave executes 200 / 211 instructions per item (first-half / second-half role) instead of 258 / 268 (tools/wino4_wait_check.py counts them).
+// Measured, same box, items alternating in one process: conv1b 366 -> 356 us, the other layers -4.9 .. -6.6 %, matrix stream 3225 -> 3097 cycles
+// per item, barrier 396 -> 335 (profiles/wino4_item3_*; NOTES.md, "F(4x4) item: scalar and no-result instructions cut", has every step by itself:
+// the scalar steps are worth 0 - 1 %, steps 8 and 16 the rest).
+#ifndef WINO4_ITEM3_STEPS
+#define WINO4_ITEM3_STEPS 31
+#endif
 #ifndef WINO4_ABL
-#define WINO4_ABL 0   // measurement builds only (tools/wino_bench.hip): 1 no input transform, 2 no filter staging, 4 no raw staging, 8 operands read once, 16 no stores
+#define WINO4_ABL 0  // measurement builds only (tools/wino_bench.hip): 1 no input transform, 2 no filter staging, 4 no raw staging, 8 operands read once, 16 no stores
 #endif
 
 #ifndef SPVO_STATIC_BANDS
@@ -178,6 +205,35 @@ __device__ __forceinline__ void wino4_out4(const float m0, const float m1, const
   y[3] = fmaf(8.f, d, b) + m5;
 }
 
+// in6 with one instruction per operation (ITEM = 3, step 16): the same twelve operations in the same association, so the same bits.  ONE
+// statement: between two asm statements of which the second reads what the first wrote, the hazard recogniser puts an s_nop.
+__device__ __forceinline__ void wino4_in6_written_out(const float x0, const float x1, const float x2, const float x3, const float x4, const float x5, float (&o)[6]) {
+  float t, u;
+  asm("v_fma_f32 %6, -4.0, %10, %12\n\t"          // e  = -4 x2 + x4
+      "v_fma_f32 %7, -4.0, %9, %11\n\t"           // od = -4 x1 + x3
+      "v_fmamk_f32 %0, %10, 0xc0a00000, %12\n\t"  // -5 x2 + x4
+      "v_fmamk_f32 %5, %11, 0xc0a00000, %13\n\t"  // -5 x3 + x5
+      "v_add_f32 %1, %6, %7\n\t"
+      "v_sub_f32 %2, %6, %7\n\t"
+      "v_sub_f32 %6, %12, %10\n\t"                // e2 = x4 - x2
+      "v_sub_f32 %7, %11, %9\n\t"                 // o2 = x3 - x1
+      "v_fma_f32 %0, 4.0, %8, %0\n\t"
+      "v_fma_f32 %5, 4.0, %9, %5\n\t"
+      "v_fma_f32 %3, 2.0, %7, %6\n\t"
+      "v_fma_f32 %4, -2.0, %7, %6"
+      : "=&v"(o[0]), "=&v"(o[1]), "=&v"(o[2]), "=&v"(o[3]), "=&v"(o[4]), "=&v"(o[5]), "=&v"(t), "=&v"(u)
+      : "v"(x0), "v"(x1), "v"(x2), "v"(x3), "v"(x4), "v"(x5));
+}
+
+// glds16_sv (conv_mfma.hip.h) on a RUNNING base (ITEM = 3, step 1).  The caller launders the base IN PLACE (wino4_opaque_base: the next `base += step`
+// then works on the same register pair; laundering a copy costs a 64-bit move per piece) and outside any lane-dependent branch (a scalar changed
+// under one would have to become a vector value); the lane offset is laundered here, in the block of the load.
+__device__ __forceinline__ void wino4_opaque_base(const char *&uniform_base) { asm volatile("" : "+s"(uniform_base)); }
+__device__ __forceinline__ void wino4_glds16_run(const char *opaque_uniform_base, unsigned &lane_off, float *lds_wave_base) {
+  asm volatile("" : "+v"(lane_off));
+  glds16(reinterpret_cast<const float *>(opaque_uniform_base + lane_off), lds_wave_base);
+}
+
 // the same on two output channels at once (v_pk_add_f32 / v_pk_fma_f32: the epilogue has no matrix instructions to hide behind)
 typedef float wino4_f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void wino4_out4(const wino4_f32x2 m0, const wino4_f32x2 m1, const wino4_f32x2 m2, const wino4_f32x2 m3, const wino4_f32x2 m4,
@@ -213,13 +269,16 @@ constexpr int wino4_wait_count(int p, int lead) {
 template <class F, int... P>
 __device__ __forceinline__ void wino4_for_each(F &&f, std::integer_sequence<int, P...>) { (f(std::integral_constant<int, P>{}), ...); }
 
-template <bool POOL, bool RELU, int TAG = 0, int TB = 2, int ITEM = 2>
+template <bool POOL, bool RELU, int TAG = 0, int TB = 2, int ITEM = 3>
 __global__ __launch_bounds__(256 * TB, TB) void conv_wino4_kernel(const ConvArgs a) {
   using T = Wino4TileT<TB>;
   constexpr int CK = T::CK, LW = T::LW, LH = T::LH, LW4 = LW / 4, NTH = T::NTH;
   constexpr int IN_V4 = T::IN_FLOATS / 4;        // 720 (400) 16-byte pieces per raw tile
   constexpr int U_V4 = T::U_FLOATS / 4;          // 2304 per filter slab
   constexpr bool NEW_ITEM = ITEM != 0 && !(WINO4_ABL & 8);   // (the read-once ablation exists in the earlier item only)
+  constexpr int STEPS = !NEW_ITEM ? 0 : ITEM == 3 ? (WINO4_ITEM3_STEPS) : ITEM >= 16 ? ITEM - 16 : 0;   // ITEM = 3's steps (mask: see WINO4_ITEM3_STEPS)
+  constexpr bool S_PTR = (STEPS & 1) != 0, S_ROLE = (STEPS & 2) != 0, S_WAIT = (STEPS & 4) != 0, S_LDS = (STEPS & 8) != 0, S_ROW = (STEPS & 16) != 0;
+  constexpr bool DMA_SV = ITEM >= 2;             // LDS-DMA from a scalar base
   constexpr int NIT_U = (U_V4 + NTH - 1) / NTH;  // 5, the last one by threads 0..255 (9, all full)
   typedef float f32x2 __attribute__((ext_vector_type(2)));
   typedef float f32x4v __attribute__((ext_vector_type(4)));
@@ -289,6 +348,27 @@ __global__ __launch_bounds__(256 * TB, TB) void conv_wino4_kernel(const ConvArgs
 #pragma unroll
     for (int it = 0; it < NIT_U; ++it)
       if (it < NIT_U - 1 || tid < U_V4 - (NIT_U - 1) * NTH) glds16_sv(wb + (size_t)16 * NTH * it, uoff, buf + (it * NTH + wave * 64) * 4);
+  };
+  // ITEM = 3, step 1: the same pieces from running bases (wp3: the filter cursor's slab, rp3: the raw cursor's tile and chunk; advance3 below) into
+  // `lds` = LDS address of (buffer, this wave's 1 KiB), which swaps between the two buffers once per item
+  // (The filter base walks through the slab's pieces and is left at the LAST piece; advance3 adds what is missing to the next slab, U_TAIL3.  The
+  // last piece is carried by whole waves, so its test is scalar.)
+  const char *wp3 = nullptr, *rp3 = nullptr;
+  constexpr int U_TAIL3 = T::U_FLOATS * 4 - (NIT_U - 1) * 16 * NTH, U_LAST_WAVES3 = (U_V4 - (NIT_U - 1) * NTH) / 64;
+  static_assert((U_V4 - (NIT_U - 1) * NTH) % 64 == 0, "the last filter piece by whole waves");
+  auto lds_ptr3 = [](unsigned lds) { return (float *)(__attribute__((address_space(3))) float *)(uintptr_t)lds; };
+  auto issue_raw3 = [&](unsigned lds) {
+    wino4_opaque_base(rp3);
+    wino4_glds16_run(rp3, roff0, lds_ptr3(lds));
+    if (raw2) wino4_glds16_run(rp3, roff1, lds_ptr3(lds + (NTH - R0) * 16));
+  };
+  auto issue_u3 = [&](unsigned lds) {
+#pragma unroll
+    for (int it = 0; it < NIT_U; ++it) {
+      if (it) wp3 += 16 * NTH;
+      wino4_opaque_base(wp3);
+      if (it < NIT_U - 1 || wave < U_LAST_WAVES3) wino4_glds16_run(wp3, uoff, lds_ptr3(lds + it * NTH * 16));
+    }
   };
 
   // ---- input transform: two threads per patch.  u = tid & 255: input channel = u >> 6 (= wave & 3), tile = lane & 31 (tile row
@@ -391,6 +471,20 @@ __global__ __launch_bounds__(256 * TB, TB) void conv_wino4_kernel(const ConvArgs
       if (q.id < n_tiles) q.t = decode(q.id);
     }
   };
+  // ITEM = 3, step 1: advance() that also moves the cursor's DMA base `p`: by `step` bytes to the next chunk, or to the new tile's base
+  // (the add comes first and unconditionally, the rare tile step overwrites it: advance()'s control flow, no second join)
+  auto advance3 = [&](Cursor &q, const char *&p, long step, bool filters) {
+    p += step;
+    if (++q.chunk == a.n_chunks) {
+      asm volatile("" ::: "memory");   // a real branch, taken once per tile
+      q.chunk = 0;
+      q.id = a.sched ? nxt_id : q.id + (int)gridDim.x;
+      if (q.id < n_tiles) {
+        q.t = decode(q.id);
+        p = filters ? reinterpret_cast<const char *>(q.t.w_base) : reinterpret_cast<const char *>(q.t.in_base);
+      }
+    }
+  };
   Cursor cu{cur, 0, tile_id};
   issue_raw(cu.t, 0, smem + T::RAW_OFF);
   issue_u(cu.t, 0, smem + T::U_OFF);
@@ -419,6 +513,32 @@ __global__ __launch_bounds__(256 * TB, TB) void conv_wino4_kernel(const ConvArgs
   int k = 0;                    // items done: selects the buffers and the transforming half
   bool drained = false;         // the LDS-DMA this item needs has been waited for already
   constexpr unsigned OOB = 0xFFFFFFFFu;
+
+  // ITEM = 3: what an item takes from k, kept as running values instead (each moves by one instruction per item; values here: item 0)
+  auto lds_addr = [](const void *p) { return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)p; };
+  const int grp3 = (wave >> TB) & 1;
+  int xf3 = grp3 ^ 1;                                                        // step 2: the role scalar (H1 of item k + 2 when != 0)
+  unsigned lds_u3 = lds_addr(smem + T::U_OFF + T::U_FLOATS + wave * 256);    // step 1: where the DMA of filters (k + 1) ...
+  unsigned lds_raw3 = lds_addr(smem + T::RAW_OFF + T::IN_FLOATS + wave * 256);   //     ... and of raw tile (k + 3) go: buffer (k + 1) & 1, this wave's first KiB (LDS address)
+  const unsigned lds_u_swap3 = 2 * lds_u3 - T::U_FLOATS * 4, lds_raw_swap3 = 2 * lds_raw3 - T::IN_FLOATS * 4;   // (sum of the two buffers' addresses)
+  unsigned ua3 = lds_addr(reinterpret_cast<const f32x4v *>(smem + T::U_OFF) + a_lane);   // step 8: operand bases in buffer k & 1 ...
+  unsigned va3 = lds_addr(reinterpret_cast<const f32x4v *>(smem + T::V_OFF) + b_lane);
+  unsigned ua_swap3 = 2 * ua3 + T::U_FLOATS * 4, va_swap3 = 2 * va3 + T::V_FLOATS * 4;   //         ... swapped by base = (sum of the two) - base
+  unsigned ra3 = lds_addr(smem + T::RAW_OFF + grp3 * T::IN_FLOATS + raw_off);            //         H1's rows: always raw buffer grp3
+  unsigned vst3 = lds_addr(smem + T::V_OFF + grp3 * T::V_FLOATS + v_off);                //         H2's stores: always V buffer grp3
+  if constexpr (S_LDS) asm volatile("" : "+v"(ua3), "+v"(va3), "+v"(ra3), "+v"(vst3), "+v"(ua_swap3), "+v"(va_swap3));   // (kept in registers: never rebuilt inside the loop)
+  auto xf_store3 = [&](int c) {   // xf_step's steps 7 + c (column pass of column c, stores) through the kept address
+    float o[6];
+    wino4_in6(xr[0][c], xr[1][c], xr[2][c], xr[0][c + 3], xr[1][c + 3], xr[2][c + 3], o);
+    float __attribute__((address_space(3))) *vp = (float __attribute__((address_space(3))) *)(uintptr_t)vst3;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) vp[((3 * i + c) >> 2) * (256 * TB) + ((3 * i + c) & 3)] = o[i];
+  };
+  if constexpr (S_PTR) {
+    wp3 = reinterpret_cast<const char *>(cu.t.w_base + (size_t)cu.chunk * T::U_FLOATS);
+    rp3 = reinterpret_cast<const char *>(cr.t.in_base + (size_t)cr.chunk * CK * in_plane);
+  }
+  const long raw_step3 = (long)(CK * in_plane * 4);
 
   while (tile_id < n_tiles) {
     if (a.sched) {
@@ -473,10 +593,14 @@ __global__ __launch_bounds__(256 * TB, TB) void conv_wino4_kernel(const ConvArgs
         // the role as a scalar, compared afresh at every step: s_cmp + s_cbranch_scc, no lane mask kept in a register pair and no vector
         // instructions (the empty asm keeps the compiler from merging the comparisons into such a mask)
         const int xf_s = ((wave >> TB) ^ k ^ 1) & 1;
-        auto is_xf = [xf_s]() __attribute__((always_inline)) { int t = xf_s; asm volatile("" : "+s"(t)); return t != 0; };
-        const unsigned ra = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)(raw_next2 + raw_off);
-        const unsigned ua = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)ub4;
-        const unsigned va = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)vb4;
+        // (ITEM = 3, step 2: the running scalar itself is laundered, in place -- a copy of xf_s costs an s_mov_b32 in front of every comparison)
+        auto is_xf = [xf_s, &xf3]() __attribute__((always_inline)) {
+          if constexpr (S_ROLE) { asm volatile("" : "+s"(xf3)); return xf3 != 0; }
+          else { int t = xf_s; asm volatile("" : "+s"(t)); return t != 0; }
+        };
+        const unsigned ra = S_LDS ? ra3 : (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)(raw_next2 + raw_off);
+        const unsigned ua = S_LDS ? ua3 : (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)ub4;
+        const unsigned va = S_LDS ? va3 : (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)vb4;
         auto read_slot = [&av, &bv, &bh, ua, va](auto qc) __attribute__((always_inline)) {
           constexpr int q = decltype(qc)::value;
           if constexpr (q < 36 && wino4_slot_reads_a(q)) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(av[q >> 2]) : "v"(ua), "n"((q >> 2) * 256 * 16));
@@ -489,7 +613,22 @@ __global__ __launch_bounds__(256 * TB, TB) void conv_wino4_kernel(const ConvArgs
           constexpr int ph = p / 18, pq = p % 18, pos = 6 * (pq / 3) + 3 * ph + pq % 3, bj = wino4_b_piece(p);
           constexpr bool half = bj % 5 == 4;
           // the first use of a piece: wait for it (the asm's operands tie the wait between the reads and the matrix instruction)
-          if constexpr (wino4_slot_reads_a(p) || wino4_slot_reads_b(p)) {
+          // (ITEM = 3, step 4: the pieces as inputs only and a scheduling barrier behind the wait -- see WINO4_ITEM3_STEPS)
+          constexpr bool waits_here = wino4_slot_reads_a(p) || wino4_slot_reads_b(p);
+          auto set_prio = []() __attribute__((always_inline)) {
+#if WINO4_PRIO
+            if constexpr (p == 0) asm volatile("s_setprio 3");
+            if constexpr (p == 9) asm volatile("s_setprio 2");
+            if constexpr (p == 18) asm volatile("s_setprio 1");
+            if constexpr (p == 27) asm volatile("s_setprio 0");
+#endif
+          };
+          if constexpr (S_WAIT && waits_here) {
+            set_prio();   // (in front of the wait: behind it, the scheduling barrier would leave it behind the matrix instruction)
+            if constexpr (half) asm volatile("s_waitcnt lgkmcnt(%2)" : : "v"(av[p >> 2]), "v"(bh[bj / 5]), "n"(wino4_wait_count(p, LEAD)));
+            else asm volatile("s_waitcnt lgkmcnt(%2)" : : "v"(av[p >> 2]), "v"(bv[bj]), "n"(wino4_wait_count(p, LEAD)));
+            __builtin_amdgcn_sched_barrier(0);
+          } else if constexpr (waits_here) {
             if constexpr (half) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(av[p >> 2]), "+v"(bh[bj / 5]) : "n"(wino4_wait_count(p, LEAD)));
             else asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(av[p >> 2]), "+v"(bv[bj]) : "n"(wino4_wait_count(p, LEAD)));
           }
@@ -497,41 +636,53 @@ __global__ __launch_bounds__(256 * TB, TB) void conv_wino4_kernel(const ConvArgs
           float b_op;
           if constexpr (half) b_op = bh[bj / 5][pq & 3];
           else b_op = bv[bj][pq & 3];
-#if WINO4_PRIO
-          if constexpr (p == 0) asm volatile("s_setprio 3");
-          if constexpr (p == 9) asm volatile("s_setprio 2");
-          if constexpr (p == 18) asm volatile("s_setprio 1");
-          if constexpr (p == 27) asm volatile("s_setprio 0");
-#endif
+          if constexpr (!(S_WAIT && waits_here)) set_prio();
           if (FIRST) acc[pos] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_op, b_op, f32x4v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
           else acc[pos] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_op, b_op, acc[pos], 0, 0, 0);
           __builtin_amdgcn_sched_barrier(0);
-          if (!(WINO4_ABL & 2) && p == 1 && cu.id < n_tiles) { if constexpr (ITEM == 2) issue_u2(cu.t, cu.chunk, u_next); else issue_u(cu.t, cu.chunk, u_next); }
-          if (!(WINO4_ABL & 4) && p == 4 && cr.id < n_tiles) { if constexpr (ITEM == 2) issue_raw2(cr.t, cr.chunk, raw_next3); else issue_raw(cr.t, cr.chunk, raw_next3); }
+          if (!(WINO4_ABL & 2) && p == 1 && cu.id < n_tiles) {
+            if constexpr (S_PTR) issue_u3(lds_u3);
+            else if constexpr (DMA_SV) issue_u2(cu.t, cu.chunk, u_next);
+            else issue_u(cu.t, cu.chunk, u_next);
+          }
+          if (!(WINO4_ABL & 4) && p == 4 && cr.id < n_tiles) {
+            if constexpr (S_PTR) issue_raw3(lds_raw3);
+            else if constexpr (DMA_SV) issue_raw2(cr.t, cr.chunk, raw_next3);
+            else issue_raw(cr.t, cr.chunk, raw_next3);
+          }
           read_slot(std::integral_constant<int, p + LEAD>{});
           // the transform: H1 of item k + 2 (its three row reads the same way: issued untracked in steps 0..2, waited for by count in front
           // of the row pass of steps 3..5) or H2 of item k + 1
-          if constexpr (!(WINO4_ABL & 1) && p >= WINO4_H1_START && p < WINO4_H1_START + WINO4_H1_STEPS * WINO4_H1_STRIDE && (p - WINO4_H1_START) % WINO4_H1_STRIDE == 0) {
-            constexpr int st = (p - WINO4_H1_START) / WINO4_H1_STRIDE;
-            if (is_xf()) {
-              if constexpr (st < 3) {
-                asm volatile("ds_read2_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(xs2[st]) : "v"(ra), "n"(st * LW), "n"(st * LW + 5));
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xa[st]) : "v"(ra), "n"((st * LW + 1) * 4));
-              } else {
-                if constexpr (st < 6) {
-                  // behind row st - 3's reads: the operand reads of the slots up to this one's, and two reads per later row
-                  constexpr int p_rd = p - 3 * WINO4_H1_STRIDE;
-                  constexpr int n = wino4_reads_before(p + LEAD + 1) - wino4_reads_before(p_rd + LEAD + 1) + 2 * (5 - st);
-                  asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(xs2[st - 3]), "+v"(xa[st - 3]) : "n"(n > 15 ? 15 : n));
-                  xs0[st - 3] = xs2[st - 3][0];
-                  xs1[st - 3] = xs2[st - 3][1];
-                }
-                xf_step(raw_next2, v_next, st);
+          constexpr bool h1_slot = !(WINO4_ABL & 1) && p >= WINO4_H1_START && p < WINO4_H1_START + WINO4_H1_STEPS * WINO4_H1_STRIDE && (p - WINO4_H1_START) % WINO4_H1_STRIDE == 0;
+          constexpr bool h2_slot = !(WINO4_ABL & 1) && p >= WINO4_H2_START && p < WINO4_H2_START + (10 - WINO4_H1_STEPS) * WINO4_H2_STRIDE && (p - WINO4_H2_START) % WINO4_H2_STRIDE == 0;
+          auto h1 = [&](auto stc) __attribute__((always_inline)) {
+            constexpr int st = decltype(stc)::value;
+            if constexpr (st < 3) {
+              asm volatile("ds_read2_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(xs2[st]) : "v"(ra), "n"(st * LW), "n"(st * LW + 5));
+              asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xa[st]) : "v"(ra), "n"((st * LW + 1) * 4));
+            } else {
+              if constexpr (st < 6) {
+                // behind row st - 3's reads: the operand reads of the slots up to this one's, and two reads per later row
+                constexpr int p_rd = p - 3 * WINO4_H1_STRIDE;
+                constexpr int n = wino4_reads_before(p + LEAD + 1) - wino4_reads_before(p_rd + LEAD + 1) + 2 * (5 - st);
+                asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(xs2[st - 3]), "+v"(xa[st - 3]) : "n"(n > 15 ? 15 : n));
+                xs0[st - 3] = xs2[st - 3][0];
+                xs1[st - 3] = xs2[st - 3][1];
               }
+              if constexpr (S_ROW && st < 6) wino4_in6_written_out(xs0[st - 3], xa[st - 3][0], xa[st - 3][1], xa[st - 3][2], xa[st - 3][3], xs1[st - 3], xr[st - 3]);
+              else xf_step(raw_next2, v_next, st);
             }
-          }
-          if constexpr (!(WINO4_ABL & 1) && p >= WINO4_H2_START && p < WINO4_H2_START + (10 - WINO4_H1_STEPS) * WINO4_H2_STRIDE && (p - WINO4_H2_START) % WINO4_H2_STRIDE == 0)
-            if (!is_xf()) xf_step(raw_next2, v_next, WINO4_H1_STEPS + (p - WINO4_H2_START) / WINO4_H2_STRIDE);
+          };
+          auto h2 = [&](auto stc) __attribute__((always_inline)) {
+            constexpr int st = decltype(stc)::value;
+            if constexpr (S_LDS && st >= 7) xf_store3(st - 7);
+            else xf_step(raw_next2, v_next, st);
+          };
+          constexpr int st1 = (p - WINO4_H1_START) / WINO4_H1_STRIDE, st2 = WINO4_H1_STEPS + (p - WINO4_H2_START) / WINO4_H2_STRIDE;
+          // (one test per step, also in the slot that holds a step of either half, p = 28: as if / else the join gets the values of both
+          // halves as phis, and the compiler pays for them with twelve 64-bit moves per item -- built for ITEM = 3, read in the listing, taken out)
+          if constexpr (h1_slot) { if (is_xf()) h1(std::integral_constant<int, st1>{}); }
+          if constexpr (h2_slot) { if (!is_xf()) h2(std::integral_constant<int, st2>{}); }
           __builtin_amdgcn_sched_barrier(0);
         };
         wino4_for_each(read_slot, std::make_integer_sequence<int, LEAD>{});
@@ -585,8 +736,20 @@ __global__ __launch_bounds__(256 * TB, TB) void conv_wino4_kernel(const ConvArgs
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-      advance(cu);
-      advance(cr);
+      if constexpr (S_PTR) {
+        advance3(cu, wp3, U_TAIL3, true);
+        advance3(cr, rp3, raw_step3, false);
+        lds_u3 = lds_u_swap3 - lds_u3;
+        lds_raw3 = lds_raw_swap3 - lds_raw3;
+      } else {
+        advance(cu);
+        advance(cr);
+      }
+      if constexpr (S_ROLE) xf3 ^= 1;
+      if constexpr (S_LDS) {
+        ua3 = ua_swap3 - ua3;
+        va3 = va_swap3 - va3;
+      }
       ++k;
 #ifdef WINO_STAMPS
       { const unsigned long long dt = __builtin_amdgcn_s_memtime() - ts2; st_mfma += dt; if (XF) st_mfma_xf += dt; }

@@ -101,7 +101,7 @@ struct Op {
   bool wino = false;       // FP32 engines: this 3x3 layer runs a Winograd kernel: F(2x2,3x3) (conv_wino2.hip.h) unless wino4 is set
   bool wino_narrow = false;   // ... with 32 instead of 64 output channels per workgroup (layers whose 64-channel tiles would leave CUs idle)
   bool wino4 = false;      // ... the F(4x4,3x3) form (conv_wino4.hip.h: 9/16 of F(2x2)'s matrix work; pooled layers with even H and W, unpooled layers of any size)
-  int wino4_item = 2;      // ... which item (conv_wino4.hip.h, ITEM; "wino4_item"): 2 counted operand waits + LDS-DMA from a scalar base, 1 counted operand waits only, 0 the compiler's waits (A/B runs)
+  int wino4_item = 3;      // ... which item (conv_wino4.hip.h, ITEM; "wino4_item"): 3 = 2 with its scalar and no-result instructions cut, 2 counted operand waits + LDS-DMA from a scalar base, 1 counted operand waits only, 0 the compiler's waits (A/B runs)
   bool dominant = false;   // the op with the most FLOPs: launched under its own kernel name (TAG = 1)
   float *d_w = nullptr, *d_b = nullptr, *d_bn_scale = nullptr, *d_bn_shift = nullptr;
   int *d_sched = nullptr;      // Winograd layers (8-wave form): {8 band counters, workgroups done}, zero between launches (SPVO_WINO_DYNAMIC=0: none)

@@ -24,7 +24,7 @@ int prepare_conv_f32(spvo_ctx *c, unsigned i, const float *w, const float *b) {
   // CUs): F(4x4,3x3) (conv_wino4.hip.h: 36 multiplies per 4x4 outputs instead of F(2x2)'s 64) where the layer has that many
   // 16 x 32 tiles; else F(2x2,3x3) (conv_wino2.hip.h) on 8 x 32 tiles of 64 output channels; else its narrow form (32 output
   // channels per workgroup: conv4a / conv4b at 45x147 are 120 wide tiles on 256 CUs); else the direct kernel.
-  // Diagnostic switches (spvo_set_tuning): "winograd" = 0 direct kernels only, "wino4" = 0 F(2x2) only, "wino4_item" = 1 / 0 the F(4x4) item with a vector address for its LDS-DMA / also without counted operand waits, "wino_narrow" = 0,
+  // Diagnostic switches (spvo_set_tuning): "winograd" = 0 direct kernels only, "wino4" = 0 F(2x2) only, "wino4_item" = 2 / 1 / 0 the F(4x4) item before its scalar and no-result instructions were cut / with a vector address for its LDS-DMA / also without counted operand waits, "wino_narrow" = 0,
   // "winograd_min_tiles" / "wino4_min_tiles" the thresholds, "wino_dynamic" = 0 static tile assignment.
   {
     const bool wino_on = tuning("winograd", 1) != 0;
@@ -42,7 +42,7 @@ int prepare_conv_f32(spvo_ctx *c, unsigned i, const float *w, const float *b) {
     const long t4 = (long)((ti.W + Wino4Tile::TW - 1) / Wino4Tile::TW) * ((ti.H + Wino4Tile::TH - 1) / Wino4Tile::TH) * op.co_tiles * c->cfg.max_batch;
     if (t4 >= tuning("wino4_min_tiles", 3 * c->num_cus / 4)) {
       op.wino4 = true;
-      op.wino4_item = (int)tuning("wino4_item", 2);   // conv_wino4.hip.h, ITEM: 2 the default; 1 and 0 the two earlier items, for A/B runs
+      op.wino4_item = (int)tuning("wino4_item", 3);   // conv_wino4.hip.h, ITEM: 3 the default; 2, 1 and 0 the three earlier items, for A/B runs
       op.ck = Wino4Tile::CK;
       op.n_chunks = op.cin / Wino4Tile::CK;
       if ((rc = upload(c, &op.d_w, pack_conv_weights_wino4(w, b, op.cout, op.cin)))) return rc;
@@ -138,7 +138,7 @@ int launch_conv_wino_sel(spvo_ctx *c, const ConvArgs &args, bool relu, bool pool
 }
 
 // conv_wino4.hip.h: Winograd F(4x4,3x3), 16 x 32 output tiles, 8 waves, one workgroup per CU
-// (ITEM: 2 the item with counted operand waits and LDS-DMA from a scalar base, 1 counted operand waits only, 0 the compiler's waits -- spvo_set_tuning
+// (ITEM: 3 the item of 2 with its scalar and no-result instructions cut, 2 counted operand waits and LDS-DMA from a scalar base, 1 counted operand waits only, 0 the compiler's waits -- spvo_set_tuning
 // "wino4_item", read when the engine is loaded)
 template <bool POOL, bool RELU, int TAG, int ITEM>
 int launch_conv_wino4_instance(spvo_ctx *c, const ConvArgs &args, hipStream_t stream) {
@@ -172,7 +172,8 @@ int launch_conv_wino4(spvo_ctx *c, const ConvArgs &a, int batch, bool relu, bool
   args.tiles_y = (a.H + Wino4Tile::TH - 1) / Wino4Tile::TH;
   args.batch = batch;
   if (pool && ((a.H | a.W) & 1)) return fail(c, SPVO_ERR_INVALID, "F(4x4) kernel: pooled layer with odd size");   // (the plan loader keeps those on the other kernels)
-  if (item >= 2) return launch_conv_wino4_sel<2>(c, args, relu, pool, dominant, stream);
+  if (item >= 3) return launch_conv_wino4_sel<3>(c, args, relu, pool, dominant, stream);
+  if (item == 2) return launch_conv_wino4_sel<2>(c, args, relu, pool, dominant, stream);
   return item == 1 ? launch_conv_wino4_sel<1>(c, args, relu, pool, dominant, stream) : launch_conv_wino4_sel<0>(c, args, relu, pool, dominant, stream);
 }
 

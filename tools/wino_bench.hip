@@ -18,7 +18,7 @@
 #define WINO4_TB 2   // -DWINO4_TB=1: the 4-wave form (8 x 32 outputs per workgroup)
 #endif
 #ifndef WINO4_ITEM
-#define WINO4_ITEM 2   // -DWINO4_ITEM=1: LDS-DMA with a vector address; 0: also the compiler's operand waits (the library's "wino4_item" switch)
+#define WINO4_ITEM 3   // -DWINO4_ITEM=2: the item before its scalar and no-result instructions were cut; 1: also LDS-DMA with a vector address; 0: also the compiler's operand waits (the library's "wino4_item" switch)
 #endif
 #define KERNEL(P, R, T, O) conv_wino4_kernel<P, R, T, WINO4_TB, WINO4_ITEM>
 #define PACK pack_conv_weights_wino4
@@ -127,11 +127,14 @@ int main(int argc, char **argv) {
   CK(hipEventElapsedTime(&ms, e0, e1));
   const double us = ms * 1e3 / reps, fl = 2.0 * batch * H * W * (double)cout * cin * 9;
 #if defined(WINO4)
-  // WINO_ITEM_AB=<rounds>: the three items of the F(4x4) kernel in ONE process, alternately, `reps` launches per block: the same-box,
+  // WINO_ITEM_AB=<rounds>: the items of the F(4x4) kernel in ONE process, alternately, `reps` launches per block: the same-box,
   // same-clock comparison (separate processes differ by ~1 % among themselves).  Afterwards one launch of each item into a cleared output:
   // all must agree bit for bit.
   if (getenv("WINO_ITEM_AB")) {
-#define WINO_AB_ITEMS(X) X(0) X(1) X(2)
+#ifndef WINO_AB_ITEMS   // which instances alternate; a measurement build names others, e.g. the steps of item 3 one on top of the other:
+                        // -D'WINO_AB_ITEMS(X)=X(2) X(17) X(19) X(23) X(31) X(3)'  (16 + mask: conv_wino4.hip.h, WINO4_ITEM3_STEPS)
+#define WINO_AB_ITEMS(X) X(0) X(1) X(2) X(3)
+#endif
     std::vector<int> items;
 #define WINO_AB_LIST(I) items.push_back(I);
     WINO_AB_ITEMS(WINO_AB_LIST)
