@@ -311,7 +311,9 @@ int spvo_orb_describe_octaves(spvo_ctx *ctx, const uint8_t *img /* or NULL */, i
  *   SPVO_ERR_STATE     a spvo_detect*_submit is in flight
  * One-off cost: the point table (64 scales x 1024 rotations x 60 points x 3 floats = 47 MB) is built once per process on the host
  * and uploaded to a context on its first BRISK call (NOTES.md, "BRISK descriptor extractor": 61 ms and 8 ms measured); the
- * Shi-Tomasi / FAST keypoints of this front end (sizes 5 and 7) read only its 737 KB scale-0 slice. */
+ * Shi-Tomasi / FAST keypoints of this front end (sizes 5 and 7) read only its 737 KB scale-0 slice.  The extractor's chain also runs
+ * behind a detector's list on the device: spvo_classic_detect's BRISK kinds, spvo_brisk_detect_pair, spvo_akaze_brisk_pair,
+ * spvo_orb_brisk_pair and spvo_sift_brisk_pair. */
 int spvo_brisk_describe(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, size_t stride, const float *xy /* [n][2] */,
                         const float *size /* [n] */, int n, int32_t *kept /* [n] */, float *angle /* [n] degrees, may be NULL */,
                         uint8_t *desc /* [n][64] */, int32_t *values0 /* [n][60], may be NULL: test hook */, int *n_kept);
@@ -330,7 +332,7 @@ int spvo_brisk_tables(int scale, float *points /* [1024][60][3] x, y, sigma; may
  * are known, as restated by tests/sift_ref.py (its header lists every choice).  The pyramid, the extrema and the refinement reproduce
  * that restatement bit for bit; orientation and descriptor use exp / atan2 and agree with it to rounding level.  Keypoints come in
  * OpenCV's total order (x, y, size, angle, response, octave ascending), records equal in (x, y, size, angle) once (the ordering runs on
- * the host, after one copy of the records; spvo_sift_detect_pair, below, orders on the device).  `n` receives their number, of which min(n, cap) rows are written; strided input is accepted.
+ * the host, after one copy of the records; spvo_sift_detect_pair, below, orders on the device, and spvo_sift_brisk_pair runs the detector without its rows in front of the BRISK extractor).  `n` receives their number, of which min(n, cap) rows are written; strided input is accepted.
  *   SPVO_ERR_INVALID   an image smaller than 6 x 6 (the first octave of the doubled image needs an interior inside its 5-pixel border)
  *   SPVO_ERR_STATE     a spvo_detect*_submit is in flight */
 typedef struct {
@@ -762,7 +764,42 @@ int spvo_orb_brisk_pair(spvo_ctx *ctx, const uint8_t *img_l, const uint8_t *img_
 int spvo_orb_sift_pair(spvo_ctx *ctx, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride,
                        int nfeatures, int slot_l, int slot_r, int slot_capacity,
                        spvo_sift_features *out_l, spvo_sift_features *out_r);
-/* The link of the two calls above -- compaction by keep flags, the reduced pyramid for octaves 0 .. max_octave, the describe launch on
+/* The SIFT detector in front of the BRISK extractor, pair-resident in the ring of ten BINARY slots (64-byte rows, spvo_brisk_detect_pair's
+ * protocol: spvo_match_hamming_slots, spvo_match_l2_u8_slots, spvo_classic_slot_rows and spvo_set_prematch work on the slots unchanged, any
+ * filled slot of 64-byte rows is the temporal partner, a larger slot_capacity than any before re-allocates).  Per image, left first, on the
+ * solver's stream and without a host round trip: the staged image becomes the context's resident u8 image; the SIFT pyramid is built from
+ * THAT image; candidates, refinement and the orientation peaks run as in spvo_sift_detect but without the 128-float rows (one keypoint per
+ * peak is kept: OpenCV's detector emits them and BRISK describes each); the raw rows are ordered on the device as in
+ * spvo_sift_detect_pair; one kernel presents the ordered list as 24-byte records {x, y, size, angle, response, octave}; and the BRISK
+ * extractor's chain reads them where they lie: the integral image, the border rule at every record's own scale index as one
+ * order-preserving compaction, the rows with the count read on the device, the finish launch.
+ *   Byte equality: per image the host receives, byte for byte in every field and row, what spvo_sift_detect(img) followed by
+ *   spvo_brisk_describe(img, its x, y, size) returns -- the detector's records [kept] with `angle` replaced by the extractor's degrees, the
+ *   64-byte rows in the detector's order.  The slot's own records hold (x, y, that angle, response, octave).
+ *   The size: on the device it comes from a double pow, on the host from spvo_sift_detect's own function.  Behind the wait the host
+ *   rebuilds every final row's record from the mirrored {candidate, offsets, angle} and compares the sizes bit for bit.  They are expected
+ *   to agree always; an image in which one differs gets the host's records uploaded and the extractor's chain once more (a second wait).
+ *   spvo_set_tuning("sift_brisk_recheck", 1) forces that second pass for both images (diagnostic).
+ * The candidate and raw-row lists grow to what was counted and the pair runs again when they overflow (spvo_sift_detect_pair's rule: a
+ * second wait).  An image without a keypoint fills its slot with 0 rows: SPVO_OK.  Afterwards the resident u8 image is the RIGHT image
+ * (spvo_brisk_describe(NULL), spvo_sift_describe(NULL) work on it), the right image's SIFT pyramid is resident (spvo_sift_debug_level), the
+ * AKAZE scale space's claim has ended and spvo_brisk_detect_debug_layer answers SPVO_ERR_STATE.
+ *   SPVO_ERR_INVALID   nothing is written or touched: NULL arguments, bad or equal slots, slot_capacity outside 1 .. 32768, cap < 0, an
+ *                      image spvo_sift_detect refuses (under 6 x 6) or spvo_brisk_describe refuses (rows * cols * 255 >= 2^31)
+ *   SPVO_ERR_STATE     a spvo_detect*_submit is in flight (outputs and slots stay as they were)
+ *   SPVO_ERR_CAPACITY  an image yields more rows than slot_capacity: out_*->n report both counts, both slots are left unfilled, nothing
+ *                      is truncated */
+int spvo_sift_brisk_pair(spvo_ctx *ctx, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride,
+                         int slot_l, int slot_r, int slot_capacity,
+                         spvo_brisk_features *out_l, spvo_brisk_features *out_r);   /* desc [cap][64] */
+/* spvo_sift_brisk_pair's chain of ONE image up to the records the BRISK extractor's chain reads (test hook): the image becomes the resident
+ * u8 image, `rec` receives min(n, cap) records in the detector's order (`angle` is still the detector's), `n` their number.  describe != 0
+ * runs the describing form of the orientation kernel in the other's place: the records must not depend on it.
+ *   SPVO_ERR_INVALID as spvo_sift_detect; SPVO_ERR_CAPACITY: the lists overflowed (they hold at least 8192 rows); SPVO_ERR_STATE: a
+ *   spvo_detect*_submit is in flight */
+int spvo_sift_records_debug(spvo_ctx *ctx, const uint8_t *img, int rows, int cols, size_t stride, int describe,
+                            spvo_sift_keypoint *rec, int cap, int *n);
+/* The link of the ORB / BRISK / AKAZE + SIFT calls above -- compaction by keep flags, the reduced pyramid for octaves 0 .. max_octave, the describe launch on
  * the fixed grid with the count read on the device -- on a caller's list against the u8 image already resident, of shape rows x cols
  * (test hook: lists no image gives).  No detector runs, no slot is touched, the image stays resident.  keep = NULL: all records take
  * part; `kept` names the original indices, and the rows equal spvo_sift_describe(img = NULL) on the kept records.

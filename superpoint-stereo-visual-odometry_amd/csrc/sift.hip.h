@@ -283,6 +283,9 @@ __device__ __forceinline__ void sift_desc_store(float d0, float d1, float *__res
 // Orientation and descriptor of every surviving candidate: one wave (= one workgroup) per candidate, lanes over the patch.  A peak of the
 // smoothed 36-bin histogram is one keypoint: row `slot` (counter[1], which keeps counting beyond kp_cap) of kp = {candidate, angle bits}
 // and of desc (128 integers 0..255 as float).
+// DESCRIBE = false (spvo_sift_brisk_pair: another extractor describes the keypoints): histogram, peaks and the raw rows {candidate, angle
+// bits} as above -- one row per peak -- without the per-peak patch loop and the row store; `desc` is not touched.
+template <bool DESCRIBE = true>
 __global__ __launch_bounds__(64) void sift_describe_kernel(SiftPyr P, const int4 *__restrict__ pos, const float4 *__restrict__ off, int *__restrict__ counter, int cap,
                                                            int2 *__restrict__ kp, float *__restrict__ desc, int kp_cap) {
   __shared__ float hist[128 * SIFT_COLS];
@@ -359,6 +362,10 @@ __global__ __launch_bounds__(64) void sift_describe_kernel(SiftPyr P, const int4
       b = b < 0.f ? 36.f + b : (b >= 36.f ? b - 36.f : b);
       float angle = 360.f - 10.f * b;
       if (fabsf(angle - 360.f) < 1.1920929e-7f) angle = 0.f;
+      if constexpr (!DESCRIBE) {
+        if (lane == 0) kp[slot] = make_int2(i, __float_as_int(angle));
+        continue;
+      }
       const int px = __float2int_rn(add_rn((float)c, f.z)), py = __float2int_rn(add_rn((float)r, f.y));
       const SiftPatch pt = sift_patch(scl, angle, px, py, h, w);
       const int radius = pt.radius, side = 2 * radius + 1, total = side * side;
@@ -697,6 +704,39 @@ __global__ __launch_bounds__(256) void sift_gather_kernel(const int *__restrict_
       s_src[r] = src;
       h_src[r] = src;
     }
+  }
+}
+
+// spvo_sift_brisk_pair, in sift_gather_kernel's place: the ordered list in the form brisk_pair_chain_enqueue reads a detector's list (SiftKey
+// is BriskDetKeypoint's layout) --
+//   rec[r]  = keys[order[r]], the final row r's key: here its `size` picks the BRISK scale index and lands in the record, so the host checks it
+//   keep[r] = 1
+//   cnt     = a BRISK detector's counter block: [1] = the final rows (cnt[2] as well), [3] = the SIFT lists overflowed (candidates or raw rows
+//             counted above list_cap: the call grows the lists and runs again)
+// and to the host's pinned mirrors every final row's source with the bits of the size used in pad[0], and h_n = {final rows, candidates
+// counted, raw rows counted}.  order / n_kept come from sift_unique_kernel: n <= min(raw rows, list_cap).
+__global__ __launch_bounds__(256) void sift_records_kernel(const int *__restrict__ order, const int *__restrict__ n_kept, const int *__restrict__ counter, int list_cap,
+                                                           const SiftKey *__restrict__ keys, const int2 *__restrict__ kp, const int4 *__restrict__ pos,
+                                                           const float4 *__restrict__ off, BriskDetKeypoint *__restrict__ rec, int *__restrict__ keep, int *__restrict__ cnt,
+                                                           SiftSrc *__restrict__ h_src, int *__restrict__ h_n) {
+  const int n = min(max(*n_kept, 0), list_cap);
+  const int tid = blockIdx.x * 256 + threadIdx.x, nth = gridDim.x * 256;
+  if (tid == 0) {
+    cnt[0] = 0; cnt[1] = n; cnt[2] = n; cnt[3] = counter[0] > list_cap || counter[1] > list_cap;
+    h_n[0] = n; h_n[1] = counter[0]; h_n[2] = counter[1];
+  }
+  for (int r = tid; r < n; r += nth) {
+    const int raw = order[r];
+    const SiftKey k = keys[raw];
+    BriskDetKeypoint d;
+    d.x = k.x; d.y = k.y; d.size = k.size; d.angle = k.angle; d.response = k.response; d.octave = k.octave;
+    rec[r] = d;
+    keep[r] = 1;
+    const int2 row = kp[raw];
+    SiftSrc src;
+    src.pos = pos[row.x]; src.off = off[row.x]; src.angle = __int_as_float(row.y);
+    src.pad[0] = __float_as_int(k.size); src.pad[1] = src.pad[2] = 0;
+    h_src[r] = src;
   }
 }
 

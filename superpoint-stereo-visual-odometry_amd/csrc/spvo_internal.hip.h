@@ -568,6 +568,15 @@ struct spvo_ctx {
     // sift_link_compact_kernel keeps, `lnk_cap` of them, its counts {kept, the hook's list length}, and the hook's keep flags
     int lnk_cap = 0;
     DevBuf<int> lnk_kept, lnk_cnt, lnk_keep;
+    // spvo_sift_brisk_pair (sift_records_kernel, sift.hip.h): the ordered list as the BRISK extractor's chain reads a detector's list --
+    // 24-byte records, keep flags, the chain's compacted records, `brk_cap` of each; a counter block per image -- and the pinned mirrors
+    // of every final row's source, [2][brk_cap], with their counts [2][4] {final rows, candidates counted, raw rows counted}
+    int brk_cap = 0;
+    DevBuf<BriskDetKeypoint> brk_rec, brk_crec;
+    DevBuf<int> brk_keep, brk_cnt;
+    PinBuf<SiftSrc> hb_src;
+    PinBuf<int> hb_n;
+    std::vector<BriskDetKeypoint> hb_rec;   // the host's records of an image whose device sizes it did not confirm (the second pass)
   } sift;
   // Hamming matcher (classic front end's binary descriptors): rows padded to 16 words
   int ham_cap = 0;

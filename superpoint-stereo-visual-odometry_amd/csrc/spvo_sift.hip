@@ -14,7 +14,10 @@
 // in the detectors' objects hand it their chain as three functions): the extractor's pyramid for octaves 0 .. the detector's highest,
 // reduced to the levels a layer-0 record reads, and the describe kernel on the records where they lie (SiftLinkIO).  spvo_sift_link_debug
 // runs that link on a caller's list.
-// All three pair calls are a PairCall<SiftPairFamily> (pair_call.hip.h: staging, slots, temporal partner, prematch, the one wait, the
+// spvo_sift_brisk_pair is the detector in front of the BRISK extractor's chain (spvo_brisk.hip: brisk_pair_chain_enqueue), a
+// PairCall<BinPairFamily> into the binary slots: the pyramid of the shared resident image, the orientation-only instantiation of
+// sift_describe_kernel, the ordering, and sift_records_kernel, which presents the ordered list as a detector's list.
+// The three SIFT-slot pair calls are a PairCall<SiftPairFamily> (pair_call.hip.h: staging, slots, temporal partner, prematch, the one wait, the
 // capacity rule) around their own allocations and chains.
 #include "spvo_internal.hip.h"
 #include "pair_call.hip.h"
@@ -116,8 +119,9 @@ int sift_enqueue_pyramid(spvo_ctx *c, const uint8_t *src, int rows, int cols, co
   return SPVO_OK;
 }
 
-// extrema -> refinement -> orientation + descriptor, behind the pyramid
-int sift_enqueue_features(spvo_ctx *c, const SiftPyr &P) {
+// extrema -> refinement -> orientation + descriptor, behind the pyramid.  describe = false: the orientation-only instantiation -- the raw
+// rows {candidate, angle bits} without the 128-float rows (spvo_sift_brisk_pair)
+int sift_enqueue_features(spvo_ctx *c, const SiftPyr &P, bool describe = true) {
   auto &s = c->sift;
   hipStream_t st = c->stream2;
   HIP_TRY(c, hipMemsetAsync(s.counters, 0, 4 * sizeof(int), st));
@@ -128,8 +132,12 @@ int sift_enqueue_features(spvo_ctx *c, const SiftPyr &P) {
     hipLaunchKernelGGL(sift_extrema_kernel, grid, dim3(256), 0, st, (const float *)(P.pyr + P.d_off[o]), h, w, o, s.cand_pos, s.cand_cap, s.counters);
   }
   hipLaunchKernelGGL(sift_refine_kernel, dim3(std::min((s.cand_cap + 255) / 256, 1024)), dim3(256), 0, st, P, s.cand_pos, s.cand_off, (const int *)s.counters, s.cand_cap);
-  hipLaunchKernelGGL(sift_describe_kernel, dim3(std::min(s.cand_cap, 8192)), dim3(64), 0, st, P, (const int4 *)s.cand_pos, (const float4 *)s.cand_off, s.counters, s.cand_cap, s.kp,
-                     s.desc, s.cand_cap);
+  if (describe)
+    hipLaunchKernelGGL(sift_describe_kernel<true>, dim3(std::min(s.cand_cap, 8192)), dim3(64), 0, st, P, (const int4 *)s.cand_pos, (const float4 *)s.cand_off, s.counters, s.cand_cap, s.kp,
+                       s.desc, s.cand_cap);
+  else
+    hipLaunchKernelGGL(sift_describe_kernel<false>, dim3(std::min(s.cand_cap, 8192)), dim3(64), 0, st, P, (const int4 *)s.cand_pos, (const float4 *)s.cand_off, s.counters, s.cand_cap, s.kp,
+                       s.desc, s.cand_cap);
   HIP_TRY(c, hipGetLastError());
   return SPVO_OK;
 }
@@ -183,6 +191,32 @@ int sift_enqueue_order(spvo_ctx *c, SiftSlot &slot, int k) {
   hipLaunchKernelGGL(sift_gather_kernel, dim3(64), dim3(256), 0, st, (const int *)s.order, (const int *)s.ord_n, (const int *)s.counters, (const int2 *)s.kp, (const int4 *)s.cand_pos,
                      (const float4 *)s.cand_off, (const float *)s.desc, s.slot_cap, slot.d_desc, slot.d_sqn, slot.d_src, slot.d_n, s.hm_desc + (size_t)k * s.slot_cap * 128,
                      s.h_src + (size_t)k * s.slot_cap, s.h_n + 4 * k);
+  HIP_TRY(c, hipGetLastError());
+  return SPVO_OK;
+}
+
+// spvo_sift_brisk_pair's buffers for lists of `n` rows
+int sift_brisk_ensure(spvo_ctx *c, int n) {
+  auto &s = c->sift;
+  if (!s.brk_cnt)
+    if (int rc = grow(c, wait_for_nothing(), {zeroed(s.brk_cnt, 2 * 4), plain(s.hb_n, 2 * 4)})) return rc;
+  if (n <= s.brk_cap) return SPVO_OK;
+  s.brk_cap = 0;
+  if (int rc = grow(c, wait_for(c->stream2), {plain(s.brk_rec, (size_t)n), plain(s.brk_crec, (size_t)n), plain(s.brk_keep, (size_t)n), plain(s.hb_src, (size_t)2 * n)})) return rc;
+  s.brk_cap = n;
+  return SPVO_OK;
+}
+
+// the raw rows of the image just given its orientations -> the ordered list as a detector's list in brk_rec / brk_keep / brk_cnt + 4 k and
+// the sources' mirrors of image k, behind sift_enqueue_features; list_cap = s.cand_cap <= s.brk_cap
+int sift_enqueue_records(spvo_ctx *c, int k) {
+  auto &s = c->sift;
+  hipStream_t st = c->stream2;
+  hipLaunchKernelGGL(sift_key_kernel, dim3(std::min((s.cand_cap + 255) / 256, 256)), dim3(256), 0, st, (const int4 *)s.cand_pos, (const float4 *)s.cand_off, (const int2 *)s.kp,
+                     (const int *)s.counters, s.cand_cap, s.keys);
+  if (int rc = sift_enqueue_sort(c, s.counters + 1, s.cand_cap)) return rc;
+  hipLaunchKernelGGL(sift_records_kernel, dim3(32), dim3(256), 0, st, (const int *)s.order, (const int *)s.ord_n, (const int *)s.counters, s.cand_cap, (const SiftKey *)s.keys,
+                     (const int2 *)s.kp, (const int4 *)s.cand_pos, (const float4 *)s.cand_off, s.brk_rec, s.brk_keep, s.brk_cnt + 4 * k, s.hb_src + (size_t)k * s.brk_cap, s.hb_n + 4 * k);
   HIP_TRY(c, hipGetLastError());
   return SPVO_OK;
 }
@@ -533,6 +567,98 @@ int spvo_sift_detect_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_
   return SPVO_OK;
 }
 
+// SIFT keypoints with BRISK descriptors, pair-resident in the BINARY slots (64-byte rows): per image what spvo_sift_detect(img) followed by
+// spvo_brisk_describe on its x, y, size hands out, byte for byte.  spvo_brisk_detect_pair's protocol (PairCall<BinPairFamily>); the chain of
+// an image is staged image -> resident image (spvo_ctx::cls) -> the SIFT pyramid of THAT image -> candidates and orientations without the
+// SIFT rows -> key / rank / unique -> sift_records_kernel -> brisk_pair_chain_enqueue.  The overflow rule is spvo_sift_detect_pair's.
+// The size: sift_key_kernel's `size` is a sort key elsewhere; here it picks the BRISK scale index and lands in the record, so behind the
+// wait the host rebuilds every final row's record with sift_record from the mirrored sources and compares the sizes bit for bit.  An
+// image with a size that differs (none is expected, ever) gets the host's records uploaded and the extractor's chain once more: a second
+// wait.  Tuning "sift_brisk_recheck" = 1 (diagnostic) forces that pass for both images.
+int spvo_sift_brisk_pair(spvo_ctx *c, const uint8_t *img_l, const uint8_t *img_r, int rows, int cols, size_t stride, int slot_l, int slot_r, int slot_capacity,
+                         spvo_brisk_features *out_l, spvo_brisk_features *out_r) {
+  if (!c || !img_l || !img_r || !out_l || !out_r || rows <= 0 || cols <= 0 || stride < (size_t)cols) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  static_assert(sizeof(spvo_brisk_keypoint) == sizeof(BriskDetKeypoint) && sizeof(SiftKey) == sizeof(BriskDetKeypoint), "record layout");
+  const char *who = "spvo_sift_brisk_pair";
+  const int cap = slot_capacity, row_bytes = 64;
+  PairCall<BinPairFamily> pc(c, who, BinPairFamily{row_bytes}, pair_out(out_l), pair_out(out_r));
+  int rc;
+  if ((rc = pc.check(slot_l, slot_r)) || (rc = pc.check_capacity(cap))) return rc;
+  if (cap > 32768) return fail(c, SPVO_ERR_INVALID, "%s: slot_capacity must be 1 .. 32768", who);
+  if ((rc = sift_check_image(c, who, rows, cols)) || (rc = brisk_check_image(c, who, rows, cols)) || (rc = pc.open())) return rc;
+  c->akaze.valid = false;   // as spvo_sift_detect_pair: the AKAZE scale space's claim ends
+  auto &s = c->sift;
+  auto &bb = c->bin;
+  hipStream_t st = c->stream2;
+  SiftPyr P{};
+  const size_t pyr_floats = sift_plan(rows, cols, P), px = (size_t)rows * cols;
+  s.rows = s.cols = 0;   // nothing resident until a pyramid is enqueued
+  const int cand_cap = std::max(s.cand_cap, std::max(8192, (int)((size_t)4 * rows * cols / 16)));
+  // every allocation and the BRISK point table before the first launch of the chain
+  if ((rc = classic_slots_ensure(c, cap, px)) || (rc = classic_image_ensure(c, rows, cols)) || (rc = brisk_chain_ensure(c, rows, cols, cap)) ||
+      (rc = sift_ensure(c, rows, cols, pyr_floats, cand_cap)) || (rc = sift_order_ensure(c, s.cand_cap)) || (rc = sift_brisk_ensure(c, std::max(s.cand_cap, cap))))
+    return rc;
+  P.pyr = s.pyr;
+  if ((rc = pc.load(img_l, img_r, rows, cols, stride))) return rc;
+  // the extractor's chain of image k on the list in brk_rec / brk_cnt + 4 k, against the resident image
+  const auto extractor = [&](int k) -> int {
+    const BinarySlot &t = bb.slots[pc.slots[k]];
+    const ChainOut out{bb.d_cnt + k * BIN_COUNTER_INTS, bb.d_kresp, t.d_kp, t.d_desc, t.d_n, bb.h_n + 4 * k, nullptr, bb.h_desc + (size_t)k * cap * row_bytes};
+    return brisk_pair_chain_enqueue(c, rows, cols, cap, s.brk_rec, s.brk_keep, s.brk_cnt + 4 * k, s.brk_cap, s.brk_crec, out, bb.h_bkp + (size_t)k * cap);
+  };
+  for (int attempt = 0;; ++attempt) {
+    for (int k = 0; k < 2; ++k) {   // left chain, then the right one: the resident image, the pyramid and the lists are reused in stream order
+      s.rows = s.cols = 0;
+      if ((rc = classic_image_from_staged(c, pc.image(k), rows, cols)) || (rc = sift_enqueue_pyramid(c, c->cls.im, rows, cols, P))) return rc;
+      s.plan = P; s.rows = rows; s.cols = cols; s.gauss_only = false;
+      if ((rc = sift_enqueue_features(c, P, false)) || (rc = sift_enqueue_records(c, k)) || (rc = extractor(k))) return rc;
+    }
+    if ((rc = pc.submit())) return rc;
+    int most = 0;
+    for (int k = 0; k < 2; ++k) most = std::max(most, std::max(s.hb_n[4 * k + 1], s.hb_n[4 * k + 2]));
+    if (most <= s.cand_cap) break;
+    // more candidates (or raw rows) than the lists hold: grow them to what was counted and run the pair again (a second wait)
+    if (attempt >= 2) {
+      pc.count(0); pc.count(1);
+      return fail(c, SPVO_ERR_CAPACITY, "%s: %d candidates / keypoints do not fit", who, most);
+    }
+    HIP_TRY(c, hipStreamSynchronize(st));   // (the prematches of the attempt read the slots on this stream)
+    if ((rc = sift_ensure(c, rows, cols, pyr_floats, most + 1024)) || (rc = sift_order_ensure(c, s.cand_cap)) || (rc = sift_brisk_ensure(c, std::max(s.cand_cap, cap)))) return rc;
+  }
+  // the sizes the device used against sift_record's
+  const bool force = tuning("sift_brisk_recheck", 0) == 1;
+  bool redo[2] = {force, force};
+  for (int k = 0; k < 2 && !force; ++k) {
+    const SiftSrc *src = s.hb_src + (size_t)k * s.brk_cap;
+    for (int i = 0, n = std::min(std::max(s.hb_n[4 * k], 0), s.brk_cap); i < n && !redo[k]; ++i)
+      redo[k] = __builtin_bit_cast(int, sift_record(src[i].pos, src[i].off, __builtin_bit_cast(int, src[i].angle)).size) != src[i].pad[0];
+  }
+  if (redo[0] || redo[1]) {
+    const int n_rows[2] = {std::min(std::max(s.hb_n[0], 0), s.brk_cap), std::min(std::max(s.hb_n[4], 0), s.brk_cap)};
+    s.hb_rec.resize((size_t)n_rows[0] + n_rows[1] + 1);   // (each image's records in a part of their own: a copy may read them until the wait)
+    for (int k = 0; k < 2; ++k) {   // (the right image is staged again behind a left pass: it is the resident one afterwards)
+      if (!redo[k] && !(k == 1 && redo[0])) continue;
+      if ((rc = classic_image_from_staged(c, pc.image(k), rows, cols))) return rc;
+      if (!redo[k]) continue;
+      const SiftSrc *src = s.hb_src + (size_t)k * s.brk_cap;
+      BriskDetKeypoint *h_rec = s.hb_rec.data() + (k ? n_rows[0] : 0);
+      const int n = n_rows[k];
+      for (int i = 0; i < n; ++i) {
+        const spvo_sift_keypoint r = sift_record(src[i].pos, src[i].off, __builtin_bit_cast(int, src[i].angle));
+        h_rec[i] = BriskDetKeypoint{r.x, r.y, r.size, r.angle, r.response, r.octave};
+      }
+      if (n > 0) HIP_TRY(c, hipMemcpyAsync(s.brk_rec, h_rec, (size_t)n * sizeof(BriskDetKeypoint), hipMemcpyHostToDevice, st));
+      if ((rc = extractor(k))) return rc;
+    }
+    if ((rc = pc.submit())) return rc;   // the second wait
+  }
+  pc.count(0); pc.count(1);
+  if (bb.h_n[1] || bb.h_n[5]) return fail(c, SPVO_ERR_STATE, "%s: the lists overflowed although they were grown to what was counted", who);
+  const PairMirror mirrors[2] = {{bb.h_bkp, sizeof(BriskDetKeypoint), bb.h_desc, (size_t)row_bytes},
+                                 {bb.h_bkp + cap, sizeof(BriskDetKeypoint), bb.h_desc + (size_t)cap * row_bytes, (size_t)row_bytes}};
+  return pc.commit(mirrors);
+}
+
 // Shi-Tomasi / FAST + SIFT of a stereo pair into two SIFT slots.  Per image: the detector's chain on the resident u8 image (spvo_classic.hip),
 // the SIFT base level of that image -- every record lies on octave 0, layer 0 -- and sift_describe_given_kernel on the detector's list,
 // whose sink is the slot and the pinned mirrors.  A slot's d_src and the mirror h_src hold the 24-byte RECORDS here (SiftKey), not sources.
@@ -708,6 +834,36 @@ int spvo_sift_link_debug(spvo_ctx *c, int rows, int cols, const spvo_sift_keypoi
   std::memcpy(kept, h_kept.data(), (size_t)m * sizeof(int));
   std::memcpy(desc, h_desc.data(), (size_t)m * 128 * sizeof(float));
   *n_kept = m;
+  return SPVO_OK;
+}
+
+// spvo_sift_brisk_pair's chain of ONE image up to sift_records_kernel (test hook): the image becomes the resident one, and the records the
+// BRISK chain would read come back.  describe != 0 runs the describing instantiation of sift_describe_kernel in the other's place.
+int spvo_sift_records_debug(spvo_ctx *c, const uint8_t *img, int rows, int cols, size_t stride, int describe, spvo_sift_keypoint *rec, int cap, int *n_out) {
+  static_assert(sizeof(spvo_sift_keypoint) == sizeof(BriskDetKeypoint), "record layout");
+  if (!c || !img || !n_out || rows <= 0 || cols <= 0 || stride < (size_t)cols || cap < 0 || (cap > 0 && !rec)) return fail(c, SPVO_ERR_INVALID, "bad argument");
+  if (int rc = sift_check_image(c, "spvo_sift_records_debug", rows, cols)) return rc;
+  if (int rc = require_idle(c)) return rc;
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  *n_out = 0;
+  c->akaze.valid = false;
+  auto &s = c->sift;
+  hipStream_t st = c->stream2;
+  SiftPyr P{};
+  const size_t pyr_floats = sift_plan(rows, cols, P);
+  s.rows = s.cols = 0;
+  const int cand_cap = std::max(s.cand_cap, std::max(8192, (int)((size_t)4 * rows * cols / 16)));
+  int rc;
+  if ((rc = sift_ensure(c, rows, cols, pyr_floats, cand_cap)) || (rc = sift_order_ensure(c, s.cand_cap)) || (rc = sift_brisk_ensure(c, s.cand_cap))) return rc;
+  P.pyr = s.pyr;
+  if ((rc = classic_upload_image(c, img, rows, cols, stride)) || (rc = sift_enqueue_pyramid(c, c->cls.im, rows, cols, P))) return rc;
+  s.plan = P; s.rows = rows; s.cols = cols; s.gauss_only = false;
+  if ((rc = sift_enqueue_features(c, P, describe != 0)) || (rc = sift_enqueue_records(c, 0))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(st));
+  if (std::max(s.hb_n[1], s.hb_n[2]) > s.cand_cap) return fail(c, SPVO_ERR_CAPACITY, "spvo_sift_records_debug: %d candidates / %d keypoints do not fit", s.hb_n[1], s.hb_n[2]);
+  const int n = std::min(std::max(s.hb_n[0], 0), s.brk_cap);
+  if (std::min(n, cap) > 0) HIP_TRY(c, hipMemcpy(rec, s.brk_rec, (size_t)std::min(n, cap) * sizeof(BriskDetKeypoint), hipMemcpyDeviceToHost));
+  *n_out = n;
   return SPVO_OK;
 }
 

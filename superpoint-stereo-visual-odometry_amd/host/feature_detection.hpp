@@ -369,6 +369,11 @@ public:
   // setOrbBriskExtractor to run at all) and ORB + SIFT take their routes (spvo_orb_brisk_pair, spvo_orb_sift_pair: the ORB detector on the
   // shared resident image, its list turned into the extractor's records on the device) only with this as well as setDeviceResident -- a
   // switch of its own again; no shape the per-image path accepts is refused.
+  // setSiftBriskExtractor: SIFT + BRISK runs (per image: spvo_sift_detect, whose 128-float rows are discarded, then spvo_brisk_describe at
+  // every keypoint's own size, the image uploaded a second time); off, the pair is refused as before and the refusal does not list it.
+  // setSiftBriskResident: the pair (which still needs setSiftBriskExtractor to run at all) takes its route (spvo_sift_brisk_pair: the SIFT
+  // pyramid of the shared resident image, orientations without the SIFT rows, the list ordered and turned into the extractor's records on
+  // the device) only with this as well as setDeviceResident; no shape the per-image path accepts is refused.
   static void setDeviceResident(bool on);
   static void setResidentCapacity(int rows);   // rows per binary slot [8192]
   static void setBriskPairResident(bool on);   // [off]
@@ -380,7 +385,9 @@ public:
   static void setSiftOctavePairsResident(bool on);   // [off]
   static void setOrbBriskExtractor(bool on);      // [off]
   static void setOrbPairsResident(bool on);       // [off]
-  // pairs that actually stayed resident (spvo_classic_detect / spvo_sift_detect_pair / spvo_brisk_detect_pair / spvo_akaze_detect_pair / spvo_classic_sift_pair / spvo_brisk_orb_pair / spvo_akaze_orb_pair / spvo_akaze_brisk_pair / spvo_brisk_sift_pair / spvo_akaze_sift_pair / spvo_orb_brisk_pair / spvo_orb_sift_pair returned SPVO_OK): what tells the resident path from its fallback
+  static void setSiftBriskExtractor(bool on);     // [off]
+  static void setSiftBriskResident(bool on);      // [off]
+  // pairs that actually stayed resident (spvo_classic_detect / spvo_sift_detect_pair / spvo_brisk_detect_pair / spvo_akaze_detect_pair / spvo_classic_sift_pair / spvo_brisk_orb_pair / spvo_akaze_orb_pair / spvo_akaze_brisk_pair / spvo_brisk_sift_pair / spvo_akaze_sift_pair / spvo_orb_brisk_pair / spvo_orb_sift_pair / spvo_sift_brisk_pair returned SPVO_OK): what tells the resident path from its fallback
   unsigned residentPairs() const { return resident_ok_pairs_; }
 
 private:
@@ -394,6 +401,8 @@ private:
   bool sift_octave_pairs_resident_ = false;   // setSiftOctavePairsResident at construction
   bool orb_brisk_ = false;             // setOrbBriskExtractor at construction
   bool orb_pairs_resident_ = false;    // setOrbPairsResident at construction
+  bool sift_brisk_ = false;            // setSiftBriskExtractor at construction
+  bool sift_brisk_resident_ = false;   // setSiftBriskResident at construction
   bool pairRuns() const;               // this detector / descriptor pair runs in this build
   int resident_capacity_ = 8192;
   unsigned resident_pairs_ = 0;   // pairs handed to a resident route: pair k lives in slots 2 (k % 4), 2 (k % 4) + 1
@@ -404,7 +413,7 @@ private:
   cv::Ptr<cv::DescriptorExtractor> extractor_;
 #else
   const ClassicPair *pair() const;   // the table's row of this detector / descriptor pair, nullptr for one that does not run
-  ClassicOptIns optIns() const;      // setAkazeDescriptor, setOrbExtractorOctaves, setOrbBriskExtractor as read at construction
+  ClassicOptIns optIns() const;      // setAkazeDescriptor, setOrbExtractorOctaves, setOrbBriskExtractor, setSiftBriskExtractor as read at construction
   // what a resident route hands out for one image -- resident_capacity_ keypoint records and descriptor rows of the pair's sizes: allocated once
   struct Staging { std::vector<uint8_t> records, rows; };
   Staging staging_[2];

@@ -20,6 +20,8 @@ static bool g_classic_octave_pairs_resident = false;
 static bool g_classic_sift_octave_pairs_resident = false;
 static bool g_classic_orb_brisk = false;
 static bool g_classic_orb_pairs_resident = false;
+static bool g_classic_sift_brisk = false;
+static bool g_classic_sift_brisk_resident = false;
 void ClassicFeatureFrontEnd::setDeviceResident(bool on) { g_classic_resident = on; }
 void ClassicFeatureFrontEnd::setBriskPairResident(bool on) { g_classic_brisk_pair_resident = on; }
 void ClassicFeatureFrontEnd::setAkazeDescriptor(bool on) { g_classic_akaze_descriptor = on; }
@@ -30,6 +32,8 @@ void ClassicFeatureFrontEnd::setOctavePairsResident(bool on) { g_classic_octave_
 void ClassicFeatureFrontEnd::setSiftOctavePairsResident(bool on) { g_classic_sift_octave_pairs_resident = on; }
 void ClassicFeatureFrontEnd::setOrbBriskExtractor(bool on) { g_classic_orb_brisk = on; }
 void ClassicFeatureFrontEnd::setOrbPairsResident(bool on) { g_classic_orb_pairs_resident = on; }
+void ClassicFeatureFrontEnd::setSiftBriskExtractor(bool on) { g_classic_sift_brisk = on; }
+void ClassicFeatureFrontEnd::setSiftBriskResident(bool on) { g_classic_sift_brisk_resident = on; }
 void ClassicFeatureFrontEnd::setResidentCapacity(int rows) { g_classic_resident_capacity = rows; }
 
 #ifdef SPVO_USE_OPENCV
@@ -96,14 +100,16 @@ void ClassicFeatureFrontEnd::addStereoImagePair(cv::Mat &img_l, cv::Mat &img_r, 
 // SIFT + SIFT describe in the detector's pass, so detectKeypoints keeps the rows for the describeKeypoints call that follows on the same image;
 // every other detector leaves the image (AKAZE: its scale space) on the device for the extractor -- except ORB, which keeps a pyramid of its
 // own: the per-image path of ORB + SIFT and ORB + BRISK uploads the image a second time (their resident routes, spvo_orb_sift_pair and
-// spvo_orb_brisk_pair, run the detector on the shared resident image).  The AKAZE extractor needs the level in
+// spvo_orb_brisk_pair, run the detector on the shared resident image) -- and SIFT, which keeps an image of its own as well: the per-image
+// path of SIFT + BRISK uploads twice and discards the detector's 128-float rows (spvo_sift_brisk_pair builds the pyramid from the shared
+// resident image and computes no SIFT row).  The AKAZE extractor needs the level in
 // class_id, which only AKAZE keypoints carry -- OpenCV's own assertion refuses the others too.
 bool ClassicFeatureFrontEnd::available() { return true; }
 
 enum class Detect { Orb, Gftt, Fast, Sift, Brisk, Akaze };       // detectKeypoints: spvo_<this>_detect
 enum class Describe { WithDetector, Orb, Brisk, Akaze, Sift };   // describeKeypoints: the rows detectKeypoints kept, or spvo_<this>_describe on the given keypoints
-enum class Route { None, Classic, SiftPair, BriskPair, AkazePair, ClassicSift, BriskOrbPair, AkazeOrbPair, AkazeBriskPair, BriskSiftPair, AkazeSiftPair, OrbBriskPair, OrbSiftPair };   // setDeviceResident: the per-image path, spvo_classic_detect (kind), spvo_sift_detect_pair, spvo_brisk_detect_pair, spvo_akaze_detect_pair, spvo_classic_sift_pair (kind), spvo_brisk_orb_pair, spvo_akaze_orb_pair, spvo_akaze_brisk_pair, spvo_brisk_sift_pair, spvo_akaze_sift_pair, spvo_orb_brisk_pair, spvo_orb_sift_pair
-enum class OptIn { None, AkazeDescriptor, OrbOctaves, BriskPairResident, AkazePairResident, SiftDescribeResident, OctavePairsResident, SiftOctavePairsResident, OrbBrisk, OrbPairsResident };   // to run at all: setAkazeDescriptor, setOrbExtractorOctaves, setOrbBriskExtractor; to stay resident: setBriskPairResident, setAkazePairResident, setSiftDescribeResident, setOctavePairsResident, setSiftOctavePairsResident, setOrbPairsResident
+enum class Route { None, Classic, SiftPair, BriskPair, AkazePair, ClassicSift, BriskOrbPair, AkazeOrbPair, AkazeBriskPair, BriskSiftPair, AkazeSiftPair, OrbBriskPair, OrbSiftPair, SiftBriskPair };   // setDeviceResident: the per-image path, spvo_classic_detect (kind), spvo_sift_detect_pair, spvo_brisk_detect_pair, spvo_akaze_detect_pair, spvo_classic_sift_pair (kind), spvo_brisk_orb_pair, spvo_akaze_orb_pair, spvo_akaze_brisk_pair, spvo_brisk_sift_pair, spvo_akaze_sift_pair, spvo_orb_brisk_pair, spvo_orb_sift_pair, spvo_sift_brisk_pair
+enum class OptIn { None, AkazeDescriptor, OrbOctaves, BriskPairResident, AkazePairResident, SiftDescribeResident, OctavePairsResident, SiftOctavePairsResident, OrbBrisk, OrbPairsResident, SiftBrisk, SiftBriskResident };   // to run at all: setAkazeDescriptor, setOrbExtractorOctaves, setOrbBriskExtractor, setSiftBriskExtractor; to stay resident: setBriskPairResident, setAkazePairResident, setSiftDescribeResident, setOctavePairsResident, setSiftOctavePairsResident, setOrbPairsResident, setSiftBriskResident
 
 struct ClassicPair {
   DetectorType detector;
@@ -139,11 +145,15 @@ static const ClassicPair kClassicPairs[] = {
     {DetectorType::AKAZE, DescriptorType::ORB, Detect::Akaze, 0.f, Describe::Orb, 32, CV_8UC1, Route::AkazeOrbPair, 0, OptIn::OrbOctaves, OptIn::OctavePairsResident},
     // the BRISK extractor on ORB keypoints (size 31 x 1.2^octave): only with setOrbBriskExtractor, and listed only then
     {DetectorType::ORB, DescriptorType::BRISK, Detect::Orb, 0.f, Describe::Brisk, 64, CV_8UC1, Route::OrbBriskPair, 0, OptIn::OrbBrisk, OptIn::OrbPairsResident},
+    // the BRISK extractor on SIFT keypoints (their own size; one keypoint per orientation peak, as OpenCV's detector emits them): only with
+    // setSiftBriskExtractor, and listed only then
+    {DetectorType::SIFT, DescriptorType::BRISK, Detect::Sift, 0.f, Describe::Brisk, 64, CV_8UC1, Route::SiftBriskPair, 0, OptIn::SiftBrisk, OptIn::SiftBriskResident},
 };
 // the run-at-all switches of a front end, as its constructor read them
-struct ClassicOptIns { bool akaze_descriptor, orb_octaves, orb_brisk; };
+struct ClassicOptIns { bool akaze_descriptor, orb_octaves, orb_brisk, sift_brisk; };
 static bool opted_in(const ClassicPair &p, const ClassicOptIns &o) {
-  return (p.opt_in != OptIn::AkazeDescriptor || o.akaze_descriptor) && (p.opt_in != OptIn::OrbOctaves || o.orb_octaves) && (p.opt_in != OptIn::OrbBrisk || o.orb_brisk);
+  return (p.opt_in != OptIn::AkazeDescriptor || o.akaze_descriptor) && (p.opt_in != OptIn::OrbOctaves || o.orb_octaves) && (p.opt_in != OptIn::OrbBrisk || o.orb_brisk) &&
+         (p.opt_in != OptIn::SiftBrisk || o.sift_brisk);
 }
 
 // the row of a pair that runs, or nullptr
@@ -152,7 +162,7 @@ static const ClassicPair *find_pair(DetectorType d, DescriptorType e, const Clas
     if (p.detector == d && p.descriptor == e && opted_in(p, o)) return &p;
   return nullptr;
 }
-ClassicOptIns ClassicFeatureFrontEnd::optIns() const { return ClassicOptIns{akaze_descriptor_, orb_octaves_, orb_brisk_}; }
+ClassicOptIns ClassicFeatureFrontEnd::optIns() const { return ClassicOptIns{akaze_descriptor_, orb_octaves_, orb_brisk_, sift_brisk_}; }
 const ClassicPair *ClassicFeatureFrontEnd::pair() const { return find_pair(detector_type_, descriptor_type_, optIns()); }
 bool ClassicFeatureFrontEnd::pairRuns() const { return pair() != nullptr; }
 
@@ -161,11 +171,11 @@ template <class Names, class T> static std::string name_of(const Names &names, T
     if (kv.second == type) return kv.first;
   return "?";
 }
-// what a pair that does not run is told: the table's rows (those behind setOrbExtractorOctaves / setOrbBriskExtractor only while that switch is on)
+// what a pair that does not run is told: the table's rows (those behind setOrbExtractorOctaves / setOrbBriskExtractor / setSiftBriskExtractor only while that switch is on)
 static std::string refusal(const ClassicOptIns &o) {
   std::string s = "this detector / descriptor pair is an OpenCV features2d call (classic.cpp:7-79) -- built without SPVO_USE_OPENCV, only these pairs run: ";
   for (const ClassicPair &p : kClassicPairs) {
-    if ((p.opt_in == OptIn::OrbOctaves && !o.orb_octaves) || (p.opt_in == OptIn::OrbBrisk && !o.orb_brisk)) continue;
+    if ((p.opt_in == OptIn::OrbOctaves && !o.orb_octaves) || (p.opt_in == OptIn::OrbBrisk && !o.orb_brisk) || (p.opt_in == OptIn::SiftBrisk && !o.sift_brisk)) continue;
     s += std::string(&p == kClassicPairs ? "" : ", ") + name_of(detector_name_to_type, p.detector) + " + " + name_of(descriptor_name_to_type, p.descriptor) +
          (p.opt_in == OptIn::AkazeDescriptor ? " (with setAkazeDescriptor)" : "");
   }
@@ -207,7 +217,7 @@ static cv::KeyPoint to_keypoint(float x, float y, float response, const ClassicP
   k.octave = 0;
   return k;
 }
-static cv::KeyPoint to_keypoint(const spvo_sift_keypoint &r, const ClassicPair &p, bool extracted) {   // SIFT, BRISK's records of the same layout, and spvo_classic_sift_pair's
+static cv::KeyPoint to_keypoint(const spvo_sift_keypoint &r, const ClassicPair &p, bool extracted) {   // SIFT (SIFT + BRISK: spvo_sift_detect's record per image -- describeKeypoints replaces the angle -- and spvo_sift_brisk_pair's, which carries the extractor's degrees; octave stays SIFT's packed field), BRISK's records of the same layout, and spvo_classic_sift_pair's
                                                                                        // (size 5 / 7, angle -1, octave 0: what to_keypoint(x, y, response, p) builds)
   cv::KeyPoint k(cv::Point2f(r.x, r.y), r.size);
   // a BRISK keypoint keeps the angle its detector reports, -1; the record of spvo_brisk_detect_pair carries the extractor's, which stays with the slot.
@@ -302,12 +312,12 @@ std::vector<cv::KeyPoint> ClassicFeatureFrontEnd::detectKeypoints(const cv::Mat 
     call = "spvo_sift_detect";
     rc = grow_and_retry(4096, n, [&](int cap) {
       kp.resize((size_t)cap);
-      desc = cv::Mat(cap, p->cols, p->type);
+      desc = cv::Mat(cap, 128, CV_32FC1);   // SIFT's own rows, whatever the pair's extractor is
       return spvo_sift_detect(ctx_, px, img.rows, img.cols, step, kp.data(), desc.ptr<float>(0), cap, &n);
     });
     if (rc == SPVO_OK) {
       keypoints = to_keypoints(kp.data(), n, *p);
-      orb_desc_ = copy_rows(desc.data, n, *p);
+      if (p->describe == Describe::WithDetector) orb_desc_ = copy_rows(desc.data, n, *p);   // (SIFT + BRISK: the rows are not kept)
     }
     break;
   }
@@ -338,8 +348,8 @@ std::vector<cv::KeyPoint> ClassicFeatureFrontEnd::detectKeypoints(const cv::Mat 
     logError(std::string(call) + ": " + spvo_last_error(ctx_));
     return keypoints;
   }
-  // (spvo_orb_detect works on a pyramid of its own and leaves no image where the extractors look for one)
-  if (p->describe != Describe::WithDetector && p->detect != Detect::Orb) { detected_data_ = img.data; detected_rows_ = img.rows; detected_cols_ = img.cols; }   // still on the device for describeKeypoints
+  // (spvo_orb_detect works on a pyramid of its own and spvo_sift_detect on an image of its own: neither leaves one where the extractors look)
+  if (p->describe != Describe::WithDetector && p->detect != Detect::Orb && p->detect != Detect::Sift) { detected_data_ = img.data; detected_rows_ = img.rows; detected_cols_ = img.cols; }   // still on the device for describeKeypoints
   return keypoints;
 }
 
@@ -391,7 +401,7 @@ cv::Mat ClassicFeatureFrontEnd::describeKeypoints(std::vector<cv::KeyPoint> &key
   } else {
     // cv::ORB::create()->compute (classic.cpp:66-68) / cv::BRISK::create(30, 3, 1.0f)->compute (classic.cpp:56-65): keypoints too close to a
     // border are ERASED from the caller's vector (it is passed by non-const reference, classic.cpp:110-111), so keypoints_dq and descriptors_dq
-    // stay aligned.  BRISK: every keypoint's own size (5: ShiTomasi, 7: FAST, 12 x its scale: BRISK, 3 x esigma: AKAZE, 31 x 1.2^octave: ORB) picks its scale, and the
+    // stay aligned.  BRISK: every keypoint's own size (5: ShiTomasi, 7: FAST, 12 x its scale: BRISK, 3 x esigma: AKAZE, 31 x 1.2^octave: ORB, SIFT: 1.6 x 2^((layer + xi) / 3 + octave), the detector's own) picks its scale, and the
     // angle comes in degrees, 0 .. 360 -- except that a BRISK keypoint keeps the angle its detector reports (-1)
     // ORB on BRISK / AKAZE keypoints (the rows behind setOrbExtractorOctaves): KeyPoint::octave names the pyramid level, the survivors come
     // grouped by level as OpenCV leaves them
@@ -511,7 +521,8 @@ bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &img_l, cv::Mat 
   const ClassicPair &p = *pair();   // (addStereoImagePair has asked pairRuns)
   if (p.route == Route::None || (p.resident_opt_in == OptIn::BriskPairResident && !brisk_pair_resident_) || (p.resident_opt_in == OptIn::AkazePairResident && !akaze_pair_resident_) ||
       (p.resident_opt_in == OptIn::SiftDescribeResident && !sift_describe_resident_) || (p.resident_opt_in == OptIn::OctavePairsResident && !octave_pairs_resident_) ||
-      (p.resident_opt_in == OptIn::SiftOctavePairsResident && !sift_octave_pairs_resident_) || (p.resident_opt_in == OptIn::OrbPairsResident && !orb_pairs_resident_))
+      (p.resident_opt_in == OptIn::SiftOctavePairsResident && !sift_octave_pairs_resident_) || (p.resident_opt_in == OptIn::OrbPairsResident && !orb_pairs_resident_) ||
+      (p.resident_opt_in == OptIn::SiftBriskResident && !sift_brisk_resident_))
     return false;
   const uint8_t *l = img_l.ptr<uint8_t>(0), *r = img_r.ptr<uint8_t>(0);
   const int rows = img_l.rows, cols = img_l.cols;
@@ -594,6 +605,11 @@ bool ClassicFeatureFrontEnd::addStereoImagePairResident(cv::Mat &img_l, cv::Mat 
     return residentPair<spvo_sift_features>(p, img_l, img_r, "spvo_orb_sift_pair", [&](int slot_l, int slot_r, spvo_sift_features *f) {
       return spvo_orb_sift_pair(ctx_, l, r, rows, cols, step, 2000, slot_l, slot_r, resident_capacity_, &f[0], &f[1]);
     });
+  // cv::SIFT::create(), as detectKeypoints; no shape is refused that the per-image path accepts
+  case Route::SiftBriskPair:
+    return residentPair<spvo_brisk_features>(p, img_l, img_r, "spvo_sift_brisk_pair", [&](int slot_l, int slot_r, spvo_brisk_features *f) {
+      return spvo_sift_brisk_pair(ctx_, l, r, rows, cols, step, slot_l, slot_r, resident_capacity_, &f[0], &f[1]);
+    });
   case Route::None:
     break;
   }
@@ -616,6 +632,7 @@ ClassicFeatureFrontEnd::ClassicFeatureFrontEnd(const DetectorType detector_type,
   akaze_descriptor_ = g_classic_akaze_descriptor;   // (initDetector and initDescriptor ask whether the pair runs)
   orb_octaves_ = g_classic_orb_octaves;
   orb_brisk_ = g_classic_orb_brisk;
+  sift_brisk_ = g_classic_sift_brisk;
   initDetector();
   initDescriptor();
   initMatcher();
@@ -630,6 +647,7 @@ ClassicFeatureFrontEnd::ClassicFeatureFrontEnd(const DetectorType detector_type,
   octave_pairs_resident_ = g_classic_octave_pairs_resident;
   sift_octave_pairs_resident_ = g_classic_sift_octave_pairs_resident;
   orb_pairs_resident_ = g_classic_orb_pairs_resident;
+  sift_brisk_resident_ = g_classic_sift_brisk_resident;
 }
 
 ClassicFeatureFrontEnd::~ClassicFeatureFrontEnd() {

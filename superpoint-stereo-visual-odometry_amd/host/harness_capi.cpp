@@ -546,6 +546,14 @@ void spvo_host_classic_set_orb_brisk(int on) { ClassicFeatureFrontEnd::setOrbBri
 // spvo_orb_brisk_pair / spvo_orb_sift_pair per pair when setDeviceResident is on as well (off by default)
 void spvo_host_classic_set_orb_pairs_resident(int on) { ClassicFeatureFrontEnd::setOrbPairsResident(on != 0); }
 
+// ClassicFeatureFrontEnd::setSiftBriskExtractor for the front ends constructed afterwards: SIFT + BRISK runs (spvo_brisk_describe on the SIFT
+// detector's keypoints at their own sizes, the per-image path); off, the pair is refused
+void spvo_host_classic_set_sift_brisk(int on) { ClassicFeatureFrontEnd::setSiftBriskExtractor(on != 0); }
+
+// ClassicFeatureFrontEnd::setSiftBriskResident for the front ends constructed afterwards: SIFT + BRISK through one spvo_sift_brisk_pair per
+// pair when setDeviceResident is on as well (off by default)
+void spvo_host_classic_set_sift_brisk_resident(int on) { ClassicFeatureFrontEnd::setSiftBriskResident(on != 0); }
+
 // the ORB + ORB front end at the native resolution (the export's first form)
 int spvo_host_classic_sequence(int n, const uint8_t *const *imgs_l, const uint8_t *const *imgs_r, int rows, int cols, const double *P_l, const double *P_r, int knn,
                                int cross_check, float stereo_threshold, int refinement_degree, int warm, double *poses, int *stats, double *seconds) {

@@ -98,7 +98,7 @@ SYMBOLS = [
     "spvo_default_config", "spvo_create", "spvo_destroy", "spvo_last_error", "spvo_load_weights", "spvo_engine_precision", "spvo_set_fp32_split",
     "spvo_preprocess", "spvo_forward", "spvo_debug_tensor", "spvo_heatmap", "spvo_nms",
     "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8", "spvo_match_last_form",
-    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_orb_describe_octaves", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_akaze_describe", "spvo_akaze_detect_pair", "spvo_akaze_suppress_debug", "spvo_brisk_orb_pair", "spvo_akaze_orb_pair", "spvo_akaze_brisk_pair", "spvo_orb_octaves_link_debug", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_describe", "spvo_sift_detect_pair", "spvo_classic_sift_pair", "spvo_brisk_sift_pair", "spvo_akaze_sift_pair", "spvo_orb_brisk_pair", "spvo_orb_sift_pair", "spvo_sift_link_debug", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_match_l2_u8", "spvo_match_l2_u8_slots", "spvo_set_binary_prematch_norm", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
+    "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_orb_describe_octaves", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_akaze_describe", "spvo_akaze_detect_pair", "spvo_akaze_suppress_debug", "spvo_brisk_orb_pair", "spvo_akaze_orb_pair", "spvo_akaze_brisk_pair", "spvo_orb_octaves_link_debug", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_describe", "spvo_sift_detect_pair", "spvo_classic_sift_pair", "spvo_brisk_sift_pair", "spvo_akaze_sift_pair", "spvo_orb_brisk_pair", "spvo_orb_sift_pair", "spvo_sift_brisk_pair", "spvo_sift_records_debug", "spvo_sift_link_debug", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_match_l2_u8", "spvo_match_l2_u8_slots", "spvo_set_binary_prematch_norm", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
     "spvo_profile_enable", "spvo_profile_reset", "spvo_profile_only", "spvo_profile_count", "spvo_profile_get", "spvo_profile_stage_kernel", "spvo_profile_stage_variant", "spvo_profile_stage_fused",
     "spvo_set_tuning", "spvo_get_tuning", "spvo_clear_tuning",
     "spvo_comm_unique_id", "spvo_comm_available", "spvo_comm_create", "spvo_comm_create_host", "spvo_comm_rank", "spvo_comm_world", "spvo_comm_destroy",
@@ -180,6 +180,8 @@ def load() -> C.CDLL:
     lib.spvo_akaze_sift_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(AkazeSiftFeatures), C.POINTER(AkazeSiftFeatures)]
     lib.spvo_orb_brisk_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(BriskFeatures), C.POINTER(BriskFeatures)]
     lib.spvo_orb_sift_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(SiftFeatures), C.POINTER(SiftFeatures)]
+    lib.spvo_sift_brisk_pair.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(BriskFeatures), C.POINTER(BriskFeatures)]
+    lib.spvo_sift_records_debug.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, vp, C.c_int, ip]
     lib.spvo_sift_link_debug.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, ip]
     lib.spvo_classic_sift_pair.argtypes = [vp, C.POINTER(ClassicOpts), vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.POINTER(SiftFeatures), C.POINTER(SiftFeatures)]
     lib.spvo_sift_slot_rows.argtypes = [vp, C.c_int, ip]
@@ -837,6 +839,30 @@ class Context:
         float32 and n -- per image what orb_detect() followed by sift_describe(img, those records) returns; nothing is erased.
         Afterwards the right image is resident.  On SPVO_ERR_CAPACITY the SpvoError carries the two counts as .counts."""
         return self._sift_octave_pair(self.lib.spvo_orb_sift_pair, SIFT_KP_DTYPE, SiftFeatures, img_l, img_r, (int(nfeatures),), slot_l, slot_r, slot_capacity, cap)
+
+    def sift_brisk_pair(self, img_l, img_r, slot_l: int, slot_r: int, slot_capacity: int = 8192, cap: Optional[int] = None):
+        """One stereo pair through the SIFT detector and the BRISK extractor into two binary feature slots of 64-byte rows
+        (spvo_sift_brisk_pair).  -> (left, right): dicts of kp [m] (BRISK_KP_DTYPE: the detector's x, y, size, response and packed octave
+        with the extractor's angle in degrees -- the records that survived the extractor's border rule, in the detector's order, one per
+        orientation peak), desc [m, 64] uint8 and n -- per image what sift_detect() followed by brisk_describe(img, its xy, its sizes)
+        returns.  Afterwards the right image is resident.  On SPVO_ERR_CAPACITY the SpvoError carries the two counts as .n_l, .n_r (and
+        .counts).  set_tuning("sift_brisk_recheck", 1): the second pass on the host's records, forced (diagnostic)."""
+        return self._octave_pair(self.lib.spvo_sift_brisk_pair, BRISK_KP_DTYPE, BriskFeatures, 64, img_l, img_r, (), slot_l, slot_r, slot_capacity, cap)
+
+    def sift_records_debug(self, img: np.ndarray, describe: bool = False, cap: Optional[int] = None) -> np.ndarray:
+        """sift_brisk_pair's chain of one image up to the records the BRISK extractor's chain reads (spvo_sift_records_debug): kp [n]
+        SIFT_KP_DTYPE in the detector's order, the detector's angle still in place.  describe: the describing form of the orientation
+        kernel in the other's place (the records must not depend on it).  Afterwards the image is resident."""
+        img = _u8_rows(img)
+        want = 8192 if cap is None else int(cap)
+        while True:
+            kp = np.zeros(max(want, 1), SIFT_KP_DTYPE)
+            n = C.c_int(0)
+            self._check(self.lib.spvo_sift_records_debug(self.h, _ptr(img), img.shape[0], img.shape[1], img.strides[0], int(bool(describe)), _ptr(kp), want, C.byref(n)))
+            self._resident_shape = img.shape
+            if cap is not None or n.value <= want:
+                return kp[:min(n.value, want)].copy()
+            want = n.value
 
     def sift_link_debug(self, kp: np.ndarray, keep=None, max_octave: int = 5, shape=None):
         """The two calls' device link and describe launch on a caller's list against the resident image (spvo_sift_link_debug): kp [n]

@@ -347,7 +347,8 @@ class FrontEnd:
 
 def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_threshold=2.0, refinement_degree=4, warm=0, detector="ORB", input_size=None, resident=False,
                      resident_capacity=0, trace=False, descriptor="ORB", brisk_resident=False, akaze_descriptor=False, akaze_resident=False, sift_describe_resident=False, orb_octaves=False,
-                     octave_pairs_resident=False, sift_octave_pairs_resident=False, matcher="BF", orb_brisk=False, orb_pairs_resident=False):
+                     octave_pairs_resident=False, sift_octave_pairs_resident=False, matcher="BF", orb_brisk=False, orb_pairs_resident=False, sift_brisk=False,
+                     sift_brisk_resident=False):
     """matcher: "BF", or "FLANN" (spvo_host_classic_sequence_matcher: the exact L2 search on the descriptor bytes, no cross-check).
     stereoCallback replayed on ClassicFeatureFrontEnd(detector, descriptor, BF, ...) (node.cpp:353-360) over host image pairs -- detector
     "ORB", "ShiTomasi" or "FAST" with descriptor "ORB", "ShiTomasi", "FAST", "BRISK" or "AKAZE" with descriptor "BRISK" (64-byte rows; detector "BRISK"
@@ -358,7 +359,7 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     "BRISK" or "AKAZE" with descriptor "SIFT" (spvo_sift_describe on the detector's keypoints as they are: 128 floats per row, matched with
     NORM_L2; the per-image path and classic_resident_pairs() stays 0 -- except "ShiTomasi" and "FAST" with sift_describe_resident=True
     (ClassicFeatureFrontEnd::setSiftDescribeResident, reset afterwards) and resident=True: then it is one spvo_classic_sift_pair per pair into the
-    SIFT slots), or detector "SIFT" (SIFT descriptors whatever `descriptor` says, as before); input_size None: at their native resolution, (height, width): through preprocessImageImpl first
+    SIFT slots), or detector "SIFT" (SIFT descriptors whatever `descriptor` says, as before -- except "BRISK": see sift_brisk); input_size None: at their native resolution, (height, width): through preprocessImageImpl first
     (classic.cpp:96-100).  Returns (poses [n, 7] = q xyzw + t of cam0_curr_T_cam0_prev, stats [n, 4] = keypoints L, R, stereo
     matches, PnP inliers, seconds spent on frames warm .. n-1).
     resident: ClassicFeatureFrontEnd::setDeviceResident for this run -- one spvo_classic_detect (SIFT: spvo_sift_detect_pair) per pair, features
@@ -380,6 +381,10 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     (ClassicFeatureFrontEnd::setOrbPairsResident, reset afterwards) with resident=True: "ORB" + "BRISK" (which still needs orb_brisk=True) and
     "ORB" + "SIFT" are one spvo_orb_brisk_pair / spvo_orb_sift_pair per pair into the binary / the SIFT slots; without it both take the
     per-image path.
+    sift_brisk (ClassicFeatureFrontEnd::setSiftBriskExtractor, reset afterwards): "SIFT" + "BRISK" runs -- per image spvo_sift_detect, whose
+    128-float rows are discarded, then spvo_brisk_describe at every keypoint's own size -- and is refused without.  sift_brisk_resident
+    (ClassicFeatureFrontEnd::setSiftBriskResident, reset afterwards) with resident=True: "SIFT" + "BRISK" (which still needs sift_brisk=True)
+    is one spvo_sift_brisk_pair per pair into the binary slots; without it the pair takes the per-image path.
     trace: a fourth value, digests [n, 8] uint64 of what every frame left in the front end (keypoints L, descriptors L, keypoints R,
     descriptors R, stereo matches, temporal matches, the previous frame's stereo matches + map, the inlier sets): equal digests = identical
     contents.  The digests are computed inside the timed loop, so `seconds` of a traced run is not a frame-rate figure."""
@@ -411,6 +416,10 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     lib.spvo_host_classic_set_orb_brisk.argtypes = [C.c_int]
     lib.spvo_host_classic_set_orb_pairs_resident.restype = None
     lib.spvo_host_classic_set_orb_pairs_resident.argtypes = [C.c_int]
+    lib.spvo_host_classic_set_sift_brisk.restype = None
+    lib.spvo_host_classic_set_sift_brisk.argtypes = [C.c_int]
+    lib.spvo_host_classic_set_sift_brisk_resident.restype = None
+    lib.spvo_host_classic_set_sift_brisk_resident.argtypes = [C.c_int]
     n = len(frames)
     ls = [np.ascontiguousarray(f[0], np.uint8) for f in frames]
     rs = [np.ascontiguousarray(f[1], np.uint8) for f in frames]
@@ -434,12 +443,15 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
     lib.spvo_host_classic_set_sift_octave_pairs_resident(int(bool(sift_octave_pairs_resident)))
     lib.spvo_host_classic_set_orb_brisk(int(bool(orb_brisk)))
     lib.spvo_host_classic_set_orb_pairs_resident(int(bool(orb_pairs_resident)))
+    lib.spvo_host_classic_set_sift_brisk(int(bool(sift_brisk)))
+    lib.spvo_host_classic_set_sift_brisk_resident(int(bool(sift_brisk_resident)))
     try:
         args =(n, pl, pr, rows, cols, Pl.ctypes.data, Pr.ctypes.data, 1 if selector == "KNN" else 0, int(cross_check), stereo_threshold, refinement_degree, warm,
                 poses.ctypes.data, stats.ctypes.data, C.byref(sec), ih, iw, digest.ctypes.data if trace else None)
+        sift_rows = detector == "SIFT" and descriptor != "BRISK"    # a SIFT detector has SIFT rows whatever is named -- except "BRISK", the pair behind sift_brisk
         if matcher != "BF":
-            rc = lib.spvo_host_classic_sequence_matcher(detector.encode(), ("SIFT" if detector == "SIFT" else descriptor).encode(), matcher.encode(), *args)
-        elif descriptor == "ORB" or detector == "SIFT":             # the export that pairs every detector with its default descriptor
+            rc = lib.spvo_host_classic_sequence_matcher(detector.encode(), ("SIFT" if sift_rows else descriptor).encode(), matcher.encode(), *args)
+        elif descriptor == "ORB" or sift_rows:                      # the export that pairs every detector with its default descriptor
             rc = lib.spvo_host_classic_sequence_trace(detector.encode(), *args)
         else:
             rc = lib.spvo_host_classic_sequence_desc(detector.encode(), descriptor.encode(), *args)
@@ -454,6 +466,8 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
         lib.spvo_host_classic_set_sift_octave_pairs_resident(0)
         lib.spvo_host_classic_set_orb_brisk(0)
         lib.spvo_host_classic_set_orb_pairs_resident(0)
+        lib.spvo_host_classic_set_sift_brisk(0)
+        lib.spvo_host_classic_set_sift_brisk_resident(0)
     if rc == -1000000:
         raise ValueError("unknown detector %r" % (detector,))
     if rc == -1000001:
@@ -469,7 +483,8 @@ def classic_sequence(frames, P_l, P_r, selector="KNN", cross_check=True, stereo_
 
 def classic_resident_pairs():
     """Pairs of the last classic_sequence() run that stayed resident on the device (spvo_host_classic_resident_pairs): 0 without `resident`,
-    every frame when all fitted their slots, fewer when pairs fell back to the per-image path."""
+    every frame when all fitted their slots, fewer when pairs fell back to the per-image path (a pair whose route lacks its switch --
+    sift_brisk_resident for "SIFT" + "BRISK" -- is not counted)."""
     lib = load()
     lib.spvo_host_classic_resident_pairs.restype = C.c_int
     lib.spvo_host_classic_resident_pairs.argtypes = []
@@ -492,11 +507,12 @@ def classic_default_probe(img_l, img_r, P_l, P_r):
     return rc, counts, buf.value.decode()
 
 
-def classic_pair_probe(detector, descriptor, img_l, img_r, P_l, P_r, akaze_descriptor=False, orb_octaves=False, orb_brisk=False):
+def classic_pair_probe(detector, descriptor, img_l, img_r, P_l, P_r, akaze_descriptor=False, orb_octaves=False, orb_brisk=False, sift_brisk=False):
     """ClassicFeatureFrontEnd(detector, descriptor, BF, NN, cross-check) at the native resolution offered one stereo pair.
     akaze_descriptor: ClassicFeatureFrontEnd::setAkazeDescriptor for this probe (AKAZE + AKAZE runs), reset afterwards.
     orb_octaves: ClassicFeatureFrontEnd::setOrbExtractorOctaves for this probe (BRISK + ORB and AKAZE + ORB run), reset afterwards.
     orb_brisk: ClassicFeatureFrontEnd::setOrbBriskExtractor for this probe (ORB + BRISK runs), reset afterwards.
+    sift_brisk: ClassicFeatureFrontEnd::setSiftBriskExtractor for this probe (SIFT + BRISK runs), reset afterwards.
     -> (deque entries, [keypoints L, descriptor rows L, keypoints R, descriptor rows R, descriptor columns], the error it logged)"""
     lib = load()
     lib.spvo_host_classic_pair_probe.restype = C.c_int
@@ -516,6 +532,9 @@ def classic_pair_probe(detector, descriptor, img_l, img_r, P_l, P_r, akaze_descr
     lib.spvo_host_classic_set_orb_brisk.restype = None
     lib.spvo_host_classic_set_orb_brisk.argtypes = [C.c_int]
     lib.spvo_host_classic_set_orb_brisk(int(bool(orb_brisk)))
+    lib.spvo_host_classic_set_sift_brisk.restype = None
+    lib.spvo_host_classic_set_sift_brisk.argtypes = [C.c_int]
+    lib.spvo_host_classic_set_sift_brisk(int(bool(sift_brisk)))
     try:
         rc = lib.spvo_host_classic_pair_probe(detector.encode(), descriptor.encode(), l.ctypes.data, r.ctypes.data, l.shape[0], l.shape[1], Pl.ctypes.data, Pr.ctypes.data,
                                               counts.ctypes.data, buf, 512)
@@ -523,6 +542,7 @@ def classic_pair_probe(detector, descriptor, img_l, img_r, P_l, P_r, akaze_descr
         lib.spvo_host_classic_set_akaze_descriptor(0)
         lib.spvo_host_classic_set_orb_octaves(0)
         lib.spvo_host_classic_set_orb_brisk(0)
+        lib.spvo_host_classic_set_sift_brisk(0)
     return rc, counts, buf.value.decode()
 
 

@@ -1,6 +1,6 @@
 """The classic front end on the GPU.
 
-python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK|AKAZE] [--descriptor ORB|BRISK|AKAZE|SIFT] [--resident] [--brisk-resident] [--akaze-resident] [--sift-resident] [--orb-octaves] [--octave-pairs-resident] [--sift-octave-pairs-resident] [--orb-brisk] [--orb-pairs-resident]
+python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK|AKAZE] [--descriptor ORB|BRISK|AKAZE|SIFT] [--resident] [--brisk-resident] [--akaze-resident] [--sift-resident] [--orb-octaves] [--octave-pairs-resident] [--sift-octave-pairs-resident] [--orb-brisk] [--orb-pairs-resident] [--sift-brisk] [--sift-brisk-resident]
     ClassicFeatureFrontEnd(detector, descriptor, BF, KNN) over the synthetic stream: frames/s of the synchronous stereoCallback
     (--descriptor BRISK: with --detector ShiTomasi, FAST, BRISK or AKAZE; --detector BRISK: with --descriptor BRISK only; --detector AKAZE:
     with --descriptor BRISK or AKAZE -- the latter sets ClassicFeatureFrontEnd::setAkazeDescriptor for the run: 61-byte MLDB rows);
@@ -14,7 +14,9 @@ python tools/classic_bench.py [frames] [--detector ORB|ShiTomasi|FAST|BRISK|AKAZ
     spvo_akaze_sift_pair per pair; needs --resident; also taken by --ab for its resident runs).
     --orb-brisk: with setOrbBriskExtractor (ORB + BRISK runs at all); --orb-pairs-resident: with setOrbPairsResident as well (ORB + BRISK /
     ORB + SIFT through one spvo_orb_brisk_pair / spvo_orb_sift_pair per pair; needs --resident; also taken by --ab for its resident runs).
-python tools/classic_bench.py [frames] --detector ShiTomasi|FAST|ORB|BRISK|AKAZE --descriptor ORB|BRISK|SIFT --ab ROUNDS [--sift-resident] [--sift-octave-pairs-resident] [--orb-brisk] [--orb-pairs-resident] [--waves N]
+    --sift-brisk: with setSiftBriskExtractor (--detector SIFT --descriptor BRISK runs at all); --sift-brisk-resident: with setSiftBriskResident
+    as well (SIFT + BRISK through one spvo_sift_brisk_pair per pair; needs --resident; also taken by --ab for its resident runs).
+python tools/classic_bench.py [frames] --detector ShiTomasi|FAST|ORB|BRISK|AKAZE|SIFT --descriptor ORB|BRISK|SIFT --ab ROUNDS [--sift-resident] [--sift-octave-pairs-resident] [--orb-brisk] [--orb-pairs-resident] [--sift-brisk] [--sift-brisk-resident] [--waves N]
     the same stream with setDeviceResident off and on, alternating, ROUNDS times each in one process: ms per pair of every run, the median
     and the min .. max spread of each setting, and how many pairs of a resident run stayed resident.  --waves N: tuning
     "sift_pair_waves_per_cu" = N for the SIFT pair calls of the resident runs.
@@ -75,6 +77,14 @@ python tools/classic_bench.py --leg orb_brisk_pair|orb_sift_pair [--calls 100]
     orb_records_kernel, then brisk_integral_*_kernel / brisk_pair_compact_kernel / brisk_describe_kernel / brisk_pair_finish_kernel, or
     sift_blur_kernel x the reduced pyramid / sift_describe_given_kernel, twice per call.  The whole pair through the host class:
     --detector ORB --descriptor BRISK|SIFT [--orb-brisk] --resident --orb-pairs-resident, or --ab.
+python tools/classic_bench.py --leg sift_brisk_pair [--calls 100]
+    spvo_sift_brisk_pair on the 1241 x 376 sample pair -- BOTH images per call -- rotating through the slot ring, and ALTERNATING with it
+    call by call in the same run its yardstick, the per-image route of both images: spvo_sift_detect (with its 128-float rows), then
+    spvo_brisk_describe at the records' x, y, size with the image passed again (spvo_sift_detect leaves none resident).  For rocprofv3
+    --kernel-trace --stats as above (--no-yardstick: the pair call alone): sift_blur_kernel x the pyramid / sift_extrema_kernel /
+    sift_refine_kernel / sift_describe_kernel<false> / sift_key_kernel / sift_rank_kernel / sift_unique_kernel / sift_records_kernel, then
+    brisk_integral_*_kernel / brisk_pair_compact_kernel / brisk_describe_kernel / brisk_pair_finish_kernel, twice per call.  The whole
+    pair through the host class: --detector SIFT --descriptor BRISK --sift-brisk --resident --sift-brisk-resident, or --ab.
 python tools/classic_bench.py --leg fast_sift|gftt_sift|sift_describe [--calls 50] [--form 0|1] [--yardstick] [--sift-resident]
     FAST + SIFT per image at 1241 x 376, for rocprofv3 --kernel-trace --stats as above.  sift_describe: spvo_sift_describe alone on the FAST
     keypoints of the sample (size 7, angle -1, octave 0; image passed with every call): sift_blur_kernel x 6 / sift_describe_given_kernel is
@@ -114,9 +124,11 @@ ap.add_argument("--octave-pairs-resident", action="store_true")
 ap.add_argument("--sift-octave-pairs-resident", action="store_true")
 ap.add_argument("--orb-brisk", action="store_true")
 ap.add_argument("--orb-pairs-resident", action="store_true")
+ap.add_argument("--sift-brisk", action="store_true")
+ap.add_argument("--sift-brisk-resident", action="store_true")
 ap.add_argument("--no-yardstick", action="store_true")
 ap.add_argument("--ab", type=int, default=0)
-ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "brisk_detect", "akaze_detect", "akaze_describe", "akaze_pair", "brisk_pair", "brisk_orb_pair", "akaze_orb_pair", "akaze_brisk_pair", "orb_brisk_pair", "orb_sift_pair", "orb_describe", "orb_octaves", "fast_sift", "gftt_sift", "sift_describe", "match", "match_slots"])
+ap.add_argument("--leg", choices=["gftt", "fast", "orb", "sift", "brisk", "brisk_detect", "akaze_detect", "akaze_describe", "akaze_pair", "brisk_pair", "brisk_orb_pair", "akaze_orb_pair", "akaze_brisk_pair", "orb_brisk_pair", "orb_sift_pair", "sift_brisk_pair", "orb_describe", "orb_octaves", "fast_sift", "gftt_sift", "sift_describe", "match", "match_slots"])
 ap.add_argument("--form", type=int, default=0, choices=[0, 1])
 ap.add_argument("--waves", type=int, default=0)
 ap.add_argument("--selector", default="KNN", choices=["NN", "KNN"])
@@ -229,7 +241,7 @@ if args.detectors or args.leg:
         return fl["n"] + fr["n"]
 
     ORB_PAIRS = ("orb_brisk_pair", "orb_sift_pair")
-    OCTAVE_PAIRS = ("brisk_orb_pair", "akaze_orb_pair", "akaze_brisk_pair") + ORB_PAIRS
+    OCTAVE_PAIRS = ("brisk_orb_pair", "akaze_orb_pair", "akaze_brisk_pair", "sift_brisk_pair") + ORB_PAIRS
     if args.leg in ("brisk_pair", "akaze_pair", "fast_sift", "gftt_sift") + OCTAVE_PAIRS:
         pair_r = np.ascontiguousarray(frames[0][1][:376, :1241])
 
@@ -255,6 +267,10 @@ if args.detectors or args.leg:
             if args.leg in ORB_PAIRS:                  # (spvo_orb_detect leaves no image resident: the extractor takes it again)
                 rec = orb_records(ctx.orb(im))
                 n += len(ctx.sift_describe(im, rec)) if args.leg == "orb_sift_pair" else len(ctx.brisk_describe(im, np.stack([rec["x"], rec["y"]], 1), rec["size"])["kept"])
+                continue
+            if args.leg == "sift_brisk_pair":          # (spvo_sift_detect keeps an image of its own: the extractor takes it again)
+                rec = ctx.sift_detect(im)["kp"]
+                n += len(ctx.brisk_describe(im, np.stack([rec["x"], rec["y"]], 1), rec["size"])["kept"])
                 continue
             kp = (ctx.brisk_detect(im, 30) if args.leg == "brisk_orb_pair" else ctx.akaze_detect(im))["kp"]
             xy = np.stack([kp["x"], kp["y"]], 1)
@@ -357,13 +373,14 @@ elif args.ab > 0:
     seq = [frames[i % 8] for i in range(n)]
     name = args.detector + ("" if args.descriptor == "ORB" else " + " + args.descriptor)
     ms = {False: [], True: []}
-    host.classic_sequence(seq[:8], P_l, P_r, "KNN", True, 2.0, 4, detector=args.detector, descriptor=args.descriptor, orb_brisk=args.orb_brisk)      # the process's one-off costs
+    host.classic_sequence(seq[:8], P_l, P_r, "KNN", True, 2.0, 4, detector=args.detector, descriptor=args.descriptor, orb_brisk=args.orb_brisk, sift_brisk=args.sift_brisk)      # the process's one-off costs
     for r in range(args.ab):
         for resident in (False, True):
             p, s, sec = host.classic_sequence(seq, P_l, P_r, "KNN", True, 2.0, 4, warm=5, detector=args.detector, resident=resident, descriptor=args.descriptor,
                                                 sift_describe_resident=resident and args.sift_resident,
                                                 sift_octave_pairs_resident=resident and args.sift_octave_pairs_resident, orb_brisk=args.orb_brisk,
-                                                orb_pairs_resident=resident and args.orb_pairs_resident)
+                                                orb_pairs_resident=resident and args.orb_pairs_resident, sift_brisk=args.sift_brisk,
+                                                sift_brisk_resident=resident and args.sift_brisk_resident)
             ms[resident].append(1e3 * sec / (n - 5))
             print("%s %dx%d round %d resident=%d: %.3f ms per pair over %d pairs, %d pairs resident, keypoints %d, stereo matches %d, inliers %d" % (
                 name, frames[0][0].shape[1], frames[0][0].shape[0], r, resident, ms[resident][-1], n - 5, host.classic_resident_pairs(), np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3])))
@@ -379,5 +396,5 @@ else:
                                         **(dict(sift_describe_resident=True) if args.sift_resident else {}), **(dict(orb_octaves=True) if args.orb_octaves else {}),
                                         **(dict(octave_pairs_resident=True) if args.octave_pairs_resident else {}),
                                         **(dict(sift_octave_pairs_resident=True) if args.sift_octave_pairs_resident else {}), orb_brisk=args.orb_brisk,
-                                        orb_pairs_resident=args.orb_pairs_resident)
+                                        orb_pairs_resident=args.orb_pairs_resident, sift_brisk=args.sift_brisk, sift_brisk_resident=args.sift_brisk_resident)
     print("classic front end (%s%s) on the GPU: %.1f stereo frames/s (%.3f ms per pair), keypoints %d, stereo matches %d, inliers %d, %d pairs resident" % (args.detector + ("" if args.descriptor == "ORB" else " + " + args.descriptor), ", device-resident" if args.resident else "", (n - 5) / sec, 1e3 * sec / (n - 5), np.median(s[5:, 0]), np.median(s[5:, 2]), np.median(s[5:, 3]), host.classic_resident_pairs()))
