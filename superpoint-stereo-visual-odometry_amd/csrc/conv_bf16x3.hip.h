@@ -20,7 +20,8 @@
 // covers ONE group of 8 channels: lane half 0 supplies one piece and lane half 1 another, so that
 //     [a0 a0] x [b0 b1] = a0b0 + a0b1,   [a1 a1] x [b0 b1] = a1b0 + a1b1,   [a0 a2] x [b2 b0] = a0b2 + a2b0
 // are the six partial products in three instructions.  Everything else (persistent tiles, LDS ring fed by
-// global_load_lds, D[co][x] mapping, fused ReLU / 2x2 max-pool, bias from the slab) is as in conv_f16.hip.h.
+// global_load_lds, D[co][x] mapping, fused ReLU / 2x2 max-pool, bias from the slab) is as in conv_f16.hip.h; the tile
+// geometry, the tile decode, the slab packer and the launcher's tile table are written once, in conv_packed.hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -83,45 +84,19 @@ struct ConvArgsS3 {
   int cout, n_chunks, tiles_x, tiles_y, co_tiles, batch;
 };
 
-template <int KS, int CKG_, int WR, int WC>
-struct ConvTileS3 {
-  static constexpr int CKG = CKG_;                          // channel groups (of 8) per chunk: 1 for 3x3, 2 for 1x1
-  static constexpr int TH = 4 * WR, TW = 32 * WC, HALO = KS / 2;
-  static constexpr int LW = TW + 2 * HALO, LH = TH + 2 * HALO;
-  static constexpr int IN_P = CKG * 3 * LH * LW;            // 16-byte pieces: one pixel of one plane
-  static constexpr int W_P = KS * KS * CKG * 3 * CO_TILE;   // one (tap, group, piece, co) row of 8 bf16
-  static constexpr int BIAS_P = CO_TILE / 4;
-  static constexpr int BUF_P = IN_P + W_P + BIAS_P;
-  static constexpr int BUF_PAD = (BUF_P + 255) / 256 * 256;   // every thread stages the same number of pieces (the tail lands in padding)
+template <int KS, int CKG_, int WR, int WC>   // CKG: channel groups (of 8) per chunk: 1 for 3x3, 2 for 1x1
+struct ConvTileS3 : PackedTile<KS, CKG_, WR, WC, 3, CO_TILE / 4> {
+  static constexpr int BUF_PAD = ConvTileS3::NIT * 256;   // every thread stages the same number of pieces (the tail lands in padding)
   // Ring depth: two chunks in flight wherever three buffers fit into the 160 KiB of LDS.  Measured: neutral for the 3x3
   // layers (a chunk of 9 taps is long enough to cover the LDS-DMA latency), 25 % faster for the 1x1 heads (2 steps per chunk).
   static constexpr int NBUF = 3 * BUF_PAD * 16 <= 160 * 1024 ? 3 : 2;
   static constexpr int LDS_BYTES = NBUF * BUF_PAD * 16;
-  static constexpr int NSTEP = KS * KS * CKG;
+  static constexpr int NSTEP = KS * KS * CKG_;
 };
 
 // OIHW fp32 weights + bias -> slabs [co_tile][chunk][tap][group][piece][co 64][8] of bf16 bits + 64 fp32 biases (chunk 0)
 inline std::vector<unsigned short> pack_conv_weights_s3(const float *w, const float *bias, int cout, int cin, int ks, int ckg) {
-  const int co_tiles = (cout + CO_TILE - 1) / CO_TILE, ck = 8 * ckg, nch = cin / ck, taps = ks * ks;
-  const size_t slab = ((size_t)taps * ckg * 3 * CO_TILE + CO_TILE / 4) * 8;   // in 16-bit units
-  std::vector<unsigned short> out((size_t)co_tiles * nch * slab, 0);
-  for (int ct = 0; ct < co_tiles; ++ct)
-    for (int ch = 0; ch < nch; ++ch) {
-      unsigned short *s = out.data() + ((size_t)ct * nch + ch) * slab;
-      for (int o = 0; o < CO_TILE; ++o) {
-        const int co = ct * CO_TILE + o;
-        if (co >= cout) continue;
-        for (int t = 0; t < taps; ++t)
-          for (int g = 0; g < ckg; ++g)
-            for (int e = 0; e < 8; ++e) {
-              unsigned short p[3];
-              split3(w[((size_t)co * cin + ch * ck + g * 8 + e) * taps + t], p);
-              for (int q = 0; q < 3; ++q) s[((((size_t)t * ckg + g) * 3 + q) * CO_TILE + o) * 8 + e] = p[q];
-            }
-        if (ch == 0) reinterpret_cast<float *>(s + (size_t)taps * ckg * 3 * CO_TILE * 8)[o] = bias[co];
-      }
-    }
-  return out;
+  return pack_conv_slabs<unsigned short, 3, true>(w, bias, cout, cin, ks, ckg, [](float v, unsigned short *pc) { split3(v, pc); });
 }
 
 template <int KS, int CKG_, int WR, int WC, bool POOL, bool RELU, bool OUT_F32>
@@ -129,7 +104,7 @@ __global__ __launch_bounds__(256) void conv_s3_kernel(const ConvArgsS3 a) {
   using T = ConvTileS3<KS, CKG_, WR, WC>;
   constexpr int NT = WR * WC, CKG = T::CKG, LW = T::LW, LH = T::LH, NSTEP = T::NSTEP;
   constexpr int TOT_P = T::BUF_P, NBUF = T::NBUF, BUF_BYTES = T::BUF_PAD * 16;
-  constexpr int NIT = T::BUF_PAD / 256;
+  constexpr int NIT = T::NIT;
   static_assert(!POOL || WR == 2, "fused pooling needs both rows of a 2x2 window in one wave");
   static_assert(!(POOL && OUT_F32), "the fp32-output layers are the unpooled heads");
 
@@ -144,21 +119,8 @@ __global__ __launch_bounds__(256) void conv_s3_kernel(const ConvArgsS3 a) {
   const size_t out_plane = (size_t)a.out_hp * a.out_wp;
   const int n_tiles = a.tiles_x * a.tiles_y * a.co_tiles * a.batch;
 
-  struct TileRef { const unsigned short *in_base, *w_base; int x0, y0, ct, img; };
-  auto decode = [&](int id) {
-    TileRef t;
-    const int tx = id % a.tiles_x;
-    id /= a.tiles_x;
-    const int ty = id % a.tiles_y;
-    id /= a.tiles_y;
-    t.ct = id % a.co_tiles;
-    t.img = id / a.co_tiles;
-    t.x0 = tx * T::TW;
-    t.y0 = ty * T::TH;
-    t.in_base = a.in + (((size_t)t.img * a.in_gtot + a.in_goff) * 3 * in_plane + (size_t)(t.y0 + PADY - T::HALO) * a.in_wp + (t.x0 + PADX - T::HALO)) * 8;
-    t.w_base = a.wpack + (size_t)t.ct * a.n_chunks * (T::W_P + T::BIAS_P) * 8;
-    return t;
-  };
+  using TileRef = spvo::TileRef<unsigned short>;
+  auto decode = [&](int id) { return decode_tile<T>(a, id, in_plane); };
 
   int piece_off[NIT];   // in 16-bit units, relative to the chunk's input / weight base
 #pragma unroll
@@ -171,12 +133,12 @@ __global__ __launch_bounds__(256) void conv_s3_kernel(const ConvArgsS3 a) {
       const int q = rem - r * LW;
       piece_off[it] = (pl * (int)in_plane + r * a.in_wp + q) * 8;
     } else {
-      piece_off[it] = (min(idx, TOT_P - 1) - T::IN_P) * 8;
+      piece_off[it] = (min(idx, T::BUF_P - 1) - T::IN_P) * 8;
     }
   }
   auto issue = [&](const TileRef &t, int chunk, unsigned char *buf) {
     const unsigned short *inb = t.in_base + (size_t)chunk * CKG * 3 * in_plane * 8;
-    const unsigned short *wb = t.w_base + (size_t)chunk * (T::W_P + T::BIAS_P) * 8;
+    const unsigned short *wb = t.w_base + (size_t)chunk * T::SLAB_P * 8;
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int idx = it * 256 + tid;

@@ -17,7 +17,9 @@
 // filter tap x 16 input channels (lane half h supplies channel group 2s + h).  A workgroup is 4 waves =
 // 64 output channels x (4*WR rows) x (32*WC columns); the reduction runs over chunks of CKG channel
 // groups whose halo tile and weight slab arrive by global_load_lds_dwordx4 in a 2-deep LDS ring.
-// The kernel is persistent with cross-tile prefetch like the fp32 one.
+// The kernel is persistent with cross-tile prefetch like the fp32 one.  The tile geometry in 16-byte pieces, the tile
+// decode, the slab packer and the launcher's tile table are shared with conv_i8.hip.h and conv_bf16x3.hip.h:
+// conv_packed.hip.h.
 //
 // At 16x the fp32 matrix rate these layers are bound by staging bandwidth (L2 -> LDS) and HBM, not
 // by the matrix pipe: DESIGN.md section 7.
@@ -25,13 +27,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <vector>
-#include "conv_mfma.hip.h"
+#include "conv_packed.hip.h"
 
 namespace spvo {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct ConvArgs16 {
   const _Float16 *in;     // C8 tensor, image 0, group 0
@@ -50,39 +51,16 @@ struct ConvArgs16 {
                                                          //        geometry (in_hp x in_wp) with cout channels, image 0
 };
 
-template <int KS, int CKG_, int WR, int WC>
-struct ConvTile16 {
-  static constexpr int CKG = CKG_;                      // channel groups (of 8) per chunk: 2 for 3x3; 4 (or 2, cin % 32 != 0) for 1x1
-  static constexpr int TH = 4 * WR, TW = 32 * WC, HALO = KS / 2;
-  static constexpr int LW = TW + 2 * HALO, LH = TH + 2 * HALO;
-  static constexpr int IN_P = CKG * LH * LW;            // 16-byte pieces: one pixel of one group
-  static constexpr int W_P = KS * KS * CKG * CO_TILE;   // one (tap, group, co) row of 8 halfs
-  static constexpr int BIAS_P = CO_TILE / 4;            // 64 fp32 biases behind the weights (chunk 0's slab)
-  static constexpr int BUF_P = IN_P + W_P + BIAS_P;
-  static constexpr int LDS_BYTES = 2 * BUF_P * 16;
-  static constexpr int NSTEP = KS * KS * (CKG / 2);
+template <int KS, int CKG_, int WR, int WC>   // CKG: channel groups (of 8) per chunk: 2 for 3x3; 4 (or 2, cin % 32 != 0) for 1x1
+struct ConvTile16 : PackedTile<KS, CKG_, WR, WC, 1, CO_TILE / 4> {   // 64 fp32 biases behind the weights (chunk 0's slab)
+  static constexpr int LDS_BYTES = 2 * ConvTile16::BUF_P * 16;
+  static constexpr int NSTEP = KS * KS * (CKG_ / 2);
 };
 
 // Host side: OIHW fp32 weights + bias -> slabs [co_tile][chunk][tap][group][co 64][8] of fp16 (round to nearest even,
 // what numpy's astype(float16) does in the oracle) followed by 64 fp32 biases (chunk 0; zeros elsewhere).
 inline std::vector<_Float16> pack_conv_weights_f16(const float *w, const float *bias, int cout, int cin, int ks, int ckg) {
-  const int co_tiles = (cout + CO_TILE - 1) / CO_TILE, ck = 8 * ckg, nch = cin / ck, taps = ks * ks;
-  const size_t slab = ((size_t)taps * ckg * CO_TILE + CO_TILE / 4) * 8;   // in halfs
-  std::vector<_Float16> out((size_t)co_tiles * nch * slab, (_Float16)0.f);
-  for (int ct = 0; ct < co_tiles; ++ct)
-    for (int ch = 0; ch < nch; ++ch) {
-      _Float16 *s = out.data() + ((size_t)ct * nch + ch) * slab;
-      for (int o = 0; o < CO_TILE; ++o) {
-        const int co = ct * CO_TILE + o;
-        if (co >= cout) continue;
-        for (int t = 0; t < taps; ++t)
-          for (int g = 0; g < ckg; ++g)
-            for (int e = 0; e < 8; ++e)
-              s[(((size_t)t * ckg + g) * CO_TILE + o) * 8 + e] = (_Float16)w[((size_t)co * cin + ch * ck + g * 8 + e) * taps + t];
-        if (ch == 0) reinterpret_cast<float *>(s + (size_t)taps * ckg * CO_TILE * 8)[o] = bias[co];
-      }
-    }
-  return out;
+  return pack_conv_slabs<_Float16, 1, true>(w, bias, cout, cin, ks, ckg, [](float v, _Float16 *pc) { pc[0] = (_Float16)v; });
 }
 
 template <int KS, int CKG_, int WR, int WC, bool POOL, bool RELU, bool OUT_F32, int EPI = 0>
@@ -90,7 +68,7 @@ __global__ __launch_bounds__(256) void conv_f16_kernel(const ConvArgs16 a) {
   using T = ConvTile16<KS, CKG_, WR, WC>;
   constexpr int NT = WR * WC, CKG = T::CKG, LW = T::LW, LH = T::LH, NSTEP = T::NSTEP;
   constexpr int TOT_P = T::BUF_P;
-  constexpr int NIT = (TOT_P + 255) / 256;
+  constexpr int NIT = T::NIT;
   static_assert(!POOL || WR == 2, "fused pooling needs both rows of a 2x2 window in one wave");
   static_assert(!(POOL && OUT_F32), "the fp32-output layers are the unpooled heads");
   static_assert(EPI == 0 || !OUT_F32, "BatchNorm / residual epilogues write C8");
@@ -106,21 +84,8 @@ __global__ __launch_bounds__(256) void conv_f16_kernel(const ConvArgs16 a) {
   const size_t out_plane = (size_t)a.out_hp * a.out_wp;
   const int n_tiles = a.tiles_x * a.tiles_y * a.co_tiles * a.batch;
 
-  struct TileRef { const _Float16 *in_base, *w_base; int x0, y0, ct, img; };
-  auto decode = [&](int id) {
-    TileRef t;
-    const int tx = id % a.tiles_x;
-    id /= a.tiles_x;
-    const int ty = id % a.tiles_y;
-    id /= a.tiles_y;
-    t.ct = id % a.co_tiles;
-    t.img = id / a.co_tiles;
-    t.x0 = tx * T::TW;
-    t.y0 = ty * T::TH;
-    t.in_base = a.in + (((size_t)t.img * a.in_gtot + a.in_goff) * in_plane + (size_t)(t.y0 + PADY - T::HALO) * a.in_wp + (t.x0 + PADX - T::HALO)) * 8;
-    t.w_base = a.wpack + (size_t)t.ct * a.n_chunks * (T::W_P + T::BIAS_P) * 8;
-    return t;
-  };
+  using TileRef = spvo::TileRef<_Float16>;
+  auto decode = [&](int id) { return decode_tile<T>(a, id, in_plane); };
 
   // staging plan: this thread's 16-byte pieces of a chunk (input halo tile first, then the weight slab)
   int piece_off[NIT];   // in halfs, relative to the chunk's input / weight base
@@ -139,7 +104,7 @@ __global__ __launch_bounds__(256) void conv_f16_kernel(const ConvArgs16 a) {
   }
   auto issue = [&](const TileRef &t, int chunk, unsigned char *buf) {
     const _Float16 *inb = t.in_base + (size_t)chunk * CKG * in_plane * 8;
-    const _Float16 *wb = t.w_base + (size_t)chunk * (T::W_P + T::BIAS_P) * 8;
+    const _Float16 *wb = t.w_base + (size_t)chunk * T::SLAB_P * 8;
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int idx = it * 256 + tid;

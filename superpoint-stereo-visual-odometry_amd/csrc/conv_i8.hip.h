@@ -11,7 +11,8 @@
 // group planes with the usual zero border (q = 0 is the real value 0: the quantisation is symmetric).  As in
 // conv_f16.hip.h that is the operand shape of the matrix instruction (lane = one pixel x 16 consecutive k), so an
 // operand is one ds_read_b128.  Tiling, LDS ring, persistence and the k-step order are those of conv_f16.hip.h;
-// a k-step is one filter tap x 32 input channels.
+// a k-step is one filter tap x 32 input channels.  The tile geometry, the tile decode, the slab packer and the
+// launcher's tile table are the shared ones of conv_packed.hip.h.
 //
 // Epilogue (per output value, in this order):  r = f32(acc) * m[co];  r = r + bias[co];  [ReLU]
 // [r = r * bn_scale[co]; r = r + bn_shift[co]; ReLU]  [r = r + f32(res_q) * s_res; ReLU]  [2x2 max]  then either
@@ -20,7 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <vector>
-#include "conv_mfma.hip.h"
+#include "conv_packed.hip.h"
 
 namespace spvo {
 
@@ -43,16 +44,10 @@ struct ConvArgs8 {
   int cout, n_chunks, tiles_x, tiles_y, co_tiles, batch;
 };
 
-template <int KS, int CKG_, int WR, int WC>
-struct ConvTile8 {
-  static constexpr int CKG = CKG_;                      // channel groups (of 16) per chunk: 2 for 3x3; 4 (or 2) for 1x1
-  static constexpr int TH = 4 * WR, TW = 32 * WC, HALO = KS / 2;
-  static constexpr int LW = TW + 2 * HALO, LH = TH + 2 * HALO;
-  static constexpr int IN_P = CKG * LH * LW;            // 16-byte pieces: one pixel of one group
-  static constexpr int W_P = KS * KS * CKG * CO_TILE;   // one (tap, group, co) row of 16 input channels
-  static constexpr int BUF_P = IN_P + W_P;
-  static constexpr int LDS_BYTES = 2 * BUF_P * 16;
-  static constexpr int NSTEP = KS * KS * (CKG / 2);
+template <int KS, int CKG_, int WR, int WC>   // CKG: channel groups (of 16) per chunk: 2 for 3x3; 4 (or 2) for 1x1
+struct ConvTile8 : PackedTile<KS, CKG_, WR, WC, 1, 0> {   // (the bias is an argument of the requantisation, not a slab row)
+  static constexpr int LDS_BYTES = 2 * ConvTile8::BUF_P * 16;
+  static constexpr int NSTEP = KS * KS * (CKG_ / 2);
 };
 
 // Host side.  Per-output-channel symmetric quantisation exactly as oracle/net_int8.py: ws = max|w[co]| / 127 (fp32
@@ -74,22 +69,7 @@ inline void quantize_conv_weights(const float *w, int cout, int per_co, std::vec
 
 // quantised OIHW weights -> slabs [co_tile][chunk][tap][group][co 64][16]
 inline std::vector<int8_t> pack_conv_weights_i8(const int8_t *wq, int cout, int cin, int ks, int ckg) {
-  const int co_tiles = (cout + CO_TILE - 1) / CO_TILE, ck = 16 * ckg, nch = cin / ck, taps = ks * ks;
-  const size_t slab = (size_t)taps * ckg * CO_TILE * 16;
-  std::vector<int8_t> out((size_t)co_tiles * nch * slab, 0);
-  for (int ct = 0; ct < co_tiles; ++ct)
-    for (int ch = 0; ch < nch; ++ch) {
-      int8_t *s = out.data() + ((size_t)ct * nch + ch) * slab;
-      for (int o = 0; o < CO_TILE; ++o) {
-        const int co = ct * CO_TILE + o;
-        if (co >= cout) continue;
-        for (int t = 0; t < taps; ++t)
-          for (int g = 0; g < ckg; ++g)
-            for (int e = 0; e < 16; ++e)
-              s[(((size_t)t * ckg + g) * CO_TILE + o) * 16 + e] = wq[((size_t)co * cin + ch * ck + g * 16 + e) * taps + t];
-      }
-    }
-  return out;
+  return pack_conv_slabs<int8_t, 1, false>(wq, nullptr, cout, cin, ks, ckg, [](int8_t v, int8_t *pc) { pc[0] = v; });
 }
 
 __device__ __forceinline__ int quantize_i8(float r, float inv_s) {
@@ -101,7 +81,7 @@ __global__ __launch_bounds__(256) void conv_i8_kernel(const ConvArgs8 a) {
   using T = ConvTile8<KS, CKG_, WR, WC>;
   constexpr int NT = WR * WC, CKG = T::CKG, LW = T::LW, LH = T::LH, NSTEP = T::NSTEP;
   constexpr int TOT_P = T::BUF_P;
-  constexpr int NIT = (TOT_P + 255) / 256;
+  constexpr int NIT = T::NIT;
   static_assert(!POOL || WR == 2, "fused pooling needs both rows of a 2x2 window in one wave");
   static_assert(!(POOL && OUT_F32), "the fp32-output layers are the unpooled heads");
   static_assert(EPI == 0 || !OUT_F32, "BatchNorm / residual epilogues write C16");
@@ -117,21 +97,8 @@ __global__ __launch_bounds__(256) void conv_i8_kernel(const ConvArgs8 a) {
   const size_t out_plane = (size_t)a.out_hp * a.out_wp;
   const int n_tiles = a.tiles_x * a.tiles_y * a.co_tiles * a.batch;
 
-  struct TileRef { const int8_t *in_base, *w_base; int x0, y0, ct, img; };
-  auto decode = [&](int id) {
-    TileRef t;
-    const int tx = id % a.tiles_x;
-    id /= a.tiles_x;
-    const int ty = id % a.tiles_y;
-    id /= a.tiles_y;
-    t.ct = id % a.co_tiles;
-    t.img = id / a.co_tiles;
-    t.x0 = tx * T::TW;
-    t.y0 = ty * T::TH;
-    t.in_base = a.in + (((size_t)t.img * a.in_gtot + a.in_goff) * in_plane + (size_t)(t.y0 + PADY - T::HALO) * a.in_wp + (t.x0 + PADX - T::HALO)) * 16;
-    t.w_base = a.wpack + (size_t)t.ct * a.n_chunks * T::W_P * 16;
-    return t;
-  };
+  using TileRef = spvo::TileRef<int8_t>;
+  auto decode = [&](int id) { return decode_tile<T>(a, id, in_plane); };
 
   int piece_off[NIT];   // in bytes, relative to the chunk's input / weight base
 #pragma unroll
@@ -149,7 +116,7 @@ __global__ __launch_bounds__(256) void conv_i8_kernel(const ConvArgs8 a) {
   }
   auto issue = [&](const TileRef &t, int chunk, unsigned char *buf) {
     const int8_t *inb = t.in_base + (size_t)chunk * CKG * in_plane * 16;
-    const int8_t *wb = t.w_base + (size_t)chunk * T::W_P * 16;
+    const int8_t *wb = t.w_base + (size_t)chunk * T::SLAB_P * 16;
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int idx = it * 256 + tid;

@@ -812,7 +812,7 @@ void set_release_match(SubmitSet &s);      // h_match_out and the cache entries 
 void set_release_segments(SubmitSet &s);   // the graphs of its launch segments (seg_free_all)
 // ---- spvo_plan.hip
 void free_plan(spvo_ctx *c);
-// a tiled layer's co_tiles and tile (wr, wc) -- it offers the tiles the launchers' `switch (key)` tables have a case for; returns the channels
+// a tiled layer's co_tiles and tile (wr, wc) -- it offers the tiles the launchers' tables have a case for (FP32: `switch (key)` in spvo_net_f32.hip; the others: with_tile_variant, conv_packed.hip.h); returns the channels
 // per chunk of the FP32 direct kernel (the other kinds chunk by their own rule)
 int choose_variant(const spvo_ctx *c, Op &op, const Tensor &ti, bool split = false);
 int upload_stem(spvo_ctx *c, Op &op, const float *w, const float *b);   // d_w, d_b of a plain single-channel-input layer: OIHW weights and bias as they are

@@ -89,44 +89,22 @@ int launch_conv16(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t st
   a.tiles_x = a.tiles_y = 0;
   a.batch = batch;
   const bool out_f32 = !to.f16;
-  const int key = op.ks * 10000 + (op.ck / 8) * 1000 + op.wr * 100 + op.wc * 10 + (pool ? 1 : 0);   // ks, groups per chunk, wr, wc, pool
+  const int key = op.ks * 10000 + (op.ck / 8) * 1000 + op.wr * 100 + op.wc * 10 + (pool ? 1 : 0);   // ks, groups per chunk, wr, wc, pool: for the error text only (the table is with_tile_variant)
   const int epi = (op.flags & FLAG_BN) ? 1 : (op.flags & FLAG_ADD) ? 2 : 0;
   if (epi) {
     a.bn_scale = op.d_bn_scale; a.bn_shift = op.d_bn_shift;
     if (epi == 2) a.residual = (const _Float16 *)ring_ptr(c, c->tensors[op.residual], img0);
-    switch (key) {
-      case 14220: return launch_conv16_epi<4, 2, 2, false>(c, a, epi, stream);
-      case 14120: return launch_conv16_epi<4, 1, 2, false>(c, a, epi, stream);
-      case 14110: return launch_conv16_epi<4, 1, 1, false>(c, a, epi, stream);
-      case 14221: return launch_conv16_epi<4, 2, 2, true>(c, a, epi, stream);
-      case 14211: return launch_conv16_epi<4, 2, 1, true>(c, a, epi, stream);
-      case 12220: return launch_conv16_epi<2, 2, 2, false>(c, a, epi, stream);
-      case 12120: return launch_conv16_epi<2, 1, 2, false>(c, a, epi, stream);
-      case 12110: return launch_conv16_epi<2, 1, 1, false>(c, a, epi, stream);
-      case 12221: return launch_conv16_epi<2, 2, 2, true>(c, a, epi, stream);
-      case 12211: return launch_conv16_epi<2, 2, 1, true>(c, a, epi, stream);
-      default: return fail(c, SPVO_ERR_INVALID, "no fp16 conv kernel variant for key %d with epilogue %d", key, epi);
-    }
   }
-  switch (key) {
-    case 32220: return launch_conv16_variant<3, 2, 2, 2, false>(c, a, relu, out_f32, stream);
-    case 32210: return launch_conv16_variant<3, 2, 2, 1, false>(c, a, relu, out_f32, stream);
-    case 32120: return launch_conv16_variant<3, 2, 1, 2, false>(c, a, relu, out_f32, stream);
-    case 32110: return launch_conv16_variant<3, 2, 1, 1, false>(c, a, relu, out_f32, stream);
-    case 32221: return launch_conv16_variant<3, 2, 2, 2, true>(c, a, relu, out_f32, stream);
-    case 32211: return launch_conv16_variant<3, 2, 2, 1, true>(c, a, relu, out_f32, stream);
-    case 14220: return launch_conv16_variant<1, 4, 2, 2, false>(c, a, relu, out_f32, stream);
-    case 14120: return launch_conv16_variant<1, 4, 1, 2, false>(c, a, relu, out_f32, stream);
-    case 14110: return launch_conv16_variant<1, 4, 1, 1, false>(c, a, relu, out_f32, stream);
-    case 14221: return launch_conv16_variant<1, 4, 2, 2, true>(c, a, relu, out_f32, stream);
-    case 14211: return launch_conv16_variant<1, 4, 2, 1, true>(c, a, relu, out_f32, stream);
-    case 12220: return launch_conv16_variant<1, 2, 2, 2, false>(c, a, relu, out_f32, stream);
-    case 12120: return launch_conv16_variant<1, 2, 1, 2, false>(c, a, relu, out_f32, stream);
-    case 12110: return launch_conv16_variant<1, 2, 1, 1, false>(c, a, relu, out_f32, stream);
-    case 12221: return launch_conv16_variant<1, 2, 2, 2, true>(c, a, relu, out_f32, stream);
-    case 12211: return launch_conv16_variant<1, 2, 2, 1, true>(c, a, relu, out_f32, stream);
-    default: return fail(c, SPVO_ERR_INVALID, "no fp16 conv kernel variant for key %d", key);
-  }
+  auto no_variant = [&] {
+    return epi ? fail(c, SPVO_ERR_INVALID, "no fp16 conv kernel variant for key %d with epilogue %d", key, epi)
+               : fail(c, SPVO_ERR_INVALID, "no fp16 conv kernel variant for key %d", key);
+  };
+  return with_tile_variant<2, 4, 2>(op.ks, op.ck / 8, op.wr, op.wc, pool, [&](auto v) {
+    using V = decltype(v);
+    if (!epi) return launch_conv16_variant<V::KS, V::CKG, V::WR, V::WC, V::POOL>(c, a, relu, out_f32, stream);
+    if constexpr (V::KS == 1) return launch_conv16_epi<V::CKG, V::WR, V::WC, V::POOL>(c, a, epi, stream);   // (the 1x1 layers have the epilogue forms)
+    else return no_variant();
+  }, no_variant);
 }
 
 int launch_maxpool_f16(spvo_ctx *c, const Tensor &ti, const Tensor &to, const float *tin, float *tout, int batch, hipStream_t stream) {

@@ -230,26 +230,11 @@ int launch_conv8(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t str
   const int epi = (op.flags & FLAG_BN) ? 1 : (op.flags & FLAG_ADD) ? 2 : 0;
   if (epi == 2) a.residual = (const int8_t *)ring_ptr(c, c->tensors[op.residual], img0);
   const bool out_f32 = !to.i8;
-  const int key = op.ks * 10000 + (op.ck / 16) * 1000 + op.wr * 100 + op.wc * 10 + (pool ? 1 : 0);   // ks, groups per chunk, wr, wc, pool
-  switch (key) {
-    case 32220: return launch_conv8_variant<3, 2, 2, 2, false>(c, a, relu, out_f32, epi, stream);
-    case 32210: return launch_conv8_variant<3, 2, 2, 1, false>(c, a, relu, out_f32, epi, stream);
-    case 32120: return launch_conv8_variant<3, 2, 1, 2, false>(c, a, relu, out_f32, epi, stream);
-    case 32110: return launch_conv8_variant<3, 2, 1, 1, false>(c, a, relu, out_f32, epi, stream);
-    case 32221: return launch_conv8_variant<3, 2, 2, 2, true>(c, a, relu, out_f32, epi, stream);
-    case 32211: return launch_conv8_variant<3, 2, 2, 1, true>(c, a, relu, out_f32, epi, stream);
-    case 14220: return launch_conv8_variant<1, 4, 2, 2, false>(c, a, relu, out_f32, epi, stream);
-    case 14120: return launch_conv8_variant<1, 4, 1, 2, false>(c, a, relu, out_f32, epi, stream);
-    case 14110: return launch_conv8_variant<1, 4, 1, 1, false>(c, a, relu, out_f32, epi, stream);
-    case 14221: return launch_conv8_variant<1, 4, 2, 2, true>(c, a, relu, out_f32, epi, stream);
-    case 14211: return launch_conv8_variant<1, 4, 2, 1, true>(c, a, relu, out_f32, epi, stream);
-    case 12220: return launch_conv8_variant<1, 2, 2, 2, false>(c, a, relu, out_f32, epi, stream);
-    case 12120: return launch_conv8_variant<1, 2, 1, 2, false>(c, a, relu, out_f32, epi, stream);
-    case 12110: return launch_conv8_variant<1, 2, 1, 1, false>(c, a, relu, out_f32, epi, stream);
-    case 12221: return launch_conv8_variant<1, 2, 2, 2, true>(c, a, relu, out_f32, epi, stream);
-    case 12211: return launch_conv8_variant<1, 2, 2, 1, true>(c, a, relu, out_f32, epi, stream);
-    default: return fail(c, SPVO_ERR_INVALID, "no int8 conv kernel variant for key %d", key);
-  }
+  const int key = op.ks * 10000 + (op.ck / 16) * 1000 + op.wr * 100 + op.wc * 10 + (pool ? 1 : 0);   // ks, groups per chunk, wr, wc, pool: for the error text only (the table is with_tile_variant)
+  return with_tile_variant<2, 4, 2>(op.ks, op.ck / 16, op.wr, op.wc, pool, [&](auto v) {
+    using V = decltype(v);
+    return launch_conv8_variant<V::KS, V::CKG, V::WR, V::WC, V::POOL>(c, a, relu, out_f32, epi, stream);
+  }, [&] { return fail(c, SPVO_ERR_INVALID, "no int8 conv kernel variant for key %d", key); });
 }
 
 // the fused tail of an INT8 engine (heads_i8.hip.h): ops head_start .. head_start + 2 in one launch

@@ -65,21 +65,11 @@ int launch_conv_s3(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t s
   a.tiles_x = a.tiles_y = 0;
   a.batch = batch;
   const bool out_f32 = !to.s3;
-  const int key = op.ks * 1000 + op.wr * 100 + op.wc * 10 + (pool ? 1 : 0);
-  switch (key) {
-    case 3220: return launch_conv_s3_variant<3, 1, 2, 2, false>(c, a, relu, out_f32, stream);
-    case 3210: return launch_conv_s3_variant<3, 1, 2, 1, false>(c, a, relu, out_f32, stream);
-    case 3120: return launch_conv_s3_variant<3, 1, 1, 2, false>(c, a, relu, out_f32, stream);
-    case 3110: return launch_conv_s3_variant<3, 1, 1, 1, false>(c, a, relu, out_f32, stream);
-    case 3221: return launch_conv_s3_variant<3, 1, 2, 2, true>(c, a, relu, out_f32, stream);
-    case 3211: return launch_conv_s3_variant<3, 1, 2, 1, true>(c, a, relu, out_f32, stream);
-    case 1220: return launch_conv_s3_variant<1, 2, 2, 2, false>(c, a, relu, out_f32, stream);
-    case 1120: return launch_conv_s3_variant<1, 2, 1, 2, false>(c, a, relu, out_f32, stream);
-    case 1110: return launch_conv_s3_variant<1, 2, 1, 1, false>(c, a, relu, out_f32, stream);
-    case 1221: return launch_conv_s3_variant<1, 2, 2, 2, true>(c, a, relu, out_f32, stream);
-    case 1211: return launch_conv_s3_variant<1, 2, 2, 1, true>(c, a, relu, out_f32, stream);
-    default: return fail(c, SPVO_ERR_INVALID, "no split-fp32 conv kernel variant for key %d", key);
-  }
+  const int key = op.ks * 1000 + op.wr * 100 + op.wc * 10 + (pool ? 1 : 0);   // for the error text only (the table is with_tile_variant)
+  return with_tile_variant<1, 2, 0>(op.ks, op.ck / 8, op.wr, op.wc, pool, [&](auto v) {
+    using V = decltype(v);
+    return launch_conv_s3_variant<V::KS, V::CKG, V::WR, V::WC, V::POOL>(c, a, relu, out_f32, stream);
+  }, [&] { return fail(c, SPVO_ERR_INVALID, "no split-fp32 conv kernel variant for key %d", key); });
 }
 
 void launch_unpad_s3(const Tensor &t, int batch, float *dst, hipStream_t stream) {
