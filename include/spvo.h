@@ -84,6 +84,17 @@ int spvo_engine_precision(const spvo_ctx *ctx);
  * nn.cpp:43-137); other graphs fail at spvo_load_weights. */
 int spvo_set_fp32_split(spvo_ctx *ctx, int enable);
 
+/* Opt-in mode for INT8 engines loaded AFTER the call (process-wide default: spvo_set_tuning "int8_general", 0; this call
+ * overrides it for the context): the loader also accepts the two things the squeeze graph needs and the default refuses --
+ *   - a stand-alone 2x2/2 max-pool between two int8 tensors of equal channel count, one level apart, on a map of even height
+ *     and width: q_o = clip(rint(f32(max of the four q_i) * m), -127, 127) with m = f32(s_i * (f32(1) / s_o)), one fp32
+ *     multiply per value, round-half-even (csrc/conv_i8.hip.h, maxpool2_i8_kernel);
+ *   - a convolution whose cin is 16 more than a multiple of 32 (16, 48, ...): its last chunk holds one group of 16 channels
+ *     and is padded with zero weights, so the int32 accumulator stays the exact sum over the real cin.
+ * The arithmetic of everything else is unchanged: an engine the default mode loads gives the same bits in this mode.  With
+ * the mode off both stay refused at spvo_load_weights, with SPVO_ERR_IO.  SPVO_ERR_INVALID for a null context. */
+int spvo_set_int8_general(spvo_ctx *ctx, int enable);
+
 /* preprocessImageImpl (base.cpp:68-121) + preprocessImage (nn.cpp:139-161):
  * centre-crop to the network aspect ratio, cv::resize(INTER_LINEAR) 8-bit
  * fixed-point semantics, scale P rows 0-1.  `P` (3x4 row-major, f64) is
@@ -1042,7 +1053,7 @@ int spvo_profile_stage_fused(spvo_ctx *ctx, const char *stage, int info[8]);
  * of the process that hosts it (a ROS node) cannot change kernels by accident.  Process-wide; a value takes effect for contexts
  * created / engines loaded afterwards.  `name` is one of the names INTEGRATION.md lists ("winograd", "wino4", "wino4_item", "wino_narrow",
  * "wino_dynamic", "winograd_min_tiles", "wino4_min_tiles", "merge_siblings", "heads_fused", "heads_on_net", "heads_split",
- * "match_fused", "fp32_split", "prematch", "spin_wait", "trunk_timing", "solve_timing", "nms_first", "upload_side", "conv_variant"); SPVO_ERR_INVALID for any other.
+ * "match_fused", "fp32_split", "prematch", "spin_wait", "trunk_timing", "solve_timing", "nms_first", "upload_side", "conv_variant", "int8_general"); SPVO_ERR_INVALID for any other.
  * spvo_get_tuning returns the value set, or `dflt`; spvo_clear_tuning forgets every value.
  * "wino4_item" selects the item of the F(4x4,3x3) kernel: 3 (the default), 2, 1 or 0, oldest last; all four give the same bits. */
 int spvo_set_tuning(const char *name, int value);

@@ -42,7 +42,10 @@ struct ConvArgs8 {
   int in_hp, in_wp, in_gtot, in_goff;     // groups of 16 channels
   int out_hp, out_wp, out_ctot, out_coff; // channels
   int cout, n_chunks, tiles_x, tiles_y, co_tiles, batch;
+  int in_groups = 0;      // groups of 16 channels the op reads (cin / 16); read by the ODD instances only
+  int pad_ = 0;           // (no implicit padding: launch_segments.hip.h compares recorded argument bytes)
 };
+static_assert(sizeof(ConvArgs8) == 8 * sizeof(void *) + 2 * sizeof(float) + 18 * sizeof(int), "ConvArgs8 has implicit padding");
 
 template <int KS, int CKG_, int WR, int WC>   // CKG: channel groups (of 16) per chunk: 2 for 3x3; 4 (or 2) for 1x1
 struct ConvTile8 : PackedTile<KS, CKG_, WR, WC, 1, 0> {   // (the bias is an argument of the requantisation, not a slab row)
@@ -76,7 +79,13 @@ __device__ __forceinline__ int quantize_i8(float r, float inv_s) {
   return (int)fminf(127.f, fmaxf(-127.f, rintf(mul_rn(r, inv_s))));
 }
 
-template <int KS, int CKG_, int WR, int WC, bool POOL, bool RELU, bool OUT_F32, int EPI = 0>
+// ODD (opt-in mode "int8_general", spvo_set_int8_general): the op reads an odd number of 16-channel groups (cin = 16, 48, ...), so the
+// last chunk has ONE group.  The slab packer pads the missing group's weights with zeros, and the staging reads the chunk's existing
+// group a second time in its place -- where the missing group would lie is the first group of the next image, or memory behind the
+// last tensor -- so the padded half of the k-step adds integer zeros: the accumulator is the exact sum over the real cin, whatever
+// the values staged.  Half of the last chunk's matrix work is wasted (all of it for cin = 16, a quarter for 48).  ODD = false
+// instances are the kernel as it was, instruction for instruction.
+template <int KS, int CKG_, int WR, int WC, bool POOL, bool RELU, bool OUT_F32, int EPI = 0, bool ODD = false>
 __global__ __launch_bounds__(256) void conv_i8_kernel(const ConvArgs8 a) {
   using T = ConvTile8<KS, CKG_, WR, WC>;
   constexpr int NT = WR * WC, CKG = T::CKG, LW = T::LW, LH = T::LH, NSTEP = T::NSTEP;
@@ -114,13 +123,24 @@ __global__ __launch_bounds__(256) void conv_i8_kernel(const ConvArgs8 a) {
       piece_off[it] = (min(idx, TOT_P - 1) - T::IN_P) * 16;
     }
   }
-  auto issue = [&](const TileRef &t, int chunk, unsigned char *buf) {
-    const int8_t *inb = t.in_base + (size_t)chunk * CKG * in_plane * 16;
-    const int8_t *wb = t.w_base + (size_t)chunk * T::SLAB_P * 16;
+  static_assert(!ODD || CKG_ == 2, "a chunk of one group exists for chunks of two");
+  int piece_one[ODD ? NIT : 1];   // ODD: the same for a chunk whose second group does not exist: its pieces are the first group's
+  if constexpr (ODD) {
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int idx = it * 256 + tid;
-      const int8_t *src = ((idx < T::IN_P) ? inb : wb) + piece_off[it];
+      piece_one[it] = (idx < T::IN_P && idx >= LH * LW) ? piece_off[it] - (int)in_plane * 16 : piece_off[it];
+    }
+  }
+  auto issue = [&](const TileRef &t, int chunk, unsigned char *buf) {
+    const int8_t *inb = t.in_base + (size_t)chunk * CKG * in_plane * 16;
+    const int8_t *wb = t.w_base + (size_t)chunk * T::SLAB_P * 16;
+    const bool one = ODD && 2 * chunk + 1 >= a.in_groups;   // (uniform: the last chunk of an op with an odd group count)
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int idx = it * 256 + tid;
+      const int off = one ? piece_one[ODD ? it : 0] : piece_off[it];
+      const int8_t *src = ((idx < T::IN_P) ? inb : wb) + off;
       if (it < NIT - 1 || idx < TOT_P)
         glds16(reinterpret_cast<const float *>(src), reinterpret_cast<float *>(buf + (size_t)(it * 256 + wave * 64) * 16));
     }
@@ -369,6 +389,39 @@ __global__ __launch_bounds__(256) void dwconv3x3_i8_kernel(const int8_t *__restr
     pk[d] = (int)u;
   }
   reinterpret_cast<i32x4 *>(out)[(size_t)pg * plane + (size_t)(y + PADY) * wp + (x + PADX)] = pk;
+}
+
+// Stand-alone 2x2/2 max-pool on C16 (opt-in mode "int8_general": the squeeze graph's pools behind a Concat, which no convolution can
+// take into its epilogue), from int8 tensor i (scale s_i) to int8 tensor o (scale s_o).  The arithmetic, defined here and in
+// tests/int8_general_ref.py:
+//     inv = f32(1) / f32(s_o)                                      one fp32 division, on the host
+//     m   = f32(f32(s_i) * inv)                                    one fp32 multiply, on the host (Op::pool_m)
+//     q_o = clip(rint(f32(max of the four q_i) * m), -127, 127)    one fp32 multiply per value, round-half-even
+// The four q_i are integers of magnitude at most 127, so f32() of their maximum is exact.  One thread = one output pixel x 16
+// channels: four 16-byte loads, a signed maximum per byte, one 16-byte store; the group is blockIdx.z.  The padded border of the
+// output plane is never written and stays zero.
+template <int UNUSED = 0>   // (a template so that every translation unit may include this header)
+__global__ __launch_bounds__(256) void maxpool2_i8_kernel(const int8_t *__restrict__ in, int8_t *__restrict__ out, float m, int OH, int OW,
+                                                           int in_hp, int in_wp, int out_hp, int out_wp) {
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  const int g = blockIdx.z;   // image * groups + group
+  if (x >= OW || y >= OH) return;
+  const i32x4 *ip = reinterpret_cast<const i32x4 *>(in) + (size_t)g * in_hp * in_wp + (size_t)(2 * y + PADY) * in_wp + (2 * x + PADX);
+  const i32x4 a0 = ip[0], a1 = ip[1], b0 = ip[in_wp], b1 = ip[in_wp + 1];
+  auto byte = [](const i32x4 &v, int e) { return (int)(int8_t)((unsigned)v[e >> 2] >> (8 * (e & 3))); };
+  i32x4 pk;
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    unsigned u = 0;
+#pragma unroll
+    for (int e = 4 * d; e < 4 * d + 4; ++e) {
+      const int mx = max(max(byte(a0, e), byte(a1, e)), max(byte(b0, e), byte(b1, e)));
+      u |= ((unsigned)quantize_i8((float)mx, m) & 0xFFu) << (8 * (e & 3));
+    }
+    pk[d] = (int)u;
+  }
+  reinterpret_cast<i32x4 *>(out)[(size_t)g * out_hp * out_wp + (size_t)(y + PADY) * out_wp + (x + PADX)] = pk;
 }
 
 // C16 int8 -> dense NCHW fp32 holding the integer values q (spvo_debug_tensor)

@@ -70,7 +70,7 @@ __device__ __forceinline__ auto decode_tile(const Args &a, int id, size_t in_pla
 template <class E, int PLANES, bool BIAS, class S, class Split>
 inline std::vector<E> pack_conv_slabs(const S *w, const float *bias, int cout, int cin, int ks, int ckg, Split split) {
   constexpr int EPP = 16 / sizeof(E);
-  const int co_tiles = (cout + CO_TILE - 1) / CO_TILE, ck = EPP * ckg, nch = cin / ck, taps = ks * ks;
+  const int co_tiles = (cout + CO_TILE - 1) / CO_TILE, ck = EPP * ckg, nch = (cin + ck - 1) / ck, taps = ks * ks;   // (a last chunk that cin does not fill keeps zeros in the groups it lacks: INT8 engines, conv_i8.hip.h ODD)
   const size_t rows = (size_t)taps * ckg * PLANES * CO_TILE * EPP, slab = rows + (BIAS ? CO_TILE / 4 * EPP : 0);   // in elements
   std::vector<E> out((size_t)co_tiles * nch * slab, (E)0);
   for (int ct = 0; ct < co_tiles; ++ct)
@@ -82,6 +82,7 @@ inline std::vector<E> pack_conv_slabs(const S *w, const float *bias, int cout, i
         for (int t = 0; t < taps; ++t)
           for (int g = 0; g < ckg; ++g)
             for (int e = 0; e < EPP; ++e) {
+              if (ch * ck + g * EPP + e >= cin) continue;
               E pc[PLANES];
               split(w[((size_t)co * cin + ch * ck + g * EPP + e) * taps + t], pc);
               for (int q = 0; q < PLANES; ++q) s[((((size_t)t * ckg + g) * PLANES + q) * CO_TILE + o) * EPP + e] = pc[q];

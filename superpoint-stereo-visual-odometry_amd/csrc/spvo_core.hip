@@ -32,7 +32,7 @@ int stage_id(spvo_ctx *c, const std::string &name) {
 // ---- diagnostic switches (include/spvo.h: spvo_set_tuning).  One process-wide table, filled by explicit calls only.
 namespace {
 const char *const kTuningNames[] = {"winograd", "wino4", "wino4_item", "wino_narrow", "wino_dynamic", "winograd_min_tiles", "wino4_min_tiles", "merge_siblings", "heads_fused",
-                                    "heads_on_net", "heads_split", "match_fused", "fp32_split", "prematch", "spin_wait", "trunk_timing", "solve_timing", "nms_first", "upload_side", "inject_launch_failure", "int8_fused", "pair_always", "preprocess_fused", "heads_keep_raw", "tail_streams", "solve_collect_first", "graphs", "solve_fuse", "solve_keep", "sift_describe_form", "sift_pair_waves_per_cu", "sift_brisk_recheck", "conv_variant"};
+                                    "heads_on_net", "heads_split", "match_fused", "fp32_split", "prematch", "spin_wait", "trunk_timing", "solve_timing", "nms_first", "upload_side", "inject_launch_failure", "int8_fused", "pair_always", "preprocess_fused", "heads_keep_raw", "tail_streams", "solve_collect_first", "graphs", "solve_fuse", "solve_keep", "sift_describe_form", "sift_pair_waves_per_cu", "sift_brisk_recheck", "conv_variant", "int8_general"};
 constexpr int kTuningCount = sizeof kTuningNames / sizeof kTuningNames[0];
 std::mutex g_tuning_mutex;
 bool g_tuning_set[kTuningCount] = {};
@@ -350,6 +350,7 @@ int spvo_create(const spvo_config *cfg, spvo_ctx **out) {
   }
   c->post = c->stream;
   c->split_req = tuning("fp32_split", 0) != 0;
+  c->int8_general_req = tuning("int8_general", 0) != 0;
   int rc = SPVO_OK;
   const size_t hw = (size_t)c->H * c->W;
   const int cap = cfg->max_keypoints;
@@ -411,6 +412,12 @@ void spvo_destroy(spvo_ctx *c) {
 int spvo_set_fp32_split(spvo_ctx *c, int enable) {
   if (!c) return SPVO_ERR_INVALID;
   c->split_req = enable != 0;
+  return SPVO_OK;
+}
+
+int spvo_set_int8_general(spvo_ctx *c, int enable) {
+  if (!c) return SPVO_ERR_INVALID;
+  c->int8_general_req = enable != 0;
   return SPVO_OK;
 }
 
@@ -501,6 +508,7 @@ int spvo_profile_stage_kernel(spvo_ctx *c, const char *stage, char *name, size_t
       else if (op.wino) { k = "conv_wino2_kernel"; f = 4.0 / 9.0; }
       else k = "conv_mfma_kernel";
     }
+    if (op.type == OP_MAXPOOL && c->int8) k = "maxpool2_i8_kernel";   // (int8_general)
     if (op.type == OP_DWCONV) k = c->int8 ? "dwconv3x3_i8_kernel" : c->fp16 ? "dwconv3x3_f16_kernel" : "dwconv3x3_kernel";
     if (name && name_cap) { std::strncpy(name, k, name_cap - 1); name[name_cap - 1] = 0; }
     if (executed_per_algorithmic) *executed_per_algorithmic = f;

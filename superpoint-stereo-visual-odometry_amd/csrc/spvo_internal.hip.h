@@ -115,6 +115,7 @@ struct Op {
   bool fused_away = false;     // INT8 engines: this op's work is done by a later op's launch
   float *d_qm = nullptr;       // INT8 engines: weight scale * input scale per output channel
   float inv_s_out = 0.f, s_res = 0.f;
+  float pool_m = 0.f;          // INT8 engines, stand-alone max-pool (int8_general): f32(s_in * (1 / s_out)), the kernel's one multiplier
   double flops_per_image = 0;
   int stage = -1;
   mutable int launch_tiles = 0, launch_wgs = 0;   // tiled kernels: tiles and workgroups of this op's most recent launch (spvo_profile_stage_variant)
@@ -320,6 +321,7 @@ struct spvo_ctx {
   bool fp16 = false;               // the loaded engine's precision
   bool split_req = false;          // spvo_set_fp32_split / SPVO_FP32_SPLIT: FP32 engines loaded from now on run on the bf16x3 kernels
   bool s3 = false;                 // the loaded FP32 engine runs in split mode
+  bool int8_general_req = false;   // spvo_set_int8_general / tuning "int8_general": INT8 engines loaded from now on accept a stand-alone max-pool and a cin of 16 more than a multiple of 32
   size_t head_start = 0;           // ops [head_start, end) = the 1x1 heads + L2 norm: a submission runs them on the tail stream
   int launch_tiles = 0, launch_wgs = 0;   // what the tiled kernels' launchers (launch_conv*_instance) last enqueued; launch_op copies them to its op
   int launch_block = 0;                   // ... and launch_dwpw8_instance: its instance (Op::launch_block)
@@ -826,6 +828,7 @@ int prepare_conv_f16(spvo_ctx *c, unsigned i, const float *w, const float *b);
 int prepare_conv_s3(spvo_ctx *c, unsigned i, const float *w, const float *b);
 int prepare_conv_i8(spvo_ctx *c, unsigned i, const float *w, const float *b);
 int prepare_dwconv_i8(spvo_ctx *c, unsigned i, const float *w, const float *b);
+int prepare_maxpool_i8(spvo_ctx *c, unsigned i);   // a stand-alone max-pool of an INT8 engine in the int8_general mode: its refusals, and Op::pool_m
 // the tail as one launch where it is the plain one (tail_is_plain + the kind's own terms): FP32 and FP16 / INT8 engines.  rp, rd: convPb's, convDb's records
 int fuse_tail_f32(spvo_ctx *c, const float *payload, const EngineOp &rp, const EngineOp &rd);
 int fuse_tail_i8(spvo_ctx *c, const float *payload, const EngineOp &rp, const EngineOp &rd);
@@ -835,6 +838,7 @@ int launch_conv8(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t str
 int launch_heads8(spvo_ctx *c, int batch, hipStream_t stream);   // spvo_net_i8.hip: the fused tail of an INT8 engine (heads_i8.hip.h)
 void plan_int8_fusion(spvo_ctx *c);   // spvo_net_i8.hip: marks the MobileNet blocks (and the stem) of a loaded INT8 plan that run as one launch
 int launch_maxpool_f16(spvo_ctx *c, const Tensor &ti, const Tensor &to, const float *tin, float *tout, int batch, hipStream_t stream);
+int launch_maxpool_i8(spvo_ctx *c, const Op &op, const Tensor &ti, const Tensor &to, const float *tin, float *tout, int batch, hipStream_t stream);   // spvo_net_i8.hip: maxpool2_i8_kernel (conv_i8.hip.h)
 void launch_unpad_c8(const Tensor &t, int batch, float *dst, hipStream_t stream);    // spvo_debug_tensor
 void launch_unpad_s3(const Tensor &t, int batch, float *dst, hipStream_t stream);
 void launch_unpad_c16(const Tensor &t, int batch, float *dst, hipStream_t stream);

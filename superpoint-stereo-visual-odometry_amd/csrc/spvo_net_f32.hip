@@ -291,6 +291,8 @@ int launch_op(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t stream
   ScopedStage st(c, op.stage, 0, batch * ((double)ti.ch * ti.H * ti.W * tsz(ti) + (double)to.ch * to.H * to.W * tsz(to)), stream);
   if (op.type == OP_MAXPOOL && ti.f16) {
     return launch_maxpool_f16(c, ti, to, tin, tout, batch, stream);
+  } else if (op.type == OP_MAXPOOL && ti.i8) {
+    return launch_maxpool_i8(c, op, ti, to, tin, tout, batch, stream);
   } else if (op.type == OP_MAXPOOL) {
     dim3 grid((to.W + 63) / 64, (to.H + 3) / 4, batch * to.ch);
     hipLaunchKernelGGL(maxpool2_kernel<>, grid, dim3(256), 0, stream, tin, tout, to.ch, to.H, to.W, ti.hp, ti.wp, to.hp, to.wp);

@@ -42,7 +42,9 @@ int prepare_conv_i8(spvo_ctx *c, unsigned i, const float *w, const float *b) {
     return upload_stem(c, op, w, b);
   }
   const int ckg = (op.ks == 3 || op.cin % 64) ? 2 : 4;   // 32 channels per chunk; 64 for 1x1 layers when they divide
-  if (op.cin % (16 * ckg) || op.in_c_off % 16) return fail(c, SPVO_ERR_IO, "op %u: cin %d / channel offset %d do not fit the INT8 chunking (%d)", i, op.cin, op.in_c_off, 16 * ckg);
+  // (int8_general: whole groups suffice -- cin 16, 48, ... end in a chunk of one group, conv_i8.hip.h ODD)
+  const int fit = c->int8_general_req ? 16 : 16 * ckg;
+  if (op.cin % fit || op.in_c_off % 16) return fail(c, SPVO_ERR_IO, "op %u: cin %d / channel offset %d do not fit the INT8 chunking (%d)", i, op.cin, op.in_c_off, fit);
   if (to.i8 && ((op.cout % 16) || (op.out_c_off % 16))) return fail(c, SPVO_ERR_IO, "op %u: cout %d / channel offset %d are not multiples of 16", i, op.cout, op.out_c_off);
   if (!to.i8 && (pool || bn || add)) return fail(c, SPVO_ERR_IO, "op %u: pooled / BatchNorm / residual layer with an fp32 output", i);
   if (add) {
@@ -51,7 +53,7 @@ int prepare_conv_i8(spvo_ctx *c, unsigned i, const float *w, const float *b) {
     op.s_res = tr.scale;
   }
   op.ck = 16 * ckg;
-  op.n_chunks = op.cin / op.ck;
+  op.n_chunks = (op.cin + op.ck - 1) / op.ck;
   choose_variant(c, op, ti);
   std::vector<int8_t> wq;
   std::vector<float> ws;
@@ -64,6 +66,21 @@ int prepare_conv_i8(spvo_ctx *c, unsigned i, const float *w, const float *b) {
   int rc = upload(c, &op.d_w8, pack_conv_weights_i8(wq.data(), op.cout, op.cin, op.ks, ckg));
   if (rc || (rc = upload(c, &op.d_qm, qm))) return rc;
   return upload(c, &op.d_b, bp);
+}
+
+// ... of a stand-alone 2x2/2 max-pool (int8_general; maxpool2_i8_kernel): nothing to upload, the kernel's multiplier is kept in the op
+int prepare_maxpool_i8(spvo_ctx *c, unsigned i) {
+  Op &op = c->ops[i];
+  const Tensor &ti = c->tensors[op.in], &to = c->tensors[op.out];
+  if (!ti.i8 || !to.i8) return fail(c, SPVO_ERR_IO, "op %u: max-pool of an INT8 engine between tensors that are not both int8", i);
+  if (to.ch != ti.ch) return fail(c, SPVO_ERR_IO, "op %u: max-pool from %d to %d channels", i, ti.ch, to.ch);
+  if (to.level != ti.level + 1) return fail(c, SPVO_ERR_IO, "op %u: level mismatch", i);
+  // (defensive: a network's size is a multiple of 8 and a level is at most 3 -- engine_file.h --, so behind the level check every map a pool
+  // reads is even; no engine file reaches this text and no test covers it)
+  if ((ti.H | ti.W) & 1) return fail(c, SPVO_ERR_IO, "op %u: pooling an odd-sized map", i);
+  const float inv = 1.f / to.scale;
+  op.pool_m = ti.scale * inv;
+  return SPVO_OK;
 }
 
 // The tail as ONE launch of heads_i8_kernel (heads_i8.hip.h; launch_heads8 below) -- int8 C16 activations of both branches in, fp32 detector
@@ -87,21 +104,21 @@ int fuse_tail_i8(spvo_ctx *c, const float *payload, const EngineOp &rp, const En
   return SPVO_OK;
 }
 
-template <int KS, int CKG, int WR, int WC, bool POOL, bool RELU, bool OUT_F32, int EPI = 0>
+template <int KS, int CKG, int WR, int WC, bool POOL, bool RELU, bool OUT_F32, int EPI = 0, bool ODD = false>
 int launch_conv8_instance(spvo_ctx *c, const ConvArgs8 &args, hipStream_t stream) {
-  return launch_persistent_tiles<ConvTile8<KS, CKG, WR, WC>, conv_i8_kernel<KS, CKG, WR, WC, POOL, RELU, OUT_F32, EPI>>(c, args, stream);
+  return launch_persistent_tiles<ConvTile8<KS, CKG, WR, WC>, conv_i8_kernel<KS, CKG, WR, WC, POOL, RELU, OUT_F32, EPI, ODD>>(c, args, stream);
 }
 
-template <int KS, int CKG, int WR, int WC, bool POOL>
+template <int KS, int CKG, int WR, int WC, bool POOL, bool ODD = false>
 int launch_conv8_variant(spvo_ctx *c, const ConvArgs8 &a, bool relu, bool out_f32, int epi, hipStream_t stream) {
   if constexpr (KS == 1) {
-    if (epi == 1) return launch_conv8_instance<1, CKG, WR, WC, POOL, true, false, 1>(c, a, stream);
-    if (epi == 2) return launch_conv8_instance<1, CKG, WR, WC, POOL, false, false, 2>(c, a, stream);
+    if (epi == 1) return launch_conv8_instance<1, CKG, WR, WC, POOL, true, false, 1, ODD>(c, a, stream);
+    if (epi == 2) return launch_conv8_instance<1, CKG, WR, WC, POOL, false, false, 2, ODD>(c, a, stream);
   }
   if constexpr (!POOL) {
-    if (out_f32) return relu ? launch_conv8_instance<KS, CKG, WR, WC, false, true, true>(c, a, stream) : launch_conv8_instance<KS, CKG, WR, WC, false, false, true>(c, a, stream);
+    if (out_f32) return relu ? launch_conv8_instance<KS, CKG, WR, WC, false, true, true, 0, ODD>(c, a, stream) : launch_conv8_instance<KS, CKG, WR, WC, false, false, true, 0, ODD>(c, a, stream);
   }
-  return relu ? launch_conv8_instance<KS, CKG, WR, WC, POOL, true, false>(c, a, stream) : launch_conv8_instance<KS, CKG, WR, WC, POOL, false, false>(c, a, stream);
+  return relu ? launch_conv8_instance<KS, CKG, WR, WC, POOL, true, false, 0, ODD>(c, a, stream) : launch_conv8_instance<KS, CKG, WR, WC, POOL, false, false, 0, ODD>(c, a, stream);
 }
 
 // ---------------------------------------------------------------- MobileNet blocks as one launch (conv_i8_fused.hip.h)
@@ -227,12 +244,16 @@ int launch_conv8(spvo_ctx *c, const Op &op, int img0, int batch, hipStream_t str
   a.cout = op.cout; a.n_chunks = op.n_chunks; a.co_tiles = op.co_tiles;
   a.tiles_x = a.tiles_y = 0;
   a.batch = batch;
+  a.in_groups = op.cin / 16;
   const int epi = (op.flags & FLAG_BN) ? 1 : (op.flags & FLAG_ADD) ? 2 : 0;
   if (epi == 2) a.residual = (const int8_t *)ring_ptr(c, c->tensors[op.residual], img0);
   const bool out_f32 = !to.i8;
   const int key = op.ks * 10000 + (op.ck / 16) * 1000 + op.wr * 100 + op.wc * 10 + (pool ? 1 : 0);   // ks, groups per chunk, wr, wc, pool: for the error text only (the table is with_tile_variant)
   return with_tile_variant<2, 4, 2>(op.ks, op.ck / 16, op.wr, op.wc, pool, [&](auto v) {
     using V = decltype(v);
+    if constexpr (V::CKG == 2) {   // an odd number of 16-channel groups (int8_general): the instances whose last chunk has one group
+      if (a.in_groups & 1) return launch_conv8_variant<V::KS, 2, V::WR, V::WC, V::POOL, true>(c, a, relu, out_f32, epi, stream);
+    }
     return launch_conv8_variant<V::KS, V::CKG, V::WR, V::WC, V::POOL>(c, a, relu, out_f32, epi, stream);
   }, [&] { return fail(c, SPVO_ERR_INVALID, "no int8 conv kernel variant for key %d", key); });
 }
@@ -256,6 +277,13 @@ int launch_heads8(spvo_ctx *c, int batch, hipStream_t stream) {
   const int ntiles = (batch * ti.H * ti.W + 31) / 32;
   c->heads_kind = 3; c->heads_tiles = c->heads_wgs = ntiles;   // (spvo_profile_stage_fused)
   hipLaunchKernelGGL(heads_i8_kernel<>, dim3(ntiles), dim3(HEADS8_THREADS), 0, stream, a);
+  HIP_TRY(c, hipGetLastError());
+  return SPVO_OK;
+}
+
+int launch_maxpool_i8(spvo_ctx *c, const Op &op, const Tensor &ti, const Tensor &to, const float *tin, float *tout, int batch, hipStream_t stream) {
+  dim3 grid((to.W + 63) / 64, (to.H + 3) / 4, batch * (to.ch / 16));
+  hipLaunchKernelGGL(maxpool2_i8_kernel<>, grid, dim3(256), 0, stream, (const int8_t *)tin, (int8_t *)tout, op.pool_m, to.H, to.W, ti.hp, ti.wp, to.hp, to.wp);
   HIP_TRY(c, hipGetLastError());
   return SPVO_OK;
 }

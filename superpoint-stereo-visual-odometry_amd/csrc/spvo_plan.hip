@@ -128,7 +128,7 @@ int assign_storage(spvo_ctx *c, const EngineFile &f, const char *path) {
     c->tensors[c->t_input].i8 = c->tensors[c->t_det].i8 = c->tensors[c->t_desc].i8 = false;   // fp32 bindings
     for (const auto &op : c->ops) {
       if (op.type == OP_L2NORM) c->tensors[op.in].i8 = false;
-      if (op.type == OP_MAXPOOL) return fail(c, SPVO_ERR_IO, "%s: INT8 engines have no stand-alone max-pool (squeeze graph)", path);
+      if (op.type == OP_MAXPOOL && !c->int8_general_req) return fail(c, SPVO_ERR_IO, "%s: INT8 engines have no stand-alone max-pool (squeeze graph)", path);
     }
   }
   if (c->fp16) {
@@ -290,6 +290,7 @@ int prepare_ops(spvo_ctx *c, const EngineFile &f) {
     int rc = SPVO_OK;
     if (op.type == OP_DWCONV) rc = prepare_dwconv(c, f, i);
     else if (op.type == OP_CONV && !op.merged) rc = prepare_conv(c, f, i);
+    else if (op.type == OP_MAXPOOL && c->int8) rc = prepare_maxpool_i8(c, i);   // (reached in the int8_general mode only: assign_storage)
     else if (op.type == OP_MAXPOOL && (to.level != ti.level + 1 || to.ch != ti.ch)) rc = fail(c, SPVO_ERR_IO, "op %u: bad pool", i);
     else if (op.type == OP_L2NORM && (ti.ch != 256 || to.ch != 256 || ti.level != 3)) rc = fail(c, SPVO_ERR_IO, "op %u: descriptor tail must be 256 channels at 1/8", i);
     if (rc) return rc;

@@ -95,7 +95,7 @@ OBS_DTYPE = np.dtype([("X", np.float32, 3), ("uv", np.float32, 2), ("cam", np.in
 
 # every symbol include/spvo.h declares
 SYMBOLS = [
-    "spvo_default_config", "spvo_create", "spvo_destroy", "spvo_last_error", "spvo_load_weights", "spvo_engine_precision", "spvo_set_fp32_split",
+    "spvo_default_config", "spvo_create", "spvo_destroy", "spvo_last_error", "spvo_load_weights", "spvo_engine_precision", "spvo_set_fp32_split", "spvo_set_int8_general",
     "spvo_preprocess", "spvo_forward", "spvo_debug_tensor", "spvo_heatmap", "spvo_nms",
     "spvo_sample_descriptors", "spvo_detect", "spvo_detect_dev", "spvo_detect_dev_submit", "spvo_detect_wait", "spvo_set_trunk_pairing", "spvo_detect_submit", "spvo_detect_collect", "spvo_detect_collect_mirrors", "spvo_detect_mirrors_wait", "spvo_match", "spvo_match_slots", "spvo_set_prematch", "spvo_set_match_fp8", "spvo_get_match_fp8", "spvo_match_last_form",
     "spvo_match_hamming", "spvo_default_classic_opts", "spvo_classic_detect", "spvo_classic_slot_rows", "spvo_match_hamming_slots", "spvo_orb_detect", "spvo_orb_tables", "spvo_gftt_detect", "spvo_gftt_last_rounds", "spvo_fast_detect", "spvo_orb_describe", "spvo_orb_describe_octaves", "spvo_brisk_describe", "spvo_brisk_tables", "spvo_brisk_detect", "spvo_brisk_detect_debug_layer", "spvo_brisk_detect_pair", "spvo_akaze_detect", "spvo_akaze_debug_level", "spvo_akaze_last_contrast", "spvo_akaze_tables", "spvo_akaze_describe", "spvo_akaze_detect_pair", "spvo_akaze_suppress_debug", "spvo_brisk_orb_pair", "spvo_akaze_orb_pair", "spvo_akaze_brisk_pair", "spvo_orb_octaves_link_debug", "spvo_sift_detect", "spvo_sift_debug_level", "spvo_sift_describe", "spvo_sift_detect_pair", "spvo_classic_sift_pair", "spvo_brisk_sift_pair", "spvo_akaze_sift_pair", "spvo_orb_brisk_pair", "spvo_orb_sift_pair", "spvo_sift_brisk_pair", "spvo_sift_records_debug", "spvo_sift_link_debug", "spvo_sift_slot_rows", "spvo_match_l2_slots", "spvo_sift_order_debug", "spvo_classic_slot_fill_debug", "spvo_match_l2", "spvo_match_l2_u8", "spvo_match_l2_u8_slots", "spvo_set_binary_prematch_norm", "spvo_triangulate", "spvo_pnp_ransac", "spvo_pnp_refine", "spvo_solve_stereo_odometry", "spvo_solve_submit", "spvo_solve_wait", "spvo_solve_wait_prior", "spvo_solve_pending", "spvo_stream", "spvo_synchronize",
@@ -125,6 +125,7 @@ def load() -> C.CDLL:
     lib.spvo_last_error.argtypes = [vp]
     lib.spvo_last_error.restype = C.c_char_p
     lib.spvo_load_weights.argtypes = [vp, C.c_char_p]
+    lib.spvo_set_int8_general.argtypes = [vp, C.c_int]
     lib.spvo_preprocess.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, dp, vp]
     lib.spvo_forward.argtypes = [vp, vp, C.c_int, vp, vp]
     lib.spvo_debug_tensor.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
@@ -375,6 +376,11 @@ class Context:
     def set_fp32_split(self, enable: bool):
         """FP32 engines loaded after this call evaluate their convolutions on the bf16x3 split kernels (include/spvo.h)."""
         self._check(self.lib.spvo_set_fp32_split(self.h, int(enable)))
+
+    def set_int8_general(self, enable: bool):
+        """INT8 engines loaded after this call may hold a stand-alone max-pool and convolutions whose cin is 16 more than a multiple
+        of 32: the squeeze graph (include/spvo.h).  Overrides the process-wide tuning "int8_general" for this context."""
+        self._check(self.lib.spvo_set_int8_general(self.h, int(enable)))
 
     def set_match_fp8(self, enable: bool):
         self._check(self.lib.spvo_set_match_fp8(self.h, int(enable)))

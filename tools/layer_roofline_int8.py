@@ -4,7 +4,8 @@ the library states for the launch (spvo_profile_*: element sizes of the engine's
 layers' operations and only the block's input and output tensors), and the roofline that bounds it: int8 MFMA dense peak 5000 TOP/s
 against HBM 8 TB/s (ridge 625 op/byte: every layer of this graph is HBM-bound).
 
-usage: python tools/layer_roofline_int8.py out.json [mbv1|mbv2|vgg] [HxW = 360x1176] [images per launch = 2]"""
+usage: python tools/layer_roofline_int8.py out.json [mbv1|mbv2|vgg|squeeze] [HxW = 360x1176] [images per launch = 2]
+(squeeze: loaded in the int8_general mode, spvo_set_int8_general -- its stand-alone pools are "pool:<op>" rows)"""
 import json, os, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "superpoint-stereo-visual-odometry_amd"))
@@ -21,7 +22,9 @@ plan = weights.vgg_plan() if graph == "vgg" else weights.load(os.path.join(ROOT,
 x = np.random.RandomState(0).rand(B, 1, H, Wd).astype(np.float32)
 plan.act_scales = quant.calibrate(plan, [x[:2]], H, Wd)
 p = os.path.join(tempfile.mkdtemp(), "w.spvw"); weights.save(plan, p, precision="INT8")
-ctx = capi.Context(net_height=H, net_width=Wd); ctx.load_weights(p)
+ctx = capi.Context(net_height=H, net_width=Wd)
+if graph == "squeeze": ctx.set_int8_general(True)
+ctx.load_weights(p)
 for _ in range(30): ctx.forward(x)
 ctx.profile_enable(True); ctx.profile_reset()
 for _ in range(200): ctx.forward(x)
